@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- path x permutation scores/sec of the MI355X path-join scorer.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config roofline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config roofline] [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the hot path (the ProcessPaths join sequence, reference src/wrapper.cpp:225-276:
 levels 1a, 1b, 2 .. path_length) over one synthetic problem whose inputs are already resident in HBM.
@@ -10,11 +10,16 @@ into N contiguous slices, each rank scores its slice, and the per-permutation nu
 the top-k tables (all-gather + merge) are exchanged over RCCL; inside a large join the ranks also share their running
 maxima (the pruning thresholds) a few times.  Workload: BASELINE configs[2] on one GPU; on several GPUs configs[3], the
 geometry BASELINE names for the 8-GPU run (same network, 10,000 patients, 100,000 permutations) -- `--config` overrides
-either.  "strong" scaling: the workload does not depend on N (results identical for every N; the line also carries the
-same workload timed on ONE of the GPUs, `one_gpu_same_workload`); `--scaling weak` runs the config's permutation count
+either.  "strong" scaling: the workload does not depend on N (results identical for every N; with `--full` the line also
+carries the same workload timed on ONE of the GPUs, `one_gpu_same_workload`); `--scaling weak` runs the config's permutation count
 PER GPU instead (K x N in total).
 
-Rank 0 prints ONE JSON line (see DESIGN.md "Measurement" for every field).
+Rank 0 prints ONE JSON line (see DESIGN.md "Measurement" for every field).  A plain run sets up, warms up, times the K
+steps and prints the headline (`value`, `ms_per_step`, the roofline accounting of the timed steps, `result_sha256`).
+`--full` adds everything else, each part measured by passes of its own after the timed steps: `steady_state`,
+`end_to_end`, `sensitivity`, `cpu_baseline`, `other_configs` and, for N > 1, `one_gpu_same_workload`.
+`--dump-outputs DIR` writes what the last timed step returned -- every level's top-k scores, ids, counts and null
+maxima -- as DIR/lst<level>_<field>.npy (float64; the null maxima float32); the inputs depend on the arguments only.
 """
 from __future__ import annotations
 
@@ -488,6 +493,24 @@ def other_configs(args, device, steps=2):
     return out
 
 
+def dump_outputs(out_dir, names, results, limit=64 << 20):
+    """Every level's result of one step as .npy files: scores (float64), src / trg / cases / ctrls (int32 ids and counts,
+    exact in float64) and the null maxima (float32) -- the JoinResult arrays a caller of ResidentPlan.run receives."""
+    arrays = {}
+    for name in names:
+        r = results[name]
+        arrays[f"lst{name}_scores"] = np.asarray(r.scores, dtype=np.float64)
+        for field in ("src", "trg", "cases", "ctrls"):
+            arrays[f"lst{name}_{field}"] = np.asarray(getattr(r, field)).astype(np.float64)
+        arrays[f"lst{name}_null"] = np.asarray(r.null, dtype=np.float32)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > limit:
+        raise SystemExit(f"--dump-outputs: {total} bytes of results exceed the {limit >> 20} MB limit")
+    os.makedirs(out_dir, exist_ok=True)
+    for key, a in arrays.items():
+        np.save(os.path.join(out_dir, key + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -507,7 +530,7 @@ def main():
                     help="N > 1: strong = the same workload for every N (K permutations in total), weak = K per GPU (K x N)")
     ap.add_argument("--no-end-to-end", action="store_true", help="skip the cold one-shot gcre_process_paths measurement")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-sensitivity", action="store_true", help="skip the 1 % / 2.5 % / 5 % carrier-rate passes")
+    ap.add_argument("--no-sensitivity", action="store_true", help="skip the 1 %% / 2.5 %% / 5 %% carrier-rate passes")
     ap.add_argument("--no-steady-state", action="store_true", help="skip the extra passes with kept inspections")
     ap.add_argument("--no-other-configs", action="store_true",
                     help="skip the passes over the other single-GPU configs (configs[1], [3], [4], method2) after the headline")
@@ -516,7 +539,14 @@ def main():
     ap.add_argument("--no-exchange", action="store_true", help="N > 1: ranks do not share their running maxima during a join")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="gloo + several ranks on one GPU is a rehearsal of the N > 1 path, not a measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what is not the headline (steady state, end to end, carrier-rate sensitivity, CPU "
+                         "baselines, the other configs, N > 1: the same workload on one GPU); the --no-* options leave parts out")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's results to DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -618,11 +648,13 @@ def main():
     total_scores = plan.total_scores()            # whole job, all ranks
     value = total_scores * args.steps / elapsed
     timed_prof = dict(prof_acc)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, plan.names, last)
 
     # Not part of `value`: the same pass with every join's mask-independent half (expansion, observed scores, top-k, kept
     # rows, lists) kept from the pass before -- what a service re-scoring one network against fresh permutations runs.
     steady = None
-    if not args.no_steady_state:
+    if args.full and not args.no_steady_state:
         def kept_step():
             return plan.run(rank, world, d_null_out=d_null.data_ptr(), on_level=on_level, keep_inspections=True, exchange=share)
         kept_step()                                # fills the cache
@@ -732,7 +764,7 @@ def main():
     }
     if steady is not None:
         line["steady_state"] = steady
-    if world > 1 and not args.no_one_gpu_reference:
+    if world > 1 and args.full and not args.no_one_gpu_reference:
         # the same workload on ONE of these GPUs (rank 0 alone, the others wait): what the N-GPU value is a speed-up of
         ref = None
         if rank == 0:
@@ -749,19 +781,20 @@ def main():
         dist.barrier()
         if ref is not None:
             line["one_gpu_same_workload"] = ref
-    if rank == 0 and world == 1 and not args.no_end_to_end and masks is not None:
+    if rank == 0 and world == 1 and args.full and not args.no_end_to_end and masks is not None:
         try:
             line["end_to_end"] = end_to_end(prob, masks, local_rank, total_scores)
         except Exception as e:   # reported, never required
             line["end_to_end"] = {"error": repr(e)}
-    if rank == 0 and world == 1 and not args.no_sensitivity and masks is not None and args.config == "roofline" and not args.carrier_rate:
+    if rank == 0 and world == 1 and args.full and not args.no_sensitivity and masks is not None and args.config == "roofline" and not args.carrier_rate:
         try:
             line["sensitivity"] = sensitivity(prob, masks, cfg, args.seed, local_rank)
         except Exception as e:   # reported, never required
             line["sensitivity"] = {"error": repr(e)}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and masks is None:
+    cpu_baseline_run = rank == 0 and world == 1 and args.full and not args.no_cpu_baseline
+    if cpu_baseline_run and masks is None:
         line["cpu_baseline"] = {"skipped": "device-drawn masks at this scale; the baseline is timed on configs[2]"}
-    elif rank == 0 and world == 1 and not args.no_cpu_baseline:
+    elif cpu_baseline_run:
         try:
             line["cpu_baseline"] = cpu_baseline(prob, masks)
             line["cpu_baseline"]["six_joins"] = six_join_baseline(cfg, args.seed, args.top_k, line["cpu_baseline"])
@@ -773,7 +806,7 @@ def main():
         lib = api.load_library()
         line["library"] = {"path": os.path.relpath(os.environ.get("GCRE_LIB") or api.lib_path(), ROOT),
                            "abi": int(lib.gcre_abi_version()), "build_flags": lib.gcre_build_flags().decode()}
-    if rank == 0 and world == 1 and default_run and args.config == "roofline" and not args.no_other_configs:
+    if rank == 0 and world == 1 and args.full and default_run and args.config == "roofline" and not args.no_other_configs:
         plan.close()          # the headline's sets and planes leave the device first
         line["other_configs"] = other_configs(args, local_rank)
     if rank == 0:

@@ -1,16 +1,17 @@
 #!/usr/bin/env python3
 """Generate tests/golden/ref_cases/*.{txt,json}: golden vectors from the PARTIAL reference build.
 
-Run in the build container only (needs /root/reference and g++):
+Needs the partial reference build (oracle/_ref/ref_driver, built by build() where the reference tree exists):
 
     make -C oracle/ref_partial && python tests/golden/make_ref_goldens.py [out_dir]
 
 (tests/test_oracle.py::test_committed_goldens_regenerate re-runs this into a temporary directory and compares the files
-byte for byte whenever the reference tree is present, so the fixtures cannot drift from their generator again.)
+byte for byte wherever the partial reference build exists -- elsewhere the inputs and case records only, with
+outputs=False -- so the fixtures cannot drift from their generator again.)
 
 oracle/_ref/ref_driver links the reference's own header-only scoring code (src/methods.h score_permute /
 merge_scores, src/gcre_paths.h PathSet, src/gcre.h need_flip, src/gcre_types.h Score) and its text-dump parser
-(test/test.cpp), compiled from /root/reference where they lie; the JoinExec members of src/join_base.cpp (which
+(test/test.cpp), compiled from the reference tree where they lie; the JoinExec members of src/join_base.cpp (which
 needs <Rcpp.h>) are the driver's own restatement -- see oracle/ref_partial/ref_driver.cpp.  The files written here
 are data only: the input dump of every case and the outputs the reference code printed for it.
 """
@@ -18,6 +19,7 @@ import json
 import os
 import subprocess
 import sys
+import tempfile
 
 import numpy as np
 
@@ -29,7 +31,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 from geneticscre_amd import api  # noqa: E402
 from geneticscre_amd.harness_io import problem_digest, write_problem, write_problem_bin  # noqa: E402
 from geneticscre_amd.synth import make_problem  # noqa: E402
-from helpers import SLOW_WIDE_CASES, WIDE_CASES, small_table, wide_problem  # noqa: E402
+from helpers import FUZZ_GOLDEN_CASES, SLOW_WIDE_CASES, WIDE_CASES, fuzz_problem, small_table, wide_problem  # noqa: E402
 
 DRIVER = os.path.join(ROOT, "oracle", "_ref", "ref_driver")
 OUT = os.path.join(HERE, "ref_cases")
@@ -46,8 +48,14 @@ CASES = [
 ]
 
 
-def main(out=OUT, wide=True, slow=True):
-    """slow=False leaves out the cases of SLOW_WIDE_CASES (minutes of reference time each); INDEX.json names them all."""
+def reference_run(args):
+    """The JSON the partial reference build prints for these arguments."""
+    return json.loads(subprocess.run([DRIVER] + args, check=True, capture_output=True, text=True).stdout)
+
+
+def main(out=OUT, wide=True, slow=True, outputs=True):
+    """slow=False leaves out the cases of SLOW_WIDE_CASES (minutes of reference time each); INDEX.json names them all.
+    outputs=False writes every file without running the reference: the input dumps, and JSON files holding only `_case`."""
     os.makedirs(out, exist_ok=True)
     index = []
     for name, method, genes, edges, nc, nt, rows, iters, length, top_k, seed, table in CASES:
@@ -58,8 +66,7 @@ def main(out=OUT, wide=True, slow=True):
         p.iterations = iters
         dump = os.path.join(out, name + ".txt")
         write_problem(dump, p)
-        res = json.loads(subprocess.run([DRIVER, dump, method, str(iters), str(top_k), str(length)], check=True,
-                                        capture_output=True, text=True).stdout)
+        res = reference_run([dump, method, str(iters), str(top_k), str(length)]) if outputs else {}
         res["_case"] = {"method": method, "iterations": iters, "top_k": top_k, "path_length": length,
                         "paths": {k: int(v) for k, v in p.levels.n_paths.items()}}
         with open(os.path.join(out, name + ".json"), "w") as f:
@@ -68,16 +75,17 @@ def main(out=OUT, wide=True, slow=True):
         print(name, os.path.getsize(dump), "B dump", {k: v for k, v in p.levels.n_paths.items()})
     wide_index = []
     if wide:
-        import tempfile
         for name, (method, genes, edges, nc, nt, perms, length, top_k, seed) in WIDE_CASES.items():
             wide_index.append(name)
             if name in SLOW_WIDE_CASES and not slow:
                 continue
             p = wide_problem(name)
-            with tempfile.TemporaryDirectory() as tmp:
-                blob = os.path.join(tmp, name + ".gcrebin")
-                write_problem_bin(blob, p)        # tens of MB: the inputs are regenerated from the seed, never committed
-                res = json.loads(subprocess.run([DRIVER, "--bin", blob], check=True, capture_output=True, text=True).stdout)
+            res = {}
+            if outputs:
+                with tempfile.TemporaryDirectory() as tmp:
+                    blob = os.path.join(tmp, name + ".gcrebin")
+                    write_problem_bin(blob, p)        # tens of MB: the inputs are regenerated from the seed, never committed
+                    res = reference_run(["--bin", blob])
             res["_case"] = {"method": method, "iterations": perms, "top_k": top_k, "path_length": length,
                             "generator": {"genes": genes, "edges": edges, "cases": nc, "ctrls": nt, "seed": seed,
                                           "table": "gcre_values_table",
@@ -88,8 +96,25 @@ def main(out=OUT, wide=True, slow=True):
             with open(os.path.join(out, name + ".json"), "w") as f:
                 json.dump(res, f, separators=(",", ":"))
             print(name, (nc + nt + 63) // 64, "words", {k: v for k, v in p.levels.n_paths.items()})
+    # the first cases of tests/test_oracle_fuzz.py: outputs committed, inputs redrawn from the case number (input_sha256)
+    fuzz_index = []
+    for case in range(FUZZ_GOLDEN_CASES):
+        name = f"fuzz{case}"
+        fuzz_index.append(name)
+        cfg, p = fuzz_problem(case)
+        res = {}
+        if outputs:
+            with tempfile.TemporaryDirectory() as tmp:
+                blob = os.path.join(tmp, name + ".gcrebin")
+                write_problem_bin(blob, p, nthreads=0)
+                res = reference_run(["--bin", blob])
+        res["_case"] = {"fuzz_case": case, "draw": cfg, "input_sha256": problem_digest(p)}
+        with open(os.path.join(out, name + ".json"), "w") as f:
+            json.dump(res, f, separators=(",", ":"))
+        print(name, cfg)
     with open(os.path.join(out, "INDEX.json"), "w") as f:
-        json.dump({"_provenance": __doc__.strip().splitlines()[0], "cases": index, "wide_cases": wide_index}, f, indent=1)
+        json.dump({"_provenance": __doc__.strip().splitlines()[0], "cases": index, "wide_cases": wide_index,
+                   "fuzz_cases": fuzz_index}, f, indent=1)
 
 
 if __name__ == "__main__":

@@ -90,6 +90,33 @@ def wide_problem(name: str) -> Problem:
     return _WIDE_PROBLEMS[name]
 
 
+# ---- goldens of the oracle fuzz (tests/golden/ref_cases/fuzz*.json) -------------------------------------------------
+# The first cases of tests/test_oracle_fuzz.py with the outputs the reference's own scoring code printed for them, so that
+# the default run compares against the reference without its source tree.  As for the wide goldens, only the outputs are
+# committed: the inputs are redrawn and their SHA-256 is checked against the one recorded with the golden.
+FUZZ_GOLDEN_CASES = 4
+
+
+def fuzz_problem(case: int):
+    """(cfg, Problem) of tests/test_oracle_fuzz.py case ``case``: the draw of tests/test_gpu_fuzz.py case 400000 + case,
+    cut to what the reference's inline mode runs in seconds."""
+    from test_gpu_fuzz import draw, value_table
+    cfg, _ = draw(400000 + case)
+    perms = max(1, min(cfg["perms"], 600))   # the reference's inline mode is one thread (K = 0 is a golden of its own)
+    if cfg["n_cases"] + cfg["n_ctrls"] > 3000:
+        perms = min(perms, 100)
+    cfg["perms"] = perms
+    if (cfg["n_cases"] + cfg["n_ctrls"]) % 64 == 0:
+        # PathSet::load asserts patients < 64 * width (src/gcre_paths.h:63).  The reference pads the width to its SIMD
+        # width (src/join_base.cpp:15-23), so it refuses cohorts of exactly k * gs_vec_width patients; the driver's width is
+        # ceil(n / 64) (the padding is layout only), so it refuses every multiple of 64: an error there, nothing to compare
+        cfg["n_ctrls"] += 1
+    p = make_problem(cfg["genes"], cfg["edges"], cfg["n_cases"], cfg["n_ctrls"], perms, cfg["length"], method=cfg["method"],
+                     top_k=cfg["top_k"], seed=cfg["seed"], threshold=cfg["threshold"],
+                     table=value_table(cfg["table"], cfg["n_cases"], cfg["n_ctrls"], cfg["seed"]))
+    return cfg, p
+
+
 def load_wide_case(name: str):
     """(Problem, expected dict) of a wide golden; fails if the regenerated inputs are not the ones the golden was cut from."""
     import json

@@ -1,7 +1,8 @@
-"""The oracle against the reference's own scoring code on seeded random problems (CPU; build container only: it needs
-oracle/_ref/ref_driver, the partial build of /root/reference's src/methods.h + src/gcre_paths.h).  Same draw as
+"""The oracle against the reference's own scoring code on seeded random problems (CPU).  Same draw as
 tests/test_gpu_fuzz.py; compared per level: every score (bit pattern), the ids in the reference's heap order, the counts, every f32 null
-maximum and the hash of the kept path rows, as `ref_driver --bin` prints them.  A handful of cases by default, GCRE_FUZZ_CASES=300 for a long run."""
+maximum and the hash of the kept path rows, as `ref_driver --bin` prints them.  The first FUZZ_GOLDEN_CASES cases compare
+against those outputs committed under tests/golden/ref_cases/ (tests/golden/make_ref_goldens.py); later ones
+(GCRE_FUZZ_CASES=300 for a long run) need oracle/_ref/ref_driver, the partial reference build."""
 import json
 import os
 import subprocess
@@ -10,38 +11,37 @@ import numpy as np
 import pytest
 
 import oracle
-from geneticscre_amd.harness_io import write_problem_bin
-from geneticscre_amd.synth import make_problem
-from helpers import fnv_rows
+from geneticscre_amd.harness_io import problem_digest, write_problem_bin
+from helpers import FUZZ_GOLDEN_CASES, fnv_rows, fuzz_problem
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BINARY = os.path.join(ROOT, "oracle", "_ref", "ref_driver")
+GOLDEN = os.path.join(ROOT, "tests", "golden", "ref_cases")
 N_CASES = min(int(os.environ.get("GCRE_FUZZ_CASES", "4")), 2000)
 
-pytestmark = pytest.mark.skipif(not (os.path.isdir("/root/reference/src") and os.path.exists(BINARY)),
-                                reason="needs the reference tree and the partial reference build (build container only)")
 
-
-@pytest.mark.parametrize("case", range(N_CASES))
-def test_oracle_matches_reference_code_on_random_problems(case, tmp_path):
-    from test_gpu_fuzz import draw, value_table
-    cfg, _ = draw(400000 + case)
-    perms = max(1, min(cfg["perms"], 600))   # the reference's inline mode is one thread (K = 0 is a golden of its own)
-    if cfg["n_cases"] + cfg["n_ctrls"] > 3000:
-        perms = min(perms, 100)
-    if (cfg["n_cases"] + cfg["n_ctrls"]) % 64 == 0:
-        # PathSet::load asserts patients < 64 * width (src/gcre_paths.h:63).  The reference pads the width to its SIMD
-        # width (src/join_base.cpp:15-23), so it refuses cohorts of exactly k * gs_vec_width patients; the driver's width is
-        # ceil(n / 64) (the padding is layout only), so it refuses every multiple of 64: an error there, nothing to compare
-        cfg["n_ctrls"] += 1
-    p = make_problem(cfg["genes"], cfg["edges"], cfg["n_cases"], cfg["n_ctrls"], perms, cfg["length"], method=cfg["method"],
-                     top_k=cfg["top_k"], seed=cfg["seed"], threshold=cfg["threshold"],
-                     table=value_table(cfg["table"], cfg["n_cases"], cfg["n_ctrls"], cfg["seed"]))
+def reference_outputs(case, cfg, p, tmp_path):
+    """What the reference's scoring code printed for this case: the committed golden when it was cut from this very draw
+    (GCRE_FUZZ_LIGHT changes some draws), else a run of the partial reference build."""
+    path = os.path.join(GOLDEN, f"fuzz{case}.json")
+    if case < FUZZ_GOLDEN_CASES:
+        ref = json.load(open(path))
+        if ref["_case"]["draw"] == cfg:
+            assert problem_digest(p) == ref["_case"]["input_sha256"], f"fuzz{case}: the generator no longer reproduces the golden's inputs"
+            return ref
+    if not os.path.exists(BINARY):
+        pytest.skip("no committed golden for this draw and no partial reference build (oracle/_ref/ref_driver)")
     dump = str(tmp_path / "case.gcrebin")
     write_problem_bin(dump, p, nthreads=0)
     r = subprocess.run([BINARY, "--bin", dump], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-400:]
-    ref = json.loads(r.stdout)
+    return json.loads(r.stdout)
+
+
+@pytest.mark.parametrize("case", range(N_CASES))
+def test_oracle_matches_reference_code_on_random_problems(case, tmp_path):
+    cfg, p = fuzz_problem(case)
+    ref = reference_outputs(case, cfg, p, tmp_path)
     got = oracle.process_paths(p, order="reference", nthreads=0)
     for lvl in range(1, cfg["length"] + 1):
         e, g = ref[f"lst{lvl}"], got[f"lst{lvl}"]
