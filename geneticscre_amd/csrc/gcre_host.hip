@@ -96,6 +96,17 @@ struct Winners {
   uint32_t n = 0;
 };
 
+// The buffers a chunk's inspector writes and its permutation kernel and top-k selection read: the context's scratch, or
+// (inspection cache on) a chunk entry's own
+struct ChunkBufs {
+  DevBuf<uint32_t> row0, row1, tot, cases, ctrls, dcnt, dlist, rowz, linfo, lover, dover;
+  DevBuf<uint64_t> key;
+  void release() {
+    for (auto* b : {&row0, &row1, &tot, &cases, &ctrls, &dcnt, &dlist, &rowz, &linfo, &lover, &dover}) b->release();
+    key.release();
+  }
+};
+
 // What the inspector of one chunk of a join left behind -- expanded row numbers, statistics, score keys, lists, flags
 // and the chunk's top-k winners.  None of it depends on the permutation masks: with the inspection cache on
 // (gcre_set_inspect_cache) the buffers belong to the join index instead of the context's scratch, and the next
@@ -108,13 +119,11 @@ struct ChunkInsp {
   bool in_recipe = false;     // ... into the kept set's recipe (not into the buffers below)
   bool flags_valid = false;   // host copy of the inspector's flag block
   bool win_valid = false;     // top-k winners
-  uint32_t flags[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  uint32_t flags[kFlagWords] = {};
   Winners win;
-  DevBuf<uint32_t> row0, row1, tot, cases, ctrls, dcnt, dlist, rowz, linfo, lover, dover;
-  DevBuf<uint64_t> key;
+  ChunkBufs bufs;
   void release() {
-    for (auto* b : {&row0, &row1, &tot, &cases, &ctrls, &dcnt, &dlist, &rowz, &linfo, &lover, &dover}) b->release();
-    key.release();
+    bufs.release();
     inspected = with_lists = flags_valid = win_valid = false;
   }
 };
@@ -326,6 +335,7 @@ struct gcre_ctx {
   bool have_table = false, have_perms = false;
   int64_t chunk_paths = int64_t(1) << 25;
   int null_blocks_per_cu = 12;
+  int cus = 256;                     // compute units of the device (read once at gcre_create)
 
   // resident inputs
   uint64_t* d_case_mask = nullptr;   // [Wp]
@@ -343,8 +353,7 @@ struct gcre_ctx {
   int ie_small_join_tiles = 8;       // GCRE_IE_SJT (tuning)
   int ie_batch = 2;                  // segments per ticket (GCRE_IE_BATCH)
   uint32_t* d_queue = nullptr;       // ticket counters of the pruned kernels' work queues (8 x 16 words)
-  uint32_t* d_max_tot = nullptr;     // 8 words: largest carrier total of the chunk, "reduced operand is wrong", overlap lists,
-                                     // looked-up tiles, entries reserved in the long-list area
+  uint32_t* d_max_tot = nullptr;     // the flag block of the inspectors (FlagWord, gcre_kernels.h)
   uint32_t* d_ladder = nullptr;      // method 1: pruning ladder of the null table [kLadderLevels][TD]
   uint32_t g00_rows = 0xffffffffu;   // method 2: vtmax[0][0] in ladder rows, rounded up (IeArgs::g00_rows)
   int null_kernel = 0;               // 0 auto, 1 dense, 2 sparse, 3 ie (GCRE_NULL_KERNEL)
@@ -366,10 +375,11 @@ struct gcre_ctx {
                            // gigabytes of planes for one window: 120-460 ms on a fresh context)
 
   // per-join scratch
-  DevBuf<uint32_t> d_row0, d_row1, d_tot, d_cases, d_ctrls, d_sel, d_small, d_chunk, d_rec_segs;
-  DevBuf<uint64_t> d_key, d_wkey, d_doff, d_scan, d_excess, d_excess_b;
-  DevBuf<uint32_t> d_dcnt, d_dlist, d_rowz, d_linfo, d_lover, d_dover;
+  ChunkBufs scratch;                 // a chunk's buffers when the inspection cache is off
+  DevBuf<uint32_t> d_sel, d_small, d_chunk, d_rec_segs;
+  DevBuf<uint64_t> d_wkey, d_doff, d_scan, d_excess, d_excess_b;
   DevBuf<uint32_t> d_wcases, d_wctrls, d_wrow0, d_wrow1;
+  DevBuf<uint64_t> d_ie_timing;      // GCRE_IE_TIMING: the section counters of a diagnostics build's pruned kernels
 
   // count-plane buffers of freed path sets, kept for the next set that needs one (hipMalloc of tens of GB costs
   // ~40 ms per GB on this platform, hipFree nothing)
@@ -384,32 +394,6 @@ struct gcre_ctx {
   gcre_profile prof{};
   std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_null, ev_stats;
   std::vector<hipEvent_t> ev_pool;
-};
-
-// The context's per-join scratch and a chunk's cached buffers trade places while the chunk is worked on: every kernel
-// argument keeps naming c->d_*; what the inspector writes ends up owned by the join index.
-struct InspSwap {
-  gcre_ctx* c;
-  ChunkInsp* e;
-  InspSwap(gcre_ctx* c_, ChunkInsp* e_) : c(c_), e(e_) { swap(); }
-  ~InspSwap() { swap(); }
-  InspSwap(const InspSwap&) = delete;
-  InspSwap& operator=(const InspSwap&) = delete;
-  void swap() {
-    if (!e) return;
-    std::swap(c->d_row0, e->row0);
-    std::swap(c->d_row1, e->row1);
-    std::swap(c->d_tot, e->tot);
-    std::swap(c->d_cases, e->cases);
-    std::swap(c->d_ctrls, e->ctrls);
-    std::swap(c->d_key, e->key);
-    std::swap(c->d_dcnt, e->dcnt);
-    std::swap(c->d_dlist, e->dlist);
-    std::swap(c->d_rowz, e->rowz);
-    std::swap(c->d_linfo, e->linfo);
-    std::swap(c->d_lover, e->lover);
-    std::swap(c->d_dover, e->dover);
-  }
 };
 
 // How a kept path set was made: row r = row row0[r] of set A | row rowz[r] of set Z, with the producing
@@ -1059,25 +1043,26 @@ int ensure_quads(gcre_ctx* c, const gcre_uids& u, gcre_uids::SegCache& sc, int64
 }
 
 // ---- top-k selection of one scored chunk: indices of the best min(k, valid) keys, ties cut in index order ----
+// `key` = the keys of the scored paths (a chunk's key buffer + its first scored path): the indices are relative to it.
 // Two halves, so that a caller with a read-back of its own (the inspector's flags) can fold the state's into it:
 // select_begin queues the eight digit passes (one read-back of the state they leave, gcre_kernels.hip) and the copy
 // of that state into *hs; select_finish -- after a stream synchronisation -- queues the collection of the winners.
-int select_begin(gcre_ctx* c, int64_t first, int64_t count, int k, SelectState* hs, hipStream_t sst) {
+int select_begin(gcre_ctx* c, const uint64_t* key, int64_t count, int k, SelectState* hs, hipStream_t sst) {
   *hs = SelectState{};
   if (count == 0 || k <= 0) return GCRE_OK;
   HIP_TRY(c, c->d_small.reserve(512));
   HIP_TRY(c, c->d_sel.reserve((size_t)k + 64));
   SelectState* d_state = (SelectState*)(c->d_small.p + 264);
-  HIP_TRY(c, launch_radix_select(c->d_key.p + first, count, std::min<int64_t>(k, count), c->d_small.p, d_state, sst));
+  HIP_TRY(c, launch_radix_select(key, count, std::min<int64_t>(k, count), c->d_small.p, d_state, sst));
   HIP_TRY(c, hipMemcpyAsync(hs, d_state, sizeof *hs, hipMemcpyDeviceToHost, sst));
   return GCRE_OK;
 }
 
-int select_finish(gcre_ctx* c, int64_t first, int64_t count, int k, const SelectState& hs, uint32_t* n_selected, hipStream_t sst) {
+int select_finish(gcre_ctx* c, const uint64_t* key, int64_t count, int k, const SelectState& hs, uint32_t* n_selected,
+                  hipStream_t sst) {
   *n_selected = 0;
   if (count == 0 || k <= 0) return GCRE_OK;
   uint32_t* d_counter = c->d_small.p + 256;
-  const uint64_t* key = c->d_key.p + first;   // selected indices are relative to `first`
   const uint64_t prefix = hs.prefix;
   const int64_t need = hs.need, greater = hs.greater;
   const uint32_t eq_count = hs.eq_count;
@@ -1116,11 +1101,11 @@ int select_finish(gcre_ctx* c, int64_t first, int64_t count, int k, const Select
   return GCRE_OK;
 }
 
-int select_chunk(gcre_ctx* c, int64_t first, int64_t count, int k, uint32_t* n_selected, hipStream_t sst) {
+int select_chunk(gcre_ctx* c, const uint64_t* key, int64_t count, int k, uint32_t* n_selected, hipStream_t sst) {
   SelectState hs{};
-  if (int rc = select_begin(c, first, count, k, &hs, sst)) return rc;
+  if (int rc = select_begin(c, key, count, k, &hs, sst)) return rc;
   HIP_TRY(c, hipStreamSynchronize(sst));
-  return select_finish(c, first, count, k, hs, n_selected, sst);
+  return select_finish(c, key, count, k, hs, n_selected, sst);
 }
 
 struct JoinPlan {
@@ -1340,41 +1325,6 @@ void merge_candidates(std::vector<Candidate>& cands, int top_k, gcre_result* out
   }
 }
 
-// The tail of a join whose kernels were launched ahead (run_join, kLaunch): wait for them, copy the maxima out of the join
-// index's own array, merge the winners its inspection cached.
-int finish_launched(gcre_ctx* c, const JoinPlan& jp, gcre_result* out) {
-  const auto t_begin = std::chrono::steady_clock::now();
-  const gcre_uids& u = *jp.u;
-  gcre_uids::Launched& L = u.launch;
-  const int K = c->win_K;
-  const int Kpad = ((K + kPermTileMax - 1) / kPermTileMax) * kPermTileMax;
-  HIP_TRY(c, hipEventSynchronize(L.done));
-  L.active = false;
-  out->n_perm = K;
-  out->null_max = (float*)std::calloc((size_t)std::max(K, 1), sizeof(float));
-  uint32_t lookups = 0;
-  if (K > 0) {
-    // (on the inspection stream, idle by now: the main stream holds the later levels' kernels, which this join's caller
-    // need not wait for)
-    hipStream_t cs = c->insp_stream;
-    HIP_TRY(c, hipMemcpyAsync(out->null_max, L.d_null.p, (size_t)K * 4, hipMemcpyDeviceToHost, cs));
-    HIP_TRY(c, hipMemcpyAsync(&lookups, L.d_null.p + Kpad, 4, hipMemcpyDeviceToHost, cs));
-    if (jp.d_null_out) HIP_TRY(c, hipMemcpyAsync(jp.d_null_out, L.d_null.p, (size_t)K * 4, hipMemcpyDeviceToDevice, cs));
-    HIP_TRY(c, hipStreamSynchronize(cs));
-  }
-  std::vector<Candidate> cands = std::move(L.cands);
-  L.cands.clear();
-  merge_candidates(cands, c->top_k, out);
-  c->prof = L.prof;
-  L.prof = gcre_profile{};
-  c->prof.null_kernel_ms = drain_events(c, L.ev_null);
-  c->prof.stats_kernel_ms = drain_events(c, L.ev_stats);
-  c->prof.ie_lookup_tiles += lookups;
-  c->prof.scores = c->prof.paths * (int64_t)K;
-  c->prof.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
-  return GCRE_OK;
-}
-
 // inspect_only (gcre_join_ahead): the mask-independent half of the join -- expansion, inspector, kept rows, recipe, flags, top-k
 // winners -- on the inspection stream, into the join index's inspection cache; nothing of the permutation kernel's (no maxima,
 // no count planes, no results).  The join proper then replays it and starts at its null kernel.
@@ -1383,45 +1333,355 @@ int finish_launched(gcre_ctx* c, const JoinPlan& jp, gcre_result* out) {
 // it launched and only finishes it (wait, copy the maxima, merge the cached winners).
 enum JoinMode { kFull = 0, kInspect = 1, kLaunch = 2 };
 
-int run_join(gcre_ctx* c, const JoinPlan& jp, gcre_result* out, JoinMode mode = kFull) {
-  const bool inspect_only = mode == kInspect, launch_only = mode == kLaunch;
-  // the join sees the permutation window (all permutations unless gcre_set_perm_window narrowed it): K, the slice of
-  // the transposed masks, of the masks (row stride stays the full Kpad) and of the maxima
-  Geometry g = c->g;
+using EvList = std::vector<std::pair<hipEvent_t, hipEvent_t>>;
+
+int run_join(gcre_ctx* c, const JoinPlan& jp, gcre_result* out, JoinMode mode = kFull);
+
+// The chain of gcre_join_ahead: once a join's own work is queued, every registered later join is inspected (on the
+// inspection stream) and launched (on the main stream) in turn -- the big inspector of the last level then runs beside the
+// small permutation kernels of the levels before it instead of after them
+int run_chain(gcre_ctx* c, const std::vector<JoinPlan>& chain) {
+  for (const JoinPlan& a : chain) {
+    if (int rc = run_join(c, a, nullptr, kInspect)) return rc;
+    if (int rc = run_join(c, a, nullptr, kLaunch)) return rc;
+    // a join that was not launched (its inspection did not validate: a broken hint) has not written what the joins
+    // behind it read: they run whole, in their own calls
+    if (!a.u->launch.active) break;
+  }
+  return GCRE_OK;
+}
+
+// The end of every join that returns a result (run_join's own, and one launched ahead): the first K maxima of `d_null` go
+// out (methods.h:101-102; format_result, join_base.cpp:144-146) on `cs`; the registered chain, if any, is queued behind
+// those copies and only they are waited for; then the candidates are merged and the context's profile gets the times of the
+// events the join booked
+int deliver_join(gcre_ctx* c, const JoinPlan& jp, gcre_result* out, int K, const uint32_t* d_null, hipStream_t cs,
+                 std::vector<Candidate>& cands, EvList& ev_null, EvList& ev_stats,
+                 std::chrono::steady_clock::time_point t_begin, std::unique_ptr<std::vector<JoinPlan>> chain) {
+  out->n_perm = K;
+  out->null_max = (float*)std::calloc((size_t)std::max(K, 1), sizeof(float));
+  if (K > 0) {
+    HIP_TRY(c, hipMemcpyAsync(out->null_max, d_null, (size_t)K * 4, hipMemcpyDeviceToHost, cs));
+    if (jp.d_null_out) HIP_TRY(c, hipMemcpyAsync(jp.d_null_out, d_null, (size_t)K * 4, hipMemcpyDeviceToDevice, cs));
+  }
+  if (chain) {
+    HIP_TRY(c, hipEventRecord(c->ev_tail, cs));
+    if (int rc = run_chain(c, *chain)) return rc;
+    HIP_TRY(c, hipEventSynchronize(c->ev_tail));
+  } else {
+    HIP_TRY(c, hipStreamSynchronize(cs));
+  }
+  merge_candidates(cands, c->top_k, out);
+  c->prof.null_kernel_ms = drain_events(c, ev_null);
+  c->prof.stats_kernel_ms = drain_events(c, ev_stats);
+  c->prof.scores = c->prof.paths * (int64_t)K;
+  c->prof.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+  return GCRE_OK;
+}
+
+// The tail of a join whose kernels were launched ahead (run_join, kLaunch): wait for them, copy the maxima out of the join
+// index's own array, merge the winners its inspection cached.
+int finish_launched(gcre_ctx* c, const JoinPlan& jp, gcre_result* out) {
+  const auto t_begin = std::chrono::steady_clock::now();
+  gcre_uids::Launched& L = jp.u->launch;
+  const int K = c->win_K;
+  const int Kpad = ((K + kPermTileMax - 1) / kPermTileMax) * kPermTileMax;
+  HIP_TRY(c, hipEventSynchronize(L.done));
+  L.active = false;
+  // (on the inspection stream, idle by now: the main stream holds the later levels' kernels, which this join's caller
+  // need not wait for)
+  uint32_t lookups = 0;
+  if (K > 0) HIP_TRY(c, hipMemcpyAsync(&lookups, L.d_null.p + Kpad, 4, hipMemcpyDeviceToHost, c->insp_stream));
+  std::vector<Candidate> cands = std::move(L.cands);
+  L.cands.clear();
+  c->prof = L.prof;
+  L.prof = gcre_profile{};
+  if (int rc = deliver_join(c, jp, out, K, L.d_null.p, c->insp_stream, cands, L.ev_null, L.ev_stats, t_begin, nullptr))
+    return rc;
+  c->prof.ie_lookup_tiles += lookups;
+  return GCRE_OK;
+}
+
+// A stretch of joined paths [b, e) of which [sb, se) is scored (the rest is only materialised: kept rows)
+struct Seg { int64_t b, e, sb, se; };
+
+// One call of run_join.  Written by begin_join unless a comment says otherwise; "(join)" marks what the chunks accumulate.
+// Nothing here outlives the call.
+struct JoinRun {
+  gcre_ctx* const c;
+  const JoinPlan& jp;
+  gcre_result* const out;
+  const JoinMode mode;
+  const gcre_uids* u = nullptr;
+  // the permutation window (all permutations unless gcre_set_perm_window narrowed it): K, the slice of the transposed
+  // masks, of the masks (row stride Kstride: the full Kpad) and of the maxima
+  Geometry g{};
+  int Kstride = 0;
+  int nkt_sp = 0;                      // 2048-permutation tiles of the window
+  NullConfig cfg{};
+  uint32_t* w_null = nullptr;          // the maxima the join writes (kLaunch: the join index's own)
+  const uint32_t* w_masks = nullptr;
+  const uint32_t* w_mt = nullptr;
+  hipStream_t st = nullptr;            // the main stream; kInspect: the inspection stream
+  uint32_t* flagblk = nullptr;         // the inspectors' flag block (FlagWord); kInspect: d_max_tot_b
+  DevBuf<uint64_t>* exbuf = nullptr;   // excess rows of a hinted join; kInspect: d_excess_b (the join in flight owns d_excess)
+  // the profile sink: the context's, or (kInspect, kLaunch) that of the join the ahead work is for (u->launch) -- not the
+  // join it runs beside
+  gcre_profile* prof = nullptr;
+  EvList* ev_null = nullptr;
+  EvList* ev_stats = nullptr;
+  std::chrono::steady_clock::time_point t_begin;
+  // kFull: the registered next joins (gcre_join_ahead) belong to THIS call: run by finish_join once this join's own kernels
+  // are in flight, dropped with the JoinRun on every other road out
+  std::unique_ptr<std::vector<JoinPlan>> ahead_plan;
+  int64_t P = 0;                       // joined paths
+  bool keep = false;                   // keep_paths = paths_res.size != 0, join_base.cpp:217
+  bool replay = false;                 // the inspection cache holds this very join
+  InspKey ikey;
+  int64_t sb = 0, se = 0;              // the shard, clamped to [0, P)
+  // plan_segments
+  std::vector<Seg> segs;
+  int64_t pl_b = 0, pl_e = 0;          // rows of res that get count planes
+  int64_t r_lo = 0, r_hi = 0;          // rows of paths0 this call reads
+  int64_t tile = 0, chunk_cap = 0;     // path tile of the dense kernel; joined paths per chunk
+  size_t cap = 0;                      // elements of a chunk's buffers
+  // prepare_operands; a chunk that finds the hint broken changes hinted, red, have_pz, want_ie and the res_planes pair
+  bool sparse_ok = false, want_ie = false, hinted = false;
+  const gcre_pathset* red = nullptr;   // the rows the join adds: the reduced operand, or paths1
+  bool have_p0 = false, have_pz = false, use_rec = false;
+  const gcre_pathset *rec_a = nullptr, *rec_z = nullptr;   // use_rec: the operands of paths0's recipe
+  gcre_recipe* rcp = nullptr;          // the recipe this join leaves with the rows it keeps (method 1)
+  bool res_planes = false;             // the kept rows' count planes are written ...
+  bool res_planes_ok = false;          // ... and no chunk was priced out of writing them
+  bool split = false;                  // chunks are cut at the shard's ends (every form but the inclusion-exclusion one; (join))
+  // (join)
+  uint32_t over_next = 0;              // entries of the recipe's overflow area handed out so far (kFlagOverReserved)
+  bool recipe_started = false, recipe_broken = false, hint_broke_late = false;
+  uint32_t join_max_tot = 0, join_max_len = 0;
+  bool ie_ran = false, ie_stat_pending = false;
+  int exchanges_done = 0;
+  std::vector<Candidate> cands;
+  double select_ms = 0, select_wait_ms = 0;
+  JoinRun(gcre_ctx* c_, const JoinPlan& jp_, gcre_result* out_, JoinMode m) : c(c_), jp(jp_), out(out_), mode(m) {}
+};
+
+// One chunk [cb, cb + n) of a join: written by open_chunk, then by the stages in turn.  What outlives it goes to its
+// inspection-cache entry or to the JoinRun.
+struct ChunkRun {
+  const Seg* sg = nullptr;
+  int64_t cb = 0, n = 0;
+  int64_t s0 = 0, s1 = 0;              // scored paths of the chunk: [s0, s1)
+  bool scored = false, partial = false;
+  int64_t npt = 0, padded = 0;         // path tiles of the dense kernel; rows up to `padded` are valid
+  ChunkInsp* ci = nullptr;             // the chunk's inspection-cache entry (cache on)
+  ChunkBufs* b = nullptr;              // its buffers: ci's, or the context's scratch
+  bool hit = false;                    // replayed: the inspector's output is in place
+  bool use_ie = false, use_sparse = false;
+  // inspect_chunk (use_ie): where the inspector's lists go -- the kept set's recipe (absolute row = cb + i), or b
+  uint32_t *rowz = nullptr, *linfo = nullptr, *lover = nullptr, *slot = nullptr, *over = nullptr;
+  size_t over_cap = 0;
+  bool sel_begun = false, sel_done = false;
+  hipStream_t sel_on = nullptr;        // the stream the selection runs on
+  Winners win;
+  bool win_from_cache = false;
+  uint32_t flags[kFlagWords] = {};     // score_chunk_ie: the inspector's flag block
+};
+
+// How a chunk's stages ended: the chunk loop of run_join runs it again after the last four
+enum class ChunkEnd {
+  kOpen,          // nothing decided yet: the null kernel is still to come
+  kScored,        // its null kernel is queued: its winners are next
+  kInspected,     // kInspect: inspected, its winners are next
+  kNotNeeded,     // nothing of it is scored (rows of another shard: kept rows, recipe entries)
+  kPricedOut,     // the inclusion-exclusion form costs more than the dense kernel: a whole chunk goes to the latter
+  kResplit,       // a partial chunk off the inclusion-exclusion form: chunks are cut at the shard's ends from here on
+  kRedoOverflow,  // more long lists than the area held: grown
+  kRedoHint,      // the reduced operand does not describe the join: again on paths1 itself
+};
+
+// room for a chunk.  A replayed chunk's buffers hold what its inspector wrote: they may only grow with their contents (the
+// path tile, and with it `cap` and the padding, depends on the window's permutation count)
+template <typename T>
+hipError_t hold(const ChunkRun& C, DevBuf<T>& buf, size_t want, hipStream_t st) {
+  return C.hit ? buf.grow_keep(want, buf.cap, st) : buf.reserve(want);
+}
+
+// counter planes a null kernel keeps for counts up to `max_tot` carriers
+int counter_planes(uint32_t max_tot) {
+  int planes = 5;
+  while (planes < 16 && (max_tot >> planes) != 0) planes++;
+  return planes;
+}
+
+// persistent waves per XCD of a launch at `waves_per_cu` resident waves per CU
+int xcd_waves(const gcre_ctx* c, int waves_per_cu) { return std::max(4, (c->cus * waves_per_cu / 8 / 4) * 4); }
+
+// halve a launch's waves per XCD (not below 4) until every one of the 8 x waves has `per_wave` of the `items`
+int spread_waves(int waves, int64_t items, int64_t per_wave) {
+  while (waves > 4 && items < (int64_t)8 * waves * per_wave) waves = std::max(4, (waves / 2 / 4) * 4);
+  return waves;
+}
+
+// Auto kernel choice (GCRE_NULL_KERNEL unset, DESIGN.md "Kernel choice"): dense = 2 VALU ops per dword per permutation at
+// ~65 lane-ops/clk/CU.  The expressions are compared at a threshold: keep their order.
+double dense_cost(const Geometry& g) { return 2.0 * g.Wp * g.method * (double)g.K * 2.0 / 65.0; }
+
+// inclusion-exclusion: one mask-row load per list entry per 2048-permutation tile at ~15 CU-cycles each; paths0 lists without
+// planes are bounded by its longest row, once per segment
+bool ie_dearer(const Geometry& g, int nkt_sp, bool have_p0, uint32_t p0_max, int64_t nseg_est, int64_t n, uint64_t n_list) {
+  const double base = have_p0 ? 0.0 : (double)p0_max * g.method * (double)nseg_est / (double)n;
+  const double entries = (double)n_list / (double)n + base + 10.0 * g.method;
+  const double ie_cost = entries * nkt_sp * 15.0;
+  return ie_cost >= dense_cost(g);
+}
+
+// delta streaming: the same per entry; base lists are bounded by the largest carrier total, once per segment
+bool sparse_dearer(const Geometry& g, uint64_t n_delta, uint32_t max_tot, int64_t nseg_est, int64_t n) {
+  const double entries = (double)n_delta / (double)n + (double)max_tot * g.method * (double)nseg_est / (double)n;
+  const double sparse_cost = entries * ((g.K + kSparseTile - 1) / kSparseTile) * 15.0;
+  return sparse_cost >= dense_cost(g);
+}
+
+// uids (rows of paths0) with at least one joined path inside [first, first+count)
+int64_t uids_in(const gcre_uids& u, int64_t first, int64_t count) {
+  const auto& pi = u.h_path_idx;
+  int64_t lo = std::upper_bound(pi.begin(), pi.end(), first) - pi.begin() - 1;
+  int64_t hi = std::lower_bound(pi.begin(), pi.end(), first + count) - pi.begin();   // first uid starting at/after the end
+  if (u.h_nonempty.empty()) {   // prefix count of the uids that join anything: once per join index
+    u.h_nonempty.assign((size_t)u.n_uids + 1, 0);
+    for (int64_t i = 0; i < u.n_uids; i++)
+      u.h_nonempty[(size_t)i + 1] = u.h_nonempty[(size_t)i] + (pi[(size_t)i + 1] > pi[(size_t)i] ? 1 : 0);
+  }
+  lo = std::max<int64_t>(lo, 0);
+  hi = std::min(hi, u.n_uids);
+  return hi > lo ? u.h_nonempty[(size_t)hi] - u.h_nonempty[(size_t)lo] : (int64_t)0;
+}
+
+// compulsory HBM bytes of the permutation scoring of `count` joined paths: every paths0 row
+// once per uid, every paths1 row once per joined path, the masks and the maxima once, the join index
+double alg_bytes(const JoinRun& R, int64_t first, int64_t count) {
+  const Geometry& g = R.g;
+  const double up = (double)uids_in(*R.u, first, count);
+  return 8.0 * g.W * g.method * (up + (double)count) + 8.0 * g.W * g.K + 4.0 * g.K + 24.0 * up;
+}
+
+// ---- thresholds shared across devices: the maxima so far go out, the merged ones come back (gcre_join_opts.exchange) ----
+int exchange_now(JoinRun& R) {
+  gcre_ctx* c = R.c;
+  const JoinPlan& jp = R.jp;
+  if (!jp.exchange || R.exchanges_done >= jp.exchanges) return GCRE_OK;
+  R.exchanges_done++;
+  if (R.g.K <= 0) return GCRE_OK;
+  HIP_TRY(c, hipMemcpyAsync(jp.d_null_out, R.w_null, (size_t)R.g.K * 4, hipMemcpyDeviceToDevice, R.st));
+  HIP_TRY(c, hipStreamSynchronize(R.st));
+  if (jp.exchange(jp.exchange_user, jp.d_null_out, c->win_k0, c->win_k0 + R.g.K) != 0)
+    return fail(c, GCRE_ERR_DEVICE, "the caller's threshold exchange failed");
+  // merged maxima are >= this shard's: a plain copy back (non-negative floats order like their bit patterns)
+  HIP_TRY(c, hipMemcpyAsync(R.w_null, jp.d_null_out, (size_t)R.g.K * 4, hipMemcpyDeviceToDevice, R.st));
+  return GCRE_OK;
+}
+
+// the look-up counter the last pruned launch left in the flag block, once the block is about to be reused
+void collect_ie_stat(JoinRun& R) {
+  if (R.mode == kLaunch) R.ie_stat_pending = false;   // (its counter sits behind its maxima and is read when the join is finished)
+  if (!R.ie_stat_pending) return;
+  uint32_t v = 0;
+  if (hipMemcpyAsync(&v, R.flagblk + kFlagLookupTiles, 4, hipMemcpyDeviceToHost, R.st) == hipSuccess &&
+      hipStreamSynchronize(R.st) == hipSuccess)
+    R.prof->ie_lookup_tiles += v;
+  R.ie_stat_pending = false;
+}
+
+// the rows the join adds and their count planes
+int prepare_z(JoinRun& R) {
+  gcre_ctx* c = R.c;
+  R.red = R.hinted ? R.u->red : R.jp.p1;
+  // a kept set read as the added rows (level 5 adds rows of paths2) without planes of its own: they are rebuilt from
+  // its bit lists now, and the join that writes its rows leaves them next time
+  if (!planes_current(c, R.red) && R.red->rec) R.red->planes_wanted = true;
+  if (int rc = ensure_lists(c, R.red)) return rc;
+  if (int rc = ensure_planes(c, R.red)) return rc;
+  R.have_pz = planes_current(c, R.red);
+  return GCRE_OK;
+}
+
+// the winners of a chunk's selection (c->d_sel): their keys, counts and rows gathered from the chunk's buffers, copied out
+int queue_winners(gcre_ctx* c, const ChunkBufs& b, int64_t s0, uint32_t nsel, Winners& w, hipStream_t qs) {
+  w.n = nsel;
+  if (nsel == 0) return GCRE_OK;
+  HIP_TRY(c, c->d_wkey.reserve(nsel));
+  HIP_TRY(c, c->d_wcases.reserve(nsel));
+  HIP_TRY(c, c->d_wctrls.reserve(nsel));
+  HIP_TRY(c, c->d_wrow0.reserve(nsel));
+  HIP_TRY(c, c->d_wrow1.reserve(nsel));
+  HIP_TRY(c, launch_gather_winners(c->d_sel.p, nsel, b.key.p + s0, b.cases.p + s0, b.ctrls.p + s0, b.row0.p + s0,
+                                   b.row1.p + s0, c->d_wkey.p, c->d_wcases.p, c->d_wctrls.p, c->d_wrow0.p, c->d_wrow1.p, qs));
+  w.sel.resize(nsel); w.cases.resize(nsel); w.ctrls.resize(nsel); w.r0.resize(nsel); w.r1.resize(nsel); w.key.resize(nsel);
+  HIP_TRY(c, hipMemcpyAsync(w.sel.data(), c->d_sel.p, nsel * 4, hipMemcpyDeviceToHost, qs));
+  HIP_TRY(c, hipMemcpyAsync(w.key.data(), c->d_wkey.p, nsel * 8, hipMemcpyDeviceToHost, qs));
+  HIP_TRY(c, hipMemcpyAsync(w.cases.data(), c->d_wcases.p, nsel * 4, hipMemcpyDeviceToHost, qs));
+  HIP_TRY(c, hipMemcpyAsync(w.ctrls.data(), c->d_wctrls.p, nsel * 4, hipMemcpyDeviceToHost, qs));
+  HIP_TRY(c, hipMemcpyAsync(w.r0.data(), c->d_wrow0.p, nsel * 4, hipMemcpyDeviceToHost, qs));
+  HIP_TRY(c, hipMemcpyAsync(w.r1.data(), c->d_wrow1.p, nsel * 4, hipMemcpyDeviceToHost, qs));
+  return GCRE_OK;
+}
+
+// the second half of a selection begun on C.sel_on, whose state has arrived (the caller waited for it): collect the
+// winners and queue their copies
+int finish_selection(JoinRun& R, ChunkRun& C) {
+  uint32_t nsel = 0;
+  const int64_t count = C.s1 - C.s0;
+  if (int rc = select_finish(R.c, C.b->key.p + C.s0, count, R.c->top_k, R.c->h_sel, &nsel, C.sel_on)) return rc;
+  if (int rc = queue_winners(R.c, *C.b, C.s0, nsel, C.win, C.sel_on)) return rc;
+  C.sel_done = true;
+  return GCRE_OK;
+}
+
+enum class Begin { kRun, kDone, kFinishLaunched };
+
+// The window, the checks of JoinExec::join, the inspection cache's verdict and what follows from it, the shard, the streams.
+// *next: kDone when there is nothing for this call to do (kInspect: already inspected; kLaunch: not launched; no cache),
+// kFinishLaunched when the join was launched ahead and only its results are left to collect.
+int begin_join(JoinRun& R, Begin* next) {
+  gcre_ctx* c = R.c;
+  const JoinPlan& jp = R.jp;
+  const JoinMode mode = R.mode;
+  *next = Begin::kDone;
+  Geometry& g = R.g;
+  g = c->g;
   g.K = c->win_K;
   g.Kpad = ((g.K + kPermTileMax - 1) / kPermTileMax) * kPermTileMax;
-  const int Kstride = c->g.Kpad;
-  uint32_t* w_null = c->d_null ? c->d_null + c->win_k0 : nullptr;
-  const uint32_t* const w_masks = c->d_masks ? c->d_masks + c->win_k0 : nullptr;
-  const uint32_t* const w_mt = c->d_mt ? c->d_mt + (size_t)(c->win_k0 / kSparseTile) * (size_t)(64 * g.Wp + 1) * 64 : nullptr;
-  const auto t_begin = std::chrono::steady_clock::now();
-  if (out) std::memset(out, 0, sizeof *out);
-  // the registered next join (gcre_join_ahead) belongs to THIS call: taken here, inspected below once this join's own
-  // kernels are in flight, dropped on every road out
-  std::unique_ptr<std::vector<JoinPlan>> ahead_plan;
+  R.Kstride = c->g.Kpad;
+  R.nkt_sp = (g.K + kSparseTile - 1) / kSparseTile;
+  R.cfg = null_config(g.method, g.K);
+  R.w_null = c->d_null ? c->d_null + c->win_k0 : nullptr;
+  R.w_masks = c->d_masks ? c->d_masks + c->win_k0 : nullptr;
+  R.w_mt = c->d_mt ? c->d_mt + (size_t)(c->win_k0 / kSparseTile) * (size_t)(64 * g.Wp + 1) * 64 : nullptr;
+  R.t_begin = std::chrono::steady_clock::now();
+  if (R.out) std::memset(R.out, 0, sizeof *R.out);
   if (mode == kFull) {
-    ahead_plan.reset(c->ahead);
+    R.ahead_plan.reset(c->ahead);
     c->ahead = nullptr;
     c->ahead_closed = false;
   }
-  uint32_t* const flagblk = inspect_only ? c->d_max_tot_b : c->d_max_tot;
+  R.flagblk = mode == kInspect ? c->d_max_tot_b : c->d_max_tot;
   if (!c->have_table) return fail(c, GCRE_ERR_ASSERT, "value table not set");
   if (g.K > 0 && !c->have_perms) return fail(c, GCRE_ERR_ASSERT, "permuted cases not set");
   if (c->top_k < 1) return fail(c, GCRE_ERR_ARG, "top_k must be >= 1");
   if (!jp.u || jp.u->ctx != c || !jp.p0 || !jp.p1 || jp.p0->ctx != c || jp.p1->ctx != c || (jp.res && jp.res->ctx != c))
     return fail(c, GCRE_ERR_ARG, "uids / path set do not belong to this context");
+  R.u = jp.u;
   const gcre_uids& u = *jp.u;
 
   // ---- the checks of JoinExec::join, join_base.cpp:196-200 ----
   if (u.n_uids != jp.p0->nrows) return fail(c, GCRE_ERR_ASSERT, "assertion: uids.size() != paths0.size");
   if (u.max_loc >= jp.p1->nrows) return fail(c, GCRE_ERR_RANGE, "assertion: uid location out of range");
-  const int64_t P = u.total;
-  const bool keep = jp.res != nullptr && jp.res->nrows != 0;   // keep_paths = paths_res.size != 0, join_base.cpp:217
+  const int64_t P = R.P = u.total;
+  const bool keep = R.keep = jp.res != nullptr && jp.res->nrows != 0;
   if (jp.res && jp.res->nrows != 0 && jp.res->nrows != P)
     return fail(c, GCRE_ERR_ASSERT, "assertion: paths_res.size != total paths");
   // ---- inspection cache: has this very join (same operand rows, kept set, shard, table) run on this index before? ----
-  InspKey ikey;
-  bool replay = false;
+  InspKey& ikey = R.ikey;
   if (c->insp_cache) {
     ikey.p0_id = jp.p0->id; ikey.p0_ver = jp.p0->version;
     ikey.p1_id = jp.p1->id; ikey.p1_ver = jp.p1->version;
@@ -1439,21 +1699,23 @@ int run_join(gcre_ctx* c, const JoinPlan& jp, gcre_result* out, JoinMode mode = 
     ikey.chunk_paths = c->chunk_paths;
     ikey.top_k = c->top_k;
     ikey.null_kernel = c->null_kernel;
-    replay = u.insp_valid && u.insp_key == ikey && (!keep || jp.res->version == u.insp_res_ver);
+    R.replay = u.insp_valid && u.insp_key == ikey && (!keep || jp.res->version == u.insp_res_ver);
     // not launched: the join's own call runs it whole
-    if (launch_only && (!replay || jp.exchange || g.K <= 0)) return GCRE_OK;
+    if (mode == kLaunch && (!R.replay || jp.exchange || g.K <= 0)) return GCRE_OK;
     if (mode == kFull && u.launch.active) {
       // this join was launched ahead: if it is still the same join (operands, kept set, shard, table, window, masks) only its
       // results are left to collect; otherwise its kernels are waited for and forgotten
       const gcre_uids::Launched& L = u.launch;
-      if (replay && L.key == ikey && L.win_k0 == c->win_k0 && L.win_K == c->win_K && L.mask_epoch == c->mask_epoch &&
-          (!keep || jp.res->version == L.res_ver) && !jp.exchange)
-        return finish_launched(c, jp, out);
+      if (R.replay && L.key == ikey && L.win_k0 == c->win_k0 && L.win_K == c->win_K && L.mask_epoch == c->mask_epoch &&
+          (!keep || jp.res->version == L.res_ver) && !jp.exchange) {
+        *next = Begin::kFinishLaunched;
+        return GCRE_OK;
+      }
       drop_launch(&u);
     }
-    if (inspect_only) drop_launch(&u);          // (a stale launch of an earlier pass)
-    if (inspect_only && replay) return GCRE_OK;   // already inspected (a later permutation window, kept inspections)
-    if (!replay) {
+    if (mode == kInspect) drop_launch(&u);          // (a stale launch of an earlier pass)
+    if (mode == kInspect && R.replay) return GCRE_OK;   // already inspected (a later permutation window, kept inspections)
+    if (!R.replay) {
       for (auto& ci : u.insp) {   // the buffers stay and serve the new chunks in turn
         ci.inspected = ci.with_lists = ci.flags_valid = ci.win_valid = false;
         ci.cb = -1;
@@ -1468,8 +1730,8 @@ int run_join(gcre_ctx* c, const JoinPlan& jp, gcre_result* out, JoinMode mode = 
     u.insp.clear();
     u.insp_valid = false;
   }
-  if (keep && !replay) jp.res->version++;
-  if (keep && !replay) {   // its rows are about to be rewritten: lists go, the plane buffer stays allocated for the new rows
+  if (keep && !R.replay) {   // its rows are about to be rewritten: lists go, the plane buffer stays allocated for the new rows
+    jp.res->version++;
     uint32_t* planes = jp.res->d_planes;
     const int groups = jp.res->plane_groups;
     const size_t pbytes = jp.res->planes_bytes;
@@ -1488,1034 +1750,990 @@ int run_join(gcre_ctx* c, const JoinPlan& jp, gcre_result* out, JoinMode mode = 
     if (u.n_signs < need_signs) return fail(c, GCRE_ERR_RANGE, "signs vector shorter than the rows it is indexed by");
   }
 
-  int64_t sb = jp.shard_begin, se = jp.shard_end;
-  if (!jp.sharded) { sb = 0; se = P; }
-  sb = std::max<int64_t>(0, std::min(sb, P));
-  se = std::max(sb, std::min(se, P));
+  R.sb = jp.sharded ? jp.shard_begin : 0;
+  R.se = jp.sharded ? jp.shard_end : P;
+  R.sb = std::max<int64_t>(0, std::min(R.sb, P));
+  R.se = std::max(R.sb, std::min(R.se, P));
 
-  hipStream_t st = inspect_only ? c->insp_stream : c->stream;
-  const int Kpad = g.Kpad;
-  // what an ahead inspection and an ahead launch cost is booked on the join they work for, not on the join they run beside
-  struct ProfSwap {
-    gcre_ctx* c;
-    gcre_uids::Launched* L;
-    ProfSwap(gcre_ctx* c_, gcre_uids::Launched* L_) : c(c_), L(L_) { swap(); }
-    ~ProfSwap() { swap(); }
-    void swap() {
-      if (!L) return;
-      std::swap(c->prof, L->prof);
-      std::swap(c->ev_null, L->ev_null);
-      std::swap(c->ev_stats, L->ev_stats);
-    }
-  } prof_swap(c, mode != kFull ? &u.launch : nullptr);
-  if (inspect_only) {
+  hipStream_t st = R.st = mode == kInspect ? c->insp_stream : c->stream;
+  R.exbuf = mode == kInspect ? &c->d_excess_b : &c->d_excess;
+  const bool own_sink = mode == kFull;
+  R.prof = own_sink ? &c->prof : &u.launch.prof;
+  R.ev_null = own_sink ? &c->ev_null : &u.launch.ev_null;
+  R.ev_stats = own_sink ? &c->ev_stats : &u.launch.ev_stats;
+  if (mode == kInspect) {
     // behind the last inspector that ran on the main stream (its kept rows and recipe are this one's operands)
     HIP_TRY(c, hipStreamWaitEvent(st, c->ev_insp_main, 0));
   } else {
     // behind an inspection that ran ahead on its own stream (a no-op when there was none)
     HIP_TRY(c, hipStreamWaitEvent(st, c->ev_insp_done, 0));
-    if (launch_only) {   // the launch's own maxima (+ its look-up counter): the context's belong to the join that is being finished
-      HIP_TRY(c, u.launch.d_null.reserve((size_t)Kpad + 64));
-      w_null = u.launch.d_null.p;
+    if (mode == kLaunch) {   // the launch's own maxima (+ its look-up counter): the context's belong to the join that is being finished
+      HIP_TRY(c, u.launch.d_null.reserve((size_t)g.Kpad + 64));
+      R.w_null = u.launch.d_null.p;
       if (!u.launch.done && hipEventCreateWithFlags(&u.launch.done, hipEventDisableTiming) != hipSuccess)
         return fail(c, GCRE_ERR_DEVICE, "hipEventCreate failed");
-      HIP_TRY(c, hipMemsetAsync(w_null, 0, ((size_t)Kpad + 1) * 4, st));
-    } else if (Kpad > 0) {
-      HIP_TRY(c, hipMemsetAsync(w_null, 0, (size_t)Kpad * 4, st));
+      HIP_TRY(c, hipMemsetAsync(R.w_null, 0, ((size_t)g.Kpad + 1) * 4, st));
+    } else if (g.Kpad > 0) {
+      HIP_TRY(c, hipMemsetAsync(R.w_null, 0, (size_t)g.Kpad * 4, st));
     }
   }
-  // The chain of gcre_join_ahead: once this join's own work is queued, every registered later join is inspected (on the
-  // inspection stream) and launched (on the main stream) in turn -- the big inspector of the last level then runs beside the
-  // small permutation kernels of the levels before it instead of after them
-  auto run_chain = [&]() -> int {
-    if (!ahead_plan) return GCRE_OK;
-    std::unique_ptr<std::vector<JoinPlan>> chain = std::move(ahead_plan);
-    int budget = 1 << 30;   // GCRE_AHEAD_MAX (diagnostics): how many of the registered joins run ahead
-    if (const char* e = std::getenv("GCRE_AHEAD_MAX")) budget = std::atoi(e);
-    for (const JoinPlan& a : *chain) {
-      if (budget-- <= 0) break;
-      if (std::getenv("GCRE_AHEAD_INSPECT_ONLY")) {   // (diagnostics: inspections ahead, no launches)
-        if (int rc = run_join(c, a, nullptr, kInspect)) return rc;
-        continue;
-      }
-      if (int rc = run_join(c, a, nullptr, kInspect)) return rc;
-      if (int rc = run_join(c, a, nullptr, kLaunch)) return rc;
-      // a join that was not launched (its inspection did not validate: a broken hint) has not written what the joins
-      // behind it read: they run whole, in their own calls
-      if (!a.u->launch.active) break;
-    }
-    return GCRE_OK;
-  };
-
-  const NullConfig cfg = null_config(g.method, g.K);
-  // ---- thresholds shared across devices: the maxima so far go out, the merged ones come back (gcre_join_opts.exchange) ----
-  int exchanges_done = 0;
-  auto exchange_now = [&]() -> int {
-    if (!jp.exchange || exchanges_done >= jp.exchanges) return GCRE_OK;
-    exchanges_done++;
-    if (g.K <= 0) return GCRE_OK;
-    HIP_TRY(c, hipMemcpyAsync(jp.d_null_out, w_null, (size_t)g.K * 4, hipMemcpyDeviceToDevice, st));
-    HIP_TRY(c, hipStreamSynchronize(st));
-    if (jp.exchange(jp.exchange_user, jp.d_null_out, c->win_k0, c->win_k0 + g.K) != 0)
-      return fail(c, GCRE_ERR_DEVICE, "the caller's threshold exchange failed");
-    // merged maxima are >= this shard's: a plain copy back (non-negative floats order like their bit patterns)
-    HIP_TRY(c, hipMemcpyAsync(w_null, jp.d_null_out, (size_t)g.K * 4, hipMemcpyDeviceToDevice, st));
-    return GCRE_OK;
-  };
-  std::vector<Candidate> cands;
   if (mode == kFull) c->prof = gcre_profile{};
-  double select_ms = 0, select_wait_ms = 0;
-  bool keep_planes_done = false;
-  int64_t keep_planes_lo = 0, keep_planes_hi = 0;
-  uint32_t keep_max_tot = 0;
+  *next = Begin::kRun;
+  return GCRE_OK;
+}
 
-  if (P > 0) {
-    // segments: rows outside the shard are only materialised (when kept); the shard [sb, se) inside a segment is scored.
-    // Kept rows next to the shard share its launches (one inspector pass, one flag read-back, one kernel that scores
-    // the shard's path runs and only writes count planes / recipe entries for the others).
-    struct Seg { int64_t b, e, sb, se; };
-    std::vector<Seg> segs;
-    // kept rows outside the scored shard: all of them, or only [keep_begin, keep_end) (gcre_join_opts.keep_ranged)
-    int64_t kb = 0, ke = P;
-    if (jp.keep_ranged) {
-      kb = std::max<int64_t>(0, std::min(jp.keep_begin, P));
-      ke = std::max(kb, std::min(jp.keep_end, P));
+// Segments: rows outside the shard are only materialised (when kept); the shard [sb, se) inside a segment is scored.
+// Kept rows next to the shard share its launches (one inspector pass, one flag read-back, one kernel that scores the shard's
+// path runs and only writes count planes / recipe entries for the others).  Then the chunk size and the rows of paths0 read.
+void plan_segments(JoinRun& R) {
+  const JoinPlan& jp = R.jp;
+  const int64_t P = R.P, sb = R.sb, se = R.se;
+  // kept rows outside the scored shard: all of them, or only [keep_begin, keep_end) (gcre_join_opts.keep_ranged)
+  int64_t kb = 0, ke = P;
+  if (jp.keep_ranged) {
+    kb = std::max<int64_t>(0, std::min(jp.keep_begin, P));
+    ke = std::max(kb, std::min(jp.keep_end, P));
+  }
+  // rows of `res` that get count planes: every produced row, or (gcre_join_opts.keep_ranged == 2) the hull of
+  // [keep_begin, keep_end) and the shard
+  R.pl_b = std::min(kb, se > sb ? sb : kb);
+  R.pl_e = std::max(ke, se > sb ? se : ke);
+  if (jp.planes_ranged) {
+    const int64_t qb = std::max<int64_t>(0, std::min(jp.keep_begin, P)), qe = std::max(qb, std::min(jp.keep_end, P));
+    R.pl_b = qe > qb ? qb : (se > sb ? sb : 0);
+    R.pl_e = qe > qb ? qe : (se > sb ? se : 0);
+    if (se > sb) {
+      R.pl_b = std::min(R.pl_b, sb);
+      R.pl_e = std::max(R.pl_e, se);
     }
-    // rows of `res` that get count planes: every produced row, or (gcre_join_opts.keep_ranged == 2) the hull of
-    // [keep_begin, keep_end) and the shard
-    int64_t pl_b = std::min(kb, se > sb ? sb : kb), pl_e = std::max(ke, se > sb ? se : ke);
-    if (jp.planes_ranged) {
-      const int64_t qb = std::max<int64_t>(0, std::min(jp.keep_begin, P)), qe = std::max(qb, std::min(jp.keep_end, P));
-      pl_b = qe > qb ? qb : (se > sb ? sb : 0);
-      pl_e = qe > qb ? qe : (se > sb ? se : 0);
-      if (se > sb) {
-        pl_b = std::min(pl_b, sb);
-        pl_e = std::max(pl_e, se);
-      }
-    }
-    if (!keep || kb >= ke) {
-      if (se > sb) segs.push_back({sb, se, sb, se});
-    } else if (se <= sb) {
-      segs.push_back({kb, ke, kb, kb});
-    } else if (kb <= se && sb <= ke) {   // overlapping or adjacent: one segment
-      segs.push_back({std::min(kb, sb), std::max(ke, se), sb, se});
-    } else if (ke < sb) {
-      segs.push_back({kb, ke, kb, kb});
-      segs.push_back({sb, se, sb, se});
-    } else {
-      segs.push_back({sb, se, sb, se});
-      segs.push_back({kb, ke, kb, kb});
-    }
+  }
+  std::vector<Seg>& segs = R.segs;
+  if (!R.keep || kb >= ke) {
+    if (se > sb) segs.push_back({sb, se, sb, se});
+  } else if (se <= sb) {
+    segs.push_back({kb, ke, kb, kb});
+  } else if (kb <= se && sb <= ke) {   // overlapping or adjacent: one segment
+    segs.push_back({std::min(kb, sb), std::max(ke, se), sb, se});
+  } else if (ke < sb) {
+    segs.push_back({kb, ke, kb, kb});
+    segs.push_back({sb, se, sb, se});
+  } else {
+    segs.push_back({sb, se, sb, se});
+    segs.push_back({kb, ke, kb, kb});
+  }
 
-    const int64_t tile = cfg.path_tile;
-    const int64_t chunk_cap = std::max<int64_t>(tile, (c->chunk_paths / tile) * tile);
-    const size_t cap = (size_t)std::min<int64_t>(chunk_cap, ((P + tile - 1) / tile) * tile) + (size_t)tile;
-    bool hint_broke_late = false;
+  R.tile = R.cfg.path_tile;
+  R.chunk_cap = std::max<int64_t>(R.tile, (R.c->chunk_paths / R.tile) * R.tile);
+  R.cap = (size_t)std::min<int64_t>(R.chunk_cap, ((P + R.tile - 1) / R.tile) * R.tile) + (size_t)R.tile;
+  // rows of paths0 this call reads: the uids of the joined paths it processes
+  if (!segs.empty()) {
+    int64_t first = P, last = 0;
+    for (const Seg& sg : segs) {
+      first = std::min(first, sg.b);
+      last = std::max(last, sg.e);
+    }
+    const auto& pi = R.u->h_path_idx;
+    R.r_lo = std::max<int64_t>(0, (int64_t)(std::upper_bound(pi.begin(), pi.end(), first) - pi.begin()) - 1);
+    R.r_hi = std::min<int64_t>(R.u->n_uids, (int64_t)(std::lower_bound(pi.begin(), pi.end(), last) - pi.begin()));
+  }
+}
 
-    // uids (rows of paths0) with at least one joined path inside [first, first+count)
-    auto uids_in = [&](int64_t first, int64_t count) {
-      const auto& pi = u.h_path_idx;
-      int64_t lo = std::upper_bound(pi.begin(), pi.end(), first) - pi.begin() - 1;
-      int64_t hi = std::lower_bound(pi.begin(), pi.end(), first + count) - pi.begin();   // first uid starting at/after the end
-      if (u.h_nonempty.empty()) {   // prefix count of the uids that join anything: once per join index
-        u.h_nonempty.assign((size_t)u.n_uids + 1, 0);
-        for (int64_t i = 0; i < u.n_uids; i++)
-          u.h_nonempty[(size_t)i + 1] = u.h_nonempty[(size_t)i] + (pi[(size_t)i + 1] > pi[(size_t)i] ? 1 : 0);
-      }
-      lo = std::max<int64_t>(lo, 0);
-      hi = std::min(hi, u.n_uids);
-      return hi > lo ? u.h_nonempty[(size_t)hi] - u.h_nonempty[(size_t)lo] : (int64_t)0;
-    };
-    // compulsory HBM bytes of the permutation scoring of `count` joined paths: every paths0 row
-    // once per uid, every paths1 row once per joined path, the masks and the maxima once, the join index
-    auto alg_bytes = [&](int64_t first, int64_t count) {
-      const double up = (double)uids_in(first, count);
-      return 8.0 * g.W * g.method * (up + (double)count) + 8.0 * g.W * g.K + 4.0 * g.K + 24.0 * up;
-    };
-    // ---- inclusion-exclusion form (gcre_ie.hip): operands and their count planes, once per join ----
-    const bool sparse_ok = sparse_enabled(c) && w_mt != nullptr;
-    bool want_ie = sparse_ok && (c->null_kernel == 0 || c->null_kernel == 3);
-    const int nkt_sp = (g.K + kSparseTile - 1) / kSparseTile;
-    bool hinted = false;
-    if (want_ie && u.red && u.d_red_index && u.n_red_index > u.max_loc) {
-      auto it = c->live_sets.find(u.red_id);   // the caller may have freed the operand since
-      hinted = it != c->live_sets.end() && it->second == u.red;
-      if (replay && !u.insp_hinted) hinted = false;   // the cached run found the hint broken: it ended on paths1 itself
-    }
-    const gcre_pathset* red = nullptr;
-    bool have_pz = false, have_p0 = false, res_planes = false, res_planes_ok = false, use_rec = false;
-    const gcre_pathset *rec_a = nullptr, *rec_z = nullptr;
-    gcre_recipe* rcp = nullptr;   // the recipe this join leaves with the rows it keeps (method 1)
-    uint32_t join_max_tot = 0, join_max_len = 0;
-    bool ie_ran = false, ie_stat_pending = false, recipe_started = false, recipe_broken = false;
-    uint32_t over_next = 0;   // entries of the kept set's overflow area (gcre_recipe::over) handed out to this join's chunks so far
-    auto collect_ie_stat = [&]() {
-      if (launch_only) ie_stat_pending = false;   // (its counter sits behind its maxima and is read when the join is finished)
-      if (!ie_stat_pending) return;
-      uint32_t v = 0;
-      if (hipMemcpyAsync(&v, flagblk + 3, 4, hipMemcpyDeviceToHost, st) == hipSuccess && hipStreamSynchronize(st) == hipSuccess)
-        c->prof.ie_lookup_tiles += v;
-      ie_stat_pending = false;
-    };
-    auto prepare_z = [&]() -> int {
-      red = hinted ? u.red : jp.p1;
-      // a kept set read as the added rows (level 5 adds rows of paths2) without planes of its own: they are rebuilt from
-      // its bit lists now, and the join that writes its rows leaves them next time
-      if (!planes_current(c, red) && red->rec) red->planes_wanted = true;
-      if (int rc = ensure_lists(c, red)) return rc;
-      if (int rc = ensure_planes(c, red)) return rc;
-      have_pz = planes_current(c, red);
-      return GCRE_OK;
-    };
-    const auto tp0 = std::chrono::steady_clock::now();
-    // rows of paths0 this call reads: the uids of the joined paths it processes
-    int64_t r_lo = 0, r_hi = 0;
-    if (!segs.empty()) {
-      int64_t first = P, last = 0;
-      for (const Seg& sg : segs) {
-        first = std::min(first, sg.b);
-        last = std::max(last, sg.e);
-      }
-      const auto& pi = u.h_path_idx;
-      r_lo = std::max<int64_t>(0, (int64_t)(std::upper_bound(pi.begin(), pi.end(), first) - pi.begin()) - 1);
-      r_hi = std::min<int64_t>(u.n_uids, (int64_t)(std::lower_bound(pi.begin(), pi.end(), last) - pi.begin()));
-    }
-    if (want_ie) {
-     if (inspect_only) {
+// ---- inclusion-exclusion form (gcre_ie.hip): operands and their count planes, once per join ----
+int prepare_operands(JoinRun& R) {
+  gcre_ctx* c = R.c;
+  const JoinPlan& jp = R.jp;
+  const gcre_uids& u = *R.u;
+  const Geometry& g = R.g;
+  const bool inspect_only = R.mode == kInspect;
+  hipStream_t st = R.st;
+  R.sparse_ok = sparse_enabled(c) && R.w_mt != nullptr;
+  R.want_ie = R.sparse_ok && (c->null_kernel == 0 || c->null_kernel == 3);
+  if (R.want_ie && u.red && u.d_red_index && u.n_red_index > u.max_loc) {
+    auto it = c->live_sets.find(u.red_id);   // the caller may have freed the operand since
+    R.hinted = it != c->live_sets.end() && it->second == u.red;
+    if (R.replay && !u.insp_hinted) R.hinted = false;   // the cached run found the hint broken: it ended on paths1 itself
+  }
+  const auto tp0 = std::chrono::steady_clock::now();
+  if (R.want_ie) {
+    if (inspect_only) {
       // count planes are the permutation kernel's business: the join proper looks after them (and decides, from what it
       // then finds, where its rows' planes go); the inspector only needs to know which rows the join adds
-      red = hinted ? u.red : jp.p1;
-      have_pz = have_p0 = true;
-     } else {
-      if (int rc = prepare_z()) return rc;
-      have_p0 = planes_cover(c, jp.p0, r_lo, r_hi);        // a kept join left them behind
-      if (!have_p0 && recipe_operands(c, jp.p0, &rec_a, &rec_z)) {
+      R.red = R.hinted ? u.red : jp.p1;
+      R.have_pz = R.have_p0 = true;
+    } else {
+      if (int rc = prepare_z(R)) return rc;
+      R.have_p0 = planes_cover(c, jp.p0, R.r_lo, R.r_hi);        // a kept join left them behind
+      if (!R.have_p0 && recipe_operands(c, jp.p0, &R.rec_a, &R.rec_z)) {
         // ... or it left the recipe: the kernel rebuilds a row's planes from the planes of the recipe's operands
         // (of which a multi-device run may hold a range only: the rows the recipe of [r_lo, r_hi) names -- the
         // producing join's paths0 rows, ascending)
-        int64_t a_lo = 0, a_hi = rec_a->nrows;
-        if (!planes_current(c, rec_a) && r_hi > r_lo && (size_t)r_hi <= jp.p0->rec->row0.cap) {
+        int64_t a_lo = 0, a_hi = R.rec_a->nrows;
+        if (!planes_current(c, R.rec_a) && R.r_hi > R.r_lo && (size_t)R.r_hi <= jp.p0->rec->row0.cap) {
           uint32_t ends[2] = {0, 0};
-          HIP_TRY(c, hipMemcpyAsync(&ends[0], jp.p0->rec->row0.p + r_lo, 4, hipMemcpyDeviceToHost, st));
-          HIP_TRY(c, hipMemcpyAsync(&ends[1], jp.p0->rec->row0.p + (r_hi - 1), 4, hipMemcpyDeviceToHost, st));
+          HIP_TRY(c, hipMemcpyAsync(&ends[0], jp.p0->rec->row0.p + R.r_lo, 4, hipMemcpyDeviceToHost, st));
+          HIP_TRY(c, hipMemcpyAsync(&ends[1], jp.p0->rec->row0.p + (R.r_hi - 1), 4, hipMemcpyDeviceToHost, st));
           HIP_TRY(c, hipStreamSynchronize(st));
           a_lo = ends[0];
           a_hi = (int64_t)ends[1] + 1;
         }
-        if (!planes_cover(c, rec_a, a_lo, a_hi)) {
-          rec_a->planes_wanted = true;
-          if (int rc = ensure_planes(c, rec_a)) return rc;
+        if (!planes_cover(c, R.rec_a, a_lo, a_hi)) {
+          R.rec_a->planes_wanted = true;
+          if (int rc = ensure_planes(c, R.rec_a)) return rc;
         }
-        if (int rc = ensure_planes(c, rec_z)) return rc;
-        use_rec = planes_cover(c, rec_a, a_lo, a_hi) && planes_current(c, rec_z);
-        have_p0 = use_rec;
+        if (int rc = ensure_planes(c, R.rec_z)) return rc;
+        R.use_rec = planes_cover(c, R.rec_a, a_lo, a_hi) && planes_current(c, R.rec_z);
+        R.have_p0 = R.use_rec;
       }
-      if (!have_p0) {
+      if (!R.have_p0) {
         if (int rc = ensure_planes(c, jp.p0)) return rc;   // from its bit lists (all rows)
-        have_p0 = planes_current(c, jp.p0);
+        R.have_p0 = planes_current(c, jp.p0);
       }
-      if (!have_p0 || !have_pz) want_ie = false;   // the planes do not fit in device memory: delta streaming (gcre_sparse.hip)
-     }
-      // (an ahead inspection has its own excess rows: the join in flight on the main stream may still be writing its own)
-      auto& exbuf = inspect_only ? c->d_excess_b : c->d_excess;
-      if (want_ie && hinted) {
-        // the hint is checked without reading paths1 per joined path: once per distinct uid range here (the reduced
-        // row lies inside paths1[loc]; what paths1[loc] has beyond it is collected per range), and per joined path in
-        // k_stats_ie (that excess lies inside paths0[idx])
-        if (int rc = ensure_ranges(c, u)) return rc;
-        const size_t ewords = (size_t)std::max<int64_t>(u.n_ranges, 1) * g.S;
-        HIP_TRY(c, exbuf.reserve(ewords));
-        HIP_TRY(c, hipMemsetAsync(exbuf.p, 0, ewords * 8, st));
-        HIP_TRY(c, hipMemsetAsync(flagblk, 0, 32, st));
-        // its verdict lands in word 6 of the flag block, which the chunks leave alone: it is read with the first
-        // chunk's flags (no round trip of its own); a reduced row that is not even part of the row it stands for sends
-        // that chunk, and the join, back to paths1 itself like any other broken hint
-        HIP_TRY(c, launch_range_union(jp.p1->d_rows, red->d_rows, u.d_red_index, u.d_pair_range, u.d_pair_loc, u.n_pairs, g.S,
-                                      g.Wp, g.method, exbuf.p, flagblk + 6, st));
+      if (!R.have_p0 || !R.have_pz) R.want_ie = false;   // the planes do not fit in device memory: delta streaming (gcre_sparse.hip)
+    }
+    if (R.want_ie && R.hinted) {
+      // the hint is checked without reading paths1 per joined path: once per distinct uid range here (the reduced
+      // row lies inside paths1[loc]; what paths1[loc] has beyond it is collected per range), and per joined path in
+      // k_stats_ie (that excess lies inside paths0[idx])
+      if (int rc = ensure_ranges(c, u)) return rc;
+      const size_t ewords = (size_t)std::max<int64_t>(u.n_ranges, 1) * g.S;
+      HIP_TRY(c, R.exbuf->reserve(ewords));
+      HIP_TRY(c, hipMemsetAsync(R.exbuf->p, 0, ewords * 8, st));
+      HIP_TRY(c, hipMemsetAsync(R.flagblk, 0, kFlagWords * 4, st));
+      // its verdict lands in word kFlagRangeUnion of the flag block, which the chunks leave alone: it is read with the first
+      // chunk's flags (no round trip of its own); a reduced row that is not even part of the row it stands for sends
+      // that chunk, and the join, back to paths1 itself like any other broken hint
+      HIP_TRY(c, launch_range_union(jp.p1->d_rows, R.red->d_rows, u.d_red_index, u.d_pair_range, u.d_pair_loc, u.n_pairs, g.S,
+                                    g.Wp, g.method, R.exbuf->p, R.flagblk + kFlagRangeUnion, st));
+    }
+    if (R.want_ie && R.keep) {
+      // carriers of a joined row <= carriers(paths0 row) + carriers(added row); <= padded patient count
+      const uint32_t bound = std::min<uint32_t>((uint32_t)(64 * g.Wp), row_max(c, jp.p0) + row_max(c, R.red));
+      const int out_groups = plane_groups_for(bound);
+      bool want_out = true;
+      // the kept rows leave with the recipe of this join (its inspector output: 60 B per row, 104 B for the signed
+      // method's two lists).  Their planes are only written when they are small, or when the next join could not use the
+      // recipe (it needs stored planes of paths0)
+      if (!jp.res->rec) jp.res->rec = new gcre_recipe();
+      gcre_recipe* rcp = R.rcp = jp.res->rec;
+      if (!R.replay) rcp->valid = false;
+      const size_t rows = (size_t)R.P, lists = rows * (size_t)g.method;
+      hipError_t e = rcp->row0.reserve(rows + 64);
+      if (e == hipSuccess) e = rcp->rowz.reserve(rows + 64);
+      if (e == hipSuccess) e = rcp->linfo.reserve(lists + 64);
+      if (e == hipSuccess) e = rcp->lover.reserve(lists + 64);
+      if (e == hipSuccess) e = rcp->tot.reserve(lists + 64);
+      if (e == hipSuccess) e = rcp->slot.reserve(lists * 8 + 64);
+      if (e == hipSuccess) e = rcp->over.reserve(std::max<size_t>(rcp->over.cap, lists * 2 + ((size_t)1 << 26)));
+      if (e != hipSuccess) {
+        (void)hipGetLastError();
+        rcp->release();
+        R.rcp = nullptr;
+      } else {
+        // (sized for the nominal window: the same answer in every window of a run)
+        const size_t nkt_nom = (size_t)((std::max(c->win_K, c->win_K_nominal) + kSparseTile - 1) / kSparseTile);
+        const size_t nominal = (size_t)std::max<int64_t>(jp.res->nrows, 1) * g.method * nkt_nom * (size_t)out_groups * 1024;
+        want_out = nominal <= c->planes_out_max || R.use_rec || jp.res->planes_wanted;
       }
-      if (want_ie && keep) {
-        // carriers of a joined row <= carriers(paths0 row) + carriers(added row); <= padded patient count
-        const uint32_t bound = std::min<uint32_t>((uint32_t)(64 * g.Wp), row_max(c, jp.p0) + row_max(c, red));
-        const int out_groups = plane_groups_for(bound);
-        bool want_out = true;
-        {
-          // the kept rows leave with the recipe of this join (its inspector output: 60 B per row, 104 B for the signed
-          // method's two lists).  Their planes are only written when they are small, or when the next join could not use the
-          // recipe (it needs stored planes of paths0)
-          if (!jp.res->rec) jp.res->rec = new gcre_recipe();
-          rcp = jp.res->rec;
-          if (!replay) rcp->valid = false;
-          const size_t rows = (size_t)P, lists = rows * (size_t)g.method;
-          hipError_t e = rcp->row0.reserve(rows + 64);
-          if (e == hipSuccess) e = rcp->rowz.reserve(rows + 64);
-          if (e == hipSuccess) e = rcp->linfo.reserve(lists + 64);
-          if (e == hipSuccess) e = rcp->lover.reserve(lists + 64);
-          if (e == hipSuccess) e = rcp->tot.reserve(lists + 64);
-          if (e == hipSuccess) e = rcp->slot.reserve(lists * 8 + 64);
-          if (e == hipSuccess) e = rcp->over.reserve(std::max<size_t>(rcp->over.cap, lists * 2 + ((size_t)1 << 26)));
-          if (e != hipSuccess) {
-            (void)hipGetLastError();
-            rcp->release();
-            rcp = nullptr;
-          } else {
-            // (sized for the nominal window: the same answer in every window of a run)
-            const size_t nkt_nom = (size_t)((std::max(c->win_K, c->win_K_nominal) + kSparseTile - 1) / kSparseTile);
-            const size_t nominal = (size_t)std::max<int64_t>(jp.res->nrows, 1) * g.method * nkt_nom * (size_t)out_groups * 1024;
-            want_out = nominal <= c->planes_out_max || use_rec || jp.res->planes_wanted;
-          }
-        }
-        if (inspect_only) {
-          // (the join proper allocates -- or drops -- the kept rows' planes)
-        } else if (want_out) {
-          res_planes = alloc_planes(c, jp.res, out_groups);
-          res_planes_ok = res_planes;
-        } else {
-          drop_planes(jp.res);   // nothing stale stays behind
-        }
+      if (inspect_only) {
+        // (the join proper allocates -- or drops -- the kept rows' planes)
+      } else if (want_out) {
+        R.res_planes = alloc_planes(c, jp.res, out_groups);
+        R.res_planes_ok = R.res_planes;
+      } else {
+        drop_planes(jp.res);   // nothing stale stays behind
       }
     }
-    c->prof.prepare_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tp0).count();
-    auto queue_winners = [&](int64_t s0, uint32_t nsel, Winners& w, hipStream_t qs) -> int {
-      w.n = nsel;
-      if (nsel == 0) return GCRE_OK;
-      HIP_TRY(c, c->d_wkey.reserve(nsel));
-      HIP_TRY(c, c->d_wcases.reserve(nsel));
-      HIP_TRY(c, c->d_wctrls.reserve(nsel));
-      HIP_TRY(c, c->d_wrow0.reserve(nsel));
-      HIP_TRY(c, c->d_wrow1.reserve(nsel));
-      HIP_TRY(c, launch_gather_winners(c->d_sel.p, nsel, c->d_key.p + s0, c->d_cases.p + s0, c->d_ctrls.p + s0,
-                                       c->d_row0.p + s0, c->d_row1.p + s0, c->d_wkey.p, c->d_wcases.p, c->d_wctrls.p, c->d_wrow0.p,
-                                       c->d_wrow1.p, qs));
-      w.sel.resize(nsel); w.cases.resize(nsel); w.ctrls.resize(nsel); w.r0.resize(nsel); w.r1.resize(nsel); w.key.resize(nsel);
-      HIP_TRY(c, hipMemcpyAsync(w.sel.data(), c->d_sel.p, nsel * 4, hipMemcpyDeviceToHost, qs));
-      HIP_TRY(c, hipMemcpyAsync(w.key.data(), c->d_wkey.p, nsel * 8, hipMemcpyDeviceToHost, qs));
-      HIP_TRY(c, hipMemcpyAsync(w.cases.data(), c->d_wcases.p, nsel * 4, hipMemcpyDeviceToHost, qs));
-      HIP_TRY(c, hipMemcpyAsync(w.ctrls.data(), c->d_wctrls.p, nsel * 4, hipMemcpyDeviceToHost, qs));
-      HIP_TRY(c, hipMemcpyAsync(w.r0.data(), c->d_wrow0.p, nsel * 4, hipMemcpyDeviceToHost, qs));
-      HIP_TRY(c, hipMemcpyAsync(w.r1.data(), c->d_wrow1.p, nsel * 4, hipMemcpyDeviceToHost, qs));
-      return GCRE_OK;
-    };
-    // only the inclusion-exclusion kernels score part of a chunk; every other form gets chunks cut at the shard's ends
-    bool split = !(want_ie && g.K > 0);
-    for (const Seg& sg : segs) {
-      int64_t next = sg.b;
-      while (next < sg.e) {
-        const int64_t cb = next;
-        int64_t ce = std::min(cb + chunk_cap, sg.e);
-        if (split && cb < sg.sb) ce = std::min(ce, sg.sb);
-        else if (split && cb < sg.se) ce = std::min(ce, sg.se);
-        next = ce;
-        const int64_t n = ce - cb;
-        const int64_t s0 = std::min(std::max<int64_t>(sg.sb - cb, 0), n);       // scored paths of this chunk: [s0, s1)
-        const int64_t s1 = std::max(s0, std::min(std::max<int64_t>(sg.se - cb, 0), n));
-        const bool scored = s1 > s0;
-        const bool partial = scored && (s0 > 0 || s1 < n);
-        SelectState& sel_state = c->h_sel;
-        bool sel_begun = false, sel_done = false;
-        hipStream_t sel_on = st;   // the stream this chunk's selection runs on
-        Winners win;
-        const int64_t npt = (n + tile - 1) / tile;
-        const int64_t padded = npt * tile;
-        // inspection cache: this chunk's buffers stand in for the context's scratch while the chunk is worked on
-        ChunkInsp* ci = nullptr;
-        if (c->insp_cache) {
-          for (auto& e : u.insp)
-            if (e.cb == cb && e.n == n) ci = &e;
-          if (!ci) {
-            for (auto& e : u.insp)   // an entry of an earlier join on this index: its buffers serve this chunk
-              if (e.cb < 0) { ci = &e; break; }
-            if (!ci) { u.insp.emplace_back(); ci = &u.insp.back(); }
-            ci->inspected = ci->with_lists = ci->flags_valid = ci->win_valid = false;
-            ci->cb = cb;
-            ci->n = n;
-          }
-          if (ci->s0 != s0 || ci->s1 != s1) ci->win_valid = false;
-          ci->s0 = s0;
-          ci->s1 = s1;
-        }
-        InspSwap swapped(c, ci);
-        const bool use_ie_chunk = want_ie && (scored || res_planes || rcp != nullptr);
-        // replayed: the inspector's output is in place (rows, statistics, keys, kept rows, lists when this chunk wants them)
-        const bool hit = ci && replay && ci->inspected &&
-                         (!use_ie_chunk || (ci->with_lists && ci->flags_valid && ci->in_recipe == (rcp != nullptr)));
-        if (ci && !hit) ci->inspected = ci->with_lists = ci->flags_valid = ci->win_valid = false;
-        if (hit) c->prof.inspect_replays++;
-        // room for this chunk.  A replayed chunk's buffers hold what its inspector wrote: they may only grow with their
-        // contents (the path tile, and with it `cap` and the padding below, depends on the window's permutation count)
-        auto hold = [&](auto& buf, size_t want) -> hipError_t { return hit ? buf.grow_keep(want, buf.cap, st) : buf.reserve(want); };
-        HIP_TRY(c, hold(c->d_row0, cap));
-        HIP_TRY(c, hold(c->d_row1, cap));
-        HIP_TRY(c, hold(c->d_tot, cap * g.method));
-        HIP_TRY(c, hold(c->d_cases, cap));
-        HIP_TRY(c, hold(c->d_ctrls, cap));
-        HIP_TRY(c, hold(c->d_key, cap));
-        // the null kernel reads whole tiles: rows / totals beyond n must be valid (row 0, zero carriers)
-        const bool pad_now = padded > n && (!hit || padded > ci->padded);
-        if (ci) ci->padded = std::max(hit ? ci->padded : (int64_t)0, padded);
-        if (pad_now) {
-          HIP_TRY(c, hipMemsetAsync(c->d_row0.p + n, 0, (size_t)(padded - n) * 4, st));
-          HIP_TRY(c, hipMemsetAsync(c->d_row1.p + n, 0, (size_t)(padded - n) * 4, st));
-          HIP_TRY(c, hipMemsetAsync(c->d_tot.p + (size_t)n * g.method, 0, (size_t)(padded - n) * 4 * g.method, st));
-        }
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        if (!hit) {
-          e0 = get_event(c);
-          e1 = get_event(c);
-          HIP_TRY(c, hipEventRecord(e0, st));
-          HIP_TRY(c, launch_expand(u.d_path_idx, u.d_location, u.n_uids, u.d_signs, u.path_length, g.method,
-                                   cb, n, c->d_row0.p, c->d_row1.p, st));
-        }
-        StatsArgs sa{};
-        sa.p0 = jp.p0->d_rows;
-        sa.p1 = jp.p1->d_rows;
-        sa.row0 = c->d_row0.p;
-        sa.row1 = c->d_row1.p;
-        sa.case_mask = c->d_case_mask;
-        sa.dvt = c->d_dvt;
-        sa.key = c->d_key.p;
-        sa.tot = c->d_tot.p;
-        sa.cases = c->d_cases.p;
-        sa.ctrls = c->d_ctrls.p;
-        sa.res = keep ? jp.res->d_rows : nullptr;
-        sa.first = cb;
-        sa.count = n;
-        sa.S = g.S;
-        sa.Wp = g.Wp;
-        const bool use_ie = use_ie_chunk;
-        const bool use_sparse = scored && sparse_ok && !want_ie;
-        if (partial && !use_ie && g.K > 0) {   // the join left the inclusion-exclusion form on an earlier chunk
-          split = true;
-          next = cb;
-          continue;
-        }
-        if (use_sparse || use_ie) {
-          collect_ie_stat();
-          // flags of this chunk; the long-list counter (word 4) runs on across the chunks of a join that keeps a recipe
-          HIP_TRY(c, hipMemsetAsync(flagblk, 0, (rcp && recipe_started) ? 16 : 24, st));   // words 6, 7: the join's
-          // ... and word 4, the entries reserved so far in the recipe's overflow area, is the JOIN's, not the flag block's: a
-          // chunk replayed from the inspection cache never touched this block, and an ahead inspection ran on the other one
-          if (rcp) HIP_TRY(c, hipMemsetD32Async((hipDeviceptr_t)(flagblk + 4), (int)over_next, 1, st));
-          recipe_started = recipe_started || rcp != nullptr;
-          sa.max_tot = flagblk;
-          HIP_TRY(c, hold(c->d_dcnt, (size_t)n * g.method));
-          sa.dcnt = c->d_dcnt.p;
-        }
-        if (use_ie) {
-          // one pass: statistics, kept rows, the check of the reduced operand, and the lists the null kernel streams
-          const size_t nl = (size_t)n * g.method;
-          HIP_TRY(c, hold(c->d_rowz, cap));
-          HIP_TRY(c, hold(c->d_linfo, nl));
-          HIP_TRY(c, hold(c->d_lover, nl));
-          HIP_TRY(c, hold(c->d_dlist, nl * 8 + 16));
-          // + the waves' chunk slack: every wave of the inspector may leave most of a 2048-entry reservation unused
-          const size_t over_slack = (std::min<size_t>(16384, ((size_t)n + 15) / 16 * 4) + 2) * 2048;
-          HIP_TRY(c, hold(c->d_dover, std::max<size_t>(c->d_dover.cap, nl * 2 + over_slack)));
-          sa.pz = red->d_rows;
-          sa.zindex = hinted ? u.d_red_index : nullptr;
-          sa.excess = hinted ? (inspect_only ? c->d_excess_b.p : c->d_excess.p) : nullptr;
-          sa.range_of = hinted ? u.d_range_of : nullptr;
-          sa.bad = flagblk + 1;
-          sa.ie_bias = 8;
-          sa.ie_rule = g.method == 1 ? 1 : 0;   // the bound filter and the quad kernel want overlap lists
-          if (rcp) {   // straight into the recipe of the kept set (absolute row = cb + i)
-            sa.rowz = rcp->rowz.p + cb;
-            sa.linfo = rcp->linfo.p + (size_t)cb * g.method;
-            sa.lover = rcp->lover.p + (size_t)cb * g.method;
-            sa.slot = rcp->slot.p + (size_t)cb * g.method * 8;
-            sa.over = rcp->over.p;
-            sa.over_cap = (uint32_t)std::min<size_t>(rcp->over.cap - 16, 0xfffffff0u);
-            if (!hit) HIP_TRY(c, hipMemcpyAsync(rcp->row0.p + cb, c->d_row0.p, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
-          } else {
-            sa.rowz = c->d_rowz.p;
-            sa.linfo = c->d_linfo.p;
-            sa.lover = c->d_lover.p;
-            sa.slot = c->d_dlist.p;
-            sa.over = c->d_dover.p;
-            sa.over_cap = (uint32_t)std::min<size_t>(c->d_dover.cap - 16, 0xfffffff0u);
-          }
-          sa.ov_count = flagblk + 4;
-          sa.zoff = (uint32_t)(64 * g.Wp) << 8;
-          if (g.method == 2 && one_sided(red)) sa.lz_off = red->d_loff;   // one round per path instead of one per half
-          if (!hit) HIP_TRY(c, launch_stats_ie(sa, g.method, st));
-          // a kept row's carrier total bounds every count of it: the next level loads only the plane groups that can be non-zero
-          if (rcp && !hit) HIP_TRY(c, hipMemcpyAsync(rcp->tot.p + (size_t)cb * g.method, c->d_tot.p, (size_t)n * g.method * 4, hipMemcpyDeviceToDevice, st));
-        } else if (!hit) {
-          HIP_TRY(c, launch_stats(sa, g.method, st));
-        }
-        if (!hit) {
-          HIP_TRY(c, hipEventRecord(e1, st));
-          if (!inspect_only) HIP_TRY(c, hipEventRecord(c->ev_insp_main, st));
-          c->ev_stats.emplace_back(e0, e1);
-          if (ci) {
-            ci->inspected = true;
-            ci->with_lists = use_ie;
-            ci->in_recipe = use_ie && rcp != nullptr;
-          }
-        }
-        bool win_from_cache = false;
-        if (hit && ci->win_valid && scored) {   // the chunk's top-k does not depend on the masks either
-          win = ci->win;
-          sel_done = true;
-          win_from_cache = true;
-        }
-        // the top-k selection only needs the keys the inspector just wrote: its digit passes run now, their state
-        // comes back with the inspector's flags, its winners are collected before the null kernel starts
-        if (use_ie && g.K > 0 && scored && !sel_done) {
-          if (c->sel_async) {   // beside the warm-up slice and the null kernel, behind the inspector
-            HIP_TRY(c, hipEventRecord(c->ev_sel, st));
-            HIP_TRY(c, hipStreamWaitEvent(c->sel_stream, c->ev_sel, 0));
-            sel_on = c->sel_stream;
-          }
-          if (int rc = select_begin(c, s0, s1 - s0, c->top_k, &sel_state, sel_on)) return rc;
-          sel_begun = true;
-        }
-        if (!scored && !(use_ie && g.K > 0)) continue;
+  }
+  R.prof->prepare_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tp0).count();
+  // only the inclusion-exclusion kernels score part of a chunk; every other form gets chunks cut at the shard's ends
+  R.split = !(R.want_ie && g.K > 0);
+  return GCRE_OK;
+}
 
-        bool ran_sparse = false, redo = false;
-        if (g.K > 0 && use_ie) do {
-          const auto ti0 = std::chrono::steady_clock::now();
-          const uint32_t zoff = (uint32_t)(64 * g.Wp) << 8;
-          const int64_t nl = n * g.method;
-          uint32_t flags[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // max carriers, hint broken, overlap lists, -, long-list entries
-          if (hit) {
-            std::memcpy(flags, ci->flags, sizeof flags);   // as the inspector left them (no round trip)
-          } else {
-            HIP_TRY(c, hipMemcpyAsync(flags, flagblk, 32, hipMemcpyDeviceToHost, st));
-            HIP_TRY(c, hipStreamSynchronize(st));
-          }
-          if ((size_t)flags[4] + 16 > (rcp ? rcp->over.cap : c->d_dover.cap)) {
-            // more long lists than the area holds: size it from what the pass asked for, run the chunk again (a recipe
-            // keeps what the earlier chunks wrote; the failed attempt's reservation is simply left unused)
-            const size_t want = (size_t)flags[4] + (size_t)flags[4] / 4 + ((size_t)1 << 24);
-            if (rcp) HIP_TRY(c, rcp->over.grow_keep(want, rcp->over.cap, st));
-            else HIP_TRY(c, c->d_dover.reserve(want));
-            redo = true;
-            if (ci) ci->inspected = false;
-            break;
-          }
-          const uint64_t n_list = (uint64_t)nl * 8 + flags[4];
-          if (rcp) over_next = std::max(over_next, flags[4]);
-          const uint32_t max_tot = flags[0];
-          join_max_tot = std::max(join_max_tot, max_tot);
-          join_max_len = std::max(join_max_len, flags[5]);
-          if (flags[1] != 0 || (hinted && flags[6] != 0)) {
-            // the hint does not describe this join: run it on paths1 itself (identity map) from this chunk on
-            if (!hinted) return fail(c, GCRE_ERR_DEVICE, "internal: joined path differs from paths0 | paths1");
-            hinted = false;
-            if (int rc = prepare_z()) return rc;
-            if (!have_pz) want_ie = false;
-            // the kept rows' planes were sized for the reduced rows: rows of paths1 may carry more
-            if (res_planes && plane_groups_for(std::min<uint32_t>((uint32_t)(64 * g.Wp), row_max(c, jp.p0) + row_max(c, red))) >
-                                  jp.res->plane_groups) {
-              res_planes = false;
-              res_planes_ok = false;
-            }
-            if (cb > sg.b || &sg != &segs.front()) recipe_broken = true;   // earlier chunks added rows of another set
-            if (cb > sg.b || &sg != &segs.front()) hint_broke_late = true;
-            redo = true;
-            if (ci) ci->inspected = false;
-            break;
-          }
-          if (ci && !hit) {
-            std::memcpy(ci->flags, flags, sizeof flags);
-            ci->flags_valid = true;
-          }
-          if (inspect_only) {   // nothing of the permutation kernel's; the chunk's winners are collected below
-            join_max_tot = std::max(join_max_tot, flags[0]);
-            if (sel_begun && scored && !sel_done) {
-              HIP_TRY(c, hipStreamSynchronize(sel_on));
-              uint32_t nsel = 0;
-              if (int rc = select_finish(c, s0, s1 - s0, c->top_k, sel_state, &nsel, sel_on)) return rc;
-              if (int rc = queue_winners(s0, nsel, win, sel_on)) return rc;
-              sel_done = true;
-            }
-            ran_sparse = true;
-            break;
-          }
-          const int64_t nseg_est = std::max<int64_t>(uids_in(cb, n), 1);
-          if (c->null_kernel == 0 && scored) {
-            // auto: dense bit vectors (or tiny K) are cheaper on the AND+BCNT kernel (DESIGN.md "Kernel choice")
-            const double base = have_p0 ? 0.0 : (double)row_max(c, jp.p0) * g.method * (double)nseg_est / (double)n;
-            const double entries = (double)n_list / (double)n + base + 10.0 * g.method;
-            const double ie_cost = entries * nkt_sp * 15.0;
-            const double dense_cost = 2.0 * g.Wp * g.method * (double)g.K * 2.0 / 65.0;
-            if (ie_cost >= dense_cost) { res_planes_ok = false; break; }
-          }
-          if (!scored && !(res_planes && cb < pl_e && cb + n > pl_b)) {   // rows of another shard that only needed their recipe entries
-            ran_sparse = true;
-            break;
-          }
-          int planes = 5;
-          while (planes < 16 && (max_tot >> planes) != 0) planes++;
-          IeArgs ia{};
-          int64_t nseg_scored = 0;
-          gcre_uids::SegCache* seg_entry = nullptr;
-          if (int rc = sparse_segments(c, u, cb, n, cb + s0, cb + s1, res_planes ? pl_b : cb + s0, res_planes ? pl_e : cb + s1,
-                                       &ia.segs, &ia.nsegs, &nseg_scored, &seg_entry))
-            return rc;
-          ia.mt = w_mt;
-          ia.tot = c->d_tot.p;
-          ia.rowz = rcp ? rcp->rowz.p + cb : c->d_rowz.p;
-          ia.planes0 = (have_p0 && !use_rec) ? jp.p0->d_planes : nullptr;
-          ia.g0 = (have_p0 && !use_rec) ? jp.p0->plane_groups : 0;
-          ia.planesz = have_pz ? red->d_planes : nullptr;
-          ia.gz = have_pz ? red->plane_groups : 0;
-          ia.rows0 = (uint32_t)(jp.p0->nrows * g.method);
-          ia.rowsz = (uint32_t)(red->nrows * g.method);
-          ia.rows_out = res_planes ? (uint32_t)(jp.res->nrows * g.method) : 0u;
-          ia.loff0 = jp.p0->d_loff;
-          ia.lidx0 = jp.p0->d_lidx;
-          ia.linfo = rcp ? rcp->linfo.p + (size_t)cb * g.method : c->d_linfo.p;
-          ia.lover = rcp ? rcp->lover.p + (size_t)cb * g.method : c->d_lover.p;
-          ia.dlist = rcp ? rcp->slot.p + (size_t)cb * g.method * 8 : c->d_dlist.p;
-          ia.dover = rcp ? rcp->over.p : c->d_dover.p;
-          if (use_rec) {
-            const gcre_recipe* r0 = jp.p0->rec;
-            ia.rec_row0 = r0->row0.p;
-            ia.rec_rowz = r0->rowz.p;
-            ia.rec_linfo = r0->linfo.p;
-            ia.rec_lover = r0->lover.p;
-            ia.rec_slot = r0->slot.p;
-            ia.rec_over = r0->over.p;
-            ia.rec_planes_a = rec_a->d_planes;
-            ia.rec_planes_z = rec_z->d_planes;
-            ia.rec_rows_a = (uint32_t)(rec_a->nrows * g.method);   // row-halves
-            ia.rec_rows_z = (uint32_t)(rec_z->nrows * g.method);
-            ia.rec_ga = rec_a->plane_groups;
-            ia.rec_gz = rec_z->plane_groups;
-            if (g.method == 1) {
-              // the recipe entries of every segment's row, next to the segment table (no load depends on row0 any more)
-              HIP_TRY(c, c->d_rec_segs.reserve((size_t)std::max<int64_t>(ia.nsegs, 1) * kRecSegWords));
-              HIP_TRY(c, launch_fill_rec_segs(ia.segs, ia.nsegs, r0->row0.p, r0->rowz.p, r0->linfo.p, r0->lover.p, r0->slot.p, r0->tot.p,
-                                              c->d_rec_segs.p, st));
-              ia.rec_segs = c->d_rec_segs.p;
-            }
-          }
-          ia.t32 = c->d_t32;
-          ia.d64 = c->d_dmax;
-          ia.ladder = c->d_ladder;
-          ia.ladder_stride = g.TD;
-          ia.lad_mode = !scored ? 1 : (c->ie_prune ? 0 : 2);
-          ia.g00_rows = c->g00_rows;
-          ia.null_bits = w_null;
-          ia.planes_out = res_planes ? jp.res->d_planes : nullptr;
-          ia.go = res_planes ? jp.res->plane_groups : 0;
-          ia.out_first = cb;
-          ia.score_begin = (uint32_t)s0;
-          ia.score_end = (uint32_t)s1;
-          ia.score_segs = (uint32_t)nseg_scored;
-          ia.nkt = nkt_sp;
-          ia.K = g.K;
-          ia.mt_rows = (uint32_t)(64 * g.Wp + 1);
-          ia.zoff = zoff;
-          c->prof.null_row_loads += ((have_p0 ? 0.0 : (double)row_max(c, jp.p0) * g.method * (double)nseg_est) + (double)n_list) * nkt_sp;
-          int dev_cus = 256;
-          (void)hipDeviceGetAttribute(&dev_cus, hipDeviceAttributeMultiprocessorCount, c->device);
-          const int wpc = std::min(c->sparse_waves_per_cu, ie_max_waves_per_cu(g.method, planes, ia.gz, ia.planes_out != nullptr, ia.rec_slot != nullptr));
-          ia.waves_per_xcd = std::max(4, (dev_cus * wpc / 8 / 4) * 4);
-          // small joins: a wave's fixed costs (cold TLB and caches, LDS set-up, threshold exchange) are per tile it
-          // visits, so give every wave at least ~32 joined paths of a tile -- counting the tiles a queue can hold whole
-          // (a wave walks a contiguous piece of the tile-major sequence)
-          const int64_t ie_tile_factor = std::min(std::max(nkt_sp * c->ie_small_join_tiles / 8, 1), nkt_sp);
-          while (ia.waves_per_xcd > 4 && n * ie_tile_factor < (int64_t)8 * ia.waves_per_xcd * 32)
-            ia.waves_per_xcd = std::max(4, (ia.waves_per_xcd / 2 / 4) * 4);
-          c->prof.inspect_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ti0).count();
-          ia.stats = launch_only ? w_null + Kpad : flagblk + 3;   // 4th word of the flag block: zeroed with it before k_stats ran
-          static uint64_t* d_timing = nullptr;   // diagnostics builds only (-DGCRE_IE_TIMING), GCRE_IE_TIMING=1
-          const bool timing = std::getenv("GCRE_IE_TIMING") != nullptr;
-          if (timing) {
-            if (!d_timing) HIP_TRY(c, hipMalloc((void**)&d_timing, 64));
-            HIP_TRY(c, hipMemsetAsync(d_timing, 0, 64, st));
-            ia.timing = d_timing;
-          }
-          if (sel_begun && scored && sel_on == st) {   // (its state came back with the flags)
-            uint32_t nsel = 0;
-            if (int rc = select_finish(c, s0, s1 - s0, c->top_k, sel_state, &nsel, st)) return rc;
-            if (int rc = queue_winners(s0, nsel, win, st)) return rc;
-            sel_done = true;
-          }
-          hipEvent_t n0 = get_event(c), n1 = get_event(c);
-          bool ie_quad_ran = false;
-          HIP_TRY(c, hipEventRecord(n0, st));
-          ia.seg_begin = 0;
-          ia.seg_end = ia.nsegs;
-          if (c->d_ladder && ia.lad_mode == 0) {
-            // warm-up: the first segments are scored without pruning (every count looked up, general kernel); what
-            // they find seeds the thresholds the pruned kernel starts from.  Joins of a few thousand paths run here whole.
-            // (the scored segments lead the table.)  The general kernel is several times slower per path: a short
-            // shard gives it an eighth of its segments, not all of them.
-            // every tile warms up on its own permutations: with many tiles the slice gets shorter (its cost is per tile)
-            int64_t n_warm = warm_segments(c, nseg_scored, nkt_sp);
-            // maxima shared with the other devices right after the warm-up: every device warms its share of the slice
-            if (jp.exchange && exchanges_done < jp.exchanges && P > 0)
-              n_warm = std::min(n_warm, std::max<int64_t>(64, (int64_t)((double)n_warm * (double)(se - sb) / (double)P) + 1));
-            if (c->ie_warm_segs == 0) n_warm = 0;   // GCRE_IE_WARM=0 (tests): everything through the pruned kernel, thresholds from 0
-            IeArgs wa = ia;
-            wa.seg_end = n_warm;
-            // a wave walks its tiles one after the other: keep enough waves that each gets about four (segment, tile) items
-            while (wa.waves_per_xcd > 4 && n_warm * nkt_sp < (int64_t)8 * wa.waves_per_xcd * c->ie_warm_items)
-              wa.waves_per_xcd = std::max(4, (wa.waves_per_xcd / 2 / 4) * 4);
-            if (n_warm > 0) HIP_TRY(c, launch_null_ie(wa, g.method, planes, true, st));
-            ia.seg_begin = n_warm;
-          }
-          if (ia.seg_begin < ia.seg_end) {
-            ia.queue = c->d_queue;
-            ia.batch = c->ie_batch;
-            // method 1, no plane output: the quad form (gcre_ieq.hip) wherever segments come in groups that join the same
-            // paths1 rows -- every level but the one whose uids are the genes themselves (one uid per pivot)
-            bool quad = false;
-            if (g.method == 1 && c->d_ladder && c->ie_quad && !ia.planes_out && seg_entry &&
-                ensure_quads(c, u, *seg_entry, ia.seg_begin) == GCRE_OK) {
-              const int64_t nq = seg_entry->nquads - seg_entry->quad_begin;
-              // worth it from 1 + (qmax - 1) / 4 segments per quad on average: 1.25 with two segments per quad (a quad of one
-              // segment does what k_null_ie_m1 does with a longer prologue); the 1.5 of the four-segment form could never be
-              // reached by joins that average 1.3-1.5
-              const int64_t qmax = ieq_quad_segs();
-              quad = nq > 0 && ((ia.seg_end - ia.seg_begin) * 4 >= nq * (4 + (qmax - 1)) || c->ie_quad == 2);
-              if (std::getenv("GCRE_HOST_TIMING"))
-                std::fprintf(stderr, "[host] quads: %lld segments in %lld quads (%.2f per quad), %lld joined paths, quad form %s\n",
-                             (long long)(ia.seg_end - ia.seg_begin), (long long)nq, (double)(ia.seg_end - ia.seg_begin) / (double)std::max<int64_t>(nq, 1),
-                             (long long)n, quad ? "on" : "off");
-              if (quad) {
-                ia.quads = seg_entry->d_quads;
-                ia.quad_begin = seg_entry->quad_begin;
-                ia.quad_end = seg_entry->nquads;
-                ia.batch = c->ieq_batch > 0 ? c->ieq_batch : std::max(1, c->ie_batch * 2);   // quads per ticket: the headers of a ticket's quads are fetched one ahead
-                const int wq = std::min(c->sparse_waves_per_cu, ieq_max_waves_per_cu(planes, ia.gz, ia.rec_slot != nullptr));
-                ia.waves_per_xcd = std::max(4, (dev_cus * wq / 8 / 4) * 4);
-                while (ia.waves_per_xcd > 4 && n * ie_tile_factor < (int64_t)8 * ia.waves_per_xcd * 128)
-                  ia.waves_per_xcd = std::max(4, (ia.waves_per_xcd / 2 / 4) * 4);
-              }
-            }
-            // tickets are 32-bit: (batches per tile) x tiles must stay below 2^32
-            while (((ia.nsegs - ia.seg_begin) / ia.batch + 1) * (int64_t)ia.nkt > (int64_t)0xf0000000ll) ia.batch *= 2;
-            // One launch -- or, when the maxima are shared with other devices as the join goes (gcre_join_opts.exchange),
-            // E slices with an exchange before each, so that the thresholds of a shard follow the whole level's maxima: the
-            // first slices double (1/2^k of the head), the last m = exchange_tail are equal steps 1/(m+1) of the range.
-            // Measured at 8 ranks on configs[3]: equal steps at the end and up to 16 exchanges halve the
-            // look-ups once more but every slice is a launch that starts cold -- doubling slices alone (m = 0) stay best.
-            const bool pruned = c->d_ladder && ia.lad_mode == 0;
-            const int n_slices = (pruned && jp.exchange) ? std::max(1, jp.exchanges - exchanges_done) : 1;
-            const int64_t r_b = quad ? ia.quad_begin : ia.seg_begin, r_e = quad ? ia.quad_end : ia.seg_end;
-            int64_t lo = r_b;
-            for (int sl = 0; sl < n_slices && lo < r_e; sl++) {
-              int64_t hi = r_e;
-              if (sl + 1 < n_slices) {
-                const int m = std::min(n_slices - 1, c->exchange_tail < 0 ? n_slices / 2 : c->exchange_tail), head = n_slices - m;
-                const double end = sl >= head ? (double)(sl - head + 2) / (double)(m + 1) : std::ldexp(1.0 / (double)(m + 1), -(head - 1 - sl));
-                hi = std::min(r_e, std::max(lo + 1, r_b + (int64_t)((double)(r_e - r_b) * end)));
-              }
-              if (pruned && jp.exchange)
-                if (int rc = exchange_now()) return rc;
-              IeArgs sa2 = ia;
-              if (quad) { sa2.quad_begin = lo; sa2.quad_end = hi; }
-              else { sa2.seg_begin = lo; sa2.seg_end = hi; }
-              HIP_TRY(c, hipMemsetAsync(sa2.queue, 0, 8 * 16 * 4, st));
-              if (quad) HIP_TRY(c, launch_null_ie_quad(sa2, planes, st));
-              else HIP_TRY(c, launch_null_ie(sa2, g.method, planes, c->d_ladder == nullptr, st));
-              lo = hi;
-            }
-            if (quad) c->prof.ie_quad_launches++;
-            ie_quad_ran = quad;
-          }
-          HIP_TRY(c, hipEventRecord(n1, st));
-          if (sel_begun && scored && !sel_done) {   // own stream: the digit passes ran beside the warm-up slice
-            const auto tw0 = std::chrono::steady_clock::now();
-            HIP_TRY(c, hipStreamSynchronize(sel_on));
-            select_wait_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tw0).count();
-            uint32_t nsel = 0;
-            if (int rc = select_finish(c, s0, s1 - s0, c->top_k, sel_state, &nsel, sel_on)) return rc;
-            if (int rc = queue_winners(s0, nsel, win, sel_on)) return rc;
-            sel_done = true;
-          }
-          if (timing && !launch_only) {
-            uint64_t tmv[8] = {0};
-            HIP_TRY(c, hipMemcpyAsync(tmv, d_timing, 64, hipMemcpyDeviceToHost, st));
-            HIP_TRY(c, hipStreamSynchronize(st));
-            const double waves = 8.0 * ia.waves_per_xcd;
-            if (g.method == 2)
-              std::fprintf(stderr, "[ie2 classes] paths %lld x %d tiles: path-tiles with the other half empty %llu, one test %llu, all steps %llu, both halves %llu; "
-                           "lists of 5-8 rows %llu, long lists %llu; permutations looked up %llu\n", (long long)n, ia.nkt, (unsigned long long)tmv[0],
-                           (unsigned long long)tmv[1], (unsigned long long)tmv[2], (unsigned long long)tmv[3], (unsigned long long)tmv[4],
-                           (unsigned long long)tmv[6], (unsigned long long)tmv[5]);
-            else if (ie_quad_ran)
-              std::fprintf(stderr, "[ieq timing] paths %lld waves %.0f quads/wave %.0f: per-wave Mcycles header+loads %.2f base counters %.2f intervals %.2f filter pass %.2f exact pass %.2f exchange %.2f total %.2f\n",
-                           (long long)n, waves, tmv[7] / waves, tmv[0] / waves / 1e6, tmv[1] / waves / 1e6, tmv[2] / waves / 1e6, tmv[3] / waves / 1e6,
-                           tmv[4] / waves / 1e6, tmv[5] / waves / 1e6, tmv[6] / waves / 1e6);
-            else
-            std::fprintf(stderr, "[ie filter] uncertain path-tiles %llu of %lld x %d tiles, lanes that fetched rows %llu\n",
-                         (unsigned long long)tmv[1], (long long)n, ia.nkt, (unsigned long long)tmv[3]);
-            std::fprintf(stderr, "[ie timing] paths %lld out %d waves %.0f: per-wave Mcycles seg %.2f load %.2f comp(incl load) %.2f lookup %.2f exch %.2f total %.2f, slowest wave %.2f\n",
-                         (long long)n, ia.planes_out != nullptr, waves, tmv[0] / waves / 1e6, tmv[1] / waves / 1e6,
-                         tmv[2] / waves / 1e6, tmv[3] / waves / 1e6, tmv[4] / waves / 1e6, tmv[5] / waves / 1e6, tmv[6] / 1e6);
-          }
-          c->ev_null.emplace_back(n0, n1);
-          if (scored) {
-            c->prof.null_kernel_launches++;
-            c->prof.null_alg_bytes += alg_bytes(cb + s0, s1 - s0);
-          }
-          c->prof.ie_launches++;
-          c->prof.ie_overlap_lists += flags[2];
-          ie_stat_pending = true;
-          ie_ran = true;
-          ran_sparse = true;
-        } while (false);
-        if (redo) {
-          // the abandoned digit passes may still be reading the keys the relaunched inspector is about to rewrite
-          if (sel_begun && sel_on != st) {
-            HIP_TRY(c, hipEventRecord(c->ev_sel_done, sel_on));
-            HIP_TRY(c, hipStreamWaitEvent(st, c->ev_sel_done, 0));
-          }
-          next = cb;   // same chunk again, now against paths1 itself
-          continue;
-        }
-        if (partial && g.K > 0 && !ran_sparse) {   // priced out of the inclusion-exclusion form: the other kernels score whole chunks
-          split = true;
-          next = cb;
-          continue;
-        }
-        if (!scored) continue;
-
-        if (g.K > 0 && use_sparse && inspect_only && ci) {
-          // the delta-streaming road sizes its counters from the inspector's flag block: an ahead inspection reads it now and
-          // leaves it with the chunk (the launch that replays the chunk finds the block cleared)
-          uint32_t flags[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-          HIP_TRY(c, hipMemcpyAsync(flags, flagblk, 32, hipMemcpyDeviceToHost, st));
-          HIP_TRY(c, hipStreamSynchronize(st));
-          std::memcpy(ci->flags, flags, sizeof flags);
-          ci->flags_valid = true;
-        }
-        if (g.K > 0 && use_sparse && !inspect_only) do {
-          // inspector (once per chunk, shared by all permutation tiles): per joined path the bits paths1 adds
-          // on top of paths0 -> offsets by a device scan of the counts k_stats left, entries by k_delta_fill
-          if (int rc = ensure_lists(c, jp.p0)) return rc;
-          if (int rc = ensure_lists(c, jp.p1)) return rc;
-          const uint32_t zoff = (uint32_t)(64 * g.Wp) << 8;
-          const int64_t nl = n * g.method;   // delta lists: one per joined path and half
-          HIP_TRY(c, c->d_doff.reserve((size_t)nl + 1));
-          HIP_TRY(c, c->d_scan.reserve((size_t)(nl + 1023) / 1024 + 2));
-          HIP_TRY(c, launch_scan_u32_u64(c->d_dcnt.p, nl, c->d_doff.p, c->d_scan.p, st));
-          uint32_t max_tot = 0;
-          uint64_t n_delta = 0;
-          HIP_TRY(c, hipMemcpyAsync(&max_tot, flagblk, 4, hipMemcpyDeviceToHost, st));
-          HIP_TRY(c, hipMemcpyAsync(&n_delta, c->d_doff.p + nl, 8, hipMemcpyDeviceToHost, st));
-          HIP_TRY(c, hipStreamSynchronize(st));
-          if (hit) max_tot = ci->flags[0];   // the flag block was cleared for this window; the inspector's value was kept
-          else if (ci) { ci->flags[0] = max_tot; ci->flags_valid = true; }
-          if (c->null_kernel == 0) {
-            // auto: price both forms for this chunk (DESIGN.md "Kernel choice").  Sparse: one mask-row load per list
-            // entry per 2048-permutation tile at ~15 CU-cycles each; dense: 2 VALU ops per dword per permutation at
-            // ~65 lane-ops/clk/CU.  Base lists are bounded by the largest carrier total, once per segment.
-            const int64_t nseg_est = std::max<int64_t>(uids_in(cb, n), 1);
-            const double entries = (double)n_delta / (double)n + (double)max_tot * g.method * (double)nseg_est / (double)n;
-            const double sparse_cost = entries * ((g.K + kSparseTile - 1) / kSparseTile) * 15.0;
-            const double dense_cost = 2.0 * g.Wp * g.method * (double)g.K * 2.0 / 65.0;
-            if (sparse_cost >= dense_cost) break;   // dense kernel below
-          }
-          if (ci) ci->with_lists = false;   // the delta lists below take the place of the inspector's
-          HIP_TRY(c, c->d_dlist.reserve((size_t)n_delta + 16));
-          HIP_TRY(c, launch_delta_fill((const uint32_t*)jp.p0->d_rows, 2 * g.S, 2 * g.Wp, g.method, c->d_row0.p,
-                                       c->d_row1.p, n, jp.p1->d_loff, jp.p1->d_lidx, c->d_doff.p, zoff,
-                                       c->d_dlist.p, st));
-          int planes = 5;
-          while (planes < 16 && (max_tot >> planes) != 0) planes++;
-          SparseArgs sp{};
-          int64_t nseg_scored = 0;
-          if (int rc = sparse_segments(c, u, cb, n, cb, cb + n, cb, cb + n, &sp.segs, &sp.nsegs, &nseg_scored)) return rc;
-          sp.mt = w_mt;
-          sp.tot = c->d_tot.p;
-          sp.loff0 = jp.p0->d_loff;
-          sp.lidx0 = jp.p0->d_lidx;
-          sp.doff = c->d_doff.p;
-          sp.dlist = c->d_dlist.p;
-          sp.t32 = c->d_t32;
-          sp.d64 = c->d_dmax;
-          sp.null_bits = w_null;
-          sp.nkt = (g.K + kSparseTile - 1) / kSparseTile;
-          sp.mt_rows = (uint32_t)(64 * g.Wp + 1);
-          sp.zoff = zoff;
-          {
-            // mask-row loads of this launch: every segment walks its paths0 list(s) once, every joined path its
-            // delta list(s), for each permutation tile
-            const auto& pi = u.h_path_idx;
-            const auto& lo = jp.p0->h_loff;
-            double base_entries = 0;
-            int64_t i = std::upper_bound(pi.begin(), pi.end(), cb) - pi.begin() - 1;
-            for (; i < u.n_uids && pi[(size_t)i] < cb + n; i++) {
-              const int64_t a0 = std::max(pi[(size_t)i], cb), a1 = std::min(pi[(size_t)i + 1], cb + n);
-              if (a1 <= a0) continue;
-              const double segs_here = (double)((a1 - a0 + kSparseSegMax - 1) / kSparseSegMax);
-              base_entries += segs_here * (double)(lo[(size_t)(i + 1) * g.method] - lo[(size_t)i * g.method]);
-            }
-            c->prof.null_row_loads += (base_entries + (double)n_delta) * sp.nkt;
-          }
-          int dev_cus = 256;
-          (void)hipDeviceGetAttribute(&dev_cus, hipDeviceAttributeMultiprocessorCount, c->device);
-          if (const char* e = std::getenv("GCRE_SPARSE_ABLATE")) sp.ablate = std::atoi(e);
-          const int wpc = std::min(c->sparse_waves_per_cu, sparse_max_waves_per_cu(g.method, planes));
-          sp.waves_per_xcd = std::max(4, (dev_cus * wpc / 8 / 4) * 4);
-          hipEvent_t n0 = get_event(c), n1 = get_event(c);
-          HIP_TRY(c, hipEventRecord(n0, st));
-          HIP_TRY(c, launch_null_sparse(sp, g.method, planes, st));
-          HIP_TRY(c, hipEventRecord(n1, st));
-          c->ev_null.emplace_back(n0, n1);
-          c->prof.null_kernel_launches++;
-          c->prof.null_alg_bytes += alg_bytes(cb, n);
-          ran_sparse = true;
-        } while (false);
-        if (g.K > 0 && !ran_sparse && !inspect_only) {
-          NullArgs na{};
-          na.p0 = (const uint32_t*)jp.p0->d_rows;
-          na.p1 = (const uint32_t*)jp.p1->d_rows;
-          na.masks = w_masks;
-          na.row0 = c->d_row0.p;
-          na.row1 = c->d_row1.p;
-          na.tot = c->d_tot.p;
-          na.t32 = c->d_t32;
-          na.d64 = c->d_dmax;
-          na.null_bits = w_null;
-          na.npaths = n;
-          na.npt = npt;
-          na.S32 = 2 * g.S;
-          na.W32p = 2 * g.Wp;
-          na.Kpad = Kstride;
-          na.nkt = (g.K + cfg.perm_tile - 1) / cfg.perm_tile;
-          int dev_cus = 256;
-          (void)hipDeviceGetAttribute(&dev_cus, hipDeviceAttributeMultiprocessorCount, c->device);
-          const int64_t want = (int64_t)dev_cus * c->null_blocks_per_cu;
-          int64_t groups = std::max<int64_t>(1, want / na.nkt);
-          groups = std::min<int64_t>(groups, npt);
-          na.pgroups = (int)groups;
-          hipEvent_t n0 = get_event(c), n1 = get_event(c);
-          HIP_TRY(c, hipEventRecord(n0, st));
-          HIP_TRY(c, launch_null(na, g.method, cfg, st));
-          HIP_TRY(c, hipEventRecord(n1, st));
-          c->ev_null.emplace_back(n0, n1);
-          c->prof.null_kernel_launches++;
-          c->prof.null_alg_bytes += alg_bytes(cb, n);
-        }
-
-        // ---- top-k of this chunk ----
-        const auto ts0 = std::chrono::steady_clock::now();
-        if (!sel_done) {
-          uint32_t nsel = 0;
-          if (sel_begun) {   // begun, then the chunk left the inclusion-exclusion road: its state is still good
-            HIP_TRY(c, hipStreamSynchronize(sel_on));
-            if (int rc = select_finish(c, s0, s1 - s0, c->top_k, sel_state, &nsel, sel_on)) return rc;
-          } else {
-            if (c->sel_stream) HIP_TRY(c, hipStreamSynchronize(c->sel_stream));   // an abandoned selection shares the scratch
-            int rc = select_chunk(c, s0, s1 - s0, c->top_k, &nsel, st);
-            if (rc != GCRE_OK) return rc;
-          }
-          if (int rc2 = queue_winners(s0, nsel, win, sel_on)) return rc2;
-          // whatever still runs on the selection stream reads this chunk's keys and rows: the next chunk's inspector (on the
-          // main stream) rewrites them, so it queues behind an event -- not behind "the results are discarded anyway"
-          if (sel_on != st) {
-            HIP_TRY(c, hipEventRecord(c->ev_sel_done, sel_on));
-            HIP_TRY(c, hipStreamWaitEvent(st, c->ev_sel_done, 0));
-          }
-        }
-        if (win.n > 0) {
-          const auto tw0 = std::chrono::steady_clock::now();
-          if (!win_from_cache) {   // (cached winners are host data: nothing to wait for)
-            if (sel_on != st) HIP_TRY(c, hipStreamSynchronize(sel_on));
-            HIP_TRY(c, hipStreamSynchronize(st));   // the null kernel of this chunk: its time is not the selection's
-          }
-          select_wait_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tw0).count();
-          for (uint32_t i = 0; i < win.n; i++)
-            cands.push_back(Candidate{key_to_score(win.key[i]), cb + s0 + (int64_t)win.sel[i], (int32_t)win.r0[i], (int32_t)win.r1[i],
-                                      (int32_t)win.cases[i], (int32_t)win.ctrls[i]});
-        }
-        if (ci && !ci->win_valid) {   // (its copies have arrived: the stream was waited for above)
-          ci->win = win;
-          ci->win_valid = true;
-        }
-        select_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ts0).count();
-        if (!inspect_only) c->prof.paths += s1 - s0;   // (a launch books them on its own profile: prof_swap)
-      }
+// The chunk [cb, ce) of segment sg: what it scores, its inspection-cache entry, its buffers and their padding
+int open_chunk(JoinRun& R, ChunkRun& C, const Seg& sg, int64_t cb, int64_t ce) {
+  gcre_ctx* c = R.c;
+  const gcre_uids& u = *R.u;
+  const int64_t n = ce - cb;
+  C.sg = &sg;
+  C.cb = cb;
+  C.n = n;
+  C.s0 = std::min(std::max<int64_t>(sg.sb - cb, 0), n);
+  C.s1 = std::max(C.s0, std::min(std::max<int64_t>(sg.se - cb, 0), n));
+  C.scored = C.s1 > C.s0;
+  C.partial = C.scored && (C.s0 > 0 || C.s1 < n);
+  C.sel_on = R.st;
+  C.npt = (n + R.tile - 1) / R.tile;
+  C.padded = C.npt * R.tile;
+  if (c->insp_cache) {
+    ChunkInsp*& ci = C.ci;
+    for (auto& e : u.insp)
+      if (e.cb == cb && e.n == n) ci = &e;
+    if (!ci) {
+      for (auto& e : u.insp)   // an entry of an earlier join on this index: its buffers serve this chunk
+        if (e.cb < 0) { ci = &e; break; }
+      if (!ci) { u.insp.emplace_back(); ci = &u.insp.back(); }
+      ci->inspected = ci->with_lists = ci->flags_valid = ci->win_valid = false;
+      ci->cb = cb;
+      ci->n = n;
     }
-    if (mode == kFull) collect_ie_stat();
-    if (rcp && want_ie && !recipe_broken) {
+    if (ci->s0 != C.s0 || ci->s1 != C.s1) ci->win_valid = false;
+    ci->s0 = C.s0;
+    ci->s1 = C.s1;
+  }
+  ChunkInsp* ci = C.ci;
+  ChunkBufs& b = *(C.b = ci ? &ci->bufs : &c->scratch);
+  C.use_ie = R.want_ie && (C.scored || R.res_planes || R.rcp != nullptr);
+  C.use_sparse = C.scored && R.sparse_ok && !R.want_ie;
+  // replayed: the inspector's output is in place (rows, statistics, keys, kept rows, lists when this chunk wants them)
+  C.hit = ci && R.replay && ci->inspected &&
+          (!C.use_ie || (ci->with_lists && ci->flags_valid && ci->in_recipe == (R.rcp != nullptr)));
+  if (ci && !C.hit) ci->inspected = ci->with_lists = ci->flags_valid = ci->win_valid = false;
+  if (C.hit) R.prof->inspect_replays++;
+  const size_t cap = R.cap;
+  hipStream_t st = R.st;
+  HIP_TRY(c, hold(C, b.row0, cap, st));
+  HIP_TRY(c, hold(C, b.row1, cap, st));
+  HIP_TRY(c, hold(C, b.tot, cap * R.g.method, st));
+  HIP_TRY(c, hold(C, b.cases, cap, st));
+  HIP_TRY(c, hold(C, b.ctrls, cap, st));
+  HIP_TRY(c, hold(C, b.key, cap, st));
+  // the null kernel reads whole tiles: rows / totals beyond n must be valid (row 0, zero carriers)
+  const int64_t padded = C.padded;
+  const bool pad_now = padded > n && (!C.hit || padded > ci->padded);
+  if (ci) ci->padded = std::max(C.hit ? ci->padded : (int64_t)0, padded);
+  if (pad_now) {
+    HIP_TRY(c, hipMemsetAsync(b.row0.p + n, 0, (size_t)(padded - n) * 4, st));
+    HIP_TRY(c, hipMemsetAsync(b.row1.p + n, 0, (size_t)(padded - n) * 4, st));
+    HIP_TRY(c, hipMemsetAsync(b.tot.p + (size_t)n * R.g.method, 0, (size_t)(padded - n) * 4 * R.g.method, st));
+  }
+  return GCRE_OK;
+}
+
+// Expansion and the inspector -- k_stats, or k_stats_ie with the lists -- unless the chunk is replayed; the start of its
+// top-k selection.  *end: kOpen, kResplit or kNotNeeded.
+int inspect_chunk(JoinRun& R, ChunkRun& C, ChunkEnd* end) {
+  gcre_ctx* c = R.c;
+  const JoinPlan& jp = R.jp;
+  const gcre_uids& u = *R.u;
+  const Geometry& g = R.g;
+  ChunkBufs& b = *C.b;
+  ChunkInsp* ci = C.ci;
+  const int64_t cb = C.cb, n = C.n;
+  hipStream_t st = R.st;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  if (!C.hit) {
+    e0 = get_event(c);
+    e1 = get_event(c);
+    HIP_TRY(c, hipEventRecord(e0, st));
+    HIP_TRY(c, launch_expand(u.d_path_idx, u.d_location, u.n_uids, u.d_signs, u.path_length, g.method,
+                             cb, n, b.row0.p, b.row1.p, st));
+  }
+  if (C.partial && !C.use_ie && g.K > 0) {   // the join left the inclusion-exclusion form on an earlier chunk
+    if (e0) {
+      c->ev_pool.push_back(e0);
+      c->ev_pool.push_back(e1);
+    }
+    *end = ChunkEnd::kResplit;
+    return GCRE_OK;
+  }
+  StatsArgs sa{};
+  sa.p0 = jp.p0->d_rows;
+  sa.p1 = jp.p1->d_rows;
+  sa.row0 = b.row0.p;
+  sa.row1 = b.row1.p;
+  sa.case_mask = c->d_case_mask;
+  sa.dvt = c->d_dvt;
+  sa.key = b.key.p;
+  sa.tot = b.tot.p;
+  sa.cases = b.cases.p;
+  sa.ctrls = b.ctrls.p;
+  sa.res = R.keep ? jp.res->d_rows : nullptr;
+  sa.first = cb;
+  sa.count = n;
+  sa.S = g.S;
+  sa.Wp = g.Wp;
+  gcre_recipe* rcp = R.rcp;
+  if (C.use_sparse || C.use_ie) {
+    collect_ie_stat(R);
+    // the chunk's words of the flag block (6, 7: the join's).  Once a recipe has started, word kFlagOverReserved -- the
+    // entries reserved so far in the recipe's overflow area -- is the JOIN's (FlagWord): written from over_next in front of
+    // every inspector that fills the recipe, never zeroed
+    HIP_TRY(c, hipMemsetAsync(R.flagblk, 0, (rcp && R.recipe_started) ? kFlagOverReserved * 4 : kFlagRangeUnion * 4, st));
+    if (rcp) HIP_TRY(c, hipMemsetD32Async((hipDeviceptr_t)(R.flagblk + kFlagOverReserved), (int)R.over_next, 1, st));
+    R.recipe_started = R.recipe_started || rcp != nullptr;
+    sa.max_tot = R.flagblk;
+    HIP_TRY(c, hold(C, b.dcnt, (size_t)n * g.method, st));
+    sa.dcnt = b.dcnt.p;
+  }
+  if (C.use_ie) {
+    // one pass: statistics, kept rows, the check of the reduced operand, and the lists the null kernel streams
+    const size_t nl = (size_t)n * g.method;
+    HIP_TRY(c, hold(C, b.rowz, R.cap, st));
+    HIP_TRY(c, hold(C, b.linfo, nl, st));
+    HIP_TRY(c, hold(C, b.lover, nl, st));
+    HIP_TRY(c, hold(C, b.dlist, nl * 8 + 16, st));
+    // + the waves' chunk slack: every wave of the inspector may leave most of a 2048-entry reservation unused
+    const size_t over_slack = (std::min<size_t>(16384, ((size_t)n + 15) / 16 * 4) + 2) * 2048;
+    HIP_TRY(c, hold(C, b.dover, std::max<size_t>(b.dover.cap, nl * 2 + over_slack), st));
+    if (rcp) {   // straight into the recipe of the kept set (absolute row = cb + i)
+      C.rowz = rcp->rowz.p + cb;
+      C.linfo = rcp->linfo.p + (size_t)cb * g.method;
+      C.lover = rcp->lover.p + (size_t)cb * g.method;
+      C.slot = rcp->slot.p + (size_t)cb * g.method * 8;
+      C.over = rcp->over.p;
+      C.over_cap = rcp->over.cap;
+    } else {
+      C.rowz = b.rowz.p;
+      C.linfo = b.linfo.p;
+      C.lover = b.lover.p;
+      C.slot = b.dlist.p;
+      C.over = b.dover.p;
+      C.over_cap = b.dover.cap;
+    }
+    sa.pz = R.red->d_rows;
+    sa.zindex = R.hinted ? u.d_red_index : nullptr;
+    sa.excess = R.hinted ? R.exbuf->p : nullptr;
+    sa.range_of = R.hinted ? u.d_range_of : nullptr;
+    sa.bad = R.flagblk + kFlagHintBroken;
+    sa.ie_bias = 8;
+    sa.ie_rule = g.method == 1 ? 1 : 0;   // the bound filter and the quad kernel want overlap lists
+    sa.rowz = C.rowz;
+    sa.linfo = C.linfo;
+    sa.lover = C.lover;
+    sa.slot = C.slot;
+    sa.over = C.over;
+    sa.over_cap = (uint32_t)std::min<size_t>(C.over_cap - 16, 0xfffffff0u);
+    if (rcp && !C.hit) HIP_TRY(c, hipMemcpyAsync(rcp->row0.p + cb, b.row0.p, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
+    sa.ov_count = R.flagblk + kFlagOverReserved;
+    sa.zoff = (uint32_t)(64 * g.Wp) << 8;
+    if (g.method == 2 && one_sided(R.red)) sa.lz_off = R.red->d_loff;   // one round per path instead of one per half
+    if (!C.hit) HIP_TRY(c, launch_stats_ie(sa, g.method, st));
+    // a kept row's carrier total bounds every count of it: the next level loads only the plane groups that can be non-zero
+    if (rcp && !C.hit)
+      HIP_TRY(c, hipMemcpyAsync(rcp->tot.p + (size_t)cb * g.method, b.tot.p, nl * 4, hipMemcpyDeviceToDevice, st));
+  } else if (!C.hit) {
+    HIP_TRY(c, launch_stats(sa, g.method, st));
+  }
+  if (!C.hit) {
+    HIP_TRY(c, hipEventRecord(e1, st));
+    if (R.mode != kInspect) HIP_TRY(c, hipEventRecord(c->ev_insp_main, st));
+    R.ev_stats->emplace_back(e0, e1);
+    if (ci) {
+      ci->inspected = true;
+      ci->with_lists = C.use_ie;
+      ci->in_recipe = C.use_ie && rcp != nullptr;
+    }
+  }
+  if (C.hit && ci->win_valid && C.scored) {   // the chunk's top-k does not depend on the masks either
+    C.win = ci->win;
+    C.sel_done = true;
+    C.win_from_cache = true;
+  }
+  // the top-k selection only needs the keys the inspector just wrote: its digit passes run now, their state
+  // comes back with the inspector's flags, its winners are collected before the null kernel starts
+  if (C.use_ie && g.K > 0 && C.scored && !C.sel_done) {
+    if (c->sel_async) {   // beside the warm-up slice and the null kernel, behind the inspector
+      HIP_TRY(c, hipEventRecord(c->ev_sel, st));
+      HIP_TRY(c, hipStreamWaitEvent(c->sel_stream, c->ev_sel, 0));
+      C.sel_on = c->sel_stream;
+    }
+    if (int rc = select_begin(c, b.key.p + C.s0, C.s1 - C.s0, c->top_k, &c->h_sel, C.sel_on)) return rc;
+    C.sel_begun = true;
+  }
+  *end = (!C.scored && !(C.use_ie && g.K > 0)) ? ChunkEnd::kNotNeeded : ChunkEnd::kOpen;
+  return GCRE_OK;
+}
+
+// the IeArgs of a chunk's pruned launches: operands, their planes or the recipe they are rebuilt from, the lists, the tables
+int fill_ie_args(JoinRun& R, const ChunkRun& C, IeArgs& ia, int64_t* nseg_scored, gcre_uids::SegCache** seg_entry) {
+  gcre_ctx* c = R.c;
+  const JoinPlan& jp = R.jp;
+  const Geometry& g = R.g;
+  const int64_t cb = C.cb, n = C.n;
+  if (int rc = sparse_segments(c, *R.u, cb, n, cb + C.s0, cb + C.s1, R.res_planes ? R.pl_b : cb + C.s0,
+                               R.res_planes ? R.pl_e : cb + C.s1, &ia.segs, &ia.nsegs, nseg_scored, seg_entry))
+    return rc;
+  ia.mt = R.w_mt;
+  ia.tot = C.b->tot.p;
+  ia.rowz = C.rowz;
+  ia.planes0 = (R.have_p0 && !R.use_rec) ? jp.p0->d_planes : nullptr;
+  ia.g0 = (R.have_p0 && !R.use_rec) ? jp.p0->plane_groups : 0;
+  ia.planesz = R.have_pz ? R.red->d_planes : nullptr;
+  ia.gz = R.have_pz ? R.red->plane_groups : 0;
+  ia.rows0 = (uint32_t)(jp.p0->nrows * g.method);
+  ia.rowsz = (uint32_t)(R.red->nrows * g.method);
+  ia.rows_out = R.res_planes ? (uint32_t)(jp.res->nrows * g.method) : 0u;
+  ia.loff0 = jp.p0->d_loff;
+  ia.lidx0 = jp.p0->d_lidx;
+  ia.linfo = C.linfo;
+  ia.lover = C.lover;
+  ia.dlist = C.slot;
+  ia.dover = C.over;
+  if (R.use_rec) {
+    const gcre_recipe* r0 = jp.p0->rec;
+    ia.rec_row0 = r0->row0.p;
+    ia.rec_rowz = r0->rowz.p;
+    ia.rec_linfo = r0->linfo.p;
+    ia.rec_lover = r0->lover.p;
+    ia.rec_slot = r0->slot.p;
+    ia.rec_over = r0->over.p;
+    ia.rec_planes_a = R.rec_a->d_planes;
+    ia.rec_planes_z = R.rec_z->d_planes;
+    ia.rec_rows_a = (uint32_t)(R.rec_a->nrows * g.method);   // row-halves
+    ia.rec_rows_z = (uint32_t)(R.rec_z->nrows * g.method);
+    ia.rec_ga = R.rec_a->plane_groups;
+    ia.rec_gz = R.rec_z->plane_groups;
+    if (g.method == 1) {
+      // the recipe entries of every segment's row, next to the segment table (no load depends on row0 any more)
+      HIP_TRY(c, c->d_rec_segs.reserve((size_t)std::max<int64_t>(ia.nsegs, 1) * kRecSegWords));
+      HIP_TRY(c, launch_fill_rec_segs(ia.segs, ia.nsegs, r0->row0.p, r0->rowz.p, r0->linfo.p, r0->lover.p, r0->slot.p, r0->tot.p,
+                                      c->d_rec_segs.p, R.st));
+      ia.rec_segs = c->d_rec_segs.p;
+    }
+  }
+  ia.t32 = c->d_t32;
+  ia.d64 = c->d_dmax;
+  ia.ladder = c->d_ladder;
+  ia.ladder_stride = g.TD;
+  ia.lad_mode = !C.scored ? 1 : (c->ie_prune ? 0 : 2);
+  ia.g00_rows = c->g00_rows;
+  ia.null_bits = R.w_null;
+  ia.planes_out = R.res_planes ? jp.res->d_planes : nullptr;
+  ia.go = R.res_planes ? jp.res->plane_groups : 0;
+  ia.out_first = cb;
+  ia.score_begin = (uint32_t)C.s0;
+  ia.score_end = (uint32_t)C.s1;
+  ia.score_segs = (uint32_t)*nseg_scored;
+  ia.nkt = R.nkt_sp;
+  ia.K = g.K;
+  ia.mt_rows = (uint32_t)(64 * g.Wp + 1);
+  ia.zoff = (uint32_t)(64 * g.Wp) << 8;
+  return GCRE_OK;
+}
+
+// The launches of a chunk's inclusion-exclusion road: the warm-up slice, then the pruned kernel -- the quad form where
+// segments come in groups -- in one launch or in slices with a threshold exchange before each.  *quad: the quad form ran.
+int launch_ie_slices(JoinRun& R, const ChunkRun& C, IeArgs& ia, int planes, int64_t nseg_scored,
+                     gcre_uids::SegCache* seg_entry, int64_t ie_tile_factor, bool* quad_ran) {
+  gcre_ctx* c = R.c;
+  const JoinPlan& jp = R.jp;
+  const Geometry& g = R.g;
+  hipStream_t st = R.st;
+  const int64_t n = C.n;
+  ia.seg_begin = 0;
+  ia.seg_end = ia.nsegs;
+  if (c->d_ladder && ia.lad_mode == 0) {
+    // warm-up: the first segments are scored without pruning (every count looked up, general kernel); what
+    // they find seeds the thresholds the pruned kernel starts from.  Joins of a few thousand paths run here whole.
+    // (the scored segments lead the table.)  The general kernel is several times slower per path: a short
+    // shard gives it an eighth of its segments, not all of them.
+    // every tile warms up on its own permutations: with many tiles the slice gets shorter (its cost is per tile)
+    int64_t n_warm = warm_segments(c, nseg_scored, R.nkt_sp);
+    // maxima shared with the other devices right after the warm-up: every device warms its share of the slice
+    if (jp.exchange && R.exchanges_done < jp.exchanges && R.P > 0)
+      n_warm = std::min(n_warm, std::max<int64_t>(64, (int64_t)((double)n_warm * (double)(R.se - R.sb) / (double)R.P) + 1));
+    if (c->ie_warm_segs == 0) n_warm = 0;   // GCRE_IE_WARM=0 (tests): everything through the pruned kernel, thresholds from 0
+    IeArgs wa = ia;
+    wa.seg_end = n_warm;
+    // a wave walks its tiles one after the other: keep enough waves that each gets about four (segment, tile) items
+    wa.waves_per_xcd = spread_waves(wa.waves_per_xcd, n_warm * R.nkt_sp, c->ie_warm_items);
+    if (n_warm > 0) HIP_TRY(c, launch_null_ie(wa, g.method, planes, true, st));
+    ia.seg_begin = n_warm;
+  }
+  if (ia.seg_begin >= ia.seg_end) return GCRE_OK;
+  ia.queue = c->d_queue;
+  ia.batch = c->ie_batch;
+  // method 1, no plane output: the quad form (gcre_ieq.hip) wherever segments come in groups that join the same
+  // paths1 rows -- every level but the one whose uids are the genes themselves (one uid per pivot)
+  bool quad = false;
+  if (g.method == 1 && c->d_ladder && c->ie_quad && !ia.planes_out && seg_entry &&
+      ensure_quads(c, *R.u, *seg_entry, ia.seg_begin) == GCRE_OK) {
+    const int64_t nq = seg_entry->nquads - seg_entry->quad_begin;
+    // worth it from 1 + (qmax - 1) / 4 segments per quad on average: 1.25 with two segments per quad (a quad of one
+    // segment does what k_null_ie_m1 does with a longer prologue); the 1.5 of the four-segment form could never be
+    // reached by joins that average 1.3-1.5
+    const int64_t qmax = ieq_quad_segs();
+    quad = nq > 0 && ((ia.seg_end - ia.seg_begin) * 4 >= nq * (4 + (qmax - 1)) || c->ie_quad == 2);
+    if (std::getenv("GCRE_HOST_TIMING"))
+      std::fprintf(stderr, "[host] quads: %lld segments in %lld quads (%.2f per quad), %lld joined paths, quad form %s\n",
+                   (long long)(ia.seg_end - ia.seg_begin), (long long)nq, (double)(ia.seg_end - ia.seg_begin) / (double)std::max<int64_t>(nq, 1),
+                   (long long)n, quad ? "on" : "off");
+    if (quad) {
+      ia.quads = seg_entry->d_quads;
+      ia.quad_begin = seg_entry->quad_begin;
+      ia.quad_end = seg_entry->nquads;
+      ia.batch = c->ieq_batch > 0 ? c->ieq_batch : std::max(1, c->ie_batch * 2);   // quads per ticket: the headers of a ticket's quads are fetched one ahead
+      const int wq = std::min(c->sparse_waves_per_cu, ieq_max_waves_per_cu(planes, ia.gz, ia.rec_slot != nullptr));
+      ia.waves_per_xcd = spread_waves(xcd_waves(c, wq), n * ie_tile_factor, 128);
+    }
+  }
+  // tickets are 32-bit: (batches per tile) x tiles must stay below 2^32
+  while (((ia.nsegs - ia.seg_begin) / ia.batch + 1) * (int64_t)ia.nkt > (int64_t)0xf0000000ll) ia.batch *= 2;
+  // One launch -- or, when the maxima are shared with other devices as the join goes (gcre_join_opts.exchange),
+  // E slices with an exchange before each, so that the thresholds of a shard follow the whole level's maxima: the
+  // first slices double (1/2^k of the head), the last m = exchange_tail are equal steps 1/(m+1) of the range.
+  // Measured at 8 ranks on configs[3]: equal steps at the end and up to 16 exchanges halve the
+  // look-ups once more but every slice is a launch that starts cold -- doubling slices alone (m = 0) stay best.
+  const bool pruned = c->d_ladder && ia.lad_mode == 0;
+  const int n_slices = (pruned && jp.exchange) ? std::max(1, jp.exchanges - R.exchanges_done) : 1;
+  const int64_t r_b = quad ? ia.quad_begin : ia.seg_begin, r_e = quad ? ia.quad_end : ia.seg_end;
+  int64_t lo = r_b;
+  for (int sl = 0; sl < n_slices && lo < r_e; sl++) {
+    int64_t hi = r_e;
+    if (sl + 1 < n_slices) {
+      const int m = std::min(n_slices - 1, c->exchange_tail < 0 ? n_slices / 2 : c->exchange_tail), head = n_slices - m;
+      const double end = sl >= head ? (double)(sl - head + 2) / (double)(m + 1) : std::ldexp(1.0 / (double)(m + 1), -(head - 1 - sl));
+      hi = std::min(r_e, std::max(lo + 1, r_b + (int64_t)((double)(r_e - r_b) * end)));
+    }
+    if (pruned && jp.exchange)
+      if (int rc = exchange_now(R)) return rc;
+    IeArgs sa2 = ia;
+    if (quad) { sa2.quad_begin = lo; sa2.quad_end = hi; }
+    else { sa2.seg_begin = lo; sa2.seg_end = hi; }
+    HIP_TRY(c, hipMemsetAsync(sa2.queue, 0, 8 * 16 * 4, st));
+    if (quad) HIP_TRY(c, launch_null_ie_quad(sa2, planes, st));
+    else HIP_TRY(c, launch_null_ie(sa2, g.method, planes, c->d_ladder == nullptr, st));
+    lo = hi;
+  }
+  if (quad) R.prof->ie_quad_launches++;
+  *quad_ran = quad;
+  return GCRE_OK;
+}
+
+// GCRE_IE_TIMING=1 with a diagnostics build (-DGCRE_IE_TIMING): the section counters of the chunk's pruned launches (stderr)
+int print_ie_timing(JoinRun& R, const ChunkRun& C, const IeArgs& ia, bool quad) {
+  gcre_ctx* c = R.c;
+  const int64_t n = C.n;
+  uint64_t tmv[8] = {0};
+  HIP_TRY(c, hipMemcpyAsync(tmv, c->d_ie_timing.p, 64, hipMemcpyDeviceToHost, R.st));
+  HIP_TRY(c, hipStreamSynchronize(R.st));
+  const double waves = 8.0 * ia.waves_per_xcd;
+  if (R.g.method == 2)
+    std::fprintf(stderr, "[ie2 classes] paths %lld x %d tiles: path-tiles with the other half empty %llu, one test %llu, all steps %llu, both halves %llu; "
+                 "lists of 5-8 rows %llu, long lists %llu; permutations looked up %llu\n", (long long)n, ia.nkt, (unsigned long long)tmv[0],
+                 (unsigned long long)tmv[1], (unsigned long long)tmv[2], (unsigned long long)tmv[3], (unsigned long long)tmv[4],
+                 (unsigned long long)tmv[6], (unsigned long long)tmv[5]);
+  else if (quad)
+    std::fprintf(stderr, "[ieq timing] paths %lld waves %.0f quads/wave %.0f: per-wave Mcycles header+loads %.2f base counters %.2f intervals %.2f filter pass %.2f exact pass %.2f exchange %.2f total %.2f\n",
+                 (long long)n, waves, tmv[7] / waves, tmv[0] / waves / 1e6, tmv[1] / waves / 1e6, tmv[2] / waves / 1e6, tmv[3] / waves / 1e6,
+                 tmv[4] / waves / 1e6, tmv[5] / waves / 1e6, tmv[6] / waves / 1e6);
+  else
+    std::fprintf(stderr, "[ie filter] uncertain path-tiles %llu of %lld x %d tiles, lanes that fetched rows %llu\n",
+                 (unsigned long long)tmv[1], (long long)n, ia.nkt, (unsigned long long)tmv[3]);
+  std::fprintf(stderr, "[ie timing] paths %lld out %d waves %.0f: per-wave Mcycles seg %.2f load %.2f comp(incl load) %.2f lookup %.2f exch %.2f total %.2f, slowest wave %.2f\n",
+               (long long)n, ia.planes_out != nullptr, waves, tmv[0] / waves / 1e6, tmv[1] / waves / 1e6,
+               tmv[2] / waves / 1e6, tmv[3] / waves / 1e6, tmv[4] / waves / 1e6, tmv[5] / waves / 1e6, tmv[6] / 1e6);
+  return GCRE_OK;
+}
+
+// The inclusion-exclusion road of a chunk (gcre_ie.hip): the inspector's flags and the checks that send the chunk round
+// again, then -- unless the chunk was only to be inspected (kInspect), is priced out or needs no scoring -- its pruned
+// launches (kLaunch: their look-up counter goes behind the launch's maxima).
+int score_chunk_ie(JoinRun& R, ChunkRun& C, ChunkEnd* end) {
+  gcre_ctx* c = R.c;
+  const JoinPlan& jp = R.jp;
+  const Geometry& g = R.g;
+  hipStream_t st = R.st;
+  ChunkInsp* ci = C.ci;
+  const int64_t cb = C.cb, n = C.n;
+  const auto ti0 = std::chrono::steady_clock::now();
+  if (C.hit) {
+    std::memcpy(C.flags, ci->flags, sizeof C.flags);   // as the inspector left them (no round trip)
+  } else {
+    HIP_TRY(c, hipMemcpyAsync(C.flags, R.flagblk, sizeof C.flags, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+  }
+  const uint32_t over_used = C.flags[kFlagOverReserved];
+  if ((size_t)over_used + 16 > C.over_cap) {
+    // more long lists than the area holds: size it from what the pass asked for, run the chunk again (a recipe
+    // keeps what the earlier chunks wrote; the failed attempt's reservation is simply left unused)
+    const size_t want = (size_t)over_used + (size_t)over_used / 4 + ((size_t)1 << 24);
+    if (R.rcp) HIP_TRY(c, R.rcp->over.grow_keep(want, R.rcp->over.cap, st));
+    else HIP_TRY(c, C.b->dover.reserve(want));
+    if (ci) ci->inspected = false;
+    *end = ChunkEnd::kRedoOverflow;
+    return GCRE_OK;
+  }
+  const uint64_t n_list = (uint64_t)(n * g.method) * 8 + over_used;
+  if (R.rcp) R.over_next = std::max(R.over_next, over_used);
+  const uint32_t max_tot = C.flags[kFlagMaxTot];
+  R.join_max_tot = std::max(R.join_max_tot, max_tot);
+  R.join_max_len = std::max(R.join_max_len, C.flags[kFlagMaxLen]);
+  if (C.flags[kFlagHintBroken] != 0 || (R.hinted && C.flags[kFlagRangeUnion] != 0)) {
+    // the hint does not describe this join: run it on paths1 itself (identity map) from this chunk on
+    if (!R.hinted) return fail(c, GCRE_ERR_DEVICE, "internal: joined path differs from paths0 | paths1");
+    R.hinted = false;
+    if (int rc = prepare_z(R)) return rc;
+    if (!R.have_pz) R.want_ie = false;
+    // the kept rows' planes were sized for the reduced rows: rows of paths1 may carry more
+    if (R.res_planes && plane_groups_for(std::min<uint32_t>((uint32_t)(64 * g.Wp), row_max(c, jp.p0) + row_max(c, R.red))) >
+                            jp.res->plane_groups) {
+      R.res_planes = false;
+      R.res_planes_ok = false;
+    }
+    if (cb > C.sg->b || C.sg != &R.segs.front()) {   // earlier chunks added rows of another set
+      R.recipe_broken = true;
+      R.hint_broke_late = true;
+    }
+    if (ci) ci->inspected = false;
+    *end = ChunkEnd::kRedoHint;
+    return GCRE_OK;
+  }
+  if (ci && !C.hit) {
+    std::memcpy(ci->flags, C.flags, sizeof C.flags);
+    ci->flags_valid = true;
+  }
+  if (R.mode == kInspect) {   // nothing of the permutation kernel's; the chunk's winners are collected next
+    if (C.sel_begun && !C.sel_done) {
+      HIP_TRY(c, hipStreamSynchronize(C.sel_on));
+      if (int rc = finish_selection(R, C)) return rc;
+    }
+    *end = ChunkEnd::kInspected;
+    return GCRE_OK;
+  }
+  const int64_t nseg_est = std::max<int64_t>(uids_in(*R.u, cb, n), 1);
+  if (c->null_kernel == 0 && C.scored && ie_dearer(g, R.nkt_sp, R.have_p0, row_max(c, jp.p0), nseg_est, n, n_list)) {
+    R.res_planes_ok = false;
+    *end = C.partial ? ChunkEnd::kResplit : ChunkEnd::kPricedOut;
+    return GCRE_OK;
+  }
+  if (!C.scored && !(R.res_planes && cb < R.pl_e && cb + n > R.pl_b)) {   // rows of another shard that only needed their recipe entries
+    *end = ChunkEnd::kNotNeeded;
+    return GCRE_OK;
+  }
+  const int planes = counter_planes(max_tot);
+  IeArgs ia{};
+  int64_t nseg_scored = 0;
+  gcre_uids::SegCache* seg_entry = nullptr;
+  if (int rc = fill_ie_args(R, C, ia, &nseg_scored, &seg_entry)) return rc;
+  R.prof->null_row_loads += ((R.have_p0 ? 0.0 : (double)row_max(c, jp.p0) * g.method * (double)nseg_est) + (double)n_list) * R.nkt_sp;
+  const int wpc = std::min(c->sparse_waves_per_cu, ie_max_waves_per_cu(g.method, planes, ia.gz, ia.planes_out != nullptr, ia.rec_slot != nullptr));
+  // small joins: a wave's fixed costs (cold TLB and caches, LDS set-up, threshold exchange) are per tile it
+  // visits, so give every wave at least ~32 joined paths of a tile -- counting the tiles a queue can hold whole
+  // (a wave walks a contiguous piece of the tile-major sequence)
+  const int64_t ie_tile_factor = std::min(std::max(R.nkt_sp * c->ie_small_join_tiles / 8, 1), R.nkt_sp);
+  ia.waves_per_xcd = spread_waves(xcd_waves(c, wpc), n * ie_tile_factor, 32);
+  R.prof->inspect_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ti0).count();
+  ia.stats = R.mode == kLaunch ? R.w_null + g.Kpad : R.flagblk + kFlagLookupTiles;   // zeroed with the block before the inspector ran
+  const bool timing = std::getenv("GCRE_IE_TIMING") != nullptr;   // diagnostics builds only (-DGCRE_IE_TIMING)
+  if (timing) {
+    HIP_TRY(c, c->d_ie_timing.reserve(8));
+    HIP_TRY(c, hipMemsetAsync(c->d_ie_timing.p, 0, 64, st));
+    ia.timing = c->d_ie_timing.p;
+  }
+  if (C.sel_begun && C.sel_on == st)   // (its state came back with the flags)
+    if (int rc = finish_selection(R, C)) return rc;
+  hipEvent_t n0 = get_event(c), n1 = get_event(c);
+  bool quad = false;
+  HIP_TRY(c, hipEventRecord(n0, st));
+  if (int rc = launch_ie_slices(R, C, ia, planes, nseg_scored, seg_entry, ie_tile_factor, &quad)) return rc;
+  HIP_TRY(c, hipEventRecord(n1, st));
+  if (C.sel_begun && !C.sel_done) {   // own stream: the digit passes ran beside the warm-up slice
+    const auto tw0 = std::chrono::steady_clock::now();
+    HIP_TRY(c, hipStreamSynchronize(C.sel_on));
+    R.select_wait_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tw0).count();
+    if (int rc = finish_selection(R, C)) return rc;
+  }
+  if (timing && R.mode != kLaunch)
+    if (int rc = print_ie_timing(R, C, ia, quad)) return rc;
+  R.ev_null->emplace_back(n0, n1);
+  if (C.scored) {
+    R.prof->null_kernel_launches++;
+    R.prof->null_alg_bytes += alg_bytes(R, cb + C.s0, C.s1 - C.s0);
+  }
+  R.prof->ie_launches++;
+  R.prof->ie_overlap_lists += C.flags[kFlagOverlapLists];
+  R.ie_stat_pending = true;
+  R.ie_ran = true;
+  *end = ChunkEnd::kScored;
+  return GCRE_OK;
+}
+
+// Delta streaming (gcre_sparse.hip): per joined path the bits paths1 adds on top of paths0 -- offsets by a device scan of
+// the counts k_stats left, entries by k_delta_fill -- once per chunk, shared by all permutation tiles.  kPricedOut: the
+// dense kernel is cheaper.
+int score_chunk_sparse(JoinRun& R, ChunkRun& C, ChunkEnd* end) {
+  gcre_ctx* c = R.c;
+  const JoinPlan& jp = R.jp;
+  const gcre_uids& u = *R.u;
+  const Geometry& g = R.g;
+  hipStream_t st = R.st;
+  ChunkBufs& b = *C.b;
+  ChunkInsp* ci = C.ci;
+  const int64_t cb = C.cb, n = C.n;
+  if (int rc = ensure_lists(c, jp.p0)) return rc;
+  if (int rc = ensure_lists(c, jp.p1)) return rc;
+  const uint32_t zoff = (uint32_t)(64 * g.Wp) << 8;
+  const int64_t nl = n * g.method;   // delta lists: one per joined path and half
+  HIP_TRY(c, c->d_doff.reserve((size_t)nl + 1));
+  HIP_TRY(c, c->d_scan.reserve((size_t)(nl + 1023) / 1024 + 2));
+  HIP_TRY(c, launch_scan_u32_u64(b.dcnt.p, nl, c->d_doff.p, c->d_scan.p, st));
+  uint32_t max_tot = 0;
+  uint64_t n_delta = 0;
+  HIP_TRY(c, hipMemcpyAsync(&max_tot, R.flagblk + kFlagMaxTot, 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipMemcpyAsync(&n_delta, c->d_doff.p + nl, 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipStreamSynchronize(st));
+  if (C.hit) max_tot = ci->flags[kFlagMaxTot];   // the flag block was cleared for this window; the inspector's value was kept
+  else if (ci) { ci->flags[kFlagMaxTot] = max_tot; ci->flags_valid = true; }
+  if (c->null_kernel == 0 && sparse_dearer(g, n_delta, max_tot, std::max<int64_t>(uids_in(u, cb, n), 1), n)) {
+    *end = ChunkEnd::kPricedOut;
+    return GCRE_OK;
+  }
+  if (ci) ci->with_lists = false;   // the delta lists below take the place of the inspector's
+  HIP_TRY(c, b.dlist.reserve((size_t)n_delta + 16));
+  HIP_TRY(c, launch_delta_fill((const uint32_t*)jp.p0->d_rows, 2 * g.S, 2 * g.Wp, g.method, b.row0.p, b.row1.p, n,
+                               jp.p1->d_loff, jp.p1->d_lidx, c->d_doff.p, zoff, b.dlist.p, st));
+  const int planes = counter_planes(max_tot);
+  SparseArgs sp{};
+  int64_t nseg_scored = 0;
+  if (int rc = sparse_segments(c, u, cb, n, cb, cb + n, cb, cb + n, &sp.segs, &sp.nsegs, &nseg_scored)) return rc;
+  sp.mt = R.w_mt;
+  sp.tot = b.tot.p;
+  sp.loff0 = jp.p0->d_loff;
+  sp.lidx0 = jp.p0->d_lidx;
+  sp.doff = c->d_doff.p;
+  sp.dlist = b.dlist.p;
+  sp.t32 = c->d_t32;
+  sp.d64 = c->d_dmax;
+  sp.null_bits = R.w_null;
+  sp.nkt = (g.K + kSparseTile - 1) / kSparseTile;
+  sp.mt_rows = (uint32_t)(64 * g.Wp + 1);
+  sp.zoff = zoff;
+  {
+    // mask-row loads of this launch: every segment walks its paths0 list(s) once, every joined path its
+    // delta list(s), for each permutation tile
+    const auto& pi = u.h_path_idx;
+    const auto& lo = jp.p0->h_loff;
+    double base_entries = 0;
+    int64_t i = std::upper_bound(pi.begin(), pi.end(), cb) - pi.begin() - 1;
+    for (; i < u.n_uids && pi[(size_t)i] < cb + n; i++) {
+      const int64_t a0 = std::max(pi[(size_t)i], cb), a1 = std::min(pi[(size_t)i + 1], cb + n);
+      if (a1 <= a0) continue;
+      const double segs_here = (double)((a1 - a0 + kSparseSegMax - 1) / kSparseSegMax);
+      base_entries += segs_here * (double)(lo[(size_t)(i + 1) * g.method] - lo[(size_t)i * g.method]);
+    }
+    R.prof->null_row_loads += (base_entries + (double)n_delta) * sp.nkt;
+  }
+  sp.waves_per_xcd = xcd_waves(c, std::min(c->sparse_waves_per_cu, sparse_max_waves_per_cu(g.method, planes)));
+  hipEvent_t n0 = get_event(c), n1 = get_event(c);
+  HIP_TRY(c, hipEventRecord(n0, st));
+  HIP_TRY(c, launch_null_sparse(sp, g.method, planes, st));
+  HIP_TRY(c, hipEventRecord(n1, st));
+  R.ev_null->emplace_back(n0, n1);
+  R.prof->null_kernel_launches++;
+  R.prof->null_alg_bytes += alg_bytes(R, cb, n);
+  *end = ChunkEnd::kScored;
+  return GCRE_OK;
+}
+
+// the AND+BCNT kernel on the bit rows themselves (gcre_kernels.hip)
+int score_chunk_dense(JoinRun& R, ChunkRun& C) {
+  gcre_ctx* c = R.c;
+  const Geometry& g = R.g;
+  const ChunkBufs& b = *C.b;
+  NullArgs na{};
+  na.p0 = (const uint32_t*)R.jp.p0->d_rows;
+  na.p1 = (const uint32_t*)R.jp.p1->d_rows;
+  na.masks = R.w_masks;
+  na.row0 = b.row0.p;
+  na.row1 = b.row1.p;
+  na.tot = b.tot.p;
+  na.t32 = c->d_t32;
+  na.d64 = c->d_dmax;
+  na.null_bits = R.w_null;
+  na.npaths = C.n;
+  na.npt = C.npt;
+  na.S32 = 2 * g.S;
+  na.W32p = 2 * g.Wp;
+  na.Kpad = R.Kstride;
+  na.nkt = (g.K + R.cfg.perm_tile - 1) / R.cfg.perm_tile;
+  const int64_t want = (int64_t)c->cus * c->null_blocks_per_cu;
+  int64_t groups = std::max<int64_t>(1, want / na.nkt);
+  groups = std::min<int64_t>(groups, C.npt);
+  na.pgroups = (int)groups;
+  hipEvent_t n0 = get_event(c), n1 = get_event(c);
+  HIP_TRY(c, hipEventRecord(n0, R.st));
+  HIP_TRY(c, launch_null(na, g.method, R.cfg, R.st));
+  HIP_TRY(c, hipEventRecord(n1, R.st));
+  R.ev_null->emplace_back(n0, n1);
+  R.prof->null_kernel_launches++;
+  R.prof->null_alg_bytes += alg_bytes(R, C.cb, C.n);
+  return GCRE_OK;
+}
+
+// ---- top-k of a scored chunk: the selection (finished, or run whole), its winners into the join's candidates ----
+int collect_winners(JoinRun& R, ChunkRun& C) {
+  gcre_ctx* c = R.c;
+  hipStream_t st = R.st;
+  const auto ts0 = std::chrono::steady_clock::now();
+  if (!C.sel_done) {
+    if (C.sel_begun) {   // begun, then the chunk left the inclusion-exclusion road: its state is still good
+      HIP_TRY(c, hipStreamSynchronize(C.sel_on));
+      if (int rc = finish_selection(R, C)) return rc;
+    } else {
+      if (c->sel_stream) HIP_TRY(c, hipStreamSynchronize(c->sel_stream));   // an abandoned selection shares the scratch
+      uint32_t nsel = 0;
+      if (int rc = select_chunk(c, C.b->key.p + C.s0, C.s1 - C.s0, c->top_k, &nsel, st)) return rc;
+      if (int rc = queue_winners(c, *C.b, C.s0, nsel, C.win, C.sel_on)) return rc;
+    }
+    // whatever still runs on the selection stream reads this chunk's keys and rows: the next chunk's inspector (on the
+    // main stream) rewrites them, so it queues behind an event -- not behind "the results are discarded anyway"
+    if (C.sel_on != st) {
+      HIP_TRY(c, hipEventRecord(c->ev_sel_done, C.sel_on));
+      HIP_TRY(c, hipStreamWaitEvent(st, c->ev_sel_done, 0));
+    }
+  }
+  const Winners& win = C.win;
+  if (win.n > 0) {
+    const auto tw0 = std::chrono::steady_clock::now();
+    if (!C.win_from_cache) {   // (cached winners are host data: nothing to wait for)
+      if (C.sel_on != st) HIP_TRY(c, hipStreamSynchronize(C.sel_on));
+      HIP_TRY(c, hipStreamSynchronize(st));   // the null kernel of this chunk: its time is not the selection's
+    }
+    R.select_wait_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tw0).count();
+    const int64_t first = C.cb + C.s0;
+    for (uint32_t i = 0; i < win.n; i++)
+      R.cands.push_back(Candidate{key_to_score(win.key[i]), first + (int64_t)win.sel[i], (int32_t)win.r0[i], (int32_t)win.r1[i],
+                                  (int32_t)win.cases[i], (int32_t)win.ctrls[i]});
+  }
+  if (C.ci && !C.ci->win_valid) {   // (its copies have arrived: the stream was waited for above)
+    C.ci->win = win;
+    C.ci->win_valid = true;
+  }
+  R.select_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ts0).count();
+  return GCRE_OK;
+}
+
+// One attempt at the chunk [cb, ce).  *end tells the chunk loop whether to run it again.
+int run_chunk(JoinRun& R, const Seg& sg, int64_t cb, int64_t ce, ChunkEnd* end) {
+  ChunkRun C;
+  *end = ChunkEnd::kOpen;
+  if (int rc = open_chunk(R, C, sg, cb, ce)) return rc;
+  if (int rc = inspect_chunk(R, C, end)) return rc;
+  if (*end == ChunkEnd::kOpen && R.g.K > 0 && C.use_ie)
+    if (int rc = score_chunk_ie(R, C, end)) return rc;
+  if (*end == ChunkEnd::kResplit || *end == ChunkEnd::kRedoOverflow || *end == ChunkEnd::kRedoHint) {
+    // the abandoned digit passes may still be reading the keys the relaunched inspector is about to rewrite
+    if (C.sel_begun && C.sel_on != R.st) {
+      HIP_TRY(R.c, hipEventRecord(R.c->ev_sel_done, C.sel_on));
+      HIP_TRY(R.c, hipStreamWaitEvent(R.st, R.c->ev_sel_done, 0));
+    }
+    return GCRE_OK;
+  }
+  if (!C.scored) return GCRE_OK;
+  if (R.g.K > 0 && (*end == ChunkEnd::kOpen || *end == ChunkEnd::kPricedOut)) {
+    if (R.mode == kInspect) {
+      if (C.use_sparse && C.ci) {
+        // the delta-streaming road sizes its counters from the inspector's flag block: an ahead inspection reads it now and
+        // leaves it with the chunk (the launch that replays the chunk finds the block cleared)
+        HIP_TRY(R.c, hipMemcpyAsync(C.ci->flags, R.flagblk, sizeof C.ci->flags, hipMemcpyDeviceToHost, R.st));
+        HIP_TRY(R.c, hipStreamSynchronize(R.st));
+        C.ci->flags_valid = true;
+      }
+    } else {
+      if (C.use_sparse)
+        if (int rc = score_chunk_sparse(R, C, end)) return rc;
+      if (*end != ChunkEnd::kScored)
+        if (int rc = score_chunk_dense(R, C)) return rc;
+    }
+  }
+  if (int rc = collect_winners(R, C)) return rc;
+  if (R.mode != kInspect) R.prof->paths += C.s1 - C.s0;   // (a launch books them on the profile of the join it is for)
+  return GCRE_OK;
+}
+
+// After the chunks: what the join leaves with its operands and its join index, then by mode -- kInspect marks its stream,
+// kLaunch leaves the launch with the join index, kFull delivers the result (and runs the registered chain)
+int finish_join(JoinRun& R) {
+  gcre_ctx* c = R.c;
+  const JoinPlan& jp = R.jp;
+  const gcre_uids& u = *R.u;
+  const Geometry& g = R.g;
+  hipStream_t st = R.st;
+  if (R.P > 0) {
+    if (R.mode == kFull) collect_ie_stat(R);
+    if (R.rcp && R.want_ie && !R.recipe_broken) {
       // the recipe names its operands by id and row version: the set paths0 was, and the rows the join really added
-      rcp->a_id = jp.p0->id;
-      rcp->a_ver = jp.p0->version;
-      rcp->z_id = red->id;
-      rcp->z_ver = red->version;
-      rcp->valid = true;
-      rcp->max_len = join_max_len;
-      jp.res->max_bits = (join_max_tot + 3u) & ~3u;
+      R.rcp->a_id = jp.p0->id;
+      R.rcp->a_ver = jp.p0->version;
+      R.rcp->z_id = R.red->id;
+      R.rcp->z_ver = R.red->version;
+      R.rcp->valid = true;
+      R.rcp->max_len = R.join_max_len;
+      jp.res->max_bits = (R.join_max_tot + 3u) & ~3u;
       jp.res->max_known = true;
     }
-    keep_planes_done = res_planes && res_planes_ok && g.K > 0;
-    keep_planes_lo = pl_b;
-    keep_planes_hi = pl_e;
-    keep_max_tot = join_max_tot;
     if (c->insp_cache) {
-      u.insp_hinted = hinted;
-      u.insp_res_ver = keep ? jp.res->version : 0;
-      u.insp_valid = !hint_broke_late;
+      u.insp_hinted = R.hinted;
+      u.insp_res_ver = R.keep ? jp.res->version : 0;
+      u.insp_valid = !R.hint_broke_late;
     }
-    if (ie_ran && hinted) c->prof.ie_hinted_joins++;
-    if (ie_ran && have_p0) c->prof.ie_plane_joins++;
+    if (R.ie_ran && R.hinted) R.prof->ie_hinted_joins++;
+    if (R.ie_ran && R.have_p0) R.prof->ie_plane_joins++;
   }
-
-  if (inspect_only) {
+  if (R.mode == kInspect) {
     // everything this inspection queued is behind this event: the join proper waits for it on the main stream
     HIP_TRY(c, hipEventRecord(c->ev_insp_done, st));
     return GCRE_OK;
   }
-  if (keep_planes_done) {
+  if (R.res_planes && R.res_planes_ok && g.K > 0) {
     // the kept rows leave with their count planes: the next level's N0 (gcre_ie.hip)
     jp.res->planes_epoch = c->mask_epoch;
     jp.res->planes_valid = true;
-    jp.res->planes_lo = keep_planes_lo;
-    jp.res->planes_hi = keep_planes_hi;
-    jp.res->max_bits = (keep_max_tot + 3u) & ~3u;
+    jp.res->planes_lo = R.pl_b;
+    jp.res->planes_hi = R.pl_e;
+    jp.res->max_bits = (R.join_max_tot + 3u) & ~3u;
     jp.res->max_known = true;
   }
-
   // a join that took another road (small, unpruned, another kernel form) still makes the calls the other devices expect
-  while (jp.exchange && exchanges_done < jp.exchanges)
-    if (int rc = exchange_now()) return rc;
-
-  if (launch_only) {
+  while (jp.exchange && R.exchanges_done < jp.exchanges)
+    if (int rc = exchange_now(R)) return rc;
+  if (R.mode == kLaunch) {
     // launched: the kernels are queued, nothing is waited for.  What the join's own call will need stays with the index
     gcre_uids::Launched& L = u.launch;
     HIP_TRY(c, hipEventRecord(L.done, st));
-    L.cands = std::move(cands);
-    L.key = ikey;
-    L.res_ver = keep ? jp.res->version : 0;
+    L.cands = std::move(R.cands);
+    L.key = R.ikey;
+    L.res_ver = R.keep ? jp.res->version : 0;
     L.mask_epoch = c->mask_epoch;
     L.win_k0 = c->win_k0;
     L.win_K = c->win_K;
     L.active = true;
     return GCRE_OK;
   }
-
-  // ---- null maxima: first K entries, f32 (methods.h:101-102; format_result, join_base.cpp:144-146) ----
-  out->n_perm = g.K;
-  out->null_max = (float*)std::calloc((size_t)std::max(g.K, 1), sizeof(float));
-  if (g.K > 0) {
-    HIP_TRY(c, hipMemcpyAsync(out->null_max, w_null, (size_t)g.K * 4, hipMemcpyDeviceToHost, st));
-    if (jp.d_null_out) HIP_TRY(c, hipMemcpyAsync(jp.d_null_out, w_null, (size_t)g.K * 4, hipMemcpyDeviceToDevice, st));
-  }
-  if (ahead_plan) {
-    // this join's copies are queued: the chain goes behind them, and only they are waited for
-    HIP_TRY(c, hipEventRecord(c->ev_tail, st));
-    if (int rc = run_chain()) return rc;
-    HIP_TRY(c, hipEventSynchronize(c->ev_tail));
-  } else {
-    HIP_TRY(c, hipStreamSynchronize(st));
-  }
-
-  merge_candidates(cands, c->top_k, out);
-
-  c->prof.null_kernel_ms = drain_events(c, c->ev_null);
-  c->prof.stats_kernel_ms = drain_events(c, c->ev_stats);
-  c->prof.select_ms = std::max(0.0, select_ms - select_wait_ms);
-  c->prof.scores = c->prof.paths * (int64_t)g.K;
-  c->prof.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+  if (int rc = deliver_join(c, jp, R.out, g.K, R.w_null, st, R.cands, c->ev_null, c->ev_stats, R.t_begin, std::move(R.ahead_plan)))
+    return rc;
+  c->prof.select_ms = std::max(0.0, R.select_ms - R.select_wait_ms);
   return GCRE_OK;
+}
+
+// The join driver (JoinExec::join): chunks of at most chunk_paths joined paths, each inspected, scored against the
+// permutations of the window and reduced to its top-k; a chunk the stages send round again runs again from its start.
+int run_join(gcre_ctx* c, const JoinPlan& jp, gcre_result* out, JoinMode mode) {
+  JoinRun R(c, jp, out, mode);
+  Begin next = Begin::kDone;
+  if (int rc = begin_join(R, &next)) return rc;
+  if (next == Begin::kDone) return GCRE_OK;
+  if (next == Begin::kFinishLaunched) return finish_launched(c, jp, out);
+  if (R.P > 0) {
+    plan_segments(R);
+    if (int rc = prepare_operands(R)) return rc;
+    for (const Seg& sg : R.segs) {
+      int64_t cb = sg.b;
+      while (cb < sg.e) {
+        int64_t ce = std::min(cb + R.chunk_cap, sg.e);
+        if (R.split && cb < sg.sb) ce = std::min(ce, sg.sb);
+        else if (R.split && cb < sg.se) ce = std::min(ce, sg.se);
+        ChunkEnd end = ChunkEnd::kOpen;
+        if (int rc = run_chunk(R, sg, cb, ce, &end)) return rc;
+        if (end == ChunkEnd::kResplit) R.split = true;
+        const bool again = end == ChunkEnd::kResplit || end == ChunkEnd::kRedoOverflow || end == ChunkEnd::kRedoHint;
+        if (!again) cb = ce;
+      }
+    }
+  }
+  return finish_join(R);
 }
 
 }  // namespace
@@ -2563,6 +2781,7 @@ gcre_ctx* gcre_create(int method, int n_cases, int n_ctrls, int iterations, int 
   }
   auto* c = new gcre_ctx();
   c->device = device;
+  (void)hipDeviceGetAttribute(&c->cus, hipDeviceAttributeMultiprocessorCount, device);
   Geometry& g = c->g;
   g.method = method;
   g.n = n_cases + n_ctrls;
@@ -2602,8 +2821,8 @@ gcre_ctx* gcre_create(int method, int n_cases, int n_ctrls, int iterations, int 
   ok = ok && hipEventCreateWithFlags(&c->ev_sel_done, hipEventDisableTiming) == hipSuccess;
   if (const char* e = std::getenv("GCRE_SELECT_STREAM")) c->sel_async = std::atoi(e) != 0;
   ok = ok && hipMalloc((void**)&c->d_case_mask, (size_t)g.Wp * 8) == hipSuccess;
-  ok = ok && hipMalloc((void**)&c->d_max_tot, 32) == hipSuccess;
-  ok = ok && hipMalloc((void**)&c->d_max_tot_b, 32) == hipSuccess;
+  ok = ok && hipMalloc((void**)&c->d_max_tot, kFlagWords * 4) == hipSuccess;
+  ok = ok && hipMalloc((void**)&c->d_max_tot_b, kFlagWords * 4) == hipSuccess;
   ok = ok && hipMalloc((void**)&c->d_queue, 8 * 16 * 4) == hipSuccess;
   if (ok && g.Kpad > 0) {
     ok = hipMalloc((void**)&c->d_masks, (size_t)2 * g.Wp * g.Kpad * 4) == hipSuccess;
@@ -2641,22 +2860,16 @@ void gcre_destroy(gcre_ctx* c) {
   for (void* p : {(void*)c->d_case_mask, (void*)c->d_masks, (void*)c->d_t32, (void*)c->d_dvt, (void*)c->d_dmax,
                   (void*)c->d_null, (void*)c->d_mt, (void*)c->d_max_tot, (void*)c->d_max_tot_b, (void*)c->d_queue, (void*)c->d_ladder})
     if (p) (void)hipFree(p);
-  for (auto* b : {&c->d_row0, &c->d_row1, &c->d_tot, &c->d_cases, &c->d_ctrls, &c->d_sel, &c->d_small, &c->d_chunk,
-                  &c->d_rec_segs, &c->d_wcases, &c->d_wctrls, &c->d_wrow0, &c->d_wrow1})
+  c->scratch.release();
+  for (auto* b : {&c->d_sel, &c->d_small, &c->d_chunk, &c->d_rec_segs, &c->d_wcases, &c->d_wctrls, &c->d_wrow0, &c->d_wrow1})
     b->release();
-  c->d_key.release();
   c->d_hub_null.release();
   c->d_wkey.release();
   c->d_doff.release();
   c->d_scan.release();
   c->d_excess.release();
   c->d_excess_b.release();
-  c->d_dcnt.release();
-  c->d_dlist.release();
-  c->d_rowz.release();
-  c->d_linfo.release();
-  c->d_lover.release();
-  c->d_dover.release();
+  c->d_ie_timing.release();
   for (auto& pb : c->plane_pool) (void)hipFree(pb.p);
   c->plane_pool.clear();
   for (auto e : c->ev_pool) (void)hipEventDestroy(e);

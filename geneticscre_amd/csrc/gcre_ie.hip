@@ -1459,8 +1459,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((M == 1 && 
   }
   if (my_max_tot) atomicMax(a.max_tot, my_max_tot);
   if (my_bad) *a.bad = 1u;
-  if (my_modes) atomicAdd(a.bad + 1, my_modes);   // statistics: overlap-mode lists
-  if (my_max_len > 8u) atomicMax(a.max_tot + 5, my_max_len);   // longest list (padded): the quad kernel sums up to 56 entries
+  if (my_modes) atomicAdd(a.bad + (kFlagOverlapLists - kFlagHintBroken), my_modes);   // statistics: overlap-mode lists
+  if (my_max_len > 8u) atomicMax(a.max_tot + kFlagMaxLen, my_max_len);   // longest list (padded): the quad kernel sums up to 56 entries
 }
 
 // Excess of paths1 over the reduced operand, per distinct (location, count) range of the join index:
@@ -1752,8 +1752,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NL <= 3 ? G
   }
   if (my_max_tot) atomicMax(a.max_tot, my_max_tot);
   if (my_bad) *a.bad = 1u;
-  if (my_modes) atomicAdd(a.bad + 1, my_modes);
-  if (my_max_len > 8u) atomicMax(a.max_tot + 5, my_max_len);
+  if (my_modes) atomicAdd(a.bad + (kFlagOverlapLists - kFlagHintBroken), my_modes);
+  if (my_max_len > 8u) atomicMax(a.max_tot + kFlagMaxLen, my_max_len);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1987,8 +1987,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NL <= 3 ? G
   }
   if (my_max_tot) atomicMax(a.max_tot, my_max_tot);
   if (my_bad) *a.bad = 1u;
-  if (my_modes) atomicAdd(a.bad + 1, my_modes);
-  if (my_max_len > 8u) atomicMax(a.max_tot + 5, my_max_len);
+  if (my_modes) atomicAdd(a.bad + (kFlagOverlapLists - kFlagHintBroken), my_modes);
+  if (my_max_len > 8u) atomicMax(a.max_tot + kFlagMaxLen, my_max_len);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2271,8 +2271,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NL <= 3 ? G
   }
   if (my_max_tot) atomicMax(a.max_tot, my_max_tot);
   if (my_bad) *a.bad = 1u;
-  if (my_modes) atomicAdd(a.bad + 1, my_modes);
-  if (my_max_len > 8u) atomicMax(a.max_tot + 5, my_max_len);
+  if (my_modes) atomicAdd(a.bad + (kFlagOverlapLists - kFlagHintBroken), my_modes);
+  if (my_max_len > 8u) atomicMax(a.max_tot + kFlagMaxLen, my_max_len);
 }
 
 hipError_t launch_stats_ie(const StatsArgs& a, int method, hipStream_t stream) {

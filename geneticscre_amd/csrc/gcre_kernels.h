@@ -82,7 +82,6 @@ struct SparseArgs {
   int waves_per_xcd;         // persistent waves per XCD (grid = 8 * waves_per_xcd / 4 blocks)
   uint32_t mt_rows;
   uint32_t zoff;             // byte offset of the all-zero mask row = (mt_rows - 1) * 256
-  int ablate;                // diagnostics only (GCRE_SPARSE_ABLATE)
 };
 constexpr int kSparseTile = 2048;
 constexpr int kSparseSegMax = 64;
@@ -193,6 +192,22 @@ hipError_t launch_masks_from_words(const uint64_t* packed, int nrows_in, const G
 hipError_t launch_expand(const int64_t* path_idx, const int64_t* location, int64_t n_uids, const int32_t* signs,
                          int path_length, int method, int64_t first, int64_t count, uint32_t* row0, uint32_t* row1,
                          hipStream_t stream);
+
+// The flag block of a chunk's inspector (StatsArgs::max_tot, ::bad, ::ov_count; IeArgs::stats): 8 words, zeroed by the host
+// in front of the inspector.  Word kFlagOverReserved is the JOIN's, not the chunk's: the long-list area of a kept set's recipe
+// fills across the chunks of the join, so the host writes the join's count of entries reserved so far (JoinRun::over_next)
+// into it in front of every inspector launch that fills a recipe -- a chunk replayed from the inspection cache never touched
+// the block, and an ahead inspection ran on another one.  Words 6-7 belong to the join too.
+enum FlagWord : int {
+  kFlagMaxTot = 0,         // largest carrier total of the chunk
+  kFlagHintBroken = 1,     // some joined path differs from paths0 | reduced row
+  kFlagOverlapLists = 2,   // lists in overlap mode
+  kFlagLookupTiles = 3,    // joined-path tiles the pruned kernel looked up
+  kFlagOverReserved = 4,   // entries reserved in the long-list area
+  kFlagMaxLen = 5,         // longest list (padded)
+  kFlagRangeUnion = 6,     // 6-7: verdict of the range-union check of a hinted join (k_range_union)
+  kFlagWords = 8,
+};
 
 struct StatsArgs {
   const uint64_t* p0;

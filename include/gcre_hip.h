@@ -178,9 +178,9 @@ int gcre_join_uids(gcre_ctx* ctx, const gcre_uids* uids, const gcre_pathset* pat
  * gcre_join / gcre_join_uids call on the context runs that join's inspector on a stream of its own as soon as its own kernels
  * are in flight, into the registered join index's inspection cache, and the registered join -- the same index, operands, kept
  * set and opts, called next -- starts at its permutation kernel.  Needs the inspection cache (gcre_set_inspect_cache(ctx, 1)
- * for the pass) and GCRE_AHEAD=1 in the environment: it is OFF by default -- measured, it does not pay (both kernels fill the
- * GPU) -- and without either the call registers nothing and every join runs whole.  uids = NULL
- * cancels a registration; freeing a registered object cancels it too.  Results never depend on it. */
+ * for the pass).  It is ON by default: ResidentPlan registers the chain for plans of up to 64 M joined paths (GCRE_AHEAD=1:
+ * for any size); GCRE_AHEAD=0 turns it off, and then, or without the cache, the call registers nothing and every join runs
+ * whole.  uids = NULL cancels a registration; freeing a registered object cancels it too.  Results never depend on it. */
 int gcre_join_ahead(gcre_ctx* ctx, const gcre_uids* uids, const gcre_pathset* paths0, const gcre_pathset* paths1,
                     gcre_pathset* res, const gcre_join_opts* opts);
 
