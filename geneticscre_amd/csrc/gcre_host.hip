@@ -2073,8 +2073,10 @@ int inspect_chunk(JoinRun& R, ChunkRun& C, ChunkEnd* end) {
     HIP_TRY(c, hold(C, b.linfo, nl, st));
     HIP_TRY(c, hold(C, b.lover, nl, st));
     HIP_TRY(c, hold(C, b.dlist, nl * 8 + 16, st));
-    // + the waves' chunk slack: every wave of the inspector may leave most of a 2048-entry reservation unused
-    const size_t over_slack = (std::min<size_t>(16384, ((size_t)n + 15) / 16 * 4) + 2) * 2048;
+    // + the waves' chunk slack: every wave of the inspector may leave most of a kOverChunk reservation unused (no
+    // inspector has more waves than k_stats_ie's grid of one block per kStatsIeBlockPaths paths)
+    const size_t ie_blocks = ((size_t)n + kStatsIeBlockPaths - 1) / kStatsIeBlockPaths;
+    const size_t over_slack = (std::min<size_t>((size_t)kInspectMaxBlocks, ie_blocks) * kInspectBlockWaves + 2) * kOverChunk;
     HIP_TRY(c, hold(C, b.dover, std::max<size_t>(b.dover.cap, nl * 2 + over_slack), st));
     if (rcp) {   // straight into the recipe of the kept set (absolute row = cb + i)
       C.rowz = rcp->rowz.p + cb;

@@ -227,9 +227,9 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(L
   // (issue), slot_at = its 8-entry slot, lover_at = where its lover word sits (long lists)
   auto add_half = [&](u32 (&C)[L], const auto& Bx, const u32 (&y)[YW], const u32 (&Z)[LZ], u32 info, const u32 GCRE_CONSTANT* slot_at,
                       const u32 GCRE_CONSTANT* lover_at) {
-    const u32 len = info & kLinfoLenMask;
-    const bool overlap = (info & 1u) != 0u;
-    const u32 real = len - (info >> 28);
+    const u32 len = linfo_len(info);
+    const bool overlap = linfo_overlap(info);
+    const u32 real = len - linfo_pad(info);
     u32 S4[4];
     {
       const u32 y03[4] = {y[0], y[1], y[2], y[3]};
@@ -320,7 +320,7 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(L
   // the loads of one list a path ahead: its first four mask rows (none when the list is empty) and, for an overlap list,
   // the planes of the added row-half
   auto issue = [&](u32 info, u32 zu, const SlotV offs, u32 (&yy)[YW], u32 (&ZZ)[LZ]) {
-    const u32 real = (info & kLinfoLenMask) - (info >> 28);
+    const u32 real = linfo_true_len(info);
     if (YW == 8 && real > 4u) {
 #pragma unroll
       for (int j = 0; j < 8; j++) yy[j % YW] = __builtin_amdgcn_raw_buffer_load_b32(mt, lane4, offs[j % YW], 0);
@@ -336,7 +336,7 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(L
 #pragma unroll
       for (int j = 0; j < 4; j++) yy[j] = 0u;
     }
-    if (info & 1u) {
+    if (linfo_overlap(info)) {
       __amdgpu_buffer_rsrc_t rz = __builtin_amdgcn_make_buffer_rsrc((void*)(k_planesz + (u64)zu * 1024u), 0, 0x7fffffff, 0x00020000);
 #pragma unroll
       for (int j = 0; j < GZ; j++) {
@@ -440,8 +440,10 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(L
       {
         const u32 i0 = a.linfo[(u64)qv * 2], i1 = a.linfo[(u64)qv * 2 + 1];
         const u32 t0_ = a.tot[(u64)qv * 2], t1_ = a.tot[(u64)qv * 2 + 1];
-        const bool e0 = !(i0 & 1u) && (i0 & kLinfoLenMask) == (i0 >> 28);
-        const bool e1 = !(i1 & 1u) && (i1 & kLinfoLenMask) == (i1 >> 28);
+        // an empty delta list: that half is paths0's.  (i & kLinfoLenMask) is linfo_len(i) written out: with the helper
+        // here the compiler schedules this kernel differently
+        const bool e0 = !linfo_overlap(i0) && (i0 & kLinfoLenMask) == linfo_pad(i0);
+        const bool e1 = !linfo_overlap(i1) && (i1 & kLinfoLenMask) == linfo_pad(i1);
         pm0 = __builtin_amdgcn_ballot_w64(inl && e1);              // the (+) half changes (or neither)
         pm1 = __builtin_amdgcn_ballot_w64(inl && e0 && !e1);       // the (-) half changes
         pm2 = __builtin_amdgcn_ballot_w64(inl && !e0 && !e1);      // both change
@@ -479,14 +481,14 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(L
 #pragma unroll
         for (int h = 0; h < 2; h++) {
           const u32 rinfo = h ? ri1 : ri0;
-          const u32 rlen = rinfo & kLinfoLenMask;
-          if (!(rinfo & 1u) && rlen == (rinfo >> 28)) continue;   // the producing join left this half as it was
+          const u32 rlen = linfo_len(rinfo);
+          if (!linfo_overlap(rinfo) && rlen == linfo_pad(rinfo)) continue;   // the producing join left this half as it was
           const u32x8 ro = *(const u32x8 GCRE_CONSTANT*)(a.rec_slot + ((u64)row0 * 2 + h) * 8u);
           u32 yr[8];
 #pragma unroll
           for (int j = 0; j < 8; j++) yr[j] = __builtin_amdgcn_raw_buffer_load_b32(mt, lane4, ro[j], 0);
           u32 ZR[LP];
-          if (rinfo & 1u) {
+          if (linfo_overlap(rinfo)) {
             const u32 hz = (rzr >> 31) ? (u32)(1 - h) : (u32)h;
             load_groups(ZR, a.rec_planes_z, ((u64)kt * (u64)a.rec_rows_z + (u64)(rzr & 0x7fffffffu) * 2 + hz) * (u64)a.rec_gz, a.rec_gz);
           }
@@ -498,7 +500,7 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(L
             for (int l = 0; l < L; l++) S[l] = (l < 4) ? S4[l < 4 ? l : 0] : 0u;
           }
           if (rlen > 8u) sum_more(S, rlen, (const u32 GCRE_CONSTANT*)a.rec_over, r_lover + (u64)row0 * 2 + h);
-          if (rinfo & 1u) {   // B = A + Z - S
+          if (linfo_overlap(rinfo)) {   // B = A + Z - S
             u32 cy = 0u, bw = 0u;
 #pragma unroll
             for (int l = 0; l < L; l++) {

@@ -260,7 +260,7 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(G
             u32 ro[8];
 #pragma unroll
             for (int j = 0; j < 8; j++) ro[j] = rdlane(hdr[g], 8 + j);
-            const u32 rtrue = (rinfo_g[g] & kLinfoLenMask) - (rinfo_g[g] >> 28);   // entries that are not padding
+            const u32 rtrue = linfo_true_len(rinfo_g[g]);   // entries that are not padding
 #pragma unroll
             for (int j = 0; j < 8; j++) {
               yr[REC ? g : 0][j] = 0u;
@@ -268,7 +268,7 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(G
             }
             // the row's carrier total bounds the counts of everything it was made from: planes above it are zero and are
             // not read (3 KB -> 2 KB of HBM per segment and tile for most rows: this load is the kernel's HBM traffic)
-            const int ga_need = (int)((rinfo_g[g] >> 1) & 3u) + 1;
+            const int ga_need = (int)linfo_groups(rinfo_g[g]) + 1;
             load_groups(Bp, a.rec_planes_a, ((u64)kt * (u64)a.rec_rows_a + (u64)ra) * (u64)a.rec_ga, ga_need < a.rec_ga ? ga_need : a.rec_ga);
           }
 #pragma unroll
@@ -288,7 +288,7 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(G
           if ((u32)g < qcnt) {
             if (rz_g[g] != rz_g[0]) load_groups(ZR, a.rec_planes_z, ((u64)kt * (u64)a.rec_rows_z + (u64)rz_g[g]) * (u64)a.rec_gz, a.rec_gz);
             const u32 rinfo = rinfo_g[g];
-            const u32 rlen = rinfo & kLinfoLenMask;
+            const u32 rlen = linfo_len(rinfo);
             u32 S[L];
             {
               u32 S4[4];
@@ -314,7 +314,7 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(G
                 }
               }
             }
-            if (rinfo & 1u) {   // B = A + Z - S
+            if (linfo_overlap(rinfo)) {   // B = A + Z - S
               u32 cy = 0u, bw = 0u;
 #pragma unroll
               for (int l = 0; l < L; l++) {
@@ -345,11 +345,11 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(G
         if ((u32)g < qcnt) {
           const u32 lh = a.ladder[lad_row + totv[g]];
           const u32 r0 = infov[g];
-          const u32 ov = (r0 & kLinfoLenMask) - (r0 >> 28);
+          const u32 ov = linfo_true_len(r0);
           const u32 lo = lh & 0xffffu;
           const u32 lo2 = lo ? lo + ov : 0u;              // counts are never negative: lo = 0 needs no margin
           lhv[g] = lh;
-          lfv[g] = ((r0 & 1u) == 0u || (lo2 >> L) != 0u) ? 1u : ((lh & 0xffff0000u) | lo2);
+          lfv[g] = (!linfo_overlap(r0) || (lo2 >> L) != 0u) ? 1u : ((lh & 0xffff0000u) | lo2);
         }
       }
 
@@ -404,8 +404,10 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(G
         const u32 info = rdlane(infov[g], t);
         // (a path with many flagged permutations -- dense genotypes, where the margin eats the interval -- is not worth
         // the look: it goes to the exact pass as before)
+        // ((info & 1u) != 0u is linfo_overlap(info) written out: with the helper here the compiler schedules this kernel
+        // differently)
         if (k_lad_mode == 0u && (info & 1u) != 0u && __builtin_amdgcn_ballot_w64(__builtin_popcount(fm) > GCRE_REFINE_MAX) == 0ull) {
-          const u32 ov = (info & kLinfoLenMask) - (info >> 28);
+          const u32 ov = linfo_true_len(info);
           const u32* lad_t = a.ladder + rdlane(totv[g], t);
           u32 Wp[L];
           u32 c2 = 0u;
@@ -479,17 +481,17 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(G
         return it;
       };
       auto item_issue = [&](const Item& it, u32 (&yy)[8], u32 (&ZZ)[LZ]) {
-        const u32 ov = (it.info & kLinfoLenMask) - (it.info >> 28);
+        const u32 ov = linfo_true_len(it.info);
 #pragma unroll
         for (int j = 0; j < 8; j++) {
           yy[j] = 0u;
           if ((u32)j < ov) yy[j] = __builtin_amdgcn_raw_buffer_load_b32(mt, lane4, it.o[j], 0);   // padding entries are not fetched
         }
-        if (it.info & 1u) issue(it.t, ZZ);
+        if (linfo_overlap(it.info)) issue(it.t, ZZ);
       };
       auto exact_f = [&](const Item& it, const u32 (&Bg)[L], const u32 (&y)[8], const u32 (&Z)[LZ]) {
-        const u32 len = it.info & kLinfoLenMask;
-        const bool overlap = (it.info & 1u) != 0u;
+        const u32 len = linfo_len(it.info);
+        const bool overlap = linfo_overlap(it.info);
         const u32 lo = it.lh & 0xffffu, hi = it.lh >> 16;
         u32 S4[4];
         sum8(y, S4);

@@ -89,9 +89,20 @@ hipError_t launch_null_sparse(const SparseArgs& a, int method, int planes, hipSt
 int sparse_max_waves_per_cu(int method, int planes);   // resident waves per CU of the variant chosen for `planes` counter planes
 // ---- inclusion-exclusion null kernel on count planes (gcre_ie.hip) ----
 constexpr int kRecSegWords = 12;
-// linfo word of a list: padded length (multiple of 8, >= 8) | mode (bit 0: 1 = overlap list) | (padding entries) << 28,
+// linfo word of a list, written by the inspectors (gcre_inspect.hip):
+//   bit 0       mode: 1 = overlap list, 0 = delta list
+//   bits 1-2    plane groups of the producing row that can be non-zero, minus one (only k_fill_rec_segs' copy of the word)
+//   bits 3-27   padded length: a multiple of 8, at least 8
+//   bits 28-31  padding entries
 // so that the list's true length = padded length - padding is known without walking it (the bound filter of k_null_ie_m1)
 constexpr uint32_t kLinfoLenMask = 0x0ffffff8u;
+__host__ __device__ __forceinline__ constexpr uint32_t linfo_make(uint32_t len8, uint32_t mode, uint32_t len) { return len8 | mode | ((len8 - len) << 28); }
+__host__ __device__ __forceinline__ constexpr uint32_t linfo_with_groups(uint32_t info, uint32_t extra) { return info | (extra << 1); }
+__host__ __device__ __forceinline__ constexpr bool linfo_overlap(uint32_t info) { return (info & 1u) != 0u; }
+__host__ __device__ __forceinline__ constexpr uint32_t linfo_groups(uint32_t info) { return (info >> 1) & 3u; }
+__host__ __device__ __forceinline__ constexpr uint32_t linfo_len(uint32_t info) { return info & kLinfoLenMask; }
+__host__ __device__ __forceinline__ constexpr uint32_t linfo_pad(uint32_t info) { return info >> 28; }
+__host__ __device__ __forceinline__ constexpr uint32_t linfo_true_len(uint32_t info) { return linfo_len(info) - linfo_pad(info); }
 constexpr int kLadderLevels = 256;   // pruning thresholds j / kLadderPerUnit, j = 0 .. kLadderLevels-1
 constexpr int kLadderPerUnit = 8;
 constexpr int kLadder2Levels = 352;  // signed method: rows r <-> threshold r / (2 kLadderPerUnit), up to 4/3 of the method-1 range
@@ -251,8 +262,16 @@ struct StatsArgs {
   int S;
   int Wp;
 };
+// The long-list area (StatsArgs::over) is handed out in chunks: a wave of an inspector reserves kOverChunk entries at a
+// time (more when one round of its lists needs more), so a launch can leave most of a chunk per wave unused.  An
+// inspector's grid is at most kInspectMaxBlocks blocks of kInspectBlockWaves waves: the host sizes the area's slack
+// from these.
+constexpr uint32_t kOverChunk = 2048;
+constexpr int kInspectBlockWaves = 4;
+constexpr int kInspectMaxBlocks = 256 * 16;
+constexpr int kStatsIeBlockPaths = 4 * kInspectBlockWaves;   // k_stats_ie: four paths per wave and pass, the most waves per path
 hipError_t launch_stats(const StatsArgs& a, int method, hipStream_t stream);
-hipError_t launch_stats_ie(const StatsArgs& a, int method, hipStream_t stream);   // gcre_ie.hip
+hipError_t launch_stats_ie(const StatsArgs& a, int method, hipStream_t stream);   // gcre_inspect.hip
 hipError_t launch_range_union(const uint64_t* p1, const uint64_t* pz, const int32_t* zindex, const int32_t* pair_range,
                               const int64_t* pair_loc, int64_t npairs, int S, int Wp, int method, uint64_t* excess,
                               uint32_t* bad, hipStream_t stream);
