@@ -84,6 +84,25 @@ class gcre_pp_input(ctypes.Structure):
                 ("window_perms", ctypes.c_int)]
 
 
+class gcre_dp_input(ctypes.Structure):
+    _fields_ = [("method", ctypes.c_int32), ("n_cases", ctypes.c_int32), ("n_ctrls", ctypes.c_int32),
+                ("n_paths", ctypes.c_int32), ("path_len", ctypes.c_void_p), ("path_rows", ctypes.c_void_p),
+                ("path_sign", ctypes.c_void_p), ("rows", ctypes.c_void_p), ("n_rows", ctypes.c_int32),
+                ("stratum", ctypes.c_void_p), ("n_strata", ctypes.c_int32), ("iterations", ctypes.c_int32),
+                ("seed", ctypes.c_uint64), ("strata_out", ctypes.c_void_p)]
+
+
+# gcre_dp_split / gcre_dp_stratum as numpy records (C layout): the library writes straight into these arrays
+DP_SPLIT = np.dtype([("path", "<i4"), ("direction", "<i4"), ("j", "<i4"), ("valid", "<i4"),
+                     ("cases1", "<i4"), ("ctrls1", "<i4"), ("cases2", "<i4"), ("ctrls2", "<i4"),
+                     ("case_pos1", "<i4"), ("ctrl_pos1", "<i4"), ("case_neg1", "<i4"), ("ctrl_neg1", "<i4"),
+                     ("case_pos2", "<i4"), ("ctrl_pos2", "<i4"), ("case_neg2", "<i4"), ("ctrl_neg2", "<i4"),
+                     ("score", "<f8"), ("k_pos", "<i4"), ("pop_pos", "<i4"), ("succ_pos", "<i4"),
+                     ("k_neg", "<i4"), ("pop_neg", "<i4"), ("succ_neg", "<i4"),
+                     ("strata_off", "<i8"), ("n_ge", "<i8"), ("pvalue", "<f8")], align=True)
+DP_STRATUM = np.dtype([("pop", "<i4"), ("cases", "<i4"), ("k_pos", "<i4"), ("k_neg", "<i4")])
+
+
 # every symbol include/gcre_hip.h declares; tests check that the library exports all of them
 EXPORTS = [
     "gcre_create", "gcre_destroy", "gcre_last_error", "gcre_abi_version", "gcre_set_top_k", "gcre_width_ul",
@@ -96,6 +115,7 @@ EXPORTS = [
     "gcre_set_perm_window", "gcre_plan_perm_window", "gcre_process_paths_devices",
     "gcre_set_inspect_cache", "gcre_drop_inspections", "gcre_build_flags", "gcre_device_count",
     "gcre_rccl_selftest", "gcre_rccl_collectives", "gcre_join_ahead",
+    "gcre_decorated_splits", "gcre_decorated_pvalues",
 ]
 
 
@@ -192,6 +212,83 @@ def load_library():
 
 def _ptr(a: Optional[np.ndarray]):
     return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+
+
+def _decorated_lib():
+    """The library with the decorated-p-value entries bound.  Bound on first use, so that a GCRE_LIB variant built before
+    they existed still loads for everything else."""
+    lib = load_library()
+    if not hasattr(lib, "gcre_decorated_pvalues"):
+        raise GcreError(f"{lib._name} has no decorated p-values (gcre_decorated_splits): rebuild it")
+    if lib.gcre_decorated_splits.argtypes is None:
+        P, I, I64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64
+        lib.gcre_decorated_splits.argtypes = [ctypes.POINTER(gcre_dp_input), P, I, I, I, P, I64, ctypes.POINTER(I64)]
+        lib.gcre_decorated_pvalues.argtypes = [P, ctypes.POINTER(gcre_dp_input), P, I64, ctypes.POINTER(I64), P]
+    return lib
+
+
+class _DpInput:
+    """gcre_dp_input over numpy arrays it keeps alive.  ``paths``: one sequence of data-row indices per path (-1 = NA gene);
+    ``rows``: the 0/1 carrier matrix [rows][patients]; ``signs``: per path, +1 / -1 per gene (None = all +1); ``strata``:
+    one id per patient, any integers (mapped to 0..n_strata-1 in ascending order of id)."""
+
+    def __init__(self, method, n_cases, n_ctrls, paths, rows, signs, strata, iterations, seed):
+        if isinstance(method, str):
+            method = 1 if method == "method1" else 2
+        n = int(n_cases) + int(n_ctrls)
+        P = len(paths)
+        self.path_len = np.array([len(p) for p in paths], dtype=np.int32)
+        if P and (self.path_len.min() < 1 or self.path_len.max() > 5):
+            raise ValueError("a path has 1 to 5 genes")
+        self.path_rows = np.full((max(P, 1), 5), -1, dtype=np.int32)
+        self.path_sign = np.ones((max(P, 1), 5), dtype=np.int32)
+        for i, p in enumerate(paths):
+            self.path_rows[i, :len(p)] = p
+            if signs is not None:
+                self.path_sign[i, :len(p)] = signs[i]
+        d = np.asarray(rows).reshape(-1, n) != 0
+        W = (n + 63) // 64
+        bits = np.zeros((d.shape[0], W * 64), dtype=bool)
+        bits[:, :n] = d
+        self.rows = np.ascontiguousarray(np.packbits(bits, axis=1, bitorder="little").view("<u8"))
+        self.n_strata = 0
+        self.stratum = None
+        if strata is not None:
+            ids, inv = np.unique(np.asarray(strata).reshape(-1), return_inverse=True)
+            if len(inv) != n:
+                raise ValueError("strata: one stratum id per patient")
+            self.stratum = np.ascontiguousarray(inv, dtype=np.int32)
+            self.n_strata = len(ids)
+        self.S = int(sum(2 * (L - 1) for L in self.path_len.tolist()))
+        self.st_out = np.zeros(max(self.S, 1) * max(self.n_strata, 1), dtype=DP_STRATUM) if strata is not None else None
+        self.c = gcre_dp_input(int(method), int(n_cases), int(n_ctrls), P, _ptr(self.path_len), _ptr(self.path_rows),
+                               _ptr(self.path_sign), _ptr(self.rows), self.rows.shape[0], _ptr(self.stratum),
+                               self.n_strata, int(iterations), int(seed) & (2**64 - 1), _ptr(self.st_out))
+
+    def out(self) -> np.ndarray:
+        return np.zeros(max(self.S, 1), dtype=DP_SPLIT)
+
+    def strata_records(self) -> Optional[np.ndarray]:
+        return None if self.st_out is None else self.st_out[:self.S * self.n_strata].reshape(self.S, self.n_strata)
+
+
+def decorated_splits(method, n_cases: int, n_ctrls: int, paths, rows, signs=None, table=None, strata=None,
+                     iterations: int = 0, seed: int = 0):
+    """Host stage of the decorated p-values (gcre_decorated_splits, no device needed): one DP_SPLIT record per split --
+    counts, observed score (NaN without ``table``), urns -- and, with ``strata``, the [splits][n_strata] DP_STRATUM urns.
+    p-values stay NaN: the permutations run on the device (JoinExec.decorated_pvalues)."""
+    lib = _decorated_lib()
+    d = _DpInput(method, n_cases, n_ctrls, paths, rows, signs, strata, iterations, seed)
+    out = d.out()
+    t = None if table is None else np.ascontiguousarray(table, dtype=np.float64)
+    n_out = ctypes.c_int64(0)
+    rc = lib.gcre_decorated_splits(ctypes.byref(d.c), _ptr(t), 0 if t is None else t.shape[0],
+                                   0 if t is None else t.shape[1], 0, _ptr(out), len(out), ctypes.byref(n_out))
+    if rc == GCRE_ERR_RANGE:
+        raise IndexError("gcre_decorated_splits: a row index or stratum id is out of range")
+    if rc != GCRE_OK:
+        raise ValueError(f"gcre_decorated_splits: bad input ({rc})")
+    return out[:n_out.value], d.strata_records()
 
 
 @dataclass
@@ -402,6 +499,21 @@ class JoinExec:
         if w < 0:
             self._check(w)
         return max(int(w), 1)
+
+    def decorated_pvalues(self, paths, rows, signs=None, strata=None, seed: int = 0, return_counts: bool = False):
+        """Decorated p-values (R/DecoratedPvalue.R) of ``paths`` on this context's device and value table, ``iters``
+        permutations per split: a DP_SPLIT record per split (paths in order, each Forward then Backward).  ``paths`` are
+        rows of ``rows`` (-1 = NA gene), ``signs`` +1 / -1 per gene (read by method 2).  With ``return_counts`` also the
+        [splits][iters][2] urn successes of every permutation (cases of the pos draw, controls of the neg draw)."""
+        lib = _decorated_lib()
+        d = _DpInput(self.method, self.num_cases, self.num_ctrls, paths, rows, signs, strata, self.iters, seed)
+        out = d.out()
+        counts = np.zeros((max(d.S, 1), self.iters, 2), dtype=np.int32) if return_counts else None
+        n_out = ctypes.c_int64(0)
+        self._check(lib.gcre_decorated_pvalues(self._h, ctypes.byref(d.c), _ptr(out), len(out), ctypes.byref(n_out),
+                                               _ptr(counts)))
+        rec = out[:n_out.value]
+        return (rec, counts[:n_out.value]) if return_counts else rec
 
     def perm_mask(self, r: int) -> np.ndarray:
         out = np.zeros(self.width_ul, dtype=np.uint64)

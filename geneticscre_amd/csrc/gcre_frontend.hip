@@ -23,15 +23,8 @@ namespace gcre {
 // Permutation r keeps a uniformly random n_cases-subset of the patients as cases (what a uniform permutation of the
 // labels induces, Utils.R:22-46 + 246-262); with strata the number of cases inside every stratum is preserved
 // (Utils.R:8-13).  Selection sampling (Knuth, Algorithm S) per stratum: patient c becomes a case with probability
-// need/remaining.  Random numbers are a pure function of (seed, r, c) -- splitmix64 finaliser -- so the CPU
+// need/remaining.  Random numbers are a pure function of (seed, r, c) -- gcre_mix64, gcre_kernels.h -- so the CPU
 // restatement in the tests reproduces every mask bit.
-__host__ __device__ inline uint64_t gcre_mix64(uint64_t z) {
-  z += 0x9e3779b97f4a7c15ull;
-  z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
-  z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
-  return z ^ (z >> 31);
-}
-
 __global__ void k_generate_masks(uint64_t seed, int K, int n, int n_strata, const int32_t* stratum, const uint32_t* cases_in,
                                  const uint32_t* size_of, uint32_t* work, int W32p, int Kpad, uint32_t* masks) {
   const int r = blockIdx.x * blockDim.x + threadIdx.x;

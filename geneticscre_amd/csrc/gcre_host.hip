@@ -3089,6 +3089,100 @@ int gcre_generate_perm_masks(gcre_ctx* c, uint64_t seed, const int32_t* stratum,
   return GCRE_OK;
 }
 
+int gcre_decorated_pvalues(gcre_ctx* c, const gcre_dp_input* in, gcre_dp_split* out, int64_t cap, int64_t* n_out,
+                           int32_t* perm_counts) {
+  if (!c) return GCRE_ERR_ARG;
+  if (!in || !n_out) return fail(c, GCRE_ERR_ARG, "decorated_pvalues: NULL argument");
+  const Geometry& g = c->g;
+  if (!c->have_table || !c->d_dvt) return fail(c, GCRE_ERR_ASSERT, "assertion: decorated_pvalues needs a value table");
+  if (in->method != g.method || in->n_cases != g.n_cases || in->n_cases + in->n_ctrls != g.n)
+    return fail(c, GCRE_ERR_ASSERT, "assertion: decorated_pvalues input does not match the context (method, cases, controls)");
+  // the host stage: counts and urns (the observed scores come from the device's own table below)
+  gcre_dp_input hin = *in;
+  std::vector<gcre_dp_stratum> st;
+  if (hin.stratum && !hin.strata_out && hin.n_strata > 0 && cap > 0) {
+    st.resize((size_t)cap * (size_t)hin.n_strata);
+    hin.strata_out = st.data();
+  }
+  int rc = gcre_decorated_splits(&hin, nullptr, 0, 0, 0, out, cap, n_out);
+  if (rc == GCRE_ERR_RANGE) return fail(c, rc, "decorated_pvalues: out of range (row index, stratum id or output capacity)");
+  if (rc != GCRE_OK) return fail(c, rc, "decorated_pvalues: bad input");
+  const int64_t S = *n_out;
+  const int K = in->iterations;
+  if (S == 0) return GCRE_OK;
+  if (S > 0x7fffffff) return fail(c, GCRE_ERR_ARG, "decorated_pvalues: too many splits");
+  // the kernel's view: sub-path-1 counts, observed counts, urns, strata that draw, stream key
+  std::vector<DpUrns> urns((size_t)S);
+  std::vector<DpStratum> dst;
+  for (int64_t i = 0; i < S; i++) {
+    const gcre_dp_split& o = out[i];
+    DpUrns& u = urns[(size_t)i];
+    std::memset(&u, 0, sizeof u);
+    u.key = dp_split_key(in->seed, i);
+    if (!o.valid) continue;   // counts 0, no draws: p-value NaN below
+    u.case_pos1 = o.case_pos1;
+    u.ctrl_pos1 = o.ctrl_pos1;
+    u.case_neg1 = o.case_neg1;
+    u.ctrl_neg1 = o.ctrl_neg1;
+    u.case_pos2 = o.case_pos2;
+    u.ctrl_pos2 = o.ctrl_pos2;
+    u.case_neg2 = o.case_neg2;
+    u.ctrl_neg2 = o.ctrl_neg2;
+    u.k_pos = o.k_pos;
+    u.k_neg = o.k_neg;
+    u.pop_pos = o.pop_pos;
+    u.succ_pos = o.succ_pos;
+    u.pop_neg = o.pop_neg;
+    u.succ_neg = o.succ_neg;
+    if (o.strata_off >= 0) {
+      u.st_off = (int32_t)dst.size();
+      for (int s = 0; s < in->n_strata; s++) {
+        const gcre_dp_stratum& q = hin.strata_out[o.strata_off + s];
+        if (q.k_pos + q.k_neg > 0) dst.push_back({q.pop, q.cases, q.k_pos, q.k_neg});
+      }
+      u.st_n = (int32_t)dst.size() - u.st_off;
+      // every draw of a stratified split happens inside its strata (st_n == 0 with k_pos == k_neg == 0: nothing to draw)
+    }
+  }
+  if (dst.size() > 0x7fffffffu) return fail(c, GCRE_ERR_ARG, "decorated_pvalues: too many strata");
+  (void)hipSetDevice(c->device);
+  DpUrns* d_urns = nullptr;
+  DpStratum* d_st = nullptr;
+  double* d_obs = nullptr;
+  unsigned long long* d_ge = nullptr;
+  int32_t* d_pc = nullptr;
+  const size_t pc_bytes = perm_counts ? (size_t)S * (size_t)K * 2 * 4 : 0;
+  std::vector<double> obs((size_t)S);
+  std::vector<unsigned long long> ge((size_t)S, 0);
+  hipError_t e = hipMalloc((void**)&d_urns, (size_t)S * sizeof(DpUrns));
+  if (e == hipSuccess) e = hipMalloc((void**)&d_st, std::max<size_t>(dst.size(), 1) * sizeof(DpStratum));
+  if (e == hipSuccess) e = hipMalloc((void**)&d_obs, (size_t)S * 8);
+  if (e == hipSuccess) e = hipMalloc((void**)&d_ge, (size_t)S * 8);
+  if (e == hipSuccess && pc_bytes) e = hipMalloc((void**)&d_pc, pc_bytes);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_urns, urns.data(), (size_t)S * sizeof(DpUrns), hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess && !dst.empty())
+    e = hipMemcpyAsync(d_st, dst.data(), dst.size() * sizeof(DpStratum), hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(d_ge, 0, (size_t)S * 8, c->stream);
+  if (e == hipSuccess) e = launch_decorated_observed(d_urns, (int)S, g.method, c->d_dvt, d_obs, c->stream);
+  if (e == hipSuccess)
+    e = launch_decorated_null(d_urns, d_st, (int)S, K, g.method, c->d_dvt, d_obs, d_ge, d_pc, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(obs.data(), d_obs, (size_t)S * 8, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(ge.data(), d_ge, (size_t)S * 8, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess && pc_bytes) e = hipMemcpyAsync(perm_counts, d_pc, pc_bytes, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  for (void* p : {(void*)d_urns, (void*)d_st, (void*)d_obs, (void*)d_ge, (void*)d_pc})
+    if (p) (void)hipFree(p);
+  if (e != hipSuccess) return fail(c, GCRE_ERR_DEVICE, std::string("decorated_pvalues: ") + hipGetErrorString(e));
+  for (int64_t i = 0; i < S; i++) {
+    gcre_dp_split& o = out[i];
+    if (!o.valid) continue;
+    o.score = obs[(size_t)i];
+    o.n_ge = (int64_t)ge[(size_t)i];
+    o.pvalue = K > 0 ? (double)o.n_ge / (double)K : std::numeric_limits<double>::quiet_NaN();
+  }
+  return GCRE_OK;
+}
+
 int gcre_set_perm_window(gcre_ctx* c, int k0, int k1) {
   if (!c) return GCRE_ERR_ARG;
   const int K = c->g.K;

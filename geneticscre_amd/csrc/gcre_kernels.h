@@ -311,4 +311,41 @@ hipError_t launch_table_to_diag(const double* table, int nrow, int ncol, int col
 hipError_t launch_fill_u32(uint32_t* p, int64_t n, uint32_t v, hipStream_t stream);
 hipError_t launch_max_merge(uint32_t* dst, const uint32_t* src, int n, hipStream_t stream);
 
+// ---- decorated p-values (gcre_decorated.hip) ----
+// One split as k_decorated_null reads it: the sub-path-1 counts its scores add to, gene 2's observed counts, the two urns
+// (without strata) or a run of DpStratum entries, and the key of its random stream.
+struct DpUrns {
+  int32_t case_pos1, ctrl_pos1, case_neg1, ctrl_neg1;   // gcre_dp_split's
+  int32_t case_pos2, ctrl_pos2, case_neg2, ctrl_neg2;   // observed gene-2 counts (k_decorated_observed)
+  int32_t k_pos, pop_pos, succ_pos, k_neg;
+  int32_t pop_neg, succ_neg;
+  int32_t st_off, st_n;   // st_n > 0: the urns are DpStratum[st_off, st_off + st_n) (only strata that draw)
+  uint64_t key;           // dp_split_key(seed, split)
+  uint64_t pad;
+};
+struct DpStratum { int32_t pop, cases, k_pos, k_neg; };
+
+// splitmix64 finaliser: the counter-based random stream of the permutation masks and of the decorated draws
+__host__ __device__ inline uint64_t gcre_mix64(uint64_t z) {
+  z += 0x9e3779b97f4a7c15ull;
+  z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
+  z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
+  return z ^ (z >> 31);
+}
+// Draw t of permutation r of split s reads u = gcre_mix64(dp_perm_base(dp_split_key(seed, s), r) + t); t counts the draws
+// of the split's urns in order (strata ascending, pos before neg), skipped draws included.
+__host__ __device__ inline uint64_t dp_split_key(uint64_t seed, int64_t s) {
+  return gcre_mix64(seed ^ (0xd1b54a32d192ed03ull * (uint64_t)(s + 1)));
+}
+__host__ __device__ inline uint64_t dp_perm_base(uint64_t key, int64_t r) {
+  return gcre_mix64(key ^ (0x51ed270b7f3c9a1dull * (uint64_t)(r + 1)));
+}
+
+// obs[s] = the observed score of split s from d_dvt (what k_decorated_null compares against)
+hipError_t launch_decorated_observed(const DpUrns* urns, int S, int method, const double* dvt, double* obs,
+                                     hipStream_t stream);
+// n_ge[s] += permutations r < K of split s whose score >= obs[s]; perm_counts (optional) [S][K][2] = urn successes
+hipError_t launch_decorated_null(const DpUrns* urns, const DpStratum* strata, int S, int K, int method, const double* dvt,
+                                 const double* obs, unsigned long long* n_ge, int32_t* perm_counts, hipStream_t stream);
+
 }  // namespace gcre

@@ -4,12 +4,14 @@
   * ``uid_to_symbol``    uid paths -> gene-symbol paths                                  (R/Utils.R:50-95)
   * ``results_table``    p-values, the GWASPA.Results columns and their order            (R/ProcessPaths.R:272-326)
   * ``preprocess_table`` / ``prepare_inputs``  the dataset and network filtering         (R/Utils.R:162-199, ProcessPaths.R:131-176)
+  * ``decorated_table``  getDecoratedPvalues: the split-path table, permutations on the device  (R/DecoratedPvalue.R)
   * ``gwaspa``           the whole call, with the table / level tables / permutations built natively
 
 Host-side post-processing of <= top_k x 5 rows: string work, nothing here touches the scored path.
 """
 from __future__ import annotations
 
+import warnings
 from dataclasses import dataclass
 from typing import Dict, List, Optional, Sequence, Tuple
 
@@ -131,6 +133,93 @@ def results_table(level_results: Dict[str, object], path_length: int, frames: Di
     p = df["Pvalues"].to_numpy()
     order = np.lexsort((-df["Scores"].to_numpy(), np.where(np.isnan(p), np.inf, p)))   # order(): NA last, stable
     return df.iloc[order].reset_index(drop=True)
+
+
+DECORATED_COLUMNS = ["SignedPaths", "Paths", "Subpaths1", "Subpaths1_Cases", "Subpaths1_Controls", "Subpaths2",
+                     "Subpaths2_Cases", "Subpaths2_Controls", "Direction", "Lengths", "Scores", "Pvalues",
+                     "DecoratedPvalues", "Cases", "Controls"]
+DECORATED_PATH_LENGTH_WARNING = "Can only compute the Decorated P-values for pathLength > 1!"
+# the decorated draws are keyed by gcre_mix64(seed ^ this tag), a stream apart from the permutation masks' (ProcessPaths.R
+# uses one R RNG stream for both; any independent stream has the same distribution)
+DECORATED_SEED_TAG = 0x6465636F72617465
+
+
+def decorated_table(results_df, genes: Sequence[str], data: np.ndarray, n_cases: int, n_ctrls: int, signed: bool,
+                    n_permutations: int, strata: Optional[Sequence[int]] = None, seed: int = 0, device: int = 0, *,
+                    path_length: Optional[int] = None, exec_=None, table: Optional[np.ndarray] = None):
+    """getDecoratedPvalues (R/DecoratedPvalue.R:48-193) over a GWASPA.Results frame: every path of length L >= 2 split at
+    its 2(L-1) cut points, Forward then Backward, each split's decorated p-value drawn on the device (k_decorated_null).
+
+    ``genes`` / ``data`` are the dataset after ``preprocess_table`` (the function looks genes up by symbol there, as R
+    does after PreprocessTable); ``strata`` one id per patient column; ``signed`` selects method 2.  Rows follow
+    ``results_df`` within each length, lengths 2, 3, ...; length-1 rows are dropped (ProcessPaths.R:334).  With
+    ``path_length == 1`` it warns as GWASPA does and returns None.  ``exec_`` / ``table``: a JoinExec that already holds
+    the value table (its iterations must be ``n_permutations``) and the table itself, to avoid building them twice.
+    A path with an NA gene gets NaN; ``n_permutations == 0`` gives NaN everywhere (R: 0/0) and runs nothing on the device.
+    Deviations from R (the random stream, the column copy of :97): INTEGRATION.md.
+    """
+    import pandas as pd
+    from . import api
+
+    if path_length == 1:
+        warnings.warn(DECORATED_PATH_LENGTH_WARNING)
+        return None
+    method = 2 if signed else 1
+    row_of: Dict[str, int] = {}
+    for i, g in enumerate(genes):
+        row_of.setdefault(g, i)
+    lengths = results_df["Lengths"].to_numpy()
+    top = int(lengths.max()) if len(lengths) else 1
+    picked = [i for L in range(2, max(top, path_length or 0) + 1) for i in np.flatnonzero(lengths == L).tolist()]
+
+    # SignedPaths "g1 (+) -> g2 (-)": gene = first word, sign = (+) or anything else (DecoratedPvalue.R:112-119)
+    hops_of, paths, signs, used = [], [], [], {}
+    for i in picked:
+        hops = [h.split(" ") for h in str(results_df["SignedPaths"].iat[i]).split(" -> ")]
+        names = [h[0] for h in hops]
+        rows = []
+        for g in names:
+            r = row_of.get(g, -1) if g != "NA" else -1
+            rows.append(-1 if r < 0 else used.setdefault(r, len(used)))
+        hops_of.append(names)
+        paths.append(rows)
+        signs.append([1 if len(h) > 1 and h[1] == POS else -1 for h in hops])
+    data = np.asarray(data)
+    sub = data[list(used.keys())] if used else np.zeros((0, n_cases + n_ctrls), np.int32)
+
+    if n_permutations == 0 or not paths:
+        vt = api.values_table(n_cases, n_ctrls) if table is None else table
+        rec, _ = api.decorated_splits(method, n_cases, n_ctrls, paths, sub, signs, vt, strata)
+    else:
+        ex = exec_
+        if ex is None:
+            ex = api.JoinExec(method, n_cases, n_ctrls, n_permutations, device=device)
+            ex.set_value_table(api.values_table(n_cases, n_ctrls) if table is None else table)
+        try:
+            rec = ex.decorated_pvalues(paths, sub, signs, strata=strata, seed=seed)
+        finally:
+            if exec_ is None:
+                ex.close()
+
+    cols: Dict[str, list] = {c: [] for c in DECORATED_COLUMNS}
+    for s in rec:
+        i, names, j = picked[int(s["path"])], hops_of[int(s["path"])], int(s["j"])
+        if s["direction"] == 0:
+            sub1, gene2, direction = names[:j], names[j], "Forward"
+        else:
+            sub1, gene2, direction = names[j - 1:][::-1], names[j - 2], "Backward"
+        # DecoratedBestPaths[, c(1,2,10,11,12,14,15)] <- the path's GWASPA.Results row (INTEGRATION.md: the intent of :97)
+        for c in ("SignedPaths", "Paths", "Lengths", "Scores", "Pvalues", "Cases", "Controls"):
+            cols[c].append(results_df[c].iat[i])
+        cols["Subpaths1"].append(" -> ".join(sub1))
+        cols["Subpaths1_Cases"].append(int(s["cases1"]))
+        cols["Subpaths1_Controls"].append(int(s["ctrls1"]))
+        cols["Subpaths2"].append(gene2)
+        cols["Subpaths2_Cases"].append(int(s["cases2"]))
+        cols["Subpaths2_Controls"].append(int(s["ctrls2"]))
+        cols["Direction"].append(direction)
+        cols["DecoratedPvalues"].append(float(s["pvalue"]))
+    return pd.DataFrame(cols, columns=DECORATED_COLUMNS)
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -279,15 +368,19 @@ def frames_of(prep: Prepared, levels) -> Dict[str, Dict[str, np.ndarray]]:
 
 def gwaspa(genes: Sequence[str], data: np.ndarray, n_cases: int, n_ctrls: int, network, signed: bool = False,
            threshold: float = 0.05, top_k: int = 10, path_length: int = 5, n_permutations: int = 100,
-           strata: Optional[Sequence[int]] = None, seed: int = 0, device: int = 0) -> Dict[str, object]:
+           strata: Optional[Sequence[int]] = None, seed: int = 0, device: int = 0,
+           decorated_pvalues: bool = False) -> Dict[str, object]:
     """GWASPA (R/ProcessPaths.R:87-344) without R: dataset -> GWASPA.Results, scored on the MI355X.
 
     ``network`` = (ents_uid, ents_symbol, rel_src, rel_trg, rel_sign): the knowledge base getStringKB() would load
     (the packaged STRING tables are data, not code -- callers bring their own).  ``strata`` gives one stratum id
     per patient column (what the strata file resolves to, ProcessPaths.R:180-191).  The scoring table, the level
     tables and the permutation masks are built by the native builders; permutations are
-    drawn on the device from ``seed``, so two runs with the same seed return identical tables.  Decorated p-values
-    (R/DecoratedPvalue.R) are not computed.
+    drawn on the device from ``seed``, so two runs with the same seed return identical tables.
+
+    ``decorated_pvalues``: also return "Decorated.Pvalues.Results", the split-path table of ``decorated_table``
+    (R/DecoratedPvalue.R), drawn from a seed derived from ``seed`` (DECORATED_SEED_TAG).  R's GWASPA defaults to
+    ``Decorated.Pvalues = TRUE``; here the default is False.  With ``path_length == 1`` it warns as R does and adds nothing.
     """
     from . import api
     from .synth import Problem
@@ -320,5 +413,11 @@ def gwaspa(genes: Sequence[str], data: np.ndarray, n_cases: int, n_ctrls: int, n
     out = {"GWASPA.Results": results_table(lsts, path_length, frames_of(prep, levels),
                                            (prep.ents_uid, prep.ents_symbol), (prep.ents2_uid, prep.ents2_symbol)),
            "levels": lsts, "prepared": prep}
+    if decorated_pvalues:
+        dseed = int(api.load_library().gcre_mix64((int(seed) ^ DECORATED_SEED_TAG) & (2**64 - 1)))
+        dec = decorated_table(out["GWASPA.Results"], genes, data, n_cases, n_ctrls, signed, n_permutations, strata,
+                              dseed, device, path_length=path_length, exec_=ex, table=table)
+        if dec is not None:
+            out["Decorated.Pvalues.Results"] = dec
     ex.close()
     return out

@@ -322,6 +322,74 @@ int gcre_drop_inspections(gcre_ctx* ctx, int release_memory);
 /* read permutation mask r back as width_ul words (bit c = patient c is a case under permutation r) */
 int gcre_get_perm_mask(gcre_ctx* ctx, int r, uint64_t* out);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Decorated p-values (getDecoratedPvalues / computeDecoratedPvalue, R/DecoratedPvalue.R:48-304; GWASPA's second table,
+ * R/ProcessPaths.R:330-337).  Every path of length L >= 2 is split at its 2(L-1) cut points -- Forward j = 1..L-1:
+ * sub-path 1 = genes 1..j, gene 2 = g(j+1); Backward j = L..2: sub-path 1 = genes L..j, gene 2 = g(j-1) -- and the
+ * carriers gene 2 adds to sub-path 1 are tested against the same number of patients drawn without replacement from those
+ * sub-path 1 does not cover.  Only the number of cases among the drawn patients matters, so each draw is an urn process
+ * (DESIGN.md "Decorated p-values").  Draws come from a counter-based stream keyed by (seed, split, permutation), not
+ * from R's RNG: the table matches R in distribution. */
+
+/* One stratum of one split: the two urns drawn in it (DecoratedPvalue.R:240-273). */
+typedef struct {
+  int32_t pop;      /* |G_s|, G_s = stratum s minus the carriers of sub-path 1, both halves */
+  int32_t cases;    /* cases in G_s: the successes of the pos urn */
+  int32_t k_pos;    /* |pos2 ∩ G_s| patients drawn from G_s for the pos half */
+  int32_t k_neg;    /* |neg2 ∩ G_s| drawn from what the pos draw left of G_s; its successes are controls */
+} gcre_dp_stratum;
+
+typedef struct {
+  int32_t method;             /* 1: every gene is "pos"; 2: a gene tagged (-) is "neg" (DecoratedPvalue.R:126-130) */
+  int32_t n_cases, n_ctrls;   /* patients 0..n_cases-1 are the cases */
+  int32_t n_paths;
+  const int32_t* path_len;    /* [n_paths], 1..5; a length-1 path has no split */
+  const int32_t* path_rows;   /* [n_paths][5]: row of `rows` of each gene, -1 = NA gene (the whole path gets NaN) */
+  const int32_t* path_sign;   /* [n_paths][5]: -1 = (-), anything else (+); read by method 2 only; may be NULL */
+  const uint64_t* rows;       /* [n_rows][ceil(n/64)] carriers, bit c of word c/64 = patient c (bits >= n ignored) */
+  int32_t n_rows;
+  const int32_t* stratum;     /* optional [n]: stratum id 0..n_strata-1 of each patient */
+  int32_t n_strata;
+  int32_t iterations;         /* permutations per split */
+  uint64_t seed;
+  gcre_dp_stratum* strata_out;   /* output, required with `stratum`: [cap][n_strata] urns, split i at strata_off */
+} gcre_dp_input;
+
+/* One split (one row of Decorated.Pvalues.Results). */
+typedef struct {
+  int32_t path;        /* index into gcre_dp_input.path_len */
+  int32_t direction;   /* 0 = "Forward", 1 = "Backward" */
+  int32_t j;           /* R's j (1-based cut point of that direction's loop) */
+  int32_t valid;       /* 0: the path holds an NA gene -- counts 0, score and p-value NaN */
+  int32_t cases1, ctrls1, cases2, ctrls2;   /* Subpaths1_Cases .. Subpaths2_Controls: case_pos + case_neg, ... */
+  /* sub-path 1 per half, the neg half counted the other way round (case_neg1 = its controls, DecoratedPvalue.R:223-226) */
+  int32_t case_pos1, ctrl_pos1, case_neg1, ctrl_neg1;
+  int32_t case_pos2, ctrl_pos2, case_neg2, ctrl_neg2;   /* gene 2 minus sub-path 1 in its own half, counted the same way */
+  double score;        /* observed score; NaN from gcre_decorated_splits without a table */
+  /* the two urns without strata: draw k from a population of pop holding succ successes (pos half: cases outside pos1;
+     neg half: controls outside neg1).  With strata k_pos / k_neg are the totals over the strata, pop / succ are 0, and
+     the urns are strata_out[strata_off .. strata_off + n_strata) */
+  int32_t k_pos, pop_pos, succ_pos;
+  int32_t k_neg, pop_neg, succ_neg;
+  int64_t strata_off;  /* -1 without strata */
+  int64_t n_ge;        /* permutations whose score >= score (gcre_decorated_pvalues) */
+  double pvalue;       /* n_ge / iterations; NaN for an invalid split or 0 iterations */
+} gcre_dp_split;
+
+/* The host stage, no device needed: every split's counts, observed score (`table`: nrow x ncol doubles, col_major != 0
+ * for an R matrix, read as the device reads its copy -- -1 outside the table; NULL leaves the score NaN) and urn
+ * parameters.  Splits follow the paths in order, each path Forward then Backward.  *n_out = the number of splits;
+ * GCRE_ERR_RANGE when cap is smaller (nothing is written), or when a row index or a stratum id is out of range. */
+int gcre_decorated_splits(const gcre_dp_input* in, const double* table, int nrow, int ncol, int col_major,
+                          gcre_dp_split* out, int64_t cap, int64_t* n_out);
+
+/* gcre_decorated_splits, then k_decorated_null on the context's device: in->iterations permutations of every split,
+ * scored against the value table of gcre_set_value_table.  Fills score, n_ge and pvalue.  in->method, n_cases and
+ * n_ctrls must be the context's; in->strata_out may be NULL here.  perm_counts, optional [n_out][iterations][2]:
+ * successes of the pos urn (cases) and of the neg urn (controls) of every permutation. */
+int gcre_decorated_pvalues(gcre_ctx* ctx, const gcre_dp_input* in, gcre_dp_split* out, int64_t cap, int64_t* n_out,
+                           int32_t* perm_counts);
+
 #ifdef __cplusplus
 }
 #endif
