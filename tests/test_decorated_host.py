@@ -146,6 +146,31 @@ def test_host_stage_matches_r_transcription(method, stratified, seed):
         assert (got["k_neg"] > 0).any() and (got["case_neg1"] + got["ctrl_neg1"] > 0).any()
 
 
+@pytest.mark.parametrize("method", [1, 2])
+def test_host_stage_at_the_cohort_limit(method):
+    """n = 65,536 (R's limit): dense rows, a gene every patient carries, 64 strata (one of a single patient, one without
+    cases) and a table smaller than the cohort (-1 cells), with and without strata."""
+    nc, nt = 60000, 5536
+    n = nc + nt
+    rng = np.random.default_rng(65536 + method)
+    data = (rng.random((8, n)) < rng.uniform(0.02, 0.7, (8, 1))).astype(np.int32)
+    data[3] = 1
+    data[6:] = rng.random((2, n)) < 0.01                        # sparse genes: splits inside the table
+    paths = [[0, 1, 2], [3, 4], [5, 3, 6], [7, 0, 1, 2, 4], [6, 7]]
+    signs = [[1, -1, 1], [-1, 1], [1, 1, -1], [1, -1, -1, 1, 1], [1, 1]]
+    strata = rng.integers(0, 62, n).astype(np.int32)
+    strata[nc + 5] = 62
+    strata[nc + 100:nc + 400] = 63
+    VT = small_table(6000, 3000, method)
+    for st_in in (None, strata):
+        got, st = api.decorated_splits(method, nc, nt, paths, data, signs, VT, st_in)
+        want = r_decorated_splits(data, paths, signs, nc, nt, method, VT, st_in)
+        assert_same(got, want, st)
+        assert max(w["k_pos"] + w["k_neg"] for w in want) >= 10000
+        assert any(w["score"] < 0 for w in want) and any(w["score"] > 0 for w in want)      # -1 cells and table cells
+    assert [w["cases1"] + w["ctrls1"] for w in want if w["path"] == 1 and w["direction"] == 0] == [n]
+
+
 def test_host_stage_column_major_table_and_na_genes():
     nc, nt, data, paths, signs, VT = random_case(77, 2)
     paths = paths[:4] + [[1, -1, 2]]

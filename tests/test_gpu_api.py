@@ -191,13 +191,14 @@ def _mix64(z):
     return z ^ (z >> 31)
 
 
-def _masks_restated(seed, K, n, n_cases, strata):
-    """CPU restatement of k_generate_masks: selection sampling per stratum on splitmix64(seed, r, patient)."""
+def _masks_restated(seed, K, n, n_cases, strata, rows=None):
+    """CPU restatement of k_generate_masks: selection sampling per stratum on splitmix64(seed, r, patient).  The masks of
+    permutations 0 .. K-1, or of the permutations listed in ``rows``."""
     M = (1 << 64) - 1
     strata = np.zeros(n, np.int64) if strata is None else np.asarray(strata)
     S = int(strata.max()) + 1
     out = []
-    for r in range(K):
+    for r in (range(K) if rows is None else rows):
         need = [int(((strata == s) & (np.arange(n) < n_cases)).sum()) for s in range(S)]
         rem = [int((strata == s).sum()) for s in range(S)]
         base = _mix64(seed ^ ((0x51ED270B7F3C9A1D * (r + 1)) & M))
