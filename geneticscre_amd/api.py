@@ -103,6 +103,18 @@ DP_SPLIT = np.dtype([("path", "<i4"), ("direction", "<i4"), ("j", "<i4"), ("vali
 DP_STRATUM = np.dtype([("pop", "<i4"), ("cases", "<i4"), ("k_pos", "<i4"), ("k_neg", "<i4")])
 
 
+class gcre_set_input(ctypes.Structure):
+    _fields_ = [("n_sets", ctypes.c_int64), ("set_off", ctypes.c_void_p), ("members", ctypes.c_void_p),
+                ("signs", ctypes.c_void_p), ("rows", ctypes.c_void_p), ("n_rows", ctypes.c_int64),
+                ("n_cols", ctypes.c_int32)]
+
+
+# gcre_set_score as a numpy record (C layout)
+SET_SCORE = np.dtype([("set", "<i8"), ("valid", "<i4"), ("cases", "<i4"), ("ctrls", "<i4"), ("cases_pos", "<i4"),
+                      ("ctrls_pos", "<i4"), ("cases_neg", "<i4"), ("ctrls_neg", "<i4"), ("score", "<f8"),
+                      ("n_ge", "<i8"), ("pvalue", "<f8")], align=True)
+
+
 # every symbol include/gcre_hip.h declares; tests check that the library exports all of them
 EXPORTS = [
     "gcre_create", "gcre_destroy", "gcre_last_error", "gcre_abi_version", "gcre_set_top_k", "gcre_width_ul",
@@ -115,7 +127,7 @@ EXPORTS = [
     "gcre_set_perm_window", "gcre_plan_perm_window", "gcre_process_paths_devices",
     "gcre_set_inspect_cache", "gcre_drop_inspections", "gcre_build_flags", "gcre_device_count",
     "gcre_rccl_selftest", "gcre_rccl_collectives", "gcre_join_ahead",
-    "gcre_decorated_splits", "gcre_decorated_pvalues",
+    "gcre_decorated_splits", "gcre_decorated_pvalues", "gcre_score_sets",
 ]
 
 
@@ -225,6 +237,25 @@ def _decorated_lib():
         lib.gcre_decorated_splits.argtypes = [ctypes.POINTER(gcre_dp_input), P, I, I, I, P, I64, ctypes.POINTER(I64)]
         lib.gcre_decorated_pvalues.argtypes = [P, ctypes.POINTER(gcre_dp_input), P, I64, ctypes.POINTER(I64), P]
     return lib
+
+
+def _sets_lib():
+    """The library with gcre_score_sets bound, on first use (as _decorated_lib)."""
+    lib = load_library()
+    if not hasattr(lib, "gcre_score_sets"):
+        raise GcreError(f"{lib._name} has no set scoring (gcre_score_sets): rebuild it")
+    if lib.gcre_score_sets.argtypes is None:
+        lib.gcre_score_sets.argtypes = [ctypes.c_void_p, ctypes.POINTER(gcre_set_input), ctypes.c_void_p, ctypes.c_int64,
+                                        ctypes.POINTER(ctypes.c_int64), ctypes.c_void_p]
+    return lib
+
+
+def pack_carriers(rows, n_cols: int) -> np.ndarray:
+    """A 0/1 carrier matrix [rows][n_cols] as gcre's packed rows: uint64 [rows][ceil(n_cols/64)], bit c = patient c."""
+    d = np.asarray(rows).reshape(-1, n_cols) != 0
+    bits = np.zeros((d.shape[0], -(-n_cols // 64) * 64), dtype=bool)
+    bits[:, :n_cols] = d
+    return np.ascontiguousarray(np.packbits(bits, axis=1, bitorder="little").view("<u8"))
 
 
 class _DpInput:
@@ -514,6 +545,41 @@ class JoinExec:
                                                _ptr(counts)))
         rec = out[:n_out.value]
         return (rec, counts[:n_out.value]) if return_counts else rec
+
+    def score_sets(self, sets, rows, signs=None, family: bool = False):
+        """Permutation tests of caller-given sets (gcre_score_sets): one SET_SCORE record per set, against this context's
+        value table and all ``iters`` permutation masks.  ``sets``: one sequence of row indices of ``rows`` per set
+        (-1 = NA gene); ``rows``: the 0/1 carrier matrix [rows][patients]; ``signs``: per set +1 / -1 per member (None =
+        all +1; read by method 2).  With ``family`` also the per-permutation maximum of the sets' null scores (float32
+        [iters]).  Errors raise GcreError with the library's message."""
+        lib = _sets_lib()
+        n = self.num_cases + self.num_ctrls
+        S = len(sets)
+        lens = [len(s) for s in sets]
+        off = np.zeros(S + 1, dtype=np.int64)
+        off[1:] = np.cumsum(lens)
+        members = np.ascontiguousarray(np.concatenate([np.asarray(s, dtype=np.int64).reshape(-1) for s in sets])
+                                       if S else np.zeros(0), dtype=np.int32)
+        sg = None
+        if signs is not None:
+            if len(signs) != S or any(len(x) != L for x, L in zip(signs, lens)):
+                raise ValueError("signs: one sign per member of every set")
+            sg = np.ascontiguousarray(np.concatenate([np.asarray(x, dtype=np.int64).reshape(-1) for x in signs])
+                                      if S else np.zeros(0), dtype=np.int32)
+        d = np.asarray(rows)
+        if d.ndim != 2:
+            d = d.reshape(-1, n)
+        packed = pack_carriers(d, d.shape[1])
+        inp = gcre_set_input(S, _ptr(off), _ptr(members), _ptr(sg), _ptr(packed), packed.shape[0], d.shape[1])
+        out = np.zeros(max(S, 1), dtype=SET_SCORE)
+        fam = np.zeros(self.iters, dtype=np.float32) if family else None
+        n_out = ctypes.c_int64(0)
+        rc = lib.gcre_score_sets(self._h, ctypes.byref(inp), _ptr(out), len(out), ctypes.byref(n_out),
+                                 _ptr(fam) if family and self.iters > 0 else None)
+        if rc != GCRE_OK:
+            raise GcreError(self._lib.gcre_last_error(self._h).decode())
+        rec = out[:n_out.value]
+        return (rec, fam) if family else rec
 
     def perm_mask(self, r: int) -> np.ndarray:
         out = np.zeros(self.width_ul, dtype=np.uint64)

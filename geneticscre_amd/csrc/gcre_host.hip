@@ -3183,6 +3183,172 @@ int gcre_decorated_pvalues(gcre_ctx* c, const gcre_dp_input* in, gcre_dp_split* 
   return GCRE_OK;
 }
 
+// The bit pattern of the smallest float x with (double)x >= score, among the non-negative floats null scores are: null
+// score r counts (R/ProcessPaths.R:316) iff its bits are >= this -- 0 when every one counts, past +inf when none does (NaN).
+static uint32_t f32_threshold(double score) {
+  if (score != score) return 0x7f800001u;
+  if (score <= 0) return 0u;
+  float f = (float)score;
+  if ((double)f < score) f = std::nextafter(f, std::numeric_limits<float>::infinity());
+  uint32_t b;
+  std::memcpy(&b, &f, 4);
+  return b;
+}
+
+int gcre_score_sets(gcre_ctx* c, const gcre_set_input* in, gcre_set_score* out, int64_t cap, int64_t* n_out,
+                    float* family_max) {
+  if (!c) return GCRE_ERR_ARG;
+  if (!in || !n_out || cap < 0 || (cap > 0 && !out)) return fail(c, GCRE_ERR_ARG, "score_sets: NULL argument");
+  *n_out = 0;
+  const Geometry& g = c->g;
+  const int K = g.K, M = g.method;
+  if (!c->have_table || !c->d_dvt) return fail(c, GCRE_ERR_ASSERT, "assertion: score_sets needs a value table");
+  if (K > 0 && !c->have_perms)
+    return fail(c, GCRE_ERR_ASSERT, "assertion: score_sets needs the permutation masks (iterations > 0, none set)");
+  if (in->n_cols != g.n)
+    return fail(c, GCRE_ERR_ARG, "score_sets: the rows have " + std::to_string(in->n_cols) +
+                                     " columns, not n_cases + n_ctrls = " + std::to_string(g.n));
+  const int64_t S = in->n_sets;
+  if (S < 0 || in->n_rows < 0 || (S > 0 && (!in->set_off || !in->members)) || (in->n_rows > 0 && !in->rows))
+    return fail(c, GCRE_ERR_ARG, "score_sets: bad input (a negative count or a NULL array)");
+  for (int64_t s = 0; s < S; s++) {
+    const int64_t b = in->set_off[s], e = in->set_off[s + 1];
+    const std::string name = "score_sets: set " + std::to_string(s);
+    if (b < 0 || e <= b) return fail(c, GCRE_ERR_ARG, name + " has no members");
+    for (int64_t i = b; i < e; i++) {
+      const int32_t row = in->members[i];
+      if (row < -1 || row >= in->n_rows)
+        return fail(c, GCRE_ERR_RANGE, name + ": member row " + std::to_string(row) + " out of range (" +
+                                           std::to_string(in->n_rows) + " rows)");
+      if (in->signs && in->signs[i] != 1 && in->signs[i] != -1)
+        return fail(c, GCRE_ERR_ARG, name + ": sign " + std::to_string(in->signs[i]) + " is neither +1 nor -1");
+    }
+  }
+  *n_out = S;
+  if (S > cap)
+    return fail(c, GCRE_ERR_RANGE, "score_sets: " + std::to_string(S) + " sets, room for " + std::to_string(cap) +
+                                       " records (out of range)");
+
+  // the host stage: per valid set the OR of its (+) members and of its (-) members (method 1: of all of them), within the
+  // n patients, and their counts; the device rows are [valid set][M][Wp] words, the dword view k_set_null reads
+  const int W = g.W, Wp = g.Wp;
+  const size_t RW = (size_t)M * Wp;
+  std::vector<uint64_t> cases((size_t)W, 0), ctrls((size_t)W, 0);
+  for (int q = 0; q < g.n; q++) (q < g.n_cases ? cases : ctrls)[(size_t)q / 64] |= uint64_t(1) << (q % 64);
+  auto count_and = [W](const uint64_t* a, const std::vector<uint64_t>& m) {
+    int n = 0;
+    for (int w = 0; w < W; w++) n += __builtin_popcountll(a[w] & m[w]);
+    return n;
+  };
+  const double nan = std::numeric_limits<double>::quiet_NaN();
+  std::vector<int64_t> vset;     // the valid sets, in input order
+  std::vector<uint64_t> urows;
+  std::vector<int32_t> cnt;      // [valid][4] cases_pos, ctrls_pos, cases_neg, ctrls_neg
+  std::vector<uint32_t> tot;     // [valid][M] carriers per half
+  for (int64_t s = 0; s < S; s++) {
+    gcre_set_score& o = out[s];
+    std::memset(&o, 0, sizeof o);
+    o.set = s;
+    o.score = nan;
+    o.pvalue = nan;
+    const int64_t b = in->set_off[s], e = in->set_off[s + 1];
+    bool valid = true;
+    for (int64_t i = b; i < e; i++) valid = valid && in->members[i] >= 0;
+    o.valid = valid ? 1 : 0;
+    if (!valid) continue;
+    const size_t v = vset.size();
+    vset.push_back(s);
+    urows.resize((v + 1) * RW, 0);
+    uint64_t* P = urows.data() + v * RW;
+    uint64_t* N = M == 2 ? P + Wp : P;
+    for (int64_t i = b; i < e; i++) {
+      const uint64_t* r = in->rows + (size_t)in->members[i] * W;
+      uint64_t* d = (M == 2 && in->signs && in->signs[i] == -1) ? N : P;
+      for (int w = 0; w < W; w++) d[w] |= r[w] & (cases[w] | ctrls[w]);
+    }
+    o.cases_pos = count_and(P, cases);
+    o.ctrls_pos = count_and(P, ctrls);
+    if (M == 2) {
+      o.cases_neg = count_and(N, ctrls);   // the (-) half counts the other way round (methods.h:183-184)
+      o.ctrls_neg = count_and(N, cases);
+    }
+    o.cases = o.cases_pos + o.cases_neg;
+    o.ctrls = o.ctrls_pos + o.ctrls_neg;
+    cnt.insert(cnt.end(), {o.cases_pos, o.ctrls_pos, o.cases_neg, o.ctrls_neg});
+    tot.push_back((uint32_t)(o.cases_pos + o.ctrls_pos));
+    if (M == 2) tot.push_back((uint32_t)(o.cases_neg + o.ctrls_neg));
+  }
+  if (family_max) std::fill(family_max, family_max + K, 0.0f);
+  const int64_t V = (int64_t)vset.size();
+  if (V == 0) return GCRE_OK;
+
+  (void)hipSetDevice(c->device);
+  uint64_t* d_rows = nullptr;
+  int32_t* d_cnt = nullptr;
+  uint32_t *d_tot = nullptr, *d_thr = nullptr, *d_fam = nullptr;
+  double* d_obs = nullptr;
+  unsigned long long* d_ge = nullptr;
+  const bool fam = family_max && K > 0;
+  std::vector<double> obs((size_t)V);
+  std::vector<unsigned long long> ge((size_t)V, 0);
+  std::vector<uint32_t> fbits(fam ? (size_t)K : 0);
+  hipError_t e = hipMalloc((void**)&d_rows, urows.size() * 8);
+  if (e == hipSuccess) e = hipMalloc((void**)&d_cnt, cnt.size() * 4);
+  if (e == hipSuccess) e = hipMalloc((void**)&d_tot, tot.size() * 4);
+  if (e == hipSuccess) e = hipMalloc((void**)&d_thr, (size_t)V * 4);
+  if (e == hipSuccess) e = hipMalloc((void**)&d_obs, (size_t)V * 8);
+  if (e == hipSuccess) e = hipMalloc((void**)&d_ge, (size_t)V * 8);
+  if (e == hipSuccess && fam) e = hipMalloc((void**)&d_fam, (size_t)g.Kpad * 4);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_rows, urows.data(), urows.size() * 8, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_cnt, cnt.data(), cnt.size() * 4, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_tot, tot.data(), tot.size() * 4, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = launch_set_observed(d_cnt, V, M, c->d_dvt, d_obs, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(obs.data(), d_obs, (size_t)V * 8, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  if (e == hipSuccess && K > 0) {
+    std::vector<uint32_t> thr((size_t)V);
+    for (int64_t v = 0; v < V; v++) thr[(size_t)v] = f32_threshold(obs[(size_t)v]);
+    SetNullArgs a{};
+    a.rows = (const uint32_t*)d_rows;
+    a.masks = c->d_masks;   // all K permutations: the window of gcre_set_perm_window is the joins' business
+    a.tot = d_tot;
+    a.thr = d_thr;
+    a.t32 = c->d_t32;
+    a.d64 = c->d_dmax;
+    a.n_ge = d_ge;
+    a.fam_bits = d_fam;
+    a.nsets = V;
+    a.W32p = 2 * Wp;
+    a.Kpad = g.Kpad;
+    a.K = K;
+    a.nkt = (K + kSetPermTile - 1) / kSetPermTile;
+    const int64_t tpb = set_null_tile_sets(M);
+    a.npt = (V + tpb - 1) / tpb;
+    // one set tile per block while that makes at least ~8 blocks per resident block slot, more per block beyond
+    const int64_t slots = (int64_t)c->cus * 4 * 8;
+    const int64_t per = std::max<int64_t>(1, (a.npt * a.nkt) / slots);
+    a.pgroups = (int)std::min<int64_t>((a.npt + per - 1) / per, 0x7fffffff / std::max(a.nkt, 1));
+    e = hipMemcpyAsync(d_thr, thr.data(), (size_t)V * 4, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(d_ge, 0, (size_t)V * 8, c->stream);
+    if (e == hipSuccess && fam) e = hipMemsetAsync(d_fam, 0, (size_t)g.Kpad * 4, c->stream);
+    if (e == hipSuccess) e = launch_set_null(a, M, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(ge.data(), d_ge, (size_t)V * 8, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess && fam) e = hipMemcpyAsync(fbits.data(), d_fam, (size_t)K * 4, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  }
+  for (void* p : {(void*)d_rows, (void*)d_cnt, (void*)d_tot, (void*)d_thr, (void*)d_obs, (void*)d_ge, (void*)d_fam})
+    if (p) (void)hipFree(p);
+  if (e != hipSuccess) return fail(c, GCRE_ERR_DEVICE, std::string("score_sets: ") + hipGetErrorString(e));
+  for (int64_t v = 0; v < V; v++) {
+    gcre_set_score& o = out[vset[(size_t)v]];
+    o.score = obs[(size_t)v];
+    o.n_ge = (int64_t)ge[(size_t)v];
+    o.pvalue = K > 0 ? (double)o.n_ge / (double)K : nan;
+  }
+  if (fam) std::memcpy(family_max, fbits.data(), (size_t)K * 4);
+  return GCRE_OK;
+}
+
 int gcre_set_perm_window(gcre_ctx* c, int k0, int k1) {
   if (!c) return GCRE_ERR_ARG;
   const int K = c->g.K;

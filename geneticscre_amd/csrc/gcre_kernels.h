@@ -348,4 +348,27 @@ hipError_t launch_decorated_observed(const DpUrns* urns, int S, int method, cons
 hipError_t launch_decorated_null(const DpUrns* urns, const DpStratum* strata, int S, int K, int method, const double* dvt,
                                  const double* obs, unsigned long long* n_ge, int32_t* perm_counts, hipStream_t stream);
 
+// ---- permutation tests of caller-given sets (gcre_sets.hip) ----
+constexpr int kSetPermTile = 512;   // permutations per block of k_set_null
+struct SetNullArgs {
+  const uint32_t* rows;         // [nsets][M][W32p] union rows of the launched sets: (+) half, then (-) half (method 2)
+  const uint32_t* masks;        // [W32p][Kpad]
+  const uint32_t* tot;          // [nsets][M] carriers per half
+  const uint32_t* thr;          // [nsets] f32 bit pattern: permutation r counts iff bits(null_r) >= thr
+  const float* t32;             // M=1: sanitised f32 null table, diagonal-major
+  const double* d64;            // M=2: f64 vtmax, diagonal-major
+  unsigned long long* n_ge;     // [nsets], zero on entry
+  uint32_t* fam_bits;           // [Kpad] maxima over the sets as u32 bit patterns (zero on entry), or nullptr
+  int64_t nsets;
+  int64_t npt;                  // set tiles (set_null_tile_sets sets each)
+  int W32p, Kpad, K;
+  int nkt;                      // permutation tiles of kSetPermTile
+  int pgroups;                  // blocks per permutation tile
+};
+int set_null_tile_sets(int method);
+// obs[s] = the observed score of set s from d_dvt; cnt[s] = cases_pos, ctrls_pos, cases_neg, ctrls_neg
+hipError_t launch_set_observed(const int32_t* cnt, int64_t S, int method, const double* dvt, double* obs,
+                               hipStream_t stream);
+hipError_t launch_set_null(const SetNullArgs& a, int method, hipStream_t stream);
+
 }  // namespace gcre

@@ -6,6 +6,8 @@
   * ``preprocess_table`` / ``prepare_inputs``  the dataset and network filtering         (R/Utils.R:162-199, ProcessPaths.R:131-176)
   * ``decorated_table``  getDecoratedPvalues: the split-path table, permutations on the device  (R/DecoratedPvalue.R)
   * ``gwaspa``           the whole call, with the table / level tables / permutations built natively
+  * ``score_paths``      permutation tests of paths and gene sets the caller names (k_set_null; beyond the reference)
+  * ``check_best_paths`` checkBestPaths: rescore a GWASPA.Results table from the raw data   (R/CheckResults.R:2-89)
 
 Host-side post-processing of <= top_k x 5 rows: string work, nothing here touches the scored path.
 """
@@ -220,6 +222,125 @@ def decorated_table(results_df, genes: Sequence[str], data: np.ndarray, n_cases:
         cols["Direction"].append(direction)
         cols["DecoratedPvalues"].append(float(s["pvalue"]))
     return pd.DataFrame(cols, columns=DECORATED_COLUMNS)
+
+
+SCORE_PATHS_COLUMNS = ["SignedPaths", "Paths", "Lengths", "Scores", "Cases", "Controls", "NominalPvalues",
+                       "FamilyPvalues", "Pvalues"]
+
+
+def parse_sets(paths, genes: Sequence[str]) -> Tuple[List[List[str]], List[List[int]], List[List[int]]]:
+    """(symbols, rows, signs) of every entry of ``paths``: a SignedPaths string "A (+) -> B (-)" (a hop whose tag is not
+    "(+)" is (-), CheckResults.R:33-34), a Paths string "A -> B" (every gene (+)), or a sequence of symbols (a gene set,
+    every gene (+)).  rows = the first row of ``genes`` holding the symbol, -1 for "NA" or a symbol not there."""
+    row_of: Dict[str, int] = {}
+    for i, g in enumerate(genes):
+        row_of.setdefault(g, i)
+    names, rows, signs = [], [], []
+    for p in paths:
+        if isinstance(p, str):
+            hops = [h.split() for h in p.split(" -> ")]
+            nm = [h[0] if h else "NA" for h in hops]
+            sg = [1 if len(h) < 2 or h[1] == POS else -1 for h in hops]
+        else:
+            nm = [str(g) for g in p]
+            sg = [1] * len(nm)
+        names.append(nm)
+        rows.append([row_of.get(g, -1) if g != "NA" else -1 for g in nm])
+        signs.append(sg)
+    return names, rows, signs
+
+
+def _score_sets(rows, signs, data, n_cases, n_ctrls, method, n_permutations, strata, seed, device):
+    """score_sets on the rows the sets use, on a context of its own: (records, family maxima)."""
+    from . import api
+    used: Dict[int, int] = {}
+    sets = [[-1 if r < 0 else used.setdefault(r, len(used)) for r in rs] for rs in rows]
+    data = np.asarray(data)
+    sub = data[list(used.keys())] if used else np.zeros((0, n_cases + n_ctrls), np.int32)
+    ex = api.JoinExec(method, n_cases, n_ctrls, n_permutations, device=device)
+    try:
+        ex.set_value_table(api.values_table(n_cases, n_ctrls))
+        if n_permutations > 0:
+            ex.generate_permutations(seed, strata)
+        return ex.score_sets(sets, sub, signs, family=True)
+    finally:
+        ex.close()
+
+
+def _tail_pvalues(null: np.ndarray, scores: np.ndarray) -> np.ndarray:
+    """#(null >= score) / len(null) for every score (R/ProcessPaths.R:316, f64 score against f32 maxima) by a sort and a
+    binary search: the same numbers as JoinResult.pvalues."""
+    t = np.sort(np.asarray(null, dtype=np.float32).astype(np.float64))
+    if len(t) == 0:
+        return np.full(len(scores), np.nan)
+    return (len(t) - np.searchsorted(t, scores, side="left")) / len(t)
+
+
+def score_paths(paths, genes: Sequence[str], data: np.ndarray, n_cases: int, n_ctrls: int, signed: bool = False,
+                threshold: float = 0.05, n_permutations: int = 100, strata: Optional[Sequence[int]] = None, seed: int = 0,
+                device: int = 0, gwaspa_out: Optional[Dict[str, object]] = None):
+    """Permutation tests of paths and gene sets the caller names (gcre_score_sets on the device): what GWASPA cannot
+    answer for a cascade outside its top K, or for a KEGG / Reactome list.  ``paths`` as ``parse_sets`` reads them;
+    genes are looked up after ``preprocess_table(threshold)``, as GWASPA and ``decorated_table`` do (a symbol not found is
+    NA: the row gets NaN).  The masks are ``generate_permutations(seed, strata)``'s, the ones ``gwaspa`` draws from the
+    same seed.
+
+    Columns: ``Scores`` / ``Cases`` / ``Controls`` as GWASPA.Results counts them; ``NominalPvalues`` the set's own
+    permutation p-value; ``FamilyPvalues`` max-T over the given paths (each score against the per-permutation maximum
+    over all of them); ``Pvalues`` against the TestScores of ``gwaspa_out``'s level of the same length -- for a network
+    path the number GWASPA would print, if the run had the same seed, strata and permutation count (NaN without
+    ``gwaspa_out`` or outside its 1..pathLength)."""
+    import pandas as pd
+    method = 2 if signed else 1
+    genes, data = preprocess_table(genes, data, threshold, n_cases, n_ctrls)
+    names, rows, signs = parse_sets(paths, genes)
+    K = int(n_permutations)
+    rec, fam = _score_sets(rows, signs, data, n_cases, n_ctrls, method, K, strata, seed, device)
+    valid = rec["valid"] != 0
+    score = rec["score"]
+    lengths = np.array([len(n) for n in names], dtype=np.int64)
+    nan = np.full(len(rec), np.nan)
+    family = np.where(valid, _tail_pvalues(fam, score), np.nan) if K > 0 else nan.copy()
+    pv = nan.copy()
+    if gwaspa_out is not None:
+        levels = gwaspa_out["levels"]
+        for L in np.unique(lengths).tolist():
+            lst = levels.get(f"lst{L}") if 1 <= L <= 5 else None
+            sel = (lengths == L) & valid
+            if lst is not None and sel.any():
+                pv[sel] = _tail_pvalues(lst.null, score[sel])
+    cols = {
+        "SignedPaths": [" -> ".join(f"{g} {POS if s == 1 else NEG}" for g, s in zip(nm, sg)) for nm, sg in zip(names, signs)],
+        "Paths": [" -> ".join(nm) for nm in names],
+        "Lengths": lengths,
+        "Scores": score,
+        "Cases": np.where(valid, rec["cases"], np.nan),
+        "Controls": np.where(valid, rec["ctrls"], np.nan),
+        "NominalPvalues": rec["pvalue"],
+        "FamilyPvalues": family,
+        "Pvalues": pv,
+    }
+    return pd.DataFrame(cols, columns=SCORE_PATHS_COLUMNS)
+
+
+def check_best_paths(results_df, genes: Sequence[str], data: np.ndarray, n_cases: int, n_ctrls: int, signed: bool,
+                     device: int = 0):
+    """checkBestPaths (R/CheckResults.R:2-89) on the device scorer without permutations: the dataset preprocessed with
+    threshold 1 (:12-13), every row's SignedPaths rescored from the raw data, compared with ``Scores`` by ``!=`` (:76).
+    Returns (passed, the rows that fail with the recomputed score, counts and checkBestPaths' half counts).  A row with an
+    NA gene fails."""
+    genes, data = preprocess_table(genes, data, 1, n_cases, n_ctrls)
+    _, rows, signs = parse_sets(list(results_df["SignedPaths"]), genes)
+    rec, _ = _score_sets(rows, signs, data, n_cases, n_ctrls, 2 if signed else 1, 0, None, 0, device)
+    bad = ~(rec["score"] == results_df["Scores"].to_numpy(dtype=np.float64))
+    out = results_df[bad].copy()
+    out["CheckScores"] = rec["score"][bad]
+    out["CheckCases"] = rec["cases"][bad]
+    out["CheckControls"] = rec["ctrls"][bad]
+    for f, c in (("cases_pos", "cases_pos"), ("ctrls_pos", "controls_pos"), ("cases_neg", "cases_neg"),
+                 ("ctrls_neg", "controls_neg")):
+        out[c] = rec[f][bad]
+    return not bool(bad.any()), out
 
 
 # ---------------------------------------------------------------------------------------------------------------

@@ -390,6 +390,49 @@ int gcre_decorated_splits(const gcre_dp_input* in, const double* table, int nrow
 int gcre_decorated_pvalues(gcre_ctx* ctx, const gcre_dp_input* in, gcre_dp_split* out, int64_t cap, int64_t* n_out,
                            int32_t* perm_counts);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Permutation tests of caller-given sets: a named path, a gene set, any list of carrier rows.  No reference counterpart
+ * (its checkBestPaths, R/CheckResults.R:2-89, rescores named paths without permutations).  A set's members are rows of a
+ * 0/1 carrier matrix; each member has a sign, read by method 2 only.
+ *   method 1: U = OR of the members; score = VT[|U & cases|][|U & ctrls|] (methods.h:90)
+ *   method 2: P = OR of the (+) members, N = OR of the (-) members (a row listed under both signs lands in both, no
+ *             conflict removal: CheckResults.R:40-44); score = VT[|P & cases|][|P & ctrls|] + VT[|N & ctrls|][|N & cases|]
+ *             (methods.h:255, CheckResults.R:69-73)
+ * Null score of permutation r (mask_r = its cases): the f32 value the join's null kernels fold into their maxima --
+ * method 1 t32[p][|U| - p], p = |U & mask_r|; method 2 (float)(vtmax[pp][|P| - pp] + vtmax[|N| - pn][pn]),
+ * pp = |P & mask_r|, pn = |N & mask_r|; NaN and negatives fold as 0 (methods.h:96-103, :220-230).  So the maximum over
+ * every joined path of a level, passed as sets, is that level's null_max bit for bit. */
+typedef struct {
+  int64_t n_sets;
+  const int64_t* set_off;   /* [n_sets + 1]: set s = members[set_off[s] .. set_off[s+1]), at least one */
+  const int32_t* members;   /* rows of `rows`; -1 = an NA gene (the set gets valid = 0) */
+  const int32_t* signs;     /* per member, parallel to `members`: +1 / -1; NULL = all +1 */
+  const uint64_t* rows;     /* [n_rows][ceil(n_cols/64)] carriers, bit c of word c/64 = patient c (bits >= n_cols ignored) */
+  int64_t n_rows;
+  int32_t n_cols;           /* patients: must be the context's n_cases + n_ctrls (columns < n_cases are the cases) */
+} gcre_set_input;
+
+/* One set's record. */
+typedef struct {
+  int64_t set;         /* index into the input */
+  int32_t valid;       /* 0: an NA member -- counts 0, score and p-value NaN, not in family_max */
+  int32_t cases, ctrls;   /* keep_score's Cases / Controls (methods.h:256-257): cases_pos + cases_neg, ctrls_pos + ctrls_neg */
+  /* checkBestPaths' names (CheckResults.R:62-65): |P & cases|, |P & ctrls|, |N & ctrls|, |N & cases| (method 1: P = U, N empty) */
+  int32_t cases_pos, ctrls_pos, cases_neg, ctrls_neg;
+  double score;        /* observed score from the context's value table */
+  int64_t n_ge;        /* permutations r < iterations with (double)null_r >= score (R/ProcessPaths.R:316) */
+  double pvalue;       /* n_ge / iterations; NaN for an invalid set or 0 iterations */
+} gcre_set_score;
+
+/* Every set of `in` against the context's value table and all `iterations` permutation masks (whatever
+ * gcre_set_perm_window says; strata come in through the masks).  *n_out = n_sets.  family_max, optional [iterations]:
+ * per permutation the maximum of null_r over the valid sets (all zeros without one): max-T over a family the caller
+ * chooses.  Errors, nothing launched: GCRE_ERR_ARG -- a set without members, a sign other than +1 / -1, n_cols not
+ * n_cases + n_ctrls; GCRE_ERR_RANGE -- a member row out of range, n_sets > cap; GCRE_ERR_ASSERT -- no value table, or
+ * iterations > 0 and no masks set.  DESIGN.md §3.6. */
+int gcre_score_sets(gcre_ctx* ctx, const gcre_set_input* in, gcre_set_score* out, int64_t cap, int64_t* n_out,
+                    float* family_max);
+
 #ifdef __cplusplus
 }
 #endif
