@@ -128,6 +128,8 @@ EXPORTS = [
     "gcre_set_inspect_cache", "gcre_drop_inspections", "gcre_build_flags", "gcre_device_count",
     "gcre_rccl_selftest", "gcre_rccl_collectives", "gcre_join_ahead",
     "gcre_decorated_splits", "gcre_decorated_pvalues", "gcre_score_sets",
+    "gcre_gene_tally_create", "gcre_join_set_tally", "gcre_process_paths_set_tally", "gcre_gene_tally_read",
+    "gcre_gene_tally_free",
 ]
 
 
@@ -248,6 +250,103 @@ def _sets_lib():
         lib.gcre_score_sets.argtypes = [ctypes.c_void_p, ctypes.POINTER(gcre_set_input), ctypes.c_void_p, ctypes.c_int64,
                                         ctypes.POINTER(ctypes.c_int64), ctypes.c_void_p]
     return lib
+
+
+def _genes_lib():
+    """The library with the per-gene tally entries bound, on first use (as _decorated_lib)."""
+    lib = load_library()
+    if not hasattr(lib, "gcre_gene_tally_create"):
+        raise GcreError(f"{lib._name} has no per-gene best-path tally (gcre_gene_tally_create): rebuild it")
+    if lib.gcre_gene_tally_create.argtypes is None:
+        V, P, I, I64 = ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64
+        lib.gcre_gene_tally_create.restype = V
+        lib.gcre_gene_tally_create.argtypes = [V, I, P, I64, I, P, I64, I]
+        lib.gcre_join_set_tally.argtypes = [V, V]
+        lib.gcre_process_paths_set_tally.argtypes = [V, ctypes.c_int, V]
+        lib.gcre_gene_tally_read.argtypes = [V, P, P, P, P, P, P]
+        lib.gcre_gene_tally_free.argtypes = [V]
+        lib.gcre_gene_tally_free.restype = None
+    return lib
+
+
+GENE_WIDTH_MAX = 3   # kGeneWidthMax: gene slots a joined path inherits from one operand row, at most
+LEVEL_INDEX = {"1a": 0, "1b": 1, "2": 2, "3": 3, "4": 4, "5": 5}   # gcre_pp_input.level
+
+
+def check_gene_tables(n_slots: int, genes0, genes1, n_uids: Optional[int] = None, max_loc: Optional[int] = None):
+    """The checks gcre_gene_tally_create and the armed join make, on the host, before the library is called: each table
+    None (that operand contributes no gene) or int32 [rows][1..3] with values -1..n_slots-1; with ``n_uids`` / ``max_loc``
+    (the join's uid rows and the largest paths1 row it reads) also the row counts.  Returns the two tables as contiguous
+    int32 arrays (or None); raises GcreError."""
+    if int(n_slots) < 1:
+        raise GcreError("gene tally: n_slots must be >= 1")
+    out = []
+    for name, g in (("genes0", genes0), ("genes1", genes1)):
+        if g is None:
+            out.append(None)
+            continue
+        a = np.asarray(g)
+        if a.ndim != 2 or not 1 <= a.shape[1] <= GENE_WIDTH_MAX:
+            raise GcreError(f"gene tally: {name} must be [rows][1..{GENE_WIDTH_MAX}], got shape {a.shape}")
+        if not np.issubdtype(a.dtype, np.integer):
+            raise GcreError(f"gene tally: {name} must hold integer slots")
+        if a.size and (a.min() < -1 or a.max() >= int(n_slots)):
+            bad = a[(a < -1) | (a >= int(n_slots))].ravel()[0]
+            raise GcreError(f"gene tally: {name} holds slot {int(bad)} outside -1..{int(n_slots) - 1}")
+        out.append(np.ascontiguousarray(a, dtype=np.int32))
+    if n_uids is not None and out[0] is not None and out[0].shape[0] != int(n_uids):
+        raise GcreError(f"gene tally: genes0 has {out[0].shape[0]} rows, the join index has {int(n_uids)} uid rows")
+    if max_loc is not None and out[1] is not None and out[1].shape[0] <= int(max_loc):
+        raise GcreError(f"gene tally: genes1 has {out[1].shape[0]} rows, the join reads paths1 row {int(max_loc)}")
+    return out[0], out[1]
+
+
+@dataclass
+class GeneBest:
+    """One entry per gene slot (gcre_gene_tally_read): -inf / -1 / 0 where no scored path touches the slot."""
+
+    score: np.ndarray      # float64
+    ordinal: np.ndarray    # int64 joined-path ordinal
+    src: np.ndarray        # int32 row of paths0 (Score.src)
+    trg: np.ndarray        # int32 row of paths1 (Score.trg)
+    cases: np.ndarray
+    ctrls: np.ndarray
+
+
+class GeneTally:
+    """gcre_gene_tally: the per-gene best-path table of a join.  ``genes0`` / ``genes1``: the slots a
+    joined path inherits from its paths0 row / its paths1 row (``report.gene_tables`` builds them per level).  Pass it as
+    ``JoinExec.join(..., tally=t)`` or ``process_paths(..., tallies={"4": t})``, then ``read()``."""
+
+    def __init__(self, owner: "JoinExec", n_slots: int, genes0, genes1):
+        self.genes0, self.genes1 = check_gene_tables(n_slots, genes0, genes1)
+        self.n_slots = int(n_slots)
+        self._owner, self._lib, self._h = owner, _genes_lib(), None
+        g0, g1 = self.genes0, self.genes1
+        self._h = self._lib.gcre_gene_tally_create(owner._h, self.n_slots,
+                                                   _ptr(g0), 0 if g0 is None else g0.shape[0], 0 if g0 is None else g0.shape[1],
+                                                   _ptr(g1), 0 if g1 is None else g1.shape[0], 0 if g1 is None else g1.shape[1])
+        if not self._h:
+            owner._raise(GCRE_ERR_ARG)
+
+    def read(self) -> GeneBest:
+        n = self.n_slots
+        score, ordinal = np.zeros(n, np.float64), np.zeros(n, np.int64)
+        src, trg, cases, ctrls = (np.zeros(n, np.int32) for _ in range(4))
+        self._owner._check(self._lib.gcre_gene_tally_read(self._h, _ptr(score), _ptr(ordinal), _ptr(src), _ptr(trg),
+                                                          _ptr(cases), _ptr(ctrls)))
+        return GeneBest(score, ordinal, src, trg, cases, ctrls)
+
+    def free(self) -> None:
+        h, self._h = self._h, None
+        if h and self._owner._h:       # (a closed context has freed it already)
+            self._lib.gcre_gene_tally_free(h)
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
 
 
 def pack_carriers(rows, n_cols: int) -> np.ndarray:
@@ -600,13 +699,15 @@ class JoinExec:
 
     def join(self, uids, paths0: PathSet, paths1: PathSet, paths_res: Optional[PathSet] = None,
              shard: Optional[Tuple[int, int]] = None, d_null_out: int = 0,
-             keep: Optional[Tuple[int, int]] = None, keep_mode: int = 1, exchange=None, exchanges: int = 0) -> JoinResult:
+             keep: Optional[Tuple[int, int]] = None, keep_mode: int = 1, exchange=None, exchanges: int = 0,
+             tally: Optional["GeneTally"] = None) -> JoinResult:
         """JoinExec::join (src/join_base.cpp:189-264).  ``paths_res`` receives the joined rows when given.
         ``uids`` is a UidRelSet (uploaded for this call) or a DeviceUids (already resident).  ``shard`` restricts
         scoring to a range of joined paths; ``keep`` restricts the rows written to ``paths_res`` to a range (plus
         the scored shard) -- the rows this device's shards of the later joins will read -- or, with ``keep_mode`` 2,
         only the rows that get count planes (all rows are still written).  ``exchange(k0, k1)`` is called ``exchanges``
-        times during the join (gcre_join_opts.exchange): it MAX-all-reduces d_null_out[k0:k1] across the ranks in place."""
+        times during the join (gcre_join_opts.exchange): it MAX-all-reduces d_null_out[k0:k1] across the ranks in place.
+        ``tally``: a GeneTally this join's scored paths are folded into (gcre_join_set_tally)."""
         opts = gcre_join_opts(0, 0, 0, 0, None, 0, 0, 0, None, None)
         cb = None
         if exchange is not None and exchanges > 0:
@@ -632,6 +733,14 @@ class JoinExec:
             opts.d_null_out = ctypes.c_void_p(int(d_null_out))
         res = gcre_result()
         res_h = paths_res._h if paths_res is not None else None
+        if tally is not None:
+            if tally._owner is not self or not tally._h:
+                raise GcreError("gene tally does not belong to this context")
+            if not isinstance(uids, DeviceUids):   # (a resident index is checked by the library, before any launch)
+                cnt = np.asarray(uids.count)
+                ends = (np.asarray(uids.location, dtype=np.int64) + cnt)[cnt > 0]
+                check_gene_tables(tally.n_slots, tally.genes0, tally.genes1, len(cnt), int(ends.max()) - 1 if len(ends) else -1)
+            self._check(_genes_lib().gcre_join_set_tally(self._h, tally._h))
         if isinstance(uids, DeviceUids):
             rc = self._lib.gcre_join_uids(self._h, uids._h, paths0._h, paths1._h, res_h, ctypes.byref(opts),
                                           ctypes.byref(res))
@@ -772,10 +881,13 @@ def _pp_input(problem, keep):
     return inp
 
 
-def process_paths_devices(problem, devices=None) -> Dict[str, object]:
+def process_paths_devices(problem, devices=None, tallies=None) -> Dict[str, object]:
     """ProcessPaths on several GPUs of the node from this one process (gcre_process_paths_devices): one context and host
     thread per entry of ``devices`` (None: every visible device; an id may repeat), joined paths sharded, maxima and top-k
-    tables merged.  Bit-identical to ``process_paths`` for any device list."""
+    tables merged.  Bit-identical to ``process_paths`` for any device list.  It takes no gene tallies (merging them across
+    devices is out of scope: shard the joins yourself, ``JoinExec.join(shard=, tally=)``): ``tallies`` raises GcreError."""
+    if tallies:
+        raise GcreError("process_paths_devices takes no gene tallies: merging tallies across devices is not supported")
     lib = load_library()
     lib.gcre_process_paths_devices.restype = ctypes.c_int
     lib.gcre_process_paths_devices.argtypes = [ctypes.c_int] * 5 + [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
@@ -798,11 +910,14 @@ def process_paths_devices(problem, devices=None) -> Dict[str, object]:
     return {f"lst{i + 1}": (None if outs[i].n < 0 else _take_result(lib, outs[i])) for i in range(5)}
 
 
-def process_paths(problem, device: int = 0, exec_: Optional[JoinExec] = None) -> Dict[str, object]:
+def process_paths(problem, device: int = 0, exec_: Optional[JoinExec] = None, tallies=None) -> Dict[str, object]:
     """ProcessPaths (src/wrapper.cpp:177-281) in one native call.  Returns {"lst1": JoinResult | None, ...}.
 
-    ``problem`` carries the 39 arguments as arrays (geneticscre_amd.synth.Problem).
+    ``problem`` carries the 39 arguments as arrays (geneticscre_amd.synth.Problem).  ``tallies``: level name ("1b", "2",
+    .., "5"; "1a" too) -> GeneTally of ``exec_``: that level's join folds its scored paths into it.
     """
+    if tallies and exec_ is None:
+        raise GcreError("process_paths: gene tallies live on a context; pass the JoinExec they were made on as exec_")
     ex = exec_ or JoinExec(problem.method, problem.n_cases, problem.n_ctrls, problem.iterations, device)
     ex.top_k = problem.top_k
     lib = ex._lib
@@ -830,6 +945,17 @@ def process_paths(problem, device: int = 0, exec_: Optional[JoinExec] = None) ->
     inp.perm_rows, inp.perm_col_major = (pc.shape[0] if pc.ndim == 2 else 0), 0
     inp.path_length = int(problem.path_length)
     outs = (gcre_result * 5)()
+    for name, t in (tallies or {}).items():
+        if name not in LEVEL_INDEX:
+            raise GcreError(f"process_paths: no level {name!r} (levels are {', '.join(LEVEL_INDEX)})")
+        if t._owner is not ex or not t._h:
+            raise GcreError("gene tally does not belong to this context")
+        u = problem.levels.uids[name]
+        cnt = np.asarray(u.count)
+        ends = (np.asarray(u.location, dtype=np.int64) + cnt)[cnt > 0]
+        check_gene_tables(t.n_slots, t.genes0, t.genes1, len(cnt), int(ends.max()) - 1 if len(ends) else -1)
+    for name, t in (tallies or {}).items():
+        ex._check(_genes_lib().gcre_process_paths_set_tally(ex._h, LEVEL_INDEX[name], t._h))
     rc = lib.gcre_process_paths(ex._h, ctypes.byref(inp), outs)
     ex._check(rc)
     result: Dict[str, object] = {}
@@ -1024,7 +1150,7 @@ class ResidentPlan:
         return int(min(most, np.floor(np.log2(work / unit))))
 
     def run(self, rank: int = 0, world: int = 1, d_null_out: int = 0, on_level=None,
-            keep_inspections: bool = False, exchange=None) -> Dict[str, JoinResult]:
+            keep_inspections: bool = False, exchange=None, tallies=None) -> Dict[str, JoinResult]:
         """One pass over all levels.  Large permutation counts run in windows of whole 2048-permutation tiles (the count
         planes of the kept sets are per tile and have to fit in device memory): all levels for window 0, then all levels
         for window 1, ...  ``on_level(name, result, shard, window)`` sees every (level, window) result -- its null
@@ -1040,7 +1166,12 @@ class ResidentPlan:
         ``exchange(name, k0, k1)`` (multi-GPU): MAX-all-reduce ``d_null_out[k0:k1]`` across the ranks in place; called
         ``exchange_count(name, world)`` times during a level's join so that every rank prunes against the whole level's
         running maxima, not only its shard's (gcre_join_opts.exchange).  The null maxima a rank then returns include what
-        it learned from the others; their MAX over the ranks is unchanged."""
+        it learned from the others; their MAX over the ranks is unchanged.
+
+        ``tallies``: level name -> GeneTally of ``self.ex``; that level's join folds its scored paths into it (every window
+        folds the same observed scores again, which changes nothing).  One rank only."""
+        if tallies and world > 1:
+            raise GcreError("ResidentPlan.run: gene tallies need world == 1 (merging tallies across ranks is not supported)")
         K = self.problem.iterations
         if self._window is None:
             self._window = self.planned_window()
@@ -1088,7 +1219,8 @@ class ResidentPlan:
                                  shard=(b, e) if (world > 1 and not by_pivot) else None,
                                  d_null_out=(d_null_out + 4 * k0) if d_null_out else 0,
                                  keep=self.needed_rows(name, rank, world), keep_mode=self.keep_mode(name),
-                                 exchange=(lambda a, b_, name=name: exchange(name, a, b_)) if n_ex else None, exchanges=n_ex)
+                                 exchange=(lambda a, b_, name=name: exchange(name, a, b_)) if n_ex else None, exchanges=n_ex,
+                                 tally=(tallies or {}).get(name))
                 for k, v in self.ex.profile().items():
                     prof[k] = prof.get(k, 0) + v
                 if on_level is not None:

@@ -388,6 +388,11 @@ struct gcre_ctx {
   // live path sets by id: a recipe names its operands by id + version, never by pointer alone
   std::unordered_map<uint64_t, const gcre_pathset*> live_sets;
   std::vector<gcre_uids*> live_uids;   // join indices created on this context (gcre_destroy releases what is still alive)
+  // per-gene best-path tallies (gcre_gene_tally): the ones alive on this context, the one the next join
+  // folds into (gcre_join_set_tally), and the ones the next gcre_process_paths hands to its levels
+  std::vector<gcre_gene_tally*> live_tallies;
+  gcre_gene_tally* armed_tally = nullptr;
+  gcre_gene_tally* pp_tally[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   uint64_t next_set_id = 0;
   size_t planes_out_max = (size_t)8 << 30;   // kept sets (method 1) whose planes are larger keep a recipe only
 
@@ -508,6 +513,24 @@ struct gcre_uids {
   mutable int64_t n_pairs = 0;              // (range, paths1 row) pairs = sum of the range lengths
   mutable int32_t* d_pair_range = nullptr;
   mutable int64_t* d_pair_loc = nullptr;
+};
+
+// The per-gene best-path table of one join: which slots a joined path touches -- through its paths0 row
+// and through its paths1 row -- and, per slot, the best joined path seen so far under (key, then smaller ordinal).
+struct gcre_gene_tally {
+  gcre_ctx* ctx = nullptr;
+  int n_slots = 0;
+  int64_t n_rows0 = 0, n_rows1 = 0;
+  int w0 = 0, w1 = 0;                 // 0: the operand contributes no gene
+  int32_t *d_genes0 = nullptr, *d_genes1 = nullptr;
+  uint64_t* d_ck = nullptr;           // chunk-local tables: empty between folds (k_gene_merge leaves them so)
+  uint32_t* d_cidx = nullptr;
+  uint64_t* d_bkey = nullptr;         // the table
+  int64_t* d_bord = nullptr;
+  int32_t *d_bsrc = nullptr, *d_btrg = nullptr, *d_bcases = nullptr, *d_bctrls = nullptr;
+  hipStream_t last = nullptr;         // the stream of the last fold: a read waits for it
+  bool folded = false;                // the table holds something (k_gene_fold then also tests against it)
+  bool folding = false;               // a fold did not get all its launches queued: the chunk-local tables are cleared first
 };
 
 namespace {
@@ -1123,6 +1146,7 @@ struct JoinPlan {
   int exchanges = 0;
   int (*exchange)(void*, void*, int32_t, int32_t) = nullptr;
   void* exchange_user = nullptr;
+  gcre_gene_tally* tally = nullptr;   // the join's scored paths are folded into it (never set on a registered later join)
   void take(const gcre_join_opts* o) {
     if (!o) return;
     if (o->keep_ranged) {
@@ -1379,6 +1403,63 @@ int deliver_join(gcre_ctx* c, const JoinPlan& jp, gcre_result* out, int K, const
   return GCRE_OK;
 }
 
+// ---- per-gene best-path tally (gcre_genes.hip): scored paths [s0, s1) of a chunk whose inspector output is in `b` ----
+// Queued on `st` behind the inspector that wrote the keys; whatever rewrites `b` next is queued behind it in turn (the next
+// chunk's inspector runs on the same stream; cached buffers are not rewritten during the pass).  Folding a chunk twice
+// changes nothing: the table only moves under (key greater) or (key equal and ordinal smaller).
+int check_tally(gcre_ctx* c, const gcre_gene_tally* t, const gcre_uids& u) {
+  if (t->ctx != c) return fail(c, GCRE_ERR_ARG, "gene tally does not belong to this context");
+  if (t->w0 > 0 && t->n_rows0 != u.n_uids)
+    return fail(c, GCRE_ERR_ARG, "gene tally: genes0 has " + std::to_string(t->n_rows0) + " rows, the join index has " +
+                                     std::to_string(u.n_uids) + " uid rows");
+  if (t->w1 > 0 && t->n_rows1 <= u.max_loc)
+    return fail(c, GCRE_ERR_ARG, "gene tally: genes1 has " + std::to_string(t->n_rows1) + " rows, the join reads paths1 row " +
+                                     std::to_string(u.max_loc));
+  return GCRE_OK;
+}
+
+int fold_genes(gcre_ctx* c, gcre_gene_tally* t, const ChunkBufs& b, int64_t cb, int64_t s0, int64_t s1, hipStream_t st) {
+  if (s1 <= s0) return GCRE_OK;
+  if (t->last && t->last != st) {   // (a join folds on one stream; the next join may use another)
+    hipEvent_t e = get_event(c);
+    HIP_TRY(c, hipEventRecord(e, t->last));
+    HIP_TRY(c, hipStreamWaitEvent(st, e, 0));
+    c->ev_pool.push_back(e);
+  }
+  if (t->folding) {
+    HIP_TRY(c, hipMemsetAsync(t->d_ck, 0, (size_t)t->n_slots * 8, st));
+    HIP_TRY(c, hipMemsetAsync(t->d_cidx, 0xff, (size_t)t->n_slots * 4, st));
+  }
+  t->folding = true;
+  t->last = st;
+  GeneFoldArgs a{};
+  a.key = b.key.p + s0;
+  a.row0 = b.row0.p + s0;
+  a.row1 = b.row1.p + s0;
+  a.cases = b.cases.p + s0;
+  a.ctrls = b.ctrls.p + s0;
+  a.count = s1 - s0;
+  a.first = cb + s0;
+  a.genes0 = t->d_genes0;
+  a.genes1 = t->d_genes1;
+  a.w0 = t->w0;
+  a.w1 = t->w1;
+  a.n_slots = t->n_slots;
+  a.prior = t->folded ? 1 : 0;
+  a.ck = t->d_ck;
+  a.cidx = t->d_cidx;
+  a.bkey = t->d_bkey;
+  a.bord = t->d_bord;
+  a.bsrc = t->d_bsrc;
+  a.btrg = t->d_btrg;
+  a.bcases = t->d_bcases;
+  a.bctrls = t->d_bctrls;
+  HIP_TRY(c, launch_gene_fold(a, c->cus, st));
+  t->folding = false;
+  t->folded = true;
+  return GCRE_OK;
+}
+
 // The tail of a join whose kernels were launched ahead (run_join, kLaunch): wait for them, copy the maxima out of the join
 // index's own array, merge the winners its inspection cached.
 int finish_launched(gcre_ctx* c, const JoinPlan& jp, gcre_result* out) {
@@ -1396,6 +1477,13 @@ int finish_launched(gcre_ctx* c, const JoinPlan& jp, gcre_result* out) {
   L.cands.clear();
   c->prof = L.prof;
   L.prof = gcre_profile{};
+  if (jp.tally) {
+    // every chunk of the join is in its inspection cache (the launch replayed it from there, or inspected it into it); an
+    // entry an abandoned attempt left behind describes the same paths and folds harmlessly
+    for (const ChunkInsp& ci : jp.u->insp)
+      if (ci.cb >= 0 && ci.inspected)
+        if (int rc = fold_genes(c, jp.tally, ci.bufs, ci.cb, ci.s0, ci.s1, c->insp_stream)) return rc;
+  }
   if (int rc = deliver_join(c, jp, out, K, L.d_null.p, c->insp_stream, cands, L.ev_null, L.ev_stats, t_begin, nullptr))
     return rc;
   c->prof.ie_lookup_tiles += lookups;
@@ -1680,6 +1768,8 @@ int begin_join(JoinRun& R, Begin* next) {
   const bool keep = R.keep = jp.res != nullptr && jp.res->nrows != 0;
   if (jp.res && jp.res->nrows != 0 && jp.res->nrows != P)
     return fail(c, GCRE_ERR_ASSERT, "assertion: paths_res.size != total paths");
+  if (jp.tally && mode == kFull)
+    if (int rc = check_tally(c, jp.tally, u)) return rc;
   // ---- inspection cache: has this very join (same operand rows, kept set, shard, table) run on this index before? ----
   InspKey& ikey = R.ikey;
   if (c->insp_cache) {
@@ -2640,6 +2730,10 @@ int run_chunk(JoinRun& R, const Seg& sg, int64_t cb, int64_t ce, ChunkEnd* end) 
         if (int rc = score_chunk_dense(R, C)) return rc;
     }
   }
+  // the chunk's keys are final (no stage sends it round again) and still in place: the tally reads them behind the chunk's
+  // own kernels, before the next chunk's inspector -- on this stream too -- may rewrite them
+  if (R.jp.tally && R.mode == kFull)
+    if (int rc = fold_genes(R.c, R.jp.tally, *C.b, C.cb, C.s0, C.s1, R.st)) return rc;
   if (int rc = collect_winners(R, C)) return rc;
   if (R.mode != kInspect) R.prof->paths += C.s1 - C.s0;   // (a launch books them on the profile of the join it is for)
   return GCRE_OK;
@@ -2854,6 +2948,7 @@ void gcre_destroy(gcre_ctx* c) {
   // path sets and join indices the caller did not free: their rows, lists, count planes, recipes and segment tables go
   // with the context (their handles are invalid from here on, include/gcre_hip.h)
   while (!c->live_uids.empty()) free_uids(c->live_uids.back());
+  while (!c->live_tallies.empty()) gcre_gene_tally_free(c->live_tallies.back());
   {
     std::vector<const gcre_pathset*> sets;
     for (const auto& kv : c->live_sets) sets.push_back(kv.second);
@@ -3548,6 +3643,8 @@ int gcre_join(gcre_ctx* c, int path_length, const int32_t* uid_count, const int6
   JoinPlan jp{u, paths0, paths1, res, opts && opts->sharded, opts ? opts->shard_begin : 0,
               opts ? opts->shard_end : 0, opts ? opts->d_null_out : nullptr};
   jp.take(opts);
+  jp.tally = c->armed_tally;
+  c->armed_tally = nullptr;
   int rc = run_join(c, jp, out);
   free_uids(u);
   if (rc != GCRE_OK) gcre_result_free(out);
@@ -3607,6 +3704,8 @@ int gcre_join_uids(gcre_ctx* c, const gcre_uids* uids, const gcre_pathset* paths
   JoinPlan jp{uids, paths0, paths1, res, opts && opts->sharded, opts ? opts->shard_begin : 0,
               opts ? opts->shard_end : 0, opts ? opts->d_null_out : nullptr};
   jp.take(opts);
+  jp.tally = c->armed_tally;
+  c->armed_tally = nullptr;
   int rc = run_join(c, jp, out);
   if (rc != GCRE_OK) gcre_result_free(out);
   return rc;
@@ -3630,6 +3729,120 @@ int gcre_join_ahead(gcre_ctx* c, const gcre_uids* uids, const gcre_pathset* path
   a.take(opts);
   c->ahead->push_back(a);
   return GCRE_OK;
+}
+
+// ---- per-gene best-path tally ----
+gcre_gene_tally* gcre_gene_tally_create(gcre_ctx* c, int32_t n_slots, const int32_t* genes0, int64_t n_rows0, int32_t w0,
+                                        const int32_t* genes1, int64_t n_rows1, int32_t w1) {
+  if (!c) return nullptr;
+  auto bad = [&](const std::string& m) -> gcre_gene_tally* {
+    fail(c, GCRE_ERR_ARG, "gene tally: " + m);
+    return nullptr;
+  };
+  if (n_slots < 1) return bad("n_slots must be >= 1");
+  if (!genes0) { n_rows0 = 0; w0 = 0; }
+  if (!genes1) { n_rows1 = 0; w1 = 0; }
+  if (n_rows0 < 0 || n_rows1 < 0) return bad("negative row count");
+  if ((genes0 && (w0 < 1 || w0 > kGeneWidthMax)) || (genes1 && (w1 < 1 || w1 > kGeneWidthMax)))
+    return bad("a table's width must be 1.." + std::to_string(kGeneWidthMax));
+  for (int64_t i = 0; i < n_rows0 * w0; i++)
+    if (genes0[i] < -1 || genes0[i] >= n_slots) return bad("genes0 holds slot " + std::to_string(genes0[i]) + " outside -1.." + std::to_string(n_slots - 1));
+  for (int64_t i = 0; i < n_rows1 * w1; i++)
+    if (genes1[i] < -1 || genes1[i] >= n_slots) return bad("genes1 holds slot " + std::to_string(genes1[i]) + " outside -1.." + std::to_string(n_slots - 1));
+  (void)hipSetDevice(c->device);
+  gcre_gene_tally* t = new gcre_gene_tally();
+  t->ctx = c;
+  t->n_slots = n_slots;
+  t->n_rows0 = n_rows0;
+  t->n_rows1 = n_rows1;
+  t->w0 = w0;
+  t->w1 = w1;
+  c->live_tallies.push_back(t);
+  const size_t n = (size_t)n_slots, g0 = (size_t)(n_rows0 * w0), g1 = (size_t)(n_rows1 * w1);
+  hipError_t e = hipSuccess;
+  auto get = [&](void** p, size_t bytes) {
+    if (e == hipSuccess) e = hipMalloc(p, std::max<size_t>(bytes, 8));
+  };
+  get((void**)&t->d_genes0, g0 * 4);
+  get((void**)&t->d_genes1, g1 * 4);
+  get((void**)&t->d_ck, n * 8);
+  get((void**)&t->d_cidx, n * 4);
+  get((void**)&t->d_bkey, n * 8);
+  get((void**)&t->d_bord, n * 8);
+  get((void**)&t->d_bsrc, n * 4);
+  get((void**)&t->d_btrg, n * 4);
+  get((void**)&t->d_bcases, n * 4);
+  get((void**)&t->d_bctrls, n * 4);
+  if (e == hipSuccess && g0) e = hipMemcpyAsync(t->d_genes0, genes0, g0 * 4, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess && g1) e = hipMemcpyAsync(t->d_genes1, genes1, g1 * 4, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(t->d_ck, 0, n * 8, c->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(t->d_cidx, 0xff, n * 4, c->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(t->d_bkey, 0, n * 8, c->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(t->d_bord, 0xff, n * 8, c->stream);   // ordinal -1
+  if (e == hipSuccess) e = hipMemsetAsync(t->d_bsrc, 0xff, n * 4, c->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(t->d_btrg, 0xff, n * 4, c->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(t->d_bcases, 0, n * 4, c->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(t->d_bctrls, 0, n * 4, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);   // (the host tables may go once the call returns)
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    gcre_gene_tally_free(t);
+    fail(c, GCRE_ERR_DEVICE, std::string("gene tally: ") + hipGetErrorString(e));
+    return nullptr;
+  }
+  t->last = c->stream;
+  return t;
+}
+
+int gcre_join_set_tally(gcre_ctx* c, gcre_gene_tally* t) {
+  if (!c) return GCRE_ERR_ARG;
+  if (t && t->ctx != c) return fail(c, GCRE_ERR_ARG, "gene tally does not belong to this context");
+  c->armed_tally = t;
+  return GCRE_OK;
+}
+
+int gcre_process_paths_set_tally(gcre_ctx* c, int level, gcre_gene_tally* t) {
+  if (!c) return GCRE_ERR_ARG;
+  if (level < 0 || level > 5) return fail(c, GCRE_ERR_ARG, "gene tally: level index must be 0..5");
+  if (t && t->ctx != c) return fail(c, GCRE_ERR_ARG, "gene tally does not belong to this context");
+  c->pp_tally[level] = t;
+  return GCRE_OK;
+}
+
+int gcre_gene_tally_read(gcre_gene_tally* t, double* score, int64_t* ordinal, int32_t* src, int32_t* trg, int32_t* cases,
+                         int32_t* ctrls) {
+  if (!t || !t->ctx) return GCRE_ERR_ARG;
+  gcre_ctx* c = t->ctx;
+  (void)hipSetDevice(c->device);
+  if (t->last) HIP_TRY(c, hipStreamSynchronize(t->last));
+  const size_t n = (size_t)t->n_slots;
+  std::vector<uint64_t> key(n);
+  HIP_TRY(c, hipMemcpy(key.data(), t->d_bkey, n * 8, hipMemcpyDeviceToHost));
+  if (score)
+    for (size_t g = 0; g < n; g++) score[g] = key[g] ? key_to_score(key[g]) : -std::numeric_limits<double>::infinity();
+  if (ordinal) HIP_TRY(c, hipMemcpy(ordinal, t->d_bord, n * 8, hipMemcpyDeviceToHost));
+  if (src) HIP_TRY(c, hipMemcpy(src, t->d_bsrc, n * 4, hipMemcpyDeviceToHost));
+  if (trg) HIP_TRY(c, hipMemcpy(trg, t->d_btrg, n * 4, hipMemcpyDeviceToHost));
+  if (cases) HIP_TRY(c, hipMemcpy(cases, t->d_bcases, n * 4, hipMemcpyDeviceToHost));
+  if (ctrls) HIP_TRY(c, hipMemcpy(ctrls, t->d_bctrls, n * 4, hipMemcpyDeviceToHost));
+  return GCRE_OK;
+}
+
+void gcre_gene_tally_free(gcre_gene_tally* t) {
+  if (!t) return;
+  if (gcre_ctx* c = t->ctx) {
+    (void)hipSetDevice(c->device);
+    if (t->last) (void)hipStreamSynchronize(t->last);
+    if (c->armed_tally == t) c->armed_tally = nullptr;
+    for (auto& p : c->pp_tally)
+      if (p == t) p = nullptr;
+    auto& v = c->live_tallies;
+    v.erase(std::remove(v.begin(), v.end(), t), v.end());
+  }
+  for (void* p : {(void*)t->d_genes0, (void*)t->d_genes1, (void*)t->d_ck, (void*)t->d_cidx, (void*)t->d_bkey, (void*)t->d_bord,
+                  (void*)t->d_bsrc, (void*)t->d_btrg, (void*)t->d_bcases, (void*)t->d_bctrls})
+    if (p) (void)hipFree(p);
+  delete t;
 }
 
 void gcre_result_free(gcre_result* r) {
@@ -3673,6 +3886,16 @@ int gcre_process_paths(gcre_ctx* c, const gcre_pp_input* in, gcre_result out[5])
     out[i].n = -1;   // NULL list entry, wrapper.cpp:223
   }
   const int L = in->path_length;
+  // the tallies armed for this call (gcre_process_paths_set_tally): taken now, so that every road out leaves none armed
+  gcre_gene_tally* tallies[6];
+  bool any_tally = false;
+  for (int i = 0; i < 6; i++) {
+    tallies[i] = c->pp_tally[i];
+    c->pp_tally[i] = nullptr;
+    any_tally = any_tally || tallies[i] != nullptr;
+  }
+  if (any_tally && in->shard_world > 1)
+    return fail(c, GCRE_ERR_ARG, "a gene tally cannot be armed for one device of several: merging tallies across devices is not supported");
   gcre_profile total{};
   auto add_prof = [&]() {
     total.null_kernel_ms += c->prof.null_kernel_ms;
@@ -3737,6 +3960,7 @@ int gcre_process_paths(gcre_ctx* c, const gcre_pp_input* in, gcre_result out[5])
       if (in_range && gcre_uids_set_reduced(u, red, red_index, n_red) != GCRE_OK) return c->last_code;
     }
     JoinPlan jp{u, p0, p1, res, false, 0, 0, nullptr};
+    jp.tally = tallies[lvi];   // (every permutation window folds the same observed scores: harmless)
     if (in->shard_world > 1) {   // one device of several: its slice of the joined paths, every kept row
       jp.sharded = true;
       jp.shard_begin = u->total * in->shard_rank / in->shard_world;

@@ -371,4 +371,29 @@ hipError_t launch_set_observed(const int32_t* cnt, int64_t S, int method, const 
                                hipStream_t stream);
 hipError_t launch_set_null(const SetNullArgs& a, int method, hipStream_t stream);
 
+// ---- per-gene best-path tally (gcre_genes.hip) ----
+constexpr int kGeneWidthMax = 3;   // gene slots a path inherits from one operand row, at most
+// One scored stretch of a chunk, as its inspector left it, folded into a join's per-slot table.
+struct GeneFoldArgs {
+  const uint64_t* key;          // [count] score keys (score_key: monotone in the score, 0 = not a score)
+  const uint32_t* row0;         // [count] paths0 row = uid row (Score.src)
+  const uint32_t* row1;         // [count] paths1 row (Score.trg), bit 31 = the signed method's half swap
+  const uint32_t* cases;        // [count]
+  const uint32_t* ctrls;        // [count]
+  int64_t count;
+  int64_t first;                // joined-path ordinal of element 0
+  const int32_t* genes0;        // [rows of paths0][w0] slots, -1 = none; unused when w0 == 0
+  const int32_t* genes1;        // [rows of paths1][w1]
+  int w0, w1;                   // 0..kGeneWidthMax
+  int n_slots;
+  int prior;                    // != 0: bkey may hold entries (an earlier chunk or join was folded into the table)
+  uint64_t* ck;                 // [n_slots] chunk-local best key, 0 on entry and on exit
+  uint32_t* cidx;               // [n_slots] chunk-local index of the best path, 0xffffffff on entry and on exit
+  uint64_t* bkey;               // [n_slots] the join's table: key (0 = no scored path), ordinal, rows, counts
+  int64_t* bord;
+  int32_t *bsrc, *btrg, *bcases, *bctrls;
+};
+// k_gene_fold, k_gene_index, k_gene_merge on `stream`, in that order
+hipError_t launch_gene_fold(const GeneFoldArgs& a, int cus, hipStream_t stream);
+
 }  // namespace gcre

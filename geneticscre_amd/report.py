@@ -8,6 +8,9 @@
   * ``gwaspa``           the whole call, with the table / level tables / permutations built natively
   * ``score_paths``      permutation tests of paths and gene sets the caller names (k_set_null; beyond the reference)
   * ``check_best_paths`` checkBestPaths: rescore a GWASPA.Results table from the raw data   (R/CheckResults.R:2-89)
+  * ``gene_tables`` / ``gene_best_reference`` / ``gene_results`` / ``gene_summary``  the per-gene best-path table: for
+                         every gene the best path of each length through it, tallied on the device during the joins
+                         (gcre_gene_tally; beyond the reference)
 
 Host-side post-processing of <= top_k x 5 rows: string work, nothing here touches the scored path.
 """
@@ -344,6 +347,138 @@ def check_best_paths(results_df, genes: Sequence[str], data: np.ndarray, n_cases
 
 
 # ---------------------------------------------------------------------------------------------------------------
+# per-gene best paths
+
+GENE_LEVELS = ["1b", "2", "3", "4", "5"]   # the join whose top-k is lst1 .. lst5
+GENE_COLUMNS = ["Gene", "Lengths", "Scores", "Pvalues", "Cases", "Controls", "SignedPaths", "Paths"]
+
+
+def gene_slots(name: str, n_genes: int, n_genes2: int) -> int:
+    """Slots of a level's tally: ranks in Ents2 at level 1, in Ents above."""
+    return int(n_genes2 if name == "1b" else n_genes)
+
+
+def gene_tables(levels, n_genes: int, n_genes2: int) -> Dict[str, Tuple[Optional[np.ndarray], Optional[np.ndarray]]]:
+    """Per level name ("1b", "2", .., "5") the slot tables of a GeneTally: (genes0, genes1).  genes0[r] / genes1[r]
+    are the genes a joined path inherits from row r of the join's paths0 / paths1 (int32 [rows][w], None = none), read
+    from exactly the columns ``get_paths`` decodes for that level: a joined path (src, trg) touches
+    genes0[src] | genes1[trg], the genes ``get_paths`` prints for ids (src + 1, trg + 1).  Slots are ranks in Ents
+    (levels 2..5, ``n_genes`` of them) or in Ents2 (level 1, ``n_genes2``): ``gene_slots``."""
+    rs, rt = np.asarray(levels.uids["3"].src, np.int32), np.asarray(levels.uids["3"].trg, np.int32)   # rels: row = relation
+    r3 = levels.rels3
+    a, b, c = (np.asarray(r3[k], np.int32) for k in ("srcuid", "trguid", "trguid2"))
+    n2 = len(levels.uids["1b"].count)
+    triple = np.stack([a, b, c], axis=1) if len(a) else np.zeros((0, 3), np.int32)
+    out = {
+        # level 1: paths0 is empty, paths1 row j is the data row of Ents2 gene data_inds["1b"][j]
+        "1b": (None, np.asarray(levels.data_inds["1b"], np.int32).reshape(n2, 1)),
+        "2": (None, np.stack([rs, rt], axis=1)),            # paths0 = the source gene's row, named by rels too
+        "3": (np.stack([rs, rt], axis=1), rt.reshape(-1, 1)),
+        "4": (triple, rt.reshape(-1, 1)),
+        "5": (triple, np.stack([b, c], axis=1) if len(a) else np.zeros((0, 2), np.int32)),
+    }
+    for name, pair in out.items():
+        for t in pair:
+            if t is not None and t.size and (t.min() < 0 or t.max() >= gene_slots(name, n_genes, n_genes2)):
+                raise ValueError(f"level {name}: a gene rank lies outside the {gene_slots(name, n_genes, n_genes2)} genes given")
+    return out
+
+
+def gene_best_reference(all_scores, all_cases, all_ctrls, uids, genes0, genes1, n_slots: int,
+                        shard: Optional[Tuple[int, int]] = None) -> Dict[str, np.ndarray]:
+    """The definition of the per-gene tally in plain numpy -- what gcre_gene_tally must return, bit for bit.
+
+    ``all_scores`` / ``all_cases`` / ``all_ctrls``: one entry per joined path in ordinal order (ordinal p = path_idx[i] + j
+    for uid row i, j < count[i]; src = i, trg = location[i] + j).  A path touches the slots genes0[src] and genes1[trg]
+    (-1 and a None table: none).  Per slot: the touching path with the largest score, ties to the smallest ordinal
+    (lexsort on (-score, ordinal)); only scores above -inf count, and only ordinals inside ``shard`` when given.  A slot
+    nothing touches has score -inf, ordinal / src / trg -1 and counts 0."""
+    count = np.maximum(np.asarray(uids.count, dtype=np.int64), 0)
+    P = int(count.sum())
+    src = np.repeat(np.arange(len(count), dtype=np.int64), count)
+    first = np.cumsum(count) - count
+    trg = np.repeat(np.asarray(uids.location, dtype=np.int64), count) + (np.arange(P, dtype=np.int64) - np.repeat(first, count))
+    score = np.asarray(all_scores, dtype=np.float64)
+    assert len(score) == P
+    ok = score > -np.inf                       # (NaN compares false: not a score)
+    if shard is not None:
+        ords = np.arange(P)
+        ok &= (ords >= shard[0]) & (ords < shard[1])
+    out = {"score": np.full(n_slots, -np.inf), "ordinal": np.full(n_slots, -1, np.int64), "src": np.full(n_slots, -1, np.int32),
+           "trg": np.full(n_slots, -1, np.int32), "cases": np.zeros(n_slots, np.int32), "ctrls": np.zeros(n_slots, np.int32)}
+    slot_list, ord_list = [], []
+    for table, rows in ((genes0, src), (genes1, trg)):
+        if table is None:
+            continue
+        t = np.asarray(table, dtype=np.int64)
+        for col in range(t.shape[1]):
+            s = t[rows, col] if P else np.zeros(0, np.int64)
+            keep = ok & (s >= 0)
+            slot_list.append(s[keep])
+            ord_list.append(np.flatnonzero(keep))
+    if not slot_list:
+        return out
+    slots, ords = np.concatenate(slot_list), np.concatenate(ord_list)
+    order = np.lexsort((ords, -score[ords], slots))     # by slot, then score descending, then ordinal ascending
+    slots, ords = slots[order], ords[order]
+    head = np.ones(len(slots), bool)
+    head[1:] = slots[1:] != slots[:-1]
+    g, p = slots[head], ords[head]
+    out["score"][g] = score[p]
+    out["ordinal"][g] = p
+    out["src"][g] = src[p]
+    out["trg"][g] = trg[p]
+    out["cases"][g] = np.asarray(all_cases)[p]
+    out["ctrls"][g] = np.asarray(all_ctrls)[p]
+    return out
+
+
+def gene_results(best: Dict[int, object], level_results: Dict[str, object], frames: Dict[str, Dict[str, np.ndarray]],
+                 ents: Tuple[Sequence[int], Sequence[str]], ents2: Tuple[Sequence[int], Sequence[str]]):
+    """Gene.Results: one row per (gene, length) with a finite best score.  ``best``: length L -> the tally of that level
+    (anything with score / src / trg / cases / ctrls per slot: api.GeneBest, or gene_best_reference's dict); the other
+    arguments as ``results_table`` takes them.  ``Pvalues`` compare the f64 score with the length's f32-rounded null
+    maxima, like a GWASPA.Results row: a gene's best score is at most the level's maximum, so it is the family-wise
+    p-value over all paths of that length.  Paths are decoded from (src, trg) by ``get_paths``.  Ordered like
+    GWASPA.Results: p ascending, score descending, stable (lengths ascending, genes in Ents order)."""
+    import pandas as pd
+
+    per_level = {1: ("rels_data2", "rels_data2"), 2: ("rels_data", "rels"), 3: ("rels", "rels"),
+                 4: ("rels3", "rels"), 5: ("rels3", "rels3")}
+    cols: Dict[str, list] = {c: [] for c in GENE_COLUMNS}
+    for L in sorted(best):
+        b = best[L]
+        get = (lambda k: np.asarray(b[k])) if isinstance(b, dict) else (lambda k: np.asarray(getattr(b, k)))
+        score = get("score")
+        sel = np.flatnonzero(np.isfinite(score))
+        who = ents2 if L == 1 else ents
+        ids = np.stack([get("src")[sel].astype(np.int64) + 1, get("trg")[sel].astype(np.int64) + 1], axis=1)
+        f1, f2 = per_level[L]
+        paths, signpaths = get_paths(ids, L, frames[f1], frames[f2])
+        cols["Gene"] += [who[1][g] for g in sel.tolist()]
+        cols["Lengths"] += [L] * len(sel)
+        cols["Scores"] += score[sel].tolist()
+        cols["Pvalues"] += _tail_pvalues(level_results[f"lst{L}"].null, score[sel]).tolist()
+        cols["Cases"] += get("cases")[sel].tolist()
+        cols["Controls"] += get("ctrls")[sel].tolist()
+        cols["SignedPaths"] += uid_to_symbol(who[0], who[1], signpaths, signed=True)
+        cols["Paths"] += uid_to_symbol(who[0], who[1], paths)
+    df = pd.DataFrame(cols, columns=GENE_COLUMNS)
+    p = df["Pvalues"].to_numpy(dtype=np.float64)
+    order = np.lexsort((-df["Scores"].to_numpy(dtype=np.float64), np.where(np.isnan(p), np.inf, p)))
+    return df.iloc[order].reset_index(drop=True)
+
+
+def gene_summary(df):
+    """Per gene the one row of Gene.Results to look at first: the smallest p-value, then the highest score, then the
+    shortest length.  Genes in order of that row (p ascending, score descending)."""
+    p = df["Pvalues"].to_numpy(dtype=np.float64)
+    order = np.lexsort((df["Lengths"].to_numpy(), -df["Scores"].to_numpy(dtype=np.float64), np.where(np.isnan(p), np.inf, p)))
+    ranked = df.iloc[order]
+    return ranked[~ranked["Gene"].duplicated()].reset_index(drop=True)
+
+
+# ---------------------------------------------------------------------------------------------------------------
 # inputs
 
 
@@ -490,7 +625,7 @@ def frames_of(prep: Prepared, levels) -> Dict[str, Dict[str, np.ndarray]]:
 def gwaspa(genes: Sequence[str], data: np.ndarray, n_cases: int, n_ctrls: int, network, signed: bool = False,
            threshold: float = 0.05, top_k: int = 10, path_length: int = 5, n_permutations: int = 100,
            strata: Optional[Sequence[int]] = None, seed: int = 0, device: int = 0,
-           decorated_pvalues: bool = False) -> Dict[str, object]:
+           decorated_pvalues: bool = False, gene_table: bool = False) -> Dict[str, object]:
     """GWASPA (R/ProcessPaths.R:87-344) without R: dataset -> GWASPA.Results, scored on the MI355X.
 
     ``network`` = (ents_uid, ents_symbol, rel_src, rel_trg, rel_sign): the knowledge base getStringKB() would load
@@ -502,6 +637,11 @@ def gwaspa(genes: Sequence[str], data: np.ndarray, n_cases: int, n_ctrls: int, n
     ``decorated_pvalues``: also return "Decorated.Pvalues.Results", the split-path table of ``decorated_table``
     (R/DecoratedPvalue.R), drawn from a seed derived from ``seed`` (DECORATED_SEED_TAG).  R's GWASPA defaults to
     ``Decorated.Pvalues = TRUE``; here the default is False.  With ``path_length == 1`` it warns as R does and adds nothing.
+
+    ``gene_table``: also return "Gene.Results" (``gene_results``): for every gene and length the best path through the
+    gene, tallied on the device while the joins run (one GeneTally per level), and "gene_best" (length ->
+    api.GeneBest, the raw tallies).  ``gene_summary`` reduces it to one row per gene.  Default False: the joins launch
+    exactly what they launch without it.
     """
     from . import api
     from .synth import Problem
@@ -530,10 +670,21 @@ def gwaspa(genes: Sequence[str], data: np.ndarray, n_cases: int, n_ctrls: int, n
     ex.set_value_table(table)
     if n_permutations > 0:
         ex.generate_permutations(seed, strata)
-    lsts = api.process_paths(problem, device=device, exec_=ex)
-    out = {"GWASPA.Results": results_table(lsts, path_length, frames_of(prep, levels),
+    tallies = {}
+    if gene_table:
+        tables = gene_tables(levels, g, n2)
+        for name in GENE_LEVELS[:path_length]:
+            tallies[name] = api.GeneTally(ex, gene_slots(name, g, n2), *tables[name])
+    lsts = api.process_paths(problem, device=device, exec_=ex, tallies=tallies or None)
+    frames = frames_of(prep, levels)
+    out = {"GWASPA.Results": results_table(lsts, path_length, frames,
                                            (prep.ents_uid, prep.ents_symbol), (prep.ents2_uid, prep.ents2_symbol)),
            "levels": lsts, "prepared": prep}
+    if gene_table:
+        best = {L + 1: tallies[name].read() for L, name in enumerate(GENE_LEVELS[:path_length])}
+        out["gene_best"] = best
+        out["Gene.Results"] = gene_results(best, lsts, frames, (prep.ents_uid, prep.ents_symbol),
+                                           (prep.ents2_uid, prep.ents2_symbol))
     if decorated_pvalues:
         dseed = int(api.load_library().gcre_mix64((int(seed) ^ DECORATED_SEED_TAG) & (2**64 - 1)))
         dec = decorated_table(out["GWASPA.Results"], genes, data, n_cases, n_ctrls, signed, n_permutations, strata,

@@ -102,7 +102,7 @@ typedef struct {
 
 /* ---- context: JoinExec::JoinExec, src/join_base.cpp:37-59.  method 1 = unsigned, 2 = signed. ---- */
 gcre_ctx* gcre_create(int method, int n_cases, int n_ctrls, int iterations, int device);
-void gcre_destroy(gcre_ctx* ctx);   /* also releases every path set and uids object still alive on the context: their handles die with it */
+void gcre_destroy(gcre_ctx* ctx);   /* also releases every path set, uids object and gene tally still alive on the context: their handles die with it */
 const char* gcre_last_error(const gcre_ctx* ctx);   /* ctx may be NULL: error of the last failed gcre_create */
 int gcre_abi_version(void);
 /* the extra compiler flags the library was built with ("" for the shipped build): a diagnostics build that switches parts of
@@ -432,6 +432,42 @@ typedef struct {
  * iterations > 0 and no masks set.  DESIGN.md §3.6. */
 int gcre_score_sets(gcre_ctx* ctx, const gcre_set_input* in, gcre_set_score* out, int64_t cap, int64_t* n_out,
                     float* family_max);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * Per-gene best-path table: for every gene, the best joined path of a join that runs through it.  No
+ * reference counterpart (it keeps the top K of a level and nothing else).  A join's inspector leaves the observed score,
+ * operand rows, cases and controls of EVERY joined path on the device; a tally armed for the join folds them, chunk by
+ * chunk, into one entry per gene slot before they are overwritten.  Nothing is rescored, the join's own result does not
+ * change, and a join without a tally launches exactly what it launched before.
+ *
+ * A joined path with ordinal p = path_idx[i] + j (uid row i, j < count[i]) has src = i and trg = location[i] + j (Score.src
+ * / .trg) and touches the slots genes0[src][0..w0) and genes1[trg][0..w1) (-1 = none; a slot listed twice counts once).
+ * Per slot the tally keeps the touching path with the largest observed score, ties to the smallest ordinal (the rule of
+ * the top-k lists); only paths the join scores count (gcre_join_opts.sharded: the shard), and only scores above -inf.
+ * The table is bit-identical whatever the chunking, the inspection cache, the launch-ahead chain, the permutation window
+ * or the null kernel form.  A level's null_max bounds every entry of that level: #{null_max >= score} / K is a family-wise
+ * p-value over all paths of the length, the number a top-k row gets. */
+typedef struct gcre_gene_tally gcre_gene_tally;
+
+/* genes0: [n_rows0][w0] int32 slots of the rows of paths0 (n_rows0 must equal the uid rows of the join it is armed for),
+ * genes1: [n_rows1][w1] of the rows of paths1 (n_rows1 must exceed every paths1 row the join reads); w 1..3, values
+ * -1..n_slots-1.  NULL for a table = that operand contributes no gene (level 1 and 2: paths0).  The tables are copied.
+ * NULL on error (GCRE_ERR_ARG with a message: nothing is launched on a malformed table).  Several joins may fold into one
+ * tally when their ordinals mean the same paths (the shards of one join). */
+gcre_gene_tally* gcre_gene_tally_create(gcre_ctx* ctx, int32_t n_slots, const int32_t* genes0, int64_t n_rows0, int32_t w0,
+                                        const int32_t* genes1, int64_t n_rows1, int32_t w1);
+/* The next gcre_join / gcre_join_uids call on the context folds into `tally`, then the context is disarmed (whether the
+ * join succeeds or not).  NULL disarms.  The row counts are checked against the join before anything is launched. */
+int gcre_join_set_tally(gcre_ctx* ctx, gcre_gene_tally* tally);
+/* The same for the next gcre_process_paths call: level = index into gcre_pp_input.level (0..5 = 1a, 1b, 2, 3, 4, 5).
+ * A call that is one device of several (shard_world > 1, which is how gcre_process_paths_devices runs its contexts)
+ * refuses an armed tally with GCRE_ERR_ARG: merging tallies across devices is left to callers of the join interface. */
+int gcre_process_paths_set_tally(gcre_ctx* ctx, int level, gcre_gene_tally* tally);
+/* Waits for the folds in flight, then one entry per slot (any output may be NULL): score -inf, ordinal / src / trg -1 and
+ * counts 0 where no scored path touches the slot. */
+int gcre_gene_tally_read(gcre_gene_tally* tally, double* score, int64_t* ordinal, int32_t* src, int32_t* trg,
+                         int32_t* cases, int32_t* ctrls);
+void gcre_gene_tally_free(gcre_gene_tally* tally);   /* gcre_destroy frees the ones still alive */
 
 #ifdef __cplusplus
 }
