@@ -130,6 +130,8 @@ EXPORTS = [
     "gcre_decorated_splits", "gcre_decorated_pvalues", "gcre_score_sets",
     "gcre_gene_tally_create", "gcre_join_set_tally", "gcre_process_paths_set_tally", "gcre_gene_tally_read",
     "gcre_gene_tally_free",
+    "gcre_exceed_create", "gcre_join_set_exceed", "gcre_process_paths_set_exceed", "gcre_exceed_read",
+    "gcre_exceed_reset", "gcre_exceed_free",
 ]
 
 
@@ -341,6 +343,73 @@ class GeneTally:
         h, self._h = self._h, None
         if h and self._owner._h:       # (a closed context has freed it already)
             self._lib.gcre_gene_tally_free(h)
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def _exceed_lib():
+    """The library with the exceedance-count entries bound, on first use (as _decorated_lib)."""
+    lib = load_library()
+    if not hasattr(lib, "gcre_exceed_create"):
+        raise GcreError(f"{lib._name} has no null exceedance counts (gcre_exceed_create): rebuild it")
+    if lib.gcre_exceed_create.argtypes is None:
+        V, P = ctypes.c_void_p, ctypes.c_void_p
+        lib.gcre_exceed_create.restype = V
+        lib.gcre_exceed_create.argtypes = [V, P, ctypes.c_int32]
+        lib.gcre_join_set_exceed.argtypes = [V, V]
+        lib.gcre_process_paths_set_exceed.argtypes = [V, ctypes.c_int, V]
+        lib.gcre_exceed_read.argtypes = [V, P, P, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]
+        lib.gcre_exceed_reset.argtypes = [V]
+        lib.gcre_exceed_free.argtypes = [V]
+        lib.gcre_exceed_free.restype = None
+    return lib
+
+
+EXCEED_MAX = 10000   # kExceedMax: thresholds of one ExceedCounts (the top_k limit)
+
+
+@dataclass
+class Exceedances:
+    """gcre_exceed_read, in the order of the thresholds given."""
+
+    exceed: np.ndarray     # uint64: (joined path, permutation) pairs with a null score >= the threshold
+    observed: np.ndarray   # uint64: joined paths with an observed score >= the threshold
+    perms: int             # permutations counted (the window lengths of the joins counted, added)
+    paths: int             # joined paths whose observed scores were counted
+
+
+class ExceedCounts:
+    """gcre_exceed: null exceedance counts of a join for a list of thresholds.  Pass it as
+    ``JoinExec.join(..., exceed=x)`` or ``process_paths(..., exceeds={"4": x})``, then ``read()``.  Counts ADD: a join counted
+    twice is counted twice (``reset()`` starts over); ``report.fdr_columns`` turns them into PFER, FDR and q-values."""
+
+    def __init__(self, owner: "JoinExec", thresholds):
+        t = np.ascontiguousarray(np.asarray(thresholds, dtype=np.float64).ravel())
+        self.thresholds = t
+        self._owner, self._lib, self._h = owner, _exceed_lib(), None
+        self._h = self._lib.gcre_exceed_create(owner._h, _ptr(t), len(t))
+        if not self._h:
+            owner._raise(GCRE_ERR_ARG)
+
+    def read(self) -> Exceedances:
+        m = len(self.thresholds)
+        exceed, observed = np.zeros(m, np.uint64), np.zeros(m, np.uint64)
+        perms, paths = ctypes.c_int64(0), ctypes.c_int64(0)
+        self._owner._check(self._lib.gcre_exceed_read(self._h, _ptr(exceed), _ptr(observed), ctypes.byref(perms),
+                                                      ctypes.byref(paths)))
+        return Exceedances(exceed, observed, int(perms.value), int(paths.value))
+
+    def reset(self) -> None:
+        self._owner._check(self._lib.gcre_exceed_reset(self._h))
+
+    def free(self) -> None:
+        h, self._h = self._h, None
+        if h and self._owner._h:       # (a closed context has freed it already)
+            self._lib.gcre_exceed_free(h)
 
     def __del__(self):
         try:
@@ -700,14 +769,15 @@ class JoinExec:
     def join(self, uids, paths0: PathSet, paths1: PathSet, paths_res: Optional[PathSet] = None,
              shard: Optional[Tuple[int, int]] = None, d_null_out: int = 0,
              keep: Optional[Tuple[int, int]] = None, keep_mode: int = 1, exchange=None, exchanges: int = 0,
-             tally: Optional["GeneTally"] = None) -> JoinResult:
+             tally: Optional["GeneTally"] = None, exceed: Optional["ExceedCounts"] = None) -> JoinResult:
         """JoinExec::join (src/join_base.cpp:189-264).  ``paths_res`` receives the joined rows when given.
         ``uids`` is a UidRelSet (uploaded for this call) or a DeviceUids (already resident).  ``shard`` restricts
         scoring to a range of joined paths; ``keep`` restricts the rows written to ``paths_res`` to a range (plus
         the scored shard) -- the rows this device's shards of the later joins will read -- or, with ``keep_mode`` 2,
         only the rows that get count planes (all rows are still written).  ``exchange(k0, k1)`` is called ``exchanges``
         times during the join (gcre_join_opts.exchange): it MAX-all-reduces d_null_out[k0:k1] across the ranks in place.
-        ``tally``: a GeneTally this join's scored paths are folded into (gcre_join_set_tally)."""
+        ``tally``: a GeneTally this join's scored paths are folded into (gcre_join_set_tally).  ``exceed``: an ExceedCounts
+        this join's null values and observed scores are counted into (gcre_join_set_exceed)."""
         opts = gcre_join_opts(0, 0, 0, 0, None, 0, 0, 0, None, None)
         cb = None
         if exchange is not None and exchanges > 0:
@@ -741,6 +811,10 @@ class JoinExec:
                 ends = (np.asarray(uids.location, dtype=np.int64) + cnt)[cnt > 0]
                 check_gene_tables(tally.n_slots, tally.genes0, tally.genes1, len(cnt), int(ends.max()) - 1 if len(ends) else -1)
             self._check(_genes_lib().gcre_join_set_tally(self._h, tally._h))
+        if exceed is not None:
+            if exceed._owner is not self or not exceed._h:
+                raise GcreError("exceedance counts do not belong to this context")
+            self._check(_exceed_lib().gcre_join_set_exceed(self._h, exceed._h))
         if isinstance(uids, DeviceUids):
             rc = self._lib.gcre_join_uids(self._h, uids._h, paths0._h, paths1._h, res_h, ctypes.byref(opts),
                                           ctypes.byref(res))
@@ -910,14 +984,17 @@ def process_paths_devices(problem, devices=None, tallies=None) -> Dict[str, obje
     return {f"lst{i + 1}": (None if outs[i].n < 0 else _take_result(lib, outs[i])) for i in range(5)}
 
 
-def process_paths(problem, device: int = 0, exec_: Optional[JoinExec] = None, tallies=None) -> Dict[str, object]:
+def process_paths(problem, device: int = 0, exec_: Optional[JoinExec] = None, tallies=None, exceeds=None) -> Dict[str, object]:
     """ProcessPaths (src/wrapper.cpp:177-281) in one native call.  Returns {"lst1": JoinResult | None, ...}.
 
     ``problem`` carries the 39 arguments as arrays (geneticscre_amd.synth.Problem).  ``tallies``: level name ("1b", "2",
-    .., "5"; "1a" too) -> GeneTally of ``exec_``: that level's join folds its scored paths into it.
+    .., "5"; "1a" too) -> GeneTally of ``exec_``: that level's join folds its scored paths into it.  ``exceeds``: level name
+    -> ExceedCounts of ``exec_``: that level's join counts into it (all permutations, the observed scores once).
     """
     if tallies and exec_ is None:
         raise GcreError("process_paths: gene tallies live on a context; pass the JoinExec they were made on as exec_")
+    if exceeds and exec_ is None:
+        raise GcreError("process_paths: exceedance counts live on a context; pass the JoinExec they were made on as exec_")
     ex = exec_ or JoinExec(problem.method, problem.n_cases, problem.n_ctrls, problem.iterations, device)
     ex.top_k = problem.top_k
     lib = ex._lib
@@ -956,6 +1033,13 @@ def process_paths(problem, device: int = 0, exec_: Optional[JoinExec] = None, ta
         check_gene_tables(t.n_slots, t.genes0, t.genes1, len(cnt), int(ends.max()) - 1 if len(ends) else -1)
     for name, t in (tallies or {}).items():
         ex._check(_genes_lib().gcre_process_paths_set_tally(ex._h, LEVEL_INDEX[name], t._h))
+    for name, x in (exceeds or {}).items():
+        if name not in LEVEL_INDEX:
+            raise GcreError(f"process_paths: no level {name!r} (levels are {', '.join(LEVEL_INDEX)})")
+        if x._owner is not ex or not x._h:
+            raise GcreError("exceedance counts do not belong to this context")
+    for name, x in (exceeds or {}).items():
+        ex._check(_exceed_lib().gcre_process_paths_set_exceed(ex._h, LEVEL_INDEX[name], x._h))
     rc = lib.gcre_process_paths(ex._h, ctypes.byref(inp), outs)
     ex._check(rc)
     result: Dict[str, object] = {}
@@ -1150,7 +1234,7 @@ class ResidentPlan:
         return int(min(most, np.floor(np.log2(work / unit))))
 
     def run(self, rank: int = 0, world: int = 1, d_null_out: int = 0, on_level=None,
-            keep_inspections: bool = False, exchange=None, tallies=None) -> Dict[str, JoinResult]:
+            keep_inspections: bool = False, exchange=None, tallies=None, exceeds=None) -> Dict[str, JoinResult]:
         """One pass over all levels.  Large permutation counts run in windows of whole 2048-permutation tiles (the count
         planes of the kept sets are per tile and have to fit in device memory): all levels for window 0, then all levels
         for window 1, ...  ``on_level(name, result, shard, window)`` sees every (level, window) result -- its null
@@ -1169,9 +1253,15 @@ class ResidentPlan:
         it learned from the others; their MAX over the ranks is unchanged.
 
         ``tallies``: level name -> GeneTally of ``self.ex``; that level's join folds its scored paths into it (every window
-        folds the same observed scores again, which changes nothing).  One rank only."""
+        folds the same observed scores again, which changes nothing).  One rank only.
+
+        ``exceeds``: level name -> ExceedCounts of ``self.ex``; that level's join counts into it.  Every (level, window) is a
+        join call of its own: the null values of the windows add up to all permutations, and the observed scores are
+        counted once per window (``Exceedances.paths`` says how often: it grows by the level's joined paths each time)."""
         if tallies and world > 1:
             raise GcreError("ResidentPlan.run: gene tallies need world == 1 (merging tallies across ranks is not supported)")
+        if exceeds and world > 1:
+            raise GcreError("ResidentPlan.run: exceedance counts need world == 1 (add the counts of sharded joins yourself)")
         K = self.problem.iterations
         if self._window is None:
             self._window = self.planned_window()
@@ -1220,7 +1310,7 @@ class ResidentPlan:
                                  d_null_out=(d_null_out + 4 * k0) if d_null_out else 0,
                                  keep=self.needed_rows(name, rank, world), keep_mode=self.keep_mode(name),
                                  exchange=(lambda a, b_, name=name: exchange(name, a, b_)) if n_ex else None, exchanges=n_ex,
-                                 tally=(tallies or {}).get(name))
+                                 tally=(tallies or {}).get(name), exceed=(exceeds or {}).get(name))
                 for k, v in self.ex.profile().items():
                     prof[k] = prof.get(k, 0) + v
                 if on_level is not None:

@@ -393,6 +393,10 @@ struct gcre_ctx {
   std::vector<gcre_gene_tally*> live_tallies;
   gcre_gene_tally* armed_tally = nullptr;
   gcre_gene_tally* pp_tally[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  // null exceedance counts (gcre_exceed): alive, armed for the next join, armed for the next gcre_process_paths
+  std::vector<gcre_exceed*> live_exceeds;
+  gcre_exceed* armed_exceed = nullptr;
+  gcre_exceed* pp_exceed[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   uint64_t next_set_id = 0;
   size_t planes_out_max = (size_t)8 << 30;   // kept sets (method 1) whose planes are larger keep a recipe only
 
@@ -531,6 +535,21 @@ struct gcre_gene_tally {
   hipStream_t last = nullptr;         // the stream of the last fold: a read waits for it
   bool folded = false;                // the table holds something (k_gene_fold then also tests against it)
   bool folding = false;               // a fold did not get all its launches queued: the chunk-local tables are cleared first
+};
+
+// Null exceedance counts of one list of thresholds.  The thresholds are kept sorted ascending on the
+// device, as f32 bit patterns for the null values and as score keys for the observed scores; a counted value lands in the
+// bin of the largest threshold it reaches, and a read sums the bins from each threshold upwards.  Sums: every chunk counted
+// adds, whichever stream it ran on.
+struct gcre_exceed {
+  gcre_ctx* ctx = nullptr;
+  int m = 0;
+  std::vector<int32_t> order;         // sorted position -> the caller's index
+  uint32_t* d_pat = nullptr;          // [m] ascending
+  uint64_t* d_tkey = nullptr;         // [m] ascending
+  unsigned long long* d_hist = nullptr;    // [m] (path, permutation) pairs per bin
+  unsigned long long* d_ohist = nullptr;   // [m] joined paths per bin
+  int64_t perms = 0, paths = 0;       // permutations / joined paths that went into the bins
 };
 
 namespace {
@@ -1147,6 +1166,8 @@ struct JoinPlan {
   int (*exchange)(void*, void*, int32_t, int32_t) = nullptr;
   void* exchange_user = nullptr;
   gcre_gene_tally* tally = nullptr;   // the join's scored paths are folded into it (never set on a registered later join)
+  gcre_exceed* exceed = nullptr;      // the join's null values and observed scores are counted into it (the same)
+  bool exceed_observed = true;        // ... the observed scores too (false: a later permutation window of the same join)
   void take(const gcre_join_opts* o) {
     if (!o) return;
     if (o->keep_ranged) {
@@ -1355,7 +1376,10 @@ void merge_candidates(std::vector<Candidate>& cands, int top_k, gcre_result* out
 // kLaunch (the chain of gcre_join_ahead): the join's permutation kernels are launched -- on the main stream, into the join
 // index's own maxima, from the inspection that ran ahead -- and nothing is waited for; the call that comes for the join finds
 // it launched and only finishes it (wait, copy the maxima, merge the cached winners).
-enum JoinMode { kFull = 0, kInspect = 1, kLaunch = 2 };
+// kCount (gcre_exceed armed on a join that was launched ahead): once the join's result is delivered, its chunks are replayed
+// from the inspection cache as far as each chunk's IeArgs, and the exceedance kernels are launched where the null kernels
+// were; no inspector, no null kernel, no selection, no result.
+enum JoinMode { kFull = 0, kInspect = 1, kLaunch = 2, kCount = 3 };
 
 using EvList = std::vector<std::pair<hipEvent_t, hipEvent_t>>;
 
@@ -1460,6 +1484,78 @@ int fold_genes(gcre_ctx* c, gcre_gene_tally* t, const ChunkBufs& b, int64_t cb, 
   return GCRE_OK;
 }
 
+// ---- null exceedance counts (gcre_exceed.hip): scored paths [s0, s1) of a chunk whose inspector output is in `b` ----
+// Queued on `st` where the tally is, for the same reason (the next inspector rewrites `b`).  `ie`: the IeArgs the chunk's own
+// inclusion-exclusion launches were given (k_exceed_ie takes the same); without them the count is k_null's mapping on the
+// chunk's row0 / row1 / tot, which every chunk has.  NOT idempotent: run_chunk counts a chunk once, when no stage sends it
+// round again.
+int xcd_waves(const gcre_ctx* c, int waves_per_cu);
+int count_exceed(gcre_ctx* c, const JoinPlan& jp, const ChunkBufs& b, int64_t s0, int64_t s1, hipStream_t st,
+                 const IeArgs* ie = nullptr, int ie_planes = 0, int64_t ie_segs = 0) {
+  gcre_exceed* x = jp.exceed;
+  if (s1 <= s0) return GCRE_OK;
+  const Geometry& g = c->g;
+  // GCRE_EXCEED_KERNEL=dense: every chunk through k_exceed_dense (two independent forms can then be compared); =ie, or
+  // unset: k_exceed_ie wherever the chunk's own null kernel took the inclusion-exclusion form
+  const char* form = std::getenv("GCRE_EXCEED_KERNEL");
+  if (form && std::strcmp(form, "dense") == 0) ie = nullptr;
+  const int lds_bins = x->m <= (ie ? kExceedLdsBinsIe : kExceedLdsBinsDense) ? x->m : 0;
+  if (jp.exceed_observed) {
+    ExceedObsArgs oa{};
+    oa.key = b.key.p + s0;
+    oa.tkey = x->d_tkey;
+    oa.hist = x->d_ohist;
+    oa.count = s1 - s0;
+    oa.m = x->m;
+    oa.lds_bins = lds_bins;
+    HIP_TRY(c, launch_exceed_observed(oa, c->cus, st));
+    x->paths += s1 - s0;
+  }
+  const int K = c->win_K;
+  if (K <= 0) return GCRE_OK;
+  if (std::getenv("GCRE_EXCEED_TRACE"))   // (tests: which form counted the chunk)
+    std::fprintf(stderr, "[exceed] %s form: %lld joined paths x %d permutations, %d thresholds\n", ie ? "ie" : "dense",
+                 (long long)(s1 - s0), K, x->m);
+  if (ie) {
+    IeArgs xa = *ie;
+    xa.seg_begin = 0;
+    xa.seg_end = ie_segs;
+    xa.planes_out = nullptr;
+    xa.null_bits = nullptr;
+    xa.stats = nullptr;
+    xa.timing = nullptr;
+    const int wpc = std::min(c->sparse_waves_per_cu, exceed_ie_max_waves_per_cu(g.method, ie_planes, lds_bins));
+    xa.waves_per_xcd = std::min(ie->waves_per_xcd, xcd_waves(c, wpc));
+    HIP_TRY(c, launch_exceed_ie(xa, g.method, ie_planes, x->d_pat, x->d_hist, x->m, lds_bins, st));
+    return GCRE_OK;
+  }
+  const NullConfig cfg = null_config(g.method, K);
+  ExceedArgs a{};
+  a.p0 = (const uint32_t*)jp.p0->d_rows;
+  a.p1 = (const uint32_t*)jp.p1->d_rows;
+  a.masks = c->d_masks + c->win_k0;
+  a.row0 = b.row0.p + s0;
+  a.row1 = b.row1.p + s0;
+  a.tot = b.tot.p + (size_t)s0 * g.method;
+  a.t32 = c->d_t32;
+  a.d64 = c->d_dmax;
+  a.pat = x->d_pat;
+  a.hist = x->d_hist;
+  a.npaths = s1 - s0;
+  a.npt = (a.npaths + cfg.path_tile - 1) / cfg.path_tile;
+  a.S32 = 2 * g.S;
+  a.W32p = 2 * g.Wp;
+  a.Kpad = g.Kpad;
+  a.K = K;
+  a.nkt = (K + cfg.perm_tile - 1) / cfg.perm_tile;
+  const int64_t want = (int64_t)c->cus * c->null_blocks_per_cu;
+  a.pgroups = (int)std::min<int64_t>(std::max<int64_t>(1, want / a.nkt), a.npt);
+  a.m = x->m;
+  a.lds_bins = lds_bins;
+  HIP_TRY(c, launch_exceed_dense(a, g.method, cfg, st));
+  return GCRE_OK;
+}
+
 // The tail of a join whose kernels were launched ahead (run_join, kLaunch): wait for them, copy the maxima out of the join
 // index's own array, merge the winners its inspection cached.
 int finish_launched(gcre_ctx* c, const JoinPlan& jp, gcre_result* out) {
@@ -1487,6 +1583,9 @@ int finish_launched(gcre_ctx* c, const JoinPlan& jp, gcre_result* out) {
   if (int rc = deliver_join(c, jp, out, K, L.d_null.p, c->insp_stream, cands, L.ev_null, L.ev_stats, t_begin, nullptr))
     return rc;
   c->prof.ie_lookup_tiles += lookups;
+  // counts are sums: every chunk once, through the chunk loop itself (its cuts are the launch's)
+  if (jp.exceed)
+    if (int rc = run_join(c, jp, nullptr, kCount)) return rc;
   return GCRE_OK;
 }
 
@@ -1573,6 +1672,11 @@ struct ChunkRun {
   Winners win;
   bool win_from_cache = false;
   uint32_t flags[kFlagWords] = {};     // score_chunk_ie: the inspector's flag block
+  // score_chunk_ie, once the chunk's launches are decided: what they were given (the exceedance count takes the same)
+  bool ie_ok = false;
+  IeArgs ie{};
+  int ie_planes = 0;
+  int64_t ie_segs = 0;                 // scored segments: the first ones of ie.segs
 };
 
 // How a chunk's stages ended: the chunk loop of run_join runs it again after the last four
@@ -1770,6 +1874,7 @@ int begin_join(JoinRun& R, Begin* next) {
     return fail(c, GCRE_ERR_ASSERT, "assertion: paths_res.size != total paths");
   if (jp.tally && mode == kFull)
     if (int rc = check_tally(c, jp.tally, u)) return rc;
+  if (jp.exceed && jp.exceed->ctx != c) return fail(c, GCRE_ERR_ARG, "exceedance counts do not belong to this context");
   // ---- inspection cache: has this very join (same operand rows, kept set, shard, table) run on this index before? ----
   InspKey& ikey = R.ikey;
   if (c->insp_cache) {
@@ -1790,6 +1895,7 @@ int begin_join(JoinRun& R, Begin* next) {
     ikey.top_k = c->top_k;
     ikey.null_kernel = c->null_kernel;
     R.replay = u.insp_valid && u.insp_key == ikey && (!keep || jp.res->version == u.insp_res_ver);
+    if (mode == kCount && !R.replay) return fail(c, GCRE_ERR_DEVICE, "internal: the counting pass of a join launched ahead found no inspection to replay");
     // not launched: the join's own call runs it whole
     if (mode == kLaunch && (!R.replay || jp.exchange || g.K <= 0)) return GCRE_OK;
     if (mode == kFull && u.launch.active) {
@@ -1813,6 +1919,8 @@ int begin_join(JoinRun& R, Begin* next) {
       u.insp_key = ikey;
     }
     u.insp_valid = false;   // until this call completes
+  } else if (mode == kCount) {
+    return fail(c, GCRE_ERR_DEVICE, "internal: the counting pass of a join launched ahead needs the inspection cache");
   } else if (mode != kFull) {
     return GCRE_OK;   // no inspection cache, nothing to inspect or launch ahead
   } else if (u.insp_valid || !u.insp.empty()) {
@@ -1863,7 +1971,7 @@ int begin_join(JoinRun& R, Begin* next) {
       if (!u.launch.done && hipEventCreateWithFlags(&u.launch.done, hipEventDisableTiming) != hipSuccess)
         return fail(c, GCRE_ERR_DEVICE, "hipEventCreate failed");
       HIP_TRY(c, hipMemsetAsync(R.w_null, 0, ((size_t)g.Kpad + 1) * 4, st));
-    } else if (g.Kpad > 0) {
+    } else if (g.Kpad > 0 && mode != kCount) {   // (a counting pass writes no maxima)
       HIP_TRY(c, hipMemsetAsync(R.w_null, 0, (size_t)g.Kpad * 4, st));
     }
   }
@@ -2024,8 +2132,8 @@ int prepare_operands(JoinRun& R) {
         const size_t nominal = (size_t)std::max<int64_t>(jp.res->nrows, 1) * g.method * nkt_nom * (size_t)out_groups * 1024;
         want_out = nominal <= c->planes_out_max || R.use_rec || jp.res->planes_wanted;
       }
-      if (inspect_only) {
-        // (the join proper allocates -- or drops -- the kept rows' planes)
+      if (inspect_only || R.mode == kCount) {
+        // (the join proper allocates -- or drops -- the kept rows' planes; a counting pass leaves them as they are)
       } else if (want_out) {
         R.res_planes = alloc_planes(c, jp.res, out_groups);
         R.res_planes_ok = R.res_planes;
@@ -2224,7 +2332,7 @@ int inspect_chunk(JoinRun& R, ChunkRun& C, ChunkEnd* end) {
   }
   // the top-k selection only needs the keys the inspector just wrote: its digit passes run now, their state
   // comes back with the inspector's flags, its winners are collected before the null kernel starts
-  if (C.use_ie && g.K > 0 && C.scored && !C.sel_done) {
+  if (C.use_ie && g.K > 0 && C.scored && !C.sel_done && R.mode != kCount) {
     if (c->sel_async) {   // beside the warm-up slice and the null kernel, behind the inspector
       HIP_TRY(c, hipEventRecord(c->ev_sel, st));
       HIP_TRY(c, hipStreamWaitEvent(c->sel_stream, c->ev_sel, 0));
@@ -2508,6 +2616,16 @@ int score_chunk_ie(JoinRun& R, ChunkRun& C, ChunkEnd* end) {
   ia.waves_per_xcd = spread_waves(xcd_waves(c, wpc), n * ie_tile_factor, 32);
   R.prof->inspect_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ti0).count();
   ia.stats = R.mode == kLaunch ? R.w_null + g.Kpad : R.flagblk + kFlagLookupTiles;   // zeroed with the block before the inspector ran
+  if (jp.exceed) {
+    C.ie = ia;
+    C.ie_planes = planes;
+    C.ie_segs = nseg_scored;
+    C.ie_ok = true;
+    if (R.mode == kCount) {   // this chunk's null kernels ran with the launch: only the count is left (run_chunk)
+      *end = ChunkEnd::kScored;
+      return GCRE_OK;
+    }
+  }
   const bool timing = std::getenv("GCRE_IE_TIMING") != nullptr;   // diagnostics builds only (-DGCRE_IE_TIMING)
   if (timing) {
     HIP_TRY(c, c->d_ie_timing.reserve(8));
@@ -2702,6 +2820,8 @@ int run_chunk(JoinRun& R, const Seg& sg, int64_t cb, int64_t ce, ChunkEnd* end) 
   ChunkRun C;
   *end = ChunkEnd::kOpen;
   if (int rc = open_chunk(R, C, sg, cb, ce)) return rc;
+  if (R.mode == kCount && !C.hit)   // (its inspector would rewrite what the joins launched behind this one are reading)
+    return fail(R.c, GCRE_ERR_DEVICE, "internal: the counting pass of a join launched ahead met a chunk that is not in the inspection cache");
   if (int rc = inspect_chunk(R, C, end)) return rc;
   if (*end == ChunkEnd::kOpen && R.g.K > 0 && C.use_ie)
     if (int rc = score_chunk_ie(R, C, end)) return rc;
@@ -2714,7 +2834,7 @@ int run_chunk(JoinRun& R, const Seg& sg, int64_t cb, int64_t ce, ChunkEnd* end) 
     return GCRE_OK;
   }
   if (!C.scored) return GCRE_OK;
-  if (R.g.K > 0 && (*end == ChunkEnd::kOpen || *end == ChunkEnd::kPricedOut)) {
+  if (R.g.K > 0 && R.mode != kCount && (*end == ChunkEnd::kOpen || *end == ChunkEnd::kPricedOut)) {
     if (R.mode == kInspect) {
       if (C.use_sparse && C.ci) {
         // the delta-streaming road sizes its counters from the inspector's flag block: an ahead inspection reads it now and
@@ -2734,6 +2854,11 @@ int run_chunk(JoinRun& R, const Seg& sg, int64_t cb, int64_t ce, ChunkEnd* end) 
   // own kernels, before the next chunk's inspector -- on this stream too -- may rewrite them
   if (R.jp.tally && R.mode == kFull)
     if (int rc = fold_genes(R.c, R.jp.tally, *C.b, C.cb, C.s0, C.s1, R.st)) return rc;
+  if (R.jp.exceed && (R.mode == kFull || R.mode == kCount))
+    if (int rc = count_exceed(R.c, R.jp, *C.b, C.s0, C.s1, R.st, (C.ie_ok && *end == ChunkEnd::kScored) ? &C.ie : nullptr,
+                              C.ie_planes, C.ie_segs))
+      return rc;
+  if (R.mode == kCount) return GCRE_OK;
   if (int rc = collect_winners(R, C)) return rc;
   if (R.mode != kInspect) R.prof->paths += C.s1 - C.s0;   // (a launch books them on the profile of the join it is for)
   return GCRE_OK;
@@ -2768,6 +2893,7 @@ int finish_join(JoinRun& R) {
     if (R.ie_ran && R.hinted) R.prof->ie_hinted_joins++;
     if (R.ie_ran && R.have_p0) R.prof->ie_plane_joins++;
   }
+  if (R.mode == kCount) return GCRE_OK;
   if (R.mode == kInspect) {
     // everything this inspection queued is behind this event: the join proper waits for it on the main stream
     HIP_TRY(c, hipEventRecord(c->ev_insp_done, st));
@@ -2829,6 +2955,7 @@ int run_join(gcre_ctx* c, const JoinPlan& jp, gcre_result* out, JoinMode mode) {
       }
     }
   }
+  if (jp.exceed && (mode == kFull || mode == kCount)) jp.exceed->perms += R.g.K;   // (every chunk above was counted once)
   return finish_join(R);
 }
 
@@ -2949,6 +3076,7 @@ void gcre_destroy(gcre_ctx* c) {
   // with the context (their handles are invalid from here on, include/gcre_hip.h)
   while (!c->live_uids.empty()) free_uids(c->live_uids.back());
   while (!c->live_tallies.empty()) gcre_gene_tally_free(c->live_tallies.back());
+  while (!c->live_exceeds.empty()) gcre_exceed_free(c->live_exceeds.back());
   {
     std::vector<const gcre_pathset*> sets;
     for (const auto& kv : c->live_sets) sets.push_back(kv.second);
@@ -3645,6 +3773,8 @@ int gcre_join(gcre_ctx* c, int path_length, const int32_t* uid_count, const int6
   jp.take(opts);
   jp.tally = c->armed_tally;
   c->armed_tally = nullptr;
+  jp.exceed = c->armed_exceed;
+  c->armed_exceed = nullptr;
   int rc = run_join(c, jp, out);
   free_uids(u);
   if (rc != GCRE_OK) gcre_result_free(out);
@@ -3706,6 +3836,8 @@ int gcre_join_uids(gcre_ctx* c, const gcre_uids* uids, const gcre_pathset* paths
   jp.take(opts);
   jp.tally = c->armed_tally;
   c->armed_tally = nullptr;
+  jp.exceed = c->armed_exceed;
+  c->armed_exceed = nullptr;
   int rc = run_join(c, jp, out);
   if (rc != GCRE_OK) gcre_result_free(out);
   return rc;
@@ -3845,6 +3977,126 @@ void gcre_gene_tally_free(gcre_gene_tally* t) {
   delete t;
 }
 
+// ---- null exceedance counts ----
+gcre_exceed* gcre_exceed_create(gcre_ctx* c, const double* thresholds, int32_t m) {
+  if (!c) return nullptr;
+  auto bad = [&](const std::string& msg) -> gcre_exceed* {
+    fail(c, GCRE_ERR_ARG, "exceedance counts: " + msg);
+    return nullptr;
+  };
+  if (!thresholds) return bad("NULL thresholds");
+  if (m < 1 || m > kExceedMax) return bad("the number of thresholds must be 1.." + std::to_string(kExceedMax) + ", not " + std::to_string(m));
+  for (int32_t i = 0; i < m; i++)
+    if (thresholds[i] != thresholds[i]) return bad("threshold " + std::to_string(i) + " is NaN");
+  (void)hipSetDevice(c->device);
+  gcre_exceed* x = new gcre_exceed();
+  x->ctx = c;
+  x->m = m;
+  x->order.resize((size_t)m);
+  for (int32_t i = 0; i < m; i++) x->order[(size_t)i] = i;
+  std::stable_sort(x->order.begin(), x->order.end(), [&](int32_t a, int32_t b) { return thresholds[a] < thresholds[b]; });
+  // both images are monotone in the threshold: one order serves both.  Observed scores are compared as score keys
+  // (gcre_kernels.hip: score_key); a zero threshold takes the key of -0.0, so that a score of either zero reaches it, and
+  // -inf the smallest key a score can have
+  std::vector<uint32_t> pat((size_t)m);
+  std::vector<uint64_t> tkey((size_t)m);
+  for (int32_t j = 0; j < m; j++) {
+    double t = thresholds[x->order[(size_t)j]];
+    pat[(size_t)j] = f32_threshold(t);
+    if (t == 0) t = -0.0;
+    uint64_t b;
+    std::memcpy(&b, &t, 8);
+    const uint64_t k = (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+    tkey[(size_t)j] = t > -std::numeric_limits<double>::infinity() ? k : 1;
+  }
+  c->live_exceeds.push_back(x);
+  hipError_t e = hipMalloc((void**)&x->d_pat, (size_t)m * 4);
+  if (e == hipSuccess) e = hipMalloc((void**)&x->d_tkey, (size_t)m * 8);
+  if (e == hipSuccess) e = hipMalloc((void**)&x->d_hist, (size_t)m * 8);
+  if (e == hipSuccess) e = hipMalloc((void**)&x->d_ohist, (size_t)m * 8);
+  if (e == hipSuccess) e = hipMemcpyAsync(x->d_pat, pat.data(), (size_t)m * 4, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(x->d_tkey, tkey.data(), (size_t)m * 8, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(x->d_hist, 0, (size_t)m * 8, c->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(x->d_ohist, 0, (size_t)m * 8, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);   // (the vectors are locals)
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    gcre_exceed_free(x);
+    fail(c, GCRE_ERR_DEVICE, std::string("exceedance counts: ") + hipGetErrorString(e));
+    return nullptr;
+  }
+  return x;
+}
+
+int gcre_join_set_exceed(gcre_ctx* c, gcre_exceed* x) {
+  if (!c) return GCRE_ERR_ARG;
+  if (x && x->ctx != c) return fail(c, GCRE_ERR_ARG, "exceedance counts do not belong to this context");
+  c->armed_exceed = x;
+  return GCRE_OK;
+}
+
+int gcre_process_paths_set_exceed(gcre_ctx* c, int level, gcre_exceed* x) {
+  if (!c) return GCRE_ERR_ARG;
+  if (level < 0 || level > 5) return fail(c, GCRE_ERR_ARG, "exceedance counts: level index must be 0..5");
+  if (x && x->ctx != c) return fail(c, GCRE_ERR_ARG, "exceedance counts do not belong to this context");
+  c->pp_exceed[level] = x;
+  return GCRE_OK;
+}
+
+// the counts may have been queued on either stream of the context
+static int exceed_wait(gcre_ctx* c) {
+  (void)hipSetDevice(c->device);
+  if (c->stream) HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (c->insp_stream) HIP_TRY(c, hipStreamSynchronize(c->insp_stream));
+  return GCRE_OK;
+}
+
+int gcre_exceed_read(gcre_exceed* x, uint64_t* exceed, uint64_t* observed, int64_t* perms_counted, int64_t* paths_counted) {
+  if (!x || !x->ctx) return GCRE_ERR_ARG;
+  gcre_ctx* c = x->ctx;
+  if (int rc = exceed_wait(c)) return rc;
+  const size_t m = (size_t)x->m;
+  std::vector<unsigned long long> h(m);
+  for (int which = 0; which < 2; which++) {
+    uint64_t* out = which ? observed : exceed;
+    if (!out) continue;
+    HIP_TRY(c, hipMemcpy(h.data(), which ? x->d_ohist : x->d_hist, m * 8, hipMemcpyDeviceToHost));
+    uint64_t run = 0;
+    for (size_t j = m; j-- > 0;) {   // a value in bin j reaches thresholds 0..j of the ascending order
+      run += h[j];
+      out[(size_t)x->order[j]] = run;
+    }
+  }
+  if (perms_counted) *perms_counted = x->perms;
+  if (paths_counted) *paths_counted = x->paths;
+  return GCRE_OK;
+}
+
+int gcre_exceed_reset(gcre_exceed* x) {
+  if (!x || !x->ctx) return GCRE_ERR_ARG;
+  gcre_ctx* c = x->ctx;
+  if (int rc = exceed_wait(c)) return rc;
+  HIP_TRY(c, hipMemset(x->d_hist, 0, (size_t)x->m * 8));
+  HIP_TRY(c, hipMemset(x->d_ohist, 0, (size_t)x->m * 8));
+  x->perms = x->paths = 0;
+  return GCRE_OK;
+}
+
+void gcre_exceed_free(gcre_exceed* x) {
+  if (!x) return;
+  if (gcre_ctx* c = x->ctx) {
+    (void)exceed_wait(c);
+    if (c->armed_exceed == x) c->armed_exceed = nullptr;
+    for (auto& p : c->pp_exceed)
+      if (p == x) p = nullptr;
+    auto& v = c->live_exceeds;
+    v.erase(std::remove(v.begin(), v.end(), x), v.end());
+  }
+  for (void* p : {(void*)x->d_pat, (void*)x->d_tkey, (void*)x->d_hist, (void*)x->d_ohist})
+    if (p) (void)hipFree(p);
+  delete x;
+}
+
 void gcre_result_free(gcre_result* r) {
   if (!r) return;
   std::free(r->scores);
@@ -3896,6 +4148,15 @@ int gcre_process_paths(gcre_ctx* c, const gcre_pp_input* in, gcre_result out[5])
   }
   if (any_tally && in->shard_world > 1)
     return fail(c, GCRE_ERR_ARG, "a gene tally cannot be armed for one device of several: merging tallies across devices is not supported");
+  gcre_exceed* exceeds[6];
+  bool any_exceed = false;
+  for (int i = 0; i < 6; i++) {
+    exceeds[i] = c->pp_exceed[i];
+    c->pp_exceed[i] = nullptr;
+    any_exceed = any_exceed || exceeds[i] != nullptr;
+  }
+  if (any_exceed && in->shard_world > 1)
+    return fail(c, GCRE_ERR_ARG, "exceedance counts cannot be armed for one device of several: add the counts of whole runs on the host");
   gcre_profile total{};
   auto add_prof = [&]() {
     total.null_kernel_ms += c->prof.null_kernel_ms;
@@ -3961,6 +4222,8 @@ int gcre_process_paths(gcre_ctx* c, const gcre_pp_input* in, gcre_result out[5])
     }
     JoinPlan jp{u, p0, p1, res, false, 0, 0, nullptr};
     jp.tally = tallies[lvi];   // (every permutation window folds the same observed scores: harmless)
+    jp.exceed = exceeds[lvi];
+    jp.exceed_observed = c->win_k0 == 0;   // the observed scores once per call, the null values of every window
     if (in->shard_world > 1) {   // one device of several: its slice of the joined paths, every kept row
       jp.sharded = true;
       jp.shard_begin = u->total * in->shard_rank / in->shard_world;

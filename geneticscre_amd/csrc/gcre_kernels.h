@@ -396,4 +396,48 @@ struct GeneFoldArgs {
 // k_gene_fold, k_gene_index, k_gene_merge on `stream`, in that order
 hipError_t launch_gene_fold(const GeneFoldArgs& a, int cus, hipStream_t stream);
 
+// ---- null exceedance counts (gcre_exceed.hip) ----
+constexpr int kExceedMax = 10000;      // thresholds of one object (the top_k limit)
+// up to here the bins of a block are a u32 histogram in LDS: 16 KB next to the 8 KB of queues in k_exceed_ie (k_null_ie's
+// maxima take 32 KB), 8 KB next to the 16 KB mask tile and the queues in k_exceed_dense
+constexpr int kExceedLdsBinsIe = 4096;
+constexpr int kExceedLdsBinsDense = 2048;
+// The scored stretch of a chunk against the permutations of the window, in k_null's mapping: the fields of NullArgs
+// (row0 / row1 / tot start at the stretch's first path; nothing beyond [0, npaths) is read), and the thresholds.
+struct ExceedArgs {
+  const uint32_t* p0;
+  const uint32_t* p1;
+  const uint32_t* masks;
+  const uint32_t* row0;
+  const uint32_t* row1;
+  const uint32_t* tot;
+  const float* t32;
+  const double* d64;
+  const uint32_t* pat;        // [m] ascending f32 bit patterns: a null value v counts for threshold j iff bits(v) >= pat[j]
+  unsigned long long* hist;   // [m] bin j += values v with pat[j] <= bits(v) and (j == m-1 or bits(v) < pat[j+1])
+  int64_t npaths;
+  int64_t npt;
+  int S32, W32p, Kpad;
+  int K;                      // permutations of the window: columns K.. of the last tile never count
+  int nkt, pgroups;
+  int m;
+  int lds_bins;               // m (<= kExceedLdsBinsDense): per-block histogram in LDS; 0: straight into `hist`
+};
+hipError_t launch_exceed_dense(const ExceedArgs& a, int method, const NullConfig& cfg, hipStream_t stream);
+// The inclusion-exclusion form: the chunk's IeArgs as k_null_ie takes them (segments [seg_begin, seg_end), paths inside
+// [score_begin, score_end) count; planes_out, null_bits, stats, ladder, queue are not read), `planes` counter planes.
+// lds_bins: m (<= kExceedLdsBinsIe) or 0.
+hipError_t launch_exceed_ie(const IeArgs& a, int method, int planes, const uint32_t* pat, unsigned long long* hist, int m,
+                            int lds_bins, hipStream_t stream);
+int exceed_ie_max_waves_per_cu(int method, int planes, int lds_bins);
+struct ExceedObsArgs {
+  const uint64_t* key;        // [count] score keys (0 = not a score: never counts)
+  const uint64_t* tkey;       // [m] ascending threshold keys (>= 1)
+  unsigned long long* hist;   // [m] bins as ExceedArgs::hist
+  int64_t count;
+  int m;
+  int lds_bins;
+};
+hipError_t launch_exceed_observed(const ExceedObsArgs& a, int cus, hipStream_t stream);
+
 }  // namespace gcre

@@ -11,6 +11,8 @@
   * ``gene_tables`` / ``gene_best_reference`` / ``gene_results`` / ``gene_summary``  the per-gene best-path table: for
                          every gene the best path of each length through it, tallied on the device during the joins
                          (gcre_gene_tally; beyond the reference)
+  * ``exceed_reference`` / ``fdr_columns``  null exceedance counts of a join in plain numpy, and the per-family error rate,
+                         permutation FDR and q-values they give (gcre_exceed; beyond the reference)
 
 Host-side post-processing of <= top_k x 5 rows: string work, nothing here touches the scored path.
 """
@@ -479,6 +481,137 @@ def gene_summary(df):
 
 
 # ---------------------------------------------------------------------------------------------------------------
+# null exceedance counts, permutation FDR
+
+FDR_COLUMNS = ["ExpectedFalse", "FDR", "Qvalues"]
+
+
+def _vt_cell(VT, n, a, b):
+    """VT[a][b] as the device reads its copy of the value table: -1 outside the caller's table and beyond n patients."""
+    a, b = np.asarray(a, np.int64), np.asarray(b, np.int64)
+    ok = (a >= 0) & (b >= 0) & (a <= n) & (b <= n) & (a < VT.shape[0]) & (b < VT.shape[1])
+    return np.where(ok, VT[np.clip(a, 0, VT.shape[0] - 1), np.clip(b, 0, VT.shape[1] - 1)], -1.0)
+
+
+def _vt_max(VT, n, a, b):
+    """compute_value_table_max (methods.h:110-118): max(VT[a][b], VT[b][a]) with std::max semantics."""
+    x, y = _vt_cell(VT, n, a, b), _vt_cell(VT, n, b, a)
+    return np.where(x < y, y, x)
+
+
+def _fold_f32(x):
+    """The f32 value a join's null kernels fold into their maxima: rounded to f32, NaN and negatives as +0."""
+    f = np.asarray(x, np.float64).astype(np.float32)
+    return np.where(f > 0, f, np.float32(0)).astype(np.float32)
+
+
+def _unpack_rows(rows, halves: int, n: int) -> np.ndarray:
+    """Packed path rows uint64 [rows][halves * W] (W >= ceil(n / 64) words per half) -> bool [halves][rows][n]."""
+    r = np.ascontiguousarray(rows, dtype="<u8")
+    r = r.reshape(len(r), halves, -1)
+    bits = np.unpackbits(r.view(np.uint8).reshape(len(r), halves, -1), axis=2, bitorder="little")[:, :, :n]
+    return np.ascontiguousarray(np.moveaxis(bits, 1, 0)).astype(bool)
+
+
+def exceed_reference(method, n_cases: int, n_ctrls: int, uids, rows0, rows1, value_table, masks, thresholds,
+                     shard: Optional[Tuple[int, int]] = None, window: Optional[Tuple[int, int]] = None
+                     ) -> Dict[str, object]:
+    """The definition of a join's exceedance counts in plain numpy -- what gcre_exceed must return, bit for bit.
+
+    ``uids``: the join index (count / location / signs / path_length); ``rows0`` / ``rows1``: the packed rows of paths0 and
+    paths1 (uint64 [rows][method * W]: the (+) half, then for the signed method the (-) half); ``masks``: the permutations'
+    case masks, packed uint64 [K][W] or bool [K][n]; ``thresholds``: any order.  Joined path p = (uid row i, paths1 row
+    location[i] + j) is paths0[i] | paths1[..], the added row's halves swapped when the signed method's relation is not
+    positive (UidRelSet::need_flip).  Per permutation r its null value is the f32 the null kernels fold into their maxima
+    -- method 1: VT[c][tot - c] for c carriers among the mask's cases; method 2: vtmax[a][P - a] + vtmax[N - b][b] added in
+    f64 --, rounded to f32, NaN and negatives as 0.  exceed[j] counts the (p, r) with (double)null >= thresholds[j] over the
+    scored paths (``shard``) and the permutations of ``window``; observed[j] the scored paths whose observed score (above
+    -inf) is >= thresholds[j].  Returns {"exceed", "observed" (uint64), "perms", "paths", "scores" (f64 per scored path)}."""
+    M = 1 if method in (1, "method1") else 2
+    n = int(n_cases) + int(n_ctrls)
+    VT = np.asarray(value_table, np.float64)
+    thr = np.asarray(thresholds, np.float64).ravel()
+    if np.isnan(thr).any():
+        raise ValueError("a threshold is NaN")
+    mk = np.asarray(masks)
+    if mk.dtype != bool:
+        mk = _unpack_rows(mk, 1, n)[0] if mk.size else np.zeros((0, n), bool)
+    mk = mk.reshape(-1, n)
+    if window is not None:
+        mk = mk[window[0]:window[1]]
+    K = len(mk)
+    mf = mk.astype(np.float32)
+    count = np.maximum(np.asarray(uids.count, dtype=np.int64), 0)
+    P = int(count.sum())
+    src = np.repeat(np.arange(len(count), dtype=np.int64), count)
+    first = np.cumsum(count) - count
+    trg = np.repeat(np.asarray(uids.location, dtype=np.int64), count) + (np.arange(P, dtype=np.int64) - np.repeat(first, count))
+    b0, b1 = (0, P) if shard is None else (max(0, min(int(shard[0]), P)), max(0, min(int(shard[1]), P)))
+    b1 = max(b0, b1)
+    src, trg = src[b0:b1], trg[b0:b1]
+    r0, r1 = _unpack_rows(rows0, M, n), _unpack_rows(rows1, M, n)
+    keep = np.ones(len(src), bool)
+    if M == 2:
+        signs, L = np.asarray(uids.signs, np.int64), int(uids.path_length)
+        sg = signs[src] if L > 3 else signs[trg] if L < 3 else np.where(signs[src] + signs[trg] == 0, -1, 1)
+        keep = sg == 1
+    case = np.arange(n) < int(n_cases)
+    order = np.argsort(thr, kind="stable")
+    ts = thr[order]
+    exceed_sorted = np.zeros(len(thr), np.uint64)
+    scores = np.zeros(len(src), np.float64)
+    step = max(1, int(4e6 // max(K, 1)), 1)
+    step = min(step, 1 << 16)
+    for lo in range(0, len(src), step):
+        s_, t_ = src[lo:lo + step], trg[lo:lo + step]
+        if M == 1:
+            bp = r0[0][s_] | r1[0][t_]
+            tot = bp.sum(axis=1)
+            scores[lo:lo + step] = _vt_cell(VT, n, (bp & case).sum(axis=1), (bp & ~case).sum(axis=1))
+            a = (bp.astype(np.float32) @ mf.T).astype(np.int64)            # exact: counts < 2^24
+            null = _fold_f32(_vt_cell(VT, n, a, tot[:, None] - a))
+        else:
+            k_ = keep[lo:lo + step, None]
+            bp = r0[0][s_] | np.where(k_, r1[0][t_], r1[1][t_])
+            bn = r0[1][s_] | np.where(k_, r1[1][t_], r1[0][t_])
+            tp, tn = bp.sum(axis=1), bn.sum(axis=1)
+            scores[lo:lo + step] = (_vt_cell(VT, n, (bp & case).sum(axis=1), (bp & ~case).sum(axis=1)) +
+                                    _vt_cell(VT, n, (bn & ~case).sum(axis=1), (bn & case).sum(axis=1)))
+            a = (bp.astype(np.float32) @ mf.T).astype(np.int64)
+            b = (bn.astype(np.float32) @ mf.T).astype(np.int64)
+            null = _fold_f32(_vt_max(VT, n, a, tp[:, None] - a) + _vt_max(VT, n, tn[:, None] - b, b))
+        v = np.sort(null.astype(np.float64).ravel())
+        exceed_sorted += (len(v) - np.searchsorted(v, ts, side="left")).astype(np.uint64)
+    sc = np.sort(scores[scores > -np.inf])                               # (NaN compares false: not a score)
+    observed_sorted = (len(sc) - np.searchsorted(sc, ts, side="left")).astype(np.uint64)
+    exceed, observed = np.zeros(len(thr), np.uint64), np.zeros(len(thr), np.uint64)
+    exceed[order], observed[order] = exceed_sorted, observed_sorted
+    return {"exceed": exceed, "observed": observed, "perms": K, "paths": len(src), "scores": scores}
+
+
+def fdr_columns(thresholds, exceed, observed, perms: int) -> Dict[str, np.ndarray]:
+    """Per threshold, in the order given: the per-family error rate PFER = exceed / B (the number of paths a permutation
+    pushes to the threshold or beyond, on average over all B permutations drawn -- no identity permutation is added), the
+    permutation FDR = min(1, PFER / observed) with pi0 = 1 (Storey-Tibshirani / SAM), and the q-value = the smallest FDR
+    among the thresholds that are not larger (the monotone step: a q-value never falls as the threshold does).  NaN where
+    nothing is observed at the threshold or B = 0; NaN entries do not take part in a q-value.  Equal thresholds get equal
+    rows.  Returns {"ExpectedFalse", "FDR", "Qvalues"}."""
+    t = np.asarray(thresholds, np.float64).ravel()
+    e, o = np.asarray(exceed, np.float64).ravel(), np.asarray(observed, np.float64).ravel()
+    B = int(perms)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        pfer = e / B if B > 0 else np.full(len(t), np.nan)
+        fdr = np.where(o > 0, np.minimum(1.0, pfer / o), np.nan)
+    # thresholds ascending (ties kept together: equal thresholds have equal counts), running minimum ignoring NaN
+    order = np.argsort(t, kind="stable")
+    run = np.minimum.accumulate(np.where(np.isnan(fdr[order]), np.inf, fdr[order]))
+    # a tie's first member has not seen its later members: equal thresholds carry equal FDRs, so nothing changes
+    q = np.empty(len(t))
+    q[order] = np.where(np.isnan(fdr[order]), np.nan, run)
+    return {"ExpectedFalse": pfer, "FDR": fdr, "Qvalues": q}
+
+
+# ---------------------------------------------------------------------------------------------------------------
 # inputs
 
 
@@ -625,7 +758,7 @@ def frames_of(prep: Prepared, levels) -> Dict[str, Dict[str, np.ndarray]]:
 def gwaspa(genes: Sequence[str], data: np.ndarray, n_cases: int, n_ctrls: int, network, signed: bool = False,
            threshold: float = 0.05, top_k: int = 10, path_length: int = 5, n_permutations: int = 100,
            strata: Optional[Sequence[int]] = None, seed: int = 0, device: int = 0,
-           decorated_pvalues: bool = False, gene_table: bool = False) -> Dict[str, object]:
+           decorated_pvalues: bool = False, gene_table: bool = False, fdr: bool = False) -> Dict[str, object]:
     """GWASPA (R/ProcessPaths.R:87-344) without R: dataset -> GWASPA.Results, scored on the MI355X.
 
     ``network`` = (ents_uid, ents_symbol, rel_src, rel_trg, rel_sign): the knowledge base getStringKB() would load
@@ -642,6 +775,13 @@ def gwaspa(genes: Sequence[str], data: np.ndarray, n_cases: int, n_ctrls: int, n
     gene, tallied on the device while the joins run (one GeneTally per level), and "gene_best" (length ->
     api.GeneBest, the raw tallies).  ``gene_summary`` reduces it to one row per gene.  Default False: the joins launch
     exactly what they launch without it.
+
+    ``fdr``: after the usual pass every level is joined once more, on the same context, with an ``api.ExceedCounts`` whose
+    thresholds are that level's finite top-K scores: GWASPA.Results gains "ExpectedFalse" (the per-family
+    error rate: paths of the row's length a permutation pushes to the row's score or beyond, on average), "FDR" and
+    "Qvalues" (``fdr_columns``: within a length, pi0 = 1), and the raw counts come back as "exceed" (length ->
+    api.Exceedances).  Sentinel rows get NaN.  The row order and the other seven columns are what ``fdr=False`` returns.
+    Default False.
     """
     from . import api
     from .synth import Problem
@@ -680,6 +820,28 @@ def gwaspa(genes: Sequence[str], data: np.ndarray, n_cases: int, n_ctrls: int, n
     out = {"GWASPA.Results": results_table(lsts, path_length, frames,
                                            (prep.ents_uid, prep.ents_symbol), (prep.ents2_uid, prep.ents2_symbol)),
            "levels": lsts, "prepared": prep}
+    if fdr:
+        counters = {}
+        for L, name in enumerate(GENE_LEVELS[:path_length], start=1):
+            s = np.asarray(lsts[f"lst{L}"].scores, np.float64)
+            if np.isfinite(s).any():
+                counters[name] = api.ExceedCounts(ex, s[np.isfinite(s)])
+        if counters:
+            api.process_paths(problem, device=device, exec_=ex, exceeds=counters)
+        df = out["GWASPA.Results"]
+        lookup, out["exceed"] = {}, {}
+        for L, name in enumerate(GENE_LEVELS[:path_length], start=1):
+            if name not in counters:
+                continue
+            got = counters[name].read()
+            out["exceed"][L] = got
+            cols = fdr_columns(counters[name].thresholds, got.exceed, got.observed, got.perms)
+            for i, t in enumerate(counters[name].thresholds.tolist()):
+                lookup[(L, t)] = tuple(cols[c][i] for c in FDR_COLUMNS)
+            counters[name].free()
+        rows = [lookup.get((int(L), float(sc)), (np.nan,) * 3) for L, sc in zip(df["Lengths"], df["Scores"])]
+        for k, c in enumerate(FDR_COLUMNS):
+            df[c] = np.array([r[k] for r in rows], np.float64)
     if gene_table:
         best = {L + 1: tallies[name].read() for L, name in enumerate(GENE_LEVELS[:path_length])}
         out["gene_best"] = best

@@ -469,6 +469,41 @@ int gcre_gene_tally_read(gcre_gene_tally* tally, double* score, int64_t* ordinal
                          int32_t* cases, int32_t* ctrls);
 void gcre_gene_tally_free(gcre_gene_tally* tally);   /* gcre_destroy frees the ones still alive */
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Null exceedance counts: for a list of thresholds, how many (joined path, permutation) pairs of a join
+ * have a null score at or above each one, and how many joined paths an observed score.  No reference counterpart: every
+ * p-value of the reference is against the per-permutation MAXIMUM over the paths (family-wise); these counts give the
+ * other standard permutation answer -- exceed / B = the expected number of paths a permutation pushes past a score (the
+ * per-family error rate), and with `observed` the permutation FDR and q-values (report.fdr_columns).
+ *
+ *   null[p][r]   the f32 value the join's null kernels fold into their maxima for joined path p and permutation r, as
+ *                stated for gcre_score_sets above (NaN and negatives fold to 0)
+ *   exceed[j]    #{(p, r) : p scored by the join, r in the permutation window, (double)null[p][r] >= thresholds[j]}
+ *   observed[j]  #{p scored by the join : observed score of p >= thresholds[j]}, scores above -inf only
+ * "scored by the join" is the shard of a sharded join, every joined path otherwise.  Both are sums: shards and permutation
+ * windows add.  Unlike the gene tally the object is NOT idempotent -- a join counted twice is counted twice --, so it
+ * records how many permutations and joined paths went into it.  The counts are bit-identical whatever the chunking, the
+ * inspection cache, the launch-ahead chain or the form of the join's own null kernel, and the join's result does not
+ * change; a join without an object launches exactly what it launched before. */
+typedef struct gcre_exceed gcre_exceed;
+
+/* thresholds: [m] doubles in any order, copied; 1 <= m <= 10,000 (the top_k limit).  +-inf are allowed.  NULL on error
+ * (GCRE_ERR_ARG with a message: m out of range, a NaN threshold). */
+gcre_exceed* gcre_exceed_create(gcre_ctx* ctx, const double* thresholds, int32_t m);
+/* The next gcre_join / gcre_join_uids call on the context counts into `x`, then the context is disarmed (whether the join
+ * succeeds or not).  NULL disarms.  A tally and an exceed object may be armed for the same join. */
+int gcre_join_set_exceed(gcre_ctx* ctx, gcre_exceed* x);
+/* The same for the next gcre_process_paths call, level 0..5 as for the tally.  The call counts the null values of every
+ * permutation window it walks (perms_counted grows by `iterations`) and the observed scores once.  One device of several
+ * (shard_world > 1) refuses an armed object with GCRE_ERR_ARG. */
+int gcre_process_paths_set_exceed(gcre_ctx* ctx, int level, gcre_exceed* x);
+/* Waits for what is in flight.  exceed / observed: [m] in the order of the thresholds given (either may be NULL).
+ * perms_counted: the sum of the window lengths of the joins counted; paths_counted: the joined paths whose observed scores
+ * were counted. */
+int gcre_exceed_read(gcre_exceed* x, uint64_t* exceed, uint64_t* observed, int64_t* perms_counted, int64_t* paths_counted);
+int gcre_exceed_reset(gcre_exceed* x);   /* all counts back to zero */
+void gcre_exceed_free(gcre_exceed* x);   /* gcre_destroy frees the ones still alive */
+
 #ifdef __cplusplus
 }
 #endif
