@@ -293,7 +293,7 @@ __global__ __launch_bounds__(kNullBlock, OCC) void k_exceed_dense(const ExceedAr
           const u32 tp = TOT[2 * (qbase + t)];
           const u32 tn = TOT[2 * (qbase + t) + 1];
           const char* dp = (const char*)(a.d64 + exc_diag(tp));
-          const char* dn = (const char*)(a.d64 + exc_diag(tn));
+          const char* dn = (const char*)(a.d64n + exc_diag(tn));
           u32 v[R];
           bool pass[R], any = false;
 #pragma unroll

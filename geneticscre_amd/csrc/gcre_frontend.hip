@@ -65,9 +65,10 @@ hipError_t launch_generate_masks(uint64_t seed, int K, int n, int n_strata, cons
 // dvt[t(t+1)/2 + i] = table[i][t-i], -1 outside the table or beyond n patients (the reference pads its (n+1)^2 copy
 // with -1, join_base.cpp:67-78); t32 = the same cell rounded to f32 with everything that can never win clamped to +0
 // (method 1, methods.h:96-103); dmax = max(table[i][t-i], table[t-i][i]) with std::max semantics (method 2,
-// compute_value_table_max, methods.h:110-118).  One block row per diagonal.
+// compute_value_table_max, methods.h:110-118).  std::max(a, b) = (a < b) ? b : a keeps a NaN that comes first and drops one
+// that comes second: *asym is set when that makes dmax differ from its mirror image.  One block row per diagonal.
 __global__ __launch_bounds__(256) void k_table_to_diag(const double* table, int nrow, int ncol, int col_major, int n, int TD,
-                                                       double* dvt, float* t32, double* dmax) {
+                                                       double* dvt, float* t32, double* dmax, uint32_t* asym) {
   const int t = blockIdx.y;
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= TD || i > t) return;
@@ -85,13 +86,29 @@ __global__ __launch_bounds__(256) void k_table_to_diag(const double* table, int 
   if (dmax) {
     const double b = VT(t - i, i);
     dmax[at] = (a < b) ? b : a;
+    if (asym && ((a != a) != (b != b))) *asym = 1u;
   }
 }
 
+// dmaxn[t][i] = dmax[t][t - i] = vtmax[t - i][i]: what the (-) half of a path reads at index i of diagonal t
+__global__ __launch_bounds__(256) void k_mirror_diag(const double* dmax, int TD, double* dmaxn) {
+  const int t = blockIdx.y;
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= TD || i > t) return;
+  const size_t base = ((size_t)t * ((size_t)t + 1)) / 2;
+  dmaxn[base + (size_t)i] = dmax[base + (size_t)(t - i)];
+}
+
 hipError_t launch_table_to_diag(const double* table, int nrow, int ncol, int col_major, int n, int TD, double* dvt,
-                                float* t32, double* dmax, hipStream_t stream) {
+                                float* t32, double* dmax, uint32_t* asym, hipStream_t stream) {
   const dim3 grid((unsigned)((TD + 255) / 256), (unsigned)TD);
-  hipLaunchKernelGGL(k_table_to_diag, grid, dim3(256), 0, stream, table, nrow, ncol, col_major, n, TD, dvt, t32, dmax);
+  hipLaunchKernelGGL(k_table_to_diag, grid, dim3(256), 0, stream, table, nrow, ncol, col_major, n, TD, dvt, t32, dmax, asym);
+  return hipGetLastError();
+}
+
+hipError_t launch_mirror_diag(const double* dmax, int TD, double* dmaxn, hipStream_t stream) {
+  const dim3 grid((unsigned)((TD + 255) / 256), (unsigned)TD);
+  hipLaunchKernelGGL(k_mirror_diag, grid, dim3(256), 0, stream, dmax, TD, dmaxn);
   return hipGetLastError();
 }
 

@@ -6,6 +6,8 @@
 //   * k_gene_merge  per slot: the chunk's entry into the join's table under "(key greater) or (key equal and ordinal
 //                   smaller)", and the chunk-local tables back to empty
 // Keys are compared, never doubles: score_key (gcre_kernels.hip) is monotone in the score, 0 = not a score (-inf, NaN).
+// The one pair of equal scores under two keys, -0.0 and +0.0, is compared as the key of +0.0 (tie_key); the tables' entry
+// of a slot is the winning path's OWN key, so the score read back has its sign.
 // The merge rule is a total order on (key, ordinal), so the table does not depend on how the join was cut into chunks,
 // on the order they arrive in, or on a chunk being folded twice.
 //
@@ -32,6 +34,8 @@ constexpr u32 kNoIndex = 0xffffffffu;
 // the CU passing the test
 __device__ __forceinline__ u64 peek(const u64* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ u32 peek(const u32* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+__device__ __forceinline__ u64 tie_key(u64 k) { return k == kKeyMinusZero ? kKeyPlusZero : k; }
 
 __device__ __forceinline__ u64 wave_max(u64 v) {
 #pragma unroll
@@ -66,7 +70,7 @@ __global__ __launch_bounds__(kGeneBlock) void k_gene_fold(const GeneFoldArgs a) 
   for (i64 base = (i64)blockIdx.x * kGeneBlock + (threadIdx.x & ~63); base < a.count; base += stride) {
     const i64 i = base + lane;
     bool valid = i < a.count;
-    const u64 key = valid ? a.key[i] : 0;
+    const u64 key = valid ? tie_key(a.key[i]) : 0;     // (the chunk-local table holds tie keys)
     valid = valid && key != 0;
     const i64 r0 = valid ? (i64)a.row0[i] : 0;
     const i64 r1 = valid ? (i64)(a.row1[i] & 0x7fffffffu) : 0;   // (bit 31: the signed method's half swap)
@@ -85,7 +89,7 @@ __global__ __launch_bounds__(kGeneBlock) void k_gene_fold(const GeneFoldArgs a) 
       const int g = slot[s] < 0 ? 0 : slot[s];
       u64 v = a.ck[g];
       if (PRIOR) {
-        const u64 b = a.bkey[g];
+        const u64 b = tie_key(a.bkey[g]);
         v = (b > v && b > key) ? ~0ull : v;   // (an equal key may still win on the ordinal)
       }
       seen[s] = v;
@@ -110,7 +114,7 @@ __device__ __forceinline__ void index_slot(const GeneFoldArgs& a, int slot, u64 
 __global__ __launch_bounds__(kGeneBlock) void k_gene_index(const GeneFoldArgs a) {
   const i64 stride = (i64)gridDim.x * kGeneBlock;
   for (i64 i = (i64)blockIdx.x * kGeneBlock + threadIdx.x; i < a.count; i += stride) {
-    const u64 key = a.key[i];
+    const u64 key = tie_key(a.key[i]);
     if (key == 0) continue;
     const i64 r0 = (i64)a.row0[i];
     const i64 r1 = (i64)(a.row1[i] & 0x7fffffffu);
@@ -132,9 +136,9 @@ __global__ __launch_bounds__(kGeneBlock) void k_gene_merge(const GeneFoldArgs a)
   a.ck[g] = 0;
   a.cidx[g] = kNoIndex;
   const i64 ord = a.first + (i64)i;
-  const u64 bk = a.bkey[g];
+  const u64 bk = tie_key(a.bkey[g]);
   if (k > bk || (k == bk && ord < a.bord[g])) {
-    a.bkey[g] = k;
+    a.bkey[g] = a.key[i];
     a.bord[g] = ord;
     a.bsrc[g] = (int32_t)a.row0[i];
     a.btrg[g] = (int32_t)(a.row1[i] & 0x7fffffffu);

@@ -343,8 +343,10 @@ struct gcre_ctx {
   float* d_t32 = nullptr;            // method 1 null table
   double* d_dvt = nullptr;           // observed-score table
   double* d_dmax = nullptr;          // method 2 null table (vtmax)
+  double* d_dmaxn = nullptr;         // its mirror image, only where vtmax is not symmetric (a NaN on one side of the diagonal)
   uint32_t* d_null = nullptr;        // [Kpad]
   uint32_t* d_mt = nullptr;          // transposed masks for the sparse kernel [nkt][64*Wp + 1][64]
+  bool mt_stale = false;             // d_masks changed while the sparse kernel was off: d_mt (if any) holds older masks
   int ieq_batch = 0;                 // GCRE_IEQ_BATCH: quads per ticket of the quad kernel (0: twice ie_batch)
   int ie_quad = 1;                   // GCRE_IE_QUAD=0: the pruned method-1 launches stay on k_null_ie_m1 (cross-check)
   int ie_warm_items = 4;             // (segment, tile) items per wave of the warm-up launch (GCRE_IE_WARM_ITEMS)
@@ -636,12 +638,14 @@ gcre_pathset* new_pathset(gcre_ctx* c, int64_t nrows, bool zero) {
 }
 
 // The sparse kernel needs counts that fit 16 bits (64*Wp < 65535 patients); GCRE_NULL_KERNEL=dense turns it off.
+// (a table whose vtmax is not symmetric is scored by the dense kernel: the (-) half reads the mirror image there, the
+// count-plane and delta-streaming kernels and their ladders index both halves of one table)
 bool sparse_enabled(const gcre_ctx* c) {
-  return c->null_kernel != 1 && c->g.K > 0 && 64 * c->g.Wp < 65535;
+  return c->null_kernel != 1 && c->g.K > 0 && 64 * c->g.Wp < 65535 && !c->d_dmaxn;
 }
 
-int build_transposed_masks(gcre_ctx* c) {
-  if (!sparse_enabled(c)) return GCRE_OK;
+// d_mt from d_masks as they are now
+int transpose_masks(gcre_ctx* c) {
   const Geometry& g = c->g;
   const int nkt = (g.K + kSparseTile - 1) / kSparseTile;
   const uint32_t mt_rows = (uint32_t)(64 * g.Wp + 1);
@@ -650,9 +654,20 @@ int build_transposed_masks(gcre_ctx* c) {
   HIP_TRY(c, hipMemsetAsync(c->d_mt, 0, bytes, c->stream));
   HIP_TRY(c, launch_build_mt(c->d_masks, 2 * g.Wp, g.Kpad, nkt, mt_rows, c->d_mt, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
+  c->mt_stale = false;
+  return GCRE_OK;
+}
+
+// The permutation masks have changed.  Whatever was derived from the old ones is void whether or not the count-plane
+// kernels are on at this moment: a later value table can turn them on again (sparse_enabled), and must then find neither
+// the old transposed copy nor count planes or a launch-ahead record of the old epoch.
+int build_transposed_masks(gcre_ctx* c) {
   c->mask_epoch++;   // every count plane built so far belongs to the old masks
+  c->mt_stale = true;
+  if (!sparse_enabled(c)) return GCRE_OK;   // (gcre_set_value_table makes the copy if a table brings the kernels back)
+  if (int rc = transpose_masks(c)) return rc;
   c->win_k0 = 0;
-  c->win_K = g.K;
+  c->win_K = c->g.K;
   c->win_K_nominal = 0;
   return GCRE_OK;
 }
@@ -1111,20 +1126,11 @@ int select_finish(gcre_ctx* c, const uint64_t* key, int64_t count, int k, const 
   const uint64_t T = prefix;   // the need-th largest key overall
   HIP_TRY(c, hipMemsetAsync(d_counter, 0, sizeof(uint32_t), sst));
   uint32_t nsel = 0;
-  if (T == 0) {
-    // fewer scorable paths than k: everything with a real score is selected
-    HIP_TRY(c, launch_collect_gt(key, count, 0, c->d_sel.p, d_counter, (uint32_t)k, sst));
-    nsel = (uint32_t)greater;
-  } else if ((int64_t)eq_count == need) {
-    // every path that ties with the threshold is wanted: no cut needed
-    HIP_TRY(c, launch_collect_gt(key, count, T - 1, c->d_sel.p, d_counter, (uint32_t)k, sst));
-    nsel = (uint32_t)(greater + need);
-  } else {
-    // ties at the threshold exceed the remaining slots: keep the `need` smallest ordinals
-    HIP_TRY(c, launch_collect_gt(key, count, T, c->d_sel.p, d_counter, (uint32_t)k, sst));
+  // keys `thr` / `alt` tie: the `m` smallest ordinals among them go behind the `at` paths already collected
+  auto cut_ties = [&](uint64_t thr, uint64_t alt, uint32_t m, int64_t at) -> int {
     const int64_t chunks = (count + 1023) / 1024;
     HIP_TRY(c, c->d_chunk.reserve((size_t)chunks));
-    HIP_TRY(c, launch_eq_count(key, count, T, c->d_chunk.p, sst));
+    HIP_TRY(c, launch_eq_count(key, count, thr, alt, c->d_chunk.p, sst));
     std::vector<uint32_t> cnt((size_t)chunks);
     HIP_TRY(c, hipMemcpyAsync(cnt.data(), c->d_chunk.p, cnt.size() * 4, hipMemcpyDeviceToHost, sst));
     HIP_TRY(c, hipStreamSynchronize(sst));
@@ -1135,8 +1141,32 @@ int select_finish(gcre_ctx* c, const uint64_t* key, int64_t count, int k, const 
       run += t;
     }
     HIP_TRY(c, hipMemcpyAsync(c->d_chunk.p, cnt.data(), cnt.size() * 4, hipMemcpyHostToDevice, sst));
-    HIP_TRY(c, launch_eq_collect(key, count, T, c->d_chunk.p, (uint32_t)need, c->d_sel.p + greater, sst));
+    HIP_TRY(c, launch_eq_collect(key, count, thr, alt, c->d_chunk.p, m, c->d_sel.p + at, sst));
     HIP_TRY(c, hipStreamSynchronize(sst));   // cnt must outlive the copy
+    return GCRE_OK;
+  };
+  if (T == 0) {
+    // fewer scorable paths than k: everything with a real score is selected
+    HIP_TRY(c, launch_collect_gt(key, count, 0, c->d_sel.p, d_counter, (uint32_t)k, sst));
+    nsel = (uint32_t)greater;
+  } else if (T == kKeyPlusZero || T == kKeyMinusZero) {
+    // the cut falls on a zero.  -0.0 and +0.0 are equal scores under two keys: every path above +0 is in, and the zeros of
+    // either sign share what is left by ordinal (how many that is follows from the number of paths above +0, which the
+    // digit passes only know when the threshold is +0 itself)
+    HIP_TRY(c, launch_collect_gt(key, count, kKeyPlusZero, c->d_sel.p, d_counter, (uint32_t)k, sst));
+    uint32_t above = 0;
+    HIP_TRY(c, hipMemcpyAsync(&above, d_counter, sizeof above, hipMemcpyDeviceToHost, sst));
+    HIP_TRY(c, hipStreamSynchronize(sst));
+    nsel = (uint32_t)(greater + need);
+    if (int rc = cut_ties(kKeyPlusZero, kKeyMinusZero, nsel - above, (int64_t)above)) return rc;
+  } else if ((int64_t)eq_count == need) {
+    // every path that ties with the threshold is wanted: no cut needed
+    HIP_TRY(c, launch_collect_gt(key, count, T - 1, c->d_sel.p, d_counter, (uint32_t)k, sst));
+    nsel = (uint32_t)(greater + need);
+  } else {
+    // ties at the threshold exceed the remaining slots: keep the `need` smallest ordinals
+    HIP_TRY(c, launch_collect_gt(key, count, T, c->d_sel.p, d_counter, (uint32_t)k, sst));
+    if (int rc = cut_ties(T, T, (uint32_t)need, greater)) return rc;
     nsel = (uint32_t)(greater + need);
   }
   *n_selected = nsel;
@@ -1539,6 +1569,7 @@ int count_exceed(gcre_ctx* c, const JoinPlan& jp, const ChunkBufs& b, int64_t s0
   a.tot = b.tot.p + (size_t)s0 * g.method;
   a.t32 = c->d_t32;
   a.d64 = c->d_dmax;
+  a.d64n = c->d_dmaxn ? c->d_dmaxn : c->d_dmax;
   a.pat = x->d_pat;
   a.hist = x->d_hist;
   a.npaths = s1 - s0;
@@ -2751,6 +2782,7 @@ int score_chunk_dense(JoinRun& R, ChunkRun& C) {
   na.tot = b.tot.p;
   na.t32 = c->d_t32;
   na.d64 = c->d_dmax;
+  na.d64n = c->d_dmaxn ? c->d_dmaxn : c->d_dmax;
   na.null_bits = R.w_null;
   na.npaths = C.n;
   na.npt = C.npt;
@@ -3082,7 +3114,7 @@ void gcre_destroy(gcre_ctx* c) {
     for (const auto& kv : c->live_sets) sets.push_back(kv.second);
     for (const gcre_pathset* ps : sets) gcre_pathset_free(const_cast<gcre_pathset*>(ps));
   }
-  for (void* p : {(void*)c->d_case_mask, (void*)c->d_masks, (void*)c->d_t32, (void*)c->d_dvt, (void*)c->d_dmax,
+  for (void* p : {(void*)c->d_case_mask, (void*)c->d_masks, (void*)c->d_t32, (void*)c->d_dvt, (void*)c->d_dmax, (void*)c->d_dmaxn,
                   (void*)c->d_null, (void*)c->d_mt, (void*)c->d_max_tot, (void*)c->d_max_tot_b, (void*)c->d_queue, (void*)c->d_ladder})
     if (p) (void)hipFree(p);
   c->scratch.release();
@@ -3130,18 +3162,24 @@ int gcre_set_value_table(gcre_ctx* c, const double* table, int nrow, int ncol, i
   // (and covers carrier counts up to the padded word width with -1).  The repacking runs on the device: the raw table
   // goes up as it is (k_table_to_diag, gcre_frontend.hip) -- on the host it is 10 s of cache misses at 50,000 patients.
   const size_t TD = (size_t)g.TD, NT = tri(TD);
-  for (void** p : {(void**)&c->d_dvt, (void**)&c->d_t32, (void**)&c->d_dmax})
+  const bool was_asym = c->d_dmaxn != nullptr;
+  for (void** p : {(void**)&c->d_dvt, (void**)&c->d_t32, (void**)&c->d_dmax, (void**)&c->d_dmaxn})
     if (*p) { (void)hipFree(*p); *p = nullptr; }
   double* d_raw = nullptr;
+  uint32_t* d_asym = nullptr;
   const size_t raw = (size_t)nrow * (size_t)ncol;
   HIP_TRY(c, hipMalloc((void**)&c->d_dvt, NT * 8));
   if (g.method == 1) HIP_TRY(c, hipMalloc((void**)&c->d_t32, NT * 4));
   else HIP_TRY(c, hipMalloc((void**)&c->d_dmax, NT * 8));
   HIP_TRY(c, hipMalloc((void**)&d_raw, std::max<size_t>(raw, 1) * 8));
   hipError_t e = hipSuccess;
-  if (raw) e = hipMemcpyAsync(d_raw, table, raw * 8, hipMemcpyHostToDevice, c->stream);
+  if (g.method == 2) {
+    e = hipMalloc((void**)&d_asym, sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMemsetAsync(d_asym, 0, sizeof(uint32_t), c->stream);
+  }
+  if (e == hipSuccess && raw) e = hipMemcpyAsync(d_raw, table, raw * 8, hipMemcpyHostToDevice, c->stream);
   if (e == hipSuccess)
-    e = launch_table_to_diag(d_raw, nrow, ncol, col_major, n, (int)TD, c->d_dvt, c->d_t32, c->d_dmax, c->stream);
+    e = launch_table_to_diag(d_raw, nrow, ncol, col_major, n, (int)TD, c->d_dvt, c->d_t32, c->d_dmax, d_asym, c->stream);
   if (e == hipSuccess && TD <= 65536) {   // counts fit the 16-bit bounds of a ladder entry
     if (!c->d_ladder) e = hipMalloc((void**)&c->d_ladder, (size_t)(kLadder2Levels + 2) * TD * 4);
     if (e == hipSuccess)
@@ -3150,6 +3188,18 @@ int gcre_set_value_table(gcre_ctx* c, const double* table, int nrow, int ncol, i
   }
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
   (void)hipFree(d_raw);
+  if (e == hipSuccess && g.method == 2) {
+    // vtmax[r][c] != vtmax[c][r] somewhere (std::max and a NaN on one side of the diagonal): the (-) half of a path, which
+    // reads vtmax[tn - b][b] at index b of its diagonal, gets the mirror image of the table
+    uint32_t asym = 0;
+    e = hipMemcpy(&asym, d_asym, sizeof asym, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && asym) {
+      e = hipMalloc((void**)&c->d_dmaxn, NT * 8);
+      if (e == hipSuccess) e = launch_mirror_diag(c->d_dmax, (int)TD, c->d_dmaxn, c->stream);
+      if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    }
+  }
+  if (d_asym) (void)hipFree(d_asym);
   c->g00_rows = 0xffffffffu;
   if (e == hipSuccess && g.method == 2) {
     // what an empty half adds to a path's null score: vtmax[0][0], as the device table holds it, rounded UP to ladder rows
@@ -3163,6 +3213,13 @@ int gcre_set_value_table(gcre_ctx* c, const double* table, int nrow, int ncol, i
   if (e != hipSuccess) return fail(c, GCRE_ERR_DEVICE, std::string("set_value_table: ") + hipGetErrorString(e));
   c->have_table = true;
   c->obs_epoch++;
+  if (c->d_dmaxn && !was_asym && !c->quiet)
+    std::fprintf(stderr, "[table] vtmax is not symmetric (a NaN on one side of the diagonal only): permutations are scored by "
+                         "the dense kernel, without pruning\n");
+  // the masks changed while such a table kept the count-plane kernels off: their transposed copy is due now (the epoch
+  // was bumped when they changed, the window is the caller's and stays)
+  if (c->have_perms && c->mt_stale && sparse_enabled(c))
+    if (int rc = transpose_masks(c)) return rc;
   return GCRE_OK;
 }
 
@@ -3538,6 +3595,7 @@ int gcre_score_sets(gcre_ctx* c, const gcre_set_input* in, gcre_set_score* out, 
     a.thr = d_thr;
     a.t32 = c->d_t32;
     a.d64 = c->d_dmax;
+    a.d64n = c->d_dmaxn ? c->d_dmaxn : c->d_dmax;
     a.n_ge = d_ge;
     a.fam_bits = d_fam;
     a.nsets = V;

@@ -38,6 +38,7 @@ struct NullArgs {
   const uint32_t* tot;      // M entries per path: carriers (M=1) or carriers in (+),(-) halves (M=2)
   const float* t32;         // M=1: sanitised f32 null table, diagonal-major
   const double* d64;        // M=2: f64 vtmax, diagonal-major
+  const double* d64n;       // M=2: the table the (-) half reads (d64, or its mirror image: launch_table_to_diag)
   uint32_t* null_bits;      // [Kpad] running maxima as u32 bit patterns of non-negative floats
   int64_t npaths;           // joined paths in this launch
   int64_t npt;              // path tiles
@@ -294,11 +295,18 @@ hipError_t launch_radix_select(const uint64_t* key, int64_t count, int64_t need,
 // appends every i with key[i] > thr (any order) to out[], counter in *n_out
 hipError_t launch_collect_gt(const uint64_t* key, int64_t count, uint64_t thr, uint32_t* out, uint32_t* n_out,
                              uint32_t cap, hipStream_t stream);
-// per 1024-entry chunk: number of key[i] == thr
-hipError_t launch_eq_count(const uint64_t* key, int64_t count, uint64_t thr, uint32_t* chunk_cnt, hipStream_t stream);
-// first `m` (in index order) entries with key[i] == thr, written at out[rank]; chunk_base = exclusive scan of chunk_cnt
-hipError_t launch_eq_collect(const uint64_t* key, int64_t count, uint64_t thr, const uint32_t* chunk_base, uint32_t m,
-                             uint32_t* out, hipStream_t stream);
+// The keys of the two zeros.  score_key is the order-preserving image of a double's BITS, so -0.0 lands one key below +0.0,
+// while as scores they are equal (the reference compares doubles, methods.h:91): wherever keys decide a tie, the two are
+// one class.  A path keeps its own key, so the score it reports has its own sign.
+constexpr uint64_t kKeyPlusZero = 0x8000000000000000ull;
+constexpr uint64_t kKeyMinusZero = 0x7fffffffffffffffull;
+// per 1024-entry chunk: number of key[i] == thr or == alt (alt = thr: one key; the two zero keys: the zeros' tie class)
+hipError_t launch_eq_count(const uint64_t* key, int64_t count, uint64_t thr, uint64_t alt, uint32_t* chunk_cnt,
+                           hipStream_t stream);
+// first `m` (in index order) entries with key[i] == thr or == alt, written at out[rank]; chunk_base = exclusive scan of
+// chunk_cnt
+hipError_t launch_eq_collect(const uint64_t* key, int64_t count, uint64_t thr, uint64_t alt, const uint32_t* chunk_base,
+                             uint32_t m, uint32_t* out, hipStream_t stream);
 hipError_t launch_gather_winners(const uint32_t* sel, uint32_t nsel, const uint64_t* key, const uint32_t* cases,
                                  const uint32_t* ctrls, const uint32_t* row0, const uint32_t* row1, uint64_t* o_key,
                                  uint32_t* o_cases, uint32_t* o_ctrls, uint32_t* o_row0, uint32_t* o_row1,
@@ -306,8 +314,13 @@ hipError_t launch_gather_winners(const uint32_t* sel, uint32_t nsel, const uint6
 hipError_t launch_generate_masks(uint64_t seed, int K, int n, int n_strata, const int32_t* stratum, const uint32_t* cases_in,
                                  const uint32_t* size_of, uint32_t* work, int W32p, int Kpad, uint32_t* masks,
                                  hipStream_t stream);
+// *asym (method 2; zero on entry) becomes 1 when vtmax is not symmetric: std::max(a, b) keeps a NaN in its first argument and
+// drops one in its second, so a NaN on one side of the diagonal only makes vtmax[r][c] != vtmax[c][r].  The (-) half of a
+// path reads vtmax[tn - b][b] (methods.h:227), the kernels index a diagonal by b: for such a table they read the (-) half
+// from the mirror image launch_mirror_diag writes (dmaxn[t][i] = dmax[t][t - i]).
 hipError_t launch_table_to_diag(const double* table, int nrow, int ncol, int col_major, int n, int TD, double* dvt,
-                                float* t32, double* dmax, hipStream_t stream);
+                                float* t32, double* dmax, uint32_t* asym, hipStream_t stream);
+hipError_t launch_mirror_diag(const double* dmax, int TD, double* dmaxn, hipStream_t stream);
 hipError_t launch_fill_u32(uint32_t* p, int64_t n, uint32_t v, hipStream_t stream);
 hipError_t launch_max_merge(uint32_t* dst, const uint32_t* src, int n, hipStream_t stream);
 
@@ -357,6 +370,7 @@ struct SetNullArgs {
   const uint32_t* thr;          // [nsets] f32 bit pattern: permutation r counts iff bits(null_r) >= thr
   const float* t32;             // M=1: sanitised f32 null table, diagonal-major
   const double* d64;            // M=2: f64 vtmax, diagonal-major
+  const double* d64n;           // M=2: the table the (-) half reads (d64, or its mirror image)
   unsigned long long* n_ge;     // [nsets], zero on entry
   uint32_t* fam_bits;           // [Kpad] maxima over the sets as u32 bit patterns (zero on entry), or nullptr
   int64_t nsets;
@@ -413,6 +427,7 @@ struct ExceedArgs {
   const uint32_t* tot;
   const float* t32;
   const double* d64;
+  const double* d64n;         // method 2: the table the (-) half reads (d64, or its mirror image)
   const uint32_t* pat;        // [m] ascending f32 bit patterns: a null value v counts for threshold j iff bits(v) >= pat[j]
   unsigned long long* hist;   // [m] bin j += values v with pat[j] <= bits(v) and (j == m-1 or bits(v) < pat[j+1])
   int64_t npaths;

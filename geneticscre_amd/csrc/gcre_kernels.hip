@@ -226,7 +226,7 @@ __global__ __launch_bounds__(kNullBlock, OCC) void k_null(const NullArgs a) {
           const u32 tp = TOT[2 * (qbase + t)];
           const u32 tn = TOT[2 * (qbase + t) + 1];
           const char* dp = (const char*)(a.d64 + diag_offset(tp));
-          const char* dn = (const char*)(a.d64 + diag_offset(tn));
+          const char* dn = (const char*)(a.d64n + diag_offset(tn));
 #pragma unroll
           for (int j = 0; j < R; j++) {
             const double s = *(const double*)(dp + (acc[0][t][j] << 3)) + *(const double*)(dn + (acc[M - 1][t][j] << 3));
@@ -705,7 +705,8 @@ hipError_t launch_collect_gt(const uint64_t* key, int64_t count, uint64_t thr, u
 
 constexpr int kEqChunk = 1024;   // entries per wave
 
-__global__ __launch_bounds__(256) void k_eq_count(const u64* key, i64 count, u64 thr, u32* chunk_cnt) {
+// thr / alt: the tie class -- one key, or the keys of -0.0 and +0.0, which tie as scores (alt == thr: one key)
+__global__ __launch_bounds__(256) void k_eq_count(const u64* key, i64 count, u64 thr, u64 alt, u32* chunk_cnt) {
   const int lane = threadIdx.x & 63;
   const i64 chunk = ((i64)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   const i64 base = chunk * kEqChunk;
@@ -713,21 +714,22 @@ __global__ __launch_bounds__(256) void k_eq_count(const u64* key, i64 count, u64
   u32 c = 0;
   for (int o = lane; o < kEqChunk; o += 64) {
     const i64 i = base + o;
-    if (i < count && key[i] == thr) c++;
+    if (i < count && (key[i] == thr || key[i] == alt)) c++;
   }
   c = wave_sum(c);
   if (lane == 0) chunk_cnt[chunk] = c;
 }
 
-hipError_t launch_eq_count(const uint64_t* key, int64_t count, uint64_t thr, uint32_t* chunk_cnt, hipStream_t stream) {
+hipError_t launch_eq_count(const uint64_t* key, int64_t count, uint64_t thr, uint64_t alt, uint32_t* chunk_cnt,
+                           hipStream_t stream) {
   const i64 chunks = (count + kEqChunk - 1) / kEqChunk;
   if (chunks == 0) return hipSuccess;
-  hipLaunchKernelGGL(k_eq_count, dim3((unsigned)((chunks + 3) / 4)), dim3(256), 0, stream, key, count, thr, chunk_cnt);
+  hipLaunchKernelGGL(k_eq_count, dim3((unsigned)((chunks + 3) / 4)), dim3(256), 0, stream, key, count, thr, alt, chunk_cnt);
   return hipGetLastError();
 }
 
-__global__ __launch_bounds__(256) void k_eq_collect(const u64* key, i64 count, u64 thr, const u32* chunk_base, u32 m,
-                                                    u32* out) {
+__global__ __launch_bounds__(256) void k_eq_collect(const u64* key, i64 count, u64 thr, u64 alt, const u32* chunk_base,
+                                                    u32 m, u32* out) {
   const int lane = threadIdx.x & 63;
   const i64 chunk = ((i64)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   const i64 base = chunk * kEqChunk;
@@ -736,7 +738,7 @@ __global__ __launch_bounds__(256) void k_eq_collect(const u64* key, i64 count, u
   if (rank >= m) return;
   for (int o = 0; o < kEqChunk; o += 64) {
     const i64 i = base + o + lane;
-    const bool eq = (i < count) && (key[i] == thr);
+    const bool eq = (i < count) && (key[i] == thr || key[i] == alt);
     const u64 ball = __ballot(eq);
     const u32 before = __popcll(ball & (((u64)1 << lane) - 1));
     if (eq && rank + before < m) out[rank + before] = (u32)i;
@@ -745,11 +747,11 @@ __global__ __launch_bounds__(256) void k_eq_collect(const u64* key, i64 count, u
   }
 }
 
-hipError_t launch_eq_collect(const uint64_t* key, int64_t count, uint64_t thr, const uint32_t* chunk_base, uint32_t m,
-                             uint32_t* out, hipStream_t stream) {
+hipError_t launch_eq_collect(const uint64_t* key, int64_t count, uint64_t thr, uint64_t alt, const uint32_t* chunk_base,
+                             uint32_t m, uint32_t* out, hipStream_t stream) {
   const i64 chunks = (count + kEqChunk - 1) / kEqChunk;
   if (chunks == 0 || m == 0) return hipSuccess;
-  hipLaunchKernelGGL(k_eq_collect, dim3((unsigned)((chunks + 3) / 4)), dim3(256), 0, stream, key, count, thr,
+  hipLaunchKernelGGL(k_eq_collect, dim3((unsigned)((chunks + 3) / 4)), dim3(256), 0, stream, key, count, thr, alt,
                      chunk_base, m, out);
   return hipGetLastError();
 }

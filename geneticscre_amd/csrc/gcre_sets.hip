@@ -193,9 +193,10 @@ __global__ __launch_bounds__(kSetBlock, OCC) void k_set_null(const SetNullArgs a
 #pragma unroll
         for (int j = 0; j < R; j++) v[j] = diag[acc[0][t][j]];
       } else {
-        // vtmax[pp][|P| - pp] + vtmax[pn][|N| - pn] (vtmax is symmetric), folded as k_null folds it
+        // vtmax[pp][|P| - pp] + vtmax[|N| - pn][pn] (d64n: d64, or its mirror image where vtmax is not symmetric), folded as
+        // k_null folds it
         const double* dp = a.d64 + sets_diag(TOT[2 * q]);
-        const double* dn = a.d64 + sets_diag(TOT[2 * q + 1]);
+        const double* dn = a.d64n + sets_diag(TOT[2 * q + 1]);
 #pragma unroll
         for (int j = 0; j < R; j++) {
           float f = (float)(dp[acc[0][t][j]] + dn[acc[M - 1][t][j]]);

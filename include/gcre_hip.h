@@ -114,7 +114,11 @@ int gcre_set_top_k(gcre_ctx* ctx, int top_k);        /* JoinExec::top_k, src/gcr
 int gcre_width_ul(const gcre_ctx* ctx);              /* 64-bit words per case/control mask, ceil(n/64) */
 int gcre_vlen(const gcre_ctx* ctx);                  /* words per path row as seen by the host = width * method */
 
-/* JoinExec::setValueTable, src/join_base.cpp:62-80.  nrow x ncol doubles; col_major != 0 for an R matrix. */
+/* JoinExec::setValueTable, src/join_base.cpp:62-80.  nrow x ncol doubles; col_major != 0 for an R matrix.  Any table: cells
+   it does not have read as -1; NaN, infinities, negatives, signed zeros and values beyond f32 score as in the reference.  A
+   signed-method table with a NaN on one side of its diagonal only (vtmax = std::max is then not symmetric) is kept with its
+   mirror image and scored by the dense permutation kernel alone, without pruning: much slower at production sizes, and
+   said so on stderr unless GCRE_QUIET is set. */
 int gcre_set_value_table(gcre_ctx* ctx, const double* table, int nrow, int ncol, int col_major);
 
 /* JoinExec::setPermutedCases, src/join_base.cpp:85-125.  nrow x ncol ints, 1 = label kept. */
@@ -140,7 +144,9 @@ void gcre_pathset_free(gcre_pathset* ps);
  *   uid_count / uid_location : uid_ref.count / .location per row of paths0 (src/gcre_types.h:50-56)
  *   signs                    : UidRelSet::signs, used by method 2 through need_flip (src/gcre.h:71-81)
  *   res                      : receives the joined rows (size must equal the total path count) or NULL
- * Ties between equal scores are resolved towards the smaller joined-path ordinal ("Ties").
+ * Ties between equal scores are resolved towards the smaller joined-path ordinal ("Ties").  Scores are
+ * compared as doubles, as the reference compares them (methods.h:91): -0.0 and +0.0 tie, whichever of the two a path
+ * scores it reports with its own sign.  The same holds for the per-gene tally and the observed exceedance counts.
  */
 int gcre_join(gcre_ctx* ctx, int path_length,
               const int32_t* uid_count, const int64_t* uid_location, int64_t n_uids,

@@ -31,7 +31,8 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 from geneticscre_amd import api  # noqa: E402
 from geneticscre_amd.harness_io import problem_digest, write_problem, write_problem_bin  # noqa: E402
 from geneticscre_amd.synth import make_problem  # noqa: E402
-from helpers import FUZZ_GOLDEN_CASES, SLOW_WIDE_CASES, WIDE_CASES, fuzz_problem, small_table, wide_problem  # noqa: E402
+from helpers import (FUZZ_GOLDEN_CASES, SLOW_WIDE_CASES, TABLE_GOLDEN_CASES, WIDE_CASES, fuzz_problem, small_table,  # noqa: E402
+                     table_golden_problem, wide_problem)
 
 DRIVER = os.path.join(ROOT, "oracle", "_ref", "ref_driver")
 OUT = os.path.join(HERE, "ref_cases")
@@ -112,9 +113,27 @@ def main(out=OUT, wide=True, slow=True, outputs=True):
         with open(os.path.join(out, name + ".json"), "w") as f:
             json.dump(res, f, separators=(",", ":"))
         print(name, cfg)
+    # the special-value table families at 70 patients (helpers.TABLE_GOLDEN_CASES): through --bin, the text dump cannot
+    # carry a NaN; outputs committed, inputs regenerated (input_sha256)
+    table_index = []
+    for name in TABLE_GOLDEN_CASES:
+        table_index.append(name)
+        p = table_golden_problem(name)
+        res = {}
+        if outputs:
+            with tempfile.TemporaryDirectory() as tmp:
+                blob = os.path.join(tmp, name + ".gcrebin")
+                write_problem_bin(blob, p, nthreads=0)
+                res = reference_run(["--bin", blob])
+        res["_case"] = {"method": p.method, "iterations": p.iterations, "top_k": p.top_k, "path_length": p.path_length,
+                        "table": list(p.value_table.shape), "paths": {k: int(v) for k, v in p.levels.n_paths.items()},
+                        "input_sha256": problem_digest(p)}
+        with open(os.path.join(out, name + ".json"), "w") as f:
+            json.dump(res, f, separators=(",", ":"))
+        print(name, p.top_k, list(p.value_table.shape))
     with open(os.path.join(out, "INDEX.json"), "w") as f:
         json.dump({"_provenance": __doc__.strip().splitlines()[0], "cases": index, "wide_cases": wide_index,
-                   "fuzz_cases": fuzz_index}, f, indent=1)
+                   "fuzz_cases": fuzz_index, "table_cases": table_index}, f, indent=1)
 
 
 if __name__ == "__main__":

@@ -126,6 +126,31 @@ def test_random_problem_matches_oracle(case, monkeypatch):
         assert_same_result(got[f"lst{lvl}"], want[f"lst{lvl}"])
 
 
+@pytest.mark.parametrize("case", range(N_CASES))
+def test_random_problem_with_special_table(case, monkeypatch):
+    """The same draws (case numbers from 500000) with only the value table replaced: the special-value families of
+    tests/helpers.py in turn -- both zeros, NaN and infinities, f32 denormals, f32 overflows, ladder levels, a table of the
+    wrong shape."""
+    from helpers import TABLE_FAMILIES, shape_tables, special_table
+    entered("special_table", BASE + 500000 + case)
+    cfg, env = draw(BASE + 500000 + case)
+    for k, v in env.items():
+        if v:
+            monkeypatch.setenv(k, v)
+    kind = TABLE_FAMILIES[case % 6]
+    if kind == "shapes":
+        shapes = shape_tables(cfg["n_cases"], cfg["n_ctrls"], cfg["seed"])
+        table = shapes[(case // 6) % len(shapes)][1]
+    else:
+        table = special_table(kind, cfg["n_cases"], cfg["n_ctrls"], cfg["seed"], variant=case // 6)
+    p = make_problem(cfg["genes"], cfg["edges"], cfg["n_cases"], cfg["n_ctrls"], cfg["perms"], cfg["length"],
+                     method=cfg["method"], top_k=cfg["top_k"], seed=cfg["seed"], threshold=cfg["threshold"], table=table)
+    want = oracle.process_paths(p, order="canonical")
+    got = api.process_paths(p)
+    for lvl in range(1, cfg["length"] + 1):
+        assert_same_result(got[f"lst{lvl}"], want[f"lst{lvl}"])
+
+
 @pytest.mark.parametrize("case", range(max(1, N_CASES // 4)))
 def test_random_sharded_plan_matches_oracle(case, monkeypatch):
     """The same draw through ResidentPlan, sharded over 2..5 ranks with the thresholds exchanged inside the joins: the

@@ -230,6 +230,26 @@ def test_oracle_matches_reference_scoring_code_at_baseline_widths(name):
         assert fnv_rows(got[f"paths{lvl}"]) == exp[key]["kept_hash"], (name, key)
 
 
+from helpers import TABLE_GOLDEN_CASES, load_table_case  # noqa: E402
+
+
+@pytest.mark.parametrize("name", TABLE_GOLDEN_CASES)
+def test_oracle_matches_reference_scoring_code_on_special_tables(name):
+    """The same, on the special-value table families of tests/helpers.py (NaN, infinities, both zeros, f32 denormals and
+    overflows, ladder levels, a table smaller than the cohort) at 70 patients: the reference's own scoring code says what
+    such cells do to scores, heap order and f32 null maxima."""
+    p, exp = load_table_case(name)
+    got = oracle.process_paths(p, order="reference", nthreads=0)
+    for lvl in range(1, p.path_length + 1):
+        e, r = exp[f"lst{lvl}"], got[f"lst{lvl}"]
+        assert [f"{int(b):016x}" for b in r.scores.view(np.uint64)] == e["scores"], (name, lvl)
+        assert r.src.tolist() == e["src"] and r.trg.tolist() == e["trg"], (name, lvl)
+        assert r.cases.tolist() == e["cases"] and r.ctrls.tolist() == e["ctrls"], (name, lvl)
+        assert [f"{int(b):08x}" for b in r.null.view(np.uint32)] == e["null"], (name, lvl)
+    for lvl, key in ((1, "lst1a"), (2, "lst2"), (3, "lst3")):
+        assert fnv_rows(got[f"paths{lvl}"]) == exp[key]["kept_hash"], (name, key)
+
+
 def test_committed_goldens_regenerate(tmp_path):
     """tests/golden/make_ref_goldens.py into a temporary directory gives the committed files byte for byte: the fixtures
     cannot drift from their generator (round 2: a table builder changed after the goldens were cut and nothing noticed).
