@@ -128,6 +128,7 @@ EXPORTS = [
     "gcre_set_inspect_cache", "gcre_drop_inspections", "gcre_build_flags", "gcre_device_count",
     "gcre_rccl_selftest", "gcre_rccl_collectives", "gcre_join_ahead",
     "gcre_decorated_splits", "gcre_decorated_pvalues", "gcre_score_sets",
+    "gcre_set_overlap", "gcre_overlap_launches",
     "gcre_gene_tally_create", "gcre_join_set_tally", "gcre_process_paths_set_tally", "gcre_gene_tally_read",
     "gcre_gene_tally_free",
     "gcre_exceed_create", "gcre_join_set_exceed", "gcre_process_paths_set_exceed", "gcre_exceed_read",
@@ -251,6 +252,22 @@ def _sets_lib():
     if lib.gcre_score_sets.argtypes is None:
         lib.gcre_score_sets.argtypes = [ctypes.c_void_p, ctypes.POINTER(gcre_set_input), ctypes.c_void_p, ctypes.c_int64,
                                         ctypes.POINTER(ctypes.c_int64), ctypes.c_void_p]
+    return lib
+
+
+OVERLAP_TILE = 64   # kOverlapTile: pairs per edge of a k_set_overlap block's tile
+
+
+def _overlap_lib():
+    """The library with gcre_set_overlap bound, on first use (as _decorated_lib)."""
+    lib = load_library()
+    if not hasattr(lib, "gcre_set_overlap"):
+        raise GcreError(f"{lib._name} has no carrier overlaps (gcre_set_overlap): rebuild it")
+    if lib.gcre_set_overlap.argtypes is None:
+        P, I64 = ctypes.c_void_p, ctypes.c_int64
+        lib.gcre_set_overlap.argtypes = [P, ctypes.POINTER(gcre_set_input), P, I64, P, I64, P, P]
+        lib.gcre_overlap_launches.restype = I64
+        lib.gcre_overlap_launches.argtypes = [P]
     return lib
 
 
@@ -748,6 +765,40 @@ class JoinExec:
             raise GcreError(self._lib.gcre_last_error(self._h).decode())
         rec = out[:n_out.value]
         return (rec, fam) if family else rec
+
+    def set_overlap(self, sets, rows, a=None, b=None):
+        """Carrier overlaps of caller-given sets (gcre_set_overlap).  A set's carrier row is the OR of all
+        its members (row indices of the 0/1 matrix ``rows``; -1 = NA gene), whatever the method.  Returns ``(size, both)``:
+        ``size`` int32 [S][2] = the carriers of every set among the cases and among the controls ((-1, -1) with an NA
+        member), ``both`` int32 [na][nb][2] = the patients sets ``a[i]`` and ``b[j]`` share, cases and controls (zeros
+        where either has an NA member).  ``a`` / ``b``: set indices, repeats allowed; None = every set in order.  Needs
+        neither a value table nor permutation masks.  Errors raise GcreError with the library's message."""
+        lib = _overlap_lib()
+        n = self.num_cases + self.num_ctrls
+        S = len(sets)
+        off = np.zeros(S + 1, dtype=np.int64)
+        off[1:] = np.cumsum([len(s) for s in sets])
+        members = np.ascontiguousarray(np.concatenate([np.asarray(s, dtype=np.int64).reshape(-1) for s in sets])
+                                       if S else np.zeros(0), dtype=np.int32)
+        d = np.asarray(rows)
+        if d.ndim != 2:
+            d = d.reshape(-1, n)
+        packed = pack_carriers(d, d.shape[1])
+        ia = None if a is None else np.ascontiguousarray(np.asarray(a, dtype=np.int64).reshape(-1))
+        ib = None if b is None else np.ascontiguousarray(np.asarray(b, dtype=np.int64).reshape(-1))
+        na = S if ia is None else len(ia)
+        nb = S if ib is None else len(ib)
+        inp = gcre_set_input(S, _ptr(off), _ptr(members), None, _ptr(packed), packed.shape[0], d.shape[1])
+        size = np.zeros((S, 2), dtype=np.int32)
+        both = np.zeros((na, nb, 2), dtype=np.int32)
+        rc = lib.gcre_set_overlap(self._h, ctypes.byref(inp), _ptr(ia), na, _ptr(ib), nb, _ptr(size), _ptr(both))
+        if rc != GCRE_OK:
+            raise GcreError(self._lib.gcre_last_error(self._h).decode())
+        return size, both
+
+    def overlap_launches(self) -> int:
+        """k_set_overlap launches of this context so far."""
+        return int(_overlap_lib().gcre_overlap_launches(self._h))
 
     def perm_mask(self, r: int) -> np.ndarray:
         out = np.zeros(self.width_ul, dtype=np.uint64)

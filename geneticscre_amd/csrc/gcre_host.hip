@@ -336,6 +336,7 @@ struct gcre_ctx {
   int64_t chunk_paths = int64_t(1) << 25;
   int null_blocks_per_cu = 12;
   int cus = 256;                     // compute units of the device (read once at gcre_create)
+  int64_t overlap_launches = 0;      // k_set_overlap launches of this context (gcre_overlap_launches)
 
   // resident inputs
   uint64_t* d_case_mask = nullptr;   // [Wp]
@@ -3629,6 +3630,140 @@ int gcre_score_sets(gcre_ctx* c, const gcre_set_input* in, gcre_set_score* out, 
   if (fam) std::memcpy(family_max, fbits.data(), (size_t)K * 4);
   return GCRE_OK;
 }
+
+// Carrier overlaps of caller-given sets: the validation of gcre_score_sets, the OR of every valid set's
+// members on the host, then k_set_overlap over the `a` list in slabs whose device output stays under GCRE_OVERLAP_SLAB_MB.
+int gcre_set_overlap(gcre_ctx* c, const gcre_set_input* in, const int64_t* a, int64_t na, const int64_t* b, int64_t nb,
+                     int32_t* size, int32_t* both) {
+  if (!c) return GCRE_ERR_ARG;
+  if (!in) return fail(c, GCRE_ERR_ARG, "set_overlap: NULL argument");
+  const Geometry& g = c->g;
+  if (in->n_cols != g.n)
+    return fail(c, GCRE_ERR_ARG, "set_overlap: the rows have " + std::to_string(in->n_cols) +
+                                     " columns, not n_cases + n_ctrls = " + std::to_string(g.n));
+  const int64_t S = in->n_sets;
+  if (S < 0 || in->n_rows < 0 || (S > 0 && (!in->set_off || !in->members)) || (in->n_rows > 0 && !in->rows))
+    return fail(c, GCRE_ERR_ARG, "set_overlap: bad input (a negative count or a NULL array)");
+  if (na < 0 || nb < 0 || (!a && na != S) || (!b && nb != S))
+    return fail(c, GCRE_ERR_ARG, "set_overlap: bad index list (a negative length, or NULL with a length other than n_sets)");
+  for (int64_t s = 0; s < S; s++) {
+    const int64_t lo = in->set_off[s], hi = in->set_off[s + 1];
+    const std::string name = "set_overlap: set " + std::to_string(s);
+    if (lo < 0 || hi <= lo) return fail(c, GCRE_ERR_ARG, name + " has no members");
+    for (int64_t i = lo; i < hi; i++) {
+      const int32_t row = in->members[i];
+      if (row < -1 || row >= in->n_rows)
+        return fail(c, GCRE_ERR_RANGE, name + ": member row " + std::to_string(row) + " out of range (" +
+                                           std::to_string(in->n_rows) + " rows)");
+      if (in->signs && in->signs[i] != 1 && in->signs[i] != -1)
+        return fail(c, GCRE_ERR_ARG, name + ": sign " + std::to_string(in->signs[i]) + " is neither +1 nor -1");
+    }
+  }
+  for (int side = 0; side < 2; side++) {
+    const int64_t* idx = side ? b : a;
+    const int64_t cnt = side ? nb : na;
+    for (int64_t i = 0; idx && i < cnt; i++)
+      if (idx[i] < 0 || idx[i] >= S)
+        return fail(c, GCRE_ERR_RANGE, std::string("set_overlap: ") + (side ? "b[" : "a[") + std::to_string(i) + "] = " +
+                                           std::to_string(idx[i]) + " out of range (" + std::to_string(S) + " sets)");
+  }
+  if (S > 0x7fffffff) return fail(c, GCRE_ERR_ARG, "set_overlap: too many sets");
+  const bool pairs = both && na > 0 && nb > 0;
+  if (!size && !pairs) return GCRE_OK;
+
+  // the host stage: per valid set the OR of all its members within the n patients, as [valid set][Wdp] dwords (zero
+  // padded to whole chunks of the kernel), and its case / control counts
+  const int W = g.W;
+  const int Wdp = (2 * W + kOverlapChunk - 1) / kOverlapChunk * kOverlapChunk;
+  const size_t RW = (size_t)Wdp / 2;   // words per device row
+  std::vector<uint64_t> cases((size_t)W, 0), ctrls((size_t)W, 0);
+  for (int q = 0; q < g.n; q++) (q < g.n_cases ? cases : ctrls)[(size_t)q / 64] |= uint64_t(1) << (q % 64);
+  std::vector<int32_t> vrow((size_t)S, -1);   // set -> row of urows, -1 = an NA member
+  std::vector<uint64_t> urows;
+  int64_t V = 0;
+  for (int64_t s = 0; s < S; s++) {
+    const int64_t lo = in->set_off[s], hi = in->set_off[s + 1];
+    bool valid = true;
+    for (int64_t i = lo; i < hi; i++) valid = valid && in->members[i] >= 0;
+    if (!valid) {
+      if (size) size[2 * s] = size[2 * s + 1] = -1;
+      continue;
+    }
+    vrow[(size_t)s] = (int32_t)V;
+    urows.resize((size_t)(V + 1) * RW, 0);
+    uint64_t* U = urows.data() + (size_t)V * RW;
+    V++;
+    for (int64_t i = lo; i < hi; i++) {
+      const uint64_t* r = in->rows + (size_t)in->members[i] * W;
+      for (int w = 0; w < W; w++) U[w] |= r[w] & (cases[w] | ctrls[w]);
+    }
+    if (size) {
+      int nc = 0, nt = 0;
+      for (int w = 0; w < W; w++) {
+        nc += __builtin_popcountll(U[w] & cases[w]);
+        nt += __builtin_popcountll(U[w] & ctrls[w]);
+      }
+      size[2 * s] = nc;
+      size[2 * s + 1] = nt;
+    }
+  }
+  if (!pairs) return GCRE_OK;
+  if (V == 0) {   // every set has an NA member: all overlaps are 0
+    std::memset(both, 0, (size_t)na * (size_t)nb * 8);
+    return GCRE_OK;
+  }
+  urows.resize((size_t)(V + 1) * RW, 0);   // row V, all zeros: what a set with an NA member and a tile's remainder read
+  auto row_of = [&](int64_t s) { return vrow[(size_t)s] < 0 ? (int32_t)V : vrow[(size_t)s]; };
+  std::vector<int32_t> ia((size_t)na), ib((size_t)nb);
+  for (int64_t i = 0; i < na; i++) ia[(size_t)i] = row_of(a ? a[i] : i);
+  for (int64_t j = 0; j < nb; j++) ib[(size_t)j] = row_of(b ? b[j] : j);
+
+  // `a` rows per launch: whole tiles, the output of a launch under the bound (one tile row at the least), the grid in range
+  double slab_mb = 256;
+  if (const char* e = std::getenv("GCRE_OVERLAP_SLAB_MB")) slab_mb = std::min(std::max(std::atof(e), 0.0), 65536.0);   // tests: fractions
+  const int64_t ntb = (nb + kOverlapTile - 1) / kOverlapTile;
+  int64_t slab = (int64_t)(slab_mb * 1048576.0) / (nb * 8) / kOverlapTile * kOverlapTile;
+  slab = std::max<int64_t>(slab, kOverlapTile);
+  slab = std::min<int64_t>(slab, (0x7fffffff / ntb) * kOverlapTile);
+  slab = std::min<int64_t>(slab, (na + kOverlapTile - 1) / kOverlapTile * kOverlapTile);
+  if (slab < kOverlapTile) return fail(c, GCRE_ERR_ARG, "set_overlap: too many b entries for one launch");
+
+  (void)hipSetDevice(c->device);
+  uint64_t* d_rows = nullptr;
+  int32_t *d_ia = nullptr, *d_ib = nullptr, *d_both = nullptr;
+  hipError_t e = hipMalloc((void**)&d_rows, urows.size() * 8);
+  if (e == hipSuccess) e = hipMalloc((void**)&d_ia, (size_t)na * 4);
+  if (e == hipSuccess) e = hipMalloc((void**)&d_ib, (size_t)nb * 4);
+  if (e == hipSuccess) e = hipMalloc((void**)&d_both, (size_t)std::min(slab, na) * (size_t)nb * 8);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_rows, urows.data(), urows.size() * 8, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_ia, ia.data(), (size_t)na * 4, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_ib, ib.data(), (size_t)nb * 4, hipMemcpyHostToDevice, c->stream);
+  for (int64_t r0 = 0; e == hipSuccess && r0 < na; r0 += slab) {
+    OverlapArgs o{};
+    o.rows = (const uint32_t*)d_rows;
+    o.ia = d_ia + r0;
+    o.ib = d_ib;
+    o.both = d_both;
+    o.na = std::min(slab, na - r0);
+    o.nb = nb;
+    o.ntb = ntb;
+    o.Wdp = Wdp;
+    o.n_cases = g.n_cases;
+    o.zero_row = (int)V;
+    e = launch_set_overlap(o, c->stream);
+    if (e == hipSuccess) c->overlap_launches++;
+    if (e == hipSuccess)
+      e = hipMemcpyAsync(both + (size_t)r0 * (size_t)nb * 2, d_both, (size_t)o.na * (size_t)nb * 8, hipMemcpyDeviceToHost,
+                         c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);   // the next slab writes d_both again
+  }
+  for (void* p : {(void*)d_rows, (void*)d_ia, (void*)d_ib, (void*)d_both})
+    if (p) (void)hipFree(p);
+  if (e != hipSuccess) return fail(c, GCRE_ERR_DEVICE, std::string("set_overlap: ") + hipGetErrorString(e));
+  return GCRE_OK;
+}
+
+int64_t gcre_overlap_launches(const gcre_ctx* c) { return c ? c->overlap_launches : -1; }
 
 int gcre_set_perm_window(gcre_ctx* c, int k0, int k1) {
   if (!c) return GCRE_ERR_ARG;

@@ -455,4 +455,20 @@ struct ExceedObsArgs {
 };
 hipError_t launch_exceed_observed(const ExceedObsArgs& a, int cus, hipStream_t stream);
 
+// ---- carrier-overlap counts of caller-given sets (gcre_overlap.hip) ----
+constexpr int kOverlapTile = 64;    // pairs per edge of a block's tile
+constexpr int kOverlapChunk = 32;   // dwords of a row per staged chunk (128 bytes): rows are padded to a multiple of it
+struct OverlapArgs {
+  const uint32_t* rows;         // [valid sets + 1][Wdp] carrier rows as dwords, zero beyond the n patients; the last is all zeros
+  const int32_t* ia;            // [na] row of `rows` per pair row of this launch (the zero row: a set with an NA member)
+  const int32_t* ib;            // [nb] the same for the pair columns
+  int32_t* both;                // [na][nb][2] cases, controls
+  int64_t na, nb;
+  int64_t ntb;                  // column tiles: ceil(nb / kOverlapTile)
+  int Wdp;                      // dwords per row, a multiple of kOverlapChunk
+  int n_cases;                  // columns below it are the cases
+  int zero_row;                 // the all-zero row of `rows`
+};
+hipError_t launch_set_overlap(const OverlapArgs& a, hipStream_t stream);
+
 }  // namespace gcre

@@ -13,6 +13,9 @@
                          (gcre_gene_tally; beyond the reference)
   * ``exceed_reference`` / ``fdr_columns``  null exceedance counts of a join in plain numpy, and the per-family error rate,
                          permutation FDR and q-values they give (gcre_exceed; beyond the reference)
+  * ``carrier_rows`` / ``overlap_reference`` / ``clump_rows`` / ``clump_paths``  which rows of a table are carried by the
+                         same patients: pairwise carrier overlaps on the device (gcre_set_overlap), greedy clumping against
+                         lead rows, and each row rescored without its lead's carriers (beyond the reference)
 
 Host-side post-processing of <= top_k x 5 rows: string work, nothing here touches the scored path.
 """
@@ -612,6 +615,191 @@ def fdr_columns(thresholds, exceed, observed, perms: int) -> Dict[str, np.ndarra
 
 
 # ---------------------------------------------------------------------------------------------------------------
+# carrier overlaps, clumping, conditional scores
+
+CLUMP_COLUMNS = ["Clump", "ClumpLead", "ClumpSize", "LeadOverlap", "SharedCases", "SharedControls"]
+RESIDUAL_COLUMNS = ["ResidualScores", "ResidualCases", "ResidualControls", "ResidualPvalues"]
+
+
+def carrier_rows(sets, rows, n: int) -> Tuple[np.ndarray, np.ndarray]:
+    """(C, valid): C bool [S][n], row s = the OR of ALL members of set s (row indices of the 0/1 matrix ``rows``, whatever
+    their signs: a patient who carries a variant in any gene of the path); valid[s] False, and the row all False, for a
+    set with an NA member (-1)."""
+    d = np.asarray(rows)[:, :n] != 0 if len(rows) else np.zeros((0, n), bool)
+    C = np.zeros((len(sets), n), bool)
+    valid = np.ones(len(sets), bool)
+    for s, members in enumerate(sets):
+        m = [int(x) for x in members]
+        if any(x < 0 for x in m):
+            valid[s] = False
+            continue
+        for x in m:
+            C[s] |= d[x]
+    return C, valid
+
+
+def overlap_reference(sets, rows, n_cases: int, n_ctrls: int, a=None, b=None) -> Tuple[np.ndarray, np.ndarray]:
+    """gcre_set_overlap by its definition, in numpy: size int32 [S][2] = carriers of every set among the cases (columns
+    < n_cases) and the controls, (-1, -1) with an NA member; both int32 [na][nb][2] = the patients sets a[i] and b[j]
+    share, zeros where either has an NA member.  ``a`` / ``b``: set indices, None = every set."""
+    n = n_cases + n_ctrls
+    C, valid = carrier_rows(sets, rows, n)
+    S = len(sets)
+    size = np.stack([C[:, :n_cases].sum(axis=1), C[:, n_cases:].sum(axis=1)], axis=1).astype(np.int32).reshape(S, 2)
+    size[~valid] = -1
+    ia = np.arange(S) if a is None else np.asarray(a, np.int64).reshape(-1)
+    ib = np.arange(S) if b is None else np.asarray(b, np.int64).reshape(-1)
+    A, B = C[ia].astype(np.float32), C[ib].astype(np.float32)   # counts <= 65,536 patients: exact in f32
+    both = np.stack([A[:, :n_cases] @ B[:, :n_cases].T, A[:, n_cases:] @ B[:, n_cases:].T], axis=2).astype(np.int32)
+    return size, both.reshape(len(ia), len(ib), 2)
+
+
+def clump_rows(order, size, both_of, r: float, measure: str = "jaccard", patients: str = "all", block: int = 256):
+    """Greedy clumping of rows by shared carriers, separable from the device.  ``order``: the rows to clump, best first;
+    ``size`` [S][2] their carriers (cases, controls); ``both_of(leads, others)`` -> [len(leads)][len(others)][2] shared
+    carriers.  Walk ``order``: a row not yet assigned becomes the lead of a new clump (numbered 0, 1, .. in that order) and
+    every later unassigned row whose overlap with it is >= r joins.  ``patients``: "all" counts cases + controls, "cases"
+    the cases only.  ``measure``: "jaccard" = both / (|A| + |B| - both), "containment" = both / min(|A|, |B|), in float64,
+    0.0 where the denominator is 0 (so a lead without carriers stays alone).  Counts are asked for in blocks of ``block``
+    candidate leads against all rows after them; the result does not depend on it.
+
+    Returns (clump, lead, value, shared): per row of ``size`` the clump id (-1 outside ``order``), the lead's row (-1
+    outside ``order``; a lead names itself), the measure against the lead (NaN on leads and outside ``order``) and the
+    shared (cases, controls) against the lead (-1 on leads and outside ``order``)."""
+    if not 0 < r <= 1:
+        raise ValueError("r must be > 0 and <= 1")
+    if measure not in ("jaccard", "containment"):
+        raise ValueError("measure must be 'jaccard' or 'containment'")
+    if patients not in ("all", "cases"):
+        raise ValueError("patients must be 'all' or 'cases'")
+    if block < 1:
+        raise ValueError("block must be >= 1")
+    size = np.asarray(size, np.int64).reshape(-1, 2)
+    S = len(size)
+    order = np.asarray(order, np.int64).reshape(-1)
+    tot = size[:, 0] + (size[:, 1] if patients == "all" else 0)
+    clump = np.full(S, -1, np.int64)
+    lead = np.full(S, -1, np.int64)
+    value = np.full(S, np.nan)
+    shared = np.full((S, 2), -1, np.int64)
+    free = np.ones(len(order), bool)   # by position in `order`
+    k = 0
+    pos = 0
+    while pos < len(order):
+        cand = pos + np.flatnonzero(free[pos:])[:block]          # positions of the next candidate leads
+        if len(cand) == 0:
+            break
+        rest = cand[0] + 1 + np.flatnonzero(free[cand[0] + 1:])  # every unassigned position after the first of them
+        counts = np.asarray(both_of(order[cand], order[rest]), np.int64).reshape(len(cand), len(rest), 2)
+        for ci, cp in enumerate(cand.tolist()):
+            if not free[cp]:
+                continue   # absorbed by an earlier lead of this block: its counts are discarded
+            row = order[cp]
+            free[cp] = False
+            clump[row], lead[row] = k, row
+            sel = (rest > cp) & free[rest]
+            others = order[rest[sel]]
+            sh = counts[ci, sel]
+            bo = sh[:, 0] + (sh[:, 1] if patients == "all" else 0)
+            A, B = tot[row], tot[others]
+            den = (A + B - bo) if measure == "jaccard" else np.minimum(A, B)
+            v = np.zeros(len(others))
+            np.divide(bo.astype(np.float64), den.astype(np.float64), out=v, where=den > 0)
+            join = v >= r
+            rows_in = others[join]
+            clump[rows_in], lead[rows_in] = k, row
+            value[rows_in] = v[join]
+            shared[rows_in] = sh[join]
+            free[rest[sel][join]] = False
+            k += 1
+        pos = int(cand[-1]) + 1
+    return clump, lead, value, shared
+
+
+def clump_paths(results_df, genes: Sequence[str], data: np.ndarray, n_cases: int, n_ctrls: int, signed: bool = False,
+                r: float = 0.5, measure: str = "jaccard", patients: str = "all", by_length: bool = False,
+                conditional: bool = False, threshold: float = 0.05, n_permutations: int = 100,
+                strata: Optional[Sequence[int]] = None, seed: int = 0, device: int = 0):
+    """Which rows of a GWASPA.Results table are the same finding: rows clumped by the patients that carry them, and with
+    ``conditional`` each row rescored without its lead's carriers.  A row's carriers are the patients
+    with a variant in any gene of its ``SignedPaths`` (``carrier_rows``); the pairwise shared-carrier counts come from the
+    device (gcre_set_overlap), the rule is ``clump_rows``.  Genes are looked up after ``preprocess_table(threshold)``, as
+    ``score_paths`` does.  Rows with a finite score and no NA gene are walked by ``Scores`` descending (ties: table
+    position); with ``by_length`` every ``Lengths`` group, ascending, is clumped on its own and the clump ids keep
+    counting.  Returns a copy of the table with
+
+      ``Clump``  the clump id (-1: a row that was not clumped), ``ClumpLead``  the lead row's ``Paths`` (None for -1),
+      ``ClumpSize``  rows in the clump (0 for -1), ``LeadOverlap``  the measure against the lead, ``SharedCases`` /
+      ``SharedControls``  the carriers shared with the lead (the last three NaN on lead rows and on -1 rows).
+
+    ``conditional``: for every non-lead row, every patient column the lead carries is zeroed in the whole carrier matrix
+    and the row's set is scored on it by ``JoinExec.score_sets`` (method 1: U & ~C_lead; method 2: both halves & ~C_lead;
+    n_cases / n_ctrls unchanged: the removed patients count as non-carriers), on one context with ``api.values_table`` and
+    the masks of ``generate_permutations(seed, strata)``: ``ResidualScores``, ``ResidualCases``, ``ResidualControls`` and
+    ``ResidualPvalues``.  ``ResidualPvalues`` is that set's NOMINAL permutation p-value n_ge / n_permutations -- the
+    residual score against its own null, not a family-wise number like ``Pvalues``.  NaN on lead rows and on -1 rows."""
+    from . import api
+    method = 2 if signed else 1
+    genes, data = preprocess_table(genes, data, threshold, n_cases, n_ctrls)
+    _, rows, signs = parse_sets([str(p) for p in results_df["SignedPaths"]], genes)
+    used: Dict[int, int] = {}
+    sets = [[-1 if x < 0 else used.setdefault(x, len(used)) for x in rs] for rs in rows]
+    sub = np.asarray(data)[list(used.keys())] if used else np.zeros((0, n_cases + n_ctrls), np.int32)
+    S = len(sets)
+    scores = results_df["Scores"].to_numpy(dtype=np.float64)
+    lengths = results_df["Lengths"].to_numpy()
+    ok = np.isfinite(scores) & np.array([all(x >= 0 for x in rs) for rs in rows], dtype=bool).reshape(S)
+    K = int(n_permutations) if conditional else 0
+    out = results_df.copy()
+    clump = np.full(S, -1, np.int64)
+    lead = np.full(S, -1, np.int64)
+    value = np.full(S, np.nan)
+    shared = np.full((S, 2), -1, np.int64)
+    res = {c: np.full(S, np.nan) for c in RESIDUAL_COLUMNS}
+    ex = api.JoinExec(method, n_cases, n_ctrls, K, device=device)
+    try:
+        size, _ = ex.set_overlap(sets, sub, a=[], b=[]) if S else (np.zeros((0, 2), np.int32), None)
+        groups = [np.flatnonzero(ok & (lengths == L)) for L in np.unique(lengths[ok]).tolist()] if by_length \
+            else [np.flatnonzero(ok)]
+        base = 0
+        for idx in groups:
+            order = idx[np.argsort(-scores[idx], kind="stable")]
+            c, l, v, sh = clump_rows(order, size, lambda la, lb: ex.set_overlap(sets, sub, a=la, b=lb)[1], r, measure,
+                                     patients)
+            clump[order], lead[order], value[order], shared[order] = c[order] + base, l[order], v[order], sh[order]
+            base += int(c[order].max()) + 1 if len(order) else 0
+        if conditional:
+            ex.set_value_table(api.values_table(n_cases, n_ctrls))
+            if K > 0:
+                ex.generate_permutations(seed, strata)
+            C, _ = carrier_rows(sets, sub, n_cases + n_ctrls)
+            members = (clump >= 0) & (lead != np.arange(S))
+            for ld in np.unique(lead[members]).tolist():   # one score_sets call per lead that has members: host-bound
+                js = np.flatnonzero(members & (lead == ld))
+                need: Dict[int, int] = {}   # the rows these sets use, without the lead's carriers
+                msets = [[need.setdefault(x, len(need)) for x in sets[j]] for j in js]
+                rec = ex.score_sets(msets, np.where(C[ld][None, :], 0, sub[list(need.keys())]), [signs[j] for j in js])
+                res["ResidualScores"][js] = rec["score"]
+                res["ResidualCases"][js] = rec["cases"]
+                res["ResidualControls"][js] = rec["ctrls"]
+                res["ResidualPvalues"][js] = rec["pvalue"]
+    finally:
+        ex.close()
+    is_member = (clump >= 0) & (lead != np.arange(S))
+    paths = [str(p) for p in results_df["Paths"]]
+    out["Clump"] = clump
+    out["ClumpLead"] = [paths[l] if l >= 0 else None for l in lead.tolist()]
+    out["ClumpSize"] = np.where(clump >= 0, np.bincount(clump[clump >= 0], minlength=1)[np.maximum(clump, 0)], 0)
+    out["LeadOverlap"] = np.where(is_member, value, np.nan)
+    out["SharedCases"] = np.where(is_member, shared[:, 0], np.nan)
+    out["SharedControls"] = np.where(is_member, shared[:, 1], np.nan)
+    if conditional:
+        for cname in RESIDUAL_COLUMNS:
+            out[cname] = res[cname]
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------
 # inputs
 
 
@@ -758,7 +946,8 @@ def frames_of(prep: Prepared, levels) -> Dict[str, Dict[str, np.ndarray]]:
 def gwaspa(genes: Sequence[str], data: np.ndarray, n_cases: int, n_ctrls: int, network, signed: bool = False,
            threshold: float = 0.05, top_k: int = 10, path_length: int = 5, n_permutations: int = 100,
            strata: Optional[Sequence[int]] = None, seed: int = 0, device: int = 0,
-           decorated_pvalues: bool = False, gene_table: bool = False, fdr: bool = False) -> Dict[str, object]:
+           decorated_pvalues: bool = False, gene_table: bool = False, fdr: bool = False,
+           clump: Optional[float] = None, clump_conditional: bool = False) -> Dict[str, object]:
     """GWASPA (R/ProcessPaths.R:87-344) without R: dataset -> GWASPA.Results, scored on the MI355X.
 
     ``network`` = (ents_uid, ents_symbol, rel_src, rel_trg, rel_sign): the knowledge base getStringKB() would load
@@ -782,6 +971,12 @@ def gwaspa(genes: Sequence[str], data: np.ndarray, n_cases: int, n_ctrls: int, n
     "Qvalues" (``fdr_columns``: within a length, pi0 = 1), and the raw counts come back as "exceed" (length ->
     api.Exceedances).  Sentinel rows get NaN.  The row order and the other seven columns are what ``fdr=False`` returns.
     Default False.
+
+    ``clump``: with a value r, GWASPA.Results goes through ``clump_paths(r=clump, conditional=clump_conditional)`` with the
+    run's own seed, strata, threshold and permutation count: it gains ``CLUMP_COLUMNS`` -- which rows are
+    carried by the same patients as a better row -- and with ``clump_conditional`` ``RESIDUAL_COLUMNS``, each row rescored
+    without its lead's carriers (``ResidualPvalues`` is a nominal per-set p-value, not a family-wise one).  The row order
+    and the other columns are unchanged.  None, the default: nothing new is called.
     """
     from . import api
     from .synth import Problem
@@ -854,4 +1049,8 @@ def gwaspa(genes: Sequence[str], data: np.ndarray, n_cases: int, n_ctrls: int, n
         if dec is not None:
             out["Decorated.Pvalues.Results"] = dec
     ex.close()
+    if clump is not None:
+        out["GWASPA.Results"] = clump_paths(out["GWASPA.Results"], genes, data, n_cases, n_ctrls, signed, r=clump,
+                                            conditional=clump_conditional, threshold=threshold,
+                                            n_permutations=n_permutations, strata=strata, seed=seed, device=device)
     return out

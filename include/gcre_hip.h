@@ -440,6 +440,25 @@ int gcre_score_sets(gcre_ctx* ctx, const gcre_set_input* in, gcre_set_score* out
                     float* family_max);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Carrier overlaps of caller-given sets: which sets are carried by the same patients.  No reference
+ * counterpart.
+ * Carrier row of set s: C_s = OR of ALL its members, whatever their signs and whatever the context's method (a patient
+ * who carries a variant in any gene of the path), bits >= n_cols ignored.
+ *   size[s]      = { |C_s & cases|, |C_s & ctrls| }  (cases = columns < n_cases); { -1, -1 } for a set with an NA member
+ *   both[i][j]   = { |C_a[i] & C_b[j] & cases|, |C_a[i] & C_b[j] & ctrls| }; { 0, 0 } when either set has an NA member
+ * a / b: set indices, repeats allowed; NULL = 0 .. n_sets-1 (then na / nb must be n_sets).  size [n_sets][2] and
+ * both [na][nb][2] are int32, either may be NULL.  Needs neither a value table nor permutation masks.
+ * The rows are uploaded once and `a` is walked in slabs so that the device output of one launch of k_set_overlap stays
+ * under GCRE_OVERLAP_SLAB_MB (environment, default 256; one row of 64 x 64 pair tiles at the least); the results do not
+ * depend on it.  Any na, nb >= 0; 0 returns at once.  Errors, nothing launched: GCRE_ERR_ARG -- a NULL argument, n_cols
+ * not n_cases + n_ctrls, a set without members, a sign other than +1 / -1; GCRE_ERR_RANGE -- a member row or a set index
+ * out of range. */
+int gcre_set_overlap(gcre_ctx* ctx, const gcre_set_input* in, const int64_t* a, int64_t na,
+                     const int64_t* b, int64_t nb, int32_t* size, int32_t* both);
+/* k_set_overlap launches of the context since gcre_create (tests: an argument error launches nothing). */
+int64_t gcre_overlap_launches(const gcre_ctx* ctx);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Per-gene best-path table: for every gene, the best joined path of a join that runs through it.  No
  * reference counterpart (it keeps the top K of a level and nothing else).  A join's inspector leaves the observed score,
  * operand rows, cases and controls of EVERY joined path on the device; a tally armed for the join folds them, chunk by
