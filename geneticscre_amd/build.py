@@ -86,6 +86,38 @@ def build_harness(force: bool = False, verbose: bool = False) -> str:
     return out
 
 
+R_MOCK_DIR = os.path.join(PKG, "..", "tests", "r_mock")
+R_SHIM_SRC = os.path.join(CSRC, "r_shim.c")
+
+
+def build_r_mock(force: bool = False, verbose: bool = False, tag: str = "") -> tuple:
+    """Test infrastructure: the .Call shim (csrc/r_shim.c) linked with the stand-in R runtime of tests/r_mock into ONE
+    shared object, and the recording backend next to it -- plain gcc, no R, no GPU.  Returns (shim + runtime, backend).
+    ``tag``: a second copy of the first object under a name of its own; the shim resolves its backend once per loaded
+    object (GCRE_HIP_LIB), so a process that drives it against two backends loads two copies."""
+    d = os.path.abspath(R_MOCK_DIR)
+    inc = [os.path.abspath(os.path.join(PKG, "..", "include"))]
+    decls = os.path.abspath(os.path.join(PKG, "..", "tests", "r_api_decls"))
+    shim_so = os.path.join(d, f"r_shim_mock{tag}.so")
+    stub_so = os.path.join(d, "gcre_stub.so")
+    jobs = [(shim_so, [os.path.abspath(R_SHIM_SRC), os.path.join(d, "r_mock.c")], inc + [decls]),
+            (stub_so, [os.path.join(d, "gcre_stub.c")], inc)]
+    hdrs = [os.path.join(inc[0], "gcre_hip.h"), os.path.join(decls, "Rinternals.h"), os.path.join(decls, "R_ext", "Rdynload.h"),
+            os.path.abspath(__file__)]
+    for out, srcs, incs in jobs:
+        if not force and os.path.exists(out) and os.path.getmtime(out) >= max(os.path.getmtime(f) for f in srcs + hdrs):
+            continue
+        tmp = out[:-3] + f".tmp{os.getpid()}.so"   # (git ignores *.so)
+        cmd = ["gcc", "-O1", "-g", "-std=gnu11", "-Wall", "-Werror=implicit-function-declaration", "-Werror=incompatible-pointer-types",
+               "-Werror=int-conversion", "-fPIC", "-shared", *[x for i in incs for x in ("-I", i)], *srcs, "-ldl", "-lm",
+               "-o", tmp]
+        if verbose:
+            print(" ".join(cmd))
+        subprocess.run(cmd, check=True)
+        os.replace(tmp, out)
+    return shim_so, stub_so
+
+
 if __name__ == "__main__":
     print(build(force=True, verbose=True))
     print(build_harness(force=True, verbose=True))

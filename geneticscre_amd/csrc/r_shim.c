@@ -4,9 +4,9 @@
  *
  * Built INSIDE the R package in place of the Rcpp sources:
  *     R CMD SHLIB -o geneticsCRE.so r_shim.c -ldl
- * It needs only R's own C API (no Rcpp).  R is not installed in the build container of this repository: there the
- * file is only syntax- and type-checked against declarations of the R API entry points it uses
- * (tests/r_api_decls/, tests/test_host_logic.py); it is deliberately plain C with no logic beyond marshalling.
+ * It needs only R's own C API (no Rcpp).  R is not installed in the build container of this repository: there the file is
+ * type-checked against declarations of the R API entry points it uses (tests/r_api_decls/) and executed under a stand-in
+ * runtime (tests/r_mock/, tests/test_r_shim_host.py), never under R itself; plain C with no logic beyond marshalling.
  *
  * The unmodified R package passes doubles for several "integer" arguments (rep(1, n) sign vectors, match(...) - 1
  * index vectors, R/ProcessPaths.R:214-256); Rcpp's IntegerVector / IntegerMatrix coerce silently, so every argument

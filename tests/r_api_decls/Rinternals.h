@@ -1,7 +1,8 @@
 /* tests/r_api_decls/Rinternals.h -- NOT R's header.  Declarations of the few R C-API entry points
  * geneticscre_amd/csrc/r_shim.c uses, with the signatures documented in "Writing R Extensions" (sections 5.9, 5.10),
- * so that the shim can be syntax- and type-checked (gcc -fsyntax-only) in an image without R.  Test
- * infrastructure only: nothing is built or linked against this file.  On a machine with R the real headers are used. */
+ * so that the shim can be syntax- and type-checked (gcc -fsyntax-only) in an image without R, and compiled together with
+ * the stand-in runtime of tests/r_mock/r_mock.c, which implements exactly these entry points, to be executed by the tests.
+ * Test infrastructure only: the product is never built against this file.  On a machine with R the real headers are used. */
 #pragma once
 #include <stddef.h>
 typedef struct SEXPREC* SEXP;
