@@ -133,6 +133,7 @@ EXPORTS = [
     "gcre_gene_tally_free",
     "gcre_exceed_create", "gcre_join_set_exceed", "gcre_process_paths_set_exceed", "gcre_exceed_read",
     "gcre_exceed_reset", "gcre_exceed_free",
+    "gcre_exceed_keep_perm_counts", "gcre_exceed_read_perm_counts",
 ]
 
 
@@ -386,7 +387,19 @@ def _exceed_lib():
     return lib
 
 
+def _perm_counts_lib():
+    """The same with the per-permutation counts bound, on first use."""
+    lib = _exceed_lib()
+    if not hasattr(lib, "gcre_exceed_keep_perm_counts") or not hasattr(lib, "gcre_exceed_read_perm_counts"):
+        raise GcreError(f"{lib._name} has no per-permutation exceedance counts (gcre_exceed_keep_perm_counts): rebuild it")
+    if lib.gcre_exceed_keep_perm_counts.argtypes is None:
+        lib.gcre_exceed_keep_perm_counts.argtypes = [ctypes.c_void_p, ctypes.c_int]
+        lib.gcre_exceed_read_perm_counts.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+    return lib
+
+
 EXCEED_MAX = 10000   # kExceedMax: thresholds of one ExceedCounts (the top_k limit)
+EXCEED_PERM_CELLS = 1 << 26   # thresholds x iterations of an ExceedCounts that keeps per-permutation counts (256 MB of u32 cells)
 
 
 @dataclass
@@ -397,20 +410,33 @@ class Exceedances:
     observed: np.ndarray   # uint64: joined paths with an observed score >= the threshold
     perms: int             # permutations counted (the window lengths of the joins counted, added)
     paths: int             # joined paths whose observed scores were counted
+    # uint64 [m][iterations]: joined paths with a null score >= the threshold, per permutation (absolute index); every row
+    # sums to ``exceed``.  None when the object keeps none (``ExceedCounts(perm_counts=False)``)
+    perm_counts: Optional[np.ndarray] = None
 
 
 class ExceedCounts:
     """gcre_exceed: null exceedance counts of a join for a list of thresholds.  Pass it as
     ``JoinExec.join(..., exceed=x)`` or ``process_paths(..., exceeds={"4": x})``, then ``read()``.  Counts ADD: a join counted
-    twice is counted twice (``reset()`` starts over); ``report.fdr_columns`` turns them into PFER, FDR and q-values."""
+    twice is counted twice (``reset()`` starts over); ``report.fdr_columns`` turns them into PFER, FDR and q-values.
 
-    def __init__(self, owner: "JoinExec", thresholds):
+    ``perm_counts=True`` also keeps the counts per permutation (gcre_exceed_keep_perm_counts, DESIGN.md §3.8a: thresholds x
+    iterations <= ``EXCEED_PERM_CELLS``), read as ``Exceedances.perm_counts``; ``report.false_count_columns`` turns them into
+    k-FWER, the median and the (1 - alpha) bound of the number of false positives.  False, the default: nothing new is called."""
+
+    def __init__(self, owner: "JoinExec", thresholds, perm_counts: bool = False):
         t = np.ascontiguousarray(np.asarray(thresholds, dtype=np.float64).ravel())
         self.thresholds = t
-        self._owner, self._lib, self._h = owner, _exceed_lib(), None
+        self.keeps_perm_counts = bool(perm_counts)
+        self._owner, self._lib, self._h = owner, (_perm_counts_lib() if perm_counts else _exceed_lib()), None
         self._h = self._lib.gcre_exceed_create(owner._h, _ptr(t), len(t))
         if not self._h:
             owner._raise(GCRE_ERR_ARG)
+        if perm_counts:
+            rc = self._lib.gcre_exceed_keep_perm_counts(self._h, 1)
+            if rc != 0:
+                self.free()
+                owner._raise(rc)
 
     def read(self) -> Exceedances:
         m = len(self.thresholds)
@@ -418,7 +444,11 @@ class ExceedCounts:
         perms, paths = ctypes.c_int64(0), ctypes.c_int64(0)
         self._owner._check(self._lib.gcre_exceed_read(self._h, _ptr(exceed), _ptr(observed), ctypes.byref(perms),
                                                       ctypes.byref(paths)))
-        return Exceedances(exceed, observed, int(perms.value), int(paths.value))
+        pc = None
+        if self.keeps_perm_counts:
+            pc = np.zeros((m, int(self._owner.iters)), np.uint64)
+            self._owner._check(self._lib.gcre_exceed_read_perm_counts(self._h, _ptr(pc)))
+        return Exceedances(exceed, observed, int(perms.value), int(paths.value), pc)
 
     def reset(self) -> None:
         self._owner._check(self._lib.gcre_exceed_reset(self._h))

@@ -24,6 +24,12 @@
 //          the other waves may go on adding) after kExceedFlushPaths = 262,144 of them; a bin holds what the four waves
 //          added since their own last flush: 4 x 2^18 x 2^11 = 2^31 at the very most
 // Every global write is a vector atomic.
+//
+// Per-permutation counts (PC instantiations): a passing value goes into the queue together with its
+// permutation's index inside the tile (16 bits, in a queue of its own), and the drain loop, next to the histogram bin, adds
+// 1 to the u32 cell pc[bin * stride + absolute permutation] in global memory -- no LDS staging: a pass is rare, and one
+// (bin, permutation) cell is hit by different waves at different times.  The instantiations without PC are the code they
+// were: `if constexpr`, and the three fields at the end of the argument structs, which they do not read.
 #include "gcre_ie_common.h"
 
 
@@ -128,8 +134,48 @@ __device__ __forceinline__ void exc_emit(const u32 (&v)[N], const bool (&pass)[N
   __builtin_amdgcn_wave_barrier();
 }
 
-// M, R, TPW, WC, OCC as k_null
-template <int M, int R, int TPW, int WC, int OCC>
+// where a kernel's per-permutation counts go
+struct ExcPerm {
+  u32* pc;        // [m][stride]
+  u32 stride;
+  u32 base;       // absolute permutation of the tile's column 0 (window start + tile start)
+};
+
+// The same with per-permutation counts: col(lane, j) < 2048 is the column of value j inside the permutation tile.  A
+// passing value is a live column of the window (the caller's `pass`): base + col < the context's permutations <= stride.
+// The columns are functions of the lane alone; they are made here, on the rare road, from a lane index the optimiser
+// cannot see through -- otherwise it keeps all of them in registers across the count loop (28 more VGPRs in k_exceed_ie).
+template <int N, typename Col>
+__device__ __forceinline__ void exc_emit_pc(const u32 (&v)[N], const bool (&pass)[N], Col col, u32* queue,
+                                            unsigned short* pqueue, const ExcBins& b, const ExcPerm& pp, int lane) {
+  static_assert(64 * N <= kExceedQueue, "queue");
+  int lane_here = lane;
+  asm volatile("" : "+v"(lane_here));
+  u32 n = 0;
+#pragma unroll
+  for (int j = 0; j < N; j++) {
+    const u64 bal = __ballot(pass[j]);
+    const u32 pos = n + __builtin_amdgcn_mbcnt_hi((u32)(bal >> 32), __builtin_amdgcn_mbcnt_lo((u32)bal, 0u));
+    if (pass[j]) {
+      queue[pos] = v[j];
+      pqueue[pos] = (unsigned short)col(lane_here, j);
+    }
+    n += (u32)__popcll(bal);
+  }
+  __builtin_amdgcn_wave_barrier();   // (a wave's LDS accesses are served in order)
+  for (u32 i = (u32)lane; i < n; i += 64u) {
+    const u32 x = queue[i];
+    const u32 r = pp.base + (u32)pqueue[i];
+    const int bin = exc_bin(b.pat, b.m, x);
+    if (b.lds) atomicAdd(&b.lds[bin], 1u);
+    else atomicAdd(b.hist + bin, 1ull);
+    atomicAdd(pp.pc + ((size_t)bin * pp.stride + r), 1u);
+  }
+  __builtin_amdgcn_wave_barrier();
+}
+
+// M, R, TPW, WC, OCC as k_null; PC: per-permutation counts too
+template <int M, int R, int TPW, int WC, int OCC, bool PC>
 __global__ __launch_bounds__(kNullBlock, OCC) void k_exceed_dense(const ExceedArgs a) {
   typedef typename ExcChunk<WC>::type rowv;
   constexpr int NW = kNullBlock / 64;
@@ -142,6 +188,7 @@ __global__ __launch_bounds__(kNullBlock, OCC) void k_exceed_dense(const ExceedAr
 
   __shared__ __attribute__((aligned(16))) u32 lds[2][CHUNK];
   __shared__ u32 queue_lds[NW][64 * R];
+  __shared__ unsigned short pqueue_lds[PC ? NW : 1][PC ? 64 * R : 1];
   extern __shared__ u32 bins[];   // a.lds_bins words
 
   const int tid = threadIdx.x;
@@ -190,6 +237,15 @@ __global__ __launch_bounds__(kNullBlock, OCC) void k_exceed_dense(const ExceedAr
 
   const ExcBins eb{a.pat, a.m, a.lds_bins ? bins : nullptr, a.hist};
   u32* const queue = queue_lds[wave];
+  unsigned short* const pqueue = pqueue_lds[PC ? wave : 0];
+  const ExcPerm pp{a.pc, (u32)a.pc_stride, (u32)(a.k0 + kt * PT)};
+  auto emit = [&](const u32 (&v)[R], const bool (&pass)[R]) {
+    if constexpr (PC) {
+      exc_emit_pc<R>(v, pass, [](int l, int j) { return exc_col<R>(l, j); }, queue, pqueue, eb, pp, lane);
+    } else {
+      exc_emit<R>(v, pass, queue, eb, lane);
+    }
+  };
 
   stage_load(0);
   stage_store(0);
@@ -288,7 +344,7 @@ __global__ __launch_bounds__(kNullBlock, OCC) void k_exceed_dense(const ExceedAr
             pass[j] = v[j] >= pat0 && exc_col<R>(lane, j) < live_cols;
             any = any || pass[j];
           }
-          if (__ballot(any)) exc_emit<R>(v, pass, queue, eb, lane);
+          if (__ballot(any)) emit(v, pass);
         } else {
           const u32 tp = TOT[2 * (qbase + t)];
           const u32 tn = TOT[2 * (qbase + t) + 1];
@@ -305,7 +361,7 @@ __global__ __launch_bounds__(kNullBlock, OCC) void k_exceed_dense(const ExceedAr
             pass[j] = v[j] >= pat0 && exc_col<R>(lane, j) < live_cols;
             any = any || pass[j];
           }
-          if (__ballot(any)) exc_emit<R>(v, pass, queue, eb, lane);
+          if (__ballot(any)) emit(v, pass);
         }
       }
     }
@@ -325,7 +381,10 @@ __global__ __launch_bounds__(kNullBlock, OCC) void k_exceed_dense(const ExceedAr
 template <int M, int R, int TPW, int WC, int OCC>
 hipError_t launch_exceed_t(const ExceedArgs& a, hipStream_t stream) {
   const dim3 grid((unsigned)(a.nkt * a.pgroups));
-  hipLaunchKernelGGL((k_exceed_dense<M, R, TPW, WC, OCC>), grid, dim3(kNullBlock), (size_t)a.lds_bins * 4, stream, a);
+  if (a.pc)
+    hipLaunchKernelGGL((k_exceed_dense<M, R, TPW, WC, OCC, true>), grid, dim3(kNullBlock), (size_t)a.lds_bins * 4, stream, a);
+  else
+    hipLaunchKernelGGL((k_exceed_dense<M, R, TPW, WC, OCC, false>), grid, dim3(kNullBlock), (size_t)a.lds_bins * 4, stream, a);
   return hipGetLastError();
 }
 
@@ -358,10 +417,15 @@ struct ExceedIeArgs {
   unsigned long long* hist;
   int m;
   int lds_bins;
+  u32* pc;          // PC: [m][pc_stride] per-permutation counts
+  int pc_stride;
+  int k0;           // PC: absolute permutation of the window's first
 };
 
-template <int M, int L>
-__global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(M == 1 ? 4 : 2))) void k_exceed_ie(const ExceedIeArgs xa) {
+// PC: per-permutation counts too.  (<2, 16, PC> comes out two VGPRs above its sibling's 167 when it may take two waves'
+// worth of registers, and loses the third wave; told to fit three it does, without a spill.)
+template <int M, int L, bool PC>
+__global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(M == 1 ? 4 : (PC && L == 16) ? 3 : 2))) void k_exceed_ie(const ExceedIeArgs xa) {
   static_assert(L % 4 == 0 && L >= 8 && L <= 16, "planes come in groups of 4");
   const IeArgs& a = xa.ie;
   const int lane = threadIdx.x & 63;
@@ -372,11 +436,14 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(M
   const i64 slices = 8 * wx;
   const u32 lane4 = (u32)lane * 4u;
   __shared__ u32 queue_lds[kIeWaves][kExceedQueue];
+  __shared__ unsigned short pqueue_lds[PC ? kIeWaves : 1][PC ? kExceedQueue : 1];
   extern __shared__ u32 bins[];   // xa.lds_bins words
   for (int i = threadIdx.x; i < xa.lds_bins; i += 64 * kIeWaves) bins[i] = 0u;
   __syncthreads();
   const ExcBins eb{xa.pat, xa.m, xa.lds_bins ? bins : nullptr, xa.hist};
   u32* const queue = queue_lds[wave];
+  unsigned short* const pqueue = pqueue_lds[PC ? wave : 0];
+  ExcPerm pp{xa.pc, (u32)xa.pc_stride, 0u};   // (base: set with the tile)
   const u32 pat0 = xa.pat[0];
   int counted = 0;   // (path, tile) items since the wave's last flush
 
@@ -401,7 +468,13 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(M
       pass[k] = v[k] >= pat0 && q0 + k < live_q;
       any = any || pass[k];
     }
-    if (__ballot(any)) exc_emit<8>(v, pass, queue, eb, lane);
+    if (__ballot(any)) {
+      if constexpr (PC) {
+        exc_emit_pc<8>(v, pass, [q0](int l, int k) { return l * 32 + q0 + k; }, queue, pqueue, eb, pp, lane);
+      } else {
+        exc_emit<8>(v, pass, queue, eb, lane);
+      }
+    }
   };
   // method 1: counts -> f32 table diagonal (methods.h:96-103), all 32 table cells of the lane in flight together
   auto finish_m1 = [&](const u32 (&C)[L], u32 total) {
@@ -462,7 +535,13 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(M
         pass[k + 4] = hi[k] >= pat0 && g0 + k + 16 < live_q;
         any = any || pass[k] || pass[k + 4];
       }
-      if (__ballot(any)) exc_emit<8>(v, pass, queue, eb, lane);
+      if (__ballot(any)) {
+        if constexpr (PC) {
+          exc_emit_pc<8>(v, pass, [g0](int l, int k) { return l * 32 + g0 + (k < 4 ? k : k + 12); }, queue, pqueue, eb, pp, lane);
+        } else {
+          exc_emit<8>(v, pass, queue, eb, lane);
+        }
+      }
     }
   };
 
@@ -486,6 +565,7 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(M
     if (kt != cur_kt) {
       cur_kt = kt;
       live_q = a.K - kt * 2048 - lane * 32;
+      if constexpr (PC) pp.base = (u32)(xa.k0 + kt * 2048);
       mt = __builtin_amdgcn_make_buffer_rsrc((void*)(a.mt + (size_t)kt * a.mt_rows * 64), 0, 0x7fffffff, 0x00020000);
     }
     for (i64 sidx = a.seg_begin + sl; sidx < a.seg_end; sidx += slices) {
@@ -635,16 +715,19 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(M
   exc_flush(bins, xa.lds_bins, xa.hist, threadIdx.x, 64 * kIeWaves);
 }
 
-#define EXC_IE_GEN(EXPR)                         \
+#define EXC_IE_GEN_(EXPR, PC)                    \
   if (method == 1) {                             \
-    if (planes <= 8) { EXPR(1, 8); }             \
-    else if (planes <= 12) { EXPR(1, 12); }      \
-    else { EXPR(1, 16); }                        \
+    if (planes <= 8) { EXPR(1, 8, PC); }         \
+    else if (planes <= 12) { EXPR(1, 12, PC); }  \
+    else { EXPR(1, 16, PC); }                    \
   } else {                                       \
-    if (planes <= 8) { EXPR(2, 8); }             \
-    else if (planes <= 12) { EXPR(2, 12); }      \
-    else { EXPR(2, 16); }                        \
+    if (planes <= 8) { EXPR(2, 8, PC); }         \
+    else if (planes <= 12) { EXPR(2, 12, PC); }  \
+    else { EXPR(2, 16, PC); }                    \
   }
+#define EXC_IE_GEN(EXPR)                         \
+  if (perm_counts) { EXC_IE_GEN_(EXPR, true) }   \
+  else { EXC_IE_GEN_(EXPR, false) }
 
 }  // namespace
 
@@ -652,6 +735,7 @@ hipError_t launch_exceed_dense(const ExceedArgs& a, int method, const NullConfig
   if (a.npaths <= 0 || a.K <= 0 || a.m <= 0) return hipSuccess;
   if ((int64_t)a.nkt * a.pgroups > 0x7fffffff || a.lds_bins > kExceedLdsBinsDense || (a.lds_bins != 0 && a.lds_bins != a.m))
     return hipErrorInvalidValue;
+  if (a.pc && (a.k0 < 0 || (int64_t)a.k0 + a.K > a.pc_stride)) return hipErrorInvalidValue;
   if (method == 1) {
     switch (cfg.R) {
       case 1: return launch_exceed_t<1, 1, 16, 8, 4>(a, stream);
@@ -678,22 +762,24 @@ hipError_t launch_exceed_observed(const ExceedObsArgs& a, int cus, hipStream_t s
 }
 
 hipError_t launch_exceed_ie(const IeArgs& a, int method, int planes, const uint32_t* pat, unsigned long long* hist, int m,
-                            int lds_bins, hipStream_t stream) {
+                            int lds_bins, hipStream_t stream, const ExceedPerm& perm) {
   if (a.seg_end <= a.seg_begin || a.K <= 0 || m <= 0) return hipSuccess;
   if (a.waves_per_xcd < kIeWaves || lds_bins > kExceedLdsBinsIe || (lds_bins != 0 && lds_bins != m)) return hipErrorInvalidValue;
-  const ExceedIeArgs xa{a, pat, hist, m, lds_bins};
+  const bool perm_counts = perm.pc != nullptr;
+  if (perm_counts && (perm.k0 < 0 || (int64_t)perm.k0 + a.K > perm.stride)) return hipErrorInvalidValue;
+  const ExceedIeArgs xa{a, pat, hist, m, lds_bins, perm.pc, perm.stride, perm.k0};
   const dim3 grid((unsigned)(8 * a.waves_per_xcd / kIeWaves));
   const dim3 block(64 * kIeWaves);
-#define EXC_LAUNCH(MM, LL) hipLaunchKernelGGL((k_exceed_ie<MM, LL>), grid, block, (size_t)lds_bins * 4, stream, xa)
+#define EXC_LAUNCH(MM, LL, PP) hipLaunchKernelGGL((k_exceed_ie<MM, LL, PP>), grid, block, (size_t)lds_bins * 4, stream, xa)
   EXC_IE_GEN(EXC_LAUNCH)
 #undef EXC_LAUNCH
   return hipGetLastError();
 }
 
-int exceed_ie_max_waves_per_cu(int method, int planes, int lds_bins) {
+int exceed_ie_max_waves_per_cu(int method, int planes, int lds_bins, bool perm_counts) {
   int blocks = 0;
   hipError_t e = hipSuccess;
-#define EXC_OCC(MM, LL) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, k_exceed_ie<MM, LL>, 64 * kIeWaves, (size_t)lds_bins * 4)
+#define EXC_OCC(MM, LL, PP) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, k_exceed_ie<MM, LL, PP>, 64 * kIeWaves, (size_t)lds_bins * 4)
   EXC_IE_GEN(EXC_OCC)
 #undef EXC_OCC
   if (e != hipSuccess || blocks < 1) blocks = 1;

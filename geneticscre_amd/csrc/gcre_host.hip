@@ -553,6 +553,10 @@ struct gcre_exceed {
   unsigned long long* d_hist = nullptr;    // [m] (path, permutation) pairs per bin
   unsigned long long* d_ohist = nullptr;   // [m] joined paths per bin
   int64_t perms = 0, paths = 0;       // permutations / joined paths that went into the bins
+  // per-permutation counts (gcre_exceed_keep_perm_counts): cell [bin][r] = values of permutation r in the bin
+  uint32_t* d_pc = nullptr;           // [m][pc_stride] u32, or nullptr: not kept
+  int pc_stride = 0;                  // the context's Kpad
+  std::vector<uint64_t> pc_load;      // per 2048-permutation tile: joined paths counted into its permutations' cells
 };
 
 namespace {
@@ -1544,6 +1548,21 @@ int count_exceed(gcre_ctx* c, const JoinPlan& jp, const ChunkBufs& b, int64_t s0
   }
   const int K = c->win_K;
   if (K <= 0) return GCRE_OK;
+  ExceedPerm perm;
+  if (x->d_pc) {
+    // a cell is 32 bits wide and takes at most one hit per joined path: refuse before the launch what could wrap it
+    const size_t t0 = (size_t)c->win_k0 / kPermTileMax, t1 = ((size_t)c->win_k0 + (size_t)K + kPermTileMax - 1) / kPermTileMax;
+    if (c->win_k0 + K > x->pc_stride || t1 > x->pc_load.size())
+      return fail(c, GCRE_ERR_ARG, "exceedance counts: the permutation window lies outside the per-permutation counts");
+    for (size_t t = t0; t < t1; t++)
+      if (x->pc_load[t] + (uint64_t)(s1 - s0) > 0xffffffffull)
+        return fail(c, GCRE_ERR_RANGE, "exceedance counts: more than 2^32-1 joined paths counted into one permutation's 32-bit cells: "
+                                       "read and reset the per-permutation counts first");
+    for (size_t t = t0; t < t1; t++) x->pc_load[t] += (uint64_t)(s1 - s0);
+    perm.pc = x->d_pc;
+    perm.stride = x->pc_stride;
+    perm.k0 = c->win_k0;
+  }
   if (std::getenv("GCRE_EXCEED_TRACE"))   // (tests: which form counted the chunk)
     std::fprintf(stderr, "[exceed] %s form: %lld joined paths x %d permutations, %d thresholds\n", ie ? "ie" : "dense",
                  (long long)(s1 - s0), K, x->m);
@@ -1555,9 +1574,9 @@ int count_exceed(gcre_ctx* c, const JoinPlan& jp, const ChunkBufs& b, int64_t s0
     xa.null_bits = nullptr;
     xa.stats = nullptr;
     xa.timing = nullptr;
-    const int wpc = std::min(c->sparse_waves_per_cu, exceed_ie_max_waves_per_cu(g.method, ie_planes, lds_bins));
+    const int wpc = std::min(c->sparse_waves_per_cu, exceed_ie_max_waves_per_cu(g.method, ie_planes, lds_bins, perm.pc != nullptr));
     xa.waves_per_xcd = std::min(ie->waves_per_xcd, xcd_waves(c, wpc));
-    HIP_TRY(c, launch_exceed_ie(xa, g.method, ie_planes, x->d_pat, x->d_hist, x->m, lds_bins, st));
+    HIP_TRY(c, launch_exceed_ie(xa, g.method, ie_planes, x->d_pat, x->d_hist, x->m, lds_bins, st, perm));
     return GCRE_OK;
   }
   const NullConfig cfg = null_config(g.method, K);
@@ -1584,6 +1603,9 @@ int count_exceed(gcre_ctx* c, const JoinPlan& jp, const ChunkBufs& b, int64_t s0
   a.pgroups = (int)std::min<int64_t>(std::max<int64_t>(1, want / a.nkt), a.npt);
   a.m = x->m;
   a.lds_bins = lds_bins;
+  a.pc = perm.pc;
+  a.pc_stride = perm.stride;
+  a.k0 = perm.k0;
   HIP_TRY(c, launch_exceed_dense(a, g.method, cfg, st));
   return GCRE_OK;
 }
@@ -4271,7 +4293,70 @@ int gcre_exceed_reset(gcre_exceed* x) {
   if (int rc = exceed_wait(c)) return rc;
   HIP_TRY(c, hipMemset(x->d_hist, 0, (size_t)x->m * 8));
   HIP_TRY(c, hipMemset(x->d_ohist, 0, (size_t)x->m * 8));
+  if (x->d_pc) HIP_TRY(c, hipMemset(x->d_pc, 0, (size_t)x->m * (size_t)x->pc_stride * 4));
+  std::fill(x->pc_load.begin(), x->pc_load.end(), 0);
   x->perms = x->paths = 0;
+  return GCRE_OK;
+}
+
+// 2^26 cells of 4 bytes: 256 MB
+static constexpr int64_t kExceedPermCells = (int64_t)1 << 26;
+
+int gcre_exceed_keep_perm_counts(gcre_exceed* x, int on) {
+  if (!x || !x->ctx) return GCRE_ERR_ARG;
+  gcre_ctx* c = x->ctx;
+  bool alive = false;
+  for (gcre_exceed* y : c->live_exceeds) alive = alive || y == x;
+  if (!alive) return fail(c, GCRE_ERR_ARG, "exceedance counts do not belong to this context");
+  if (int rc = exceed_wait(c)) return rc;
+  if (!on) {
+    if (x->d_pc) (void)hipFree(x->d_pc);
+    x->d_pc = nullptr;
+    x->pc_stride = 0;
+    x->pc_load.clear();
+    return GCRE_OK;
+  }
+  if (x->d_pc) return GCRE_OK;
+  if (x->perms != 0 || x->paths != 0)
+    return fail(c, GCRE_ERR_ARG, "exceedance counts: per-permutation counts cannot be switched on after something was counted (" +
+                                 std::to_string(x->perms) + " permutations, " + std::to_string(x->paths) + " joined paths): reset first");
+  const int64_t K = c->g.K;
+  if (K <= 0) return fail(c, GCRE_ERR_ARG, "exceedance counts: per-permutation counts need a context with permutations (it has 0 iterations)");
+  if ((int64_t)x->m * K > kExceedPermCells)
+    return fail(c, GCRE_ERR_ARG, "exceedance counts: per-permutation counts of " + std::to_string(x->m) + " thresholds x " + std::to_string(K) +
+                                 " iterations exceed the limit of 2^26 = 67108864 cells (256 MB)");
+  const size_t bytes = (size_t)x->m * (size_t)c->g.Kpad * 4;
+  hipError_t e = hipMalloc((void**)&x->d_pc, bytes);
+  if (e == hipSuccess) e = hipMemset(x->d_pc, 0, bytes);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    if (x->d_pc) (void)hipFree(x->d_pc);
+    x->d_pc = nullptr;
+    return fail(c, GCRE_ERR_DEVICE, std::string("exceedance counts: per-permutation counts: ") + hipGetErrorString(e));
+  }
+  x->pc_stride = c->g.Kpad;
+  x->pc_load.assign((size_t)(c->g.Kpad / kPermTileMax), 0);
+  return GCRE_OK;
+}
+
+int gcre_exceed_read_perm_counts(gcre_exceed* x, uint64_t* out) {
+  if (!x || !x->ctx) return GCRE_ERR_ARG;
+  gcre_ctx* c = x->ctx;
+  if (!x->d_pc) return fail(c, GCRE_ERR_ARG, "exceedance counts: the object keeps no per-permutation counts (gcre_exceed_keep_perm_counts)");
+  if (!out) return fail(c, GCRE_ERR_ARG, "exceedance counts: NULL output");
+  if (int rc = exceed_wait(c)) return rc;
+  const size_t m = (size_t)x->m, K = (size_t)c->g.K, stride = (size_t)x->pc_stride;
+  std::vector<uint32_t> h(m * stride);
+  HIP_TRY(c, hipMemcpy(h.data(), x->d_pc, m * stride * 4, hipMemcpyDeviceToHost));
+  std::vector<uint64_t> run(K, 0);
+  for (size_t j = m; j-- > 0;) {   // as gcre_exceed_read: a value in bin j reaches thresholds 0..j of the ascending order
+    const uint32_t* row = h.data() + j * stride;
+    uint64_t* dst = out + (size_t)x->order[j] * K;
+    for (size_t r = 0; r < K; r++) {
+      run[r] += row[r];
+      dst[r] = run[r];
+    }
+  }
   return GCRE_OK;
 }
 
@@ -4285,7 +4370,7 @@ void gcre_exceed_free(gcre_exceed* x) {
     auto& v = c->live_exceeds;
     v.erase(std::remove(v.begin(), v.end(), x), v.end());
   }
-  for (void* p : {(void*)x->d_pat, (void*)x->d_tkey, (void*)x->d_hist, (void*)x->d_ohist})
+  for (void* p : {(void*)x->d_pat, (void*)x->d_tkey, (void*)x->d_hist, (void*)x->d_ohist, (void*)x->d_pc})
     if (p) (void)hipFree(p);
   delete x;
 }

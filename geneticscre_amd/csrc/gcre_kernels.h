@@ -437,14 +437,24 @@ struct ExceedArgs {
   int nkt, pgroups;
   int m;
   int lds_bins;               // m (<= kExceedLdsBinsDense): per-block histogram in LDS; 0: straight into `hist`
+  // per-permutation counts; nullptr: none, and the kernels are the ones they were
+  uint32_t* pc;               // [m][pc_stride] cell [bin][k0 + r] += 1 with every value of window permutation r binned
+  int pc_stride;              // >= k0 + K
+  int k0;                     // absolute index of the window's first permutation
+};
+// the same three for the inclusion-exclusion form
+struct ExceedPerm {
+  uint32_t* pc = nullptr;
+  int stride = 0;
+  int k0 = 0;
 };
 hipError_t launch_exceed_dense(const ExceedArgs& a, int method, const NullConfig& cfg, hipStream_t stream);
 // The inclusion-exclusion form: the chunk's IeArgs as k_null_ie takes them (segments [seg_begin, seg_end), paths inside
 // [score_begin, score_end) count; planes_out, null_bits, stats, ladder, queue are not read), `planes` counter planes.
 // lds_bins: m (<= kExceedLdsBinsIe) or 0.
 hipError_t launch_exceed_ie(const IeArgs& a, int method, int planes, const uint32_t* pat, unsigned long long* hist, int m,
-                            int lds_bins, hipStream_t stream);
-int exceed_ie_max_waves_per_cu(int method, int planes, int lds_bins);
+                            int lds_bins, hipStream_t stream, const ExceedPerm& perm = ExceedPerm());
+int exceed_ie_max_waves_per_cu(int method, int planes, int lds_bins, bool perm_counts = false);
 struct ExceedObsArgs {
   const uint64_t* key;        // [count] score keys (0 = not a score: never counts)
   const uint64_t* tkey;       // [m] ascending threshold keys (>= 1)

@@ -13,6 +13,8 @@
                          (gcre_gene_tally; beyond the reference)
   * ``exceed_reference`` / ``fdr_columns``  null exceedance counts of a join in plain numpy, and the per-family error rate,
                          permutation FDR and q-values they give (gcre_exceed; beyond the reference)
+  * ``false_count_columns``  k-FWER, the median and the (1 - alpha) bound of the number of false positives, from the same
+                         counts kept per permutation
   * ``carrier_rows`` / ``overlap_reference`` / ``clump_rows`` / ``clump_paths``  which rows of a table are carried by the
                          same patients: pairwise carrier overlaps on the device (gcre_set_overlap), greedy clumping against
                          lead rows, and each row rescored without its lead's carriers (beyond the reference)
@@ -23,6 +25,7 @@ from __future__ import annotations
 
 import warnings
 from dataclasses import dataclass
+from fractions import Fraction
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -517,8 +520,8 @@ def _unpack_rows(rows, halves: int, n: int) -> np.ndarray:
 
 
 def exceed_reference(method, n_cases: int, n_ctrls: int, uids, rows0, rows1, value_table, masks, thresholds,
-                     shard: Optional[Tuple[int, int]] = None, window: Optional[Tuple[int, int]] = None
-                     ) -> Dict[str, object]:
+                     shard: Optional[Tuple[int, int]] = None, window: Optional[Tuple[int, int]] = None,
+                     per_permutation: bool = False) -> Dict[str, object]:
     """The definition of a join's exceedance counts in plain numpy -- what gcre_exceed must return, bit for bit.
 
     ``uids``: the join index (count / location / signs / path_length); ``rows0`` / ``rows1``: the packed rows of paths0 and
@@ -529,7 +532,12 @@ def exceed_reference(method, n_cases: int, n_ctrls: int, uids, rows0, rows1, val
     -- method 1: VT[c][tot - c] for c carriers among the mask's cases; method 2: vtmax[a][P - a] + vtmax[N - b][b] added in
     f64 --, rounded to f32, NaN and negatives as 0.  exceed[j] counts the (p, r) with (double)null >= thresholds[j] over the
     scored paths (``shard``) and the permutations of ``window``; observed[j] the scored paths whose observed score (above
-    -inf) is >= thresholds[j].  Returns {"exceed", "observed" (uint64), "perms", "paths", "scores" (f64 per scored path)}."""
+    -inf) is >= thresholds[j].  Returns {"exceed", "observed" (uint64), "perms", "paths", "scores" (f64 per scored path)}.
+
+    ``per_permutation``: the result also has "perm_counts", uint64 [m][K] over the window's K permutations (column r is
+    permutation window[0] + r), in the order of the thresholds given: perm_counts[j][r] counts the scored paths p with
+    (double)null[p][r] >= thresholds[j], from the same null matrix -- what gcre_exceed_read_perm_counts must return for those
+    permutations, exactly.  Every row sums to exceed[j]."""
     M = 1 if method in (1, "method1") else 2
     n = int(n_cases) + int(n_ctrls)
     VT = np.asarray(value_table, np.float64)
@@ -562,6 +570,7 @@ def exceed_reference(method, n_cases: int, n_ctrls: int, uids, rows0, rows1, val
     order = np.argsort(thr, kind="stable")
     ts = thr[order]
     exceed_sorted = np.zeros(len(thr), np.uint64)
+    perm_sorted = np.zeros((len(thr), K), np.uint64) if per_permutation else None
     scores = np.zeros(len(src), np.float64)
     step = max(1, int(4e6 // max(K, 1)), 1)
     step = min(step, 1 << 16)
@@ -585,11 +594,19 @@ def exceed_reference(method, n_cases: int, n_ctrls: int, uids, rows0, rows1, val
             null = _fold_f32(_vt_max(VT, n, a, tp[:, None] - a) + _vt_max(VT, n, tn[:, None] - b, b))
         v = np.sort(null.astype(np.float64).ravel())
         exceed_sorted += (len(v) - np.searchsorted(v, ts, side="left")).astype(np.uint64)
+        if per_permutation and null.size:
+            reached = np.searchsorted(ts, null.astype(np.float64), side="right")   # thresholds <= the value: 0 .. m
+            h = np.bincount((reached * K + np.arange(K)[None, :]).ravel(), minlength=(len(ts) + 1) * K).reshape(-1, K)
+            perm_sorted += np.cumsum(h[::-1], axis=0)[::-1][1:].astype(np.uint64)   # row j: values reaching more than j
     sc = np.sort(scores[scores > -np.inf])                               # (NaN compares false: not a score)
     observed_sorted = (len(sc) - np.searchsorted(sc, ts, side="left")).astype(np.uint64)
     exceed, observed = np.zeros(len(thr), np.uint64), np.zeros(len(thr), np.uint64)
     exceed[order], observed[order] = exceed_sorted, observed_sorted
-    return {"exceed": exceed, "observed": observed, "perms": K, "paths": len(src), "scores": scores}
+    out = {"exceed": exceed, "observed": observed, "perms": K, "paths": len(src), "scores": scores}
+    if per_permutation:
+        out["perm_counts"] = np.zeros((len(thr), K), np.uint64)
+        out["perm_counts"][order] = perm_sorted
+    return out
 
 
 def fdr_columns(thresholds, exceed, observed, perms: int) -> Dict[str, np.ndarray]:
@@ -612,6 +629,59 @@ def fdr_columns(thresholds, exceed, observed, perms: int) -> Dict[str, np.ndarra
     q = np.empty(len(t))
     q[order] = np.where(np.isnan(fdr[order]), np.nan, run)
     return {"ExpectedFalse": pfer, "FDR": fdr, "Qvalues": q}
+
+
+EXCEED_PERM_CELLS = 1 << 26   # api.EXCEED_PERM_CELLS: thresholds x permutations of one object's per-permutation counts
+
+
+def false_count_names(ks=(2, 5, 10)) -> List[str]:
+    """The columns of ``false_count_columns``, in order."""
+    return ["MedianFalse", "FDRmedian", "FalseBound", "FDPbound"] + [f"kFWER.{int(k)}" for k in ks]
+
+
+def false_count_columns(thresholds, perm_counts, observed, perms: int, ks=(2, 5, 10), alpha: float = 0.05
+                        ) -> Dict[str, np.ndarray]:
+    """Per threshold, in the order given, from V = ``perm_counts`` (uint64 [m][B]: V[j][r] = paths permutation r pushes to
+    threshold j or beyond; ``Exceedances.perm_counts``) and ``observed`` (paths whose observed score reaches it), B = ``perms``
+    = the number of permutations V's columns stand for:
+
+      MedianFalse   the ceil(B / 2)-th smallest of V[j][.]: the median number of false positives of a permutation
+      FDRmedian     min(1, MedianFalse / observed): SAM's FDR estimate
+      FalseBound    the ceil((1 - alpha) B)-th smallest (the rank is taken exactly, on alpha's shortest decimal form, and
+                    is at least 1): the count a permutation does not exceed with frequency >= 1 - alpha
+      FDPbound      min(1, FalseBound / observed): the same as a proportion of the rows at or above the threshold
+      kFWER.<k>     #{r : V[j][r] >= k} / B for every k of ``ks``: how often at least k paths reach the threshold
+
+    Everything is integer order statistics and one division: deterministic.  What they are: single-threshold permutation
+    quantiles under the complete null (every path null, pi0 = 1) -- the distribution over permutations whose mean is
+    ``fdr_columns``' ExpectedFalse.  What they are NOT: simultaneous over thresholds (reading the bound at the threshold
+    that looks best is a selection the bound does not cover), nor a confidence statement about this data set's false
+    discovery proportion when some paths are truly associated.  kFWER.1 is the ``Pvalues`` column (the family-wise p-value
+    from the null maxima, no identity permutation added).  NaN where ``fdr_columns`` gives NaN: B = 0 for every column,
+    observed = 0 for the two ratios.  Equal thresholds get equal rows."""
+    t = np.asarray(thresholds, np.float64).ravel()
+    m, B = len(t), int(perms)
+    o = np.asarray(observed, np.float64).ravel()
+    if not 0.0 <= float(alpha) <= 1.0:
+        raise ValueError(f"alpha must be in [0, 1], not {alpha}")
+    names = false_count_names(ks)
+    if B <= 0:
+        return {c: np.full(m, np.nan) for c in names}
+    V = np.asarray(perm_counts, np.uint64).reshape(m, -1)
+    if V.shape[1] != B:
+        raise ValueError(f"perm_counts has {V.shape[1]} permutations per threshold, perms says {B}")
+    Vs = np.sort(V, axis=1)
+    r_med = (B + 1) // 2                                                 # ceil(B / 2) >= 1
+    # ceil((1 - alpha) B) in exact arithmetic on the decimal alpha given, clamped into 1 .. B
+    f = (1 - Fraction(str(float(alpha)))) * B
+    r_bnd = min(B, max(1, -((-f.numerator) // f.denominator)))
+    med, bnd = Vs[:, r_med - 1].astype(np.float64), Vs[:, r_bnd - 1].astype(np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        out = {"MedianFalse": med, "FDRmedian": np.where(o > 0, np.minimum(1.0, med / o), np.nan),
+               "FalseBound": bnd, "FDPbound": np.where(o > 0, np.minimum(1.0, bnd / o), np.nan)}
+    for k in ks:
+        out[f"kFWER.{int(k)}"] = (V >= np.uint64(max(int(k), 0))).sum(axis=1).astype(np.float64) / B
+    return out
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -947,7 +1017,8 @@ def gwaspa(genes: Sequence[str], data: np.ndarray, n_cases: int, n_ctrls: int, n
            threshold: float = 0.05, top_k: int = 10, path_length: int = 5, n_permutations: int = 100,
            strata: Optional[Sequence[int]] = None, seed: int = 0, device: int = 0,
            decorated_pvalues: bool = False, gene_table: bool = False, fdr: bool = False,
-           clump: Optional[float] = None, clump_conditional: bool = False) -> Dict[str, object]:
+           clump: Optional[float] = None, clump_conditional: bool = False, false_counts: bool = False,
+           false_count_ks: Sequence[int] = (2, 5, 10), false_count_alpha: float = 0.05) -> Dict[str, object]:
     """GWASPA (R/ProcessPaths.R:87-344) without R: dataset -> GWASPA.Results, scored on the MI355X.
 
     ``network`` = (ents_uid, ents_symbol, rel_src, rel_trg, rel_sign): the knowledge base getStringKB() would load
@@ -972,6 +1043,14 @@ def gwaspa(genes: Sequence[str], data: np.ndarray, n_cases: int, n_ctrls: int, n
     api.Exceedances).  Sentinel rows get NaN.  The row order and the other seven columns are what ``fdr=False`` returns.
     Default False.
 
+    ``false_counts``: the same counting pass is made (whether or not ``fdr`` is set) with counters that keep the counts per
+    permutation (``api.ExceedCounts(perm_counts=True)``), and GWASPA.Results gains the columns of
+    ``false_count_columns(ks=false_count_ks, alpha=false_count_alpha)``: "MedianFalse", "FDRmedian", "FalseBound",
+    "FDPbound" and "kFWER.<k>" -- single-threshold permutation quantiles under the complete null, not simultaneous over
+    rows.  The raw arrays come back in "exceed" (``Exceedances.perm_counts``); ``fdr``'s own three columns appear only with
+    ``fdr=True``.  ``top_k * n_permutations`` above 2^26 raises ValueError before anything runs; ``n_permutations == 0`` adds
+    NaN columns.  Sentinel rows get NaN.  Default False: nothing new is called.
+
     ``clump``: with a value r, GWASPA.Results goes through ``clump_paths(r=clump, conditional=clump_conditional)`` with the
     run's own seed, strata, threshold and permutation count: it gains ``CLUMP_COLUMNS`` -- which rows are
     carried by the same patients as a better row -- and with ``clump_conditional`` ``RESIDUAL_COLUMNS``, each row rescored
@@ -984,6 +1063,9 @@ def gwaspa(genes: Sequence[str], data: np.ndarray, n_cases: int, n_ctrls: int, n
 
     method = "method2" if signed else "method1"
     check_input(n_cases, n_ctrls, method, threshold, top_k, path_length, n_permutations)
+    if false_counts and int(top_k) * int(n_permutations) > EXCEED_PERM_CELLS:
+        raise ValueError(f"false_counts: top_k x n_permutations = {int(top_k) * int(n_permutations)} exceeds the limit of "
+                         f"2^26 = {EXCEED_PERM_CELLS} per-permutation cells of a level")
     genes, data = preprocess_table(genes, data, threshold, n_cases, n_ctrls)
     prep = prepare_inputs(genes, data, *network)
     g = len(prep.ents_uid)
@@ -1015,12 +1097,16 @@ def gwaspa(genes: Sequence[str], data: np.ndarray, n_cases: int, n_ctrls: int, n
     out = {"GWASPA.Results": results_table(lsts, path_length, frames,
                                            (prep.ents_uid, prep.ents_symbol), (prep.ents2_uid, prep.ents2_symbol)),
            "levels": lsts, "prepared": prep}
-    if fdr:
+    if fdr or false_counts:
+        keep = bool(false_counts) and n_permutations > 0
+        fc_names = false_count_names(false_count_ks) if false_counts else []
+        new_cols = (FDR_COLUMNS if fdr else []) + fc_names
         counters = {}
         for L, name in enumerate(GENE_LEVELS[:path_length], start=1):
             s = np.asarray(lsts[f"lst{L}"].scores, np.float64)
             if np.isfinite(s).any():
-                counters[name] = api.ExceedCounts(ex, s[np.isfinite(s)])
+                counters[name] = api.ExceedCounts(ex, s[np.isfinite(s)], perm_counts=True) if keep else \
+                    api.ExceedCounts(ex, s[np.isfinite(s)])
         if counters:
             api.process_paths(problem, device=device, exec_=ex, exceeds=counters)
         df = out["GWASPA.Results"]
@@ -1030,12 +1116,15 @@ def gwaspa(genes: Sequence[str], data: np.ndarray, n_cases: int, n_ctrls: int, n
                 continue
             got = counters[name].read()
             out["exceed"][L] = got
-            cols = fdr_columns(counters[name].thresholds, got.exceed, got.observed, got.perms)
+            cols = fdr_columns(counters[name].thresholds, got.exceed, got.observed, got.perms) if fdr else {}
+            if false_counts:
+                cols.update(false_count_columns(counters[name].thresholds, got.perm_counts, got.observed, got.perms,
+                                                ks=false_count_ks, alpha=false_count_alpha))
             for i, t in enumerate(counters[name].thresholds.tolist()):
-                lookup[(L, t)] = tuple(cols[c][i] for c in FDR_COLUMNS)
+                lookup[(L, t)] = tuple(cols[c][i] for c in new_cols)
             counters[name].free()
-        rows = [lookup.get((int(L), float(sc)), (np.nan,) * 3) for L, sc in zip(df["Lengths"], df["Scores"])]
-        for k, c in enumerate(FDR_COLUMNS):
+        rows = [lookup.get((int(L), float(sc)), (np.nan,) * len(new_cols)) for L, sc in zip(df["Lengths"], df["Scores"])]
+        for k, c in enumerate(new_cols):
             df[c] = np.array([r[k] for r in rows], np.float64)
     if gene_table:
         best = {L + 1: tallies[name].read() for L, name in enumerate(GENE_LEVELS[:path_length])}

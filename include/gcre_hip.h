@@ -529,6 +529,21 @@ int gcre_exceed_read(gcre_exceed* x, uint64_t* exceed, uint64_t* observed, int64
 int gcre_exceed_reset(gcre_exceed* x);   /* all counts back to zero */
 void gcre_exceed_free(gcre_exceed* x);   /* gcre_destroy frees the ones still alive */
 
+/* Per-permutation counts: next to exceed[j], the distribution over the permutations it is the sum of,
+ *   V[j][r] = #{p scored by the join : (double)null[p][r] >= thresholds[j]},   r = 0 .. iterations-1 (absolute, whatever
+ * the permutation window), from which report.false_count_columns takes k-FWER, the median and the (1 - alpha) bound of the
+ * number of false positives.  on != 0 allocates and zeroes the device array (u32 [m][iterations rounded up to 2048]);
+ * 0 frees it.  GCRE_ERR_ARG with a message: after anything was counted into x (gcre_exceed_reset lifts this), a context
+ * with 0 iterations, m x iterations above 2^26 (256 MB of cells), an object of another (or a destroyed) context.  Counts
+ * add as exceed does: shards cell by cell, windows fill disjoint ranges, a join counted twice is counted twice.  A cell is
+ * 32 bits wide: a count that would take the joined paths counted into one permutation's cells past 2^32-1 is refused before
+ * any launch with GCRE_ERR_RANGE (reset first).  An object without them launches exactly what it launched before. */
+int gcre_exceed_keep_perm_counts(gcre_exceed* x, int on);
+/* Waits for what is in flight.  out: [m][iterations], row j in the order of the thresholds given; equal thresholds get
+ * equal rows; permutations no counted join's window covered read 0; every row sums to exceed[j].  GCRE_ERR_ARG when x
+ * keeps no per-permutation counts. */
+int gcre_exceed_read_perm_counts(gcre_exceed* x, uint64_t* out /* [m][iterations] */);
+
 #ifdef __cplusplus
 }
 #endif
