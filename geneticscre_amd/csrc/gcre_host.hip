@@ -350,6 +350,7 @@ struct gcre_ctx {
   bool mt_stale = false;             // d_masks changed while the sparse kernel was off: d_mt (if any) holds older masks
   int ieq_batch = 0;                 // GCRE_IEQ_BATCH: quads per ticket of the quad kernel (0: twice ie_batch)
   int ie_quad = 1;                   // GCRE_IE_QUAD=0: the pruned method-1 launches stay on k_null_ie_m1 (cross-check)
+  int ie_zwide = 0;                  // GCRE_IE_ZWIDE=1: the quad kernel reaches every added row through a descriptor of its own (tests)
   int ie_warm_items = 4;             // (segment, tile) items per wave of the warm-up launch (GCRE_IE_WARM_ITEMS)
   int exchange_tail = 0;             // slices of the pruned launch that are equal steps at its end (GCRE_EXCHANGE_TAIL; -1: half of them; 0: doubling slices only)
   int ie_warm_segs = 1024;           // least number of segments in the warm-up slice (GCRE_IE_WARM; 2048 until round 3: the filter's second look made early thresholds matter less)
@@ -2517,8 +2518,12 @@ int launch_ie_slices(JoinRun& R, const ChunkRun& C, IeArgs& ia, int planes, int6
       ia.quads = seg_entry->d_quads;
       ia.quad_begin = seg_entry->quad_begin;
       ia.quad_end = seg_entry->nquads;
+      // an added row's planes are a 32-bit byte offset from the tile's first row wherever a tile of them stays below 4 GiB
+      const uint64_t z_units = (uint64_t)ia.rowsz * (uint64_t)ia.gz;
+      ia.z_wide = (c->ie_zwide || z_units >= (1ull << 22)) ? 1u : 0u;
+      ia.z_tile_units = ia.z_wide ? 0u : (uint32_t)z_units;
       ia.batch = c->ieq_batch > 0 ? c->ieq_batch : std::max(1, c->ie_batch * 2);   // quads per ticket: the headers of a ticket's quads are fetched one ahead
-      const int wq = std::min(c->sparse_waves_per_cu, ieq_max_waves_per_cu(planes, ia.gz, ia.rec_slot != nullptr));
+      const int wq = std::min(c->sparse_waves_per_cu, ieq_max_waves_per_cu(planes, ia.gz, ia.rec_slot != nullptr, ia.z_wide != 0u));
       ia.waves_per_xcd = spread_waves(xcd_waves(c, wq), n * ie_tile_factor, 128);
     }
   }
@@ -3085,6 +3090,7 @@ gcre_ctx* gcre_create(int method, int n_cases, int n_ctrls, int iterations, int 
   if (const char* e = std::getenv("GCRE_IE_BATCH")) c->ie_batch = std::min(std::max(std::atoi(e), 1), 4096);
   if (const char* e = std::getenv("GCRE_IEQ_BATCH")) c->ieq_batch = std::max(0, std::atoi(e));
   if (const char* e = std::getenv("GCRE_IE_QUAD")) c->ie_quad = std::min(std::max(std::atoi(e), 0), 2);   // 2: wherever it can run
+  if (const char* e = std::getenv("GCRE_IE_ZWIDE")) c->ie_zwide = std::atoi(e) != 0;
   if (const char* e = std::getenv("GCRE_PLANES_OUT_MAX_MB")) c->planes_out_max = (size_t)std::max(0ll, std::atoll(e)) << 20;
   if (const char* e = std::getenv("GCRE_SPARSE_WAVES_PER_CU")) c->sparse_waves_per_cu = std::max(1, std::atoi(e));
 

@@ -8,9 +8,11 @@
 //
 // tested against the pruning ladder's interval [lo, hi] of the path's table diagonal; only what falls outside is looked
 // up (methods.h:96-103).  With the bound filter (W = N0 + Nz against [lo + ov, hi], see k_null_ie_m1) nine path-tiles in
-// ten never read a mask row, and what is left of k_null_ie_m1's vector-memory traffic is dominated by the two 1-KB plane
-// loads of the added row per path-tile: the kernel is bound by the CU's vector-memory pipe at ~20 clocks per wave-load
-// (tools/row_gather_rate.hip), not by VALU issue and not by bytes.
+// ten never read a mask row.  What binds the kernel is instruction issue: neither HBM nor latency -- a
+// section's time follows its instruction count, vector, scalar and read-lane alike.  Faster = fewer instructions per
+// path-tile: 63 of them are the filter's arithmetic, the rest is control, addressing and scalar-spill traffic, which is
+// why the filter pass is one of three loops chosen once per quad and an added row costs one read-lane to address
+// (tools/isa_count.py counts a build's instructions per loop).
 //
 // All uids with the same pivot gene join the same paths1 rows (the join index gives them the same location and count), so
 // their segments walk the same sequence of added rows.  The host groups up to kQSegs such segments into a "quad" (the name stayed from the four-segment form)
@@ -18,6 +20,8 @@
 // t of the shared sequence, loads Nz[z_t] once and scores path t of each segment against it: the plane loads per
 // path-tile drop from 2 to 0.5, the instruction stream per path-tile is unchanged.
 #include "gcre_ie_common.h"
+
+#include <type_traits>
 
 namespace gcre {
 
@@ -45,7 +49,17 @@ constexpr int kQSegs = GCRE_QSEGS;
 #define GCRE_QT_ADD(i, t1, t0)
 #endif
 
-template <int L, int GZ, bool REC>
+// `count` is one of 1..N: calls f with it as a compile-time constant
+template <int N, class F>
+__device__ __forceinline__ void with_count(u32 count, F&& f) {
+  if constexpr (N > 1) {
+    if (count != (u32)N) return with_count<N - 1>(count, f);
+  }
+  f(std::integral_constant<int, N>{});
+}
+
+// WIDE: one tile of the added rows' planes does not fit a 32-bit byte offset (IeArgs::z_wide)
+template <int L, int GZ, bool REC, bool WIDE>
 __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(GCRE_QWAVES))) void k_null_ie_q(const IeArgs a) {
   constexpr int LP = (L + 3) / 4 * 4;
   constexpr int LZ = 4 * GZ;
@@ -83,6 +97,7 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(G
   const u32 k_lad_mode = uni((u32)a.lad_mode), k_score_segs = uni(a.score_segs);
   const char* k_mt = uni_ptr(a.mt);
   const char* k_planesz = uni_ptr(a.planesz);
+  const u32 k_ztile = uni(a.z_tile_units);
 
   int cur_kt = -1;
   u32 valid = 0u;
@@ -94,9 +109,10 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(G
   const u64 tm_begin = __builtin_amdgcn_s_memtime();
 #endif
   __amdgpu_buffer_rsrc_t mt = __builtin_amdgcn_make_buffer_rsrc((void*)k_mt, 0, 0x7fffffff, 0x00020000);
+  // the planes of the rows the joins add, one descriptor per tile: a row is then a scalar byte offset into it (the
+  // scalar offset takes no part in the range check).  WIDE builds a descriptor per row instead.
+  __amdgpu_buffer_rsrc_t zt = __builtin_amdgcn_make_buffer_rsrc((void*)k_planesz, 0, 0x7fffffff, 0x00020000);
 
-  // publish the wave's maxima, read everybody's, set the threshold level to the smallest running maximum of the tile's
-  // live permutations (a stale read only lowers it: still exact)
   // publish the wave's maxima, read everybody's, set the threshold level to the smallest running maximum of the tile's
   // live permutations (a stale read only lowers it: still exact).  The merged values stay in LDS: nm[] is then the best
   // maximum this wave KNOWS of every permutation of the tile (its own finds + the others' as of the last exchange), which
@@ -155,6 +171,7 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(G
       flush_tile();
       cur_kt = kt;
       mt = __builtin_amdgcn_make_buffer_rsrc((void*)(k_mt + (size_t)kt * k_mt_rows * 256u), 0, 0x7fffffff, 0x00020000);
+      if constexpr (!WIDE) zt = __builtin_amdgcn_make_buffer_rsrc((void*)(k_planesz + (u64)kt * (u64)k_ztile * 1024u), 0, 0x7fffffff, 0x00020000);
       const int live = (int)k_K - kt * 2048 - lane * 32;
       valid = live >= 32 ? 0xffffffffu : (live <= 0 ? 0u : ((1u << live) - 1u));
       if (k_lad_mode == 0u) lad_base = 0u;
@@ -200,7 +217,6 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(G
       const u32 qcnt = (qe >> 30) + 1u;
       const u32 s0 = qe & 0x3fffffffu;
       const u32 npaths = rdlane(hdr[0], 2);
-      const u32 last = npaths - 1u;
       GCRE_QT(te0);
       if (k_lad_mode == 0u && ++since >= period) {
         exchange();
@@ -215,13 +231,17 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(G
       u32 infov[kQSegs], lhv[kQSegs], lfv[kQSegs], firstg[kQSegs];
       u32 B[kQSegs][L];
       u32 zunit = 0u;
-      auto load_groups = [&](u32 (&P)[LP], const u32* planes, u64 unit, int groups) {
+      // (P holds L or LP planes: the base counters are loaded in place, what a group has above L is dropped)
+      auto load_groups = [&](auto& P, const u32* planes, u64 unit, int groups) {
+        constexpr int NP = (int)(sizeof(P) / sizeof(u32));
         __amdgpu_buffer_rsrc_t rp = __builtin_amdgcn_make_buffer_rsrc((void*)(uni_ptr(planes) + unit * 1024u), 0, 0x7fffffff, 0x00020000);
 #pragma unroll
         for (int j = 0; j < LP / 4; j++) {
           u32x4 v = {0u, 0u, 0u, 0u};
           if (j < groups) v = __builtin_amdgcn_raw_buffer_load_b128(rp, lane4 * 4u + (u32)j * 1024u, 0, 0);
-          P[4 * j + 0] = v.x; P[4 * j + 1] = v.y; P[4 * j + 2] = v.z; P[4 * j + 3] = v.w;
+#pragma unroll
+          for (int i = 0; i < 4; i++)
+            if (4 * j + i < NP) P[4 * j + i] = v[i];
         }
       };
       // (a) everything the quad's segments need from memory goes out together: their paths' metadata, the planes their
@@ -240,16 +260,18 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(G
           const u32 qv = first + (((u32)lane < npaths) ? (u32)lane : 0u);
           infov[g] = a.linfo[qv];
           totv[g] = a.tot[qv];
-          if (g == 0) zunit = ((u32)kt * (u32)a.rowsz + (a.rowz[qv] & 0x7fffffffu)) * (u32)a.gz;   // the same for every segment of the quad
+          if (g == 0) {   // the same for every segment of the quad: 1-KB units from planesz, or bytes from the tile's first row
+            if constexpr (WIDE) zunit = ((u32)kt * (u32)a.rowsz + (a.rowz[qv] & 0x7fffffffu)) * (u32)a.gz;
+            else zunit = ((a.rowz[qv] & 0x7fffffffu) * (u32)a.gz) << 10;
+          }
         }
       }
 #pragma unroll
       for (int g = 0; g < kQSegs; g++) {
         if ((u32)g < qcnt) {
           const u32 row0 = rdlane(hdr[g], 0);
-          u32 Bp[LP];
           if constexpr (!REC) {
-            load_groups(Bp, a.planes0, ((u64)kt * (u64)a.rows0 + (u64)row0) * (u64)a.g0, a.g0);
+            load_groups(B[g], a.planes0, ((u64)kt * (u64)a.rows0 + (u64)row0) * (u64)a.g0, a.g0);
           } else {
             // the segment's recipe words sit next to the segment table (k_fill_rec_segs): paths0 row of the producing
             // join, row it added, list info, where a long list continues, the list's first 8 entries
@@ -269,10 +291,8 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(G
             // the row's carrier total bounds the counts of everything it was made from: planes above it are zero and are
             // not read (3 KB -> 2 KB of HBM per segment and tile for most rows: this load is the kernel's HBM traffic)
             const int ga_need = (int)linfo_groups(rinfo_g[g]) + 1;
-            load_groups(Bp, a.rec_planes_a, ((u64)kt * (u64)a.rec_rows_a + (u64)ra) * (u64)a.rec_ga, ga_need < a.rec_ga ? ga_need : a.rec_ga);
+            load_groups(B[g], a.rec_planes_a, ((u64)kt * (u64)a.rec_rows_a + (u64)ra) * (u64)a.rec_ga, ga_need < a.rec_ga ? ga_need : a.rec_ga);
           }
-#pragma unroll
-          for (int l = 0; l < L; l++) B[g][l] = Bp[l];
         }
       }
       if (have_next) load_hdr(qe_n, hdr_n);
@@ -356,15 +376,20 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(G
       GCRE_QT(t3);
       GCRE_QT_ADD(2, t3, t2);
       const u32x8 GCRE_CONSTANT* slots = (const u32x8 GCRE_CONSTANT*)a.dlist;
-      auto issue = [&](u32 t2, u32 (&ZZ)[LZ]) {
-        __amdgpu_buffer_rsrc_t rz = __builtin_amdgcn_make_buffer_rsrc((void*)(k_planesz + (u64)rdlane(zunit, t2) * 1024u), 0, 0x7fffffff, 0x00020000);
+      // (zu = rdlane(zunit, position): the filter pass reads it one step ahead, a scalar that comes out of a read-lane
+      // cannot address a load in the next few cycles)
+      auto issue_at = [&](u32 zu, u32 (&ZZ)[LZ]) {
+        __amdgpu_buffer_rsrc_t rz = zt;
+        u32 so = 0u;
+        if constexpr (WIDE) rz = __builtin_amdgcn_make_buffer_rsrc((void*)(k_planesz + (u64)zu * 1024u), 0, 0x7fffffff, 0x00020000);
+        else so = zu;
 #pragma unroll
         for (int j = 0; j < GZ; j++) {
-          const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rz, lane4 * 4u + (u32)j * 1024u, 0, 0);
+          const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rz, lane4 * 4u + (u32)j * 1024u, so, 0);
           ZZ[4 * j + 0] = v.x; ZZ[4 * j + 1] = v.y; ZZ[4 * j + 2] = v.z; ZZ[4 * j + 3] = v.w;
         }
       };
-      auto at = [&](u32 t2) -> u32 { return t2 < last ? t2 : last; };
+      auto issue = [&](u32 t2, u32 (&ZZ)[LZ]) { issue_at(rdlane(zunit, t2), ZZ); };
 
       // ---- first pass: the bound filter.  Path t of segment g against the planes Z of the row the quad's segments all
       // add: W = B_g + Z is inside [lo + ov, hi] for every live permutation <=> no count of the path can raise a maximum
@@ -372,9 +397,6 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(G
       // marked, one bit per path in a scalar mask per segment: nothing in this loop waits for anything but the planes.
       u64 todo[kQSegs] = {};
       auto filter_f = [&](int g, u32 t, const u32 (&Bg)[L], const u32 (&Z)[LZ]) {
-        // rows of another shard (the ladder's all-inside row): nothing of theirs is scored, so nothing is examined -- neither
-        // a carry out of the top plane nor a delta list may send such a path to the second look or the exact pass
-        if (lad_row == lad_keep) return;
         const u32 lf = rdlane(lfv[g], t);   // hi << 16 | lo + ov
         u32 cy = 0u, blo = 0u, bhi = 0u;
 #pragma unroll
@@ -445,22 +467,40 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(G
         todo[g] |= 1ull << t;
       };
 
-      // the planes of the next added row are in flight while up to four paths are tested against the current one
-      {
-        u32 ZA[LZ], ZB[LZ];
-        issue(0u, ZA);
-        for (u32 t = 0; t < npaths; t += 2) {
-          issue(at(t + 1), ZB);
+      // The pass is decided once per quad.  Rows of another shard (the ladder's all-inside row) skip it with its loads:
+      // nothing of theirs is scored, so nothing is examined -- neither a carry out of the top plane nor a delta list may
+      // send such a path to the second look or the exact pass.  (No launch has such quads today: segments outside the
+      // scored range exist only for rows that get count planes, and those joins stay on k_null_ie_m1.)  Every other
+      // quad takes the loop made for its number of
+      // segments.  The planes of the next added row are in flight while the quad's paths are tested against the current
+      // one; the last one or two positions are peeled, so that no row is requested twice and every iteration of the
+      // loop has the same loads in flight.
+      if (lad_row != lad_keep && npaths != 0u) {
+        with_count<kQSegs>(qcnt, [&](auto ns) {
+          u32 ZA[LZ], ZB[LZ];
+          auto position = [&](u32 t, const u32 (&Z)[LZ]) {
 #pragma unroll
-          for (int g = 0; g < kQSegs; g++)
-            if ((u32)g < qcnt) filter_f(g, t, B[g], ZA);
-          if (t + 1 < npaths) {
-            issue(at(t + 2), ZA);
-#pragma unroll
-            for (int g = 0; g < kQSegs; g++)
-              if ((u32)g < qcnt) filter_f(g, t + 1, B[g], ZB);
+            for (int g = 0; g < decltype(ns)::value; g++) filter_f(g, t, B[g], Z);
+          };
+          issue(0u, ZA);
+          u32 zu = rdlane(zunit, 1u);   // (a lane past the quad's last path is read and not used)
+          u32 t = 0u;
+          for (; t + 2u < npaths; t += 2u) {
+            issue_at(zu, ZB);
+            zu = rdlane(zunit, t + 2u);
+            position(t, ZA);
+            issue_at(zu, ZA);
+            zu = rdlane(zunit, t + 3u);
+            position(t + 1u, ZB);
           }
-        }
+          if (t + 1u < npaths) {
+            issue_at(zu, ZB);
+            position(t, ZA);
+            position(t + 1u, ZB);
+          } else {
+            position(t, ZA);
+          }
+        });
       }
 
       GCRE_QT(t4);
@@ -618,7 +658,8 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(G
   if (a.stats && lane == 0 && n_slow) atomicAdd(a.stats, n_slow);
 }
 
-#define GCRE_IEQ_R(EXPR, LL, GG) if (rec) { EXPR(LL, GG, true); } else { EXPR(LL, GG, false); }
+#define GCRE_IEQ_W(EXPR, LL, GG, RR) if (wide) { EXPR(LL, GG, RR, true); } else { EXPR(LL, GG, RR, false); }
+#define GCRE_IEQ_R(EXPR, LL, GG) if (rec) { GCRE_IEQ_W(EXPR, LL, GG, true) } else { GCRE_IEQ_W(EXPR, LL, GG, false) }
 
 #ifdef GCRE_IEQ_ONLY   // quick builds while tuning: one variant
 #define GCRE_IEQ(EXPR) { (void)gz; (void)planes; GCRE_IEQ_R(EXPR, 10, 2) }
@@ -643,8 +684,8 @@ hipError_t launch_null_ie_quad(const IeArgs& a, int planes, hipStream_t stream) 
   const dim3 grid((unsigned)(8 * a.waves_per_xcd / kIeWaves));
   const dim3 block(64 * kIeWaves);
   const int gz = a.gz;
-  const bool rec = a.rec_slot != nullptr;
-#define GCRE_LAUNCHQ(LL, GG, RR) hipLaunchKernelGGL((k_null_ie_q<LL, GG, RR>), grid, block, 0, stream, a)
+  const bool rec = a.rec_slot != nullptr, wide = a.z_wide != 0u;
+#define GCRE_LAUNCHQ(LL, GG, RR, WW) hipLaunchKernelGGL((k_null_ie_q<LL, GG, RR, WW>), grid, block, 0, stream, a)
   GCRE_IEQ(GCRE_LAUNCHQ)
 #undef GCRE_LAUNCHQ
   return hipGetLastError();
@@ -652,10 +693,10 @@ hipError_t launch_null_ie_quad(const IeArgs& a, int planes, hipStream_t stream) 
 
 int ieq_quad_segs() { return kQSegs; }
 
-int ieq_max_waves_per_cu(int planes, int gz, bool rec) {
+int ieq_max_waves_per_cu(int planes, int gz, bool rec, bool wide) {
   int blocks = 0;
   hipError_t e = hipSuccess;
-#define GCRE_OCCQ(LL, GG, RR) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, k_null_ie_q<LL, GG, RR>, 64 * kIeWaves, 0)
+#define GCRE_OCCQ(LL, GG, RR, WW) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, k_null_ie_q<LL, GG, RR, WW>, 64 * kIeWaves, 0)
   GCRE_IEQ(GCRE_OCCQ)
 #undef GCRE_OCCQ
   if (e != hipSuccess || blocks < 1) blocks = 1;

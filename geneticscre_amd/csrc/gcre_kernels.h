@@ -160,9 +160,12 @@ struct IeArgs {
   // consecutive segments of `segs` that join the same paths1 rows
   const uint32_t* quads;
   int64_t quad_begin, quad_end;
+  // the added rows' planes in the quad kernel: rowsz * gz, the 1-KB units of one tile; z_wide: a tile of them is 4 GiB
+  // or more (or GCRE_IE_ZWIDE=1), a row is then reached through a descriptor of its own instead of a 32-bit byte offset
+  uint32_t z_tile_units, z_wide;
 };
 hipError_t launch_null_ie_quad(const IeArgs& a, int planes, hipStream_t stream);   // gcre_ieq.hip
-int ieq_max_waves_per_cu(int planes, int gz, bool rec);
+int ieq_max_waves_per_cu(int planes, int gz, bool rec, bool wide);
 int ieq_quad_segs();   // segments a quad may hold (gcre_ieq.hip)
 // r_tot (optional): carriers of the recipe's rows; bits 1-2 of the gathered list-info word then say how many groups of 4
 // count planes of the row can be non-zero, minus one (counts never exceed the carrier total)
