@@ -134,6 +134,7 @@ EXPORTS = [
     "gcre_exceed_create", "gcre_join_set_exceed", "gcre_process_paths_set_exceed", "gcre_exceed_read",
     "gcre_exceed_reset", "gcre_exceed_free",
     "gcre_exceed_keep_perm_counts", "gcre_exceed_read_perm_counts",
+    "gcre_exceed_stepdown", "gcre_stepdown_launches",
 ]
 
 
@@ -398,6 +399,18 @@ def _perm_counts_lib():
     return lib
 
 
+def _stepdown_lib():
+    """The same with the step-down entries bound, on first use."""
+    lib = _perm_counts_lib()
+    if not hasattr(lib, "gcre_exceed_stepdown") or not hasattr(lib, "gcre_stepdown_launches"):
+        raise GcreError(f"{lib._name} has no step-down counts (gcre_exceed_stepdown): rebuild it")
+    if lib.gcre_exceed_stepdown.argtypes is None:
+        lib.gcre_exceed_stepdown.argtypes = [ctypes.c_void_p, ctypes.POINTER(gcre_set_input), ctypes.c_void_p]
+        lib.gcre_stepdown_launches.restype = ctypes.c_int64
+        lib.gcre_stepdown_launches.argtypes = [ctypes.c_void_p]
+    return lib
+
+
 EXCEED_MAX = 10000   # kExceedMax: thresholds of one ExceedCounts (the top_k limit)
 EXCEED_PERM_CELLS = 1 << 26   # thresholds x iterations of an ExceedCounts that keeps per-permutation counts (256 MB of u32 cells)
 
@@ -450,6 +463,22 @@ class ExceedCounts:
             self._owner._check(self._lib.gcre_exceed_read_perm_counts(self._h, _ptr(pc)))
         return Exceedances(exceed, observed, int(perms.value), int(paths.value), pc)
 
+    def stepdown(self, sets, rows, signs=None) -> np.ndarray:
+        """Step-down max-T counts (gcre_exceed_stepdown) of an object that keeps per-permutation counts and
+        holds exactly one full pass of one join.  ``sets`` / ``rows`` / ``signs`` as ``JoinExec.score_sets`` takes them, one set
+        per threshold, in the thresholds' order: set j is the joined path whose observed score is threshold j (the library
+        refuses a set whose score is not its threshold, bit for bit).  Returns int64 [m]: n_ge[j] = the permutations whose
+        maximum null value over the join's paths, the rows with a strictly larger threshold left out, reaches threshold j.
+        ``report.stepdown_columns`` turns them into ``PvaluesStepDown``.  The object is not changed."""
+        lib = _stepdown_lib()
+        inp, keep = _set_input(sets, rows, signs, self._owner.num_cases + self._owner.num_ctrls)
+        n_ge = np.zeros(len(self.thresholds), dtype=np.int64)
+        rc = lib.gcre_exceed_stepdown(self._h, ctypes.byref(inp), _ptr(n_ge))
+        del keep
+        if rc != GCRE_OK:                  # (as score_sets: every refusal is a GcreError with the library's message)
+            raise GcreError(self._lib.gcre_last_error(self._owner._h).decode())
+        return n_ge
+
     def reset(self) -> None:
         self._owner._check(self._lib.gcre_exceed_reset(self._h))
 
@@ -463,6 +492,28 @@ class ExceedCounts:
             self.free()
         except Exception:
             pass
+
+
+def _set_input(sets, rows, signs, n: int):
+    """gcre_set_input of ``JoinExec.score_sets``' arguments, and the arrays it points into (keep them alive for the call)."""
+    S = len(sets)
+    lens = [len(s) for s in sets]
+    off = np.zeros(S + 1, dtype=np.int64)
+    off[1:] = np.cumsum(lens)
+    members = np.ascontiguousarray(np.concatenate([np.asarray(s, dtype=np.int64).reshape(-1) for s in sets])
+                                   if S else np.zeros(0), dtype=np.int32)
+    sg = None
+    if signs is not None:
+        if len(signs) != S or any(len(x) != L for x, L in zip(signs, lens)):
+            raise ValueError("signs: one sign per member of every set")
+        sg = np.ascontiguousarray(np.concatenate([np.asarray(x, dtype=np.int64).reshape(-1) for x in signs])
+                                  if S else np.zeros(0), dtype=np.int32)
+    d = np.asarray(rows)
+    if d.ndim != 2:
+        d = d.reshape(-1, n)
+    packed = pack_carriers(d, d.shape[1])
+    inp = gcre_set_input(S, _ptr(off), _ptr(members), _ptr(sg), _ptr(packed), packed.shape[0], d.shape[1])
+    return inp, (off, members, sg, packed)
 
 
 def pack_carriers(rows, n_cols: int) -> np.ndarray:
@@ -825,6 +876,10 @@ class JoinExec:
         if rc != GCRE_OK:
             raise GcreError(self._lib.gcre_last_error(self._h).decode())
         return size, both
+
+    def stepdown_launches(self) -> int:
+        """k_stepdown_null / k_stepdown_finish launches of this context so far."""
+        return int(_stepdown_lib().gcre_stepdown_launches(self._h))
 
     def overlap_launches(self) -> int:
         """k_set_overlap launches of this context so far."""

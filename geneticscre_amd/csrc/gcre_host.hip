@@ -337,6 +337,7 @@ struct gcre_ctx {
   int null_blocks_per_cu = 12;
   int cus = 256;                     // compute units of the device (read once at gcre_create)
   int64_t overlap_launches = 0;      // k_set_overlap launches of this context (gcre_overlap_launches)
+  int64_t stepdown_launches = 0;     // k_stepdown_null / k_stepdown_finish launches of this context (gcre_stepdown_launches)
 
   // resident inputs
   uint64_t* d_case_mask = nullptr;   // [Wp]
@@ -549,6 +550,7 @@ struct gcre_exceed {
   gcre_ctx* ctx = nullptr;
   int m = 0;
   std::vector<int32_t> order;         // sorted position -> the caller's index
+  std::vector<double> thr;            // the thresholds as given (gcre_exceed_stepdown compares scores with them)
   uint32_t* d_pat = nullptr;          // [m] ascending
   uint64_t* d_tkey = nullptr;         // [m] ascending
   unsigned long long* d_hist = nullptr;    // [m] (path, permutation) pairs per bin
@@ -3504,25 +3506,22 @@ static uint32_t f32_threshold(double score) {
   return b;
 }
 
-int gcre_score_sets(gcre_ctx* c, const gcre_set_input* in, gcre_set_score* out, int64_t cap, int64_t* n_out,
-                    float* family_max) {
-  if (!c) return GCRE_ERR_ARG;
-  if (!in || !n_out || cap < 0 || (cap > 0 && !out)) return fail(c, GCRE_ERR_ARG, "score_sets: NULL argument");
-  *n_out = 0;
+// What gcre_score_sets refuses of a set list, before anything is launched (`who` opens the message): the context's state,
+// the shape of the input, every set's members and signs.
+static int check_sets(gcre_ctx* c, const gcre_set_input* in, const std::string& who) {
   const Geometry& g = c->g;
-  const int K = g.K, M = g.method;
-  if (!c->have_table || !c->d_dvt) return fail(c, GCRE_ERR_ASSERT, "assertion: score_sets needs a value table");
-  if (K > 0 && !c->have_perms)
-    return fail(c, GCRE_ERR_ASSERT, "assertion: score_sets needs the permutation masks (iterations > 0, none set)");
+  if (!c->have_table || !c->d_dvt) return fail(c, GCRE_ERR_ASSERT, "assertion: " + who + " needs a value table");
+  if (g.K > 0 && !c->have_perms)
+    return fail(c, GCRE_ERR_ASSERT, "assertion: " + who + " needs the permutation masks (iterations > 0, none set)");
   if (in->n_cols != g.n)
-    return fail(c, GCRE_ERR_ARG, "score_sets: the rows have " + std::to_string(in->n_cols) +
+    return fail(c, GCRE_ERR_ARG, who + ": the rows have " + std::to_string(in->n_cols) +
                                      " columns, not n_cases + n_ctrls = " + std::to_string(g.n));
   const int64_t S = in->n_sets;
   if (S < 0 || in->n_rows < 0 || (S > 0 && (!in->set_off || !in->members)) || (in->n_rows > 0 && !in->rows))
-    return fail(c, GCRE_ERR_ARG, "score_sets: bad input (a negative count or a NULL array)");
+    return fail(c, GCRE_ERR_ARG, who + ": bad input (a negative count or a NULL array)");
   for (int64_t s = 0; s < S; s++) {
     const int64_t b = in->set_off[s], e = in->set_off[s + 1];
-    const std::string name = "score_sets: set " + std::to_string(s);
+    const std::string name = who + ": set " + std::to_string(s);
     if (b < 0 || e <= b) return fail(c, GCRE_ERR_ARG, name + " has no members");
     for (int64_t i = b; i < e; i++) {
       const int32_t row = in->members[i];
@@ -3533,6 +3532,50 @@ int gcre_score_sets(gcre_ctx* c, const gcre_set_input* in, gcre_set_score* out, 
         return fail(c, GCRE_ERR_ARG, name + ": sign " + std::to_string(in->signs[i]) + " is neither +1 nor -1");
     }
   }
+  return GCRE_OK;
+}
+
+// The host stage gcre_score_sets and gcre_exceed_stepdown share: the case / control masks of the n patients, and one set's
+// union rows -- P = the OR of its (+) members, N = P + Wp the OR of its (-) members (method 1: everything into P), within the
+// n patients -- with k = cases_pos, ctrls_pos, cases_neg, ctrls_neg.  `P` holds M * Wp zeroed words; no member is NA.
+struct SetUnion {
+  const Geometry& g;
+  std::vector<uint64_t> cases, ctrls;
+  explicit SetUnion(const Geometry& geo) : g(geo), cases((size_t)geo.W, 0), ctrls((size_t)geo.W, 0) {
+    for (int q = 0; q < g.n; q++) (q < g.n_cases ? cases : ctrls)[(size_t)q / 64] |= uint64_t(1) << (q % 64);
+  }
+  int count_and(const uint64_t* a, const std::vector<uint64_t>& m) const {
+    int n = 0;
+    for (int w = 0; w < g.W; w++) n += __builtin_popcountll(a[w] & m[w]);
+    return n;
+  }
+  void build(const gcre_set_input* in, int64_t s, uint64_t* P, int32_t k[4]) const {
+    const int W = g.W, M = g.method;
+    uint64_t* N = M == 2 ? P + g.Wp : P;
+    for (int64_t i = in->set_off[s]; i < in->set_off[s + 1]; i++) {
+      const uint64_t* r = in->rows + (size_t)in->members[i] * W;
+      uint64_t* d = (M == 2 && in->signs && in->signs[i] == -1) ? N : P;
+      for (int w = 0; w < W; w++) d[w] |= r[w] & (cases[w] | ctrls[w]);
+    }
+    k[0] = count_and(P, cases);
+    k[1] = count_and(P, ctrls);
+    k[2] = k[3] = 0;
+    if (M == 2) {
+      k[2] = count_and(N, ctrls);   // the (-) half counts the other way round (methods.h:183-184)
+      k[3] = count_and(N, cases);
+    }
+  }
+};
+
+int gcre_score_sets(gcre_ctx* c, const gcre_set_input* in, gcre_set_score* out, int64_t cap, int64_t* n_out,
+                    float* family_max) {
+  if (!c) return GCRE_ERR_ARG;
+  if (!in || !n_out || cap < 0 || (cap > 0 && !out)) return fail(c, GCRE_ERR_ARG, "score_sets: NULL argument");
+  *n_out = 0;
+  const Geometry& g = c->g;
+  const int K = g.K, M = g.method;
+  const int64_t S = in->n_sets;
+  if (int rc = check_sets(c, in, "score_sets")) return rc;
   *n_out = S;
   if (S > cap)
     return fail(c, GCRE_ERR_RANGE, "score_sets: " + std::to_string(S) + " sets, room for " + std::to_string(cap) +
@@ -3540,15 +3583,9 @@ int gcre_score_sets(gcre_ctx* c, const gcre_set_input* in, gcre_set_score* out, 
 
   // the host stage: per valid set the OR of its (+) members and of its (-) members (method 1: of all of them), within the
   // n patients, and their counts; the device rows are [valid set][M][Wp] words, the dword view k_set_null reads
-  const int W = g.W, Wp = g.Wp;
+  const int Wp = g.Wp;
   const size_t RW = (size_t)M * Wp;
-  std::vector<uint64_t> cases((size_t)W, 0), ctrls((size_t)W, 0);
-  for (int q = 0; q < g.n; q++) (q < g.n_cases ? cases : ctrls)[(size_t)q / 64] |= uint64_t(1) << (q % 64);
-  auto count_and = [W](const uint64_t* a, const std::vector<uint64_t>& m) {
-    int n = 0;
-    for (int w = 0; w < W; w++) n += __builtin_popcountll(a[w] & m[w]);
-    return n;
-  };
+  const SetUnion un(g);
   const double nan = std::numeric_limits<double>::quiet_NaN();
   std::vector<int64_t> vset;     // the valid sets, in input order
   std::vector<uint64_t> urows;
@@ -3568,24 +3605,17 @@ int gcre_score_sets(gcre_ctx* c, const gcre_set_input* in, gcre_set_score* out, 
     const size_t v = vset.size();
     vset.push_back(s);
     urows.resize((v + 1) * RW, 0);
-    uint64_t* P = urows.data() + v * RW;
-    uint64_t* N = M == 2 ? P + Wp : P;
-    for (int64_t i = b; i < e; i++) {
-      const uint64_t* r = in->rows + (size_t)in->members[i] * W;
-      uint64_t* d = (M == 2 && in->signs && in->signs[i] == -1) ? N : P;
-      for (int w = 0; w < W; w++) d[w] |= r[w] & (cases[w] | ctrls[w]);
-    }
-    o.cases_pos = count_and(P, cases);
-    o.ctrls_pos = count_and(P, ctrls);
-    if (M == 2) {
-      o.cases_neg = count_and(N, ctrls);   // the (-) half counts the other way round (methods.h:183-184)
-      o.ctrls_neg = count_and(N, cases);
-    }
+    int32_t k[4];
+    un.build(in, s, urows.data() + v * RW, k);
+    o.cases_pos = k[0];
+    o.ctrls_pos = k[1];
+    o.cases_neg = k[2];
+    o.ctrls_neg = k[3];
     o.cases = o.cases_pos + o.cases_neg;
     o.ctrls = o.ctrls_pos + o.ctrls_neg;
-    cnt.insert(cnt.end(), {o.cases_pos, o.ctrls_pos, o.cases_neg, o.ctrls_neg});
-    tot.push_back((uint32_t)(o.cases_pos + o.ctrls_pos));
-    if (M == 2) tot.push_back((uint32_t)(o.cases_neg + o.ctrls_neg));
+    cnt.insert(cnt.end(), k, k + 4);
+    tot.push_back((uint32_t)(k[0] + k[1]));
+    if (M == 2) tot.push_back((uint32_t)(k[2] + k[3]));
   }
   if (family_max) std::fill(family_max, family_max + K, 0.0f);
   const int64_t V = (int64_t)vset.size();
@@ -4213,6 +4243,7 @@ gcre_exceed* gcre_exceed_create(gcre_ctx* c, const double* thresholds, int32_t m
   gcre_exceed* x = new gcre_exceed();
   x->ctx = c;
   x->m = m;
+  x->thr.assign(thresholds, thresholds + m);
   x->order.resize((size_t)m);
   for (int32_t i = 0; i < m; i++) x->order[(size_t)i] = i;
   std::stable_sort(x->order.begin(), x->order.end(), [&](int32_t a, int32_t b) { return thresholds[a] < thresholds[b]; });
@@ -4365,6 +4396,133 @@ int gcre_exceed_read_perm_counts(gcre_exceed* x, uint64_t* out) {
   }
   return GCRE_OK;
 }
+
+// Step-down max-T.  Set j is the joined path whose observed score is threshold j: its null values, found
+// in the bins of the thresholds strictly below it, are what the join's per-permutation counts hold too many of once the
+// better rows are taken out of the family.
+int gcre_exceed_stepdown(gcre_exceed* x, const gcre_set_input* in, int64_t* n_ge) {
+  if (!x || !x->ctx) return GCRE_ERR_ARG;
+  gcre_ctx* c = x->ctx;
+  bool alive = false;
+  for (gcre_exceed* y : c->live_exceeds) alive = alive || y == x;
+  if (!alive) return fail(c, GCRE_ERR_ARG, "exceedance counts do not belong to this context");
+  if (!in || !n_ge) return fail(c, GCRE_ERR_ARG, "stepdown: NULL argument");
+  if (!x->d_pc)
+    return fail(c, GCRE_ERR_ARG, "stepdown: the object keeps no per-permutation counts (gcre_exceed_keep_perm_counts)");
+  const Geometry& g = c->g;
+  const int K = g.K, M = g.method, m = x->m;
+  if (x->perms != K || x->paths <= 0)
+    return fail(c, GCRE_ERR_ARG, "stepdown: the object must hold exactly one full pass of one join (" + std::to_string(x->perms) +
+                                     " permutations of " + std::to_string(x->paths) + " joined paths counted, the context has " +
+                                     std::to_string(K) + " iterations)");
+  if (in->n_sets != m)
+    return fail(c, GCRE_ERR_ARG, "stepdown: " + std::to_string(in->n_sets) + " sets for " + std::to_string(m) + " thresholds");
+  for (int j = 0; j < m; j++)
+    if (!std::isfinite(x->thr[(size_t)j])) return fail(c, GCRE_ERR_ARG, "stepdown: threshold " + std::to_string(j) + " is not finite");
+  if (int rc = check_sets(c, in, "stepdown")) return rc;
+  for (int64_t s = 0; s < m; s++)
+    for (int64_t i = in->set_off[s]; i < in->set_off[s + 1]; i++)
+      if (in->members[i] < 0) return fail(c, GCRE_ERR_ARG, "stepdown: set " + std::to_string(s) + " has an NA member");
+  if (int rc = exceed_wait(c)) return rc;
+
+  // the host stage of gcre_score_sets: per set its union rows and counts
+  const int Wp = g.Wp;
+  const size_t RW = (size_t)M * Wp;
+  const SetUnion un(g);
+  std::vector<uint64_t> urows((size_t)m * RW, 0);
+  std::vector<int32_t> cnt((size_t)m * 4, 0);   // cases_pos, ctrls_pos, cases_neg, ctrls_neg
+  std::vector<uint32_t> tot((size_t)m * M);
+  for (int64_t s = 0; s < m; s++) {
+    int32_t* k = cnt.data() + 4 * s;
+    un.build(in, s, urows.data() + (size_t)s * RW, k);
+    tot[(size_t)s * M] = (uint32_t)(k[0] + k[1]);
+    if (M == 2) tot[(size_t)s * M + 1] = (uint32_t)(k[2] + k[3]);
+  }
+  // cap[j] = the last sorted index strictly below threshold j (compared as f64: tied rows do not exclude one another)
+  std::vector<int32_t> cap((size_t)m);
+  for (int b = 0, first = 0; b < m; b++) {
+    if (x->thr[(size_t)x->order[(size_t)b]] > x->thr[(size_t)x->order[(size_t)first]]) first = b;
+    cap[(size_t)x->order[(size_t)b]] = first - 1;
+  }
+
+  (void)hipSetDevice(c->device);
+  const size_t stride = (size_t)x->pc_stride, cells = (size_t)m * stride;
+  uint64_t* d_rows = nullptr;
+  int32_t *d_cnt = nullptr, *d_cap = nullptr;
+  uint32_t *d_tot = nullptr, *d_E = nullptr, *d_out = nullptr;   // d_out: n_ge per sorted threshold, then the bad counter
+  double* d_obs = nullptr;
+  std::vector<double> obs((size_t)m);
+  std::vector<uint32_t> got((size_t)m + 1, 0);
+  hipError_t e = hipMalloc((void**)&d_rows, urows.size() * 8);
+  if (e == hipSuccess) e = hipMalloc((void**)&d_cnt, cnt.size() * 4);
+  if (e == hipSuccess) e = hipMalloc((void**)&d_tot, tot.size() * 4);
+  if (e == hipSuccess) e = hipMalloc((void**)&d_cap, (size_t)m * 4);
+  if (e == hipSuccess) e = hipMalloc((void**)&d_obs, (size_t)m * 8);
+  if (e == hipSuccess) e = hipMalloc((void**)&d_out, ((size_t)m + 1) * 4);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_rows, urows.data(), urows.size() * 8, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_cnt, cnt.data(), cnt.size() * 4, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_tot, tot.data(), tot.size() * 4, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_cap, cap.data(), (size_t)m * 4, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = launch_set_observed(d_cnt, m, M, c->d_dvt, d_obs, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(obs.data(), d_obs, (size_t)m * 8, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  int64_t off_set = -1;   // the first set whose observed score is not its threshold, bit for bit
+  for (int64_t s = 0; e == hipSuccess && s < m && off_set < 0; s++)
+    if (std::memcmp(&obs[(size_t)s], &x->thr[(size_t)s], 8) != 0) off_set = s;
+  if (e == hipSuccess && off_set < 0) {
+    e = hipMalloc((void**)&d_E, cells * 4);
+    if (e == hipSuccess) e = hipMemsetAsync(d_E, 0, cells * 4, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(d_out, 0, ((size_t)m + 1) * 4, c->stream);
+    StepdownArgs a{};
+    a.rows = (const uint32_t*)d_rows;
+    a.masks = c->d_masks;
+    a.tot = d_tot;
+    a.t32 = c->d_t32;
+    a.d64 = c->d_dmax;
+    a.d64n = c->d_dmaxn ? c->d_dmaxn : c->d_dmax;
+    a.pat = x->d_pat;
+    a.cap = d_cap;
+    a.E = d_E;
+    a.nsets = m;
+    a.W32p = 2 * Wp;
+    a.Kpad = g.Kpad;
+    a.K = K;
+    a.nkt = (K + kSetPermTile - 1) / kSetPermTile;
+    const int64_t tpb = set_null_tile_sets(M);
+    a.npt = (m + tpb - 1) / tpb;
+    const int64_t slots = (int64_t)c->cus * 4 * 8;   // gcre_score_sets' rule
+    const int64_t per = std::max<int64_t>(1, (a.npt * a.nkt) / slots);
+    a.pgroups = (int)std::min<int64_t>((a.npt + per - 1) / per, 0x7fffffff / std::max(a.nkt, 1));
+    a.m = m;
+    a.stride = (int)stride;
+    const StepdownFinishArgs f{x->d_pc, d_E, d_out, d_out + m, m, (int)stride, K};
+    if (e == hipSuccess) e = launch_stepdown_null(a, M, c->stream);
+    if (e == hipSuccess) c->stepdown_launches++;
+    if (e == hipSuccess) e = launch_stepdown_finish(f, c->stream);
+    if (e == hipSuccess) c->stepdown_launches++;
+    if (e == hipSuccess) e = hipMemcpyAsync(got.data(), d_out, ((size_t)m + 1) * 4, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  }
+  for (void* p : {(void*)d_rows, (void*)d_cnt, (void*)d_tot, (void*)d_cap, (void*)d_obs, (void*)d_out, (void*)d_E})
+    if (p) (void)hipFree(p);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(c, GCRE_ERR_DEVICE, std::string("stepdown: ") + hipGetErrorString(e));
+  }
+  if (off_set >= 0) {
+    char buf[256];
+    std::snprintf(buf, sizeof buf, ": its observed score is %.17g, threshold %lld is %.17g (the rows must be the rows the thresholds came from)",
+                  obs[(size_t)off_set], (long long)off_set, x->thr[(size_t)off_set]);
+    return fail(c, GCRE_ERR_ARG, "stepdown: set " + std::to_string(off_set) + buf);
+  }
+  if (got[(size_t)m] != 0)
+    return fail(c, GCRE_ERR_ASSERT, "assertion: stepdown: the sets are not distinct joined paths of the counted join (" +
+                                        std::to_string(got[(size_t)m]) + " permutations count more top rows than joined paths at a threshold)");
+  for (int b = 0; b < m; b++) n_ge[(size_t)x->order[(size_t)b]] = (int64_t)got[(size_t)b];
+  return GCRE_OK;
+}
+
+int64_t gcre_stepdown_launches(const gcre_ctx* c) { return c ? c->stepdown_launches : -1; }
 
 void gcre_exceed_free(gcre_exceed* x) {
   if (!x) return;

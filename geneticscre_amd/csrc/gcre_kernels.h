@@ -468,6 +468,34 @@ struct ExceedObsArgs {
 };
 hipError_t launch_exceed_observed(const ExceedObsArgs& a, int cus, hipStream_t stream);
 
+// ---- step-down max-T counts of a level's top rows (gcre_stepdown.hip) ----
+// k_set_null's launch geometry (set_null_tile_sets sets per tile, kSetPermTile permutations per block) over the top rows.
+struct StepdownArgs {
+  const uint32_t* rows;         // [nsets][M][W32p] union rows, as SetNullArgs
+  const uint32_t* masks;        // [W32p][Kpad]
+  const uint32_t* tot;          // [nsets][M] carriers per half
+  const float* t32;
+  const double* d64;
+  const double* d64n;
+  const uint32_t* pat;          // [m] ascending f32 bit patterns (gcre_exceed)
+  const int32_t* cap;           // [nsets] the last sorted index strictly below the set's own threshold (f64), -1: none
+  uint32_t* E;                  // [m][stride] zero on entry: cell [bin][r] += 1, bin = min(the value's bin, cap)
+  int64_t nsets;
+  int64_t npt;
+  int W32p, Kpad, K;
+  int nkt, pgroups;
+  int m, stride;                // stride >= K
+};
+hipError_t launch_stepdown_null(const StepdownArgs& a, int method, hipStream_t stream);
+struct StepdownFinishArgs {
+  const uint32_t* pc;           // [m][stride] the join's per-permutation counts per bin
+  const uint32_t* E;            // [m][stride]
+  uint32_t* n_ge;               // [m] zero on entry: permutations r < K with V[b][r] > E[b][r], per sorted threshold
+  uint32_t* bad;                // [1] zero on entry: permutations with E > V in some bin
+  int m, stride, K;
+};
+hipError_t launch_stepdown_finish(const StepdownFinishArgs& a, hipStream_t stream);
+
 // ---- carrier-overlap counts of caller-given sets (gcre_overlap.hip) ----
 constexpr int kOverlapTile = 64;    // pairs per edge of a block's tile
 constexpr int kOverlapChunk = 32;   // dwords of a row per staged chunk (128 bytes): rows are padded to a multiple of it

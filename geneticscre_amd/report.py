@@ -15,6 +15,8 @@
                          permutation FDR and q-values they give (gcre_exceed; beyond the reference)
   * ``false_count_columns``  k-FWER, the median and the (1 - alpha) bound of the number of false positives, from the same
                          counts kept per permutation
+  * ``stepdown_reference`` / ``stepdown_columns``  step-down max-T p-values of a level's top rows: each row against the
+                         null maxima of the paths that are not better rows (gcre_exceed_stepdown)
   * ``carrier_rows`` / ``overlap_reference`` / ``clump_rows`` / ``clump_paths``  which rows of a table are carried by the
                          same patients: pairwise carrier overlaps on the device (gcre_set_overlap), greedy clumping against
                          lead rows, and each row rescored without its lead's carriers (beyond the reference)
@@ -519,31 +521,22 @@ def _unpack_rows(rows, halves: int, n: int) -> np.ndarray:
     return np.ascontiguousarray(np.moveaxis(bits, 1, 0)).astype(bool)
 
 
-def exceed_reference(method, n_cases: int, n_ctrls: int, uids, rows0, rows1, value_table, masks, thresholds,
-                     shard: Optional[Tuple[int, int]] = None, window: Optional[Tuple[int, int]] = None,
-                     per_permutation: bool = False) -> Dict[str, object]:
-    """The definition of a join's exceedance counts in plain numpy -- what gcre_exceed must return, bit for bit.
+def _n_masks(masks, n: int, window=None) -> int:
+    """The permutations ``_join_null_blocks`` walks for these masks and this window."""
+    mk = np.asarray(masks)
+    K = (mk.size // n if mk.dtype == bool else len(mk.reshape(len(mk), -1))) if mk.size else 0
+    return len(range(K)[window[0]:window[1]]) if window is not None else K
 
-    ``uids``: the join index (count / location / signs / path_length); ``rows0`` / ``rows1``: the packed rows of paths0 and
-    paths1 (uint64 [rows][method * W]: the (+) half, then for the signed method the (-) half); ``masks``: the permutations'
-    case masks, packed uint64 [K][W] or bool [K][n]; ``thresholds``: any order.  Joined path p = (uid row i, paths1 row
-    location[i] + j) is paths0[i] | paths1[..], the added row's halves swapped when the signed method's relation is not
-    positive (UidRelSet::need_flip).  Per permutation r its null value is the f32 the null kernels fold into their maxima
-    -- method 1: VT[c][tot - c] for c carriers among the mask's cases; method 2: vtmax[a][P - a] + vtmax[N - b][b] added in
-    f64 --, rounded to f32, NaN and negatives as 0.  exceed[j] counts the (p, r) with (double)null >= thresholds[j] over the
-    scored paths (``shard``) and the permutations of ``window``; observed[j] the scored paths whose observed score (above
-    -inf) is >= thresholds[j].  Returns {"exceed", "observed" (uint64), "perms", "paths", "scores" (f64 per scored path)}.
 
-    ``per_permutation``: the result also has "perm_counts", uint64 [m][K] over the window's K permutations (column r is
-    permutation window[0] + r), in the order of the thresholds given: perm_counts[j][r] counts the scored paths p with
-    (double)null[p][r] >= thresholds[j], from the same null matrix -- what gcre_exceed_read_perm_counts must return for those
-    permutations, exactly.  Every row sums to exceed[j]."""
+def _join_null_blocks(method, n_cases: int, n_ctrls: int, uids, rows0, rows1, value_table, masks,
+                      shard: Optional[Tuple[int, int]] = None, window: Optional[Tuple[int, int]] = None):
+    """The null matrix of a join in blocks of joined paths, as ``exceed_reference`` states it: yields
+    (lo, src, trg, scores, null) per block -- the block's first scored path, its (uid row, paths1 row) pairs, the observed
+    scores (f64) and null[p][r] (f32 [paths][K], the value the null kernels fold into their maxima).  An empty join yields
+    nothing."""
     M = 1 if method in (1, "method1") else 2
     n = int(n_cases) + int(n_ctrls)
     VT = np.asarray(value_table, np.float64)
-    thr = np.asarray(thresholds, np.float64).ravel()
-    if np.isnan(thr).any():
-        raise ValueError("a threshold is NaN")
     mk = np.asarray(masks)
     if mk.dtype != bool:
         mk = _unpack_rows(mk, 1, n)[0] if mk.size else np.zeros((0, n), bool)
@@ -567,11 +560,6 @@ def exceed_reference(method, n_cases: int, n_ctrls: int, uids, rows0, rows1, val
         sg = signs[src] if L > 3 else signs[trg] if L < 3 else np.where(signs[src] + signs[trg] == 0, -1, 1)
         keep = sg == 1
     case = np.arange(n) < int(n_cases)
-    order = np.argsort(thr, kind="stable")
-    ts = thr[order]
-    exceed_sorted = np.zeros(len(thr), np.uint64)
-    perm_sorted = np.zeros((len(thr), K), np.uint64) if per_permutation else None
-    scores = np.zeros(len(src), np.float64)
     step = max(1, int(4e6 // max(K, 1)), 1)
     step = min(step, 1 << 16)
     for lo in range(0, len(src), step):
@@ -579,7 +567,7 @@ def exceed_reference(method, n_cases: int, n_ctrls: int, uids, rows0, rows1, val
         if M == 1:
             bp = r0[0][s_] | r1[0][t_]
             tot = bp.sum(axis=1)
-            scores[lo:lo + step] = _vt_cell(VT, n, (bp & case).sum(axis=1), (bp & ~case).sum(axis=1))
+            scores = _vt_cell(VT, n, (bp & case).sum(axis=1), (bp & ~case).sum(axis=1))
             a = (bp.astype(np.float32) @ mf.T).astype(np.int64)            # exact: counts < 2^24
             null = _fold_f32(_vt_cell(VT, n, a, tot[:, None] - a))
         else:
@@ -587,22 +575,57 @@ def exceed_reference(method, n_cases: int, n_ctrls: int, uids, rows0, rows1, val
             bp = r0[0][s_] | np.where(k_, r1[0][t_], r1[1][t_])
             bn = r0[1][s_] | np.where(k_, r1[1][t_], r1[0][t_])
             tp, tn = bp.sum(axis=1), bn.sum(axis=1)
-            scores[lo:lo + step] = (_vt_cell(VT, n, (bp & case).sum(axis=1), (bp & ~case).sum(axis=1)) +
-                                    _vt_cell(VT, n, (bn & ~case).sum(axis=1), (bn & case).sum(axis=1)))
+            scores = (_vt_cell(VT, n, (bp & case).sum(axis=1), (bp & ~case).sum(axis=1)) +
+                      _vt_cell(VT, n, (bn & ~case).sum(axis=1), (bn & case).sum(axis=1)))
             a = (bp.astype(np.float32) @ mf.T).astype(np.int64)
             b = (bn.astype(np.float32) @ mf.T).astype(np.int64)
             null = _fold_f32(_vt_max(VT, n, a, tp[:, None] - a) + _vt_max(VT, n, tn[:, None] - b, b))
+        yield lo, s_, t_, scores, null.reshape(len(s_), K)
+
+
+def exceed_reference(method, n_cases: int, n_ctrls: int, uids, rows0, rows1, value_table, masks, thresholds,
+                     shard: Optional[Tuple[int, int]] = None, window: Optional[Tuple[int, int]] = None,
+                     per_permutation: bool = False) -> Dict[str, object]:
+    """The definition of a join's exceedance counts in plain numpy -- what gcre_exceed must return, bit for bit.
+
+    ``uids``: the join index (count / location / signs / path_length); ``rows0`` / ``rows1``: the packed rows of paths0 and
+    paths1 (uint64 [rows][method * W]: the (+) half, then for the signed method the (-) half); ``masks``: the permutations'
+    case masks, packed uint64 [K][W] or bool [K][n]; ``thresholds``: any order.  Joined path p = (uid row i, paths1 row
+    location[i] + j) is paths0[i] | paths1[..], the added row's halves swapped when the signed method's relation is not
+    positive (UidRelSet::need_flip).  Per permutation r its null value is the f32 the null kernels fold into their maxima
+    -- method 1: VT[c][tot - c] for c carriers among the mask's cases; method 2: vtmax[a][P - a] + vtmax[N - b][b] added in
+    f64 --, rounded to f32, NaN and negatives as 0.  exceed[j] counts the (p, r) with (double)null >= thresholds[j] over the
+    scored paths (``shard``) and the permutations of ``window``; observed[j] the scored paths whose observed score (above
+    -inf) is >= thresholds[j].  Returns {"exceed", "observed" (uint64), "perms", "paths", "scores" (f64 per scored path)}.
+
+    ``per_permutation``: the result also has "perm_counts", uint64 [m][K] over the window's K permutations (column r is
+    permutation window[0] + r), in the order of the thresholds given: perm_counts[j][r] counts the scored paths p with
+    (double)null[p][r] >= thresholds[j], from the same null matrix -- what gcre_exceed_read_perm_counts must return for those
+    permutations, exactly.  Every row sums to exceed[j]."""
+    thr = np.asarray(thresholds, np.float64).ravel()
+    if np.isnan(thr).any():
+        raise ValueError("a threshold is NaN")
+    K = _n_masks(masks, int(n_cases) + int(n_ctrls), window)
+    order = np.argsort(thr, kind="stable")
+    ts = thr[order]
+    exceed_sorted = np.zeros(len(thr), np.uint64)
+    perm_sorted = np.zeros((len(thr), K), np.uint64) if per_permutation else None
+    parts = []
+    for _lo, _s, _t, sc_, null in _join_null_blocks(method, n_cases, n_ctrls, uids, rows0, rows1, value_table, masks,
+                                                     shard, window):
+        parts.append(sc_)
         v = np.sort(null.astype(np.float64).ravel())
         exceed_sorted += (len(v) - np.searchsorted(v, ts, side="left")).astype(np.uint64)
         if per_permutation and null.size:
             reached = np.searchsorted(ts, null.astype(np.float64), side="right")   # thresholds <= the value: 0 .. m
             h = np.bincount((reached * K + np.arange(K)[None, :]).ravel(), minlength=(len(ts) + 1) * K).reshape(-1, K)
             perm_sorted += np.cumsum(h[::-1], axis=0)[::-1][1:].astype(np.uint64)   # row j: values reaching more than j
+    scores = np.concatenate(parts).astype(np.float64) if parts else np.zeros(0, np.float64)
     sc = np.sort(scores[scores > -np.inf])                               # (NaN compares false: not a score)
     observed_sorted = (len(sc) - np.searchsorted(sc, ts, side="left")).astype(np.uint64)
     exceed, observed = np.zeros(len(thr), np.uint64), np.zeros(len(thr), np.uint64)
     exceed[order], observed[order] = exceed_sorted, observed_sorted
-    out = {"exceed": exceed, "observed": observed, "perms": K, "paths": len(src), "scores": scores}
+    out = {"exceed": exceed, "observed": observed, "perms": K, "paths": len(scores), "scores": scores}
     if per_permutation:
         out["perm_counts"] = np.zeros((len(thr), K), np.uint64)
         out["perm_counts"][order] = perm_sorted
@@ -682,6 +705,87 @@ def false_count_columns(thresholds, perm_counts, observed, perms: int, ks=(2, 5,
     for k in ks:
         out[f"kFWER.{int(k)}"] = (V >= np.uint64(max(int(k), 0))).sum(axis=1).astype(np.float64) / B
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# step-down max-T p-values of a level's top rows
+
+STEPDOWN_COLUMNS = ["PvaluesStepDown"]
+
+
+def stepdown_reference(method, n_cases: int, n_ctrls: int, uids, rows0, rows1, value_table, masks, top) -> Dict[str, object]:
+    """The definition of a join's step-down max-T counts (Westfall & Young 1993, Alg. 4.1) in plain numpy -- what
+    gcre_exceed_stepdown must return, exactly.  The join is given as for ``exceed_reference``; ``top`` = (src, trg, scores)
+    of its top rows: joined path (uid row src, paths1 row trg) and its observed score tau, all finite, sentinel rows left
+    out, every pair a different joined path of the join.
+
+    With null[p][r] as ``exceed_reference`` states it and D_j = {i : tau_i > tau_j} (f64: rows with equal scores do not
+    exclude one another), u_j[r] = the maximum of null[p][r] over the joined paths p that are not rows of D_j, and
+    n_ge[j] = #{r : (double)u_j[r] >= tau_j}.  It is computed from the successive maxima themselves: the null matrix in
+    blocks of paths, a running maximum over the paths that are not top rows, the top rows' own null rows, and per row the
+    maximum of the rest with the rows that are not better -- not through the counts V - E the device uses.
+
+    Returns {"n_ge" (int64 [m], in the order of ``top``), "single" (int64 [m]: #{r : null_max[r] >= tau_j}, the single-step
+    count), "null_max" (f32 [K]), "top_null" (f32 [m][K]: the rows' own null values), "scores" (f64 [m]: the rows' observed
+    scores as the join computes them), "perms"}."""
+    src_t = np.asarray(top[0], np.int64).ravel()
+    trg_t = np.asarray(top[1], np.int64).ravel()
+    tau = np.asarray(top[2], np.float64).ravel()
+    m = len(tau)
+    if not (len(src_t) == len(trg_t) == m):
+        raise ValueError("top: one src, trg and score per row")
+    if not np.isfinite(tau).all():
+        raise ValueError("top: every score must be finite (leave the sentinel rows out)")
+    where = {}
+    for j, key in enumerate(zip(src_t.tolist(), trg_t.tolist())):
+        if key in where:
+            raise ValueError(f"top: rows {where[key]} and {j} are the same joined path {key}")
+        where[key] = j
+    K = _n_masks(masks, int(n_cases) + int(n_ctrls))
+    rest = np.zeros(K, np.float32)                      # null values are >= 0
+    top_null = np.zeros((m, K), np.float32)
+    top_score = np.full(m, np.nan)
+    found = np.zeros(m, bool)
+    for _lo, s_, t_, sc_, null in _join_null_blocks(method, n_cases, n_ctrls, uids, rows0, rows1, value_table, masks):
+        is_top = np.zeros(len(s_), bool)
+        for i, key in enumerate(zip(s_.tolist(), t_.tolist())):
+            j = where.get(key)
+            if j is not None:
+                is_top[i], found[j] = True, True
+                top_null[j], top_score[j] = null[i], sc_[i]
+        if (~is_top).any() and K:
+            rest = np.maximum(rest, null[~is_top].max(axis=0))
+    if not found.all():
+        raise ValueError(f"top: row {int(np.flatnonzero(~found)[0])} is not a joined path of the join")
+    null_max = np.maximum(rest, top_null.max(axis=0)) if m and K else rest.copy()
+    n_ge = np.zeros(m, np.int64)
+    for j in range(m):
+        inside = tau <= tau[j]                          # the rows that stay in the family: not strictly better than row j
+        u = np.maximum(rest, top_null[inside].max(axis=0)) if K else rest
+        n_ge[j] = int((u.astype(np.float64) >= tau[j]).sum())
+    single = (null_max.astype(np.float64)[None, :] >= tau[:, None]).sum(axis=1).astype(np.int64)
+    return {"n_ge": n_ge, "single": single, "null_max": null_max, "top_null": top_null, "scores": top_score, "perms": K}
+
+
+def stepdown_columns(thresholds, n_ge, perms: int) -> Dict[str, np.ndarray]:
+    """Per threshold, in the order given: ``PvaluesStepDown`` = the largest raw step-down value n_ge[i] / B among the rows i
+    whose threshold is at least this one (the monotone step of Westfall & Young's algorithm: a p-value never falls as the
+    score does; equal thresholds get equal values).  B = ``perms``; NaN when B = 0.  No identity permutation is added, as in
+    ``Pvalues``.  Returns {"PvaluesStepDown"}."""
+    t = np.asarray(thresholds, np.float64).ravel()
+    g = np.asarray(n_ge, np.float64).ravel()
+    if len(g) != len(t):
+        raise ValueError(f"{len(g)} counts for {len(t)} thresholds")
+    B = int(perms)
+    if B <= 0:
+        return {"PvaluesStepDown": np.full(len(t), np.nan)}
+    order = np.argsort(-t, kind="stable")               # descending; a tie group takes the value at its last member
+    run = np.maximum.accumulate(g[order] / B)
+    ts = t[order]
+    last = np.searchsorted(-ts, -ts, side="right") - 1
+    out = np.empty(len(t))
+    out[order] = run[last]
+    return {"PvaluesStepDown": out}
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -1018,7 +1122,8 @@ def gwaspa(genes: Sequence[str], data: np.ndarray, n_cases: int, n_ctrls: int, n
            strata: Optional[Sequence[int]] = None, seed: int = 0, device: int = 0,
            decorated_pvalues: bool = False, gene_table: bool = False, fdr: bool = False,
            clump: Optional[float] = None, clump_conditional: bool = False, false_counts: bool = False,
-           false_count_ks: Sequence[int] = (2, 5, 10), false_count_alpha: float = 0.05) -> Dict[str, object]:
+           false_count_ks: Sequence[int] = (2, 5, 10), false_count_alpha: float = 0.05,
+           stepdown: bool = False) -> Dict[str, object]:
     """GWASPA (R/ProcessPaths.R:87-344) without R: dataset -> GWASPA.Results, scored on the MI355X.
 
     ``network`` = (ents_uid, ents_symbol, rel_src, rel_trg, rel_sign): the knowledge base getStringKB() would load
@@ -1051,6 +1156,15 @@ def gwaspa(genes: Sequence[str], data: np.ndarray, n_cases: int, n_ctrls: int, n
     ``fdr=True``.  ``top_k * n_permutations`` above 2^26 raises ValueError before anything runs; ``n_permutations == 0`` adds
     NaN columns.  Sentinel rows get NaN.  Default False: nothing new is called.
 
+    ``stepdown``: the counting pass of ``false_counts`` is made (one pass and one set of counters when both are set), each
+    level's finite top rows are turned into sets from the table's ``SignedPaths`` (``parse_sets``, signs for the signed
+    method) and ``api.ExceedCounts.stepdown`` gives their step-down max-T counts (Westfall & Young 1993):
+    GWASPA.Results gains "PvaluesStepDown" (``stepdown_columns``, within a length) -- the family-wise p-value of the row with
+    the better rows of its length taken out of the family: never above ``Pvalues``, equal to it on each length's best row,
+    the same FWER under the same assumption -- and the raw counts come back as "stepdown" (length -> int64 array, in the
+    order of the level's finite scores).  ``top_k * n_permutations`` above 2^26 raises ValueError before anything runs;
+    ``n_permutations == 0`` adds a NaN column.  Sentinel rows get NaN.  Default False: nothing new is called.
+
     ``clump``: with a value r, GWASPA.Results goes through ``clump_paths(r=clump, conditional=clump_conditional)`` with the
     run's own seed, strata, threshold and permutation count: it gains ``CLUMP_COLUMNS`` -- which rows are
     carried by the same patients as a better row -- and with ``clump_conditional`` ``RESIDUAL_COLUMNS``, each row rescored
@@ -1063,8 +1177,8 @@ def gwaspa(genes: Sequence[str], data: np.ndarray, n_cases: int, n_ctrls: int, n
 
     method = "method2" if signed else "method1"
     check_input(n_cases, n_ctrls, method, threshold, top_k, path_length, n_permutations)
-    if false_counts and int(top_k) * int(n_permutations) > EXCEED_PERM_CELLS:
-        raise ValueError(f"false_counts: top_k x n_permutations = {int(top_k) * int(n_permutations)} exceeds the limit of "
+    if (false_counts or stepdown) and int(top_k) * int(n_permutations) > EXCEED_PERM_CELLS:
+        raise ValueError(f"{'false_counts' if false_counts else 'stepdown'}: top_k x n_permutations = {int(top_k) * int(n_permutations)} exceeds the limit of "
                          f"2^26 = {EXCEED_PERM_CELLS} per-permutation cells of a level")
     genes, data = preprocess_table(genes, data, threshold, n_cases, n_ctrls)
     prep = prepare_inputs(genes, data, *network)
@@ -1097,10 +1211,10 @@ def gwaspa(genes: Sequence[str], data: np.ndarray, n_cases: int, n_ctrls: int, n
     out = {"GWASPA.Results": results_table(lsts, path_length, frames,
                                            (prep.ents_uid, prep.ents_symbol), (prep.ents2_uid, prep.ents2_symbol)),
            "levels": lsts, "prepared": prep}
-    if fdr or false_counts:
-        keep = bool(false_counts) and n_permutations > 0
+    if fdr or false_counts or stepdown:
+        keep = bool(false_counts or stepdown) and n_permutations > 0
         fc_names = false_count_names(false_count_ks) if false_counts else []
-        new_cols = (FDR_COLUMNS if fdr else []) + fc_names
+        new_cols = (FDR_COLUMNS if fdr else []) + fc_names + (STEPDOWN_COLUMNS if stepdown else [])
         counters = {}
         for L, name in enumerate(GENE_LEVELS[:path_length], start=1):
             s = np.asarray(lsts[f"lst{L}"].scores, np.float64)
@@ -1110,16 +1224,53 @@ def gwaspa(genes: Sequence[str], data: np.ndarray, n_cases: int, n_ctrls: int, n
         if counters:
             api.process_paths(problem, device=device, exec_=ex, exceeds=counters)
         df = out["GWASPA.Results"]
-        lookup, out["exceed"] = {}, {}
+        lookup, counted = {}, {}
+        if fdr or false_counts:
+            out["exceed"] = counted
+        if stepdown:
+            out["stepdown"] = {}
         for L, name in enumerate(GENE_LEVELS[:path_length], start=1):
             if name not in counters:
                 continue
             got = counters[name].read()
-            out["exceed"][L] = got
+            counted[L] = got
             cols = fdr_columns(counters[name].thresholds, got.exceed, got.observed, got.perms) if fdr else {}
             if false_counts:
                 cols.update(false_count_columns(counters[name].thresholds, got.perm_counts, got.observed, got.perms,
                                                 ks=false_count_ks, alpha=false_count_alpha))
+            if stepdown:
+                thr = counters[name].thresholds
+                if keep:
+                    # set j = a table row of this length whose score is threshold j (tied rows: any of them, once each)
+                    # (matched on the bits: the library compares a set's score with its threshold bit for bit)
+                    sc_all = df["Scores"].to_numpy(np.float64)
+                    at: Dict[bytes, List[int]] = {}
+                    for i in np.flatnonzero((df["Lengths"].to_numpy() == L) & np.isfinite(sc_all)).tolist():
+                        at.setdefault(sc_all[i].tobytes(), []).append(i)
+                    picked = []
+                    for t in thr:
+                        left = at.get(t.tobytes())
+                        if not left:
+                            raise ValueError(f"stepdown: length {L}: no table row left for the top score {float(t)!r}")
+                        picked.append(left.pop(0))
+                    _, rows, signs = parse_sets([str(df["SignedPaths"].iat[i]) for i in picked], genes)
+                    for i, rs in zip(picked, rows):
+                        if any(r < 0 for r in rs):
+                            raise ValueError(f"stepdown: length {L}, table row {i} ({df['SignedPaths'].iat[i]}): a gene is not "
+                                             "in the dataset, so the row's carriers cannot be rebuilt")
+                    used: Dict[int, int] = {}
+                    sets = [[used.setdefault(r, len(used)) for r in rs] for rs in rows]
+                    sub = np.asarray(data)[list(used.keys())] if used else np.zeros((0, n_cases + n_ctrls), np.int32)
+                    try:
+                        n_ge = counters[name].stepdown(sets, sub, signs if signed else None)
+                    except api.GcreError as e:
+                        # e.g. duplicate gene symbols: parse_sets takes the first row of a symbol, the join may have scored another
+                        raise ValueError(f"stepdown: length {L}: the carriers rebuilt from SignedPaths are not the rows the join "
+                                         f"scored ({e}); the other columns do not depend on this: run with stepdown=False") from e
+                else:
+                    n_ge = np.zeros(len(thr), np.int64)
+                out["stepdown"][L] = n_ge
+                cols.update(stepdown_columns(thr, n_ge, got.perms))
             for i, t in enumerate(counters[name].thresholds.tolist()):
                 lookup[(L, t)] = tuple(cols[c][i] for c in new_cols)
             counters[name].free()

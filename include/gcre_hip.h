@@ -544,6 +544,29 @@ int gcre_exceed_keep_perm_counts(gcre_exceed* x, int on);
  * keeps no per-permutation counts. */
 int gcre_exceed_read_perm_counts(gcre_exceed* x, uint64_t* out /* [m][iterations] */);
 
+/* Step-down max-T (Westfall & Young 1993, Alg. 4.1): the family-wise p-values of a level's top rows with
+ * the better rows taken out of the family.  x keeps per-permutation counts and was counted over exactly one full pass of one
+ * join (perms_counted == iterations); its m thresholds are observed scores of joined paths of that join, all finite.
+ * in->n_sets == m, and set j IS the joined path whose observed score is threshold j: its members are the path's rows, signed
+ * as for gcre_score_sets.  With D_j = the sets whose threshold is strictly above threshold j (compared as doubles: tied rows do
+ * not exclude one another) and null[p][r] as stated for gcre_score_sets,
+ *   n_ge[j] = #{r < iterations : max over the join's paths p outside D_j of (double)null[p][r] >= thresholds[j]}
+ * -- the raw step-down p-value is n_ge[j] / iterations; report.stepdown_columns takes the monotone step.  It is computed as
+ * V[j][r] - E[j][r] >= 1: V the counts x holds, E[j][r] = #{i in D_j : (double)null[i][r] >= thresholds[j]} from
+ * k_stepdown_null over the m sets, compared by k_stepdown_finish.  n_ge[j] never exceeds #{r : null_max[r] >= thresholds[j]}
+ * and equals it for the best row.  x is not changed: calling it twice gives the same answer.
+ * Waits for what is in flight.  Errors before any launch: GCRE_ERR_ARG -- x keeps no per-permutation counts, nothing or not
+ * exactly one full pass was counted, x not among its context's live objects (the check gcre_exceed_keep_perm_counts makes: the
+ * call takes no context of its own, so there is no other one to belong to), n_sets != m, a threshold that is not finite, an NA
+ * member; and everything gcre_score_sets refuses.  After k_set_observed and before the two kernels: GCRE_ERR_ARG naming the
+ * first set whose observed score is not its threshold bit for bit (the rows must be the rows the thresholds came from).  After
+ * them: GCRE_ERR_ASSERT "the sets are not distinct joined paths of the counted join" when some permutation counts more
+ * top rows than joined paths at a threshold (n_ge is then not written).  Memory: m x iterations (rounded up to 2048) u32 cells,
+ * freed on return. */
+int gcre_exceed_stepdown(gcre_exceed* x, const gcre_set_input* in, int64_t* n_ge /* [m] */);
+/* k_stepdown_null / k_stepdown_finish launches of the context since gcre_create (tests: a refusal launches nothing). */
+int64_t gcre_stepdown_launches(const gcre_ctx* ctx);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,198 @@
+"""Step-down max-T in plain numpy (report.stepdown_reference, report.stepdown_columns): the reference
+against a brute-force triple loop on a tiny join with tied scores, the consequences the definition has, and the identity
+V - E >= 1 the device computes it by, with V from report.exceed_reference(per_permutation=True).  No GPU."""
+from __future__ import annotations
+
+import numpy as np
+import pytest
+
+from geneticscre_amd import report
+from geneticscre_amd.uids import UidRelSet
+
+
+def tiny_join(method, seed):
+    """A join of 30 paths (6 uid rows x 5 paths1 rows each, path length 4: the sign of a path is its uid row's) over 23
+    patients and 7 permutations, with a table of twenty values: tied scores and tied null values."""
+    rng = np.random.default_rng(seed)
+    M, nc, nt, K = method, 11, 12, 7
+    n = nc + nt
+    count = np.full(6, 5, np.int32)
+    location = np.array([0, 2, 4, 1, 3, 0], np.int64)
+    uids = UidRelSet(4, np.arange(6), np.arange(6), count, location, rng.choice([-1, 1], size=6))
+    bits0 = rng.random((6, M, n)) < 0.15
+    bits1 = rng.random((9, M, n)) < 0.15
+
+    def pack(b):
+        w = np.zeros((b.shape[0], M, 64), bool)
+        w[:, :, :n] = b
+        return np.packbits(w.reshape(len(b), -1), axis=1, bitorder="little").view(np.uint64)
+
+    VT = rng.integers(0, 20, size=(n + 1, n + 1)).astype(np.float64) * 0.75
+    VT[rng.random(VT.shape) < 0.1] = -1.0
+    masks = np.array([rng.permutation(n) < nc for _ in range(K)])
+    return dict(method=M, nc=nc, nt=nt, K=K, uids=uids, bits0=bits0, bits1=bits1, rows0=pack(bits0), rows1=pack(bits1),
+                VT=VT, masks=masks)
+
+
+def brute_force(j_, top):
+    """Scalar code only: every (top row, permutation, joined path) visited; the null value written out per method."""
+    M, nc, n, VT, masks = j_["method"], j_["nc"], j_["nc"] + j_["nt"], j_["VT"], j_["masks"]
+    u = j_["uids"]
+
+    def vt(a, b):
+        return float(VT[a][b])
+
+    def vtmax(a, b):
+        x, y = vt(a, b), vt(b, a)
+        return y if x < y else x
+
+    def fold(x):
+        f = np.float32(x)
+        return f if f > 0 else np.float32(0)
+
+    paths = []          # (src, trg, null per permutation, observed score)
+    for i in range(len(u.count)):
+        for k in range(int(u.count[i])):
+            t = int(u.location[i]) + k
+            swap = M == 2 and int(u.signs[i]) != 1
+            pos = [bool(j_["bits0"][i][0][c] or j_["bits1"][t][1 if swap else 0][c]) for c in range(n)]
+            neg = [bool(j_["bits0"][i][1][c] or j_["bits1"][t][0 if swap else 1][c]) for c in range(n)] if M == 2 else None
+            null = []
+            for r in range(len(masks)):
+                a = sum(1 for c in range(n) if pos[c] and masks[r][c])
+                if M == 1:
+                    null.append(fold(vt(a, sum(pos) - a)))
+                else:
+                    b = sum(1 for c in range(n) if neg[c] and masks[r][c])
+                    null.append(fold(vtmax(a, sum(pos) - a) + vtmax(sum(neg) - b, b)))
+            cp = sum(1 for c in range(n) if pos[c] and c < nc)
+            score = vt(cp, sum(pos) - cp)
+            if M == 2:
+                cn = sum(1 for c in range(n) if neg[c] and c < nc)
+                score = score + vt(sum(neg) - cn, cn)
+            paths.append((i, t, null, score))
+    src, trg, tau = top
+    key = {(int(s), int(t)): j for j, (s, t) in enumerate(zip(src, trg))}
+    n_ge = []
+    for j in range(len(tau)):
+        count = 0
+        for r in range(len(masks)):
+            best = None
+            for (s, t, null, _) in paths:
+                i = key.get((s, t))
+                if i is not None and tau[i] > tau[j]:
+                    continue                         # a better row: out of the family
+                best = null[r] if best is None or null[r] > best else best
+            count += 1 if float(best) >= tau[j] else 0
+        n_ge.append(count)
+    return np.array(n_ge, np.int64), paths
+
+
+def top_of(paths, m):
+    """The m best paths (score descending, then ordinal), as (src, trg, scores)."""
+    order = sorted(range(len(paths)), key=lambda p: (-paths[p][3], p))[:m]
+    return (np.array([paths[p][0] for p in order]), np.array([paths[p][1] for p in order]),
+            np.array([paths[p][3] for p in order], np.float64))
+
+
+def reference(j_, top):
+    return report.stepdown_reference(j_["method"], j_["nc"], j_["nt"], j_["uids"], j_["rows0"], j_["rows1"], j_["VT"],
+                                     j_["masks"], top)
+
+
+CASES = [(method, seed) for method in (1, 2) for seed in range(6)]
+
+
+@pytest.mark.parametrize("method,seed", CASES)
+def test_reference_equals_the_triple_loop(method, seed):
+    j_ = tiny_join(method, seed)
+    _, paths = brute_force(j_, (np.zeros(0, int), np.zeros(0, int), np.zeros(0)))
+    assert len(paths) == 30
+    top = top_of(paths, 12)
+    assert len(set(top[2].tolist())) < len(top[2])                     # tied scores among the top rows
+    want, _ = brute_force(j_, top)
+    got = reference(j_, top)
+    np.testing.assert_array_equal(got["n_ge"], want)
+    np.testing.assert_array_equal(got["scores"], top[2])
+    # the order of the rows, tied ones included, does not matter
+    perm = np.random.default_rng(seed).permutation(12)
+    again = reference(j_, tuple(a[perm] for a in top))
+    np.testing.assert_array_equal(again["n_ge"], want[perm])
+
+
+def test_the_triple_loop_can_tell():
+    """Over the cases some row's step-down count is strictly below its single-step count: the loop above tests more than
+    the single-step p-value."""
+    gain = 0
+    for method, seed in CASES:
+        j_ = tiny_join(method, seed)
+        _, paths = brute_force(j_, (np.zeros(0, int), np.zeros(0, int), np.zeros(0)))
+        got = reference(j_, top_of(paths, 12))
+        gain += int((got["n_ge"] < got["single"]).sum())
+    assert gain > 0
+
+
+@pytest.mark.parametrize("method,seed", CASES)
+def test_consequences_and_identity(method, seed):
+    j_ = tiny_join(method, seed)
+    _, paths = brute_force(j_, (np.zeros(0, int), np.zeros(0, int), np.zeros(0)))
+    top = top_of(paths, 12)
+    src, trg, tau = top
+    got = reference(j_, top)
+    K = j_["K"]
+    # the join's own maxima
+    want_max = np.array([max(p[2][r] for p in paths) for r in range(K)], np.float32)
+    np.testing.assert_array_equal(got["null_max"].view(np.uint32), want_max.view(np.uint32))
+    single = (want_max.astype(np.float64)[None, :] >= tau[:, None]).sum(axis=1)
+    np.testing.assert_array_equal(got["single"], single)
+    best = tau == tau.max()
+    np.testing.assert_array_equal(got["n_ge"][best], single[best])     # the best row(s): nothing is excluded
+    assert (got["n_ge"] <= single).all()
+    cols = report.stepdown_columns(tau, got["n_ge"], K)["PvaluesStepDown"]
+    assert (cols <= single / K).all() and (cols[best] == single[best] / K).all()
+    # V - E >= 1, V from the exceedance reference, E from the top rows' own null rows
+    V = report.exceed_reference(j_["method"], j_["nc"], j_["nt"], j_["uids"], j_["rows0"], j_["rows1"], j_["VT"], j_["masks"],
+                                tau, per_permutation=True)["perm_counts"].astype(np.int64)
+    own = got["top_null"].astype(np.float64)
+    E = np.zeros_like(V)
+    for j in range(len(tau)):
+        better = tau > tau[j]
+        E[j] = (own[better] >= tau[j]).sum(axis=0)
+    assert (V >= E).all()
+    np.testing.assert_array_equal((V - E >= 1).sum(axis=1), got["n_ge"])
+
+
+def test_reference_refuses_what_is_not_a_top_list():
+    j_ = tiny_join(1, 0)
+    _, paths = brute_force(j_, (np.zeros(0, int), np.zeros(0, int), np.zeros(0)))
+    src, trg, tau = top_of(paths, 4)
+    with pytest.raises(ValueError, match="same joined path"):
+        reference(j_, (np.append(src, src[0]), np.append(trg, trg[0]), np.append(tau, tau[0])))
+    with pytest.raises(ValueError, match="not a joined path"):
+        reference(j_, (np.array([0]), np.array([8]), np.array([1.0])))
+    with pytest.raises(ValueError, match="finite"):
+        reference(j_, (src, trg, np.where(np.arange(4) == 2, -np.inf, tau)))
+
+
+def test_stepdown_columns():
+    t = np.array([3.0, 5.0, 3.0, 1.0, 4.0, 0.5])
+    n_ge = np.array([40, 10, 40, 20, 50, 90])
+    got = report.stepdown_columns(t, n_ge, 100)
+    assert list(got) == ["PvaluesStepDown"] == report.STEPDOWN_COLUMNS
+    # by score descending: 5 -> .1, 4 -> .5, 3, 3 -> .5 (the step), 1 -> .5 (raw .2), 0.5 -> .9
+    np.testing.assert_array_equal(got["PvaluesStepDown"], [0.5, 0.1, 0.5, 0.5, 0.5, 0.9])
+    # ties are equal whatever the raw values of their members and wherever they stand
+    tied = report.stepdown_columns([2.0, 7.0, 2.0, 2.0], [30, 5, 10, 20], 50)["PvaluesStepDown"]
+    np.testing.assert_array_equal(tied, [0.6, 0.1, 0.6, 0.6])
+    # monotone: never falls as the threshold does
+    rng = np.random.default_rng(1)
+    t = rng.integers(0, 6, size=40).astype(np.float64)
+    col = report.stepdown_columns(t, rng.integers(0, 101, size=40), 100)["PvaluesStepDown"]
+    order = np.argsort(-t, kind="stable")
+    assert (np.diff(col[order]) >= 0).all()
+    for v in np.unique(t):
+        assert len(set(col[t == v].tolist())) == 1
+    assert np.isnan(report.stepdown_columns([1.0, 2.0], [0, 0], 0)["PvaluesStepDown"]).all()
+    assert len(report.stepdown_columns([], [], 10)["PvaluesStepDown"]) == 0
+    with pytest.raises(ValueError):
+        report.stepdown_columns([1.0], [1, 2], 10)
