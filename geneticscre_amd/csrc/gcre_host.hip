@@ -351,6 +351,7 @@ struct gcre_ctx {
   bool mt_stale = false;             // d_masks changed while the sparse kernel was off: d_mt (if any) holds older masks
   int ieq_batch = 0;                 // GCRE_IEQ_BATCH: quads per ticket of the quad kernel (0: twice ie_batch)
   int ie_quad = 1;                   // GCRE_IE_QUAD=0: the pruned method-1 launches stay on k_null_ie_m1 (cross-check)
+  int ie_flagq = 1;                  // GCRE_IE_FLAGQ=0: the quad kernel's second look + exact pass instead of the flag queue (A/B runs, tests)
   int ie_zwide = 0;                  // GCRE_IE_ZWIDE=1: the quad kernel reaches every added row through a descriptor of its own (tests)
   int ie_warm_items = 4;             // (segment, tile) items per wave of the warm-up launch (GCRE_IE_WARM_ITEMS)
   int exchange_tail = 0;             // slices of the pruned launch that are equal steps at its end (GCRE_EXCHANGE_TAIL; -1: half of them; 0: doubling slices only)
@@ -2522,6 +2523,8 @@ int launch_ie_slices(JoinRun& R, const ChunkRun& C, IeArgs& ia, int planes, int6
       ia.quad_end = seg_entry->nquads;
       // an added row's planes are a 32-bit byte offset from the tile's first row wherever a tile of them stays below 4 GiB
       const uint64_t z_units = (uint64_t)ia.rowsz * (uint64_t)ia.gz;
+      // (the queue's drain addresses a mask row through a range-checked 31-bit vector offset)
+      ia.flagq = (c->ie_flagq && (uint64_t)ia.mt_rows * 256u < (1ull << 31)) ? 1u : 0u;
       ia.z_wide = (c->ie_zwide || z_units >= (1ull << 22)) ? 1u : 0u;
       ia.z_tile_units = ia.z_wide ? 0u : (uint32_t)z_units;
       ia.batch = c->ieq_batch > 0 ? c->ieq_batch : std::max(1, c->ie_batch * 2);   // quads per ticket: the headers of a ticket's quads are fetched one ahead
@@ -2566,8 +2569,8 @@ int launch_ie_slices(JoinRun& R, const ChunkRun& C, IeArgs& ia, int planes, int6
 int print_ie_timing(JoinRun& R, const ChunkRun& C, const IeArgs& ia, bool quad) {
   gcre_ctx* c = R.c;
   const int64_t n = C.n;
-  uint64_t tmv[8] = {0};
-  HIP_TRY(c, hipMemcpyAsync(tmv, c->d_ie_timing.p, 64, hipMemcpyDeviceToHost, R.st));
+  uint64_t tmv[12] = {0};
+  HIP_TRY(c, hipMemcpyAsync(tmv, c->d_ie_timing.p, sizeof tmv, hipMemcpyDeviceToHost, R.st));
   HIP_TRY(c, hipStreamSynchronize(R.st));
   const double waves = 8.0 * ia.waves_per_xcd;
   if (R.g.method == 2)
@@ -2576,9 +2579,11 @@ int print_ie_timing(JoinRun& R, const ChunkRun& C, const IeArgs& ia, bool quad) 
                  (unsigned long long)tmv[1], (unsigned long long)tmv[2], (unsigned long long)tmv[3], (unsigned long long)tmv[4],
                  (unsigned long long)tmv[6], (unsigned long long)tmv[5]);
   else if (quad)
-    std::fprintf(stderr, "[ieq timing] paths %lld waves %.0f quads/wave %.0f: per-wave Mcycles header+loads %.2f base counters %.2f intervals %.2f filter pass %.2f exact pass %.2f exchange %.2f total %.2f\n",
+    std::fprintf(stderr, "[ieq timing] paths %lld waves %.0f quads/wave %.0f: per-wave Mcycles header+loads %.2f base counters %.2f intervals %.2f filter pass %.2f exact pass %.2f exchange %.2f total %.2f; "
+                 "inside the filter pass: second look / queueing %.2f drains %.2f; flagged path-tiles %llu with %llu flagged permutations\n",
                  (long long)n, waves, tmv[7] / waves, tmv[0] / waves / 1e6, tmv[1] / waves / 1e6, tmv[2] / waves / 1e6, tmv[3] / waves / 1e6,
-                 tmv[4] / waves / 1e6, tmv[5] / waves / 1e6, tmv[6] / waves / 1e6);
+                 tmv[4] / waves / 1e6, tmv[5] / waves / 1e6, tmv[6] / waves / 1e6, tmv[8] / waves / 1e6, tmv[9] / waves / 1e6,
+                 (unsigned long long)tmv[10], (unsigned long long)tmv[11]);
   else
     std::fprintf(stderr, "[ie filter] uncertain path-tiles %llu of %lld x %d tiles, lanes that fetched rows %llu\n",
                  (unsigned long long)tmv[1], (long long)n, ia.nkt, (unsigned long long)tmv[3]);
@@ -2689,8 +2694,8 @@ int score_chunk_ie(JoinRun& R, ChunkRun& C, ChunkEnd* end) {
   }
   const bool timing = std::getenv("GCRE_IE_TIMING") != nullptr;   // diagnostics builds only (-DGCRE_IE_TIMING)
   if (timing) {
-    HIP_TRY(c, c->d_ie_timing.reserve(8));
-    HIP_TRY(c, hipMemsetAsync(c->d_ie_timing.p, 0, 64, st));
+    HIP_TRY(c, c->d_ie_timing.reserve(12));
+    HIP_TRY(c, hipMemsetAsync(c->d_ie_timing.p, 0, 96, st));
     ia.timing = c->d_ie_timing.p;
   }
   if (C.sel_begun && C.sel_on == st)   // (its state came back with the flags)
@@ -3092,6 +3097,7 @@ gcre_ctx* gcre_create(int method, int n_cases, int n_ctrls, int iterations, int 
   if (const char* e = std::getenv("GCRE_IE_BATCH")) c->ie_batch = std::min(std::max(std::atoi(e), 1), 4096);
   if (const char* e = std::getenv("GCRE_IEQ_BATCH")) c->ieq_batch = std::max(0, std::atoi(e));
   if (const char* e = std::getenv("GCRE_IE_QUAD")) c->ie_quad = std::min(std::max(std::atoi(e), 0), 2);   // 2: wherever it can run
+  if (const char* e = std::getenv("GCRE_IE_FLAGQ")) c->ie_flagq = std::atoi(e) != 0;
   if (const char* e = std::getenv("GCRE_IE_ZWIDE")) c->ie_zwide = std::atoi(e) != 0;
   if (const char* e = std::getenv("GCRE_PLANES_OUT_MAX_MB")) c->planes_out_max = (size_t)std::max(0ll, std::atoll(e)) << 20;
   if (const char* e = std::getenv("GCRE_SPARSE_WAVES_PER_CU")) c->sparse_waves_per_cu = std::max(1, std::atoi(e));

@@ -30,7 +30,7 @@ namespace gcre {
 // and the exact pass wait on memory, a fourth wave covers more of that than sharing a plane load four ways saves);
 // four segments at four waves spill (128 VGPRs), three at four do too.
 #ifndef GCRE_REFINE_MAX
-#define GCRE_REFINE_MAX 2   // flagged permutations per lane up to which the filter takes its second look (tuning builds)
+#define GCRE_REFINE_MAX 2   // flagged permutations per lane up to which a path-tile is queued (or takes the second look); above: exact pass (tuning builds)
 #endif
 #ifndef GCRE_QSEGS
 #define GCRE_QSEGS 2
@@ -79,6 +79,12 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(G
   for (int q = 0; q < 32; q++) nm[q * 64] = 0u;
   u32 (*lq)[kLqCap] = lq_lds[wave];
   u32 lq_n = 0u;   // entries waiting (wave-uniform)
+  // flagged permutations of the filter pass, queued (joined path; count W | bit << 17 | lane << 22) and scored 64 at a
+  // time by fq_drain below: the items address the current tile's masks and maxima
+  constexpr u32 kFqCap = 64u;
+  __shared__ u32 fq_lds[kIeWaves][2][kFqCap];
+  u32 (*fq)[kFqCap] = fq_lds[wave];
+  u32 fq_n = 0u;
   auto lq_drain = [&]() {
     for (u32 base = 0u; base < lq_n; base += 64u) {
       const u32 i = base + (u32)lane;
@@ -99,13 +105,20 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(G
   const char* k_planesz = uni_ptr(a.planesz);
   const u32 k_ztile = uni(a.z_tile_units);
 
+  // what a path-tile with flagged permutations does: 2 queue them (GCRE_IE_FLAGQ=1), 1 the second look of the ladder,
+  // 0 the exact pass at once (thresholds that do not come from the maxima)
+  const u32 k_road = (k_lad_mode == 0u) ? (uni(a.flagq) != 0u ? 2u : 1u) : 0u;
+
   int cur_kt = -1;
   u32 valid = 0u;
   u32 lad_base = (k_lad_mode == 0u) ? 0u : ((u32)kLadderLevels - 1u + k_lad_mode) * k_lstride;
   const u32 lad_keep = (u32)kLadderLevels * k_lstride;
   u32 n_slow = 0u;
 #ifdef GCRE_IE_TIMING
-  u64 tm[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // header + loads issued, base counters, filter intervals, filter pass, exact pass, exchange, total, quads
+  // header + loads issued, base counters, filter intervals, filter pass, exact pass, exchange, total, quads; inside the
+  // filter pass: second look or queueing, drains; flagged path-tiles; (per lane) flagged permutations
+  u64 tm[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  u32 n_flagged = 0u;
   const u64 tm_begin = __builtin_amdgcn_s_memtime();
 #endif
   __amdgpu_buffer_rsrc_t mt = __builtin_amdgcn_make_buffer_rsrc((void*)k_mt, 0, 0x7fffffff, 0x00020000);
@@ -113,10 +126,41 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(G
   // scalar offset takes no part in the range check).  WIDE builds a descriptor per row instead.
   __amdgpu_buffer_rsrc_t zt = __builtin_amdgcn_make_buffer_rsrc((void*)k_planesz, 0, 0x7fffffff, 0x00020000);
 
+  // The queued permutations, one per lane: S = how many of the path's (at most 8) overlap patients are cases in that
+  // permutation -- bit `bb` of one dword of each patient's mask row, padding entries point at the all-zero row --
+  // count = W - S, one table cell, one maximum.  Three memory round trips per 64 items.
+  auto fq_drain = [&]() {
+    GCRE_QT(td0);
+    if ((u32)lane < fq_n) {
+      const u32 q = fq[0][lane], w = fq[1][lane];
+      const u32 bb = (w >> 17) & 31u, at = (w >> 22) * 4u;
+      const u32x4* e = (const u32x4*)(a.dlist + (u64)q * 8u);
+      const u32x4 e0 = e[0], e1 = e[1];
+      const u32 tot = a.tot[q];
+      // (the entry is per lane here, so it goes into the vector offset, which the descriptor's 2-GiB range check sees --
+      // the exact pass has it in the unchecked scalar offset.  The host switches the queue off where a tile of masks
+      // reaches 2 GiB, gcre_host.hip: 8 million patients)
+      u32 y[8];
+#pragma unroll
+      for (int j = 0; j < 4; j++) {
+        y[j] = __builtin_amdgcn_raw_buffer_load_b32(mt, e0[j] + at, 0, 0);
+        y[4 + j] = __builtin_amdgcn_raw_buffer_load_b32(mt, e1[j] + at, 0, 0);
+      }
+      u32 S = 0u;
+#pragma unroll
+      for (int j = 0; j < 8; j++) S += (y[j] >> bb) & 1u;
+      const u32 cell = sp_diag_offset(tot) + (w & 0x1ffffu) - S;
+      __hip_atomic_fetch_max(nmax_lds[wave] + bb * 64u + (w >> 22), ((const u32*)a.t32)[cell], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);   // ds_max_u32
+    }
+    fq_n = 0u;
+    GCRE_QT(td1);
+    GCRE_QT_ADD(9, td1, td0);
+  };
+
   // publish the wave's maxima, read everybody's, set the threshold level to the smallest running maximum of the tile's
   // live permutations (a stale read only lowers it: still exact).  The merged values stay in LDS: nm[] is then the best
   // maximum this wave KNOWS of every permutation of the tile (its own finds + the others' as of the last exchange), which
-  // is what the per-permutation second look of the filter (refine, below) tests against.
+  // is what the queued permutations are folded into (fq_drain) and what the second look of the filter tests against.
   auto merge_global = [&](bool want_theta) {
     u32* out = a.null_bits + (size_t)cur_kt * 2048 + lane * 32;
     __amdgpu_buffer_rsrc_t nb = __builtin_amdgcn_make_buffer_rsrc((void*)(a.null_bits + (size_t)cur_kt * 2048), 0, 8192, 0x00020000);
@@ -136,6 +180,7 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(G
     return lo;
   };
   auto exchange = [&]() {
+    fq_drain();
     lq_drain();
     u32 theta = __builtin_amdgcn_readfirstlane(wave_min_u32(merge_global(true)));
     if (theta == 0xffffffffu) theta = 0u;
@@ -143,7 +188,8 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(G
     j = j < 0 ? 0 : (j > kLadderLevels - 1 ? kLadderLevels - 1 : j);
     lad_base = (u32)j * k_lstride;
   };
-  auto flush_tile = [&]() {
+  auto flush_tile = [&]() {   // (before the tile changes: queued items address this tile's masks)
+    fq_drain();
     lq_drain();
     if (cur_kt >= 0) (void)merge_global(false);
   };
@@ -418,22 +464,29 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(G
         // "above hi", not a small W)
         u32 fm = (blo | bhi | cy) & valid;
         if (__builtin_amdgcn_ballot_w64(fm != 0u) == 0ull) return;
-        // ---- a second look, permutation by permutation.  The interval above belongs to the LOWEST running maximum of the
-        // tile's 2048 permutations; a flagged permutation only matters if its count can leave the (wider) interval of its
-        // OWN maximum as far as this wave knows it (nm[], refreshed at every exchange).  count = W - S with 0 <= S <= ov, so
-        // [W - ov, W] inside that interval settles it without a mask row: most flagged paths end here instead of in the
-        // exact pass (a path costs ~300 instructions there).  Overlap lists only, thresholds from the maxima only. ----
+        // ---- a flagged path-tile (one in ten).  A flagged permutation needs its own count W - S, one table cell and one
+        // max: the path queues its flagged permutations with their W (the carry out of the top plane is part of it) and
+        // fq_drain scores them 64 at a time -- no ladder, no whole-tile arithmetic, and the path is not marked.  Overlap
+        // lists of at most 8 entries only, thresholds from the maxima only; a path with many flagged permutations in
+        // one lane -- dense genotypes, where the margin eats the interval -- goes to the exact pass as before, and so
+        // does everything else.
+        // GCRE_IE_FLAGQ=0 keeps the second look the queue replaced: the interval above belongs to the LOWEST running
+        // maximum of the tile's 2048 permutations; a flagged permutation only matters if its count can leave the (wider)
+        // interval of its OWN maximum as far as this wave knows it (nm[], refreshed at every exchange).  count = W - S
+        // with 0 <= S <= ov, so [W - ov, W] inside that interval settles it without a mask row. ----
         const u32 info = rdlane(infov[g], t);
-        // (a path with many flagged permutations -- dense genotypes, where the margin eats the interval -- is not worth
-        // the look: it goes to the exact pass as before)
         // ((info & 1u) != 0u is linfo_overlap(info) written out: with the helper here the compiler schedules this kernel
         // differently)
-        if (k_lad_mode == 0u && (info & 1u) != 0u && __builtin_amdgcn_ballot_w64(__builtin_popcount(fm) > GCRE_REFINE_MAX) == 0ull) {
-          const u32 ov = linfo_true_len(info);
-          const u32* lad_t = a.ladder + rdlane(totv[g], t);
+        if (k_road != 0u && (info & 1u) != 0u && __builtin_amdgcn_ballot_w64(__builtin_popcount(fm) > GCRE_REFINE_MAX) == 0ull) {
+          GCRE_QT(ts0);
+#ifdef GCRE_IE_TIMING
+          tm[10] += 1;
+          n_flagged += (u32)__builtin_popcount(fm);
+#endif
+          // W again, kept this time: the filter loop above holds no plane of it
           u32 Wp[L];
           u32 c2 = 0u;
-          {
+          auto sum_w = [&]() {
 #pragma unroll
             for (int l = 0; l < L; l++) {
               if (l < LZ) {
@@ -444,7 +497,51 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(G
                 c2 = Bg[l] & c2;
               }
             }
+          };
+          if (k_road == 2u && linfo_len(info) <= 8u) {
+            // how many items the path-tile queues (at most GCRE_REFINE_MAX per lane): room is made before W is rebuilt,
+            // so that a drain does not have the planes of W to keep
+            u32 total = 0u;
+            {
+              u32 f = fm;
+              asm volatile("" : "+v"(f));   // (not the ballot of the hot path: that one stays a compare into vcc)
+#pragma unroll
+              for (int r = 0; r < GCRE_REFINE_MAX; r++) {
+                total += (u32)__builtin_popcountll(__builtin_amdgcn_ballot_w64(f != 0u));
+                f &= f - 1u;
+              }
+            }
+            if (total <= kFqCap) {
+              if (fq_n + total > kFqCap) fq_drain();
+              sum_w();
+              const u32 q = firstg[g] + t;
+              while (__builtin_amdgcn_ballot_w64(fm != 0u) != 0ull) {   // one flagged permutation per lane and round
+                const bool has = fm != 0u;
+                const u32 bb = has ? (u32)__builtin_ctz(fm) : 0u;
+                fm &= fm - 1u;
+                u32 cnt = ((c2 >> bb) & 1u) << L;   // the carry out of the top plane is part of W
+#pragma unroll
+                for (int l = 0; l < L; l++) cnt |= ((Wp[l] >> bb) & 1u) << l;
+                const u64 hm = __builtin_amdgcn_ballot_w64(has);
+                const u32 pos = fq_n + __builtin_amdgcn_mbcnt_hi((u32)(hm >> 32), __builtin_amdgcn_mbcnt_lo((u32)hm, 0u));
+                if (has) {
+                  fq[0][pos] = q;
+                  fq[1][pos] = cnt | (bb << 17) | ((u32)lane << 22);
+                }
+                fq_n += (u32)__builtin_popcountll(hm);
+              }
+              n_slow++;
+              GCRE_QT(ts1);
+              GCRE_QT_ADD(8, ts1, ts0);
+              return;
+            }
           }
+          // the second look at the ladder: the old road, and what the queue does not take (lists of more than 8 entries:
+          // marking those at once, as first planned, took the exact pass of the level-4 launch from 2.8 to 6.4 of a
+          // wave's 41 Mcycles and the gain with it)
+          const u32 ov = linfo_true_len(info);
+          const u32* lad_t = a.ladder + rdlane(totv[g], t);
+          sum_w();
           bool unsafe = false;
           while (__builtin_amdgcn_ballot_w64(fm != 0u) != 0ull) {   // one flagged permutation per lane and round
             const bool has = fm != 0u;
@@ -462,6 +559,8 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(G
               if (cnt > hi || (lo != 0u && cnt < lo + ov)) unsafe = true;
             }
           }
+          GCRE_QT(ts1);
+          GCRE_QT_ADD(8, ts1, ts0);
           if (__builtin_amdgcn_ballot_w64(unsafe) == 0ull) return;
         }
         todo[g] |= 1ull << t;
@@ -653,7 +752,8 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(G
 #ifdef GCRE_IE_TIMING
   tm[6] = __builtin_amdgcn_s_memtime() - tm_begin;
   if (a.timing && lane == 0)
-    for (int i = 0; i < 8; i++) atomicAdd((unsigned long long*)a.timing + i, (unsigned long long)tm[i]);
+    for (int i = 0; i < 11; i++) atomicAdd((unsigned long long*)a.timing + i, (unsigned long long)tm[i]);
+  if (a.timing && n_flagged) atomicAdd((unsigned long long*)a.timing + 11, (unsigned long long)n_flagged);
 #endif
   if (a.stats && lane == 0 && n_slow) atomicAdd(a.stats, n_slow);
 }

@@ -138,7 +138,7 @@ struct IeArgs {
   const double* d64;
   const uint32_t* ladder;    // [kLadderLevels + 2][ladder_stride] hi << 16 | lo (method 1); rows kLadderLevels, +1: all inside / all outside
   uint32_t* null_bits;
-  uint64_t* timing;          // diagnostics build (-DGCRE_IE_TIMING): 6 per-section cycle sums over all waves
+  uint64_t* timing;          // diagnostics build (-DGCRE_IE_TIMING): 12 per-section cycle sums and counts over all waves
   uint32_t* stats;           // optional: [0] += joined-path tiles that were looked up (not pruned)
   uint32_t* planes_out;      // optional: planes of the joined paths [tile][(out_first+q)*M+h][go][64][4]
   int64_t out_first;
@@ -163,6 +163,9 @@ struct IeArgs {
   // the added rows' planes in the quad kernel: rowsz * gz, the 1-KB units of one tile; z_wide: a tile of them is 4 GiB
   // or more (or GCRE_IE_ZWIDE=1), a row is then reached through a descriptor of its own instead of a 32-bit byte offset
   uint32_t z_tile_units, z_wide;
+  // quad kernel: 1 = a path-tile's flagged permutations are queued and scored one per lane (GCRE_IE_FLAGQ, the default),
+  // 0 = the second look at the ladder and the exact pass
+  uint32_t flagq;
 };
 hipError_t launch_null_ie_quad(const IeArgs& a, int planes, hipStream_t stream);   // gcre_ieq.hip
 int ieq_max_waves_per_cu(int planes, int gz, bool rec, bool wide);
