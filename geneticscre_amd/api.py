@@ -8,6 +8,7 @@ missing, construction raises.
 from __future__ import annotations
 
 import ctypes
+import functools
 import os
 from dataclasses import dataclass
 from typing import Dict, Optional, Tuple
@@ -153,6 +154,11 @@ def load_library():
         lib = ctypes.CDLL(path)
     except OSError as e:   # no silent fallback: the product IS this library
         raise GcreError(f"cannot load {path}: {e}") from e
+    if os.environ.get("GCRE_LIB"):
+        # a variant library skips build()'s staleness check: make up for it here, before any other symbol is touched
+        abi = lib.gcre_abi_version() if hasattr(lib, "gcre_abi_version") else "?"
+        if abi != EXPECTED_ABI:
+            raise GcreError(f"GCRE_LIB={path}: ABI {abi}, this tree expects {EXPECTED_ABI} (rebuild the variant: tools/build_variant.py)")
     V, I, I64, P = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_void_p
     lib.gcre_create.restype = V
     lib.gcre_create.argtypes = [I, I, I, I, I]
@@ -163,10 +169,7 @@ def load_library():
     lib.gcre_abi_version.restype = I
     lib.gcre_build_flags.restype = ctypes.c_char_p
     if os.environ.get("GCRE_LIB"):
-        # a variant library skips build()'s staleness and diagnostics checks: make up for them here
-        if not hasattr(lib, "gcre_abi_version") or lib.gcre_abi_version() != EXPECTED_ABI:
-            raise GcreError(f"GCRE_LIB={path}: ABI {lib.gcre_abi_version() if hasattr(lib, 'gcre_abi_version') else '?'}, "
-                            f"this tree expects {EXPECTED_ABI} (rebuild the variant: tools/build_variant.py)")
+        # ... and for build()'s diagnostics check
         flags = lib.gcre_build_flags().decode()
         diag = [f for f in flags.split() if f.startswith("-D") and (f[2:].split("=")[0] in _build.DIAG_DEFINES or "ZHACK" in f or
                                                                       (f[2:].startswith("GCRE_") and "_NO" in f[2:]))]
@@ -233,63 +236,68 @@ def _ptr(a: Optional[np.ndarray]):
     return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
 
 
-def _decorated_lib():
-    """The library with the decorated-p-value entries bound.  Bound on first use, so that a GCRE_LIB variant built before
-    they existed still loads for everything else."""
-    lib = load_library()
-    if not hasattr(lib, "gcre_decorated_pvalues"):
-        raise GcreError(f"{lib._name} has no decorated p-values (gcre_decorated_splits): rebuild it")
-    if lib.gcre_decorated_splits.argtypes is None:
-        P, I, I64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64
-        lib.gcre_decorated_splits.argtypes = [ctypes.POINTER(gcre_dp_input), P, I, I, I, P, I64, ctypes.POINTER(I64)]
-        lib.gcre_decorated_pvalues.argtypes = [P, ctypes.POINTER(gcre_dp_input), P, I64, ctypes.POINTER(I64), P]
+# The entry points that came after the first release: bound on first use, so that a GCRE_LIB variant built before one of
+# them existed still loads for everything else.  Per feature: the feature it builds on, the symbols that must exist, what
+# the library lacks without them, and (restype, argtypes) of every symbol it binds.
+_V = _P = ctypes.c_void_p
+_I, _I32, _I64 = ctypes.c_int, ctypes.c_int32, ctypes.c_int64
+_FEATURES = {
+    "decorated": (None, ["gcre_decorated_pvalues"], "decorated p-values (gcre_decorated_splits)", {
+        "gcre_decorated_splits": (_I, [ctypes.POINTER(gcre_dp_input), _P, _I, _I, _I, _P, _I64, ctypes.POINTER(_I64)]),
+        "gcre_decorated_pvalues": (_I, [_P, ctypes.POINTER(gcre_dp_input), _P, _I64, ctypes.POINTER(_I64), _P])}),
+    "sets": (None, ["gcre_score_sets"], "set scoring (gcre_score_sets)", {
+        "gcre_score_sets": (_I, [_V, ctypes.POINTER(gcre_set_input), _P, _I64, ctypes.POINTER(_I64), _P])}),
+    "overlap": (None, ["gcre_set_overlap"], "carrier overlaps (gcre_set_overlap)", {
+        "gcre_set_overlap": (_I, [_V, ctypes.POINTER(gcre_set_input), _P, _I64, _P, _I64, _P, _P]),
+        "gcre_overlap_launches": (_I64, [_V])}),
+    "genes": (None, ["gcre_gene_tally_create"], "per-gene best-path tally (gcre_gene_tally_create)", {
+        "gcre_gene_tally_create": (_V, [_V, _I32, _P, _I64, _I32, _P, _I64, _I32]),
+        "gcre_join_set_tally": (_I, [_V, _V]),
+        "gcre_process_paths_set_tally": (_I, [_V, _I, _V]),
+        "gcre_gene_tally_read": (_I, [_V, _P, _P, _P, _P, _P, _P]),
+        "gcre_gene_tally_free": (None, [_V])}),
+    "exceed": (None, ["gcre_exceed_create"], "null exceedance counts (gcre_exceed_create)", {
+        "gcre_exceed_create": (_V, [_V, _P, _I32]),
+        "gcre_join_set_exceed": (_I, [_V, _V]),
+        "gcre_process_paths_set_exceed": (_I, [_V, _I, _V]),
+        "gcre_exceed_read": (_I, [_V, _P, _P, ctypes.POINTER(_I64), ctypes.POINTER(_I64)]),
+        "gcre_exceed_reset": (_I, [_V]),
+        "gcre_exceed_free": (None, [_V])}),
+    "perm_counts": ("exceed", ["gcre_exceed_keep_perm_counts", "gcre_exceed_read_perm_counts"],
+                    "per-permutation exceedance counts (gcre_exceed_keep_perm_counts)", {
+        "gcre_exceed_keep_perm_counts": (_I, [_V, _I]),
+        "gcre_exceed_read_perm_counts": (_I, [_V, _P])}),
+    "stepdown": ("perm_counts", ["gcre_exceed_stepdown", "gcre_stepdown_launches"],
+                 "step-down counts (gcre_exceed_stepdown)", {
+        "gcre_exceed_stepdown": (_I, [_V, ctypes.POINTER(gcre_set_input), _P]),
+        "gcre_stepdown_launches": (_I64, [_V])}),
+}
+del _V, _P, _I, _I32, _I64
+
+
+def _feature_lib(feature: str):
+    """The library with the entries of ``feature`` (and of what it builds on) bound."""
+    parent, needs, what, binds = _FEATURES[feature]
+    lib = _feature_lib(parent) if parent else load_library()
+    if not all(hasattr(lib, sym) for sym in needs):
+        raise GcreError(f"{lib._name} has no {what}: rebuild it")
+    for sym, (restype, argtypes) in binds.items():
+        fn = getattr(lib, sym)
+        if fn.argtypes is None:
+            fn.restype, fn.argtypes = restype, argtypes
     return lib
 
 
-def _sets_lib():
-    """The library with gcre_score_sets bound, on first use (as _decorated_lib)."""
-    lib = load_library()
-    if not hasattr(lib, "gcre_score_sets"):
-        raise GcreError(f"{lib._name} has no set scoring (gcre_score_sets): rebuild it")
-    if lib.gcre_score_sets.argtypes is None:
-        lib.gcre_score_sets.argtypes = [ctypes.c_void_p, ctypes.POINTER(gcre_set_input), ctypes.c_void_p, ctypes.c_int64,
-                                        ctypes.POINTER(ctypes.c_int64), ctypes.c_void_p]
-    return lib
+_decorated_lib = functools.partial(_feature_lib, "decorated")
+_sets_lib = functools.partial(_feature_lib, "sets")
+_overlap_lib = functools.partial(_feature_lib, "overlap")
+_genes_lib = functools.partial(_feature_lib, "genes")
+_exceed_lib = functools.partial(_feature_lib, "exceed")
+_perm_counts_lib = functools.partial(_feature_lib, "perm_counts")
+_stepdown_lib = functools.partial(_feature_lib, "stepdown")
 
 
 OVERLAP_TILE = 64   # kOverlapTile: pairs per edge of a k_set_overlap block's tile
-
-
-def _overlap_lib():
-    """The library with gcre_set_overlap bound, on first use (as _decorated_lib)."""
-    lib = load_library()
-    if not hasattr(lib, "gcre_set_overlap"):
-        raise GcreError(f"{lib._name} has no carrier overlaps (gcre_set_overlap): rebuild it")
-    if lib.gcre_set_overlap.argtypes is None:
-        P, I64 = ctypes.c_void_p, ctypes.c_int64
-        lib.gcre_set_overlap.argtypes = [P, ctypes.POINTER(gcre_set_input), P, I64, P, I64, P, P]
-        lib.gcre_overlap_launches.restype = I64
-        lib.gcre_overlap_launches.argtypes = [P]
-    return lib
-
-
-def _genes_lib():
-    """The library with the per-gene tally entries bound, on first use (as _decorated_lib)."""
-    lib = load_library()
-    if not hasattr(lib, "gcre_gene_tally_create"):
-        raise GcreError(f"{lib._name} has no per-gene best-path tally (gcre_gene_tally_create): rebuild it")
-    if lib.gcre_gene_tally_create.argtypes is None:
-        V, P, I, I64 = ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64
-        lib.gcre_gene_tally_create.restype = V
-        lib.gcre_gene_tally_create.argtypes = [V, I, P, I64, I, P, I64, I]
-        lib.gcre_join_set_tally.argtypes = [V, V]
-        lib.gcre_process_paths_set_tally.argtypes = [V, ctypes.c_int, V]
-        lib.gcre_gene_tally_read.argtypes = [V, P, P, P, P, P, P]
-        lib.gcre_gene_tally_free.argtypes = [V]
-        lib.gcre_gene_tally_free.restype = None
-    return lib
-
-
 GENE_WIDTH_MAX = 3   # kGeneWidthMax: gene slots a joined path inherits from one operand row, at most
 LEVEL_INDEX = {"1a": 0, "1b": 1, "2": 2, "3": 3, "4": 4, "5": 5}   # gcre_pp_input.level
 
@@ -368,47 +376,6 @@ class GeneTally:
             self.free()
         except Exception:
             pass
-
-
-def _exceed_lib():
-    """The library with the exceedance-count entries bound, on first use (as _decorated_lib)."""
-    lib = load_library()
-    if not hasattr(lib, "gcre_exceed_create"):
-        raise GcreError(f"{lib._name} has no null exceedance counts (gcre_exceed_create): rebuild it")
-    if lib.gcre_exceed_create.argtypes is None:
-        V, P = ctypes.c_void_p, ctypes.c_void_p
-        lib.gcre_exceed_create.restype = V
-        lib.gcre_exceed_create.argtypes = [V, P, ctypes.c_int32]
-        lib.gcre_join_set_exceed.argtypes = [V, V]
-        lib.gcre_process_paths_set_exceed.argtypes = [V, ctypes.c_int, V]
-        lib.gcre_exceed_read.argtypes = [V, P, P, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]
-        lib.gcre_exceed_reset.argtypes = [V]
-        lib.gcre_exceed_free.argtypes = [V]
-        lib.gcre_exceed_free.restype = None
-    return lib
-
-
-def _perm_counts_lib():
-    """The same with the per-permutation counts bound, on first use."""
-    lib = _exceed_lib()
-    if not hasattr(lib, "gcre_exceed_keep_perm_counts") or not hasattr(lib, "gcre_exceed_read_perm_counts"):
-        raise GcreError(f"{lib._name} has no per-permutation exceedance counts (gcre_exceed_keep_perm_counts): rebuild it")
-    if lib.gcre_exceed_keep_perm_counts.argtypes is None:
-        lib.gcre_exceed_keep_perm_counts.argtypes = [ctypes.c_void_p, ctypes.c_int]
-        lib.gcre_exceed_read_perm_counts.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
-    return lib
-
-
-def _stepdown_lib():
-    """The same with the step-down entries bound, on first use."""
-    lib = _perm_counts_lib()
-    if not hasattr(lib, "gcre_exceed_stepdown") or not hasattr(lib, "gcre_stepdown_launches"):
-        raise GcreError(f"{lib._name} has no step-down counts (gcre_exceed_stepdown): rebuild it")
-    if lib.gcre_exceed_stepdown.argtypes is None:
-        lib.gcre_exceed_stepdown.argtypes = [ctypes.c_void_p, ctypes.POINTER(gcre_set_input), ctypes.c_void_p]
-        lib.gcre_stepdown_launches.restype = ctypes.c_int64
-        lib.gcre_stepdown_launches.argtypes = [ctypes.c_void_p]
-    return lib
 
 
 EXCEED_MAX = 10000   # kExceedMax: thresholds of one ExceedCounts (the top_k limit)

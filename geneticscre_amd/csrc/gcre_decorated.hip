@@ -3,7 +3,7 @@
 //   * k_decorated_observed    the observed score of every split, read from the device's value table
 //   * k_decorated_null        one lane per (split, permutation): the urn draws, the permutation score, the count of
 //                             permutation scores >= the observed one
-// The context-side entry, gcre_decorated_pvalues, is in gcre_host.hip.  DESIGN.md "Decorated p-values".
+// The context-side entry, gcre_decorated_pvalues, is in gcre_host_stats.hip.  DESIGN.md "Decorated p-values".
 #include "../../include/gcre_hip.h"
 #include "gcre_kernels.h"
 

@@ -1,35 +1,12 @@
 // gcre_host.hip -- host side of libgcre_hip.so: the C ABI of include/gcre_hip.h on top of the gfx950
 // kernels in gcre_kernels.hip.  Owns device memory, the stream, the join driver (JoinExec::join,
 // reference src/join_base.cpp:189-264), the top-k merge (merge_scores / format_result, methods.h:25-39,
-// join_base.cpp:138-154) and the ProcessPaths sequence (src/wrapper.cpp:216-276).
+// join_base.cpp:138-154) and the ProcessPaths sequence (src/wrapper.cpp:216-276).  The state behind the handles is in
+// gcre_host.h; the entry points that do not touch the join driver -- generated permutation masks, decorated p-values, set
+// scores and overlaps, the gene tally and the exceedance counts as objects -- are in gcre_host_stats.hip.
 //
 // There is no CPU fallback: without a gfx950 device gcre_create fails with GCRE_ERR_DEVICE.
-#include "../../include/gcre_hip.h"
-#include "gcre_kernels.h"
-
-#include <dlfcn.h>
-#include <rccl/rccl.h>   // types and prototypes only: the library is dlopen'ed where several devices are used (RcclApi)
-
-#include <algorithm>
-#include <array>
-#include <atomic>
-#include <chrono>
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <limits>
-#include <memory>
-#include <mutex>
-#include <condition_variable>
-#include <string>
-#include <unordered_map>
-#include <thread>
-#include <functional>
-#include <deque>
-#include <vector>
-
-using namespace gcre;
+#include "gcre_host.h"
 
 namespace {
 
@@ -46,105 +23,6 @@ inline void poison_planes(void* p, size_t bytes) {
   (void)hipDeviceSynchronize();
   (void)hipMemset(p, 0x5A, bytes);
   (void)hipDeviceSynchronize();
-}
-
-template <typename T>
-struct DevBuf {   // grow-only device scratch
-  T* p = nullptr;
-  size_t cap = 0;
-  hipError_t reserve(size_t n) {
-    if (n <= cap) return hipSuccess;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    hipError_t e = hipMalloc((void**)&p, n * sizeof(T));
-    if (e == hipSuccess) cap = n;
-    return e;
-  }
-  // grow and keep the first `keep` elements
-  hipError_t grow_keep(size_t n, size_t keep, hipStream_t stream) {
-    if (n <= cap) return hipSuccess;
-    T* q = nullptr;
-    hipError_t e = hipMalloc((void**)&q, n * sizeof(T));
-    if (e != hipSuccess) return e;
-    if (p && keep) {
-      e = hipMemcpyAsync(q, p, std::min(keep, cap) * sizeof(T), hipMemcpyDeviceToDevice, stream);
-      if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    }
-    if (p) (void)hipFree(p);
-    p = q;
-    cap = n;
-    return e;
-  }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-  }
-};
-
-struct Candidate {
-  double score;
-  int64_t path;   // absolute joined-path ordinal
-  int32_t src, trg, cases, ctrls;
-};
-
-// top-k of a chunk: indices chosen by the radix select, their keys / counts / rows gathered and copied out
-struct Winners {
-  std::vector<uint32_t> sel, cases, ctrls, r0, r1;
-  std::vector<uint64_t> key;
-  uint32_t n = 0;
-};
-
-// The buffers a chunk's inspector writes and its permutation kernel and top-k selection read: the context's scratch, or
-// (inspection cache on) a chunk entry's own
-struct ChunkBufs {
-  DevBuf<uint32_t> row0, row1, tot, cases, ctrls, dcnt, dlist, rowz, linfo, lover, dover;
-  DevBuf<uint64_t> key;
-  void release() {
-    for (auto* b : {&row0, &row1, &tot, &cases, &ctrls, &dcnt, &dlist, &rowz, &linfo, &lover, &dover}) b->release();
-    key.release();
-  }
-};
-
-// What the inspector of one chunk of a join left behind -- expanded row numbers, statistics, score keys, lists, flags
-// and the chunk's top-k winners.  None of it depends on the permutation masks: with the inspection cache on
-// (gcre_set_inspect_cache) the buffers belong to the join index instead of the context's scratch, and the next
-// permutation window of the same join starts at the null kernel.
-struct ChunkInsp {
-  int64_t cb = -1, n = 0, s0 = 0, s1 = 0;
-  int64_t padded = 0;         // rows / totals are zero up to here (whole path tiles of the dense kernel)
-  bool inspected = false;     // rows / statistics / keys (and kept rows) are those of this chunk
-  bool with_lists = false;    // ... written by the inclusion-exclusion inspector: lists, rowz, linfo
-  bool in_recipe = false;     // ... into the kept set's recipe (not into the buffers below)
-  bool flags_valid = false;   // host copy of the inspector's flag block
-  bool win_valid = false;     // top-k winners
-  uint32_t flags[kFlagWords] = {};
-  Winners win;
-  ChunkBufs bufs;
-  void release() {
-    bufs.release();
-    inspected = with_lists = flags_valid = win_valid = false;
-  }
-};
-
-struct InspKey {
-  uint64_t p0_id = 0, p0_ver = 0, p1_id = 0, p1_ver = 0, red_id = 0, red_ver = 0, res_id = 0, obs_epoch = 0;
-  int64_t sb = 0, se = 0, keep_begin = 0, keep_end = 0, chunk_paths = 0;
-  int keep_mode = 0, top_k = 0, null_kernel = 0;
-  bool operator==(const InspKey& o) const {
-    return p0_id == o.p0_id && p0_ver == o.p0_ver && p1_id == o.p1_id && p1_ver == o.p1_ver && red_id == o.red_id &&
-           red_ver == o.red_ver && res_id == o.res_id && obs_epoch == o.obs_epoch && sb == o.sb && se == o.se &&
-           keep_begin == o.keep_begin && keep_end == o.keep_end && chunk_paths == o.chunk_paths && keep_mode == o.keep_mode &&
-           top_k == o.top_k && null_kernel == o.null_kernel;
-  }
-};
-
-inline double key_to_score(uint64_t k) {
-  const uint64_t b = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
-  double d;
-  std::memcpy(&d, &b, sizeof d);
-  return d;
 }
 
 inline size_t tri(size_t t) { return t * (t + 1) / 2; }
@@ -208,364 +86,9 @@ struct HostTimer {
 
 }  // namespace
 
-// RCCL, loaded on first use (gcre_process_paths_devices with several distinct devices, gcre_rccl_selftest): the library
-// does not link librccl, so a one-GPU user -- the R drop-in's default -- never needs it.  north_star: "RCCL all-reduce over
-// xGMI of the per-permutation null maxima": ncclAllReduce(ncclMax) on each device's stream, in place on the device, for
-// the thresholds shared inside a join and for the per-level merge; the host hub below stays the fallback (RCCL missing,
-// a device listed twice) and the place where the device threads meet under a deadline before every collective.
 std::atomic<int64_t> g_rccl_collectives{0};   // RCCL collectives issued by this process (gcre_rccl_collectives)
 
-struct RcclApi {
-  void* so = nullptr;
-  decltype(&ncclCommInitAll) comm_init_all = nullptr;
-  decltype(&ncclCommDestroy) comm_destroy = nullptr;
-  decltype(&ncclAllReduce) all_reduce = nullptr;
-  decltype(&ncclGetErrorString) error_string = nullptr;
-  bool ok = false;
-  static RcclApi& get() {
-    static RcclApi api = [] {
-      RcclApi a;
-      const char* off = std::getenv("GCRE_RCCL");
-      if (off && std::strcmp(off, "0") == 0) return a;   // GCRE_RCCL=0: host hub only
-      for (const char* name : {"librccl.so", "librccl.so.1", "/opt/rocm/lib/librccl.so"}) {
-        a.so = dlopen(name, RTLD_NOW | RTLD_LOCAL);
-        if (a.so) break;
-      }
-      if (!a.so) return a;
-      a.comm_init_all = (decltype(a.comm_init_all))dlsym(a.so, "ncclCommInitAll");
-      a.comm_destroy = (decltype(a.comm_destroy))dlsym(a.so, "ncclCommDestroy");
-      a.all_reduce = (decltype(a.all_reduce))dlsym(a.so, "ncclAllReduce");
-      a.error_string = (decltype(a.error_string))dlsym(a.so, "ncclGetErrorString");
-      a.ok = a.comm_init_all && a.comm_destroy && a.all_reduce && a.error_string;
-      return a;
-    }();
-    return api;
-  }
-};
-
-// gcre_process_paths_devices: the device threads of one call meet here to MAX-merge their running null maxima during a
-// join (gcre_join_opts.exchange, served inside the library).  K floats per call: the host does the reduction.  With RCCL
-// the data stays on the devices and only the meeting (`meet`) happens here.
-struct ExchangeHub {
-  int n = 0;
-  std::mutex m;
-  std::condition_variable cv;
-  int arrived = 0;
-  uint64_t gen = 0;
-  bool failed = false, timed_out = false;
-  double timeout_s = 300.0;
-  std::vector<float> acc, result;
-  uint64_t round_tag = 0;
-  // tag = (level, permutation window, ordinal of the exchange inside the join): every device of a round must bring the same
-  // one -- a device that skipped or repeated an exchange would otherwise MAX another level's maxima into the thresholds
-  int reduce(std::vector<float>& mine, uint64_t tag) {   // in: this device's maxima; out: the MAX over all devices
-    std::unique_lock<std::mutex> lk(m);
-    if (failed) return 1;
-    if (arrived == 0) {
-      acc = mine;
-      round_tag = tag;
-    } else {
-      if (acc.size() != mine.size() || tag != round_tag) { failed = true; cv.notify_all(); return 1; }
-      for (size_t i = 0; i < mine.size(); i++) acc[i] = std::max(acc[i], mine[i]);
-    }
-    if (++arrived == n) {
-      result.swap(acc);
-      arrived = 0;
-      gen++;
-      cv.notify_all();
-    } else {
-      // a device that never arrives (its thread died, it took another road through the join) must not hold the others for
-      // ever: past the deadline the round -- and with it the call -- fails (GCRE_HUB_TIMEOUT_S, default 300 s: a join of
-      // configs[4] on a shared GPU takes seconds)
-      const uint64_t g = gen;
-      if (!cv.wait_for(lk, std::chrono::duration<double>(timeout_s), [&] { return gen != g || failed; })) {
-        failed = true;
-        timed_out = true;
-        cv.notify_all();
-        return 1;
-      }
-      if (gen == g) return 1;   // somebody failed before this round completed
-    }
-    mine = result;
-    return 0;
-  }
-  // every device arrives with the same tag or the round fails; no data (the collective that follows moves it)
-  int meet(uint64_t tag) {
-    std::vector<float> none;
-    return reduce(none, tag);
-  }
-  void fail() {
-    std::lock_guard<std::mutex> lk(m);
-    failed = true;
-    cv.notify_all();
-  }
-};
-
-namespace { struct JoinPlan; }
-
-struct gcre_ctx {
-  Geometry g{};
-  int device = 0;
-  int top_k = 12;   // JoinExec::top_k, gcre.h:120
-  hipStream_t stream = nullptr;
-  // the top-k selection of a chunk only reads the keys its inspector wrote: it runs beside the warm-up slice and the
-  // null kernel on a stream of its own (GCRE_SELECT_STREAM=0: on the main stream, as in round 1)
-  hipStream_t sel_stream = nullptr;
-  hipEvent_t ev_sel = nullptr, ev_sel_done = nullptr;
-  bool sel_async = true;
-  // Inspect-ahead (gcre_join_ahead, round 4).  The inspector of the NEXT join of a sequence only needs what the current
-  // join's inspector wrote (kept rows, recipe) -- not its permutation kernel -- so it runs on a stream of its own while
-  // that kernel is in flight, into the next join's inspection cache; the next join then starts at its null kernel.
-  hipStream_t insp_stream = nullptr;
-  hipEvent_t ev_insp_done = nullptr;    // recorded on insp_stream when an ahead inspection has queued all its work
-  hipEvent_t ev_insp_main = nullptr;    // recorded on the main stream behind the last inspector that ran there
-  hipEvent_t ev_tail = nullptr;         // behind a join's own result copies, before the chain it launches
-  uint32_t* d_max_tot_b = nullptr;      // the flag block of ahead inspections (the null kernel in flight owns d_max_tot)
-  std::vector<JoinPlan>* ahead = nullptr;   // the registered later joins of the sequence, consumed by the next join call
-  bool ahead_closed = false;            // a join that cannot run ahead was offered: nothing behind it is registered either
-  bool ahead_on = true;                 // GCRE_AHEAD=0 turns gcre_join_ahead into a no-op.  The caller decides which joins to register:
-                                        // measured, the chain is worth 8 % on configs[1] (host gaps between small joins) and
-                                        // 0.5 % on configs[2] -- there the next level's inspector and this level's permutation
-                                        // kernel each fill the GPU (26.1 + 9.9 ms of kernel time inside 31.1 ms instead of
-                                        // 23.0 + 6.0 one after the other)
-  SelectState h_sel{};               // where the digit passes' state lands (outlives any one chunk: the copy is asynchronous)
-  std::string err;
-  int last_code = GCRE_OK;
-  bool quiet = false;
-  bool have_table = false, have_perms = false;
-  int64_t chunk_paths = int64_t(1) << 25;
-  int null_blocks_per_cu = 12;
-  int cus = 256;                     // compute units of the device (read once at gcre_create)
-  int64_t overlap_launches = 0;      // k_set_overlap launches of this context (gcre_overlap_launches)
-  int64_t stepdown_launches = 0;     // k_stepdown_null / k_stepdown_finish launches of this context (gcre_stepdown_launches)
-
-  // resident inputs
-  uint64_t* d_case_mask = nullptr;   // [Wp]
-  uint32_t* d_masks = nullptr;       // [W32p][Kpad]
-  float* d_t32 = nullptr;            // method 1 null table
-  double* d_dvt = nullptr;           // observed-score table
-  double* d_dmax = nullptr;          // method 2 null table (vtmax)
-  double* d_dmaxn = nullptr;         // its mirror image, only where vtmax is not symmetric (a NaN on one side of the diagonal)
-  uint32_t* d_null = nullptr;        // [Kpad]
-  uint32_t* d_mt = nullptr;          // transposed masks for the sparse kernel [nkt][64*Wp + 1][64]
-  bool mt_stale = false;             // d_masks changed while the sparse kernel was off: d_mt (if any) holds older masks
-  int ieq_batch = 0;                 // GCRE_IEQ_BATCH: quads per ticket of the quad kernel (0: twice ie_batch)
-  int ie_quad = 1;                   // GCRE_IE_QUAD=0: the pruned method-1 launches stay on k_null_ie_m1 (cross-check)
-  int ie_flagq = 1;                  // GCRE_IE_FLAGQ=0: the quad kernel's second look + exact pass instead of the flag queue (A/B runs, tests)
-  int ie_zwide = 0;                  // GCRE_IE_ZWIDE=1: the quad kernel reaches every added row through a descriptor of its own (tests)
-  int ie_warm_items = 4;             // (segment, tile) items per wave of the warm-up launch (GCRE_IE_WARM_ITEMS)
-  int exchange_tail = 0;             // slices of the pruned launch that are equal steps at its end (GCRE_EXCHANGE_TAIL; -1: half of them; 0: doubling slices only)
-  int ie_warm_segs = 1024;           // least number of segments in the warm-up slice (GCRE_IE_WARM; 2048 until round 3: the filter's second look made early thresholds matter less)
-  int ie_small_join_tiles = 8;       // GCRE_IE_SJT (tuning)
-  int ie_batch = 2;                  // segments per ticket (GCRE_IE_BATCH)
-  uint32_t* d_queue = nullptr;       // ticket counters of the pruned kernels' work queues (8 x 16 words)
-  uint32_t* d_max_tot = nullptr;     // the flag block of the inspectors (FlagWord, gcre_kernels.h)
-  uint32_t* d_ladder = nullptr;      // method 1: pruning ladder of the null table [kLadderLevels][TD]
-  uint32_t g00_rows = 0xffffffffu;   // method 2: vtmax[0][0] in ladder rows, rounded up (IeArgs::g00_rows)
-  int null_kernel = 0;               // 0 auto, 1 dense, 2 sparse, 3 ie (GCRE_NULL_KERNEL)
-  int sparse_waves_per_cu = 32;
-  int ie_prune = 1;                  // GCRE_IE_PRUNE=0 looks every count up (diagnostics)
-  uint64_t mask_epoch = 0;           // bumped whenever the permutation masks change: count planes are per epoch
-  uint64_t obs_epoch = 0;            // bumped whenever the value table changes: observed scores (keys, winners) are per epoch
-  bool insp_cache = false;           // gcre_set_inspect_cache: a join's inspector output stays with its join index
-  ExchangeHub* hub = nullptr;        // set by gcre_process_paths_devices for the duration of a call
-  ncclComm_t comm = nullptr;         // ... and this device's RCCL communicator when the devices are distinct and RCCL loads
-  int64_t rccl_calls = 0;            // collectives this context issued during the call (diagnostics, tests)
-  DevBuf<float> d_hub_null;          // the maxima this device hands to the hub
-  int hub_level = 0, hub_round = 0;  // what the next exchange of this device is: part of the hub's round tag
-  // permutation window [win_k0, win_k0 + win_K): what a join scores.  The whole range by default; gcre_set_perm_window
-  // narrows it so that the count planes of the kept sets (one per 2048-permutation tile) fit in device memory
-  int win_k0 = 0, win_K = 0;
-  int win_K_nominal = 0;   // the largest window since the masks were set: whether a kept set leaves with planes or with a recipe
-                           // is decided for THAT size, so that a short last window does not flip the decision (and hipMalloc
-                           // gigabytes of planes for one window: 120-460 ms on a fresh context)
-
-  // per-join scratch
-  ChunkBufs scratch;                 // a chunk's buffers when the inspection cache is off
-  DevBuf<uint32_t> d_sel, d_small, d_chunk, d_rec_segs;
-  DevBuf<uint64_t> d_wkey, d_doff, d_scan, d_excess, d_excess_b;
-  DevBuf<uint32_t> d_wcases, d_wctrls, d_wrow0, d_wrow1;
-  DevBuf<uint64_t> d_ie_timing;      // GCRE_IE_TIMING: the section counters of a diagnostics build's pruned kernels
-
-  // count-plane buffers of freed path sets, kept for the next set that needs one (hipMalloc of tens of GB costs
-  // ~40 ms per GB on this platform, hipFree nothing)
-  struct PlaneBuf { uint32_t* p; size_t bytes; };
-  std::vector<PlaneBuf> plane_pool;
-  // live path sets by id: a recipe names its operands by id + version, never by pointer alone
-  std::unordered_map<uint64_t, const gcre_pathset*> live_sets;
-  std::vector<gcre_uids*> live_uids;   // join indices created on this context (gcre_destroy releases what is still alive)
-  // per-gene best-path tallies (gcre_gene_tally): the ones alive on this context, the one the next join
-  // folds into (gcre_join_set_tally), and the ones the next gcre_process_paths hands to its levels
-  std::vector<gcre_gene_tally*> live_tallies;
-  gcre_gene_tally* armed_tally = nullptr;
-  gcre_gene_tally* pp_tally[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  // null exceedance counts (gcre_exceed): alive, armed for the next join, armed for the next gcre_process_paths
-  std::vector<gcre_exceed*> live_exceeds;
-  gcre_exceed* armed_exceed = nullptr;
-  gcre_exceed* pp_exceed[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  uint64_t next_set_id = 0;
-  size_t planes_out_max = (size_t)8 << 30;   // kept sets (method 1) whose planes are larger keep a recipe only
-
-  gcre_profile prof{};
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_null, ev_stats;
-  std::vector<hipEvent_t> ev_pool;
-};
-
-// How a kept path set was made: row r = row row0[r] of set A | row rowz[r] of set Z, with the producing
-// join's list (the overlap of the two rows, or what Z adds) as its inspector left it.  Enough to rebuild the count
-// planes of any row for any permutation tile from the planes of A and Z, so the set's own planes (3 KB per row and
-// tile) need not be stored, written or read.  Independent of the masks.
-struct gcre_recipe {
-  uint64_t a_id = 0, z_id = 0;     // the operands: path-set ids and the versions of their rows
-  uint64_t a_ver = 0, z_ver = 0;
-  DevBuf<uint32_t> row0, rowz, linfo, lover, slot, over, tot;   // tot: carriers of every kept row
-  uint32_t max_len = 0;            // longest list (padded) the producing join's inspector wrote
-  bool valid = false;
-  void release() {
-    for (auto* b : {&row0, &rowz, &linfo, &lover, &slot, &over, &tot}) b->release();
-    valid = false;
-  }
-};
-
-struct gcre_pathset {
-  gcre_ctx* ctx;
-  int64_t nrows;
-  uint64_t* d_rows;   // max(nrows,1) x S words
-  uint64_t id = 0;                 // never reused inside a context
-  mutable uint64_t version = 0;    // bumped when the rows are rewritten
-  mutable gcre_recipe* rec = nullptr;
-  // CSR bit lists for the sparse kernel, built on first use and dropped whenever the rows are rewritten
-  mutable uint64_t* d_loff = nullptr;
-  mutable uint32_t* d_lidx = nullptr;
-  mutable std::vector<uint64_t> h_loff;   // host copy of the offsets (sizes the work of a sparse launch)
-  mutable uint32_t max_bits = 0;          // longest list (entries incl. padding): bounds the carriers of any row
-  mutable bool max_known = false;
-  mutable int one_sided = -1;             // method 2: every row has an empty half (-1: not looked at; from h_loff)
-  // count planes for the inclusion-exclusion kernel: [tile][row*M+h][groups][64][4] dwords, valid for one mask epoch
-  mutable uint32_t* d_planes = nullptr;
-  mutable int plane_groups = 0;
-  mutable size_t planes_bytes = 0;   // capacity of d_planes
-  mutable uint64_t planes_epoch = 0;
-  mutable bool planes_valid = false;
-  mutable int64_t planes_lo = 0, planes_hi = 0;   // rows whose planes are valid (a multi-device join fills a range)
-  mutable bool planes_wanted = false;   // a later join had to rebuild this set's planes from its bit lists: next time the
-                                        // join that writes its rows leaves the planes too, whatever their size
-};
-
-// UidRelSet (src/gcre.h:49-90) resident on the device: prefix sums of count, locations, signs
-struct gcre_uids {
-  gcre_ctx* ctx;
-  int path_length;
-  int64_t n_uids;
-  int64_t n_signs;
-  int64_t total;      // count_total_paths()
-  int64_t max_loc;    // largest paths1 row referenced, -1 if none
-  int64_t max_idx;    // largest uid row with count > 0, -1 if none
-  int64_t* d_path_idx;
-  int64_t* d_location;
-  int32_t* d_signs;
-  std::vector<int64_t> h_path_idx;   // host copy, for building the sparse kernel's segment tables
-  mutable std::vector<int64_t> h_nonempty;   // prefix count of the uids with count > 0 (built on first use)
-  std::vector<int64_t> h_location;   // host copy: segments are ordered by the paths1 rows they join (L2 reuse of their planes)
-  struct SegCache {
-    int64_t first, count, score_b, score_e, plane_b, plane_e;
-    int64_t nsegs, nscored;
-    SparseSeg* d_segs;
-    // quad table of the pruned method-1 kernel (gcre_ieq.hip), built on first use for one warm-up length: runs of up to
-    // four consecutive segments that join the same paths1 rows, none straddling `q_warm` or `nscored`
-    std::vector<SparseSeg> h_segs;
-    int64_t q_warm = -1, nquads = 0, quad_begin = 0;
-    uint32_t* d_quads = nullptr;
-  };
-  mutable std::vector<SegCache> seg_cache;
-  // A segment table (and its quads) built ahead of the join that will ask for it, by a helper thread that touches nothing
-  // but the host copies of the join index (gcre_process_paths: the last level's tables while the first levels run)
-  struct Prefetch {
-    int64_t first = 0, count = 0, score_b = 0, score_e = 0, plane_b = 0, plane_e = 0;
-    std::vector<SparseSeg> segs;
-    int64_t nscored = 0;
-    std::vector<uint32_t> quads;
-    int64_t q_warm = -1, quad_begin = 0;
-    bool ready = false, quads_ready = false, quads_for_table = false;
-    std::thread th;
-  };
-  mutable std::unique_ptr<Prefetch> prefetch;
-  // inspection cache (gcre_set_inspect_cache): the inspector output of the last join that ran on this index, per chunk,
-  // valid while the operands' rows, the kept set, the shard and the observed-score inputs are the same
-  mutable std::deque<ChunkInsp> insp;
-  mutable InspKey insp_key;
-  mutable bool insp_valid = false;       // the join completed: every chunk entry describes it
-  mutable bool insp_hinted = false;      // ... with the reduced operand standing (the hint was not broken)
-  mutable uint64_t insp_res_ver = 0;     // version of the kept set's rows as that join left them
-  // A join on this index whose permutation kernels were LAUNCHED ahead (gcre_join_ahead chain): they write into the index's
-  // own maxima, the winners are the inspection cache's; the join call that comes for it only waits, copies and merges
-  struct Launched {
-    bool active = false;
-    InspKey key;
-    uint64_t res_ver = 0, mask_epoch = 0;
-    int win_k0 = 0, win_K = 0;
-    std::vector<Candidate> cands;
-    DevBuf<uint32_t> d_null;              // Kpad running maxima + one word: the launch's look-up counter
-    hipEvent_t done = nullptr;            // behind the last kernel of the launch (main stream)
-    gcre_profile prof{};                  // what the ahead inspection and the launch accumulated for this join
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_null, ev_stats;
-  };
-  mutable Launched launch;
-  // optional hint (gcre_uids_set_reduced): paths0[idx] | paths1[loc] == paths0[idx] | red[red_index[loc]] for every
-  // joined path; checked on the device for every join, ignored when it does not hold
-  const gcre_pathset* red = nullptr;
-  uint64_t red_id = 0;             // the set's id: a freed operand is noticed, not dereferenced
-  int32_t* d_red_index = nullptr;
-  int64_t n_red_index = 0;
-  // distinct (location, count) ranges of the uids (all uids with the same pivot gene share one): built on first use
-  mutable int64_t n_ranges = -1;
-  mutable int32_t* d_range_of = nullptr;    // uid -> range
-  mutable int64_t n_pairs = 0;              // (range, paths1 row) pairs = sum of the range lengths
-  mutable int32_t* d_pair_range = nullptr;
-  mutable int64_t* d_pair_loc = nullptr;
-};
-
-// The per-gene best-path table of one join: which slots a joined path touches -- through its paths0 row
-// and through its paths1 row -- and, per slot, the best joined path seen so far under (key, then smaller ordinal).
-struct gcre_gene_tally {
-  gcre_ctx* ctx = nullptr;
-  int n_slots = 0;
-  int64_t n_rows0 = 0, n_rows1 = 0;
-  int w0 = 0, w1 = 0;                 // 0: the operand contributes no gene
-  int32_t *d_genes0 = nullptr, *d_genes1 = nullptr;
-  uint64_t* d_ck = nullptr;           // chunk-local tables: empty between folds (k_gene_merge leaves them so)
-  uint32_t* d_cidx = nullptr;
-  uint64_t* d_bkey = nullptr;         // the table
-  int64_t* d_bord = nullptr;
-  int32_t *d_bsrc = nullptr, *d_btrg = nullptr, *d_bcases = nullptr, *d_bctrls = nullptr;
-  hipStream_t last = nullptr;         // the stream of the last fold: a read waits for it
-  bool folded = false;                // the table holds something (k_gene_fold then also tests against it)
-  bool folding = false;               // a fold did not get all its launches queued: the chunk-local tables are cleared first
-};
-
-// Null exceedance counts of one list of thresholds.  The thresholds are kept sorted ascending on the
-// device, as f32 bit patterns for the null values and as score keys for the observed scores; a counted value lands in the
-// bin of the largest threshold it reaches, and a read sums the bins from each threshold upwards.  Sums: every chunk counted
-// adds, whichever stream it ran on.
-struct gcre_exceed {
-  gcre_ctx* ctx = nullptr;
-  int m = 0;
-  std::vector<int32_t> order;         // sorted position -> the caller's index
-  std::vector<double> thr;            // the thresholds as given (gcre_exceed_stepdown compares scores with them)
-  uint32_t* d_pat = nullptr;          // [m] ascending
-  uint64_t* d_tkey = nullptr;         // [m] ascending
-  unsigned long long* d_hist = nullptr;    // [m] (path, permutation) pairs per bin
-  unsigned long long* d_ohist = nullptr;   // [m] joined paths per bin
-  int64_t perms = 0, paths = 0;       // permutations / joined paths that went into the bins
-  // per-permutation counts (gcre_exceed_keep_perm_counts): cell [bin][r] = values of permutation r in the bin
-  uint32_t* d_pc = nullptr;           // [m][pc_stride] u32, or nullptr: not kept
-  int pc_stride = 0;                  // the context's Kpad
-  std::vector<uint64_t> pc_load;      // per 2048-permutation tile: joined paths counted into its permutations' cells
-};
-
-namespace {
-
-int fail(gcre_ctx* c, int code, const std::string& msg) {
+int gcre_host::fail(gcre_ctx* c, int code, const std::string& msg) {
   if (c) {
     c->err = msg;
     c->last_code = code;
@@ -575,12 +98,7 @@ int fail(gcre_ctx* c, int code, const std::string& msg) {
   return code;
 }
 
-#define HIP_TRY(ctx, expr)                                                                            \
-  do {                                                                                                \
-    hipError_t e__ = (expr);                                                                          \
-    if (e__ != hipSuccess)                                                                            \
-      return fail((ctx), GCRE_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e__));        \
-  } while (0)
+namespace {
 
 hipEvent_t get_event(gcre_ctx* c) {
   if (!c->ev_pool.empty()) {
@@ -667,10 +185,12 @@ int transpose_masks(gcre_ctx* c) {
   return GCRE_OK;
 }
 
+}  // namespace
+
 // The permutation masks have changed.  Whatever was derived from the old ones is void whether or not the count-plane
 // kernels are on at this moment: a later value table can turn them on again (sparse_enabled), and must then find neither
 // the old transposed copy nor count planes or a launch-ahead record of the old epoch.
-int build_transposed_masks(gcre_ctx* c) {
+int gcre_host::build_transposed_masks(gcre_ctx* c) {
   c->mask_epoch++;   // every count plane built so far belongs to the old masks
   c->mt_stale = true;
   if (!sparse_enabled(c)) return GCRE_OK;   // (gcre_set_value_table makes the copy if a table brings the kernels back)
@@ -680,6 +200,8 @@ int build_transposed_masks(gcre_ctx* c) {
   c->win_K_nominal = 0;
   return GCRE_OK;
 }
+
+namespace {
 
 void drop_planes(const gcre_pathset* ps) {
   if (ps->d_planes) {
@@ -1188,40 +710,6 @@ int select_chunk(gcre_ctx* c, const uint64_t* key, int64_t count, int k, uint32_
   HIP_TRY(c, hipStreamSynchronize(sst));
   return select_finish(c, key, count, k, hs, n_selected, sst);
 }
-
-struct JoinPlan {
-  const gcre_uids* u;
-  const gcre_pathset* p0;
-  const gcre_pathset* p1;
-  gcre_pathset* res;
-  bool sharded;
-  int64_t shard_begin, shard_end;
-  void* d_null_out;
-  bool keep_ranged = false;        // rows outside [keep_begin, keep_end) and the shard are not produced at all
-  bool planes_ranged = false;      // every row is produced, count planes only for [keep_begin, keep_end) and the shard
-  int64_t keep_begin = 0, keep_end = 0;
-  // thresholds shared with the other devices during the join (gcre_join_opts.exchange)
-  int exchanges = 0;
-  int (*exchange)(void*, void*, int32_t, int32_t) = nullptr;
-  void* exchange_user = nullptr;
-  gcre_gene_tally* tally = nullptr;   // the join's scored paths are folded into it (never set on a registered later join)
-  gcre_exceed* exceed = nullptr;      // the join's null values and observed scores are counted into it (the same)
-  bool exceed_observed = true;        // ... the observed scores too (false: a later permutation window of the same join)
-  void take(const gcre_join_opts* o) {
-    if (!o) return;
-    if (o->keep_ranged) {
-      keep_ranged = o->keep_ranged == 1;
-      planes_ranged = o->keep_ranged == 2;
-      keep_begin = o->keep_begin;
-      keep_end = o->keep_end;
-    }
-    if (o->exchange && o->exchanges > 0 && o->d_null_out) {
-      exchanges = o->exchanges;
-      exchange = o->exchange;
-      exchange_user = o->exchange_user;
-    }
-  }
-};
 
 void drop_ahead(gcre_ctx* c) {
   delete c->ahead;
@@ -3372,463 +2860,6 @@ int gcre_set_perm_masks(gcre_ctx* c, const uint64_t* masks, int nrow) {
   return GCRE_OK;
 }
 
-int gcre_generate_perm_masks(gcre_ctx* c, uint64_t seed, const int32_t* stratum, int n_strata) {
-  if (!c || (stratum && n_strata < 1)) return fail(c, GCRE_ERR_ARG, "bad strata");
-  (void)hipSetDevice(c->device);
-  const Geometry& g = c->g;
-  if (g.K == 0) { c->have_perms = true; return GCRE_OK; }
-  if (!stratum) n_strata = 1;
-  // cases are the first n_cases patient columns (join_base.cpp:50-54): cases and size per stratum
-  std::vector<uint32_t> cases_in((size_t)n_strata, 0), size_of((size_t)n_strata, 0);
-  for (int q = 0; q < g.n; q++) {
-    const int s = stratum ? stratum[q] : 0;
-    if (s < 0 || s >= n_strata) return fail(c, GCRE_ERR_RANGE, "stratum id out of range");
-    size_of[(size_t)s]++;
-    if (q < g.n_cases) cases_in[(size_t)s]++;
-  }
-  uint32_t *d_cases = nullptr, *d_size = nullptr, *d_work = nullptr;
-  int32_t* d_str = nullptr;
-  hipError_t e = hipMalloc((void**)&d_cases, (size_t)n_strata * 4);
-  if (e == hipSuccess) e = hipMalloc((void**)&d_size, (size_t)n_strata * 4);
-  if (e == hipSuccess) e = hipMalloc((void**)&d_work, (size_t)g.K * n_strata * 2 * 4);
-  if (e == hipSuccess && stratum) e = hipMalloc((void**)&d_str, (size_t)g.n * 4);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_cases, cases_in.data(), (size_t)n_strata * 4, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_size, size_of.data(), (size_t)n_strata * 4, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess && stratum) e = hipMemcpyAsync(d_str, stratum, (size_t)g.n * 4, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess)
-    e = launch_generate_masks(seed, g.K, g.n, n_strata, d_str, d_cases, d_size, d_work, 2 * g.Wp, g.Kpad, c->d_masks, c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  for (void* p : {(void*)d_cases, (void*)d_size, (void*)d_work, (void*)d_str})
-    if (p) (void)hipFree(p);
-  if (e != hipSuccess) return fail(c, GCRE_ERR_DEVICE, std::string("generate_perm_masks: ") + hipGetErrorString(e));
-  if (int rc = build_transposed_masks(c)) return rc;
-  c->have_perms = true;
-  return GCRE_OK;
-}
-
-int gcre_decorated_pvalues(gcre_ctx* c, const gcre_dp_input* in, gcre_dp_split* out, int64_t cap, int64_t* n_out,
-                           int32_t* perm_counts) {
-  if (!c) return GCRE_ERR_ARG;
-  if (!in || !n_out) return fail(c, GCRE_ERR_ARG, "decorated_pvalues: NULL argument");
-  const Geometry& g = c->g;
-  if (!c->have_table || !c->d_dvt) return fail(c, GCRE_ERR_ASSERT, "assertion: decorated_pvalues needs a value table");
-  if (in->method != g.method || in->n_cases != g.n_cases || in->n_cases + in->n_ctrls != g.n)
-    return fail(c, GCRE_ERR_ASSERT, "assertion: decorated_pvalues input does not match the context (method, cases, controls)");
-  // the host stage: counts and urns (the observed scores come from the device's own table below)
-  gcre_dp_input hin = *in;
-  std::vector<gcre_dp_stratum> st;
-  if (hin.stratum && !hin.strata_out && hin.n_strata > 0 && cap > 0) {
-    st.resize((size_t)cap * (size_t)hin.n_strata);
-    hin.strata_out = st.data();
-  }
-  int rc = gcre_decorated_splits(&hin, nullptr, 0, 0, 0, out, cap, n_out);
-  if (rc == GCRE_ERR_RANGE) return fail(c, rc, "decorated_pvalues: out of range (row index, stratum id or output capacity)");
-  if (rc != GCRE_OK) return fail(c, rc, "decorated_pvalues: bad input");
-  const int64_t S = *n_out;
-  const int K = in->iterations;
-  if (S == 0) return GCRE_OK;
-  if (S > 0x7fffffff) return fail(c, GCRE_ERR_ARG, "decorated_pvalues: too many splits");
-  // the kernel's view: sub-path-1 counts, observed counts, urns, strata that draw, stream key
-  std::vector<DpUrns> urns((size_t)S);
-  std::vector<DpStratum> dst;
-  for (int64_t i = 0; i < S; i++) {
-    const gcre_dp_split& o = out[i];
-    DpUrns& u = urns[(size_t)i];
-    std::memset(&u, 0, sizeof u);
-    u.key = dp_split_key(in->seed, i);
-    if (!o.valid) continue;   // counts 0, no draws: p-value NaN below
-    u.case_pos1 = o.case_pos1;
-    u.ctrl_pos1 = o.ctrl_pos1;
-    u.case_neg1 = o.case_neg1;
-    u.ctrl_neg1 = o.ctrl_neg1;
-    u.case_pos2 = o.case_pos2;
-    u.ctrl_pos2 = o.ctrl_pos2;
-    u.case_neg2 = o.case_neg2;
-    u.ctrl_neg2 = o.ctrl_neg2;
-    u.k_pos = o.k_pos;
-    u.k_neg = o.k_neg;
-    u.pop_pos = o.pop_pos;
-    u.succ_pos = o.succ_pos;
-    u.pop_neg = o.pop_neg;
-    u.succ_neg = o.succ_neg;
-    if (o.strata_off >= 0) {
-      u.st_off = (int32_t)dst.size();
-      for (int s = 0; s < in->n_strata; s++) {
-        const gcre_dp_stratum& q = hin.strata_out[o.strata_off + s];
-        if (q.k_pos + q.k_neg > 0) dst.push_back({q.pop, q.cases, q.k_pos, q.k_neg});
-      }
-      u.st_n = (int32_t)dst.size() - u.st_off;
-      // every draw of a stratified split happens inside its strata (st_n == 0 with k_pos == k_neg == 0: nothing to draw)
-    }
-  }
-  if (dst.size() > 0x7fffffffu) return fail(c, GCRE_ERR_ARG, "decorated_pvalues: too many strata");
-  (void)hipSetDevice(c->device);
-  DpUrns* d_urns = nullptr;
-  DpStratum* d_st = nullptr;
-  double* d_obs = nullptr;
-  unsigned long long* d_ge = nullptr;
-  int32_t* d_pc = nullptr;
-  const size_t pc_bytes = perm_counts ? (size_t)S * (size_t)K * 2 * 4 : 0;
-  std::vector<double> obs((size_t)S);
-  std::vector<unsigned long long> ge((size_t)S, 0);
-  hipError_t e = hipMalloc((void**)&d_urns, (size_t)S * sizeof(DpUrns));
-  if (e == hipSuccess) e = hipMalloc((void**)&d_st, std::max<size_t>(dst.size(), 1) * sizeof(DpStratum));
-  if (e == hipSuccess) e = hipMalloc((void**)&d_obs, (size_t)S * 8);
-  if (e == hipSuccess) e = hipMalloc((void**)&d_ge, (size_t)S * 8);
-  if (e == hipSuccess && pc_bytes) e = hipMalloc((void**)&d_pc, pc_bytes);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_urns, urns.data(), (size_t)S * sizeof(DpUrns), hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess && !dst.empty())
-    e = hipMemcpyAsync(d_st, dst.data(), dst.size() * sizeof(DpStratum), hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) e = hipMemsetAsync(d_ge, 0, (size_t)S * 8, c->stream);
-  if (e == hipSuccess) e = launch_decorated_observed(d_urns, (int)S, g.method, c->d_dvt, d_obs, c->stream);
-  if (e == hipSuccess)
-    e = launch_decorated_null(d_urns, d_st, (int)S, K, g.method, c->d_dvt, d_obs, d_ge, d_pc, c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(obs.data(), d_obs, (size_t)S * 8, hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(ge.data(), d_ge, (size_t)S * 8, hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess && pc_bytes) e = hipMemcpyAsync(perm_counts, d_pc, pc_bytes, hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  for (void* p : {(void*)d_urns, (void*)d_st, (void*)d_obs, (void*)d_ge, (void*)d_pc})
-    if (p) (void)hipFree(p);
-  if (e != hipSuccess) return fail(c, GCRE_ERR_DEVICE, std::string("decorated_pvalues: ") + hipGetErrorString(e));
-  for (int64_t i = 0; i < S; i++) {
-    gcre_dp_split& o = out[i];
-    if (!o.valid) continue;
-    o.score = obs[(size_t)i];
-    o.n_ge = (int64_t)ge[(size_t)i];
-    o.pvalue = K > 0 ? (double)o.n_ge / (double)K : std::numeric_limits<double>::quiet_NaN();
-  }
-  return GCRE_OK;
-}
-
-// The bit pattern of the smallest float x with (double)x >= score, among the non-negative floats null scores are: null
-// score r counts (R/ProcessPaths.R:316) iff its bits are >= this -- 0 when every one counts, past +inf when none does (NaN).
-static uint32_t f32_threshold(double score) {
-  if (score != score) return 0x7f800001u;
-  if (score <= 0) return 0u;
-  float f = (float)score;
-  if ((double)f < score) f = std::nextafter(f, std::numeric_limits<float>::infinity());
-  uint32_t b;
-  std::memcpy(&b, &f, 4);
-  return b;
-}
-
-// What gcre_score_sets refuses of a set list, before anything is launched (`who` opens the message): the context's state,
-// the shape of the input, every set's members and signs.
-static int check_sets(gcre_ctx* c, const gcre_set_input* in, const std::string& who) {
-  const Geometry& g = c->g;
-  if (!c->have_table || !c->d_dvt) return fail(c, GCRE_ERR_ASSERT, "assertion: " + who + " needs a value table");
-  if (g.K > 0 && !c->have_perms)
-    return fail(c, GCRE_ERR_ASSERT, "assertion: " + who + " needs the permutation masks (iterations > 0, none set)");
-  if (in->n_cols != g.n)
-    return fail(c, GCRE_ERR_ARG, who + ": the rows have " + std::to_string(in->n_cols) +
-                                     " columns, not n_cases + n_ctrls = " + std::to_string(g.n));
-  const int64_t S = in->n_sets;
-  if (S < 0 || in->n_rows < 0 || (S > 0 && (!in->set_off || !in->members)) || (in->n_rows > 0 && !in->rows))
-    return fail(c, GCRE_ERR_ARG, who + ": bad input (a negative count or a NULL array)");
-  for (int64_t s = 0; s < S; s++) {
-    const int64_t b = in->set_off[s], e = in->set_off[s + 1];
-    const std::string name = who + ": set " + std::to_string(s);
-    if (b < 0 || e <= b) return fail(c, GCRE_ERR_ARG, name + " has no members");
-    for (int64_t i = b; i < e; i++) {
-      const int32_t row = in->members[i];
-      if (row < -1 || row >= in->n_rows)
-        return fail(c, GCRE_ERR_RANGE, name + ": member row " + std::to_string(row) + " out of range (" +
-                                           std::to_string(in->n_rows) + " rows)");
-      if (in->signs && in->signs[i] != 1 && in->signs[i] != -1)
-        return fail(c, GCRE_ERR_ARG, name + ": sign " + std::to_string(in->signs[i]) + " is neither +1 nor -1");
-    }
-  }
-  return GCRE_OK;
-}
-
-// The host stage gcre_score_sets and gcre_exceed_stepdown share: the case / control masks of the n patients, and one set's
-// union rows -- P = the OR of its (+) members, N = P + Wp the OR of its (-) members (method 1: everything into P), within the
-// n patients -- with k = cases_pos, ctrls_pos, cases_neg, ctrls_neg.  `P` holds M * Wp zeroed words; no member is NA.
-struct SetUnion {
-  const Geometry& g;
-  std::vector<uint64_t> cases, ctrls;
-  explicit SetUnion(const Geometry& geo) : g(geo), cases((size_t)geo.W, 0), ctrls((size_t)geo.W, 0) {
-    for (int q = 0; q < g.n; q++) (q < g.n_cases ? cases : ctrls)[(size_t)q / 64] |= uint64_t(1) << (q % 64);
-  }
-  int count_and(const uint64_t* a, const std::vector<uint64_t>& m) const {
-    int n = 0;
-    for (int w = 0; w < g.W; w++) n += __builtin_popcountll(a[w] & m[w]);
-    return n;
-  }
-  void build(const gcre_set_input* in, int64_t s, uint64_t* P, int32_t k[4]) const {
-    const int W = g.W, M = g.method;
-    uint64_t* N = M == 2 ? P + g.Wp : P;
-    for (int64_t i = in->set_off[s]; i < in->set_off[s + 1]; i++) {
-      const uint64_t* r = in->rows + (size_t)in->members[i] * W;
-      uint64_t* d = (M == 2 && in->signs && in->signs[i] == -1) ? N : P;
-      for (int w = 0; w < W; w++) d[w] |= r[w] & (cases[w] | ctrls[w]);
-    }
-    k[0] = count_and(P, cases);
-    k[1] = count_and(P, ctrls);
-    k[2] = k[3] = 0;
-    if (M == 2) {
-      k[2] = count_and(N, ctrls);   // the (-) half counts the other way round (methods.h:183-184)
-      k[3] = count_and(N, cases);
-    }
-  }
-};
-
-int gcre_score_sets(gcre_ctx* c, const gcre_set_input* in, gcre_set_score* out, int64_t cap, int64_t* n_out,
-                    float* family_max) {
-  if (!c) return GCRE_ERR_ARG;
-  if (!in || !n_out || cap < 0 || (cap > 0 && !out)) return fail(c, GCRE_ERR_ARG, "score_sets: NULL argument");
-  *n_out = 0;
-  const Geometry& g = c->g;
-  const int K = g.K, M = g.method;
-  const int64_t S = in->n_sets;
-  if (int rc = check_sets(c, in, "score_sets")) return rc;
-  *n_out = S;
-  if (S > cap)
-    return fail(c, GCRE_ERR_RANGE, "score_sets: " + std::to_string(S) + " sets, room for " + std::to_string(cap) +
-                                       " records (out of range)");
-
-  // the host stage: per valid set the OR of its (+) members and of its (-) members (method 1: of all of them), within the
-  // n patients, and their counts; the device rows are [valid set][M][Wp] words, the dword view k_set_null reads
-  const int Wp = g.Wp;
-  const size_t RW = (size_t)M * Wp;
-  const SetUnion un(g);
-  const double nan = std::numeric_limits<double>::quiet_NaN();
-  std::vector<int64_t> vset;     // the valid sets, in input order
-  std::vector<uint64_t> urows;
-  std::vector<int32_t> cnt;      // [valid][4] cases_pos, ctrls_pos, cases_neg, ctrls_neg
-  std::vector<uint32_t> tot;     // [valid][M] carriers per half
-  for (int64_t s = 0; s < S; s++) {
-    gcre_set_score& o = out[s];
-    std::memset(&o, 0, sizeof o);
-    o.set = s;
-    o.score = nan;
-    o.pvalue = nan;
-    const int64_t b = in->set_off[s], e = in->set_off[s + 1];
-    bool valid = true;
-    for (int64_t i = b; i < e; i++) valid = valid && in->members[i] >= 0;
-    o.valid = valid ? 1 : 0;
-    if (!valid) continue;
-    const size_t v = vset.size();
-    vset.push_back(s);
-    urows.resize((v + 1) * RW, 0);
-    int32_t k[4];
-    un.build(in, s, urows.data() + v * RW, k);
-    o.cases_pos = k[0];
-    o.ctrls_pos = k[1];
-    o.cases_neg = k[2];
-    o.ctrls_neg = k[3];
-    o.cases = o.cases_pos + o.cases_neg;
-    o.ctrls = o.ctrls_pos + o.ctrls_neg;
-    cnt.insert(cnt.end(), k, k + 4);
-    tot.push_back((uint32_t)(k[0] + k[1]));
-    if (M == 2) tot.push_back((uint32_t)(k[2] + k[3]));
-  }
-  if (family_max) std::fill(family_max, family_max + K, 0.0f);
-  const int64_t V = (int64_t)vset.size();
-  if (V == 0) return GCRE_OK;
-
-  (void)hipSetDevice(c->device);
-  uint64_t* d_rows = nullptr;
-  int32_t* d_cnt = nullptr;
-  uint32_t *d_tot = nullptr, *d_thr = nullptr, *d_fam = nullptr;
-  double* d_obs = nullptr;
-  unsigned long long* d_ge = nullptr;
-  const bool fam = family_max && K > 0;
-  std::vector<double> obs((size_t)V);
-  std::vector<unsigned long long> ge((size_t)V, 0);
-  std::vector<uint32_t> fbits(fam ? (size_t)K : 0);
-  hipError_t e = hipMalloc((void**)&d_rows, urows.size() * 8);
-  if (e == hipSuccess) e = hipMalloc((void**)&d_cnt, cnt.size() * 4);
-  if (e == hipSuccess) e = hipMalloc((void**)&d_tot, tot.size() * 4);
-  if (e == hipSuccess) e = hipMalloc((void**)&d_thr, (size_t)V * 4);
-  if (e == hipSuccess) e = hipMalloc((void**)&d_obs, (size_t)V * 8);
-  if (e == hipSuccess) e = hipMalloc((void**)&d_ge, (size_t)V * 8);
-  if (e == hipSuccess && fam) e = hipMalloc((void**)&d_fam, (size_t)g.Kpad * 4);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_rows, urows.data(), urows.size() * 8, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_cnt, cnt.data(), cnt.size() * 4, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_tot, tot.data(), tot.size() * 4, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) e = launch_set_observed(d_cnt, V, M, c->d_dvt, d_obs, c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(obs.data(), d_obs, (size_t)V * 8, hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  if (e == hipSuccess && K > 0) {
-    std::vector<uint32_t> thr((size_t)V);
-    for (int64_t v = 0; v < V; v++) thr[(size_t)v] = f32_threshold(obs[(size_t)v]);
-    SetNullArgs a{};
-    a.rows = (const uint32_t*)d_rows;
-    a.masks = c->d_masks;   // all K permutations: the window of gcre_set_perm_window is the joins' business
-    a.tot = d_tot;
-    a.thr = d_thr;
-    a.t32 = c->d_t32;
-    a.d64 = c->d_dmax;
-    a.d64n = c->d_dmaxn ? c->d_dmaxn : c->d_dmax;
-    a.n_ge = d_ge;
-    a.fam_bits = d_fam;
-    a.nsets = V;
-    a.W32p = 2 * Wp;
-    a.Kpad = g.Kpad;
-    a.K = K;
-    a.nkt = (K + kSetPermTile - 1) / kSetPermTile;
-    const int64_t tpb = set_null_tile_sets(M);
-    a.npt = (V + tpb - 1) / tpb;
-    // one set tile per block while that makes at least ~8 blocks per resident block slot, more per block beyond
-    const int64_t slots = (int64_t)c->cus * 4 * 8;
-    const int64_t per = std::max<int64_t>(1, (a.npt * a.nkt) / slots);
-    a.pgroups = (int)std::min<int64_t>((a.npt + per - 1) / per, 0x7fffffff / std::max(a.nkt, 1));
-    e = hipMemcpyAsync(d_thr, thr.data(), (size_t)V * 4, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(d_ge, 0, (size_t)V * 8, c->stream);
-    if (e == hipSuccess && fam) e = hipMemsetAsync(d_fam, 0, (size_t)g.Kpad * 4, c->stream);
-    if (e == hipSuccess) e = launch_set_null(a, M, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(ge.data(), d_ge, (size_t)V * 8, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess && fam) e = hipMemcpyAsync(fbits.data(), d_fam, (size_t)K * 4, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  }
-  for (void* p : {(void*)d_rows, (void*)d_cnt, (void*)d_tot, (void*)d_thr, (void*)d_obs, (void*)d_ge, (void*)d_fam})
-    if (p) (void)hipFree(p);
-  if (e != hipSuccess) return fail(c, GCRE_ERR_DEVICE, std::string("score_sets: ") + hipGetErrorString(e));
-  for (int64_t v = 0; v < V; v++) {
-    gcre_set_score& o = out[vset[(size_t)v]];
-    o.score = obs[(size_t)v];
-    o.n_ge = (int64_t)ge[(size_t)v];
-    o.pvalue = K > 0 ? (double)o.n_ge / (double)K : nan;
-  }
-  if (fam) std::memcpy(family_max, fbits.data(), (size_t)K * 4);
-  return GCRE_OK;
-}
-
-// Carrier overlaps of caller-given sets: the validation of gcre_score_sets, the OR of every valid set's
-// members on the host, then k_set_overlap over the `a` list in slabs whose device output stays under GCRE_OVERLAP_SLAB_MB.
-int gcre_set_overlap(gcre_ctx* c, const gcre_set_input* in, const int64_t* a, int64_t na, const int64_t* b, int64_t nb,
-                     int32_t* size, int32_t* both) {
-  if (!c) return GCRE_ERR_ARG;
-  if (!in) return fail(c, GCRE_ERR_ARG, "set_overlap: NULL argument");
-  const Geometry& g = c->g;
-  if (in->n_cols != g.n)
-    return fail(c, GCRE_ERR_ARG, "set_overlap: the rows have " + std::to_string(in->n_cols) +
-                                     " columns, not n_cases + n_ctrls = " + std::to_string(g.n));
-  const int64_t S = in->n_sets;
-  if (S < 0 || in->n_rows < 0 || (S > 0 && (!in->set_off || !in->members)) || (in->n_rows > 0 && !in->rows))
-    return fail(c, GCRE_ERR_ARG, "set_overlap: bad input (a negative count or a NULL array)");
-  if (na < 0 || nb < 0 || (!a && na != S) || (!b && nb != S))
-    return fail(c, GCRE_ERR_ARG, "set_overlap: bad index list (a negative length, or NULL with a length other than n_sets)");
-  for (int64_t s = 0; s < S; s++) {
-    const int64_t lo = in->set_off[s], hi = in->set_off[s + 1];
-    const std::string name = "set_overlap: set " + std::to_string(s);
-    if (lo < 0 || hi <= lo) return fail(c, GCRE_ERR_ARG, name + " has no members");
-    for (int64_t i = lo; i < hi; i++) {
-      const int32_t row = in->members[i];
-      if (row < -1 || row >= in->n_rows)
-        return fail(c, GCRE_ERR_RANGE, name + ": member row " + std::to_string(row) + " out of range (" +
-                                           std::to_string(in->n_rows) + " rows)");
-      if (in->signs && in->signs[i] != 1 && in->signs[i] != -1)
-        return fail(c, GCRE_ERR_ARG, name + ": sign " + std::to_string(in->signs[i]) + " is neither +1 nor -1");
-    }
-  }
-  for (int side = 0; side < 2; side++) {
-    const int64_t* idx = side ? b : a;
-    const int64_t cnt = side ? nb : na;
-    for (int64_t i = 0; idx && i < cnt; i++)
-      if (idx[i] < 0 || idx[i] >= S)
-        return fail(c, GCRE_ERR_RANGE, std::string("set_overlap: ") + (side ? "b[" : "a[") + std::to_string(i) + "] = " +
-                                           std::to_string(idx[i]) + " out of range (" + std::to_string(S) + " sets)");
-  }
-  if (S > 0x7fffffff) return fail(c, GCRE_ERR_ARG, "set_overlap: too many sets");
-  const bool pairs = both && na > 0 && nb > 0;
-  if (!size && !pairs) return GCRE_OK;
-
-  // the host stage: per valid set the OR of all its members within the n patients, as [valid set][Wdp] dwords (zero
-  // padded to whole chunks of the kernel), and its case / control counts
-  const int W = g.W;
-  const int Wdp = (2 * W + kOverlapChunk - 1) / kOverlapChunk * kOverlapChunk;
-  const size_t RW = (size_t)Wdp / 2;   // words per device row
-  std::vector<uint64_t> cases((size_t)W, 0), ctrls((size_t)W, 0);
-  for (int q = 0; q < g.n; q++) (q < g.n_cases ? cases : ctrls)[(size_t)q / 64] |= uint64_t(1) << (q % 64);
-  std::vector<int32_t> vrow((size_t)S, -1);   // set -> row of urows, -1 = an NA member
-  std::vector<uint64_t> urows;
-  int64_t V = 0;
-  for (int64_t s = 0; s < S; s++) {
-    const int64_t lo = in->set_off[s], hi = in->set_off[s + 1];
-    bool valid = true;
-    for (int64_t i = lo; i < hi; i++) valid = valid && in->members[i] >= 0;
-    if (!valid) {
-      if (size) size[2 * s] = size[2 * s + 1] = -1;
-      continue;
-    }
-    vrow[(size_t)s] = (int32_t)V;
-    urows.resize((size_t)(V + 1) * RW, 0);
-    uint64_t* U = urows.data() + (size_t)V * RW;
-    V++;
-    for (int64_t i = lo; i < hi; i++) {
-      const uint64_t* r = in->rows + (size_t)in->members[i] * W;
-      for (int w = 0; w < W; w++) U[w] |= r[w] & (cases[w] | ctrls[w]);
-    }
-    if (size) {
-      int nc = 0, nt = 0;
-      for (int w = 0; w < W; w++) {
-        nc += __builtin_popcountll(U[w] & cases[w]);
-        nt += __builtin_popcountll(U[w] & ctrls[w]);
-      }
-      size[2 * s] = nc;
-      size[2 * s + 1] = nt;
-    }
-  }
-  if (!pairs) return GCRE_OK;
-  if (V == 0) {   // every set has an NA member: all overlaps are 0
-    std::memset(both, 0, (size_t)na * (size_t)nb * 8);
-    return GCRE_OK;
-  }
-  urows.resize((size_t)(V + 1) * RW, 0);   // row V, all zeros: what a set with an NA member and a tile's remainder read
-  auto row_of = [&](int64_t s) { return vrow[(size_t)s] < 0 ? (int32_t)V : vrow[(size_t)s]; };
-  std::vector<int32_t> ia((size_t)na), ib((size_t)nb);
-  for (int64_t i = 0; i < na; i++) ia[(size_t)i] = row_of(a ? a[i] : i);
-  for (int64_t j = 0; j < nb; j++) ib[(size_t)j] = row_of(b ? b[j] : j);
-
-  // `a` rows per launch: whole tiles, the output of a launch under the bound (one tile row at the least), the grid in range
-  double slab_mb = 256;
-  if (const char* e = std::getenv("GCRE_OVERLAP_SLAB_MB")) slab_mb = std::min(std::max(std::atof(e), 0.0), 65536.0);   // tests: fractions
-  const int64_t ntb = (nb + kOverlapTile - 1) / kOverlapTile;
-  int64_t slab = (int64_t)(slab_mb * 1048576.0) / (nb * 8) / kOverlapTile * kOverlapTile;
-  slab = std::max<int64_t>(slab, kOverlapTile);
-  slab = std::min<int64_t>(slab, (0x7fffffff / ntb) * kOverlapTile);
-  slab = std::min<int64_t>(slab, (na + kOverlapTile - 1) / kOverlapTile * kOverlapTile);
-  if (slab < kOverlapTile) return fail(c, GCRE_ERR_ARG, "set_overlap: too many b entries for one launch");
-
-  (void)hipSetDevice(c->device);
-  uint64_t* d_rows = nullptr;
-  int32_t *d_ia = nullptr, *d_ib = nullptr, *d_both = nullptr;
-  hipError_t e = hipMalloc((void**)&d_rows, urows.size() * 8);
-  if (e == hipSuccess) e = hipMalloc((void**)&d_ia, (size_t)na * 4);
-  if (e == hipSuccess) e = hipMalloc((void**)&d_ib, (size_t)nb * 4);
-  if (e == hipSuccess) e = hipMalloc((void**)&d_both, (size_t)std::min(slab, na) * (size_t)nb * 8);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_rows, urows.data(), urows.size() * 8, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_ia, ia.data(), (size_t)na * 4, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_ib, ib.data(), (size_t)nb * 4, hipMemcpyHostToDevice, c->stream);
-  for (int64_t r0 = 0; e == hipSuccess && r0 < na; r0 += slab) {
-    OverlapArgs o{};
-    o.rows = (const uint32_t*)d_rows;
-    o.ia = d_ia + r0;
-    o.ib = d_ib;
-    o.both = d_both;
-    o.na = std::min(slab, na - r0);
-    o.nb = nb;
-    o.ntb = ntb;
-    o.Wdp = Wdp;
-    o.n_cases = g.n_cases;
-    o.zero_row = (int)V;
-    e = launch_set_overlap(o, c->stream);
-    if (e == hipSuccess) c->overlap_launches++;
-    if (e == hipSuccess)
-      e = hipMemcpyAsync(both + (size_t)r0 * (size_t)nb * 2, d_both, (size_t)o.na * (size_t)nb * 8, hipMemcpyDeviceToHost,
-                         c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);   // the next slab writes d_both again
-  }
-  for (void* p : {(void*)d_rows, (void*)d_ia, (void*)d_ib, (void*)d_both})
-    if (p) (void)hipFree(p);
-  if (e != hipSuccess) return fail(c, GCRE_ERR_DEVICE, std::string("set_overlap: ") + hipGetErrorString(e));
-  return GCRE_OK;
-}
-
-int64_t gcre_overlap_launches(const gcre_ctx* c) { return c ? c->overlap_launches : -1; }
-
 int gcre_set_perm_window(gcre_ctx* c, int k0, int k1) {
   if (!c) return GCRE_ERR_ARG;
   const int K = c->g.K;
@@ -4118,431 +3149,6 @@ int gcre_join_ahead(gcre_ctx* c, const gcre_uids* uids, const gcre_pathset* path
   a.take(opts);
   c->ahead->push_back(a);
   return GCRE_OK;
-}
-
-// ---- per-gene best-path tally ----
-gcre_gene_tally* gcre_gene_tally_create(gcre_ctx* c, int32_t n_slots, const int32_t* genes0, int64_t n_rows0, int32_t w0,
-                                        const int32_t* genes1, int64_t n_rows1, int32_t w1) {
-  if (!c) return nullptr;
-  auto bad = [&](const std::string& m) -> gcre_gene_tally* {
-    fail(c, GCRE_ERR_ARG, "gene tally: " + m);
-    return nullptr;
-  };
-  if (n_slots < 1) return bad("n_slots must be >= 1");
-  if (!genes0) { n_rows0 = 0; w0 = 0; }
-  if (!genes1) { n_rows1 = 0; w1 = 0; }
-  if (n_rows0 < 0 || n_rows1 < 0) return bad("negative row count");
-  if ((genes0 && (w0 < 1 || w0 > kGeneWidthMax)) || (genes1 && (w1 < 1 || w1 > kGeneWidthMax)))
-    return bad("a table's width must be 1.." + std::to_string(kGeneWidthMax));
-  for (int64_t i = 0; i < n_rows0 * w0; i++)
-    if (genes0[i] < -1 || genes0[i] >= n_slots) return bad("genes0 holds slot " + std::to_string(genes0[i]) + " outside -1.." + std::to_string(n_slots - 1));
-  for (int64_t i = 0; i < n_rows1 * w1; i++)
-    if (genes1[i] < -1 || genes1[i] >= n_slots) return bad("genes1 holds slot " + std::to_string(genes1[i]) + " outside -1.." + std::to_string(n_slots - 1));
-  (void)hipSetDevice(c->device);
-  gcre_gene_tally* t = new gcre_gene_tally();
-  t->ctx = c;
-  t->n_slots = n_slots;
-  t->n_rows0 = n_rows0;
-  t->n_rows1 = n_rows1;
-  t->w0 = w0;
-  t->w1 = w1;
-  c->live_tallies.push_back(t);
-  const size_t n = (size_t)n_slots, g0 = (size_t)(n_rows0 * w0), g1 = (size_t)(n_rows1 * w1);
-  hipError_t e = hipSuccess;
-  auto get = [&](void** p, size_t bytes) {
-    if (e == hipSuccess) e = hipMalloc(p, std::max<size_t>(bytes, 8));
-  };
-  get((void**)&t->d_genes0, g0 * 4);
-  get((void**)&t->d_genes1, g1 * 4);
-  get((void**)&t->d_ck, n * 8);
-  get((void**)&t->d_cidx, n * 4);
-  get((void**)&t->d_bkey, n * 8);
-  get((void**)&t->d_bord, n * 8);
-  get((void**)&t->d_bsrc, n * 4);
-  get((void**)&t->d_btrg, n * 4);
-  get((void**)&t->d_bcases, n * 4);
-  get((void**)&t->d_bctrls, n * 4);
-  if (e == hipSuccess && g0) e = hipMemcpyAsync(t->d_genes0, genes0, g0 * 4, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess && g1) e = hipMemcpyAsync(t->d_genes1, genes1, g1 * 4, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) e = hipMemsetAsync(t->d_ck, 0, n * 8, c->stream);
-  if (e == hipSuccess) e = hipMemsetAsync(t->d_cidx, 0xff, n * 4, c->stream);
-  if (e == hipSuccess) e = hipMemsetAsync(t->d_bkey, 0, n * 8, c->stream);
-  if (e == hipSuccess) e = hipMemsetAsync(t->d_bord, 0xff, n * 8, c->stream);   // ordinal -1
-  if (e == hipSuccess) e = hipMemsetAsync(t->d_bsrc, 0xff, n * 4, c->stream);
-  if (e == hipSuccess) e = hipMemsetAsync(t->d_btrg, 0xff, n * 4, c->stream);
-  if (e == hipSuccess) e = hipMemsetAsync(t->d_bcases, 0, n * 4, c->stream);
-  if (e == hipSuccess) e = hipMemsetAsync(t->d_bctrls, 0, n * 4, c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);   // (the host tables may go once the call returns)
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    gcre_gene_tally_free(t);
-    fail(c, GCRE_ERR_DEVICE, std::string("gene tally: ") + hipGetErrorString(e));
-    return nullptr;
-  }
-  t->last = c->stream;
-  return t;
-}
-
-int gcre_join_set_tally(gcre_ctx* c, gcre_gene_tally* t) {
-  if (!c) return GCRE_ERR_ARG;
-  if (t && t->ctx != c) return fail(c, GCRE_ERR_ARG, "gene tally does not belong to this context");
-  c->armed_tally = t;
-  return GCRE_OK;
-}
-
-int gcre_process_paths_set_tally(gcre_ctx* c, int level, gcre_gene_tally* t) {
-  if (!c) return GCRE_ERR_ARG;
-  if (level < 0 || level > 5) return fail(c, GCRE_ERR_ARG, "gene tally: level index must be 0..5");
-  if (t && t->ctx != c) return fail(c, GCRE_ERR_ARG, "gene tally does not belong to this context");
-  c->pp_tally[level] = t;
-  return GCRE_OK;
-}
-
-int gcre_gene_tally_read(gcre_gene_tally* t, double* score, int64_t* ordinal, int32_t* src, int32_t* trg, int32_t* cases,
-                         int32_t* ctrls) {
-  if (!t || !t->ctx) return GCRE_ERR_ARG;
-  gcre_ctx* c = t->ctx;
-  (void)hipSetDevice(c->device);
-  if (t->last) HIP_TRY(c, hipStreamSynchronize(t->last));
-  const size_t n = (size_t)t->n_slots;
-  std::vector<uint64_t> key(n);
-  HIP_TRY(c, hipMemcpy(key.data(), t->d_bkey, n * 8, hipMemcpyDeviceToHost));
-  if (score)
-    for (size_t g = 0; g < n; g++) score[g] = key[g] ? key_to_score(key[g]) : -std::numeric_limits<double>::infinity();
-  if (ordinal) HIP_TRY(c, hipMemcpy(ordinal, t->d_bord, n * 8, hipMemcpyDeviceToHost));
-  if (src) HIP_TRY(c, hipMemcpy(src, t->d_bsrc, n * 4, hipMemcpyDeviceToHost));
-  if (trg) HIP_TRY(c, hipMemcpy(trg, t->d_btrg, n * 4, hipMemcpyDeviceToHost));
-  if (cases) HIP_TRY(c, hipMemcpy(cases, t->d_bcases, n * 4, hipMemcpyDeviceToHost));
-  if (ctrls) HIP_TRY(c, hipMemcpy(ctrls, t->d_bctrls, n * 4, hipMemcpyDeviceToHost));
-  return GCRE_OK;
-}
-
-void gcre_gene_tally_free(gcre_gene_tally* t) {
-  if (!t) return;
-  if (gcre_ctx* c = t->ctx) {
-    (void)hipSetDevice(c->device);
-    if (t->last) (void)hipStreamSynchronize(t->last);
-    if (c->armed_tally == t) c->armed_tally = nullptr;
-    for (auto& p : c->pp_tally)
-      if (p == t) p = nullptr;
-    auto& v = c->live_tallies;
-    v.erase(std::remove(v.begin(), v.end(), t), v.end());
-  }
-  for (void* p : {(void*)t->d_genes0, (void*)t->d_genes1, (void*)t->d_ck, (void*)t->d_cidx, (void*)t->d_bkey, (void*)t->d_bord,
-                  (void*)t->d_bsrc, (void*)t->d_btrg, (void*)t->d_bcases, (void*)t->d_bctrls})
-    if (p) (void)hipFree(p);
-  delete t;
-}
-
-// ---- null exceedance counts ----
-gcre_exceed* gcre_exceed_create(gcre_ctx* c, const double* thresholds, int32_t m) {
-  if (!c) return nullptr;
-  auto bad = [&](const std::string& msg) -> gcre_exceed* {
-    fail(c, GCRE_ERR_ARG, "exceedance counts: " + msg);
-    return nullptr;
-  };
-  if (!thresholds) return bad("NULL thresholds");
-  if (m < 1 || m > kExceedMax) return bad("the number of thresholds must be 1.." + std::to_string(kExceedMax) + ", not " + std::to_string(m));
-  for (int32_t i = 0; i < m; i++)
-    if (thresholds[i] != thresholds[i]) return bad("threshold " + std::to_string(i) + " is NaN");
-  (void)hipSetDevice(c->device);
-  gcre_exceed* x = new gcre_exceed();
-  x->ctx = c;
-  x->m = m;
-  x->thr.assign(thresholds, thresholds + m);
-  x->order.resize((size_t)m);
-  for (int32_t i = 0; i < m; i++) x->order[(size_t)i] = i;
-  std::stable_sort(x->order.begin(), x->order.end(), [&](int32_t a, int32_t b) { return thresholds[a] < thresholds[b]; });
-  // both images are monotone in the threshold: one order serves both.  Observed scores are compared as score keys
-  // (gcre_kernels.hip: score_key); a zero threshold takes the key of -0.0, so that a score of either zero reaches it, and
-  // -inf the smallest key a score can have
-  std::vector<uint32_t> pat((size_t)m);
-  std::vector<uint64_t> tkey((size_t)m);
-  for (int32_t j = 0; j < m; j++) {
-    double t = thresholds[x->order[(size_t)j]];
-    pat[(size_t)j] = f32_threshold(t);
-    if (t == 0) t = -0.0;
-    uint64_t b;
-    std::memcpy(&b, &t, 8);
-    const uint64_t k = (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-    tkey[(size_t)j] = t > -std::numeric_limits<double>::infinity() ? k : 1;
-  }
-  c->live_exceeds.push_back(x);
-  hipError_t e = hipMalloc((void**)&x->d_pat, (size_t)m * 4);
-  if (e == hipSuccess) e = hipMalloc((void**)&x->d_tkey, (size_t)m * 8);
-  if (e == hipSuccess) e = hipMalloc((void**)&x->d_hist, (size_t)m * 8);
-  if (e == hipSuccess) e = hipMalloc((void**)&x->d_ohist, (size_t)m * 8);
-  if (e == hipSuccess) e = hipMemcpyAsync(x->d_pat, pat.data(), (size_t)m * 4, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(x->d_tkey, tkey.data(), (size_t)m * 8, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) e = hipMemsetAsync(x->d_hist, 0, (size_t)m * 8, c->stream);
-  if (e == hipSuccess) e = hipMemsetAsync(x->d_ohist, 0, (size_t)m * 8, c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);   // (the vectors are locals)
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    gcre_exceed_free(x);
-    fail(c, GCRE_ERR_DEVICE, std::string("exceedance counts: ") + hipGetErrorString(e));
-    return nullptr;
-  }
-  return x;
-}
-
-int gcre_join_set_exceed(gcre_ctx* c, gcre_exceed* x) {
-  if (!c) return GCRE_ERR_ARG;
-  if (x && x->ctx != c) return fail(c, GCRE_ERR_ARG, "exceedance counts do not belong to this context");
-  c->armed_exceed = x;
-  return GCRE_OK;
-}
-
-int gcre_process_paths_set_exceed(gcre_ctx* c, int level, gcre_exceed* x) {
-  if (!c) return GCRE_ERR_ARG;
-  if (level < 0 || level > 5) return fail(c, GCRE_ERR_ARG, "exceedance counts: level index must be 0..5");
-  if (x && x->ctx != c) return fail(c, GCRE_ERR_ARG, "exceedance counts do not belong to this context");
-  c->pp_exceed[level] = x;
-  return GCRE_OK;
-}
-
-// the counts may have been queued on either stream of the context
-static int exceed_wait(gcre_ctx* c) {
-  (void)hipSetDevice(c->device);
-  if (c->stream) HIP_TRY(c, hipStreamSynchronize(c->stream));
-  if (c->insp_stream) HIP_TRY(c, hipStreamSynchronize(c->insp_stream));
-  return GCRE_OK;
-}
-
-int gcre_exceed_read(gcre_exceed* x, uint64_t* exceed, uint64_t* observed, int64_t* perms_counted, int64_t* paths_counted) {
-  if (!x || !x->ctx) return GCRE_ERR_ARG;
-  gcre_ctx* c = x->ctx;
-  if (int rc = exceed_wait(c)) return rc;
-  const size_t m = (size_t)x->m;
-  std::vector<unsigned long long> h(m);
-  for (int which = 0; which < 2; which++) {
-    uint64_t* out = which ? observed : exceed;
-    if (!out) continue;
-    HIP_TRY(c, hipMemcpy(h.data(), which ? x->d_ohist : x->d_hist, m * 8, hipMemcpyDeviceToHost));
-    uint64_t run = 0;
-    for (size_t j = m; j-- > 0;) {   // a value in bin j reaches thresholds 0..j of the ascending order
-      run += h[j];
-      out[(size_t)x->order[j]] = run;
-    }
-  }
-  if (perms_counted) *perms_counted = x->perms;
-  if (paths_counted) *paths_counted = x->paths;
-  return GCRE_OK;
-}
-
-int gcre_exceed_reset(gcre_exceed* x) {
-  if (!x || !x->ctx) return GCRE_ERR_ARG;
-  gcre_ctx* c = x->ctx;
-  if (int rc = exceed_wait(c)) return rc;
-  HIP_TRY(c, hipMemset(x->d_hist, 0, (size_t)x->m * 8));
-  HIP_TRY(c, hipMemset(x->d_ohist, 0, (size_t)x->m * 8));
-  if (x->d_pc) HIP_TRY(c, hipMemset(x->d_pc, 0, (size_t)x->m * (size_t)x->pc_stride * 4));
-  std::fill(x->pc_load.begin(), x->pc_load.end(), 0);
-  x->perms = x->paths = 0;
-  return GCRE_OK;
-}
-
-// 2^26 cells of 4 bytes: 256 MB
-static constexpr int64_t kExceedPermCells = (int64_t)1 << 26;
-
-int gcre_exceed_keep_perm_counts(gcre_exceed* x, int on) {
-  if (!x || !x->ctx) return GCRE_ERR_ARG;
-  gcre_ctx* c = x->ctx;
-  bool alive = false;
-  for (gcre_exceed* y : c->live_exceeds) alive = alive || y == x;
-  if (!alive) return fail(c, GCRE_ERR_ARG, "exceedance counts do not belong to this context");
-  if (int rc = exceed_wait(c)) return rc;
-  if (!on) {
-    if (x->d_pc) (void)hipFree(x->d_pc);
-    x->d_pc = nullptr;
-    x->pc_stride = 0;
-    x->pc_load.clear();
-    return GCRE_OK;
-  }
-  if (x->d_pc) return GCRE_OK;
-  if (x->perms != 0 || x->paths != 0)
-    return fail(c, GCRE_ERR_ARG, "exceedance counts: per-permutation counts cannot be switched on after something was counted (" +
-                                 std::to_string(x->perms) + " permutations, " + std::to_string(x->paths) + " joined paths): reset first");
-  const int64_t K = c->g.K;
-  if (K <= 0) return fail(c, GCRE_ERR_ARG, "exceedance counts: per-permutation counts need a context with permutations (it has 0 iterations)");
-  if ((int64_t)x->m * K > kExceedPermCells)
-    return fail(c, GCRE_ERR_ARG, "exceedance counts: per-permutation counts of " + std::to_string(x->m) + " thresholds x " + std::to_string(K) +
-                                 " iterations exceed the limit of 2^26 = 67108864 cells (256 MB)");
-  const size_t bytes = (size_t)x->m * (size_t)c->g.Kpad * 4;
-  hipError_t e = hipMalloc((void**)&x->d_pc, bytes);
-  if (e == hipSuccess) e = hipMemset(x->d_pc, 0, bytes);
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    if (x->d_pc) (void)hipFree(x->d_pc);
-    x->d_pc = nullptr;
-    return fail(c, GCRE_ERR_DEVICE, std::string("exceedance counts: per-permutation counts: ") + hipGetErrorString(e));
-  }
-  x->pc_stride = c->g.Kpad;
-  x->pc_load.assign((size_t)(c->g.Kpad / kPermTileMax), 0);
-  return GCRE_OK;
-}
-
-int gcre_exceed_read_perm_counts(gcre_exceed* x, uint64_t* out) {
-  if (!x || !x->ctx) return GCRE_ERR_ARG;
-  gcre_ctx* c = x->ctx;
-  if (!x->d_pc) return fail(c, GCRE_ERR_ARG, "exceedance counts: the object keeps no per-permutation counts (gcre_exceed_keep_perm_counts)");
-  if (!out) return fail(c, GCRE_ERR_ARG, "exceedance counts: NULL output");
-  if (int rc = exceed_wait(c)) return rc;
-  const size_t m = (size_t)x->m, K = (size_t)c->g.K, stride = (size_t)x->pc_stride;
-  std::vector<uint32_t> h(m * stride);
-  HIP_TRY(c, hipMemcpy(h.data(), x->d_pc, m * stride * 4, hipMemcpyDeviceToHost));
-  std::vector<uint64_t> run(K, 0);
-  for (size_t j = m; j-- > 0;) {   // as gcre_exceed_read: a value in bin j reaches thresholds 0..j of the ascending order
-    const uint32_t* row = h.data() + j * stride;
-    uint64_t* dst = out + (size_t)x->order[j] * K;
-    for (size_t r = 0; r < K; r++) {
-      run[r] += row[r];
-      dst[r] = run[r];
-    }
-  }
-  return GCRE_OK;
-}
-
-// Step-down max-T.  Set j is the joined path whose observed score is threshold j: its null values, found
-// in the bins of the thresholds strictly below it, are what the join's per-permutation counts hold too many of once the
-// better rows are taken out of the family.
-int gcre_exceed_stepdown(gcre_exceed* x, const gcre_set_input* in, int64_t* n_ge) {
-  if (!x || !x->ctx) return GCRE_ERR_ARG;
-  gcre_ctx* c = x->ctx;
-  bool alive = false;
-  for (gcre_exceed* y : c->live_exceeds) alive = alive || y == x;
-  if (!alive) return fail(c, GCRE_ERR_ARG, "exceedance counts do not belong to this context");
-  if (!in || !n_ge) return fail(c, GCRE_ERR_ARG, "stepdown: NULL argument");
-  if (!x->d_pc)
-    return fail(c, GCRE_ERR_ARG, "stepdown: the object keeps no per-permutation counts (gcre_exceed_keep_perm_counts)");
-  const Geometry& g = c->g;
-  const int K = g.K, M = g.method, m = x->m;
-  if (x->perms != K || x->paths <= 0)
-    return fail(c, GCRE_ERR_ARG, "stepdown: the object must hold exactly one full pass of one join (" + std::to_string(x->perms) +
-                                     " permutations of " + std::to_string(x->paths) + " joined paths counted, the context has " +
-                                     std::to_string(K) + " iterations)");
-  if (in->n_sets != m)
-    return fail(c, GCRE_ERR_ARG, "stepdown: " + std::to_string(in->n_sets) + " sets for " + std::to_string(m) + " thresholds");
-  for (int j = 0; j < m; j++)
-    if (!std::isfinite(x->thr[(size_t)j])) return fail(c, GCRE_ERR_ARG, "stepdown: threshold " + std::to_string(j) + " is not finite");
-  if (int rc = check_sets(c, in, "stepdown")) return rc;
-  for (int64_t s = 0; s < m; s++)
-    for (int64_t i = in->set_off[s]; i < in->set_off[s + 1]; i++)
-      if (in->members[i] < 0) return fail(c, GCRE_ERR_ARG, "stepdown: set " + std::to_string(s) + " has an NA member");
-  if (int rc = exceed_wait(c)) return rc;
-
-  // the host stage of gcre_score_sets: per set its union rows and counts
-  const int Wp = g.Wp;
-  const size_t RW = (size_t)M * Wp;
-  const SetUnion un(g);
-  std::vector<uint64_t> urows((size_t)m * RW, 0);
-  std::vector<int32_t> cnt((size_t)m * 4, 0);   // cases_pos, ctrls_pos, cases_neg, ctrls_neg
-  std::vector<uint32_t> tot((size_t)m * M);
-  for (int64_t s = 0; s < m; s++) {
-    int32_t* k = cnt.data() + 4 * s;
-    un.build(in, s, urows.data() + (size_t)s * RW, k);
-    tot[(size_t)s * M] = (uint32_t)(k[0] + k[1]);
-    if (M == 2) tot[(size_t)s * M + 1] = (uint32_t)(k[2] + k[3]);
-  }
-  // cap[j] = the last sorted index strictly below threshold j (compared as f64: tied rows do not exclude one another)
-  std::vector<int32_t> cap((size_t)m);
-  for (int b = 0, first = 0; b < m; b++) {
-    if (x->thr[(size_t)x->order[(size_t)b]] > x->thr[(size_t)x->order[(size_t)first]]) first = b;
-    cap[(size_t)x->order[(size_t)b]] = first - 1;
-  }
-
-  (void)hipSetDevice(c->device);
-  const size_t stride = (size_t)x->pc_stride, cells = (size_t)m * stride;
-  uint64_t* d_rows = nullptr;
-  int32_t *d_cnt = nullptr, *d_cap = nullptr;
-  uint32_t *d_tot = nullptr, *d_E = nullptr, *d_out = nullptr;   // d_out: n_ge per sorted threshold, then the bad counter
-  double* d_obs = nullptr;
-  std::vector<double> obs((size_t)m);
-  std::vector<uint32_t> got((size_t)m + 1, 0);
-  hipError_t e = hipMalloc((void**)&d_rows, urows.size() * 8);
-  if (e == hipSuccess) e = hipMalloc((void**)&d_cnt, cnt.size() * 4);
-  if (e == hipSuccess) e = hipMalloc((void**)&d_tot, tot.size() * 4);
-  if (e == hipSuccess) e = hipMalloc((void**)&d_cap, (size_t)m * 4);
-  if (e == hipSuccess) e = hipMalloc((void**)&d_obs, (size_t)m * 8);
-  if (e == hipSuccess) e = hipMalloc((void**)&d_out, ((size_t)m + 1) * 4);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_rows, urows.data(), urows.size() * 8, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_cnt, cnt.data(), cnt.size() * 4, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_tot, tot.data(), tot.size() * 4, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_cap, cap.data(), (size_t)m * 4, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) e = launch_set_observed(d_cnt, m, M, c->d_dvt, d_obs, c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(obs.data(), d_obs, (size_t)m * 8, hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  int64_t off_set = -1;   // the first set whose observed score is not its threshold, bit for bit
-  for (int64_t s = 0; e == hipSuccess && s < m && off_set < 0; s++)
-    if (std::memcmp(&obs[(size_t)s], &x->thr[(size_t)s], 8) != 0) off_set = s;
-  if (e == hipSuccess && off_set < 0) {
-    e = hipMalloc((void**)&d_E, cells * 4);
-    if (e == hipSuccess) e = hipMemsetAsync(d_E, 0, cells * 4, c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(d_out, 0, ((size_t)m + 1) * 4, c->stream);
-    StepdownArgs a{};
-    a.rows = (const uint32_t*)d_rows;
-    a.masks = c->d_masks;
-    a.tot = d_tot;
-    a.t32 = c->d_t32;
-    a.d64 = c->d_dmax;
-    a.d64n = c->d_dmaxn ? c->d_dmaxn : c->d_dmax;
-    a.pat = x->d_pat;
-    a.cap = d_cap;
-    a.E = d_E;
-    a.nsets = m;
-    a.W32p = 2 * Wp;
-    a.Kpad = g.Kpad;
-    a.K = K;
-    a.nkt = (K + kSetPermTile - 1) / kSetPermTile;
-    const int64_t tpb = set_null_tile_sets(M);
-    a.npt = (m + tpb - 1) / tpb;
-    const int64_t slots = (int64_t)c->cus * 4 * 8;   // gcre_score_sets' rule
-    const int64_t per = std::max<int64_t>(1, (a.npt * a.nkt) / slots);
-    a.pgroups = (int)std::min<int64_t>((a.npt + per - 1) / per, 0x7fffffff / std::max(a.nkt, 1));
-    a.m = m;
-    a.stride = (int)stride;
-    const StepdownFinishArgs f{x->d_pc, d_E, d_out, d_out + m, m, (int)stride, K};
-    if (e == hipSuccess) e = launch_stepdown_null(a, M, c->stream);
-    if (e == hipSuccess) c->stepdown_launches++;
-    if (e == hipSuccess) e = launch_stepdown_finish(f, c->stream);
-    if (e == hipSuccess) c->stepdown_launches++;
-    if (e == hipSuccess) e = hipMemcpyAsync(got.data(), d_out, ((size_t)m + 1) * 4, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  }
-  for (void* p : {(void*)d_rows, (void*)d_cnt, (void*)d_tot, (void*)d_cap, (void*)d_obs, (void*)d_out, (void*)d_E})
-    if (p) (void)hipFree(p);
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    return fail(c, GCRE_ERR_DEVICE, std::string("stepdown: ") + hipGetErrorString(e));
-  }
-  if (off_set >= 0) {
-    char buf[256];
-    std::snprintf(buf, sizeof buf, ": its observed score is %.17g, threshold %lld is %.17g (the rows must be the rows the thresholds came from)",
-                  obs[(size_t)off_set], (long long)off_set, x->thr[(size_t)off_set]);
-    return fail(c, GCRE_ERR_ARG, "stepdown: set " + std::to_string(off_set) + buf);
-  }
-  if (got[(size_t)m] != 0)
-    return fail(c, GCRE_ERR_ASSERT, "assertion: stepdown: the sets are not distinct joined paths of the counted join (" +
-                                        std::to_string(got[(size_t)m]) + " permutations count more top rows than joined paths at a threshold)");
-  for (int b = 0; b < m; b++) n_ge[(size_t)x->order[(size_t)b]] = (int64_t)got[(size_t)b];
-  return GCRE_OK;
-}
-
-int64_t gcre_stepdown_launches(const gcre_ctx* c) { return c ? c->stepdown_launches : -1; }
-
-void gcre_exceed_free(gcre_exceed* x) {
-  if (!x) return;
-  if (gcre_ctx* c = x->ctx) {
-    (void)exceed_wait(c);
-    if (c->armed_exceed == x) c->armed_exceed = nullptr;
-    for (auto& p : c->pp_exceed)
-      if (p == x) p = nullptr;
-    auto& v = c->live_exceeds;
-    v.erase(std::remove(v.begin(), v.end(), x), v.end());
-  }
-  for (void* p : {(void*)x->d_pat, (void*)x->d_tkey, (void*)x->d_hist, (void*)x->d_ohist, (void*)x->d_pc})
-    if (p) (void)hipFree(p);
-  delete x;
 }
 
 void gcre_result_free(gcre_result* r) {

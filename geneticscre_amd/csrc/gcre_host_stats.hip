@@ -1,0 +1,759 @@
+// gcre_host_stats.hip -- the entry points of include/gcre_hip.h that use a context but not the join driver: generated
+// permutation masks, decorated p-values (gcre_decorated.hip), set scores (gcre_sets.hip) and carrier overlaps
+// (gcre_overlap.hip), and the per-gene tally (gcre_genes.hip) and the null exceedance counts (gcre_exceed.hip,
+// gcre_stepdown.hip) as objects.  What a join does with an armed tally or armed counts -- check_tally, fold_genes,
+// count_exceed -- is in gcre_host.hip.  Host code only.
+#include "gcre_host.h"
+#include "gcre_setlists.h"
+
+namespace {
+
+// The bit pattern of the smallest float x with (double)x >= score, among the non-negative floats null scores are: null
+// score r counts (R/ProcessPaths.R:316) iff its bits are >= this -- 0 when every one counts, past +inf when none does (NaN).
+uint32_t f32_threshold(double score) {
+  if (score != score) return 0x7f800001u;
+  if (score <= 0) return 0u;
+  float f = (float)score;
+  if ((double)f < score) f = std::nextafter(f, std::numeric_limits<float>::infinity());
+  uint32_t b;
+  std::memcpy(&b, &f, 4);
+  return b;
+}
+
+// What gcre_score_sets and gcre_exceed_stepdown refuse before anything is launched (`who` opens the message): a context
+// without a table or without masks, then the shape of the set list, then every set's members and signs
+int check_sets(gcre_ctx* c, const gcre_set_input* in, const std::string& who) {
+  if (!c->have_table || !c->d_dvt) return fail(c, GCRE_ERR_ASSERT, "assertion: " + who + " needs a value table");
+  if (c->g.K > 0 && !c->have_perms)
+    return fail(c, GCRE_ERR_ASSERT, "assertion: " + who + " needs the permutation masks (iterations > 0, none set)");
+  std::string msg;
+  int rc = check_set_shape(in, c->g.n, who, msg);
+  if (rc == GCRE_OK) rc = check_set_members(in, who, msg);
+  return rc == GCRE_OK ? GCRE_OK : fail(c, rc, msg);
+}
+
+// The launch geometry of k_set_null and k_stepdown_null (SetNullArgs, StepdownArgs): V sets' union rows [V][M][Wp] words and
+// carrier totals against all K permutations -- the window of gcre_set_perm_window is the joins' business
+template <typename Args>
+void fill_set_launch(Args& a, const gcre_ctx* c, const uint64_t* d_rows, const uint32_t* d_tot, int64_t V) {
+  const Geometry& g = c->g;
+  a.rows = (const uint32_t*)d_rows;
+  a.masks = c->d_masks;
+  a.tot = d_tot;
+  a.t32 = c->d_t32;
+  a.d64 = c->d_dmax;
+  a.d64n = c->d_dmaxn ? c->d_dmaxn : c->d_dmax;
+  a.nsets = V;
+  a.W32p = 2 * g.Wp;
+  a.Kpad = g.Kpad;
+  a.K = g.K;
+  a.nkt = (g.K + kSetPermTile - 1) / kSetPermTile;
+  const int64_t tpb = set_null_tile_sets(g.method);
+  a.npt = (V + tpb - 1) / tpb;
+  // one set tile per block while that makes at least ~8 blocks per resident block slot, more per block beyond
+  const int64_t slots = (int64_t)c->cus * 4 * 8;
+  const int64_t per = std::max<int64_t>(1, (a.npt * a.nkt) / slots);
+  a.pgroups = (int)std::min<int64_t>((a.npt + per - 1) / per, 0x7fffffff / std::max(a.nkt, 1));
+}
+
+// the counts may have been queued on either stream of the context
+int exceed_wait(gcre_ctx* c) {
+  (void)hipSetDevice(c->device);
+  if (c->stream) HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (c->insp_stream) HIP_TRY(c, hipStreamSynchronize(c->insp_stream));
+  return GCRE_OK;
+}
+
+// x is one of the context's live objects, or the call is refused
+int exceed_alive(gcre_ctx* c, const gcre_exceed* x) {
+  const auto& v = c->live_exceeds;
+  return std::find(v.begin(), v.end(), x) != v.end() ? GCRE_OK : fail(c, GCRE_ERR_ARG, "exceedance counts do not belong to this context");
+}
+
+// 2^26 cells of 4 bytes: 256 MB
+constexpr int64_t kExceedPermCells = (int64_t)1 << 26;
+
+}  // namespace
+
+extern "C" {
+
+int gcre_generate_perm_masks(gcre_ctx* c, uint64_t seed, const int32_t* stratum, int n_strata) {
+  if (!c || (stratum && n_strata < 1)) return fail(c, GCRE_ERR_ARG, "bad strata");
+  (void)hipSetDevice(c->device);
+  const Geometry& g = c->g;
+  if (g.K == 0) { c->have_perms = true; return GCRE_OK; }
+  if (!stratum) n_strata = 1;
+  // cases are the first n_cases patient columns (join_base.cpp:50-54): cases and size per stratum
+  std::vector<uint32_t> cases_in((size_t)n_strata, 0), size_of((size_t)n_strata, 0);
+  for (int q = 0; q < g.n; q++) {
+    const int s = stratum ? stratum[q] : 0;
+    if (s < 0 || s >= n_strata) return fail(c, GCRE_ERR_RANGE, "stratum id out of range");
+    size_of[(size_t)s]++;
+    if (q < g.n_cases) cases_in[(size_t)s]++;
+  }
+  {
+    DevScratch d(c->stream);
+    const uint32_t* d_cases = d.put(cases_in.data(), (size_t)n_strata);
+    const uint32_t* d_size = d.put(size_of.data(), (size_t)n_strata);
+    const int32_t* d_str = stratum ? d.put(stratum, (size_t)g.n) : nullptr;
+    uint32_t* d_work = d.take<uint32_t>((size_t)g.K * n_strata * 2);
+    if (d.ok())
+      d.e = launch_generate_masks(seed, g.K, g.n, n_strata, d_str, d_cases, d_size, d_work, 2 * g.Wp, g.Kpad, c->d_masks, c->stream);
+    d.sync();
+    if (!d.ok()) return fail(c, GCRE_ERR_DEVICE, std::string("generate_perm_masks: ") + hipGetErrorString(d.e));
+  }
+  if (int rc = build_transposed_masks(c)) return rc;
+  c->have_perms = true;
+  return GCRE_OK;
+}
+
+int gcre_decorated_pvalues(gcre_ctx* c, const gcre_dp_input* in, gcre_dp_split* out, int64_t cap, int64_t* n_out,
+                           int32_t* perm_counts) {
+  if (!c) return GCRE_ERR_ARG;
+  if (!in || !n_out) return fail(c, GCRE_ERR_ARG, "decorated_pvalues: NULL argument");
+  const Geometry& g = c->g;
+  if (!c->have_table || !c->d_dvt) return fail(c, GCRE_ERR_ASSERT, "assertion: decorated_pvalues needs a value table");
+  if (in->method != g.method || in->n_cases != g.n_cases || in->n_cases + in->n_ctrls != g.n)
+    return fail(c, GCRE_ERR_ASSERT, "assertion: decorated_pvalues input does not match the context (method, cases, controls)");
+  // the host stage: counts and urns (the observed scores come from the device's own table below)
+  gcre_dp_input hin = *in;
+  std::vector<gcre_dp_stratum> st;
+  if (hin.stratum && !hin.strata_out && hin.n_strata > 0 && cap > 0) {
+    st.resize((size_t)cap * (size_t)hin.n_strata);
+    hin.strata_out = st.data();
+  }
+  int rc = gcre_decorated_splits(&hin, nullptr, 0, 0, 0, out, cap, n_out);
+  if (rc == GCRE_ERR_RANGE) return fail(c, rc, "decorated_pvalues: out of range (row index, stratum id or output capacity)");
+  if (rc != GCRE_OK) return fail(c, rc, "decorated_pvalues: bad input");
+  const int64_t S = *n_out;
+  const int K = in->iterations;
+  if (S == 0) return GCRE_OK;
+  if (S > 0x7fffffff) return fail(c, GCRE_ERR_ARG, "decorated_pvalues: too many splits");
+  // the kernel's view: sub-path-1 counts, observed counts, urns, strata that draw, stream key
+  std::vector<DpUrns> urns((size_t)S);
+  std::vector<DpStratum> dst;
+  for (int64_t i = 0; i < S; i++) {
+    const gcre_dp_split& o = out[i];
+    DpUrns& u = urns[(size_t)i];
+    std::memset(&u, 0, sizeof u);
+    u.key = dp_split_key(in->seed, i);
+    if (!o.valid) continue;   // counts 0, no draws: p-value NaN below
+    u.case_pos1 = o.case_pos1;
+    u.ctrl_pos1 = o.ctrl_pos1;
+    u.case_neg1 = o.case_neg1;
+    u.ctrl_neg1 = o.ctrl_neg1;
+    u.case_pos2 = o.case_pos2;
+    u.ctrl_pos2 = o.ctrl_pos2;
+    u.case_neg2 = o.case_neg2;
+    u.ctrl_neg2 = o.ctrl_neg2;
+    u.k_pos = o.k_pos;
+    u.k_neg = o.k_neg;
+    u.pop_pos = o.pop_pos;
+    u.succ_pos = o.succ_pos;
+    u.pop_neg = o.pop_neg;
+    u.succ_neg = o.succ_neg;
+    if (o.strata_off >= 0) {
+      u.st_off = (int32_t)dst.size();
+      for (int s = 0; s < in->n_strata; s++) {
+        const gcre_dp_stratum& q = hin.strata_out[o.strata_off + s];
+        if (q.k_pos + q.k_neg > 0) dst.push_back({q.pop, q.cases, q.k_pos, q.k_neg});
+      }
+      u.st_n = (int32_t)dst.size() - u.st_off;
+      // every draw of a stratified split happens inside its strata (st_n == 0 with k_pos == k_neg == 0: nothing to draw)
+    }
+  }
+  if (dst.size() > 0x7fffffffu) return fail(c, GCRE_ERR_ARG, "decorated_pvalues: too many strata");
+  (void)hipSetDevice(c->device);
+  const size_t n_pc = perm_counts ? (size_t)S * (size_t)K * 2 : 0;
+  std::vector<double> obs((size_t)S);
+  std::vector<unsigned long long> ge((size_t)S, 0);
+  DevScratch d(c->stream);
+  const DpUrns* d_urns = d.put(urns.data(), (size_t)S);
+  DpStratum* d_st = d.take<DpStratum>(std::max<size_t>(dst.size(), 1));
+  double* d_obs = d.take<double>((size_t)S);
+  unsigned long long* d_ge = d.take<unsigned long long>((size_t)S);
+  int32_t* d_pc = n_pc ? d.take<int32_t>(n_pc) : nullptr;
+  if (!dst.empty()) d.upload(d_st, dst.data(), dst.size());
+  d.zero(d_ge, (size_t)S);
+  if (d.ok()) d.e = launch_decorated_observed(d_urns, (int)S, g.method, c->d_dvt, d_obs, c->stream);
+  if (d.ok()) d.e = launch_decorated_null(d_urns, d_st, (int)S, K, g.method, c->d_dvt, d_obs, d_ge, d_pc, c->stream);
+  d.download(obs.data(), d_obs, (size_t)S);
+  d.download(ge.data(), d_ge, (size_t)S);
+  if (n_pc) d.download(perm_counts, d_pc, n_pc);
+  d.sync();
+  if (!d.ok()) return fail(c, GCRE_ERR_DEVICE, std::string("decorated_pvalues: ") + hipGetErrorString(d.e));
+  for (int64_t i = 0; i < S; i++) {
+    gcre_dp_split& o = out[i];
+    if (!o.valid) continue;
+    o.score = obs[(size_t)i];
+    o.n_ge = (int64_t)ge[(size_t)i];
+    o.pvalue = K > 0 ? (double)o.n_ge / (double)K : std::numeric_limits<double>::quiet_NaN();
+  }
+  return GCRE_OK;
+}
+
+int gcre_score_sets(gcre_ctx* c, const gcre_set_input* in, gcre_set_score* out, int64_t cap, int64_t* n_out,
+                    float* family_max) {
+  if (!c) return GCRE_ERR_ARG;
+  if (!in || !n_out || cap < 0 || (cap > 0 && !out)) return fail(c, GCRE_ERR_ARG, "score_sets: NULL argument");
+  *n_out = 0;
+  const Geometry& g = c->g;
+  const int K = g.K, M = g.method;
+  const int64_t S = in->n_sets;
+  if (int rc = check_sets(c, in, "score_sets")) return rc;
+  *n_out = S;
+  if (S > cap)
+    return fail(c, GCRE_ERR_RANGE, "score_sets: " + std::to_string(S) + " sets, room for " + std::to_string(cap) +
+                                       " records (out of range)");
+
+  // the host stage: per valid set the OR of its (+) members and of its (-) members (method 1: of all of them), within the
+  // n patients, and their counts; the device rows are [valid set][M][Wp] words, the dword view k_set_null reads
+  const int Wp = g.Wp;
+  const size_t RW = (size_t)M * Wp;
+  const SetUnion un(g.W, g.n, g.n_cases);
+  const double nan = std::numeric_limits<double>::quiet_NaN();
+  std::vector<int64_t> vset;     // the valid sets, in input order
+  std::vector<uint64_t> urows;
+  std::vector<int32_t> cnt;      // [valid][4] cases_pos, ctrls_pos, cases_neg, ctrls_neg
+  std::vector<uint32_t> tot;     // [valid][M] carriers per half
+  for (int64_t s = 0; s < S; s++) {
+    gcre_set_score& o = out[s];
+    std::memset(&o, 0, sizeof o);
+    o.set = s;
+    o.score = nan;
+    o.pvalue = nan;
+    o.valid = set_is_valid(in, s) ? 1 : 0;
+    if (!o.valid) continue;
+    const size_t v = vset.size();
+    vset.push_back(s);
+    urows.resize((v + 1) * RW, 0);
+    int32_t k[4];
+    un.build(in, s, urows.data() + v * RW, (size_t)Wp, M == 2, k);
+    o.cases_pos = k[0];
+    o.ctrls_pos = k[1];
+    o.cases_neg = k[2];
+    o.ctrls_neg = k[3];
+    o.cases = o.cases_pos + o.cases_neg;
+    o.ctrls = o.ctrls_pos + o.ctrls_neg;
+    cnt.insert(cnt.end(), k, k + 4);
+    tot.push_back((uint32_t)(k[0] + k[1]));
+    if (M == 2) tot.push_back((uint32_t)(k[2] + k[3]));
+  }
+  if (family_max) std::fill(family_max, family_max + K, 0.0f);
+  const int64_t V = (int64_t)vset.size();
+  if (V == 0) return GCRE_OK;
+
+  (void)hipSetDevice(c->device);
+  const bool fam = family_max && K > 0;
+  std::vector<double> obs((size_t)V);
+  std::vector<unsigned long long> ge((size_t)V, 0);
+  std::vector<uint32_t> fbits(fam ? (size_t)K : 0);
+  DevScratch d(c->stream);
+  const uint64_t* d_rows = d.put(urows.data(), urows.size());
+  const int32_t* d_cnt = d.put(cnt.data(), cnt.size());
+  const uint32_t* d_tot = d.put(tot.data(), tot.size());
+  uint32_t* d_thr = d.take<uint32_t>((size_t)V);
+  double* d_obs = d.take<double>((size_t)V);
+  unsigned long long* d_ge = d.take<unsigned long long>((size_t)V);
+  uint32_t* d_fam = fam ? d.take<uint32_t>((size_t)g.Kpad) : nullptr;
+  if (d.ok()) d.e = launch_set_observed(d_cnt, V, M, c->d_dvt, d_obs, c->stream);
+  d.download(obs.data(), d_obs, (size_t)V);
+  d.sync();
+  if (d.ok() && K > 0) {
+    std::vector<uint32_t> thr((size_t)V);
+    for (int64_t v = 0; v < V; v++) thr[(size_t)v] = f32_threshold(obs[(size_t)v]);
+    SetNullArgs a{};
+    fill_set_launch(a, c, d_rows, d_tot, V);
+    a.thr = d_thr;
+    a.n_ge = d_ge;
+    a.fam_bits = d_fam;
+    d.upload(d_thr, thr.data(), (size_t)V);
+    d.zero(d_ge, (size_t)V);
+    if (fam) d.zero(d_fam, (size_t)g.Kpad);
+    if (d.ok()) d.e = launch_set_null(a, M, c->stream);
+    d.download(ge.data(), d_ge, (size_t)V);
+    if (fam) d.download(fbits.data(), d_fam, (size_t)K);
+    d.sync();
+  }
+  if (!d.ok()) return fail(c, GCRE_ERR_DEVICE, std::string("score_sets: ") + hipGetErrorString(d.e));
+  for (int64_t v = 0; v < V; v++) {
+    gcre_set_score& o = out[vset[(size_t)v]];
+    o.score = obs[(size_t)v];
+    o.n_ge = (int64_t)ge[(size_t)v];
+    o.pvalue = K > 0 ? (double)o.n_ge / (double)K : nan;
+  }
+  if (fam) std::memcpy(family_max, fbits.data(), (size_t)K * 4);
+  return GCRE_OK;
+}
+
+// Carrier overlaps of caller-given sets: the validation of gcre_score_sets, the OR of every valid set's
+// members on the host, then k_set_overlap over the `a` list in slabs whose device output stays under GCRE_OVERLAP_SLAB_MB.
+int gcre_set_overlap(gcre_ctx* c, const gcre_set_input* in, const int64_t* a, int64_t na, const int64_t* b, int64_t nb,
+                     int32_t* size, int32_t* both) {
+  if (!c) return GCRE_ERR_ARG;
+  if (!in) return fail(c, GCRE_ERR_ARG, "set_overlap: NULL argument");
+  const Geometry& g = c->g;
+  std::string msg;
+  if (int rc = check_set_shape(in, g.n, "set_overlap", msg)) return fail(c, rc, msg);
+  const int64_t S = in->n_sets;
+  if (na < 0 || nb < 0 || (!a && na != S) || (!b && nb != S))
+    return fail(c, GCRE_ERR_ARG, "set_overlap: bad index list (a negative length, or NULL with a length other than n_sets)");
+  if (int rc = check_set_members(in, "set_overlap", msg)) return fail(c, rc, msg);
+  for (int side = 0; side < 2; side++) {
+    const int64_t* idx = side ? b : a;
+    const int64_t cnt = side ? nb : na;
+    for (int64_t i = 0; idx && i < cnt; i++)
+      if (idx[i] < 0 || idx[i] >= S)
+        return fail(c, GCRE_ERR_RANGE, std::string("set_overlap: ") + (side ? "b[" : "a[") + std::to_string(i) + "] = " +
+                                           std::to_string(idx[i]) + " out of range (" + std::to_string(S) + " sets)");
+  }
+  if (S > 0x7fffffff) return fail(c, GCRE_ERR_ARG, "set_overlap: too many sets");
+  const bool pairs = both && na > 0 && nb > 0;
+  if (!size && !pairs) return GCRE_OK;
+
+  // the host stage: per valid set the OR of all its members within the n patients, as [valid set][Wdp] dwords (zero
+  // padded to whole chunks of the kernel), and its case / control counts
+  const int W = g.W;
+  const int Wdp = (2 * W + kOverlapChunk - 1) / kOverlapChunk * kOverlapChunk;
+  const size_t RW = (size_t)Wdp / 2;   // words per device row
+  const SetUnion un(W, g.n, g.n_cases);
+  std::vector<int32_t> vrow((size_t)S, -1);   // set -> row of urows, -1 = an NA member
+  std::vector<uint64_t> urows;
+  int64_t V = 0;
+  for (int64_t s = 0; s < S; s++) {
+    if (!set_is_valid(in, s)) {
+      if (size) size[2 * s] = size[2 * s + 1] = -1;
+      continue;
+    }
+    vrow[(size_t)s] = (int32_t)V;
+    urows.resize((size_t)(V + 1) * RW, 0);
+    int32_t k[4];
+    un.build(in, s, urows.data() + (size_t)V * RW, 0, false, size ? k : nullptr);   // all members into one row, whatever their signs
+    V++;
+    if (size) std::memcpy(size + 2 * s, k, 8);   // cases, controls
+  }
+  if (!pairs) return GCRE_OK;
+  if (V == 0) {   // every set has an NA member: all overlaps are 0
+    std::memset(both, 0, (size_t)na * (size_t)nb * 8);
+    return GCRE_OK;
+  }
+  urows.resize((size_t)(V + 1) * RW, 0);   // row V, all zeros: what a set with an NA member and a tile's remainder read
+  auto row_of = [&](int64_t s) { return vrow[(size_t)s] < 0 ? (int32_t)V : vrow[(size_t)s]; };
+  std::vector<int32_t> ia((size_t)na), ib((size_t)nb);
+  for (int64_t i = 0; i < na; i++) ia[(size_t)i] = row_of(a ? a[i] : i);
+  for (int64_t j = 0; j < nb; j++) ib[(size_t)j] = row_of(b ? b[j] : j);
+
+  // `a` rows per launch: whole tiles, the output of a launch under the bound (one tile row at the least), the grid in range
+  double slab_mb = 256;
+  if (const char* e = std::getenv("GCRE_OVERLAP_SLAB_MB")) slab_mb = std::min(std::max(std::atof(e), 0.0), 65536.0);   // tests: fractions
+  const int64_t ntb = (nb + kOverlapTile - 1) / kOverlapTile;
+  int64_t slab = (int64_t)(slab_mb * 1048576.0) / (nb * 8) / kOverlapTile * kOverlapTile;
+  slab = std::max<int64_t>(slab, kOverlapTile);
+  slab = std::min<int64_t>(slab, (0x7fffffff / ntb) * kOverlapTile);
+  slab = std::min<int64_t>(slab, (na + kOverlapTile - 1) / kOverlapTile * kOverlapTile);
+  if (slab < kOverlapTile) return fail(c, GCRE_ERR_ARG, "set_overlap: too many b entries for one launch");
+
+  (void)hipSetDevice(c->device);
+  DevScratch d(c->stream);
+  const uint64_t* d_rows = d.put(urows.data(), urows.size());
+  const int32_t* d_ia = d.put(ia.data(), (size_t)na);
+  const int32_t* d_ib = d.put(ib.data(), (size_t)nb);
+  int32_t* d_both = d.take<int32_t>((size_t)std::min(slab, na) * (size_t)nb * 2);
+  for (int64_t r0 = 0; d.ok() && r0 < na; r0 += slab) {
+    OverlapArgs o{};
+    o.rows = (const uint32_t*)d_rows;
+    o.ia = d_ia + r0;
+    o.ib = d_ib;
+    o.both = d_both;
+    o.na = std::min(slab, na - r0);
+    o.nb = nb;
+    o.ntb = ntb;
+    o.Wdp = Wdp;
+    o.n_cases = g.n_cases;
+    o.zero_row = (int)V;
+    d.e = launch_set_overlap(o, c->stream);
+    if (d.ok()) c->overlap_launches++;
+    d.download(both + (size_t)r0 * (size_t)nb * 2, d_both, (size_t)o.na * (size_t)nb * 2);
+    d.sync();   // the next slab writes d_both again
+  }
+  if (!d.ok()) return fail(c, GCRE_ERR_DEVICE, std::string("set_overlap: ") + hipGetErrorString(d.e));
+  return GCRE_OK;
+}
+
+int64_t gcre_overlap_launches(const gcre_ctx* c) { return c ? c->overlap_launches : -1; }
+
+// ---- per-gene best-path tally ----
+gcre_gene_tally* gcre_gene_tally_create(gcre_ctx* c, int32_t n_slots, const int32_t* genes0, int64_t n_rows0, int32_t w0,
+                                        const int32_t* genes1, int64_t n_rows1, int32_t w1) {
+  if (!c) return nullptr;
+  auto bad = [&](const std::string& m) -> gcre_gene_tally* {
+    fail(c, GCRE_ERR_ARG, "gene tally: " + m);
+    return nullptr;
+  };
+  if (n_slots < 1) return bad("n_slots must be >= 1");
+  if (!genes0) { n_rows0 = 0; w0 = 0; }
+  if (!genes1) { n_rows1 = 0; w1 = 0; }
+  if (n_rows0 < 0 || n_rows1 < 0) return bad("negative row count");
+  if ((genes0 && (w0 < 1 || w0 > kGeneWidthMax)) || (genes1 && (w1 < 1 || w1 > kGeneWidthMax)))
+    return bad("a table's width must be 1.." + std::to_string(kGeneWidthMax));
+  for (int64_t i = 0; i < n_rows0 * w0; i++)
+    if (genes0[i] < -1 || genes0[i] >= n_slots) return bad("genes0 holds slot " + std::to_string(genes0[i]) + " outside -1.." + std::to_string(n_slots - 1));
+  for (int64_t i = 0; i < n_rows1 * w1; i++)
+    if (genes1[i] < -1 || genes1[i] >= n_slots) return bad("genes1 holds slot " + std::to_string(genes1[i]) + " outside -1.." + std::to_string(n_slots - 1));
+  (void)hipSetDevice(c->device);
+  gcre_gene_tally* t = new gcre_gene_tally();
+  t->ctx = c;
+  t->n_slots = n_slots;
+  t->n_rows0 = n_rows0;
+  t->n_rows1 = n_rows1;
+  t->w0 = w0;
+  t->w1 = w1;
+  c->live_tallies.push_back(t);
+  const size_t n = (size_t)n_slots, g0 = (size_t)(n_rows0 * w0), g1 = (size_t)(n_rows1 * w1);
+  struct { void** p; size_t bytes; int fill; } tabs[] = {   // fill -1: the table comes from the host
+      {(void**)&t->d_genes0, g0 * 4, -1}, {(void**)&t->d_genes1, g1 * 4, -1}, {(void**)&t->d_ck, n * 8, 0},
+      {(void**)&t->d_cidx, n * 4, 0xff},  {(void**)&t->d_bkey, n * 8, 0},     {(void**)&t->d_bord, n * 8, 0xff},   // ordinal -1
+      {(void**)&t->d_bsrc, n * 4, 0xff},  {(void**)&t->d_btrg, n * 4, 0xff},  {(void**)&t->d_bcases, n * 4, 0},
+      {(void**)&t->d_bctrls, n * 4, 0}};
+  hipError_t e = hipSuccess;
+  for (auto& b : tabs)
+    if (e == hipSuccess) e = hipMalloc(b.p, std::max<size_t>(b.bytes, 8));
+  if (e == hipSuccess && g0) e = hipMemcpyAsync(t->d_genes0, genes0, g0 * 4, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess && g1) e = hipMemcpyAsync(t->d_genes1, genes1, g1 * 4, hipMemcpyHostToDevice, c->stream);
+  for (auto& b : tabs)
+    if (e == hipSuccess && b.fill >= 0) e = hipMemsetAsync(*b.p, b.fill, b.bytes, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);   // (the host tables may go once the call returns)
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    gcre_gene_tally_free(t);
+    fail(c, GCRE_ERR_DEVICE, std::string("gene tally: ") + hipGetErrorString(e));
+    return nullptr;
+  }
+  t->last = c->stream;
+  return t;
+}
+
+int gcre_join_set_tally(gcre_ctx* c, gcre_gene_tally* t) {
+  if (!c) return GCRE_ERR_ARG;
+  if (t && t->ctx != c) return fail(c, GCRE_ERR_ARG, "gene tally does not belong to this context");
+  c->armed_tally = t;
+  return GCRE_OK;
+}
+
+int gcre_process_paths_set_tally(gcre_ctx* c, int level, gcre_gene_tally* t) {
+  if (!c) return GCRE_ERR_ARG;
+  if (level < 0 || level > 5) return fail(c, GCRE_ERR_ARG, "gene tally: level index must be 0..5");
+  if (t && t->ctx != c) return fail(c, GCRE_ERR_ARG, "gene tally does not belong to this context");
+  c->pp_tally[level] = t;
+  return GCRE_OK;
+}
+
+int gcre_gene_tally_read(gcre_gene_tally* t, double* score, int64_t* ordinal, int32_t* src, int32_t* trg, int32_t* cases,
+                         int32_t* ctrls) {
+  if (!t || !t->ctx) return GCRE_ERR_ARG;
+  gcre_ctx* c = t->ctx;
+  (void)hipSetDevice(c->device);
+  if (t->last) HIP_TRY(c, hipStreamSynchronize(t->last));
+  const size_t n = (size_t)t->n_slots;
+  std::vector<uint64_t> key(n);
+  HIP_TRY(c, hipMemcpy(key.data(), t->d_bkey, n * 8, hipMemcpyDeviceToHost));
+  if (score)
+    for (size_t g = 0; g < n; g++) score[g] = key[g] ? key_to_score(key[g]) : -std::numeric_limits<double>::infinity();
+  if (ordinal) HIP_TRY(c, hipMemcpy(ordinal, t->d_bord, n * 8, hipMemcpyDeviceToHost));
+  if (src) HIP_TRY(c, hipMemcpy(src, t->d_bsrc, n * 4, hipMemcpyDeviceToHost));
+  if (trg) HIP_TRY(c, hipMemcpy(trg, t->d_btrg, n * 4, hipMemcpyDeviceToHost));
+  if (cases) HIP_TRY(c, hipMemcpy(cases, t->d_bcases, n * 4, hipMemcpyDeviceToHost));
+  if (ctrls) HIP_TRY(c, hipMemcpy(ctrls, t->d_bctrls, n * 4, hipMemcpyDeviceToHost));
+  return GCRE_OK;
+}
+
+void gcre_gene_tally_free(gcre_gene_tally* t) {
+  if (!t) return;
+  if (gcre_ctx* c = t->ctx) {
+    (void)hipSetDevice(c->device);
+    if (t->last) (void)hipStreamSynchronize(t->last);
+    if (c->armed_tally == t) c->armed_tally = nullptr;
+    for (auto& p : c->pp_tally)
+      if (p == t) p = nullptr;
+    auto& v = c->live_tallies;
+    v.erase(std::remove(v.begin(), v.end(), t), v.end());
+  }
+  for (void* p : {(void*)t->d_genes0, (void*)t->d_genes1, (void*)t->d_ck, (void*)t->d_cidx, (void*)t->d_bkey, (void*)t->d_bord,
+                  (void*)t->d_bsrc, (void*)t->d_btrg, (void*)t->d_bcases, (void*)t->d_bctrls})
+    if (p) (void)hipFree(p);
+  delete t;
+}
+
+// ---- null exceedance counts ----
+gcre_exceed* gcre_exceed_create(gcre_ctx* c, const double* thresholds, int32_t m) {
+  if (!c) return nullptr;
+  auto bad = [&](const std::string& msg) -> gcre_exceed* {
+    fail(c, GCRE_ERR_ARG, "exceedance counts: " + msg);
+    return nullptr;
+  };
+  if (!thresholds) return bad("NULL thresholds");
+  if (m < 1 || m > kExceedMax) return bad("the number of thresholds must be 1.." + std::to_string(kExceedMax) + ", not " + std::to_string(m));
+  for (int32_t i = 0; i < m; i++)
+    if (thresholds[i] != thresholds[i]) return bad("threshold " + std::to_string(i) + " is NaN");
+  (void)hipSetDevice(c->device);
+  gcre_exceed* x = new gcre_exceed();
+  x->ctx = c;
+  x->m = m;
+  x->thr.assign(thresholds, thresholds + m);
+  x->order.resize((size_t)m);
+  for (int32_t i = 0; i < m; i++) x->order[(size_t)i] = i;
+  std::stable_sort(x->order.begin(), x->order.end(), [&](int32_t a, int32_t b) { return thresholds[a] < thresholds[b]; });
+  // both images are monotone in the threshold: one order serves both.  Observed scores are compared as score keys
+  // (gcre_kernels.hip: score_key); a zero threshold takes the key of -0.0, so that a score of either zero reaches it, and
+  // -inf the smallest key a score can have
+  std::vector<uint32_t> pat((size_t)m);
+  std::vector<uint64_t> tkey((size_t)m);
+  for (int32_t j = 0; j < m; j++) {
+    double t = thresholds[x->order[(size_t)j]];
+    pat[(size_t)j] = f32_threshold(t);
+    if (t == 0) t = -0.0;
+    uint64_t b;
+    std::memcpy(&b, &t, 8);
+    const uint64_t k = (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+    tkey[(size_t)j] = t > -std::numeric_limits<double>::infinity() ? k : 1;
+  }
+  c->live_exceeds.push_back(x);
+  hipError_t e = hipMalloc((void**)&x->d_pat, (size_t)m * 4);
+  if (e == hipSuccess) e = hipMalloc((void**)&x->d_tkey, (size_t)m * 8);
+  if (e == hipSuccess) e = hipMalloc((void**)&x->d_hist, (size_t)m * 8);
+  if (e == hipSuccess) e = hipMalloc((void**)&x->d_ohist, (size_t)m * 8);
+  if (e == hipSuccess) e = hipMemcpyAsync(x->d_pat, pat.data(), (size_t)m * 4, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(x->d_tkey, tkey.data(), (size_t)m * 8, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(x->d_hist, 0, (size_t)m * 8, c->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(x->d_ohist, 0, (size_t)m * 8, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);   // (the vectors are locals)
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    gcre_exceed_free(x);
+    fail(c, GCRE_ERR_DEVICE, std::string("exceedance counts: ") + hipGetErrorString(e));
+    return nullptr;
+  }
+  return x;
+}
+
+int gcre_join_set_exceed(gcre_ctx* c, gcre_exceed* x) {
+  if (!c) return GCRE_ERR_ARG;
+  if (x && x->ctx != c) return fail(c, GCRE_ERR_ARG, "exceedance counts do not belong to this context");
+  c->armed_exceed = x;
+  return GCRE_OK;
+}
+
+int gcre_process_paths_set_exceed(gcre_ctx* c, int level, gcre_exceed* x) {
+  if (!c) return GCRE_ERR_ARG;
+  if (level < 0 || level > 5) return fail(c, GCRE_ERR_ARG, "exceedance counts: level index must be 0..5");
+  if (x && x->ctx != c) return fail(c, GCRE_ERR_ARG, "exceedance counts do not belong to this context");
+  c->pp_exceed[level] = x;
+  return GCRE_OK;
+}
+
+int gcre_exceed_read(gcre_exceed* x, uint64_t* exceed, uint64_t* observed, int64_t* perms_counted, int64_t* paths_counted) {
+  if (!x || !x->ctx) return GCRE_ERR_ARG;
+  gcre_ctx* c = x->ctx;
+  if (int rc = exceed_wait(c)) return rc;
+  const size_t m = (size_t)x->m;
+  std::vector<unsigned long long> h(m);
+  for (int which = 0; which < 2; which++) {
+    uint64_t* out = which ? observed : exceed;
+    if (!out) continue;
+    HIP_TRY(c, hipMemcpy(h.data(), which ? x->d_ohist : x->d_hist, m * 8, hipMemcpyDeviceToHost));
+    uint64_t run = 0;
+    for (size_t j = m; j-- > 0;) {   // a value in bin j reaches thresholds 0..j of the ascending order
+      run += h[j];
+      out[(size_t)x->order[j]] = run;
+    }
+  }
+  if (perms_counted) *perms_counted = x->perms;
+  if (paths_counted) *paths_counted = x->paths;
+  return GCRE_OK;
+}
+
+int gcre_exceed_reset(gcre_exceed* x) {
+  if (!x || !x->ctx) return GCRE_ERR_ARG;
+  gcre_ctx* c = x->ctx;
+  if (int rc = exceed_wait(c)) return rc;
+  HIP_TRY(c, hipMemset(x->d_hist, 0, (size_t)x->m * 8));
+  HIP_TRY(c, hipMemset(x->d_ohist, 0, (size_t)x->m * 8));
+  if (x->d_pc) HIP_TRY(c, hipMemset(x->d_pc, 0, (size_t)x->m * (size_t)x->pc_stride * 4));
+  std::fill(x->pc_load.begin(), x->pc_load.end(), 0);
+  x->perms = x->paths = 0;
+  return GCRE_OK;
+}
+
+int gcre_exceed_keep_perm_counts(gcre_exceed* x, int on) {
+  if (!x || !x->ctx) return GCRE_ERR_ARG;
+  gcre_ctx* c = x->ctx;
+  if (int rc = exceed_alive(c, x)) return rc;
+  if (int rc = exceed_wait(c)) return rc;
+  if (!on) {
+    if (x->d_pc) (void)hipFree(x->d_pc);
+    x->d_pc = nullptr;
+    x->pc_stride = 0;
+    x->pc_load.clear();
+    return GCRE_OK;
+  }
+  if (x->d_pc) return GCRE_OK;
+  if (x->perms != 0 || x->paths != 0)
+    return fail(c, GCRE_ERR_ARG, "exceedance counts: per-permutation counts cannot be switched on after something was counted (" +
+                                 std::to_string(x->perms) + " permutations, " + std::to_string(x->paths) + " joined paths): reset first");
+  const int64_t K = c->g.K;
+  if (K <= 0) return fail(c, GCRE_ERR_ARG, "exceedance counts: per-permutation counts need a context with permutations (it has 0 iterations)");
+  if ((int64_t)x->m * K > kExceedPermCells)
+    return fail(c, GCRE_ERR_ARG, "exceedance counts: per-permutation counts of " + std::to_string(x->m) + " thresholds x " + std::to_string(K) +
+                                 " iterations exceed the limit of 2^26 = 67108864 cells (256 MB)");
+  const size_t bytes = (size_t)x->m * (size_t)c->g.Kpad * 4;
+  hipError_t e = hipMalloc((void**)&x->d_pc, bytes);
+  if (e == hipSuccess) e = hipMemset(x->d_pc, 0, bytes);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    if (x->d_pc) (void)hipFree(x->d_pc);
+    x->d_pc = nullptr;
+    return fail(c, GCRE_ERR_DEVICE, std::string("exceedance counts: per-permutation counts: ") + hipGetErrorString(e));
+  }
+  x->pc_stride = c->g.Kpad;
+  x->pc_load.assign((size_t)(c->g.Kpad / kPermTileMax), 0);
+  return GCRE_OK;
+}
+
+int gcre_exceed_read_perm_counts(gcre_exceed* x, uint64_t* out) {
+  if (!x || !x->ctx) return GCRE_ERR_ARG;
+  gcre_ctx* c = x->ctx;
+  if (!x->d_pc) return fail(c, GCRE_ERR_ARG, "exceedance counts: the object keeps no per-permutation counts (gcre_exceed_keep_perm_counts)");
+  if (!out) return fail(c, GCRE_ERR_ARG, "exceedance counts: NULL output");
+  if (int rc = exceed_wait(c)) return rc;
+  const size_t m = (size_t)x->m, K = (size_t)c->g.K, stride = (size_t)x->pc_stride;
+  std::vector<uint32_t> h(m * stride);
+  HIP_TRY(c, hipMemcpy(h.data(), x->d_pc, m * stride * 4, hipMemcpyDeviceToHost));
+  std::vector<uint64_t> run(K, 0);
+  for (size_t j = m; j-- > 0;) {   // as gcre_exceed_read: a value in bin j reaches thresholds 0..j of the ascending order
+    const uint32_t* row = h.data() + j * stride;
+    uint64_t* dst = out + (size_t)x->order[j] * K;
+    for (size_t r = 0; r < K; r++) {
+      run[r] += row[r];
+      dst[r] = run[r];
+    }
+  }
+  return GCRE_OK;
+}
+
+// Step-down max-T.  Set j is the joined path whose observed score is threshold j: its null values, found
+// in the bins of the thresholds strictly below it, are what the join's per-permutation counts hold too many of once the
+// better rows are taken out of the family.
+int gcre_exceed_stepdown(gcre_exceed* x, const gcre_set_input* in, int64_t* n_ge) {
+  if (!x || !x->ctx) return GCRE_ERR_ARG;
+  gcre_ctx* c = x->ctx;
+  if (int rc = exceed_alive(c, x)) return rc;
+  if (!in || !n_ge) return fail(c, GCRE_ERR_ARG, "stepdown: NULL argument");
+  if (!x->d_pc)
+    return fail(c, GCRE_ERR_ARG, "stepdown: the object keeps no per-permutation counts (gcre_exceed_keep_perm_counts)");
+  const Geometry& g = c->g;
+  const int K = g.K, M = g.method, m = x->m;
+  if (x->perms != K || x->paths <= 0)
+    return fail(c, GCRE_ERR_ARG, "stepdown: the object must hold exactly one full pass of one join (" + std::to_string(x->perms) +
+                                     " permutations of " + std::to_string(x->paths) + " joined paths counted, the context has " +
+                                     std::to_string(K) + " iterations)");
+  if (in->n_sets != m)
+    return fail(c, GCRE_ERR_ARG, "stepdown: " + std::to_string(in->n_sets) + " sets for " + std::to_string(m) + " thresholds");
+  for (int j = 0; j < m; j++)
+    if (!std::isfinite(x->thr[(size_t)j])) return fail(c, GCRE_ERR_ARG, "stepdown: threshold " + std::to_string(j) + " is not finite");
+  if (int rc = check_sets(c, in, "stepdown")) return rc;
+  for (int64_t s = 0; s < m; s++)
+    if (!set_is_valid(in, s)) return fail(c, GCRE_ERR_ARG, "stepdown: set " + std::to_string(s) + " has an NA member");
+  if (int rc = exceed_wait(c)) return rc;
+
+  // the host stage of gcre_score_sets: per set its union rows and counts
+  const int Wp = g.Wp;
+  const size_t RW = (size_t)M * Wp;
+  const SetUnion un(g.W, g.n, g.n_cases);
+  std::vector<uint64_t> urows((size_t)m * RW, 0);
+  std::vector<int32_t> cnt((size_t)m * 4, 0);   // cases_pos, ctrls_pos, cases_neg, ctrls_neg
+  std::vector<uint32_t> tot((size_t)m * M);
+  for (int64_t s = 0; s < m; s++) {
+    int32_t* k = cnt.data() + 4 * s;
+    un.build(in, s, urows.data() + (size_t)s * RW, (size_t)Wp, M == 2, k);
+    tot[(size_t)s * M] = (uint32_t)(k[0] + k[1]);
+    if (M == 2) tot[(size_t)s * M + 1] = (uint32_t)(k[2] + k[3]);
+  }
+  // cap[j] = the last sorted index strictly below threshold j (compared as f64: tied rows do not exclude one another)
+  std::vector<int32_t> cap((size_t)m);
+  for (int b = 0, first = 0; b < m; b++) {
+    if (x->thr[(size_t)x->order[(size_t)b]] > x->thr[(size_t)x->order[(size_t)first]]) first = b;
+    cap[(size_t)x->order[(size_t)b]] = first - 1;
+  }
+
+  (void)hipSetDevice(c->device);
+  const size_t stride = (size_t)x->pc_stride, cells = (size_t)m * stride;
+  std::vector<double> obs((size_t)m);
+  std::vector<uint32_t> got((size_t)m + 1, 0);
+  int64_t off_set = -1;   // the first set whose observed score is not its threshold, bit for bit
+  DevScratch d(c->stream);
+  const uint64_t* d_rows = d.put(urows.data(), urows.size());
+  const int32_t* d_cnt = d.put(cnt.data(), cnt.size());
+  const uint32_t* d_tot = d.put(tot.data(), tot.size());
+  const int32_t* d_cap = d.put(cap.data(), (size_t)m);
+  double* d_obs = d.take<double>((size_t)m);
+  uint32_t* d_out = d.take<uint32_t>((size_t)m + 1);   // n_ge per sorted threshold, then the bad counter
+  if (d.ok()) d.e = launch_set_observed(d_cnt, m, M, c->d_dvt, d_obs, c->stream);
+  d.download(obs.data(), d_obs, (size_t)m);
+  d.sync();
+  for (int64_t s = 0; d.ok() && s < m && off_set < 0; s++)
+    if (std::memcmp(&obs[(size_t)s], &x->thr[(size_t)s], 8) != 0) off_set = s;
+  if (d.ok() && off_set < 0) {
+    uint32_t* d_E = d.take<uint32_t>(cells);
+    d.zero(d_E, cells);
+    d.zero(d_out, (size_t)m + 1);
+    StepdownArgs a{};
+    fill_set_launch(a, c, d_rows, d_tot, m);
+    a.pat = x->d_pat;
+    a.cap = d_cap;
+    a.E = d_E;
+    a.m = m;
+    a.stride = (int)stride;
+    const StepdownFinishArgs f{x->d_pc, d_E, d_out, d_out + m, m, (int)stride, K};
+    if (d.ok()) d.e = launch_stepdown_null(a, M, c->stream);
+    if (d.ok()) c->stepdown_launches++;
+    if (d.ok()) d.e = launch_stepdown_finish(f, c->stream);
+    if (d.ok()) c->stepdown_launches++;
+    d.download(got.data(), d_out, (size_t)m + 1);
+    d.sync();
+  }
+  d.release();   // (before the error state is cleared, as ever)
+  if (!d.ok()) {
+    (void)hipGetLastError();
+    return fail(c, GCRE_ERR_DEVICE, std::string("stepdown: ") + hipGetErrorString(d.e));
+  }
+  if (off_set >= 0) {
+    char buf[256];
+    std::snprintf(buf, sizeof buf, ": its observed score is %.17g, threshold %lld is %.17g (the rows must be the rows the thresholds came from)",
+                  obs[(size_t)off_set], (long long)off_set, x->thr[(size_t)off_set]);
+    return fail(c, GCRE_ERR_ARG, "stepdown: set " + std::to_string(off_set) + buf);
+  }
+  if (got[(size_t)m] != 0)
+    return fail(c, GCRE_ERR_ASSERT, "assertion: stepdown: the sets are not distinct joined paths of the counted join (" +
+                                        std::to_string(got[(size_t)m]) + " permutations count more top rows than joined paths at a threshold)");
+  for (int b = 0; b < m; b++) n_ge[(size_t)x->order[(size_t)b]] = (int64_t)got[(size_t)b];
+  return GCRE_OK;
+}
+
+int64_t gcre_stepdown_launches(const gcre_ctx* c) { return c ? c->stepdown_launches : -1; }
+
+void gcre_exceed_free(gcre_exceed* x) {
+  if (!x) return;
+  if (gcre_ctx* c = x->ctx) {
+    (void)exceed_wait(c);
+    if (c->armed_exceed == x) c->armed_exceed = nullptr;
+    for (auto& p : c->pp_exceed)
+      if (p == x) p = nullptr;
+    auto& v = c->live_exceeds;
+    v.erase(std::remove(v.begin(), v.end(), x), v.end());
+  }
+  for (void* p : {(void*)x->d_pat, (void*)x->d_tkey, (void*)x->d_hist, (void*)x->d_ohist, (void*)x->d_pc})
+    if (p) (void)hipFree(p);
+  delete x;
+}
+
+}  // extern "C"

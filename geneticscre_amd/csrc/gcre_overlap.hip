@@ -1,7 +1,7 @@
 // gcre_overlap.hip -- carrier-overlap counts of caller-given sets (gcre_set_overlap): for every pair (a[i], b[j]) the
 // patients both carrier rows hold, cases and controls apart.
 //   * k_set_overlap  a popcount "GEMM" of the `a` rows against the `b` rows: AND + popcount over the rows' dwords
-// The context-side entry, gcre_set_overlap, is in gcre_host.hip.  DESIGN.md §3.9.
+// The context-side entry, gcre_set_overlap, is in gcre_host_stats.hip.  DESIGN.md §3.9.
 //
 // A block of four waves owns a 64 x 64 pair tile, a lane a 4 x 4 micro-tile of it with two counters per pair (32
 // accumulators).  Both operand tiles go through LDS in chunks of 32 dwords per row (one 128-byte line), double buffered; a lane reads one

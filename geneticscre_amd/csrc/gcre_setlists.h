@@ -1,0 +1,87 @@
+// gcre_setlists.h -- the host stage that gcre_score_sets, gcre_set_overlap and gcre_exceed_stepdown share (gcre_host_stats.hip):
+// what they refuse of a caller's set list, and the union rows and counts of one set.  Plain C++17 over include/gcre_hip.h, no
+// HIP: tests/native/setlists_main.cpp drives it on a machine without a GPU.
+#pragma once
+#include "../../include/gcre_hip.h"
+
+#include <string>
+#include <vector>
+
+namespace gcre_host __attribute__((visibility("hidden"))) {
+
+// The two checks return a code and leave the message in `msg`; `who` opens it.  They are separate so that an entry can put
+// checks of its own between them.
+
+// The shape of the input: the column count against the context's n patients, negative counts, NULL arrays.
+inline int check_set_shape(const gcre_set_input* in, int n, const std::string& who, std::string& msg) {
+  const int64_t S = in->n_sets;
+  if (in->n_cols != n)
+    msg = who + ": the rows have " + std::to_string(in->n_cols) + " columns, not n_cases + n_ctrls = " + std::to_string(n);
+  else if (S < 0 || in->n_rows < 0 || (S > 0 && (!in->set_off || !in->members)) || (in->n_rows > 0 && !in->rows))
+    msg = who + ": bad input (a negative count or a NULL array)";
+  else
+    return GCRE_OK;
+  return GCRE_ERR_ARG;
+}
+
+// Every set's members and signs: no empty set, rows -1 (NA) .. n_rows - 1, signs +1 or -1.
+inline int check_set_members(const gcre_set_input* in, const std::string& who, std::string& msg) {
+  auto bad = [&](int code, int64_t s, const std::string& what) {
+    msg = who + ": set " + std::to_string(s) + what;
+    return code;
+  };
+  for (int64_t s = 0; s < in->n_sets; s++) {
+    const int64_t b = in->set_off[s], e = in->set_off[s + 1];
+    if (b < 0 || e <= b) return bad(GCRE_ERR_ARG, s, " has no members");
+    for (int64_t i = b; i < e; i++) {
+      const int32_t row = in->members[i];
+      if (row < -1 || row >= in->n_rows)
+        return bad(GCRE_ERR_RANGE, s, ": member row " + std::to_string(row) + " out of range (" + std::to_string(in->n_rows) + " rows)");
+      if (in->signs && in->signs[i] != 1 && in->signs[i] != -1)
+        return bad(GCRE_ERR_ARG, s, ": sign " + std::to_string(in->signs[i]) + " is neither +1 nor -1");
+    }
+  }
+  return GCRE_OK;
+}
+
+// no member of set s is NA
+inline bool set_is_valid(const gcre_set_input* in, int64_t s) {
+  bool valid = true;
+  for (int64_t i = in->set_off[s]; i < in->set_off[s + 1]; i++) valid = valid && in->members[i] >= 0;
+  return valid;
+}
+
+// The case / control masks of the n patients (cases are the first n_cases columns), and one set's union rows: P = the OR of
+// its (+) members, N = P + neg_off the OR of its (-) members (`split` off: everything into P, N is not touched), within the
+// n patients -- with k = cases_pos, ctrls_pos, cases_neg, ctrls_neg (NULL: not counted).  `P` (and N) hold W zeroed words at
+// the least; no member is NA.
+struct SetUnion {
+  int W;
+  std::vector<uint64_t> cases, ctrls;
+  SetUnion(int words, int n, int n_cases) : W(words), cases((size_t)words, 0), ctrls((size_t)words, 0) {
+    for (int q = 0; q < n; q++) (q < n_cases ? cases : ctrls)[(size_t)q / 64] |= uint64_t(1) << (q % 64);
+  }
+  int count_and(const uint64_t* a, const std::vector<uint64_t>& m) const {
+    int n = 0;
+    for (int w = 0; w < W; w++) n += __builtin_popcountll(a[w] & m[w]);
+    return n;
+  }
+  void build(const gcre_set_input* in, int64_t s, uint64_t* P, size_t neg_off, bool split, int32_t k[4]) const {
+    uint64_t* N = split ? P + neg_off : P;
+    for (int64_t i = in->set_off[s]; i < in->set_off[s + 1]; i++) {
+      const uint64_t* r = in->rows + (size_t)in->members[i] * W;
+      uint64_t* d = (split && in->signs && in->signs[i] == -1) ? N : P;
+      for (int w = 0; w < W; w++) d[w] |= r[w] & (cases[w] | ctrls[w]);
+    }
+    if (!k) return;   // the rows only
+    k[0] = count_and(P, cases);
+    k[1] = count_and(P, ctrls);
+    k[2] = k[3] = 0;
+    if (split) {
+      k[2] = count_and(N, ctrls);   // the (-) half counts the other way round (methods.h:183-184)
+      k[3] = count_and(N, cases);
+    }
+  }
+};
+
+}  // namespace gcre_host

@@ -38,7 +38,7 @@ def case_counts(n):
     return sorted(c for c in out if 1 <= c <= n - 1)
 
 
-def raw_overlap(ex, sets, packed, n_cols, a=None, b=None, na=None, nb=None, want_size=True, want_both=True):
+def raw_overlap(ex, sets, packed, n_cols, a=None, b=None, na=None, nb=None, want_size=True, want_both=True, signs=None):
     """gcre_set_overlap through the C entry: (rc, size, both)."""
     lib = api._overlap_lib()
     S = len(sets)
@@ -49,7 +49,8 @@ def raw_overlap(ex, sets, packed, n_cols, a=None, b=None, na=None, nb=None, want
     ib = None if b is None else np.ascontiguousarray(b, np.int64)
     na = (S if ia is None else len(ia)) if na is None else na
     nb = (S if ib is None else len(ib)) if nb is None else nb
-    inp = api.gcre_set_input(S, api._ptr(off), api._ptr(mem), None, api._ptr(packed), len(packed), n_cols)
+    sg = None if signs is None else np.ascontiguousarray(np.concatenate([np.asarray(s, np.int64) for s in signs]), np.int32)
+    inp = api.gcre_set_input(S, api._ptr(off), api._ptr(mem), api._ptr(sg), api._ptr(packed), len(packed), n_cols)
     size = np.full((S, 2), -7, np.int32) if want_size else None
     both = np.full((max(na, 0), max(nb, 0), 2), -7, np.int32) if want_both else None
     rc = lib.gcre_set_overlap(ex._h, ctypes.byref(inp), api._ptr(ia), na, api._ptr(ib), nb, api._ptr(size), api._ptr(both))
@@ -125,6 +126,31 @@ def test_contexts_give_the_same_arrays():
         for g, g2, w in zip(got, got2, want):
             np.testing.assert_array_equal(g, w)
             np.testing.assert_array_equal(g2, w)
+
+
+def test_signs_do_not_split_the_carrier_row():
+    """A signed context, signs given: the carrier row is still the OR of ALL members -- the host stage that gcre_score_sets
+    splits by sign is the one that builds it.  The same arrays as without signs, and as the numpy OR."""
+    n, nc = 70, 31
+    rng = np.random.default_rng(70)
+    rows = carrier_matrix(rng, n, R=6)
+    sets = [[2, 3], [3, 4, 5], [0, -1, 2], [1], [2, 2, 5]]
+    signs = [[-1, -1], [1, -1, 1], [1, -1, -1], [-1], [-1, 1, -1]]   # every member (-), mixed, an NA member, the empty row
+    carriers = np.array([np.any([rows[m] for m in s], axis=0) for s in sets])
+    case = np.arange(n) < nc
+    want_size = np.array([[(c & case).sum(), (c & ~case).sum()] for c in carriers], np.int32)
+    want_both = np.array([[[(x & y & case).sum(), (x & y & ~case).sum()] for y in carriers] for x in carriers], np.int32)
+    want_size[2] = -1
+    want_both[2], want_both[:, 2] = 0, 0
+    packed = api.pack_carriers(rows, n)
+    ex = api.JoinExec(2, nc, n - nc, 0)
+    rc, size, both = raw_overlap(ex, sets, packed, n, signs=signs)
+    rc0, size0, both0 = raw_overlap(ex, sets, packed, n)
+    ex.close()
+    assert rc == api.GCRE_OK and rc0 == api.GCRE_OK
+    for got, plain, want in ((size, size0, want_size), (both, both0, want_both)):
+        np.testing.assert_array_equal(got, plain)
+        np.testing.assert_array_equal(got, want)
 
 
 @pytest.mark.parametrize("n", [33, 200])

@@ -89,6 +89,18 @@ def test_library_exports_every_declared_symbol():
     assert declared <= exported
 
 
+def test_variant_library_without_an_abi_version_is_refused(monkeypatch):
+    """GCRE_LIB naming a library from before gcre_abi_version existed (here: the R tests' recording backend, which has
+    none): the message that says so, raised before any symbol of the library is bound."""
+    from geneticscre_amd import build
+    _, stub = build.build_r_mock()
+    monkeypatch.setattr(api, "_LIB", None)
+    monkeypatch.setenv("GCRE_LIB", stub)
+    with pytest.raises(api.GcreError, match=r"ABI \?, this tree expects 4 \(rebuild the variant"):
+        api.load_library()
+    assert api._LIB is None
+
+
 def test_product_never_imports_the_oracle():
     """The product path must not route through the CPU oracle: no module of geneticscre_amd mentions it."""
     pkg = os.path.join(ROOT, "geneticscre_amd")
