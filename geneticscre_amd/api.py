@@ -136,6 +136,8 @@ EXPORTS = [
     "gcre_exceed_reset", "gcre_exceed_free",
     "gcre_exceed_keep_perm_counts", "gcre_exceed_read_perm_counts",
     "gcre_exceed_stepdown", "gcre_stepdown_launches",
+    "gcre_hits_create", "gcre_join_set_hits", "gcre_process_paths_set_hits", "gcre_hits_count", "gcre_hits_read",
+    "gcre_hits_reset", "gcre_hits_free", "gcre_hits_launches",
 ]
 
 
@@ -271,6 +273,15 @@ _FEATURES = {
                  "step-down counts (gcre_exceed_stepdown)", {
         "gcre_exceed_stepdown": (_I, [_V, ctypes.POINTER(gcre_set_input), _P]),
         "gcre_stepdown_launches": (_I64, [_V])}),
+    "hits": (None, ["gcre_hits_create"], "hit lists (gcre_hits_create)", {
+        "gcre_hits_create": (_V, [_V, ctypes.c_double, _I64]),
+        "gcre_join_set_hits": (_I, [_V, _V]),
+        "gcre_process_paths_set_hits": (_I, [_V, _I, _V]),
+        "gcre_hits_count": (_I, [_V, ctypes.POINTER(_I64), ctypes.POINTER(_I64)]),
+        "gcre_hits_read": (_I, [_V, _I64, _P, _P, _P, _P, _P, _P]),
+        "gcre_hits_reset": (_I, [_V]),
+        "gcre_hits_free": (None, [_V]),
+        "gcre_hits_launches": (_I64, [_V])}),
 }
 del _V, _P, _I, _I32, _I64
 
@@ -295,6 +306,7 @@ _genes_lib = functools.partial(_feature_lib, "genes")
 _exceed_lib = functools.partial(_feature_lib, "exceed")
 _perm_counts_lib = functools.partial(_feature_lib, "perm_counts")
 _stepdown_lib = functools.partial(_feature_lib, "stepdown")
+_hits_lib = functools.partial(_feature_lib, "hits")
 
 
 OVERLAP_TILE = 64   # kOverlapTile: pairs per edge of a k_set_overlap block's tile
@@ -453,6 +465,86 @@ class ExceedCounts:
         h, self._h = self._h, None
         if h and self._owner._h:       # (a closed context has freed it already)
             self._lib.gcre_exceed_free(h)
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+HITS_CAP_MAX = 1 << 26   # kHitsCapMax: records of one HitList (32 B each on the device)
+
+
+@dataclass
+class Hits:
+    """gcre_hits_count / gcre_hits_read: the joined paths at or above a HitList's cut-off, best first (score descending as
+    doubles, then ordinal ascending).  The six arrays are empty when the list overflowed (``complete`` False): ``found`` is
+    exact all the same."""
+
+    found: int             # joined paths at or above the cut-off (may exceed the list's cap)
+    paths: int             # joined paths looked at
+    complete: bool         # found <= cap: the arrays hold every hit
+    score: np.ndarray      # float64
+    ordinal: np.ndarray    # int64 joined-path ordinal
+    src: np.ndarray        # int32 row of paths0 (Score.src)
+    trg: np.ndarray        # int32 row of paths1 (Score.trg)
+    cases: np.ndarray
+    ctrls: np.ndarray
+
+    def as_join_result(self, null) -> "JoinResult":
+        """The hits as ``report.results_table`` takes a level: a JoinResult (scores ascending, as a top-k list has them)
+        whose ``pvalues()`` compare with ``null``, the level's null maxima."""
+        r = slice(None, None, -1)
+        return JoinResult(self.score[r].copy(), self.src[r].copy(), self.trg[r].copy(), self.cases[r].copy(),
+                          self.ctrls[r].copy(), np.asarray(null, dtype=np.float32))
+
+
+class HitList:
+    """gcre_hits: every joined path of a join whose observed score is >= ``cutoff``, up to ``cap``
+    records (32 x cap bytes of device memory).  Pass it as ``JoinExec.join(..., hits=h)``, ``process_paths(..., hits={"4":
+    h})`` or ``ResidentPlan.run(..., hits={"4": h})``, then ``read()``.  The list ADDS: shards of one join append into one
+    list, a join collected twice is listed twice (``reset()`` starts over)."""
+
+    def __init__(self, owner: "JoinExec", cutoff: float, cap: int = 1 << 20):
+        self.cutoff, self.cap = float(cutoff), int(cap)
+        self._owner, self._lib, self._h = owner, _hits_lib(), None
+        if not owner._h:
+            raise GcreError("hit list: the context is closed")
+        if not -(1 << 63) <= self.cap < (1 << 63):
+            raise GcreError(f"hit list: cap must be 1..{HITS_CAP_MAX} (2^26), not {self.cap}")
+        self._h = self._lib.gcre_hits_create(owner._h, self.cutoff, self.cap)
+        if not self._h:
+            owner._raise(GCRE_ERR_ARG)
+
+    def _alive(self):
+        if not self._h or not self._owner._h:     # (a closed context has freed it already)
+            raise GcreError("hit list does not belong to this context (freed, or its context is closed)")
+        return self._h
+
+    def count(self) -> Tuple[int, int]:
+        """(found, paths): joined paths at or above the cut-off, and joined paths looked at."""
+        found, paths = ctypes.c_int64(0), ctypes.c_int64(0)
+        self._owner._check(self._lib.gcre_hits_count(self._alive(), ctypes.byref(found), ctypes.byref(paths)))
+        return int(found.value), int(paths.value)
+
+    def read(self) -> Hits:
+        found, paths = self.count()
+        n = found if found <= self.cap else 0
+        score, ordinal = np.zeros(n, np.float64), np.zeros(n, np.int64)
+        src, trg, cases, ctrls = (np.zeros(n, np.int32) for _ in range(4))
+        if found <= self.cap:
+            self._owner._check(self._lib.gcre_hits_read(self._alive(), found, _ptr(score), _ptr(ordinal), _ptr(src), _ptr(trg),
+                                                        _ptr(cases), _ptr(ctrls)))
+        return Hits(found, paths, found <= self.cap, score, ordinal, src, trg, cases, ctrls)
+
+    def reset(self) -> None:
+        self._owner._check(self._lib.gcre_hits_reset(self._alive()))
+
+    def free(self) -> None:
+        h, self._h = self._h, None
+        if h and self._owner._h:       # (a closed context has freed it already)
+            self._lib.gcre_hits_free(h)
 
     def __del__(self):
         try:
@@ -872,7 +964,8 @@ class JoinExec:
     def join(self, uids, paths0: PathSet, paths1: PathSet, paths_res: Optional[PathSet] = None,
              shard: Optional[Tuple[int, int]] = None, d_null_out: int = 0,
              keep: Optional[Tuple[int, int]] = None, keep_mode: int = 1, exchange=None, exchanges: int = 0,
-             tally: Optional["GeneTally"] = None, exceed: Optional["ExceedCounts"] = None) -> JoinResult:
+             tally: Optional["GeneTally"] = None, exceed: Optional["ExceedCounts"] = None,
+             hits: Optional["HitList"] = None) -> JoinResult:
         """JoinExec::join (src/join_base.cpp:189-264).  ``paths_res`` receives the joined rows when given.
         ``uids`` is a UidRelSet (uploaded for this call) or a DeviceUids (already resident).  ``shard`` restricts
         scoring to a range of joined paths; ``keep`` restricts the rows written to ``paths_res`` to a range (plus
@@ -880,7 +973,8 @@ class JoinExec:
         only the rows that get count planes (all rows are still written).  ``exchange(k0, k1)`` is called ``exchanges``
         times during the join (gcre_join_opts.exchange): it MAX-all-reduces d_null_out[k0:k1] across the ranks in place.
         ``tally``: a GeneTally this join's scored paths are folded into (gcre_join_set_tally).  ``exceed``: an ExceedCounts
-        this join's null values and observed scores are counted into (gcre_join_set_exceed)."""
+        this join's null values and observed scores are counted into (gcre_join_set_exceed).  ``hits``: a HitList this
+        join's scored paths at or above its cut-off are appended to (gcre_join_set_hits)."""
         opts = gcre_join_opts(0, 0, 0, 0, None, 0, 0, 0, None, None)
         cb = None
         if exchange is not None and exchanges > 0:
@@ -918,6 +1012,10 @@ class JoinExec:
             if exceed._owner is not self or not exceed._h:
                 raise GcreError("exceedance counts do not belong to this context")
             self._check(_exceed_lib().gcre_join_set_exceed(self._h, exceed._h))
+        if hits is not None:
+            if hits._owner is not self or not hits._h:
+                raise GcreError("hit list does not belong to this context")
+            self._check(_hits_lib().gcre_join_set_hits(self._h, hits._h))
         if isinstance(uids, DeviceUids):
             rc = self._lib.gcre_join_uids(self._h, uids._h, paths0._h, paths1._h, res_h, ctypes.byref(opts),
                                           ctypes.byref(res))
@@ -1087,17 +1185,22 @@ def process_paths_devices(problem, devices=None, tallies=None) -> Dict[str, obje
     return {f"lst{i + 1}": (None if outs[i].n < 0 else _take_result(lib, outs[i])) for i in range(5)}
 
 
-def process_paths(problem, device: int = 0, exec_: Optional[JoinExec] = None, tallies=None, exceeds=None) -> Dict[str, object]:
+def process_paths(problem, device: int = 0, exec_: Optional[JoinExec] = None, tallies=None, exceeds=None,
+                  hits=None) -> Dict[str, object]:
     """ProcessPaths (src/wrapper.cpp:177-281) in one native call.  Returns {"lst1": JoinResult | None, ...}.
 
     ``problem`` carries the 39 arguments as arrays (geneticscre_amd.synth.Problem).  ``tallies``: level name ("1b", "2",
     .., "5"; "1a" too) -> GeneTally of ``exec_``: that level's join folds its scored paths into it.  ``exceeds``: level name
     -> ExceedCounts of ``exec_``: that level's join counts into it (all permutations, the observed scores once).
+    ``hits``: level name -> HitList of ``exec_``: that level's join appends its scored paths at or above the list's cut-off
+    (once, however many permutation windows the call walks).
     """
     if tallies and exec_ is None:
         raise GcreError("process_paths: gene tallies live on a context; pass the JoinExec they were made on as exec_")
     if exceeds and exec_ is None:
         raise GcreError("process_paths: exceedance counts live on a context; pass the JoinExec they were made on as exec_")
+    if hits and exec_ is None:
+        raise GcreError("process_paths: hit lists live on a context; pass the JoinExec they were made on as exec_")
     ex = exec_ or JoinExec(problem.method, problem.n_cases, problem.n_ctrls, problem.iterations, device)
     ex.top_k = problem.top_k
     lib = ex._lib
@@ -1143,6 +1246,13 @@ def process_paths(problem, device: int = 0, exec_: Optional[JoinExec] = None, ta
             raise GcreError("exceedance counts do not belong to this context")
     for name, x in (exceeds or {}).items():
         ex._check(_exceed_lib().gcre_process_paths_set_exceed(ex._h, LEVEL_INDEX[name], x._h))
+    for name, h in (hits or {}).items():
+        if name not in LEVEL_INDEX:
+            raise GcreError(f"process_paths: no level {name!r} (levels are {', '.join(LEVEL_INDEX)})")
+        if h._owner is not ex or not h._h:
+            raise GcreError("hit list does not belong to this context")
+    for name, h in (hits or {}).items():
+        ex._check(_hits_lib().gcre_process_paths_set_hits(ex._h, LEVEL_INDEX[name], h._h))
     rc = lib.gcre_process_paths(ex._h, ctypes.byref(inp), outs)
     ex._check(rc)
     result: Dict[str, object] = {}
@@ -1337,7 +1447,7 @@ class ResidentPlan:
         return int(min(most, np.floor(np.log2(work / unit))))
 
     def run(self, rank: int = 0, world: int = 1, d_null_out: int = 0, on_level=None,
-            keep_inspections: bool = False, exchange=None, tallies=None, exceeds=None) -> Dict[str, JoinResult]:
+            keep_inspections: bool = False, exchange=None, tallies=None, exceeds=None, hits=None) -> Dict[str, JoinResult]:
         """One pass over all levels.  Large permutation counts run in windows of whole 2048-permutation tiles (the count
         planes of the kept sets are per tile and have to fit in device memory): all levels for window 0, then all levels
         for window 1, ...  ``on_level(name, result, shard, window)`` sees every (level, window) result -- its null
@@ -1360,11 +1470,17 @@ class ResidentPlan:
 
         ``exceeds``: level name -> ExceedCounts of ``self.ex``; that level's join counts into it.  Every (level, window) is a
         join call of its own: the null values of the windows add up to all permutations, and the observed scores are
-        counted once per window (``Exceedances.paths`` says how often: it grows by the level's joined paths each time)."""
+        counted once per window (``Exceedances.paths`` says how often: it grows by the level's joined paths each time).
+
+        ``hits``: level name -> HitList of ``self.ex``; that level's join appends its scored paths at or above the list's
+        cut-off -- in the first window only (the observed scores do not depend on the window): a pass lists a level once.
+        One rank only."""
         if tallies and world > 1:
             raise GcreError("ResidentPlan.run: gene tallies need world == 1 (merging tallies across ranks is not supported)")
         if exceeds and world > 1:
             raise GcreError("ResidentPlan.run: exceedance counts need world == 1 (add the counts of sharded joins yourself)")
+        if hits and world > 1:
+            raise GcreError("ResidentPlan.run: hit lists need world == 1 (merging lists across ranks is not supported)")
         K = self.problem.iterations
         if self._window is None:
             self._window = self.planned_window()
@@ -1413,7 +1529,8 @@ class ResidentPlan:
                                  d_null_out=(d_null_out + 4 * k0) if d_null_out else 0,
                                  keep=self.needed_rows(name, rank, world), keep_mode=self.keep_mode(name),
                                  exchange=(lambda a, b_, name=name: exchange(name, a, b_)) if n_ex else None, exchanges=n_ex,
-                                 tally=(tallies or {}).get(name), exceed=(exceeds or {}).get(name))
+                                 tally=(tallies or {}).get(name), exceed=(exceeds or {}).get(name),
+                                 hits=(hits or {}).get(name) if k0 == 0 else None)
                 for k, v in self.ex.profile().items():
                     prof[k] = prof.get(k, 0) + v
                 if on_level is not None:

@@ -151,6 +151,7 @@ struct JoinPlan {
   gcre_gene_tally* tally = nullptr;   // the join's scored paths are folded into it (never set on a registered later join)
   gcre_exceed* exceed = nullptr;      // the join's null values and observed scores are counted into it (the same)
   bool exceed_observed = true;        // ... the observed scores too (false: a later permutation window of the same join)
+  gcre_hits* hits = nullptr;          // the join's scored paths at or above the list's cut-off are appended to it (the same)
   void take(const gcre_join_opts* o) {
     if (!o) return;
     if (o->keep_ranged) {
@@ -410,6 +411,11 @@ struct gcre_ctx {
   std::vector<gcre_exceed*> live_exceeds;
   gcre_exceed* armed_exceed = nullptr;
   gcre_exceed* pp_exceed[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  // hit lists (gcre_hits): the same three, and the k_hits_collect launches since gcre_create
+  std::vector<gcre_hits*> live_hits;
+  gcre_hits* armed_hits = nullptr;
+  gcre_hits* pp_hits[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  int64_t hits_launches = 0;
   uint64_t next_set_id = 0;
   size_t planes_out_max = (size_t)8 << 30;   // kept sets (method 1) whose planes are larger keep a recipe only
 
@@ -568,4 +574,20 @@ struct gcre_exceed {
   uint32_t* d_pc = nullptr;           // [m][pc_stride] u32, or nullptr: not kept
   int pc_stride = 0;                  // the context's Kpad
   std::vector<uint64_t> pc_load;      // per 2048-permutation tile: joined paths counted into its permutations' cells
+};
+
+// The hit list of one cut-off: the records of the joined paths whose observed score reaches it, in the
+// order the waves reserved them, as struct-of-arrays carved out of one allocation of 32 x cap bytes, and the 64-bit
+// cursor that counts every hit (also those past `cap`).  Appends: every chunk collected adds, whichever join it is of.
+struct gcre_hits {
+  gcre_ctx* ctx = nullptr;
+  double cutoff = 0;
+  uint64_t tkey = 1;                  // the cut-off as a score key (gcre_exceed's rule: either zero -> the key of -0.0, -inf -> 1)
+  int64_t cap = 0;
+  unsigned long long* d_cursor = nullptr;
+  void* d_rec = nullptr;              // [cap] x (i64 ordinal, u64 key, i32 src, i32 trg, i32 cases, i32 ctrls), array after array
+  int64_t paths = 0;                  // joined paths looked at
+  int64_t* ord() const { return (int64_t*)d_rec; }
+  uint64_t* key() const { return (uint64_t*)d_rec + cap; }
+  int32_t* field(int k) const { return (int32_t*)((uint64_t*)d_rec + 2 * cap) + (int64_t)k * cap; }   // 0 src, 1 trg, 2 cases, 3 ctrls
 };

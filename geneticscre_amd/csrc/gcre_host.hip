@@ -903,9 +903,9 @@ void merge_candidates(std::vector<Candidate>& cands, int top_k, gcre_result* out
 // kLaunch (the chain of gcre_join_ahead): the join's permutation kernels are launched -- on the main stream, into the join
 // index's own maxima, from the inspection that ran ahead -- and nothing is waited for; the call that comes for the join finds
 // it launched and only finishes it (wait, copy the maxima, merge the cached winners).
-// kCount (gcre_exceed armed on a join that was launched ahead): once the join's result is delivered, its chunks are replayed
-// from the inspection cache as far as each chunk's IeArgs, and the exceedance kernels are launched where the null kernels
-// were; no inspector, no null kernel, no selection, no result.
+// kCount (gcre_exceed or gcre_hits armed on a join that was launched ahead): once the join's result is delivered, its chunks
+// are replayed from the inspection cache as far as each chunk's IeArgs, and the exceedance kernels are launched where the
+// null kernels were (and k_hits_collect behind them); no inspector, no null kernel, no selection, no result.
 enum JoinMode { kFull = 0, kInspect = 1, kLaunch = 2, kCount = 3 };
 
 using EvList = std::vector<std::pair<hipEvent_t, hipEvent_t>>;
@@ -1102,6 +1102,34 @@ int count_exceed(gcre_ctx* c, const JoinPlan& jp, const ChunkBufs& b, int64_t s0
   return GCRE_OK;
 }
 
+// ---- hit lists (gcre_hits.hip): scored paths [s0, s1) of a chunk whose inspector output is in `b` ----
+// Queued on `st` where the tally and the observed counts are, for the same reason.  NOT idempotent either: run_chunk
+// collects a chunk exactly where and when it counts one.
+int collect_hits(gcre_ctx* c, gcre_hits* h, const ChunkBufs& b, int64_t cb, int64_t s0, int64_t s1, hipStream_t st) {
+  if (s1 <= s0) return GCRE_OK;
+  HitsArgs a{};
+  a.key = b.key.p + s0;
+  a.row0 = b.row0.p + s0;
+  a.row1 = b.row1.p + s0;
+  a.cases = b.cases.p + s0;
+  a.ctrls = b.ctrls.p + s0;
+  a.count = s1 - s0;
+  a.first = cb + s0;
+  a.tkey = h->tkey;
+  a.cursor = h->d_cursor;
+  a.cap = h->cap;
+  a.ord = h->ord();
+  a.hkey = h->key();
+  a.src = h->field(0);
+  a.trg = h->field(1);
+  a.hcases = h->field(2);
+  a.hctrls = h->field(3);
+  HIP_TRY(c, launch_hits_collect(a, c->cus, st));
+  c->hits_launches++;
+  h->paths += s1 - s0;
+  return GCRE_OK;
+}
+
 // The tail of a join whose kernels were launched ahead (run_join, kLaunch): wait for them, copy the maxima out of the join
 // index's own array, merge the winners its inspection cached.
 int finish_launched(gcre_ctx* c, const JoinPlan& jp, gcre_result* out) {
@@ -1129,8 +1157,8 @@ int finish_launched(gcre_ctx* c, const JoinPlan& jp, gcre_result* out) {
   if (int rc = deliver_join(c, jp, out, K, L.d_null.p, c->insp_stream, cands, L.ev_null, L.ev_stats, t_begin, nullptr))
     return rc;
   c->prof.ie_lookup_tiles += lookups;
-  // counts are sums: every chunk once, through the chunk loop itself (its cuts are the launch's)
-  if (jp.exceed)
+  // counts are sums, and a hit list appends: every chunk once, through the chunk loop itself (its cuts are the launch's)
+  if (jp.exceed || jp.hits)
     if (int rc = run_join(c, jp, nullptr, kCount)) return rc;
   return GCRE_OK;
 }
@@ -1421,6 +1449,7 @@ int begin_join(JoinRun& R, Begin* next) {
   if (jp.tally && mode == kFull)
     if (int rc = check_tally(c, jp.tally, u)) return rc;
   if (jp.exceed && jp.exceed->ctx != c) return fail(c, GCRE_ERR_ARG, "exceedance counts do not belong to this context");
+  if (jp.hits && jp.hits->ctx != c) return fail(c, GCRE_ERR_ARG, "hit list does not belong to this context");
   // ---- inspection cache: has this very join (same operand rows, kept set, shard, table) run on this index before? ----
   InspKey& ikey = R.ikey;
   if (c->insp_cache) {
@@ -2170,7 +2199,7 @@ int score_chunk_ie(JoinRun& R, ChunkRun& C, ChunkEnd* end) {
   ia.waves_per_xcd = spread_waves(xcd_waves(c, wpc), n * ie_tile_factor, 32);
   R.prof->inspect_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ti0).count();
   ia.stats = R.mode == kLaunch ? R.w_null + g.Kpad : R.flagblk + kFlagLookupTiles;   // zeroed with the block before the inspector ran
-  if (jp.exceed) {
+  if (jp.exceed || R.mode == kCount) {   // (a counting pass for a hit list alone stops here too)
     C.ie = ia;
     C.ie_planes = planes;
     C.ie_segs = nseg_scored;
@@ -2413,6 +2442,8 @@ int run_chunk(JoinRun& R, const Seg& sg, int64_t cb, int64_t ce, ChunkEnd* end) 
     if (int rc = count_exceed(R.c, R.jp, *C.b, C.s0, C.s1, R.st, (C.ie_ok && *end == ChunkEnd::kScored) ? &C.ie : nullptr,
                               C.ie_planes, C.ie_segs))
       return rc;
+  if (R.jp.hits && (R.mode == kFull || R.mode == kCount))
+    if (int rc = collect_hits(R.c, R.jp.hits, *C.b, C.cb, C.s0, C.s1, R.st)) return rc;
   if (R.mode == kCount) return GCRE_OK;
   if (int rc = collect_winners(R, C)) return rc;
   if (R.mode != kInspect) R.prof->paths += C.s1 - C.s0;   // (a launch books them on the profile of the join it is for)
@@ -2634,6 +2665,7 @@ void gcre_destroy(gcre_ctx* c) {
   while (!c->live_uids.empty()) free_uids(c->live_uids.back());
   while (!c->live_tallies.empty()) gcre_gene_tally_free(c->live_tallies.back());
   while (!c->live_exceeds.empty()) gcre_exceed_free(c->live_exceeds.back());
+  while (!c->live_hits.empty()) gcre_hits_free(c->live_hits.back());
   {
     std::vector<const gcre_pathset*> sets;
     for (const auto& kv : c->live_sets) sets.push_back(kv.second);
@@ -3063,6 +3095,8 @@ int gcre_join(gcre_ctx* c, int path_length, const int32_t* uid_count, const int6
   c->armed_tally = nullptr;
   jp.exceed = c->armed_exceed;
   c->armed_exceed = nullptr;
+  jp.hits = c->armed_hits;
+  c->armed_hits = nullptr;
   int rc = run_join(c, jp, out);
   free_uids(u);
   if (rc != GCRE_OK) gcre_result_free(out);
@@ -3126,6 +3160,8 @@ int gcre_join_uids(gcre_ctx* c, const gcre_uids* uids, const gcre_pathset* paths
   c->armed_tally = nullptr;
   jp.exceed = c->armed_exceed;
   c->armed_exceed = nullptr;
+  jp.hits = c->armed_hits;
+  c->armed_hits = nullptr;
   int rc = run_join(c, jp, out);
   if (rc != GCRE_OK) gcre_result_free(out);
   return rc;
@@ -3211,6 +3247,15 @@ int gcre_process_paths(gcre_ctx* c, const gcre_pp_input* in, gcre_result out[5])
   }
   if (any_exceed && in->shard_world > 1)
     return fail(c, GCRE_ERR_ARG, "exceedance counts cannot be armed for one device of several: add the counts of whole runs on the host");
+  gcre_hits* hit_lists[6];
+  bool any_hits = false;
+  for (int i = 0; i < 6; i++) {
+    hit_lists[i] = c->pp_hits[i];
+    c->pp_hits[i] = nullptr;
+    any_hits = any_hits || hit_lists[i] != nullptr;
+  }
+  if (any_hits && in->shard_world > 1)
+    return fail(c, GCRE_ERR_ARG, "a hit list cannot be armed for one device of several: merging lists across devices is not supported");
   gcre_profile total{};
   auto add_prof = [&]() {
     total.null_kernel_ms += c->prof.null_kernel_ms;
@@ -3278,6 +3323,7 @@ int gcre_process_paths(gcre_ctx* c, const gcre_pp_input* in, gcre_result out[5])
     jp.tally = tallies[lvi];   // (every permutation window folds the same observed scores: harmless)
     jp.exceed = exceeds[lvi];
     jp.exceed_observed = c->win_k0 == 0;   // the observed scores once per call, the null values of every window
+    jp.hits = c->win_k0 == 0 ? hit_lists[lvi] : nullptr;   // (the same rule: a list appends)
     if (in->shard_world > 1) {   // one device of several: its slice of the joined paths, every kept row
       jp.sharded = true;
       jp.shard_begin = u->total * in->shard_rank / in->shard_world;

@@ -1,8 +1,8 @@
 // gcre_host_stats.hip -- the entry points of include/gcre_hip.h that use a context but not the join driver: generated
 // permutation masks, decorated p-values (gcre_decorated.hip), set scores (gcre_sets.hip) and carrier overlaps
-// (gcre_overlap.hip), and the per-gene tally (gcre_genes.hip) and the null exceedance counts (gcre_exceed.hip,
-// gcre_stepdown.hip) as objects.  What a join does with an armed tally or armed counts -- check_tally, fold_genes,
-// count_exceed -- is in gcre_host.hip.  Host code only.
+// (gcre_overlap.hip), and the per-gene tally (gcre_genes.hip), the null exceedance counts (gcre_exceed.hip,
+// gcre_stepdown.hip) and the hit lists (gcre_hits.hip) as objects.  What a join does with an armed tally, armed counts or
+// an armed list -- check_tally, fold_genes, count_exceed, collect_hits -- is in gcre_host.hip.  Host code only.
 #include "gcre_host.h"
 #include "gcre_setlists.h"
 
@@ -68,6 +68,13 @@ int exceed_wait(gcre_ctx* c) {
 int exceed_alive(gcre_ctx* c, const gcre_exceed* x) {
   const auto& v = c->live_exceeds;
   return std::find(v.begin(), v.end(), x) != v.end() ? GCRE_OK : fail(c, GCRE_ERR_ARG, "exceedance counts do not belong to this context");
+}
+
+// h is one of the context's live lists, or the call is refused (a list of another context, or of a destroyed one whose
+// memory is gone: the pointer is looked up, never followed)
+int hits_alive(gcre_ctx* c, const gcre_hits* h) {
+  const auto& v = c->live_hits;
+  return std::find(v.begin(), v.end(), h) != v.end() ? GCRE_OK : fail(c, GCRE_ERR_ARG, "hit list does not belong to this context");
 }
 
 // 2^26 cells of 4 bytes: 256 MB
@@ -740,6 +747,134 @@ int gcre_exceed_stepdown(gcre_exceed* x, const gcre_set_input* in, int64_t* n_ge
 }
 
 int64_t gcre_stepdown_launches(const gcre_ctx* c) { return c ? c->stepdown_launches : -1; }
+
+// ---- hit lists ----
+gcre_hits* gcre_hits_create(gcre_ctx* c, double cutoff, int64_t cap) {
+  if (!c) return nullptr;
+  auto bad = [&](const std::string& msg) -> gcre_hits* {
+    fail(c, GCRE_ERR_ARG, "hit list: " + msg);
+    return nullptr;
+  };
+  if (cutoff != cutoff) return bad("the cut-off is NaN");
+  if (cap < 1 || cap > kHitsCapMax) return bad("cap must be 1.." + std::to_string(kHitsCapMax) + " (2^26), not " + std::to_string(cap));
+  (void)hipSetDevice(c->device);
+  gcre_hits* h = new gcre_hits();
+  h->ctx = c;
+  h->cutoff = cutoff;
+  h->cap = cap;
+  // the threshold key as gcre_exceed_create makes its own: a zero cut-off takes the key of -0.0, so that a score of either
+  // zero reaches it, and -inf the smallest key a score can have
+  double t = cutoff == 0 ? -0.0 : cutoff;
+  uint64_t b;
+  std::memcpy(&b, &t, 8);
+  const uint64_t k = (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+  h->tkey = t > -std::numeric_limits<double>::infinity() ? k : 1;
+  c->live_hits.push_back(h);
+  hipError_t e = hipMalloc((void**)&h->d_cursor, 8);
+  if (e == hipSuccess) e = hipMalloc(&h->d_rec, (size_t)cap * 32);
+  if (e == hipSuccess) e = hipMemsetAsync(h->d_cursor, 0, 8, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    gcre_hits_free(h);
+    fail(c, GCRE_ERR_DEVICE, std::string("hit list: ") + hipGetErrorString(e));
+    return nullptr;
+  }
+  return h;
+}
+
+int gcre_join_set_hits(gcre_ctx* c, gcre_hits* h) {
+  if (!c) return GCRE_ERR_ARG;
+  if (h && hits_alive(c, h) != GCRE_OK) return c->last_code;
+  c->armed_hits = h;
+  return GCRE_OK;
+}
+
+int gcre_process_paths_set_hits(gcre_ctx* c, int level, gcre_hits* h) {
+  if (!c) return GCRE_ERR_ARG;
+  if (level < 0 || level > 5) return fail(c, GCRE_ERR_ARG, "hit list: level index must be 0..5");
+  if (h && hits_alive(c, h) != GCRE_OK) return c->last_code;
+  c->pp_hits[level] = h;
+  return GCRE_OK;
+}
+
+int gcre_hits_count(gcre_hits* h, int64_t* found, int64_t* paths) {
+  if (!h || !h->ctx) return GCRE_ERR_ARG;
+  gcre_ctx* c = h->ctx;
+  if (int rc = exceed_wait(c)) return rc;
+  if (found) {
+    unsigned long long n = 0;
+    HIP_TRY(c, hipMemcpy(&n, h->d_cursor, 8, hipMemcpyDeviceToHost));
+    *found = (int64_t)n;
+  }
+  if (paths) *paths = h->paths;
+  return GCRE_OK;
+}
+
+int gcre_hits_read(gcre_hits* h, int64_t n, double* score, int64_t* ordinal, int32_t* src, int32_t* trg, int32_t* cases,
+                   int32_t* ctrls) {
+  if (!h || !h->ctx) return GCRE_ERR_ARG;
+  gcre_ctx* c = h->ctx;
+  int64_t found = 0;
+  if (int rc = gcre_hits_count(h, &found, nullptr)) return rc;
+  if (n != found)
+    return fail(c, GCRE_ERR_ARG, "hit list: n = " + std::to_string(n) + ", the list found " + std::to_string(found) + " (gcre_hits_count)");
+  if (found > h->cap)
+    return fail(c, GCRE_ERR_RANGE, "hit list: " + std::to_string(found) + " joined paths reach the cut-off, the list holds " +
+                                       std::to_string(h->cap) + ": reset it or make a larger one, and collect again");
+  const size_t m = (size_t)found;
+  if (m == 0) return GCRE_OK;
+  std::vector<int64_t> ord(m);
+  std::vector<uint64_t> key(m);
+  HIP_TRY(c, hipMemcpy(ord.data(), h->ord(), m * 8, hipMemcpyDeviceToHost));
+  HIP_TRY(c, hipMemcpy(key.data(), h->key(), m * 8, hipMemcpyDeviceToHost));
+  // best first: the key with the two zeros made one (they are equal as doubles) descending, then the ordinal ascending
+  auto tie = [](uint64_t k) { return k == kKeyMinusZero ? kKeyPlusZero : k; };
+  std::vector<uint32_t> perm(m);
+  for (size_t i = 0; i < m; i++) perm[i] = (uint32_t)i;
+  std::sort(perm.begin(), perm.end(), [&](uint32_t a, uint32_t b) {
+    const uint64_t ka = tie(key[a]), kb = tie(key[b]);
+    return ka != kb ? ka > kb : ord[a] < ord[b];
+  });
+  if (score)
+    for (size_t i = 0; i < m; i++) score[i] = key_to_score(key[perm[i]]);
+  if (ordinal)
+    for (size_t i = 0; i < m; i++) ordinal[i] = ord[perm[i]];
+  std::vector<int32_t> f(m);
+  int32_t* outs[4] = {src, trg, cases, ctrls};
+  for (int k = 0; k < 4; k++) {
+    if (!outs[k]) continue;
+    HIP_TRY(c, hipMemcpy(f.data(), h->field(k), m * 4, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < m; i++) outs[k][i] = f[perm[i]];
+  }
+  return GCRE_OK;
+}
+
+int gcre_hits_reset(gcre_hits* h) {
+  if (!h || !h->ctx) return GCRE_ERR_ARG;
+  gcre_ctx* c = h->ctx;
+  if (int rc = exceed_wait(c)) return rc;
+  HIP_TRY(c, hipMemset(h->d_cursor, 0, 8));
+  h->paths = 0;
+  return GCRE_OK;
+}
+
+int64_t gcre_hits_launches(const gcre_ctx* c) { return c ? c->hits_launches : -1; }
+
+void gcre_hits_free(gcre_hits* h) {
+  if (!h) return;
+  if (gcre_ctx* c = h->ctx) {
+    (void)exceed_wait(c);
+    if (c->armed_hits == h) c->armed_hits = nullptr;
+    for (auto& p : c->pp_hits)
+      if (p == h) p = nullptr;
+    auto& v = c->live_hits;
+    v.erase(std::remove(v.begin(), v.end(), h), v.end());
+  }
+  for (void* p : {(void*)h->d_cursor, h->d_rec})
+    if (p) (void)hipFree(p);
+  delete h;
+}
 
 void gcre_exceed_free(gcre_exceed* x) {
   if (!x) return;

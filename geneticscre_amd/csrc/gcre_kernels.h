@@ -471,6 +471,26 @@ struct ExceedObsArgs {
 };
 hipError_t launch_exceed_observed(const ExceedObsArgs& a, int cus, hipStream_t stream);
 
+// ---- hit lists (gcre_hits.hip) ----
+constexpr int64_t kHitsCapMax = (int64_t)1 << 26;   // records of one list: 2 GB of device memory at 32 B each
+// One scored stretch of a chunk, as its inspector left it (the fields of GeneFoldArgs), compacted into a join's hit list.
+struct HitsArgs {
+  const uint64_t* key;          // [count] score keys (0 = not a score: never a hit)
+  const uint32_t* row0;         // [count] paths0 row = uid row (Score.src)
+  const uint32_t* row1;         // [count] paths1 row (Score.trg), bit 31 = the signed method's half swap
+  const uint32_t* cases;        // [count]
+  const uint32_t* ctrls;        // [count]
+  int64_t count;
+  int64_t first;                // joined-path ordinal of element 0
+  uint64_t tkey;                // a path is a hit iff key != 0 && key >= tkey
+  unsigned long long* cursor;   // hits found so far: grows by every hit, also past `cap`
+  int64_t cap;                  // records the arrays below hold; a hit whose slot is >= cap is counted and not written
+  int64_t* ord;                 // [cap] joined-path ordinal
+  uint64_t* hkey;               // [cap] the path's own key
+  int32_t *src, *trg, *hcases, *hctrls;   // [cap] each
+};
+hipError_t launch_hits_collect(const HitsArgs& a, int cus, hipStream_t stream);
+
 // ---- step-down max-T counts of a level's top rows (gcre_stepdown.hip) ----
 // k_set_null's launch geometry (set_null_tile_sets sets per tile, kSetPermTile permutations per block) over the top rows.
 struct StepdownArgs {

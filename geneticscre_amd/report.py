@@ -489,6 +489,82 @@ def gene_summary(df):
 
 
 # ---------------------------------------------------------------------------------------------------------------
+# hit lists: every joined path at or above a score
+
+def hits_reference(all_scores, all_cases, all_ctrls, uids, cutoff: float,
+                   shard: Optional[Tuple[int, int]] = None) -> Dict[str, object]:
+    """The definition of a hit list in plain numpy -- what gcre_hits must return, bit for bit.
+
+    ``all_scores`` / ``all_cases`` / ``all_ctrls``: one entry per joined path in ordinal order, as ``gene_best_reference``
+    takes them (ordinal p = path_idx[i] + j for uid row i, j < count[i]; src = i, trg = location[i] + j).  A path is a
+    hit when its score is >= ``cutoff`` as doubles (so a cut-off of either zero admits both zeros) and above -inf (NaN
+    compares false: not a score); only ordinals inside ``shard`` when given.  Returns "found" and the six arrays "score",
+    "ordinal", "src", "trg", "cases", "ctrls", best first: score descending (the two zeros tie), then ordinal ascending."""
+    count = np.maximum(np.asarray(uids.count, dtype=np.int64), 0)
+    P = int(count.sum())
+    src = np.repeat(np.arange(len(count), dtype=np.int64), count)
+    first = np.cumsum(count) - count
+    trg = np.repeat(np.asarray(uids.location, dtype=np.int64), count) + (np.arange(P, dtype=np.int64) - np.repeat(first, count))
+    score = np.asarray(all_scores, dtype=np.float64)
+    assert len(score) == P
+    if np.isnan(cutoff):
+        raise ValueError("hits_reference: the cut-off is NaN")
+    with np.errstate(invalid="ignore"):
+        ok = (score >= float(cutoff)) & (score > -np.inf)
+    if shard is not None:
+        ords = np.arange(P)
+        ok &= (ords >= shard[0]) & (ords < shard[1])
+    p = np.flatnonzero(ok)
+    p = p[np.lexsort((p, -score[p]))]
+    return {"found": int(len(p)), "score": score[p], "ordinal": p.astype(np.int64), "src": src[p].astype(np.int32),
+            "trg": trg[p].astype(np.int32), "cases": np.asarray(all_cases)[p].astype(np.int32),
+            "ctrls": np.asarray(all_ctrls)[p].astype(np.int32)}
+
+
+def significance_cutoff(null_max, alpha: float) -> float:
+    """The smallest double c such that a score is >= c exactly when its ``Pvalues`` entry -- #(null_max >= score) /
+    len(null_max), the f64 score against the f32 maxima (``JoinResult.pvalues``) -- would be <= ``alpha``.
+
+    With K maxima, m = the largest n in 0..K with n / K <= alpha (the very division ``pvalues`` makes, not
+    floor(alpha * K): 0.29 * 100 is 28.999...) and nm the maxima as doubles in descending order, a score has at most m
+    maxima at or above it exactly when it lies above nm[m]: the cut-off is nextafter(nm[m], +inf), and -inf when m == K
+    (every score passes).  Null maxima are finite (table values), so the cut-off is."""
+    nm = np.sort(np.asarray(null_max, dtype=np.float32).astype(np.float64).ravel())[::-1]
+    K = len(nm)
+    if K == 0:
+        raise ValueError("significance_cutoff: no null maxima (0 permutations): there are no p-values to cut at")
+    if np.isnan(alpha):
+        raise ValueError("significance_cutoff: alpha is NaN")
+    n = np.arange(K + 1, dtype=np.int64)
+    ok = np.flatnonzero(n / K <= alpha)
+    if len(ok) == 0:           # alpha < 0: no p-value is that small
+        return float("inf")
+    m = int(ok[-1])
+    return float(np.nextafter(nm[m], np.inf)) if m < K else float("-inf")
+
+
+def hit_gene_counts(hits, genes0, genes1, n_slots: int) -> np.ndarray:
+    """How many hits run through each gene slot: int64 [n_slots].  ``hits``: anything with src / trg per hit (api.Hits, or
+    ``hits_reference``'s dict); ``genes0`` / ``genes1``: the level's tables from ``gene_tables`` (None = none): a hit
+    (src, trg) touches genes0[src] | genes1[trg].  A slot a path lists twice counts once."""
+    get = (lambda k: np.asarray(hits[k])) if isinstance(hits, dict) else (lambda k: np.asarray(getattr(hits, k)))
+    cols = []
+    for table, rows in ((genes0, get("src")), (genes1, get("trg"))):
+        if table is not None:
+            t = np.asarray(table, dtype=np.int64)
+            cols.append(t[rows.astype(np.int64)].reshape(len(rows), t.shape[1]))
+    out = np.zeros(int(n_slots), np.int64)
+    if not cols or len(cols[0]) == 0:
+        return out
+    s = np.sort(np.concatenate(cols, axis=1), axis=1)
+    s[:, 1:][s[:, 1:] == s[:, :-1]] = -1          # the second listing of a slot on one path
+    s = s[s >= 0]
+    if s.size and s.max() >= int(n_slots):
+        raise ValueError(f"hit_gene_counts: slot {int(s.max())} lies outside the {int(n_slots)} slots given")
+    return np.bincount(s, minlength=int(n_slots)).astype(np.int64)
+
+
+# ---------------------------------------------------------------------------------------------------------------
 # null exceedance counts, permutation FDR (DESIGN.md §3.8)
 
 FDR_COLUMNS = ["ExpectedFalse", "FDR", "Qvalues"]
@@ -1123,7 +1199,8 @@ def gwaspa(genes: Sequence[str], data: np.ndarray, n_cases: int, n_ctrls: int, n
            decorated_pvalues: bool = False, gene_table: bool = False, fdr: bool = False,
            clump: Optional[float] = None, clump_conditional: bool = False, false_counts: bool = False,
            false_count_ks: Sequence[int] = (2, 5, 10), false_count_alpha: float = 0.05,
-           stepdown: bool = False) -> Dict[str, object]:
+           stepdown: bool = False, significant: Optional[float] = None,
+           significant_cap: int = 1_000_000) -> Dict[str, object]:
     """GWASPA (R/ProcessPaths.R:87-344) without R: dataset -> GWASPA.Results, scored on the MI355X.
 
     ``network`` = (ents_uid, ents_symbol, rel_src, rel_trg, rel_sign): the knowledge base getStringKB() would load
@@ -1170,6 +1247,16 @@ def gwaspa(genes: Sequence[str], data: np.ndarray, n_cases: int, n_ctrls: int, n
     carried by the same patients as a better row -- and with ``clump_conditional`` ``RESIDUAL_COLUMNS``, each row rescored
     without its lead's carriers (``ResidualPvalues`` is a nominal per-set p-value, not a family-wise one).  The row order
     and the other columns are unchanged.  None, the default: nothing new is called.
+
+    ``significant``: with a level alpha in (0, 1), after the usual pass each length's cut-off is taken from its own null
+    maxima (``significance_cutoff``) and every level is joined once more with an ``api.HitList`` of ``significant_cap``
+    records armed -- the same second pass that carries the counters of ``fdr`` / ``false_counts`` /
+    ``stepdown`` when they are set: one extra pass in all.  "Significant.Results" has ``COLUMNS`` and holds EVERY path with
+    ``Pvalues <= significant``, not only those among the ``top_k`` best of their length (built by ``results_table`` from the
+    lists: same naming, same order); "significant" is length -> api.Hits, "significant_cutoffs" length -> float.  A length
+    whose list overflowed contributes no rows and a warning naming how many were found.  Outside (0, 1), or with
+    ``n_permutations == 0``, ValueError before anything runs.  GWASPA.Results and everything else are what
+    ``significant=None`` returns.  None, the default: nothing new is called.
     """
     from . import api
     from .synth import Problem
@@ -1177,6 +1264,13 @@ def gwaspa(genes: Sequence[str], data: np.ndarray, n_cases: int, n_ctrls: int, n
 
     method = "method2" if signed else "method1"
     check_input(n_cases, n_ctrls, method, threshold, top_k, path_length, n_permutations)
+    if significant is not None:
+        if not 0.0 < float(significant) < 1.0:      # (NaN fails both comparisons)
+            raise ValueError(f"significant: the family-wise level must lie inside (0, 1), not {significant!r}")
+        if int(n_permutations) == 0:
+            raise ValueError("significant: there are no p-values to cut at without permutations (n_permutations == 0)")
+        if not 1 <= int(significant_cap) <= api.HITS_CAP_MAX:
+            raise ValueError(f"significant_cap must be 1..{api.HITS_CAP_MAX} (2^26), not {significant_cap!r}")
     if (false_counts or stepdown) and int(top_k) * int(n_permutations) > EXCEED_PERM_CELLS:
         raise ValueError(f"{'false_counts' if false_counts else 'stepdown'}: top_k x n_permutations = {int(top_k) * int(n_permutations)} exceeds the limit of "
                          f"2^26 = {EXCEED_PERM_CELLS} per-permutation cells of a level")
@@ -1211,6 +1305,12 @@ def gwaspa(genes: Sequence[str], data: np.ndarray, n_cases: int, n_ctrls: int, n
     out = {"GWASPA.Results": results_table(lsts, path_length, frames,
                                            (prep.ents_uid, prep.ents_symbol), (prep.ents2_uid, prep.ents2_symbol)),
            "levels": lsts, "prepared": prep}
+    hit_lists, cutoffs = {}, {}
+    if significant is not None:
+        for L, name in enumerate(GENE_LEVELS[:path_length], start=1):
+            cutoffs[L] = significance_cutoff(lsts[f"lst{L}"].null, float(significant))
+            hit_lists[name] = api.HitList(ex, cutoffs[L], cap=int(significant_cap))
+    hits_collected = False
     if fdr or false_counts or stepdown:
         keep = bool(false_counts or stepdown) and n_permutations > 0
         fc_names = false_count_names(false_count_ks) if false_counts else []
@@ -1222,7 +1322,8 @@ def gwaspa(genes: Sequence[str], data: np.ndarray, n_cases: int, n_ctrls: int, n
                 counters[name] = api.ExceedCounts(ex, s[np.isfinite(s)], perm_counts=True) if keep else \
                     api.ExceedCounts(ex, s[np.isfinite(s)])
         if counters:
-            api.process_paths(problem, device=device, exec_=ex, exceeds=counters)
+            api.process_paths(problem, device=device, exec_=ex, exceeds=counters, hits=hit_lists or None)
+            hits_collected = True
         df = out["GWASPA.Results"]
         lookup, counted = {}, {}
         if fdr or false_counts:
@@ -1277,6 +1378,22 @@ def gwaspa(genes: Sequence[str], data: np.ndarray, n_cases: int, n_ctrls: int, n
         rows = [lookup.get((int(L), float(sc)), (np.nan,) * len(new_cols)) for L, sc in zip(df["Lengths"], df["Scores"])]
         for k, c in enumerate(new_cols):
             df[c] = np.array([r[k] for r in rows], np.float64)
+    if hit_lists:
+        import warnings
+        if not hits_collected:
+            api.process_paths(problem, device=device, exec_=ex, hits=hit_lists)
+        found, as_levels = {}, {}
+        for L, name in enumerate(GENE_LEVELS[:path_length], start=1):
+            h = found[L] = hit_lists[name].read()
+            hit_lists[name].free()
+            if not h.complete:
+                warnings.warn(f"significant: length {L}: {h.found} paths reach the cut-off, more than significant_cap = "
+                              f"{int(significant_cap)}: the length contributes no rows to Significant.Results")
+            as_levels[f"lst{L}"] = h.as_join_result(lsts[f"lst{L}"].null)
+        out["Significant.Results"] = results_table(as_levels, path_length, frames, (prep.ents_uid, prep.ents_symbol),
+                                                   (prep.ents2_uid, prep.ents2_symbol))
+        out["significant"] = found
+        out["significant_cutoffs"] = cutoffs
     if gene_table:
         best = {L + 1: tallies[name].read() for L, name in enumerate(GENE_LEVELS[:path_length])}
         out["gene_best"] = best

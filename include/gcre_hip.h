@@ -567,6 +567,49 @@ int gcre_exceed_stepdown(gcre_exceed* x, const gcre_set_input* in, int64_t* n_ge
 /* k_stepdown_null / k_stepdown_finish launches of the context since gcre_create (tests: a refusal launches nothing). */
 int64_t gcre_stepdown_launches(const gcre_ctx* ctx);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Hit lists: every joined path of a join whose observed score reaches a cut-off -- the rows a top-K list
+ * would hold if K were unbounded and the list ended at the cut-off.  No reference counterpart: the reference reports the
+ * top_k <= 10,000 best rows of a level and nothing below them.  With the cut-off report.significance_cutoff takes from a
+ * level's null maxima the list is "everything significant at family-wise level alpha", however long.
+ *
+ *   hits   {p scored by the join : observed score of p >= cutoff}, compared as doubles, scores above -inf only
+ * (a cut-off of either zero admits scores of both zeros; -inf admits every score; NaN and -inf scores are never hits).
+ * "scored by the join" is the shard of a sharded join, every joined path otherwise.  A record is the path's ordinal
+ * (path_idx[i] + j for uid row i), its score, src / trg as in a top-k list (Score.src / .trg: the uid row i and
+ * location[i] + j), cases and controls.  The list ADDS: shards of one join append into one list, and -- like the
+ * exceedance counts, unlike the gene tally -- it is NOT idempotent: a join collected twice is listed twice
+ * (gcre_hits_reset starts over), so it records how many joined paths were looked at.  A list needs no permutations
+ * (0 iterations work) and may be armed together with a tally and an exceed object.  The list and the count are identical
+ * whatever the chunking, the inspection cache, the launch-ahead chain, the permutation window or the form of the join's
+ * null kernel, and the join's result does not change; a join without a list launches exactly what it launched before.
+ * Overflow: `found` counts every hit, also those beyond `cap`; a list that overflowed cannot be read (which records it
+ * kept is not defined) -- reset it, or make a larger one, and collect again. */
+typedef struct gcre_hits gcre_hits;
+
+/* cutoff: any double but NaN (+-inf are allowed).  cap: records the list can hold, 1 .. 2^26; 32 x cap bytes of device
+ * memory are allocated here.  NULL on error (GCRE_ERR_ARG with a message: a NaN cut-off, cap out of range; GCRE_ERR_DEVICE:
+ * no memory). */
+gcre_hits* gcre_hits_create(gcre_ctx* ctx, double cutoff, int64_t cap);
+/* The next gcre_join / gcre_join_uids call on the context appends to `h`, then the context is disarmed (whether the join
+ * succeeds or not).  NULL disarms. */
+int gcre_join_set_hits(gcre_ctx* ctx, gcre_hits* h);
+/* The same for the next gcre_process_paths call, level 0..5 as for the tally.  The call collects the level once, not once
+ * per permutation window.  One device of several (shard_world > 1) refuses an armed list with GCRE_ERR_ARG. */
+int gcre_process_paths_set_hits(gcre_ctx* ctx, int level, gcre_hits* h);
+/* Waits for what is in flight.  found: joined paths at or above the cut-off (may exceed cap); paths: joined paths looked
+ * at.  Either may be NULL. */
+int gcre_hits_count(gcre_hits* h, int64_t* found, int64_t* paths);
+/* Waits for what is in flight.  n must equal `found` (GCRE_ERR_ARG otherwise); GCRE_ERR_RANGE when found > cap.  On error
+ * the outputs are untouched.  Records come best first: score descending as doubles (+-0 tie), then ordinal ascending --
+ * the tie rule of the top-k lists.  Any output may be NULL. */
+int gcre_hits_read(gcre_hits* h, int64_t n, double* score, int64_t* ordinal, int32_t* src, int32_t* trg,
+                   int32_t* cases, int32_t* ctrls);
+int gcre_hits_reset(gcre_hits* h);   /* an empty list again: found = paths = 0 */
+void gcre_hits_free(gcre_hits* h);   /* gcre_destroy frees the ones still alive */
+/* k_hits_collect launches of the context since gcre_create (tests: a refusal launches nothing). */
+int64_t gcre_hits_launches(const gcre_ctx* ctx);
+
 #ifdef __cplusplus
 }
 #endif
