@@ -757,6 +757,7 @@ hipError_t launch_exceed_observed(const ExceedObsArgs& a, int cus, hipStream_t s
   if (a.lds_bins > kExceedLdsBinsIe || (a.lds_bins != 0 && a.lds_bins != a.m)) return hipErrorInvalidValue;
   const i64 want = (a.count + kObsBlock - 1) / kObsBlock;
   const int grid = (int)(want < (i64)cus * kObsBlocksPerCu ? want : (i64)cus * kObsBlocksPerCu);
+  trace_launch("k_exceed_observed", want, grid);
   hipLaunchKernelGGL(k_exceed_observed, dim3(grid), dim3(kObsBlock), (size_t)a.lds_bins * 4, stream, a);
   return hipGetLastError();
 }

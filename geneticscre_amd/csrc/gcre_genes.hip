@@ -153,6 +153,7 @@ hipError_t launch_gene_fold(const GeneFoldArgs& a, int cus, hipStream_t stream) 
   if (a.count <= 0 || a.n_slots <= 0) return hipSuccess;
   const i64 want = (a.count + kGeneBlock - 1) / kGeneBlock;
   const int grid = (int)(want < (i64)cus * kGeneBlocksPerCu ? want : (i64)cus * kGeneBlocksPerCu);
+  trace_launch("k_gene_fold", want, grid);
   if (a.prior) hipLaunchKernelGGL(k_gene_fold<true>, dim3(grid), dim3(kGeneBlock), 0, stream, a);
   else hipLaunchKernelGGL(k_gene_fold<false>, dim3(grid), dim3(kGeneBlock), 0, stream, a);
   hipLaunchKernelGGL(k_gene_index, dim3(grid), dim3(kGeneBlock), 0, stream, a);

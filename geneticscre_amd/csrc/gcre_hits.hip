@@ -60,6 +60,7 @@ hipError_t launch_hits_collect(const HitsArgs& a, int cus, hipStream_t stream) {
   if (a.cap < 1 || !a.cursor) return hipErrorInvalidValue;
   const i64 want = (a.count + kHitsBlock - 1) / kHitsBlock;
   const int grid = (int)(want < (i64)cus * kHitsBlocksPerCu ? want : (i64)cus * kHitsBlocksPerCu);
+  trace_launch("k_hits_collect", want, grid);
   hipLaunchKernelGGL(k_hits_collect, dim3(grid), dim3(kHitsBlock), 0, stream, a);
   return hipGetLastError();
 }

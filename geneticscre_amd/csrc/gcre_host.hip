@@ -2604,6 +2604,7 @@ gcre_ctx* gcre_create(int method, int n_cases, int n_ctrls, int iterations, int 
   c->win_k0 = 0;
   c->win_K = g.K;
   if (const char* e = std::getenv("GCRE_QUIET")) c->quiet = std::atoi(e) != 0;
+  g_launch_trace = std::getenv("GCRE_LAUNCH_TRACE") != nullptr;   // (tests: which launches went past their grid caps)
   if (const char* e = std::getenv("GCRE_CHUNK_PATHS")) c->chunk_paths = std::max<long long>(64, std::atoll(e));
   if (const char* e = std::getenv("GCRE_NULL_BLOCKS_PER_CU")) c->null_blocks_per_cu = std::max(1, std::atoi(e));
   if (const char* e = std::getenv("GCRE_NULL_KERNEL"))

@@ -252,6 +252,7 @@ hipError_t launch_range_union(const uint64_t* p1, const uint64_t* pz, const int3
                               uint32_t* bad, hipStream_t stream) {
   if (npairs == 0) return hipSuccess;
   const i64 blocks = (npairs + 3) / 4;
+  trace_launch("k_range_union", blocks, blocks < 16384 ? blocks : 16384);
   hipLaunchKernelGGL(k_range_union, dim3((unsigned)(blocks < 16384 ? blocks : 16384)), dim3(256), 0, stream, p1, pz, zindex,
                      pair_range, pair_loc, npairs, S, Wp, method, excess, bad);
   return hipGetLastError();
@@ -974,11 +975,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NL <= 3 ? k
 
 // a block-staged inspector: kernel[NL - 1], NL = ceil(Wp / 32) <= 5, a wave per `per_wave` consecutive paths
 using StatsKernel = void (*)(StatsArgs);
-static hipError_t launch_staged(const StatsKernel (&kernel)[5], i64 per_wave, const StatsArgs& a, hipStream_t stream) {
+static hipError_t launch_staged(const StatsKernel (&kernel)[5], const char* name, i64 per_wave, const StatsArgs& a,
+                                hipStream_t stream) {
   const i64 nb = (a.count + per_wave - 1) / per_wave;
   const i64 blocks = (nb + kInspectBlockWaves - 1) / kInspectBlockWaves;
   const dim3 grid((unsigned)(blocks < kInspectMaxBlocks ? blocks : kInspectMaxBlocks)), block(64 * kInspectBlockWaves);
   const int nl = (a.Wp + 31) / 32;
+  trace_launch(name, blocks, grid.x);
   hipLaunchKernelGGL(kernel[nl <= 1 ? 0 : nl - 1], grid, block, 0, stream, a);
   return hipGetLastError();
 }
@@ -989,13 +992,14 @@ hipError_t launch_stats_ie(const StatsArgs& a, int method, hipStream_t stream) {
   static const StatsKernel ie2h[5] = {k_stats_ie2h<1>, k_stats_ie2h<2>, k_stats_ie2h<3>, k_stats_ie2h<4>, k_stats_ie2h<5>};
   static const StatsKernel ie2s[5] = {k_stats_ie2s<1>, k_stats_ie2s<2>, k_stats_ie2s<3>, k_stats_ie2s<4>, k_stats_ie2s<5>};
   if (a.Wp <= 160) {
-    if (method == 1) return launch_staged(ie2, 64, a, stream);
+    if (method == 1) return launch_staged(ie2, "k_stats_ie2", 64, a, stream);
     // the signed method with one-sided reduced rows: one round per path (k_stats_ie2h); otherwise one per half
-    if (a.lz_off) return launch_staged(ie2h, 64, a, stream);
-    return launch_staged(ie2s, 32, a, stream);
+    if (a.lz_off) return launch_staged(ie2h, "k_stats_ie2h", 64, a, stream);
+    return launch_staged(ie2s, "k_stats_ie2s", 32, a, stream);
   }
   const i64 blocks = (a.count + kStatsIeBlockPaths - 1) / kStatsIeBlockPaths;
   const dim3 grid((unsigned)(blocks < kInspectMaxBlocks ? blocks : kInspectMaxBlocks)), block(64 * kInspectBlockWaves);
+  trace_launch("k_stats_ie<M>", blocks, grid.x);
   if (method == 1) hipLaunchKernelGGL(k_stats_ie<1>, grid, block, 0, stream, a);
   else hipLaunchKernelGGL(k_stats_ie<2>, grid, block, 0, stream, a);
   return hipGetLastError();

@@ -4,8 +4,16 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdio.h>
 
 namespace gcre {
+
+// GCRE_LAUNCH_TRACE (tests, read at gcre_create): every launcher that clamps its grid names on stderr the blocks (or rounds)
+// the input asks for and the ones it launches, so that a test can tell that it drove a kernel past its cap
+extern bool g_launch_trace __attribute__((visibility("hidden")));
+inline void trace_launch(const char* kernel, long long want, long long got) {
+  if (g_launch_trace) fprintf(stderr, "launch %s want=%lld got=%lld\n", kernel, want, got);
+}
 
 // Device layout (DESIGN.md "Data layout in HBM"):
 //   path rows : uint64 [rows][S], S = M * Wp, Wp = ceil(n/64) rounded up to 4 words (32-byte chunks);

@@ -19,6 +19,7 @@
 namespace gcre {
 
 static inline int64_t hmin(int64_t a, int64_t b) { return a < b ? a : b; }
+bool g_launch_trace = false;
 
 typedef uint32_t u32;
 typedef uint64_t u64;
@@ -333,6 +334,7 @@ __global__ void k_select(const u64* from, const int32_t* idx, i64 n, int S, u64*
 hipError_t launch_select(const uint64_t* from, const int32_t* idx, int64_t n, int S, uint64_t* out, hipStream_t stream) {
   if (n == 0) return hipSuccess;
   const int grid = (int)hmin((n * S + 255) / 256, 16384);
+  trace_launch("k_select", (n * S + 255) / 256, grid);
   hipLaunchKernelGGL(k_select, dim3(grid), dim3(256), 0, stream, from, idx, n, S, out);
   return hipGetLastError();
 }
@@ -442,6 +444,7 @@ hipError_t launch_expand(const int64_t* path_idx, const int64_t* location, int64
                          hipStream_t stream) {
   if (count == 0) return hipSuccess;
   const int grid = (int)hmin((count + 255) / 256, 16384);
+  trace_launch("k_expand", (count + 255) / 256, grid);
   hipLaunchKernelGGL(k_expand, dim3(grid), dim3(256), 0, stream, path_idx, location, n_uids, signs, path_length, method,
                      first, count, row0, row1);
   return hipGetLastError();
@@ -607,6 +610,7 @@ __global__ __launch_bounds__(256) void k_stats(const StatsArgs a) {
 hipError_t launch_stats(const StatsArgs& a, int method, hipStream_t stream) {
   if (a.count == 0) return hipSuccess;
   const int grid = (int)hmin((a.count + 3) / 4, 256 * 16);
+  trace_launch("k_stats", (a.count + 3) / 4, grid);
   if (method == 1) hipLaunchKernelGGL(k_stats<1>, dim3(grid), dim3(256), 0, stream, a);
   else hipLaunchKernelGGL(k_stats<2>, dim3(grid), dim3(256), 0, stream, a);
   return hipGetLastError();
@@ -632,6 +636,7 @@ __global__ __launch_bounds__(256) void k_hist(const u64* key, i64 count, int shi
 hipError_t launch_hist(const uint64_t* key, int64_t count, int shift, uint64_t prefix, uint32_t* hist256,
                        hipStream_t stream) {
   const int grid = (int)hmin((count + 2047) / 2048, 2048);
+  trace_launch("k_hist", (count + 2047) / 2048, grid);
   hipLaunchKernelGGL(k_hist, dim3(grid > 0 ? grid : 1), dim3(256), 0, stream, key, count, shift, prefix, hist256);
   return hipGetLastError();
 }
@@ -679,6 +684,7 @@ __global__ __launch_bounds__(256) void k_select_step(SelectState* st, u32* hist2
 hipError_t launch_radix_select(const uint64_t* key, int64_t count, int64_t need, uint32_t* hist256, SelectState* st,
                                hipStream_t stream) {
   const int grid = (int)hmin((count + 2047) / 2048, 2048);
+  trace_launch("k_hist_st", (count + 2047) / 2048, grid);
   hipLaunchKernelGGL(k_select_init, dim3(1), dim3(256), 0, stream, st, need, hist256);
   for (int shift = 56; shift >= 0; shift -= 8) {
     hipLaunchKernelGGL(k_hist_st, dim3(grid > 0 ? grid : 1), dim3(256), 0, stream, key, count, shift, st, hist256);
@@ -699,6 +705,7 @@ __global__ __launch_bounds__(256) void k_collect_gt(const u64* key, i64 count, u
 hipError_t launch_collect_gt(const uint64_t* key, int64_t count, uint64_t thr, uint32_t* out, uint32_t* n_out,
                              uint32_t cap, hipStream_t stream) {
   const int grid = (int)hmin((count + 2047) / 2048, 2048);
+  trace_launch("k_collect_gt", (count + 2047) / 2048, grid);
   hipLaunchKernelGGL(k_collect_gt, dim3(grid > 0 ? grid : 1), dim3(256), 0, stream, key, count, thr, out, n_out, cap);
   return hipGetLastError();
 }

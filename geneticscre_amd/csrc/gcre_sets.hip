@@ -241,6 +241,9 @@ hipError_t launch_set_null(const SetNullArgs& a, int method, hipStream_t stream)
   if (a.nsets == 0 || a.K == 0) return hipSuccess;
   if ((int64_t)a.nkt * a.pgroups > 0x7fffffff || a.W32p % kSetWC != 0) return hipErrorInvalidValue;
   const dim3 grid((unsigned)(a.nkt * a.pgroups));
+  if (g_launch_trace)   // a block walks `per` set tiles
+    fprintf(stderr, "launch k_set_null npt=%lld pgroups=%d per=%lld\n", (long long)a.npt, a.pgroups,
+            (long long)((a.npt + a.pgroups - 1) / a.pgroups));
   if (method == 1) hipLaunchKernelGGL((k_set_null<1, 4, 4>), grid, dim3(kSetBlock), 0, stream, a);
   else hipLaunchKernelGGL((k_set_null<2, 2, 4>), grid, dim3(kSetBlock), 0, stream, a);
   return hipGetLastError();

@@ -281,6 +281,7 @@ hipError_t launch_delta_fill(const uint32_t* p0, int S32, int W32p, int method, 
                              const uint64_t* doff, uint32_t zoff, uint32_t* dlist, hipStream_t stream) {
   if (count == 0) return hipSuccess;
   const i64 blocks = (count * method + 3) / 4;
+  trace_launch("k_delta_fill", blocks, blocks < 16384 ? blocks : 16384);
   hipLaunchKernelGGL(k_delta_fill, dim3((unsigned)(blocks < 16384 ? blocks : 16384)), dim3(256), 0, stream, p0, S32,
                      W32p, method, row0, row1, count, loff1, lidx1, doff, zoff, dlist);
   return hipGetLastError();
@@ -362,6 +363,7 @@ __global__ __launch_bounds__(256) void k_scan_apply(const u32* cnt, i64 n, const
 hipError_t launch_scan_u32_u64(const uint32_t* cnt, int64_t n, uint64_t* off, uint64_t* scratch, hipStream_t stream) {
   if (n <= 0) return hipMemsetAsync(off, 0, 8, stream);
   const i64 nb = (n + 1023) / 1024;
+  trace_launch("k_scan_top", (nb + 1023) / 1024, 1);   // 1,024-wide rounds of its one block
   hipLaunchKernelGGL(k_scan_partial, dim3((unsigned)nb), dim3(256), 0, stream, cnt, n, scratch);
   hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(1024), 0, stream, scratch, nb);
   hipLaunchKernelGGL(k_scan_apply, dim3((unsigned)nb), dim3(256), 0, stream, cnt, n, scratch, off);
@@ -422,6 +424,7 @@ __global__ __launch_bounds__(256) void k_row_fill(const u32* rows, i64 nrows, in
 hipError_t launch_row_bits(const uint32_t* rows, int64_t nrows, int S32, int W32p, uint32_t* cnt, hipStream_t stream) {
   if (nrows == 0) return hipSuccess;
   const i64 blocks = (nrows + 3) / 4;
+  trace_launch("k_row_bits", blocks, blocks < 8192 ? blocks : 8192);
   hipLaunchKernelGGL(k_row_bits, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(256), 0, stream, rows, nrows, S32,
                      W32p, cnt);
   return hipGetLastError();
@@ -431,6 +434,7 @@ hipError_t launch_row_fill(const uint32_t* rows, int64_t nrows, int S32, int W32
                            uint32_t* idx, hipStream_t stream) {
   if (nrows == 0) return hipSuccess;
   const i64 blocks = (nrows + 3) / 4;
+  trace_launch("k_row_fill", blocks, blocks < 8192 ? blocks : 8192);
   hipLaunchKernelGGL(k_row_fill, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(256), 0, stream, rows, nrows, S32,
                      W32p, off, zoff, idx);
   return hipGetLastError();

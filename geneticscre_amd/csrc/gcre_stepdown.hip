@@ -284,6 +284,9 @@ hipError_t launch_stepdown_null(const StepdownArgs& a, int method, hipStream_t s
       (int64_t)a.nkt * kSdPT < a.K || a.nsets > a.m)
     return hipErrorInvalidValue;
   const dim3 grid((unsigned)(a.nkt * a.pgroups));
+  if (g_launch_trace)   // a block walks `per` set tiles
+    fprintf(stderr, "launch k_stepdown_null npt=%lld pgroups=%d per=%lld\n", (long long)a.npt, a.pgroups,
+            (long long)((a.npt + a.pgroups - 1) / a.pgroups));
   if (method == 1) hipLaunchKernelGGL((k_stepdown_null<1, 4, 4>), grid, dim3(kSdBlock), 0, stream, a);
   else hipLaunchKernelGGL((k_stepdown_null<2, 2, 4>), grid, dim3(kSdBlock), 0, stream, a);
   return hipGetLastError();

@@ -74,6 +74,69 @@ def restate(method, n_cases, n_ctrls, sets, rows, signs, VT, masks):
     return recs, nulls, family
 
 
+def restate_slabs(method, n_cases, n_ctrls, pos, neg, VT, masks, slab=512):
+    """``restate`` for many sets, each given by its union rows (``pos`` bool [V][n], and for method 2 ``neg``): the same
+    definition a slab of sets at a time.  Every cell the sets can read is looked up once through vt_cell / vt_max ([a][b] for
+    a, b <= n); a slab's null values are then one gather per cell.  Returns arrays over the sets (the record fields, "score",
+    "n_ge") and "family" (f32 [K])."""
+    n = n_cases + n_ctrls
+    pos = np.asarray(pos) != 0
+    neg = np.asarray(neg) != 0 if method == 2 else np.zeros_like(pos)
+    V, K = len(pos), len(masks)
+    mft = np.ascontiguousarray(np.asarray(masks, dtype=np.float32).reshape(K, n).T)
+    case = np.arange(n) < n_cases
+    a, b = np.meshgrid(np.arange(n + 1), np.arange(n + 1), indexing="ij")
+    cell = vt_cell(VT, n, a, b)
+    out = {"cases_pos": (pos & case).sum(axis=1), "ctrls_pos": (pos & ~case).sum(axis=1),
+           "cases_neg": (neg & ~case).sum(axis=1), "ctrls_neg": (neg & case).sum(axis=1)}
+    out["cases"], out["ctrls"] = out["cases_pos"] + out["cases_neg"], out["ctrls_pos"] + out["ctrls_neg"]
+    out["score"] = cell[out["cases_pos"], out["ctrls_pos"]]
+    if method == 2:
+        out["score"] = out["score"] + cell[out["cases_neg"], out["ctrls_neg"]]
+        big = vt_max(VT, n, a, b).ravel()
+    else:
+        folded = fold_f32(cell).ravel()
+    tp, tn = pos.sum(axis=1), neg.sum(axis=1)
+    out["n_ge"] = np.zeros(V, np.int64)
+    family = np.zeros(K, np.float32)
+    for lo in range(0, V, slab):
+        s = slice(lo, lo + slab)
+        pp = (pos[s].astype(np.float32) @ mft).astype(np.intp)          # exact: counts < 2^24
+        if method == 1:
+            null = folded[pp * n + tp[s, None]]                          # [pp][tot - pp] of an (n + 1)-wide table
+        else:
+            pn = (neg[s].astype(np.float32) @ mft).astype(np.intp)
+            null = fold_f32(big[pp * n + tp[s, None]] + big[(tn[s, None] - pn) * (n + 1) + pn])
+        out["n_ge"][s] = (null.astype(np.float64) >= out["score"][s, None]).sum(axis=1)
+        if null.size:
+            family = np.maximum(family, null.max(axis=0))
+    out["family"] = family
+    return out
+
+
+def test_slabs_equal_the_restatement():
+    """restate_slabs == restate on sets of one (+) and one (-) member, several slabs with a ragged last one."""
+    rng = np.random.default_rng(5)
+    nc, nt, K, V = 33, 37, 45, 53
+    n = nc + nt
+    VT = small_table(n, n, 2)
+    VT[rng.random(VT.shape) < 0.05] *= -1
+    masks = rng.random((K, n)) < 0.5
+    pos = rng.random((V, n)) < rng.uniform(0.0, 0.6, size=(V, 1))
+    neg = rng.random((V, n)) < rng.uniform(0.0, 0.6, size=(V, 1))
+    pos[0], neg[1] = False, True
+    for method in (1, 2):
+        recs, _, family = restate(method, nc, nt, [[i, V + i] for i in range(V)], np.vstack([pos, neg]), [[1, -1]] * V, VT, masks)
+        if method == 1:      # method 1 ignores the signs: both members join the one union
+            got = restate_slabs(1, nc, nt, pos | neg, None, VT, masks, slab=16)
+        else:
+            got = restate_slabs(2, nc, nt, pos, neg, VT, masks, slab=16)
+        for f in ("cases", "ctrls", "cases_pos", "ctrls_pos", "cases_neg", "ctrls_neg", "n_ge"):
+            assert got[f].tolist() == [r[f] for r in recs], (method, f)
+        assert got["score"].view(np.uint64).tolist() == [np.float64(r["score"]).view(np.uint64) for r in recs]
+        assert family.view(np.uint32).tolist() == got["family"].view(np.uint32).tolist()
+
+
 # ---- hand-worked examples -------------------------------------------------------------------------------------------
 # patients 0-2 are cases, 3-5 controls; VT[a][b] = 4a + b + 0.25 (so vtmax[a][b] = 4 max + min + 0.25)
 ROWS = np.array([[1, 0, 0, 1, 0, 0],     # g0

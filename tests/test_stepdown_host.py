@@ -100,7 +100,57 @@ def reference(j_, top):
                                      j_["masks"], top)
 
 
+def reference_sorted(method, n_cases, n_ctrls, uids, rows0, rows1, value_table, masks, top, slab=256):
+    """report.stepdown_reference's "n_ge", "single", "null_max" and "scores" for thousands of top rows.  The same null matrix
+    (report._join_null_blocks) and the same split into the top rows' own null rows and the running maximum of the rest; the
+    maximum over the rows that are not better than row j, which the reference takes in one pass per row, is read from ONE
+    running maximum over the rows in ascending score order, at the last row whose score is <= tau_j (rows of equal score
+    stay in one another's family)."""
+    src_t, trg_t = np.asarray(top[0], np.int64).ravel(), np.asarray(top[1], np.int64).ravel()
+    tau = np.asarray(top[2], np.float64).ravel()
+    m = len(tau)
+    keys = src_t << 32 | trg_t
+    assert len(set(keys.tolist())) == m and np.isfinite(tau).all()
+    order_k = np.argsort(keys)
+    K = report._n_masks(masks, int(n_cases) + int(n_ctrls))
+    rest = np.zeros(K, np.float32)
+    top_null, top_score, found = np.zeros((m, K), np.float32), np.full(m, np.nan), np.zeros(m, bool)
+    for _lo, s_, t_, sc_, null in report._join_null_blocks(method, n_cases, n_ctrls, uids, rows0, rows1, value_table, masks):
+        k = s_ << 32 | t_
+        at = np.minimum(np.searchsorted(keys[order_k], k), m - 1)
+        is_top = keys[order_k][at] == k
+        j = order_k[at[is_top]]
+        top_null[j], top_score[j], found[j] = null[is_top], sc_[is_top], True
+        if (~is_top).any() and K:
+            rest = np.maximum(rest, null[~is_top].max(axis=0))
+    assert found.all()
+    null_max = np.maximum(rest, top_null.max(axis=0)) if m and K else rest.copy()
+    up = np.argsort(tau, kind="stable")
+    run = np.maximum.accumulate(top_null[up], axis=0)                      # row k: the maximum over the k + 1 lowest rows
+    last = np.searchsorted(tau[up], tau, side="right") - 1                 # the last row that is not better than row j
+    n_ge = np.zeros(m, np.int64)
+    for lo in range(0, m, slab):
+        u = np.maximum(rest[None, :], run[last[lo:lo + slab]])
+        n_ge[lo:lo + slab] = (u.astype(np.float64) >= tau[lo:lo + slab, None]).sum(axis=1)
+    single = (null_max.astype(np.float64)[None, :] >= tau[:, None]).sum(axis=1).astype(np.int64)
+    return {"n_ge": n_ge, "single": single, "null_max": null_max, "scores": top_score, "perms": K}
+
+
 CASES = [(method, seed) for method in (1, 2) for seed in range(6)]
+
+
+@pytest.mark.parametrize("method,seed", CASES)
+def test_sorted_form_equals_the_reference(method, seed):
+    j_ = tiny_join(method, seed)
+    _, paths = brute_force(j_, (np.zeros(0, int), np.zeros(0, int), np.zeros(0)))
+    for m in (1, 12, 30):
+        top = top_of(paths, m)
+        top = tuple(a[np.random.default_rng(seed).permutation(m)] for a in top)
+        want = reference(j_, top)
+        got = reference_sorted(j_["method"], j_["nc"], j_["nt"], j_["uids"], j_["rows0"], j_["rows1"], j_["VT"], j_["masks"],
+                               top, slab=5)
+        for f in ("n_ge", "single", "null_max", "scores"):
+            np.testing.assert_array_equal(got[f], want[f], err_msg=f"{m} {f}")
 
 
 @pytest.mark.parametrize("method,seed", CASES)
