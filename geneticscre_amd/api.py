@@ -130,6 +130,7 @@ EXPORTS = [
     "gcre_rccl_selftest", "gcre_rccl_collectives", "gcre_join_ahead",
     "gcre_decorated_splits", "gcre_decorated_pvalues", "gcre_score_sets",
     "gcre_set_overlap", "gcre_overlap_launches",
+    "gcre_clump_sets", "gcre_clump_launches",
     "gcre_gene_tally_create", "gcre_join_set_tally", "gcre_process_paths_set_tally", "gcre_gene_tally_read",
     "gcre_gene_tally_free",
     "gcre_exceed_create", "gcre_join_set_exceed", "gcre_process_paths_set_exceed", "gcre_exceed_read",
@@ -252,6 +253,9 @@ _FEATURES = {
     "overlap": (None, ["gcre_set_overlap"], "carrier overlaps (gcre_set_overlap)", {
         "gcre_set_overlap": (_I, [_V, ctypes.POINTER(gcre_set_input), _P, _I64, _P, _I64, _P, _P]),
         "gcre_overlap_launches": (_I64, [_V])}),
+    "clump": ("overlap", ["gcre_clump_sets", "gcre_clump_launches"], "device-side clumping (gcre_clump_sets)", {
+        "gcre_clump_sets": (_I, [_V, ctypes.POINTER(gcre_set_input), _P, _I64, ctypes.c_double, _I, _I, _P, _P, _P, _P, _P]),
+        "gcre_clump_launches": (_I64, [_V])}),
     "genes": (None, ["gcre_gene_tally_create"], "per-gene best-path tally (gcre_gene_tally_create)", {
         "gcre_gene_tally_create": (_V, [_V, _I32, _P, _I64, _I32, _P, _I64, _I32]),
         "gcre_join_set_tally": (_I, [_V, _V]),
@@ -302,6 +306,7 @@ def _feature_lib(feature: str):
 _decorated_lib = functools.partial(_feature_lib, "decorated")
 _sets_lib = functools.partial(_feature_lib, "sets")
 _overlap_lib = functools.partial(_feature_lib, "overlap")
+_clump_lib = functools.partial(_feature_lib, "clump")
 _genes_lib = functools.partial(_feature_lib, "genes")
 _exceed_lib = functools.partial(_feature_lib, "exceed")
 _perm_counts_lib = functools.partial(_feature_lib, "perm_counts")
@@ -935,6 +940,56 @@ class JoinExec:
         if rc != GCRE_OK:
             raise GcreError(self._lib.gcre_last_error(self._h).decode())
         return size, both
+
+    def clump_sets(self, sets, rows, order, r: float = 0.5, measure: str = "jaccard", patients: str = "all"):
+        """Greedy clumping of caller-given sets by shared carriers, on the device (gcre_clump_sets):
+        ``report.clump_rows(order, size, both_of, r, measure, patients)`` with ``size`` / ``both`` as ``set_overlap``
+        defines them, bit for bit, without a pair count leaving the GPU.  ``sets``: one sequence of row indices of the
+        0/1 matrix ``rows`` per set, or a pair ``(off, members)`` -- int64 [S + 1] offsets into int32 members, what
+        ``report.hit_sets`` returns; ``order``: the sets to clump, best first, each at most once, none with an NA member
+        (-1).  Returns ``(clump, lead, value, shared, size)``: int64 [S] clump ids, int64 [S] the lead's set (a lead names
+        itself), float64 [S] the measure against the lead (NaN on leads), int64 [S][2] the carriers shared with it (-1 on
+        leads) -- all -1 / NaN for a set outside ``order`` -- and int32 [S][2] the sets' carriers.  Raises the
+        ValueErrors of ``clump_rows`` before the library is touched; the library's refusals raise GcreError."""
+        if not 0 < r <= 1:
+            raise ValueError("r must be > 0 and <= 1")
+        if measure not in ("jaccard", "containment"):
+            raise ValueError("measure must be 'jaccard' or 'containment'")
+        if patients not in ("all", "cases"):
+            raise ValueError("patients must be 'all' or 'cases'")
+        lib = _clump_lib()
+        n = self.num_cases + self.num_ctrls
+        if isinstance(sets, tuple) and len(sets) == 2 and isinstance(sets[0], np.ndarray):
+            off = np.ascontiguousarray(sets[0], dtype=np.int64)
+            members = np.ascontiguousarray(sets[1], dtype=np.int32)
+            S = len(off) - 1
+        else:
+            S = len(sets)
+            off = np.zeros(S + 1, dtype=np.int64)
+            off[1:] = np.cumsum([len(x) for x in sets])
+            members = np.ascontiguousarray(np.concatenate([np.asarray(x, dtype=np.int64).reshape(-1) for x in sets])
+                                           if S else np.zeros(0), dtype=np.int32)
+        d = np.asarray(rows)
+        if d.ndim != 2:
+            d = d.reshape(-1, n)
+        packed = pack_carriers(d, d.shape[1])
+        io = np.ascontiguousarray(np.asarray(order, dtype=np.int64).reshape(-1))
+        inp = gcre_set_input(S, _ptr(off), _ptr(members), None, _ptr(packed), packed.shape[0], d.shape[1])
+        size = np.zeros((S, 2), dtype=np.int32)
+        clump = np.zeros(S, dtype=np.int64)
+        lead = np.zeros(S, dtype=np.int64)
+        value = np.zeros(S, dtype=np.float64)
+        shared = np.zeros((S, 2), dtype=np.int32)
+        rc = lib.gcre_clump_sets(self._h, ctypes.byref(inp), _ptr(io), len(io), float(r), 0 if measure == "jaccard" else 1,
+                                 0 if patients == "all" else 1, _ptr(size), _ptr(clump), _ptr(lead), _ptr(value), _ptr(shared))
+        if rc != GCRE_OK:
+            raise GcreError(self._lib.gcre_last_error(self._h).decode())
+        return clump, lead, value, shared.astype(np.int64), size
+
+    @property
+    def clump_launches(self) -> int:
+        """Kernels gcre_clump_sets launched on this context so far."""
+        return int(_clump_lib().gcre_clump_launches(self._h))
 
     def stepdown_launches(self) -> int:
         """k_stepdown_null / k_stepdown_finish launches of this context so far."""

@@ -1,10 +1,11 @@
 // gcre_host_stats.hip -- the entry points of include/gcre_hip.h that use a context but not the join driver: generated
 // permutation masks, decorated p-values (gcre_decorated.hip), set scores (gcre_sets.hip) and carrier overlaps
-// (gcre_overlap.hip), and the per-gene tally (gcre_genes.hip), the null exceedance counts (gcre_exceed.hip,
+// (gcre_overlap.hip) and greedy clumps (gcre_clump.hip), and the per-gene tally (gcre_genes.hip), the null exceedance counts (gcre_exceed.hip,
 // gcre_stepdown.hip) and the hit lists (gcre_hits.hip) as objects.  What a join does with an armed tally, armed counts or
 // an armed list -- check_tally, fold_genes, count_exceed, collect_hits -- is in gcre_host.hip.  Host code only.
 #include "gcre_host.h"
 #include "gcre_setlists.h"
+#include "gcre_clumporder.h"
 
 namespace {
 
@@ -388,6 +389,142 @@ int gcre_set_overlap(gcre_ctx* c, const gcre_set_input* in, const int64_t* a, in
 }
 
 int64_t gcre_overlap_launches(const gcre_ctx* c) { return c ? c->overlap_launches : -1; }
+
+// Greedy clumping of caller-given sets on the device: report.clump_rows without a pair count leaving the
+// GPU.  The gene rows and a member table in walk order go up once; k_clump_union makes the union rows; rounds of
+// k_clump_leads + k_clump_assign are queued in batches, the 16-byte state of the walk is read once per batch.
+int gcre_clump_sets(gcre_ctx* c, const gcre_set_input* in, const int64_t* order, int64_t n_order, double r, int measure,
+                    int patients, int32_t* size, int64_t* clump, int64_t* lead, double* value, int32_t* shared) {
+  if (!c) return GCRE_ERR_ARG;
+  if (!in) return fail(c, GCRE_ERR_ARG, "clump_sets: NULL argument");
+  const Geometry& g = c->g;
+  std::string msg;
+  if (int rc = check_set_shape(in, g.n, "clump_sets", msg)) return fail(c, rc, msg);
+  if (int rc = check_set_members(in, "clump_sets", msg)) return fail(c, rc, msg);
+  const int64_t S = in->n_sets;
+  if (S > 0 && (!clump || !lead || !value || !shared)) return fail(c, GCRE_ERR_ARG, "clump_sets: NULL output");
+  if (int rc = check_clump_rule(r, measure, patients, msg)) return fail(c, rc, msg);
+  if (int rc = check_clump_order(in, order, n_order, msg)) return fail(c, rc, msg);
+  const int W = g.W;
+  const int Wdp = (2 * W + kOverlapChunk - 1) / kOverlapChunk * kOverlapChunk;
+  if (int rc = check_clump_bytes(n_order, (int64_t)Wdp * 4, clump_max_mb(), msg)) return fail(c, rc, msg);
+  if (n_order >= 0x7ffffff0) return fail(c, GCRE_ERR_ARG, "clump_sets: too many rows");
+
+  const double nan = std::numeric_limits<double>::quiet_NaN();
+  for (int64_t s = 0; s < S; s++) {
+    clump[s] = lead[s] = -1;
+    value[s] = nan;
+    shared[2 * s] = shared[2 * s + 1] = -1;
+  }
+  // the sizes of the sets outside the walk, as gcre_set_overlap fills them (those inside it come from the device)
+  std::vector<unsigned char> walked((size_t)S, 0);
+  for (int64_t i = 0; i < n_order; i++) walked[(size_t)order[i]] = 1;
+  if (size) {
+    const SetUnion un(W, g.n, g.n_cases);
+    std::vector<uint64_t> row((size_t)std::max(W, 1));
+    for (int64_t s = 0; s < S; s++) {
+      if (walked[(size_t)s]) continue;
+      if (!set_is_valid(in, s)) {
+        size[2 * s] = size[2 * s + 1] = -1;
+        continue;
+      }
+      std::fill(row.begin(), row.end(), 0);
+      int32_t k[4];
+      un.build(in, s, row.data(), 0, false, k);
+      std::memcpy(size + 2 * s, k, 8);
+    }
+  }
+  if (n_order == 0) return GCRE_OK;
+
+  // the member table [n_order][M] in walk order, -1 behind a set's last member
+  const int64_t n = n_order;
+  int64_t M = 1;
+  for (int64_t i = 0; i < n; i++) M = std::max(M, in->set_off[order[i] + 1] - in->set_off[order[i]]);
+  if (M > 0x7fffffff / 4 || (double)n * (double)M * 4.0 > clump_max_mb() * 1048576.0)
+    return fail(c, GCRE_ERR_ARG, "clump_sets: the member table of " + std::to_string(n) + " rows x " + std::to_string(M) +
+                                     " members exceeds GCRE_CLUMP_MAX_MB");
+  std::vector<int32_t> table((size_t)n * (size_t)M, -1);
+  for (int64_t i = 0; i < n; i++) {
+    const int64_t b = in->set_off[order[i]], e = in->set_off[order[i] + 1];
+    std::copy(in->members + b, in->members + e, table.begin() + (size_t)i * (size_t)M);
+  }
+
+  (void)hipSetDevice(c->device);
+  DevScratch d(c->stream);
+  ClumpArgs a{};
+  ClumpUnionArgs u{};
+  u.rows = (const uint32_t*)d.put(in->rows, std::max<size_t>((size_t)in->n_rows * (size_t)W, 1));
+  u.members = d.put(table.data(), table.size());
+  u.M = (int)M;
+  u.W2 = 2 * W;
+  u.n_patients = g.n;
+  a.U = d.take<uint32_t>((size_t)(n + 1) * (size_t)Wdp);
+  a.cnt = d.take<int32_t>((size_t)n * 2);
+  a.free_ = d.take<uint32_t>((size_t)n);
+  a.clump = d.take<int32_t>((size_t)n);
+  a.lead = d.take<int32_t>((size_t)n);
+  a.value = d.take<double>((size_t)n);
+  a.shared = d.take<int32_t>((size_t)n * 2);
+  a.state = d.take<ClumpState>(1);
+  a.leads = d.take<int32_t>(kClumpCand);
+  a.stats = d.take<unsigned long long>(kClumpStats);
+  a.n = n;
+  a.Wdp = Wdp;
+  a.n_cases = g.n_cases;
+  a.measure = measure;
+  a.patients = patients;
+  a.r = r;
+  if (d.ok()) d.zero(a.U + (size_t)n * (size_t)Wdp, (size_t)Wdp);   // the zero row
+  d.zero(a.state, 1);
+  d.zero(a.stats, kClumpStats);
+  if (d.ok()) d.e = launch_clump_union(a, u, c->stream);
+  if (d.ok()) c->clump_launches++;
+  // rounds in batches: every kernel of a round reads the state and ends at once on an empty round, so a batch may run
+  // past the end of the walk; tiles below the cursor the host saw last are not launched at all
+  constexpr int kBatch = 16;
+  ClumpState st{};
+  int64_t batches = 0;
+  while (d.ok() && st.cursor < n) {
+    const int64_t tile0 = st.cursor / kOverlapTile;
+    for (int k = 0; d.ok() && k < kBatch; k++) {
+      d.e = launch_clump_round(a, tile0, c->stream);
+      if (d.ok()) c->clump_launches += 2;
+    }
+    d.download(&st, a.state, 1);
+    d.sync();
+    batches++;
+  }
+  std::vector<int32_t> cnt((size_t)n * 2), h_clump((size_t)n), h_lead((size_t)n), h_shared((size_t)n * 2);
+  std::vector<double> h_value((size_t)n);
+  unsigned long long stats[kClumpStats] = {};
+  d.download(cnt.data(), a.cnt, cnt.size());
+  d.download(h_clump.data(), a.clump, h_clump.size());
+  d.download(h_lead.data(), a.lead, h_lead.size());
+  d.download(h_value.data(), a.value, h_value.size());
+  d.download(h_shared.data(), a.shared, h_shared.size());
+  d.download(stats, a.stats, (size_t)kClumpStats);
+  d.sync();
+  d.release();
+  if (!d.ok()) {
+    (void)hipGetLastError();
+    return fail(c, GCRE_ERR_DEVICE, std::string("clump_sets: ") + hipGetErrorString(d.e));
+  }
+  if (std::getenv("GCRE_CLUMP_STATS"))   // (tools/clump_time.py)
+    fprintf(stderr, "clump rows=%lld rounds=%llu leads=%d batches=%lld tiles_run=%llu tiles_skipped=%llu\n", (long long)n,
+            stats[kClumpRounds], st.next_clump, (long long)batches, stats[kClumpTilesRun], stats[kClumpTilesSkipped]);
+  for (int64_t i = 0; i < n; i++) {
+    const int64_t s = order[i];
+    if (size) std::memcpy(size + 2 * s, cnt.data() + 2 * i, 8);
+    clump[s] = h_clump[(size_t)i];
+    lead[s] = order[h_lead[(size_t)i]];
+    value[s] = h_value[(size_t)i];
+    shared[2 * s] = h_shared[2 * (size_t)i];
+    shared[2 * s + 1] = h_shared[2 * (size_t)i + 1];
+  }
+  return GCRE_OK;
+}
+
+int64_t gcre_clump_launches(const gcre_ctx* c) { return c ? c->clump_launches : -1; }
 
 // ---- per-gene best-path tally ----
 gcre_gene_tally* gcre_gene_tally_create(gcre_ctx* c, int32_t n_slots, const int32_t* genes0, int64_t n_rows0, int32_t w0,

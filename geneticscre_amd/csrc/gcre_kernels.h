@@ -543,4 +543,43 @@ struct OverlapArgs {
 };
 hipError_t launch_set_overlap(const OverlapArgs& a, hipStream_t stream);
 
+// ---- greedy carrier clumping on the device (gcre_clump.hip) ----
+// Everything is indexed by POSITION in the walk order.  A round takes the next <= kClumpCand unassigned positions as
+// candidate leads, resolves them among themselves (k_clump_leads) and lets the true leads absorb every later row
+// (k_clump_assign).  The state of a round lives on the device, so rounds are queued without the host looking.
+constexpr int kClumpCand = 64;      // candidate leads of a round = the `a` edge of k_clump_assign's tile
+struct ClumpState {                 // 16 bytes: what the host reads once per batch of rounds
+  int32_t cursor;                   // every position below it is assigned; >= n: the walk is over
+  int32_t ncand;                    // candidates of the last round (0: an empty round)
+  int32_t nlead;                    // ... and the true leads among them, compacted in `leads`
+  int32_t next_clump;               // clump ids handed out so far
+};
+enum ClumpStat { kClumpRounds = 0, kClumpTilesRun = 1, kClumpTilesSkipped = 2, kClumpStats = 4 };
+struct ClumpArgs {
+  uint32_t* U;                      // [n + 1][Wdp] union rows in k_set_overlap's layout; row n is all zeros
+  int32_t* cnt;                     // [n][2] carriers of every position: cases, controls
+  uint32_t* free_;                  // [n] 1 = not assigned yet
+  int32_t* clump;                   // [n] outputs per position: clump id,
+  int32_t* lead;                    // [n] the lead's POSITION (a lead names itself),
+  double* value;                    // [n] the measure against the lead (NaN on a lead),
+  int32_t* shared;                  // [n][2] carriers shared with the lead ((-1, -1) on a lead)
+  ClumpState* state;
+  int32_t* leads;                   // [kClumpCand] positions of the round's true leads, in walk order
+  unsigned long long* stats;        // [kClumpStats]
+  int64_t n;                        // positions
+  int Wdp;                          // dwords per union row, a multiple of kOverlapChunk
+  int n_cases;
+  int measure;                      // 0 jaccard, 1 containment
+  int patients;                     // 0 all, 1 cases
+  double r;
+};
+struct ClumpUnionArgs {
+  const uint32_t* rows;             // [n_rows][W2] the caller's gene rows as dwords
+  const int32_t* members;           // [n][M] rows of every position's set, -1 = no further member
+  int M, W2, n_patients;
+};
+hipError_t launch_clump_union(const ClumpArgs& a, const ClumpUnionArgs& u, hipStream_t stream);
+// one round: k_clump_leads, then k_clump_assign over the tiles from `tile0` on (positions below 64 * tile0 are assigned)
+hipError_t launch_clump_round(const ClumpArgs& a, int64_t tile0, hipStream_t stream);
+
 }  // namespace gcre

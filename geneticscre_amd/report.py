@@ -564,6 +564,59 @@ def hit_gene_counts(hits, genes0, genes1, n_slots: int) -> np.ndarray:
     return np.bincount(s, minlength=int(n_slots)).astype(np.int64)
 
 
+def hit_sets(found, tables, n_genes: int, n_genes2: int, nulls=None) -> Tuple[np.ndarray, np.ndarray]:
+    """The member lists of every hit of every length, as ``api.JoinExec.clump_sets`` takes sets: ``(off, members)``, set s
+    = members[off[s]:off[s + 1]], rows of ``vstack(data1, data2)``.  ``found``: length -> api.Hits (a list that overflowed
+    has no records and contributes no sets); ``tables``: ``gene_tables``.  A hit (src, trg) of a level has the members
+    genes0[src] | genes1[trg] with -1 dropped and a slot listed twice kept once, ascending; the slots of levels 2..5 are
+    ranks in Ents (``n_genes`` rows of data1), those of level 1 ranks in Ents2, offset by ``n_genes`` into the stacked
+    matrix.  The sets are in the row order in which ``results_table`` lays out the same lists (``Hits.as_join_result``):
+    p-value ascending, then score descending, stable over the lengths one after the other, each from its worst hit to its
+    best; ``nulls``: length -> the level's null maxima, which the p-values compare with as ``JoinResult.pvalues`` does
+    (None: no p-values, as with no permutations).  Whole-array numpy: no strings, no loop over hits."""
+    lengths = sorted(int(L) for L in found)
+    blocks, scores, pvals = [], [], []
+    for L in lengths:
+        h = found[L]
+        name = GENE_LEVELS[L - 1]
+        src = np.asarray(h.src, np.int64)[::-1]
+        trg = np.asarray(h.trg, np.int64)[::-1]
+        sc = np.asarray(h.score, np.float64)[::-1]
+        cols = []
+        for table, idx in zip(tables[name], (src, trg)):
+            if table is not None:
+                t = np.asarray(table, np.int64)
+                cols.append(t[idx].reshape(len(idx), t.shape[1]))
+        m = np.concatenate(cols, axis=1) if cols else np.zeros((len(sc), 0), np.int64)
+        slots = gene_slots(name, n_genes, n_genes2)
+        if m.size and m.max() >= slots:
+            raise ValueError(f"hit_sets: length {L}: slot {int(m.max())} lies outside the {slots} slots given")
+        if name == "1b":
+            m = np.where(m >= 0, m + int(n_genes), -1)
+        blocks.append(m)
+        scores.append(sc)
+        t = None if nulls is None else np.sort(np.asarray(nulls[L], np.float32).astype(np.float64))
+        pvals.append(np.full(len(sc), np.nan) if t is None or len(t) == 0 else
+                     (len(t) - np.searchsorted(t, sc, side="left")) / len(t))
+    n = sum(len(b) for b in blocks)
+    if n == 0:
+        return np.zeros(1, np.int64), np.zeros(0, np.int32)
+    w = max(b.shape[1] for b in blocks)
+    m = np.full((n, w), -1, np.int64)
+    at = 0
+    for b in blocks:
+        m[at:at + len(b), :b.shape[1]] = b
+        at += len(b)
+    sc, p = np.concatenate(scores), np.concatenate(pvals)
+    m = m[np.lexsort((-sc, np.where(np.isnan(p), np.inf, p)))]     # results_table's order
+    m = np.sort(m, axis=1)
+    m[:, 1:][m[:, 1:] == m[:, :-1]] = -1                            # the second listing of a slot on one path
+    keep = m >= 0
+    off = np.zeros(n + 1, np.int64)
+    off[1:] = np.cumsum(keep.sum(axis=1))
+    return off, np.ascontiguousarray(m[keep], dtype=np.int32)
+
+
 # ---------------------------------------------------------------------------------------------------------------
 # null exceedance counts, permutation FDR (DESIGN.md §3.8)
 
@@ -966,10 +1019,23 @@ def clump_rows(order, size, both_of, r: float, measure: str = "jaccard", patient
     return clump, lead, value, shared
 
 
+def _set_clump_columns(out, clump, lead, value, shared) -> None:
+    """``CLUMP_COLUMNS`` of a results table from the per-row arrays of ``clump_rows`` / ``clump_sets``."""
+    S = len(out)
+    is_member = (clump >= 0) & (lead != np.arange(S))
+    paths = [str(p) for p in out["Paths"]]
+    out["Clump"] = clump
+    out["ClumpLead"] = [paths[l] if l >= 0 else None for l in lead.tolist()]
+    out["ClumpSize"] = np.where(clump >= 0, np.bincount(clump[clump >= 0], minlength=1)[np.maximum(clump, 0)], 0)
+    out["LeadOverlap"] = np.where(is_member, value, np.nan)
+    out["SharedCases"] = np.where(is_member, shared[:, 0], np.nan)
+    out["SharedControls"] = np.where(is_member, shared[:, 1], np.nan)
+
+
 def clump_paths(results_df, genes: Sequence[str], data: np.ndarray, n_cases: int, n_ctrls: int, signed: bool = False,
                 r: float = 0.5, measure: str = "jaccard", patients: str = "all", by_length: bool = False,
                 conditional: bool = False, threshold: float = 0.05, n_permutations: int = 100,
-                strata: Optional[Sequence[int]] = None, seed: int = 0, device: int = 0):
+                strata: Optional[Sequence[int]] = None, seed: int = 0, device: int = 0, on_device: bool = False):
     """Which rows of a GWASPA.Results table are the same finding: rows clumped by the patients that carry them, and with
     ``conditional`` each row rescored without its lead's carriers.  A row's carriers are the patients
     with a variant in any gene of its ``SignedPaths`` (``carrier_rows``); the pairwise shared-carrier counts come from the
@@ -987,7 +1053,11 @@ def clump_paths(results_df, genes: Sequence[str], data: np.ndarray, n_cases: int
     n_cases / n_ctrls unchanged: the removed patients count as non-carriers), on one context with ``api.values_table`` and
     the masks of ``generate_permutations(seed, strata)``: ``ResidualScores``, ``ResidualCases``, ``ResidualControls`` and
     ``ResidualPvalues``.  ``ResidualPvalues`` is that set's NOMINAL permutation p-value n_ge / n_permutations -- the
-    residual score against its own null, not a family-wise number like ``Pvalues``.  NaN on lead rows and on -1 rows."""
+    residual score against its own null, not a family-wise number like ``Pvalues``.  NaN on lead rows and on -1 rows.
+
+    ``on_device``: the rule runs on the device too -- one ``api.JoinExec.clump_sets`` call per group instead of the
+    ``clump_rows`` / ``set_overlap`` loop, no pair count comes back.  Every column is what it is without
+    it; ``conditional`` is host-bound either way."""
     from . import api
     method = 2 if signed else 1
     genes, data = preprocess_table(genes, data, threshold, n_cases, n_ctrls)
@@ -1008,14 +1078,17 @@ def clump_paths(results_df, genes: Sequence[str], data: np.ndarray, n_cases: int
     res = {c: np.full(S, np.nan) for c in RESIDUAL_COLUMNS}
     ex = api.JoinExec(method, n_cases, n_ctrls, K, device=device)
     try:
-        size, _ = ex.set_overlap(sets, sub, a=[], b=[]) if S else (np.zeros((0, 2), np.int32), None)
+        size, _ = ex.set_overlap(sets, sub, a=[], b=[]) if S and not on_device else (np.zeros((0, 2), np.int32), None)
         groups = [np.flatnonzero(ok & (lengths == L)) for L in np.unique(lengths[ok]).tolist()] if by_length \
             else [np.flatnonzero(ok)]
         base = 0
         for idx in groups:
             order = idx[np.argsort(-scores[idx], kind="stable")]
-            c, l, v, sh = clump_rows(order, size, lambda la, lb: ex.set_overlap(sets, sub, a=la, b=lb)[1], r, measure,
-                                     patients)
+            if on_device:
+                c, l, v, sh, _ = ex.clump_sets(sets, sub, order, r, measure, patients)
+            else:
+                c, l, v, sh = clump_rows(order, size, lambda la, lb: ex.set_overlap(sets, sub, a=la, b=lb)[1], r, measure,
+                                         patients)
             clump[order], lead[order], value[order], shared[order] = c[order] + base, l[order], v[order], sh[order]
             base += int(c[order].max()) + 1 if len(order) else 0
         if conditional:
@@ -1035,14 +1108,7 @@ def clump_paths(results_df, genes: Sequence[str], data: np.ndarray, n_cases: int
                 res["ResidualPvalues"][js] = rec["pvalue"]
     finally:
         ex.close()
-    is_member = (clump >= 0) & (lead != np.arange(S))
-    paths = [str(p) for p in results_df["Paths"]]
-    out["Clump"] = clump
-    out["ClumpLead"] = [paths[l] if l >= 0 else None for l in lead.tolist()]
-    out["ClumpSize"] = np.where(clump >= 0, np.bincount(clump[clump >= 0], minlength=1)[np.maximum(clump, 0)], 0)
-    out["LeadOverlap"] = np.where(is_member, value, np.nan)
-    out["SharedCases"] = np.where(is_member, shared[:, 0], np.nan)
-    out["SharedControls"] = np.where(is_member, shared[:, 1], np.nan)
+    _set_clump_columns(out, clump, lead, value, shared)
     if conditional:
         for cname in RESIDUAL_COLUMNS:
             out[cname] = res[cname]
@@ -1200,7 +1266,7 @@ def gwaspa(genes: Sequence[str], data: np.ndarray, n_cases: int, n_ctrls: int, n
            clump: Optional[float] = None, clump_conditional: bool = False, false_counts: bool = False,
            false_count_ks: Sequence[int] = (2, 5, 10), false_count_alpha: float = 0.05,
            stepdown: bool = False, significant: Optional[float] = None,
-           significant_cap: int = 1_000_000) -> Dict[str, object]:
+           significant_cap: int = 1_000_000, clump_significant: bool = False) -> Dict[str, object]:
     """GWASPA (R/ProcessPaths.R:87-344) without R: dataset -> GWASPA.Results, scored on the MI355X.
 
     ``network`` = (ents_uid, ents_symbol, rel_src, rel_trg, rel_sign): the knowledge base getStringKB() would load
@@ -1257,6 +1323,13 @@ def gwaspa(genes: Sequence[str], data: np.ndarray, n_cases: int, n_ctrls: int, n
     whose list overflowed contributes no rows and a warning naming how many were found.  Outside (0, 1), or with
     ``n_permutations == 0``, ValueError before anything runs.  GWASPA.Results and everything else are what
     ``significant=None`` returns.  None, the default: nothing new is called.
+
+    ``clump_significant``: needs both ``clump`` and ``significant`` (ValueError before anything runs otherwise).
+    "Significant.Results" gains ``CLUMP_COLUMNS``: its rows of all lengths are walked together by ``Scores`` descending
+    (ties: table position), as ``clump_paths`` walks a table, with r = ``clump``, Jaccard over all patients.  The sets come
+    from the hit lists themselves (``hit_sets``: no string is parsed) and the rule runs on the device, in one
+    ``api.JoinExec.clump_sets`` call on the run's own context.  A length whose list overflowed contributes
+    no rows, as without it; residual columns for hits are not built.  False, the default: nothing new is called.
     """
     from . import api
     from .synth import Problem
@@ -1264,6 +1337,10 @@ def gwaspa(genes: Sequence[str], data: np.ndarray, n_cases: int, n_ctrls: int, n
 
     method = "method2" if signed else "method1"
     check_input(n_cases, n_ctrls, method, threshold, top_k, path_length, n_permutations)
+    if clump_significant and (clump is None or significant is None):
+        raise ValueError("clump_significant: needs both clump (the overlap r) and significant (the family-wise level)")
+    if clump_significant and not 0 < clump <= 1:
+        raise ValueError("r must be > 0 and <= 1")
     if significant is not None:
         if not 0.0 < float(significant) < 1.0:      # (NaN fails both comparisons)
             raise ValueError(f"significant: the family-wise level must lie inside (0, 1), not {significant!r}")
@@ -1394,6 +1471,17 @@ def gwaspa(genes: Sequence[str], data: np.ndarray, n_cases: int, n_ctrls: int, n
                                                    (prep.ents2_uid, prep.ents2_symbol))
         out["significant"] = found
         out["significant_cutoffs"] = cutoffs
+        if clump_significant:
+            sig = out["Significant.Results"]
+            hsets = hit_sets(found, gene_tables(levels, g, n2), g, n2,
+                             nulls={L: lsts[f"lst{L}"].null for L in found})
+            if len(hsets[0]) - 1 != len(sig):
+                raise ValueError(f"clump_significant: {len(hsets[0]) - 1} hit sets for {len(sig)} rows of Significant.Results")
+            sc = sig["Scores"].to_numpy(dtype=np.float64)
+            idx = np.flatnonzero(np.isfinite(sc))
+            order = idx[np.argsort(-sc[idx], kind="stable")]
+            c, l, v, sh, _ = ex.clump_sets(hsets, np.vstack([prep.data1, prep.data2]), order, r=clump)
+            _set_clump_columns(sig, c, l, v, sh)
     if gene_table:
         best = {L + 1: tallies[name].read() for L, name in enumerate(GENE_LEVELS[:path_length])}
         out["gene_best"] = best

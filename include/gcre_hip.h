@@ -459,6 +459,26 @@ int gcre_set_overlap(gcre_ctx* ctx, const gcre_set_input* in, const int64_t* a, 
 int64_t gcre_overlap_launches(const gcre_ctx* ctx);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Greedy clumping of caller-given sets by shared carriers, on the device.  No reference counterpart.
+ * The sets, their carrier rows, `size` and the shared counts are those of gcre_set_overlap.  `order` [n_order] names the
+ * sets to clump, best first, each at most once and none with an NA member.  Walk it: a set not yet assigned becomes the
+ * lead of a new clump (ids 0, 1, .. in walk order) and every later unassigned set whose overlap with it is >= r joins;
+ * overlap = both / den in f64, correctly rounded, 0.0 where den is 0, with both / |A| / |B| counted over all patients
+ * (patients 0) or the cases (1) and den = |A| + |B| - both (measure 0, jaccard) or min(|A|, |B|) (1, containment).
+ * Outputs per set: clump [n_sets] the clump id, lead [n_sets] the lead's set index (a lead names itself), value [n_sets]
+ * the overlap with the lead (NaN on a lead), shared [n_sets][2] the carriers shared with the lead ((-1, -1) on a lead); a
+ * set outside `order` gets -1 / -1 / NaN / (-1, -1).  size [n_sets][2], optional, as gcre_set_overlap fills it.
+ * No pair count leaves the device.  Errors, nothing launched: what gcre_set_overlap refuses of the set list; GCRE_ERR_ARG
+ * -- r outside (0, 1] or NaN, measure or patients not 0 or 1, a set listed twice, a listed set with an NA member,
+ * n_order x the bytes of a device row (the patients as bits, padded to 128 bytes) above GCRE_CLUMP_MAX_MB (environment,
+ * read per call, default 32768); GCRE_ERR_RANGE -- an order entry out of range.  n_order == 0 launches nothing. */
+int gcre_clump_sets(gcre_ctx* ctx, const gcre_set_input* in, const int64_t* order, int64_t n_order, double r,
+                    int measure, int patients, int32_t* size, int64_t* clump, int64_t* lead, double* value,
+                    int32_t* shared);
+/* kernels launched by gcre_clump_sets on the context since gcre_create (tests: a refusal launches nothing). */
+int64_t gcre_clump_launches(const gcre_ctx* ctx);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Per-gene best-path table: for every gene, the best joined path of a join that runs through it.  No
  * reference counterpart (it keeps the top K of a level and nothing else).  A join's inspector leaves the observed score,
  * operand rows, cases and controls of EVERY joined path on the device; a tally armed for the join folds them, chunk by
