@@ -363,6 +363,7 @@ struct gcre_ctx {
   int ie_flagq = 1;                  // GCRE_IE_FLAGQ=0: the quad kernel's second look + exact pass instead of the flag queue (A/B runs, tests)
   int ie_zwide = 0;                  // GCRE_IE_ZWIDE=1: the quad kernel reaches every added row through a descriptor of its own (tests)
   int ie_warm_items = 4;             // (segment, tile) items per wave of the warm-up launch (GCRE_IE_WARM_ITEMS)
+  int ie_warm_div = 4096;            // the slice grows with the join as scored segments / this (GCRE_IE_WARM_DIV; warm_segments)
   int exchange_tail = 0;             // slices of the pruned launch that are equal steps at its end (GCRE_EXCHANGE_TAIL; -1: half of them; 0: doubling slices only)
   int ie_warm_segs = 1024;           // least number of segments in the warm-up slice (GCRE_IE_WARM; 2048 until round 3: the filter's second look made early thresholds matter less)
   int ie_small_join_tiles = 8;       // GCRE_IE_SJT (tuning)

@@ -541,11 +541,17 @@ void build_quads_host(const gcre_uids& u, const std::vector<SparseSeg>& segs, in
   *quad_begin_out = quad_begin;
 }
 
-// segments of the warm-up slice of a pruned launch (run_join): the first n_warm scored segments are scored without pruning
+// segments of the warm-up slice of a pruned launch (run_join): the first n_warm scored segments are scored without pruning.
+// A slice only has to leave every permutation of a tile with some non-zero maximum to prune against; once the pruned
+// kernel runs, its waves' own finds (exchanged after 1, 2, 4, .. segments) outnumber the slice's many times over.  So
+// the slice is ie_warm_segs segments (per eight tiles), and grows with the join only as nseg / ie_warm_div
+// (GCRE_IE_WARM_DIV).  The divisor is 4096: at 1024 the benchmark's last level (2.3 million scored segments) had a slice
+// of 2,270 segments, and the sweep (profiles/warmup_sweep.txt) took 0.27 ms less per pass with 1,024 although 1.5 % more
+// path-tiles were then looked up; at 512 and 256 the look-ups cost more than the shorter slice saves.
 int64_t warm_segments(const gcre_ctx* c, int64_t nseg_scored, int nkt) {
   if (c->ie_warm_segs == 0) return 0;   // GCRE_IE_WARM=0 (tests): everything through the pruned kernel, thresholds from 0
   const int64_t warm_min = std::max<int64_t>(256, (int64_t)c->ie_warm_segs * 8 / std::max(nkt, 8));
-  return std::min<int64_t>(nseg_scored, std::min<int64_t>(std::max<int64_t>(warm_min, nseg_scored / 1024),
+  return std::min<int64_t>(nseg_scored, std::min<int64_t>(std::max<int64_t>(warm_min, nseg_scored / c->ie_warm_div),
                                                           std::max<int64_t>(256, nseg_scored / 8)));
 }
 
@@ -2013,7 +2019,18 @@ int launch_ie_slices(JoinRun& R, const ChunkRun& C, IeArgs& ia, int planes, int6
     wa.seg_end = n_warm;
     // a wave walks its tiles one after the other: keep enough waves that each gets about four (segment, tile) items
     wa.waves_per_xcd = spread_waves(wa.waves_per_xcd, n_warm * R.nkt_sp, c->ie_warm_items);
+    if (wa.timing) wa.timing += 12;   // diagnostics build: the slice's section clocks, next to the pruned launch's
     if (n_warm > 0) HIP_TRY(c, launch_null_ie(wa, g.method, planes, true, st));
+    if (n_warm > 0 && wa.timing && R.mode != kLaunch) {
+      uint64_t tw[7] = {0};
+      HIP_TRY(c, hipMemcpyAsync(tw, wa.timing, sizeof tw, hipMemcpyDeviceToHost, st));
+      HIP_TRY(c, hipStreamSynchronize(st));
+      const double waves = 8.0 * wa.waves_per_xcd;
+      std::fprintf(stderr, "[ie warm timing] level %d paths %lld segments %lld x %d tiles, waves %.0f: per-wave kcycles prologue %.1f paths to counts %.1f "
+                   "transpose+look-ups %.1f flush %.1f (%.2f flushes) total %.1f, slowest wave %.1f\n", R.u->path_length, (long long)n,
+                   (long long)n_warm, wa.nkt, waves, tw[0] / waves / 1e3, tw[1] / waves / 1e3, tw[2] / waves / 1e3, tw[3] / waves / 1e3,
+                   (double)tw[4] / waves, tw[5] / waves / 1e3, tw[6] / 1e3);
+    }
     ia.seg_begin = n_warm;
   }
   if (ia.seg_begin >= ia.seg_end) return GCRE_OK;
@@ -2211,8 +2228,8 @@ int score_chunk_ie(JoinRun& R, ChunkRun& C, ChunkEnd* end) {
   }
   const bool timing = std::getenv("GCRE_IE_TIMING") != nullptr;   // diagnostics builds only (-DGCRE_IE_TIMING)
   if (timing) {
-    HIP_TRY(c, c->d_ie_timing.reserve(12));
-    HIP_TRY(c, hipMemsetAsync(c->d_ie_timing.p, 0, 96, st));
+    HIP_TRY(c, c->d_ie_timing.reserve(24));   // [0,12) the pruned launches, [12,24) the warm-up slice
+    HIP_TRY(c, hipMemsetAsync(c->d_ie_timing.p, 0, 192, st));
     ia.timing = c->d_ie_timing.p;
   }
   if (C.sel_begun && C.sel_on == st)   // (its state came back with the flags)
@@ -2613,6 +2630,7 @@ gcre_ctx* gcre_create(int method, int n_cases, int n_ctrls, int iterations, int 
   if (const char* e = std::getenv("GCRE_EXCHANGE_TAIL")) c->exchange_tail = std::min(std::max(std::atoi(e), -1), 64);
   if (const char* e = std::getenv("GCRE_IE_WARM")) c->ie_warm_segs = std::min(std::max(std::atoi(e), 0), 1 << 20);
   if (const char* e = std::getenv("GCRE_IE_WARM_ITEMS")) c->ie_warm_items = std::min(std::max(std::atoi(e), 1), 64);
+  if (const char* e = std::getenv("GCRE_IE_WARM_DIV")) c->ie_warm_div = std::min(std::max(std::atoi(e), 1), 1 << 30);
   if (const char* e = std::getenv("GCRE_IE_SJT")) c->ie_small_join_tiles = std::atoi(e);
   if (const char* e = std::getenv("GCRE_IE_BATCH")) c->ie_batch = std::min(std::max(std::atoi(e), 1), 4096);
   if (const char* e = std::getenv("GCRE_IEQ_BATCH")) c->ieq_batch = std::max(0, std::atoi(e));

@@ -26,22 +26,39 @@
 
 namespace gcre {
 
-
+// section clocks of a diagnostics build (-DGCRE_IE_TIMING): every mark drains the wave's memory counters first
+#ifdef GCRE_IE_TIMING
+#define GCRE_TM_MARK(var) __builtin_amdgcn_s_waitcnt(0); const u64 var = __builtin_amdgcn_s_memtime()
+#define GCRE_TM_ADD(i, t1, t0) tm[i] += (t1) - (t0)
+#else
+#define GCRE_TM_MARK(var)
+#define GCRE_TM_ADD(i, t1, t0)
+#endif
 
 // The general kernel: both methods, every count looked up (no pruning).  Runs the signed method, and for method 1 the
 // warm-up slice that seeds the pruned kernel's thresholds.  L = counter planes of the joined paths, a multiple of 4.
+//
+// Work is dealt by BLOCK.  A chunk is kIeWaves neighbouring segments of one tile, one per wave of a block; the launch's
+// chunks, tile-major, are cut into eight contiguous parts, one per XCD (blocks b and b + 8 share an L2), and block i of
+// an XCD takes chunks i, i + blocks-per-XCD, ... of its part.  So the blocks of an XCD work on neighbouring segments of
+// one tile at a time (the table is sorted by the added rows), the tiles a block visits are consecutive, and blocks
+// differ by one chunk at the most.  Striding matters: segments differ in length and long ones come in runs -- contiguous
+// equal shares of the table left the slowest wave at 3.2 times the mean, strides at 1.8 (profiles/warmup_after.txt).
+// The four waves change tile together, and their running maxima leave LDS in ONE merged flush per (block, tile): see
+// flush below.  Every wave of a block walks every chunk of the block, with or without a segment of its own in it, and
+// no wave leaves before the last flush: the flush has the kernel's only barriers.
 template <int M, int L>
 __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(M == 1 ? 4 : 2))) void k_null_ie(const IeArgs a) {
   static_assert(L % 4 == 0 && L >= 8 && L <= 16, "planes come in groups of 4");
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int xcd = blockIdx.x & 7;
-  const i64 wi = (i64)(blockIdx.x >> 3) * kIeWaves + wave;
-  const i64 wx = a.waves_per_xcd;
-  const i64 slices = 8 * wx;
+  const i64 bi = (i64)(blockIdx.x >> 3);
+  const i64 bx = a.waves_per_xcd / kIeWaves;   // blocks per XCD (launch_null_ie: waves_per_xcd is a multiple of kIeWaves)
+  const i64 cpt = (a.seg_end - a.seg_begin + kIeWaves - 1) / kIeWaves;   // chunks per tile
+  const i64 chunks = cpt * a.nkt;                                        // < 2^45
   const u32 lane4 = (u32)lane * 4u;
-  // the wave's 2048 running maxima of its current tile: 8 KB of LDS, [q][lane], flushed to the global array with
-  // atomicMax whenever the wave moves to another tile
+  // the waves' 2048 running maxima of the block's current tile: 8 KB of LDS each, [q][lane] <-> permutation 32 * lane + q
   __shared__ u32 gmax_lds[kIeWaves][32 * 64];
   u32* scr = gmax_lds[wave] + lane;
 #pragma unroll
@@ -53,17 +70,50 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(M
 
   int cur_kt = -1;
   __amdgpu_buffer_rsrc_t mt = __builtin_amdgcn_make_buffer_rsrc((void*)a.mt, 0, 0x7fffffff, 0x00020000);
+#ifdef GCRE_IE_TIMING
+  u64 tm[6] = {0, 0, 0, 0, 0, 0};   // segment prologue, path loop up to the counts, transpose + look-ups, flush, flushes, total
+  const u64 tm_begin = __builtin_amdgcn_s_memtime();
+#endif
 
+  // The block's merged flush, when its tile changes and at the end (cur_kt is block-uniform: all four waves come here
+  // together).  Behind a barrier the four waves' arrays are combined: wave w takes permutations [512 w, 512 w + 512) of
+  // the tile, 8 consecutive ones per lane -- two wide loads of the global values, past the caches that never see the
+  // other XCDs' atomics (sc1, as the pruned kernels' exchange) -- and issues atomicMax only where the block's maximum is
+  // larger.  A stale global value is a smaller one: an atomic too many, never one too few.  All four arrays are zero
+  // again behind the second barrier, for the next tile.
   auto flush = [&]() {
     if (cur_kt < 0) return;
-    u32* out = a.null_bits + (size_t)cur_kt * 2048 + lane * 32;
-    for (int q = 0; q < 32; q++) {
-      const u32 own = scr[q * 64];
-      if (own != 0u) {
-        atomicMax(out + q, own);
-        scr[q * 64] = 0u;
+    GCRE_TM_MARK(tf0);
+    __syncthreads();
+    const u32 slot0 = (u32)wave * 512u + (u32)lane * 8u;
+    __amdgpu_buffer_rsrc_t nb = __builtin_amdgcn_make_buffer_rsrc((void*)(a.null_bits + (size_t)cur_kt * 2048), 0, 8192, 0x00020000);
+    const u32x4 g0 = __builtin_amdgcn_raw_buffer_load_b128(nb, slot0 * 4u, 0, 16 /* sc1 */);
+    const u32x4 g1 = __builtin_amdgcn_raw_buffer_load_b128(nb, slot0 * 4u + 16u, 0, 16 /* sc1 */);
+    u32* out = a.null_bits + (size_t)cur_kt * 2048 + slot0;
+    u32* cell = &gmax_lds[0][0] + (slot0 & 31u) * 64u + (slot0 >> 5);   // permutation 32 l + q lives at [q][l]
+    u32 own[8];
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+      u32 m = 0u;
+#pragma unroll
+      for (int w = 0; w < kIeWaves; w++) {
+        const u32 v = cell[w * 32 * 64 + j * 64];
+        m = v > m ? v : m;
+        cell[w * 32 * 64 + j * 64] = 0u;
       }
+      own[j] = m;
     }
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+      const u32 g = j < 4 ? g0[j & 3] : g1[j & 3];
+      if (own[j] > g) atomicMax(out + j, own[j]);
+    }
+    __syncthreads();
+    GCRE_TM_MARK(tf1);
+    GCRE_TM_ADD(3, tf1, tf0);
+#ifdef GCRE_IE_TIMING
+    tm[4] += 1;
+#endif
   };
 
   auto to_counts = [&](const u32 (&C)[L], u32 (&R)[16]) {
@@ -136,16 +186,17 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(M
     }
   };
 
-  for (int step = 0; step < a.nkt; step++) {
-    const i64 item = (i64)xcd * a.nkt * wx + wi + (i64)step * wx;
-    const int kt = (int)(item / slices);
-    const i64 sl = item % slices;
+  const i64 c_end = (i64)(xcd + 1) * chunks / 8;
+  for (i64 c = (i64)xcd * chunks / 8 + bi; c < c_end; c += bx) {   // block-uniform
+    const int kt = (int)(c / cpt);
     if (kt != cur_kt) {
       flush();
       cur_kt = kt;
       mt = __builtin_amdgcn_make_buffer_rsrc((void*)(a.mt + (size_t)kt * a.mt_rows * 64), 0, 0x7fffffff, 0x00020000);
     }
-    for (i64 sidx = a.seg_begin + sl; sidx < a.seg_end; sidx += slices) {
+    const i64 sidx = a.seg_begin + (c - (i64)kt * cpt) * kIeWaves + wave;
+    if (sidx < a.seg_end) {   // (a tile's last chunk may be short)
+      GCRE_TM_MARK(ts0);
       const u32 row0 = segs[sidx].row0;
       const u32 first = segs[sidx].first;
       const u32 npaths = segs[sidx].n;
@@ -229,7 +280,10 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(M
         }
       }
 
+      GCRE_TM_MARK(ts1);
+      GCRE_TM_ADD(0, ts1, ts0);
       for (u32 t = 0; t < npaths; t++) {
+        GCRE_TM_MARK(tp0);
         const u32 q = first + t;
         u32 C[M][L];
 #pragma unroll
@@ -297,16 +351,26 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(M
             }
           }
         }
+        GCRE_TM_MARK(tp1);
+        GCRE_TM_ADD(1, tp1, tp0);
         if (q < a.score_begin || q >= a.score_end) continue;   // planes only: the path belongs to another shard
         if constexpr (M == 1) {
           finish_m1(C[0], rdlane(ttv[0], t));
         } else {
           finish_m2(C[0], C[M - 1], rdlane(ttv[0], t), rdlane(ttv[M - 1], t));
         }
+        GCRE_TM_MARK(tp2);
+        GCRE_TM_ADD(2, tp2, tp1);
       }
     }
   }
   flush();
+#ifdef GCRE_IE_TIMING
+  tm[5] = __builtin_amdgcn_s_memtime() - tm_begin;
+  if (a.timing && lane == 0)
+    for (int i = 0; i < 6; i++) atomicAdd((unsigned long long*)a.timing + i, (unsigned long long)tm[i]);
+  if (a.timing && lane == 0) atomicMax((unsigned long long*)a.timing + 6, (unsigned long long)tm[5]);
+#endif
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -344,11 +408,6 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(L
 #ifdef GCRE_IE_TIMING
   u64 tm[6] = {0, 0, 0, 0, 0, 0};   // seg prologue, load wait, compute, lookups, exchange, total
   const u64 tm_begin = __builtin_amdgcn_s_memtime();
-#define GCRE_TM_MARK(var) __builtin_amdgcn_s_waitcnt(0); const u64 var = __builtin_amdgcn_s_memtime()
-#define GCRE_TM_ADD(i, t1, t0) tm[i] += (t1) - (t0)
-#else
-#define GCRE_TM_MARK(var)
-#define GCRE_TM_ADD(i, t1, t0)
 #endif
   __amdgpu_buffer_rsrc_t mt = __builtin_amdgcn_make_buffer_rsrc((void*)a.mt, 0, 0x7fffffff, 0x00020000);
 
@@ -994,6 +1053,7 @@ hipError_t launch_null_ie(const IeArgs& a, int method, int planes, bool general,
   } else if (method == 2 && !general) {
     return launch_null_ie_m2(a, planes, stream);
   } else {
+    if (a.waves_per_xcd < kIeWaves || a.waves_per_xcd % kIeWaves != 0) return hipErrorInvalidValue;   // whole blocks per XCD: work is dealt by block
 #define GCRE_LAUNCH(MM, LL) hipLaunchKernelGGL((k_null_ie<MM, LL>), grid, block, 0, stream, a)
     GCRE_IE_GEN(GCRE_LAUNCH)
 #undef GCRE_LAUNCH
