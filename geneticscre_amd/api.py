@@ -129,6 +129,7 @@ EXPORTS = [
     "gcre_set_inspect_cache", "gcre_drop_inspections", "gcre_build_flags", "gcre_device_count",
     "gcre_rccl_selftest", "gcre_rccl_collectives", "gcre_join_ahead",
     "gcre_decorated_splits", "gcre_decorated_pvalues", "gcre_score_sets",
+    "gcre_score_sets_given", "gcre_given_launches",
     "gcre_set_overlap", "gcre_overlap_launches",
     "gcre_clump_sets", "gcre_clump_launches",
     "gcre_gene_tally_create", "gcre_join_set_tally", "gcre_process_paths_set_tally", "gcre_gene_tally_read",
@@ -250,6 +251,9 @@ _FEATURES = {
         "gcre_decorated_pvalues": (_I, [_P, ctypes.POINTER(gcre_dp_input), _P, _I64, ctypes.POINTER(_I64), _P])}),
     "sets": (None, ["gcre_score_sets"], "set scoring (gcre_score_sets)", {
         "gcre_score_sets": (_I, [_V, ctypes.POINTER(gcre_set_input), _P, _I64, ctypes.POINTER(_I64), _P])}),
+    "given": ("sets", ["gcre_score_sets_given", "gcre_given_launches"], "conditional set scores (gcre_score_sets_given)", {
+        "gcre_score_sets_given": (_I, [_V, ctypes.POINTER(gcre_set_input), _P, _P, _I64, _P, _I64, ctypes.POINTER(_I64), _P]),
+        "gcre_given_launches": (_I64, [_V])}),
     "overlap": (None, ["gcre_set_overlap"], "carrier overlaps (gcre_set_overlap)", {
         "gcre_set_overlap": (_I, [_V, ctypes.POINTER(gcre_set_input), _P, _I64, _P, _I64, _P, _P]),
         "gcre_overlap_launches": (_I64, [_V])}),
@@ -305,6 +309,7 @@ def _feature_lib(feature: str):
 
 _decorated_lib = functools.partial(_feature_lib, "decorated")
 _sets_lib = functools.partial(_feature_lib, "sets")
+_given_lib = functools.partial(_feature_lib, "given")
 _overlap_lib = functools.partial(_feature_lib, "overlap")
 _clump_lib = functools.partial(_feature_lib, "clump")
 _genes_lib = functools.partial(_feature_lib, "genes")
@@ -876,12 +881,22 @@ class JoinExec:
         rec = out[:n_out.value]
         return (rec, counts[:n_out.value]) if return_counts else rec
 
-    def score_sets(self, sets, rows, signs=None, family: bool = False):
+    def score_sets(self, sets, rows, signs=None, family: bool = False, given=None, which=None):
         """Permutation tests of caller-given sets (gcre_score_sets): one SET_SCORE record per set, against this context's
         value table and all ``iters`` permutation masks.  ``sets``: one sequence of row indices of ``rows`` per set
         (-1 = NA gene); ``rows``: the 0/1 carrier matrix [rows][patients]; ``signs``: per set +1 / -1 per member (None =
         all +1; read by method 2).  With ``family`` also the per-permutation maximum of the sets' null scores (float32
-        [iters]).  Errors raise GcreError with the library's message."""
+        [iters]).  Errors raise GcreError with the library's message.
+
+        ``given`` / ``which``: conditional scores (gcre_score_sets_given), one record per ENTRY: entry i is
+        set ``which[i]`` (None: every set in order; repeats allowed) scored without the carriers of set ``given[i]`` -- the
+        patients with a variant in any member of that set, whatever the signs; -1 or ``given=None``: nothing set aside.
+        The removed patients count as non-carriers.  ``sets`` may then also be a pair ``(off, members)`` as
+        ``report.hit_sets`` returns it (``signs`` then one flat array, or None).  An index out of range, ``given`` and
+        ``which`` of different lengths, or a given set with an NA member raise ValueError before the library is touched.
+        With both None nothing changes: the same call, the same records."""
+        if given is not None or which is not None:
+            return JoinExec._score_sets_given(self, sets, rows, signs, family, given, which)
         lib = _sets_lib()
         n = self.num_cases + self.num_ctrls
         S = len(sets)
@@ -910,6 +925,63 @@ class JoinExec:
             raise GcreError(self._lib.gcre_last_error(self._h).decode())
         rec = out[:n_out.value]
         return (rec, fam) if family else rec
+
+    def _score_sets_given(self, sets, rows, signs, family, given, which):
+        if isinstance(sets, tuple) and len(sets) == 2 and isinstance(sets[0], np.ndarray):
+            off = np.ascontiguousarray(sets[0], dtype=np.int64)
+            members = np.ascontiguousarray(sets[1], dtype=np.int32)
+            S = len(off) - 1
+            sg = None if signs is None else np.ascontiguousarray(np.asarray(signs, dtype=np.int64).reshape(-1), dtype=np.int32)
+            if sg is not None and len(sg) != len(members):
+                raise ValueError("signs: one sign per member of every set")
+        else:
+            S = len(sets)
+            lens = [len(s) for s in sets]
+            off = np.zeros(S + 1, dtype=np.int64)
+            off[1:] = np.cumsum(lens)
+            members = np.ascontiguousarray(np.concatenate([np.asarray(s, dtype=np.int64).reshape(-1) for s in sets])
+                                           if S else np.zeros(0), dtype=np.int32)
+            sg = None
+            if signs is not None:
+                if len(signs) != S or any(len(x) != L for x, L in zip(signs, lens)):
+                    raise ValueError("signs: one sign per member of every set")
+                sg = np.ascontiguousarray(np.concatenate([np.asarray(x, dtype=np.int64).reshape(-1) for x in signs])
+                                          if S else np.zeros(0), dtype=np.int32)
+        iw = None if which is None else np.ascontiguousarray(np.asarray(which, dtype=np.int64).reshape(-1))
+        ig = None if given is None else np.ascontiguousarray(np.asarray(given, dtype=np.int64).reshape(-1))
+        E = S if iw is None else len(iw)
+        if ig is not None and len(ig) != E:
+            raise ValueError(f"given: {len(ig)} entries for {E} scored sets (one per entry of which, or per set)")
+        if iw is not None and len(iw) and (iw.min() < 0 or iw.max() >= S):
+            raise ValueError(f"which: a set index outside 0..{S - 1}")
+        if ig is not None and len(ig):
+            if ig.min() < -1 or ig.max() >= S:
+                raise ValueError(f"given: a set index outside -1..{S - 1}")
+            na = np.zeros(S, bool)
+            np.logical_or.at(na, np.repeat(np.arange(S), np.diff(off)), members < 0)
+            if na[ig[ig >= 0]].any():
+                raise ValueError("given: a given set has an NA member (-1): its carriers are not known")
+        lib = _given_lib()
+        n = self.num_cases + self.num_ctrls
+        d = np.asarray(rows)
+        if d.ndim != 2:
+            d = d.reshape(-1, n)
+        packed = pack_carriers(d, d.shape[1])
+        inp = gcre_set_input(S, _ptr(off), _ptr(members), _ptr(sg), _ptr(packed), packed.shape[0], d.shape[1])
+        out = np.zeros(max(E, 1), dtype=SET_SCORE)
+        fam = np.zeros(self.iters, dtype=np.float32) if family else None
+        n_out = ctypes.c_int64(0)
+        rc = lib.gcre_score_sets_given(self._h, ctypes.byref(inp), _ptr(iw), _ptr(ig), E, _ptr(out), len(out),
+                                       ctypes.byref(n_out), _ptr(fam) if family and self.iters > 0 else None)
+        if rc != GCRE_OK:
+            raise GcreError(self._lib.gcre_last_error(self._h).decode())
+        rec = out[:n_out.value]
+        return (rec, fam) if family else rec
+
+    @property
+    def given_launches(self) -> int:
+        """Kernels gcre_score_sets_given launched on this context so far."""
+        return int(_given_lib().gcre_given_launches(self._h))
 
     def set_overlap(self, sets, rows, a=None, b=None):
         """Carrier overlaps of caller-given sets (gcre_set_overlap).  A set's carrier row is the OR of all

@@ -1,5 +1,5 @@
 // gcre_host_stats.hip -- the entry points of include/gcre_hip.h that use a context but not the join driver: generated
-// permutation masks, decorated p-values (gcre_decorated.hip), set scores (gcre_sets.hip) and carrier overlaps
+// permutation masks, decorated p-values (gcre_decorated.hip), set scores (gcre_sets.hip, conditional: gcre_given.hip) and carrier overlaps
 // (gcre_overlap.hip) and greedy clumps (gcre_clump.hip), and the per-gene tally (gcre_genes.hip), the null exceedance counts (gcre_exceed.hip,
 // gcre_stepdown.hip) and the hit lists (gcre_hits.hip) as objects.  What a join does with an armed tally, armed counts or
 // an armed list -- check_tally, fold_genes, count_exceed, collect_hits -- is in gcre_host.hip.  Host code only.
@@ -55,6 +55,46 @@ void fill_set_launch(Args& a, const gcre_ctx* c, const uint64_t* d_rows, const u
   const int64_t slots = (int64_t)c->cus * 4 * 8;
   const int64_t per = std::max<int64_t>(1, (a.npt * a.nkt) / slots);
   a.pgroups = (int)std::min<int64_t>((a.npt + per - 1) / per, 0x7fffffff / std::max(a.nkt, 1));
+}
+
+// The device stage gcre_score_sets and gcre_score_sets_given share.  V sets' union rows [V][M][Wp], counts [V][4] and totals
+// [V][M] are on the device: the observed scores (k_set_observed), their f32 thresholds on the host and, with permutations,
+// k_set_null.  obs / ge [V] are read back (ge stays as it is without permutations); d_fam [Kpad], zeroed by the caller or
+// nullptr, takes the maxima over these sets too and is read back into fam_out [K] where that is given.  Ends synchronised;
+// errors stay in `d`.  `launches` (or nullptr) counts the kernels launched.
+struct SetStageBufs {
+  uint32_t* thr;              // [V]
+  double* obs;                // [V]
+  unsigned long long* ge;     // [V]
+};
+void score_set_rows(gcre_ctx* c, DevScratch& d, const uint64_t* d_rows, const int32_t* d_cnt, const uint32_t* d_tot,
+                    const SetStageBufs& b, uint32_t* d_fam, int64_t V, double* obs, unsigned long long* ge, uint32_t* fam_out,
+                    int64_t* launches) {
+  const int K = c->g.K, M = c->g.method;
+  if (d.ok()) {
+    d.e = launch_set_observed(d_cnt, V, M, c->d_dvt, b.obs, c->stream);
+    if (d.ok() && launches) ++*launches;
+  }
+  d.download(obs, b.obs, (size_t)V);
+  d.sync();
+  if (d.ok() && K > 0) {
+    std::vector<uint32_t> thr((size_t)V);
+    for (int64_t v = 0; v < V; v++) thr[(size_t)v] = f32_threshold(obs[(size_t)v]);
+    SetNullArgs a{};
+    fill_set_launch(a, c, d_rows, d_tot, V);
+    a.thr = b.thr;
+    a.n_ge = b.ge;
+    a.fam_bits = d_fam;
+    d.upload(b.thr, thr.data(), (size_t)V);
+    d.zero(b.ge, (size_t)V);
+    if (d.ok()) {
+      d.e = launch_set_null(a, M, c->stream);
+      if (d.ok() && launches) ++*launches;
+    }
+    d.download(ge, b.ge, (size_t)V);
+    if (fam_out) d.download(fam_out, d_fam, (size_t)K);
+    d.sync();
+  }
 }
 
 // the counts may have been queued on either stream of the context
@@ -264,25 +304,9 @@ int gcre_score_sets(gcre_ctx* c, const gcre_set_input* in, gcre_set_score* out, 
   double* d_obs = d.take<double>((size_t)V);
   unsigned long long* d_ge = d.take<unsigned long long>((size_t)V);
   uint32_t* d_fam = fam ? d.take<uint32_t>((size_t)g.Kpad) : nullptr;
-  if (d.ok()) d.e = launch_set_observed(d_cnt, V, M, c->d_dvt, d_obs, c->stream);
-  d.download(obs.data(), d_obs, (size_t)V);
-  d.sync();
-  if (d.ok() && K > 0) {
-    std::vector<uint32_t> thr((size_t)V);
-    for (int64_t v = 0; v < V; v++) thr[(size_t)v] = f32_threshold(obs[(size_t)v]);
-    SetNullArgs a{};
-    fill_set_launch(a, c, d_rows, d_tot, V);
-    a.thr = d_thr;
-    a.n_ge = d_ge;
-    a.fam_bits = d_fam;
-    d.upload(d_thr, thr.data(), (size_t)V);
-    d.zero(d_ge, (size_t)V);
-    if (fam) d.zero(d_fam, (size_t)g.Kpad);
-    if (d.ok()) d.e = launch_set_null(a, M, c->stream);
-    d.download(ge.data(), d_ge, (size_t)V);
-    if (fam) d.download(fbits.data(), d_fam, (size_t)K);
-    d.sync();
-  }
+  if (fam) d.zero(d_fam, (size_t)g.Kpad);
+  score_set_rows(c, d, d_rows, d_cnt, d_tot, {d_thr, d_obs, d_ge}, d_fam, V, obs.data(), ge.data(), fam ? fbits.data() : nullptr,
+                 nullptr);
   if (!d.ok()) return fail(c, GCRE_ERR_DEVICE, std::string("score_sets: ") + hipGetErrorString(d.e));
   for (int64_t v = 0; v < V; v++) {
     gcre_set_score& o = out[vset[(size_t)v]];
@@ -293,6 +317,115 @@ int gcre_score_sets(gcre_ctx* c, const gcre_set_input* in, gcre_set_score* out, 
   if (fam) std::memcpy(family_max, fbits.data(), (size_t)K * 4);
   return GCRE_OK;
 }
+
+// Conditional set scores: gcre_score_sets on residual union rows that k_set_residual builds on the device
+// from the caller's gene rows and set list, uploaded once.  The entries without an NA member are walked in slabs so that the
+// device rows stay bounded; every slab goes through score_set_rows, and the family maxima accumulate across the slabs.
+int gcre_score_sets_given(gcre_ctx* c, const gcre_set_input* in, const int64_t* which, const int64_t* given, int64_t n_which,
+                          gcre_set_score* out, int64_t cap, int64_t* n_out, float* family_max) {
+  if (!c) return GCRE_ERR_ARG;
+  if (!in || !n_out || cap < 0 || (cap > 0 && !out)) return fail(c, GCRE_ERR_ARG, "score_sets_given: NULL argument");
+  *n_out = 0;
+  const Geometry& g = c->g;
+  const int K = g.K, M = g.method;
+  if (int rc = check_sets(c, in, "score_sets_given")) return rc;
+  std::string msg;
+  if (int rc = check_given_index(in, which, given, n_which, cap, "score_sets_given", msg)) return fail(c, rc, msg);
+  *n_out = n_which;
+  if (family_max) std::fill(family_max, family_max + K, 0.0f);
+  if (n_which == 0) return GCRE_OK;
+
+  // the entries to launch: those whose set has no NA member, in input order
+  const int64_t S = in->n_sets;
+  const double nan = std::numeric_limits<double>::quiet_NaN();
+  std::vector<signed char> valid((size_t)S, -1);   // -1: not looked at yet
+  std::vector<int64_t> ventry, vw, vg;
+  for (int64_t i = 0; i < n_which; i++) {
+    const int64_t s = which ? which[i] : i;
+    if (valid[(size_t)s] < 0) valid[(size_t)s] = set_is_valid(in, s) ? 1 : 0;
+    gcre_set_score& o = out[i];
+    std::memset(&o, 0, sizeof o);
+    o.set = s;
+    o.score = nan;
+    o.pvalue = nan;
+    o.valid = valid[(size_t)s];
+    if (!o.valid) continue;
+    ventry.push_back(i);
+    vw.push_back(s);
+    vg.push_back(given ? given[i] : -1);
+  }
+  const int64_t V = (int64_t)ventry.size();
+  if (V == 0) return GCRE_OK;
+
+  // entries per slab: 1 GiB of residual rows, one tile of k_set_null at the least (GCRE_GIVEN_SLAB_SETS: tests)
+  const size_t RW = (size_t)M * g.Wp;   // words per entry
+  int64_t slab = std::max<int64_t>(((int64_t)1 << 30) / (int64_t)(RW * 8), set_null_tile_sets(M));
+  if (const char* e = std::getenv("GCRE_GIVEN_SLAB_SETS")) slab = std::min<int64_t>(std::max<int64_t>(std::atoll(e), 1), (int64_t)1 << 28);
+  slab = std::min(slab, V);
+
+  (void)hipSetDevice(c->device);
+  const bool fam = family_max && K > 0;
+  const bool split = M == 2 && in->signs;
+  const int64_t n_members = in->set_off[S];
+  std::vector<double> obs((size_t)slab);
+  std::vector<unsigned long long> ge((size_t)slab);
+  std::vector<int32_t> cnt((size_t)slab * 4);
+  std::vector<uint32_t> fbits(fam ? (size_t)K : 0);
+  DevScratch d(c->stream);
+  SetResidualArgs a{};
+  a.rows = (const uint32_t*)d.put(in->rows, std::max<size_t>((size_t)in->n_rows * (size_t)g.W, 1));
+  a.set_off = d.put(in->set_off, (size_t)S + 1);
+  a.members = d.put(in->members, (size_t)n_members);
+  a.signs = split ? d.put(in->signs, (size_t)n_members) : nullptr;
+  const int64_t* d_which = d.put(vw.data(), (size_t)V);
+  const int64_t* d_given = d.put(vg.data(), (size_t)V);
+  uint64_t* d_rows = d.take<uint64_t>((size_t)slab * RW);
+  a.out = (uint32_t*)d_rows;
+  a.cnt = d.take<int32_t>((size_t)slab * 4);
+  a.tot = d.take<uint32_t>((size_t)slab * M);
+  a.W2 = 2 * g.W;
+  a.W32p = 2 * g.Wp;
+  a.n_patients = g.n;
+  a.n_cases = g.n_cases;
+  const SetStageBufs b{d.take<uint32_t>((size_t)slab), d.take<double>((size_t)slab), d.take<unsigned long long>((size_t)slab)};
+  uint32_t* d_fam = fam ? d.take<uint32_t>((size_t)g.Kpad) : nullptr;
+  if (fam) d.zero(d_fam, (size_t)g.Kpad);   // once: the maxima run over all slabs
+  int64_t slabs = 0;
+  for (int64_t v0 = 0; d.ok() && v0 < V; v0 += slab, slabs++) {
+    const int64_t nv = std::min(slab, V - v0);
+    a.which = d_which + v0;
+    a.given = d_given + v0;
+    a.n = nv;
+    d.e = launch_set_residual(a, M, c->stream);
+    if (d.ok()) c->given_launches++;
+    d.download(cnt.data(), a.cnt, (size_t)nv * 4);
+    std::fill(ge.begin(), ge.begin() + nv, 0ull);
+    score_set_rows(c, d, d_rows, a.cnt, a.tot, b, d_fam, nv, obs.data(), ge.data(),
+                   fam && v0 + nv == V ? fbits.data() : nullptr, &c->given_launches);
+    if (!d.ok()) break;
+    for (int64_t v = 0; v < nv; v++) {
+      gcre_set_score& o = out[ventry[(size_t)(v0 + v)]];
+      const int32_t* k = cnt.data() + 4 * v;
+      o.cases_pos = k[0];
+      o.ctrls_pos = k[1];
+      o.cases_neg = k[2];
+      o.ctrls_neg = k[3];
+      o.cases = o.cases_pos + o.cases_neg;
+      o.ctrls = o.ctrls_pos + o.ctrls_neg;
+      o.score = obs[(size_t)v];
+      o.n_ge = (int64_t)ge[(size_t)v];
+      o.pvalue = K > 0 ? (double)o.n_ge / (double)K : nan;
+    }
+  }
+  if (!d.ok()) return fail(c, GCRE_ERR_DEVICE, std::string("score_sets_given: ") + hipGetErrorString(d.e));
+  if (std::getenv("GCRE_GIVEN_STATS"))   // (tools/given_time.py)
+    fprintf(stderr, "given entries=%lld launched=%lld slab=%lld slabs=%lld\n", (long long)n_which, (long long)V, (long long)slab,
+            (long long)slabs);
+  if (fam) std::memcpy(family_max, fbits.data(), (size_t)K * 4);
+  return GCRE_OK;
+}
+
+int64_t gcre_given_launches(const gcre_ctx* c) { return c ? c->given_launches : -1; }
 
 // Carrier overlaps of caller-given sets: the validation of gcre_score_sets, the OR of every valid set's
 // members on the host, then k_set_overlap over the `a` list in slabs whose device output stays under GCRE_OVERLAP_SLAB_MB.

@@ -399,6 +399,26 @@ hipError_t launch_set_observed(const int32_t* cnt, int64_t S, int method, const 
                                hipStream_t stream);
 hipError_t launch_set_null(const SetNullArgs& a, int method, hipStream_t stream);
 
+// ---- residual union rows of (set, given set) pairs (gcre_given.hip) ----
+// Entry e: the unions of set which[e] without the carriers of set given[e], in SetNullArgs' row layout, with the counts and
+// totals SetUnion::build gives such rows.
+struct SetResidualArgs {
+  const uint32_t* rows;         // [n_rows][W2] the caller's gene rows as dwords (bits beyond the patients are ignored)
+  const int64_t* set_off;       // [n_sets + 1] the caller's set list as it is
+  const int32_t* members;       // rows of every set; none of a launched entry's sets is NA
+  const int32_t* signs;         // per member +1 / -1, or nullptr = all +1 (read by method 2)
+  const int64_t* which;         // [n] the set of every entry
+  const int64_t* given;         // [n] the set whose carriers are set aside, -1 = none
+  uint32_t* out;                // [n][M][W32p] residual rows: (+) half, then (-) half (method 2); zero beyond the patients
+  int32_t* cnt;                 // [n][4] cases_pos, ctrls_pos, cases_neg, ctrls_neg
+  uint32_t* tot;                // [n][M] carriers per half
+  int64_t n;                    // entries
+  int W2;                       // dwords per gene row
+  int W32p;                     // dwords per half of an output row, >= W2
+  int n_patients, n_cases;
+};
+hipError_t launch_set_residual(const SetResidualArgs& a, int method, hipStream_t stream);
+
 // ---- per-gene best-path tally (gcre_genes.hip) ----
 constexpr int kGeneWidthMax = 3;   // gene slots a path inherits from one operand row, at most
 // One scored stretch of a chunk, as its inspector left it, folded into a join's per-slot table.

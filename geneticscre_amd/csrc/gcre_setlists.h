@@ -51,6 +51,38 @@ inline bool set_is_valid(const gcre_set_input* in, int64_t s) {
   return valid;
 }
 
+// The index lists of gcre_score_sets_given, after the two checks above passed: `which` [n_which] names the sets to score
+// (NULL: 0 .. n_sets - 1, and then n_which must be n_sets), `given` [n_which] the set whose carriers are set aside (-1 or
+// NULL: none), which must not have an NA member; `cap` records are there to be written.
+inline int check_given_index(const gcre_set_input* in, const int64_t* which, const int64_t* given, int64_t n_which,
+                             int64_t cap, const std::string& who, std::string& msg) {
+  const int64_t S = in->n_sets;
+  if (n_which < 0 || (!which && n_which != S)) {
+    msg = who + ": bad index list (a negative length, or NULL `which` with a length other than n_sets)";
+    return GCRE_ERR_ARG;
+  }
+  for (int64_t i = 0; i < n_which; i++) {
+    if (which && (which[i] < 0 || which[i] >= S)) {
+      msg = who + ": which[" + std::to_string(i) + "] = " + std::to_string(which[i]) + " out of range (" + std::to_string(S) + " sets)";
+      return GCRE_ERR_RANGE;
+    }
+    if (given && (given[i] < -1 || given[i] >= S)) {
+      msg = who + ": given[" + std::to_string(i) + "] = " + std::to_string(given[i]) + " out of range (" + std::to_string(S) + " sets, -1 = none)";
+      return GCRE_ERR_RANGE;
+    }
+  }
+  for (int64_t i = 0; given && i < n_which; i++)
+    if (given[i] >= 0 && !set_is_valid(in, given[i])) {
+      msg = who + ": given[" + std::to_string(i) + "] = set " + std::to_string(given[i]) + " has an NA member: its carriers are not known";
+      return GCRE_ERR_ARG;
+    }
+  if (n_which > cap) {
+    msg = who + ": " + std::to_string(n_which) + " entries, room for " + std::to_string(cap) + " records (out of range)";
+    return GCRE_ERR_RANGE;
+  }
+  return GCRE_OK;
+}
+
 // The case / control masks of the n patients (cases are the first n_cases columns), and one set's union rows: P = the OR of
 // its (+) members, N = P + neg_off the OR of its (-) members (`split` off: everything into P, N is not touched), within the
 // n patients -- with k = cases_pos, ctrls_pos, cases_neg, ctrls_neg (NULL: not counted).  `P` (and N) hold W zeroed words at

@@ -1032,10 +1032,65 @@ def _set_clump_columns(out, clump, lead, value, shared) -> None:
     out["SharedControls"] = np.where(is_member, shared[:, 1], np.nan)
 
 
+def residual_rows(sets, rows, signs, which, given, n: int, method: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """gcre_score_sets_given's union rows by their definition, in numpy: (pos, neg, valid), bool [entries][n]
+    twice and bool [entries].  Entry i is set ``which[i]`` (None: every set in order) without the carriers of set
+    ``given[i]`` (-1, or ``given`` None: nothing set aside): pos = the OR of its (+) members, neg of its (-) members (method
+    1, or ``signs`` None: every member into pos), both ``& ~C_given`` with C the OR of ALL members of the given set
+    (``carrier_rows``) -- the given set's own full row, whatever it is given itself.  An entry whose set has an NA member
+    (-1) is not valid and its rows are all False; a given set with an NA member raises ValueError."""
+    d = np.asarray(rows)[:, :n] != 0 if len(rows) else np.zeros((0, n), bool)
+    S = len(sets)
+    C, cvalid = carrier_rows(sets, rows, n)
+    iw = np.arange(S) if which is None else np.asarray(which, np.int64).reshape(-1)
+    ig = np.full(len(iw), -1, np.int64) if given is None else np.asarray(given, np.int64).reshape(-1)
+    if len(ig) != len(iw):
+        raise ValueError(f"given: {len(ig)} entries for {len(iw)} scored sets")
+    pos = np.zeros((len(iw), n), bool)
+    neg = np.zeros((len(iw), n), bool)
+    valid = np.ones(len(iw), bool)
+    for i, (s, g) in enumerate(zip(iw.tolist(), ig.tolist())):
+        if not 0 <= s < S or not -1 <= g < S:
+            raise ValueError(f"entry {i}: set {s} given {g} out of range ({S} sets)")
+        if g >= 0 and not cvalid[g]:
+            raise ValueError(f"entry {i}: the given set {g} has an NA member")
+        members = [int(x) for x in sets[s]]
+        if any(x < 0 for x in members):
+            valid[i] = False
+            continue
+        sg = [1] * len(members) if signs is None else [int(x) for x in signs[s]]
+        for m, x in zip(members, sg):
+            if method == 2 and x == -1:
+                neg[i] |= d[m]
+            else:
+                pos[i] |= d[m]
+        if g >= 0:
+            pos[i] &= ~C[g]
+            neg[i] &= ~C[g]
+    return pos, neg, valid
+
+
+def _set_residual_columns(out, ex, sets, rows, signs, clump, lead) -> None:
+    """``RESIDUAL_COLUMNS`` of a clumped table: every member row rescored without its lead's carriers, all of them in ONE
+    ``JoinExec.score_sets(which=members, given=their leads)`` call on ``ex``.  NaN on leads and -1 rows."""
+    S = len(out)
+    res = {c: np.full(S, np.nan) for c in RESIDUAL_COLUMNS}
+    js = np.flatnonzero((clump >= 0) & (lead != np.arange(S)))
+    if len(js):
+        rec = ex.score_sets(sets, rows, signs, which=js, given=lead[js])
+        res["ResidualScores"][js] = rec["score"]
+        res["ResidualCases"][js] = rec["cases"]
+        res["ResidualControls"][js] = rec["ctrls"]
+        res["ResidualPvalues"][js] = rec["pvalue"]
+    for cname in RESIDUAL_COLUMNS:
+        out[cname] = res[cname]
+
+
 def clump_paths(results_df, genes: Sequence[str], data: np.ndarray, n_cases: int, n_ctrls: int, signed: bool = False,
                 r: float = 0.5, measure: str = "jaccard", patients: str = "all", by_length: bool = False,
                 conditional: bool = False, threshold: float = 0.05, n_permutations: int = 100,
-                strata: Optional[Sequence[int]] = None, seed: int = 0, device: int = 0, on_device: bool = False):
+                strata: Optional[Sequence[int]] = None, seed: int = 0, device: int = 0, on_device: bool = False, *,
+                exec_=None, table: Optional[np.ndarray] = None):
     """Which rows of a GWASPA.Results table are the same finding: rows clumped by the patients that carry them, and with
     ``conditional`` each row rescored without its lead's carriers.  A row's carriers are the patients
     with a variant in any gene of its ``SignedPaths`` (``carrier_rows``); the pairwise shared-carrier counts come from the
@@ -1048,16 +1103,21 @@ def clump_paths(results_df, genes: Sequence[str], data: np.ndarray, n_cases: int
       ``ClumpSize``  rows in the clump (0 for -1), ``LeadOverlap``  the measure against the lead, ``SharedCases`` /
       ``SharedControls``  the carriers shared with the lead (the last three NaN on lead rows and on -1 rows).
 
-    ``conditional``: for every non-lead row, every patient column the lead carries is zeroed in the whole carrier matrix
-    and the row's set is scored on it by ``JoinExec.score_sets`` (method 1: U & ~C_lead; method 2: both halves & ~C_lead;
-    n_cases / n_ctrls unchanged: the removed patients count as non-carriers), on one context with ``api.values_table`` and
-    the masks of ``generate_permutations(seed, strata)``: ``ResidualScores``, ``ResidualCases``, ``ResidualControls`` and
+    ``conditional``: every non-lead row is scored as if every patient column its lead carries were zeroed in the whole
+    carrier matrix (method 1: U & ~C_lead; method 2: both halves & ~C_lead; n_cases / n_ctrls unchanged: the removed
+    patients count as non-carriers) -- all of them in ONE ``JoinExec.score_sets(which=rows, given=their leads)`` call, the
+    residual rows built on the device, on one context with ``api.values_table`` and the masks of
+    ``generate_permutations(seed, strata)``: ``ResidualScores``, ``ResidualCases``, ``ResidualControls`` and
     ``ResidualPvalues``.  ``ResidualPvalues`` is that set's NOMINAL permutation p-value n_ge / n_permutations -- the
     residual score against its own null, not a family-wise number like ``Pvalues``.  NaN on lead rows and on -1 rows.
 
     ``on_device``: the rule runs on the device too -- one ``api.JoinExec.clump_sets`` call per group instead of the
     ``clump_rows`` / ``set_overlap`` loop, no pair count comes back.  Every column is what it is without
-    it; ``conditional`` is host-bound either way."""
+    it.
+
+    ``exec_`` / ``table``: a JoinExec of this method and these patients to run everything on -- with ``conditional`` it must
+    already hold the value table and the masks, and its iterations must be ``n_permutations`` -- or, without one, the value
+    table itself, so that neither is built twice (``seed`` / ``strata`` are then the caller's business)."""
     from . import api
     method = 2 if signed else 1
     genes, data = preprocess_table(genes, data, threshold, n_cases, n_ctrls)
@@ -1075,8 +1135,9 @@ def clump_paths(results_df, genes: Sequence[str], data: np.ndarray, n_cases: int
     lead = np.full(S, -1, np.int64)
     value = np.full(S, np.nan)
     shared = np.full((S, 2), -1, np.int64)
-    res = {c: np.full(S, np.nan) for c in RESIDUAL_COLUMNS}
-    ex = api.JoinExec(method, n_cases, n_ctrls, K, device=device)
+    if exec_ is not None and conditional and exec_.iters != K:
+        raise ValueError(f"exec_: a context of {exec_.iters} permutations, n_permutations = {K}")
+    ex = exec_ if exec_ is not None else api.JoinExec(method, n_cases, n_ctrls, K, device=device)
     try:
         size, _ = ex.set_overlap(sets, sub, a=[], b=[]) if S and not on_device else (np.zeros((0, 2), np.int32), None)
         groups = [np.flatnonzero(ok & (lengths == L)) for L in np.unique(lengths[ok]).tolist()] if by_length \
@@ -1091,27 +1152,16 @@ def clump_paths(results_df, genes: Sequence[str], data: np.ndarray, n_cases: int
                                          patients)
             clump[order], lead[order], value[order], shared[order] = c[order] + base, l[order], v[order], sh[order]
             base += int(c[order].max()) + 1 if len(order) else 0
+        _set_clump_columns(out, clump, lead, value, shared)
         if conditional:
-            ex.set_value_table(api.values_table(n_cases, n_ctrls))
-            if K > 0:
-                ex.generate_permutations(seed, strata)
-            C, _ = carrier_rows(sets, sub, n_cases + n_ctrls)
-            members = (clump >= 0) & (lead != np.arange(S))
-            for ld in np.unique(lead[members]).tolist():   # one score_sets call per lead that has members: host-bound
-                js = np.flatnonzero(members & (lead == ld))
-                need: Dict[int, int] = {}   # the rows these sets use, without the lead's carriers
-                msets = [[need.setdefault(x, len(need)) for x in sets[j]] for j in js]
-                rec = ex.score_sets(msets, np.where(C[ld][None, :], 0, sub[list(need.keys())]), [signs[j] for j in js])
-                res["ResidualScores"][js] = rec["score"]
-                res["ResidualCases"][js] = rec["cases"]
-                res["ResidualControls"][js] = rec["ctrls"]
-                res["ResidualPvalues"][js] = rec["pvalue"]
+            if exec_ is None:
+                ex.set_value_table(api.values_table(n_cases, n_ctrls) if table is None else table)
+                if K > 0:
+                    ex.generate_permutations(seed, strata)
+            _set_residual_columns(out, ex, sets, sub, signs, clump, lead)
     finally:
-        ex.close()
-    _set_clump_columns(out, clump, lead, value, shared)
-    if conditional:
-        for cname in RESIDUAL_COLUMNS:
-            out[cname] = res[cname]
+        if exec_ is None:
+            ex.close()
     return out
 
 
@@ -1329,7 +1379,10 @@ def gwaspa(genes: Sequence[str], data: np.ndarray, n_cases: int, n_ctrls: int, n
     (ties: table position), as ``clump_paths`` walks a table, with r = ``clump``, Jaccard over all patients.  The sets come
     from the hit lists themselves (``hit_sets``: no string is parsed) and the rule runs on the device, in one
     ``api.JoinExec.clump_sets`` call on the run's own context.  A length whose list overflowed contributes
-    no rows, as without it; residual columns for hits are not built.  False, the default: nothing new is called.
+    no rows, as without it.  With ``clump_conditional`` as well it gains ``RESIDUAL_COLUMNS`` too: every member row rescored
+    without its lead's carriers in one ``score_sets(which=, given=)`` call on the run's own context -- its seed, strata and
+    permutation count -- over the hit sets (unsigned) or the sets parsed from ``SignedPaths`` with their
+    signs (signed).  False, the default: nothing new is called.
     """
     from . import api
     from .synth import Problem
@@ -1482,6 +1535,15 @@ def gwaspa(genes: Sequence[str], data: np.ndarray, n_cases: int, n_ctrls: int, n
             order = idx[np.argsort(-sc[idx], kind="stable")]
             c, l, v, sh, _ = ex.clump_sets(hsets, np.vstack([prep.data1, prep.data2]), order, r=clump)
             _set_clump_columns(sig, c, l, v, sh)
+            if clump_conditional:
+                if signed:   # the signs are in the table, not in the hit lists
+                    _, prows, psigns = parse_sets([str(p) for p in sig["SignedPaths"]], genes)
+                    used: Dict[int, int] = {}
+                    rsets = [[-1 if x < 0 else used.setdefault(x, len(used)) for x in rs] for rs in prows]
+                    rsub = np.asarray(data)[list(used.keys())] if used else np.zeros((0, n_cases + n_ctrls), np.int32)
+                    _set_residual_columns(sig, ex, rsets, rsub, psigns, c, l)
+                else:
+                    _set_residual_columns(sig, ex, hsets, np.vstack([prep.data1, prep.data2]), None, c, l)
     if gene_table:
         best = {L + 1: tallies[name].read() for L, name in enumerate(GENE_LEVELS[:path_length])}
         out["gene_best"] = best
@@ -1493,9 +1555,14 @@ def gwaspa(genes: Sequence[str], data: np.ndarray, n_cases: int, n_ctrls: int, n
                               dseed, device, path_length=path_length, exec_=ex, table=table)
         if dec is not None:
             out["Decorated.Pvalues.Results"] = dec
-    ex.close()
     if clump is not None:
-        out["GWASPA.Results"] = clump_paths(out["GWASPA.Results"], genes, data, n_cases, n_ctrls, signed, r=clump,
-                                            conditional=clump_conditional, threshold=threshold,
-                                            n_permutations=n_permutations, strata=strata, seed=seed, device=device)
+        try:
+            out["GWASPA.Results"] = clump_paths(out["GWASPA.Results"], genes, data, n_cases, n_ctrls, signed, r=clump,
+                                                conditional=clump_conditional, threshold=threshold,
+                                                n_permutations=n_permutations, strata=strata, seed=seed, device=device,
+                                                exec_=ex, table=table)
+        finally:
+            ex.close()
+    else:
+        ex.close()
     return out

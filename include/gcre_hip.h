@@ -439,6 +439,27 @@ typedef struct {
 int gcre_score_sets(gcre_ctx* ctx, const gcre_set_input* in, gcre_set_score* out, int64_t cap, int64_t* n_out,
                     float* family_max);
 
+/* Conditional (residual) set scores: many (set, given set) pairs in one call.  Entry i scores set
+ * s = which[i] with the carriers of set g = given[i] set aside: with P_s, N_s the unions gcre_score_sets defines (method 1:
+ * U_s alone) and C_g the carrier row gcre_set_overlap defines -- the OR of ALL members of g, whatever their signs and the
+ * method, bits >= n_cols ignored; g's own full row, never a residual itself -- the entry is scored as gcre_score_sets scores
+ * a set whose unions are P_s & ~C_g and N_s & ~C_g: counts, observed score, n_ge and pvalue against all `iterations` masks.
+ * n_cases / n_ctrls are unchanged: the removed patients count as non-carriers.  The rows are built on the device
+ * (k_set_residual) from the gene rows and the set list, uploaded once.
+ * which [n_which]: repeats allowed (leave-one-gene-out: one entry per gene, the one-gene set as the given set); NULL =
+ * 0 .. n_sets-1, and then n_which must be n_sets.  given [n_which]: -1 = nothing set aside; NULL = all -1; given[i] ==
+ * which[i] is allowed (an empty residual).  out[i].set = which[i], *n_out = n_which.  An entry whose set has an NA member
+ * gets valid = 0 as in gcre_score_sets.  family_max, optional [iterations]: the maximum of null_r over the valid entries
+ * (all zeros without one).  The entries are walked in slabs of GCRE_GIVEN_SLAB_SETS (environment, read per call; default:
+ * what fits in 1 GiB of device rows); the results do not depend on it.
+ * Errors, nothing launched: everything gcre_score_sets refuses of the context and the set list; GCRE_ERR_RANGE -- a `which`
+ * entry outside 0 .. n_sets-1, a `given` entry outside -1 .. n_sets-1, n_which > cap; GCRE_ERR_ARG -- a `given` entry naming
+ * a set with an NA member, n_which < 0, NULL `which` with n_which != n_sets.  n_which == 0 returns at once. */
+int gcre_score_sets_given(gcre_ctx* ctx, const gcre_set_input* in, const int64_t* which, const int64_t* given,
+                          int64_t n_which, gcre_set_score* out, int64_t cap, int64_t* n_out, float* family_max);
+/* kernels launched by gcre_score_sets_given on the context since gcre_create (tests: a refusal launches nothing). */
+int64_t gcre_given_launches(const gcre_ctx* ctx);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Carrier overlaps of caller-given sets: which sets are carried by the same patients.  No reference
  * counterpart.

@@ -16,7 +16,7 @@ Per shape one JSON line:
                 against all `b` rows, checked against the device, and SCALED to all rows: host_ms_rows * sets / H
 Then report.clump_paths on a 1,000-row table over the small shape (paths through three strong genes and their
 neighbours), with and without `conditional` (1,000 permutations): wall time, leads, leads with members, and the share of
-the conditional call spent inside JoinExec.score_sets (one call per lead with members: host-bound, not a kernel) and
+the conditional call spent inside JoinExec.score_sets (one call over all member rows) and
 inside api.values_table (the value table of the call's one context).
 """
 from __future__ import annotations
