@@ -132,6 +132,7 @@ EXPORTS = [
     "gcre_score_sets_given", "gcre_given_launches",
     "gcre_set_overlap", "gcre_overlap_launches",
     "gcre_clump_sets", "gcre_clump_launches",
+    "gcre_set_patient_counts", "gcre_patient_launches",
     "gcre_gene_tally_create", "gcre_join_set_tally", "gcre_process_paths_set_tally", "gcre_gene_tally_read",
     "gcre_gene_tally_free",
     "gcre_exceed_create", "gcre_join_set_exceed", "gcre_process_paths_set_exceed", "gcre_exceed_read",
@@ -260,6 +261,9 @@ _FEATURES = {
     "clump": ("overlap", ["gcre_clump_sets", "gcre_clump_launches"], "device-side clumping (gcre_clump_sets)", {
         "gcre_clump_sets": (_I, [_V, ctypes.POINTER(gcre_set_input), _P, _I64, ctypes.c_double, _I, _I, _P, _P, _P, _P, _P]),
         "gcre_clump_launches": (_I64, [_V])}),
+    "patients": (None, ["gcre_set_patient_counts", "gcre_patient_launches"], "carrier tallies per patient (gcre_set_patient_counts)", {
+        "gcre_set_patient_counts": (_I, [_V, ctypes.POINTER(gcre_set_input), _P, _I64, _P, _I32, _I, _P, _P, ctypes.POINTER(_I64)]),
+        "gcre_patient_launches": (_I64, [_V])}),
     "genes": (None, ["gcre_gene_tally_create"], "per-gene best-path tally (gcre_gene_tally_create)", {
         "gcre_gene_tally_create": (_V, [_V, _I32, _P, _I64, _I32, _P, _I64, _I32]),
         "gcre_join_set_tally": (_I, [_V, _V]),
@@ -312,6 +316,7 @@ _sets_lib = functools.partial(_feature_lib, "sets")
 _given_lib = functools.partial(_feature_lib, "given")
 _overlap_lib = functools.partial(_feature_lib, "overlap")
 _clump_lib = functools.partial(_feature_lib, "clump")
+_patients_lib = functools.partial(_feature_lib, "patients")
 _genes_lib = functools.partial(_feature_lib, "genes")
 _exceed_lib = functools.partial(_feature_lib, "exceed")
 _perm_counts_lib = functools.partial(_feature_lib, "perm_counts")
@@ -583,6 +588,33 @@ def _set_input(sets, rows, signs, n: int):
     packed = pack_carriers(d, d.shape[1])
     inp = gcre_set_input(S, _ptr(off), _ptr(members), _ptr(sg), _ptr(packed), packed.shape[0], d.shape[1])
     return inp, (off, members, sg, packed)
+
+
+def _set_lists(sets, signs):
+    """(S, off, members, signs) as the set entries take them -- int64 [S + 1] offsets into int32 members, int32 signs or None
+    -- from one sequence of rows per set with one sequence of signs per set, or from an ``(off, members)`` pair (what
+    ``report.hit_sets`` returns) with one flat signs array.  ValueError where the signs do not match the members."""
+    if isinstance(sets, tuple) and len(sets) == 2 and isinstance(sets[0], np.ndarray):
+        off = np.ascontiguousarray(sets[0], dtype=np.int64)
+        members = np.ascontiguousarray(sets[1], dtype=np.int32)
+        S = len(off) - 1
+        sg = None if signs is None else np.ascontiguousarray(np.asarray(signs, dtype=np.int64).reshape(-1), dtype=np.int32)
+        if sg is not None and len(sg) != len(members):
+            raise ValueError("signs: one sign per member of every set")
+    else:
+        S = len(sets)
+        lens = [len(s) for s in sets]
+        off = np.zeros(S + 1, dtype=np.int64)
+        off[1:] = np.cumsum(lens)
+        members = np.ascontiguousarray(np.concatenate([np.asarray(s, dtype=np.int64).reshape(-1) for s in sets])
+                                       if S else np.zeros(0), dtype=np.int32)
+        sg = None
+        if signs is not None:
+            if len(signs) != S or any(len(x) != L for x, L in zip(signs, lens)):
+                raise ValueError("signs: one sign per member of every set")
+            sg = np.ascontiguousarray(np.concatenate([np.asarray(x, dtype=np.int64).reshape(-1) for x in signs])
+                                      if S else np.zeros(0), dtype=np.int32)
+    return S, off, members, sg
 
 
 def pack_carriers(rows, n_cols: int) -> np.ndarray:
@@ -927,26 +959,7 @@ class JoinExec:
         return (rec, fam) if family else rec
 
     def _score_sets_given(self, sets, rows, signs, family, given, which):
-        if isinstance(sets, tuple) and len(sets) == 2 and isinstance(sets[0], np.ndarray):
-            off = np.ascontiguousarray(sets[0], dtype=np.int64)
-            members = np.ascontiguousarray(sets[1], dtype=np.int32)
-            S = len(off) - 1
-            sg = None if signs is None else np.ascontiguousarray(np.asarray(signs, dtype=np.int64).reshape(-1), dtype=np.int32)
-            if sg is not None and len(sg) != len(members):
-                raise ValueError("signs: one sign per member of every set")
-        else:
-            S = len(sets)
-            lens = [len(s) for s in sets]
-            off = np.zeros(S + 1, dtype=np.int64)
-            off[1:] = np.cumsum(lens)
-            members = np.ascontiguousarray(np.concatenate([np.asarray(s, dtype=np.int64).reshape(-1) for s in sets])
-                                           if S else np.zeros(0), dtype=np.int32)
-            sg = None
-            if signs is not None:
-                if len(signs) != S or any(len(x) != L for x, L in zip(signs, lens)):
-                    raise ValueError("signs: one sign per member of every set")
-                sg = np.ascontiguousarray(np.concatenate([np.asarray(x, dtype=np.int64).reshape(-1) for x in signs])
-                                          if S else np.zeros(0), dtype=np.int32)
+        S, off, members, sg = _set_lists(sets, signs)
         iw = None if which is None else np.ascontiguousarray(np.asarray(which, dtype=np.int64).reshape(-1))
         ig = None if given is None else np.ascontiguousarray(np.asarray(given, dtype=np.int64).reshape(-1))
         E = S if iw is None else len(iw)
@@ -1062,6 +1075,59 @@ class JoinExec:
     def clump_launches(self) -> int:
         """Kernels gcre_clump_sets launched on this context so far."""
         return int(_clump_lib().gcre_clump_launches(self._h))
+
+    def patient_counts(self, sets, rows, which=None, group=None, n_groups=None, by_sign: bool = False, signs=None):
+        """How many of the listed sets each patient carries (gcre_set_patient_counts): exact counts,
+        descriptive only -- no test statistic, and the carriers of sets selected on the case / control labels are enriched
+        in cases by construction.  ``sets``: one sequence of row indices of the 0/1 matrix ``rows`` per set (-1 = NA
+        gene), or a pair ``(off, members)`` as ``clump_sets`` takes it (``signs`` then one flat array); ``which``: the sets
+        to count, repeats allowed and counted as often (None: every set once); ``group``: per entry 0 .. n_groups - 1, or
+        -1 = not counted (None: all in group 0); ``n_groups``: None = 1 without ``group``, max(group) + 1 (at least 1) with
+        it.  ``by_sign`` False: one plane, the carrier row of ``set_overlap`` (the OR of all members); True: two planes,
+        the OR of the +1 members and the OR of the -1 members of ``signs`` (as ``score_sets`` takes them; None: all +1),
+        whatever the context's method.  Returns ``(counts, group_sets, skipped)``: int32 [n_groups][1 + by_sign][n],
+        int64 [n_groups] the entries counted into every group, and the number of entries with a group whose set has an NA
+        member (counted nowhere).  An index out of range, ``group`` of another length than the entries, or a wrong signs
+        shape raise ValueError before the library is touched; the library's refusals raise GcreError."""
+        S, off, members, sg = _set_lists(sets, signs)
+        iw = None if which is None else np.ascontiguousarray(np.asarray(which, dtype=np.int64).reshape(-1))
+        ig = None if group is None else np.ascontiguousarray(np.asarray(group, dtype=np.int64).reshape(-1))
+        E = S if iw is None else len(iw)
+        if iw is not None and len(iw) and (iw.min() < 0 or iw.max() >= S):
+            raise ValueError(f"which: a set index outside 0..{S - 1}")
+        if ig is not None and len(ig) != E:
+            raise ValueError(f"group: {len(ig)} entries for {E} counted sets (one per entry of which, or per set)")
+        if n_groups is None:
+            n_groups = 1 if ig is None or not len(ig) else max(int(ig.max()) + 1, 1)
+        G = int(n_groups)
+        if G < 1:
+            raise ValueError(f"n_groups must be at least 1, not {n_groups!r}")
+        if ig is None and G != 1:
+            raise ValueError(f"group: None puts every entry in group 0, so n_groups must be 1, not {G}")
+        if ig is not None and len(ig) and (ig.min() < -1 or ig.max() >= G):
+            raise ValueError(f"group: a group outside -1..{G - 1}")
+        lib = _patients_lib()
+        n = self.num_cases + self.num_ctrls
+        d = np.asarray(rows)
+        if d.ndim != 2:
+            d = d.reshape(-1, n)
+        packed = pack_carriers(d, d.shape[1])
+        inp = gcre_set_input(S, _ptr(off), _ptr(members), _ptr(sg), _ptr(packed), packed.shape[0], d.shape[1])
+        ig32 = None if ig is None else np.ascontiguousarray(ig, dtype=np.int32)
+        H = 2 if by_sign else 1
+        counts = np.zeros((G, H, d.shape[1]), dtype=np.int32)
+        group_sets = np.zeros(G, dtype=np.int64)
+        skipped = ctypes.c_int64(0)
+        rc = lib.gcre_set_patient_counts(self._h, ctypes.byref(inp), _ptr(iw), E, _ptr(ig32), G, 1 if by_sign else 0,
+                                         _ptr(counts), _ptr(group_sets), ctypes.byref(skipped))
+        if rc != GCRE_OK:
+            raise GcreError(self._lib.gcre_last_error(self._h).decode())
+        return counts, group_sets, int(skipped.value)
+
+    @property
+    def patient_launches(self) -> int:
+        """Kernels gcre_set_patient_counts launched on this context so far."""
+        return int(_patients_lib().gcre_patient_launches(self._h))
 
     def stepdown_launches(self) -> int:
         """k_stepdown_null / k_stepdown_finish launches of this context so far."""

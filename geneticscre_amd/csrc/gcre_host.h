@@ -348,6 +348,7 @@ struct gcre_ctx {
   int64_t stepdown_launches = 0;     // k_stepdown_null / k_stepdown_finish launches of this context (gcre_stepdown_launches)
   int64_t clump_launches = 0;        // kernels gcre_clump_sets launched on this context (gcre_clump_launches)
   int64_t given_launches = 0;        // kernels gcre_score_sets_given launched on this context (gcre_given_launches)
+  int64_t patient_launches = 0;      // kernels gcre_set_patient_counts launched on this context (gcre_patient_launches)
 
   // resident inputs
   uint64_t* d_case_mask = nullptr;   // [Wp]

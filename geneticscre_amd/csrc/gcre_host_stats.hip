@@ -1,6 +1,6 @@
 // gcre_host_stats.hip -- the entry points of include/gcre_hip.h that use a context but not the join driver: generated
 // permutation masks, decorated p-values (gcre_decorated.hip), set scores (gcre_sets.hip, conditional: gcre_given.hip) and carrier overlaps
-// (gcre_overlap.hip) and greedy clumps (gcre_clump.hip), and the per-gene tally (gcre_genes.hip), the null exceedance counts (gcre_exceed.hip,
+// (gcre_overlap.hip), greedy clumps (gcre_clump.hip) and carrier tallies per patient (gcre_patients.hip), and the per-gene tally (gcre_genes.hip), the null exceedance counts (gcre_exceed.hip,
 // gcre_stepdown.hip) and the hit lists (gcre_hits.hip) as objects.  What a join does with an armed tally, armed counts or
 // an armed list -- check_tally, fold_genes, count_exceed, collect_hits -- is in gcre_host.hip.  Host code only.
 #include "gcre_host.h"
@@ -658,6 +658,134 @@ int gcre_clump_sets(gcre_ctx* c, const gcre_set_input* in, const int64_t* order,
 }
 
 int64_t gcre_clump_launches(const gcre_ctx* c) { return c ? c->clump_launches : -1; }
+
+// Carrier tallies per patient: the validation of gcre_set_overlap, then the kept entries -- group >= 0,
+// no NA member -- counting-sorted by group into a member table and cut into segments of one group each; gene rows, table
+// and segments go up once, k_set_patient_counts adds into zeroed cells, which come back as they are (a count is below
+// n_which < 2^31).
+int gcre_set_patient_counts(gcre_ctx* c, const gcre_set_input* in, const int64_t* which, int64_t n_which, const int32_t* group,
+                            int32_t n_groups, int by_sign, int32_t* counts, int64_t* group_sets, int64_t* skipped) {
+  if (!c) return GCRE_ERR_ARG;
+  if (!in) return fail(c, GCRE_ERR_ARG, "set_patient_counts: NULL argument");
+  const Geometry& g = c->g;
+  const std::string who = "set_patient_counts";
+  std::string msg;
+  if (int rc = check_set_shape(in, g.n, who, msg)) return fail(c, rc, msg);
+  if (int rc = check_set_members(in, who, msg)) return fail(c, rc, msg);
+  if (int rc = check_patient_index(in, which, n_which, group, n_groups, by_sign, counts != nullptr, patient_max_mb(), who, msg))
+    return fail(c, rc, msg);
+  if (by_sign && in->n_rows > (int64_t)kPatientNegBit)
+    return fail(c, GCRE_ERR_ARG, who + ": too many gene rows for by_sign (the sign travels in bit 30 of a member)");
+  const auto t_begin = std::chrono::steady_clock::now();
+  const int H = 1 + by_sign, W = g.W;
+  const size_t n_cells = (size_t)n_groups * (size_t)H * (size_t)g.n;
+  std::memset(counts, 0, n_cells * sizeof(int32_t));
+  if (group_sets) std::memset(group_sets, 0, (size_t)n_groups * sizeof(int64_t));
+  if (skipped) *skipped = 0;
+
+  // the kept entries, counting-sorted by group (stable): at[g] = where group g's run begins
+  const int64_t S = in->n_sets;
+  std::vector<unsigned char> valid((size_t)S);
+  for (int64_t s = 0; s < S; s++) valid[(size_t)s] = set_is_valid(in, s);
+  std::vector<int64_t> at((size_t)n_groups + 1, 0);
+  int64_t n_skipped = 0, M = 1;
+  for (int64_t i = 0; i < n_which; i++) {
+    const int32_t gi = group ? group[i] : 0;
+    if (gi < 0) continue;
+    const int64_t s = which ? which[i] : i;
+    if (!valid[(size_t)s]) {
+      n_skipped++;
+      continue;
+    }
+    at[(size_t)gi + 1]++;
+    M = std::max(M, in->set_off[s + 1] - in->set_off[s]);
+  }
+  if (skipped) *skipped = n_skipped;
+  for (int32_t k = 0; k < n_groups; k++) {
+    if (group_sets) group_sets[k] = at[(size_t)k + 1];
+    at[(size_t)k + 1] += at[(size_t)k];
+  }
+  const int64_t n = at[(size_t)n_groups];
+  if (n == 0 || g.n == 0) return GCRE_OK;
+  if (M > 0x7fffffff / 4 || (double)n * (double)M * 4.0 > patient_max_mb() * 1048576.0)
+    return fail(c, GCRE_ERR_ARG, who + ": the member table of " + std::to_string(n) + " entries x " + std::to_string(M) +
+                                     " members exceeds GCRE_PATIENT_MAX_MB");
+
+  // the member table [M][n] in sorted order -- member m of every entry side by side, which the kernel reads 16 entries at a
+  // time -- with -1 behind a set's last member; by_sign: bit 30 marks a (-) member
+  std::vector<int32_t> table((size_t)n * (size_t)M, -1), width((size_t)n);
+  {
+    std::vector<int64_t> next(at.begin(), at.end() - 1);
+    for (int64_t i = 0; i < n_which; i++) {
+      const int32_t gi = group ? group[i] : 0;
+      const int64_t s = which ? which[i] : i;
+      if (gi < 0 || !valid[(size_t)s]) continue;
+      const int64_t pos = next[(size_t)gi]++, b = in->set_off[s], e = in->set_off[s + 1];
+      for (int64_t k = b; k < e; k++)
+        table[(size_t)(k - b) * (size_t)n + (size_t)pos] = in->members[k] | (by_sign && in->signs && in->signs[k] == -1 ? kPatientNegBit : 0);
+      width[(size_t)pos] = (int32_t)(e - b);
+    }
+  }
+  // segments: every group's run in pieces of at most GCRE_PATIENT_SEG entries; by default as many as spread the (segment,
+  // tile) pairs over about 4,096 waves, between 64 (a flush per segment is 32 atomic instructions) and 1,024
+  const int64_t tiles = (g.n + kPatientTile - 1) / kPatientTile;
+  int64_t seg = std::min<int64_t>(std::max<int64_t>((n * tiles + 4095) / 4096, 64), 1024);
+  if (const char* e = std::getenv("GCRE_PATIENT_SEG")) seg = std::min<int64_t>(std::max<int64_t>(std::atoll(e), 1), (int64_t)1 << 30);
+  std::vector<PatientSeg> segs;
+  for (int32_t k = 0; k < n_groups; k++)
+    for (int64_t b = at[(size_t)k]; b < at[(size_t)k + 1]; b += seg) {
+      PatientSeg sg{};
+      sg.begin = (int32_t)b;
+      sg.count = (int32_t)std::min(seg, at[(size_t)k + 1] - b);
+      sg.group = k;
+      sg.width = *std::max_element(width.begin() + b, width.begin() + b + sg.count);
+      segs.push_back(sg);
+    }
+
+  // GCRE_PATIENT_STATS (tools/patients_time.py): one line on stderr, with the stages timed between extra synchronisations
+  const bool stats = std::getenv("GCRE_PATIENT_STATS") != nullptr;
+  const auto now = [] { return std::chrono::steady_clock::now(); };
+  const auto ms = [](std::chrono::steady_clock::time_point t0, std::chrono::steady_clock::time_point t1) {
+    return std::chrono::duration<double, std::milli>(t1 - t0).count();
+  };
+  const auto t_host = now();
+  (void)hipSetDevice(c->device);
+  DevScratch d(c->stream);
+  PatientCountArgs a{};
+  a.rows = (const uint32_t*)d.put(in->rows, std::max<size_t>((size_t)in->n_rows * (size_t)W, 1));
+  a.members = d.put(table.data(), table.size());
+  a.segs = d.put(segs.data(), segs.size());
+  a.cells = d.take<uint32_t>(n_cells);
+  a.n = n;
+  a.nseg = (int64_t)segs.size();
+  a.M = (int)M;
+  a.W2 = 2 * W;
+  a.n_patients = g.n;
+  a.H = H;
+  d.zero(a.cells, n_cells);
+  if (stats) d.sync();
+  const auto t_up = now();
+  if (d.ok()) {
+    d.e = launch_set_patient_counts(a, c->stream);
+    if (d.ok()) c->patient_launches++;
+  }
+  d.download((uint32_t*)counts, a.cells, n_cells);
+  d.sync();
+  d.release();
+  if (!d.ok()) {
+    (void)hipGetLastError();
+    std::memset(counts, 0, n_cells * sizeof(int32_t));
+    return fail(c, GCRE_ERR_DEVICE, who + ": " + hipGetErrorString(d.e));
+  }
+  if (stats)
+    fprintf(stderr, "patients entries=%lld members=%lld segments=%lld groups=%d planes=%d upload_bytes=%lld host_ms=%.3f upload_ms=%.3f "
+                    "kernel_download_ms=%.3f\n", (long long)n, (long long)M, (long long)segs.size(), n_groups, H,
+            (long long)((size_t)in->n_rows * (size_t)W * 8 + table.size() * 4 + segs.size() * sizeof(PatientSeg)), ms(t_begin, t_host),
+            ms(t_host, t_up), ms(t_up, now()));
+  return GCRE_OK;
+}
+
+int64_t gcre_patient_launches(const gcre_ctx* c) { return c ? c->patient_launches : -1; }
 
 // ---- per-gene best-path tally ----
 gcre_gene_tally* gcre_gene_tally_create(gcre_ctx* c, int32_t n_slots, const int32_t* genes0, int64_t n_rows0, int32_t w0,

@@ -602,4 +602,27 @@ hipError_t launch_clump_union(const ClumpArgs& a, const ClumpUnionArgs& u, hipSt
 // one round: k_clump_leads, then k_clump_assign over the tiles from `tile0` on (positions below 64 * tile0 are assigned)
 hipError_t launch_clump_round(const ClumpArgs& a, int64_t tile0, hipStream_t stream);
 
+// ---- carrier tallies per patient (gcre_patients.hip) ----
+// The kept entries are sorted by group and cut into segments of one group each.  One wave adds a segment's carrier rows
+// up over one tile of kPatientTile patients in bit-sliced counters of kPatientPlanes planes (gcre_bitslice.h) and flushes
+// them into the group's 32-bit cells before they can overflow: after at most 2^kPatientPlanes - 1 entries.
+constexpr int kPatientPlanes = 12;
+constexpr int kPatientTile = 2048;                   // patients per wave: one dword column per lane
+constexpr int32_t kPatientNegBit = 1 << 30;          // by_sign: set on a table entry whose member has sign -1
+struct PatientSeg {
+  int32_t begin, count;             // entries [begin, begin + count) of the table
+  int32_t group;
+  int32_t width;                    // the most members of one of its entries, <= M: the member columns the wave reads
+};
+struct PatientCountArgs {
+  const uint32_t* rows;             // [n_rows][W2] the caller's gene rows as dwords (bits beyond the patients are ignored)
+  const int32_t* members;           // [M][n] member m of every kept entry's set, -1 = no further member (read-only: scalar loads)
+  const PatientSeg* segs;           // [nseg] (read-only)
+  uint32_t* cells;                  // [n_groups][H][n_patients], zeroed
+  int64_t n, nseg;                  // kept entries, segments
+  int M, W2, n_patients;
+  int H;                            // 1: all members into one plane; 2: the (+) members, then the (-) members
+};
+hipError_t launch_set_patient_counts(const PatientCountArgs& a, hipStream_t stream);
+
 }  // namespace gcre

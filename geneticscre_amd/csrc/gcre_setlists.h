@@ -1,9 +1,12 @@
 // gcre_setlists.h -- the host stage that gcre_score_sets, gcre_set_overlap and gcre_exceed_stepdown share (gcre_host_stats.hip):
 // what they refuse of a caller's set list, and the union rows and counts of one set.  Plain C++17 over include/gcre_hip.h, no
-// HIP: tests/native/setlists_main.cpp drives it on a machine without a GPU.
+// HIP: tests/native/setlists_main.cpp drives it on a machine without a GPU (given_main.cpp and patients_main.cpp: the index
+// checks of gcre_score_sets_given and gcre_set_patient_counts).
 #pragma once
 #include "../../include/gcre_hip.h"
 
+#include <algorithm>
+#include <cstdlib>
 #include <string>
 #include <vector>
 
@@ -81,6 +84,54 @@ inline int check_given_index(const gcre_set_input* in, const int64_t* which, con
     return GCRE_ERR_RANGE;
   }
   return GCRE_OK;
+}
+
+// GCRE_PATIENT_MAX_MB: the bound on the count cells (and on the member table) gcre_set_patient_counts holds on the device,
+// read per call (tests set fractions); default 1024
+inline double patient_max_mb() {
+  double mb = 1024;
+  if (const char* e = std::getenv("GCRE_PATIENT_MAX_MB")) mb = std::min(std::max(std::atof(e), 0.0), 65536.0);
+  return mb;
+}
+
+// What gcre_set_patient_counts refuses of its own arguments, after the two checks above passed: `which` [n_which] names the
+// sets to count (NULL: 0 .. n_sets - 1, and then n_which must be n_sets), `group` [n_which] the group of every entry (-1:
+// not counted; NULL: group 0, and then n_groups must be 1); H = 1 + by_sign planes of n_cols int32 cells per group against
+// `max_mb`.  Fewer than 2^31 - 16 entries, so that a 32-bit cell cannot overflow.
+inline int check_patient_index(const gcre_set_input* in, const int64_t* which, int64_t n_which, const int32_t* group,
+                               int32_t n_groups, int by_sign, bool have_counts, double max_mb, const std::string& who,
+                               std::string& msg) {
+  const int64_t S = in->n_sets;
+  if (by_sign != 0 && by_sign != 1)
+    msg = who + ": by_sign must be 0 or 1, not " + std::to_string(by_sign);
+  else if (n_groups < 1)
+    msg = who + ": n_groups must be at least 1, not " + std::to_string(n_groups);
+  else if (n_which < 0 || (!which && n_which != S))
+    msg = who + ": bad index list (a negative length, or NULL `which` with a length other than n_sets)";
+  else if (!group && n_groups != 1)
+    msg = who + ": NULL `group` puts every entry in group 0: n_groups must be 1, not " + std::to_string(n_groups);
+  else if (!have_counts)
+    msg = who + ": NULL counts";
+  else if (n_which >= 0x7fffffff - 16)
+    msg = who + ": " + std::to_string(n_which) + " entries: a 32-bit count could overflow (fewer than 2^31 - 16)";
+  else if ((double)n_groups * (double)(1 + by_sign) * (double)in->n_cols * 4.0 > max_mb * 1048576.0)
+    msg = who + ": " + std::to_string(n_groups) + " groups x " + std::to_string(1 + by_sign) + " planes x " +
+          std::to_string(in->n_cols) + " patients x 4 bytes exceed GCRE_PATIENT_MAX_MB = " + std::to_string(max_mb);
+  else {
+    for (int64_t i = 0; i < n_which; i++) {
+      if (which && (which[i] < 0 || which[i] >= S)) {
+        msg = who + ": which[" + std::to_string(i) + "] = " + std::to_string(which[i]) + " out of range (" + std::to_string(S) + " sets)";
+        return GCRE_ERR_RANGE;
+      }
+      if (group && (group[i] < -1 || group[i] >= n_groups)) {
+        msg = who + ": group[" + std::to_string(i) + "] = " + std::to_string(group[i]) + " out of range (" + std::to_string(n_groups) +
+              " groups, -1 = not counted)";
+        return GCRE_ERR_RANGE;
+      }
+    }
+    return GCRE_OK;
+  }
+  return GCRE_ERR_ARG;
 }
 
 // The case / control masks of the n patients (cases are the first n_cases columns), and one set's union rows: P = the OR of

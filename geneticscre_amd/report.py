@@ -21,6 +21,9 @@
                          same patients: pairwise carrier overlaps on the device (gcre_set_overlap), greedy clumping against
                          lead rows, and each row rescored without its lead's carriers (beyond the reference)
 
+  * ``patient_counts_reference`` / ``patient_table``  who carries the findings: how many of a list of sets every patient
+                         carries, per group of sets (gcre_set_patient_counts; beyond the reference)
+
 Host-side post-processing of <= top_k x 5 rows: string work, nothing here touches the scored path.
 """
 from __future__ import annotations
@@ -1070,6 +1073,109 @@ def residual_rows(sets, rows, signs, which, given, n: int, method: int) -> Tuple
     return pos, neg, valid
 
 
+def _set_lists(sets, signs):
+    """``sets`` as a list of member lists and ``signs`` as a list of sign lists (or None), from either form the set entries
+    of ``api.JoinExec`` take: sequences per set, or ``(off, members)`` with one flat signs array."""
+    if isinstance(sets, tuple) and len(sets) == 2 and isinstance(sets[0], np.ndarray):
+        off = np.asarray(sets[0], np.int64)
+        members = np.asarray(sets[1], np.int64)
+        flat = None if signs is None else np.asarray(signs, np.int64).reshape(-1)
+        if flat is not None and len(flat) != len(members):
+            raise ValueError("signs: one sign per member of every set")
+        return ([members[off[s]:off[s + 1]].tolist() for s in range(len(off) - 1)],
+                None if flat is None else [flat[off[s]:off[s + 1]].tolist() for s in range(len(off) - 1)])
+    lists = [[int(x) for x in m] for m in sets]
+    if signs is None:
+        return lists, None
+    sg = [[int(x) for x in m] for m in signs]
+    if len(sg) != len(lists) or any(len(a) != len(b) for a, b in zip(sg, lists)):
+        raise ValueError("signs: one sign per member of every set")
+    return lists, sg
+
+
+def patient_counts_reference(sets, rows, signs, which, group, n_groups, n: int, by_sign) -> Tuple[np.ndarray, np.ndarray, int]:
+    """gcre_set_patient_counts by its definition, in numpy: ``(counts, group_sets, skipped)``.  Entry i is
+    set ``which[i]`` (None: every set once; a set listed twice is counted twice) in group ``group[i]`` (-1: not counted;
+    None: group 0).  counts int32 [n_groups][H][n], H = 1 + by_sign: the carrier rows of the entries of a group, added up
+    per patient -- plane 0 the OR of ALL members (``carrier_rows``) without ``by_sign``; with it plane 0 the OR of the +1
+    members and plane 1 of the -1 members of ``signs`` (None: all +1), no conflict removal.  An entry with a group whose
+    set has an NA member (-1) is counted nowhere but in ``skipped``; group_sets int64 [n_groups] = the entries counted.
+    Columns of ``rows`` beyond ``n`` are not patients.  ``n_groups`` None: 1 without ``group``, max(group) + 1 with it."""
+    lists, sg = _set_lists(sets, signs)
+    d = np.asarray(rows)[:, :n] != 0 if len(rows) else np.zeros((0, n), bool)
+    S = len(lists)
+    iw = np.arange(S) if which is None else np.asarray(which, np.int64).reshape(-1)
+    ig = np.zeros(len(iw), np.int64) if group is None else np.asarray(group, np.int64).reshape(-1)
+    if len(ig) != len(iw):
+        raise ValueError(f"group: {len(ig)} entries for {len(iw)} counted sets")
+    G = (max(int(ig.max()) + 1, 1) if len(ig) else 1) if n_groups is None else int(n_groups)
+    if G < 1 or (group is None and G != 1):
+        raise ValueError(f"n_groups = {G}: at least 1, and 1 without group")
+    H = 2 if by_sign else 1
+    counts = np.zeros((G, H, n), np.int64)
+    group_sets = np.zeros(G, np.int64)
+    skipped = 0
+    for i, (s, g) in enumerate(zip(iw.tolist(), ig.tolist())):
+        if not 0 <= s < S or not -1 <= g < G:
+            raise ValueError(f"entry {i}: set {s} in group {g} out of range ({S} sets, {G} groups)")
+        if g < 0:
+            continue
+        if any(x < 0 for x in lists[s]):
+            skipped += 1
+            continue
+        group_sets[g] += 1
+        planes = np.zeros((H, n), bool)
+        for k, x in enumerate(lists[s]):
+            planes[1 if by_sign and sg is not None and sg[s][k] == -1 else 0] |= d[x]
+        counts[g] += planes
+    return counts.astype(np.int32), group_sets, skipped
+
+
+PATIENT_COLUMNS = ["Patient", "Label", "Hits", "HitShare"]   # the group columns stand between Label and Hits
+
+
+def patient_table(counts, n_cases: int, names=None, columns=None, group_sets=None, summed=None):
+    """One row per patient, in patient order, from the counts of ``JoinExec.patient_counts`` / ``patient_counts_reference``
+    (int [n_groups][1][n], or [n_groups][n]; the two planes of ``by_sign`` are not one tally and raise ValueError):
+    "Patient" (the index, or ``names[q]``), "Label" ("case" for the first ``n_cases`` patients, "control" after them), one
+    count column per group (``columns``; default "Group0", "Group1", ..), "Hits" -- the sum of the first ``summed`` group
+    columns (None: all of them) -- and "HitShare" = Hits over the number of sets counted into those groups
+    (``group_sets``; NaN without it or where that number is 0).  Descriptive: no p-value is attached, and the carriers of
+    sets that were selected on the labels are enriched in cases by construction."""
+    import pandas as pd
+
+    c = np.asarray(counts)
+    if c.ndim == 3:
+        if c.shape[1] != 1:
+            raise ValueError(f"patient_table: {c.shape[1]} planes (by_sign) are not one tally: pass one plane")
+        c = c[:, 0, :]
+    if c.ndim != 2:
+        raise ValueError("patient_table: counts [n_groups][n] or [n_groups][1][n]")
+    G, n = c.shape
+    cols = [f"Group{g}" for g in range(G)] if columns is None else [str(x) for x in columns]
+    if len(cols) != G or len(set(cols)) != G or set(cols) & set(PATIENT_COLUMNS):
+        raise ValueError(f"patient_table: {G} distinct column names, none of {PATIENT_COLUMNS}")
+    if not 0 <= int(n_cases) <= n:
+        raise ValueError(f"patient_table: n_cases = {n_cases} of {n} patients")
+    if names is not None and len(names) != n:
+        raise ValueError(f"patient_table: {len(names)} names for {n} patients")
+    k = G if summed is None else int(summed)
+    if not 0 <= k <= G:
+        raise ValueError(f"patient_table: summed = {summed} of {G} groups")
+    out = {"Patient": list(names) if names is not None else np.arange(n, dtype=np.int64),
+           "Label": np.where(np.arange(n) < int(n_cases), "case", "control")}
+    for g, name in enumerate(cols):
+        out[name] = c[g].astype(np.int64)
+    hits = c[:k].astype(np.int64).sum(axis=0)
+    total = 0 if group_sets is None else int(np.asarray(group_sets, np.int64).reshape(-1)[:k].sum())
+    out["Hits"] = hits
+    out["HitShare"] = hits / total if total > 0 else np.full(n, np.nan)
+    return pd.DataFrame(out, columns=["Patient", "Label"] + cols + ["Hits", "HitShare"])
+
+
+_patient_table = patient_table   # (gwaspa has a keyword of the same name)
+
+
 def _set_residual_columns(out, ex, sets, rows, signs, clump, lead) -> None:
     """``RESIDUAL_COLUMNS`` of a clumped table: every member row rescored without its lead's carriers, all of them in ONE
     ``JoinExec.score_sets(which=members, given=their leads)`` call on ``ex``.  NaN on leads and -1 rows."""
@@ -1316,7 +1422,8 @@ def gwaspa(genes: Sequence[str], data: np.ndarray, n_cases: int, n_ctrls: int, n
            clump: Optional[float] = None, clump_conditional: bool = False, false_counts: bool = False,
            false_count_ks: Sequence[int] = (2, 5, 10), false_count_alpha: float = 0.05,
            stepdown: bool = False, significant: Optional[float] = None,
-           significant_cap: int = 1_000_000, clump_significant: bool = False) -> Dict[str, object]:
+           significant_cap: int = 1_000_000, clump_significant: bool = False,
+           patient_table: bool = False) -> Dict[str, object]:
     """GWASPA (R/ProcessPaths.R:87-344) without R: dataset -> GWASPA.Results, scored on the MI355X.
 
     ``network`` = (ents_uid, ents_symbol, rel_src, rel_trg, rel_sign): the knowledge base getStringKB() would load
@@ -1383,6 +1490,16 @@ def gwaspa(genes: Sequence[str], data: np.ndarray, n_cases: int, n_ctrls: int, n
     without its lead's carriers in one ``score_sets(which=, given=)`` call on the run's own context -- its seed, strata and
     permutation count -- over the hit sets (unsigned) or the sets parsed from ``SignedPaths`` with their
     signs (signed).  False, the default: nothing new is called.
+
+    ``patient_table``: needs ``significant`` (ValueError before anything runs otherwise).  "Patient.Results"
+    (``patient_table``) says who carries the findings: one row per patient with "Hits.L1" .. "Hits.L<path_length>" -- how
+    many rows of Significant.Results of that length the patient carries (a variant in any gene of the path, both methods)
+    -- their sum "Hits" and "HitShare", from ONE ``api.JoinExec.patient_counts`` call on the run's own context over the hit
+    sets.  With ``clump_significant`` the clump leads are listed a second time into one more group:
+    "Leads", the distinct findings the patient carries.  The raw arrays come back as "patient_counts" = (counts,
+    group_sets, skipped).  The table is descriptive: exact counts, no test statistic -- the paths were selected on these
+    very labels, so their carriers are enriched in cases by construction; look for a handful of patients on every hit (a
+    batch artefact), not for significance.  False, the default: the output and every launch are what they were.
     """
     from . import api
     from .synth import Problem
@@ -1394,6 +1511,8 @@ def gwaspa(genes: Sequence[str], data: np.ndarray, n_cases: int, n_ctrls: int, n
         raise ValueError("clump_significant: needs both clump (the overlap r) and significant (the family-wise level)")
     if clump_significant and not 0 < clump <= 1:
         raise ValueError("r must be > 0 and <= 1")
+    if patient_table and significant is None:
+        raise ValueError("patient_table: needs significant (the family-wise level): the tally runs over the hit lists")
     if significant is not None:
         if not 0.0 < float(significant) < 1.0:      # (NaN fails both comparisons)
             raise ValueError(f"significant: the family-wise level must lie inside (0, 1), not {significant!r}")
@@ -1524,17 +1643,21 @@ def gwaspa(genes: Sequence[str], data: np.ndarray, n_cases: int, n_ctrls: int, n
                                                    (prep.ents2_uid, prep.ents2_symbol))
         out["significant"] = found
         out["significant_cutoffs"] = cutoffs
-        if clump_significant:
+        if clump_significant or patient_table:
             sig = out["Significant.Results"]
             hsets = hit_sets(found, gene_tables(levels, g, n2), g, n2,
                              nulls={L: lsts[f"lst{L}"].null for L in found})
             if len(hsets[0]) - 1 != len(sig):
-                raise ValueError(f"clump_significant: {len(hsets[0]) - 1} hit sets for {len(sig)} rows of Significant.Results")
+                raise ValueError(f"{'clump_significant' if clump_significant else 'patient_table'}: {len(hsets[0]) - 1} hit sets for "
+                                 f"{len(sig)} rows of Significant.Results")
+        lead_rows = None
+        if clump_significant:
             sc = sig["Scores"].to_numpy(dtype=np.float64)
             idx = np.flatnonzero(np.isfinite(sc))
             order = idx[np.argsort(-sc[idx], kind="stable")]
             c, l, v, sh, _ = ex.clump_sets(hsets, np.vstack([prep.data1, prep.data2]), order, r=clump)
             _set_clump_columns(sig, c, l, v, sh)
+            lead_rows = np.flatnonzero((c >= 0) & (l == np.arange(len(sig))))
             if clump_conditional:
                 if signed:   # the signs are in the table, not in the hit lists
                     _, prows, psigns = parse_sets([str(p) for p in sig["SignedPaths"]], genes)
@@ -1544,6 +1667,18 @@ def gwaspa(genes: Sequence[str], data: np.ndarray, n_cases: int, n_ctrls: int, n
                     _set_residual_columns(sig, ex, rsets, rsub, psigns, c, l)
                 else:
                     _set_residual_columns(sig, ex, hsets, np.vstack([prep.data1, prep.data2]), None, c, l)
+    if patient_table:
+        # group = length - 1; the clump leads once more, into a group of their own (a set listed twice is counted twice)
+        which = np.arange(len(sig), dtype=np.int64)
+        grp = sig["Lengths"].to_numpy(dtype=np.int64) - 1
+        names = [f"Hits.L{L}" for L in range(1, path_length + 1)]
+        if lead_rows is not None:
+            which = np.concatenate([which, lead_rows])
+            grp = np.concatenate([grp, np.full(len(lead_rows), path_length, np.int64)])
+            names.append("Leads")
+        got = ex.patient_counts(hsets, np.vstack([prep.data1, prep.data2]), which=which, group=grp, n_groups=len(names))
+        out["patient_counts"] = got
+        out["Patient.Results"] = _patient_table(got[0], n_cases, columns=names, group_sets=got[1], summed=path_length)
     if gene_table:
         best = {L + 1: tallies[name].read() for L, name in enumerate(GENE_LEVELS[:path_length])}
         out["gene_best"] = best

@@ -500,6 +500,39 @@ int gcre_clump_sets(gcre_ctx* ctx, const gcre_set_input* in, const int64_t* orde
 int64_t gcre_clump_launches(const gcre_ctx* ctx);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Carrier tallies of caller-given sets: how many of the listed sets each patient carries.  No reference
+ * counterpart.  Exact integer counts, descriptive only: no test statistic; the carriers of sets that were selected on
+ * the case / control labels are enriched in cases by construction.
+ * Entry i names set s = which[i]; repeats are allowed and a set listed twice is counted twice; which = NULL means
+ * 0 .. n_sets-1, and then n_which must be n_sets.  group [n_which]: the group of entry i, -1 .. n_groups-1, -1 = not
+ * counted; NULL = everything in group 0, and then n_groups must be 1.  Planes H = 1 + by_sign:
+ *   by_sign 0: the one plane is the carrier row C_s gcre_set_overlap defines (the OR of ALL members, whatever their signs
+ *              and the context's method, bits >= n_cols ignored);
+ *   by_sign 1: plane 0 is P_s, the OR of the +1 members, plane 1 is N_s, the OR of the -1 members, read from `signs`
+ *              whatever the context's method, without conflict removal (as gcre_score_sets states for method 2);
+ *              signs = NULL: everything is in P.
+ *   counts[g][h][q] = #{ i : group[i] == g, set which[i] has no NA member, bit q of plane h of set which[i] }
+ *                     int32 [n_groups][H][n_cols]
+ *   group_sets[g], optional [n_groups]: the entries counted into group g
+ *   *skipped, optional: the entries with group >= 0 whose set has an NA member: their carriers are not known, they are
+ *                     counted nowhere
+ * Needs neither a value table nor permutation masks.  The gene rows, a member table and a segment list go up once;
+ * k_set_patient_counts adds the rows up in bit-sliced counters, one wave per (segment of one group's entries, 2,048
+ * patients).  Segments hold at most GCRE_PATIENT_SEG entries (environment, read per call; default: what spreads the call
+ * over about 4,096 waves, 64 to 1,024 entries); the results do not depend on it.  n_which == 0, or every entry -1 or NA,
+ * launches nothing and writes zeros.
+ * Errors, nothing launched: what gcre_set_overlap refuses of the set list; GCRE_ERR_ARG -- by_sign not 0 or 1,
+ * n_groups < 1, n_which < 0, NULL `which` with n_which != n_sets, NULL `group` with n_groups != 1, NULL counts,
+ * n_which >= 2^31 - 16 (a 32-bit cell cannot overflow), n_groups x H x n_cols x 4 bytes (or the member table) above
+ * GCRE_PATIENT_MAX_MB (environment, read per call, default 1024); GCRE_ERR_RANGE -- a `which` entry outside
+ * 0 .. n_sets-1, a `group` entry outside -1 .. n_groups-1. */
+int gcre_set_patient_counts(gcre_ctx* ctx, const gcre_set_input* in, const int64_t* which, int64_t n_which,
+                            const int32_t* group, int32_t n_groups, int by_sign, int32_t* counts,
+                            int64_t* group_sets, int64_t* skipped);
+/* kernels launched by gcre_set_patient_counts on the context since gcre_create (tests: a refusal launches nothing). */
+int64_t gcre_patient_launches(const gcre_ctx* ctx);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Per-gene best-path table: for every gene, the best joined path of a join that runs through it.  No
  * reference counterpart (it keeps the top K of a level and nothing else).  A join's inspector leaves the observed score,
  * operand rows, cases and controls of EVERY joined path on the device; a tally armed for the join folds them, chunk by
