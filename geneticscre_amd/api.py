@@ -114,6 +114,9 @@ class gcre_set_input(ctypes.Structure):
 SET_SCORE = np.dtype([("set", "<i8"), ("valid", "<i4"), ("cases", "<i4"), ("ctrls", "<i4"), ("cases_pos", "<i4"),
                       ("ctrls_pos", "<i4"), ("cases_neg", "<i4"), ("ctrls_neg", "<i4"), ("score", "<f8"),
                       ("n_ge", "<i8"), ("pvalue", "<f8")], align=True)
+# gcre_burden
+BURDEN = np.dtype([("total", "<i8"), ("observed", "<i8"), ("n_ge", "<i8"), ("n_le", "<i8"), ("planes", "<i4"),
+                   ("p_upper", "<f8"), ("p_lower", "<f8")], align=True)
 
 
 # every symbol include/gcre_hip.h declares; tests check that the library exports all of them
@@ -133,6 +136,7 @@ EXPORTS = [
     "gcre_set_overlap", "gcre_overlap_launches",
     "gcre_clump_sets", "gcre_clump_launches",
     "gcre_set_patient_counts", "gcre_patient_launches",
+    "gcre_patient_burden", "gcre_burden_launches",
     "gcre_gene_tally_create", "gcre_join_set_tally", "gcre_process_paths_set_tally", "gcre_gene_tally_read",
     "gcre_gene_tally_free",
     "gcre_exceed_create", "gcre_join_set_exceed", "gcre_process_paths_set_exceed", "gcre_exceed_read",
@@ -264,6 +268,9 @@ _FEATURES = {
     "patients": (None, ["gcre_set_patient_counts", "gcre_patient_launches"], "carrier tallies per patient (gcre_set_patient_counts)", {
         "gcre_set_patient_counts": (_I, [_V, ctypes.POINTER(gcre_set_input), _P, _I64, _P, _I32, _I, _P, _P, ctypes.POINTER(_I64)]),
         "gcre_patient_launches": (_I64, [_V])}),
+    "burden": (None, ["gcre_patient_burden", "gcre_burden_launches"], "burden tests of per-patient weights (gcre_patient_burden)", {
+        "gcre_patient_burden": (_I, [_V, _P, _I64, _I32, _P, _P]),
+        "gcre_burden_launches": (_I64, [_V])}),
     "genes": (None, ["gcre_gene_tally_create"], "per-gene best-path tally (gcre_gene_tally_create)", {
         "gcre_gene_tally_create": (_V, [_V, _I32, _P, _I64, _I32, _P, _I64, _I32]),
         "gcre_join_set_tally": (_I, [_V, _V]),
@@ -317,6 +324,7 @@ _given_lib = functools.partial(_feature_lib, "given")
 _overlap_lib = functools.partial(_feature_lib, "overlap")
 _clump_lib = functools.partial(_feature_lib, "clump")
 _patients_lib = functools.partial(_feature_lib, "patients")
+_burden_lib = functools.partial(_feature_lib, "burden")
 _genes_lib = functools.partial(_feature_lib, "genes")
 _exceed_lib = functools.partial(_feature_lib, "exceed")
 _perm_counts_lib = functools.partial(_feature_lib, "perm_counts")
@@ -1128,6 +1136,45 @@ class JoinExec:
     def patient_launches(self) -> int:
         """Kernels gcre_set_patient_counts launched on this context so far."""
         return int(_patients_lib().gcre_patient_launches(self._h))
+
+    def patient_burden(self, weights, null: bool = False):
+        """Burden tests of per-patient weights (gcre_patient_burden): for every row of non-negative
+        integer ``weights`` -- [rows][n], or the [G][H][n] counts ``patient_counts`` returns, flattened to G * H rows --
+        the weighted sum over the cases, ``observed``, against the same sum over the cases of every one of the context's
+        permutation masks (all of them, whatever the permutation window; strata come in through the masks).  Returns a
+        dict of arrays with one entry per row: ``total``, ``observed``, ``n_ge``, ``n_le`` (int64: the permutations whose
+        sum is >= / <= the observed one; a tie counts in both), ``planes`` (int32, the bit length of the row's largest
+        weight), ``p_upper`` = n_ge / iterations, ``p_lower`` = n_le / iterations (NaN at 0 iterations) and, with
+        ``null``, ``null``: int64 [rows][iterations], every null sum.  All sums are exact integers.  A p-value on weights
+        selected on these very labels (the tallies of a run's own significant paths) is meaningless.  A wrong shape, a
+        negative weight or one above 2^31 - 1 raise ValueError before the library is touched; the library's refusals
+        raise GcreError (ValueError: no permutation masks set)."""
+        n = self.num_cases + self.num_ctrls
+        w = np.asarray(weights)
+        if w.dtype == object or not (np.issubdtype(w.dtype, np.integer) or np.issubdtype(w.dtype, np.bool_)):
+            raise ValueError(f"weights: integers, not {w.dtype}")
+        if w.ndim not in (2, 3) or w.shape[-1] != n:
+            raise ValueError(f"weights: [rows][{n}] or [groups][planes][{n}] (n_cases + n_ctrls columns), not {list(w.shape)}")
+        w = w.reshape(-1, n)
+        if w.size and (int(w.min()) < 0 or int(w.max()) > 2**31 - 1):
+            raise ValueError("weights: every weight must lie in 0 .. 2^31 - 1")
+        w32 = np.ascontiguousarray(w, dtype=np.int32)
+        lib = _burden_lib()
+        R = w32.shape[0]
+        rec = np.zeros(R, dtype=BURDEN)
+        sums = np.zeros((R, self.iters), dtype=np.int64) if null else None
+        rc = lib.gcre_patient_burden(self._h, _ptr(w32), R, n, _ptr(rec), _ptr(sums))
+        if rc != GCRE_OK:
+            self._raise(rc)
+        out = {k: np.ascontiguousarray(rec[k]) for k in ("total", "observed", "n_ge", "n_le", "planes", "p_upper", "p_lower")}
+        if null:
+            out["null"] = sums
+        return out
+
+    @property
+    def burden_launches(self) -> int:
+        """Kernels gcre_patient_burden launched on this context so far."""
+        return int(_burden_lib().gcre_burden_launches(self._h))
 
     def stepdown_launches(self) -> int:
         """k_stepdown_null / k_stepdown_finish launches of this context so far."""

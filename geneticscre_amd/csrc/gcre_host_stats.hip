@@ -1,6 +1,6 @@
 // gcre_host_stats.hip -- the entry points of include/gcre_hip.h that use a context but not the join driver: generated
 // permutation masks, decorated p-values (gcre_decorated.hip), set scores (gcre_sets.hip, conditional: gcre_given.hip) and carrier overlaps
-// (gcre_overlap.hip), greedy clumps (gcre_clump.hip) and carrier tallies per patient (gcre_patients.hip), and the per-gene tally (gcre_genes.hip), the null exceedance counts (gcre_exceed.hip,
+// (gcre_overlap.hip), greedy clumps (gcre_clump.hip), carrier tallies per patient (gcre_patients.hip) and burden tests of per-patient weights (gcre_burden.hip), and the per-gene tally (gcre_genes.hip), the null exceedance counts (gcre_exceed.hip,
 // gcre_stepdown.hip) and the hit lists (gcre_hits.hip) as objects.  What a join does with an armed tally, armed counts or
 // an armed list -- check_tally, fold_genes, count_exceed, collect_hits -- is in gcre_host.hip.  Host code only.
 #include "gcre_host.h"
@@ -786,6 +786,156 @@ int gcre_set_patient_counts(gcre_ctx* c, const gcre_set_input* in, const int64_t
 }
 
 int64_t gcre_patient_launches(const gcre_ctx* c) { return c ? c->patient_launches : -1; }
+
+// Burden tests of per-patient weights.  check_burden_args gives every row's planes; totals and observed
+// sums are the host's.  The rows are walked in slabs whose planes and sums stay under GCRE_BURDEN_MAX_MB; of a slab the
+// rows with a non-zero weight are listed, their planes cut into items, and three kernels run: k_burden_planes,
+// k_burden_null, k_burden_finish.  Every sum is an exact integer, so no result depends on the slabs.
+int gcre_patient_burden(gcre_ctx* c, const int32_t* weights, int64_t n_rows, int32_t n_cols, gcre_burden* out, int64_t* null_sums) {
+  if (!c) return GCRE_ERR_ARG;
+  const Geometry& g = c->g;
+  const std::string who = "patient_burden";
+  const int K = g.K, W32p = 2 * g.Wp;
+  std::string msg;
+  std::vector<int32_t> planes;
+  if (int rc = check_burden_args(weights, n_rows, n_cols, g.n, out != nullptr, K, c->have_perms, W32p, g.Kpad, burden_max_mb(), who,
+                                 planes, msg))
+    return fail(c, rc, msg);
+  if (n_rows == 0) return GCRE_OK;
+  const auto t_begin = std::chrono::steady_clock::now();
+  const int n = g.n;
+  const double nan = std::numeric_limits<double>::quiet_NaN();
+  std::vector<int64_t> observed((size_t)n_rows);
+  for (int64_t r = 0; r < n_rows; r++) {
+    const int32_t* w = weights + (size_t)r * (size_t)n;
+    int64_t cases = 0, all = 0;
+    for (int q = 0; q < n; q++) {
+      all += w[q];
+      if (q < g.n_cases) cases += w[q];
+    }
+    gcre_burden& o = out[r];
+    std::memset(&o, 0, sizeof o);
+    o.total = all;
+    o.observed = observed[(size_t)r] = cases;
+    o.planes = planes[(size_t)r];
+    // a row of zeros: every sum is 0 = observed, a tie in both tails
+    o.n_ge = o.n_le = o.planes == 0 ? K : 0;
+    o.p_upper = o.p_lower = K > 0 && o.planes == 0 ? 1.0 : nan;
+  }
+  if (K == 0) return GCRE_OK;
+  if (null_sums) std::memset(null_sums, 0, (size_t)n_rows * (size_t)K * sizeof(int64_t));
+
+  // GCRE_BURDEN_STATS (tools/burden_time.py): one line on stderr
+  const bool stats = std::getenv("GCRE_BURDEN_STATS") != nullptr;
+  int64_t slab_rows = n_rows, n_slabs = 0, n_items = 0, n_planes = 0;
+  if (const char* e = std::getenv("GCRE_BURDEN_SLAB_ROWS")) slab_rows = std::min<int64_t>(std::max<int64_t>(std::atoll(e), 1), n_rows);
+  const double cap = burden_max_mb() * 1048576.0;
+  (void)hipSetDevice(c->device);
+  for (int64_t r0 = 0; r0 < n_rows;) {
+    // the slab [r0, r1): rows while their planes and sums fit (one row always does: check_burden_args)
+    int64_t r1 = r0;
+    double bytes = 0;
+    while (r1 < n_rows && r1 - r0 < slab_rows && r1 - r0 < 0x7fffffff) {
+      const double more = (double)planes[(size_t)r1] * W32p * 4.0 + (double)g.Kpad * 8.0;
+      if (r1 > r0 && bytes + more > cap) break;
+      bytes += more;
+      r1++;
+    }
+    const int64_t rows = r1 - r0;
+    std::vector<int32_t> act, np, pbase;
+    std::vector<int64_t> obs;
+    std::vector<BurdenItem> items;
+    int32_t at = 0;
+    for (int64_t r = r0; r < r1; r++) {
+      const int32_t p = planes[(size_t)r];
+      if (p == 0) continue;
+      act.push_back((int32_t)(r - r0));
+      np.push_back(p);
+      pbase.push_back(at);
+      obs.push_back(observed[(size_t)r]);
+      for (int32_t b = 0; b < p; b += kBurdenItemPlanes)
+        items.push_back({(int32_t)(r - r0), at + b, std::min<int32_t>(kBurdenItemPlanes, p - b), b});
+      at += p;
+    }
+    r0 = r1;
+    if (act.empty()) continue;   // nothing but rows of zeros: nothing is launched
+    n_slabs++;
+    n_items += (int64_t)items.size();
+    n_planes += at;
+    const size_t nact = act.size();
+    std::vector<unsigned long long> tails(2 * nact);
+    DevScratch d(c->stream);
+    BurdenPlaneArgs pa{};
+    pa.w = d.put(weights + (size_t)(r1 - rows) * (size_t)n, (size_t)rows * (size_t)n);
+    pa.act = d.put(act.data(), nact);
+    pa.nplanes = d.put(np.data(), nact);
+    pa.pbase = d.put(pbase.data(), nact);
+    pa.planes = d.take<uint32_t>((size_t)at * (size_t)W32p);
+    pa.nact = (int64_t)nact;
+    pa.n = n;
+    pa.Wp = g.Wp;
+    BurdenNullArgs na{};
+    na.planes = pa.planes;
+    na.masks = c->d_masks;
+    na.items = d.put(items.data(), items.size());
+    na.sums = d.take<unsigned long long>((size_t)rows * (size_t)g.Kpad);
+    na.nitems = (int64_t)items.size();
+    na.npt = (na.nitems + 3) / 4;
+    na.nkt = (K + kSetPermTile - 1) / kSetPermTile;
+    // one item tile per block while that makes at least ~8 blocks per resident block slot, more per block beyond (k_set_null's rule)
+    const int64_t per = std::max<int64_t>(1, (na.npt * na.nkt) / ((int64_t)c->cus * 4 * 8));
+    na.pgroups = (int)std::min<int64_t>((na.npt + per - 1) / per, 0x7fffffff / std::max(na.nkt, 1));
+    na.W32p = W32p;
+    na.Kpad = g.Kpad;
+    na.K = K;
+    BurdenFinishArgs fa{};
+    fa.sums = na.sums;
+    fa.act = pa.act;
+    fa.observed = d.put(obs.data(), nact);
+    fa.tails = d.take<unsigned long long>(2 * nact);
+    fa.nact = (int64_t)nact;
+    fa.Kpad = g.Kpad;
+    fa.K = K;
+    d.zero(na.sums, (size_t)rows * (size_t)g.Kpad);
+    d.zero(fa.tails, 2 * nact);
+    if (d.ok()) {
+      d.e = launch_burden_planes(pa, c->stream);
+      if (d.ok()) c->burden_launches++;
+    }
+    if (d.ok()) {
+      d.e = launch_burden_null(na, c->stream);
+      if (d.ok()) c->burden_launches++;
+    }
+    if (d.ok()) {
+      d.e = launch_burden_finish(fa, c->stream);
+      if (d.ok()) c->burden_launches++;
+    }
+    d.download(tails.data(), fa.tails, 2 * nact);
+    if (null_sums && d.ok())   // the sums without the padding (a row of zeros: zeros)
+      d.e = hipMemcpy2DAsync(null_sums + (size_t)(r1 - rows) * (size_t)K, (size_t)K * 8, na.sums, (size_t)g.Kpad * 8, (size_t)K * 8,
+                             (size_t)rows, hipMemcpyDeviceToHost, c->stream);
+    d.sync();
+    d.release();
+    if (!d.ok()) {
+      (void)hipGetLastError();
+      return fail(c, GCRE_ERR_DEVICE, who + ": " + hipGetErrorString(d.e));
+    }
+    for (size_t i = 0; i < nact; i++) {
+      gcre_burden& o = out[(r1 - rows) + act[i]];
+      o.n_ge = (int64_t)tails[2 * i];
+      o.n_le = (int64_t)tails[2 * i + 1];
+      o.p_upper = (double)o.n_ge / (double)K;
+      o.p_lower = (double)o.n_le / (double)K;
+    }
+  }
+  if (stats)
+    fprintf(stderr, "burden rows=%lld planes=%lld items=%lld slabs=%lld iterations=%d entry_ms=%.3f\n", (long long)n_rows,
+            (long long)n_planes, (long long)n_items, (long long)n_slabs, K,
+            std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count());
+  return GCRE_OK;
+}
+
+int64_t gcre_burden_launches(const gcre_ctx* c) { return c ? c->burden_launches : -1; }
 
 // ---- per-gene best-path tally ----
 gcre_gene_tally* gcre_gene_tally_create(gcre_ctx* c, int32_t n_slots, const int32_t* genes0, int64_t n_rows0, int32_t w0,

@@ -625,4 +625,46 @@ struct PatientCountArgs {
 };
 hipError_t launch_set_patient_counts(const PatientCountArgs& a, hipStream_t stream);
 
+// ---- burden tests of per-patient weights (gcre_burden.hip) ----
+// The rows of a slab that have a non-zero weight are listed (`act`); each gets the bit planes its largest weight needs,
+// [Wp] 64-bit words per plane in SetNullArgs' row layout.  An item is up to kBurdenItemPlanes consecutive planes of one
+// row: one wave of k_burden_null counts it against a tile of kSetPermTile permutations.
+constexpr int kBurdenItemPlanes = 4;
+constexpr int kBurdenMaxPlanes = 31;                 // weights are non-negative int32
+struct BurdenItem {
+  int32_t row;                      // row of the slab: sums[row][..]
+  int32_t plane;                    // its first plane, as an index into the slab's planes
+  int32_t count;                    // 1 .. kBurdenItemPlanes planes
+  int32_t base;                     // the bit the first plane holds
+};
+struct BurdenPlaneArgs {
+  const int32_t* w;                 // [slab rows][n] weights, >= 0
+  const int32_t* act;               // [nact] rows of the slab with a non-zero weight
+  const int32_t* nplanes;           // [nact] 1 .. kBurdenMaxPlanes
+  const int32_t* pbase;             // [nact] first plane of the row
+  uint32_t* planes;                 // [sum nplanes][2 * Wp], every word written (zero beyond the patients)
+  int64_t nact;
+  int n, Wp;
+};
+struct BurdenNullArgs {
+  const uint32_t* planes;           // [..][W32p] (read-only: scalar loads)
+  const uint32_t* masks;            // [W32p][Kpad]
+  const BurdenItem* items;          // [nitems] (read-only)
+  unsigned long long* sums;         // [slab rows][Kpad], zeroed; permutations K .. Kpad are never written
+  int64_t nitems, npt;              // npt = ceil(nitems / 4) item tiles
+  int nkt, pgroups;                 // permutation tiles; item tiles walked in parallel: grid = nkt * pgroups
+  int W32p, Kpad, K;
+};
+struct BurdenFinishArgs {
+  const unsigned long long* sums;   // [slab rows][Kpad]
+  const int32_t* act;               // [nact]
+  const int64_t* observed;          // [nact]
+  unsigned long long* tails;        // [nact][2] n_ge, n_le, zeroed
+  int64_t nact;
+  int Kpad, K;
+};
+hipError_t launch_burden_planes(const BurdenPlaneArgs& a, hipStream_t stream);
+hipError_t launch_burden_null(const BurdenNullArgs& a, hipStream_t stream);
+hipError_t launch_burden_finish(const BurdenFinishArgs& a, hipStream_t stream);
+
 }  // namespace gcre

@@ -1,7 +1,7 @@
 // gcre_setlists.h -- the host stage that gcre_score_sets, gcre_set_overlap and gcre_exceed_stepdown share (gcre_host_stats.hip):
 // what they refuse of a caller's set list, and the union rows and counts of one set.  Plain C++17 over include/gcre_hip.h, no
-// HIP: tests/native/setlists_main.cpp drives it on a machine without a GPU (given_main.cpp and patients_main.cpp: the index
-// checks of gcre_score_sets_given and gcre_set_patient_counts).
+// HIP: tests/native/setlists_main.cpp drives it on a machine without a GPU (given_main.cpp, patients_main.cpp and
+// burden_main.cpp: the argument checks of gcre_score_sets_given, gcre_set_patient_counts and gcre_patient_burden).
 #pragma once
 #include "../../include/gcre_hip.h"
 
@@ -128,6 +128,69 @@ inline int check_patient_index(const gcre_set_input* in, const int64_t* which, i
               " groups, -1 = not counted)";
         return GCRE_ERR_RANGE;
       }
+    }
+    return GCRE_OK;
+  }
+  return GCRE_ERR_ARG;
+}
+
+// GCRE_BURDEN_MAX_MB: the bound on the bit planes and the sums gcre_patient_burden holds on the device at one time, read
+// per call (tests set fractions); default 1024
+inline double burden_max_mb() {
+  double mb = 1024;
+  if (const char* e = std::getenv("GCRE_BURDEN_MAX_MB")) mb = std::min(std::max(std::atof(e), 0.0), 65536.0);
+  return mb;
+}
+
+// the bit length of a non-negative weight: the planes a row whose largest weight it is needs
+inline int32_t burden_bit_length(int32_t v) {
+  int32_t b = 0;
+  for (uint32_t u = (uint32_t)v; u != 0; u >>= 1) b++;
+  return b;
+}
+
+// What gcre_patient_burden refuses of its arguments: weights [n_rows][n_cols], >= 0, on a context of `n_patients` patients,
+// `iterations` permutations (`have_masks`: set) whose masks are [W32p][Kpad] dwords.  planes[g] = the bit length of row
+// g's largest weight; a row's device bytes are its planes of W32p dwords and its Kpad 64-bit sums, and the largest row's
+// must fit `max_mb` (the rows are walked in slabs).
+inline int check_burden_args(const int32_t* weights, int64_t n_rows, int32_t n_cols, int32_t n_patients, bool have_out,
+                             int32_t iterations, bool have_masks, int32_t W32p, int32_t Kpad, double max_mb,
+                             const std::string& who, std::vector<int32_t>& planes, std::string& msg) {
+  planes.clear();
+  if (!have_out)
+    msg = who + ": NULL out";
+  else if (n_rows < 0)
+    msg = who + ": n_rows must not be negative, not " + std::to_string(n_rows);
+  else if (!weights && n_rows > 0)
+    msg = who + ": NULL weights with " + std::to_string(n_rows) + " rows";
+  else if (n_cols != n_patients)
+    msg = who + ": " + std::to_string(n_cols) + " columns for " + std::to_string(n_patients) + " patients (n_cases + n_ctrls)";
+  else if (iterations > 0 && !have_masks) {
+    msg = "assertion: " + who + " needs the permutation masks (iterations > 0, none set)";
+    return GCRE_ERR_ASSERT;
+  } else {
+    planes.assign((size_t)n_rows, 0);
+    int32_t most = 0;
+    for (int64_t g = 0; g < n_rows; g++) {
+      const int32_t* w = weights + (size_t)g * (size_t)n_cols;
+      int32_t top = 0;
+      for (int32_t q = 0; q < n_cols; q++) {
+        if (w[q] < 0) {
+          msg = who + ": weights[" + std::to_string(g) + "][" + std::to_string(q) + "] = " + std::to_string(w[q]) + " is negative";
+          planes.clear();
+          return GCRE_ERR_ARG;
+        }
+        top = std::max(top, w[q]);
+      }
+      planes[(size_t)g] = burden_bit_length(top);
+      most = std::max(most, planes[(size_t)g]);
+    }
+    const double row_bytes = (double)most * (double)W32p * 4.0 + (double)Kpad * 8.0;
+    if (iterations > 0 && most > 0 && row_bytes > max_mb * 1048576.0) {
+      msg = who + ": one row of " + std::to_string(most) + " planes and " + std::to_string(Kpad) + " sums takes " +
+            std::to_string((int64_t)row_bytes) + " bytes: above GCRE_BURDEN_MAX_MB = " + std::to_string(max_mb);
+      planes.clear();
+      return GCRE_ERR_ARG;
     }
     return GCRE_OK;
   }

@@ -24,6 +24,10 @@
   * ``patient_counts_reference`` / ``patient_table``  who carries the findings: how many of a list of sets every patient
                          carries, per group of sets (gcre_set_patient_counts; beyond the reference)
 
+  * ``burden_reference`` / ``burden_table`` / ``burden_test`` / ``replicate``  permutation p-values of per-patient loads:
+                         do the cases carry more of a list of sets than the cases of a random relabelling -- gene-set
+                         burden tests, replication in a second cohort (gcre_patient_burden)
+
 Host-side post-processing of <= top_k x 5 rows: string work, nothing here touches the scored path.
 """
 from __future__ import annotations
@@ -1174,6 +1178,197 @@ def patient_table(counts, n_cases: int, names=None, columns=None, group_sets=Non
 
 
 _patient_table = patient_table   # (gwaspa has a keyword of the same name)
+
+
+def unpack_masks(masks, n: int) -> np.ndarray:
+    """Packed permutation masks -- the uint64 words ``JoinExec.perm_mask`` returns, one row per permutation -- as a 0/1
+    int64 matrix [permutations][n]: bit q of a row is patient q."""
+    W = (int(n) + 63) // 64
+    m = np.asarray(masks, dtype=np.uint64).reshape(-1, W)
+    bits = (m[:, :, None] >> np.arange(64, dtype=np.uint64)[None, None, :]) & np.uint64(1)
+    return bits.reshape(len(m), W * 64)[:, :n].astype(np.int64)
+
+
+def burden_reference(weights, masks, n_cases: int) -> Dict[str, np.ndarray]:
+    """gcre_patient_burden by its definition, in numpy and int64.  ``weights``: non-negative integers
+    [rows][n] (or [G][H][n], flattened), columns < ``n_cases`` the cases; ``masks``: the packed words ``JoinExec.perm_mask``
+    returns, one row per permutation (bits beyond n are not patients).  For every row g: ``total`` = sum_q w[g][q],
+    ``observed`` = the sum over q < n_cases, ``null`` [rows][permutations] = the sum over the q with bit q of the mask set,
+    ``n_ge`` / ``n_le`` = the permutations with null >= / <= observed (a tie counts in both), ``planes`` = the bit length of
+    the row's largest weight, ``p_upper`` / ``p_lower`` = n_ge / n_le over the permutations (NaN without any)."""
+    w = np.asarray(weights)
+    if w.ndim < 2:
+        raise ValueError("weights: [rows][n]")
+    n = w.shape[-1]
+    w = w.reshape(-1, n).astype(np.int64)
+    if (w < 0).any() or (w > 2**31 - 1).any():
+        raise ValueError("weights: every weight must lie in 0 .. 2^31 - 1")
+    if not 0 <= int(n_cases) <= n:
+        raise ValueError(f"n_cases = {n_cases} of {n} patients")
+    m = unpack_masks(masks, n) if np.size(masks) else np.zeros((0, n), np.int64)
+    K = len(m)
+    total = w.sum(axis=1)
+    observed = w[:, :int(n_cases)].sum(axis=1)
+    null = w @ m.T                                  # int64, exact
+    n_ge = (null >= observed[:, None]).sum(axis=1).astype(np.int64)
+    n_le = (null <= observed[:, None]).sum(axis=1).astype(np.int64)
+    top = w.max(axis=1) if n else np.zeros(len(w), np.int64)
+    planes = np.array([int(x).bit_length() for x in top], dtype=np.int32)
+    nan = np.full(len(w), np.nan)
+    return {"total": total, "observed": observed, "n_ge": n_ge, "n_le": n_le, "planes": planes,
+            "p_upper": n_ge / K if K else nan, "p_lower": n_le / K if K else nan.copy(), "null": null}
+
+
+BURDEN_COLUMNS = ["Group", "Sets", "Load", "CaseLoad", "ControlLoad", "CaseMean", "ControlMean", "PvalueUpper", "PvalueLower"]
+BURDEN_NULL_COLUMNS = ["NullMean", "NullSD", "Z"]
+
+
+def burden_table(res, n_cases: int, n_ctrls: int, names=None, group_sets=None):
+    """One row per weight row of ``JoinExec.patient_burden`` / ``burden_reference`` (``res``, the dict either returns):
+    "Group" (the row's index, or ``names[g]``), "Sets" (``group_sets[g]``, the sets tallied into the row; NaN without it),
+    "Load" = total, "CaseLoad" = observed, "ControlLoad" = total - observed, "CaseMean" = CaseLoad / n_cases,
+    "ControlMean" = ControlLoad / n_ctrls, "PvalueUpper" = n_ge / permutations (cases carry MORE than a random split),
+    "PvalueLower" = n_le / permutations.  Where ``res`` holds the null sums: "NullMean" = null.mean(axis=1), "NullSD" =
+    null.std(axis=1) (both float64 on the exact int64 matrix) and "Z" = (CaseLoad - NullMean) / NullSD, NaN where NullSD
+    is 0 or there is no permutation.  The p-values mean something only where the weights were not selected on these
+    labels: a second cohort, or sets chosen without the labels."""
+    import pandas as pd
+
+    total = np.asarray(res["total"], np.int64).reshape(-1)
+    observed = np.asarray(res["observed"], np.int64).reshape(-1)
+    R = len(total)
+    if names is not None and len(names) != R:
+        raise ValueError(f"burden_table: {len(names)} names for {R} rows")
+    sets = np.full(R, np.nan) if group_sets is None else np.asarray(group_sets, np.int64).reshape(-1)
+    if len(sets) != R:
+        raise ValueError(f"burden_table: {len(sets)} set counts for {R} rows")
+    if int(n_cases) < 0 or int(n_ctrls) < 0:
+        raise ValueError("burden_table: n_cases and n_ctrls must not be negative")
+    with np.errstate(divide="ignore", invalid="ignore"):
+        out = {"Group": list(names) if names is not None else np.arange(R, dtype=np.int64), "Sets": sets, "Load": total,
+               "CaseLoad": observed, "ControlLoad": total - observed,
+               "CaseMean": observed / np.float64(n_cases), "ControlMean": (total - observed) / np.float64(n_ctrls),
+               "PvalueUpper": np.asarray(res["p_upper"], np.float64).reshape(-1),
+               "PvalueLower": np.asarray(res["p_lower"], np.float64).reshape(-1)}
+        cols = list(BURDEN_COLUMNS)
+        if res.get("null") is not None:
+            null = np.asarray(res["null"], np.int64).reshape(R, -1)
+            if null.shape[1]:
+                mean, sd = null.mean(axis=1), null.std(axis=1)
+            else:
+                mean, sd = np.full(R, np.nan), np.full(R, np.nan)
+            out["NullMean"], out["NullSD"] = mean, sd
+            out["Z"] = np.where(sd > 0, (observed - mean) / np.where(sd > 0, sd, 1.0), np.nan)
+            cols += BURDEN_NULL_COLUMNS
+    return pd.DataFrame(out, columns=cols)
+
+
+def burden_test(sets, genes: Sequence[str], data: np.ndarray, n_cases: int, n_ctrls: int, signed: bool = False, group=None,
+                names=None, threshold: float = 0.05, n_permutations: int = 100, strata: Optional[Sequence[int]] = None,
+                seed: int = 0, device: int = 0):
+    """Burden test of sets the caller names: per patient, how many sets of a group the patient carries
+    (``JoinExec.patient_counts``), and whether the cases carry more -- or fewer -- of them than the cases of
+    ``n_permutations`` random relabellings (``JoinExec.patient_burden``), all on one context of its own with
+    the masks of ``generate_permutations(seed, strata)``.  ``sets`` as ``parse_sets`` reads them; genes are looked up after
+    ``preprocess_table(threshold)`` (a set with a symbol not found is counted nowhere).  ``group``: per set 0 .. G - 1, or
+    -1 = not counted (None: one group); ``names``: one per group.  ``signed``: ``by_sign`` tallies, a (+) and a (-) row per
+    group.  Returns the ``burden_table`` (with the null columns); ``.attrs["skipped"]`` is the number of sets skipped.
+
+    A gene-set burden test -- per patient the number of genes of a pathway with a variant -- is this call with one-gene
+    sets and ``group`` the pathway's index::
+
+        pathways = {"KEGG_A": ["TP53", "ATM"], "KEGG_B": ["BRCA2", "ATM", "CHEK2"]}
+        sets = [[g] for p in pathways.values() for g in p]
+        group = [i for i, p in enumerate(pathways.values()) for _ in p]
+        burden_test(sets, genes, data, n_cases, n_ctrls, group=group, names=list(pathways), n_permutations=10000)
+
+    The p-values are valid where the sets were chosen without looking at these labels -- a pathway list, or the findings
+    of ANOTHER cohort (``replicate``).  A burden p-value on sets selected on the same labels -- a run's own significant
+    paths -- is meaningless: their carriers are enriched in cases by construction."""
+    from . import api
+    genes, data = preprocess_table(genes, data, threshold, n_cases, n_ctrls)
+    _, rows, signs = parse_sets(sets, genes)
+    used: Dict[int, int] = {}
+    idx = [[-1 if r < 0 else used.setdefault(r, len(used)) for r in rs] for rs in rows]
+    sub = np.asarray(data)[list(used.keys())] if used else np.zeros((0, n_cases + n_ctrls), np.int32)
+    ex = api.JoinExec(2 if signed else 1, n_cases, n_ctrls, int(n_permutations), device=device)
+    try:
+        if n_permutations > 0:
+            ex.generate_permutations(seed, strata)
+        counts, group_sets, skipped = ex.patient_counts(idx, sub, group=group, by_sign=bool(signed), signs=signs if signed else None)
+        res = ex.patient_burden(counts, null=True)
+    finally:
+        ex.close()
+    G, H = counts.shape[:2]
+    if names is not None and len(names) != G:
+        raise ValueError(f"burden_test: {len(names)} names for {G} groups")
+    base = [str(x) for x in names] if names is not None else [f"Group{g}" for g in range(G)]
+    labels = [f"{b} {s}" for b in base for s in (POS, NEG)] if H == 2 else base
+    out = burden_table(res, n_cases, n_ctrls, names=labels, group_sets=np.repeat(group_sets, H))
+    out.attrs["skipped"] = int(skipped)
+    return out
+
+
+REPLICATE_GROUPS = ["L1", "L2", "L3", "L4", "L5", "All"]
+
+
+def replicate(results_df, genes: Sequence[str], data: np.ndarray, n_cases: int, n_ctrls: int, signed: bool = False,
+              threshold: float = 0.05, n_permutations: int = 100, strata: Optional[Sequence[int]] = None, seed: int = 0,
+              device: int = 0, leads_only: bool = False) -> Dict[str, object]:
+    """Do the findings of a DISCOVERY run replicate in a second cohort?  ``results_df``: a GWASPA.Results or
+    Significant.Results table of the discovery run (its ``SignedPaths`` column with ``signed``, else ``Paths``);
+    ``genes`` / ``data`` / ``n_cases`` / ``n_ctrls``: the matrix of the SECOND cohort, which the paths were not selected on.
+
+      "Replication.Paths"   ``score_paths`` of every row in the second cohort: one permutation p-value per path
+      "Replication.Burden"  the ``burden_table`` of the carrier tallies (``JoinExec.patient_counts``: a patient carries a
+                            path with a variant in any of its genes), one row per path length "L1" .. "L5" and "All",
+                            with a "Skipped" column: do the second cohort's cases carry more of the findings than the
+                            cases of a random relabelling do (``JoinExec.patient_burden``)
+      "skipped"             paths with a gene that is absent from the second cohort (after ``preprocess_table``): NA in
+                            "Replication.Paths", counted in no tally, reported per group in "Skipped"
+
+    ``leads_only``: only the rows that are their own ``ClumpLead`` (``clump_paths`` / ``gwaspa(clump=..)``) go into the
+    tallies -- one vote per finding.  Both use the masks of ``generate_permutations(seed, strata)``.
+
+    This is valid because the second cohort's labels had no part in choosing the paths.  A burden p-value on sets
+    selected on the same labels -- the discovery cohort's own matrix here -- is meaningless: the carriers of selected paths
+    are enriched in cases by construction (which is why ``gwaspa(patient_table=True)`` attaches none)."""
+    from . import api
+    col = "SignedPaths" if signed and "SignedPaths" in results_df else "Paths"
+    paths = [str(p) for p in results_df[col]]
+    keep = np.ones(len(paths), bool)
+    if leads_only:
+        if "ClumpLead" not in results_df:
+            raise ValueError("leads_only: the table has no ClumpLead column (clump_paths, or gwaspa(clump=..))")
+        keep = (results_df["ClumpLead"].astype(object) == results_df["Paths"].astype(object)).to_numpy(dtype=bool)
+    out: Dict[str, object] = {"Replication.Paths": score_paths(paths, genes, data, n_cases, n_ctrls, signed, threshold,
+                                                                n_permutations, strata, seed, device)}
+    pgenes, pdata = preprocess_table(genes, data, threshold, n_cases, n_ctrls)
+    names, rows, _ = parse_sets(paths, pgenes)
+    used: Dict[int, int] = {}
+    idx = [[-1 if r < 0 else used.setdefault(r, len(used)) for r in rs] for rs in rows]
+    sub = np.asarray(pdata)[list(used.keys())] if used else np.zeros((0, n_cases + n_ctrls), np.int32)
+    G = len(REPLICATE_GROUPS)
+    sel = np.flatnonzero(keep)
+    lengths = np.array([len(nm) for nm in names], np.int64)[sel]
+    # every kept path once into its length's group (lengths outside 1 .. 5: none) and once into "All"
+    which = np.concatenate([sel, sel])
+    grp = np.concatenate([np.where((lengths >= 1) & (lengths <= 5), lengths - 1, -1), np.full(len(sel), G - 1, np.int64)])
+    na = np.array([any(r < 0 for r in rows[s]) for s in sel.tolist()], bool)
+    skipped_of = np.bincount(grp[np.concatenate([na, na]) & (grp >= 0)], minlength=G).astype(np.int64)
+    ex = api.JoinExec(2 if signed else 1, n_cases, n_ctrls, int(n_permutations), device=device)
+    try:
+        if n_permutations > 0:
+            ex.generate_permutations(seed, strata)
+        counts, group_sets, _ = ex.patient_counts(idx, sub, which=which, group=grp, n_groups=G)
+        res = ex.patient_burden(counts, null=True)
+    finally:
+        ex.close()
+    table = burden_table(res, n_cases, n_ctrls, names=REPLICATE_GROUPS, group_sets=group_sets)
+    table["Skipped"] = skipped_of
+    out["Replication.Burden"] = table
+    out["skipped"] = int(na.sum())
+    return out
 
 
 def _set_residual_columns(out, ex, sets, rows, signs, clump, lead) -> None:

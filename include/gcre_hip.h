@@ -533,6 +533,38 @@ int gcre_set_patient_counts(gcre_ctx* ctx, const gcre_set_input* in, const int64
 int64_t gcre_patient_launches(const gcre_ctx* ctx);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Burden tests of per-patient weights: permutation p-values of a weighted sum over the cases.  No
+ * reference counterpart.  weights int32 [n_rows][n_cols], every one >= 0, n_cols = n_cases + n_ctrls of the context,
+ * columns < n_cases are the cases: a row of gcre_set_patient_counts' counts, or any other non-negative integer load.
+ * For every row g and every one of the context's `iterations` permutation masks (all of them: the window of
+ * gcre_set_perm_window is the joins' business; strata come in through the masks):
+ *   total     = sum_q w[g][q]
+ *   observed  = sum_{q < n_cases} w[g][q]
+ *   null[g][r]= sum_{q : bit q of mask r} w[g][q]          int64, exact: below 2^47
+ *   n_ge      = #{ r : null[g][r] >= observed }            the upper tail; a tie counts in both tails
+ *   n_le      = #{ r : null[g][r] <= observed }            the lower tail
+ *   p_upper   = n_ge / iterations, p_lower = n_le / iterations (R/ProcessPaths.R:316's rule); NaN at 0 iterations
+ *   planes    = the bit length of the row's largest weight: the bit planes the device reads of it
+ * null_sums, optional [n_rows][iterations]: every null sum.  Where every mask holds the same number of cases the sum
+ * orders the permutations as the difference of the mean load of cases and controls does.
+ * A p-value on weights that were selected on these very labels -- the tallies of a run's own significant paths -- is
+ * meaningless: tally in a second cohort, or over sets chosen without the labels (gene sets).
+ * The weights go up in slabs of rows whose planes and sums stay under GCRE_BURDEN_MAX_MB (environment, read per call,
+ * default 1024; GCRE_BURDEN_SLAB_ROWS bounds the rows of a slab: tests); the results do not depend on the slabs.
+ * k_burden_planes cuts the rows into bit planes, k_burden_null adds 2^b popcount(plane_b & mask) into 64-bit sums with
+ * integer atomics, k_burden_finish counts the tails.  n_rows == 0 returns at once; iterations == 0 fills total,
+ * observed and planes, zero counts and NaN, and launches nothing; a row of zeros has planes = 0 and
+ * n_ge = n_le = iterations, and nothing is launched for it.
+ * Errors, nothing launched: GCRE_ERR_ARG -- NULL out, n_rows < 0, NULL weights with n_rows > 0, n_cols other than
+ * n_cases + n_ctrls, a negative weight, one row's planes and sums above GCRE_BURDEN_MAX_MB; GCRE_ERR_ASSERT --
+ * iterations > 0 and no permutation masks set. */
+typedef struct { int64_t total, observed, n_ge, n_le; int32_t planes; double p_upper, p_lower; } gcre_burden;
+int gcre_patient_burden(gcre_ctx* ctx, const int32_t* weights, int64_t n_rows, int32_t n_cols, gcre_burden* out,
+                        int64_t* null_sums);
+/* kernels launched by gcre_patient_burden on the context since gcre_create (tests: a refusal launches nothing). */
+int64_t gcre_burden_launches(const gcre_ctx* ctx);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Per-gene best-path table: for every gene, the best joined path of a join that runs through it.  No
  * reference counterpart (it keeps the top K of a level and nothing else).  A join's inspector leaves the observed score,
  * operand rows, cases and controls of EVERY joined path on the device; a tally armed for the join folds them, chunk by
