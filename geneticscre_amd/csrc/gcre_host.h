@@ -1,13 +1,12 @@
 // gcre_host.h -- private to the host side of libgcre_hip.so: the state behind the handles of include/gcre_hip.h and the
-// few helpers that its two translation units share.  gcre_host.hip holds the join driver and everything that feeds it,
+// few helpers that its three translation units share.  gcre_host.hip holds the join driver and everything that feeds it,
 // gcre_host_stats.hip the entry points that only use a context (set statistics, decorated p-values, the gene tally and the
-// exceedance counts as objects).  Nothing here is part of the ABI.
+// exceedance counts as objects), gcre_host_pipeline.hip the one-call pipeline on one device and on several (and with it
+// everything of RCCL).  Nothing here is part of the ABI.
 #pragma once
 #include "../../include/gcre_hip.h"
 #include "gcre_kernels.h"
-
-#include <dlfcn.h>
-#include <rccl/rccl.h>   // types and prototypes only: the library is dlopen'ed where several devices are used (RcclApi)
+#include "gcre_pipeline.h"   // Candidate and merge_candidates; ExchangeHub, which a context only points to
 
 #include <algorithm>
 #include <array>
@@ -30,7 +29,9 @@
 
 using namespace gcre;
 
-// What the two host files see of each other stays out of the dynamic symbol table
+struct ncclComm;   // RCCL's communicator, opaque here (ncclComm_t is a pointer to it): only gcre_host_pipeline.hip includes rccl.h
+
+// What the host files see of each other stays out of the dynamic symbol table
 namespace gcre_host __attribute__((visibility("hidden"))) {
 
 template <typename T>
@@ -66,12 +67,6 @@ struct DevBuf {   // grow-only device scratch
     p = nullptr;
     cap = 0;
   }
-};
-
-struct Candidate {
-  double score;
-  int64_t path;   // absolute joined-path ordinal
-  int32_t src, trg, cases, ctrls;
 };
 
 // top-k of a chunk: indices chosen by the radix select, their keys / counts / rows gathered and copied out
@@ -220,97 +215,6 @@ struct DevScratch {
 }  // namespace gcre_host
 using namespace gcre_host;
 
-// RCCL, loaded on first use (gcre_process_paths_devices with several distinct devices, gcre_rccl_selftest): the library
-// does not link librccl, so a one-GPU user -- the R drop-in's default -- never needs it.  north_star: "RCCL all-reduce over
-// xGMI of the per-permutation null maxima": ncclAllReduce(ncclMax) on each device's stream, in place on the device, for
-// the thresholds shared inside a join and for the per-level merge; the host hub below stays the fallback (RCCL missing,
-// a device listed twice) and the place where the device threads meet under a deadline before every collective.
-struct RcclApi {
-  void* so = nullptr;
-  decltype(&ncclCommInitAll) comm_init_all = nullptr;
-  decltype(&ncclCommDestroy) comm_destroy = nullptr;
-  decltype(&ncclAllReduce) all_reduce = nullptr;
-  decltype(&ncclGetErrorString) error_string = nullptr;
-  bool ok = false;
-  static RcclApi& get() {
-    static RcclApi api = [] {
-      RcclApi a;
-      const char* off = std::getenv("GCRE_RCCL");
-      if (off && std::strcmp(off, "0") == 0) return a;   // GCRE_RCCL=0: host hub only
-      for (const char* name : {"librccl.so", "librccl.so.1", "/opt/rocm/lib/librccl.so"}) {
-        a.so = dlopen(name, RTLD_NOW | RTLD_LOCAL);
-        if (a.so) break;
-      }
-      if (!a.so) return a;
-      a.comm_init_all = (decltype(a.comm_init_all))dlsym(a.so, "ncclCommInitAll");
-      a.comm_destroy = (decltype(a.comm_destroy))dlsym(a.so, "ncclCommDestroy");
-      a.all_reduce = (decltype(a.all_reduce))dlsym(a.so, "ncclAllReduce");
-      a.error_string = (decltype(a.error_string))dlsym(a.so, "ncclGetErrorString");
-      a.ok = a.comm_init_all && a.comm_destroy && a.all_reduce && a.error_string;
-      return a;
-    }();
-    return api;
-  }
-};
-
-// gcre_process_paths_devices: the device threads of one call meet here to MAX-merge their running null maxima during a
-// join (gcre_join_opts.exchange, served inside the library).  K floats per call: the host does the reduction.  With RCCL
-// the data stays on the devices and only the meeting (`meet`) happens here.
-struct ExchangeHub {
-  int n = 0;
-  std::mutex m;
-  std::condition_variable cv;
-  int arrived = 0;
-  uint64_t gen = 0;
-  bool failed = false, timed_out = false;
-  double timeout_s = 300.0;
-  std::vector<float> acc, result;
-  uint64_t round_tag = 0;
-  // tag = (level, permutation window, ordinal of the exchange inside the join): every device of a round must bring the same
-  // one -- a device that skipped or repeated an exchange would otherwise MAX another level's maxima into the thresholds
-  int reduce(std::vector<float>& mine, uint64_t tag) {   // in: this device's maxima; out: the MAX over all devices
-    std::unique_lock<std::mutex> lk(m);
-    if (failed) return 1;
-    if (arrived == 0) {
-      acc = mine;
-      round_tag = tag;
-    } else {
-      if (acc.size() != mine.size() || tag != round_tag) { failed = true; cv.notify_all(); return 1; }
-      for (size_t i = 0; i < mine.size(); i++) acc[i] = std::max(acc[i], mine[i]);
-    }
-    if (++arrived == n) {
-      result.swap(acc);
-      arrived = 0;
-      gen++;
-      cv.notify_all();
-    } else {
-      // a device that never arrives (its thread died, it took another road through the join) must not hold the others for
-      // ever: past the deadline the round -- and with it the call -- fails (GCRE_HUB_TIMEOUT_S, default 300 s: a join of
-      // configs[4] on a shared GPU takes seconds)
-      const uint64_t g = gen;
-      if (!cv.wait_for(lk, std::chrono::duration<double>(timeout_s), [&] { return gen != g || failed; })) {
-        failed = true;
-        timed_out = true;
-        cv.notify_all();
-        return 1;
-      }
-      if (gen == g) return 1;   // somebody failed before this round completed
-    }
-    mine = result;
-    return 0;
-  }
-  // every device arrives with the same tag or the round fails; no data (the collective that follows moves it)
-  int meet(uint64_t tag) {
-    std::vector<float> none;
-    return reduce(none, tag);
-  }
-  void fail() {
-    std::lock_guard<std::mutex> lk(m);
-    failed = true;
-    cv.notify_all();
-  }
-};
-
 struct gcre_ctx {
   Geometry g{};
   int device = 0;
@@ -382,7 +286,7 @@ struct gcre_ctx {
   uint64_t obs_epoch = 0;            // bumped whenever the value table changes: observed scores (keys, winners) are per epoch
   bool insp_cache = false;           // gcre_set_inspect_cache: a join's inspector output stays with its join index
   ExchangeHub* hub = nullptr;        // set by gcre_process_paths_devices for the duration of a call
-  ncclComm_t comm = nullptr;         // ... and this device's RCCL communicator when the devices are distinct and RCCL loads
+  struct ncclComm* comm = nullptr;   // ... and this device's RCCL communicator when the devices are distinct and RCCL loads
   int64_t rccl_calls = 0;            // collectives this context issued during the call (diagnostics, tests)
   DevBuf<float> d_hub_null;          // the maxima this device hands to the hub
   int hub_level = 0, hub_round = 0;  // what the next exchange of this device is: part of the hub's round tag
@@ -596,3 +500,21 @@ struct gcre_hits {
   uint64_t* key() const { return (uint64_t*)d_rec + cap; }
   int32_t* field(int k) const { return (int32_t*)((uint64_t*)d_rec + 2 * cap) + (int64_t)k * cap; }   // 0 src, 1 trg, 2 cases, 3 ctrls
 };
+
+// What the join driver (gcre_host.hip) shows the one-call pipeline (gcre_host_pipeline.hip)
+namespace gcre_host __attribute__((visibility("hidden"))) {
+
+int join_once(gcre_ctx* c, const JoinPlan& jp, gcre_result* out);   // run_join for a whole join
+// validation that does not need the path sets (join_base.cpp:198-200 checks the rest in run_join)
+gcre_uids* make_uids(gcre_ctx* c, int path_length, const int32_t* uid_count, const int64_t* uid_location, int64_t n_uids,
+                     const int32_t* signs, int64_t n_signs);
+void free_uids(gcre_uids* u);
+gcre_pathset* new_pathset(gcre_ctx* c, int64_t nrows, bool zero);
+size_t plane_bytes(const gcre_ctx* c, int64_t nrows, int groups);
+bool sparse_enabled(const gcre_ctx* c);
+bool inspect_cache_allowed();
+// The segment table and the quads of join index `u` (P joined paths, none kept apart) for windows of `window` permutations,
+// built by a helper thread that the join which asks for them -- or free_uids -- joins
+void start_table_prefetch(gcre_ctx* c, gcre_uids* u, int64_t P, int window);
+
+}  // namespace gcre_host

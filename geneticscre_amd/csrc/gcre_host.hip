@@ -1,9 +1,10 @@
 // gcre_host.hip -- host side of libgcre_hip.so: the C ABI of include/gcre_hip.h on top of the gfx950
-// kernels in gcre_kernels.hip.  Owns device memory, the stream, the join driver (JoinExec::join,
-// reference src/join_base.cpp:189-264), the top-k merge (merge_scores / format_result, methods.h:25-39,
-// join_base.cpp:138-154) and the ProcessPaths sequence (src/wrapper.cpp:216-276).  The state behind the handles is in
-// gcre_host.h; the entry points that do not touch the join driver -- generated permutation masks, decorated p-values, set
-// scores and overlaps, the gene tally and the exceedance counts as objects -- are in gcre_host_stats.hip.
+// kernels in gcre_kernels.hip.  Owns device memory, the stream and the join driver (JoinExec::join,
+// reference src/join_base.cpp:189-264).  The state behind the handles is in gcre_host.h; the top-k merge (merge_scores /
+// format_result, methods.h:25-39, join_base.cpp:138-154) is in gcre_pipeline.h, the ProcessPaths sequence
+// (src/wrapper.cpp:216-276) on one device and on several in gcre_host_pipeline.hip; the entry points that do not touch the
+// join driver -- generated permutation masks, decorated p-values, set scores and overlaps, the gene tally and the
+// exceedance counts as objects -- are in gcre_host_stats.hip.
 //
 // There is no CPU fallback: without a gfx950 device gcre_create fails with GCRE_ERR_DEVICE.
 #include "gcre_host.h"
@@ -86,8 +87,6 @@ struct HostTimer {
 
 }  // namespace
 
-std::atomic<int64_t> g_rccl_collectives{0};   // RCCL collectives issued by this process (gcre_rccl_collectives)
-
 int gcre_host::fail(gcre_ctx* c, int code, const std::string& msg) {
   if (c) {
     c->err = msg;
@@ -123,7 +122,9 @@ double drain_events(gcre_ctx* c, std::vector<std::pair<hipEvent_t, hipEvent_t>>&
   return ms;
 }
 
-gcre_pathset* new_pathset(gcre_ctx* c, int64_t nrows, bool zero) {
+}  // namespace
+
+gcre_pathset* gcre_host::new_pathset(gcre_ctx* c, int64_t nrows, bool zero) {
   HostTimer ht("new_pathset");
   if (nrows < 0) {
     fail(c, GCRE_ERR_ARG, "negative path-set size");
@@ -167,9 +168,11 @@ gcre_pathset* new_pathset(gcre_ctx* c, int64_t nrows, bool zero) {
 // The sparse kernel needs counts that fit 16 bits (64*Wp < 65535 patients); GCRE_NULL_KERNEL=dense turns it off.
 // (a table whose vtmax is not symmetric is scored by the dense kernel: the (-) half reads the mirror image there, the
 // count-plane and delta-streaming kernels and their ladders index both halves of one table)
-bool sparse_enabled(const gcre_ctx* c) {
+bool gcre_host::sparse_enabled(const gcre_ctx* c) {
   return c->null_kernel != 1 && c->g.K > 0 && 64 * c->g.Wp < 65535 && !c->d_dmaxn;
 }
+
+namespace {
 
 // d_mt from d_masks as they are now
 int transpose_masks(gcre_ctx* c) {
@@ -307,10 +310,14 @@ bool planes_cover(const gcre_ctx* c, const gcre_pathset* ps, int64_t lo, int64_t
 }
 bool planes_current(const gcre_ctx* c, const gcre_pathset* ps) { return planes_cover(c, ps, 0, ps->nrows); }
 
-size_t plane_bytes(const gcre_ctx* c, int64_t nrows, int groups) {
+}  // namespace
+
+size_t gcre_host::plane_bytes(const gcre_ctx* c, int64_t nrows, int groups) {
   const size_t nkt = (size_t)((c->win_K + kSparseTile - 1) / kSparseTile);
   return (size_t)std::max<int64_t>(nrows, 1) * c->g.method * nkt * (size_t)groups * 1024;
 }
+
+namespace {
 
 // room for `bytes` more on the device, leaving a quarter of what is free for the scratch of the join itself
 // `bytes` fit into three quarters of the free device memory (counting `reclaimable` bytes as free)
@@ -736,7 +743,9 @@ void drop_launch(const gcre_uids* u) {
   u->launch.prof = gcre_profile{};
 }
 
-void free_uids(gcre_uids* u) {
+}  // namespace
+
+void gcre_host::free_uids(gcre_uids* u) {
   if (!u) return;
   if (u->ctx && u->ctx->ahead)   // a registered later join names this index
     for (const JoinPlan& a : *u->ctx->ahead)
@@ -763,8 +772,8 @@ void free_uids(gcre_uids* u) {
 }
 
 // validation that does not need the path sets (join_base.cpp:198-200 checks the rest in run_join)
-gcre_uids* make_uids(gcre_ctx* c, int path_length, const int32_t* uid_count, const int64_t* uid_location,
-                     int64_t n_uids, const int32_t* signs, int64_t n_signs) {
+gcre_uids* gcre_host::make_uids(gcre_ctx* c, int path_length, const int32_t* uid_count, const int64_t* uid_location,
+                                int64_t n_uids, const int32_t* signs, int64_t n_signs) {
   HostTimer ht("make_uids");
   auto* u = new gcre_uids{};
   u->ctx = c;
@@ -808,6 +817,8 @@ gcre_uids* make_uids(gcre_ctx* c, int path_length, const int32_t* uid_count, con
   c->live_uids.push_back(u);
   return u;
 }
+
+namespace {
 
 // distinct (location, count) ranges of a join index, uid -> range (see k_range_union)
 int ensure_ranges(gcre_ctx* c, const gcre_uids& u) {
@@ -867,40 +878,6 @@ int ensure_ranges(gcre_ctx* c, const gcre_uids& u) {
   u.n_pairs = (int64_t)T;
   u.n_ranges = (int64_t)R;
   return GCRE_OK;
-}
-
-// ---- merge: global heap starts with the {-inf,-1,-1,0,0} sentinel (join_base.cpp:192-194); the best
-// top_k of {sentinel} U candidates survive, reported in ascending order (format_result :140-151).
-// Ties: smaller joined-path ordinal wins (DESIGN.md "Ties").
-void merge_candidates(std::vector<Candidate>& cands, int top_k, gcre_result* out) {
-  std::sort(cands.begin(), cands.end(), [](const Candidate& a, const Candidate& b) {
-    if (a.score != b.score) return a.score > b.score;
-    return a.path < b.path;
-  });
-  size_t keepn = std::min(cands.size(), (size_t)top_k);
-  const bool with_sentinel = cands.size() < (size_t)top_k;
-  const size_t n_out = keepn + (with_sentinel ? 1 : 0);
-  out->n = (int32_t)n_out;
-  out->scores = (double*)std::calloc(std::max<size_t>(n_out, 1), sizeof(double));
-  out->src = (int32_t*)std::calloc(std::max<size_t>(n_out, 1), sizeof(int32_t));
-  out->trg = (int32_t*)std::calloc(std::max<size_t>(n_out, 1), sizeof(int32_t));
-  out->cases = (int32_t*)std::calloc(std::max<size_t>(n_out, 1), sizeof(int32_t));
-  out->ctrls = (int32_t*)std::calloc(std::max<size_t>(n_out, 1), sizeof(int32_t));
-  size_t o = 0;
-  if (with_sentinel) {
-    out->scores[o] = -std::numeric_limits<double>::infinity();
-    out->src[o] = -1;
-    out->trg[o] = -1;
-    o++;
-  }
-  for (size_t i = keepn; i-- > 0;) {   // ascending: worst kept first
-    out->scores[o] = cands[i].score;
-    out->src[o] = cands[i].src;
-    out->trg[o] = cands[i].trg;
-    out->cases[o] = cands[i].cases;
-    out->ctrls[o] = cands[i].ctrls;
-    o++;
-  }
 }
 
 // inspect_only (gcre_join_ahead): the mask-independent half of the join -- expansion, inspector, kept rows, recipe, flags, top-k
@@ -2564,6 +2541,33 @@ int run_join(gcre_ctx* c, const JoinPlan& jp, gcre_result* out, JoinMode mode) {
 
 }  // namespace
 
+int gcre_host::join_once(gcre_ctx* c, const JoinPlan& jp, gcre_result* out) { return run_join(c, jp, out); }
+
+// GCRE_INSPECT_CACHE=0: every join inspects, whatever the caller asked for (cross-check)
+bool gcre_host::inspect_cache_allowed() {
+  static const bool off = std::getenv("GCRE_INSPECT_CACHE") && std::atoi(std::getenv("GCRE_INSPECT_CACHE")) == 0;
+  return !off;
+}
+
+void gcre_host::start_table_prefetch(gcre_ctx* c, gcre_uids* u, int64_t P, int window) {
+  u->prefetch.reset(new gcre_uids::Prefetch());
+  gcre_uids::Prefetch* pf = u->prefetch.get();
+  pf->first = 0; pf->count = P; pf->score_b = 0; pf->score_e = P; pf->plane_b = 0; pf->plane_e = P;
+  const int nkt = (window + kSparseTile - 1) / kSparseTile;
+  const bool with_quads = c->g.method == 1 && c->ie_quad && c->d_ladder;
+  const gcre_ctx* cc = c;
+  pf->th = std::thread([u, pf, P, nkt, with_quads, cc]() {
+    HostTimer hb("prefetched tables: build (helper thread)");
+    build_segments_host(*u, 0, P, 0, P, 0, P, pf->segs, &pf->nscored);
+    pf->ready = true;
+    if (with_quads && (int64_t)pf->segs.size() < ((int64_t)1 << 30)) {
+      pf->q_warm = warm_segments(cc, pf->nscored, nkt);
+      build_quads_host(*u, pf->segs, 0, pf->nscored, pf->q_warm, pf->quads, &pf->quad_begin);
+      pf->quads_ready = true;
+    }
+  });
+}
+
 // ================================================================================================
 // C ABI
 // ================================================================================================
@@ -2797,12 +2801,6 @@ int gcre_set_value_table(gcre_ctx* c, const double* table, int nrow, int ncol, i
   if (c->have_perms && c->mt_stale && sparse_enabled(c))
     if (int rc = transpose_masks(c)) return rc;
   return GCRE_OK;
-}
-
-// GCRE_INSPECT_CACHE=0: every join inspects, whatever the caller asked for (cross-check)
-static bool inspect_cache_allowed() {
-  static const bool off = std::getenv("GCRE_INSPECT_CACHE") && std::atoi(std::getenv("GCRE_INSPECT_CACHE")) == 0;
-  return !off;
 }
 
 int gcre_set_inspect_cache(gcre_ctx* c, int on) {
@@ -3237,547 +3235,6 @@ int gcre_resolve_count_locs(const int32_t* trg_uids, int64_t n_uids, const int32
     out_location[k] = (it == map.end()) ? 0 : it->second.second;
   }
   return GCRE_OK;
-}
-
-int gcre_process_paths(gcre_ctx* c, const gcre_pp_input* in, gcre_result out[5]) {
-  if (!c || !in || !out) return fail(c, GCRE_ERR_ARG, "bad process_paths arguments");
-  (void)hipSetDevice(c->device);
-  for (int i = 0; i < 5; i++) {
-    std::memset(&out[i], 0, sizeof out[i]);
-    out[i].n = -1;   // NULL list entry, wrapper.cpp:223
-  }
-  const int L = in->path_length;
-  // the tallies armed for this call (gcre_process_paths_set_tally): taken now, so that every road out leaves none armed
-  gcre_gene_tally* tallies[6];
-  bool any_tally = false;
-  for (int i = 0; i < 6; i++) {
-    tallies[i] = c->pp_tally[i];
-    c->pp_tally[i] = nullptr;
-    any_tally = any_tally || tallies[i] != nullptr;
-  }
-  if (any_tally && in->shard_world > 1)
-    return fail(c, GCRE_ERR_ARG, "a gene tally cannot be armed for one device of several: merging tallies across devices is not supported");
-  gcre_exceed* exceeds[6];
-  bool any_exceed = false;
-  for (int i = 0; i < 6; i++) {
-    exceeds[i] = c->pp_exceed[i];
-    c->pp_exceed[i] = nullptr;
-    any_exceed = any_exceed || exceeds[i] != nullptr;
-  }
-  if (any_exceed && in->shard_world > 1)
-    return fail(c, GCRE_ERR_ARG, "exceedance counts cannot be armed for one device of several: add the counts of whole runs on the host");
-  gcre_hits* hit_lists[6];
-  bool any_hits = false;
-  for (int i = 0; i < 6; i++) {
-    hit_lists[i] = c->pp_hits[i];
-    c->pp_hits[i] = nullptr;
-    any_hits = any_hits || hit_lists[i] != nullptr;
-  }
-  if (any_hits && in->shard_world > 1)
-    return fail(c, GCRE_ERR_ARG, "a hit list cannot be armed for one device of several: merging lists across devices is not supported");
-  gcre_profile total{};
-  auto add_prof = [&]() {
-    total.null_kernel_ms += c->prof.null_kernel_ms;
-    total.null_kernel_launches += c->prof.null_kernel_launches;
-    total.stats_kernel_ms += c->prof.stats_kernel_ms;
-    total.select_ms += c->prof.select_ms;
-    total.total_ms += c->prof.total_ms;
-    total.paths += c->prof.paths;
-    total.scores += c->prof.scores;
-    total.null_alg_bytes += c->prof.null_alg_bytes;
-    total.null_row_loads += c->prof.null_row_loads;
-    total.ie_launches += c->prof.ie_launches;
-    total.ie_overlap_lists += c->prof.ie_overlap_lists;
-    total.ie_hinted_joins += c->prof.ie_hinted_joins;
-    total.ie_plane_joins += c->prof.ie_plane_joins;
-    total.ie_lookup_tiles += c->prof.ie_lookup_tiles;
-    total.prepare_ms += c->prof.prepare_ms;
-    total.inspect_ms += c->prof.inspect_ms;
-  };
-
-  int rc = gcre_set_value_table(c, in->value_table, in->vt_rows, in->vt_cols, in->vt_col_major);   // wrapper.cpp:213
-  if (rc != GCRE_OK) return rc;
-  // a context whose masks were generated on the device (gcre_generate_perm_masks) or uploaded packed keeps them
-  // when the caller passes no matrix; otherwise wrapper.cpp:214
-  if (!(in->perm_cases == nullptr && in->perm_rows == 0 && c->have_perms))
-    rc = gcre_set_perm_cases(c, in->perm_cases, in->perm_rows, c->g.n, in->perm_col_major);
-  if (rc != GCRE_OK) return rc;
-
-  gcre_pathset *parsed1 = nullptr, *parsed2 = nullptr, *paths1 = nullptr, *paths2 = nullptr, *paths3 = nullptr;
-  std::vector<gcre_pathset*> temps;
-  gcre_uids** uids_to_free = nullptr;
-  bool multi_window = false, cache_before = c->insp_cache;
-  auto cleanup = [&]() {
-    if (multi_window) c->insp_cache = cache_before;
-    if (uids_to_free)
-      for (int i = 0; i < 6; i++) { free_uids(uids_to_free[i]); uids_to_free[i] = nullptr; }
-    for (auto* p : temps) gcre_pathset_free(p);
-    for (auto* p : {parsed1, parsed2, paths1, paths2, paths3}) gcre_pathset_free(p);
-  };
-  auto total_paths = [](const gcre_level& lv) {
-    int64_t t = 0;
-    for (int64_t i = 0; i < lv.n_uids; i++) t += std::max(lv.uid_count[i], 0);
-    return t;
-  };
-  // red/red_index: what the join really adds to paths0 (gcre_uids_set_reduced) -- checked per join, never trusted.
-  // The join index of a level is uploaded once and serves every permutation window.
-  gcre_uids* level_uids[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  uids_to_free = level_uids;
-  int pp_window = 0;   // permutations per window, once it is known (below)
-  auto join = [&](int plen, int lvi, const gcre_pathset* p0, const gcre_pathset* p1, gcre_pathset* res,
-                  gcre_result* o, const gcre_pathset* red = nullptr, const int32_t* red_index = nullptr,
-                  int64_t n_red = 0) -> int {
-    const gcre_level& lv = in->level[lvi];
-    gcre_uids*& u = level_uids[lvi];
-    if (!u) {
-      u = make_uids(c, plen, lv.uid_count, lv.uid_location, lv.n_uids, lv.signs, lv.n_signs);
-      if (!u) return c->last_code;
-    }
-    if (!u->red && red && red_index && n_red >= p1->nrows) {   // once: the operand outlives the windows
-      bool in_range = true;
-      for (int64_t i = 0; i < n_red && in_range; i++) in_range = (int64_t)((uint32_t)red_index[i] & 0x7fffffffu) < red->nrows;
-      if (in_range && gcre_uids_set_reduced(u, red, red_index, n_red) != GCRE_OK) return c->last_code;
-    }
-    JoinPlan jp{u, p0, p1, res, false, 0, 0, nullptr};
-    jp.tally = tallies[lvi];   // (every permutation window folds the same observed scores: harmless)
-    jp.exceed = exceeds[lvi];
-    jp.exceed_observed = c->win_k0 == 0;   // the observed scores once per call, the null values of every window
-    jp.hits = c->win_k0 == 0 ? hit_lists[lvi] : nullptr;   // (the same rule: a list appends)
-    if (in->shard_world > 1) {   // one device of several: its slice of the joined paths, every kept row
-      jp.sharded = true;
-      jp.shard_begin = u->total * in->shard_rank / in->shard_world;
-      jp.shard_end = u->total * (in->shard_rank + 1) / in->shard_world;
-      if (c->hub && c->win_K > 0) {
-        // the devices of this call share their running maxima during the join: one exchange per doubling of a device's
-        // work beyond GCRE_EXCHANGE_UNIT path-tiles (as ResidentPlan.exchange_count; the same on every device)
-        double unit = 2e6;
-        if (const char* e = std::getenv("GCRE_EXCHANGE_UNIT")) unit = std::atof(e);
-        const double work = (double)u->total / in->shard_world * (double)((pp_window + kSparseTile - 1) / kSparseTile);
-        if (unit > 0 && work >= 2 * unit) {
-          // the number of exchanges must be the same on every device BY CONSTRUCTION: a device that cannot get its buffer
-          // fails the call (its thread then fails the hub) instead of silently joining with none -- the others would wait
-          // for it for ever, or pair their round with its next join
-          if (c->d_hub_null.reserve((size_t)c->g.Kpad + 64) != hipSuccess) return fail(c, GCRE_ERR_DEVICE, "no memory for the exchange buffer");
-          double most = 8.0;
-          if (const char* e = std::getenv("GCRE_EXCHANGE_MAX")) most = std::min(std::max(std::atof(e), 1.0), 32.0);
-          jp.exchanges = (int)std::min(most, std::floor(std::log2(work / unit)));
-          jp.d_null_out = c->d_hub_null.p;
-          jp.exchange_user = c;
-          c->hub_level = lvi;          // 0..5 = levels 1a, 1b, 2, 3, 4, 5
-          c->hub_round = 0;
-          jp.exchange = [](void* user, void* d_null, int32_t k0, int32_t k1) -> int {
-            gcre_ctx* cc = (gcre_ctx*)user;
-            std::vector<float> v((size_t)std::max(k1 - k0, 0));
-            if (v.empty()) return 0;
-            const uint64_t tag = ((uint64_t)(uint32_t)cc->hub_level << 48) ^ ((uint64_t)(uint32_t)k0 << 16) ^ (uint64_t)(cc->hub_round++ & 0xffff);
-            if (cc->comm) {
-              // RCCL: the maxima never leave the devices.  The threads meet first (same level, window and exchange on
-              // every device, under the hub's deadline), then each issues the in-place MAX all-reduce on its stream
-              if (cc->hub->meet(tag) != 0) return 1;
-              const ncclResult_t nr = RcclApi::get().all_reduce(d_null, d_null, v.size(), ncclFloat32, ncclMax, cc->comm, cc->stream);
-              cc->rccl_calls++;
-              g_rccl_collectives++;
-              if (nr != ncclSuccess || hipStreamSynchronize(cc->stream) != hipSuccess) { cc->hub->fail(); return 1; }
-              return 0;
-            }
-            if (hipMemcpy(v.data(), d_null, v.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) { cc->hub->fail(); return 1; }
-            if (cc->hub->reduce(v, tag) != 0) return 1;
-            return hipMemcpy(d_null, v.data(), v.size() * 4, hipMemcpyHostToDevice) == hipSuccess ? 0 : 1;
-          };
-        }
-      }
-    }
-    gcre_result tmp;
-    int r = run_join(c, jp, &tmp);
-    if (r != GCRE_OK) { gcre_result_free(&tmp); return r; }
-    if (o && c->comm && c->hub && c->win_K > 0 && tmp.null_max) {   // (the 1a join's result is discarded: nothing to merge)
-      // merge_scores across devices (src/methods.h:34-37) over RCCL: element-wise MAX all-reduce of this window's f32 null
-      // maxima, in place on the device -- exact for any sharding (f32 max is associative, the values are f32-rounded).
-      // Every device then returns the merged maxima; the caller's host-side MAX over devices changes nothing any more.
-      const uint64_t tag = ((uint64_t)(uint32_t)lvi << 48) ^ ((uint64_t)(uint32_t)c->win_k0 << 16) ^ 0xffffull;
-      if (c->hub->meet(tag) != 0) { gcre_result_free(&tmp); return fail(c, GCRE_ERR_DEVICE, "the devices did not meet for the level's RCCL merge"); }
-      float* d = (float*)(c->d_null + c->win_k0);
-      const ncclResult_t nr = RcclApi::get().all_reduce(d, d, (size_t)c->win_K, ncclFloat32, ncclMax, c->comm, c->stream);
-      c->rccl_calls++;
-      g_rccl_collectives++;
-      hipError_t he = nr == ncclSuccess ? hipMemcpyAsync(tmp.null_max, d, (size_t)c->win_K * 4, hipMemcpyDeviceToHost, c->stream) : hipErrorUnknown;
-      if (he == hipSuccess) he = hipStreamSynchronize(c->stream);
-      if (he != hipSuccess) {
-        c->hub->fail();
-        gcre_result_free(&tmp);
-        return fail(c, GCRE_ERR_DEVICE, std::string("RCCL all-reduce of the null maxima failed: ") + (nr != ncclSuccess ? RcclApi::get().error_string(nr) : hipGetErrorString(he)));
-      }
-    }
-    add_prof();
-    if (o) *o = tmp; else gcre_result_free(&tmp);
-    return GCRE_OK;
-  };
-#define PP_REQUIRE(ptr)            \
-  do {                             \
-    if (!(ptr)) { cleanup(); return c->last_code != GCRE_OK ? c->last_code : GCRE_ERR_DEVICE; } \
-  } while (0)
-#define PP_TRY(expr)               \
-  do {                             \
-    int r__ = (expr);              \
-    if (r__ != GCRE_OK) { cleanup(); return r__; } \
-  } while (0)
-
-  const int ncol = c->g.n;
-  // Large permutation counts run in windows of whole 2048-permutation tiles: the count planes of the kept sets are per
-  // tile, and a window is as many tiles as fit next to the rows.  Scores and top-k lists do not depend on the window (the
-  // first window's are returned); the null maxima of the windows are concatenated.
-  std::vector<int64_t> set_rows = {in->data1_rows, in->data2_rows};
-  for (int lv = 0; lv < 4 && lv <= L; lv++)
-    if (lv != 1) set_rows.push_back(total_paths(in->level[lv]));
-  const int Kall = c->g.K;
-  int win = std::max(1, gcre_plan_perm_window(c, set_rows.data(), (int)set_rows.size()));
-  if (in->window_perms > 0) {
-    win = in->window_perms >= Kall ? std::max(Kall, 1) : std::max(kSparseTile, in->window_perms / kSparseTile * kSparseTile);
-  } else if (Kall > kSparseTile && sparse_enabled(c)) {
-    // A context without a pooled plane buffer of the full size (the R shim makes a fresh context per call, as the
-    // reference does) has to hipMalloc the planes: ~40 ms per GB here, 3 KB per kept row and tile.  Against ~25 ms of
-    // repeated inspector work per extra window, few tiles per window win: w* = sqrt(25 ms * tiles / (ms per tile)).
-    // (A set above the recipe limit stores no planes.)
-    const int nkt_all = (Kall + kSparseTile - 1) / kSparseTile;
-    int64_t biggest = 0;
-    for (size_t i = 2; i < set_rows.size(); i++) {
-      const double full = (double)set_rows[i] * c->g.method * 3072.0 * nkt_all;
-      if (full <= (double)c->planes_out_max) biggest = std::max(biggest, set_rows[i]);
-    }
-    const double ms_per_tile = (double)biggest * c->g.method * 3072.0 / 1e9 * 40.0;
-    const size_t full_bytes = (size_t)biggest * c->g.method * 3072 * (size_t)((win + kSparseTile - 1) / kSparseTile);
-    bool pooled = false;
-    for (const auto& pb : c->plane_pool) pooled = pooled || pb.bytes >= full_bytes;
-    if (ms_per_tile > 1.0 && !pooled) {
-      const int w = std::max(1, (int)std::sqrt(25.0 * nkt_all / ms_per_tile));
-      win = std::min(win, w * kSparseTile);
-    }
-  }
-  pp_window = std::max(1, std::min(win, std::max(Kall, 1)));
-  // The last level's segment table and quads (tens of milliseconds of host work at 2.5 M uids) depend on its join index
-  // only: a helper thread builds them while the first levels run (GCRE_PREFETCH_TABLES=0: built when the join asks)
-  if (L >= 3 && Kall > 0 && in->shard_world <= 1 && sparse_enabled(c) && (c->null_kernel == 0 || c->null_kernel == 3) &&
-      !(std::getenv("GCRE_PREFETCH_TABLES") && std::atoi(std::getenv("GCRE_PREFETCH_TABLES")) == 0)) {
-    const gcre_level& lv = in->level[L];
-    const int64_t P = total_paths(lv);
-    if (lv.n_uids > 100000 && P > 0 && P <= c->chunk_paths && !level_uids[L]) {
-      gcre_uids* u = make_uids(c, L, lv.uid_count, lv.uid_location, lv.n_uids, lv.signs, lv.n_signs);
-      if (!u) { cleanup(); return c->last_code; }
-      level_uids[L] = u;
-      u->prefetch.reset(new gcre_uids::Prefetch());
-      gcre_uids::Prefetch* pf = u->prefetch.get();
-      pf->first = 0; pf->count = P; pf->score_b = 0; pf->score_e = P; pf->plane_b = 0; pf->plane_e = P;
-      const int nkt = (pp_window + kSparseTile - 1) / kSparseTile;
-      const bool with_quads = c->g.method == 1 && c->ie_quad && c->d_ladder;
-      const gcre_ctx* cc = c;
-      pf->th = std::thread([u, pf, P, nkt, with_quads, cc]() {
-        HostTimer hb("prefetched tables: build (helper thread)");
-        build_segments_host(*u, 0, P, 0, P, 0, P, pf->segs, &pf->nscored);
-        pf->ready = true;
-        if (with_quads && (int64_t)pf->segs.size() < ((int64_t)1 << 30)) {
-          pf->q_warm = warm_segments(cc, pf->nscored, nkt);
-          build_quads_host(*u, pf->segs, 0, pf->nscored, pf->q_warm, pf->quads, &pf->quad_begin);
-          pf->quads_ready = true;
-        }
-      });
-    }
-  }
-  std::vector<float> null_all[5];
-  // several windows: the joins of the 2nd..nth window start at their null kernels (inspection cache; the operands below
-  // are made once, so that every window joins the same sets)
-  multi_window = Kall > win;
-  if (multi_window) c->insp_cache = inspect_cache_allowed();
-  gcre_pathset *zero1 = nullptr, *input1 = nullptr, *zero2 = nullptr, *input2 = nullptr, *input_l2 = nullptr, *input_l3 = nullptr;
-  for (int k0 = 0; k0 < std::max(Kall, 1); k0 += win) {
-    const bool first_window = k0 == 0;
-    if (Kall > 0) PP_TRY(gcre_set_perm_window(c, k0, std::min(Kall, k0 + win)));
-    gcre_result wout[5];
-    for (int i = 0; i < 5; i++) { std::memset(&wout[i], 0, sizeof wout[i]); wout[i].n = -1; }
-    gcre_result* const out_w = first_window ? out : wout;
-    auto fold = [&]() {   // this window's maxima behind the ones we have; later windows only contribute maxima
-      for (int i = 0; i < 5; i++) {
-        if (out_w[i].n < 0) continue;
-        null_all[i].insert(null_all[i].end(), out_w[i].null_max, out_w[i].null_max + out_w[i].n_perm);
-        if (!first_window) gcre_result_free(&out_w[i]);
-      }
-    };
-    (void)fold;
-    if (!parsed1) parsed1 = gcre_pathset_from_dense(c, in->data1, in->data1_rows, ncol, in->data_col_major);   // wrapper.cpp:216-217
-    PP_REQUIRE(parsed1);
-
-    if (L >= 1) {   // wrapper.cpp:225-244
-      if (!c->quiet && first_window) std::printf("Processing Path Length: %d\n", 1);
-      if (!paths1) paths1 = new_pathset(c, total_paths(in->level[0]), true);
-      PP_REQUIRE(paths1);
-      if (!zero1) temps.push_back(zero1 = gcre_pathset_zeros(c, in->n_data_inds[0]));
-      PP_REQUIRE(zero1);
-      if (!input1) temps.push_back(input1 = gcre_pathset_select(c, parsed1, in->data_inds[0], in->n_data_inds[0]));
-      PP_REQUIRE(input1);
-      PP_TRY(join(1, 0, zero1, input1, paths1, nullptr, parsed1, in->data_inds[0], in->n_data_inds[0]));   // result discarded, wrapper.cpp:233
-
-      if (!c->quiet && first_window) std::printf("Processing Path Length: %d\n", 1);
-      if (!zero2) temps.push_back(zero2 = gcre_pathset_zeros(c, in->n_data_inds[1]));
-      PP_REQUIRE(zero2);
-      if (!parsed2) parsed2 = gcre_pathset_from_dense(c, in->data2, in->data2_rows, ncol, in->data_col_major);
-      PP_REQUIRE(parsed2);
-      if (!input2) temps.push_back(input2 = gcre_pathset_select(c, parsed2, in->data_inds[1], in->n_data_inds[1]));
-      PP_REQUIRE(input2);
-      PP_TRY(join(1, 1, zero2, input2, nullptr, &out_w[0], parsed2, in->data_inds[1], in->n_data_inds[1]));
-    }
-    if (L >= 2) {   // wrapper.cpp:246-253
-      if (!c->quiet && first_window) std::printf("Processing Path Length: %d\n", 2);
-      if (!paths2) paths2 = new_pathset(c, total_paths(in->level[2]), true);
-      PP_REQUIRE(paths2);
-      // the sequence is known here: when level 3's rows are too many to leave with count planes they leave with a recipe
-      // whose operand is this set -- which then must not be recipe-only itself (it would be rebuilt from bit lists)
-      if (L >= 4 && plane_bytes(c, total_paths(in->level[3]), 2) > c->planes_out_max) paths2->planes_wanted = true;
-      if (L >= 5) paths2->planes_wanted = true;   // level 5 adds rows of this set: their planes are read per joined path
-      // the reference reads data_idx2 from r_data_inds3 (wrapper.cpp:207); R passes identical vectors
-      if (!input_l2) temps.push_back(input_l2 = gcre_pathset_select(c, parsed1, in->data_inds[3], in->n_data_inds[3]));
-      gcre_pathset* const input = input_l2;
-      PP_REQUIRE(input);
-      PP_TRY(join(2, 2, paths1, input, paths2, &out_w[1], parsed1, in->data_inds[3], in->n_data_inds[3]));
-    }
-    if (L >= 3) {   // wrapper.cpp:255-262
-      if (!c->quiet && first_window) std::printf("Processing Path Length: %d\n", 3);
-      if (!paths3) paths3 = new_pathset(c, total_paths(in->level[3]), true);
-      PP_REQUIRE(paths3);
-      if (!input_l3) temps.push_back(input_l3 = gcre_pathset_select(c, parsed1, in->data_inds[3], in->n_data_inds[3]));
-      gcre_pathset* const input = input_l3;
-      PP_REQUIRE(input);
-      PP_TRY(join(3, 3, paths2, input, paths3, &out_w[2], parsed1, in->data_inds[3], in->n_data_inds[3]));
-    }
-    if (L >= 4) {   // wrapper.cpp:264-269
-      if (!c->quiet && first_window) std::printf("Processing Path Length: %d\n", 4);
-      // paths2[loc] = (c, d) with c already on paths3[idx]: the join adds gene d = the data row level 2 joined at loc
-      // (signed method: level 2 put d into the (-) half when the relation's sign is not 1, gcre.h:71-81 -> bit 31)
-      std::vector<int32_t> added((size_t)in->n_data_inds[3]);
-      for (int64_t i = 0; i < in->n_data_inds[3]; i++) {
-        const bool neg = c->g.method == 2 && i < in->level[2].n_signs && in->level[2].signs[i] != 1;
-        added[(size_t)i] = (int32_t)((uint32_t)in->data_inds[3][i] | (neg ? 0x80000000u : 0u));
-      }
-      PP_TRY(join(4, 4, paths3, paths2, nullptr, &out_w[3], parsed1, added.data(), (int64_t)added.size()));
-    }
-    if (L >= 5) {   // wrapper.cpp:271-276
-      if (!c->quiet && first_window) std::printf("Processing Path Length: %d\n", 5);
-      // paths3[loc] = (c, d, e) with c on paths3[idx]: the join adds the 2-gene path (d, e) = paths2[second relation],
-      // and the second relation of joined path q of level 3 is the paths1 row it joined: location3[uid] + offset
-      std::vector<int32_t> second;
-      {
-        const gcre_level& l3 = in->level[3];
-        for (int64_t i = 0; i < l3.n_uids; i++) {
-          // signed method: (d, e) sits in paths3[loc] with both halves swapped when the relation (c, d) is not positive
-          const bool neg = c->g.method == 2 && i < l3.n_signs && l3.signs[i] != 1;
-          for (int32_t t = 0; t < l3.uid_count[i]; t++)
-            second.push_back((int32_t)((uint32_t)(l3.uid_location[i] + t) | (neg ? 0x80000000u : 0u)));
-        }
-      }
-      PP_TRY(join(5, 5, paths3, paths3, nullptr, &out_w[4], paths2, second.data(), (int64_t)second.size()));
-    }
-    fold();
-    if (Kall == 0) break;
-  }
-  for (auto* p : temps) gcre_pathset_free(p);   // the operand copies (the same rows served every window)
-  temps.clear();
-  if (multi_window) {
-    c->insp_cache = cache_before;
-    if (!cache_before) (void)gcre_drop_inspections(c, 1);
-  }
-  if (Kall > 0) PP_TRY(gcre_set_perm_window(c, 0, Kall));
-  for (int i = 0; i < 5; i++) {
-    if (out[i].n < 0 || Kall == 0) continue;
-    std::free(out[i].null_max);
-    out[i].n_perm = Kall;
-    out[i].null_max = (float*)std::calloc((size_t)Kall, sizeof(float));
-    std::memcpy(out[i].null_max, null_all[i].data(), (size_t)Kall * sizeof(float));
-  }
-  if (!c->quiet) std::printf("[success]\n");   // wrapper.cpp:278
-  cleanup();
-  c->prof = total;
-  return GCRE_OK;
-#undef PP_REQUIRE
-#undef PP_TRY
-}
-
-// ---- several devices, one process (include/gcre_hip.h) ----
-int gcre_process_paths_devices(int method, int n_cases, int n_ctrls, int iterations, int top_k, const int* devices,
-                               int n_devices, const gcre_pp_input* in, gcre_result out[5], char* err, size_t errlen) {
-  auto say = [&](const std::string& m) {
-    if (err && errlen) std::snprintf(err, errlen, "%s", m.c_str());
-  };
-  if (!in || !out) { say("bad arguments"); return GCRE_ERR_ARG; }
-  for (int i = 0; i < 5; i++) { std::memset(&out[i], 0, sizeof out[i]); out[i].n = -1; }
-  int visible = 0;
-  if (hipGetDeviceCount(&visible) != hipSuccess || visible <= 0) { say("no HIP device: libgcre_hip has no CPU fallback"); return GCRE_ERR_DEVICE; }
-  std::vector<int> dev;
-  if (n_devices <= 0) n_devices = visible;
-  for (int i = 0; i < n_devices; i++) dev.push_back(devices ? devices[i] : i % visible);
-  const int N = (int)dev.size();
-  // contexts first (one per device), so that every device can be asked for its window before anybody starts
-  std::vector<gcre_ctx*> ctx((size_t)N, nullptr);
-  int rc = GCRE_OK;
-  for (int r = 0; r < N && rc == GCRE_OK; r++) {
-    ctx[(size_t)r] = gcre_create(method, n_cases, n_ctrls, iterations, dev[(size_t)r]);
-    if (!ctx[(size_t)r]) { say(gcre_last_error(nullptr)); rc = GCRE_ERR_DEVICE; break; }
-    ctx[(size_t)r]->quiet = ctx[(size_t)r]->quiet || r > 0;   // the reference's progress lines once
-    rc = gcre_set_top_k(ctx[(size_t)r], top_k);
-    if (rc != GCRE_OK) say(gcre_last_error(ctx[(size_t)r]));
-  }
-  int window = 0;
-  if (rc == GCRE_OK && N > 1 && iterations > 0) {
-    // the smallest window any device plans: all of them walk the same windows (their maxima are merged per window)
-    std::vector<int64_t> set_rows = {in->data1_rows, in->data2_rows};
-    for (int lv = 0; lv < 4 && lv <= in->path_length; lv++)
-      if (lv != 1) {
-        int64_t t = 0;
-        for (int64_t i = 0; i < in->level[lv].n_uids; i++) t += std::max(in->level[lv].uid_count[i], 0);
-        set_rows.push_back(t);
-      }
-    window = iterations;
-    for (int r = 0; r < N; r++) {
-      (void)hipSetDevice(dev[(size_t)r]);
-      window = std::min(window, std::max(1, gcre_plan_perm_window(ctx[(size_t)r], set_rows.data(), (int)set_rows.size())));
-    }
-  }
-  std::vector<std::array<gcre_result, 5>> part((size_t)N);
-  std::vector<int> rcs((size_t)N, GCRE_OK);
-  ExchangeHub hub;   // where the device threads MAX-merge their running maxima during the large joins
-  hub.n = N;
-  if (const char* e = std::getenv("GCRE_HUB_TIMEOUT_S")) hub.timeout_s = std::max(0.01, std::atof(e));
-  // RCCL communicators, one per device, when every device is listed once (RCCL refuses a device twice: the one-GPU
-  // rehearsal stays on the host hub) and the library loads.  GCRE_RCCL=0: never; GCRE_RCCL=force: also for one device
-  // (one-rank collectives: what a one-GPU box can exercise of this path).
-  std::vector<ncclComm_t> comms;
-  {
-    const char* mode = std::getenv("GCRE_RCCL");
-    const bool force = mode && std::strcmp(mode, "force") == 0;
-    bool distinct = true;
-    for (int a = 0; a < N; a++)
-      for (int b = a + 1; b < N; b++) distinct = distinct && dev[(size_t)a] != dev[(size_t)b];
-    if (rc == GCRE_OK && distinct && (N > 1 || force) && iterations > 0 && RcclApi::get().ok) {
-      comms.assign((size_t)N, nullptr);
-      if (RcclApi::get().comm_init_all(comms.data(), N, dev.data()) != ncclSuccess) {
-        comms.clear();   // (no communicator: the host hub serves the call)
-        (void)hipGetLastError();
-      }
-    }
-  }
-  if (rc == GCRE_OK) {
-    auto work = [&](int r) {
-      gcre_pp_input mine = *in;
-      mine.shard_rank = N > 1 ? r : 0;
-      mine.shard_world = N > 1 ? N : 0;
-      mine.window_perms = N > 1 ? window : in->window_perms;
-      ctx[(size_t)r]->hub = (N > 1 || !comms.empty()) ? &hub : nullptr;
-      ctx[(size_t)r]->comm = comms.empty() ? nullptr : comms[(size_t)r];
-      rcs[(size_t)r] = gcre_process_paths(ctx[(size_t)r], &mine, part[(size_t)r].data());
-      ctx[(size_t)r]->hub = nullptr;
-      ctx[(size_t)r]->comm = nullptr;
-      if (rcs[(size_t)r] != GCRE_OK) hub.fail();   // nobody waits for a device that has given up
-    };
-    std::vector<std::thread> th;
-    for (int r = 1; r < N; r++) th.emplace_back(work, r);
-    work(0);
-    for (auto& t : th) t.join();
-    for (int r = 0; r < N; r++)
-      if (rcs[(size_t)r] != GCRE_OK && rc == GCRE_OK) {
-        rc = rcs[(size_t)r];
-        say("device " + std::to_string(dev[(size_t)r]) + ": " + gcre_last_error(ctx[(size_t)r]) +
-            (hub.timed_out ? " (a device waited longer than GCRE_HUB_TIMEOUT_S for the others at a threshold exchange)" : ""));
-      }
-  }
-  if (rc == GCRE_OK) {
-    // merge_scores / format_result (methods.h:25-39, join_base.cpp:138-154) across devices: f32 MAX of the maxima (exact
-    // for any sharding: f32 max is associative, every device holds f32-rounded values), best top_k of all tables with the
-    // canonical tie rule (smaller joined-path ordinal = smaller (idx, loc)), the sentinel when fewer than top_k exist
-    for (int lv = 0; lv < 5; lv++) {
-      if (part[0][(size_t)lv].n < 0) continue;
-      gcre_result& o = out[lv];
-      const int K = part[0][(size_t)lv].n_perm;
-      o.n_perm = K;
-      o.null_max = (float*)std::calloc((size_t)std::max(K, 1), sizeof(float));
-      std::vector<Candidate> cands;
-      for (int r = 0; r < N; r++) {
-        const gcre_result& p = part[(size_t)r][(size_t)lv];
-        for (int k = 0; k < K; k++) o.null_max[k] = std::max(o.null_max[k], p.null_max[k]);
-        for (int i = 0; i < p.n; i++)
-          if (p.src[i] >= 0) cands.push_back(Candidate{p.scores[i], ((int64_t)p.src[i] << 32) | (uint32_t)p.trg[i], p.src[i], p.trg[i], p.cases[i], p.ctrls[i]});
-      }
-      std::sort(cands.begin(), cands.end(), [](const Candidate& a, const Candidate& b) {
-        if (a.score != b.score) return a.score > b.score;
-        return a.path < b.path;
-      });
-      const size_t keepn = std::min(cands.size(), (size_t)top_k);
-      const bool with_sentinel = cands.size() < (size_t)top_k;
-      const size_t n_out = keepn + (with_sentinel ? 1 : 0);
-      o.n = (int32_t)n_out;
-      o.scores = (double*)std::calloc(std::max<size_t>(n_out, 1), sizeof(double));
-      o.src = (int32_t*)std::calloc(std::max<size_t>(n_out, 1), sizeof(int32_t));
-      o.trg = (int32_t*)std::calloc(std::max<size_t>(n_out, 1), sizeof(int32_t));
-      o.cases = (int32_t*)std::calloc(std::max<size_t>(n_out, 1), sizeof(int32_t));
-      o.ctrls = (int32_t*)std::calloc(std::max<size_t>(n_out, 1), sizeof(int32_t));
-      size_t w = 0;
-      if (with_sentinel) {
-        o.scores[w] = -std::numeric_limits<double>::infinity();
-        o.src[w] = o.trg[w] = -1;
-        w++;
-      }
-      for (size_t i = keepn; i-- > 0;) {
-        o.scores[w] = cands[i].score;
-        o.src[w] = cands[i].src;
-        o.trg[w] = cands[i].trg;
-        o.cases[w] = cands[i].cases;
-        o.ctrls[w] = cands[i].ctrls;
-        w++;
-      }
-    }
-  }
-  for (ncclComm_t cm : comms)
-    if (cm) (void)RcclApi::get().comm_destroy(cm);
-  for (int r = 0; r < N; r++) {
-    if (rcs[(size_t)r] == GCRE_OK)
-      for (int lv = 0; lv < 5; lv++)
-        if (part[(size_t)r][(size_t)lv].n >= 0 || part[(size_t)r][(size_t)lv].null_max) gcre_result_free(&part[(size_t)r][(size_t)lv]);
-    if (ctx[(size_t)r]) {
-      (void)hipSetDevice(dev[(size_t)r]);
-      gcre_destroy(ctx[(size_t)r]);
-    }
-  }
-  return rc;
-}
-
-int64_t gcre_rccl_collectives(void) { return g_rccl_collectives.load(); }
-
-int gcre_rccl_selftest(int device, char* err, size_t errlen) {
-  auto say = [&](const std::string& m) {
-    if (err && errlen) std::snprintf(err, errlen, "%s", m.c_str());
-  };
-  RcclApi& api = RcclApi::get();
-  if (!api.ok) { say("librccl.so not found (or GCRE_RCCL=0)"); return GCRE_ERR_DEVICE; }
-  if (hipSetDevice(device) != hipSuccess) { say("no such device"); return GCRE_ERR_DEVICE; }
-  ncclComm_t comm = nullptr;
-  ncclResult_t nr = api.comm_init_all(&comm, 1, &device);
-  if (nr != ncclSuccess) { say(std::string("ncclCommInitAll: ") + api.error_string(nr)); return GCRE_ERR_DEVICE; }
-  const size_t n = 4096;
-  std::vector<float> h(n), back(n);
-  for (size_t i = 0; i < n; i++) h[i] = (float)((i * 2654435761u) % 1000u) / 8.0f;
-  float* d = nullptr;
-  hipStream_t st = nullptr;
-  int rc = GCRE_OK;
-  if (hipMalloc((void**)&d, n * 4) != hipSuccess || hipStreamCreate(&st) != hipSuccess) rc = GCRE_ERR_DEVICE;
-  if (rc == GCRE_OK && hipMemcpyAsync(d, h.data(), n * 4, hipMemcpyHostToDevice, st) != hipSuccess) rc = GCRE_ERR_DEVICE;
-  if (rc == GCRE_OK) {
-    nr = api.all_reduce(d, d, n, ncclFloat32, ncclMax, comm, st);   // one rank: MAX over {x} = x
-    g_rccl_collectives++;
-    if (nr != ncclSuccess) { say(std::string("ncclAllReduce: ") + api.error_string(nr)); rc = GCRE_ERR_DEVICE; }
-  }
-  if (rc == GCRE_OK && (hipMemcpyAsync(back.data(), d, n * 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess))
-    rc = GCRE_ERR_DEVICE;
-  if (rc == GCRE_OK && std::memcmp(h.data(), back.data(), n * 4) != 0) { say("one-rank MAX all-reduce changed the data"); rc = GCRE_ERR_DEVICE; }
-  if (d) (void)hipFree(d);
-  if (st) (void)hipStreamDestroy(st);
-  (void)api.comm_destroy(comm);
-  return rc;
 }
 
 }  // extern "C"

@@ -1,4 +1,6 @@
 """JoinExec / PathSet level tests of the HIP library against the oracle (pytest -m gpu, real MI355X)."""
+import ctypes
+import functools
 import math
 
 import numpy as np
@@ -387,6 +389,53 @@ def test_rccl_selftest_through_the_librarys_own_binding():
     assert api.rccl_collectives() == before + 1
 
 
+@functools.lru_cache(maxsize=None)
+def two_window_problem(method):
+    """With GCRE_WINDOW_TILES=1 two permutation windows, 2048 + 252: the smallest shape that has a second one.  The problem
+    and the oracle's results, computed once."""
+    p = make_problem(60, 200, 33, 41, 2300, 4, method=method, top_k=11, seed=23, table=small_table(33, 41, 6))
+    return p, oracle.process_paths(p, order="canonical", nthreads=4)
+
+
+@pytest.mark.parametrize("method", ["method1", "method2"])
+def test_a_refused_level_leaves_no_results_and_the_context_as_it_was(method, monkeypatch):
+    """gcre_process_paths (gcre_host_pipeline.hip) on a failing return: level 3's join index names a paths1 row that is not
+    there -- refused on the host before anything of level 3 is launched, in the first of two permutation windows, after
+    levels 1 and 2 had filled their results.  Every out[i] comes back freed and reading as NULL, and the context's permutation
+    window is [0, iterations) again: a join through the join interface returns `iterations` maxima, not the 2048 of the window
+    the call was in, and the same context then runs the unbroken problem to the oracle's results."""
+    monkeypatch.setenv("GCRE_WINDOW_TILES", "1")
+    p, want = two_window_problem(method)
+    lv = p.levels
+    ex = api.JoinExec(p.method, p.n_cases, p.n_ctrls, p.iterations)
+    ex.top_k = p.top_k
+
+    def level2_through_the_join_interface():
+        r2 = ex.join(lv.uids["2"], ex.from_words(want["paths1"]), ex.load(p.data1).select(lv.data_inds["2"]))
+        assert len(r2.null) == p.iterations
+        assert_same_result(r2, want["lst2"])
+
+    try:
+        keep = []
+        inp = api._pp_input(p, keep)
+        count = np.asarray(lv.uids["3"].count)
+        location = np.array(lv.uids["3"].location, dtype=np.int64)
+        location[np.flatnonzero(count > 0)[-1]] = len(lv.data_inds["3"])      # one row past the operand level 3 joins
+        inp.level[3].uid_location = api._ptr(location)
+        outs = (api.gcre_result * 5)()
+        assert ex._lib.gcre_process_paths(ex._h, ctypes.byref(inp), outs) == api.GCRE_ERR_RANGE
+        assert b"uid location out of range" in ex._lib.gcre_last_error(ex._h)
+        for o in outs:
+            assert o.n == -1 and not o.null_max and not o.scores and not o.src
+        level2_through_the_join_interface()
+        got = api.process_paths(p, exec_=ex)
+        for lvl in range(1, 5):
+            assert_same_result(got[f"lst{lvl}"], want[f"lst{lvl}"])
+        level2_through_the_join_interface()
+    finally:
+        ex.close()
+
+
 @pytest.mark.parametrize("method", ["method1", "method2"])
 def test_process_paths_devices_merges_the_maxima_over_rccl(method, monkeypatch):
     """GCRE_RCCL=force: gcre_process_paths_devices creates a communicator even for ONE device and merges every level's null
@@ -394,8 +443,7 @@ def test_process_paths_devices_merges_the_maxima_over_rccl(method, monkeypatch):
     several distinct devices the same code runs with N ranks; on this box it is the one-rank case.  Results: the oracle's."""
     monkeypatch.setenv("GCRE_RCCL", "force")
     monkeypatch.setenv("GCRE_WINDOW_TILES", "1")
-    p = make_problem(60, 200, 33, 41, 2300, 4, method=method, top_k=11, seed=23, table=small_table(33, 41, 6))
-    want = oracle.process_paths(p, order="canonical", nthreads=4)
+    p, want = two_window_problem(method)
     before = api.rccl_collectives()
     got = api.process_paths_devices(p, [0])
     assert api.rccl_collectives() - before == 4 * 2      # lst1..lst4 (the 1a join's result is discarded, its merge is not needed) x 2 windows
