@@ -114,6 +114,9 @@ class gcre_set_input(ctypes.Structure):
 SET_SCORE = np.dtype([("set", "<i8"), ("valid", "<i4"), ("cases", "<i4"), ("ctrls", "<i4"), ("cases_pos", "<i4"),
                       ("ctrls_pos", "<i4"), ("cases_neg", "<i4"), ("ctrls_neg", "<i4"), ("score", "<f8"),
                       ("n_ge", "<i8"), ("pvalue", "<f8")], align=True)
+# gcre_family_score
+FAMILY_SCORE = np.dtype([("n_ge_stepdown", "<i8"), ("exceed", "<u8"), ("observed", "<i8")], align=True)
+FAMILY_KMAX = 10   # GCRE_FAMILY_KMAX
 # gcre_burden
 BURDEN = np.dtype([("total", "<i8"), ("observed", "<i8"), ("n_ge", "<i8"), ("n_le", "<i8"), ("planes", "<i4"),
                    ("p_upper", "<f8"), ("p_lower", "<f8")], align=True)
@@ -133,6 +136,7 @@ EXPORTS = [
     "gcre_rccl_selftest", "gcre_rccl_collectives", "gcre_join_ahead",
     "gcre_decorated_splits", "gcre_decorated_pvalues", "gcre_score_sets",
     "gcre_score_sets_given", "gcre_given_launches",
+    "gcre_score_sets_family", "gcre_family_launches",
     "gcre_set_overlap", "gcre_overlap_launches",
     "gcre_clump_sets", "gcre_clump_launches",
     "gcre_set_patient_counts", "gcre_patient_launches",
@@ -259,6 +263,9 @@ _FEATURES = {
     "given": ("sets", ["gcre_score_sets_given", "gcre_given_launches"], "conditional set scores (gcre_score_sets_given)", {
         "gcre_score_sets_given": (_I, [_V, ctypes.POINTER(gcre_set_input), _P, _P, _I64, _P, _I64, ctypes.POINTER(_I64), _P]),
         "gcre_given_launches": (_I64, [_V])}),
+    "family": ("sets", ["gcre_score_sets_family", "gcre_family_launches"], "family-wise set inference (gcre_score_sets_family)", {
+        "gcre_score_sets_family": (_I, [_V, ctypes.POINTER(gcre_set_input), _P, _I64, ctypes.POINTER(_I64), _P, _P, _P]),
+        "gcre_family_launches": (_I64, [_V])}),
     "overlap": (None, ["gcre_set_overlap"], "carrier overlaps (gcre_set_overlap)", {
         "gcre_set_overlap": (_I, [_V, ctypes.POINTER(gcre_set_input), _P, _I64, _P, _I64, _P, _P]),
         "gcre_overlap_launches": (_I64, [_V])}),
@@ -321,6 +328,7 @@ def _feature_lib(feature: str):
 _decorated_lib = functools.partial(_feature_lib, "decorated")
 _sets_lib = functools.partial(_feature_lib, "sets")
 _given_lib = functools.partial(_feature_lib, "given")
+_family_lib = functools.partial(_feature_lib, "family")
 _overlap_lib = functools.partial(_feature_lib, "overlap")
 _clump_lib = functools.partial(_feature_lib, "clump")
 _patients_lib = functools.partial(_feature_lib, "patients")
@@ -1003,6 +1011,36 @@ class JoinExec:
     def given_launches(self) -> int:
         """Kernels gcre_score_sets_given launched on this context so far."""
         return int(_given_lib().gcre_given_launches(self._h))
+
+    def family_tests(self, sets, rows, signs=None, kmax: bool = False, null: bool = False):
+        """Step-down, k-FWER and FDR over the family of the given sets (gcre_score_sets_family).  ``sets`` /
+        ``rows`` / ``signs`` as ``score_sets`` takes them.  Returns ``(records, family)``: the SET_SCORE records of
+        ``score_sets``, and one FAMILY_SCORE record per set -- ``n_ge_stepdown`` (permutations whose maximum over the sets
+        that do not score strictly higher reaches the set's score), ``exceed`` (null scores of ALL sets and permutations
+        that reach it) and ``observed`` (sets that reach it); a NaN score gives 0 / 0 / 0, an NA member -1 / 0 / -1.
+        With ``kmax`` also float32 [FAMILY_KMAX][iters], row k the (k+1)-th largest null score of every permutation (row 0
+        = ``score_sets(family=True)``'s maxima); with ``null`` also the null matrix, float32 [sets][iters] (NaN rows for
+        sets with an NA member).  ``report.family_columns`` turns these into p-values.  Errors raise GcreError."""
+        lib = _family_lib()
+        n = self.num_cases + self.num_ctrls
+        S = len(sets)
+        inp, keep = _set_input(sets, rows, signs, n)
+        out = np.zeros(max(S, 1), dtype=SET_SCORE)
+        fam = np.zeros(max(S, 1), dtype=FAMILY_SCORE)
+        km = np.zeros((FAMILY_KMAX, self.iters), dtype=np.float32) if kmax else None
+        nul = np.zeros((S, self.iters), dtype=np.float32) if null else None
+        n_out = ctypes.c_int64(0)
+        rc = lib.gcre_score_sets_family(self._h, ctypes.byref(inp), _ptr(out), len(out), ctypes.byref(n_out), _ptr(fam),
+                                        _ptr(km) if kmax and km.size else None, _ptr(nul) if null and nul.size else None)
+        del keep
+        if rc != GCRE_OK:
+            raise GcreError(self._lib.gcre_last_error(self._h).decode())
+        res = (out[:n_out.value], fam[:n_out.value])
+        return res + ((km,) if kmax else ()) + ((nul,) if null else ())
+
+    def family_launches(self) -> int:
+        """k_family_null / k_family_scan / k_family_hist launches of this context so far."""
+        return int(_family_lib().gcre_family_launches(self._h))
 
     def set_overlap(self, sets, rows, a=None, b=None):
         """Carrier overlaps of caller-given sets (gcre_set_overlap).  A set's carrier row is the OR of all

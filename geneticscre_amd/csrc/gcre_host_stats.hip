@@ -1,5 +1,5 @@
 // gcre_host_stats.hip -- the entry points of include/gcre_hip.h that use a context but not the join driver: generated
-// permutation masks, decorated p-values (gcre_decorated.hip), set scores (gcre_sets.hip, conditional: gcre_given.hip) and carrier overlaps
+// permutation masks, decorated p-values (gcre_decorated.hip), set scores (gcre_sets.hip, conditional: gcre_given.hip, family-wise: gcre_family.hip) and carrier overlaps
 // (gcre_overlap.hip), greedy clumps (gcre_clump.hip), carrier tallies per patient (gcre_patients.hip) and burden tests of per-patient weights (gcre_burden.hip), and the per-gene tally (gcre_genes.hip), the null exceedance counts (gcre_exceed.hip,
 // gcre_stepdown.hip) and the hit lists (gcre_hits.hip) as objects.  What a join does with an armed tally, armed counts or
 // an armed list -- check_tally, fold_genes, count_exceed, collect_hits -- is in gcre_host.hip.  Host code only.
@@ -240,19 +240,183 @@ int gcre_decorated_pvalues(gcre_ctx* c, const gcre_dp_input* in, gcre_dp_split* 
   return GCRE_OK;
 }
 
-int gcre_score_sets(gcre_ctx* c, const gcre_set_input* in, gcre_set_score* out, int64_t cap, int64_t* n_out,
-                    float* family_max) {
+}  // extern "C"
+
+namespace {
+
+// What gcre_score_sets_family returns beside the records
+static_assert(kFamilyKmax == GCRE_FAMILY_KMAX, "the header's constant");
+struct FamilyOut {
+  gcre_family_score* fam;   // [n_sets]
+  float* kmax;              // optional [GCRE_FAMILY_KMAX][iterations]
+  float* null_scores;       // optional [n_sets][iterations]
+};
+
+// The slab of gcre_score_sets_family: whole permutation tiles whose null matrix, one row per valid set, stays under
+// GCRE_FAMILY_MAX_MB (GCRE_FAMILY_SLAB_PERMS bounds it further: tests).  One row of one tile above the limit is refused.
+int check_family(gcre_ctx* c, const gcre_set_input* in, const FamilyOut& fo, const std::string& who, int64_t& slab_tiles) {
+  slab_tiles = 0;
+  const int64_t S = in->n_sets;
+  if (S > 0 && !fo.fam) return fail(c, GCRE_ERR_ARG, who + ": NULL argument (fam_out)");
+  int64_t V = 0;
+  for (int64_t s = 0; s < S; s++) V += set_is_valid(in, s) ? 1 : 0;
+  if (V > 0x7fffffff) return fail(c, GCRE_ERR_ARG, who + ": too many sets");
+  const int K = c->g.K;
+  if (V == 0 || K == 0) return GCRE_OK;
+  double mb = 1024;
+  if (const char* e = std::getenv("GCRE_FAMILY_MAX_MB")) mb = std::min(std::max(std::atof(e), 0.0), 1048576.0);   // tests: fractions
+  const double tile_bytes = (double)V * kSetPermTile * 4.0;
+  if (tile_bytes > mb * 1048576.0)
+    return fail(c, GCRE_ERR_ARG, who + ": the null scores of " + std::to_string(V) + " sets under one tile of " +
+                                     std::to_string(kSetPermTile) + " permutations exceed GCRE_FAMILY_MAX_MB");
+  const int64_t tiles = ((int64_t)K + kSetPermTile - 1) / kSetPermTile;
+  slab_tiles = std::min<int64_t>(tiles, (int64_t)(mb * 1048576.0 / tile_bytes));
+  if (const char* e = std::getenv("GCRE_FAMILY_SLAB_PERMS"))
+    slab_tiles = std::min<int64_t>(slab_tiles, std::max<int64_t>(std::atoll(e) / kSetPermTile, 1));
+  return GCRE_OK;
+}
+
+// The family stage of gcre_score_sets_family, behind score_set_rows: V valid sets' union rows and totals are on the device,
+// obs [V] are their observed scores.  The rows of N are the sets in ascending observed order (NaN first, then as doubles,
+// +-0 tie); per slab of `slab_tiles` permutation tiles k_family_null fills N, k_family_scan adds the step-down counts and
+// stores the slab's columns of kmax, k_family_hist adds the pooled histogram; the host takes the suffix sums.  Every count is
+// an exact integer and every column belongs to one slab, so no result depends on the slabs.  Errors stay in `d`.
+void family_stage(gcre_ctx* c, DevScratch& d, const uint64_t* d_rows, const uint32_t* d_tot, const std::vector<int64_t>& vset,
+                  const std::vector<double>& obs, int64_t slab_tiles, const FamilyOut& fo) {
+  const Geometry& g = c->g;
+  const int K = g.K, M = g.method;
+  const int64_t V = (int64_t)vset.size();
+  std::vector<int64_t> order((size_t)V);
+  for (int64_t v = 0; v < V; v++) order[(size_t)v] = v;
+  std::stable_sort(order.begin(), order.end(), [&](int64_t x, int64_t y) {
+    const double a = obs[(size_t)x], b = obs[(size_t)y];
+    const bool na = a != a, nb = b != b;
+    return (na || nb) ? (na && !nb) : a < b;
+  });
+  // per row: the threshold pattern, the end of its tie group, the start of that group, its bin among the distinct patterns
+  std::vector<uint32_t> rank((size_t)V), meta((size_t)((V + 63) / 64 * 64), 0u), pat;   // (meta: zeros up to whole 64 rows)
+  std::vector<int64_t> gstart((size_t)V), bin((size_t)V, -1);
+  for (int64_t i = 0; i < V; i++) {
+    const double o = obs[(size_t)order[(size_t)i]];
+    rank[(size_t)order[(size_t)i]] = (uint32_t)i;
+    const uint32_t thr = f32_threshold(o);
+    const bool end = i + 1 == V || !(obs[(size_t)order[(size_t)(i + 1)]] == o);
+    meta[(size_t)i] = thr | (end ? 0x80000000u : 0u);
+    gstart[(size_t)i] = i > 0 && obs[(size_t)order[(size_t)(i - 1)]] == o ? gstart[(size_t)(i - 1)] : i;
+    if (o != o) continue;   // a NaN score reaches nothing and nothing reaches it
+    if (pat.empty() || pat.back() != thr) pat.push_back(thr);   // (ascending: the threshold is monotone in the score)
+    bin[(size_t)i] = (int64_t)pat.size() - 1;
+  }
+  const int m = (int)pat.size();   // 0: every score is NaN -- no histogram, and the scan counts nothing
+  if (pat.empty()) pat.push_back(0u);
+
+  const int64_t tiles = ((int64_t)K + kSetPermTile - 1) / kSetPermTile;
+  const int64_t max_stride = slab_tiles * kSetPermTile;
+  const uint32_t* d_rank = d.put(rank.data(), (size_t)V);
+  const uint32_t* d_meta = d.put(meta.data(), meta.size());
+  const uint32_t* d_pat = d.put(pat.data(), (size_t)std::max(m, 1));
+  uint32_t* d_N = d.take<uint32_t>((size_t)V * (size_t)max_stride);
+  uint32_t* d_sd = d.take<uint32_t>((size_t)V);
+  unsigned long long* d_hist = d.take<unsigned long long>((size_t)std::max(m, 1));
+  uint32_t* d_kmax = fo.kmax ? d.take<uint32_t>((size_t)kFamilyKmax * (size_t)K) : nullptr;
+  d.zero(d_sd, (size_t)V);
+  d.zero(d_hist, (size_t)std::max(m, 1));
+  FamilyNullArgs na{};
+  fill_set_launch(na, c, d_rows, d_tot, V);
+  na.rank = d_rank;
+  na.N = d_N;
+  // the optional null matrix comes back through a staging buffer of whole rows, at most ~32 MB at a time
+  std::vector<uint32_t> stage;
+  for (int64_t kt0 = 0; d.ok() && kt0 < tiles; kt0 += slab_tiles) {
+    const int64_t nk = std::min(slab_tiles, tiles - kt0);
+    const int64_t stride = nk * kSetPermTile, k0 = kt0 * kSetPermTile;
+    const int live = (int)std::min<int64_t>(stride, (int64_t)K - k0);
+    na.kt0 = (int)kt0;
+    na.nkt = (int)nk;
+    na.stride = stride;
+    {  // fill_set_launch's rule for the blocks per tile, over the slab's tiles
+      const int64_t slots = (int64_t)c->cus * 4 * 8;
+      const int64_t per = std::max<int64_t>(1, (na.npt * nk) / slots);
+      na.pgroups = (int)std::min<int64_t>((na.npt + per - 1) / per, 0x7fffffff / nk);
+    }
+    d.e = launch_family_null(na, M, c->stream);
+    if (d.ok()) c->family_launches++;
+    FamilyScanArgs sa{};
+    sa.N = d_N;
+    sa.meta = d_meta;
+    sa.n_ge = d_sd;
+    sa.kmax = d_kmax;
+    sa.nsets = V;
+    sa.stride = stride;
+    sa.kstride = K;
+    sa.live = live;
+    sa.k0 = (int)k0;
+    if (d.ok()) {
+      d.e = launch_family_scan(sa, c->stream);
+      if (d.ok()) c->family_launches++;
+    }
+    FamilyHistArgs ha{};
+    ha.N = d_N;
+    ha.pat = d_pat;
+    ha.hist = d_hist;
+    ha.nsets = V;
+    ha.stride = stride;
+    ha.live = live;
+    ha.m = m;
+    if (d.ok() && m > 0) {
+      d.e = launch_family_hist(ha, c->cus, c->stream);
+      if (d.ok()) c->family_launches++;
+    }
+    if (fo.null_scores) {
+      const int64_t rows_at_once = std::max<int64_t>(1, ((int64_t)8 << 20) / stride);
+      stage.resize((size_t)std::min(rows_at_once, V) * (size_t)stride);
+      for (int64_t r0 = 0; d.ok() && r0 < V; r0 += rows_at_once) {
+        const int64_t nr = std::min(rows_at_once, V - r0);
+        d.download(stage.data(), d_N + (size_t)r0 * (size_t)stride, (size_t)nr * (size_t)stride);
+        d.sync();
+        if (!d.ok()) break;
+        for (int64_t r = 0; r < nr; r++)
+          std::memcpy(fo.null_scores + (size_t)vset[(size_t)order[(size_t)(r0 + r)]] * (size_t)K + (size_t)k0,
+                      stage.data() + (size_t)r * (size_t)stride, (size_t)live * 4);
+      }
+    }
+  }
+  std::vector<uint32_t> sd((size_t)V);
+  std::vector<unsigned long long> hist((size_t)std::max(m, 1));
+  d.download(sd.data(), d_sd, (size_t)V);
+  d.download(hist.data(), d_hist, (size_t)std::max(m, 1));
+  if (fo.kmax) d.download((uint32_t*)fo.kmax, d_kmax, (size_t)kFamilyKmax * (size_t)K);
+  d.sync();
+  if (!d.ok()) return;
+  for (int b = m - 2; b >= 0; b--) hist[(size_t)b] += hist[(size_t)b + 1];   // exceed per bin: the suffix sums
+  for (int64_t i = V - 2; i >= 0; i--)   // a tie group's count stands at its last row
+    if (!(meta[(size_t)i] >> 31)) sd[(size_t)i] = sd[(size_t)i + 1];
+  for (int64_t i = 0; i < V; i++) {
+    gcre_family_score& f = fo.fam[vset[(size_t)order[(size_t)i]]];
+    if (bin[(size_t)i] < 0) continue;   // a NaN score: 0 / 0 / 0
+    f.n_ge_stepdown = (int64_t)sd[(size_t)i];
+    f.exceed = hist[(size_t)bin[(size_t)i]];
+    f.observed = V - gstart[(size_t)i];
+  }
+}
+
+// gcre_score_sets, and with `fo` gcre_score_sets_family: the same checks, host stage and device stage
+int score_sets_common(gcre_ctx* c, const gcre_set_input* in, gcre_set_score* out, int64_t cap, int64_t* n_out, float* family_max,
+                      const std::string& who, const FamilyOut* fo) {
   if (!c) return GCRE_ERR_ARG;
-  if (!in || !n_out || cap < 0 || (cap > 0 && !out)) return fail(c, GCRE_ERR_ARG, "score_sets: NULL argument");
+  if (!in || !n_out || cap < 0 || (cap > 0 && !out)) return fail(c, GCRE_ERR_ARG, who + ": NULL argument");
   *n_out = 0;
   const Geometry& g = c->g;
   const int K = g.K, M = g.method;
   const int64_t S = in->n_sets;
-  if (int rc = check_sets(c, in, "score_sets")) return rc;
+  if (int rc = check_sets(c, in, who)) return rc;
   *n_out = S;
   if (S > cap)
-    return fail(c, GCRE_ERR_RANGE, "score_sets: " + std::to_string(S) + " sets, room for " + std::to_string(cap) +
+    return fail(c, GCRE_ERR_RANGE, who + ": " + std::to_string(S) + " sets, room for " + std::to_string(cap) +
                                        " records (out of range)");
+  int64_t slab_tiles = 0;
+  if (fo)
+    if (int rc = check_family(c, in, *fo, who, slab_tiles)) return rc;
 
   // the host stage: per valid set the OR of its (+) members and of its (-) members (method 1: of all of them), within the
   // n patients, and their counts; the device rows are [valid set][M][Wp] words, the dword view k_set_null reads
@@ -288,6 +452,15 @@ int gcre_score_sets(gcre_ctx* c, const gcre_set_input* in, gcre_set_score* out, 
     if (M == 2) tot.push_back((uint32_t)(k[2] + k[3]));
   }
   if (family_max) std::fill(family_max, family_max + K, 0.0f);
+  if (fo) {   // what an invalid set, a family without valid sets and a context without permutations keep
+    for (int64_t s = 0; s < S; s++) {
+      gcre_family_score& f = fo->fam[s];
+      f.n_ge_stepdown = f.observed = out[s].valid ? 0 : -1;
+      f.exceed = 0;
+    }
+    if (fo->kmax) std::fill(fo->kmax, fo->kmax + (size_t)kFamilyKmax * (size_t)K, 0.0f);
+    if (fo->null_scores) std::fill(fo->null_scores, fo->null_scores + (size_t)S * (size_t)K, std::numeric_limits<float>::quiet_NaN());
+  }
   const int64_t V = (int64_t)vset.size();
   if (V == 0) return GCRE_OK;
 
@@ -307,7 +480,7 @@ int gcre_score_sets(gcre_ctx* c, const gcre_set_input* in, gcre_set_score* out, 
   if (fam) d.zero(d_fam, (size_t)g.Kpad);
   score_set_rows(c, d, d_rows, d_cnt, d_tot, {d_thr, d_obs, d_ge}, d_fam, V, obs.data(), ge.data(), fam ? fbits.data() : nullptr,
                  nullptr);
-  if (!d.ok()) return fail(c, GCRE_ERR_DEVICE, std::string("score_sets: ") + hipGetErrorString(d.e));
+  if (!d.ok()) return fail(c, GCRE_ERR_DEVICE, who + ": " + hipGetErrorString(d.e));
   for (int64_t v = 0; v < V; v++) {
     gcre_set_score& o = out[vset[(size_t)v]];
     o.score = obs[(size_t)v];
@@ -315,8 +488,31 @@ int gcre_score_sets(gcre_ctx* c, const gcre_set_input* in, gcre_set_score* out, 
     o.pvalue = K > 0 ? (double)o.n_ge / (double)K : nan;
   }
   if (fam) std::memcpy(family_max, fbits.data(), (size_t)K * 4);
+  if (fo && K > 0) {
+    family_stage(c, d, d_rows, d_tot, vset, obs, slab_tiles, *fo);
+    if (!d.ok()) return fail(c, GCRE_ERR_DEVICE, who + ": " + hipGetErrorString(d.e));
+  }
   return GCRE_OK;
 }
+
+}  // namespace
+
+extern "C" {
+
+int gcre_score_sets(gcre_ctx* c, const gcre_set_input* in, gcre_set_score* out, int64_t cap, int64_t* n_out,
+                    float* family_max) {
+  return score_sets_common(c, in, out, cap, n_out, family_max, "score_sets", nullptr);
+}
+
+// Step-down, k-FWER and FDR over the family of the given sets: gcre_score_sets, then the family stage on
+// the same device rows.  kmax[0] is the family maximum, so k_set_null is not asked for it.
+int gcre_score_sets_family(gcre_ctx* c, const gcre_set_input* in, gcre_set_score* out, int64_t cap, int64_t* n_out,
+                           gcre_family_score* fam_out, float* kmax, float* null_scores) {
+  const FamilyOut fo{fam_out, kmax, null_scores};
+  return score_sets_common(c, in, out, cap, n_out, nullptr, "score_sets_family", &fo);
+}
+
+int64_t gcre_family_launches(const gcre_ctx* c) { return c ? c->family_launches : -1; }
 
 // Conditional set scores: gcre_score_sets on residual union rows that k_set_residual builds on the device
 // from the caller's gene rows and set list, uploaded once.  The entries without an NA member are walked in slabs so that the

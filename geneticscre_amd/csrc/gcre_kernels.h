@@ -547,6 +547,48 @@ struct StepdownFinishArgs {
 };
 hipError_t launch_stepdown_finish(const StepdownFinishArgs& a, hipStream_t stream);
 
+// ---- step-down, k-FWER and FDR over a family of caller-given sets (gcre_family.hip) ----
+// N [nsets][stride]: the null scores of a slab of `nkt` whole permutation tiles as u32 bit patterns of non-negative floats,
+// row = the set's rank in ascending observed order.  Columns >= live (the padding of the last tile) are never counted.
+constexpr int kFamilyKmax = 10;        // GCRE_FAMILY_KMAX: the largest values of a column k_family_scan keeps
+constexpr int kFamilyHistBins = 4096;  // bins of k_family_hist's LDS histogram: one pass over N per that many thresholds
+struct FamilyNullArgs {
+  const uint32_t* rows;         // [nsets][M][W32p] union rows, as SetNullArgs
+  const uint32_t* masks;        // [W32p][Kpad]
+  const uint32_t* tot;          // [nsets][M] carriers per half
+  const float* t32;
+  const double* d64;
+  const double* d64n;
+  const uint32_t* rank;         // [nsets] the row of N a set's values go to, a permutation of 0 .. nsets-1
+  uint32_t* N;                  // [nsets][stride]
+  int64_t nsets;
+  int64_t npt;                  // set tiles (set_null_tile_sets sets each)
+  int64_t stride;               // nkt * kSetPermTile
+  int W32p, Kpad, K;
+  int kt0, nkt;                 // the slab: permutation tiles [kt0, kt0 + nkt) of kSetPermTile
+  int pgroups;                  // blocks per permutation tile
+};
+hipError_t launch_family_null(const FamilyNullArgs& a, int method, hipStream_t stream);
+struct FamilyScanArgs {
+  const uint32_t* N;            // [nsets][stride]
+  const uint32_t* meta;         // [nsets padded to 64, with zeros] by row: the f32 threshold pattern; bit 31 = the last row of a tie group
+  uint32_t* n_ge;               // [nsets] by row, adds at the last row of every tie group: live columns (< 2^31 in all) whose
+                                // running maximum reaches the group's threshold
+  uint32_t* kmax;               // [kFamilyKmax][kstride] the column's largest values, descending (0: no such set), or nullptr
+  int64_t nsets, stride, kstride;
+  int live;                     // live columns of the slab
+  int k0;                       // the slab's first permutation: column c is kmax's column k0 + c
+};
+hipError_t launch_family_scan(const FamilyScanArgs& a, hipStream_t stream);
+struct FamilyHistArgs {
+  const uint32_t* N;            // [nsets][stride]
+  const uint32_t* pat;          // [m] ascending distinct f32 threshold patterns
+  unsigned long long* hist;     // [m] adds: live values whose largest reached pattern is this one
+  int64_t nsets, stride;
+  int live, m;
+};
+hipError_t launch_family_hist(const FamilyHistArgs& a, int cus, hipStream_t stream);
+
 // ---- carrier-overlap counts of caller-given sets (gcre_overlap.hip) ----
 constexpr int kOverlapTile = 64;    // pairs per edge of a block's tile
 constexpr int kOverlapChunk = 32;   // dwords of a row per staged chunk (128 bytes): rows are padded to a multiple of it

@@ -270,8 +270,9 @@ def parse_sets(paths, genes: Sequence[str]) -> Tuple[List[List[str]], List[List[
     return names, rows, signs
 
 
-def _score_sets(rows, signs, data, n_cases, n_ctrls, method, n_permutations, strata, seed, device):
-    """score_sets on the rows the sets use, on a context of its own: (records, family maxima)."""
+def _score_sets(rows, signs, data, n_cases, n_ctrls, method, n_permutations, strata, seed, device, family_inference=False):
+    """score_sets on the rows the sets use, on a context of its own: (records, family maxima); with ``family_inference``
+    family_tests instead: (records, family maxima, family records, kmax)."""
     from . import api
     used: Dict[int, int] = {}
     sets = [[-1 if r < 0 else used.setdefault(r, len(used)) for r in rs] for rs in rows]
@@ -282,6 +283,9 @@ def _score_sets(rows, signs, data, n_cases, n_ctrls, method, n_permutations, str
         ex.set_value_table(api.values_table(n_cases, n_ctrls))
         if n_permutations > 0:
             ex.generate_permutations(seed, strata)
+        if family_inference:
+            rec, fam, kmax = ex.family_tests(sets, sub, signs, kmax=True)
+            return rec, kmax[0], fam, kmax
         return ex.score_sets(sets, sub, signs, family=True)
     finally:
         ex.close()
@@ -298,7 +302,7 @@ def _tail_pvalues(null: np.ndarray, scores: np.ndarray) -> np.ndarray:
 
 def score_paths(paths, genes: Sequence[str], data: np.ndarray, n_cases: int, n_ctrls: int, signed: bool = False,
                 threshold: float = 0.05, n_permutations: int = 100, strata: Optional[Sequence[int]] = None, seed: int = 0,
-                device: int = 0, gwaspa_out: Optional[Dict[str, object]] = None):
+                device: int = 0, gwaspa_out: Optional[Dict[str, object]] = None, family_inference: bool = False):
     """Permutation tests of paths and gene sets the caller names (gcre_score_sets on the device): what GWASPA cannot
     answer for a cascade outside its top K, or for a KEGG / Reactome list.  ``paths`` as ``parse_sets`` reads them;
     genes are looked up after ``preprocess_table(threshold)``, as GWASPA and ``decorated_table`` do (a symbol not found is
@@ -309,13 +313,17 @@ def score_paths(paths, genes: Sequence[str], data: np.ndarray, n_cases: int, n_c
     permutation p-value; ``FamilyPvalues`` max-T over the given paths (each score against the per-permutation maximum
     over all of them); ``Pvalues`` against the TestScores of ``gwaspa_out``'s level of the same length -- for a network
     path the number GWASPA would print, if the run had the same seed, strata and permutation count (NaN without
-    ``gwaspa_out`` or outside its 1..pathLength)."""
+    ``gwaspa_out`` or outside its 1..pathLength).
+
+    ``family_inference``: the FAMILY_COLUMNS of ``family_columns`` behind these (gcre_score_sets_family):
+    step-down adjusted p-values, expected false positives, FDR and q-values, and k-FWER p-values over the given paths as
+    one family."""
     import pandas as pd
     method = 2 if signed else 1
     genes, data = preprocess_table(genes, data, threshold, n_cases, n_ctrls)
     names, rows, signs = parse_sets(paths, genes)
     K = int(n_permutations)
-    rec, fam = _score_sets(rows, signs, data, n_cases, n_ctrls, method, K, strata, seed, device)
+    rec, fam, *more = _score_sets(rows, signs, data, n_cases, n_ctrls, method, K, strata, seed, device, family_inference)
     valid = rec["valid"] != 0
     score = rec["score"]
     lengths = np.array([len(n) for n in names], dtype=np.int64)
@@ -340,7 +348,78 @@ def score_paths(paths, genes: Sequence[str], data: np.ndarray, n_cases: int, n_c
         "FamilyPvalues": family,
         "Pvalues": pv,
     }
-    return pd.DataFrame(cols, columns=SCORE_PATHS_COLUMNS)
+    if not family_inference:
+        return pd.DataFrame(cols, columns=SCORE_PATHS_COLUMNS)
+    cols.update(family_columns(score, valid, more[0], more[1], K))
+    return pd.DataFrame(cols, columns=SCORE_PATHS_COLUMNS + FAMILY_COLUMNS)
+
+
+FAMILY_KMAX = 10   # GCRE_FAMILY_KMAX: the largest null scores of a permutation gcre_score_sets_family keeps
+FAMILY_KS = (2, 5, 10)
+FAMILY_COLUMNS = ["FamilyPvaluesStepDown", "FamilyExpectedFalse", "FamilyFDR", "FamilyQvalues"] + [f"FamilykFWER.{k}" for k in FAMILY_KS]
+
+
+def family_reference(obs, valid, null) -> Dict[str, np.ndarray]:
+    """The numpy statement of gcre_score_sets_family, no device call: ``obs`` the observed scores, ``valid``
+    which sets have no NA member, ``null`` the float32 null matrix [n_sets][K] (rows of invalid sets are not read).  Over the
+    valid sets, every comparison as doubles: D_j = {i : obs_i > obs_j} (ties never exclude one another, a NaN score is in
+    no D); ``n_ge_stepdown[j]`` = #{r : max over i not in D_j of null[i][r] >= obs_j}; ``exceed[j]`` = #{(i, r) :
+    null[i][r] >= obs_j}; ``observed[j]`` = #{i : obs_i >= obs_j}; ``kmax[k][r]`` = the (k+1)-th largest of column r (0
+    beyond the valid sets).  A NaN score gets 0 / 0 / 0, an invalid set -1 / 0 / -1.  Computed by one running maximum down
+    the sets in ascending order and one sort of the pooled values."""
+    obs = np.asarray(obs, np.float64).ravel()
+    S = len(obs)
+    valid = np.asarray(valid).ravel() != 0
+    N = np.asarray(null, np.float32).reshape(S, -1)
+    K = N.shape[1]
+    sd = np.where(valid, 0, -1).astype(np.int64)
+    ob = sd.copy()
+    ex = np.zeros(S, np.uint64)
+    kmax = np.zeros((FAMILY_KMAX, K), np.float32)
+    idx = np.flatnonzero(valid)
+    if len(idx) == 0:
+        return {"n_ge_stepdown": sd, "exceed": ex, "observed": ob, "kmax": kmax}
+    ov = obs[idx]
+    isnan = np.isnan(ov)
+    order = np.concatenate([np.flatnonzero(isnan), np.flatnonzero(~isnan)[np.argsort(ov[~isnan], kind="stable")]])
+    Nv = N[idx][order].astype(np.float64)                 # ascending observed order, NaN scores first
+    top = -np.sort(-N[idx], axis=0)[:FAMILY_KMAX]
+    kmax[:len(top)] = top
+    t = ov[order]
+    n_nan = int(isnan.sum())
+    ts = t[n_nan:]
+    run = np.maximum.accumulate(Nv, axis=0)               # run[i] = the maximum over the sets up to sorted position i
+    last = n_nan + np.searchsorted(ts, ts, side="right") - 1    # the end of each tie group: nothing up to it is in D
+    first = n_nan + np.searchsorted(ts, ts, side="left")
+    pooled = np.sort(Nv.ravel())
+    dst = idx[order[n_nan:]]
+    sd[dst] = (run[last] >= ts[:, None]).sum(axis=1)
+    ex[dst] = (len(pooled) - np.searchsorted(pooled, ts, side="left")).astype(np.uint64)
+    ob[dst] = len(idx) - first
+    return {"n_ge_stepdown": sd, "exceed": ex, "observed": ob, "kmax": kmax}
+
+
+def family_columns(scores, valid, family, kmax, perms: int) -> Dict[str, np.ndarray]:
+    """FAMILY_COLUMNS of one family of given sets, from what ``JoinExec.family_tests(kmax=True)`` (or ``family_reference``)
+    returns: ``family`` with n_ge_stepdown / exceed / observed per set, ``kmax`` float32 [FAMILY_KMAX][perms].
+    ``FamilyPvaluesStepDown`` through ``stepdown_columns`` (the monotone step), ``FamilyExpectedFalse`` / ``FamilyFDR`` /
+    ``FamilyQvalues`` through ``fdr_columns``, ``FamilykFWER.k`` = the share of permutations whose k-th largest null score
+    reaches the set's score (the probability of k or more false positives at that threshold, single-step).  NaN for a set
+    with an NA member or a NaN score, and everywhere when perms = 0."""
+    s = np.asarray(scores, np.float64).ravel()
+    ok = (np.asarray(valid).ravel() != 0) & ~np.isnan(s)
+    B = int(perms)
+    out = {c: np.full(len(s), np.nan) for c in FAMILY_COLUMNS}
+    if B <= 0 or not ok.any():
+        return out
+    out["FamilyPvaluesStepDown"][ok] = stepdown_columns(s[ok], np.asarray(family["n_ge_stepdown"])[ok], B)["PvaluesStepDown"]
+    fdr = fdr_columns(s[ok], np.asarray(family["exceed"])[ok], np.asarray(family["observed"])[ok], B)
+    for c in FDR_COLUMNS:
+        out["Family" + c][ok] = fdr[c]
+    km = np.asarray(kmax, np.float32).reshape(FAMILY_KMAX, -1)
+    for k in FAMILY_KS:
+        out[f"FamilykFWER.{k}"][ok] = _tail_pvalues(km[k - 1], s[ok])
+    return out
 
 
 def check_best_paths(results_df, genes: Sequence[str], data: np.ndarray, n_cases: int, n_ctrls: int, signed: bool,

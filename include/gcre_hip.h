@@ -460,6 +460,36 @@ int gcre_score_sets_given(gcre_ctx* ctx, const gcre_set_input* in, const int64_t
 /* kernels launched by gcre_score_sets_given on the context since gcre_create (tests: a refusal launches nothing). */
 int64_t gcre_given_launches(const gcre_ctx* ctx);
 
+/* Step-down, k-FWER and FDR over the family of the given sets.  `out`, *n_out: exactly what
+ * gcre_score_sets gives.  With N[i][r] = the f32 null score of valid set i under permutation r as stated above, obs_i its
+ * observed score, every comparison as doubles against (double)N, over the valid sets:
+ *   D_j              = {i : obs_i > obs_j}: tied sets never exclude one another, a set with a NaN score is in no D
+ *   n_ge_stepdown[j] = #{r : max over i not in D_j of N[i][r] >= obs_j}    (Westfall-Young step-down, before the monotone step)
+ *   exceed[j]        = #{(i, r) : N[i][r] >= obs_j}                        (the pooled null: expected false positives, FDR)
+ *   observed[j]      = #{i : obs_i >= obs_j}
+ *   kmax[k][r]       = the (k+1)-th largest of N[.][r], 0 where the family has fewer valid sets (k-FWER); kmax[0] is
+ *                      gcre_score_sets' family_max bit for bit
+ * A set with a NaN observed score gets 0 / 0 / 0; an invalid set (an NA member) -1 / 0 / -1 and an all-NaN row of null_scores.
+ * So the best set's n_ge_stepdown is #{r : kmax[0][r] >= obs}; out[j].n_ge <= n_ge_stepdown[j] <= #{r : kmax[0][r] >= obs_j},
+ * the single-step count; exceed[j] is the sum over i of #{r : N[i][r] >= obs_j}.  iterations == 0: `out` as gcre_score_sets
+ * fills it, zeros for every valid set, nothing of the family launched.
+ * N is kept on the device for a slab of whole 512-permutation tiles at a time, valid sets x slab permutations x 4 bytes
+ * under GCRE_FAMILY_MAX_MB (environment, read per call, default 1024; GCRE_FAMILY_SLAB_PERMS bounds a slab further); no
+ * result depends on the slabs.  fam_out [n_sets]; kmax optional [GCRE_FAMILY_KMAX][iterations]; null_scores optional
+ * [n_sets][iterations] = N.
+ * Errors, nothing launched and no output array written (*n_out as gcre_score_sets leaves it): everything gcre_score_sets
+ * refuses; GCRE_ERR_ARG -- NULL fam_out, one 512-permutation tile of the valid sets above GCRE_FAMILY_MAX_MB. */
+#define GCRE_FAMILY_KMAX 10
+typedef struct {
+  int64_t n_ge_stepdown;
+  uint64_t exceed;
+  int64_t observed;
+} gcre_family_score;
+int gcre_score_sets_family(gcre_ctx* ctx, const gcre_set_input* in, gcre_set_score* out, int64_t cap, int64_t* n_out,
+                           gcre_family_score* fam_out, float* kmax, float* null_scores);
+/* k_family_null / k_family_scan / k_family_hist launches on the context since gcre_create. */
+int64_t gcre_family_launches(const gcre_ctx* ctx);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Carrier overlaps of caller-given sets: which sets are carried by the same patients.  No reference
  * counterpart.
