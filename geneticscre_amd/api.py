@@ -1278,6 +1278,7 @@ class JoinExec:
             opts.d_null_out = ctypes.c_void_p(int(d_null_out))
         res = gcre_result()
         res_h = paths_res._h if paths_res is not None else None
+        # every observer of the call is checked before any is armed: a refused call leaves nothing armed for the next join
         if tally is not None:
             if tally._owner is not self or not tally._h:
                 raise GcreError("gene tally does not belong to this context")
@@ -1285,15 +1286,19 @@ class JoinExec:
                 cnt = np.asarray(uids.count)
                 ends = (np.asarray(uids.location, dtype=np.int64) + cnt)[cnt > 0]
                 check_gene_tables(tally.n_slots, tally.genes0, tally.genes1, len(cnt), int(ends.max()) - 1 if len(ends) else -1)
-            self._check(_genes_lib().gcre_join_set_tally(self._h, tally._h))
-        if exceed is not None:
-            if exceed._owner is not self or not exceed._h:
-                raise GcreError("exceedance counts do not belong to this context")
-            self._check(_exceed_lib().gcre_join_set_exceed(self._h, exceed._h))
-        if hits is not None:
-            if hits._owner is not self or not hits._h:
-                raise GcreError("hit list does not belong to this context")
-            self._check(_hits_lib().gcre_join_set_hits(self._h, hits._h))
+        if exceed is not None and (exceed._owner is not self or not exceed._h):
+            raise GcreError("exceedance counts do not belong to this context")
+        if hits is not None and (hits._owner is not self or not hits._h):
+            raise GcreError("hit list does not belong to this context")
+        armed = [(setter, o._h) for setter, o in ((lambda h: _genes_lib().gcre_join_set_tally(self._h, h), tally),
+                                                  (lambda h: _exceed_lib().gcre_join_set_exceed(self._h, h), exceed),
+                                                  (lambda h: _hits_lib().gcre_join_set_hits(self._h, h), hits)) if o is not None]
+        for i, (setter, h) in enumerate(armed):
+            rc = setter(h)
+            if rc != GCRE_OK:                      # the library's own refusal: disarm what this call armed before it
+                for undo, _ in armed[:i]:
+                    undo(None)
+                self._check(rc)
         if isinstance(uids, DeviceUids):
             rc = self._lib.gcre_join_uids(self._h, uids._h, paths0._h, paths1._h, res_h, ctypes.byref(opts),
                                           ctypes.byref(res))
@@ -1506,31 +1511,31 @@ def process_paths(problem, device: int = 0, exec_: Optional[JoinExec] = None, ta
     inp.perm_rows, inp.perm_col_major = (pc.shape[0] if pc.ndim == 2 else 0), 0
     inp.path_length = int(problem.path_length)
     outs = (gcre_result * 5)()
-    for name, t in (tallies or {}).items():
-        if name not in LEVEL_INDEX:
-            raise GcreError(f"process_paths: no level {name!r} (levels are {', '.join(LEVEL_INDEX)})")
-        if t._owner is not ex or not t._h:
-            raise GcreError("gene tally does not belong to this context")
-        u = problem.levels.uids[name]
-        cnt = np.asarray(u.count)
-        ends = (np.asarray(u.location, dtype=np.int64) + cnt)[cnt > 0]
-        check_gene_tables(t.n_slots, t.genes0, t.genes1, len(cnt), int(ends.max()) - 1 if len(ends) else -1)
-    for name, t in (tallies or {}).items():
-        ex._check(_genes_lib().gcre_process_paths_set_tally(ex._h, LEVEL_INDEX[name], t._h))
-    for name, x in (exceeds or {}).items():
-        if name not in LEVEL_INDEX:
-            raise GcreError(f"process_paths: no level {name!r} (levels are {', '.join(LEVEL_INDEX)})")
-        if x._owner is not ex or not x._h:
-            raise GcreError("exceedance counts do not belong to this context")
-    for name, x in (exceeds or {}).items():
-        ex._check(_exceed_lib().gcre_process_paths_set_exceed(ex._h, LEVEL_INDEX[name], x._h))
-    for name, h in (hits or {}).items():
-        if name not in LEVEL_INDEX:
-            raise GcreError(f"process_paths: no level {name!r} (levels are {', '.join(LEVEL_INDEX)})")
-        if h._owner is not ex or not h._h:
-            raise GcreError("hit list does not belong to this context")
-    for name, h in (hits or {}).items():
-        ex._check(_hits_lib().gcre_process_paths_set_hits(ex._h, LEVEL_INDEX[name], h._h))
+    # every observer of every level is checked before any is set: a refused call leaves nothing for the next call to consume
+    for what, given in (("tally", tallies), ("exceed", exceeds), ("hits", hits)):
+        for name, o in (given or {}).items():
+            if name not in LEVEL_INDEX:
+                raise GcreError(f"process_paths: no level {name!r} (levels are {', '.join(LEVEL_INDEX)})")
+            if o._owner is not ex or not o._h:
+                raise GcreError({"tally": "gene tally does not", "exceed": "exceedance counts do not",
+                                 "hits": "hit list does not"}[what] + " belong to this context")
+            if what == "tally":
+                u = problem.levels.uids[name]
+                cnt = np.asarray(u.count)
+                ends = (np.asarray(u.location, dtype=np.int64) + cnt)[cnt > 0]
+                check_gene_tables(o.n_slots, o.genes0, o.genes1, len(cnt), int(ends.max()) - 1 if len(ends) else -1)
+    setters = {"tally": lambda i, h: _genes_lib().gcre_process_paths_set_tally(ex._h, i, h),
+               "exceed": lambda i, h: _exceed_lib().gcre_process_paths_set_exceed(ex._h, i, h),
+               "hits": lambda i, h: _hits_lib().gcre_process_paths_set_hits(ex._h, i, h)}
+    done = []
+    for what, given in (("tally", tallies), ("exceed", exceeds), ("hits", hits)):
+        for name, o in (given or {}).items():
+            rc = setters[what](LEVEL_INDEX[name], o._h)
+            if rc != GCRE_OK:                      # the library's own refusal: take back what this call set before it
+                for w, i in done:
+                    setters[w](i, None)
+                ex._check(rc)
+            done.append((what, LEVEL_INDEX[name]))
     rc = lib.gcre_process_paths(ex._h, ctypes.byref(inp), outs)
     ex._check(rc)
     result: Dict[str, object] = {}
