@@ -48,15 +48,17 @@ namespace gcre {
 // flush below.  Every wave of a block walks every chunk of the block, with or without a segment of its own in it, and
 // no wave leaves before the last flush: the flush has the kernel's only barriers.
 template <int M, int L>
-__global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(M == 1 ? 4 : 2))) void k_null_ie(const IeArgs a) {
+__global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(M == 1 ? 4 : 2))) void k_null_ie(const IeArgs /* read through ie_args() */) {
+  // every argument is read through ap where it is used, never through the by-value copy (gcre_ie_common.h)
+  const IeArgs GCRE_CONSTANT* ap = ie_args();
   static_assert(L % 4 == 0 && L >= 8 && L <= 16, "planes come in groups of 4");
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int xcd = blockIdx.x & 7;
   const i64 bi = (i64)(blockIdx.x >> 3);
-  const i64 bx = a.waves_per_xcd / kIeWaves;   // blocks per XCD (launch_null_ie: waves_per_xcd is a multiple of kIeWaves)
-  const i64 cpt = (a.seg_end - a.seg_begin + kIeWaves - 1) / kIeWaves;   // chunks per tile
-  const i64 chunks = cpt * a.nkt;                                        // < 2^45
+  const i64 bx = ap->waves_per_xcd / kIeWaves;   // blocks per XCD (launch_null_ie: waves_per_xcd is a multiple of kIeWaves)
+  const i64 cpt = (ap->seg_end - ap->seg_begin + kIeWaves - 1) / kIeWaves;   // chunks per tile
+  const i64 chunks = cpt * ap->nkt;                                        // < 2^45
   const u32 lane4 = (u32)lane * 4u;
   // the waves' 2048 running maxima of the block's current tile: 8 KB of LDS each, [q][lane] <-> permutation 32 * lane + q
   __shared__ u32 gmax_lds[kIeWaves][32 * 64];
@@ -64,12 +66,8 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(M
 #pragma unroll
   for (int q = 0; q < 32; q++) scr[q * 64] = 0u;
 
-  const SparseSeg GCRE_CONSTANT* segs = (const SparseSeg GCRE_CONSTANT*)a.segs;
-  const u64 GCRE_CONSTANT* loff0 = (const u64 GCRE_CONSTANT*)a.loff0;
-  const u32 GCRE_CONSTANT* lidx0 = (const u32 GCRE_CONSTANT*)a.lidx0;
-
   int cur_kt = -1;
-  __amdgpu_buffer_rsrc_t mt = __builtin_amdgcn_make_buffer_rsrc((void*)a.mt, 0, 0x7fffffff, 0x00020000);
+  __amdgpu_buffer_rsrc_t mt = __builtin_amdgcn_make_buffer_rsrc((void*)ap->mt, 0, 0x7fffffff, 0x00020000);
 #ifdef GCRE_IE_TIMING
   u64 tm[6] = {0, 0, 0, 0, 0, 0};   // segment prologue, path loop up to the counts, transpose + look-ups, flush, flushes, total
   const u64 tm_begin = __builtin_amdgcn_s_memtime();
@@ -86,10 +84,10 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(M
     GCRE_TM_MARK(tf0);
     __syncthreads();
     const u32 slot0 = (u32)wave * 512u + (u32)lane * 8u;
-    __amdgpu_buffer_rsrc_t nb = __builtin_amdgcn_make_buffer_rsrc((void*)(a.null_bits + (size_t)cur_kt * 2048), 0, 8192, 0x00020000);
+    __amdgpu_buffer_rsrc_t nb = __builtin_amdgcn_make_buffer_rsrc((void*)(ap->null_bits + (size_t)cur_kt * 2048), 0, 8192, 0x00020000);
     const u32x4 g0 = __builtin_amdgcn_raw_buffer_load_b128(nb, slot0 * 4u, 0, 16 /* sc1 */);
     const u32x4 g1 = __builtin_amdgcn_raw_buffer_load_b128(nb, slot0 * 4u + 16u, 0, 16 /* sc1 */);
-    u32* out = a.null_bits + (size_t)cur_kt * 2048 + slot0;
+    u32* out = ap->null_bits + (size_t)cur_kt * 2048 + slot0;
     u32* cell = &gmax_lds[0][0] + (slot0 & 31u) * 64u + (slot0 >> 5);   // permutation 32 l + q lives at [q][l]
     u32 own[8];
 #pragma unroll
@@ -126,7 +124,7 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(M
   auto finish_m1 = [&](const u32 (&C)[L], u32 total) {
     u32 R[16];
     to_counts(C, R);
-    const u32* diag_g = (const u32*)a.t32 + sp_diag_offset(total);
+    const u32* diag_g = (const u32*)ap->t32 + sp_diag_offset(total);
     u32 v[32], o[32];
 #pragma unroll
     for (int j = 0; j < 16; j++) {
@@ -145,8 +143,8 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(M
     u32 Rp[16], Rn[16];
     to_counts(Cp, Rp);
     to_counts(Cn, Rn);
-    const double* dp = a.d64 + sp_diag_offset(tp);
-    const double* dn = a.d64 + sp_diag_offset(tn);
+    const double* dp = ap->d64 + sp_diag_offset(tp);
+    const double* dn = ap->d64 + sp_diag_offset(tn);
 #pragma unroll
     for (int g0 = 0; g0 < 16; g0 += 4) {
       double sp[8], sn[8];
@@ -188,15 +186,17 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(M
 
   const i64 c_end = (i64)(xcd + 1) * chunks / 8;
   for (i64 c = (i64)xcd * chunks / 8 + bi; c < c_end; c += bx) {   // block-uniform
+    ie_args_again(ap);
     const int kt = (int)(c / cpt);
     if (kt != cur_kt) {
       flush();
       cur_kt = kt;
-      mt = __builtin_amdgcn_make_buffer_rsrc((void*)(a.mt + (size_t)kt * a.mt_rows * 64), 0, 0x7fffffff, 0x00020000);
+      mt = __builtin_amdgcn_make_buffer_rsrc((void*)(ap->mt + (size_t)kt * ap->mt_rows * 64), 0, 0x7fffffff, 0x00020000);
     }
-    const i64 sidx = a.seg_begin + (c - (i64)kt * cpt) * kIeWaves + wave;
-    if (sidx < a.seg_end) {   // (a tile's last chunk may be short)
+    const i64 sidx = ap->seg_begin + (c - (i64)kt * cpt) * kIeWaves + wave;
+    if (sidx < ap->seg_end) {   // (a tile's last chunk may be short)
       GCRE_TM_MARK(ts0);
+      const SparseSeg GCRE_CONSTANT* segs = (const SparseSeg GCRE_CONSTANT*)ap->segs;
       const u32 row0 = segs[sidx].row0;
       const u32 first = segs[sidx].first;
       const u32 npaths = segs[sidx].n;
@@ -206,23 +206,23 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(M
       u32 infov[M], lovv[M];   // padded list length | mode, and where a long list continues
 #pragma unroll
       for (int h = 0; h < M; h++) {
-        infov[h] = a.linfo[(u64)qv * M + h];
-        lovv[h] = a.lover[(u64)qv * M + h];
+        infov[h] = ap->linfo[(u64)qv * M + h];
+        lovv[h] = ap->lover[(u64)qv * M + h];
       }
-      const u32 rzv = a.rowz[qv];
+      const u32 rzv = ap->rowz[qv];
       u32 zunit[M];      // where the planes of the added row-half start, in 1 KB units
 #pragma unroll
       for (int h = 0; h < M; h++) {
         const u32 hz = (M == 2 && (rzv >> 31)) ? (u32)(1 - h) : (u32)h;
-        zunit[h] = ((u32)kt * (u32)a.rowsz + (rzv & 0x7fffffffu) * (u32)M + hz) * (u32)a.gz;
+        zunit[h] = ((u32)kt * (u32)ap->rowsz + (rzv & 0x7fffffffu) * (u32)M + hz) * (u32)ap->gz;
       }
       u32 ttv[M];
 #pragma unroll
-      for (int h = 0; h < M; h++) ttv[h] = a.tot[(u64)qv * M + h];
+      for (int h = 0; h < M; h++) ttv[h] = ap->tot[(u64)qv * M + h];
       u32 lv[M][8];      // the first 8 entries of every list (lists are padded to 8: most lists end there)
 #pragma unroll
       for (int h = 0; h < M; h++) {
-        const u32x4* lp = (const u32x4*)(a.dlist + ((u64)qv * M + h) * 8u);
+        const u32x4* lp = (const u32x4*)(ap->dlist + ((u64)qv * M + h) * 8u);
         const u32x4 e0 = lp[0], e1 = lp[1];
         lv[h][0] = e0.x; lv[h][1] = e0.y; lv[h][2] = e0.z; lv[h][3] = e0.w;
         lv[h][4] = e1.x; lv[h][5] = e1.y; lv[h][6] = e1.z; lv[h][7] = e1.w;
@@ -248,21 +248,21 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(M
 #pragma unroll
       for (int h = 0; h < M; h++) {
         const u64 r = (u64)row0 * M + h;
-        if (a.planes0) {
-          load_planes(B[h], a.planes0, (u32)(((u64)kt * (u64)a.rows0 + r) * (u64)a.g0), a.g0);
-        } else if (a.rec_slot) {
+        if (ap->planes0) {
+          load_planes(B[h], ap->planes0, (u32)(((u64)kt * (u64)ap->rows0 + r) * (u64)ap->g0), ap->g0);
+        } else if (ap->rec_slot) {
           // the set has the recipe of the join that made it (see k_null_ie_m1 / k_null_ie_m2): per half
           // A[row0'][h] + Z[z'][h'] -/+ that join's list of the half (rec_rows_a / rec_rows_z count row-halves)
-          const u32 ra = a.rec_row0[row0], rzr = a.rec_rowz[row0], rz = rzr & 0x7fffffffu, rinfo = a.rec_linfo[r];
+          const u32 ra = ap->rec_row0[row0], rzr = ap->rec_rowz[row0], rz = rzr & 0x7fffffffu, rinfo = ap->rec_linfo[r];
           const u32 hz = (M == 2 && (rzr >> 31)) ? (u32)(1 - h) : (u32)h;
           u32 ZR[L], S[L];
-          load_planes(B[h], a.rec_planes_a, (u32)(((u64)kt * (u64)a.rec_rows_a + (u64)ra * M + h) * (u64)a.rec_ga), a.rec_ga);
-          load_planes(ZR, a.rec_planes_z, (u32)(((u64)kt * (u64)a.rec_rows_z + (u64)rz * M + hz) * (u64)a.rec_gz), a.rec_gz);
+          load_planes(B[h], ap->rec_planes_a, (u32)(((u64)kt * (u64)ap->rec_rows_a + (u64)ra * M + h) * (u64)ap->rec_ga), ap->rec_ga);
+          load_planes(ZR, ap->rec_planes_z, (u32)(((u64)kt * (u64)ap->rec_rows_z + (u64)rz * M + hz) * (u64)ap->rec_gz), ap->rec_gz);
 #pragma unroll
           for (int l = 0; l < L; l++) S[l] = 0u;
           const u32 rlen = linfo_len(rinfo);
-          stream(S, (const u32 GCRE_CONSTANT*)(a.rec_slot + r * 8u), 0, 8);
-          if (rlen > 8u) stream(S, (const u32 GCRE_CONSTANT*)(a.rec_over + a.rec_lover[r]), 0, (u64)(rlen - 8u));
+          stream(S, (const u32 GCRE_CONSTANT*)(ap->rec_slot + r * 8u), 0, 8);
+          if (rlen > 8u) stream(S, (const u32 GCRE_CONSTANT*)(ap->rec_over + ap->rec_lover[r]), 0, (u64)(rlen - 8u));
           u32 cy = 0u, bw = 0u;
 #pragma unroll
           for (int l = 0; l < L; l++) {
@@ -276,7 +276,8 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(M
         } else {
 #pragma unroll
           for (int l = 0; l < L; l++) B[h][l] = 0u;
-          stream(B[h], lidx0, loff0[r], loff0[r + 1]);
+          const u64 GCRE_CONSTANT* loff0 = (const u64 GCRE_CONSTANT*)ap->loff0;
+          stream(B[h], (const u32 GCRE_CONSTANT*)ap->lidx0, loff0[r], loff0[r + 1]);
         }
       }
 
@@ -300,7 +301,7 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(M
           // ... and the planes of the row the join adds, when the list is the overlap with paths0
           u32 Z[L];
           if (overlap) {
-            load_planes(Z, a.planesz, rdlane(zunit[h], t), a.gz);
+            load_planes(Z, ap->planesz, rdlane(zunit[h], t), ap->gz);
           } else {
 #pragma unroll
             for (int l = 0; l < L; l++) Z[l] = 0u;
@@ -317,7 +318,7 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(M
           S[0] = s0; S[1] = s1; S[2] = d0 ^ d1; S[3] = d0 & d1;
 #pragma unroll
           for (int l = 4; l < L; l++) S[l] = 0u;
-          if (len > 8u) stream(S, (const u32 GCRE_CONSTANT*)(a.dover + rdlane(lovv[h], t)), 0, (u64)(len - 8u));   // long list (rare)
+          if (len > 8u) stream(S, (const u32 GCRE_CONSTANT*)(ap->dover + rdlane(lovv[h], t)), 0, (u64)(len - 8u));   // long list (rare)
           if (overlap) {   // C = B + Nz - S
             u32 cy = 0u, bw = 0u;
 #pragma unroll
@@ -336,14 +337,14 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(M
             }
           }
         }
-        if (a.planes_out) {
+        if (ap->planes_out) {
 #pragma unroll
           for (int h = 0; h < M; h++) {
-            const u64 rh = ((u64)a.out_first + q) * M + h;
-            u32x4* dst = (u32x4*)(a.planes_out + (((u64)cur_kt * (u64)a.rows_out + rh) * (u64)a.go) * 256u) + lane;
+            const u64 rh = ((u64)ap->out_first + q) * M + h;
+            u32x4* dst = (u32x4*)(ap->planes_out + (((u64)cur_kt * (u64)ap->rows_out + rh) * (u64)ap->go) * 256u) + lane;
 #pragma unroll
             for (int j = 0; j < 4; j++) {
-              if (j < a.go) {
+              if (j < ap->go) {
                 u32x4 v = {0u, 0u, 0u, 0u};
                 if (4 * j < L) v = u32x4{C[h][(4 * j) % L], C[h][(4 * j + 1) % L], C[h][(4 * j + 2) % L], C[h][(4 * j + 3) % L]};
                 dst[j * 64] = v;
@@ -353,7 +354,7 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(M
         }
         GCRE_TM_MARK(tp1);
         GCRE_TM_ADD(1, tp1, tp0);
-        if (q < a.score_begin || q >= a.score_end) continue;   // planes only: the path belongs to another shard
+        if (q < ap->score_begin || q >= ap->score_end) continue;   // planes only: the path belongs to another shard
         if constexpr (M == 1) {
           finish_m1(C[0], rdlane(ttv[0], t));
         } else {
@@ -367,9 +368,9 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(M
   flush();
 #ifdef GCRE_IE_TIMING
   tm[5] = __builtin_amdgcn_s_memtime() - tm_begin;
-  if (a.timing && lane == 0)
-    for (int i = 0; i < 6; i++) atomicAdd((unsigned long long*)a.timing + i, (unsigned long long)tm[i]);
-  if (a.timing && lane == 0) atomicMax((unsigned long long*)a.timing + 6, (unsigned long long)tm[5]);
+  if (ap->timing && lane == 0)
+    for (int i = 0; i < 6; i++) atomicAdd((unsigned long long*)ap->timing + i, (unsigned long long)tm[i]);
+  if (ap->timing && lane == 0) atomicMax((unsigned long long*)ap->timing + 6, (unsigned long long)tm[5]);
 #endif
 }
 
@@ -381,7 +382,9 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(M
 // ------------------------------------------------------------------------------------------------
 
 template <int L, int GZ, bool OUT, bool REC>
-__global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(L <= 12 ? 4 : 3))) void k_null_ie_m1(const IeArgs a) {
+__global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(L <= 12 ? 4 : 3))) void k_null_ie_m1(const IeArgs /* read through ie_args() */) {
+  // every argument is read through ap where it is used, never through the by-value copy (gcre_ie_common.h)
+  const IeArgs GCRE_CONSTANT* ap = ie_args();
   // L counter planes (any even number: the arithmetic runs over exactly L); plane arrays come in groups of 4
   constexpr int LP = (L + 3) / 4 * 4;
   static_assert(L >= 8 && L <= 16 && GZ >= 2 && 4 * GZ <= LP, "planes come in groups of 4");
@@ -393,53 +396,48 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(L
   u32* nm = nmax_lds[wave] + lane;
 #pragma unroll
   for (int q = 0; q < 32; q++) nm[q * 64] = 0u;
-  const SparseSeg GCRE_CONSTANT* segs = (const SparseSeg GCRE_CONSTANT*)a.segs;
-  // pinned to scalar registers (the compiler re-loads kernel arguments on both sides of the ticket's `lane == 0` branch
-  // and then treats them as divergent): the base of the added rows' planes, so that their loads take the scalar-base form
-  const char* k_planesz = (const char*)(((u64)(u32)__builtin_amdgcn_readfirstlane((int)(u32)((u64)a.planesz >> 32)) << 32) |
-                                        (u64)(u32)__builtin_amdgcn_readfirstlane((int)(u32)(u64)a.planesz));
-
   int cur_kt = -1;
   u32 valid = 0u;
-  u32 lad_base = (a.lad_mode == 0) ? 0u : (u32)(kLadderLevels - 1 + a.lad_mode) * (u32)a.ladder_stride;
-  const u32 lad_keep = (u32)kLadderLevels * (u32)a.ladder_stride;
+  u32 lad_base = (ap->lad_mode == 0) ? 0u : (u32)(kLadderLevels - 1 + ap->lad_mode) * (u32)ap->ladder_stride;
   bool dirty = false;     // nm holds maxima the global array has not seen
   u32 n_slow = 0u;
 #ifdef GCRE_IE_TIMING
   u64 tm[6] = {0, 0, 0, 0, 0, 0};   // seg prologue, load wait, compute, lookups, exchange, total
   const u64 tm_begin = __builtin_amdgcn_s_memtime();
 #endif
-  __amdgpu_buffer_rsrc_t mt = __builtin_amdgcn_make_buffer_rsrc((void*)a.mt, 0, 0x7fffffff, 0x00020000);
+  __amdgpu_buffer_rsrc_t mt = __builtin_amdgcn_make_buffer_rsrc((void*)ap->mt, 0, 0x7fffffff, 0x00020000);
 
   // publish the wave's maxima, read everybody's, set the threshold level to the smallest running maximum of the
   // tile's live permutations (a stale read only lowers it: still exact)
   auto exchange = [&]() {
     // the tile's 2048 running maxima: lane holds 32 consecutive ones = 8 wide loads, issued together.  sc1: served
     // by the memory side, not by this CU's L1 or this XCD's L2, which never see the other XCDs' atomics.
-    u32* out = a.null_bits + (size_t)cur_kt * 2048 + lane * 32;
-    __amdgpu_buffer_rsrc_t nb = __builtin_amdgcn_make_buffer_rsrc((void*)(a.null_bits + (size_t)cur_kt * 2048), 0, 8192, 0x00020000);
+    u32* out = ap->null_bits + (size_t)cur_kt * 2048 + lane * 32;
+    __amdgpu_buffer_rsrc_t nb = __builtin_amdgcn_make_buffer_rsrc((void*)(ap->null_bits + (size_t)cur_kt * 2048), 0, 8192, 0x00020000);
     u32x4 g4[8];
 #pragma unroll
     for (int j = 0; j < 8; j++) g4[j] = __builtin_amdgcn_raw_buffer_load_b128(nb, (u32)lane * 128u + (u32)j * 16u, 0, 16 /* sc1 */);
     u32 lo = 0xffffffffu;
+    u32 live = valid;   // (tested here, not as 32 lane masks made when the tile changes: k_null_ie_q's merge_global)
+    asm volatile("" : "+v"(live));
 #pragma unroll
     for (int q = 0; q < 32; q++) {
       const u32 g = g4[q >> 2][q & 3];
       const u32 own = nm[q * 64];
       if (dirty && own > g) atomicMax(out + q, own);
       const u32 v = own > g ? own : g;
-      if ((valid >> q) & 1u) lo = v < lo ? v : lo;
+      if ((live >> q) & 1u) lo = v < lo ? v : lo;
     }
     dirty = false;
     u32 theta = __builtin_amdgcn_readfirstlane(wave_min_u32(lo));
     if (theta == 0xffffffffu) theta = 0u;
     int j = (int)(__uint_as_float(theta) * (float)kLadderPerUnit);   // level j covers thresholds >= j / kLadderPerUnit
     j = j < 0 ? 0 : (j > kLadderLevels - 1 ? kLadderLevels - 1 : j);
-    lad_base = (u32)j * (u32)a.ladder_stride;
+    lad_base = (u32)j * (u32)ap->ladder_stride;
   };
   auto flush_tile = [&]() {
     if (cur_kt >= 0) {
-      u32* out = a.null_bits + (size_t)cur_kt * 2048 + lane * 32;
+      u32* out = ap->null_bits + (size_t)cur_kt * 2048 + lane * 32;
 #pragma unroll 8
       for (int q = 0; q < 32; q++) {
         const u32 own = nm[q * 64];
@@ -457,13 +455,14 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(L
   __shared__ u32 wq_state[kIeWaves][8];
   WorkQueue wq;
   wq.st = wq_state[wave];
-  wq.init(a.queue, (u32)((a.seg_end - a.seg_begin + a.batch - 1) / a.batch), (u32)a.nkt);
+  wq.init(ap->queue, (u32)((ap->seg_end - ap->seg_begin + ap->batch - 1) / ap->batch), (u32)ap->nkt);
   {
     wq.select(blockIdx.x & 7u);   // workgroups are dealt round the XCDs: blocks b and b + 8 share an L2
   }
   u32 ticket = wq.take(lane);
   int since = 0, period = 1;   // thresholds: refresh after 1, 2, 4, .. segments while they climb, then every kIeRefresh
   for (;;) {
+    ie_args_again(ap);
     const u32 work = __builtin_amdgcn_readfirstlane(ticket);
     const u32 q_n = wq.get(2);
     if (work >= q_n) {
@@ -475,15 +474,15 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(L
     ticket = wq.take(lane);   // the next ticket is on its way while this batch is worked on
     const u32 item = wq.get(1) + work, nb = wq.get(3);
     const int kt = (int)(item / nb);
-    const i64 s_lo = a.seg_begin + (i64)(item - (u32)kt * nb) * a.batch;
-    const i64 s_hi = s_lo + a.batch < a.seg_end ? s_lo + a.batch : a.seg_end;
+    const i64 s_lo = ap->seg_begin + (i64)(item - (u32)kt * nb) * ap->batch;
+    const i64 s_hi = s_lo + ap->batch < ap->seg_end ? s_lo + ap->batch : ap->seg_end;
     if (kt != cur_kt) {
       flush_tile();
       cur_kt = kt;
-      mt = __builtin_amdgcn_make_buffer_rsrc((void*)(a.mt + (size_t)kt * a.mt_rows * 64), 0, 0x7fffffff, 0x00020000);
-      const int live = a.K - kt * 2048 - lane * 32;
+      mt = __builtin_amdgcn_make_buffer_rsrc((void*)(ap->mt + (size_t)kt * ap->mt_rows * 64), 0, 0x7fffffff, 0x00020000);
+      const int live = ap->K - kt * 2048 - lane * 32;
       valid = live >= 32 ? 0xffffffffu : (live <= 0 ? 0u : ((1u << live) - 1u));
-      if (a.lad_mode == 0) lad_base = 0u;
+      if (ap->lad_mode == 0) lad_base = 0u;
       since = 0;
       period = 1;
     }
@@ -494,6 +493,7 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(L
     u32 nextv = 0u;
     bool have_next = false;
     for (i64 sidx = s_lo; sidx < s_hi; sidx++) {
+      ie_args_again(ap);
       u32 row0, first, npaths;
       u32 rc_a = 0u, rc_z = 0u, rc_info = 0u, rc_lov = 0u;
       typedef u32 __attribute__((ext_vector_type(8))) u32x8;
@@ -511,11 +511,12 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(L
           for (int j = 0; j < 8; j++) rc_o[j] = rdlane(nextv, 8 + j);
         }
       } else {
+        const SparseSeg GCRE_CONSTANT* segs = (const SparseSeg GCRE_CONSTANT*)ap->segs;
         row0 = segs[sidx].row0;
         first = segs[sidx].first;
         npaths = segs[sidx].n;
         if constexpr (REC) {
-          const u32 GCRE_CONSTANT* rs = (const u32 GCRE_CONSTANT*)a.rec_segs + (u64)sidx * kRecSegWords;
+          const u32 GCRE_CONSTANT* rs = (const u32 GCRE_CONSTANT*)ap->rec_segs + (u64)sidx * kRecSegWords;
           rc_a = rs[0];
           rc_z = rs[1];
           rc_info = rs[2];
@@ -525,14 +526,14 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(L
       }
       have_next = sidx + 1 < s_hi;
       if (have_next) {
-        const u32* src = (const u32*)a.segs + (u64)(sidx + 1) * 3u + (u32)(lane < 3 ? lane : 0);
+        const u32* src = (const u32*)ap->segs + (u64)(sidx + 1) * 3u + (u32)(lane < 3 ? lane : 0);
         if constexpr (REC) {
-          if (lane >= 4 && lane < 16) src = a.rec_segs + (u64)(sidx + 1) * kRecSegWords + (u32)(lane - 4);
+          if (lane >= 4 && lane < 16) src = ap->rec_segs + (u64)(sidx + 1) * kRecSegWords + (u32)(lane - 4);
         }
         nextv = *src;
       }
       GCRE_TM_MARK(ts0);
-      if (a.lad_mode == 0 && ++since >= period) {
+      if (ap->lad_mode == 0 && ++since >= period) {
         exchange();
         since = 0;
         period = period < kIeRefresh ? period * 2 : kIeRefresh;
@@ -542,15 +543,15 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(L
 
       // ---- per-path metadata of the whole segment in a few coalesced loads: lane t <-> joined path first + t ----
       const u32 qv = first + (((u32)lane < npaths) ? (u32)lane : 0u);
-      const u32 infov = a.linfo[qv];                 // padded list length | mode
-      const u32 lovv = a.lover[qv];                  // where a long list continues
-      const u32 zunit = ((u32)kt * (u32)a.rowsz + (a.rowz[qv] & 0x7fffffffu)) * (u32)a.gz;   // 1 KB units into planesz
-      const u32 totv = a.tot[qv];
+      const u32 infov = ap->linfo[qv];                 // padded list length | mode
+      const u32 lovv = ap->lover[qv];                  // where a long list continues
+      const u32 zunit = ((u32)kt * (u32)ap->rowsz + (ap->rowz[qv] & 0x7fffffffu)) * (u32)ap->gz;   // 1 KB units into planesz
+      const u32 totv = ap->tot[qv];
       // segments of another shard's rows: the all-inside row of the ladder (no count is looked up), planes only
-      const u32 lhv = a.ladder[((u64)sidx < (u64)a.score_segs ? lad_base : lad_keep) + totv];
+      const u32 lhv = ap->ladder[((u64)sidx < (u64)ap->score_segs ? lad_base : (u32)kLadderLevels * (u32)ap->ladder_stride) + totv];
       // the first 8 entries of every list (lists are padded to 8: most lists end there) are wave-uniform: they come
       // through the scalar cache, one s_load_dwordx8 per path, fetched one path ahead of the loads that use them
-      const u32x8 GCRE_CONSTANT* slots = (const u32x8 GCRE_CONSTANT*)(a.dlist + (u64)first * 8u);
+      const u32x8 GCRE_CONSTANT* slots = (const u32x8 GCRE_CONSTANT*)(ap->dlist + (u64)first * 8u);
       // OUT (every count is needed): the path's 8 mask rows and the added row's planes.  Otherwise only the planes: the
       // rows are fetched by the lanes the bound filter leaves uncertain (see compute)
       auto issue = [&](u32 t2, const u32x8 offs, u32 (&yy)[8], u32 (&ZZ)[4 * GZ]) {
@@ -560,7 +561,7 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(L
         }
         // scalar base + 32-bit lane offset: the address never sits in vector registers (a vector address pair that shares
         // registers with a load still in flight costs a full s_waitcnt vmcnt(0) per path)
-        __amdgpu_buffer_rsrc_t rz = __builtin_amdgcn_make_buffer_rsrc((void*)(k_planesz + (u64)rdlane(zunit, t2) * 1024u), 0, 0x7fffffff, 0x00020000);
+        __amdgpu_buffer_rsrc_t rz = __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)ap->planesz + (u64)rdlane(zunit, t2) * 1024u), 0, 0x7fffffff, 0x00020000);
 #pragma unroll
         for (int j = 0; j < GZ; j++) {
           const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rz, lane4 * 4u + (u32)j * 1024u, 0, 0);
@@ -587,7 +588,7 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(L
         }
       };
       if constexpr (!REC) {
-        load_groups(B, a.planes0, ((u64)kt * (u64)a.rows0 + (u64)row0) * (u64)a.g0, a.g0);
+        load_groups(B, ap->planes0, ((u64)kt * (u64)ap->rows0 + (u64)row0) * (u64)ap->g0, ap->g0);
       } else {
         const u32 ra = rc_a, rz = rc_z & 0x7fffffffu, rinfo = rc_info;
         const u32x8 ro = rc_o;
@@ -595,8 +596,8 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(L
 #pragma unroll
         for (int j = 0; j < 8; j++) yr[j] = __builtin_amdgcn_raw_buffer_load_b32(mt, lane4, ro[j], 0);
         u32 ZR[LP];
-        load_groups(B, a.rec_planes_a, ((u64)kt * (u64)a.rec_rows_a + (u64)ra) * (u64)a.rec_ga, a.rec_ga);
-        load_groups(ZR, a.rec_planes_z, ((u64)kt * (u64)a.rec_rows_z + (u64)rz) * (u64)a.rec_gz, a.rec_gz);
+        load_groups(B, ap->rec_planes_a, ((u64)kt * (u64)ap->rec_rows_a + (u64)ra) * (u64)ap->rec_ga, ap->rec_ga);
+        load_groups(ZR, ap->rec_planes_z, ((u64)kt * (u64)ap->rec_rows_z + (u64)rz) * (u64)ap->rec_gz, ap->rec_gz);
         u32 S[L];
         {
           u32 S4[4];
@@ -606,7 +607,7 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(L
         }
         const u32 rlen = linfo_len(rinfo);
         if (rlen > 8u) {   // the producing join's list was long: the rest of it, 8 entries at a time
-          const u32 GCRE_CONSTANT* more = (const u32 GCRE_CONSTANT*)(a.rec_over + rc_lov);
+          const u32 GCRE_CONSTANT* more = (const u32 GCRE_CONSTANT*)(ap->rec_over + rc_lov);
           for (u32 p = 0u; p + 8u < rlen; p += 8u) {
             const u32x8 o8 = *(const u32x8 GCRE_CONSTANT*)(more + p);
             u32 yy[8], s4[4];
@@ -699,7 +700,7 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(L
           u32 S[L];
 #pragma unroll
           for (int l = 0; l < L; l++) S[l] = (l < 4) ? S4[l < 4 ? l : 0] : 0u;
-          const u32 GCRE_CONSTANT* more = (const u32 GCRE_CONSTANT*)(a.dover + rdlane(lovv, t));
+          const u32 GCRE_CONSTANT* more = (const u32 GCRE_CONSTANT*)(ap->dover + rdlane(lovv, t));
           for (u32 p = 0u; p + 8u < len; p += 8u) {
             const u32x8 o8 = *(const u32x8 GCRE_CONSTANT*)(more + p);
             u32 yy[8], s4[4];
@@ -739,11 +740,11 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(L
           }
         }
         if constexpr (OUT) {
-          const u64 rh = (u64)a.out_first + first + t;
-          u32x4* dst = (u32x4*)(a.planes_out + (((u64)kt * (u64)a.rows_out + rh) * (u64)a.go) * 256u) + lane;
+          const u64 rh = (u64)ap->out_first + first + t;
+          u32x4* dst = (u32x4*)(ap->planes_out + (((u64)kt * (u64)ap->rows_out + rh) * (u64)ap->go) * 256u) + lane;
 #pragma unroll
           for (int j = 0; j < 4; j++) {
-            if (j < a.go) {
+            if (j < ap->go) {
               u32x4 v = {0u, 0u, 0u, 0u};
               if (4 * j < L) v = u32x4{C[(4 * j) % L], (4 * j + 1 < L) ? C[(4 * j + 1) % L] : 0u, (4 * j + 2 < L) ? C[(4 * j + 2) % L] : 0u,
                                        (4 * j + 3 < L) ? C[(4 * j + 3) % L] : 0u};
@@ -768,7 +769,7 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(L
         if (__builtin_amdgcn_ballot_w64(m != 0u) == 0ull) return;
         // ---- the few permutations that can raise a maximum: rebuild each count from the planes, look it up ----
         n_slow++;
-        const u32* diag_g = (const u32*)a.t32 + sp_diag_offset(rdlane(totv, t));
+        const u32* diag_g = (const u32*)ap->t32 + sp_diag_offset(rdlane(totv, t));
         while (m != 0u) {
           // up to 4 permutations per round: their table cells are independent loads in flight together
           u32 bb[4], vv[4];
@@ -852,7 +853,7 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(L
 #pragma unroll
           for (int l = 0; l < L; l++) S[l] = (l < 4) ? S4[l < 4 ? l : 0] : 0u;
           if (len > 8u) {   // long list: further blocks of 8 entries
-            const u32 GCRE_CONSTANT* more = (const u32 GCRE_CONSTANT*)(a.dover + rdlane(lovv, t));
+            const u32 GCRE_CONSTANT* more = (const u32 GCRE_CONSTANT*)(ap->dover + rdlane(lovv, t));
             for (u32 p = 0u; p + 8u < len; p += 8u) {
               const u32x8 o8 = *(const u32x8 GCRE_CONSTANT*)(more + p);
               u32 yy[8], s4[4];
@@ -900,7 +901,7 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(L
           u32 m = (blo | bhi) & mu;
           if (m != 0u) {
             slow = 1u;
-            const u32* diag_g = (const u32*)a.t32 + sp_diag_offset(rdlane(totv, t));
+            const u32* diag_g = (const u32*)ap->t32 + sp_diag_offset(rdlane(totv, t));
             while (m != 0u) {
               u32 bb[4], vv[4];
 #pragma unroll
@@ -959,11 +960,11 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(L
   flush_tile();
 #ifdef GCRE_IE_TIMING
   tm[5] = __builtin_amdgcn_s_memtime() - tm_begin;
-  if (a.timing && lane == 0)
-    for (int i = 0; i < 6; i++) atomicAdd((unsigned long long*)a.timing + i, (unsigned long long)tm[i]);
-  if (a.timing && lane == 0) atomicMax((unsigned long long*)a.timing + 6, (unsigned long long)tm[5]);
+  if (ap->timing && lane == 0)
+    for (int i = 0; i < 6; i++) atomicAdd((unsigned long long*)ap->timing + i, (unsigned long long)tm[i]);
+  if (ap->timing && lane == 0) atomicMax((unsigned long long*)ap->timing + 6, (unsigned long long)tm[5]);
 #endif
-  if (a.stats && lane == 0 && n_slow) atomicAdd(a.stats, n_slow);
+  if (ap->stats && lane == 0 && n_slow) atomicAdd(ap->stats, n_slow);
 }
 
 // method 2 runs the general kernel; method 1 the specialised one: L from the largest carrier total, GZ = plane groups of

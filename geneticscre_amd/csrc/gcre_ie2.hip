@@ -48,14 +48,16 @@
 namespace gcre {
 
 template <int L, int GZ, bool OUT, bool REC>
-__global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(L <= 10 ? 4 : (L <= 12 ? 3 : GCRE_M2_WAVES16)))) void k_null_ie_m2(const IeArgs a) {
+__global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(L <= 10 ? 4 : (L <= 12 ? 3 : GCRE_M2_WAVES16)))) void k_null_ie_m2(const IeArgs /* read through ie_args() */) {
+  // every argument is read through ap where it is used, never through the by-value copy (gcre_ie_common.h)
+  const IeArgs GCRE_CONSTANT* ap = ie_args();
   constexpr int NS = GCRE_M2_STEPS;
   static_assert(NS == 2 || NS == 3, "two or three steps");
   constexpr int LP = (L + 3) / 4 * 4;
   // mask rows of a list fetched a path ahead: four in the 4-wave variants (rare variants: most overlaps are shorter, and
   // four more registers in both buffers cost spills inside the path loop), the whole slot where there are registers
   constexpr int YW = L <= 10 ? 4 : GCRE_M2_YW_WIDE;
-  constexpr int LZ = 4 * GZ;   // planes of an added row (GZ groups; the launch picks GZ >= a.gz)
+  constexpr int LZ = 4 * GZ;   // planes of an added row (GZ groups; the launch picks GZ >= ap->gz)
   static_assert(LZ <= LP, "added rows have no more planes than joined paths");
   static_assert(L >= 8 && L <= 16, "8 to 16 counter planes");
   typedef u32 __attribute__((ext_vector_type(8))) u32x8;
@@ -72,7 +74,6 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(L
   u32* nm = nmax_lds[wave] + lane;
 #pragma unroll
   for (int q = 0; q < 32; q++) nm[q * 64] = 0u;
-  const SparseSeg GCRE_CONSTANT* segs = (const SparseSeg GCRE_CONSTANT*)a.segs;
   u32 (*lq)[kLqCap] = lq_lds[wave];
   u32 lq_n = 0u;   // entries waiting (wave-uniform)
   bool dirty = false;
@@ -80,7 +81,7 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(L
     for (u32 base = 0u; base < lq_n; base += 64u) {
       const u32 i = base + (u32)lane;
       if (i < lq_n) {
-        const double f64 = a.d64[lq[0][i]] + a.d64[lq[1][i]];   // vtmax[a][tp - a] + vtmax[tn - b][b], methods.h:227
+        const double f64 = ap->d64[lq[0][i]] + ap->d64[lq[1][i]];   // vtmax[a][tp - a] + vtmax[tn - b][b], methods.h:227
         float f = (float)f64;
         f = (f > 0.0f) ? f : 0.0f;
         __hip_atomic_fetch_max(nmax_lds[wave] + lq[2][i], __float_as_uint(f), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
@@ -89,21 +90,16 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(L
     if (lq_n != 0u) dirty = true;
     lq_n = 0u;
   };
-  // the base of the added rows' planes in scalar registers: their loads take the scalar-base buffer form
-  const char* k_planesz = (const char*)(((u64)(u32)__builtin_amdgcn_readfirstlane((int)(u32)((u64)a.planesz >> 32)) << 32) |
-                                        (u64)(u32)__builtin_amdgcn_readfirstlane((int)(u32)(u64)a.planesz));
-
   int cur_kt = -1;
   u32 valid = 0u;
   // the staircase: ladder rows r_0 <= .. <= r_{NS-1} with r_s + r_{NS-1-s} <= 2 j, rows in units of 1 / (2 kLadderPerUnit)
   u32 lad[NS];
 #pragma unroll
-  for (int s = 0; s < NS; s++) lad[s] = (a.lad_mode == 0) ? 0u : (u32)(kLadder2Levels - 1 + a.lad_mode) * (u32)a.ladder_stride;
-  const u32 lad_keep = (u32)kLadder2Levels * (u32)a.ladder_stride;
+  for (int s = 0; s < NS; s++) lad[s] = (ap->lad_mode == 0) ? 0u : (u32)(kLadder2Levels - 1 + ap->lad_mode) * (u32)ap->ladder_stride;
   // the row for a changed half whose other half is empty: G = vtmax[0][0] <= g00_rows / (2 kLadderPerUnit), so F may use
   // all of 2 j - g00_rows (top_ok: that is not negative)
   u32 lad_top = lad[0];
-  bool top_ok = a.lad_mode != 0 || a.g00_rows == 0u;
+  bool top_ok = ap->lad_mode != 0 || ap->g00_rows == 0u;
   u32 n_slow = 0u;
 #ifdef GCRE_IE_TIMING
   // diagnostics build: path-tiles by class -- [0] other half empty, [1] one test, [2] all steps, [3] both halves change,
@@ -113,23 +109,25 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(L
 #else
 #define GCRE_TM_COUNT(i, n)
 #endif
-  __amdgpu_buffer_rsrc_t mt = __builtin_amdgcn_make_buffer_rsrc((void*)a.mt, 0, 0x7fffffff, 0x00020000);
+  __amdgpu_buffer_rsrc_t mt = __builtin_amdgcn_make_buffer_rsrc((void*)ap->mt, 0, 0x7fffffff, 0x00020000);
 
   auto exchange = [&]() {
     lq_drain();   // what the queue still holds belongs to the maxima that go out
-    u32* out = a.null_bits + (size_t)cur_kt * 2048 + lane * 32;
-    __amdgpu_buffer_rsrc_t nb = __builtin_amdgcn_make_buffer_rsrc((void*)(a.null_bits + (size_t)cur_kt * 2048), 0, 8192, 0x00020000);
+    u32* out = ap->null_bits + (size_t)cur_kt * 2048 + lane * 32;
+    __amdgpu_buffer_rsrc_t nb = __builtin_amdgcn_make_buffer_rsrc((void*)(ap->null_bits + (size_t)cur_kt * 2048), 0, 8192, 0x00020000);
     u32x4 g4[8];
 #pragma unroll
     for (int j = 0; j < 8; j++) g4[j] = __builtin_amdgcn_raw_buffer_load_b128(nb, (u32)lane * 128u + (u32)j * 16u, 0, 16 /* sc1 */);
     u32 lo = 0xffffffffu;
+    u32 live = valid;   // (tested here, not as 32 lane masks made when the tile changes: k_null_ie_q's merge_global)
+    asm volatile("" : "+v"(live));
 #pragma unroll
     for (int q = 0; q < 32; q++) {
       const u32 g = g4[q >> 2][q & 3];
       const u32 own = nm[q * 64];
       if (dirty && own > g) atomicMax(out + q, own);
       const u32 v = own > g ? own : g;
-      if ((valid >> q) & 1u) lo = v < lo ? v : lo;
+      if ((live >> q) & 1u) lo = v < lo ? v : lo;
     }
     dirty = false;
     u32 theta = __builtin_amdgcn_readfirstlane(wave_min_u32(lo));
@@ -148,16 +146,16 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(L
 #pragma unroll
     for (int s = 0; s < NS; s++) {
       const int rs = r[s] > kLadder2Levels - 1 ? kLadder2Levels - 1 : r[s];   // a lower row is a lower threshold: still exact
-      lad[s] = (u32)rs * (u32)a.ladder_stride;
+      lad[s] = (u32)rs * (u32)ap->ladder_stride;
     }
-    const int rt = 2 * j - (int)a.g00_rows;
-    top_ok = a.g00_rows != 0xffffffffu && rt >= 0;
-    lad_top = (u32)(rt < 0 ? 0 : (rt > kLadder2Levels - 1 ? kLadder2Levels - 1 : rt)) * (u32)a.ladder_stride;
+    const int rt = 2 * j - (int)ap->g00_rows;
+    top_ok = ap->g00_rows != 0xffffffffu && rt >= 0;
+    lad_top = (u32)(rt < 0 ? 0 : (rt > kLadder2Levels - 1 ? kLadder2Levels - 1 : rt)) * (u32)ap->ladder_stride;
   };
   auto flush_tile = [&]() {
     lq_drain();
     if (cur_kt >= 0) {
-      u32* out = a.null_bits + (size_t)cur_kt * 2048 + lane * 32;
+      u32* out = ap->null_bits + (size_t)cur_kt * 2048 + lane * 32;
 #pragma unroll 8
       for (int q = 0; q < 32; q++) {
         const u32 own = nm[q * 64];
@@ -297,7 +295,7 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(L
     u32 S[L];
 #pragma unroll
     for (int l = 0; l < L; l++) S[l] = (l < 4) ? S4[l < 4 ? l : 0] : 0u;
-    sum_more(S, len, (const u32 GCRE_CONSTANT*)a.dover, lover_at);
+    sum_more(S, len, (const u32 GCRE_CONSTANT*)ap->dover, lover_at);
     if (overlap) {
       u32 cy = 0u, bw = 0u;
 #pragma unroll
@@ -337,14 +335,14 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(L
       for (int j = 0; j < 4; j++) yy[j] = 0u;
     }
     if (linfo_overlap(info)) {
-      __amdgpu_buffer_rsrc_t rz = __builtin_amdgcn_make_buffer_rsrc((void*)(k_planesz + (u64)zu * 1024u), 0, 0x7fffffff, 0x00020000);
+      __amdgpu_buffer_rsrc_t rz = __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)ap->planesz + (u64)zu * 1024u), 0, 0x7fffffff, 0x00020000);
 #pragma unroll
       for (int j = 0; j < GZ; j++) {
         u32x4 v = {0u, 0u, 0u, 0u};
 #ifdef GCRE_M2_NOZLOAD   // timing experiment (wrong results): no plane loads of the added rows
         v = u32x4{zu, zu + (u32)j, lane4, 0u};
 #else
-        if (j < 2 || j < a.gz) v = __builtin_amdgcn_raw_buffer_load_b128(rz, lane4 * 4u + (u32)j * 1024u, 0, 0);   // (a.gz >= 2: plane_groups_for)
+        if (j < 2 || j < ap->gz) v = __builtin_amdgcn_raw_buffer_load_b128(rz, lane4 * 4u + (u32)j * 1024u, 0, 0);   // (ap->gz >= 2: plane_groups_for)
 #endif
         ZZ[4 * j + 0] = v.x; ZZ[4 * j + 1] = v.y; ZZ[4 * j + 2] = v.z; ZZ[4 * j + 3] = v.w;
       }
@@ -380,11 +378,12 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(L
   __shared__ u32 wq_state[kIeWaves][8];
   WorkQueue wq;
   wq.st = wq_state[wave];
-  wq.init(a.queue, (u32)((a.seg_end - a.seg_begin + a.batch - 1) / a.batch), (u32)a.nkt);
+  wq.init(ap->queue, (u32)((ap->seg_end - ap->seg_begin + ap->batch - 1) / ap->batch), (u32)ap->nkt);
   wq.select(blockIdx.x & 7u);   // workgroups are dealt round the XCDs: blocks b and b + 8 share an L2
   u32 ticket = wq.take(lane);
   int since = 0, period = 1;
   for (;;) {
+    ie_args_again(ap);
     const u32 work = __builtin_amdgcn_readfirstlane(ticket);
     const u32 q_n = wq.get(2);
     if (work >= q_n) {
@@ -396,28 +395,30 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(L
     ticket = wq.take(lane);   // the next ticket is on its way while this batch is worked on
     const u32 item = wq.get(1) + work, nb = wq.get(3);
     const int kt = (int)(item / nb);
-    const i64 s_lo = a.seg_begin + (i64)(item - (u32)kt * nb) * a.batch;
-    const i64 s_hi = s_lo + a.batch < a.seg_end ? s_lo + a.batch : a.seg_end;
+    const i64 s_lo = ap->seg_begin + (i64)(item - (u32)kt * nb) * ap->batch;
+    const i64 s_hi = s_lo + ap->batch < ap->seg_end ? s_lo + ap->batch : ap->seg_end;
     if (kt != cur_kt) {
       flush_tile();
       cur_kt = kt;
-      mt = __builtin_amdgcn_make_buffer_rsrc((void*)(a.mt + (size_t)kt * a.mt_rows * 64), 0, 0x7fffffff, 0x00020000);
-      const int live = a.K - kt * 2048 - lane * 32;
+      mt = __builtin_amdgcn_make_buffer_rsrc((void*)(ap->mt + (size_t)kt * ap->mt_rows * 64), 0, 0x7fffffff, 0x00020000);
+      const int live = ap->K - kt * 2048 - lane * 32;
       valid = live >= 32 ? 0xffffffffu : (live <= 0 ? 0u : ((1u << live) - 1u));
-      if (a.lad_mode == 0) {
+      if (ap->lad_mode == 0) {
 #pragma unroll
         for (int s = 0; s < NS; s++) lad[s] = 0u;
         lad_top = 0u;
-        top_ok = a.g00_rows == 0u;
+        top_ok = ap->g00_rows == 0u;
       }
       since = 0;
       period = 1;
     }
     for (i64 sidx = s_lo; sidx < s_hi; sidx++) {
+      ie_args_again(ap);
+      const SparseSeg GCRE_CONSTANT* segs = (const SparseSeg GCRE_CONSTANT*)ap->segs;
       const u32 row0 = segs[sidx].row0;
       const u32 first = segs[sidx].first;
       const u32 npaths = segs[sidx].n;
-      if (a.lad_mode == 0 && ++since >= period) {
+      if (ap->lad_mode == 0 && ++since >= period) {
         exchange();
         since = 0;
         period = period < kIeRefresh ? period * 2 : kIeRefresh;
@@ -427,19 +428,20 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(L
       // half's list info, planes and ladder rows stay in vector registers ----
       const bool inl = (u32)lane < npaths;
       const u32 qv = first + (inl ? (u32)lane : 0u);
-      const u32 rzv = a.rowz[qv];
-      const bool mine = (u64)sidx < (u64)a.score_segs;   // else: rows of another shard, the ladder's all-inside row
+      const u32 rzv = ap->rowz[qv];
+      const bool mine = (u64)sidx < (u64)ap->score_segs;   // else: rows of another shard, the ladder's all-inside row
+      const u32 lad_keep = (u32)kLadder2Levels * (u32)ap->ladder_stride;
       const bool seg_top_ok = top_ok;   // the rows read below and this flag belong together (an exchange moves both)
       // (where a long list continues, the slot entries and the carrier totals are read where they are used, through the
       // scalar cache)
-      const u32 GCRE_CONSTANT* k_lover = (const u32 GCRE_CONSTANT*)a.lover + (u64)first * 2u;
-      const u32 GCRE_CONSTANT* k_tot = (const u32 GCRE_CONSTANT*)a.tot + (u64)first * 2u;
-      const u32 GCRE_CONSTANT* k_slot = (const u32 GCRE_CONSTANT*)a.dlist + (u64)first * 16u;
+      const u32 GCRE_CONSTANT* k_lover = (const u32 GCRE_CONSTANT*)ap->lover + (u64)first * 2u;
+      const u32 GCRE_CONSTANT* k_tot = (const u32 GCRE_CONSTANT*)ap->tot + (u64)first * 2u;
+      const u32 GCRE_CONSTANT* k_slot = (const u32 GCRE_CONSTANT*)ap->dlist + (u64)first * 16u;
       u32 infoc, zunitc, ladc[NS], ladt, ladu[NS], totu;
       u64 pm0, pm1, pm2;
       {
-        const u32 i0 = a.linfo[(u64)qv * 2], i1 = a.linfo[(u64)qv * 2 + 1];
-        const u32 t0_ = a.tot[(u64)qv * 2], t1_ = a.tot[(u64)qv * 2 + 1];
+        const u32 i0 = ap->linfo[(u64)qv * 2], i1 = ap->linfo[(u64)qv * 2 + 1];
+        const u32 t0_ = ap->tot[(u64)qv * 2], t1_ = ap->tot[(u64)qv * 2 + 1];
         // an empty delta list: that half is paths0's.  (i & kLinfoLenMask) is linfo_len(i) written out: with the helper
         // here the compiler schedules this kernel differently
         const bool e0 = !linfo_overlap(i0) && (i0 & kLinfoLenMask) == linfo_pad(i0);
@@ -450,15 +452,15 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(L
         const bool c1 = e0 && !e1;
         infoc = c1 ? i1 : i0;
         const u32 hz = ((rzv >> 31) != 0u) != c1 ? 1u : 0u;        // the added row's half that lands in the changed half
-        zunitc = ((u32)kt * (u32)a.rowsz + (rzv & 0x7fffffffu) * 2u + hz) * (u32)a.gz;
+        zunitc = ((u32)kt * (u32)ap->rowsz + (rzv & 0x7fffffffu) * 2u + hz) * (u32)ap->gz;
         const u32 tc = c1 ? t1_ : t0_;
         totu = c1 ? t0_ : t1_;
 #pragma unroll
         for (int s = 0; s < NS; s++) {
-          ladc[s] = a.ladder[(mine ? lad[s] : lad_keep) + tc];
-          ladu[s] = a.ladder[(mine ? lad[NS - 1 - s] : lad_keep) + totu];   // step s pairs F <= r_s with G <= r_{NS-1-s}
+          ladc[s] = ap->ladder[(mine ? lad[s] : lad_keep) + tc];
+          ladu[s] = ap->ladder[(mine ? lad[NS - 1 - s] : lad_keep) + totu];   // step s pairs F <= r_s with G <= r_{NS-1-s}
         }
-        ladt = a.ladder[(mine ? lad_top : lad_keep) + tc];   // the changed half's interval when the other half is empty
+        ladt = ap->ladder[(mine ? lad_top : lad_keep) + tc];   // the changed half's interval when the other half is empty
       }
 
       // ---- base counters of the two halves: the planes of paths0[row0] -- stored, or (REC) rebuilt from the recipe of the
@@ -467,30 +469,30 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(L
       if constexpr (!REC) {
 #pragma unroll
         for (int h = 0; h < 2; h++)
-          load_groups(B[h], a.planes0, ((u64)kt * (u64)a.rows0 + (u64)row0 * 2 + h) * (u64)a.g0, a.g0);
+          load_groups(B[h], ap->planes0, ((u64)kt * (u64)ap->rows0 + (u64)row0 * 2 + h) * (u64)ap->g0, ap->g0);
       } else {
-        const u32 GCRE_CONSTANT* r_row0 = (const u32 GCRE_CONSTANT*)a.rec_row0;
-        const u32 GCRE_CONSTANT* r_rowz = (const u32 GCRE_CONSTANT*)a.rec_rowz;
-        const u32 GCRE_CONSTANT* r_linfo = (const u32 GCRE_CONSTANT*)a.rec_linfo;
-        const u32 GCRE_CONSTANT* r_lover = (const u32 GCRE_CONSTANT*)a.rec_lover;
+        const u32 GCRE_CONSTANT* r_row0 = (const u32 GCRE_CONSTANT*)ap->rec_row0;
+        const u32 GCRE_CONSTANT* r_rowz = (const u32 GCRE_CONSTANT*)ap->rec_rowz;
+        const u32 GCRE_CONSTANT* r_linfo = (const u32 GCRE_CONSTANT*)ap->rec_linfo;
+        const u32 GCRE_CONSTANT* r_lover = (const u32 GCRE_CONSTANT*)ap->rec_lover;
         const u32 ra = r_row0[row0], rzr = r_rowz[row0];
         const u32 ri0 = r_linfo[(u64)row0 * 2], ri1 = r_linfo[(u64)row0 * 2 + 1];
 #pragma unroll
         for (int h = 0; h < 2; h++)
-          load_groups(B[h], a.rec_planes_a, ((u64)kt * (u64)a.rec_rows_a + (u64)ra * 2 + h) * (u64)a.rec_ga, a.rec_ga);
+          load_groups(B[h], ap->rec_planes_a, ((u64)kt * (u64)ap->rec_rows_a + (u64)ra * 2 + h) * (u64)ap->rec_ga, ap->rec_ga);
 #pragma unroll
         for (int h = 0; h < 2; h++) {
           const u32 rinfo = h ? ri1 : ri0;
           const u32 rlen = linfo_len(rinfo);
           if (!linfo_overlap(rinfo) && rlen == linfo_pad(rinfo)) continue;   // the producing join left this half as it was
-          const u32x8 ro = *(const u32x8 GCRE_CONSTANT*)(a.rec_slot + ((u64)row0 * 2 + h) * 8u);
+          const u32x8 ro = *(const u32x8 GCRE_CONSTANT*)(ap->rec_slot + ((u64)row0 * 2 + h) * 8u);
           u32 yr[8];
 #pragma unroll
           for (int j = 0; j < 8; j++) yr[j] = __builtin_amdgcn_raw_buffer_load_b32(mt, lane4, ro[j], 0);
           u32 ZR[LP];
           if (linfo_overlap(rinfo)) {
             const u32 hz = (rzr >> 31) ? (u32)(1 - h) : (u32)h;
-            load_groups(ZR, a.rec_planes_z, ((u64)kt * (u64)a.rec_rows_z + (u64)(rzr & 0x7fffffffu) * 2 + hz) * (u64)a.rec_gz, a.rec_gz);
+            load_groups(ZR, ap->rec_planes_z, ((u64)kt * (u64)ap->rec_rows_z + (u64)(rzr & 0x7fffffffu) * 2 + hz) * (u64)ap->rec_gz, ap->rec_gz);
           }
           u32 S[L];
           {
@@ -499,7 +501,7 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(L
 #pragma unroll
             for (int l = 0; l < L; l++) S[l] = (l < 4) ? S4[l < 4 ? l : 0] : 0u;
           }
-          if (rlen > 8u) sum_more(S, rlen, (const u32 GCRE_CONSTANT*)a.rec_over, r_lover + (u64)row0 * 2 + h);
+          if (rlen > 8u) sum_more(S, rlen, (const u32 GCRE_CONSTANT*)ap->rec_over, r_lover + (u64)row0 * 2 + h);
           if (linfo_overlap(rinfo)) {   // B = A + Z - S
             u32 cy = 0u, bw = 0u;
 #pragma unroll
@@ -522,11 +524,11 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(L
       }
       auto write_out = [&](u32 h, u32 t, const auto& C) {   // planes of half h of joined path first + t
         if constexpr (OUT) {
-          const u64 rh = ((u64)a.out_first + first + t) * 2 + h;
-          u32x4* dst = (u32x4*)(a.planes_out + (((u64)kt * (u64)a.rows_out + rh) * (u64)a.go) * 256u) + lane;
+          const u64 rh = ((u64)ap->out_first + first + t) * 2 + h;
+          u32x4* dst = (u32x4*)(ap->planes_out + (((u64)kt * (u64)ap->rows_out + rh) * (u64)ap->go) * 256u) + lane;
 #pragma unroll
           for (int j = 0; j < 4; j++) {
-            if (j < a.go) {
+            if (j < ap->go) {
               u32x4 v = {0u, 0u, 0u, 0u};
               if (4 * j < L) v = u32x4{C[(4 * j) % L], (4 * j + 1 < L) ? C[(4 * j + 1) % L] : 0u,
                                        (4 * j + 2 < L) ? C[(4 * j + 2) % L] : 0u, (4 * j + 3 < L) ? C[(4 * j + 3) % L] : 0u};
@@ -546,12 +548,12 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(L
         u32 info2[2], zunit2[2], lad2[NS][2];
 #pragma unroll
         for (int h = 0; h < 2; h++) {
-          info2[h] = a.linfo[(u64)qv * 2 + h];
+          info2[h] = ap->linfo[(u64)qv * 2 + h];
           const u32 hz = (rzv >> 31) ? (u32)(1 - h) : (u32)h;
-          zunit2[h] = ((u32)kt * (u32)a.rowsz + (rzv & 0x7fffffffu) * 2u + hz) * (u32)a.gz;
-          const u32 th = a.tot[(u64)qv * 2 + h];
+          zunit2[h] = ((u32)kt * (u32)ap->rowsz + (rzv & 0x7fffffffu) * 2u + hz) * (u32)ap->gz;
+          const u32 th = ap->tot[(u64)qv * 2 + h];
 #pragma unroll
-          for (int s = 0; s < NS; s++) lad2[s][h] = a.ladder[(mine ? lad[s] : lad_keep) + th];
+          for (int s = 0; s < NS; s++) lad2[s][h] = ap->ladder[(mine ? lad[s] : lad_keep) + th];
         }
         u64 rem = pm2;
         u32 t = (u32)__builtin_ctzll(rem);
@@ -680,10 +682,10 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(L
   }
   flush_tile();
 #ifdef GCRE_IE_TIMING
-  if (a.timing && lane == 0)
-    for (int i = 0; i < 7; i++) atomicAdd((unsigned long long*)a.timing + i, (unsigned long long)tm[i]);
+  if (ap->timing && lane == 0)
+    for (int i = 0; i < 7; i++) atomicAdd((unsigned long long*)ap->timing + i, (unsigned long long)tm[i]);
 #endif
-  if (a.stats && lane == 0 && n_slow) atomicAdd(a.stats, n_slow);
+  if (ap->stats && lane == 0 && n_slow) atomicAdd(ap->stats, n_slow);
 }
 
 // counter planes of the joined paths x plane groups of the added rows

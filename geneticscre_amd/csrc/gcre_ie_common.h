@@ -4,11 +4,30 @@
 #include "gcre_bitslice.h"
 #include "gcre_kernels.h"
 
+#include <type_traits>
+
 namespace gcre {
 
 constexpr int kIeWaves = 4;
 constexpr int kIeQueueStride = 16;  // words between two ticket counters (64 B)
 constexpr int kIeRefresh = 32;      // segments between two reads of the global maxima once the thresholds have settled
+
+// The launch arguments, read where they are used.  The pruned kernels take one explicit argument, `const IeArgs a`
+// by value, which the loader puts at offset 0 of the kernarg segment.  Read as `a.field` the compiler loads every field at
+// kernel entry and keeps it in a scalar register for the whole kernel -- ~60 words that it then spills to vector lanes
+// across the filter loop and reloads (v_readlane + wait states) in the per-quad blocks.  Read through a pointer it
+// cannot see through, a field is one scalar load from the scalar cache next to its use and is live nowhere else.
+// ie_args() gives that pointer; ie_args_again(ap) makes it a new value, so that no load through it is hoisted above
+// this point (out of the loop that begins here).  Coming out of a scalar asm operand the pointer, and with it every
+// field, is wave-uniform by construction.
+// (A kernel that gets a second explicit argument, or one in front of `a`, must not use this.)
+static_assert(std::is_trivially_copyable<IeArgs>::value && alignof(IeArgs) <= 16, "IeArgs sits in the kernarg segment byte for byte as the host fills it");
+__device__ __forceinline__ void ie_args_again(const IeArgs GCRE_CONSTANT*& ap) { asm volatile("" : "+s"(ap)); }
+__device__ __forceinline__ const IeArgs GCRE_CONSTANT* ie_args() {
+  const IeArgs GCRE_CONSTANT* ap = (const IeArgs GCRE_CONSTANT*)__builtin_amdgcn_kernarg_segment_ptr();
+  ie_args_again(ap);
+  return ap;
+}
 
 __device__ __forceinline__ u32 maj3(u32 a, u32 b, u32 c) { return (a & b) | ((a ^ b) & c); }
 

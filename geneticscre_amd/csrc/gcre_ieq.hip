@@ -60,11 +60,14 @@ __device__ __forceinline__ void with_count(u32 count, F&& f) {
 
 // WIDE: one tile of the added rows' planes does not fit a 32-bit byte offset (IeArgs::z_wide)
 template <int L, int GZ, bool REC, bool WIDE>
-__global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(GCRE_QWAVES))) void k_null_ie_q(const IeArgs a) {
+__global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(GCRE_QWAVES))) void k_null_ie_q(const IeArgs /* read through ie_args() */) {
   constexpr int LP = (L + 3) / 4 * 4;
   constexpr int LZ = 4 * GZ;
   static_assert(L >= 8 && L <= 16 && GZ >= 2 && LZ <= LP, "planes come in groups of 4");
   typedef u32 __attribute__((ext_vector_type(8))) u32x8;
+  // every argument is read through ap, where it is used, and never through the by-value copy (gcre_ie_common.h): the
+  // lambdas below capture ap by reference and see the pointer as the loops renew it
+  const IeArgs GCRE_CONSTANT* ap = ie_args();
   __shared__ u32 nmax_lds[kIeWaves][32 * 64];   // the waves' running maxima [bit][lane]
   __shared__ u32 wq_state[kIeWaves][8];
   // look-ups are queued (cell of the table, slot of the maximum) and made 64 at a time: one memory round trip per 64
@@ -89,30 +92,23 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(G
     for (u32 base = 0u; base < lq_n; base += 64u) {
       const u32 i = base + (u32)lane;
       if (i < lq_n)
-        __hip_atomic_fetch_max(nmax_lds[wave] + lq[1][i], ((const u32*)a.t32)[lq[0][i]], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);   // ds_max_u32
+        __hip_atomic_fetch_max(nmax_lds[wave] + lq[1][i], ((const u32*)ap->t32)[lq[0][i]], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);   // ds_max_u32
     }
     lq_n = 0u;
   };
-  // Launch constants that steer control flow or end up in buffer descriptors, pinned to scalar registers: the compiler
-  // re-loads kernel arguments on both sides of the `lane == 0` branch around the ticket atomic, and whatever is derived
-  // from such a pair counts as divergent (waterfall loops around buffer loads, vector-register loop counters).
+  // No launch constant is pinned to a register (they were, with readfirstlane: read as `a.field` the compiler re-loaded
+  // arguments on both sides of the `lane == 0` branch around the ticket atomic and what was derived from such a pair
+  // counted as divergent).  A field read through ap is uniform -- the pointer comes out of a scalar asm operand -- and is
+  // loaded where it is used; uni() remains for values that come out of vector registers.
   auto uni = [](u32 v) -> u32 { return (u32)__builtin_amdgcn_readfirstlane((int)v); };
   auto uni_ptr = [&](const void* p) -> const char* { return (const char*)(((u64)uni((u32)((u64)p >> 32)) << 32) | (u64)uni((u32)(u64)p)); };
-  const u32 k_quad_begin = uni((u32)a.quad_begin), k_quad_end = uni((u32)a.quad_end), k_batch = uni((u32)a.batch);
-  const u32 k_nkt = uni((u32)a.nkt), k_K = uni((u32)a.K), k_mt_rows = uni(a.mt_rows), k_lstride = uni((u32)a.ladder_stride);
-  const u32 k_lad_mode = uni((u32)a.lad_mode), k_score_segs = uni(a.score_segs);
-  const char* k_mt = uni_ptr(a.mt);
-  const char* k_planesz = uni_ptr(a.planesz);
-  const u32 k_ztile = uni(a.z_tile_units);
-
   // what a path-tile with flagged permutations does: 2 queue them (GCRE_IE_FLAGQ=1), 1 the second look of the ladder,
   // 0 the exact pass at once (thresholds that do not come from the maxima)
-  const u32 k_road = (k_lad_mode == 0u) ? (uni(a.flagq) != 0u ? 2u : 1u) : 0u;
+  auto road = [&]() -> u32 { return (ap->lad_mode == 0) ? (ap->flagq != 0u ? 2u : 1u) : 0u; };
 
   int cur_kt = -1;
   u32 valid = 0u;
-  u32 lad_base = (k_lad_mode == 0u) ? 0u : ((u32)kLadderLevels - 1u + k_lad_mode) * k_lstride;
-  const u32 lad_keep = (u32)kLadderLevels * k_lstride;
+  u32 lad_base = (ap->lad_mode == 0) ? 0u : ((u32)kLadderLevels - 1u + (u32)ap->lad_mode) * (u32)ap->ladder_stride;
   u32 n_slow = 0u;
 #ifdef GCRE_IE_TIMING
   // header + loads issued, base counters, filter intervals, filter pass, exact pass, exchange, total, quads; inside the
@@ -121,10 +117,10 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(G
   u32 n_flagged = 0u;
   const u64 tm_begin = __builtin_amdgcn_s_memtime();
 #endif
-  __amdgpu_buffer_rsrc_t mt = __builtin_amdgcn_make_buffer_rsrc((void*)k_mt, 0, 0x7fffffff, 0x00020000);
+  __amdgpu_buffer_rsrc_t mt = __builtin_amdgcn_make_buffer_rsrc((void*)ap->mt, 0, 0x7fffffff, 0x00020000);
   // the planes of the rows the joins add, one descriptor per tile: a row is then a scalar byte offset into it (the
   // scalar offset takes no part in the range check).  WIDE builds a descriptor per row instead.
-  __amdgpu_buffer_rsrc_t zt = __builtin_amdgcn_make_buffer_rsrc((void*)k_planesz, 0, 0x7fffffff, 0x00020000);
+  __amdgpu_buffer_rsrc_t zt = __builtin_amdgcn_make_buffer_rsrc((void*)ap->planesz, 0, 0x7fffffff, 0x00020000);
 
   // The queued permutations, one per lane: S = how many of the path's (at most 8) overlap patients are cases in that
   // permutation -- bit `bb` of one dword of each patient's mask row, padding entries point at the all-zero row --
@@ -134,9 +130,9 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(G
     if ((u32)lane < fq_n) {
       const u32 q = fq[0][lane], w = fq[1][lane];
       const u32 bb = (w >> 17) & 31u, at = (w >> 22) * 4u;
-      const u32x4* e = (const u32x4*)(a.dlist + (u64)q * 8u);
+      const u32x4* e = (const u32x4*)(ap->dlist + (u64)q * 8u);
       const u32x4 e0 = e[0], e1 = e[1];
-      const u32 tot = a.tot[q];
+      const u32 tot = ap->tot[q];
       // (the entry is per lane here, so it goes into the vector offset, which the descriptor's 2-GiB range check sees --
       // the exact pass has it in the unchecked scalar offset.  The host switches the queue off where a tile of masks
       // reaches 2 GiB, gcre_host.hip: 8 million patients)
@@ -150,7 +146,7 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(G
 #pragma unroll
       for (int j = 0; j < 8; j++) S += (y[j] >> bb) & 1u;
       const u32 cell = sp_diag_offset(tot) + (w & 0x1ffffu) - S;
-      __hip_atomic_fetch_max(nmax_lds[wave] + bb * 64u + (w >> 22), ((const u32*)a.t32)[cell], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);   // ds_max_u32
+      __hip_atomic_fetch_max(nmax_lds[wave] + bb * 64u + (w >> 22), ((const u32*)ap->t32)[cell], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);   // ds_max_u32
     }
     fq_n = 0u;
     GCRE_QT(td1);
@@ -162,12 +158,16 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(G
   // maximum this wave KNOWS of every permutation of the tile (its own finds + the others' as of the last exchange), which
   // is what the queued permutations are folded into (fq_drain) and what the second look of the filter tests against.
   auto merge_global = [&](bool want_theta) {
-    u32* out = a.null_bits + (size_t)cur_kt * 2048 + lane * 32;
-    __amdgpu_buffer_rsrc_t nb = __builtin_amdgcn_make_buffer_rsrc((void*)(a.null_bits + (size_t)cur_kt * 2048), 0, 8192, 0x00020000);
+    u32* out = ap->null_bits + (size_t)cur_kt * 2048 + lane * 32;
+    __amdgpu_buffer_rsrc_t nb = __builtin_amdgcn_make_buffer_rsrc((void*)(ap->null_bits + (size_t)cur_kt * 2048), 0, 8192, 0x00020000);
     u32x4 g4[8];
 #pragma unroll
     for (int j = 0; j < 8; j++) g4[j] = __builtin_amdgcn_raw_buffer_load_b128(nb, (u32)lane * 128u + (u32)j * 16u, 0, 16 /* sc1 */);
     u32 lo = 0xffffffffu;
+    // (the live bits tested HERE: left to itself the compiler turns the 32 tests into 32 lane masks when the tile
+    // changes -- 64 scalar registers, spilled once per ticket and reloaded at every exchange)
+    u32 live = valid;
+    asm volatile("" : "+v"(live));
 #pragma unroll
     for (int q = 0; q < 32; q++) {
       const u32 g = g4[q >> 2][q & 3];
@@ -175,7 +175,7 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(G
       if (own > g) atomicMax(out + q, own);     // only what this wave raised itself can be above the global value
       const u32 v = own > g ? own : g;
       nm[q * 64] = want_theta ? v : 0u;         // the tile ends: the next tile starts from nothing
-      if ((valid >> q) & 1u) lo = v < lo ? v : lo;
+      if ((live >> q) & 1u) lo = v < lo ? v : lo;
     }
     return lo;
   };
@@ -186,7 +186,7 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(G
     if (theta == 0xffffffffu) theta = 0u;
     int j = (int)(__uint_as_float(theta) * (float)kLadderPerUnit);
     j = j < 0 ? 0 : (j > kLadderLevels - 1 ? kLadderLevels - 1 : j);
-    lad_base = (u32)j * k_lstride;
+    lad_base = (u32)j * (u32)ap->ladder_stride;
   };
   auto flush_tile = [&]() {   // (before the tile changes: queued items address this tile's masks)
     fq_drain();
@@ -196,11 +196,12 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(G
 
   WorkQueue wq;
   wq.st = wq_state[wave];
-  wq.init(a.queue, (k_quad_end - k_quad_begin + k_batch - 1u) / k_batch, k_nkt);
+  wq.init(ap->queue, ((u32)ap->quad_end - (u32)ap->quad_begin + (u32)ap->batch - 1u) / (u32)ap->batch, (u32)ap->nkt);
   wq.select(blockIdx.x & 7u);
   u32 ticket = wq.take(lane);
   int since = 0, period = 1;
   for (;;) {
+    ie_args_again(ap);
     const u32 work = __builtin_amdgcn_readfirstlane(ticket);
     const u32 q_n = wq.get(2);
     if (work >= q_n) {
@@ -211,16 +212,16 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(G
     ticket = wq.take(lane);
     const u32 item = wq.get(1) + work, nbt = wq.get(3);
     const int kt = __builtin_amdgcn_readfirstlane((int)(item / nbt));
-    const u32 q_lo = uni(k_quad_begin + (item - (u32)kt * nbt) * k_batch);
-    const u32 q_hi = uni(q_lo + k_batch < k_quad_end ? q_lo + k_batch : k_quad_end);
+    const u32 q_lo = uni((u32)ap->quad_begin + (item - (u32)kt * nbt) * (u32)ap->batch);
+    const u32 q_hi = uni(q_lo + (u32)ap->batch < (u32)ap->quad_end ? q_lo + (u32)ap->batch : (u32)ap->quad_end);
     if (kt != cur_kt) {
       flush_tile();
       cur_kt = kt;
-      mt = __builtin_amdgcn_make_buffer_rsrc((void*)(k_mt + (size_t)kt * k_mt_rows * 256u), 0, 0x7fffffff, 0x00020000);
-      if constexpr (!WIDE) zt = __builtin_amdgcn_make_buffer_rsrc((void*)(k_planesz + (u64)kt * (u64)k_ztile * 1024u), 0, 0x7fffffff, 0x00020000);
-      const int live = (int)k_K - kt * 2048 - lane * 32;
+      mt = __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)ap->mt + (size_t)kt * ap->mt_rows * 256u), 0, 0x7fffffff, 0x00020000);
+      if constexpr (!WIDE) zt = __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)ap->planesz + (u64)kt * (u64)ap->z_tile_units * 1024u), 0, 0x7fffffff, 0x00020000);
+      const int live = ap->K - kt * 2048 - lane * 32;
       valid = live >= 32 ? 0xffffffffu : (live <= 0 ? 0u : ((1u << live) - 1u));
-      if (k_lad_mode == 0u) lad_base = 0u;
+      if (ap->lad_mode == 0) lad_base = 0u;
       since = 0;
       period = 1;
     }
@@ -234,9 +235,9 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(G
       for (int g = 0; g < kQSegs; g++) {
         h[g] = 0u;
         if ((u32)g < cnt_) {
-          const u32* src = (const u32*)a.segs + (u64)(s0_ + (u32)g) * 3u + (u32)(lane < 3 ? lane : 0);
+          const u32* src = (const u32*)ap->segs + (u64)(s0_ + (u32)g) * 3u + (u32)(lane < 3 ? lane : 0);
           if constexpr (REC) {
-            if (lane >= 4 && lane < 16) src = a.rec_segs + (u64)(s0_ + (u32)g) * kRecSegWords + (u32)(lane - 4);
+            if (lane >= 4 && lane < 16) src = ap->rec_segs + (u64)(s0_ + (u32)g) * kRecSegWords + (u32)(lane - 4);
           }
           h[g] = *src;
         }
@@ -247,6 +248,7 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(G
     bool have_next = false;
     for (u32 qi = q_lo; qi < q_hi; qi++) {
       // ---- the quad: up to kQSegs consecutive segments of the table, same added rows, same length ----
+      ie_args_again(ap);
       GCRE_QT(t0);
       u32 hdr[kQSegs];
       u32 qe;
@@ -255,23 +257,24 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(G
 #pragma unroll
         for (int g = 0; g < kQSegs; g++) hdr[g] = hdr_n[g];
       } else {
-        qe = uni(((const u32 GCRE_CONSTANT*)a.quads)[qi]);
+        qe = uni(((const u32 GCRE_CONSTANT*)ap->quads)[qi]);
         load_hdr(qe, hdr);
       }
       have_next = qi + 1u < q_hi;
-      if (have_next) qe_n = uni(((const u32 GCRE_CONSTANT*)a.quads)[qi + 1u]);   // its headers go out below, behind this quad's loads
+      if (have_next) qe_n = uni(((const u32 GCRE_CONSTANT*)ap->quads)[qi + 1u]);   // its headers go out below, behind this quad's loads
       const u32 qcnt = (qe >> 30) + 1u;
       const u32 s0 = qe & 0x3fffffffu;
       const u32 npaths = rdlane(hdr[0], 2);
       GCRE_QT(te0);
-      if (k_lad_mode == 0u && ++since >= period) {
+      if (ap->lad_mode == 0 && ++since >= period) {
         exchange();
         since = 0;
         period = period < kIeRefresh ? period * 2 : kIeRefresh;
       }
       GCRE_QT(te1);
       GCRE_QT_ADD(5, te1, te0);
-      const u32 lad_row = (s0 < k_score_segs) ? lad_base : lad_keep;
+      const u32 lad_keep = (u32)kLadderLevels * (u32)ap->ladder_stride;
+      const u32 lad_row = (s0 < ap->score_segs) ? lad_base : lad_keep;
 
       // ---- per segment: the metadata of its paths (lane t <-> path first + t) and its base counters ----
       u32 infov[kQSegs], lhv[kQSegs], lfv[kQSegs], firstg[kQSegs];
@@ -304,11 +307,11 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(G
           const u32 first = rdlane(hdr[g], 1);
           firstg[g] = first;
           const u32 qv = first + (((u32)lane < npaths) ? (u32)lane : 0u);
-          infov[g] = a.linfo[qv];
-          totv[g] = a.tot[qv];
+          infov[g] = ap->linfo[qv];
+          totv[g] = ap->tot[qv];
           if (g == 0) {   // the same for every segment of the quad: 1-KB units from planesz, or bytes from the tile's first row
-            if constexpr (WIDE) zunit = ((u32)kt * (u32)a.rowsz + (a.rowz[qv] & 0x7fffffffu)) * (u32)a.gz;
-            else zunit = ((a.rowz[qv] & 0x7fffffffu) * (u32)a.gz) << 10;
+            if constexpr (WIDE) zunit = ((u32)kt * (u32)ap->rowsz + (ap->rowz[qv] & 0x7fffffffu)) * (u32)ap->gz;
+            else zunit = ((ap->rowz[qv] & 0x7fffffffu) * (u32)ap->gz) << 10;
           }
         }
       }
@@ -317,7 +320,7 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(G
         if ((u32)g < qcnt) {
           const u32 row0 = rdlane(hdr[g], 0);
           if constexpr (!REC) {
-            load_groups(B[g], a.planes0, ((u64)kt * (u64)a.rows0 + (u64)row0) * (u64)a.g0, a.g0);
+            load_groups(B[g], ap->planes0, ((u64)kt * (u64)ap->rows0 + (u64)row0) * (u64)ap->g0, ap->g0);
           } else {
             // the segment's recipe words sit next to the segment table (k_fill_rec_segs): paths0 row of the producing
             // join, row it added, list info, where a long list continues, the list's first 8 entries
@@ -337,7 +340,7 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(G
             // the row's carrier total bounds the counts of everything it was made from: planes above it are zero and are
             // not read (3 KB -> 2 KB of HBM per segment and tile for most rows: this load is the kernel's HBM traffic)
             const int ga_need = (int)linfo_groups(rinfo_g[g]) + 1;
-            load_groups(B[g], a.rec_planes_a, ((u64)kt * (u64)a.rec_rows_a + (u64)ra) * (u64)a.rec_ga, ga_need < a.rec_ga ? ga_need : a.rec_ga);
+            load_groups(B[g], ap->rec_planes_a, ((u64)kt * (u64)ap->rec_rows_a + (u64)ra) * (u64)ap->rec_ga, ga_need < ap->rec_ga ? ga_need : ap->rec_ga);
           }
         }
       }
@@ -348,11 +351,11 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(G
       // producing join added -- that gene -- is the same for all of them: its planes are loaded once
       if constexpr (REC) {
         u32 ZR[LP];
-        load_groups(ZR, a.rec_planes_z, ((u64)kt * (u64)a.rec_rows_z + (u64)rz_g[0]) * (u64)a.rec_gz, a.rec_gz);
+        load_groups(ZR, ap->rec_planes_z, ((u64)kt * (u64)ap->rec_rows_z + (u64)rz_g[0]) * (u64)ap->rec_gz, ap->rec_gz);
 #pragma unroll
         for (int g = 0; g < kQSegs; g++) {
           if ((u32)g < qcnt) {
-            if (rz_g[g] != rz_g[0]) load_groups(ZR, a.rec_planes_z, ((u64)kt * (u64)a.rec_rows_z + (u64)rz_g[g]) * (u64)a.rec_gz, a.rec_gz);
+            if (rz_g[g] != rz_g[0]) load_groups(ZR, ap->rec_planes_z, ((u64)kt * (u64)ap->rec_rows_z + (u64)rz_g[g]) * (u64)ap->rec_gz, ap->rec_gz);
             const u32 rinfo = rinfo_g[g];
             const u32 rlen = linfo_len(rinfo);
             u32 S[L];
@@ -363,7 +366,7 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(G
               for (int l = 0; l < L; l++) S[l] = (l < 4) ? S4[l < 4 ? l : 0] : 0u;
             }
             if (rlen > 8u) {   // the producing join's list was long: the rest of it, 8 entries at a time
-              const u32 GCRE_CONSTANT* more = (const u32 GCRE_CONSTANT*)(a.rec_over + rlov_g[g]);
+              const u32 GCRE_CONSTANT* more = (const u32 GCRE_CONSTANT*)(ap->rec_over + rlov_g[g]);
               for (u32 p = 0u; p + 8u < rlen; p += 8u) {
                 const u32x8 o8 = *(const u32x8 GCRE_CONSTANT*)(more + p);
                 u32 yy[8], s4[4];
@@ -398,7 +401,7 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(G
                 cy = majority(bl, S[l], cy);
               }
             }
-            if (rz_g[g] != rz_g[0]) load_groups(ZR, a.rec_planes_z, ((u64)kt * (u64)a.rec_rows_z + (u64)rz_g[0]) * (u64)a.rec_gz, a.rec_gz);
+            if (rz_g[g] != rz_g[0]) load_groups(ZR, ap->rec_planes_z, ((u64)kt * (u64)ap->rec_rows_z + (u64)rz_g[0]) * (u64)ap->rec_gz, ap->rec_gz);
           }
         }
       }
@@ -409,7 +412,7 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(G
 #pragma unroll
       for (int g = 0; g < kQSegs; g++) {
         if ((u32)g < qcnt) {
-          const u32 lh = a.ladder[lad_row + totv[g]];
+          const u32 lh = ap->ladder[lad_row + totv[g]];
           const u32 r0 = infov[g];
           const u32 ov = linfo_true_len(r0);
           const u32 lo = lh & 0xffffu;
@@ -421,13 +424,13 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(G
 
       GCRE_QT(t3);
       GCRE_QT_ADD(2, t3, t2);
-      const u32x8 GCRE_CONSTANT* slots = (const u32x8 GCRE_CONSTANT*)a.dlist;
+      const u32x8 GCRE_CONSTANT* slots = (const u32x8 GCRE_CONSTANT*)ap->dlist;
       // (zu = rdlane(zunit, position): the filter pass reads it one step ahead, a scalar that comes out of a read-lane
       // cannot address a load in the next few cycles)
       auto issue_at = [&](u32 zu, u32 (&ZZ)[LZ]) {
         __amdgpu_buffer_rsrc_t rz = zt;
         u32 so = 0u;
-        if constexpr (WIDE) rz = __builtin_amdgcn_make_buffer_rsrc((void*)(k_planesz + (u64)zu * 1024u), 0, 0x7fffffff, 0x00020000);
+        if constexpr (WIDE) rz = __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)ap->planesz + (u64)zu * 1024u), 0, 0x7fffffff, 0x00020000);
         else so = zu;
 #pragma unroll
         for (int j = 0; j < GZ; j++) {
@@ -477,7 +480,7 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(G
         const u32 info = rdlane(infov[g], t);
         // ((info & 1u) != 0u is linfo_overlap(info) written out: with the helper here the compiler schedules this kernel
         // differently)
-        if (k_road != 0u && (info & 1u) != 0u && __builtin_amdgcn_ballot_w64(__builtin_popcount(fm) > GCRE_REFINE_MAX) == 0ull) {
+        if ((info & 1u) != 0u && road() != 0u && __builtin_amdgcn_ballot_w64(__builtin_popcount(fm) > GCRE_REFINE_MAX) == 0ull) {
           GCRE_QT(ts0);
 #ifdef GCRE_IE_TIMING
           tm[10] += 1;
@@ -498,7 +501,7 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(G
               }
             }
           };
-          if (k_road == 2u && linfo_len(info) <= 8u) {
+          if (road() == 2u && linfo_len(info) <= 8u) {
             // how many items the path-tile queues (at most GCRE_REFINE_MAX per lane): room is made before W is rebuilt,
             // so that a drain does not have the planes of W to keep
             u32 total = 0u;
@@ -540,7 +543,7 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(G
           // marking those at once, as first planned, took the exact pass of the level-4 launch from 2.8 to 6.4 of a
           // wave's 41 Mcycles and the gain with it)
           const u32 ov = linfo_true_len(info);
-          const u32* lad_t = a.ladder + rdlane(totv[g], t);
+          const u32* lad_t = ap->ladder + rdlane(totv[g], t);
           sum_w();
           bool unsafe = false;
           while (__builtin_amdgcn_ballot_w64(fm != 0u) != 0ull) {   // one flagged permutation per lane and round
@@ -553,7 +556,7 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(G
             if (has) {
               int j = (int)(__uint_as_float(nm[bb * 64]) * (float)kLadderPerUnit);
               j = j < 0 ? 0 : (j > kLadderLevels - 1 ? kLadderLevels - 1 : j);
-              const u32 lh = lad_t[(u32)j * k_lstride];
+              const u32 lh = lad_t[(u32)j * (u32)ap->ladder_stride];
               const u32 lo = lh & 0xffffu, hi = lh >> 16;
               // every count in [max(0, W - ov), W] inside [lo, hi]?  (counts are never negative: lo = 0 needs no margin)
               if (cnt > hi || (lo != 0u && cnt < lo + ov)) unsafe = true;
@@ -638,7 +641,7 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(G
 #pragma unroll
         for (int l = 0; l < L; l++) S[l] = (l < 4) ? S4[l < 4 ? l : 0] : 0u;
         if (len > 8u) {   // long list: further blocks of 8 entries
-          const u32 GCRE_CONSTANT* more = (const u32 GCRE_CONSTANT*)(a.dover + ((const u32 GCRE_CONSTANT*)a.lover)[it.lov]);
+          const u32 GCRE_CONSTANT* more = (const u32 GCRE_CONSTANT*)(ap->dover + ((const u32 GCRE_CONSTANT*)ap->lover)[it.lov]);
           for (u32 p = 0u; p + 8u < len; p += 8u) {
             const u32x8 o8 = *(const u32x8 GCRE_CONSTANT*)(more + p);
             u32 yy[8], s4[4];
@@ -751,11 +754,11 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(G
   flush_tile();
 #ifdef GCRE_IE_TIMING
   tm[6] = __builtin_amdgcn_s_memtime() - tm_begin;
-  if (a.timing && lane == 0)
-    for (int i = 0; i < 11; i++) atomicAdd((unsigned long long*)a.timing + i, (unsigned long long)tm[i]);
-  if (a.timing && n_flagged) atomicAdd((unsigned long long*)a.timing + 11, (unsigned long long)n_flagged);
+  if (ap->timing && lane == 0)
+    for (int i = 0; i < 11; i++) atomicAdd((unsigned long long*)ap->timing + i, (unsigned long long)tm[i]);
+  if (ap->timing && n_flagged) atomicAdd((unsigned long long*)ap->timing + 11, (unsigned long long)n_flagged);
 #endif
-  if (a.stats && lane == 0 && n_slow) atomicAdd(a.stats, n_slow);
+  if (ap->stats && lane == 0 && n_slow) atomicAdd(ap->stats, n_slow);
 }
 
 #define GCRE_IEQ_W(EXPR, LL, GG, RR) if (wide) { EXPR(LL, GG, RR, true); } else { EXPR(LL, GG, RR, false); }
