@@ -117,6 +117,8 @@ SET_SCORE = np.dtype([("set", "<i8"), ("valid", "<i4"), ("cases", "<i4"), ("ctrl
 # gcre_family_score
 FAMILY_SCORE = np.dtype([("n_ge_stepdown", "<i8"), ("exceed", "<u8"), ("observed", "<i8")], align=True)
 FAMILY_KMAX = 10   # GCRE_FAMILY_KMAX
+# gcre_minp_score
+MINP_SCORE = np.dtype([("n_le_minp", "<i8"), ("n_le_stepdown", "<i8")], align=True)
 # gcre_burden
 BURDEN = np.dtype([("total", "<i8"), ("observed", "<i8"), ("n_ge", "<i8"), ("n_le", "<i8"), ("planes", "<i4"),
                    ("p_upper", "<f8"), ("p_lower", "<f8")], align=True)
@@ -137,6 +139,7 @@ EXPORTS = [
     "gcre_decorated_splits", "gcre_decorated_pvalues", "gcre_score_sets",
     "gcre_score_sets_given", "gcre_given_launches",
     "gcre_score_sets_family", "gcre_family_launches",
+    "gcre_score_sets_minp", "gcre_minp_launches",
     "gcre_set_overlap", "gcre_overlap_launches",
     "gcre_clump_sets", "gcre_clump_launches",
     "gcre_set_patient_counts", "gcre_patient_launches",
@@ -266,6 +269,9 @@ _FEATURES = {
     "family": ("sets", ["gcre_score_sets_family", "gcre_family_launches"], "family-wise set inference (gcre_score_sets_family)", {
         "gcre_score_sets_family": (_I, [_V, ctypes.POINTER(gcre_set_input), _P, _I64, ctypes.POINTER(_I64), _P, _P, _P]),
         "gcre_family_launches": (_I64, [_V])}),
+    "minp": ("sets", ["gcre_score_sets_minp", "gcre_minp_launches"], "min-P set inference (gcre_score_sets_minp)", {
+        "gcre_score_sets_minp": (_I, [_V, ctypes.POINTER(gcre_set_input), _P, _I64, ctypes.POINTER(_I64), _P, _P, _P]),
+        "gcre_minp_launches": (_I64, [_V])}),
     "overlap": (None, ["gcre_set_overlap"], "carrier overlaps (gcre_set_overlap)", {
         "gcre_set_overlap": (_I, [_V, ctypes.POINTER(gcre_set_input), _P, _I64, _P, _I64, _P, _P]),
         "gcre_overlap_launches": (_I64, [_V])}),
@@ -329,6 +335,7 @@ _decorated_lib = functools.partial(_feature_lib, "decorated")
 _sets_lib = functools.partial(_feature_lib, "sets")
 _given_lib = functools.partial(_feature_lib, "given")
 _family_lib = functools.partial(_feature_lib, "family")
+_minp_lib = functools.partial(_feature_lib, "minp")
 _overlap_lib = functools.partial(_feature_lib, "overlap")
 _clump_lib = functools.partial(_feature_lib, "clump")
 _patients_lib = functools.partial(_feature_lib, "patients")
@@ -1041,6 +1048,36 @@ class JoinExec:
     def family_launches(self) -> int:
         """k_family_null / k_family_scan / k_family_hist launches of this context so far."""
         return int(_family_lib().gcre_family_launches(self._h))
+
+    def minp_tests(self, sets, rows, signs=None, min_count: bool = False, counts: bool = False):
+        """Westfall-Young min-P over the family of the given sets (gcre_score_sets_minp).  ``sets`` / ``rows``
+        / ``signs`` as ``score_sets`` takes them.  Returns ``(records, minp)``: the SET_SCORE records of ``score_sets``, and
+        one MINP_SCORE record per set -- ``n_le_minp`` (permutations whose smallest within-set count over ALL valid sets is at
+        most the set's own ``n_ge``) and ``n_le_stepdown`` (the same with the sets of a smaller ``n_ge`` left out); a NaN
+        score gives 0 / 0, an NA member -1 / -1.  With ``min_count`` also uint32 [iters], per permutation the smallest count
+        over the valid sets (0xFFFFFFFF without one); with ``counts`` also uint32 [sets][iters], the count R of every null
+        score within its own row -- the permutations of that set whose null score is at least as large (rows of 0xFFFFFFFF
+        for sets with an NA member).  ``report.minp_columns`` turns the records into p-values.  Errors raise GcreError."""
+        lib = _minp_lib()
+        n = self.num_cases + self.num_ctrls
+        S = len(sets)
+        inp, keep = _set_input(sets, rows, signs, n)
+        out = np.zeros(max(S, 1), dtype=SET_SCORE)
+        mp = np.zeros(max(S, 1), dtype=MINP_SCORE)
+        mc = np.full(self.iters, 0xFFFFFFFF, dtype=np.uint32) if min_count else None
+        cn = np.full((S, self.iters), 0xFFFFFFFF, dtype=np.uint32) if counts else None
+        n_out = ctypes.c_int64(0)
+        rc = lib.gcre_score_sets_minp(self._h, ctypes.byref(inp), _ptr(out), len(out), ctypes.byref(n_out), _ptr(mp),
+                                      _ptr(mc) if min_count and mc.size else None, _ptr(cn) if counts and cn.size else None)
+        del keep
+        if rc != GCRE_OK:
+            raise GcreError(self._lib.gcre_last_error(self._h).decode())
+        res = (out[:n_out.value], mp[:n_out.value])
+        return res + ((mc,) if min_count else ()) + ((cn,) if counts else ())
+
+    def minp_launches(self) -> int:
+        """k_minp_gather / k_family_null / k_minp_rank / k_minp_scan launches of ``minp_tests`` on this context so far."""
+        return int(_minp_lib().gcre_minp_launches(self._h))
 
     def set_overlap(self, sets, rows, a=None, b=None):
         """Carrier overlaps of caller-given sets (gcre_set_overlap).  A set's carrier row is the OR of all

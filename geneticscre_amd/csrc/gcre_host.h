@@ -255,6 +255,7 @@ struct gcre_ctx {
   int64_t patient_launches = 0;      // kernels gcre_set_patient_counts launched on this context (gcre_patient_launches)
   int64_t burden_launches = 0;       // kernels gcre_patient_burden launched on this context (gcre_burden_launches)
   int64_t family_launches = 0;       // k_family_null / _scan / _hist launches of this context (gcre_family_launches)
+  int64_t minp_launches = 0;         // k_minp_gather / k_family_null / k_minp_rank / _scan launches of gcre_score_sets_minp
 
   // resident inputs
   uint64_t* d_case_mask = nullptr;   // [Wp]

@@ -1,5 +1,5 @@
 // gcre_host_stats.hip -- the entry points of include/gcre_hip.h that use a context but not the join driver: generated
-// permutation masks, decorated p-values (gcre_decorated.hip), set scores (gcre_sets.hip, conditional: gcre_given.hip, family-wise: gcre_family.hip) and carrier overlaps
+// permutation masks, decorated p-values (gcre_decorated.hip), set scores (gcre_sets.hip, conditional: gcre_given.hip, family-wise: gcre_family.hip, min-P: gcre_minp.hip) and carrier overlaps
 // (gcre_overlap.hip), greedy clumps (gcre_clump.hip), carrier tallies per patient (gcre_patients.hip) and burden tests of per-patient weights (gcre_burden.hip), and the per-gene tally (gcre_genes.hip), the null exceedance counts (gcre_exceed.hip,
 // gcre_stepdown.hip) and the hit lists (gcre_hits.hip) as objects.  What a join does with an armed tally, armed counts or
 // an armed list -- check_tally, fold_genes, count_exceed, collect_hits -- is in gcre_host.hip.  Host code only.
@@ -400,9 +400,157 @@ void family_stage(gcre_ctx* c, DevScratch& d, const uint64_t* d_rows, const uint
   }
 }
 
-// gcre_score_sets, and with `fo` gcre_score_sets_family: the same checks, host stage and device stage
+// What gcre_score_sets_minp returns beside the records
+struct MinpOut {
+  gcre_minp_score* mp;      // [n_sets]
+  uint32_t* min_count;      // optional [iterations]
+  uint32_t* null_counts;    // optional [n_sets][iterations]
+};
+
+// The slab of gcre_score_sets_minp: whole rows -- every permutation tile of a valid set, its null scores and its counts, 8
+// bytes per column -- under GCRE_MINP_MAX_MB (GCRE_MINP_SLAB_SETS bounds it further: tests).  One row above the limit is refused.
+int check_minp(gcre_ctx* c, const gcre_set_input* in, const MinpOut& mo, const std::string& who, int64_t& slab_rows) {
+  slab_rows = 0;
+  const int64_t S = in->n_sets;
+  if (S > 0 && !mo.mp) return fail(c, GCRE_ERR_ARG, who + ": NULL argument (mp_out)");
+  int64_t V = 0;
+  for (int64_t s = 0; s < S; s++) V += set_is_valid(in, s) ? 1 : 0;
+  if (V > 0x7fffffff) return fail(c, GCRE_ERR_ARG, who + ": too many sets");
+  const int K = c->g.K;
+  if (V == 0 || K == 0) return GCRE_OK;
+  double mb = 1024;
+  if (const char* e = std::getenv("GCRE_MINP_MAX_MB")) mb = std::min(std::max(std::atof(e), 0.0), 1048576.0);   // tests: fractions
+  const int64_t tiles = ((int64_t)K + kSetPermTile - 1) / kSetPermTile;
+  const double row_bytes = (double)tiles * kSetPermTile * 8.0;
+  if (row_bytes > mb * 1048576.0)
+    return fail(c, GCRE_ERR_ARG, who + ": the null scores and counts of one set under " + std::to_string(tiles) + " tiles of " +
+                                     std::to_string(kSetPermTile) + " permutations exceed GCRE_MINP_MAX_MB");
+  slab_rows = std::min<int64_t>(V, (int64_t)(mb * 1048576.0 / row_bytes));
+  if (const char* e = std::getenv("GCRE_MINP_SLAB_SETS")) slab_rows = std::min<int64_t>(slab_rows, std::max<int64_t>(std::atoll(e), 1));
+  return GCRE_OK;
+}
+
+// The min-P stage of gcre_score_sets_minp, behind score_set_rows: V valid sets' union rows and totals are on the device, obs
+// [V] their observed scores and ge [V] their counts c.  The walk order is NaN scores first, then c descending, stable;
+// k_minp_gather copies rows and totals into it.  Per slab of `slab_rows` rows of the walk k_family_null fills N over all
+// permutation tiles, k_minp_rank turns N into R, k_minp_scan carries the running minimum on and counts at the end of every
+// tie group.  Every count is an exact integer and the minimum is carried across the slabs, so no result depends on them.
+// Errors stay in `d`.
+void minp_stage(gcre_ctx* c, DevScratch& d, const uint64_t* d_rows, const uint32_t* d_tot, const std::vector<int64_t>& vset,
+                const std::vector<double>& obs, const std::vector<unsigned long long>& ge, int64_t slab_rows, const MinpOut& mo) {
+  const Geometry& g = c->g;
+  const int K = g.K, M = g.method;
+  const int64_t V = (int64_t)vset.size();
+  std::vector<uint32_t> order((size_t)V);
+  for (int64_t v = 0; v < V; v++) order[(size_t)v] = (uint32_t)v;
+  auto is_nan = [&](uint32_t v) { return obs[v] != obs[v]; };
+  std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) {
+    const bool nx = is_nan(x), ny = is_nan(y);
+    return (nx || ny) ? (nx && !ny) : ge[x] > ge[y];
+  });
+  // per row of the walk: c, and whether it ends a tie group that is counted (a run of equal c among the scored sets)
+  std::vector<uint32_t> meta((size_t)V);
+  for (int64_t i = 0; i < V; i++) {
+    const uint32_t v = order[(size_t)i];
+    const bool end = !is_nan(v) && (i + 1 == V || ge[order[(size_t)(i + 1)]] != ge[v]);   // (NaN rows come first: none follows)
+    meta[(size_t)i] = (uint32_t)ge[v] | (end ? 0x80000000u : 0u);                          // c <= K < 2^31
+  }
+  const int64_t tiles = ((int64_t)K + kSetPermTile - 1) / kSetPermTile;
+  const int64_t stride = tiles * kSetPermTile;
+  const int rw = M * 2 * g.Wp;
+  std::vector<uint32_t> ident((size_t)slab_rows), qinit((size_t)K, 0xffffffffu);
+  for (int64_t i = 0; i < slab_rows; i++) ident[(size_t)i] = (uint32_t)i;
+  const uint32_t* d_order = d.put(order.data(), (size_t)V);
+  const uint32_t* d_meta = d.put(meta.data(), (size_t)V);
+  const uint32_t* d_ident = d.put(ident.data(), (size_t)slab_rows);
+  uint32_t* d_q = d.put(qinit.data(), (size_t)K);
+  uint32_t* d_grows = d.take<uint32_t>((size_t)V * (size_t)rw);
+  uint32_t* d_gtot = d.take<uint32_t>((size_t)V * (size_t)M);
+  uint32_t* d_N = d.take<uint32_t>((size_t)slab_rows * (size_t)stride);
+  uint32_t* d_R = d.take<uint32_t>((size_t)slab_rows * (size_t)stride);
+  uint32_t* d_le = d.take<uint32_t>((size_t)V);
+  d.zero(d_le, (size_t)V);
+  if (d.ok()) {
+    MinpGatherArgs ga{};
+    ga.rows = (const uint32_t*)d_rows;
+    ga.tot = d_tot;
+    ga.order = d_order;
+    ga.rows_out = d_grows;
+    ga.tot_out = d_gtot;
+    ga.nsets = V;
+    ga.rw = rw;
+    ga.m = M;
+    d.e = launch_minp_gather(ga, c->stream);
+    if (d.ok()) c->minp_launches++;
+  }
+  std::vector<uint32_t> stage;
+  for (int64_t r0 = 0; d.ok() && r0 < V; r0 += slab_rows) {
+    const int64_t nr = std::min(slab_rows, V - r0);
+    FamilyNullArgs na{};
+    fill_set_launch(na, c, (const uint64_t*)(d_grows + (size_t)r0 * (size_t)rw), d_gtot + (size_t)r0 * (size_t)M, nr);
+    na.rank = d_ident;
+    na.N = d_N;
+    na.kt0 = 0;
+    na.stride = stride;   // (nkt = tiles, pgroups by the rule over all tiles: as fill_set_launch left them)
+    d.e = launch_family_null(na, M, c->stream);
+    if (d.ok()) c->minp_launches++;
+    MinpRankArgs ra{};
+    ra.N = d_N;
+    ra.R = d_R;
+    ra.nsets = nr;
+    ra.stride = stride;
+    ra.K = K;
+    if (d.ok()) {
+      d.e = launch_minp_rank(ra, c->stream);
+      if (d.ok()) c->minp_launches++;
+    }
+    if (mo.null_counts) {   // whole rows through a staging buffer, at most ~32 MB at a time
+      const int64_t rows_at_once = std::max<int64_t>(1, ((int64_t)8 << 20) / stride);
+      stage.resize((size_t)std::min(rows_at_once, nr) * (size_t)stride);
+      for (int64_t q0 = 0; d.ok() && q0 < nr; q0 += rows_at_once) {
+        const int64_t nq = std::min(rows_at_once, nr - q0);
+        d.download(stage.data(), d_R + (size_t)q0 * (size_t)stride, (size_t)nq * (size_t)stride);
+        d.sync();
+        if (!d.ok()) break;
+        for (int64_t r = 0; r < nq; r++)
+          std::memcpy(mo.null_counts + (size_t)vset[order[(size_t)(r0 + q0 + r)]] * (size_t)K, stage.data() + (size_t)r * (size_t)stride,
+                      (size_t)K * 4);
+      }
+    }
+    MinpScanArgs sa{};
+    sa.R = d_R;
+    sa.meta = d_meta + r0;
+    sa.q = d_q;
+    sa.n_le = d_le + r0;
+    sa.nsets = nr;
+    sa.stride = stride;
+    sa.K = K;
+    if (d.ok()) {
+      d.e = launch_minp_scan(sa, c->stream);
+      if (d.ok()) c->minp_launches++;
+    }
+  }
+  std::vector<uint32_t> le((size_t)V), q((size_t)K);
+  d.download(le.data(), d_le, (size_t)V);
+  d.download(q.data(), d_q, (size_t)K);
+  d.sync();
+  if (!d.ok()) return;
+  if (mo.min_count) std::memcpy(mo.min_count, q.data(), (size_t)K * 4);
+  std::sort(q.begin(), q.end());
+  for (int64_t i = V - 2; i >= 0; i--)   // a tie group's count stands at its last row
+    if (!(meta[(size_t)i] >> 31) && !is_nan(order[(size_t)i])) le[(size_t)i] = le[(size_t)i + 1];
+  for (int64_t i = 0; i < V; i++) {
+    const uint32_t v = order[(size_t)i];
+    if (is_nan(v)) continue;   // a NaN score: 0 / 0
+    gcre_minp_score& m = mo.mp[vset[v]];
+    m.n_le_stepdown = (int64_t)le[(size_t)i];
+    m.n_le_minp = (int64_t)(std::upper_bound(q.begin(), q.end(), (uint32_t)ge[v]) - q.begin());
+  }
+}
+
+// gcre_score_sets, with `fo` gcre_score_sets_family and with `mo` gcre_score_sets_minp: the same checks, host stage and device stage
 int score_sets_common(gcre_ctx* c, const gcre_set_input* in, gcre_set_score* out, int64_t cap, int64_t* n_out, float* family_max,
-                      const std::string& who, const FamilyOut* fo) {
+                      const std::string& who, const FamilyOut* fo, const MinpOut* mo = nullptr) {
   if (!c) return GCRE_ERR_ARG;
   if (!in || !n_out || cap < 0 || (cap > 0 && !out)) return fail(c, GCRE_ERR_ARG, who + ": NULL argument");
   *n_out = 0;
@@ -417,6 +565,9 @@ int score_sets_common(gcre_ctx* c, const gcre_set_input* in, gcre_set_score* out
   int64_t slab_tiles = 0;
   if (fo)
     if (int rc = check_family(c, in, *fo, who, slab_tiles)) return rc;
+  int64_t slab_rows = 0;
+  if (mo)
+    if (int rc = check_minp(c, in, *mo, who, slab_rows)) return rc;
 
   // the host stage: per valid set the OR of its (+) members and of its (-) members (method 1: of all of them), within the
   // n patients, and their counts; the device rows are [valid set][M][Wp] words, the dword view k_set_null reads
@@ -461,6 +612,11 @@ int score_sets_common(gcre_ctx* c, const gcre_set_input* in, gcre_set_score* out
     if (fo->kmax) std::fill(fo->kmax, fo->kmax + (size_t)kFamilyKmax * (size_t)K, 0.0f);
     if (fo->null_scores) std::fill(fo->null_scores, fo->null_scores + (size_t)S * (size_t)K, std::numeric_limits<float>::quiet_NaN());
   }
+  if (mo) {   // as above: an invalid set -1 / -1 and a row of all ones, no minimum without a valid set or a permutation
+    for (int64_t s = 0; s < S; s++) mo->mp[s].n_le_minp = mo->mp[s].n_le_stepdown = out[s].valid ? 0 : -1;
+    if (mo->min_count) std::fill(mo->min_count, mo->min_count + K, 0xffffffffu);
+    if (mo->null_counts) std::fill(mo->null_counts, mo->null_counts + (size_t)S * (size_t)K, 0xffffffffu);
+  }
   const int64_t V = (int64_t)vset.size();
   if (V == 0) return GCRE_OK;
 
@@ -492,6 +648,10 @@ int score_sets_common(gcre_ctx* c, const gcre_set_input* in, gcre_set_score* out
     family_stage(c, d, d_rows, d_tot, vset, obs, slab_tiles, *fo);
     if (!d.ok()) return fail(c, GCRE_ERR_DEVICE, who + ": " + hipGetErrorString(d.e));
   }
+  if (mo && K > 0) {
+    minp_stage(c, d, d_rows, d_tot, vset, obs, ge, slab_rows, *mo);
+    if (!d.ok()) return fail(c, GCRE_ERR_DEVICE, who + ": " + hipGetErrorString(d.e));
+  }
   return GCRE_OK;
 }
 
@@ -513,6 +673,16 @@ int gcre_score_sets_family(gcre_ctx* c, const gcre_set_input* in, gcre_set_score
 }
 
 int64_t gcre_family_launches(const gcre_ctx* c) { return c ? c->family_launches : -1; }
+
+// Westfall-Young min-P over the family of the given sets: gcre_score_sets, then the min-P stage on the same
+// device rows.
+int gcre_score_sets_minp(gcre_ctx* c, const gcre_set_input* in, gcre_set_score* out, int64_t cap, int64_t* n_out,
+                         gcre_minp_score* mp_out, uint32_t* min_count, uint32_t* null_counts) {
+  const MinpOut mo{mp_out, min_count, null_counts};
+  return score_sets_common(c, in, out, cap, n_out, nullptr, "score_sets_minp", nullptr, &mo);
+}
+
+int64_t gcre_minp_launches(const gcre_ctx* c) { return c ? c->minp_launches : -1; }
 
 // Conditional set scores: gcre_score_sets on residual union rows that k_set_residual builds on the device
 // from the caller's gene rows and set list, uploaded once.  The entries without an NA member are walked in slabs so that the

@@ -589,6 +589,37 @@ struct FamilyHistArgs {
 };
 hipError_t launch_family_hist(const FamilyHistArgs& a, int cus, hipStream_t stream);
 
+// ---- min-P over a family of caller-given sets (gcre_minp.hip) ----
+// A slab is a run of rows of the walk order (NaN scores first, then the count c descending) with ALL permutation tiles:
+// N [rows][stride] from k_family_null, R [rows][stride] the within-row counts "values >= mine" over the live columns.
+constexpr int kMinpChunk = 16384;      // values of a row k_minp_rank sorts in LDS at a time (64 KiB)
+struct MinpGatherArgs {
+  const uint32_t* rows;         // [nsets][rw] union rows as the set stage left them
+  const uint32_t* tot;          // [nsets][m]
+  const uint32_t* order;        // [nsets] row of the input per row of the walk, a permutation of 0 .. nsets-1
+  uint32_t* rows_out;           // [nsets][rw]
+  uint32_t* tot_out;            // [nsets][m]
+  int64_t nsets;
+  int rw, m;                    // dwords per set (M * W32p), halves per set (M)
+};
+hipError_t launch_minp_gather(const MinpGatherArgs& a, hipStream_t stream);
+struct MinpRankArgs {
+  const uint32_t* N;            // [nsets][stride] bit patterns of non-negative floats
+  uint32_t* R;                  // [nsets][stride] column r < K: #{r' < K : N[.][r'] >= N[.][r]}; the other columns 0xffffffff
+  int64_t nsets, stride;        // stride: a multiple of 16 at or above K
+  int K;
+};
+hipError_t launch_minp_rank(const MinpRankArgs& a, hipStream_t stream);
+struct MinpScanArgs {
+  const uint32_t* R;            // [nsets][stride]
+  const uint32_t* meta;         // [nsets] by row: the count c; bit 31 = the last row of a counted tie group
+  uint32_t* q;                  // [K] the running minimum per permutation: read at the start, written at the end
+  uint32_t* n_le;               // [nsets] by row, adds at the last row of every counted tie group: permutations with q <= c
+  int64_t nsets, stride;
+  int K;
+};
+hipError_t launch_minp_scan(const MinpScanArgs& a, hipStream_t stream);
+
 // ---- carrier-overlap counts of caller-given sets (gcre_overlap.hip) ----
 constexpr int kOverlapTile = 64;    // pairs per edge of a block's tile
 constexpr int kOverlapChunk = 32;   // dwords of a row per staged chunk (128 bytes): rows are padded to a multiple of it

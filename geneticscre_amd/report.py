@@ -11,6 +11,7 @@
   * ``gene_tables`` / ``gene_best_reference`` / ``gene_results`` / ``gene_summary``  the per-gene best-path table: for
                          every gene the best path of each length through it, tallied on the device during the joins
                          (gcre_gene_tally; beyond the reference)
+  * ``minp_reference`` / ``minp_columns``  Westfall-Young min-P over a family of given sets in plain numpy, and its columns
   * ``exceed_reference`` / ``fdr_columns``  null exceedance counts of a join in plain numpy, and the per-family error rate,
                          permutation FDR and q-values they give (gcre_exceed; beyond the reference)
   * ``false_count_columns``  k-FWER, the median and the (1 - alpha) bound of the number of false positives, from the same
@@ -270,9 +271,11 @@ def parse_sets(paths, genes: Sequence[str]) -> Tuple[List[List[str]], List[List[
     return names, rows, signs
 
 
-def _score_sets(rows, signs, data, n_cases, n_ctrls, method, n_permutations, strata, seed, device, family_inference=False):
+def _score_sets(rows, signs, data, n_cases, n_ctrls, method, n_permutations, strata, seed, device, family_inference=False,
+                minp=False):
     """score_sets on the rows the sets use, on a context of its own: (records, family maxima); with ``family_inference``
-    family_tests instead: (records, family maxima, family records, kmax)."""
+    family_tests instead: (records, family maxima, family records, kmax); with ``minp`` the MINP_SCORE records of
+    minp_tests on the same context behind either."""
     from . import api
     used: Dict[int, int] = {}
     sets = [[-1 if r < 0 else used.setdefault(r, len(used)) for r in rs] for rs in rows]
@@ -283,10 +286,11 @@ def _score_sets(rows, signs, data, n_cases, n_ctrls, method, n_permutations, str
         ex.set_value_table(api.values_table(n_cases, n_ctrls))
         if n_permutations > 0:
             ex.generate_permutations(seed, strata)
+        more = (ex.minp_tests(sets, sub, signs)[1],) if minp else ()
         if family_inference:
             rec, fam, kmax = ex.family_tests(sets, sub, signs, kmax=True)
-            return rec, kmax[0], fam, kmax
-        return ex.score_sets(sets, sub, signs, family=True)
+            return (rec, kmax[0], fam, kmax) + more
+        return ex.score_sets(sets, sub, signs, family=True) + more
     finally:
         ex.close()
 
@@ -302,7 +306,8 @@ def _tail_pvalues(null: np.ndarray, scores: np.ndarray) -> np.ndarray:
 
 def score_paths(paths, genes: Sequence[str], data: np.ndarray, n_cases: int, n_ctrls: int, signed: bool = False,
                 threshold: float = 0.05, n_permutations: int = 100, strata: Optional[Sequence[int]] = None, seed: int = 0,
-                device: int = 0, gwaspa_out: Optional[Dict[str, object]] = None, family_inference: bool = False):
+                device: int = 0, gwaspa_out: Optional[Dict[str, object]] = None, minp: bool = False,
+                family_inference: bool = False):
     """Permutation tests of paths and gene sets the caller names (gcre_score_sets on the device): what GWASPA cannot
     answer for a cascade outside its top K, or for a KEGG / Reactome list.  ``paths`` as ``parse_sets`` reads them;
     genes are looked up after ``preprocess_table(threshold)``, as GWASPA and ``decorated_table`` do (a symbol not found is
@@ -317,13 +322,25 @@ def score_paths(paths, genes: Sequence[str], data: np.ndarray, n_cases: int, n_c
 
     ``family_inference``: the FAMILY_COLUMNS of ``family_columns`` behind these (gcre_score_sets_family):
     step-down adjusted p-values, expected false positives, FDR and q-values, and k-FWER p-values over the given paths as
-    one family."""
+    one family.
+
+    ``minp``: the MINP_COLUMNS of ``minp_columns`` behind all of these (gcre_score_sets_minp).
+    ``FamilyPvalues`` is max-T on RAW scores: a path's score against the per-permutation maximum of every given set's null
+    score, so in a family of paths of mixed length and gene sets the sets with the heaviest null tail own that maximum and
+    decide everybody's p-value.  ``FamilyPvaluesMinP`` puts the sets on one scale first: every null score is replaced by the
+    nominal p-value it would have got from its own set's null distribution, the per-permutation MINIMUM is taken over the
+    family, and the path's ``NominalPvalues`` is held against it (Westfall & Young's min-P, from one set of permutations as
+    Ge, Dudoit & Speed 2003 do it).  ``FamilyPvaluesMinPStepDown`` leaves out of that minimum the sets that are more
+    significant than the path, and is then made monotone.  With K permutations a set whose ``NominalPvalues`` is 0 (no null
+    score reaches it) gets 0 here too, as everywhere in this frame; and the smallest nominal p-value a permutation can
+    show is 1 / K, so min-P over V sets needs K well above V before it can tell anything from 1.  ``minp=False`` returns
+    exactly the frame without it."""
     import pandas as pd
     method = 2 if signed else 1
     genes, data = preprocess_table(genes, data, threshold, n_cases, n_ctrls)
     names, rows, signs = parse_sets(paths, genes)
     K = int(n_permutations)
-    rec, fam, *more = _score_sets(rows, signs, data, n_cases, n_ctrls, method, K, strata, seed, device, family_inference)
+    rec, fam, *more = _score_sets(rows, signs, data, n_cases, n_ctrls, method, K, strata, seed, device, family_inference, minp)
     valid = rec["valid"] != 0
     score = rec["score"]
     lengths = np.array([len(n) for n in names], dtype=np.int64)
@@ -348,10 +365,14 @@ def score_paths(paths, genes: Sequence[str], data: np.ndarray, n_cases: int, n_c
         "FamilyPvalues": family,
         "Pvalues": pv,
     }
-    if not family_inference:
-        return pd.DataFrame(cols, columns=SCORE_PATHS_COLUMNS)
-    cols.update(family_columns(score, valid, more[0], more[1], K))
-    return pd.DataFrame(cols, columns=SCORE_PATHS_COLUMNS + FAMILY_COLUMNS)
+    names_out = list(SCORE_PATHS_COLUMNS)
+    if family_inference:
+        cols.update(family_columns(score, valid, more[0], more[1], K))
+        names_out += FAMILY_COLUMNS
+    if minp:
+        cols.update(minp_columns(rec["n_ge"], valid, score, more[-1], K))
+        names_out += MINP_COLUMNS
+    return pd.DataFrame(cols, columns=names_out)
 
 
 FAMILY_KMAX = 10   # GCRE_FAMILY_KMAX: the largest null scores of a permutation gcre_score_sets_family keeps
@@ -419,6 +440,78 @@ def family_columns(scores, valid, family, kmax, perms: int) -> Dict[str, np.ndar
     km = np.asarray(kmax, np.float32).reshape(FAMILY_KMAX, -1)
     for k in FAMILY_KS:
         out[f"FamilykFWER.{k}"][ok] = _tail_pvalues(km[k - 1], s[ok])
+    return out
+
+
+MINP_COLUMNS = ["FamilyPvaluesMinP", "FamilyPvaluesMinPStepDown"]
+
+
+def minp_reference(obs, valid, null) -> Dict[str, np.ndarray]:
+    """The numpy statement of gcre_score_sets_minp, no device call: ``obs`` the observed scores, ``valid``
+    which sets have no NA member, ``null`` the float32 null matrix [n_sets][K] (rows of invalid sets are not read).  Over the
+    valid sets: ``n_ge[i]`` = c_i = #{r : (double)null[i][r] >= obs_i} (0 for a NaN score); ``counts[i][r]`` = R[i][r] =
+    #{r' : null[i][r'] >= null[i][r]}, compared as float32; ``min_count[r]`` = the minimum of R[.][r];  ``n_le_minp[j]`` =
+    #{r : min_count[r] <= c_j}; D_j = {i : c_i < c_j} (ties never exclude one another, a NaN score is in no D);
+    ``n_le_stepdown[j]`` = #{r : min over i not in D_j of R[i][r] <= c_j}.  A NaN score gets 0 / 0, an invalid set n_ge 0,
+    -1 / -1 and a row of 0xFFFFFFFF; ``min_count`` is 0xFFFFFFFF without a valid set.  Computed by one sort per row and one
+    running minimum down the sets in descending order of c."""
+    obs = np.asarray(obs, np.float64).ravel()
+    S = len(obs)
+    valid = np.asarray(valid).ravel() != 0
+    N = np.asarray(null, np.float32).reshape(S, -1)
+    K = N.shape[1]
+    c = np.zeros(S, np.int64)
+    mp = np.where(valid, 0, -1).astype(np.int64)
+    sd = mp.copy()
+    counts = np.full((S, K), 0xFFFFFFFF, np.uint32)
+    mc = np.full(K, 0xFFFFFFFF, np.uint32)
+    idx = np.flatnonzero(valid)
+    if len(idx) == 0 or K == 0:
+        return {"n_ge": c, "n_le_minp": mp, "n_le_stepdown": sd, "min_count": mc, "counts": counts}
+    Nv = N[idx]
+    srt = np.sort(Nv, axis=1)
+    for k, i in enumerate(idx):
+        counts[i] = K - np.searchsorted(srt[k], Nv[k], side="left")
+        if not np.isnan(obs[i]):
+            c[i] = K - np.searchsorted(srt[k].astype(np.float64), obs[i], side="left")
+    Rv = counts[idx]
+    mc = Rv.min(axis=0)
+    cv = c[idx]
+    isnan = np.isnan(obs[idx])
+    scored = np.flatnonzero(~isnan)
+    order = np.concatenate([np.flatnonzero(isnan), scored[np.argsort(-cv[scored], kind="stable")]])
+    run = np.minimum.accumulate(Rv[order], axis=0)        # run[i] = the minimum over the sets up to walk position i
+    n_nan = int(isnan.sum())
+    cs = cv[order[n_nan:]]                                # descending
+    last = n_nan + np.searchsorted(-cs, -cs, side="right") - 1   # the end of each tie group: nothing up to it is in D
+    dst = idx[order[n_nan:]]
+    sd[dst] = (run[last] <= cs[:, None].astype(np.uint32)).sum(axis=1)
+    mcs = np.sort(mc)
+    mp[dst] = np.searchsorted(mcs, cs.astype(np.uint32), side="right")
+    return {"n_ge": c, "n_le_minp": mp, "n_le_stepdown": sd, "min_count": mc, "counts": counts}
+
+
+def minp_columns(n_ge, valid, scores, minp, perms: int) -> Dict[str, np.ndarray]:
+    """MINP_COLUMNS of one family of given sets, from what ``JoinExec.minp_tests`` (or ``minp_reference``) returns: ``minp``
+    with n_le_minp / n_le_stepdown per set, ``n_ge`` the sets' own counts c.  ``FamilyPvaluesMinP`` = n_le_minp / perms,
+    the single-step min-P adjusted p-value; ``FamilyPvaluesMinPStepDown`` = n_le_stepdown / perms made monotone by a
+    running maximum from the smallest c upwards (a less significant set never gets a smaller adjusted p-value; sets that tie
+    in c are equal).  NaN for a set with an NA member or a NaN score, and everywhere when perms = 0."""
+    s = np.asarray(scores, np.float64).ravel()
+    ok = (np.asarray(valid).ravel() != 0) & ~np.isnan(s)
+    B = int(perms)
+    out = {col: np.full(len(s), np.nan) for col in MINP_COLUMNS}
+    if B <= 0 or not ok.any():
+        return out
+    c = np.asarray(n_ge, np.int64).ravel()[ok]
+    out["FamilyPvaluesMinP"][ok] = np.asarray(minp["n_le_minp"], np.int64).ravel()[ok] / B
+    sd = np.asarray(minp["n_le_stepdown"], np.int64).ravel()[ok]
+    order = np.argsort(c, kind="stable")
+    mono = np.maximum.accumulate(sd[order])
+    last = np.searchsorted(c[order], c[order], side="right") - 1     # tied sets take the value at the end of their group
+    adj = np.empty(len(c))
+    adj[order] = mono[last] / B
+    out["FamilyPvaluesMinPStepDown"][ok] = adj
     return out
 
 

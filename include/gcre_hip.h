@@ -490,6 +490,37 @@ int gcre_score_sets_family(gcre_ctx* ctx, const gcre_set_input* in, gcre_set_sco
 /* k_family_null / k_family_scan / k_family_hist launches on the context since gcre_create. */
 int64_t gcre_family_launches(const gcre_ctx* ctx);
 
+/* Westfall-Young min-P over the family of the given sets: every null score is replaced by the nominal
+ * permutation p-value its permutation's data would have got from that set's OWN null distribution, and the minimum is
+ * taken over the family -- sets whose raw null scores are not comparable (paths of mixed length, unions of many genes)
+ * then weigh alike, which max-T on raw scores (family_max, gcre_score_sets_family) does not give.  One set of permutations
+ * serves both roles (Ge, Dudoit & Speed 2003).  `out`, *n_out: exactly what gcre_score_sets gives.  With N[i][r] as above,
+ * over the valid sets, comparisons against obs as doubles and among the values of one row on the f32 values:
+ *   c_i              = out[i].n_ge = #{r : (double)N[i][r] >= obs_i}; 0 for a NaN score
+ *   R[i][r]          = #{r' < iterations : N[i][r'] >= N[i][r]}, 1 .. iterations: iterations x the nominal p-value of r
+ *   min_count[r]     = min over the valid sets i of R[i][r]
+ *   n_le_minp[j]     = #{r : min_count[r] <= c_j}                              (single-step min-P)
+ *   D_j              = {i : c_i < c_j}: tied sets never exclude one another, a set with a NaN score is in no D
+ *   n_le_stepdown[j] = #{r : min over i not in D_j of R[i][r] <= c_j}           (step-down, before the monotone step)
+ * So #{r : R[j][r] <= c_j} = c_j <= n_le_stepdown[j] <= n_le_minp[j], with equality of the two for the sets of the smallest
+ * c, and a family of one valid set gives c for both.  A set with a NaN observed score gets 0 / 0; an invalid set (an NA
+ * member) -1 / -1 and an all-0xFFFFFFFF row of null_counts.  iterations == 0: `out` as gcre_score_sets fills it, zeros for
+ * every valid set, nothing of this stage launched.  min_count is all 0xFFFFFFFF without a valid set.
+ * The valid sets are walked least significant first (NaN scores, then c descending) in slabs of whole rows: a row keeps
+ * its null scores and its counts, 8 bytes per permutation of every 512-permutation tile, and a slab stays under
+ * GCRE_MINP_MAX_MB (environment, read per call, default 1024; GCRE_MINP_SLAB_SETS bounds a slab further); no result depends
+ * on the slabs.  mp_out [n_sets]; min_count optional [iterations]; null_counts optional [n_sets][iterations] = R.
+ * Errors, nothing launched and no output array written (*n_out as gcre_score_sets leaves it): everything gcre_score_sets
+ * refuses; GCRE_ERR_ARG -- NULL mp_out, one row of the working set above GCRE_MINP_MAX_MB. */
+typedef struct { int64_t n_le_minp; int64_t n_le_stepdown; } gcre_minp_score;
+int gcre_score_sets_minp(gcre_ctx* ctx, const gcre_set_input* in, gcre_set_score* out, int64_t cap, int64_t* n_out,
+                         gcre_minp_score* mp_out /* [n_sets] */,
+                         uint32_t* min_count     /* optional [iterations] */,
+                         uint32_t* null_counts   /* optional [n_sets][iterations] = R */);
+/* k_minp_gather / k_family_null / k_minp_rank / k_minp_scan launches of gcre_score_sets_minp on the context since
+ * gcre_create (gcre_family_launches does not count them, nor the reverse). */
+int64_t gcre_minp_launches(const gcre_ctx* ctx);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Carrier overlaps of caller-given sets: which sets are carried by the same patients.  No reference
  * counterpart.

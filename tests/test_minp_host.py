@@ -1,0 +1,176 @@
+"""Westfall-Young min-P over a family of given sets (gcre_score_sets_minp), the parts that need no device:
+``report.minp_reference`` -- the contract every device test compares against -- on a hand-worked example and against the
+definitions taken literally, the consequences the definitions have, ``report.minp_columns``, and the interface (header,
+ctypes mirror, ``score_paths``)."""
+from __future__ import annotations
+
+import inspect
+import os
+import re
+
+import numpy as np
+import pytest
+
+from geneticscre_amd import api, report
+
+NAN = float("nan")
+ONES = 0xFFFFFFFF
+
+# four valid sets x six permutations and a set with an NA member.  Sets 0 and 1 tie in c; set 3 has a NaN score and a row
+# whose values are all equal; set 2 is the most significant one.
+EX_NULL = np.array([[1, 2, 3, 4, 5, 6],
+                    [3, 3, 1, 1, 2, 2],
+                    [0, 0, 7, 0, 0, 0],
+                    [2, 2, 2, 2, 2, 2],
+                    [NAN] * 6], np.float32)
+EX_OBS = np.array([5.0, 3.0, 7.0, NAN, NAN])
+EX_VALID = np.array([1, 1, 1, 1, 0])
+EX_COUNTS = np.array([[6, 5, 4, 3, 2, 1],
+                      [2, 2, 6, 6, 4, 4],
+                      [6, 6, 1, 6, 6, 6],
+                      [6, 6, 6, 6, 6, 6],
+                      [ONES] * 6], np.uint32)
+
+
+def test_the_worked_example():
+    ref = report.minp_reference(EX_OBS, EX_VALID, EX_NULL)
+    assert ref["n_ge"].tolist() == [2, 2, 1, 0, 0]
+    np.testing.assert_array_equal(ref["counts"], EX_COUNTS)
+    assert ref["counts"].dtype == np.uint32 and ref["min_count"].dtype == np.uint32
+    # per permutation the smallest count of the four valid rows
+    assert ref["min_count"].tolist() == [2, 2, 1, 3, 2, 1]
+    # c = 2: five minima are <= 2; c = 1: two are; the NaN score 0, the NA set -1
+    assert ref["n_le_minp"].tolist() == [5, 5, 2, 0, -1]
+    # sets 0 and 1 without set 2 (c = 1 < 2), with the NaN-score set: minima 2 2 4 3 2 1 -> four <= 2; set 2 against all
+    assert ref["n_le_stepdown"].tolist() == [4, 4, 2, 0, -1]
+
+
+def test_the_example_columns():
+    ref = report.minp_reference(EX_OBS, EX_VALID, EX_NULL)
+    cols = report.minp_columns(ref["n_ge"], EX_VALID, EX_OBS, ref, 6)
+    assert list(cols) == report.MINP_COLUMNS == ["FamilyPvaluesMinP", "FamilyPvaluesMinPStepDown"]
+    np.testing.assert_array_equal(cols["FamilyPvaluesMinP"], np.array([5 / 6, 5 / 6, 2 / 6, NAN, NAN]))
+    np.testing.assert_array_equal(cols["FamilyPvaluesMinPStepDown"], np.array([4 / 6, 4 / 6, 2 / 6, NAN, NAN]))
+    none = report.minp_columns(ref["n_ge"], EX_VALID, EX_OBS, ref, 0)
+    assert all(np.isnan(none[c]).all() for c in report.MINP_COLUMNS)
+    # the monotone step: a less significant set whose own count is smaller takes the larger one
+    mp = {"n_le_minp": np.array([9, 7, 8]), "n_le_stepdown": np.array([3, 6, 2])}
+    cols = report.minp_columns(np.array([4, 2, 1]), np.ones(3), np.array([1.0, 2.0, 3.0]), mp, 10)
+    assert cols["FamilyPvaluesMinPStepDown"].tolist() == [0.6, 0.6, 0.2]
+    assert cols["FamilyPvaluesMinP"].tolist() == [0.9, 0.7, 0.8]
+
+
+def literal(obs, valid, null):
+    """The definitions of DESIGN.md §3.16, one set and one permutation at a time."""
+    S, K = null.shape
+    vs = [i for i in range(S) if valid[i]]
+    c = [0] * S
+    R = [[ONES] * K for _ in range(S)]
+    for i in vs:
+        c[i] = sum(1 for r in range(K) if float(null[i][r]) >= obs[i])           # (False for a NaN score)
+        for r in range(K):
+            R[i][r] = sum(1 for q in range(K) if null[i][q] >= null[i][r])
+    mc = [min([R[i][r] for i in vs], default=ONES) for r in range(K)]
+    mp, sd = [-1] * S, [-1] * S
+    for j in vs:
+        if np.isnan(obs[j]):
+            mp[j] = sd[j] = 0
+            continue
+        mp[j] = sum(1 for r in range(K) if mc[r] <= c[j])
+        keep = [i for i in vs if np.isnan(obs[i]) or not c[i] < c[j]]
+        sd[j] = sum(1 for r in range(K) if min(R[i][r] for i in keep) <= c[j])
+    return c, mp, sd, mc, R
+
+
+def random_family(rng):
+    S = int(rng.integers(1, 9))
+    K = int(rng.integers(1, 13))
+    levels = np.array([0.0, 0.5, 1.0, 2.5, np.inf], np.float32)[:int(rng.integers(1, 6))]
+    null = rng.choice(levels, size=(S, K)).astype(np.float32)
+    obs = rng.choice(np.array([0.0, 0.25, 0.5, 1.0, 2.5, 3.0, np.inf, NAN]), size=S)
+    valid = (rng.random(S) < 0.85).astype(np.int32)
+    null[valid == 0] = NAN
+    return obs, valid, null
+
+
+def test_the_reference_is_the_definitions_taken_literally():
+    rng = np.random.default_rng(316)
+    ties_c = ties_row = 0
+    for _ in range(300):
+        obs, valid, null = random_family(rng)
+        ref = report.minp_reference(obs, valid, null)
+        c, mp, sd, mc, R = literal(obs, valid, null)
+        assert ref["n_ge"].tolist() == c
+        assert ref["n_le_minp"].tolist() == mp
+        assert ref["n_le_stepdown"].tolist() == sd
+        assert ref["min_count"].tolist() == mc
+        assert ref["counts"].tolist() == R
+        scored = [c[i] for i in range(len(c)) if valid[i] and not np.isnan(obs[i])]
+        ties_c += len(scored) != len(set(scored))
+        ties_row += any(len(set(null[i].tolist())) < null.shape[1] for i in range(len(c)) if valid[i])
+    assert ties_c > 100 and ties_row > 100      # ties in c and inside rows are common
+
+
+def test_the_consequences_of_the_definitions():
+    rng = np.random.default_rng(317)
+    for _ in range(300):
+        obs, valid, null = random_family(rng)
+        ref = report.minp_reference(obs, valid, null)
+        c, mp, sd, R = ref["n_ge"], ref["n_le_minp"], ref["n_le_stepdown"], ref["counts"]
+        scored = np.flatnonzero((valid != 0) & ~np.isnan(obs))
+        for j in scored:
+            assert int((R[j] <= c[j]).sum()) == c[j]          # a set alone: its own nominal count
+            assert c[j] <= sd[j] <= mp[j]
+        if len(scored):
+            low = scored[c[scored] == c[scored].min()]
+            assert (sd[low] == mp[low]).all()                 # nothing is left out for the smallest c
+        # a family of one valid set gives c for both
+        for j in scored:
+            one = np.zeros_like(valid)
+            one[j] = 1
+            alone = report.minp_reference(obs, one, null)
+            assert alone["n_le_minp"][j] == alone["n_le_stepdown"][j] == c[j]
+        # the step-down column is monotone in c, tied sets are equal, and it lies between the nominal and the single step
+        K = null.shape[1]
+        cols = report.minp_columns(c, valid, obs, ref, K)
+        a = cols["FamilyPvaluesMinPStepDown"]
+        for x in scored:
+            assert c[x] / K <= a[x] <= cols["FamilyPvaluesMinP"][x]
+            for y in scored:
+                if c[x] <= c[y]:
+                    assert a[x] <= a[y]
+        rest = np.setdiff1d(np.arange(len(obs)), scored)
+        assert np.isnan(a[rest]).all() and np.isnan(cols["FamilyPvaluesMinP"][rest]).all()
+
+
+def test_no_valid_set_and_no_permutation():
+    ref = report.minp_reference([1.0, 2.0], [0, 0], np.full((2, 3), NAN, np.float32))
+    assert ref["n_le_minp"].tolist() == ref["n_le_stepdown"].tolist() == [-1, -1]
+    assert ref["min_count"].tolist() == [ONES] * 3 and (ref["counts"] == ONES).all()
+    ref = report.minp_reference([1.0, NAN, 2.0], [1, 1, 0], np.zeros((3, 0), np.float32))
+    assert ref["n_le_minp"].tolist() == ref["n_le_stepdown"].tolist() == [0, 0, -1]
+    assert ref["min_count"].shape == (0,) and ref["counts"].shape == (3, 0) and ref["n_ge"].tolist() == [0, 0, 0]
+
+
+def test_the_interface():
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    with open(os.path.join(root, "include", "gcre_hip.h")) as f:
+        header = f.read()
+    assert re.search(r"#define\s+GCRE_ABI_VERSION\s+4\b", header)
+    assert api.EXPECTED_ABI == 4
+    m = re.search(r"typedef\s+struct\s*\{([^}]*)\}\s*gcre_minp_score\s*;", header)
+    assert m and re.findall(r"int64_t\s+(\w+)\s*;", m.group(1)) == ["n_le_minp", "n_le_stepdown"]
+    assert re.search(r"\bint\s+gcre_score_sets_minp\s*\(\s*gcre_ctx\s*\*", header)
+    assert re.search(r"\bint64_t\s+gcre_minp_launches\s*\(\s*const\s+gcre_ctx\s*\*", header)
+    assert api.MINP_SCORE.itemsize == 16 and list(api.MINP_SCORE.names) == ["n_le_minp", "n_le_stepdown"]
+    assert api.MINP_SCORE.fields["n_le_stepdown"][1] == 8
+    assert {"gcre_score_sets_minp", "gcre_minp_launches"} <= set(api.EXPORTS)
+    parent, needs, _, binds = api._FEATURES["minp"]
+    assert parent == "sets" and set(needs) == set(binds) == {"gcre_score_sets_minp", "gcre_minp_launches"}
+    assert len(binds["gcre_score_sets_minp"][1]) == 8
+    p = inspect.signature(report.score_paths).parameters["minp"]
+    assert p.default is False
+    sig = inspect.signature(api.JoinExec.minp_tests).parameters
+    assert [k for k in sig][1:] == ["sets", "rows", "signs", "min_count", "counts"]
+    assert sig["min_count"].default is False and sig["counts"].default is False
+    assert callable(api.JoinExec.minp_launches)
