@@ -140,6 +140,7 @@ EXPORTS = [
     "gcre_score_sets_given", "gcre_given_launches",
     "gcre_score_sets_family", "gcre_family_launches",
     "gcre_score_sets_minp", "gcre_minp_launches",
+    "gcre_score_sets_compete", "gcre_compete_launches",
     "gcre_set_overlap", "gcre_overlap_launches",
     "gcre_clump_sets", "gcre_clump_launches",
     "gcre_set_patient_counts", "gcre_patient_launches",
@@ -272,6 +273,10 @@ _FEATURES = {
     "minp": ("sets", ["gcre_score_sets_minp", "gcre_minp_launches"], "min-P set inference (gcre_score_sets_minp)", {
         "gcre_score_sets_minp": (_I, [_V, ctypes.POINTER(gcre_set_input), _P, _I64, ctypes.POINTER(_I64), _P, _P, _P]),
         "gcre_minp_launches": (_I64, [_V])}),
+    "compete": ("sets", ["gcre_score_sets_compete", "gcre_compete_launches"], "competitive set tests (gcre_score_sets_compete)", {
+        "gcre_score_sets_compete": (_I, [_V, ctypes.POINTER(gcre_set_input), _P, _I32, _I64, ctypes.c_uint64, _P, _I64,
+                                         ctypes.POINTER(_I64), _P, _P, _P]),
+        "gcre_compete_launches": (_I64, [_V])}),
     "overlap": (None, ["gcre_set_overlap"], "carrier overlaps (gcre_set_overlap)", {
         "gcre_set_overlap": (_I, [_V, ctypes.POINTER(gcre_set_input), _P, _I64, _P, _I64, _P, _P]),
         "gcre_overlap_launches": (_I64, [_V])}),
@@ -336,6 +341,7 @@ _sets_lib = functools.partial(_feature_lib, "sets")
 _given_lib = functools.partial(_feature_lib, "given")
 _family_lib = functools.partial(_feature_lib, "family")
 _minp_lib = functools.partial(_feature_lib, "minp")
+_compete_lib = functools.partial(_feature_lib, "compete")
 _overlap_lib = functools.partial(_feature_lib, "overlap")
 _clump_lib = functools.partial(_feature_lib, "clump")
 _patients_lib = functools.partial(_feature_lib, "patients")
@@ -1078,6 +1084,47 @@ class JoinExec:
     def minp_launches(self) -> int:
         """k_minp_gather / k_family_null / k_minp_rank / k_minp_scan launches of ``minp_tests`` on this context so far."""
         return int(_minp_lib().gcre_minp_launches(self._h))
+
+    def competitive_tests(self, sets, rows, signs=None, bins=None, draws: int = 1000, seed: int = 0, null: bool = False,
+                          picks: bool = False):
+        """Competitive tests of the given sets (gcre_score_sets_compete): every set against ``draws`` random
+        sets of the same size, drawn from ``rows`` -- here the whole gene POOL, not only the members -- and scored on the
+        observed labels.  ``bins``: per row of ``rows`` its bin 0 .. max, or -1 for a row that is never drawn (a member on
+        such a row is fixed: it stays itself in every draw); None = one bin.  A member is replaced by a row of its own bin.
+        No permutation mask is read: a context with ``iters`` = 0 will do.  Returns ``(records, n_ge)``: the SET_SCORE
+        records of ``score_sets``, and int64 per set the draws whose score reaches the set's (-1 for an NA member).  With
+        ``null`` also float64 [sets][draws], the score of every draw (NaN rows for sets with an NA member); with ``picks``
+        also int32 [draws][members of all sets], the row every member received.  ``report.competitive_columns`` turns n_ge
+        into p-values, ``report.competitive_reference`` restates the call in numpy.  Errors raise GcreError."""
+        lib = _compete_lib()
+        n = self.num_cases + self.num_ctrls
+        S = len(sets)
+        B = int(draws)
+        inp, keep = _set_input(sets, rows, signs, n)
+        nb = 1
+        bn = None
+        if bins is not None:
+            bn = np.ascontiguousarray(np.asarray(bins, dtype=np.int64).reshape(-1), dtype=np.int32)
+            if len(bn) != keep[3].shape[0]:
+                raise ValueError(f"bins: {len(bn)} entries for {keep[3].shape[0]} rows")
+            nb = max(int(bn.max()) + 1, 1) if len(bn) else 1
+        out = np.zeros(max(S, 1), dtype=SET_SCORE)
+        ge = np.zeros(max(S, 1), dtype=np.int64)
+        nul = np.full((S, max(B, 0)), np.nan, dtype=np.float64) if null else None
+        pk = np.full((max(B, 0), len(keep[1])), -1, dtype=np.int32) if picks else None
+        n_out = ctypes.c_int64(0)
+        rc = lib.gcre_score_sets_compete(self._h, ctypes.byref(inp), _ptr(bn), nb, B, int(seed) & (2**64 - 1), _ptr(out), len(out),
+                                         ctypes.byref(n_out), _ptr(ge), _ptr(nul) if null and nul.size else None,
+                                         _ptr(pk) if picks and pk.size else None)
+        del keep
+        if rc != GCRE_OK:
+            raise GcreError(self._lib.gcre_last_error(self._h).decode())
+        res = (out[:n_out.value], ge[:n_out.value])
+        return res + ((nul,) if null else ()) + ((pk,) if picks else ())
+
+    def compete_launches(self) -> int:
+        """k_compete_null launches of ``competitive_tests`` on this context so far."""
+        return int(_compete_lib().gcre_compete_launches(self._h))
 
     def set_overlap(self, sets, rows, a=None, b=None):
         """Carrier overlaps of caller-given sets (gcre_set_overlap).  A set's carrier row is the OR of all

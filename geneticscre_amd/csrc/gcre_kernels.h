@@ -620,6 +620,38 @@ struct MinpScanArgs {
 };
 hipError_t launch_minp_scan(const MinpScanArgs& a, hipStream_t stream);
 
+// ---- competitive set tests: matched random sets on the observed labels (gcre_compete.hip) ----
+// One wave of k_compete_null takes a valid set and a run of `dpw` draws of the slab [b0, b0 + nb): per draw it makes the
+// picks by the rule of gcre_compete.h, ORs the picked gene rows over the patients and looks the score up in the f64 table.
+struct CompeteSet {
+  int64_t set;                      // index in the caller's list: the key of its random stream
+  int32_t moff, k;                  // its members are entries [moff, moff + k) of `mem` / `signs`
+};
+struct CompeteMemberDev { int32_t off, n; };   // gcre_compete::CompeteMember: off < 0 fixed on row n, else pool rows [off, off + n)
+struct CompeteArgs {
+  const uint32_t* rows;             // [n_rows][Wd] the caller's gene rows as dwords, Wd a multiple of 4 (16-byte lanes)
+  const int32_t* pool_rows;         // the pool table: rows by bin, ascending (read-only: scalar loads)
+  const CompeteMemberDev* mem;      // [members of the list]
+  const int32_t* signs;             // [members of the list] +1 / -1, or nullptr (method 2 reads them)
+  const CompeteSet* sets;           // [V] the valid sets (read-only: scalar loads)
+  const double* dvt;                // the observed-score table, diagonal-major
+  const double* obs;                // [V] observed scores as k_set_observed left them
+  unsigned long long* n_ge;         // [V] adds: draws whose null score >= obs
+  double* null_out;                 // optional [V][stride]: column b - b0
+  int32_t* picks_out;               // optional [nb][tm]: the row every member received (members of invalid sets are not written)
+  uint64_t seed;
+  int64_t b0;                       // first draw of the slab
+  int64_t stride;                   // columns of null_out
+  int64_t tm;                       // members of the whole list
+  int32_t V, nb;                    // valid sets, draws of the slab
+  int32_t dpw, groups;              // draws per wave, waves per set = ceil(nb / dpw)
+  int32_t Wd;                       // dwords per gene row
+  int32_t n, n_cases;               // patients; columns below n_cases are the cases
+  int32_t attempts;                 // 1 .. 64
+  int32_t maxk;                     // the most members of a valid set
+};
+hipError_t launch_compete_null(const CompeteArgs& a, int method, hipStream_t stream);
+
 // ---- carrier-overlap counts of caller-given sets (gcre_overlap.hip) ----
 constexpr int kOverlapTile = 64;    // pairs per edge of a block's tile
 constexpr int kOverlapChunk = 32;   // dwords of a row per staged chunk (128 bytes): rows are padded to a multiple of it

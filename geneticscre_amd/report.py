@@ -307,6 +307,7 @@ def _tail_pvalues(null: np.ndarray, scores: np.ndarray) -> np.ndarray:
 def score_paths(paths, genes: Sequence[str], data: np.ndarray, n_cases: int, n_ctrls: int, signed: bool = False,
                 threshold: float = 0.05, n_permutations: int = 100, strata: Optional[Sequence[int]] = None, seed: int = 0,
                 device: int = 0, gwaspa_out: Optional[Dict[str, object]] = None, minp: bool = False,
+                competitive: int = 0, competitive_bins: int = 10, fixed: Optional[Sequence[str]] = None,
                 family_inference: bool = False):
     """Permutation tests of paths and gene sets the caller names (gcre_score_sets on the device): what GWASPA cannot
     answer for a cascade outside its top K, or for a KEGG / Reactome list.  ``paths`` as ``parse_sets`` reads them;
@@ -334,7 +335,19 @@ def score_paths(paths, genes: Sequence[str], data: np.ndarray, n_cases: int, n_c
     significant than the path, and is then made monotone.  With K permutations a set whose ``NominalPvalues`` is 0 (no null
     score reaches it) gets 0 here too, as everywhere in this frame; and the smallest nominal p-value a permutation can
     show is 1 / K, so min-P over V sets needs K well above V before it can tell anything from 1.  ``minp=False`` returns
-    exactly the frame without it."""
+    exactly the frame without it.
+
+    ``competitive`` > 0: the COMPETITIVE_COLUMNS behind all of these (gcre_score_sets_compete).  Every
+    p-value above is self-contained: it permutes the labels and asks whether the set is associated with the phenotype at
+    all, which one strong gene answers for every set that contains it.  ``CompetitivePvalues`` asks the competitive
+    question instead: the share of ``competitive`` random gene sets of the same size, every gene replaced by one of the same
+    ``carrier_bins(data, competitive_bins)`` bin of carrier frequency out of the whole preprocessed table, that score at
+    least as high on the OBSERVED labels (drawn from ``seed``; n / K, so 0 when no draw reaches the set).  It is a rank among
+    matched random sets conditional on the labels, one set at a time: not a family-wise statement, and nothing here corrects
+    it over the paths.  ``fixed``: gene symbols that stay themselves in every draw of the sets that contain them -- "is this
+    set anything beyond its known driver?"; the other sets are drawn from the full pool, so naming a gene changes only the
+    sets it is in.  A bin must hold twice as many genes as a set draws from it: lower ``competitive_bins`` for large sets on
+    a small table.  ``competitive=0`` returns exactly the frame without it."""
     import pandas as pd
     method = 2 if signed else 1
     genes, data = preprocess_table(genes, data, threshold, n_cases, n_ctrls)
@@ -372,7 +385,33 @@ def score_paths(paths, genes: Sequence[str], data: np.ndarray, n_cases: int, n_c
     if minp:
         cols.update(minp_columns(rec["n_ge"], valid, score, more[-1], K))
         names_out += MINP_COLUMNS
+    if int(competitive) > 0:
+        n_ge = _competitive_counts(rows, signs, genes, data, n_cases, n_ctrls, method, int(competitive), competitive_bins, fixed,
+                                   seed, device)
+        cols.update(competitive_columns(n_ge, valid & ~np.isnan(score), int(competitive)))
+        names_out += COMPETITIVE_COLUMNS
     return pd.DataFrame(cols, columns=names_out)
+
+
+def _competitive_counts(rows, signs, genes, data, n_cases, n_ctrls, method, draws, n_bins, fixed, seed, device) -> np.ndarray:
+    """n_ge of competitive_tests for ``score_paths``: the whole table is the pool, the bins are ``carrier_bins``'; the sets
+    that contain a ``fixed`` gene come from a second call in which those genes have bin -1."""
+    from . import api
+    data = np.asarray(data)
+    bins = carrier_bins(data, n_bins)
+    ex = api.JoinExec(method, n_cases, n_ctrls, 0, device=device)
+    try:
+        ex.set_value_table(api.values_table(n_cases, n_ctrls))
+        n_ge = ex.competitive_tests(rows, data, signs, bins=bins, draws=draws, seed=seed)[1].copy()
+        held = {i for i, g in enumerate(genes) if g in set(fixed)} if fixed else set()
+        touched = np.array([any(r in held for r in rs) for rs in rows], bool)
+        if touched.any():
+            fb = bins.copy()
+            fb[sorted(held)] = -1
+            n_ge[touched] = ex.competitive_tests(rows, data, signs, bins=fb, draws=draws, seed=seed)[1][touched]
+        return n_ge
+    finally:
+        ex.close()
 
 
 FAMILY_KMAX = 10   # GCRE_FAMILY_KMAX: the largest null scores of a permutation gcre_score_sets_family keeps
@@ -513,6 +552,169 @@ def minp_columns(n_ge, valid, scores, minp, perms: int) -> Dict[str, np.ndarray]
     adj[order] = mono[last] / B
     out["FamilyPvaluesMinPStepDown"][ok] = adj
     return out
+
+
+# competitive set tests: matched random sets on the observed labels
+
+COMPETITIVE_COLUMNS = ["CompetitivePvalues"]
+COMPETE_ATTEMPTS = 64      # attempts of a member before the fallback, and the stride of the member index in the random stream
+_U64 = np.uint64
+
+
+def _mix64(z):
+    """gcre_mix64 (the splitmix64 finaliser) on numpy uint64, wrapping."""
+    with np.errstate(over="ignore"):
+        z = np.asarray(z, dtype=_U64) + _U64(0x9E3779B97F4A7C15)
+        z = (z ^ (z >> _U64(30))) * _U64(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> _U64(27))) * _U64(0x94D049BB133111EB)
+        return z ^ (z >> _U64(31))
+
+
+def _compete_base(seed: int, s: int, b) -> np.ndarray:
+    """dp_perm_base(dp_split_key(seed, s), b) for every draw of ``b``."""
+    with np.errstate(over="ignore"):
+        key = _mix64(_U64(int(seed) & (2**64 - 1)) ^ (_U64(0xD1B54A32D192ED03) * _U64(int(s) + 1)))
+        return _mix64(key ^ (_U64(0x51ED270B7F3C9A1D) * (np.asarray(b, dtype=_U64) + _U64(1))))
+
+
+def _mulhi(u, n: int) -> np.ndarray:
+    """floor(u * n / 2^64) for uint64 u and 0 < n < 2^32, by 32-bit halves: neither partial product leaves 64 bits."""
+    u = np.asarray(u, dtype=_U64)
+    n = _U64(n)
+    hi, lo = u >> _U64(32), u & _U64(0xFFFFFFFF)
+    return ((hi * n + ((lo * n) >> _U64(32))) >> _U64(32)).astype(np.int64)
+
+
+def _compete_pools(bins, n_rows: int):
+    """(bin of every row, {bin: its rows ascending}); ``bins`` None = one bin with every row."""
+    bn = np.zeros(int(n_rows), np.int64) if bins is None else np.asarray(bins, dtype=np.int64).reshape(-1)
+    if len(bn) != n_rows:
+        raise ValueError(f"bins: {len(bn)} entries for {n_rows} rows")
+    return bn, {int(v): np.flatnonzero(bn == v) for v in np.unique(bn[bn >= 0])}
+
+
+def _compete_draws(members, bn, pools, s: int, b, seed: int, attempts: int) -> np.ndarray:
+    """The draw rule for the draws ``b`` of set ``s`` at once: int64 [len(b)][members]."""
+    members = np.asarray(members, dtype=np.int64).reshape(-1)
+    b = np.asarray(b, dtype=np.int64).reshape(-1)
+    if not 1 <= int(attempts) <= COMPETE_ATTEMPTS:
+        raise ValueError(f"attempts must be 1..{COMPETE_ATTEMPTS}")
+    base = _compete_base(seed, s, b)
+    picks = np.full((len(b), len(members)), -1, np.int64)
+    need: Dict[int, int] = {}
+    for j, row in enumerate(members.tolist()):
+        beta = int(bn[row]) if row >= 0 else -1
+        if beta < 0:                     # a fixed member stays itself
+            picks[:, j] = row
+            continue
+        pool = pools[beta]
+        need[beta] = need.get(beta, 0) + 1
+        if 2 * need[beta] > len(pool):
+            raise ValueError(f"set {s} draws {need[beta]} members from bin {beta} of {len(pool)} rows: 2k <= N is required")
+        pending = np.arange(len(b))
+        with np.errstate(over="ignore"):
+            at = base + _U64(COMPETE_ATTEMPTS * j)
+        for t in range(int(attempts)):
+            if len(pending) == 0:
+                break
+            with np.errstate(over="ignore"):
+                u = _mix64(at[pending] + _U64(t))
+            cand = pool[_mulhi(u, len(pool))]
+            taken = (picks[pending, :j] == cand[:, None]).any(axis=1)
+            picks[pending[~taken], j] = cand[~taken]
+            pending = pending[taken]
+        for i in pending.tolist():        # the fallback: the lowest pool entry not yet handed out
+            picks[i, j] = pool[~np.isin(pool, picks[i, :j])][0]
+    return picks
+
+
+def competitive_picks(set_members, bins, n_rows: int, s: int, b: int, seed: int, attempts: int = COMPETE_ATTEMPTS) -> np.ndarray:
+    """The draw rule of gcre_score_sets_compete (csrc/gcre_compete.h is the same rule in C++): the row every
+    member of set ``s`` (``set_members``: rows of the pool, in list order) receives in draw ``b``.  ``bins`` [n_rows]: the bin
+    of every row, -1 = never drawn (a member there is fixed); None = one bin.  The pool of a bin is its rows, ascending.
+    Member j, in order, reads u = mix64(base + 64 j + t) for attempt t = 0, 1, ..., base = mix64(key ^ C2 (b + 1)), key =
+    mix64(seed ^ C1 (s + 1)) (dp_perm_base / dp_split_key), proposes pool entry floor(u N / 2^64) and takes the first proposal
+    no earlier member of the draw received; after ``attempts`` failures the lowest pool entry not handed out.  A pure
+    function of (seed, s, b).  int64 [members]."""
+    bn, pools = _compete_pools(bins, n_rows)
+    return _compete_draws(set_members, bn, pools, s, [b], seed, attempts)[0]
+
+
+def competitive_reference(sets, rows, signs, bins, draws: int, seed: int, n_cases: int, table, method: int,
+                          attempts: int = COMPETE_ATTEMPTS) -> Dict[str, np.ndarray]:
+    """The numpy statement of gcre_score_sets_compete, no device call.  ``rows``: the 0/1 carrier matrix
+    [pool rows][patients], columns < n_cases the cases; ``sets`` / ``signs`` as ``JoinExec.score_sets`` takes them; ``table``
+    the value table.  Per valid set and draw the picks of ``competitive_picks``, the unions of the drawn rows (method 1 the OR
+    of all, method 2 P / N by sign), and table[|P & cases|][|P & ctrls|] (+ table[|N & ctrls|][|N & cases|], added in this
+    order).  Returns ``n_ge`` int64 [sets] = #{b : null >= observed} as doubles (-1 for a set with an NA member), ``null``
+    float64 [sets][draws] (NaN rows for those), ``picks`` int32 [draws][members of all sets] (-1 for those) and ``obs``."""
+    d = np.asarray(rows) != 0
+    n = d.shape[1]
+    B = int(draws)
+    VT = np.asarray(table, np.float64)
+    case = np.arange(n) < n_cases
+    bn, pools = _compete_pools(bins, len(d))
+    S = len(sets)
+    lens = [len(x) for x in sets]
+    off = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    n_ge = np.zeros(S, np.int64)
+    obs = np.full(S, np.nan)
+    null = np.full((S, B), np.nan)
+    picks = np.full((B, int(off[-1])), -1, np.int32)
+
+    def scores(r, sg):                       # r [draws][members] rows, sg [members]
+        neg = (sg == -1) if method == 2 else np.zeros(len(sg), bool)
+        P = np.zeros((len(r), n), bool)
+        N = np.zeros((len(r), n), bool)
+        for j in range(r.shape[1]):
+            (N if neg[j] else P)[:] |= d[r[:, j]]
+        v = _vt_cell(VT, n, (P & case).sum(axis=1), (P & ~case).sum(axis=1))
+        if method == 2:
+            with np.errstate(invalid="ignore"):                       # inf - inf
+                v = v + _vt_cell(VT, n, (N & ~case).sum(axis=1), (N & case).sum(axis=1))
+        return v
+
+    for s in range(S):
+        m = np.asarray(sets[s], dtype=np.int64).reshape(-1)
+        if (m < 0).any():
+            n_ge[s] = -1
+            continue
+        sg = np.ones(len(m), np.int64) if signs is None else np.asarray(signs[s], dtype=np.int64).reshape(-1)
+        obs[s] = scores(m[None, :], sg)[0]
+        if B == 0:
+            continue
+        pk = _compete_draws(m, bn, pools, s, np.arange(B), seed, attempts)
+        picks[:, off[s]:off[s + 1]] = pk
+        null[s] = scores(pk, sg)
+        n_ge[s] = int((null[s] >= obs[s]).sum())
+    return {"n_ge": n_ge, "null": null, "picks": picks, "obs": obs}
+
+
+def carrier_bins(data, n_bins: int) -> np.ndarray:
+    """Bins of equal count by carrier total for ``competitive_tests``: the rows of the 0/1 matrix ``data`` ordered by their
+    carrier totals (stable: ties by row) and cut into ``n_bins`` runs whose sizes differ by at most one, the fewest
+    carriers in bin 0.  int32 [rows]; fewer rows than bins leave the upper bins empty."""
+    tot = (np.asarray(data) != 0).sum(axis=1)
+    R = len(tot)
+    nb = max(int(n_bins), 1)
+    order = np.argsort(tot, kind="stable")
+    out = np.zeros(R, np.int32)
+    out[order] = (np.arange(R, dtype=np.int64) * nb // max(R, 1)).astype(np.int32)
+    return out
+
+
+def competitive_columns(n_ge, valid, draws: int) -> Dict[str, np.ndarray]:
+    """COMPETITIVE_COLUMNS from what ``JoinExec.competitive_tests`` (or ``competitive_reference``) returns:
+    ``CompetitivePvalues`` = n_ge / draws, the share of matched random sets that score at least as high on the observed
+    labels -- the project's n / K convention, not (n + 1) / (K + 1).  NaN for a set with an NA member (``valid`` 0 or n_ge
+    < 0), for a NaN score (``valid`` may carry ``~isnan(score)``) and with 0 draws."""
+    c = np.asarray(n_ge, np.int64).ravel()
+    ok = (np.asarray(valid).ravel() != 0) & (c >= 0)
+    B = int(draws)
+    out = np.full(len(c), np.nan)
+    if B > 0:
+        out[ok] = c[ok] / B
+    return {"CompetitivePvalues": out}
 
 
 def check_best_paths(results_df, genes: Sequence[str], data: np.ndarray, n_cases: int, n_ctrls: int, signed: bool,

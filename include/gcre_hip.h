@@ -521,6 +521,45 @@ int gcre_score_sets_minp(gcre_ctx* ctx, const gcre_set_input* in, gcre_set_score
  * gcre_create (gcre_family_launches does not count them, nor the reverse). */
 int64_t gcre_minp_launches(const gcre_ctx* ctx);
 
+/* Competitive tests of the given sets (Goeman & Buhlmann 2007): does a set score higher, on the OBSERVED
+ * labels, than random gene sets of the same size and the same carrier frequencies?  The null is over genes, not labels: no
+ * permutation mask is read, and a context with iterations == 0 and no masks is the usual one.  `out`, *n_out: exactly what
+ * gcre_score_sets gives, so one call yields both p-values.
+ * in->rows are the whole gene POOL, not only the members.  bin [n_rows]: 0 .. n_bins-1, or -1; NULL = one bin holding every
+ * row.  The pool of bin B is the rows with bin[row] == B in ascending row order, N_B of them.  A row with bin -1 is never
+ * drawn, and a member on such a row is FIXED: it stays itself in every draw.
+ * Draw b (0 .. draws-1) of set s replaces every member that is not fixed, in member order j = 0, 1, ... (the position in the
+ * set's list), by a row of its own bin that no earlier member of this draw has received; the member keeps its sign.  With
+ *   base = dp_perm_base(dp_split_key(seed, s), b)      (the keys of gcre_decorated_pvalues; gcre_mix64 below)
+ * attempt t = 0, 1, ... of member j reads u = gcre_mix64(base + 64 j + t) and proposes pool entry floor(u N_B / 2^64) (the
+ * 128-bit product); the first proposal not yet handed out in this draw is taken.  After A failed attempts the member gets
+ * the lowest pool entry of its bin not yet handed out; A = 64 (GCRE_COMPETE_ATTEMPTS, environment, read per call, lowers it
+ * to 1 .. 64: tests).  A set with k members to draw from a bin needs 2 k <= N_B, so every attempt succeeds with probability
+ * 1/2 or more.  A draw may hand out rows that are members of the set; draws of different sets and different b are
+ * independent and a pure function of (seed, s, b).
+ * Null score of a draw: the unions of the drawn rows as gcre_score_sets defines them for the context's method (method 1 the
+ * OR of all rows, method 2 P / N by sign), counted against the observed labels (columns < n_cases are the cases), and the
+ * f64 value of the context's table for those counts: the expression of the observed score, and for method 2 its order of the
+ * addition -- a draw that hands every member its own row reproduces the observed score bit for bit.
+ *   n_ge[s] = #{b < draws : null[s][b] >= obs_s} as doubles (a NaN on either side never counts); -1 for an invalid set (an
+ *   NA member); zeros with draws == 0, which launches nothing of this stage.
+ * null_scores, optional [n_sets][draws] (NaN rows for invalid sets); picks, optional [draws][total members]: the row each
+ * member received, in the order of in->members (fixed members their own row, -1 for the members of invalid sets).  The
+ * draws are walked in slabs whose optional outputs stay under GCRE_COMPETE_MAX_MB on the device (environment, read per
+ * call, default 1024; GCRE_COMPETE_SLAB_DRAWS bounds a slab further); no result depends on the slabs.
+ * Errors, nothing launched and no output array written (*n_out as gcre_score_sets leaves it): everything gcre_score_sets
+ * refuses; GCRE_ERR_ARG -- NULL n_ge, draws < 0, n_bins < 1, a bin value outside -1 .. n_bins-1, a set that breaks
+ * 2 k <= N_B, a set of more than GCRE_COMPETE_MAX_MEMBERS members, the optional outputs of one draw above
+ * GCRE_COMPETE_MAX_MB.
+ * The number is a rank among matched random sets conditional on the labels; it is not a family-wise statement. */
+#define GCRE_COMPETE_MAX_MEMBERS 1024
+int gcre_score_sets_compete(gcre_ctx* ctx, const gcre_set_input* in, const int32_t* bin, int32_t n_bins, int64_t draws,
+                            uint64_t seed, gcre_set_score* out, int64_t cap, int64_t* n_out, int64_t* n_ge,
+                            double* null_scores, int32_t* picks);
+/* k_compete_null launches of gcre_score_sets_compete on the context since gcre_create (no other launch counter counts
+ * them, nor the reverse). */
+int64_t gcre_compete_launches(const gcre_ctx* ctx);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Carrier overlaps of caller-given sets: which sets are carried by the same patients.  No reference
  * counterpart.
