@@ -73,6 +73,7 @@ struct DevBuf {   // grow-only device scratch
 struct Winners {
   std::vector<uint32_t> sel, cases, ctrls, r0, r1;
   std::vector<uint64_t> key;
+  std::vector<uint64_t> pack;   // where the device's copy lands: n keys, then cases, ctrls, r0, r1 as 32-bit words (unpack_winners)
   uint32_t n = 0;
 };
 
@@ -225,6 +226,13 @@ struct gcre_ctx {
   hipStream_t sel_stream = nullptr;
   hipEvent_t ev_sel = nullptr, ev_sel_done = nullptr;
   bool sel_async = true;
+  // The recipe gather of a pruned method-1 launch (k_fill_rec_segs) is read by the pruned kernels only, not by the warm-up
+  // slice in front of them: it runs beside the slice on a stream of its own (GCRE_REC_STREAM=0: on the join's stream, in
+  // front of the slice).  ev_rec_in: on the join's stream where the gather is queued -- behind the recipe copies, the
+  // segment-table upload and every earlier pruned launch, all of which are on that stream; ev_rec_done: behind the gather
+  hipStream_t rec_stream = nullptr;
+  hipEvent_t ev_rec_in = nullptr, ev_rec_done = nullptr;
+  bool rec_async = true;
   // Inspect-ahead (gcre_join_ahead, round 4).  The inspector of the NEXT join of a sequence only needs what the current
   // join's inspector wrote (kept rows, recipe) -- not its permutation kernel -- so it runs on a stream of its own while
   // that kernel is in flight, into the next join's inspection cache; the next join then starts at its null kernel.
@@ -274,6 +282,7 @@ struct gcre_ctx {
   int ie_zwide = 0;                  // GCRE_IE_ZWIDE=1: the quad kernel reaches every added row through a descriptor of its own (tests)
   int ie_warm_items = 4;             // (segment, tile) items per wave of the warm-up launch (GCRE_IE_WARM_ITEMS)
   int ie_warm_div = 4096;            // the slice grows with the join as scored segments / this (GCRE_IE_WARM_DIV; warm_segments)
+  int ie_warm_cap_div = 8;           // ... and is at most scored segments / this, at least 256 (GCRE_IE_WARM_CAP_DIV; warm_segments)
   int exchange_tail = 0;             // slices of the pruned launch that are equal steps at its end (GCRE_EXCHANGE_TAIL; -1: half of them; 0: doubling slices only)
   int ie_warm_segs = 1024;           // least number of segments in the warm-up slice (GCRE_IE_WARM; 2048 until round 3: the filter's second look made early thresholds matter less)
   int ie_small_join_tiles = 8;       // GCRE_IE_SJT (tuning)
@@ -304,7 +313,6 @@ struct gcre_ctx {
   ChunkBufs scratch;                 // a chunk's buffers when the inspection cache is off
   DevBuf<uint32_t> d_sel, d_small, d_chunk, d_rec_segs;
   DevBuf<uint64_t> d_wkey, d_doff, d_scan, d_excess, d_excess_b;
-  DevBuf<uint32_t> d_wcases, d_wctrls, d_wrow0, d_wrow1;
   DevBuf<uint64_t> d_ie_timing;      // GCRE_IE_TIMING: the section counters of a diagnostics build's pruned kernels
 
   // count-plane buffers of freed path sets, kept for the next set that needs one (hipMalloc of tens of GB costs

@@ -555,11 +555,14 @@ void build_quads_host(const gcre_uids& u, const std::vector<SparseSeg>& segs, in
 // (GCRE_IE_WARM_DIV).  The divisor is 4096: at 1024 the benchmark's last level (2.3 million scored segments) had a slice
 // of 2,270 segments, and the sweep (profiles/warmup_sweep.txt) took 0.27 ms less per pass with 1,024 although 1.5 % more
 // path-tiles were then looked up; at 512 and 256 the look-ups cost more than the shorter slice saves.
+// A small join gets less: at most nseg / ie_warm_cap_div (GCRE_IE_WARM_CAP_DIV), never below 256.  The divisor is 8:
+// a shorter slice is not a faster one (the launch keeps about four items per wave, so it only has fewer waves), and at
+// 32 and above the thinner thresholds cost the pruned launches more than the slices save (profiles/warm_size_sweep.txt).
 int64_t warm_segments(const gcre_ctx* c, int64_t nseg_scored, int nkt) {
   if (c->ie_warm_segs == 0) return 0;   // GCRE_IE_WARM=0 (tests): everything through the pruned kernel, thresholds from 0
   const int64_t warm_min = std::max<int64_t>(256, (int64_t)c->ie_warm_segs * 8 / std::max(nkt, 8));
   return std::min<int64_t>(nseg_scored, std::min<int64_t>(std::max<int64_t>(warm_min, nseg_scored / c->ie_warm_div),
-                                                          std::max<int64_t>(256, nseg_scored / 8)));
+                                                          std::max<int64_t>(256, nseg_scored / c->ie_warm_cap_div)));
 }
 
 int sparse_segments(gcre_ctx* c, const gcre_uids& u, int64_t first, int64_t count, int64_t score_b, int64_t score_e,
@@ -755,6 +758,7 @@ void gcre_host::free_uids(gcre_uids* u) {
   if (u->launch.done) (void)hipEventDestroy(u->launch.done);
   if (u->ctx && u->ctx->stream) (void)hipStreamSynchronize(u->ctx->stream);
   if (u->ctx && u->ctx->insp_stream) (void)hipStreamSynchronize(u->ctx->insp_stream);
+  if (u->ctx && u->ctx->rec_stream) (void)hipStreamSynchronize(u->ctx->rec_stream);   // (the gather reads the segment tables)
   if (u->ctx) {
     auto& v = u->ctx->live_uids;
     v.erase(std::remove(v.begin(), v.end(), u), v.end());
@@ -1191,6 +1195,7 @@ struct JoinRun {
   size_t cap = 0;                      // elements of a chunk's buffers
   // prepare_operands; a chunk that finds the hint broken changes hinted, red, have_pz, want_ie and the res_planes pair
   bool sparse_ok = false, want_ie = false, hinted = false;
+  bool range_union_due = false;        // hinted: the range check of the hint has not been queued yet (range_union_now)
   const gcre_pathset* red = nullptr;   // the rows the join adds: the reduced operand, or paths1
   bool have_p0 = false, have_pz = false, use_rec = false;
   const gcre_pathset *rec_a = nullptr, *rec_z = nullptr;   // use_rec: the operands of paths0's recipe
@@ -1358,21 +1363,30 @@ int prepare_z(JoinRun& R) {
 int queue_winners(gcre_ctx* c, const ChunkBufs& b, int64_t s0, uint32_t nsel, Winners& w, hipStream_t qs) {
   w.n = nsel;
   if (nsel == 0) return GCRE_OK;
-  HIP_TRY(c, c->d_wkey.reserve(nsel));
-  HIP_TRY(c, c->d_wcases.reserve(nsel));
-  HIP_TRY(c, c->d_wctrls.reserve(nsel));
-  HIP_TRY(c, c->d_wrow0.reserve(nsel));
-  HIP_TRY(c, c->d_wrow1.reserve(nsel));
+  // keys, then cases, ctrls and the two rows, in one buffer: one copy out instead of five (a copy into pageable memory
+  // holds the host for 20-30 us, and this host is what the chain's next launch waits for); unpack_winners splits it
+  HIP_TRY(c, c->d_wkey.reserve((size_t)nsel * 3));
+  uint32_t* d32 = (uint32_t*)(c->d_wkey.p + nsel);
   HIP_TRY(c, launch_gather_winners(c->d_sel.p, nsel, b.key.p + s0, b.cases.p + s0, b.ctrls.p + s0, b.row0.p + s0,
-                                   b.row1.p + s0, c->d_wkey.p, c->d_wcases.p, c->d_wctrls.p, c->d_wrow0.p, c->d_wrow1.p, qs));
-  w.sel.resize(nsel); w.cases.resize(nsel); w.ctrls.resize(nsel); w.r0.resize(nsel); w.r1.resize(nsel); w.key.resize(nsel);
+                                   b.row1.p + s0, c->d_wkey.p, d32, d32 + nsel, d32 + (size_t)nsel * 2, d32 + (size_t)nsel * 3, qs));
+  w.sel.resize(nsel);
+  w.pack.resize((size_t)nsel * 3);
   HIP_TRY(c, hipMemcpyAsync(w.sel.data(), c->d_sel.p, nsel * 4, hipMemcpyDeviceToHost, qs));
-  HIP_TRY(c, hipMemcpyAsync(w.key.data(), c->d_wkey.p, nsel * 8, hipMemcpyDeviceToHost, qs));
-  HIP_TRY(c, hipMemcpyAsync(w.cases.data(), c->d_wcases.p, nsel * 4, hipMemcpyDeviceToHost, qs));
-  HIP_TRY(c, hipMemcpyAsync(w.ctrls.data(), c->d_wctrls.p, nsel * 4, hipMemcpyDeviceToHost, qs));
-  HIP_TRY(c, hipMemcpyAsync(w.r0.data(), c->d_wrow0.p, nsel * 4, hipMemcpyDeviceToHost, qs));
-  HIP_TRY(c, hipMemcpyAsync(w.r1.data(), c->d_wrow1.p, nsel * 4, hipMemcpyDeviceToHost, qs));
+  HIP_TRY(c, hipMemcpyAsync(w.pack.data(), c->d_wkey.p, (size_t)nsel * 24, hipMemcpyDeviceToHost, qs));
   return GCRE_OK;
+}
+
+// once the copies queue_winners queued have arrived (the caller waited for their stream)
+void unpack_winners(Winners& w) {
+  if (w.pack.empty()) return;
+  const size_t n = w.n;
+  const uint32_t* h32 = (const uint32_t*)(w.pack.data() + n);
+  w.key.assign(w.pack.data(), w.pack.data() + n);
+  w.cases.assign(h32, h32 + n);
+  w.ctrls.assign(h32 + n, h32 + 2 * n);
+  w.r0.assign(h32 + 2 * n, h32 + 3 * n);
+  w.r1.assign(h32 + 3 * n, h32 + 4 * n);
+  w.pack.clear();
 }
 
 // the second half of a selection begun on C.sel_on, whose state has arrived (the caller waited for it): collect the
@@ -1651,15 +1665,11 @@ int prepare_operands(JoinRun& R) {
       // row lies inside paths1[loc]; what paths1[loc] has beyond it is collected per range), and per joined path in
       // k_stats_ie (that excess lies inside paths0[idx])
       if (int rc = ensure_ranges(c, u)) return rc;
-      const size_t ewords = (size_t)std::max<int64_t>(u.n_ranges, 1) * g.S;
-      HIP_TRY(c, R.exbuf->reserve(ewords));
-      HIP_TRY(c, hipMemsetAsync(R.exbuf->p, 0, ewords * 8, st));
-      HIP_TRY(c, hipMemsetAsync(R.flagblk, 0, kFlagWords * 4, st));
-      // its verdict lands in word kFlagRangeUnion of the flag block, which the chunks leave alone: it is read with the first
-      // chunk's flags (no round trip of its own); a reduced row that is not even part of the row it stands for sends
-      // that chunk, and the join, back to paths1 itself like any other broken hint
-      HIP_TRY(c, launch_range_union(jp.p1->d_rows, R.red->d_rows, u.d_red_index, u.d_pair_range, u.d_pair_loc, u.n_pairs, g.S,
-                                    g.Wp, g.method, R.exbuf->p, R.flagblk + kFlagRangeUnion, st));
+      HIP_TRY(c, R.exbuf->reserve((size_t)std::max<int64_t>(u.n_ranges, 1) * g.S));
+      // the check itself (k_range_union) feeds the inspector alone: it is queued in front of the first inspector this join
+      // launches (range_union_now) -- a join that replays every chunk from the inspection cache launches none, and its
+      // chunks carry the verdict in their cached flags
+      R.range_union_due = true;
     }
     if (R.want_ie && R.keep) {
       // carriers of a joined row <= carriers(paths0 row) + carriers(added row); <= padded patient count
@@ -1703,6 +1713,23 @@ int prepare_operands(JoinRun& R) {
   R.prof->prepare_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tp0).count();
   // only the inclusion-exclusion kernels score part of a chunk; every other form gets chunks cut at the shard's ends
   R.split = !(R.want_ie && g.K > 0);
+  return GCRE_OK;
+}
+
+// The range check of a hinted join, once, in front of the first inspector the join launches: what paths1[loc] has beyond the
+// reduced row, per distinct uid range (the inspector's `excess`).  Its verdict lands in words kFlagRangeUnion.. of the flag
+// block, which the chunks leave alone: it is read with that chunk's flags (no round trip of its own); a reduced row that is
+// not even part of the row it stands for sends that chunk, and the join, back to paths1 itself like any other broken hint
+int range_union_now(JoinRun& R) {
+  gcre_ctx* c = R.c;
+  const gcre_uids& u = *R.u;
+  const Geometry& g = R.g;
+  R.range_union_due = false;
+  const size_t ewords = (size_t)std::max<int64_t>(u.n_ranges, 1) * g.S;
+  HIP_TRY(c, hipMemsetAsync(R.exbuf->p, 0, ewords * 8, R.st));
+  HIP_TRY(c, hipMemsetAsync(R.flagblk + kFlagRangeUnion, 0, (kFlagWords - kFlagRangeUnion) * 4, R.st));
+  HIP_TRY(c, launch_range_union(R.jp.p1->d_rows, R.red->d_rows, u.d_red_index, u.d_pair_range, u.d_pair_loc, u.n_pairs, g.S,
+                                g.Wp, g.method, R.exbuf->p, R.flagblk + kFlagRangeUnion, R.st));
   return GCRE_OK;
 }
 
@@ -1810,6 +1837,8 @@ int inspect_chunk(JoinRun& R, ChunkRun& C, ChunkEnd* end) {
   sa.S = g.S;
   sa.Wp = g.Wp;
   gcre_recipe* rcp = R.rcp;
+  if (C.use_ie && !C.hit && R.hinted && R.range_union_due)
+    if (int rc = range_union_now(R)) return rc;
   if (C.use_sparse || C.use_ie) {
     collect_ie_stat(R);
     // the chunk's words of the flag block (6, 7: the join's).  Once a recipe has started, word kFlagOverReserved -- the
@@ -1943,10 +1972,9 @@ int fill_ie_args(JoinRun& R, const ChunkRun& C, IeArgs& ia, int64_t* nseg_scored
     ia.rec_ga = R.rec_a->plane_groups;
     ia.rec_gz = R.rec_z->plane_groups;
     if (g.method == 1) {
-      // the recipe entries of every segment's row, next to the segment table (no load depends on row0 any more)
+      // the recipe entries of every segment's row, next to the segment table (no load depends on row0 any more):
+      // gathered by launch_ie_slices in front of the pruned launches that read them
       HIP_TRY(c, c->d_rec_segs.reserve((size_t)std::max<int64_t>(ia.nsegs, 1) * kRecSegWords));
-      HIP_TRY(c, launch_fill_rec_segs(ia.segs, ia.nsegs, r0->row0.p, r0->rowz.p, r0->linfo.p, r0->lover.p, r0->slot.p, r0->tot.p,
-                                      c->d_rec_segs.p, R.st));
       ia.rec_segs = c->d_rec_segs.p;
     }
   }
@@ -1981,17 +2009,47 @@ int launch_ie_slices(JoinRun& R, const ChunkRun& C, IeArgs& ia, int planes, int6
   const int64_t n = C.n;
   ia.seg_begin = 0;
   ia.seg_end = ia.nsegs;
-  if (c->d_ladder && ia.lad_mode == 0) {
+  const bool warm_up = c->d_ladder && ia.lad_mode == 0;
+  int64_t n_warm = 0;
+  if (warm_up) {
     // warm-up: the first segments are scored without pruning (every count looked up, general kernel); what
     // they find seeds the thresholds the pruned kernel starts from.  Joins of a few thousand paths run here whole.
     // (the scored segments lead the table.)  The general kernel is several times slower per path: a short
     // shard gives it an eighth of its segments, not all of them.
     // every tile warms up on its own permutations: with many tiles the slice gets shorter (its cost is per tile)
-    int64_t n_warm = warm_segments(c, nseg_scored, R.nkt_sp);
+    n_warm = warm_segments(c, nseg_scored, R.nkt_sp);
     // maxima shared with the other devices right after the warm-up: every device warms its share of the slice
     if (jp.exchange && R.exchanges_done < jp.exchanges && R.P > 0)
       n_warm = std::min(n_warm, std::max<int64_t>(64, (int64_t)((double)n_warm * (double)(R.se - R.sb) / (double)R.P) + 1));
     if (c->ie_warm_segs == 0) n_warm = 0;   // GCRE_IE_WARM=0 (tests): everything through the pruned kernel, thresholds from 0
+  }
+  // The recipe gather (k_fill_rec_segs) feeds the pruned launches only -- the slice reads the recipe itself -- so a join
+  // that fits whole into its slice needs none, and any other gets it beside its slice, on the context's gather stream.
+  // That stream starts behind everything queued on this one so far (ev_rec_in): the recipe copies, the segment-table
+  // upload, and every earlier pruned launch that reads the one d_rec_segs buffer -- the chunk before this one, the slices
+  // of an exchanged join, the level before, a join launched ahead; they are all on the context's main stream, as is
+  // every join that gets here (an ahead inspection stops at its flags).  The pruned launches wait for ev_rec_done below.
+  // Until they do, `gathering` waits for the gather stream on every way out: the gather reads the segment table and the
+  // recipe of paths0, which the caller may free as soon as a failed join returns.
+  struct Gathering {
+    hipStream_t on = nullptr;
+    ~Gathering() { if (on) (void)hipStreamSynchronize(on); }
+  } gathering;
+  const bool gather = ia.rec_segs != nullptr && n_warm < ia.nsegs;
+  if (gather) {
+    const gcre_recipe* r0 = jp.p0->rec;
+    const bool beside = n_warm > 0 && c->rec_async && st == c->stream;
+    if (beside) {
+      HIP_TRY(c, hipEventRecord(c->ev_rec_in, st));
+      HIP_TRY(c, hipStreamWaitEvent(c->rec_stream, c->ev_rec_in, 0));
+      gathering.on = c->rec_stream;
+    }
+    // (the gather also zeroes the ticket counters of the first pruned launch: nothing on either stream uses them before)
+    HIP_TRY(c, launch_fill_rec_segs(ia.segs, ia.nsegs, r0->row0.p, r0->rowz.p, r0->linfo.p, r0->lover.p, r0->slot.p, r0->tot.p,
+                                    c->d_rec_segs.p, c->d_queue, beside ? c->rec_stream : st));
+    if (beside) HIP_TRY(c, hipEventRecord(c->ev_rec_done, c->rec_stream));
+  }
+  if (warm_up) {
     IeArgs wa = ia;
     wa.seg_end = n_warm;
     // a wave walks its tiles one after the other: keep enough waves that each gets about four (segment, tile) items
@@ -2009,6 +2067,10 @@ int launch_ie_slices(JoinRun& R, const ChunkRun& C, IeArgs& ia, int planes, int6
                    (double)tw[4] / waves, tw[5] / waves / 1e3, tw[6] / 1e3);
     }
     ia.seg_begin = n_warm;
+  }
+  if (gathering.on) {   // from here on this stream carries the gather: whoever waits for it waits for both
+    HIP_TRY(c, hipStreamWaitEvent(st, c->ev_rec_done, 0));
+    gathering.on = nullptr;
   }
   if (ia.seg_begin >= ia.seg_end) return GCRE_OK;
   ia.queue = c->d_queue;
@@ -2066,7 +2128,7 @@ int launch_ie_slices(JoinRun& R, const ChunkRun& C, IeArgs& ia, int planes, int6
     IeArgs sa2 = ia;
     if (quad) { sa2.quad_begin = lo; sa2.quad_end = hi; }
     else { sa2.seg_begin = lo; sa2.seg_end = hi; }
-    HIP_TRY(c, hipMemsetAsync(sa2.queue, 0, 8 * 16 * 4, st));
+    if (sl > 0 || !gather) HIP_TRY(c, hipMemsetAsync(sa2.queue, 0, 8 * 16 * 4, st));   // (the first launch's: zeroed by the gather)
     if (quad) HIP_TRY(c, launch_null_ie_quad(sa2, planes, st));
     else HIP_TRY(c, launch_null_ie(sa2, g.method, planes, c->d_ladder == nullptr, st));
     lo = hi;
@@ -2378,6 +2440,7 @@ int collect_winners(JoinRun& R, ChunkRun& C) {
     if (!C.win_from_cache) {   // (cached winners are host data: nothing to wait for)
       if (C.sel_on != st) HIP_TRY(c, hipStreamSynchronize(C.sel_on));
       HIP_TRY(c, hipStreamSynchronize(st));   // the null kernel of this chunk: its time is not the selection's
+      unpack_winners(C.win);
     }
     R.select_wait_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tw0).count();
     const int64_t first = C.cb + C.s0;
@@ -2635,6 +2698,7 @@ gcre_ctx* gcre_create(int method, int n_cases, int n_ctrls, int iterations, int 
   if (const char* e = std::getenv("GCRE_IE_WARM")) c->ie_warm_segs = std::min(std::max(std::atoi(e), 0), 1 << 20);
   if (const char* e = std::getenv("GCRE_IE_WARM_ITEMS")) c->ie_warm_items = std::min(std::max(std::atoi(e), 1), 64);
   if (const char* e = std::getenv("GCRE_IE_WARM_DIV")) c->ie_warm_div = std::min(std::max(std::atoi(e), 1), 1 << 30);
+  if (const char* e = std::getenv("GCRE_IE_WARM_CAP_DIV")) c->ie_warm_cap_div = std::min(std::max(std::atoi(e), 1), 1 << 30);
   if (const char* e = std::getenv("GCRE_IE_SJT")) c->ie_small_join_tiles = std::atoi(e);
   if (const char* e = std::getenv("GCRE_IE_BATCH")) c->ie_batch = std::min(std::max(std::atoi(e), 1), 4096);
   if (const char* e = std::getenv("GCRE_IEQ_BATCH")) c->ieq_batch = std::max(0, std::atoi(e));
@@ -2647,6 +2711,10 @@ gcre_ctx* gcre_create(int method, int n_cases, int n_ctrls, int iterations, int 
   bool ok = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) == hipSuccess;
   ok = ok && hipStreamCreateWithFlags(&c->sel_stream, hipStreamNonBlocking) == hipSuccess;
   ok = ok && hipStreamCreateWithFlags(&c->insp_stream, hipStreamNonBlocking) == hipSuccess;
+  ok = ok && hipStreamCreateWithFlags(&c->rec_stream, hipStreamNonBlocking) == hipSuccess;
+  ok = ok && hipEventCreateWithFlags(&c->ev_rec_in, hipEventDisableTiming) == hipSuccess;
+  ok = ok && hipEventCreateWithFlags(&c->ev_rec_done, hipEventDisableTiming) == hipSuccess;
+  if (const char* e = std::getenv("GCRE_REC_STREAM")) c->rec_async = std::atoi(e) != 0;
   ok = ok && hipEventCreateWithFlags(&c->ev_insp_done, hipEventDisableTiming) == hipSuccess;
   ok = ok && hipEventCreateWithFlags(&c->ev_insp_main, hipEventDisableTiming) == hipSuccess;
   ok = ok && hipEventCreateWithFlags(&c->ev_tail, hipEventDisableTiming) == hipSuccess;
@@ -2682,6 +2750,7 @@ void gcre_destroy(gcre_ctx* c) {
   (void)hipSetDevice(c->device);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   if (c->insp_stream) (void)hipStreamSynchronize(c->insp_stream);
+  if (c->rec_stream) (void)hipStreamSynchronize(c->rec_stream);
   drop_ahead(c);
   // path sets and join indices the caller did not free: their rows, lists, count planes, recipes and segment tables go
   // with the context (their handles are invalid from here on, include/gcre_hip.h)
@@ -2698,8 +2767,7 @@ void gcre_destroy(gcre_ctx* c) {
                   (void*)c->d_null, (void*)c->d_mt, (void*)c->d_max_tot, (void*)c->d_max_tot_b, (void*)c->d_queue, (void*)c->d_ladder})
     if (p) (void)hipFree(p);
   c->scratch.release();
-  for (auto* b : {&c->d_sel, &c->d_small, &c->d_chunk, &c->d_rec_segs, &c->d_wcases, &c->d_wctrls, &c->d_wrow0, &c->d_wrow1})
-    b->release();
+  for (auto* b : {&c->d_sel, &c->d_small, &c->d_chunk, &c->d_rec_segs}) b->release();
   c->d_hub_null.release();
   c->d_wkey.release();
   c->d_doff.release();
@@ -2713,6 +2781,10 @@ void gcre_destroy(gcre_ctx* c) {
   if (c->sel_stream) (void)hipStreamSynchronize(c->sel_stream);
   if (c->sel_stream) (void)hipStreamDestroy(c->sel_stream);
   if (c->insp_stream) (void)hipStreamDestroy(c->insp_stream);
+  if (c->rec_stream) (void)hipStreamSynchronize(c->rec_stream);
+  if (c->rec_stream) (void)hipStreamDestroy(c->rec_stream);
+  if (c->ev_rec_in) (void)hipEventDestroy(c->ev_rec_in);
+  if (c->ev_rec_done) (void)hipEventDestroy(c->ev_rec_done);
   if (c->ev_insp_done) (void)hipEventDestroy(c->ev_insp_done);
   if (c->ev_insp_main) (void)hipEventDestroy(c->ev_insp_main);
   if (c->ev_tail) (void)hipEventDestroy(c->ev_tail);
@@ -3081,6 +3153,7 @@ void gcre_pathset_free(gcre_pathset* ps) {
     (void)hipSetDevice(ps->ctx->device);
     if (ps->ctx->stream) (void)hipStreamSynchronize(ps->ctx->stream);
     if (ps->ctx->insp_stream) (void)hipStreamSynchronize(ps->ctx->insp_stream);
+    if (ps->ctx->rec_stream) (void)hipStreamSynchronize(ps->ctx->rec_stream);   // (the gather reads the set's recipe)
     if (ps->ctx->ahead)
       for (const JoinPlan& a : *ps->ctx->ahead)
         if (a.p0 == ps || a.p1 == ps || a.res == ps) { drop_ahead(ps->ctx); break; }

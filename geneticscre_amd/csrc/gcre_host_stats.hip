@@ -103,6 +103,7 @@ int exceed_wait(gcre_ctx* c) {
   (void)hipSetDevice(c->device);
   if (c->stream) HIP_TRY(c, hipStreamSynchronize(c->stream));
   if (c->insp_stream) HIP_TRY(c, hipStreamSynchronize(c->insp_stream));
+  if (c->rec_stream) HIP_TRY(c, hipStreamSynchronize(c->rec_stream));
   return GCRE_OK;
 }
 

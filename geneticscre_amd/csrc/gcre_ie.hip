@@ -1006,8 +1006,9 @@ __global__ __launch_bounds__(64 * kIeWaves) __attribute__((amdgpu_waves_per_eu(L
 // long list continues, the list's first 8 entries) so that the pruned kernel needs no load that depends on row0.
 __global__ __launch_bounds__(256) void k_fill_rec_segs(const SparseSeg* segs, i64 nsegs, const u32* r_row0, const u32* r_rowz,
                                                        const u32* r_linfo, const u32* r_lover, const u32* r_slot, const u32* r_tot,
-                                                       u32* out) {
+                                                       u32* out, u32* queue) {
   const i64 t = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+  if (queue && t < 8 * 16) queue[t] = 0u;   // the ticket counters of the pruned launch behind this gather
   const i64 sidx = t >> 2;
   const int part = (int)(t & 3);   // four threads per segment: the four scalars, then the slot in two halves
   if (sidx >= nsegs) return;
@@ -1033,11 +1034,11 @@ __global__ __launch_bounds__(256) void k_fill_rec_segs(const SparseSeg* segs, i6
 
 hipError_t launch_fill_rec_segs(const SparseSeg* segs, int64_t nsegs, const uint32_t* r_row0, const uint32_t* r_rowz,
                                 const uint32_t* r_linfo, const uint32_t* r_lover, const uint32_t* r_slot, const uint32_t* r_tot,
-                                uint32_t* out, hipStream_t stream) {
+                                uint32_t* out, uint32_t* queue, hipStream_t stream) {
   if (nsegs == 0) return hipSuccess;
   const i64 blocks = (nsegs * 4 + 255) / 256;
   hipLaunchKernelGGL(k_fill_rec_segs, dim3((unsigned)blocks), dim3(256), 0, stream, segs, nsegs, r_row0, r_rowz, r_linfo, r_lover,
-                     r_slot, r_tot, out);
+                     r_slot, r_tot, out, queue);
   return hipGetLastError();
 }
 

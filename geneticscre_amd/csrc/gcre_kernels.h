@@ -179,10 +179,11 @@ hipError_t launch_null_ie_quad(const IeArgs& a, int planes, hipStream_t stream);
 int ieq_max_waves_per_cu(int planes, int gz, bool rec, bool wide);
 int ieq_quad_segs();   // segments a quad may hold (gcre_ieq.hip)
 // r_tot (optional): carriers of the recipe's rows; bits 1-2 of the gathered list-info word then say how many groups of 4
-// count planes of the row can be non-zero, minus one (counts never exceed the carrier total)
+// count planes of the row can be non-zero, minus one (counts never exceed the carrier total).  queue (optional): the 8 x 16
+// ticket counters of the pruned launch that follows, zeroed on the way (nsegs > 0)
 hipError_t launch_fill_rec_segs(const SparseSeg* segs, int64_t nsegs, const uint32_t* r_row0, const uint32_t* r_rowz,
                                 const uint32_t* r_linfo, const uint32_t* r_lover, const uint32_t* r_slot, const uint32_t* r_tot,
-                                uint32_t* out, hipStream_t stream);
+                                uint32_t* out, uint32_t* queue, hipStream_t stream);
 hipError_t launch_null_ie(const IeArgs& a, int method, int planes, bool general, hipStream_t stream);
 int ie_max_waves_per_cu(int method, int planes, int gz, bool out, bool rec);
 // the signed method's pruned kernel (gcre_ie2.hip); rec_rows_a / rec_rows_z count row-halves
