@@ -398,10 +398,61 @@ class GeneBest:
     ctrls: np.ndarray
 
 
-class GeneTally:
+class _Observer:
+    """What GeneTally, ExceedCounts and HitList share: an object of the library that lives on a context (``_owner``), is
+    armed for one join or for one level of process_paths, and is freed once -- by ``free()``, or by its context's close()."""
+
+    _FREE = _JOIN_SET = _LEVEL_SET = ""   # gcre_*_free, gcre_join_set_*, gcre_process_paths_set_*
+    _SET_LIB = ""                         # the module-level accessor of the library with the two setters bound
+    _REFUSAL = ""                         # "<what> does not", in front of " belong to this context"
+
+    def _check_armable(self, ex: "JoinExec", uids) -> None:
+        """Raises unless the object can be armed on ``ex``.  ``uids``: the join's index where the host holds it (None: it is
+        resident, and the library checks what depends on it before any launch)."""
+        if self._owner is not ex or not self._h:
+            raise GcreError(self._REFUSAL + " belong to this context")
+
+    def _set(self, level: Optional[int], h) -> int:
+        """Arm (``h`` = the handle) or disarm (None) for the owner's next join, or for ``level`` of its next process_paths."""
+        lib = globals()[self._SET_LIB]()       # (looked up per call: the accessors can be replaced)
+        if level is None:
+            return getattr(lib, self._JOIN_SET)(self._owner._h, h)
+        return getattr(lib, self._LEVEL_SET)(self._owner._h, level, h)
+
+    def free(self) -> None:
+        h, self._h = self._h, None
+        if h and self._owner._h:       # (a closed context has freed it already)
+            getattr(self._lib, self._FREE)(h)
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def _arm_observers(ex: "JoinExec", observers) -> None:
+    """Arm ``observers`` -- [(observer, level index of process_paths or None for a single join, the join's host-side uids or
+    None)], tallies first, then exceedance counts, then hit lists -- for the next call on ``ex``.  Every one is checked before
+    any is armed, and a refusal by the library disarms what was armed before it: a refused call leaves nothing armed for
+    the next one to consume."""
+    for o, _, uids in observers:
+        o._check_armable(ex, uids)
+    for i, (o, level, _) in enumerate(observers):
+        rc = o._set(level, o._h)
+        if rc != GCRE_OK:
+            for armed, at, _ in observers[:i]:
+                armed._set(at, None)
+            ex._check(rc)
+
+
+class GeneTally(_Observer):
     """gcre_gene_tally: the per-gene best-path table of a join.  ``genes0`` / ``genes1``: the slots a
     joined path inherits from its paths0 row / its paths1 row (``report.gene_tables`` builds them per level).  Pass it as
     ``JoinExec.join(..., tally=t)`` or ``process_paths(..., tallies={"4": t})``, then ``read()``."""
+
+    _FREE, _JOIN_SET, _LEVEL_SET = "gcre_gene_tally_free", "gcre_join_set_tally", "gcre_process_paths_set_tally"
+    _SET_LIB, _REFUSAL = "_genes_lib", "gene tally does not"
 
     def __init__(self, owner: "JoinExec", n_slots: int, genes0, genes1):
         self.genes0, self.genes1 = check_gene_tables(n_slots, genes0, genes1)
@@ -422,16 +473,12 @@ class GeneTally:
                                                           _ptr(cases), _ptr(ctrls)))
         return GeneBest(score, ordinal, src, trg, cases, ctrls)
 
-    def free(self) -> None:
-        h, self._h = self._h, None
-        if h and self._owner._h:       # (a closed context has freed it already)
-            self._lib.gcre_gene_tally_free(h)
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
+    def _check_armable(self, ex, uids) -> None:
+        super()._check_armable(ex, uids)
+        if uids is not None:
+            cnt = np.asarray(uids.count)
+            ends = (np.asarray(uids.location, dtype=np.int64) + cnt)[cnt > 0]
+            check_gene_tables(self.n_slots, self.genes0, self.genes1, len(cnt), int(ends.max()) - 1 if len(ends) else -1)
 
 
 EXCEED_MAX = 10000   # kExceedMax: thresholds of one ExceedCounts (the top_k limit)
@@ -451,7 +498,7 @@ class Exceedances:
     perm_counts: Optional[np.ndarray] = None
 
 
-class ExceedCounts:
+class ExceedCounts(_Observer):
     """gcre_exceed: null exceedance counts of a join for a list of thresholds.  Pass it as
     ``JoinExec.join(..., exceed=x)`` or ``process_paths(..., exceeds={"4": x})``, then ``read()``.  Counts ADD: a join counted
     twice is counted twice (``reset()`` starts over); ``report.fdr_columns`` turns them into PFER, FDR and q-values.
@@ -459,6 +506,9 @@ class ExceedCounts:
     ``perm_counts=True`` also keeps the counts per permutation (gcre_exceed_keep_perm_counts, DESIGN.md §3.8a: thresholds x
     iterations <= ``EXCEED_PERM_CELLS``), read as ``Exceedances.perm_counts``; ``report.false_count_columns`` turns them into
     k-FWER, the median and the (1 - alpha) bound of the number of false positives.  False, the default: nothing new is called."""
+
+    _FREE, _JOIN_SET, _LEVEL_SET = "gcre_exceed_free", "gcre_join_set_exceed", "gcre_process_paths_set_exceed"
+    _SET_LIB, _REFUSAL = "_exceed_lib", "exceedance counts do not"
 
     def __init__(self, owner: "JoinExec", thresholds, perm_counts: bool = False):
         t = np.ascontiguousarray(np.asarray(thresholds, dtype=np.float64).ravel())
@@ -488,33 +538,21 @@ class ExceedCounts:
 
     def stepdown(self, sets, rows, signs=None) -> np.ndarray:
         """Step-down max-T counts (gcre_exceed_stepdown) of an object that keeps per-permutation counts and
-        holds exactly one full pass of one join.  ``sets`` / ``rows`` / ``signs`` as ``JoinExec.score_sets`` takes them, one set
-        per threshold, in the thresholds' order: set j is the joined path whose observed score is threshold j (the library
-        refuses a set whose score is not its threshold, bit for bit).  Returns int64 [m]: n_ge[j] = the permutations whose
-        maximum null value over the join's paths, the rows with a strictly larger threshold left out, reaches threshold j.
-        ``report.stepdown_columns`` turns them into ``PvaluesStepDown``.  The object is not changed."""
+        holds exactly one full pass of one join.  ``sets`` / ``rows`` / ``signs`` as ``JoinExec.score_sets`` takes them (lists
+        per set, or an ``(off, members)`` pair with flat signs), one set per threshold, in the thresholds' order: set j is
+        the joined path whose observed score is threshold j (the library refuses a set whose score is not its threshold,
+        bit for bit).  Returns int64 [m]: n_ge[j] = the permutations whose maximum null value over the join's paths, the
+        rows with a strictly larger threshold left out, reaches threshold j.  ``report.stepdown_columns`` turns them into
+        ``PvaluesStepDown``.  The object is not changed."""
         lib = _stepdown_lib()
         inp, keep = _set_input(sets, rows, signs, self._owner.num_cases + self._owner.num_ctrls)
         n_ge = np.zeros(len(self.thresholds), dtype=np.int64)
         rc = lib.gcre_exceed_stepdown(self._h, ctypes.byref(inp), _ptr(n_ge))
-        del keep
-        if rc != GCRE_OK:                  # (as score_sets: every refusal is a GcreError with the library's message)
-            raise GcreError(self._lib.gcre_last_error(self._owner._h).decode())
+        self._owner._check_gcre(rc)        # (as score_sets: every refusal is a GcreError with the library's message)
         return n_ge
 
     def reset(self) -> None:
         self._owner._check(self._lib.gcre_exceed_reset(self._h))
-
-    def free(self) -> None:
-        h, self._h = self._h, None
-        if h and self._owner._h:       # (a closed context has freed it already)
-            self._lib.gcre_exceed_free(h)
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
 
 
 HITS_CAP_MAX = 1 << 26   # kHitsCapMax: records of one HitList (32 B each on the device)
@@ -544,11 +582,14 @@ class Hits:
                           self.ctrls[r].copy(), np.asarray(null, dtype=np.float32))
 
 
-class HitList:
+class HitList(_Observer):
     """gcre_hits: every joined path of a join whose observed score is >= ``cutoff``, up to ``cap``
     records (32 x cap bytes of device memory).  Pass it as ``JoinExec.join(..., hits=h)``, ``process_paths(..., hits={"4":
     h})`` or ``ResidentPlan.run(..., hits={"4": h})``, then ``read()``.  The list ADDS: shards of one join append into one
     list, a join collected twice is listed twice (``reset()`` starts over)."""
+
+    _FREE, _JOIN_SET, _LEVEL_SET = "gcre_hits_free", "gcre_join_set_hits", "gcre_process_paths_set_hits"
+    _SET_LIB, _REFUSAL = "_hits_lib", "hit list does not"
 
     def __init__(self, owner: "JoinExec", cutoff: float, cap: int = 1 << 20):
         self.cutoff, self.cap = float(cutoff), int(cap)
@@ -585,37 +626,15 @@ class HitList:
     def reset(self) -> None:
         self._owner._check(self._lib.gcre_hits_reset(self._alive()))
 
-    def free(self) -> None:
-        h, self._h = self._h, None
-        if h and self._owner._h:       # (a closed context has freed it already)
-            self._lib.gcre_hits_free(h)
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
-
 
 def _set_input(sets, rows, signs, n: int):
-    """gcre_set_input of ``JoinExec.score_sets``' arguments, and the arrays it points into (keep them alive for the call)."""
-    S = len(sets)
-    lens = [len(s) for s in sets]
-    off = np.zeros(S + 1, dtype=np.int64)
-    off[1:] = np.cumsum(lens)
-    members = np.ascontiguousarray(np.concatenate([np.asarray(s, dtype=np.int64).reshape(-1) for s in sets])
-                                   if S else np.zeros(0), dtype=np.int32)
-    sg = None
-    if signs is not None:
-        if len(signs) != S or any(len(x) != L for x, L in zip(signs, lens)):
-            raise ValueError("signs: one sign per member of every set")
-        sg = np.ascontiguousarray(np.concatenate([np.asarray(x, dtype=np.int64).reshape(-1) for x in signs])
-                                  if S else np.zeros(0), dtype=np.int32)
-    d = np.asarray(rows)
-    if d.ndim != 2:
-        d = d.reshape(-1, n)
-    packed = pack_carriers(d, d.shape[1])
-    inp = gcre_set_input(S, _ptr(off), _ptr(members), _ptr(sg), _ptr(packed), packed.shape[0], d.shape[1])
+    """gcre_set_input of the ``sets`` / ``rows`` / ``signs`` every set entry takes (``n``: the context's patients), and the
+    arrays it points into (keep them alive for the call): ``(inp, (off, members, signs, packed rows))``.  An entry that has
+    index lists to check before it reads its context parses with ``_set_lists`` first and passes ``(off, members)`` and the
+    flat signs on to here -- they are a set list like any other."""
+    S, off, members, sg = _set_lists(sets, signs)
+    packed, n_cols = _carrier_rows(rows, n)
+    inp = gcre_set_input(S, _ptr(off), _ptr(members), _ptr(sg), _ptr(packed), packed.shape[0], n_cols)
     return inp, (off, members, sg, packed)
 
 
@@ -623,27 +642,25 @@ def _set_lists(sets, signs):
     """(S, off, members, signs) as the set entries take them -- int64 [S + 1] offsets into int32 members, int32 signs or None
     -- from one sequence of rows per set with one sequence of signs per set, or from an ``(off, members)`` pair (what
     ``report.hit_sets`` returns) with one flat signs array.  ValueError where the signs do not match the members."""
+    def flat(lists):
+        return np.ascontiguousarray(np.concatenate([np.asarray(x, dtype=np.int64).reshape(-1) for x in lists])
+                                    if len(lists) else np.zeros(0), dtype=np.int32)
+
     if isinstance(sets, tuple) and len(sets) == 2 and isinstance(sets[0], np.ndarray):
         off = np.ascontiguousarray(sets[0], dtype=np.int64)
         members = np.ascontiguousarray(sets[1], dtype=np.int32)
-        S = len(off) - 1
-        sg = None if signs is None else np.ascontiguousarray(np.asarray(signs, dtype=np.int64).reshape(-1), dtype=np.int32)
-        if sg is not None and len(sg) != len(members):
-            raise ValueError("signs: one sign per member of every set")
+        sg = None if signs is None else flat([signs])
+        matching = sg is None or len(sg) == len(members)
     else:
-        S = len(sets)
         lens = [len(s) for s in sets]
-        off = np.zeros(S + 1, dtype=np.int64)
+        off = np.zeros(len(sets) + 1, dtype=np.int64)
         off[1:] = np.cumsum(lens)
-        members = np.ascontiguousarray(np.concatenate([np.asarray(s, dtype=np.int64).reshape(-1) for s in sets])
-                                       if S else np.zeros(0), dtype=np.int32)
-        sg = None
-        if signs is not None:
-            if len(signs) != S or any(len(x) != L for x, L in zip(signs, lens)):
-                raise ValueError("signs: one sign per member of every set")
-            sg = np.ascontiguousarray(np.concatenate([np.asarray(x, dtype=np.int64).reshape(-1) for x in signs])
-                                      if S else np.zeros(0), dtype=np.int32)
-    return S, off, members, sg
+        members = flat(sets)
+        matching = signs is None or (len(signs) == len(sets) and all(len(x) == L for x, L in zip(signs, lens)))
+        sg = flat(signs) if matching and signs is not None else None
+    if not matching:
+        raise ValueError("signs: one sign per member of every set")
+    return len(off) - 1, off, members, sg
 
 
 def pack_carriers(rows, n_cols: int) -> np.ndarray:
@@ -652,6 +669,15 @@ def pack_carriers(rows, n_cols: int) -> np.ndarray:
     bits = np.zeros((d.shape[0], -(-n_cols // 64) * 64), dtype=bool)
     bits[:, :n_cols] = d
     return np.ascontiguousarray(np.packbits(bits, axis=1, bitorder="little").view("<u8"))
+
+
+def _carrier_rows(rows, n: int):
+    """(packed rows, columns) of the carrier matrix a set entry is given: a 2-D ``rows`` keeps its width (the library
+    compares it with the context's), anything else is read as rows of ``n`` patients."""
+    d = np.asarray(rows)
+    if d.ndim != 2:
+        d = d.reshape(-1, n)
+    return pack_carriers(d, d.shape[1]), d.shape[1]
 
 
 class _DpInput:
@@ -673,11 +699,8 @@ class _DpInput:
             self.path_rows[i, :len(p)] = p
             if signs is not None:
                 self.path_sign[i, :len(p)] = signs[i]
-        d = np.asarray(rows).reshape(-1, n) != 0
-        W = (n + 63) // 64
-        bits = np.zeros((d.shape[0], W * 64), dtype=bool)
-        bits[:, :n] = d
-        self.rows = np.ascontiguousarray(np.packbits(bits, axis=1, bitorder="little").view("<u8"))
+        # always n columns, whatever shape ``rows`` has: gcre_dp_input states no width of its own
+        self.rows = pack_carriers(rows, n)
         self.n_strata = 0
         self.stratum = None
         if strata is not None:
@@ -864,6 +887,11 @@ class JoinExec:
         if rc != GCRE_OK:
             self._raise(rc)
 
+    def _check_gcre(self, rc: int):
+        """``_check`` of the set entries: every refusal is a GcreError with the library's message."""
+        if rc != GCRE_OK:
+            raise GcreError(self._lib.gcre_last_error(self._h).decode())
+
     def close(self):
         h, self._h = self._h, None
         if h:
@@ -945,49 +973,17 @@ class JoinExec:
     def score_sets(self, sets, rows, signs=None, family: bool = False, given=None, which=None):
         """Permutation tests of caller-given sets (gcre_score_sets): one SET_SCORE record per set, against this context's
         value table and all ``iters`` permutation masks.  ``sets``: one sequence of row indices of ``rows`` per set
-        (-1 = NA gene); ``rows``: the 0/1 carrier matrix [rows][patients]; ``signs``: per set +1 / -1 per member (None =
-        all +1; read by method 2).  With ``family`` also the per-permutation maximum of the sets' null scores (float32
-        [iters]).  Errors raise GcreError with the library's message.
+        (-1 = NA gene), or a pair ``(off, members)`` -- int64 [S + 1] offsets into int32 members, what ``report.hit_sets``
+        returns; ``rows``: the 0/1 carrier matrix [rows][patients]; ``signs``: per set +1 / -1 per member, with a pair one
+        flat array (None = all +1; read by method 2).  With ``family`` also the per-permutation maximum of the sets' null
+        scores (float32 [iters]).  Errors raise GcreError with the library's message.
 
         ``given`` / ``which``: conditional scores (gcre_score_sets_given), one record per ENTRY: entry i is
         set ``which[i]`` (None: every set in order; repeats allowed) scored without the carriers of set ``given[i]`` -- the
         patients with a variant in any member of that set, whatever the signs; -1 or ``given=None``: nothing set aside.
-        The removed patients count as non-carriers.  ``sets`` may then also be a pair ``(off, members)`` as
-        ``report.hit_sets`` returns it (``signs`` then one flat array, or None).  An index out of range, ``given`` and
-        ``which`` of different lengths, or a given set with an NA member raise ValueError before the library is touched.
+        The removed patients count as non-carriers.  An index out of range, ``given`` and ``which`` of different lengths,
+        or a given set with an NA member raise ValueError before the library is touched.
         With both None nothing changes: the same call, the same records."""
-        if given is not None or which is not None:
-            return JoinExec._score_sets_given(self, sets, rows, signs, family, given, which)
-        lib = _sets_lib()
-        n = self.num_cases + self.num_ctrls
-        S = len(sets)
-        lens = [len(s) for s in sets]
-        off = np.zeros(S + 1, dtype=np.int64)
-        off[1:] = np.cumsum(lens)
-        members = np.ascontiguousarray(np.concatenate([np.asarray(s, dtype=np.int64).reshape(-1) for s in sets])
-                                       if S else np.zeros(0), dtype=np.int32)
-        sg = None
-        if signs is not None:
-            if len(signs) != S or any(len(x) != L for x, L in zip(signs, lens)):
-                raise ValueError("signs: one sign per member of every set")
-            sg = np.ascontiguousarray(np.concatenate([np.asarray(x, dtype=np.int64).reshape(-1) for x in signs])
-                                      if S else np.zeros(0), dtype=np.int32)
-        d = np.asarray(rows)
-        if d.ndim != 2:
-            d = d.reshape(-1, n)
-        packed = pack_carriers(d, d.shape[1])
-        inp = gcre_set_input(S, _ptr(off), _ptr(members), _ptr(sg), _ptr(packed), packed.shape[0], d.shape[1])
-        out = np.zeros(max(S, 1), dtype=SET_SCORE)
-        fam = np.zeros(self.iters, dtype=np.float32) if family else None
-        n_out = ctypes.c_int64(0)
-        rc = lib.gcre_score_sets(self._h, ctypes.byref(inp), _ptr(out), len(out), ctypes.byref(n_out),
-                                 _ptr(fam) if family and self.iters > 0 else None)
-        if rc != GCRE_OK:
-            raise GcreError(self._lib.gcre_last_error(self._h).decode())
-        rec = out[:n_out.value]
-        return (rec, fam) if family else rec
-
-    def _score_sets_given(self, sets, rows, signs, family, given, which):
         S, off, members, sg = _set_lists(sets, signs)
         iw = None if which is None else np.ascontiguousarray(np.asarray(which, dtype=np.int64).reshape(-1))
         ig = None if given is None else np.ascontiguousarray(np.asarray(given, dtype=np.int64).reshape(-1))
@@ -1003,20 +999,17 @@ class JoinExec:
             np.logical_or.at(na, np.repeat(np.arange(S), np.diff(off)), members < 0)
             if na[ig[ig >= 0]].any():
                 raise ValueError("given: a given set has an NA member (-1): its carriers are not known")
-        lib = _given_lib()
-        n = self.num_cases + self.num_ctrls
-        d = np.asarray(rows)
-        if d.ndim != 2:
-            d = d.reshape(-1, n)
-        packed = pack_carriers(d, d.shape[1])
-        inp = gcre_set_input(S, _ptr(off), _ptr(members), _ptr(sg), _ptr(packed), packed.shape[0], d.shape[1])
+        conditional = iw is not None or ig is not None
+        lib = _given_lib() if conditional else _sets_lib()
+        inp, keep = _set_input((off, members), rows, sg, self.num_cases + self.num_ctrls)
         out = np.zeros(max(E, 1), dtype=SET_SCORE)
         fam = np.zeros(self.iters, dtype=np.float32) if family else None
         n_out = ctypes.c_int64(0)
-        rc = lib.gcre_score_sets_given(self._h, ctypes.byref(inp), _ptr(iw), _ptr(ig), E, _ptr(out), len(out),
-                                       ctypes.byref(n_out), _ptr(fam) if family and self.iters > 0 else None)
-        if rc != GCRE_OK:
-            raise GcreError(self._lib.gcre_last_error(self._h).decode())
+        tail = (_ptr(out), len(out), ctypes.byref(n_out), _ptr(fam) if family and self.iters > 0 else None)
+        if conditional:
+            self._check_gcre(lib.gcre_score_sets_given(self._h, ctypes.byref(inp), _ptr(iw), _ptr(ig), E, *tail))
+        else:
+            self._check_gcre(lib.gcre_score_sets(self._h, ctypes.byref(inp), *tail))
         rec = out[:n_out.value]
         return (rec, fam) if family else rec
 
@@ -1027,27 +1020,25 @@ class JoinExec:
 
     def family_tests(self, sets, rows, signs=None, kmax: bool = False, null: bool = False):
         """Step-down, k-FWER and FDR over the family of the given sets (gcre_score_sets_family).  ``sets`` /
-        ``rows`` / ``signs`` as ``score_sets`` takes them.  Returns ``(records, family)``: the SET_SCORE records of
-        ``score_sets``, and one FAMILY_SCORE record per set -- ``n_ge_stepdown`` (permutations whose maximum over the sets
-        that do not score strictly higher reaches the set's score), ``exceed`` (null scores of ALL sets and permutations
-        that reach it) and ``observed`` (sets that reach it); a NaN score gives 0 / 0 / 0, an NA member -1 / 0 / -1.
+        ``rows`` / ``signs`` as ``score_sets`` takes them (lists per set, or an ``(off, members)`` pair with flat signs).
+        Returns ``(records, family)``: the SET_SCORE records of ``score_sets``, and one FAMILY_SCORE record per set --
+        ``n_ge_stepdown`` (permutations whose maximum over the sets that do not score strictly higher reaches the set's
+        score), ``exceed`` (null scores of ALL sets and permutations that reach it) and ``observed`` (sets that reach
+        it); a NaN score gives 0 / 0 / 0, an NA member -1 / 0 / -1.
         With ``kmax`` also float32 [FAMILY_KMAX][iters], row k the (k+1)-th largest null score of every permutation (row 0
         = ``score_sets(family=True)``'s maxima); with ``null`` also the null matrix, float32 [sets][iters] (NaN rows for
         sets with an NA member).  ``report.family_columns`` turns these into p-values.  Errors raise GcreError."""
         lib = _family_lib()
-        n = self.num_cases + self.num_ctrls
-        S = len(sets)
-        inp, keep = _set_input(sets, rows, signs, n)
+        inp, keep = _set_input(sets, rows, signs, self.num_cases + self.num_ctrls)
+        S = inp.n_sets
         out = np.zeros(max(S, 1), dtype=SET_SCORE)
         fam = np.zeros(max(S, 1), dtype=FAMILY_SCORE)
         km = np.zeros((FAMILY_KMAX, self.iters), dtype=np.float32) if kmax else None
         nul = np.zeros((S, self.iters), dtype=np.float32) if null else None
         n_out = ctypes.c_int64(0)
-        rc = lib.gcre_score_sets_family(self._h, ctypes.byref(inp), _ptr(out), len(out), ctypes.byref(n_out), _ptr(fam),
-                                        _ptr(km) if kmax and km.size else None, _ptr(nul) if null and nul.size else None)
-        del keep
-        if rc != GCRE_OK:
-            raise GcreError(self._lib.gcre_last_error(self._h).decode())
+        self._check_gcre(lib.gcre_score_sets_family(self._h, ctypes.byref(inp), _ptr(out), len(out), ctypes.byref(n_out), _ptr(fam),
+                                                    _ptr(km) if kmax and km.size else None,
+                                                    _ptr(nul) if null and nul.size else None))
         res = (out[:n_out.value], fam[:n_out.value])
         return res + ((km,) if kmax else ()) + ((nul,) if null else ())
 
@@ -1057,27 +1048,25 @@ class JoinExec:
 
     def minp_tests(self, sets, rows, signs=None, min_count: bool = False, counts: bool = False):
         """Westfall-Young min-P over the family of the given sets (gcre_score_sets_minp).  ``sets`` / ``rows``
-        / ``signs`` as ``score_sets`` takes them.  Returns ``(records, minp)``: the SET_SCORE records of ``score_sets``, and
-        one MINP_SCORE record per set -- ``n_le_minp`` (permutations whose smallest within-set count over ALL valid sets is at
-        most the set's own ``n_ge``) and ``n_le_stepdown`` (the same with the sets of a smaller ``n_ge`` left out); a NaN
-        score gives 0 / 0, an NA member -1 / -1.  With ``min_count`` also uint32 [iters], per permutation the smallest count
+        / ``signs`` as ``score_sets`` takes them (lists per set, or an ``(off, members)`` pair with flat signs).  Returns
+        ``(records, minp)``: the SET_SCORE records of ``score_sets``, and one MINP_SCORE record per set -- ``n_le_minp``
+        (permutations whose smallest within-set count over ALL valid sets is at most the set's own ``n_ge``) and
+        ``n_le_stepdown`` (the same with the sets of a smaller ``n_ge`` left out); a NaN score gives 0 / 0, an NA member
+        -1 / -1.  With ``min_count`` also uint32 [iters], per permutation the smallest count
         over the valid sets (0xFFFFFFFF without one); with ``counts`` also uint32 [sets][iters], the count R of every null
         score within its own row -- the permutations of that set whose null score is at least as large (rows of 0xFFFFFFFF
         for sets with an NA member).  ``report.minp_columns`` turns the records into p-values.  Errors raise GcreError."""
         lib = _minp_lib()
-        n = self.num_cases + self.num_ctrls
-        S = len(sets)
-        inp, keep = _set_input(sets, rows, signs, n)
+        inp, keep = _set_input(sets, rows, signs, self.num_cases + self.num_ctrls)
+        S = inp.n_sets
         out = np.zeros(max(S, 1), dtype=SET_SCORE)
         mp = np.zeros(max(S, 1), dtype=MINP_SCORE)
         mc = np.full(self.iters, 0xFFFFFFFF, dtype=np.uint32) if min_count else None
         cn = np.full((S, self.iters), 0xFFFFFFFF, dtype=np.uint32) if counts else None
         n_out = ctypes.c_int64(0)
-        rc = lib.gcre_score_sets_minp(self._h, ctypes.byref(inp), _ptr(out), len(out), ctypes.byref(n_out), _ptr(mp),
-                                      _ptr(mc) if min_count and mc.size else None, _ptr(cn) if counts and cn.size else None)
-        del keep
-        if rc != GCRE_OK:
-            raise GcreError(self._lib.gcre_last_error(self._h).decode())
+        self._check_gcre(lib.gcre_score_sets_minp(self._h, ctypes.byref(inp), _ptr(out), len(out), ctypes.byref(n_out), _ptr(mp),
+                                                  _ptr(mc) if min_count and mc.size else None,
+                                                  _ptr(cn) if counts and cn.size else None))
         res = (out[:n_out.value], mp[:n_out.value])
         return res + ((mc,) if min_count else ()) + ((cn,) if counts else ())
 
@@ -1089,18 +1078,17 @@ class JoinExec:
                           picks: bool = False):
         """Competitive tests of the given sets (gcre_score_sets_compete): every set against ``draws`` random
         sets of the same size, drawn from ``rows`` -- here the whole gene POOL, not only the members -- and scored on the
-        observed labels.  ``bins``: per row of ``rows`` its bin 0 .. max, or -1 for a row that is never drawn (a member on
+        observed labels.  ``sets`` / ``signs`` as ``score_sets`` takes them (lists per set, or an ``(off, members)`` pair with
+        flat signs).  ``bins``: per row of ``rows`` its bin 0 .. max, or -1 for a row that is never drawn (a member on
         such a row is fixed: it stays itself in every draw); None = one bin.  A member is replaced by a row of its own bin.
         No permutation mask is read: a context with ``iters`` = 0 will do.  Returns ``(records, n_ge)``: the SET_SCORE
         records of ``score_sets``, and int64 per set the draws whose score reaches the set's (-1 for an NA member).  With
         ``null`` also float64 [sets][draws], the score of every draw (NaN rows for sets with an NA member); with ``picks``
         also int32 [draws][members of all sets], the row every member received.  ``report.competitive_columns`` turns n_ge
         into p-values, ``report.competitive_reference`` restates the call in numpy.  Errors raise GcreError."""
-        lib = _compete_lib()
-        n = self.num_cases + self.num_ctrls
-        S = len(sets)
+        inp, keep = _set_input(sets, rows, signs, self.num_cases + self.num_ctrls)
+        S = inp.n_sets
         B = int(draws)
-        inp, keep = _set_input(sets, rows, signs, n)
         nb = 1
         bn = None
         if bins is not None:
@@ -1108,17 +1096,16 @@ class JoinExec:
             if len(bn) != keep[3].shape[0]:
                 raise ValueError(f"bins: {len(bn)} entries for {keep[3].shape[0]} rows")
             nb = max(int(bn.max()) + 1, 1) if len(bn) else 1
+        lib = _compete_lib()
         out = np.zeros(max(S, 1), dtype=SET_SCORE)
         ge = np.zeros(max(S, 1), dtype=np.int64)
         nul = np.full((S, max(B, 0)), np.nan, dtype=np.float64) if null else None
         pk = np.full((max(B, 0), len(keep[1])), -1, dtype=np.int32) if picks else None
         n_out = ctypes.c_int64(0)
-        rc = lib.gcre_score_sets_compete(self._h, ctypes.byref(inp), _ptr(bn), nb, B, int(seed) & (2**64 - 1), _ptr(out), len(out),
-                                         ctypes.byref(n_out), _ptr(ge), _ptr(nul) if null and nul.size else None,
-                                         _ptr(pk) if picks and pk.size else None)
-        del keep
-        if rc != GCRE_OK:
-            raise GcreError(self._lib.gcre_last_error(self._h).decode())
+        self._check_gcre(lib.gcre_score_sets_compete(self._h, ctypes.byref(inp), _ptr(bn), nb, B, int(seed) & (2**64 - 1), _ptr(out),
+                                                     len(out), ctypes.byref(n_out), _ptr(ge),
+                                                     _ptr(nul) if null and nul.size else None,
+                                                     _ptr(pk) if picks and pk.size else None))
         res = (out[:n_out.value], ge[:n_out.value])
         return res + ((nul,) if null else ()) + ((pk,) if picks else ())
 
@@ -1128,32 +1115,22 @@ class JoinExec:
 
     def set_overlap(self, sets, rows, a=None, b=None):
         """Carrier overlaps of caller-given sets (gcre_set_overlap).  A set's carrier row is the OR of all
-        its members (row indices of the 0/1 matrix ``rows``; -1 = NA gene), whatever the method.  Returns ``(size, both)``:
+        its members (row indices of the 0/1 matrix ``rows``; -1 = NA gene), whatever the method; ``sets``: one sequence of
+        members per set, or an ``(off, members)`` pair as ``clump_sets`` takes it.  Returns ``(size, both)``:
         ``size`` int32 [S][2] = the carriers of every set among the cases and among the controls ((-1, -1) with an NA
         member), ``both`` int32 [na][nb][2] = the patients sets ``a[i]`` and ``b[j]`` share, cases and controls (zeros
         where either has an NA member).  ``a`` / ``b``: set indices, repeats allowed; None = every set in order.  Needs
         neither a value table nor permutation masks.  Errors raise GcreError with the library's message."""
         lib = _overlap_lib()
-        n = self.num_cases + self.num_ctrls
-        S = len(sets)
-        off = np.zeros(S + 1, dtype=np.int64)
-        off[1:] = np.cumsum([len(s) for s in sets])
-        members = np.ascontiguousarray(np.concatenate([np.asarray(s, dtype=np.int64).reshape(-1) for s in sets])
-                                       if S else np.zeros(0), dtype=np.int32)
-        d = np.asarray(rows)
-        if d.ndim != 2:
-            d = d.reshape(-1, n)
-        packed = pack_carriers(d, d.shape[1])
+        inp, keep = _set_input(sets, rows, None, self.num_cases + self.num_ctrls)
+        S = inp.n_sets
         ia = None if a is None else np.ascontiguousarray(np.asarray(a, dtype=np.int64).reshape(-1))
         ib = None if b is None else np.ascontiguousarray(np.asarray(b, dtype=np.int64).reshape(-1))
         na = S if ia is None else len(ia)
         nb = S if ib is None else len(ib)
-        inp = gcre_set_input(S, _ptr(off), _ptr(members), None, _ptr(packed), packed.shape[0], d.shape[1])
         size = np.zeros((S, 2), dtype=np.int32)
         both = np.zeros((na, nb, 2), dtype=np.int32)
-        rc = lib.gcre_set_overlap(self._h, ctypes.byref(inp), _ptr(ia), na, _ptr(ib), nb, _ptr(size), _ptr(both))
-        if rc != GCRE_OK:
-            raise GcreError(self._lib.gcre_last_error(self._h).decode())
+        self._check_gcre(lib.gcre_set_overlap(self._h, ctypes.byref(inp), _ptr(ia), na, _ptr(ib), nb, _ptr(size), _ptr(both)))
         return size, both
 
     def clump_sets(self, sets, rows, order, r: float = 0.5, measure: str = "jaccard", patients: str = "all"):
@@ -1173,32 +1150,17 @@ class JoinExec:
         if patients not in ("all", "cases"):
             raise ValueError("patients must be 'all' or 'cases'")
         lib = _clump_lib()
-        n = self.num_cases + self.num_ctrls
-        if isinstance(sets, tuple) and len(sets) == 2 and isinstance(sets[0], np.ndarray):
-            off = np.ascontiguousarray(sets[0], dtype=np.int64)
-            members = np.ascontiguousarray(sets[1], dtype=np.int32)
-            S = len(off) - 1
-        else:
-            S = len(sets)
-            off = np.zeros(S + 1, dtype=np.int64)
-            off[1:] = np.cumsum([len(x) for x in sets])
-            members = np.ascontiguousarray(np.concatenate([np.asarray(x, dtype=np.int64).reshape(-1) for x in sets])
-                                           if S else np.zeros(0), dtype=np.int32)
-        d = np.asarray(rows)
-        if d.ndim != 2:
-            d = d.reshape(-1, n)
-        packed = pack_carriers(d, d.shape[1])
+        inp, keep = _set_input(sets, rows, None, self.num_cases + self.num_ctrls)
+        S = inp.n_sets
         io = np.ascontiguousarray(np.asarray(order, dtype=np.int64).reshape(-1))
-        inp = gcre_set_input(S, _ptr(off), _ptr(members), None, _ptr(packed), packed.shape[0], d.shape[1])
         size = np.zeros((S, 2), dtype=np.int32)
         clump = np.zeros(S, dtype=np.int64)
         lead = np.zeros(S, dtype=np.int64)
         value = np.zeros(S, dtype=np.float64)
         shared = np.zeros((S, 2), dtype=np.int32)
-        rc = lib.gcre_clump_sets(self._h, ctypes.byref(inp), _ptr(io), len(io), float(r), 0 if measure == "jaccard" else 1,
-                                 0 if patients == "all" else 1, _ptr(size), _ptr(clump), _ptr(lead), _ptr(value), _ptr(shared))
-        if rc != GCRE_OK:
-            raise GcreError(self._lib.gcre_last_error(self._h).decode())
+        self._check_gcre(lib.gcre_clump_sets(self._h, ctypes.byref(inp), _ptr(io), len(io), float(r),
+                                             0 if measure == "jaccard" else 1, 0 if patients == "all" else 1,
+                                             _ptr(size), _ptr(clump), _ptr(lead), _ptr(value), _ptr(shared)))
         return clump, lead, value, shared.astype(np.int64), size
 
     @property
@@ -1237,21 +1199,14 @@ class JoinExec:
         if ig is not None and len(ig) and (ig.min() < -1 or ig.max() >= G):
             raise ValueError(f"group: a group outside -1..{G - 1}")
         lib = _patients_lib()
-        n = self.num_cases + self.num_ctrls
-        d = np.asarray(rows)
-        if d.ndim != 2:
-            d = d.reshape(-1, n)
-        packed = pack_carriers(d, d.shape[1])
-        inp = gcre_set_input(S, _ptr(off), _ptr(members), _ptr(sg), _ptr(packed), packed.shape[0], d.shape[1])
+        inp, keep = _set_input((off, members), rows, sg, self.num_cases + self.num_ctrls)
         ig32 = None if ig is None else np.ascontiguousarray(ig, dtype=np.int32)
         H = 2 if by_sign else 1
-        counts = np.zeros((G, H, d.shape[1]), dtype=np.int32)
+        counts = np.zeros((G, H, inp.n_cols), dtype=np.int32)
         group_sets = np.zeros(G, dtype=np.int64)
         skipped = ctypes.c_int64(0)
-        rc = lib.gcre_set_patient_counts(self._h, ctypes.byref(inp), _ptr(iw), E, _ptr(ig32), G, 1 if by_sign else 0,
-                                         _ptr(counts), _ptr(group_sets), ctypes.byref(skipped))
-        if rc != GCRE_OK:
-            raise GcreError(self._lib.gcre_last_error(self._h).decode())
+        self._check_gcre(lib.gcre_set_patient_counts(self._h, ctypes.byref(inp), _ptr(iw), E, _ptr(ig32), G, 1 if by_sign else 0,
+                                                     _ptr(counts), _ptr(group_sets), ctypes.byref(skipped)))
         return counts, group_sets, int(skipped.value)
 
     @property
@@ -1362,27 +1317,8 @@ class JoinExec:
             opts.d_null_out = ctypes.c_void_p(int(d_null_out))
         res = gcre_result()
         res_h = paths_res._h if paths_res is not None else None
-        # every observer of the call is checked before any is armed: a refused call leaves nothing armed for the next join
-        if tally is not None:
-            if tally._owner is not self or not tally._h:
-                raise GcreError("gene tally does not belong to this context")
-            if not isinstance(uids, DeviceUids):   # (a resident index is checked by the library, before any launch)
-                cnt = np.asarray(uids.count)
-                ends = (np.asarray(uids.location, dtype=np.int64) + cnt)[cnt > 0]
-                check_gene_tables(tally.n_slots, tally.genes0, tally.genes1, len(cnt), int(ends.max()) - 1 if len(ends) else -1)
-        if exceed is not None and (exceed._owner is not self or not exceed._h):
-            raise GcreError("exceedance counts do not belong to this context")
-        if hits is not None and (hits._owner is not self or not hits._h):
-            raise GcreError("hit list does not belong to this context")
-        armed = [(setter, o._h) for setter, o in ((lambda h: _genes_lib().gcre_join_set_tally(self._h, h), tally),
-                                                  (lambda h: _exceed_lib().gcre_join_set_exceed(self._h, h), exceed),
-                                                  (lambda h: _hits_lib().gcre_join_set_hits(self._h, h), hits)) if o is not None]
-        for i, (setter, h) in enumerate(armed):
-            rc = setter(h)
-            if rc != GCRE_OK:                      # the library's own refusal: disarm what this call armed before it
-                for undo, _ in armed[:i]:
-                    undo(None)
-                self._check(rc)
+        host_uids = None if isinstance(uids, DeviceUids) else uids
+        _arm_observers(self, [(o, None, host_uids) for o in (tally, exceed, hits) if o is not None])
         if isinstance(uids, DeviceUids):
             rc = self._lib.gcre_join_uids(self._h, uids._h, paths0._h, paths1._h, res_h, ctypes.byref(opts),
                                           ctypes.byref(res))
@@ -1562,64 +1498,20 @@ def process_paths(problem, device: int = 0, exec_: Optional[JoinExec] = None, ta
     ``hits``: level name -> HitList of ``exec_``: that level's join appends its scored paths at or above the list's cut-off
     (once, however many permutation windows the call walks).
     """
-    if tallies and exec_ is None:
-        raise GcreError("process_paths: gene tallies live on a context; pass the JoinExec they were made on as exec_")
-    if exceeds and exec_ is None:
-        raise GcreError("process_paths: exceedance counts live on a context; pass the JoinExec they were made on as exec_")
-    if hits and exec_ is None:
-        raise GcreError("process_paths: hit lists live on a context; pass the JoinExec they were made on as exec_")
+    for given, what in ((tallies, "gene tallies"), (exceeds, "exceedance counts"), (hits, "hit lists")):
+        if given and exec_ is None:
+            raise GcreError(f"process_paths: {what} live on a context; pass the JoinExec they were made on as exec_")
     ex = exec_ or JoinExec(problem.method, problem.n_cases, problem.n_ctrls, problem.iterations, device)
     ex.top_k = problem.top_k
     lib = ex._lib
     keep = []   # keep numpy buffers alive across the call
-
-    def arr(a, dt):
-        b = np.ascontiguousarray(a, dtype=dt)
-        keep.append(b)
-        return b
-
-    inp = gcre_pp_input()
-    for i, name in enumerate(["1a", "1b", "2", "3", "4", "5"]):
-        u = problem.levels.uids[name]
-        c, l, s = arr(u.count, np.int32), arr(u.location, np.int64), arr(u.signs, np.int32)
-        inp.level[i] = gcre_level(_ptr(c), _ptr(l), len(c), _ptr(s), len(s))
-    for i, name in enumerate(["1a", "1b", "2", "3"]):
-        d = arr(problem.levels.data_inds[name], np.int32)
-        inp.data_inds[i], inp.n_data_inds[i] = _ptr(d), len(d)
-    d1, d2 = arr(problem.data1, np.int32), arr(problem.data2, np.int32)
-    inp.data1, inp.data1_rows, inp.data2, inp.data2_rows, inp.data_col_major = _ptr(d1), d1.shape[0], _ptr(d2), d2.shape[0], 0
-    vt = arr(problem.value_table, np.float64)
-    inp.value_table, inp.vt_rows, inp.vt_cols, inp.vt_col_major = _ptr(vt), vt.shape[0], vt.shape[1], 0
-    pc = arr(problem.perm_cases, np.int32)
-    inp.perm_cases = _ptr(pc) if pc.size else None
-    inp.perm_rows, inp.perm_col_major = (pc.shape[0] if pc.ndim == 2 else 0), 0
-    inp.path_length = int(problem.path_length)
+    inp = _pp_input(problem, keep)
     outs = (gcre_result * 5)()
-    # every observer of every level is checked before any is set: a refused call leaves nothing for the next call to consume
-    for what, given in (("tally", tallies), ("exceed", exceeds), ("hits", hits)):
-        for name, o in (given or {}).items():
-            if name not in LEVEL_INDEX:
-                raise GcreError(f"process_paths: no level {name!r} (levels are {', '.join(LEVEL_INDEX)})")
-            if o._owner is not ex or not o._h:
-                raise GcreError({"tally": "gene tally does not", "exceed": "exceedance counts do not",
-                                 "hits": "hit list does not"}[what] + " belong to this context")
-            if what == "tally":
-                u = problem.levels.uids[name]
-                cnt = np.asarray(u.count)
-                ends = (np.asarray(u.location, dtype=np.int64) + cnt)[cnt > 0]
-                check_gene_tables(o.n_slots, o.genes0, o.genes1, len(cnt), int(ends.max()) - 1 if len(ends) else -1)
-    setters = {"tally": lambda i, h: _genes_lib().gcre_process_paths_set_tally(ex._h, i, h),
-               "exceed": lambda i, h: _exceed_lib().gcre_process_paths_set_exceed(ex._h, i, h),
-               "hits": lambda i, h: _hits_lib().gcre_process_paths_set_hits(ex._h, i, h)}
-    done = []
-    for what, given in (("tally", tallies), ("exceed", exceeds), ("hits", hits)):
-        for name, o in (given or {}).items():
-            rc = setters[what](LEVEL_INDEX[name], o._h)
-            if rc != GCRE_OK:                      # the library's own refusal: take back what this call set before it
-                for w, i in done:
-                    setters[w](i, None)
-                ex._check(rc)
-            done.append((what, LEVEL_INDEX[name]))
+    observers = [(name, o) for given in (tallies, exceeds, hits) for name, o in (given or {}).items()]
+    for name, _ in observers:
+        if name not in LEVEL_INDEX:
+            raise GcreError(f"process_paths: no level {name!r} (levels are {', '.join(LEVEL_INDEX)})")
+    _arm_observers(ex, [(o, LEVEL_INDEX[name], problem.levels.uids[name]) for name, o in observers])
     rc = lib.gcre_process_paths(ex._h, ctypes.byref(inp), outs)
     ex._check(rc)
     result: Dict[str, object] = {}
