@@ -119,6 +119,9 @@ FAMILY_SCORE = np.dtype([("n_ge_stepdown", "<i8"), ("exceed", "<u8"), ("observed
 FAMILY_KMAX = 10   # GCRE_FAMILY_KMAX
 # gcre_minp_score
 MINP_SCORE = np.dtype([("n_le_minp", "<i8"), ("n_le_stepdown", "<i8")], align=True)
+# gcre_prefix_score
+PREFIX_SCORE = np.dtype([("score", "<f8"), ("n_ge", "<i8"), ("best_step", "<i4"), ("best_members", "<i4"), ("steps", "<i4"),
+                         ("cases_pos", "<i4"), ("ctrls_pos", "<i4"), ("cases_neg", "<i4"), ("ctrls_neg", "<i4")], align=True)
 # gcre_burden
 BURDEN = np.dtype([("total", "<i8"), ("observed", "<i8"), ("n_ge", "<i8"), ("n_le", "<i8"), ("planes", "<i4"),
                    ("p_upper", "<f8"), ("p_lower", "<f8")], align=True)
@@ -141,6 +144,7 @@ EXPORTS = [
     "gcre_score_sets_family", "gcre_family_launches",
     "gcre_score_sets_minp", "gcre_minp_launches",
     "gcre_score_sets_compete", "gcre_compete_launches",
+    "gcre_score_sets_prefix", "gcre_prefix_launches",
     "gcre_set_overlap", "gcre_overlap_launches",
     "gcre_clump_sets", "gcre_clump_launches",
     "gcre_set_patient_counts", "gcre_patient_launches",
@@ -277,6 +281,9 @@ _FEATURES = {
         "gcre_score_sets_compete": (_I, [_V, ctypes.POINTER(gcre_set_input), _P, _I32, _I64, ctypes.c_uint64, _P, _I64,
                                          ctypes.POINTER(_I64), _P, _P, _P]),
         "gcre_compete_launches": (_I64, [_V])}),
+    "prefix": ("sets", ["gcre_score_sets_prefix", "gcre_prefix_launches"], "variable-threshold set tests (gcre_score_sets_prefix)", {
+        "gcre_score_sets_prefix": (_I, [_V, ctypes.POINTER(gcre_set_input), _P, _P, _I64, ctypes.POINTER(_I64), _P, _P, _P, _P]),
+        "gcre_prefix_launches": (_I64, [_V])}),
     "overlap": (None, ["gcre_set_overlap"], "carrier overlaps (gcre_set_overlap)", {
         "gcre_set_overlap": (_I, [_V, ctypes.POINTER(gcre_set_input), _P, _I64, _P, _I64, _P, _P]),
         "gcre_overlap_launches": (_I64, [_V])}),
@@ -342,6 +349,7 @@ _given_lib = functools.partial(_feature_lib, "given")
 _family_lib = functools.partial(_feature_lib, "family")
 _minp_lib = functools.partial(_feature_lib, "minp")
 _compete_lib = functools.partial(_feature_lib, "compete")
+_prefix_lib = functools.partial(_feature_lib, "prefix")
 _overlap_lib = functools.partial(_feature_lib, "overlap")
 _clump_lib = functools.partial(_feature_lib, "clump")
 _patients_lib = functools.partial(_feature_lib, "patients")
@@ -1112,6 +1120,51 @@ class JoinExec:
     def compete_launches(self) -> int:
         """k_compete_null launches of ``competitive_tests`` on this context so far."""
         return int(_compete_lib().gcre_compete_launches(self._h))
+
+    def prefix_tests(self, sets, rows, signs=None, cuts=None, family: bool = False, null: bool = False, steps: bool = False):
+        """Variable-threshold tests of the given sets (gcre_score_sets_prefix): the best score over nested
+        prefixes of every set's member list, with the same maximum taken under every permutation.  ``sets`` / ``rows`` /
+        ``signs`` as ``score_sets`` takes them (lists per set, or an ``(off, members)`` pair with flat signs); the ORDER of a
+        set's members is the order its prefixes grow in (``report.threshold_order``).  ``cuts`` follows ``signs``: per member
+        non-zero where a prefix may end (the last member of a set always ends one); None = every member.  Returns
+        ``(records, prefix)``: the SET_SCORE records of ``score_sets`` for the full sets, and one PREFIX_SCORE record per set
+        -- ``score`` the best step's observed score, ``best_step`` / ``best_members`` which prefix that is, ``steps``, its
+        four counts, and ``n_ge`` the permutations whose maximum over the steps reaches ``score`` (-1 for an NA member).
+        With ``family`` also float32 [iters], per permutation the maximum over the sets; with ``null`` also float32
+        [sets][iters], the maximum over every set's steps (NaN rows for sets with an NA member); with ``steps`` also float64
+        [members], the observed score of the step ending at every member (NaN where none does).  The order and the cuts must
+        not be chosen from the labels.  Errors raise GcreError."""
+        S, off, members, sg = _set_lists(sets, signs)
+        ct = None
+        if cuts is not None:
+            if isinstance(sets, tuple) and len(sets) == 2 and isinstance(sets[0], np.ndarray):
+                ct = np.asarray(cuts).reshape(-1)
+                matching = len(ct) == len(members)
+            else:
+                matching = len(cuts) == S and all(len(x) == L for x, L in zip(cuts, np.diff(off)))
+                ct = np.concatenate([np.asarray(x).reshape(-1) for x in cuts]) if matching and S else np.zeros(0)
+            if not matching:
+                raise ValueError("cuts: one flag per member of every set")
+            ct = np.ascontiguousarray(ct != 0, dtype=np.uint8)
+        lib = _prefix_lib()
+        inp, keep = _set_input((off, members), rows, sg, self.num_cases + self.num_ctrls)
+        out = np.zeros(max(S, 1), dtype=SET_SCORE)
+        px = np.zeros(max(S, 1), dtype=PREFIX_SCORE)
+        fam = np.zeros(self.iters, dtype=np.float32) if family else None
+        nul = np.full((S, self.iters), np.nan, dtype=np.float32) if null else None
+        stp = np.full(len(members), np.nan, dtype=np.float64) if steps else None
+        n_out = ctypes.c_int64(0)
+        self._check_gcre(lib.gcre_score_sets_prefix(self._h, ctypes.byref(inp), _ptr(ct) if ct is not None and ct.size else None,
+                                                    _ptr(out), len(out), ctypes.byref(n_out), _ptr(px),
+                                                    _ptr(fam) if family and fam.size else None,
+                                                    _ptr(nul) if null and nul.size else None,
+                                                    _ptr(stp) if steps and stp.size else None))
+        res = (out[:n_out.value], px[:n_out.value])
+        return res + ((fam,) if family else ()) + ((nul,) if null else ()) + ((stp,) if steps else ())
+
+    def prefix_launches(self) -> int:
+        """Kernels ``prefix_tests`` launched for its own stage on this context so far."""
+        return int(_prefix_lib().gcre_prefix_launches(self._h))
 
     def set_overlap(self, sets, rows, a=None, b=None):
         """Carrier overlaps of caller-given sets (gcre_set_overlap).  A set's carrier row is the OR of all

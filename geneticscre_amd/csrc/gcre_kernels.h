@@ -653,6 +653,53 @@ struct CompeteArgs {
 };
 hipError_t launch_compete_null(const CompeteArgs& a, int method, hipStream_t stream);
 
+// ---- variable-threshold set tests: the best prefix of a set's member list (gcre_prefix.hip) ----
+// One slab of whole sets.  Slot e of the slab is set which[e] of the caller's list; its step rows are rows [row0[e],
+// row0[e + 1]) of the slab, in SetNullArgs' row layout.  k_prefix_rows builds them and their counts, k_set_observed scores
+// them, k_prefix_pick takes every slot's best step and k_prefix_null the maximum over a slot's steps under every permutation.
+struct PrefixWaveDev { int32_t slot, steps; int64_t row0; };   // gcre_prefix::PrefixWave: slot < 0 = no set
+struct PrefixPick {
+  double score;                 // the best observed score over the slot's steps, NaN if every step is NaN
+  int32_t best_step;            // the smallest step that attains it, -1 for NaN
+  int32_t cnt[4];               // cases_pos, ctrls_pos, cases_neg, ctrls_neg of that step (zeros for NaN)
+  int32_t pad;
+};
+struct PrefixArgs {
+  // k_prefix_rows
+  const uint32_t* gene_rows;    // [n_rows][W2] the caller's gene rows as dwords (bits beyond the patients are ignored)
+  const int64_t* set_off;       // [n_sets + 1] the caller's set list as it is
+  const int32_t* members;       // rows of every set; none of a launched set is NA
+  const int32_t* signs;         // per member +1 / -1, or nullptr = all +1 (read by method 2)
+  const uint8_t* cut;           // per member: != 0 ends a step; nullptr = every member does
+  const int64_t* which;         // [nslots] the set of every slot
+  const int64_t* row0;          // [nslots + 1] first step row of every slot
+  uint32_t* rows;               // [nrows][M][W32p] step rows: (+) half, then (-) half (method 2); zero beyond the patients
+  int32_t* cnt;                 // [nrows][4] cases_pos, ctrls_pos, cases_neg, ctrls_neg; zero on entry (k_prefix_rows adds)
+  // k_prefix_pick
+  const double* obs;            // [nrows] observed score of every step row (k_set_observed)
+  uint32_t* tot;                // [nrows][M] carriers per half
+  uint32_t* thr;                // [nslots] f32 bit pattern: a permutation counts iff bits(T) >= thr
+  PrefixPick* pick;             // [nslots]
+  // k_prefix_null
+  const PrefixWaveDev* waves;   // [nblocks][4] the block table
+  const uint32_t* masks;        // [W32p][Kpad]
+  const float* t32;             // M=1: sanitised f32 null table, diagonal-major
+  const double* d64;            // M=2: f64 vtmax, diagonal-major
+  const double* d64n;           // M=2: the table the (-) half reads
+  unsigned long long* n_ge;     // [nslots], zero on entry
+  uint32_t* null_max;           // optional [nslots][Kpad]: T as u32 bit patterns
+  uint32_t* fam_bits;           // optional [Kpad] maxima over the slots (zero on entry; accumulates over the slabs)
+  int64_t nslots, nrows;
+  int nblocks;                  // blocks of four slots
+  int W2;                       // dwords per gene row
+  int W32p, Kpad, K;
+  int nkt;                      // permutation tiles of kSetPermTile
+  int n_patients, n_cases;
+};
+hipError_t launch_prefix_rows(const PrefixArgs& a, int method, hipStream_t stream);
+hipError_t launch_prefix_pick(const PrefixArgs& a, int method, hipStream_t stream);
+hipError_t launch_prefix_null(const PrefixArgs& a, int method, hipStream_t stream);
+
 // ---- carrier-overlap counts of caller-given sets (gcre_overlap.hip) ----
 constexpr int kOverlapTile = 64;    // pairs per edge of a block's tile
 constexpr int kOverlapChunk = 32;   // dwords of a row per staged chunk (128 bytes): rows are padded to a multiple of it

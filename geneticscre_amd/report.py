@@ -717,6 +717,164 @@ def competitive_columns(n_ge, valid, draws: int) -> Dict[str, np.ndarray]:
     return {"CompetitivePvalues": out}
 
 
+VARIABLE_THRESHOLD_COLUMNS = ["Sets", "Genes", "Scores", "NominalPvalues", "BestGenes", "BestThreshold", "AdaptiveScores",
+                              "AdaptivePvalues", "AdaptiveFamilyPvalues"]
+
+
+def _cut_lists(lists, cuts, flat_input: bool):
+    """``cuts`` as one list of 0/1 flags per set of ``lists`` (None: every member), from either form ``prefix_tests`` takes."""
+    if cuts is None:
+        return [[1] * len(m) for m in lists]
+    if flat_input:
+        flat = (np.asarray(cuts).reshape(-1) != 0).astype(int).tolist()
+        if len(flat) != sum(len(m) for m in lists):
+            raise ValueError("cuts: one flag per member of every set")
+        pos = np.concatenate([[0], np.cumsum([len(m) for m in lists])]).astype(int)
+        return [flat[pos[s]:pos[s + 1]] for s in range(len(lists))]
+    ct = [[int(bool(x)) for x in m] for m in cuts]
+    if len(ct) != len(lists) or any(len(a) != len(b) for a, b in zip(ct, lists)):
+        raise ValueError("cuts: one flag per member of every set")
+    return ct
+
+
+def prefix_sets(sets, signs, cuts):
+    """The steps of ``JoinExec.prefix_tests`` as sets of their own: ``(step_sets, step_signs, step_set)``.
+    Step k of set s is its members up to and including the k-th member with a non-zero ``cuts`` flag (None: every member;
+    the last member of a set always ends a step), with their signs; the steps of set 0 come first, then those of set 1.
+    ``step_signs`` is None without ``signs``; ``step_set`` int64 [steps] names the set of every step.  ``sets`` / ``signs`` /
+    ``cuts`` in either form the set entries take.  ``score_sets`` and ``family_tests`` on ``step_sets`` give what
+    ``prefix_reference`` turns back into the call's results."""
+    flat_input = isinstance(sets, tuple) and len(sets) == 2 and isinstance(sets[0], np.ndarray)
+    lists, sg = _set_lists(sets, signs)
+    ct = _cut_lists(lists, cuts, flat_input)
+    step_sets, step_signs, step_set = [], [], []
+    for s, m in enumerate(lists):
+        for i in range(len(m)):
+            if ct[s][i] or i + 1 == len(m):
+                step_sets.append(list(m[:i + 1]))
+                step_signs.append(list(sg[s][:i + 1]) if sg is not None else None)
+                step_set.append(s)
+    return step_sets, (step_signs if sg is not None else None), np.asarray(step_set, np.int64)
+
+
+def prefix_reference(step_obs, step_null, step_set, n_sets: int, valid) -> Dict[str, np.ndarray]:
+    """gcre_score_sets_prefix by its definition, in numpy, no device call.  ``step_obs`` float64 [steps] the
+    observed score of every step, ``step_null`` float32 [steps][K] its null scores (already folded: what
+    ``family_tests(null=True)`` returns for ``prefix_sets``), ``step_set`` [steps] the set of every step, ``valid`` [n_sets].
+    Per set: ``best_step`` the smallest step that attains the maximum of the observed scores, NaN steps skipped (-1 if all
+    are NaN); ``score`` the observed score of that step (NaN); ``null_max`` float32 [n_sets][K] the maximum over the set's
+    steps per permutation; ``n_ge`` the permutations with (double) null_max >= score (0 for a NaN score).  A set that is not
+    valid gets NaN, -1, a NaN row and n_ge -1."""
+    obs = np.asarray(step_obs, np.float64).reshape(-1)
+    null = np.asarray(step_null, np.float32)
+    null = null.reshape(len(obs), -1) if null.size else np.zeros((len(obs), 0), np.float32)
+    owner = np.asarray(step_set, np.int64).reshape(-1)
+    ok = np.asarray(valid).reshape(-1) != 0
+    K = null.shape[1]
+    out = {"score": np.full(n_sets, np.nan), "best_step": np.full(n_sets, -1, np.int64), "n_ge": np.zeros(n_sets, np.int64),
+           "null_max": np.full((n_sets, K), np.nan, np.float32)}
+    for s in range(int(n_sets)):
+        if not ok[s]:
+            out["n_ge"][s] = -1
+            continue
+        rows = np.flatnonzero(owner == s)
+        best = -1
+        for k, r in enumerate(rows.tolist()):
+            if obs[r] == obs[r] and (best < 0 or obs[r] > obs[rows[best]]):
+                best = k
+        t = null[rows].max(axis=0) if len(rows) else np.zeros(K, np.float32)
+        out["null_max"][s] = t
+        if best >= 0:
+            out["best_step"][s] = best
+            out["score"][s] = obs[rows[best]]
+            out["n_ge"][s] = int((t.astype(np.float64) >= obs[rows[best]]).sum())
+    return out
+
+
+def threshold_order(set_genes, data):
+    """The order and the cuts of the variable-threshold test (Price et al. 2010) for one set: ``(order, cuts)``.  ``set_genes``
+    are rows of the 0/1 matrix ``data`` (-1 = NA); ``order`` int64 are positions of ``set_genes`` by ascending carrier total
+    of their rows, ties by row (then by position; NA last), so the set's members in prefix order are
+    ``np.asarray(set_genes)[order]`` and its signs likewise; ``cuts`` uint8 flag the last gene of every run of equal carrier
+    total, so that genes of one total enter together: every step is "all genes with at most t carriers".  The carrier totals
+    do not look at the labels, which is what makes the permutation test of the best step valid."""
+    rows = np.asarray(set_genes, np.int64).reshape(-1)
+    d = np.asarray(data)
+    tot = np.array([int((d[r] != 0).sum()) if r >= 0 else np.iinfo(np.int64).max for r in rows.tolist()], np.int64)
+    key_row = np.where(rows >= 0, rows, np.iinfo(np.int64).max)
+    order = np.lexsort((np.arange(len(rows)), key_row, tot)).astype(np.int64)
+    st = tot[order]
+    cuts = np.ones(len(rows), np.uint8)
+    if len(rows) > 1:
+        cuts[:-1] = (st[1:] != st[:-1]) | (rows[order][:-1] < 0)
+    return order, cuts
+
+
+def variable_threshold_test(sets, genes: Sequence[str], data: np.ndarray, n_cases: int, n_ctrls: int, signed: bool = False,
+                            names=None, threshold: float = 0.05, n_permutations: int = 100,
+                            strata: Optional[Sequence[int]] = None, seed: int = 0, device: int = 0):
+    """Variable-threshold test of gene sets the caller names (``JoinExec.prefix_tests``).  Every other set
+    statistic scores a set's full union, so which genes count is decided by one carrier-frequency threshold chosen before
+    the analysis; here a set's genes are ordered by carrier total (``threshold_order``), every prefix "all genes with at
+    most t carriers" is scored, the best one is the statistic, and the same maximum is taken under every permutation.
+    ``sets`` as ``parse_sets`` reads them; genes are looked up after ``preprocess_table(threshold)`` (pass a generous
+    threshold: the test chooses its own); ``names``: one per set.  The masks are ``generate_permutations(seed, strata)``'s.
+
+    One row per set, VARIABLE_THRESHOLD_COLUMNS: ``Genes`` the set's size; ``Scores`` / ``NominalPvalues`` of the full set,
+    as ``score_paths`` gives them; ``BestGenes`` the size of the best prefix and ``BestThreshold`` the carrier total of its
+    last gene; ``AdaptiveScores`` its score; ``AdaptivePvalues`` = n_ge / permutations, a self-contained permutation p-value
+    of the maximum over the set's nested prefixes, one set at a time; ``AdaptiveFamilyPvalues`` single-step max-T of that
+    statistic over the call's sets.  NaN for a set with a gene not found, a NaN score and 0 permutations."""
+    import pandas as pd
+    from . import api
+    genes, data = preprocess_table(genes, data, threshold, n_cases, n_ctrls)
+    data = np.asarray(data)
+    _, rows, signs = parse_sets(sets, genes)
+    S = len(rows)
+    if names is not None and len(names) != S:
+        raise ValueError(f"variable_threshold_test: {len(names)} names for {S} sets")
+    K = int(n_permutations)
+    ordered, osigns, cuts = [], [], []
+    for rs, sg in zip(rows, signs):
+        order, ct = threshold_order(rs, data)
+        ordered.append(np.asarray(rs, np.int64)[order].tolist())
+        osigns.append(np.asarray(sg, np.int64)[order].tolist())
+        cuts.append(ct.tolist())
+    used: Dict[int, int] = {}
+    idx = [[-1 if r < 0 else used.setdefault(r, len(used)) for r in rs] for rs in ordered]
+    sub = data[list(used.keys())] if used else np.zeros((0, n_cases + n_ctrls), np.int32)
+    ex = api.JoinExec(2 if signed else 1, n_cases, n_ctrls, K, device=device)
+    try:
+        ex.set_value_table(api.values_table(n_cases, n_ctrls))
+        if K > 0:
+            ex.generate_permutations(seed, strata)
+        rec, px, fam = ex.prefix_tests(idx, sub, osigns, cuts=cuts, family=True)
+    finally:
+        ex.close()
+    nan = np.full(S, np.nan)
+    ok = (rec["valid"] != 0) & (px["best_step"] >= 0) & (K > 0)
+    tot = (data != 0).sum(axis=1) if len(data) else np.zeros(0, np.int64)
+    best_thr = nan.copy()
+    for s in np.flatnonzero(ok).tolist():
+        best_thr[s] = tot[ordered[s][px["best_members"][s] - 1]]
+    adaptive_p, family_p = nan.copy(), nan.copy()
+    if K > 0:
+        adaptive_p[ok] = px["n_ge"][ok] / K
+        family_p[ok] = _tail_pvalues(fam, px["score"][ok])
+    cols = {
+        "Sets": [str(x) for x in names] if names is not None else [f"Set{s}" for s in range(S)],
+        "Genes": np.array([len(r) for r in rows], np.int64),
+        "Scores": rec["score"],
+        "NominalPvalues": rec["pvalue"],
+        "BestGenes": np.where(ok, px["best_members"], np.nan),
+        "BestThreshold": best_thr,
+        "AdaptiveScores": np.where(ok, px["score"], np.nan),
+        "AdaptivePvalues": adaptive_p,
+        "AdaptiveFamilyPvalues": family_p,
+    }
+    return pd.DataFrame(cols, columns=VARIABLE_THRESHOLD_COLUMNS)
+
+
 def check_best_paths(results_df, genes: Sequence[str], data: np.ndarray, n_cases: int, n_ctrls: int, signed: bool,
                      device: int = 0):
     """checkBestPaths (R/CheckResults.R:2-89) on the device scorer without permutations: the dataset preprocessed with

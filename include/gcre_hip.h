@@ -560,6 +560,50 @@ int gcre_score_sets_compete(gcre_ctx* ctx, const gcre_set_input* in, const int32
  * them, nor the reverse). */
 int64_t gcre_compete_launches(const gcre_ctx* ctx);
 
+/* Variable-threshold tests of the given sets (Price et al. 2010): the best score over nested prefixes of a
+ * set's member list, with the same maximum taken under every permutation, so that the selection of the prefix is paid for
+ * inside the null.  `out`, *n_out: exactly what gcre_score_sets gives for the full sets, so one call yields both p-values.
+ * Steps.  Member i of the flat member list ends a step if cut[i] != 0; the last member of every set always ends one; cut
+ * NULL = every member is a cut.  Step k (0, 1, ...) of set s is the set made of its members up to and including the k-th
+ * cut member, with their signs, and is scored as gcre_score_sets scores that set: the same counts, the same f64 observed
+ * expression, the same f32 null value N[step][r] (NaN and negatives folded to 0).
+ *   score        = the observed score of step best_step
+ *   best_step    = the smallest step that attains the maximum of the observed step scores, NaN steps skipped (-1 and a NaN
+ *                  score if every step is NaN)
+ *   best_members = members of that prefix (0 for NaN); steps = the steps of the set
+ *   cases_pos .. ctrls_neg = the counts of that step (zeros for NaN)
+ *   T[s][r]      = max over the steps of set s of N[step][r]
+ *   n_ge         = #{r < iterations : (double)T[s][r] >= score}; 0 for a NaN score, -1 for an invalid set (an NA member)
+ * iterations == 0: nothing of this stage is launched; every record keeps `steps`, n_ge = 0 (-1 for an invalid set), a NaN
+ * score and best_step = -1.  An invalid set has a NaN score, best_step = -1 and its `steps`.
+ * family_max, optional [iterations]: max of T[s][r] over the valid sets (all zeros without one) -- bit for bit
+ * gcre_score_sets' family_max over the step sets.  null_max, optional [n_sets][iterations] = T (NaN rows for invalid sets).
+ * step_scores, optional [members of the list]: the observed score of the step that ends at member i, NaN where i ends no
+ * step and for invalid sets.
+ * The step rows are built on the device (k_prefix_rows) from the gene rows and the set list, uploaded once.  The valid sets
+ * are walked in slabs of whole sets whose step rows -- and null_max rows, when asked -- stay under GCRE_PREFIX_MAX_MB on the
+ * device (environment, read per call, default 1024; GCRE_PREFIX_SLAB_SETS bounds a slab further); no result depends on the
+ * slabs.
+ * Errors, nothing launched and no output array written (*n_out as gcre_score_sets leaves it): everything gcre_score_sets
+ * refuses; GCRE_ERR_ARG -- NULL px_out, one valid set whose step rows (and null_max row) exceed GCRE_PREFIX_MAX_MB.
+ * n_ge / iterations is a self-contained permutation p-value of the maximum over the caller's nested prefixes, one set at a
+ * time; the order and the cuts must not be chosen from the labels. */
+typedef struct {
+  double score;
+  int64_t n_ge;
+  int32_t best_step, best_members, steps;
+  int32_t cases_pos, ctrls_pos, cases_neg, ctrls_neg;
+} gcre_prefix_score;
+int gcre_score_sets_prefix(gcre_ctx* ctx, const gcre_set_input* in, const uint8_t* cut /* [members], optional */,
+                           gcre_set_score* out, int64_t cap, int64_t* n_out,
+                           gcre_prefix_score* px_out      /* [n_sets] */,
+                           float* family_max              /* optional [iterations] */,
+                           float* null_max                /* optional [n_sets][iterations] */,
+                           double* step_scores            /* optional [members] */);
+/* k_prefix_rows / k_set_observed / k_prefix_pick / k_prefix_null launches of gcre_score_sets_prefix on the context since
+ * gcre_create (no other launch counter counts them, nor the reverse); -1 for a NULL context. */
+int64_t gcre_prefix_launches(const gcre_ctx* ctx);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Carrier overlaps of caller-given sets: which sets are carried by the same patients.  No reference
  * counterpart.
