@@ -145,6 +145,7 @@ EXPORTS = [
     "gcre_score_sets_minp", "gcre_minp_launches",
     "gcre_score_sets_compete", "gcre_compete_launches",
     "gcre_score_sets_prefix", "gcre_prefix_launches",
+    "gcre_score_sets_subsample", "gcre_subsample_launches",
     "gcre_set_overlap", "gcre_overlap_launches",
     "gcre_clump_sets", "gcre_clump_launches",
     "gcre_set_patient_counts", "gcre_patient_launches",
@@ -284,6 +285,10 @@ _FEATURES = {
     "prefix": ("sets", ["gcre_score_sets_prefix", "gcre_prefix_launches"], "variable-threshold set tests (gcre_score_sets_prefix)", {
         "gcre_score_sets_prefix": (_I, [_V, ctypes.POINTER(gcre_set_input), _P, _P, _I64, ctypes.POINTER(_I64), _P, _P, _P, _P]),
         "gcre_prefix_launches": (_I64, [_V])}),
+    "subsample": ("sets", ["gcre_score_sets_subsample", "gcre_subsample_launches"], "split-half stability counts (gcre_score_sets_subsample)", {
+        "gcre_score_sets_subsample": (_I, [_V, ctypes.POINTER(gcre_set_input), _I32, _I32, _I64, ctypes.c_uint64, _P, _I, _I, _P, _I, _I,
+                                           _P, _I32, _P, _I64, ctypes.POINTER(_I64), _P, _P, _P, _P, _P]),
+        "gcre_subsample_launches": (_I64, [_V])}),
     "overlap": (None, ["gcre_set_overlap"], "carrier overlaps (gcre_set_overlap)", {
         "gcre_set_overlap": (_I, [_V, ctypes.POINTER(gcre_set_input), _P, _I64, _P, _I64, _P, _P]),
         "gcre_overlap_launches": (_I64, [_V])}),
@@ -350,6 +355,7 @@ _family_lib = functools.partial(_feature_lib, "family")
 _minp_lib = functools.partial(_feature_lib, "minp")
 _compete_lib = functools.partial(_feature_lib, "compete")
 _prefix_lib = functools.partial(_feature_lib, "prefix")
+_subsample_lib = functools.partial(_feature_lib, "subsample")
 _overlap_lib = functools.partial(_feature_lib, "overlap")
 _clump_lib = functools.partial(_feature_lib, "clump")
 _patients_lib = functools.partial(_feature_lib, "patients")
@@ -1161,6 +1167,65 @@ class JoinExec:
                                                     _ptr(stp) if steps and stp.size else None))
         res = (out[:n_out.value], px[:n_out.value])
         return res + ((fam,) if family else ()) + ((nul,) if null else ()) + ((stp,) if steps else ())
+
+    def subsample_tests(self, sets, rows, signs=None, m_cases=None, m_ctrls=None, draws: int = 100, seed: int = 0, table_a=None,
+                        table_b=None, cuts=None, scores: bool = False):
+        """Split-half stability of the given sets (gcre_score_sets_subsample): every set scored on ``draws``
+        random halves of the cohort -- ``m_cases`` of the cases and ``m_ctrls`` of the controls (None: ``n // 2`` of each
+        label), half A -- and on the complementary halves, half B.  ``sets`` / ``rows`` / ``signs`` as ``score_sets`` takes
+        them.  ``table_a`` / ``table_b``: the value tables of the two half cohorts (None: ``values_table(m_cases, m_ctrls)``
+        and that of the patients left); ``table_b=False`` scores half A only.  ``cuts``: the cut-offs in score units, one
+        list for every set or one list per set (at most 8 each); None = no counts.  No permutation mask is read: a context
+        with ``iters`` = 0 will do.  Returns ``(records, counts)``: the SET_SCORE records of ``score_sets`` on the full
+        cohort, and ``counts`` with ``n_a`` / ``n_b`` / ``n_both``, int64 [sets][cuts] -- the draws in which half A, half B
+        and both reach the cut (-1 for a set with an NA member; ``n_b`` and ``n_both`` None without half B).  With ``scores``
+        also float64 [sets][draws] twice, the A and the B score of every draw (NaN rows for sets with an NA member; None
+        for B without half B).  ``report.stability_columns`` turns the counts into frequencies, ``report.subsample_reference``
+        restates the call in numpy.  Errors raise GcreError."""
+        inp, keep = _set_input(sets, rows, signs, self.num_cases + self.num_ctrls)
+        S = inp.n_sets
+        B = int(draws)
+        ma = self.num_cases // 2 if m_cases is None else int(m_cases)
+        mt = self.num_ctrls // 2 if m_ctrls is None else int(m_ctrls)
+        ct = None
+        n_cut = 0
+        if cuts is not None:
+            ct = np.asarray(cuts, dtype=np.float64)
+            if ct.ndim == 1:
+                ct = np.broadcast_to(ct, (S, len(ct)))
+            if ct.ndim != 2 or ct.shape[0] != S:
+                raise ValueError(f"cuts: one list, or one list per set ({S} sets), not shape {ct.shape}")
+            n_cut = ct.shape[1]
+            ct = np.ascontiguousarray(ct) if ct.size else np.zeros(max(n_cut, 1))     # (no set: still an array to point to)
+        half_b = table_b is not False
+        in_range = 0 <= ma <= self.num_cases and 0 <= mt <= self.num_ctrls     # (otherwise the library refuses)
+        if table_a is None and in_range:
+            table_a = values_table(ma, mt)
+        if table_b is None and in_range:
+            table_b = values_table(self.num_cases - ma, self.num_ctrls - mt)
+        ta = None if table_a is None else np.ascontiguousarray(table_a, dtype=np.float64)
+        tb = np.ascontiguousarray(table_b, dtype=np.float64) if half_b and table_b is not None else None
+        if any(t is not None and t.ndim != 2 for t in (ta, tb)):
+            raise ValueError("table_a / table_b: a value table has rows and columns")
+        lib = _subsample_lib()
+        out = np.zeros(max(S, 1), dtype=SET_SCORE)
+        cnt = [np.zeros((max(S, 1), n_cut), dtype=np.int64) if h == 0 or half_b else None for h in range(3)]
+        sc = [np.full((S, max(B, 0)), np.nan, dtype=np.float64) if scores and (h == 0 or half_b) else None for h in range(2)]
+        n_out = ctypes.c_int64(0)
+        given = lambda a: _ptr(a) if a is not None and a.size else None
+        self._check_gcre(lib.gcre_score_sets_subsample(
+            self._h, ctypes.byref(inp), ma, mt, B, int(seed) & (2**64 - 1),
+            _ptr(ta), 0 if ta is None else ta.shape[0], 0 if ta is None else ta.shape[1],
+            _ptr(tb), 0 if tb is None else tb.shape[0], 0 if tb is None else tb.shape[1],
+            given(ct), n_cut, _ptr(out), len(out), ctypes.byref(n_out), given(cnt[0]), given(cnt[1]), given(cnt[2]),
+            given(sc[0]), given(sc[1])))
+        n = n_out.value
+        counts = {k: None if c is None else c[:n] for k, c in zip(("n_a", "n_b", "n_both"), cnt)}
+        return (out[:n], counts) + ((sc[0], sc[1]) if scores else ())
+
+    def subsample_launches(self) -> int:
+        """Kernels ``subsample_tests`` launched for its own stage on this context so far: one per table, two per slab."""
+        return int(_subsample_lib().gcre_subsample_launches(self._h))
 
     def prefix_launches(self) -> int:
         """Kernels ``prefix_tests`` launched for its own stage on this context so far."""

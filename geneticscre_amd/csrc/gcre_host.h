@@ -266,6 +266,7 @@ struct gcre_ctx {
   int64_t minp_launches = 0;         // k_minp_gather / k_family_null / k_minp_rank / _scan launches of gcre_score_sets_minp
   int64_t compete_launches = 0;      // k_compete_null launches of gcre_score_sets_compete (gcre_compete_launches)
   int64_t prefix_launches = 0;       // kernels gcre_score_sets_prefix launched for its own stage (gcre_prefix_launches)
+  int64_t subsample_launches = 0;    // kernels gcre_score_sets_subsample launched for its own stage (gcre_subsample_launches)
 
   // resident inputs
   uint64_t* d_case_mask = nullptr;   // [Wp]

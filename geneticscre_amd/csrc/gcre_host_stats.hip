@@ -1,5 +1,5 @@
 // gcre_host_stats.hip -- the entry points of include/gcre_hip.h that use a context but not the join driver: generated
-// permutation masks, decorated p-values (gcre_decorated.hip), set scores (gcre_sets.hip, conditional: gcre_given.hip, family-wise: gcre_family.hip, min-P: gcre_minp.hip, competitive: gcre_compete.hip, variable-threshold: gcre_prefix.hip) and carrier overlaps
+// permutation masks, decorated p-values (gcre_decorated.hip), set scores (gcre_sets.hip, conditional: gcre_given.hip, family-wise: gcre_family.hip, min-P: gcre_minp.hip, competitive: gcre_compete.hip, variable-threshold: gcre_prefix.hip, split-half stability: gcre_subsample.hip) and carrier overlaps
 // (gcre_overlap.hip), greedy clumps (gcre_clump.hip), carrier tallies per patient (gcre_patients.hip) and burden tests of per-patient weights (gcre_burden.hip), and the per-gene tally (gcre_genes.hip), the null exceedance counts (gcre_exceed.hip,
 // gcre_stepdown.hip) and the hit lists (gcre_hits.hip) as objects.  What a join does with an armed tally, armed counts or
 // an armed list -- check_tally, fold_genes, count_exceed, collect_hits -- is in gcre_host.hip.  Host code only.
@@ -7,6 +7,7 @@
 #include "gcre_setlists.h"
 #include "gcre_compete.h"
 #include "gcre_prefix.h"
+#include "gcre_subsample.h"
 #include "gcre_clumporder.h"
 
 namespace {
@@ -809,11 +810,157 @@ void prefix_stage(gcre_ctx* c, DevScratch& d, const gcre_set_input* in, const st
   }
 }
 
-// gcre_score_sets, with `fo` gcre_score_sets_family, with `mo` gcre_score_sets_minp, with `co` gcre_score_sets_compete and with
-// `po` gcre_score_sets_prefix: the same checks, host stage and device stage
+// What gcre_score_sets_subsample takes and returns beside the records
+struct SubsampleOut {
+  int32_t m_cases, m_ctrls;
+  int64_t draws;
+  uint64_t seed;
+  const double* table_a;    // [nrow_a][ncol_a]
+  int nrow_a, ncol_a;
+  const double* table_b;    // [nrow_b][ncol_b] or NULL
+  int nrow_b, ncol_b;
+  const double* cut;        // [n_sets][n_cut] or NULL
+  int32_t n_cut;
+  int64_t* n_a;             // [n_sets][n_cut]
+  int64_t* n_b;             // optional, with table_b
+  int64_t* n_both;          // optional, with table_b
+  double* scores_a;         // optional [n_sets][draws]
+  double* scores_b;         // optional, with table_b
+};
+
+gcre_subsample::SubsampleAsk subsample_ask(const gcre_ctx* c, const SubsampleOut& so) {
+  return {c->g.n_cases, c->g.n - c->g.n_cases, so.m_cases, so.m_ctrls, so.draws, so.table_a != nullptr, so.nrow_a, so.ncol_a,
+          so.table_b != nullptr, so.nrow_b, so.ncol_b, so.cut, so.n_cut, so.n_a != nullptr, so.n_b != nullptr, so.n_both != nullptr,
+          so.scores_a != nullptr, so.scores_b != nullptr};
+}
+
+// the argument checks of gcre_subsample.h, and what the device's 32-bit indices add
+int check_subsample(gcre_ctx* c, const gcre_set_input* in, const SubsampleOut& so, const std::string& who) {
+  std::string msg;
+  if (int rc = gcre_subsample::check_subsample_args(in, subsample_ask(c, so), gcre_subsample::subsample_max_mb(), who, msg))
+    return fail(c, rc, msg);
+  if (in->n_sets > 0x7fffffff / (2 * GCRE_SUBSAMPLE_MAX_CUTS)) return fail(c, GCRE_ERR_ARG, who + ": too many sets");
+  return GCRE_OK;
+}
+
+// The subsampling stage of gcre_score_sets_subsample, behind score_set_rows: d_rows are the valid sets' union rows as
+// k_set_null reads them, cnt [V][4] their counts as SetUnion::build gives them.  The two tables go up as they are and become
+// diagonal-major on the device (k_table_to_diag, sized for the half cohorts); then, per slab of whole draw tiles,
+// k_subsample_masks and k_subsample_null.  The counts are exact sums and every draw belongs to one slab, so no result depends
+// on the slabs.  Errors stay in `d`.
+void subsample_stage(gcre_ctx* c, DevScratch& d, const gcre_set_input* in, const uint64_t* d_rows, const std::vector<int32_t>& cnt,
+                     const std::vector<int64_t>& vset, const SubsampleOut& so) {
+  const Geometry& g = c->g;
+  const int M = g.method, n_cut = so.n_cut;
+  const int64_t V = (int64_t)vset.size(), B = so.draws;
+  const int nA = so.m_cases + so.m_ctrls, nB = g.n - nA;
+  const bool have_b = so.table_b != nullptr;
+
+  // the carriers of every half-row among the cases and among the controls (the (-) half is counted the other way round)
+  std::vector<uint32_t> tot((size_t)V * 2 * M);
+  for (int64_t v = 0; v < V; v++) {
+    const int32_t* k = cnt.data() + 4 * v;
+    tot[(size_t)v * 2 * M] = (uint32_t)k[0];
+    tot[(size_t)v * 2 * M + 1] = (uint32_t)k[1];
+    if (M == 2) {
+      tot[(size_t)v * 4 + 2] = (uint32_t)k[3];
+      tot[(size_t)v * 4 + 3] = (uint32_t)k[2];
+    }
+  }
+  std::vector<double> cuts((size_t)V * std::max(n_cut, 1), 0.0);
+  for (int64_t v = 0; v < V && n_cut > 0; v++)
+    std::memcpy(cuts.data() + (size_t)v * n_cut, so.cut + (size_t)vset[(size_t)v] * n_cut, (size_t)n_cut * 8);
+
+  auto diag_table = [&](const double* table, int nrow, int ncol, int n_half) -> double* {
+    const size_t TD = (size_t)n_half + 1;
+    const double* d_raw = d.put(table, (size_t)nrow * (size_t)ncol);
+    double* dvt = d.take<double>(TD * (TD + 1) / 2);
+    if (d.ok()) {
+      d.e = launch_table_to_diag(d_raw, nrow, ncol, 0, n_half, (int)TD, dvt, nullptr, nullptr, nullptr, c->stream);
+      if (d.ok()) c->subsample_launches++;
+    }
+    return dvt;
+  };
+  SubsampleArgs a{};
+  a.dvt_a = diag_table(so.table_a, so.nrow_a, so.ncol_a, nA);
+  a.dvt_b = have_b ? diag_table(so.table_b, so.nrow_b, so.ncol_b, nB) : nullptr;
+  a.rows = (const uint32_t*)d_rows;
+  a.tot = d.put(tot.data(), tot.size());
+  a.cut = n_cut > 0 ? d.put(cuts.data(), cuts.size()) : nullptr;
+  const size_t NC = (size_t)V * (size_t)std::max(n_cut, 1);
+  a.n_a = d.take<unsigned long long>(NC);
+  a.n_b = have_b ? d.take<unsigned long long>(NC) : nullptr;
+  a.n_both = have_b ? d.take<unsigned long long>(NC) : nullptr;
+  d.zero(a.n_a, NC);
+  if (have_b) {
+    d.zero(a.n_b, NC);
+    d.zero(a.n_both, NC);
+  }
+  a.nsets = V;
+  a.W32p = 2 * g.Wp;
+  a.n_cases = g.n_cases;
+  a.n_cut = n_cut;
+  const int64_t tpb = subsample_tile_sets(M);
+  a.npt = (V + tpb - 1) / tpb;
+
+  const double per_draw = gcre_subsample::subsample_draw_bytes(in, subsample_ask(c, so));
+  int64_t slab = gcre_subsample::subsample_slab_draws(B, a.W32p, per_draw, gcre_subsample::subsample_max_mb());
+  slab = std::min<int64_t>(slab, (int64_t)1 << 30);   // the 32-bit draw index of a slab
+  a.Kpad = (int)slab;
+  a.stride = slab;
+  uint32_t* d_masks = d.take<uint32_t>((size_t)a.W32p * (size_t)slab);
+  a.masks = d_masks;
+  a.scores_a = so.scores_a ? d.take<double>((size_t)V * (size_t)slab) : nullptr;
+  a.scores_b = so.scores_b ? d.take<double>((size_t)V * (size_t)slab) : nullptr;
+  std::vector<double> stage(a.scores_a || a.scores_b ? (size_t)V * (size_t)slab : 0);
+  const uint64_t seed1 = gcre_subsample::subsample_seed(so.seed);
+  for (int64_t b0 = 0; d.ok() && b0 < B; b0 += slab) {
+    const int64_t nb = std::min(slab, B - b0);
+    a.K = (int)nb;
+    a.nkt = (int)((nb + kSetPermTile - 1) / kSetPermTile);
+    // one set tile per block while that makes at least ~8 blocks per resident block slot, more per block beyond (k_set_null's rule)
+    const int64_t slots = (int64_t)c->cus * 4 * 8;
+    const int64_t per = std::max<int64_t>(1, (a.npt * a.nkt) / slots);
+    a.pgroups = (int)std::min<int64_t>((a.npt + per - 1) / per, 0x7fffffff / std::max(a.nkt, 1));
+    d.e = launch_subsample_masks(seed1, b0, (int)nb, g.n_cases, g.n - g.n_cases, so.m_cases, so.m_ctrls, a.W32p, a.Kpad, d_masks, c->stream);
+    if (d.ok()) c->subsample_launches++;
+    if (d.ok()) {
+      d.e = launch_subsample_null(a, M, c->stream);
+      if (d.ok()) c->subsample_launches++;
+    }
+    for (int half = 0; half < 2; half++) {
+      const double* d_sc = half == 0 ? a.scores_a : a.scores_b;
+      double* h_sc = half == 0 ? so.scores_a : so.scores_b;
+      if (!d_sc) continue;
+      d.download(stage.data(), d_sc, (size_t)V * (size_t)slab);
+      d.sync();
+      if (!d.ok()) break;
+      for (int64_t v = 0; v < V; v++)
+        std::memcpy(h_sc + (size_t)vset[(size_t)v] * (size_t)B + (size_t)b0, stage.data() + (size_t)v * (size_t)slab, (size_t)nb * 8);
+    }
+  }
+  std::vector<unsigned long long> na(NC), nbv(have_b ? NC : 0), nab(have_b ? NC : 0);
+  d.download(na.data(), a.n_a, NC);
+  if (have_b) {
+    d.download(nbv.data(), a.n_b, NC);
+    d.download(nab.data(), a.n_both, NC);
+  }
+  d.sync();
+  if (!d.ok()) return;
+  for (int64_t v = 0; v < V; v++)
+    for (int j = 0; j < n_cut; j++) {
+      const size_t to = (size_t)vset[(size_t)v] * n_cut + j, from = (size_t)v * n_cut + j;
+      so.n_a[to] = (int64_t)na[from];
+      if (so.n_b) so.n_b[to] = (int64_t)nbv[from];
+      if (so.n_both) so.n_both[to] = (int64_t)nab[from];
+    }
+}
+
+// gcre_score_sets, with `fo` gcre_score_sets_family, with `mo` gcre_score_sets_minp, with `co` gcre_score_sets_compete, with
+// `po` gcre_score_sets_prefix and with `so` gcre_score_sets_subsample: the same checks, host stage and device stage
 int score_sets_common(gcre_ctx* c, const gcre_set_input* in, gcre_set_score* out, int64_t cap, int64_t* n_out, float* family_max,
                       const std::string& who, const FamilyOut* fo, const MinpOut* mo = nullptr, const CompeteOut* co = nullptr,
-                      const PrefixOut* po = nullptr) {
+                      const PrefixOut* po = nullptr, const SubsampleOut* so = nullptr) {
   if (!c) return GCRE_ERR_ARG;
   if (!in || !n_out || cap < 0 || (cap > 0 && !out)) return fail(c, GCRE_ERR_ARG, who + ": NULL argument");
   *n_out = 0;
@@ -836,6 +983,8 @@ int score_sets_common(gcre_ctx* c, const gcre_set_input* in, gcre_set_score* out
   gcre_prefix::PrefixSteps steps;
   if (po)
     if (int rc = check_prefix(c, in, *po, who, steps)) return rc;
+  if (so)
+    if (int rc = check_subsample(c, in, *so, who)) return rc;
 
   // the host stage: per valid set the OR of its (+) members and of its (-) members (method 1: of all of them), within the
   // n patients, and their counts; the device rows are [valid set][M][Wp] words, the dword view k_set_null reads
@@ -903,6 +1052,17 @@ int score_sets_common(gcre_ctx* c, const gcre_set_input* in, gcre_set_score* out
     if (po->null_max) std::fill(po->null_max, po->null_max + (size_t)S * (size_t)K, std::numeric_limits<float>::quiet_NaN());
     if (po->step_scores && S > 0) std::fill(po->step_scores, po->step_scores + (size_t)in->set_off[S], nan);
   }
+  if (so) {   // an invalid set -1 and NaN rows; zeros without a draw
+    for (int64_t s = 0; s < S; s++)
+      for (int32_t j = 0; j < so->n_cut; j++) {
+        const size_t at = (size_t)s * so->n_cut + j;
+        so->n_a[at] = out[s].valid ? 0 : -1;
+        if (so->n_b) so->n_b[at] = so->n_a[at];
+        if (so->n_both) so->n_both[at] = so->n_a[at];
+      }
+    if (so->scores_a) std::fill(so->scores_a, so->scores_a + (size_t)S * (size_t)so->draws, nan);
+    if (so->scores_b) std::fill(so->scores_b, so->scores_b + (size_t)S * (size_t)so->draws, nan);
+  }
   const int64_t V = (int64_t)vset.size();
   if (V == 0) return GCRE_OK;
 
@@ -944,6 +1104,10 @@ int score_sets_common(gcre_ctx* c, const gcre_set_input* in, gcre_set_score* out
   }
   if (po && K > 0) {
     prefix_stage(c, d, in, vset, steps, *po);
+    if (!d.ok()) return fail(c, GCRE_ERR_DEVICE, who + ": " + hipGetErrorString(d.e));
+  }
+  if (so && so->draws > 0) {
+    subsample_stage(c, d, in, d_rows, cnt, vset, *so);
     if (!d.ok()) return fail(c, GCRE_ERR_DEVICE, who + ": " + hipGetErrorString(d.e));
   }
   return GCRE_OK;
@@ -997,6 +1161,19 @@ int gcre_score_sets_prefix(gcre_ctx* c, const gcre_set_input* in, const uint8_t*
 }
 
 int64_t gcre_prefix_launches(const gcre_ctx* c) { return c ? c->prefix_launches : -1; }
+
+// Split-half stability of the given sets: gcre_score_sets, then the same device rows scored on random halves
+// of the cohort and on their complements.
+int gcre_score_sets_subsample(gcre_ctx* c, const gcre_set_input* in, int32_t m_cases, int32_t m_ctrls, int64_t draws, uint64_t seed,
+                              const double* table_a, int nrow_a, int ncol_a, const double* table_b, int nrow_b, int ncol_b,
+                              const double* cut, int32_t n_cut, gcre_set_score* out, int64_t cap, int64_t* n_out, int64_t* n_a,
+                              int64_t* n_b, int64_t* n_both, double* scores_a, double* scores_b) {
+  const SubsampleOut so{m_cases, m_ctrls, draws, seed, table_a, nrow_a, ncol_a, table_b, nrow_b, ncol_b, cut, n_cut,
+                        n_a, n_b, n_both, scores_a, scores_b};
+  return score_sets_common(c, in, out, cap, n_out, nullptr, "score_sets_subsample", nullptr, nullptr, nullptr, nullptr, &so);
+}
+
+int64_t gcre_subsample_launches(const gcre_ctx* c) { return c ? c->subsample_launches : -1; }
 
 // Conditional set scores: gcre_score_sets on residual union rows that k_set_residual builds on the device
 // from the caller's gene rows and set list, uploaded once.  The entries without an NA member are walked in slabs so that the

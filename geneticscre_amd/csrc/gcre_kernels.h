@@ -653,6 +653,36 @@ struct CompeteArgs {
 };
 hipError_t launch_compete_null(const CompeteArgs& a, int method, hipStream_t stream);
 
+// ---- split-half stability: sets scored on random halves of the cohort (gcre_subsample.hip) ----
+// k_subsample_masks writes the masks of draws [b0, b0 + nb) by the rule of gcre_subsample.h (seed1 = subsample_seed(seed)) in
+// SetNullArgs' mask layout, [W32p][Kpad] dwords with the columns nb .. Kpad-1 and the rows beyond the patients zero;
+// k_subsample_null scores the launched sets on every draw (half A) and on its complement (half B) with k_set_null's geometry.
+struct SubsampleArgs {
+  const uint32_t* rows;         // [nsets][M][W32p] union rows of the launched sets: (+) half, then (-) half (method 2)
+  const uint32_t* masks;        // [W32p][Kpad] the slab's draws
+  const uint32_t* tot;          // [nsets][M][2] carriers per half-row among the cases, among the controls
+  const double* dvt_a;          // half A's table, diagonal-major, diagonals 0 .. m_cases + m_ctrls
+  const double* dvt_b;          // the complement's, diagonals 0 .. n - m_cases - m_ctrls, or nullptr: half B is not scored
+  const double* cut;            // [nsets][n_cut] (read-only: scalar loads), nullptr with n_cut == 0
+  unsigned long long* n_a;      // [nsets][n_cut] adds: draws whose A score >= cut
+  unsigned long long* n_b;      // ... whose B score >= cut (with dvt_b)
+  unsigned long long* n_both;   // ... both (with dvt_b)
+  double* scores_a;             // optional [nsets][stride]: column = draw of the slab
+  double* scores_b;             // optional, with dvt_b
+  int64_t nsets;
+  int64_t npt;                  // set tiles (subsample_tile_sets sets each)
+  int64_t stride;               // columns of scores_a / scores_b, >= Kpad
+  int W32p, Kpad, K;            // K: draws of the slab
+  int nkt;                      // draw tiles of kSetPermTile
+  int pgroups;                  // blocks per draw tile
+  int n_cases;                  // columns below it are the cases
+  int n_cut;
+};
+int subsample_tile_sets(int method);
+hipError_t launch_subsample_masks(uint64_t seed1, int64_t b0, int nb, int n_cases, int n_ctrls, int m_cases, int m_ctrls, int W32p,
+                                  int Kpad, uint32_t* masks, hipStream_t stream);
+hipError_t launch_subsample_null(const SubsampleArgs& a, int method, hipStream_t stream);
+
 // ---- variable-threshold set tests: the best prefix of a set's member list (gcre_prefix.hip) ----
 // One slab of whole sets.  Slot e of the slab is set which[e] of the caller's list; its step rows are rows [row0[e],
 // row0[e + 1]) of the slab, in SetNullArgs' row layout.  k_prefix_rows builds them and their counts, k_set_observed scores

@@ -29,6 +29,10 @@
                          do the cases carry more of a list of sets than the cases of a random relabelling -- gene-set
                          burden tests, replication in a second cohort (gcre_patient_burden)
 
+  * ``subsample_masks`` / ``subsample_reference`` / ``stability_columns`` / ``stability_bound``  split-half stability: sets
+                         scored on random halves of the cohort and on their complements, how often each half reaches a
+                         cut-off (gcre_score_sets_subsample; beyond the reference)
+
 Host-side post-processing of <= top_k x 5 rows: string work, nothing here touches the scored path.
 """
 from __future__ import annotations
@@ -308,7 +312,7 @@ def score_paths(paths, genes: Sequence[str], data: np.ndarray, n_cases: int, n_c
                 threshold: float = 0.05, n_permutations: int = 100, strata: Optional[Sequence[int]] = None, seed: int = 0,
                 device: int = 0, gwaspa_out: Optional[Dict[str, object]] = None, minp: bool = False,
                 competitive: int = 0, competitive_bins: int = 10, fixed: Optional[Sequence[str]] = None,
-                family_inference: bool = False):
+                stability: int = 0, stability_cuts=None, family_inference: bool = False):
     """Permutation tests of paths and gene sets the caller names (gcre_score_sets on the device): what GWASPA cannot
     answer for a cascade outside its top K, or for a KEGG / Reactome list.  ``paths`` as ``parse_sets`` reads them;
     genes are looked up after ``preprocess_table(threshold)``, as GWASPA and ``decorated_table`` do (a symbol not found is
@@ -347,8 +351,27 @@ def score_paths(paths, genes: Sequence[str], data: np.ndarray, n_cases: int, n_c
     it over the paths.  ``fixed``: gene symbols that stay themselves in every draw of the sets that contain them -- "is this
     set anything beyond its known driver?"; the other sets are drawn from the full pool, so naming a gene changes only the
     sets it is in.  A bin must hold twice as many genes as a set draws from it: lower ``competitive_bins`` for large sets on
-    a small table.  ``competitive=0`` returns exactly the frame without it."""
+    a small table.  ``competitive=0`` returns exactly the frame without it.
+
+    ``stability`` = B > 0: the columns of ``stability_columns`` behind all of these (gcre_score_sets_subsample; DESIGN.md
+    §3.19).  Every p-value above is a statement under one null; none says how much a row depends on the particular patients
+    of the cohort.  Each path is scored on B random halves of the cohort (half of the cases and half of the controls, drawn
+    from ``seed``) and on the complementary halves, each half against the value table of its own size: ``StabilityA`` /
+    ``StabilityB`` / ``StabilityBoth`` are the shares of the draws in which half A, half B and both reach the cut, and
+    ``HalfReplication`` the share of half A's selections that the untouched half B confirms.  ``stability_cuts``, in score
+    units on a HALF cohort: one list for every path, or one list per path (a length-3 path and a 200-gene set do not share a
+    cut-off); with several cuts the columns carry the cut's index as a suffix.  It is required and has no default: a cut
+    is a choice, and the labels must not make it -- a cut taken from this cohort's scores puts the selection back into
+    every frequency here.  The numbers are selection frequencies under subsampling of this cohort: descriptive, no p-value
+    and no family-wise statement, and ``HalfReplication`` is honest only if neither the paths nor the cuts were chosen on the
+    full cohort's labels; otherwise it is optimistic.  The frame's ``attrs["PerHalfSelected"]`` holds, per cut, the mean
+    number of paths half A selects in a draw (the q of ``stability_bound``).  ``stability=0`` returns exactly the frame
+    without it."""
     import pandas as pd
+    if int(stability) < 0:
+        raise ValueError("stability: the number of draws must not be negative")
+    if int(stability) > 0 and stability_cuts is None:
+        raise ValueError("stability > 0 needs stability_cuts: there is no default cut (a cut is a choice the labels must not make)")
     method = 2 if signed else 1
     genes, data = preprocess_table(genes, data, threshold, n_cases, n_ctrls)
     names, rows, signs = parse_sets(paths, genes)
@@ -390,7 +413,32 @@ def score_paths(paths, genes: Sequence[str], data: np.ndarray, n_cases: int, n_c
                                    seed, device)
         cols.update(competitive_columns(n_ge, valid & ~np.isnan(score), int(competitive)))
         names_out += COMPETITIVE_COLUMNS
-    return pd.DataFrame(cols, columns=names_out)
+    per_half = None
+    if int(stability) > 0:
+        counts = _stability_counts(rows, signs, data, n_cases, n_ctrls, method, int(stability), stability_cuts, seed, device)
+        more_cols, per_half = stability_columns(counts, valid, int(stability))
+        cols.update(more_cols)
+        names_out += list(more_cols)
+    df = pd.DataFrame(cols, columns=names_out)
+    if per_half is not None:
+        df.attrs["PerHalfSelected"] = per_half
+    return df
+
+
+def _stability_counts(rows, signs, data, n_cases, n_ctrls, method, draws, cuts, seed, device) -> Dict[str, np.ndarray]:
+    """The counts of subsample_tests for ``score_paths``: the default halves and their tables, on the rows the sets use, on a
+    context of its own without permutations."""
+    from . import api
+    used: Dict[int, int] = {}
+    sets = [[-1 if r < 0 else used.setdefault(r, len(used)) for r in rs] for rs in rows]
+    data = np.asarray(data)
+    sub = data[list(used.keys())] if used else np.zeros((0, n_cases + n_ctrls), np.int32)
+    ex = api.JoinExec(method, n_cases, n_ctrls, 0, device=device)
+    try:
+        ex.set_value_table(api.values_table(n_cases, n_ctrls))
+        return ex.subsample_tests(sets, sub, signs, draws=draws, seed=seed, cuts=cuts)[1]
+    finally:
+        ex.close()
 
 
 def _competitive_counts(rows, signs, genes, data, n_cases, n_ctrls, method, draws, n_bins, fixed, seed, device) -> np.ndarray:
@@ -715,6 +763,149 @@ def competitive_columns(n_ge, valid, draws: int) -> Dict[str, np.ndarray]:
     if B > 0:
         out[ok] = c[ok] / B
     return {"CompetitivePvalues": out}
+
+
+# split-half stability: sets scored on random halves of the cohort and on their complements
+
+STABILITY_COLUMNS = ["StabilityA", "StabilityB", "StabilityBoth", "HalfReplication"]
+SUBSAMPLE_SEED_TAG = 0x73756273616D706C     # "subsampl": seed' = mix64(seed ^ tag)
+
+
+def subsample_masks(n_cases: int, n_ctrls: int, m_cases: int, m_ctrls: int, draws, seed: int) -> np.ndarray:
+    """The draw rule of gcre_score_sets_subsample (csrc/gcre_subsample.h is the same rule in C++): bool
+    [draws][n_cases + n_ctrls], row b the patients of draw b -- exactly ``m_cases`` among the columns < n_cases and
+    ``m_ctrls`` among the rest.  ``draws``: their number (draws 0 .. draws-1), or a sequence of draw indices.  Knuth's
+    selection sampling with the label as the stratum: with seed' = mix64(seed ^ SUBSAMPLE_SEED_TAG) and base_b = mix64(seed'
+    ^ C2 (b + 1)), patient c, in column order, reads u = mix64(base_b + c) and is taken when floor(u rem / 2^64) < need, rem
+    the patients of its stratum not yet walked (c included) and need those still to be taken.  A pure function of (seed, b,
+    c)."""
+    n_cases, n_ctrls, m_cases, m_ctrls = int(n_cases), int(n_ctrls), int(m_cases), int(m_ctrls)
+    if not (0 <= m_cases <= n_cases and 0 <= m_ctrls <= n_ctrls):
+        raise ValueError(f"m = ({m_cases}, {m_ctrls}) outside 0 .. ({n_cases}, {n_ctrls})")
+    b = np.arange(int(draws), dtype=np.int64) if np.ndim(draws) == 0 else np.asarray(draws, dtype=np.int64).reshape(-1)
+    n = n_cases + n_ctrls
+    with np.errstate(over="ignore"):
+        seed1 = _mix64(_U64(int(seed) & (2**64 - 1)) ^ _U64(SUBSAMPLE_SEED_TAG))
+        base = _mix64(seed1 ^ (_U64(0x51ED270B7F3C9A1D) * (b.astype(_U64) + _U64(1))))
+    out = np.zeros((len(b), n), bool)
+    need = np.zeros(len(b), np.int64)
+    for c in range(n):
+        if c == 0:
+            rem, need[:] = n_cases, m_cases
+        if c == n_cases:
+            rem, need[:] = n_ctrls, m_ctrls
+        with np.errstate(over="ignore"):
+            u = _mix64(base + _U64(c))
+        take = _mulhi(u, rem) < need
+        out[:, c] = take
+        need -= take
+        rem -= 1
+    return out
+
+
+def subsample_reference(sets, rows, signs, n_cases: int, m_cases: int, m_ctrls: int, draws: int, seed: int, table_a, table_b,
+                        cuts, method: int) -> Dict[str, np.ndarray]:
+    """The numpy statement of gcre_score_sets_subsample, no device call.  ``rows``: the 0/1 carrier matrix
+    [rows][patients], columns < n_cases the cases; ``sets`` / ``signs`` as ``JoinExec.score_sets`` takes them; ``table_a`` /
+    ``table_b`` the value tables of the half cohorts (``table_b`` None or False: half B is not scored); ``cuts`` [sets][cuts],
+    one list for every set, or None.  Per valid set and draw S_b of ``subsample_masks``: half A = table_a[|P & S_b &
+    cases|][|P & S_b & ctrls|] (+ table_a[|N & S_b & ctrls|][|N & S_b & cases|], added in this order), half B the same on
+    the complement of S_b from table_b; cells a table does not have read as -1.  Returns ``n_a`` / ``n_b`` / ``n_both`` int64
+    [sets][cuts] (-1 for a set with an NA member; the B counts None without half B) and ``scores_a`` / ``scores_b`` float64
+    [sets][draws] (NaN rows for those)."""
+    d = np.asarray(rows) != 0
+    n = d.shape[1]
+    B = int(draws)
+    S = len(sets)
+    case = np.arange(n) < n_cases
+    half_b = table_b is not None and table_b is not False
+    TA = np.asarray(table_a, np.float64)
+    TB = np.asarray(table_b, np.float64) if half_b else None
+    ct = np.zeros((S, 0)) if cuts is None else np.asarray(cuts, np.float64)
+    if ct.ndim == 1:
+        ct = np.broadcast_to(ct, (S, len(ct)))
+    mk = subsample_masks(n_cases, n - n_cases, m_cases, m_ctrls, B, seed)
+    n_half = int(m_cases) + int(m_ctrls)
+
+    def scores(P, N, keep, VT, nh):                 # P, N bool [n]; keep bool [draws][n]
+        v = _vt_cell(VT, nh, (keep & (P & case)).sum(axis=1), (keep & (P & ~case)).sum(axis=1))
+        if method == 2:
+            with np.errstate(invalid="ignore"):      # inf - inf
+                v = v + _vt_cell(VT, nh, (keep & (N & ~case)).sum(axis=1), (keep & (N & case)).sum(axis=1))
+        return v
+
+    res = {"n_a": np.zeros((S, ct.shape[1]), np.int64), "scores_a": np.full((S, B), np.nan),
+           "n_b": np.zeros((S, ct.shape[1]), np.int64) if half_b else None,
+           "n_both": np.zeros((S, ct.shape[1]), np.int64) if half_b else None,
+           "scores_b": np.full((S, B), np.nan) if half_b else None}
+    for s in range(S):
+        m = np.asarray(sets[s], dtype=np.int64).reshape(-1)
+        if (m < 0).any():
+            for k in ("n_a", "n_b", "n_both"):
+                if res[k] is not None:
+                    res[k][s] = -1
+            continue
+        sg = np.ones(len(m), np.int64) if signs is None else np.asarray(signs[s], dtype=np.int64).reshape(-1)
+        neg = (sg == -1) if method == 2 else np.zeros(len(m), bool)
+        P = d[m[~neg]].any(axis=0) if (~neg).any() else np.zeros(n, bool)
+        N = d[m[neg]].any(axis=0) if neg.any() else np.zeros(n, bool)
+        A = scores(P, N, mk, TA, n_half)
+        res["scores_a"][s] = A
+        with np.errstate(invalid="ignore"):
+            ga = A[None, :] >= ct[s][:, None]                            # [cuts][draws]; a NaN never counts
+            res["n_a"][s] = ga.sum(axis=1)
+            if half_b:
+                Bs = scores(P, N, ~mk, TB, n - n_half)
+                res["scores_b"][s] = Bs
+                gb = Bs[None, :] >= ct[s][:, None]
+                res["n_b"][s] = gb.sum(axis=1)
+                res["n_both"][s] = (ga & gb).sum(axis=1)
+    return res
+
+
+def stability_columns(counts, valid, draws: int):
+    """(columns, PerHalfSelected) from the ``counts`` of ``JoinExec.subsample_tests`` (or ``subsample_reference``):
+    ``StabilityA`` = n_a / draws, ``StabilityB`` = n_b / draws and ``StabilityBoth`` = n_both / draws, the shares of the
+    draws in which half A, the complementary half B and both reach the cut; ``HalfReplication`` = n_both / n_a, the share of
+    half A's selections that half B confirms, NaN where half A never selects.  With several cuts every name carries the
+    cut's index (``StabilityA.0``, ``StabilityA.1``, ...).  NaN for a set with an NA member (``valid`` 0 or a count < 0) and
+    with 0 draws; the B columns are all NaN without half B.  ``PerHalfSelected``: per cut the mean number of valid sets half
+    A selects in a draw, the sum of n_a over the valid sets / draws -- the q of ``stability_bound``.
+    Selection frequencies under subsampling of this cohort: descriptive, not p-values, and ``HalfReplication`` is optimistic
+    if the sets or the cuts were chosen on the full cohort's labels."""
+    na = np.asarray(counts["n_a"], np.int64)
+    na = na.reshape(len(na), -1)
+    S, C = na.shape
+    B = int(draws)
+    ok = (np.asarray(valid).ravel()[:S] != 0)[:, None] & (na >= 0)
+    get = lambda k: (np.asarray(counts[k], np.int64).reshape(S, C) if counts.get(k) is not None else None)
+    nb, nab = get("n_b"), get("n_both")
+
+    def share(num, den):
+        out = np.full((S, C), np.nan)
+        if num is not None:
+            den = np.broadcast_to(np.asarray(den, np.float64), (S, C))
+            sel = ok & (den > 0)
+            out[sel] = num[sel] / den[sel]
+        return out
+
+    mats = {"StabilityA": share(na, B), "StabilityB": share(nb, B), "StabilityBoth": share(nab, B), "HalfReplication": share(nab, na)}
+    cols = {(name if C == 1 else f"{name}.{j}"): mats[name][:, j] for j in range(C) for name in STABILITY_COLUMNS}
+    per_half = (np.where(ok, na, 0).sum(axis=0) / B) if B > 0 else np.full(C, np.nan)
+    return cols, per_half
+
+
+def stability_bound(q: float, n_sets: int, tau: float) -> float:
+    """Meinshausen & Buhlmann's (2010, Theorem 1) bound on the expected number of falsely selected sets among those whose
+    selection frequency is at least ``tau`` > 1/2: q^2 / ((2 tau - 1) n_sets), q the mean number of sets a half selects
+    (``PerHalfSelected``) and ``n_sets`` the size of the family.  The bound assumes that the selection of the null sets is
+    exchangeable and no worse than random guessing.  Overlapping paths through one gene do not meet this -- they are
+    selected together or not at all -- so the number is indicative, not a guarantee."""
+    if not tau > 0.5:
+        raise ValueError("stability_bound: tau must be above 1/2")
+    if n_sets < 1:
+        raise ValueError("stability_bound: n_sets must be at least 1")
+    return float(q) * float(q) / ((2.0 * float(tau) - 1.0) * float(n_sets))
 
 
 VARIABLE_THRESHOLD_COLUMNS = ["Sets", "Genes", "Scores", "NominalPvalues", "BestGenes", "BestThreshold", "AdaptiveScores",

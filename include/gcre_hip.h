@@ -604,6 +604,52 @@ int gcre_score_sets_prefix(gcre_ctx* ctx, const gcre_set_input* in, const uint8_
  * gcre_create (no other launch counter counts them, nor the reverse); -1 for a NULL context. */
 int64_t gcre_prefix_launches(const gcre_ctx* ctx);
 
+/* Split-half stability of the given sets (Meinshausen & Buhlmann 2010, Shah & Samworth 2013): how often does
+ * a set still reach a cut-off when it is scored on a random half of the cases and of the controls (half A), on the
+ * complementary half (half B), and on both?  The draws subsample the PATIENTS; the labels stay as observed.  No permutation
+ * mask is read: the draws are independent of the context's masks, and a context with iterations == 0 is the usual one.
+ * `out`, *n_out: exactly what gcre_score_sets gives on the full cohort, so one call yields both.
+ * Draw b (0 .. draws-1) is a mask S_b over the n = n_cases + n_ctrls patients with exactly m_cases bits among the columns
+ * < n_cases and exactly m_ctrls among the rest, made by the rule of gcre_generate_perm_masks (Knuth's selection sampling)
+ * with two strata, a patient's stratum being its label, and the needs (m_cases, m_ctrls):
+ *   seed'  = gcre_mix64(seed ^ 0x73756273616d706c)
+ *   base_b = gcre_mix64(seed' ^ (0x51ed270b7f3c9a1d * (b + 1)))
+ * patient c, in column order, reads u = gcre_mix64(base_b + c) and is taken when floor(u rem / 2^64) < need (the 128-bit
+ * product), rem the patients of its stratum not yet walked (c included) and need those still to be taken.  A pure function
+ * of (seed, b, c).
+ * Scores.  With P, N the unions gcre_score_sets defines (method 1: one union alone), half A's counts are |P & S_b & cases|,
+ * |P & S_b & ctrls| and likewise for N; its score is the f64 expression of the observed score -- for method 2 in its order of
+ * the addition -- read from table_a [nrow_a][ncol_a], row-major, the value table of a cohort of m_cases cases and m_ctrls
+ * controls.  Half B's counts are the set's totals minus half A's, its score is read from table_b, the table of the
+ * n_cases - m_cases cases and n_ctrls - m_ctrls controls left; table_b NULL = half B is not scored.  Cells a table does not
+ * have read as -1, as in gcre_set_value_table.  With m = (n_cases, n_ctrls) and table_a the context's table every A score is
+ * the observed score bit for bit; with m = (0, 0) and table_b the context's table every B score is.
+ * Counts, as doubles, a NaN on either side never counting; cut [n_sets][n_cut] holds every set's own cut-offs:
+ *   n_a[s][j]    = #{b : A_sb >= cut[s][j]}
+ *   n_b[s][j]    = #{b : B_sb >= cut[s][j]}
+ *   n_both[s][j] = #{b : A_sb >= cut[s][j] and B_sb >= cut[s][j]}
+ * all [n_sets][n_cut]; n_b and n_both may be NULL also with table_b.  A set with an NA member gets -1 in every count and NaN
+ * rows in scores_a / scores_b, optional [n_sets][draws].  draws == 0: zeros, nothing of this stage launched.
+ * The draws are walked in slabs of whole 512-draw tiles; a slab's masks and its optional outputs on the device stay under
+ * GCRE_SUBSAMPLE_MAX_MB (environment, read per call, default 1024; one tile at the least; GCRE_SUBSAMPLE_SLAB_DRAWS bounds
+ * a slab further).  The counts are integer sums and every draw belongs to one slab: no result depends on the slabs.
+ * Errors, nothing launched and no output array written (*n_out as gcre_score_sets leaves it): everything gcre_score_sets
+ * refuses; GCRE_ERR_ARG -- draws < 0, m_cases outside 0 .. n_cases, m_ctrls outside 0 .. n_ctrls, NULL table_a, a table
+ * without a row or a column, n_cut outside 0 .. GCRE_SUBSAMPLE_MAX_CUTS, n_cut > 0 with NULL cut or NULL n_a, n_b / n_both /
+ * scores_b without table_b, a NaN in cut, the optional outputs of one 512-draw tile above GCRE_SUBSAMPLE_MAX_MB.
+ * The counts are selection frequencies under subsampling of THIS cohort: descriptive, no p-value and no family-wise
+ * statement.  n_both / n_a says how often the untouched half confirms a selection only if neither the sets nor the cuts
+ * were chosen on the full cohort's labels; otherwise it is optimistic. */
+#define GCRE_SUBSAMPLE_MAX_CUTS 8
+int gcre_score_sets_subsample(gcre_ctx* ctx, const gcre_set_input* in, int32_t m_cases, int32_t m_ctrls, int64_t draws,
+                              uint64_t seed, const double* table_a, int nrow_a, int ncol_a, const double* table_b, int nrow_b,
+                              int ncol_b, const double* cut, int32_t n_cut, gcre_set_score* out, int64_t cap, int64_t* n_out,
+                              int64_t* n_a, int64_t* n_b, int64_t* n_both, double* scores_a, double* scores_b);
+/* k_table_to_diag / k_subsample_masks / k_subsample_null launches of gcre_score_sets_subsample on the context since
+ * gcre_create -- one per table, then two per slab of draws (no other launch counter counts them, nor the reverse); -1 for a
+ * NULL context. */
+int64_t gcre_subsample_launches(const gcre_ctx* ctx);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Carrier overlaps of caller-given sets: which sets are carried by the same patients.  No reference
  * counterpart.
