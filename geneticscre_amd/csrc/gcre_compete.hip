@@ -6,7 +6,7 @@
 //                     picked gene rows over the patients, 16 bytes a lane so that a wave-load is a contiguous 1 KB of one
 //                     row, eight rows' loads in flight; AND with the case / control bits (computed, not loaded), popcount,
 //                     wave reduction, the look-up in the f64 table k_set_observed reads, in its order of the addition.
-// No LDS; every global write is a vector store or a vector atomic.  The context-side entry is in gcre_host_stats.hip.
+// No LDS; every global write is a vector store or a vector atomic.  The context-side entry is in gcre_host_compete.hip.
 #include "gcre_kernels.h"
 #include "gcre_compete.h"
 

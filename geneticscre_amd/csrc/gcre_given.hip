@@ -2,7 +2,7 @@
 //   * k_set_residual  per (set, given set) pair: the set's (+) and (-) unions with every carrier of the given set taken
 //                     out, written in k_set_null's row layout, and the counts SetUnion::build (gcre_setlists.h) gives
 // The rows are scored by the kernels of gcre_sets.hip in later launches on the same stream; the context-side entry is in
-// gcre_host_stats.hip.
+// gcre_host_sets.hip.
 //
 // k_clump_union's mapping (gcre_clump.hip): one wave per entry, lanes stride over the dwords of a row, every member's
 // dword is one coalesced vector load.  The set list is read as the caller gave it (CSR), so a lane walks the members of

@@ -1,8 +1,10 @@
 // gcre_host.h -- private to the host side of libgcre_hip.so: the state behind the handles of include/gcre_hip.h and the
-// few helpers that its three translation units share.  gcre_host.hip holds the join driver and everything that feeds it,
-// gcre_host_stats.hip the entry points that only use a context (set statistics, decorated p-values, the gene tally and the
-// exceedance counts as objects), gcre_host_pipeline.hip the one-call pipeline on one device and on several (and with it
-// everything of RCCL).  Nothing here is part of the ABI.
+// few helpers that its translation units share.  gcre_host.hip holds the join driver and everything that feeds it,
+// gcre_host_sets.hip the set scores and their driver (gcre_set_stage.h), with one file per stage behind them
+// (gcre_host_family.hip, _minp, _compete, _prefix, _subsample), gcre_host_stats.hip the other entry points that only use a
+// context (decorated p-values, overlaps, clumps, tallies, burden tests, the gene tally, the exceedance counts and the hit lists
+// as objects), gcre_host_pipeline.hip the one-call pipeline on one device and on several (and with it everything of RCCL).
+// Nothing here is part of the ABI.
 #pragma once
 #include "../../include/gcre_hip.h"
 #include "gcre_kernels.h"

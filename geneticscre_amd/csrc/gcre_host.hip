@@ -3,8 +3,8 @@
 // reference src/join_base.cpp:189-264).  The state behind the handles is in gcre_host.h; the top-k merge (merge_scores /
 // format_result, methods.h:25-39, join_base.cpp:138-154) is in gcre_pipeline.h, the ProcessPaths sequence
 // (src/wrapper.cpp:216-276) on one device and on several in gcre_host_pipeline.hip; the entry points that do not touch the
-// join driver -- generated permutation masks, decorated p-values, set scores and overlaps, the gene tally and the
-// exceedance counts as objects -- are in gcre_host_stats.hip.
+// join driver are in gcre_host_sets.hip and the stage files beside it (set scores) and in gcre_host_stats.hip (generated
+// permutation masks, decorated p-values, overlaps, the gene tally and the exceedance counts as objects).
 //
 // There is no CPU fallback: without a gfx950 device gcre_create fails with GCRE_ERR_DEVICE.
 #include "gcre_host.h"

@@ -1,4 +1,4 @@
-// gcre_kernels.h -- launch interface between the host library (gcre_host.hip, gcre_host_stats.hip) and the gfx950 kernels
+// gcre_kernels.h -- launch interface between the host library (gcre_host.hip and the gcre_host_*.hip files beside it) and the gfx950 kernels
 // (gcre_kernels.hip).  Internal; the public boundary is include/gcre_hip.h.
 #pragma once
 

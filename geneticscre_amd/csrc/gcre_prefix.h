@@ -1,7 +1,7 @@
 // gcre_prefix.h -- the host plan of the variable-threshold set tests (gcre_score_sets_prefix), defined once:
 // the expansion of the cut flags into steps, what the entry refuses of its own arguments, the slabs of whole sets, the
 // size-sorted order of a slab's sets and the block table k_prefix_null reads.  Plain C++17 over include/gcre_hip.h, no HIP:
-// the host stage (gcre_host_stats.hip) includes it under hipcc and tests/native/prefix_main.cpp under plain g++.
+// the host stage (gcre_host_prefix.hip) includes it under hipcc and tests/native/prefix_main.cpp under plain g++.
 // tests/test_prefix_host.py restates it in Python.
 #pragma once
 #include "../../include/gcre_hip.h"

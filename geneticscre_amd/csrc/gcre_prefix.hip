@@ -8,7 +8,7 @@
 //                    the count of permutations whose maximum reaches the set's best observed score, and the
 //                    per-permutation maximum over the sets of the launch
 // The step rows are scored by k_set_observed (gcre_sets.hip) between the first two.  The context-side entry is in
-// gcre_host_stats.hip, the host plan (steps, slabs, block table) in gcre_prefix.h.
+// gcre_host_prefix.hip, the host plan (steps, slabs, block table) in gcre_prefix.h.
 //
 // k_prefix_rows is k_set_residual's mapping (gcre_given.hip), lanes over the dwords of a row, with one wave per set and
 // 64-dword stretch of the row: a wave's walk over the members is a chain of dependent loads, so the stretches of a row go to
@@ -112,7 +112,7 @@ __global__ __launch_bounds__(kPfxBlock) void k_prefix_rows(const PrefixArgs a) {
 }
 
 // The bit pattern of the smallest float x with (double)x >= score among the non-negative floats: f32_threshold of the host
-// stage (gcre_host_stats.hip)
+// side (gcre_threshold.h)
 __device__ __forceinline__ u32 pfx_threshold(double score) {
   if (score != score) return 0x7f800001u;
   if (score <= 0) return 0u;

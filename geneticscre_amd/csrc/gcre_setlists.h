@@ -1,4 +1,5 @@
-// gcre_setlists.h -- the host stage that gcre_score_sets, gcre_set_overlap and gcre_exceed_stepdown share (gcre_host_stats.hip):
+// gcre_setlists.h -- the host stage that gcre_score_sets (gcre_host_sets.hip), gcre_set_overlap and gcre_exceed_stepdown
+// (gcre_host_stats.hip) share:
 // what they refuse of a caller's set list, and the union rows and counts of one set.  Plain C++17 over include/gcre_hip.h, no
 // HIP: tests/native/setlists_main.cpp drives it on a machine without a GPU (given_main.cpp, patients_main.cpp and
 // burden_main.cpp: the argument checks of gcre_score_sets_given, gcre_set_patient_counts and gcre_patient_burden).

@@ -4,7 +4,7 @@
 //                     mask, the null score the join's kernels fold into their maxima (methods.h:96-103, :220-230), the
 //                     count of permutations whose null score reaches the set's observed score, and the per-permutation
 //                     maximum over the sets of the launch
-// The context-side entry, gcre_score_sets, is in gcre_host_stats.hip.  DESIGN.md §3.6.
+// The context-side entry, gcre_score_sets, is in gcre_host_sets.hip.  DESIGN.md §3.6.
 //
 // k_set_null is k_null's mapping (gcre_kernels.hip) with one operand row instead of two: lanes own permutations (8 per
 // lane), a set's words are wave-uniform (scalar loads), the mask tile goes through LDS and is shared by the block's four

@@ -9,7 +9,7 @@
 // (scalar loads), the mask tile goes through LDS and is shared by the block's four waves.  It keeps two accumulators per
 // half-row; which one a mask dword feeds is wave-uniform by its word index, so the chunks left of the one that holds patient
 // n_cases feed the cases, the chunks right of it the controls, and only in that chunk is a set word split by constant masks.
-// Every global write is a vector store or a vector atomic.  The context-side entry is in gcre_host_stats.hip.
+// Every global write is a vector store or a vector atomic.  The context-side entry is in gcre_host_subsample.hip.
 #include "gcre_kernels.h"
 #include "gcre_subsample.h"
 

@@ -1,6 +1,8 @@
 """Step-down, k-FWER and FDR over a family of given sets, host side: ``report.family_reference`` -- the
 definition of gcre_score_sets_family -- on a hand-worked example and against the definitions taken literally on random
-matrices; the consequences the header states; ``report.family_columns``; the interface.  No GPU needed."""
+matrices; the consequences the header states; ``report.family_columns``; the host plan in C++ (csrc/gcre_family.h), driven
+by tests/native/family_main.cpp under the address and undefined-behaviour sanitizers as a child process; the interface.  No
+GPU needed."""
 from __future__ import annotations
 
 import inspect
@@ -8,7 +10,9 @@ import os
 import re
 
 import numpy as np
+import pytest
 
+import family_native
 from geneticscre_amd import api, report
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -151,6 +155,107 @@ def test_family_columns_monotone_on_random_families():
         assert (np.diff(qq) >= 0).all(), case
         same = np.flatnonzero(np.diff(obs[order]) == 0)
         assert (sdp[same] == sdp[same + 1]).all()                                # tied scores, equal values
+
+
+# ---- the host plan in C++ (csrc/gcre_family.h), under the sanitizers ---------------------------------------------------
+TOP = 0x80000000
+SLAB_REFUSAL = "score_sets_family: the null scores of 3 sets under one tile of 512 permutations exceed GCRE_FAMILY_MAX_MB"
+
+
+@pytest.fixture(scope="module")
+def prog(tmp_path_factory):
+    return family_native.build_prog(tmp_path_factory.mktemp("family"))
+
+
+def _walk(out):
+    """The seven lines a `family` command prints first."""
+    assert out[0].split()[0] == "family"
+    return {"m": int(out[0].split()[1]), **{k: family_native.ints(out[1 + i], k)
+                                            for i, k in enumerate(("order", "rank", "meta", "gstart", "bin", "pat"))}}
+
+
+def test_native_hand_worked_walk_and_finish(prog, tmp_path):
+    vset = np.flatnonzero(VALID).tolist()
+    obs = OBS[vset].tolist()                                   # 3.0, 1.0, 1.0, NaN
+    order, sd, pat, hist = family_native.family_device_part(obs, NULL[vset])
+    assert (order, sd, pat, hist) == ([3, 1, 2, 0], [0, 0, 4, 2], [0x3F800000, 0x40400000], [4, 3])
+    out = family_native.run_case(prog, tmp_path, [("n_sets", 5), ("vset", vset), ("obs", obs), ("sd", [0, 0, 4, 2]), ("hist", [4, 3]),
+                                                  ("family", [])])
+    w = _walk(out)
+    assert w["m"] == 2 and w["order"] == [3, 1, 2, 0] and w["rank"] == [3, 1, 2, 0]
+    assert len(w["meta"]) == 64 and not any(w["meta"][4:])
+    assert [x >> 31 for x in w["meta"][:4]] == [1, 0, 1, 1]                        # tie groups end at rows 0, 2, 3
+    assert [x & ~TOP for x in w["meta"][:4]] == [0x7F800001, 0x3F800000, 0x3F800000, 0x40400000]
+    assert w["gstart"] == [0, 1, 1, 3] and w["bin"] == [-1, 0, 0, 1] and w["pat"] == [0x3F800000, 0x40400000]
+    rec = np.array(family_native.ints(out[7], "records")).reshape(5, 3)
+    assert rec[:, 0].tolist() == SD and rec[:, 1].tolist() == EXCEED and rec[:, 2].tolist() == OBSERVED
+
+
+def test_native_walk_edges(prog, tmp_path):
+    w = _walk(family_native.run_case(prog, tmp_path, [("n_sets", 1), ("vset", [0]), ("obs", [2.5]), ("family", [])]))
+    assert w["order"] == [0] and w["rank"] == [0] and w["gstart"] == [0] and w["bin"] == [0] and w["m"] == 1
+    assert len(w["meta"]) == 64 and w["meta"][0] == TOP | 0x40200000 and w["pat"] == [0x40200000]
+    # every score NaN: no bin, no pattern but the one placeholder, every row ends a group that counts nothing
+    out = family_native.run_case(prog, tmp_path, [("n_sets", 3), ("vset", [0, 1, 2]), ("obs", [NAN, NAN, NAN]), ("sd", [0, 0, 0]),
+                                                  ("hist", [0]), ("family", [])])
+    w = _walk(out)
+    assert w["m"] == 0 and w["pat"] == [0] and w["bin"] == [-1, -1, -1] and w["order"] == [0, 1, 2]
+    assert w["meta"][:3] == [TOP | 0x7F800001] * 3
+    assert family_native.ints(out[7], "records") == [0, 0, 0] * 3
+    # +0.0 against -0.0: one tie group, one pattern
+    w = _walk(family_native.run_case(prog, tmp_path, [("n_sets", 2), ("vset", [0, 1]), ("obs", [0.0, -0.0]), ("family", [])]))
+    assert w["order"] == [0, 1] and w["meta"][:2] == [0, TOP] and w["gstart"] == [0, 0] and w["bin"] == [0, 0] and w["pat"] == [0]
+    # the padding of meta: whole 64 rows
+    for V, padded in ((64, 64), (65, 128)):
+        obs = [float(v % 7) for v in range(V)]
+        w = _walk(family_native.run_case(prog, tmp_path, [("n_sets", V), ("vset", list(range(V))), ("obs", obs), ("family", [])]))
+        assert len(w["meta"]) == padded and not any(w["meta"][V:]) and w["meta"][V - 1] >> 31 == 1
+        assert sorted(w["order"]) == list(range(V)) and [w["rank"][v] for v in w["order"]] == list(range(V))
+        assert w["order"] == family_native.family_walk(obs)[0] and w["m"] == 7
+    assert [family_native.ints(line, "thr")[0] for line in family_native.run_case(
+        prog, tmp_path, [("thr", 1.0), ("thr", 1.0 + 1e-12), ("thr", -0.0), ("thr", NAN), ("thr", float("inf"))])] == [
+            0x3F800000, 0x3F800001, 0, 0x7F800001, 0x7F800000] == [family_native.f32_threshold(x) for x in (1.0, 1.0 + 1e-12, -0.0, NAN,
+                                                                                                             float("inf"))]
+
+
+def test_native_slab_sizing(prog, tmp_path):
+    one_tile = 3 * family_native.TILE * 4 / 1048576.0          # three rows of one tile, in MB: exact in binary
+    below = float(np.nextafter(one_tile, 0.0))
+    asks = [((3, 2000, 512, one_tile, 0), "family_slab 0 1 "),((3, 2000, 512, below, 0), f"family_slab -4 0 {SLAB_REFUSAL}"),
+            ((3, 2000, 512, 1024.0, 0), "family_slab 0 4 "), ((3, 2000, 512, 1024.0, 1), "family_slab 0 1 "),
+            ((3, 2000, 512, 1024.0, 1023), "family_slab 0 1 "), ((3, 2000, 512, 1024.0, 1024), "family_slab 0 2 "),
+            ((3, 2000, 512, 2 * one_tile, 0), "family_slab 0 2 "), ((0, 2000, 512, below, 0), "family_slab 0 0 "),
+            ((3, 0, 512, below, 0), "family_slab 0 0 ")]
+    assert family_native.run_case(prog, tmp_path, [("family_slab", a) for a, _ in asks]) == [w for _, w in asks]
+    env = {k: v for k, v in os.environ.items() if not k.startswith("GCRE_")}
+    assert family_native.run_case(prog, tmp_path, [("env", [])], env=env) == ["env 1024 0 1024 0"]
+    for perms, want in (("0", 1), ("-5", 1), ("700", 700)):       # the test-only bound: one permutation at the least, so one tile
+        out = family_native.run_case(prog, tmp_path, [("env", [])], env={**env, "GCRE_FAMILY_SLAB_PERMS": perms, "GCRE_FAMILY_MAX_MB": "0.25"})
+        assert out == [f"env 0.25 {want} 1024 0"]
+    assert family_native.run_case(prog, tmp_path, [("env", [])], env={**env, "GCRE_FAMILY_MAX_MB": "-3"}) == ["env 0 0 1024 0"]
+    assert family_native.run_case(prog, tmp_path, [("env", [])], env={**env, "GCRE_FAMILY_MAX_MB": "1e9"}) == ["env 1048576 0 1024 0"]
+
+
+def test_native_finish_on_random_families(prog, tmp_path):
+    """The device's part taken literally from a null matrix, the native walk and finish, every field against the reference."""
+    rng = np.random.default_rng(318)
+    case, want = [], []
+    for _ in range(200):
+        S, K = int(rng.integers(1, 41)), int(rng.integers(1, 51))
+        obs, valid, null = _random_family(rng, S, K)
+        vset = np.flatnonzero(valid).tolist()
+        order, sd, pat, hist = family_native.family_device_part(obs[vset].tolist(), null[vset])
+        case += [("n_sets", S), ("vset", vset), ("obs", obs[vset].tolist()), ("sd", sd), ("hist", hist), ("family", [])]
+        want.append((order, pat, report.family_reference(obs, valid, null)))
+    out = family_native.run_case(prog, tmp_path, case)
+    assert len(out) == 8 * len(want)
+    for i, (order, pat, ref) in enumerate(want):
+        w = _walk(out[8 * i:8 * i + 7])
+        assert w["order"] == order and w["m"] == len(pat) and w["pat"] == (pat or [0]), i
+        rec = np.array(family_native.ints(out[8 * i + 7], "records"), dtype=object).reshape(-1, 3)
+        assert rec[:, 0].tolist() == ref["n_ge_stepdown"].tolist(), i
+        assert rec[:, 1].tolist() == ref["exceed"].tolist(), i
+        assert rec[:, 2].tolist() == ref["observed"].tolist(), i
 
 
 # ---- the interface ---------------------------------------------------------------------------------------------------

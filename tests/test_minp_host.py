@@ -1,7 +1,8 @@
 """Westfall-Young min-P over a family of given sets (gcre_score_sets_minp), the parts that need no device:
 ``report.minp_reference`` -- the contract every device test compares against -- on a hand-worked example and against the
-definitions taken literally, the consequences the definitions have, ``report.minp_columns``, and the interface (header,
-ctypes mirror, ``score_paths``)."""
+definitions taken literally, the consequences the definitions have, ``report.minp_columns``, the host plan in C++
+(csrc/gcre_minp.h: slab sizing, walk order, finish), driven by tests/native/family_main.cpp under the address and
+undefined-behaviour sanitizers as a child process, and the interface (header, ctypes mirror, ``score_paths``)."""
 from __future__ import annotations
 
 import inspect
@@ -11,6 +12,7 @@ import re
 import numpy as np
 import pytest
 
+import family_native
 from geneticscre_amd import api, report
 
 NAN = float("nan")
@@ -150,6 +152,95 @@ def test_no_valid_set_and_no_permutation():
     ref = report.minp_reference([1.0, NAN, 2.0], [1, 1, 0], np.zeros((3, 0), np.float32))
     assert ref["n_le_minp"].tolist() == ref["n_le_stepdown"].tolist() == [0, 0, -1]
     assert ref["min_count"].shape == (0,) and ref["counts"].shape == (3, 0) and ref["n_ge"].tolist() == [0, 0, 0]
+
+
+# ---- the host plan in C++ (csrc/gcre_minp.h), driven by tests/native/family_main.cpp under the sanitizers -------------
+TOP = 0x80000000
+SLAB_REFUSAL = "score_sets_minp: the null scores and counts of one set under 2 tiles of 512 permutations exceed GCRE_MINP_MAX_MB"
+
+
+@pytest.fixture(scope="module")
+def prog(tmp_path_factory):
+    return family_native.build_prog(tmp_path_factory.mktemp("minp"))
+
+
+def test_native_worked_example(prog, tmp_path):
+    vset = np.flatnonzero(EX_VALID).tolist()
+    obs = EX_OBS[vset].tolist()
+    order, ge, le, q = family_native.minp_device_part(obs, EX_NULL[vset])
+    assert (order, ge, le, q) == ([3, 0, 1, 2], [2, 2, 1, 0], [0, 0, 4, 2], [2, 2, 1, 3, 2, 1])
+    out = family_native.run_case(prog, tmp_path, [("n_sets", 5), ("vset", vset), ("obs", obs), ("ge", ge), ("le", le), ("q", q), ("minp", [])])
+    assert out[0] == "minp" and family_native.ints(out[1], "order") == order
+    # the NaN score first and never the end of a group; sets 0 and 1 tie in c: their group ends at the second
+    assert family_native.ints(out[2], "meta") == [0, 2, TOP | 2, TOP | 1]
+    rec = np.array(family_native.ints(out[3], "records")).reshape(5, 2)
+    assert rec[:, 0].tolist() == [5, 5, 2, 0, -1] and rec[:, 1].tolist() == [4, 4, 2, 0, -1]
+
+
+def test_native_walk_and_finish_edges(prog, tmp_path):
+    # NaN-scored sets first, in input order, none ending a group -- not even as the last row of the walk
+    out = family_native.run_case(prog, tmp_path, [("n_sets", 2), ("vset", [0, 1]), ("obs", [NAN, NAN]), ("ge", [0, 0]), ("le", [0, 0]),
+                                                  ("q", [1, 1]), ("minp", [])])
+    assert family_native.ints(out[1], "order") == [0, 1] and family_native.ints(out[2], "meta") == [0, 0]
+    assert family_native.ints(out[3], "records") == [0, 0, 0, 0]
+    # ties in c among scored sets, stable; the last row of the walk inside a tie group: its count goes to the whole group
+    obs, ge = [1.0, NAN, 2.0, 3.0, 4.0], [3, 0, 7, 3, 3]
+    out = family_native.run_case(prog, tmp_path, [("n_sets", 6), ("vset", [0, 1, 2, 4, 5]), ("obs", obs), ("ge", ge), ("le", [0, 2, 0, 0, 5]),
+                                                  ("q", [9, 2, 4, 4]), ("minp", [])])
+    assert family_native.ints(out[1], "order") == [1, 2, 0, 3, 4] == family_native.minp_walk(obs, ge)[0]
+    assert family_native.ints(out[2], "meta") == [0, TOP | 7, 3, 3, TOP | 3]
+    # n_le_minp against the sorted minima 2 4 4 9: c = 3 between them, c = 7 too; the invalid set 3 keeps -1 / -1
+    assert family_native.ints(out[3], "records") == [1, 5, 0, 0, 3, 2, -1, -1, 1, 5, 1, 5]
+    # c equal to, below and above every minimum
+    out = family_native.run_case(prog, tmp_path, [("n_sets", 4), ("vset", [0, 1, 2, 3]), ("obs", [1.0, 1.0, 1.0, 1.0]), ("ge", [4, 1, 9, 2]),
+                                                  ("le", [3, 2, 1, 0]), ("q", [4, 2, 4]), ("minp", [])])
+    assert family_native.ints(out[1], "order") == [2, 0, 3, 1]
+    assert family_native.ints(out[3], "records") == [3, 2, 0, 0, 3, 3, 1, 1]
+    # one set
+    out = family_native.run_case(prog, tmp_path, [("n_sets", 1), ("vset", [0]), ("obs", [0.5]), ("ge", [0]), ("le", [0]), ("q", [1]), ("minp", [])])
+    assert family_native.ints(out[2], "meta") == [TOP] and family_native.ints(out[3], "records") == [0, 0]
+
+
+def test_native_slab_sizing(prog, tmp_path):
+    one_row = 2 * family_native.TILE * 8 / 1048576.0           # 1000 permutations: two tiles, 8 bytes a column, in MB: exact in binary
+    below = float(np.nextafter(one_row, 0.0))
+    asks = [((5, 1000, 512, one_row, 0), "minp_slab 0 1 "), ((5, 1000, 512, below, 0), f"minp_slab -4 0 {SLAB_REFUSAL}"),
+            ((5, 1000, 512, 1024.0, 0), "minp_slab 0 5 "), ((5, 1000, 512, 1024.0, 1), "minp_slab 0 1 "),
+            ((5, 1000, 512, 1024.0, 7), "minp_slab 0 5 "), ((5, 1000, 512, 3 * one_row, 0), "minp_slab 0 3 "),
+            ((0, 1000, 512, below, 0), "minp_slab 0 0 "), ((5, 0, 512, below, 0), "minp_slab 0 0 ")]
+    assert family_native.run_case(prog, tmp_path, [("minp_slab", a) for a, _ in asks]) == [w for _, w in asks]
+    env = {k: v for k, v in os.environ.items() if not k.startswith("GCRE_")}
+    for sets, want in (("0", 1), ("-2", 1), ("3", 3)):            # the test-only bound: one row at the least
+        out = family_native.run_case(prog, tmp_path, [("env", [])], env={**env, "GCRE_MINP_SLAB_SETS": sets, "GCRE_MINP_MAX_MB": "0.5"})
+        assert out == [f"env 1024 0 0.5 {want}"]
+    assert family_native.run_case(prog, tmp_path, [("env", [])], env={**env, "GCRE_MINP_MAX_MB": "-1"}) == ["env 1024 0 0 0"]
+    assert family_native.run_case(prog, tmp_path, [("env", [])], env={**env, "GCRE_MINP_MAX_MB": "2e6"}) == ["env 1024 0 1048576 0"]
+
+
+def test_native_finish_on_random_families(prog, tmp_path):
+    """The device's part taken literally from a null matrix, the native walk and finish, every field against the reference."""
+    rng = np.random.default_rng(319)
+    levels = np.array([0.0, 0.5, 1.0, 2.5, np.inf], np.float32)
+    case, want = [], []
+    for _ in range(200):
+        S, K = int(rng.integers(1, 41)), int(rng.integers(1, 51))
+        null = rng.choice(levels[:int(rng.integers(1, 6))], size=(S, K)).astype(np.float32)
+        obs = rng.choice(np.array([0.0, 0.25, 0.5, 1.0, 2.5, 3.0, np.inf, NAN]), size=S)
+        valid = (rng.random(S) < 0.85).astype(np.int32)
+        null[valid == 0] = NAN
+        vset = np.flatnonzero(valid).tolist()
+        order, ge, le, q = family_native.minp_device_part(obs[vset].tolist(), null[vset])
+        ref = report.minp_reference(obs, valid, null)
+        assert ref["n_ge"][vset].tolist() == ge and (not vset or ref["min_count"].tolist() == q)
+        case += [("n_sets", S), ("vset", vset), ("obs", obs[vset].tolist()), ("ge", ge), ("le", le), ("q", q), ("minp", [])]
+        want.append((order, ref))
+    out = family_native.run_case(prog, tmp_path, case)
+    assert len(out) == 4 * len(want)
+    for i, (order, ref) in enumerate(want):
+        assert family_native.ints(out[4 * i + 1], "order") == order, i
+        rec = np.array(family_native.ints(out[4 * i + 3], "records")).reshape(-1, 2)
+        assert rec[:, 0].tolist() == ref["n_le_minp"].tolist(), i
+        assert rec[:, 1].tolist() == ref["n_le_stepdown"].tolist(), i
 
 
 def test_the_interface():
