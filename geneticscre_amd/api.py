@@ -122,6 +122,11 @@ MINP_SCORE = np.dtype([("n_le_minp", "<i8"), ("n_le_stepdown", "<i8")], align=Tr
 # gcre_prefix_score
 PREFIX_SCORE = np.dtype([("score", "<f8"), ("n_ge", "<i8"), ("best_step", "<i4"), ("best_members", "<i4"), ("steps", "<i4"),
                          ("cases_pos", "<i4"), ("ctrls_pos", "<i4"), ("cases_neg", "<i4"), ("ctrls_neg", "<i4")], align=True)
+# gcre_dose_score
+DOSE_SCORE = np.dtype([("score", "<f8"), ("n_ge", "<i8"), ("best_index", "<i4"), ("best_level", "<i4"), ("levels", "<i4"),
+                       ("cases_pos", "<i4"), ("ctrls_pos", "<i4"), ("cases_neg", "<i4"), ("ctrls_neg", "<i4"), ("pad", "<i4")],
+                      align=True)
+DOSE_MAX_LEVEL = 15   # GCRE_DOSE_MAX_LEVEL
 # gcre_burden
 BURDEN = np.dtype([("total", "<i8"), ("observed", "<i8"), ("n_ge", "<i8"), ("n_le", "<i8"), ("planes", "<i4"),
                    ("p_upper", "<f8"), ("p_lower", "<f8")], align=True)
@@ -146,6 +151,7 @@ EXPORTS = [
     "gcre_score_sets_compete", "gcre_compete_launches",
     "gcre_score_sets_prefix", "gcre_prefix_launches",
     "gcre_score_sets_subsample", "gcre_subsample_launches",
+    "gcre_score_sets_dose", "gcre_dose_launches",
     "gcre_set_overlap", "gcre_overlap_launches",
     "gcre_clump_sets", "gcre_clump_launches",
     "gcre_set_patient_counts", "gcre_patient_launches",
@@ -289,6 +295,9 @@ _FEATURES = {
         "gcre_score_sets_subsample": (_I, [_V, ctypes.POINTER(gcre_set_input), _I32, _I32, _I64, ctypes.c_uint64, _P, _I, _I, _P, _I, _I,
                                            _P, _I32, _P, _I64, ctypes.POINTER(_I64), _P, _P, _P, _P, _P]),
         "gcre_subsample_launches": (_I64, [_V])}),
+    "dose": ("sets", ["gcre_score_sets_dose", "gcre_dose_launches"], "multi-hit set tests (gcre_score_sets_dose)", {
+        "gcre_score_sets_dose": (_I, [_V, ctypes.POINTER(gcre_set_input), _P, _I32, _P, _I64, ctypes.POINTER(_I64), _P, _P, _P, _P]),
+        "gcre_dose_launches": (_I64, [_V])}),
     "overlap": (None, ["gcre_set_overlap"], "carrier overlaps (gcre_set_overlap)", {
         "gcre_set_overlap": (_I, [_V, ctypes.POINTER(gcre_set_input), _P, _I64, _P, _I64, _P, _P]),
         "gcre_overlap_launches": (_I64, [_V])}),
@@ -356,6 +365,7 @@ _minp_lib = functools.partial(_feature_lib, "minp")
 _compete_lib = functools.partial(_feature_lib, "compete")
 _prefix_lib = functools.partial(_feature_lib, "prefix")
 _subsample_lib = functools.partial(_feature_lib, "subsample")
+_dose_lib = functools.partial(_feature_lib, "dose")
 _overlap_lib = functools.partial(_feature_lib, "overlap")
 _clump_lib = functools.partial(_feature_lib, "clump")
 _patients_lib = functools.partial(_feature_lib, "patients")
@@ -675,6 +685,21 @@ def _set_lists(sets, signs):
     if not matching:
         raise ValueError("signs: one sign per member of every set")
     return len(off) - 1, off, members, sg
+
+
+def _dose_levels(levels) -> np.ndarray:
+    """``levels`` of ``dose_tests`` as int32: 1 to 15 strictly ascending integers in 1 .. 15, or ValueError."""
+    a = np.asarray(levels)
+    if a.ndim != 1 or not 1 <= a.size <= DOSE_MAX_LEVEL:
+        raise ValueError(f"levels: 1 to {DOSE_MAX_LEVEL} levels, one list")
+    lv = a.astype(np.int64)
+    if not np.array_equal(lv, a):
+        raise ValueError("levels: whole numbers")
+    if lv.min() < 1 or lv.max() > DOSE_MAX_LEVEL:
+        raise ValueError(f"levels: every level in 1 .. {DOSE_MAX_LEVEL}")
+    if (np.diff(lv) <= 0).any():
+        raise ValueError("levels: strictly ascending")
+    return np.ascontiguousarray(lv, dtype=np.int32)
 
 
 def pack_carriers(rows, n_cols: int) -> np.ndarray:
@@ -1222,6 +1247,45 @@ class JoinExec:
         n = n_out.value
         counts = {k: None if c is None else c[:n] for k, c in zip(("n_a", "n_b", "n_both"), cnt)}
         return (out[:n], counts) + ((sc[0], sc[1]) if scores else ())
+
+    def dose_tests(self, sets, rows, signs=None, levels=(1, 2), family: bool = False, null: bool = False,
+                   level_scores: bool = False):
+        """Multi-hit tests of the given sets (gcre_score_sets_dose): per set and per level m of ``levels`` the
+        row "patients who carry at least m of the set's members" is scored, the best level is the statistic, and the same
+        maximum is taken under every permutation.  ``sets`` / ``rows`` / ``signs`` as ``score_sets`` takes them (lists per set,
+        or an ``(off, members)`` pair with flat signs); ``levels``: 1 to 15 strictly ascending integers in 1 .. 15, the same
+        for every set.  Method 1 counts all members whatever their signs (a member listed twice counts twice); method 2
+        counts the (+) and the (-) members apart, into the two halves of the row.  Level 1 is the set's union.  Returns
+        ``(records, dose)``: the SET_SCORE records of ``score_sets`` for the full sets, and one DOSE_SCORE record per set --
+        ``score`` the best level's observed score, ``best_index`` / ``best_level`` which level that is (the smallest that
+        attains the maximum), ``levels``, its four counts, and ``n_ge`` the permutations whose maximum over the levels
+        reaches ``score`` (-1 for an NA member).  With ``family`` also float32 [iters], per permutation the maximum over the
+        sets; with ``null`` also float32 [sets][iters], the maximum over every set's levels (NaN rows for sets with an NA
+        member); with ``level_scores`` also float64 [sets][levels], the observed score of every level row (NaN rows
+        likewise).  ``report.dose_sets`` restates the level rows in numpy; ``report.pair_sets`` with ``levels=[2]`` screens
+        gene pairs.  The levels must not be chosen from the labels.  Bad ``levels`` raise ValueError, errors of the library
+        GcreError."""
+        S, off, members, sg = _set_lists(sets, signs)
+        lv = _dose_levels(levels)
+        lib = _dose_lib()
+        inp, keep = _set_input((off, members), rows, sg, self.num_cases + self.num_ctrls)
+        L = len(lv)
+        out = np.zeros(max(S, 1), dtype=SET_SCORE)
+        ds = np.zeros(max(S, 1), dtype=DOSE_SCORE)
+        fam = np.zeros(self.iters, dtype=np.float32) if family else None
+        nul = np.full((S, self.iters), np.nan, dtype=np.float32) if null else None
+        lsc = np.full((S, L), np.nan, dtype=np.float64) if level_scores else None
+        n_out = ctypes.c_int64(0)
+        self._check_gcre(lib.gcre_score_sets_dose(self._h, ctypes.byref(inp), _ptr(lv), L, _ptr(out), len(out), ctypes.byref(n_out),
+                                                  _ptr(ds), _ptr(fam) if family and fam.size else None,
+                                                  _ptr(nul) if null and nul.size else None,
+                                                  _ptr(lsc) if level_scores and lsc.size else None))
+        res = (out[:n_out.value], ds[:n_out.value])
+        return res + ((fam,) if family else ()) + ((nul,) if null else ()) + ((lsc,) if level_scores else ())
+
+    def dose_launches(self) -> int:
+        """Kernels ``dose_tests`` launched for its own stage on this context so far."""
+        return int(_dose_lib().gcre_dose_launches(self._h))
 
     def subsample_launches(self) -> int:
         """Kernels ``subsample_tests`` launched for its own stage on this context so far: one per table, two per slab."""

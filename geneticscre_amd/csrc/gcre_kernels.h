@@ -730,6 +730,27 @@ hipError_t launch_prefix_rows(const PrefixArgs& a, int method, hipStream_t strea
 hipError_t launch_prefix_pick(const PrefixArgs& a, int method, hipStream_t stream);
 hipError_t launch_prefix_null(const PrefixArgs& a, int method, hipStream_t stream);
 
+// ---- multi-hit set tests: the patients who carry at least m members of a set (gcre_dose.hip) ----
+// k_dose_rows builds what k_prefix_rows builds -- the rows and counts of a PrefixArgs slab -- from a per-patient count of the
+// set's members: row row0[e] + l of slot e is "carries at least level l of the set's members".  The rest of the slab's walk
+// is the prefix stage's own (k_set_observed, k_prefix_pick, k_prefix_null).
+struct DoseArgs {
+  const uint32_t* gene_rows;    // [n_rows][W2] the caller's gene rows as dwords (bits beyond the patients are ignored)
+  const int64_t* set_off;       // [n_sets + 1] the caller's set list as it is
+  const int32_t* members;       // rows of every set; none of a launched set is NA
+  const int32_t* signs;         // per member +1 / -1, or nullptr = all +1 (read by method 2)
+  const int64_t* which;         // [nslots] the set of every slot
+  uint32_t* rows;               // [nslots * n_levels][M][W32p] level rows: (+) half, then (-) half (method 2); zero beyond the patients
+  int32_t* cnt;                 // [nslots * n_levels][4] cases_pos, ctrls_pos, cases_neg, ctrls_neg; zero on entry (the kernel adds)
+  uint64_t levels;              // level l in bits [4 l, 4 l + 4): 1 .. 15, ascending
+  int64_t nslots;
+  int n_levels;                 // 1 .. 15
+  int W2;                       // dwords per gene row
+  int W32p;
+  int n_patients, n_cases;
+};
+hipError_t launch_dose_rows(const DoseArgs& a, int method, hipStream_t stream);
+
 // ---- carrier-overlap counts of caller-given sets (gcre_overlap.hip) ----
 constexpr int kOverlapTile = 64;    // pairs per edge of a block's tile
 constexpr int kOverlapChunk = 32;   // dwords of a row per staged chunk (128 bytes): rows are padded to a multiple of it

@@ -1066,6 +1066,118 @@ def variable_threshold_test(sets, genes: Sequence[str], data: np.ndarray, n_case
     return pd.DataFrame(cols, columns=VARIABLE_THRESHOLD_COLUMNS)
 
 
+MULTI_HIT_COLUMNS = ["Sets", "Genes", "Scores", "NominalPvalues", "BestLevel", "BestCases", "BestControls", "MultiHitScores",
+                     "MultiHitPvalues", "MultiHitFamilyPvalues"]
+
+
+def dose_sets(sets, rows, signs, levels, signed):
+    """The level rows of ``JoinExec.dose_tests`` written out in numpy as synthetic "genes", and the sets that score them
+    (DESIGN.md §3.20): ``(level_rows, level_sets, level_signs, owner)``.  Per set and per level m of ``levels``, in that
+    order: without ``signed`` (method 1) one row, the patients who carry at least m of the set's listed members -- the signs
+    are ignored and a member listed twice counts twice -- and the one-member set of that row; with ``signed`` (method 2) two
+    rows, the same count over the (+) members and over the (-) members of ``signs`` (None: all (+)), and the two-member set
+    of the (+) row with sign +1 and the (-) row with sign -1.  ``level_rows`` int8 [rows made][patients] over all the columns
+    of ``rows``; ``owner`` int64 [level sets] names the set of every level set.  A set with an NA member (-1) has no rows:
+    its level sets hold -1 and are scored by nobody.  ``sets`` / ``signs`` in either form the set entries take.
+    ``score_sets`` and ``family_tests(null=True)`` on ``level_sets``, folded by ``prefix_reference``, are what the call returns."""
+    lists, sg = _set_lists(sets, signs)
+    d = np.asarray(rows) != 0
+    if d.ndim != 2:
+        raise ValueError("dose_sets: rows is a 0/1 matrix [rows][patients]")
+    lv = [int(m) for m in levels]
+    n = d.shape[1]
+    made, level_sets, level_signs, owner = [], [], [], []
+    for s, m in enumerate(lists):
+        valid = all(r >= 0 for r in m)
+        if valid:
+            g = np.ones(len(m), bool) if not signed or sg is None else np.asarray(sg[s]) != -1
+            mem = np.asarray(m, np.int64)
+            pos = d[mem[g]].sum(axis=0, dtype=np.int64) if g.any() else np.zeros(n, np.int64)
+            neg = d[mem[~g]].sum(axis=0, dtype=np.int64) if (~g).any() else np.zeros(n, np.int64)
+        for level in lv:
+            if not valid:
+                level_sets.append([-1, -1] if signed else [-1])
+            else:
+                level_sets.append([len(made), len(made) + 1] if signed else [len(made)])
+                made.append(pos >= level)
+                if signed:
+                    made.append(neg >= level)
+            level_signs.append([1, -1] if signed else [1])
+            owner.append(s)
+    level_rows = np.array(made, np.int8).reshape(len(made), n)
+    return level_rows, level_sets, level_signs, np.asarray(owner, np.int64)
+
+
+def pair_sets(rows):
+    """All unordered pairs of the gene rows ``rows`` as two-member sets, in the order (0,1), (0,2), .., (1,2), ..: digenic
+    screening is ``dose_tests(pair_sets(g), data, levels=[2], family=True)`` -- the patients who carry both genes."""
+    g = [int(r) for r in rows]
+    return [[g[i], g[j]] for i in range(len(g)) for j in range(i + 1, len(g))]
+
+
+def multi_hit_test(sets, genes: Sequence[str], data: np.ndarray, n_cases: int, n_ctrls: int, signed: bool = False,
+                   names=None, levels=(1, 2, 3), threshold: float = 0.05, n_permutations: int = 100,
+                   strata: Optional[Sequence[int]] = None, seed: int = 0, device: int = 0):
+    """Multi-hit test of gene sets the caller names (``JoinExec.dose_tests``).  Every other set statistic
+    scores a set's union, where a patient with a variant in one gene of a pathway and a patient with variants in four count
+    the same; here, per level m of ``levels``, the patients who carry at least m of the set's genes are scored, the best
+    level is the statistic, and the same maximum is taken under every permutation.  ``sets`` as ``parse_sets`` reads them;
+    genes are looked up after ``preprocess_table(threshold)``; a gene named twice in a set is kept once (its first sign);
+    ``names``: one per set.  With ``signed`` the (+) and the (-) genes are counted apart.  The masks are
+    ``generate_permutations(seed, strata)``'s.  The levels must not be chosen from the labels.
+
+    One row per set, MULTI_HIT_COLUMNS: ``Genes`` the set's distinct genes; ``Scores`` / ``NominalPvalues`` of the full
+    union, as ``score_paths`` gives them; ``BestLevel`` the best level and ``BestCases`` / ``BestControls`` the cases and
+    controls of its (+) row; ``MultiHitScores`` its score; ``MultiHitPvalues`` = n_ge / permutations, a self-contained
+    permutation p-value of the maximum over the levels, one set at a time; ``MultiHitFamilyPvalues`` single-step max-T of
+    that statistic over the call's sets.  NaN for a set with a gene not found, a NaN score and 0 permutations."""
+    import pandas as pd
+    from . import api
+    genes, data = preprocess_table(genes, data, threshold, n_cases, n_ctrls)
+    data = np.asarray(data)
+    names_of, rows, signs = parse_sets(sets, genes)
+    S = len(rows)
+    if names is not None and len(names) != S:
+        raise ValueError(f"multi_hit_test: {len(names)} names for {S} sets")
+    K = int(n_permutations)
+    lv = api._dose_levels(levels)
+    once, osigns = [], []
+    for nm, rs, sg in zip(names_of, rows, signs):
+        first = [i for i, x in enumerate(nm) if x not in nm[:i]]
+        once.append([rs[i] for i in first])
+        osigns.append([sg[i] for i in first])
+    used: Dict[int, int] = {}
+    idx = [[-1 if r < 0 else used.setdefault(r, len(used)) for r in rs] for rs in once]
+    sub = data[list(used.keys())] if used else np.zeros((0, n_cases + n_ctrls), np.int32)
+    ex = api.JoinExec(2 if signed else 1, n_cases, n_ctrls, K, device=device)
+    try:
+        ex.set_value_table(api.values_table(n_cases, n_ctrls))
+        if K > 0:
+            ex.generate_permutations(seed, strata)
+        rec, ds, fam = ex.dose_tests(idx, sub, osigns, levels=lv, family=True)
+    finally:
+        ex.close()
+    nan = np.full(S, np.nan)
+    ok = (rec["valid"] != 0) & (ds["best_index"] >= 0) & (K > 0)
+    own_p, family_p = nan.copy(), nan.copy()
+    if K > 0:
+        own_p[ok] = ds["n_ge"][ok] / K
+        family_p[ok] = _tail_pvalues(fam, ds["score"][ok])
+    cols = {
+        "Sets": [str(x) for x in names] if names is not None else [f"Set{s}" for s in range(S)],
+        "Genes": np.array([len(r) for r in once], np.int64),
+        "Scores": rec["score"],
+        "NominalPvalues": rec["pvalue"],
+        "BestLevel": np.where(ok, ds["best_level"], np.nan),
+        "BestCases": np.where(ok, ds["cases_pos"], np.nan),
+        "BestControls": np.where(ok, ds["ctrls_pos"], np.nan),
+        "MultiHitScores": np.where(ok, ds["score"], np.nan),
+        "MultiHitPvalues": own_p,
+        "MultiHitFamilyPvalues": family_p,
+    }
+    return pd.DataFrame(cols, columns=MULTI_HIT_COLUMNS)
+
+
 def check_best_paths(results_df, genes: Sequence[str], data: np.ndarray, n_cases: int, n_ctrls: int, signed: bool,
                      device: int = 0):
     """checkBestPaths (R/CheckResults.R:2-89) on the device scorer without permutations: the dataset preprocessed with

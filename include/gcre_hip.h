@@ -650,6 +650,61 @@ int gcre_score_sets_subsample(gcre_ctx* ctx, const gcre_set_input* in, int32_t m
  * NULL context. */
 int64_t gcre_subsample_launches(const gcre_ctx* ctx);
 
+/* Multi-hit tests of the given sets: are the patients who carry AT LEAST m members of a set enriched in
+ * cases?  Every other set statistic scores the union of a set's members, where a patient with one hit and one with four
+ * count the same.  The best score over the caller's levels m is the statistic, and the same maximum is taken under every
+ * permutation, so that the selection of m is paid for inside the null.  `out`, *n_out: exactly what gcre_score_sets gives
+ * for the full sets, so one call yields both p-values.
+ * Levels.  `levels` holds n_levels (1 .. GCRE_DOSE_MAX_LEVEL) strictly ascending integers in 1 .. GCRE_DOSE_MAX_LEVEL; the same
+ * levels apply to every set.  Level row i of set s, within the context's n patients:
+ *   method 1: the patients who carry at least levels[i] of the set's listed members, whatever the signs; a member listed
+ *             twice counts twice
+ *   method 2: a (+) half, the patients who carry at least levels[i] of the (+) members, and a (-) half, the same over the (-)
+ *             members: two independent counts
+ * and is scored as gcre_score_sets scores a set with these union rows: the same counts (the (-) half the other way round),
+ * the same f64 observed expression, the same f32 null value N[row][r] (NaN and negatives folded to 0).  Level 1 is the set's
+ * union rows, bit for bit; a level above the number of members is an empty row, scored like any row of non-carriers.
+ *   score        = the observed score of level row best_index
+ *   best_index   = the smallest index that attains the maximum of the observed level scores, NaN levels skipped (-1 and a
+ *                  NaN score if every level is NaN)
+ *   best_level   = levels[best_index] (0 for NaN); levels = n_levels
+ *   cases_pos .. ctrls_neg = the counts of that level row (zeros for NaN)
+ *   T[s][r]      = max over the levels of set s of N[row][r]
+ *   n_ge         = #{r < iterations : (double)T[s][r] >= score}; 0 for a NaN score, -1 for an invalid set (an NA member)
+ * iterations == 0: nothing of this stage is launched; every record keeps `levels`, n_ge = 0 (-1 for an invalid set), a NaN
+ * score, best_index = -1 and best_level = 0.  An invalid set has a NaN score, best_index = -1, best_level = 0.
+ * family_max, optional [iterations]: max of T[s][r] over the valid sets (all zeros without one).  null_max, optional
+ * [n_sets][iterations] = T (NaN rows for invalid sets).  level_scores, optional [n_sets][n_levels]: the observed score of
+ * every level row, NaN for invalid sets.
+ * The level rows are built on the device (k_dose_rows: a bit-sliced count per patient, compared with every level) from the
+ * gene rows and the set list, uploaded once.  The valid sets are walked in slabs of whole sets whose level rows -- and
+ * null_max rows, when asked -- stay under GCRE_PREFIX_MAX_MB on the device (environment, read per call, default 1024;
+ * GCRE_PREFIX_SLAB_SETS bounds a slab further); no result depends on the slabs.
+ * Errors, nothing launched and no output array written (*n_out as gcre_score_sets leaves it): everything gcre_score_sets
+ * refuses; GCRE_ERR_ARG -- NULL dose_out, n_levels outside 1 .. GCRE_DOSE_MAX_LEVEL, NULL levels, a level outside
+ * 1 .. GCRE_DOSE_MAX_LEVEL, levels not strictly ascending, one valid set whose level rows (and null_max row) exceed
+ * GCRE_PREFIX_MAX_MB.
+ * n_ge / iterations is a self-contained permutation p-value of the maximum over the caller's levels, one set at a time; the
+ * levels must not be chosen from the labels.  Not built: step-down, min-P and competitive nulls of this statistic, levels
+ * above 15, per-gene weights, doses that count alleles. */
+#define GCRE_DOSE_MAX_LEVEL 15
+typedef struct {
+  double score;
+  int64_t n_ge;
+  int32_t best_index, best_level, levels;
+  int32_t cases_pos, ctrls_pos, cases_neg, ctrls_neg;
+  int32_t pad;
+} gcre_dose_score;
+int gcre_score_sets_dose(gcre_ctx* ctx, const gcre_set_input* in, const int32_t* levels, int32_t n_levels,
+                         gcre_set_score* out, int64_t cap, int64_t* n_out,
+                         gcre_dose_score* dose_out      /* [n_sets] */,
+                         float* family_max              /* optional [iterations] */,
+                         float* null_max                /* optional [n_sets][iterations] */,
+                         double* level_scores           /* optional [n_sets][n_levels] */);
+/* k_dose_rows / k_set_observed / k_prefix_pick / k_prefix_null launches of gcre_score_sets_dose on the context since
+ * gcre_create (no other launch counter counts them, nor the reverse); -1 for a NULL context. */
+int64_t gcre_dose_launches(const gcre_ctx* ctx);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Carrier overlaps of caller-given sets: which sets are carried by the same patients.  No reference
  * counterpart.
