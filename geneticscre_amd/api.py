@@ -127,6 +127,8 @@ DOSE_SCORE = np.dtype([("score", "<f8"), ("n_ge", "<i8"), ("best_index", "<i4"),
                        ("cases_pos", "<i4"), ("ctrls_pos", "<i4"), ("cases_neg", "<i4"), ("ctrls_neg", "<i4"), ("pad", "<i4")],
                       align=True)
 DOSE_MAX_LEVEL = 15   # GCRE_DOSE_MAX_LEVEL
+# gcre_seq_score
+SEQ_SCORE = np.dtype([("n_hit", "<i8"), ("n_perm", "<i8"), ("stopped", "<i4"), ("pad", "<i4")], align=True)
 # gcre_burden
 BURDEN = np.dtype([("total", "<i8"), ("observed", "<i8"), ("n_ge", "<i8"), ("n_le", "<i8"), ("planes", "<i4"),
                    ("p_upper", "<f8"), ("p_lower", "<f8")], align=True)
@@ -152,6 +154,7 @@ EXPORTS = [
     "gcre_score_sets_prefix", "gcre_prefix_launches",
     "gcre_score_sets_subsample", "gcre_subsample_launches",
     "gcre_score_sets_dose", "gcre_dose_launches",
+    "gcre_score_sets_sequential", "gcre_sequential_launches",
     "gcre_set_overlap", "gcre_overlap_launches",
     "gcre_clump_sets", "gcre_clump_launches",
     "gcre_set_patient_counts", "gcre_patient_launches",
@@ -298,6 +301,10 @@ _FEATURES = {
     "dose": ("sets", ["gcre_score_sets_dose", "gcre_dose_launches"], "multi-hit set tests (gcre_score_sets_dose)", {
         "gcre_score_sets_dose": (_I, [_V, ctypes.POINTER(gcre_set_input), _P, _I32, _P, _I64, ctypes.POINTER(_I64), _P, _P, _P, _P]),
         "gcre_dose_launches": (_I64, [_V])}),
+    "sequential": ("sets", ["gcre_score_sets_sequential", "gcre_sequential_launches"], "sequential permutation p-values (gcre_score_sets_sequential)", {
+        "gcre_score_sets_sequential": (_I, [_V, ctypes.POINTER(gcre_set_input), ctypes.c_uint64, _P, _I, _I64, _I64, _P, _I64,
+                                            ctypes.POINTER(_I64), _P]),
+        "gcre_sequential_launches": (_I64, [_V])}),
     "overlap": (None, ["gcre_set_overlap"], "carrier overlaps (gcre_set_overlap)", {
         "gcre_set_overlap": (_I, [_V, ctypes.POINTER(gcre_set_input), _P, _I64, _P, _I64, _P, _P]),
         "gcre_overlap_launches": (_I64, [_V])}),
@@ -366,6 +373,7 @@ _compete_lib = functools.partial(_feature_lib, "compete")
 _prefix_lib = functools.partial(_feature_lib, "prefix")
 _subsample_lib = functools.partial(_feature_lib, "subsample")
 _dose_lib = functools.partial(_feature_lib, "dose")
+_sequential_lib = functools.partial(_feature_lib, "sequential")
 _overlap_lib = functools.partial(_feature_lib, "overlap")
 _clump_lib = functools.partial(_feature_lib, "clump")
 _patients_lib = functools.partial(_feature_lib, "patients")
@@ -1282,6 +1290,35 @@ class JoinExec:
                                                   _ptr(lsc) if level_scores and lsc.size else None))
         res = (out[:n_out.value], ds[:n_out.value])
         return res + ((fam,) if family else ()) + ((nul,) if null else ()) + ((lsc,) if level_scores else ())
+
+    def sequential_tests(self, sets, rows, signs=None, hits: int = 20, max_perms: int = 10**6, seed: int = 0, strata=None):
+        """Sequential permutation p-values of the given sets (gcre_score_sets_sequential): every set is
+        permuted until its null score has reached its observed score ``hits`` times, or ``max_perms`` permutations are used.
+        ``sets`` / ``rows`` / ``signs`` as ``score_sets`` takes them.  The permutations are those ``generate_permutations(seed,
+        strata)`` draws -- permutation r is the same mask here and there -- but they are made in batches as they are needed
+        and never kept, so ``max_perms`` may be far above what a context can hold, and a context with ``iters`` = 0 will do.
+        Returns ``(records, seq)``: the SET_SCORE records of ``score_sets`` on this context, and one SEQ_SCORE record per
+        set -- ``n_hit`` the exceedances counted, ``n_perm`` the permutations used (the position of the ``hits``-th
+        exceedance, or ``max_perms``), ``stopped`` whether it was reached; ``n_hit`` = ``n_perm`` = -1 for a set with an NA
+        member.  ``n_hit / n_perm`` is the set's nominal p-value (``report.sequential_columns``); no value depends on the
+        batches.  ``report.sequential_reference`` states the rule in numpy.  Errors raise GcreError."""
+        inp, keep = _set_input(sets, rows, signs, self.num_cases + self.num_ctrls)
+        S = inp.n_sets
+        lib = _feature_lib("sequential")
+        st = None if strata is None else np.ascontiguousarray(strata, dtype=np.int32).reshape(-1)
+        if st is not None and len(st) != self.num_cases + self.num_ctrls:
+            raise ValueError(f"strata: one id per patient ({self.num_cases + self.num_ctrls}), not {len(st)}")
+        out = np.zeros(max(S, 1), dtype=SET_SCORE)
+        seq = np.zeros(max(S, 1), dtype=SEQ_SCORE)
+        n_out = ctypes.c_int64(0)
+        self._check_gcre(lib.gcre_score_sets_sequential(self._h, ctypes.byref(inp), int(seed) & (2**64 - 1), _ptr(st),
+                                                        0 if st is None else int(st.max()) + 1, int(hits), int(max_perms), _ptr(out),
+                                                        len(out), ctypes.byref(n_out), _ptr(seq)))
+        return out[:n_out.value], seq[:n_out.value]
+
+    def sequential_launches(self) -> int:
+        """Kernels ``sequential_tests`` launched for its own stage on this context so far: three per batch."""
+        return int(_feature_lib("sequential").gcre_sequential_launches(self._h))
 
     def dose_launches(self) -> int:
         """Kernels ``dose_tests`` launched for its own stage on this context so far."""

@@ -683,6 +683,57 @@ hipError_t launch_subsample_masks(uint64_t seed1, int64_t b0, int nb, int n_case
                                   int Kpad, uint32_t* masks, hipStream_t stream);
 hipError_t launch_subsample_null(const SubsampleArgs& a, int method, hipStream_t stream);
 
+// ---- sequential permutation p-values: every set stops at its h-th exceedance (gcre_sequential.hip) ----
+// One batch of permutations [r0, r0 + nb), never resident beyond it.  k_seq_masks writes their masks by the rule of
+// gcre_sequential.h (k_generate_masks' rule) in SetNullArgs' mask layout, [W32p][stride] dwords with the columns nb .. stride-1
+// and the rows beyond the patients zero.  k_seq_null runs k_set_null's count loop over the sets of the active list and writes,
+// per active slot, the batch's bit row; k_seq_retire stops the slots whose h-th exceedance lies in it and lists the others.
+struct SeqMaskArgs {
+  uint64_t seed;
+  uint64_t r0;                  // the first permutation of the batch
+  const int32_t* stratum;       // [n] (read-only: scalar loads), or nullptr: one stratum
+  const uint32_t* cases_in;     // [n_strata] cases of every stratum
+  const uint32_t* size_of;      // [n_strata] patients of every stratum
+  uint32_t* work;               // [2 n_strata][stride] need / rem of every column, only above kSeqRegStrata strata
+  uint32_t* masks;              // [W32p][stride]
+  int n, n_strata;
+  int nb;                       // permutations of the batch, <= stride
+  int W32p, stride;             // stride: a multiple of 64
+};
+constexpr int kSeqRegStrata = 4;   // up to so many strata keep need / rem in registers
+struct SeqNullArgs {
+  const uint32_t* rows;         // [sets][M][W32p] union rows, as SetNullArgs
+  const uint32_t* masks;        // [W32p][stride] the batch's masks
+  const uint32_t* tot;          // [sets][M] carriers per half
+  const uint32_t* thr;          // [sets] f32 bit pattern: a permutation counts iff bits(null) >= thr
+  const float* t32;             // M=1: sanitised f32 null table, diagonal-major
+  const double* d64;            // M=2: f64 vtmax, diagonal-major
+  const double* d64n;           // M=2: the table the (-) half reads
+  const uint32_t* active;       // [nactive] set indices (read-only: scalar loads), in any order
+  unsigned long long* bits;     // [nactive][stride / 64]: bit i of slot a = permutation r0 + i reached set active[a]'s score
+  int64_t nactive;
+  int64_t npt;                  // set tiles (set_null_tile_sets sets each) of the active list
+  int W32p, stride, K;          // K: permutations of the batch; the columns K .. nkt * kSetPermTile - 1 write 0
+  int nkt;                      // permutation tiles of kSetPermTile
+  int pgroups;                  // blocks per permutation tile
+};
+struct SeqRetireArgs {
+  const unsigned long long* bits;   // [nactive][wstride]
+  const uint32_t* active;           // [nactive]
+  uint32_t* next;                   // [>= nactive] the slots that go on, in any order
+  uint32_t* n_next;                 // one dword, zero on entry: how many
+  uint32_t* prior;                  // [sets] exceedances so far, < h while a set is active
+  long long* n_perm;                // [sets] 0 while a set has not stopped, then the 1-based position of its h-th exceedance
+  uint64_t r0;
+  int64_t nactive;
+  int64_t wstride;                  // words per slot
+  int nw;                           // words of a slot that hold the batch: nkt * kSetPermTile / 64
+  uint32_t h;
+};
+hipError_t launch_seq_masks(const SeqMaskArgs& a, hipStream_t stream);
+hipError_t launch_seq_null(const SeqNullArgs& a, int method, hipStream_t stream);
+hipError_t launch_seq_retire(const SeqRetireArgs& a, hipStream_t stream);
+
 // ---- variable-threshold set tests: the best prefix of a set's member list (gcre_prefix.hip) ----
 // One slab of whole sets.  Slot e of the slab is set which[e] of the caller's list; its step rows are rows [row0[e],
 // row0[e + 1]) of the slab, in SetNullArgs' row layout.  k_prefix_rows builds them and their counts, k_set_observed scores

@@ -33,6 +33,10 @@
                          scored on random halves of the cohort and on their complements, how often each half reaches a
                          cut-off (gcre_score_sets_subsample; beyond the reference)
 
+  * ``permutation_masks`` / ``sequential_reference`` / ``sequential_columns``  sequential permutation p-values: the mask rule
+                         of generate_permutations in numpy, every set stopped at its h-th exceedance
+                         (gcre_score_sets_sequential; beyond the reference)
+
 Host-side post-processing of <= top_k x 5 rows: string work, nothing here touches the scored path.
 """
 from __future__ import annotations
@@ -312,7 +316,8 @@ def score_paths(paths, genes: Sequence[str], data: np.ndarray, n_cases: int, n_c
                 threshold: float = 0.05, n_permutations: int = 100, strata: Optional[Sequence[int]] = None, seed: int = 0,
                 device: int = 0, gwaspa_out: Optional[Dict[str, object]] = None, minp: bool = False,
                 competitive: int = 0, competitive_bins: int = 10, fixed: Optional[Sequence[str]] = None,
-                stability: int = 0, stability_cuts=None, family_inference: bool = False):
+                stability: int = 0, stability_cuts=None, sequential: int = 0, sequential_hits: int = 20,
+                family_inference: bool = False):
     """Permutation tests of paths and gene sets the caller names (gcre_score_sets on the device): what GWASPA cannot
     answer for a cascade outside its top K, or for a KEGG / Reactome list.  ``paths`` as ``parse_sets`` reads them;
     genes are looked up after ``preprocess_table(threshold)``, as GWASPA and ``decorated_table`` do (a symbol not found is
@@ -366,10 +371,22 @@ def score_paths(paths, genes: Sequence[str], data: np.ndarray, n_cases: int, n_c
     and no family-wise statement, and ``HalfReplication`` is honest only if neither the paths nor the cuts were chosen on the
     full cohort's labels; otherwise it is optimistic.  The frame's ``attrs["PerHalfSelected"]`` holds, per cut, the mean
     number of paths half A selects in a draw (the q of ``stability_bound``).  ``stability=0`` returns exactly the frame
-    without it."""
+    without it.
+
+    ``sequential`` = max_perms > 0: the SEQUENTIAL_COLUMNS of ``sequential_columns`` behind all of these
+    (gcre_score_sets_sequential).  ``NominalPvalues`` cannot go below 1 / ``n_permutations``, and every path
+    pays for all of them.  Here each path is permuted until its null score has reached its score ``sequential_hits`` times, or
+    ``sequential`` permutations are used -- the permutations ``generate_permutations(seed, strata)`` would draw, made in
+    batches and never kept, so the limit may be far above what a context holds.  ``SequentialPvalues`` = hits / permutations
+    used, with a relative error of about 1 / sqrt(``sequential_hits``) wherever it is above ``sequential_hits`` /
+    ``sequential``; ``SequentialPerms`` / ``SequentialHits`` are the two counts and ``SequentialStopped`` says whether the
+    path reached its hits.  A nominal p-value, one path at a time: the paths stop at different permutations, so there is no
+    family-wise version of it.  ``sequential=0`` returns exactly the frame without it."""
     import pandas as pd
     if int(stability) < 0:
         raise ValueError("stability: the number of draws must not be negative")
+    if int(sequential) < 0:
+        raise ValueError("sequential: the limit of permutations must not be negative")
     if int(stability) > 0 and stability_cuts is None:
         raise ValueError("stability > 0 needs stability_cuts: there is no default cut (a cut is a choice the labels must not make)")
     method = 2 if signed else 1
@@ -419,6 +436,10 @@ def score_paths(paths, genes: Sequence[str], data: np.ndarray, n_cases: int, n_c
         more_cols, per_half = stability_columns(counts, valid, int(stability))
         cols.update(more_cols)
         names_out += list(more_cols)
+    if int(sequential) > 0:
+        seq = _sequential_counts(rows, signs, data, n_cases, n_ctrls, method, int(sequential_hits), int(sequential), strata, seed, device)
+        cols.update(sequential_columns(seq, valid))
+        names_out += SEQUENTIAL_COLUMNS
     df = pd.DataFrame(cols, columns=names_out)
     if per_half is not None:
         df.attrs["PerHalfSelected"] = per_half
@@ -437,6 +458,22 @@ def _stability_counts(rows, signs, data, n_cases, n_ctrls, method, draws, cuts, 
     try:
         ex.set_value_table(api.values_table(n_cases, n_ctrls))
         return ex.subsample_tests(sets, sub, signs, draws=draws, seed=seed, cuts=cuts)[1]
+    finally:
+        ex.close()
+
+
+def _sequential_counts(rows, signs, data, n_cases, n_ctrls, method, hits, max_perms, strata, seed, device) -> np.ndarray:
+    """The SEQ_SCORE records of sequential_tests for ``score_paths``: on the rows the sets use, on a context of its own
+    without permutations."""
+    from . import api
+    used: Dict[int, int] = {}
+    sets = [[-1 if r < 0 else used.setdefault(r, len(used)) for r in rs] for rs in rows]
+    data = np.asarray(data)
+    sub = data[list(used.keys())] if used else np.zeros((0, n_cases + n_ctrls), np.int32)
+    ex = api.JoinExec(method, n_cases, n_ctrls, 0, device=device)
+    try:
+        ex.set_value_table(api.values_table(n_cases, n_ctrls))
+        return ex.sequential_tests(sets, sub, signs, hits=hits, max_perms=max_perms, seed=seed, strata=strata)[1]
     finally:
         ex.close()
 
@@ -906,6 +943,95 @@ def stability_bound(q: float, n_sets: int, tau: float) -> float:
     if n_sets < 1:
         raise ValueError("stability_bound: n_sets must be at least 1")
     return float(q) * float(q) / ((2.0 * float(tau) - 1.0) * float(n_sets))
+
+
+SEQUENTIAL_COLUMNS = ["SequentialPvalues", "SequentialPerms", "SequentialHits", "SequentialStopped"]
+
+
+def permutation_masks(n_cases: int, n_ctrls: int, perms, seed: int, strata=None) -> np.ndarray:
+    """The mask rule of ``JoinExec.generate_permutations(seed, strata)`` and of gcre_score_sets_sequential (k_generate_masks;
+    csrc/gcre_sequential.h is the same rule in C++): bool [perms][n_cases + n_ctrls], row r the patients that permutation r
+    labels as cases -- inside every stratum as many as it has cases among the columns < n_cases.  ``perms``: their number
+    (permutations 0 .. perms-1), or a sequence of permutation indices (any non-negative integers below 2^64 - 1).
+    ``strata``: one id >= 0 per patient, or None for one stratum.  Knuth's selection sampling per stratum: with base_r =
+    mix64(seed ^ C2 (r + 1)), patient c, in column order, reads u = mix64(base_r + c) and becomes a case when
+    floor(u rem / 2^64) < need, rem the patients of its stratum not yet walked (c included) and need its cases still to be
+    placed.  A pure function of (seed, r, c)."""
+    n_cases, n_ctrls = int(n_cases), int(n_ctrls)
+    n = n_cases + n_ctrls
+    r = np.arange(int(perms), dtype=_U64) if np.ndim(perms) == 0 else np.array([int(x) for x in np.asarray(perms, dtype=object).reshape(-1)], dtype=_U64)
+    st = np.zeros(n, np.int64) if strata is None else np.asarray(strata, dtype=np.int64).reshape(-1)
+    if len(st) != n or (st < 0).any():
+        raise ValueError(f"strata: one id >= 0 per patient ({n}), not {len(st)} of which {(st < 0).sum()} are negative")
+    ns = int(st.max()) + 1 if n else 1
+    with np.errstate(over="ignore"):
+        base = _mix64(_U64(int(seed) & (2**64 - 1)) ^ (_U64(0x51ED270B7F3C9A1D) * (r + _U64(1))))
+    out = np.zeros((len(r), n), bool)
+    need = np.zeros((ns, len(r)), np.int64)
+    rem = np.zeros(ns, np.int64)
+    for s in range(ns):
+        need[s] = int((st[:n_cases] == s).sum())
+        rem[s] = int((st == s).sum())
+    for c in range(n):
+        s = int(st[c])
+        with np.errstate(over="ignore"):
+            u = _mix64(base + _U64(c))
+        take = _mulhi(u, int(rem[s])) < need[s]
+        out[:, c] = take
+        need[s] -= take
+        rem[s] -= 1
+    return out
+
+
+def sequential_reference(null, obs, valid, hits: int, max_perms: int) -> Dict[str, np.ndarray]:
+    """The definition of gcre_score_sets_sequential taken literally on a null matrix.  ``null``
+    [sets][>= max_perms]: the null score of every set under permutations 0, 1, ... in order (the f32 values of
+    ``score_sets``); ``obs`` [sets] the observed scores; ``valid`` [sets].  With e[r] = (float64(null[r]) >= obs), r <
+    max_perms (a NaN never counts): a set with at least ``hits`` ones stops at the 1-based position of the ``hits``-th --
+    ``n_perm`` that position, ``n_hit`` = hits, ``stopped`` 1; otherwise ``n_perm`` = max_perms, ``n_hit`` their number,
+    ``stopped`` 0.  An invalid set gets ``n_hit`` = ``n_perm`` = -1.  Returns int64 ``n_hit``, ``n_perm`` and int32
+    ``stopped``, [sets] each."""
+    h, P = int(hits), int(max_perms)
+    if h < 1 or P < 0:
+        raise ValueError(f"sequential_reference: hits = {hits} must be at least 1 and max_perms = {max_perms} not negative")
+    obs = np.asarray(obs, np.float64).reshape(-1)
+    S = len(obs)
+    nul = np.asarray(null).reshape(S, -1) if S else np.zeros((0, P))
+    if nul.shape[1] < P:
+        raise ValueError(f"sequential_reference: {nul.shape[1]} null scores per set for max_perms = {P}")
+    ok = np.asarray(valid).reshape(-1)[:S] != 0
+    n_hit, n_perm, stopped = np.zeros(S, np.int64), np.zeros(S, np.int64), np.zeros(S, np.int32)
+    for s in range(S):
+        if not ok[s]:
+            n_hit[s] = n_perm[s] = -1
+            continue
+        with np.errstate(invalid="ignore"):
+            e = nul[s, :P].astype(np.float64) >= obs[s]
+        at = np.flatnonzero(e)
+        if len(at) >= h:
+            n_hit[s], n_perm[s], stopped[s] = h, int(at[h - 1]) + 1, 1
+        else:
+            n_hit[s], n_perm[s] = len(at), P
+    return {"n_hit": n_hit, "n_perm": n_perm, "stopped": stopped}
+
+
+def sequential_columns(seq, valid) -> Dict[str, np.ndarray]:
+    """The SEQUENTIAL_COLUMNS from the ``seq`` records of ``JoinExec.sequential_tests`` (or the dict of
+    ``sequential_reference``): ``SequentialPvalues`` = n_hit / n_perm, the set's nominal p-value by the n / K convention of
+    this module (0 where no permutation reached the score; with the counts beside it a caller forms (n_hit + 1) / (n_perm +
+    1) for the sets that did not stop); ``SequentialPerms`` and ``SequentialHits`` the two counts; ``SequentialStopped`` 1
+    where the set reached its hits before the limit, else 0.  NaN for a set with an NA member (``valid`` 0 or a count < 0);
+    the p-value is NaN also where no permutation was used."""
+    n_hit = np.asarray(seq["n_hit"], np.int64).reshape(-1)
+    n_perm = np.asarray(seq["n_perm"], np.int64).reshape(-1)
+    stopped = np.asarray(seq["stopped"], np.int64).reshape(-1)
+    ok = (np.asarray(valid).reshape(-1)[:len(n_hit)] != 0) & (n_hit >= 0) & (n_perm >= 0)
+    nan = np.full(len(n_hit), np.nan)
+    p = nan.copy()
+    sel = ok & (n_perm > 0)
+    p[sel] = n_hit[sel] / n_perm[sel]
+    return {"SequentialPvalues": p, "SequentialPerms": np.where(ok, n_perm, nan), "SequentialHits": np.where(ok, n_hit, nan),
+            "SequentialStopped": np.where(ok, stopped, nan)}
 
 
 VARIABLE_THRESHOLD_COLUMNS = ["Sets", "Genes", "Scores", "NominalPvalues", "BestGenes", "BestThreshold", "AdaptiveScores",

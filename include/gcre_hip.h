@@ -705,6 +705,49 @@ int gcre_score_sets_dose(gcre_ctx* ctx, const gcre_set_input* in, const int32_t*
  * gcre_create (no other launch counter counts them, nor the reverse); -1 for a NULL context. */
 int64_t gcre_dose_launches(const gcre_ctx* ctx);
 
+/* Sequential permutation p-values of the given sets (Besag & Clifford 1991, the adaptive permutation of
+ * PLINK): every set is permuted until its null score has reached its observed score `h` times, then it stops; the p-value is
+ * n_hit / n_perm.  A set that is plainly null stops after about h / p permutations, an interesting one runs on to max_perms,
+ * which may be far above what a context can hold: the masks are drawn in batches as they are needed and are never resident
+ * as a whole, and the context's own masks are not read -- a context with iterations == 0 is the usual one.
+ * `out`, *n_out: exactly what gcre_score_sets gives on this context (n_ge / pvalue against the context's own masks), so one
+ * call yields both.
+ * Definition, independent of the batches.  mask_r, 0 <= r < max_perms (r is 64-bit), is the mask gcre_generate_perm_masks(seed,
+ * stratum, n_strata) gives permutation r, bit for bit: base_r = gcre_mix64(seed ^ (0x51ed270b7f3c9a1d * (r + 1))), patient c in
+ * column order reads u = gcre_mix64(base_r + c) and becomes a case when floor(u rem / 2^64) < need, rem the patients of its
+ * stratum not yet walked (c included) and need the cases of the stratum still to be placed.  No tag in between: for r below a
+ * context's iterations these are the context's generated permutations.  With null_s(mask) the f32 null score of
+ * gcre_score_sets (above) and score_s the observed score,
+ *   e_s[r] = ((double)null_s(mask_r) >= score_s)              a NaN score never counts
+ * If e_s has at least h ones in [0, max_perms): n_perm = the 1-based position of the h-th one, n_hit = h, stopped = 1.
+ * Otherwise n_perm = max_perms, n_hit = the number of ones, stopped = 0.  A set with an NA member gets n_hit = n_perm = -1
+ * and stopped = 0.  max_perms == 0: nothing of this stage is launched, every valid set gets zeros.
+ * The outputs are integers and a pure function of (sets, rows, signs, table, seed, strata, h, max_perms).  Batches are whole
+ * 512-permutation tiles: the first holds 4,096 permutations, every later one four times the one before, up to the tiles whose
+ * masks and bit rows (one bit per active set and permutation) stay under GCRE_SEQ_MAX_MB on the device (environment, read per
+ * call, default 1024; one tile at the least); GCRE_SEQ_BATCH_PERMS bounds a batch further.  Neither they, nor the order of the
+ * active list, nor the launch shape change a value.
+ * Errors, nothing launched and no output array written (*n_out as gcre_score_sets leaves it): everything gcre_score_sets
+ * refuses; GCRE_ERR_ARG -- NULL seq_out, h outside 1 .. 2^31 - 1, max_perms outside 0 .. 2^40, `stratum` with n_strata < 1;
+ * GCRE_ERR_RANGE -- a stratum id outside 0 .. n_strata-1.
+ * n_hit / n_perm is a nominal p-value, one set at a time, with a relative error of about 1 / sqrt(h) wherever it is above
+ * h / max_perms; for the sets that did not stop, (n_hit + 1) / (n_perm + 1) is the usual conservative estimate.  The sets stop
+ * at different permutations, so there is no common null matrix.  Not built: family-wise versions (max-T, step-down, min-P) of
+ * it, sequential stopping of the prefix / dose / competitive statistics and of the joins, an early stop for sets that are
+ * clearly significant. */
+typedef struct {
+  int64_t n_hit;       /* exceedances counted: h when stopped; -1 for an invalid set */
+  int64_t n_perm;      /* permutations used: the position of the h-th exceedance, or max_perms; -1 for an invalid set */
+  int32_t stopped;     /* 1: the h-th exceedance was reached */
+  int32_t pad;
+} gcre_seq_score;
+int gcre_score_sets_sequential(gcre_ctx* ctx, const gcre_set_input* in, uint64_t seed, const int32_t* stratum, int n_strata,
+                               int64_t h, int64_t max_perms, gcre_set_score* out, int64_t cap, int64_t* n_out,
+                               gcre_seq_score* seq_out /* [n_sets] */);
+/* k_seq_masks / k_seq_null / k_seq_retire launches of gcre_score_sets_sequential on the context since gcre_create -- three
+ * per batch (no other launch counter counts them, nor the reverse); -1 for a NULL context. */
+int64_t gcre_sequential_launches(const gcre_ctx* ctx);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Carrier overlaps of caller-given sets: which sets are carried by the same patients.  No reference
  * counterpart.
