@@ -3,18 +3,11 @@
 // (plane p = bit p of the 32 counts).  Everything here is full-rate bit logic (v_bitop3 / v_xor3).
 #pragma once
 
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+#include "gcre_count_tile.h"   // u32 .. u32x4, GCRE_CONSTANT
 
 namespace gcre {
 
-typedef uint32_t u32;
-typedef uint64_t u64;
-typedef int64_t i64;
-typedef u32 __attribute__((ext_vector_type(4))) u32x4;
 typedef u32 __attribute__((ext_vector_type(16))) u32x16;
-
-#define GCRE_CONSTANT __attribute__((address_space(4)))
 
 __device__ __forceinline__ u32 sp_diag_offset(u32 t) { return (u32)(((u64)t * (u64)(t + 1)) >> 1); }
 

@@ -4,29 +4,22 @@
 // exact in integers and independent of the order of evaluation.
 //   * k_burden_planes  the uploaded int32 rows as bit planes in SetNullArgs' row layout ([W32p] dwords per plane, zero
 //                      beyond the patients), every row only the planes its largest weight needs
-//   * k_burden_null    k_set_null's count loop (gcre_sets.hip) with planes in place of sets: per item -- up to four
+//   * k_burden_null    count_tile (gcre_count_tile.h) with planes as rows, one half only: per item -- up to four
 //                      consecutive planes of one row -- and permutation the shifted popcounts, added into sums[row][perm]
 //   * k_burden_finish  per row the permutations whose sum is >= / <= the observed sum, the padding masked out (a wave
 //                      walks 1,024 permutations, then one atomic per tail)
 // The context-side entry (the slabs, the item list) is in gcre_host_stats.hip.  Every global write is a vector store or a
 // vector atomic from plain C++.
-#include "gcre_kernels.h"
-#include "gcre_bitslice.h"
+#include "gcre_count_tile.h"
 
 namespace gcre {
 namespace {
 
-constexpr int kBdBlock = 256;                 // threads per block
-constexpr int kBdWaves = kBdBlock / 64;       // one item per wave
-constexpr int kBdR = 8;                       // permutations per lane
-constexpr int kBdPT = 64 * kBdR;              // permutations per tile: k_set_null's
-constexpr int kBdWC = 4;                      // mask dwords per staged chunk
+constexpr int kBdBlock = kCtBlock;            // threads per block, of k_burden_planes and k_burden_finish as well
+constexpr int kBdWaves = kCtWaves;            // one item per wave
 constexpr int kBdT = kBurdenItemPlanes;       // planes per item
 constexpr int kBdFinishSpan = 1024;           // permutations per wave of k_burden_finish
-static_assert(kBdPT == kSetPermTile && kBdT == 4, "k_set_null's tile, four planes per item");
-
-// column of the permutation tile that register j of a lane holds (k_set_null's layout)
-__device__ __forceinline__ int bd_col(int lane, int j) { return (j >> 2) * 256 + lane * 4 + (j & 3); }
+static_assert(kBdT == 4, "four planes per item");
 
 }  // namespace
 
@@ -52,53 +45,24 @@ __global__ __launch_bounds__(kBdBlock) void k_burden_planes(const BurdenPlaneArg
 
 // grid: nkt * pgroups blocks; a block stays on permutation tile kt = blockIdx.x % nkt and walks the item tiles g, g + pgroups, ..
 __global__ __launch_bounds__(kBdBlock, 4) void k_burden_null(const BurdenNullArgs a) {
-  constexpr int R = kBdR, WC = kBdWC, PT = kBdPT, T = kBdT;
-  constexpr int CHUNK = WC * PT;                // dwords per staged mask chunk
-  constexpr int VEC = CHUNK / 4 / kBdBlock;     // uint4 per thread per chunk
-  static_assert(VEC >= 1 && CHUNK % (4 * kBdBlock) == 0, "staging shape");
+  constexpr int R = kCtR, PT = kCtPT, T = kBdT;
 
-  __shared__ __attribute__((aligned(16))) u32 lds[2][CHUNK];
+  __shared__ __attribute__((aligned(16))) u32 lds[2][kCtChunk];
 
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int kt = blockIdx.x % a.nkt;
   const int g = blockIdx.x / a.nkt;
 
-  const u32 GCRE_CONSTANT* PLANES = (const u32 GCRE_CONSTANT*)a.planes;
-  const BurdenItem GCRE_CONSTANT* ITEMS = (const BurdenItem GCRE_CONSTANT*)a.items;
-
-  const int nchunks = a.W32p / WC;
-  const u32* mask_tile = a.masks + (size_t)kt * PT;   // column offset of this permutation tile
-
-  // ---- mask staging: chunk c = rows [c*WC, c*WC+WC) x PT columns, row-major in LDS (as k_set_null) ----
-  u32x4 stage[VEC];
-  u32 voff[VEC];
-#pragma unroll
-  for (int i = 0; i < VEC; i++) {
-    const int e = tid + i * kBdBlock;
-    voff[i] = (u32)((e / (PT / 4)) * a.Kpad + (e % (PT / 4)) * 4) * 4u;
-  }
-  const size_t chunk_bytes = (size_t)WC * a.Kpad * 4;
-  auto stage_load = [&](int c) {
-    const char* cb = (const char*)mask_tile + (size_t)c * chunk_bytes;
-#pragma unroll
-    for (int i = 0; i < VEC; i++) stage[i] = *(const u32x4*)(cb + voff[i]);
-  };
-  auto stage_store = [&](int buf) {
-#pragma unroll
-    for (int i = 0; i < VEC; i++) *(u32x4*)(&lds[buf][(tid + i * kBdBlock) * 4]) = stage[i];
-  };
+  const u32 GCRE_CONSTANT* PLANES = as_const(a.planes);
+  const BurdenItem GCRE_CONSTANT* ITEMS = as_const(a.items);
 
   // whether the permutation of each register is one of the K: the padding up to Kpad is never written
   bool live[R];
 #pragma unroll
-  for (int j = 0; j < R; j++) live[j] = kt * PT + bd_col(lane, j) < a.K;
+  for (int j = 0; j < R; j++) live[j] = kt * PT + ct_col(lane, j) < a.K;
 
-  stage_load(0);
-  stage_store(0);
-  __syncthreads();
-  int buf = 0;
+  MaskStream ms(lds, a.masks + (size_t)kt * PT, a.Kpad);   // column offset of this permutation tile
 
   for (i64 pt = g; pt < a.npt; pt += a.pgroups) {
     // this wave's item; a wave past the end walks the last item and drops what it counted (the chunk loop holds a barrier)
@@ -107,54 +71,12 @@ __global__ __launch_bounds__(kBdBlock, 4) void k_burden_null(const BurdenNullArg
     const BurdenItem GCRE_CONSTANT* ip = ITEMS + (have ? it : a.nitems - 1);
     const int row = ip->row, plane = ip->plane, cnt = ip->count, base = ip->base;
 
-    u32 acc[T][R];
-#pragma unroll
-    for (int t = 0; t < T; t++)
-#pragma unroll
-      for (int j = 0; j < R; j++) acc[t][j] = 0u;
-
     // dword offsets of the item's planes, wave-uniform; a plane past the item's last reads the last one again (dropped below)
     size_t o[T];
 #pragma unroll
     for (int t = 0; t < T; t++) o[t] = (size_t)(plane + (t < cnt ? t : cnt - 1)) * (size_t)a.W32p;
 
-    // software pipeline over the flattened (chunk, plane) sequence: the next plane's words are in flight during the counts
-    u32x4 nx;
-    auto fetch = [&](int c, int t) { nx = *(const u32x4 GCRE_CONSTANT*)(PLANES + o[t] + (size_t)c * WC); };
-    fetch(0, 0);
-
-    for (int c = 0; c < nchunks; c++) {
-      const int cn = (c + 1 == nchunks) ? 0 : c + 1;
-      stage_load(cn);   // the next chunk of this block's (periodic) mask stream
-
-      u32 m[WC][R];
-#pragma unroll
-      for (int w = 0; w < WC; w++) {
-        const u32* mrow = &lds[buf][w * PT];
-        const u32x4 v0 = *(const u32x4*)(mrow + lane * 4);
-        const u32x4 v1 = *(const u32x4*)(mrow + 256 + lane * 4);
-        m[w][0] = v0.x; m[w][1] = v0.y; m[w][2] = v0.z; m[w][3] = v0.w;
-        m[w][4] = v1.x; m[w][5] = v1.y; m[w][6] = v1.z; m[w][7] = v1.w;
-      }
-
-#pragma unroll
-      for (int t = 0; t < T; t++) {
-        u32 jn[WC];
-#pragma unroll
-        for (int w = 0; w < WC; w++) jn[w] = __builtin_amdgcn_readfirstlane(nx[w]);
-        if (t + 1 < T) fetch(c, t + 1);
-        else fetch(cn, 0);
-#pragma unroll
-        for (int w = 0; w < WC; w++)
-#pragma unroll
-          for (int j = 0; j < R; j++) acc[t][j] += __builtin_popcount(jn[w] & m[w][j]);
-        __builtin_amdgcn_sched_barrier(0);   // keep each plane's scalar loads in its own region
-      }
-
-      stage_store(buf ^ 1);
-      __syncthreads();
-      buf ^= 1;
-    }
+    const TileCounts<1, T> acc = count_tile<1, T>(ms, PLANES, o, a.W32p);
 
     // ---- the item's share of the sums: sum_t acc[t] << (base + t), one 64-bit integer atomic per live permutation ----
     if (!have) continue;   // wave-uniform
@@ -164,8 +86,8 @@ __global__ __launch_bounds__(kBdBlock, 4) void k_burden_null(const BurdenNullArg
       u64 s = 0;
 #pragma unroll
       for (int t = 0; t < T; t++)
-        if (t < cnt) s += (u64)acc[t][j] << (base + t);
-      if (live[j] && s != 0) atomicAdd(out + bd_col(lane, j), (unsigned long long)s);
+        if (t < cnt) s += (u64)acc.v[0][t][j] << (base + t);
+      if (live[j] && s != 0) atomicAdd(out + ct_col(lane, j), (unsigned long long)s);
     }
   }
 }
@@ -210,8 +132,8 @@ hipError_t launch_burden_planes(const BurdenPlaneArgs& a, hipStream_t stream) {
 
 hipError_t launch_burden_null(const BurdenNullArgs& a, hipStream_t stream) {
   if (a.nitems == 0 || a.K == 0) return hipSuccess;
-  if (a.nitems < 0 || a.K < 0 || a.K > a.Kpad || a.Kpad % kBdPT != 0 || a.W32p < kBdWC || a.W32p % kBdWC != 0 ||
-      a.nkt != (a.K + kBdPT - 1) / kBdPT || a.npt != (a.nitems + kBdWaves - 1) / kBdWaves || a.pgroups < 1 || a.pgroups > a.npt ||
+  if (a.nitems < 0 || a.K < 0 || a.K > a.Kpad || a.Kpad % kCtPT != 0 || a.W32p < kCtWC || a.W32p % kCtWC != 0 ||
+      a.nkt != (a.K + kCtPT - 1) / kCtPT || a.npt != (a.nitems + kBdWaves - 1) / kBdWaves || a.pgroups < 1 || a.pgroups > a.npt ||
       (i64)a.nkt * a.pgroups > 0x7fffffff)
     return hipErrorInvalidValue;
   if (g_launch_trace)   // a block walks `per` item tiles

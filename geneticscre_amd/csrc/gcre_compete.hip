@@ -7,25 +7,11 @@
 //                     row, eight rows' loads in flight; AND with the case / control bits (computed, not loaded), popcount,
 //                     wave reduction, the look-up in the f64 table k_set_observed reads, in its order of the addition.
 // No LDS; every global write is a vector store or a vector atomic.  The context-side entry is in gcre_host_compete.hip.
-#include "gcre_kernels.h"
+#include "gcre_count_tile.h"   // GCRE_CONSTANT, as_const, tri_index
 #include "gcre_compete.h"
 
 namespace gcre {
 namespace {
-
-typedef uint32_t u32;
-typedef uint64_t u64;
-typedef int64_t i64;
-typedef u32 __attribute__((ext_vector_type(4))) u32x4;
-
-// wave-uniform read-only inputs through the constant address space: scalar loads
-#define COMPETE_CONSTANT __attribute__((address_space(4)))
-template <typename T>
-__device__ __forceinline__ const T COMPETE_CONSTANT* compete_const(const T* p) {
-  return (const T COMPETE_CONSTANT*)p;
-}
-
-__device__ __forceinline__ u64 compete_diag(u64 t) { return (t * (t + 1)) >> 1; }
 
 // the low x bits set (x <= 0: none, x >= 32: all)
 __device__ __forceinline__ u32 compete_below(int x) { return x <= 0 ? 0u : (x >= 32 ? 0xffffffffu : ((1u << x) - 1u)); }
@@ -61,8 +47,8 @@ __global__ __launch_bounds__(kCompeteBlock) COMPETE_WAVES void k_compete_null(co
   const int v = (int)(w / a.groups);
   const int grp = (int)(w % a.groups);
 
-  const CompeteSet COMPETE_CONSTANT* SETS = compete_const(a.sets);
-  const int32_t COMPETE_CONSTANT* POOL = compete_const(a.pool_rows);
+  const CompeteSet GCRE_CONSTANT* SETS = as_const(a.sets);
+  const int32_t GCRE_CONSTANT* POOL = as_const(a.pool_rows);
   const i64 set = SETS[v].set;
   const int moff = SETS[v].moff;
   const int k = SETS[v].k;
@@ -164,8 +150,8 @@ __global__ __launch_bounds__(kCompeteBlock) COMPETE_WAVES void k_compete_null(co
     for (int h = 0; h < 2 * M; h++) cnt[h] = compete_wave_sum(cnt[h]);
 
     // ---- the null score: k_set_observed's expression on (cases, controls) of P and (controls, cases) of N ----
-    double score = a.dvt[compete_diag((u64)cnt[0] + (u64)cnt[1]) + (u64)cnt[0]];
-    if constexpr (M == 2) score = score + a.dvt[compete_diag((u64)cnt[3] + (u64)cnt[2]) + (u64)cnt[3]];
+    double score = a.dvt[tri_index((u64)cnt[0] + (u64)cnt[1]) + (u64)cnt[0]];
+    if constexpr (M == 2) score = score + a.dvt[tri_index((u64)cnt[3] + (u64)cnt[2]) + (u64)cnt[3]];
     ge += score >= obs ? 1u : 0u;               // a NaN on either side never counts
     if (a.null_out && lane == 0) a.null_out[(size_t)v * (size_t)a.stride + (size_t)bi] = score;
   }

@@ -12,21 +12,10 @@
 // a carry out of plane 3 sets the patient's sticky bit, so a patient with 16 or more carried members stays at or above every
 // level.  The member loads do not depend on the counter: kDoseFly of them are issued before the first is added.  Every global
 // write is a vector store or a vector atomic.
-#include "gcre_kernels.h"
+#include "gcre_count_tile.h"   // GCRE_CONSTANT, as_const
 
 namespace gcre {
 namespace {
-
-typedef uint32_t u32;
-typedef uint64_t u64;
-typedef int64_t i64;
-
-// wave-uniform read-only inputs through the constant address space: scalar loads
-#define DOSE_CONSTANT __attribute__((address_space(4)))
-template <typename T>
-__device__ __forceinline__ const T DOSE_CONSTANT* dose_const(const T* p) {
-  return (const T DOSE_CONSTANT*)p;
-}
 
 constexpr int kDoseBlock = 256;   // threads per block: four waves
 constexpr int kDoseFly = 8;       // member rows whose loads are in flight per lane
@@ -73,10 +62,10 @@ __global__ __launch_bounds__(kDoseBlock) void k_dose_rows(const DoseArgs a) {
   const i64 e = wv / nch;
   const int lane = threadIdx.x & 63;
   if (e >= a.nslots) return;   // the whole wave; the kernel has no barrier
-  const i64 s = dose_const(a.which)[e];
-  const i64 sb = dose_const(a.set_off)[s], se = dose_const(a.set_off)[s + 1];
-  const int32_t DOSE_CONSTANT* MEM = dose_const(a.members);
-  const int32_t DOSE_CONSTANT* SGN = dose_const(a.signs);
+  const i64 s = as_const(a.which)[e];
+  const i64 sb = as_const(a.set_off)[s], se = as_const(a.set_off)[s + 1];
+  const int32_t GCRE_CONSTANT* MEM = as_const(a.members);
+  const int32_t GCRE_CONSTANT* SGN = as_const(a.signs);
   const int split = a.n_cases >> 5;
   const u32 split_mask = (1u << (a.n_cases & 31)) - 1u;
   const size_t rs = (size_t)M * a.W32p;

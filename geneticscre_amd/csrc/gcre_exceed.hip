@@ -39,12 +39,6 @@ namespace {
 typedef u32 __attribute__((ext_vector_type(2))) u32x2;
 typedef u32 __attribute__((ext_vector_type(8))) u32x8;
 
-#define EXC_CONSTANT __attribute__((address_space(4)))
-template <typename T>
-__device__ __forceinline__ const T EXC_CONSTANT* exc_const(const T* p) {
-  return (const T EXC_CONSTANT*)p;
-}
-
 __device__ __forceinline__ u32 exc_diag(u32 t) { return (u32)(((u64)t * (u64)(t + 1)) >> 1); }
 
 constexpr int kExceedFlushTiles = 65536;
@@ -197,11 +191,11 @@ __global__ __launch_bounds__(kNullBlock, OCC) void k_exceed_dense(const ExceedAr
   const int kt = blockIdx.x % a.nkt;
   const int g = blockIdx.x / a.nkt;
 
-  const u32 EXC_CONSTANT* P0 = exc_const(a.p0);
-  const u32 EXC_CONSTANT* P1 = exc_const(a.p1);
-  const u32 EXC_CONSTANT* ROW0 = exc_const(a.row0);
-  const u32 EXC_CONSTANT* ROW1 = exc_const(a.row1);
-  const u32 EXC_CONSTANT* TOT = exc_const(a.tot);
+  const u32 GCRE_CONSTANT* P0 = as_const(a.p0);
+  const u32 GCRE_CONSTANT* P1 = as_const(a.p1);
+  const u32 GCRE_CONSTANT* ROW0 = as_const(a.row0);
+  const u32 GCRE_CONSTANT* ROW1 = as_const(a.row1);
+  const u32 GCRE_CONSTANT* TOT = as_const(a.tot);
 
   const int nchunks = a.W32p / WC;
   const u32* mask_tile = a.masks + (size_t)kt * PT;
@@ -286,13 +280,13 @@ __global__ __launch_bounds__(kNullBlock, OCC) void k_exceed_dense(const ExceedAr
 
     rowv nx[M], ny[M];
     auto fetch = [&](int c, int t) {
-      const u32 EXC_CONSTANT* b0 = P0 + (size_t)c * WC;
-      const u32 EXC_CONSTANT* b1 = P1 + (size_t)c * WC;
-      nx[0] = *(const rowv EXC_CONSTANT*)(b0 + ((size_t)o0[t] << 3));
-      ny[0] = *(const rowv EXC_CONSTANT*)(b1 + ((size_t)o1[t] << 3));
+      const u32 GCRE_CONSTANT* b0 = P0 + (size_t)c * WC;
+      const u32 GCRE_CONSTANT* b1 = P1 + (size_t)c * WC;
+      nx[0] = *(const rowv GCRE_CONSTANT*)(b0 + ((size_t)o0[t] << 3));
+      ny[0] = *(const rowv GCRE_CONSTANT*)(b1 + ((size_t)o1[t] << 3));
       if constexpr (M == 2) {
-        nx[M - 1] = *(const rowv EXC_CONSTANT*)(b0 + ((size_t)(o0[t] + h8) << 3));
-        ny[M - 1] = *(const rowv EXC_CONSTANT*)(b1 + ((size_t)o1n[t] << 3));
+        nx[M - 1] = *(const rowv GCRE_CONSTANT*)(b0 + ((size_t)(o0[t] + h8) << 3));
+        ny[M - 1] = *(const rowv GCRE_CONSTANT*)(b1 + ((size_t)o1n[t] << 3));
       }
     };
     fetch(0, 0);

@@ -1,10 +1,8 @@
 // gcre_family.hip -- step-down, k-FWER and FDR over a family of caller-given sets (gcre_score_sets_family).
 // All of them are functions of one matrix: N[i][r], the f32 null score of valid set i under permutation r.
-//   * k_family_null   per (set, permutation): the count work of k_set_null (gcre_sets.hip: one union row per set against every
-//                     mask, lanes own 8 permutations, the mask tile through LDS, set words as wave-uniform scalar loads, the
-//                     same table look-ups and fold) -- a copy, so that the set kernels' code object does not move -- with
-//                     another finish: a lane stores its eight values as two 16-byte vector stores into N[row][perm], row =
-//                     the set's rank in ascending observed order
+//   * k_family_null   per (set, permutation): k_set_null's counts and null scores (count_tile and null_scores of
+//                     gcre_count_tile.h; row = set) with another finish: a lane stores its eight values as two 16-byte vector
+//                     stores into N[row][perm], row = the set's rank in ascending observed order
 //   * k_family_scan   lane = permutation: walks the rows in that order with a running maximum; at the end of each tie group
 //                     the lanes whose maximum reaches the group's threshold are counted (a ballot; the counts of 64 rows
 //                     leave a wave as one atomic instruction); in the same walk a sorted insertion keeps the column's
@@ -15,49 +13,25 @@
 // N is kept for a slab of whole 512-permutation tiles at a time; its row stride is the slab's permutation count.  Padded
 // columns (permutations >= K) hold whatever the padded masks give: k_family_scan and k_family_hist never count them.
 // Every global write is a plain vector store or a vector atomic.
-#include "gcre_kernels.h"
+#include "gcre_count_tile.h"
 
 namespace gcre {
 namespace {
 
-typedef uint32_t u32;
-typedef uint64_t u64;
-typedef int64_t i64;
-typedef u32 __attribute__((ext_vector_type(4))) u32x4;
-
-// wave-uniform read-only inputs through the constant address space: scalar loads
-#define FAM_CONSTANT __attribute__((address_space(4)))
-template <typename T>
-__device__ __forceinline__ const T FAM_CONSTANT* fam_const(const T* p) {
-  return (const T FAM_CONSTANT*)p;
-}
-
-__device__ __forceinline__ u64 fam_diag(u64 t) { return (t * (t + 1)) >> 1; }
-
-constexpr int kFamBlock = 256;               // threads per block of k_family_null
-constexpr int kFamR = 8;                     // permutations per lane
-constexpr int kFamPT = 64 * kFamR;           // permutations per tile
-constexpr int kFamWC = 4;                    // mask dwords per staged chunk
 constexpr int kFamScanBlock = 64;            // one wave per block: K / 64 waves is all the scan has, spread over the CUs
 constexpr int kFamScanBatch = 32;            // rows whose loads k_family_scan has in flight before it walks them
 constexpr int kFamHistBlock = 256;
 constexpr int kFamHistRound = 1 << 20;       // vectors per thread between two flushes; with the row that follows, at most
                                              // 2^21: a block counts at most 2^31 values into its LDS counters
-static_assert(kFamPT == kSetPermTile, "k_set_null's tile");
-
 }  // namespace
 
 // M method, TPW sets per wave and set tile, OCC waves per SIMD the register allocation must admit
 template <int M, int TPW, int OCC>
-__global__ __launch_bounds__(kFamBlock, OCC) void k_family_null(const FamilyNullArgs a) {
-  constexpr int R = kFamR, WC = kFamWC, PT = kFamPT;
-  constexpr int NW = kFamBlock / 64;
-  constexpr int TPB = NW * TPW;
-  constexpr int CHUNK = WC * PT;                // dwords per staged mask chunk
-  constexpr int VEC = CHUNK / 4 / kFamBlock;    // uint4 per thread per chunk
-  static_assert(VEC >= 1 && CHUNK % (4 * kFamBlock) == 0, "staging shape");
+__global__ __launch_bounds__(kCtBlock, OCC) void k_family_null(const FamilyNullArgs a) {
+  constexpr int R = kCtR, PT = kCtPT;
+  constexpr int TPB = kCtWaves * TPW;
 
-  __shared__ __attribute__((aligned(16))) u32 lds[2][CHUNK];
+  __shared__ __attribute__((aligned(16))) u32 lds[2][kCtChunk];
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -65,49 +39,16 @@ __global__ __launch_bounds__(kFamBlock, OCC) void k_family_null(const FamilyNull
   const int kt = blockIdx.x % a.nkt;            // tile of the slab
   const int g = blockIdx.x / a.nkt;
 
-  const u32 FAM_CONSTANT* ROWS = fam_const(a.rows);
-  const u32 FAM_CONSTANT* TOT = fam_const(a.tot);
-  const u32 FAM_CONSTANT* RANK = fam_const(a.rank);
+  const u32 GCRE_CONSTANT* ROWS = as_const(a.rows);
+  const u32 GCRE_CONSTANT* TOT = as_const(a.tot);
+  const u32 GCRE_CONSTANT* RANK = as_const(a.rank);
 
-  const int nchunks = a.W32p / WC;
-  const u32* mask_tile = a.masks + (size_t)(a.kt0 + kt) * PT;   // column offset of this permutation tile
-
-  // ---- mask staging: chunk c = rows [c*WC, c*WC+WC) x PT columns, row-major in LDS ----
-  u32x4 stage[VEC];
-  u32 voff[VEC];
-#pragma unroll
-  for (int i = 0; i < VEC; i++) {
-    const int e = tid + i * kFamBlock;
-    voff[i] = (u32)((e / (PT / 4)) * a.Kpad + (e % (PT / 4)) * 4) * 4u;
-  }
-  const size_t chunk_bytes = (size_t)WC * a.Kpad * 4;
-  auto stage_load = [&](int c) {
-    const char* cb = (const char*)mask_tile + (size_t)c * chunk_bytes;
-#pragma unroll
-    for (int i = 0; i < VEC; i++) stage[i] = *(const u32x4*)(cb + voff[i]);
-  };
-  auto stage_store = [&](int buf) {
-#pragma unroll
-    for (int i = 0; i < VEC; i++) *(u32x4*)(&lds[buf][(tid + i * kFamBlock) * 4]) = stage[i];
-  };
-
-  stage_load(0);
-  stage_store(0);
-  __syncthreads();
-  int buf = 0;
+  MaskStream ms(lds, a.masks + (size_t)(a.kt0 + kt) * PT, a.Kpad);   // column offset of this permutation tile
 
   const size_t rs = (size_t)M * a.W32p;   // dwords per set: (+) half, then (-) half (method 2)
 
   for (i64 pt = g; pt < a.npt; pt += a.pgroups) {
     const i64 qbase = pt * TPB + (i64)wave * TPW;
-    u32 acc[M][TPW][R];
-#pragma unroll
-    for (int h = 0; h < M; h++)
-#pragma unroll
-      for (int t = 0; t < TPW; t++)
-#pragma unroll
-        for (int j = 0; j < R; j++) acc[h][t][j] = 0u;
-
     // row offsets of this wave's sets, wave-uniform; a set past the end reads the last set's row (its result is dropped)
     size_t o[TPW];
 #pragma unroll
@@ -115,77 +56,16 @@ __global__ __launch_bounds__(kFamBlock, OCC) void k_family_null(const FamilyNull
       const i64 q = qbase + t < a.nsets ? qbase + t : a.nsets - 1;
       o[t] = (size_t)q * rs;
     }
-
-    // software pipeline over the flattened (chunk, set) sequence, as k_set_null
-    u32x4 nx[M];
-    auto fetch = [&](int c, int t) {
-      const u32 FAM_CONSTANT* b = ROWS + o[t] + (size_t)c * WC;
-      nx[0] = *(const u32x4 FAM_CONSTANT*)b;
-      if constexpr (M == 2) nx[1] = *(const u32x4 FAM_CONSTANT*)(b + a.W32p);
-    };
-    fetch(0, 0);
-
-    for (int c = 0; c < nchunks; c++) {
-      const int cn = (c + 1 == nchunks) ? 0 : c + 1;
-      stage_load(cn);   // the next chunk of this block's (periodic) mask stream
-
-      u32 m[WC][R];
-#pragma unroll
-      for (int w = 0; w < WC; w++) {
-        const u32* row = &lds[buf][w * PT];
-        const u32x4 v0 = *(const u32x4*)(row + lane * 4);
-        const u32x4 v1 = *(const u32x4*)(row + 256 + lane * 4);
-        m[w][0] = v0.x; m[w][1] = v0.y; m[w][2] = v0.z; m[w][3] = v0.w;
-        m[w][4] = v1.x; m[w][5] = v1.y; m[w][6] = v1.z; m[w][7] = v1.w;
-      }
-
-#pragma unroll
-      for (int t = 0; t < TPW; t++) {
-        u32 jn[M][WC];
-#pragma unroll
-        for (int h = 0; h < M; h++)
-#pragma unroll
-          for (int w = 0; w < WC; w++) jn[h][w] = __builtin_amdgcn_readfirstlane(nx[h][w]);
-        if (t + 1 < TPW) fetch(c, t + 1);
-        else fetch(cn, 0);
-#pragma unroll
-        for (int h = 0; h < M; h++)
-#pragma unroll
-          for (int w = 0; w < WC; w++)
-#pragma unroll
-            for (int j = 0; j < R; j++) acc[h][t][j] += __builtin_popcount(jn[h][w] & m[w][j]);
-        __builtin_amdgcn_sched_barrier(0);   // keep each set's scalar loads in its own region
-      }
-
-      stage_store(buf ^ 1);
-      __syncthreads();
-      buf ^= 1;
-    }
+    const TileCounts<M, TPW> acc = count_tile<M, TPW>(ms, ROWS, o, a.W32p);
 
     // ---- null scores on each set's table diagonal, stored as they are: registers 0..3 are columns 4 lane .. 4 lane + 3 of
-    // the tile, registers 4..7 the same columns of its second half (k_set_null's layout) ----
+    // the tile, registers 4..7 the same columns of its second half (ct_col) ----
 #pragma unroll
     for (int t = 0; t < TPW; t++) {
       const i64 q = qbase + t;
       if (q >= a.nsets) continue;   // wave-uniform
       u32 v[R];
-      if constexpr (M == 1) {
-        // the sanitised f32 table: non-negative floats, ordered as their bit patterns
-        const u32* diag = (const u32*)a.t32 + fam_diag(TOT[q]);
-#pragma unroll
-        for (int j = 0; j < R; j++) v[j] = diag[acc[0][t][j]];
-      } else {
-        // vtmax[pp][|P| - pp] + vtmax[|N| - pn][pn] (d64n: d64, or its mirror image where vtmax is not symmetric), folded as
-        // k_null folds it
-        const double* dp = a.d64 + fam_diag(TOT[2 * q]);
-        const double* dn = a.d64n + fam_diag(TOT[2 * q + 1]);
-#pragma unroll
-        for (int j = 0; j < R; j++) {
-          float f = (float)(dp[acc[0][t][j]] + dn[acc[M - 1][t][j]]);
-          f = (f > 0.0f) ? f : 0.0f;   // NaN and negatives fold as 0, as into the join's maxima
-          v[j] = __float_as_uint(f);
-        }
-      }
+      null_scores<M>(a.t32, a.d64, a.d64n, TOT, q, acc.v[0][t], acc.v[M - 1][t], v);
       // rank < nsets and (kt + 1) * PT <= stride: inside N [nsets][stride]
       u32* dst = a.N + ((size_t)RANK[q] * (size_t)a.stride + (size_t)kt * PT + (size_t)lane * 4);
       u32x4 lo, hi;
@@ -210,7 +90,7 @@ __global__ __launch_bounds__(kFamScanBlock) void k_family_scan(const FamilyScanA
   const bool live = col < a.live;
   const size_t c = live ? (size_t)col : 0;   // (a lane past the end reads column 0 and never counts or stores)
   const int lane = threadIdx.x & 63;
-  const u32 FAM_CONSTANT* META = fam_const(a.meta);
+  const u32 GCRE_CONSTANT* META = as_const(a.meta);
   u32 run = 0u;
   u32 top[KM];
 #pragma unroll
@@ -309,15 +189,15 @@ __global__ __launch_bounds__(kFamHistBlock) void k_family_hist(const FamilyHistA
 
 hipError_t launch_family_null(const FamilyNullArgs& a, int method, hipStream_t stream) {
   if (a.nsets <= 0 || a.nkt <= 0) return hipSuccess;
-  if ((int64_t)a.nkt * a.pgroups > 0x7fffffff || a.pgroups < 1 || a.W32p % kFamWC != 0 || a.kt0 < 0 ||
-      (int64_t)(a.kt0 + a.nkt) * kFamPT > a.Kpad || a.stride != (int64_t)a.nkt * kFamPT)
+  if ((int64_t)a.nkt * a.pgroups > 0x7fffffff || a.pgroups < 1 || a.W32p % kCtWC != 0 || a.kt0 < 0 ||
+      (int64_t)(a.kt0 + a.nkt) * kCtPT > a.Kpad || a.stride != (int64_t)a.nkt * kCtPT)
     return hipErrorInvalidValue;
   const dim3 grid((unsigned)(a.nkt * a.pgroups));
   if (g_launch_trace)   // a block walks `per` set tiles
     fprintf(stderr, "launch k_family_null npt=%lld pgroups=%d per=%lld\n", (long long)a.npt, a.pgroups,
             (long long)((a.npt + a.pgroups - 1) / a.pgroups));
-  if (method == 1) hipLaunchKernelGGL((k_family_null<1, 4, 4>), grid, dim3(kFamBlock), 0, stream, a);
-  else hipLaunchKernelGGL((k_family_null<2, 2, 4>), grid, dim3(kFamBlock), 0, stream, a);
+  if (method == 1) hipLaunchKernelGGL((k_family_null<1, 4, 4>), grid, dim3(kCtBlock), 0, stream, a);
+  else hipLaunchKernelGGL((k_family_null<2, 2, 4>), grid, dim3(kCtBlock), 0, stream, a);
   return hipGetLastError();
 }
 

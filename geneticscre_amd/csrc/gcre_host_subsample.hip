@@ -117,7 +117,7 @@ struct SubsampleStage final : SetStage {
     a.W32p = 2 * g.Wp;
     a.n_cases = g.n_cases;
     a.n_cut = n_cut;
-    const int64_t tpb = subsample_tile_sets(M);
+    const int64_t tpb = set_null_tile_sets(M);
     a.npt = (V + tpb - 1) / tpb;
 
     const double per_draw = gcre_subsample::subsample_draw_bytes(r.in, ask(c));

@@ -670,7 +670,7 @@ struct SubsampleArgs {
   double* scores_a;             // optional [nsets][stride]: column = draw of the slab
   double* scores_b;             // optional, with dvt_b
   int64_t nsets;
-  int64_t npt;                  // set tiles (subsample_tile_sets sets each)
+  int64_t npt;                  // set tiles (set_null_tile_sets sets each)
   int64_t stride;               // columns of scores_a / scores_b, >= Kpad
   int W32p, Kpad, K;            // K: draws of the slab
   int nkt;                      // draw tiles of kSetPermTile
@@ -678,7 +678,6 @@ struct SubsampleArgs {
   int n_cases;                  // columns below it are the cases
   int n_cut;
 };
-int subsample_tile_sets(int method);
 hipError_t launch_subsample_masks(uint64_t seed1, int64_t b0, int nb, int n_cases, int n_ctrls, int m_cases, int m_ctrls, int W32p,
                                   int Kpad, uint32_t* masks, hipStream_t stream);
 hipError_t launch_subsample_null(const SubsampleArgs& a, int method, hipStream_t stream);
@@ -686,7 +685,7 @@ hipError_t launch_subsample_null(const SubsampleArgs& a, int method, hipStream_t
 // ---- sequential permutation p-values: every set stops at its h-th exceedance (gcre_sequential.hip) ----
 // One batch of permutations [r0, r0 + nb), never resident beyond it.  k_seq_masks writes their masks by the rule of
 // gcre_sequential.h (k_generate_masks' rule) in SetNullArgs' mask layout, [W32p][stride] dwords with the columns nb .. stride-1
-// and the rows beyond the patients zero.  k_seq_null runs k_set_null's count loop over the sets of the active list and writes,
+// and the rows beyond the patients zero.  k_seq_null runs the count loop of gcre_count_tile.h over the sets of the active list and writes,
 // per active slot, the batch's bit row; k_seq_retire stops the slots whose h-th exceedance lies in it and lists the others.
 struct SeqMaskArgs {
   uint64_t seed;

@@ -14,28 +14,15 @@
 //     barrier per chunk) and shared by the 4 waves of a block; each wave keeps its 8*R mask registers
 //     for TPW paths, so one LDS read feeds 2*TPW VALU ops;
 //   * a block stays on one permutation tile for all its path tiles: 64*R atomics per block at the end.
-#include "gcre_kernels.h"
+#include "gcre_count_tile.h"   // u32 .. u32x4, GCRE_CONSTANT, as_const
 
 namespace gcre {
 
 static inline int64_t hmin(int64_t a, int64_t b) { return a < b ? a : b; }
 bool g_launch_trace = false;
 
-typedef uint32_t u32;
-typedef uint64_t u64;
-typedef int64_t i64;
 typedef u32 __attribute__((ext_vector_type(2))) u32x2;
-typedef u32 __attribute__((ext_vector_type(4))) u32x4;
 typedef u32 __attribute__((ext_vector_type(8))) u32x8;
-
-#define GCRE_CONSTANT __attribute__((address_space(4)))
-
-// Read-only kernel inputs are addressed through the constant address space so that wave-uniform
-// addresses select scalar loads.
-template <typename T>
-__device__ __forceinline__ const T GCRE_CONSTANT* as_const(const T* p) {
-  return (const T GCRE_CONSTANT*)p;
-}
 
 __device__ __forceinline__ u32 diag_offset(u32 t) { return (u32)(((u64)t * (u64)(t + 1)) >> 1); }
 

@@ -14,17 +14,10 @@
 //                     the slab and stored at its end; at the last row of a tie group the lanes whose minimum is <= the
 //                     group's c are counted (a ballot; the counts of 64 rows leave a wave as one atomic instruction)
 // Every global write is a plain vector store or a vector atomic.
-#include "gcre_kernels.h"
+#include "gcre_count_tile.h"   // GCRE_CONSTANT
 
 namespace gcre {
 namespace {
-
-typedef uint32_t u32;
-typedef uint64_t u64;
-typedef int64_t i64;
-typedef u32 __attribute__((ext_vector_type(4))) u32x4;
-
-#define MINP_CONSTANT __attribute__((address_space(4)))
 
 constexpr int kRankBlock = 1024;                  // 16 waves sort one chunk: 16 values per thread
 constexpr int kRankE = kMinpChunk / kRankBlock;   // values of a chunk per thread: the strides below it stay in registers
@@ -173,7 +166,7 @@ __global__ __launch_bounds__(kScanBlock) void k_minp_scan(const MinpScanArgs a) 
   const bool live = col < a.K;
   const size_t c = live ? (size_t)col : 0;   // (a lane past the end reads column 0 and never counts or stores)
   const int lane = threadIdx.x & 63;
-  const u32 MINP_CONSTANT* META = (const u32 MINP_CONSTANT*)a.meta;
+  const u32 GCRE_CONSTANT* META = (const u32 GCRE_CONSTANT*)a.meta;
   u32 run = a.q[c];
   for (i64 r0 = 0; r0 < a.nsets; r0 += 64) {
     u32 mine = 0u;   // the count of row r0 + lane, 0 unless that row ends a group

@@ -13,44 +13,21 @@
 // k_prefix_rows is k_set_residual's mapping (gcre_given.hip), lanes over the dwords of a row, with one wave per set and
 // 64-dword stretch of the row: a wave's walk over the members is a chain of dependent loads, so the stretches of a row go to
 // waves of their own.
-// k_prefix_null is k_set_null's loop (gcre_sets.hip) with the sets of a wave's tile replaced by consecutive steps of ONE set:
-// lanes own 8 permutations, the mask tile goes through LDS and is shared by the block's four waves, a block stays on one
-// permutation tile, and the running maximum over the steps stays in registers.  Every global write is a vector store or a
-// vector atomic.
-#include "gcre_kernels.h"
+// k_prefix_null counts with count_tile (gcre_count_tile.h), the rows of a wave's tile being consecutive steps of ONE set;
+// the running maximum over the steps stays in registers.  Every global write is a vector store or a vector atomic.
+#include "gcre_count_tile.h"
 
 namespace gcre {
 namespace {
 
-typedef uint32_t u32;
-typedef uint64_t u64;
-typedef int64_t i64;
-typedef u32 __attribute__((ext_vector_type(4))) u32x4;
-
-// wave-uniform read-only inputs through the constant address space: scalar loads
-#define PREFIX_CONSTANT __attribute__((address_space(4)))
-template <typename T>
-__device__ __forceinline__ const T PREFIX_CONSTANT* prefix_const(const T* p) {
-  return (const T PREFIX_CONSTANT*)p;
-}
-
-__device__ __forceinline__ u64 prefix_diag(u64 t) { return (t * (t + 1)) >> 1; }
-
-constexpr int kPfxBlock = 256;                // threads per block: four waves, one set each
-constexpr int kPfxR = 8;                      // permutations per lane
-constexpr int kPfxPT = 64 * kPfxR;            // permutations per tile
-constexpr int kPfxWC = 4;                     // mask dwords per staged chunk
-static_assert(kPfxPT == kSetPermTile, "tile");
-
-// k_set_null's column layout: register j of a lane holds permutations {4 lane .. 4 lane + 3} and {256 + 4 lane ..}
-__device__ __forceinline__ int pfx_col(int lane, int j) { return (j >> 2) * 256 + lane * 4 + (j & 3); }
+constexpr int kPfxRowsBlock = 256;            // threads per block of k_prefix_rows: four waves
 
 }  // namespace
 
 template <int M>
-__global__ __launch_bounds__(kPfxBlock) void k_prefix_rows(const PrefixArgs a) {
+__global__ __launch_bounds__(kPfxRowsBlock) void k_prefix_rows(const PrefixArgs a) {
   const int nch = (a.W32p + 63) / 64;   // 64-dword stretches of a row: one wave each
-  const i64 wv = (i64)blockIdx.x * (kPfxBlock / 64) + (threadIdx.x >> 6);
+  const i64 wv = (i64)blockIdx.x * (kPfxRowsBlock / 64) + (threadIdx.x >> 6);
   const i64 e = wv / nch;
   const int lane = threadIdx.x & 63;
   if (e >= a.nslots) return;   // the whole wave
@@ -149,14 +126,10 @@ __global__ __launch_bounds__(256) void k_prefix_pick(const PrefixArgs a) {
 
 // M method, TPW steps per wave and step tile, OCC waves per SIMD the register allocation must admit
 template <int M, int TPW, int OCC>
-__global__ __launch_bounds__(kPfxBlock, OCC) void k_prefix_null(const PrefixArgs a) {
-  constexpr int R = kPfxR, WC = kPfxWC, PT = kPfxPT;
-  constexpr int NW = kPfxBlock / 64;
-  constexpr int CHUNK = WC * PT;                // dwords per staged mask chunk
-  constexpr int VEC = CHUNK / 4 / kPfxBlock;    // uint4 per thread per chunk
-  static_assert(VEC >= 1 && CHUNK % (4 * kPfxBlock) == 0, "staging shape");
+__global__ __launch_bounds__(kCtBlock, OCC) void k_prefix_null(const PrefixArgs a) {
+  constexpr int R = kCtR, PT = kCtPT, NW = kCtWaves;
 
-  __shared__ __attribute__((aligned(16))) u32 lds[2][CHUNK];
+  __shared__ __attribute__((aligned(16))) u32 lds[2][kCtChunk];
   __shared__ u32 red[NW][PT];
 
   const int tid = threadIdx.x;
@@ -165,9 +138,9 @@ __global__ __launch_bounds__(kPfxBlock, OCC) void k_prefix_null(const PrefixArgs
   const int kt = blockIdx.x % a.nkt;
   const int g = blockIdx.x / a.nkt;
 
-  const u32 PREFIX_CONSTANT* ROWS = prefix_const(a.rows);
-  const u32 PREFIX_CONSTANT* TOT = prefix_const(a.tot);
-  const PrefixWaveDev PREFIX_CONSTANT* WV = prefix_const(a.waves) + (size_t)g * NW;
+  const u32 GCRE_CONSTANT* ROWS = as_const(a.rows);
+  const u32 GCRE_CONSTANT* TOT = as_const(a.tot);
+  const PrefixWaveDev GCRE_CONSTANT* WV = as_const(a.waves) + (size_t)g * NW;
 
   // this wave's set, and the step tiles the block walks: those of its first wave, the longest of the four (gcre_prefix.h)
   const int slot = WV[wave].slot;
@@ -175,50 +148,17 @@ __global__ __launch_bounds__(kPfxBlock, OCC) void k_prefix_null(const PrefixArgs
   const i64 row0 = WV[wave].row0;
   const int ntiles = (WV[0].steps + TPW - 1) / TPW;
 
-  const int nchunks = a.W32p / WC;
-  const u32* mask_tile = a.masks + (size_t)kt * PT;   // column offset of this permutation tile
-
-  // ---- mask staging: chunk c = rows [c*WC, c*WC+WC) x PT columns, row-major in LDS ----
-  u32x4 stage[VEC];
-  u32 voff[VEC];
-#pragma unroll
-  for (int i = 0; i < VEC; i++) {
-    const int e = tid + i * kPfxBlock;
-    voff[i] = (u32)((e / (PT / 4)) * a.Kpad + (e % (PT / 4)) * 4) * 4u;
-  }
-  const size_t chunk_bytes = (size_t)WC * a.Kpad * 4;
-  auto stage_load = [&](int c) {
-    const char* cb = (const char*)mask_tile + (size_t)c * chunk_bytes;
-#pragma unroll
-    for (int i = 0; i < VEC; i++) stage[i] = *(const u32x4*)(cb + voff[i]);
-  };
-  auto stage_store = [&](int buf) {
-#pragma unroll
-    for (int i = 0; i < VEC; i++) *(u32x4*)(&lds[buf][(tid + i * kPfxBlock) * 4]) = stage[i];
-  };
-
   // the running maximum over this wave's steps, per permutation of the lane
   u32 tmax[R];
 #pragma unroll
   for (int j = 0; j < R; j++) tmax[j] = 0u;
 
-  stage_load(0);
-  stage_store(0);
-  __syncthreads();
-  int buf = 0;
+  MaskStream ms(lds, a.masks + (size_t)kt * PT, a.Kpad);   // column offset of this permutation tile
 
   const size_t rs = (size_t)M * a.W32p;   // dwords per step row: (+) half, then (-) half (method 2)
 
   for (int st = 0; st < ntiles; st++) {
     const int kbase = st * TPW;
-    u32 acc[M][TPW][R];
-#pragma unroll
-    for (int h = 0; h < M; h++)
-#pragma unroll
-      for (int t = 0; t < TPW; t++)
-#pragma unroll
-        for (int j = 0; j < R; j++) acc[h][t][j] = 0u;
-
     // rows of this wave's steps, wave-uniform; a step past the set's end reads the set's last row and a wave without a
     // set the slab's first row (their results are dropped)
     i64 q[TPW];
@@ -230,84 +170,25 @@ __global__ __launch_bounds__(kPfxBlock, OCC) void k_prefix_null(const PrefixArgs
       o[t] = (size_t)q[t] * rs;
     }
 
-    // software pipeline over the flattened (chunk, step) sequence, as in k_set_null
-    u32x4 nx[M];
-    auto fetch = [&](int c, int t) {
-      const u32 PREFIX_CONSTANT* b = ROWS + o[t] + (size_t)c * WC;
-      nx[0] = *(const u32x4 PREFIX_CONSTANT*)b;
-      if constexpr (M == 2) nx[1] = *(const u32x4 PREFIX_CONSTANT*)(b + a.W32p);
-    };
-    fetch(0, 0);
-
-    for (int c = 0; c < nchunks; c++) {
-      const int cn = (c + 1 == nchunks) ? 0 : c + 1;
-      stage_load(cn);   // the next chunk of this block's (periodic) mask stream
-
-      u32 m[WC][R];
-#pragma unroll
-      for (int w = 0; w < WC; w++) {
-        const u32* row = &lds[buf][w * PT];
-        const u32x4 v0 = *(const u32x4*)(row + lane * 4);
-        const u32x4 v1 = *(const u32x4*)(row + 256 + lane * 4);
-        m[w][0] = v0.x; m[w][1] = v0.y; m[w][2] = v0.z; m[w][3] = v0.w;
-        m[w][4] = v1.x; m[w][5] = v1.y; m[w][6] = v1.z; m[w][7] = v1.w;
-      }
-
-#pragma unroll
-      for (int t = 0; t < TPW; t++) {
-        u32 jn[M][WC];
-#pragma unroll
-        for (int h = 0; h < M; h++)
-#pragma unroll
-          for (int w = 0; w < WC; w++) jn[h][w] = __builtin_amdgcn_readfirstlane(nx[h][w]);
-        if (t + 1 < TPW) fetch(c, t + 1);
-        else fetch(cn, 0);
-#pragma unroll
-        for (int h = 0; h < M; h++)
-#pragma unroll
-          for (int w = 0; w < WC; w++)
-#pragma unroll
-            for (int j = 0; j < R; j++) acc[h][t][j] += __builtin_popcount(jn[h][w] & m[w][j]);
-        __builtin_amdgcn_sched_barrier(0);   // keep each step's scalar loads in its own region
-      }
-
-      stage_store(buf ^ 1);
-      __syncthreads();
-      buf ^= 1;
-    }
+    const TileCounts<M, TPW> acc = count_tile<M, TPW>(ms, ROWS, o, a.W32p);
 
     // ---- null scores on each step's table diagonal, folded into the running maximum ----
 #pragma unroll
     for (int t = 0; t < TPW; t++) {
       if (kbase + t >= nsteps) continue;   // wave-uniform
-      if constexpr (M == 1) {
-        // the sanitised f32 table: non-negative floats, ordered as their bit patterns
-        const u32* diag = (const u32*)a.t32 + prefix_diag(TOT[q[t]]);
+      u32 v[R];
+      null_scores<M>(a.t32, a.d64, a.d64n, TOT, q[t], acc.v[0][t], acc.v[M - 1][t], v);
 #pragma unroll
-        for (int j = 0; j < R; j++) {
-          const u32 v = diag[acc[0][t][j]];
-          tmax[j] = (v > tmax[j]) ? v : tmax[j];
-        }
-      } else {
-        const double* dp = a.d64 + prefix_diag(TOT[2 * q[t]]);
-        const double* dn = a.d64n + prefix_diag(TOT[2 * q[t] + 1]);
-#pragma unroll
-        for (int j = 0; j < R; j++) {
-          float f = (float)(dp[acc[0][t][j]] + dn[acc[M - 1][t][j]]);
-          f = (f > 0.0f) ? f : 0.0f;   // NaN and negatives fold as 0, as into the join's maxima
-          const u32 v = __float_as_uint(f);
-          tmax[j] = (v > tmax[j]) ? v : tmax[j];
-        }
-      }
+      for (int j = 0; j < R; j++) tmax[j] = (v[j] > tmax[j]) ? v[j] : tmax[j];
     }
   }
 
   // ---- the set's end: n_ge by ballot over the live permutations, T into the null_max slab ----
   bool live[R];
 #pragma unroll
-  for (int j = 0; j < R; j++) live[j] = kt * PT + pfx_col(lane, j) < a.K;   // the padding up to Kpad never counts
+  for (int j = 0; j < R; j++) live[j] = kt * PT + ct_col(lane, j) < a.K;   // the padding up to Kpad never counts
   if (slot >= 0) {   // wave-uniform
-    const u32 thr = prefix_const(a.thr)[slot];
+    const u32 thr = as_const(a.thr)[slot];
     u32 ge = 0;
 #pragma unroll
     for (int j = 0; j < R; j++) ge += (u32)__popcll(__ballot(live[j] && tmax[j] >= thr));
@@ -325,9 +206,9 @@ __global__ __launch_bounds__(kPfxBlock, OCC) void k_prefix_null(const PrefixArgs
   if (!a.fam_bits) return;   // uniform over the grid
   // ---- block reduction, then one atomic per permutation ----
 #pragma unroll
-  for (int j = 0; j < R; j++) red[wave][pfx_col(lane, j)] = (slot >= 0 && live[j]) ? tmax[j] : 0u;
+  for (int j = 0; j < R; j++) red[wave][ct_col(lane, j)] = (slot >= 0 && live[j]) ? tmax[j] : 0u;
   __syncthreads();
-  for (int i = tid; i < PT; i += kPfxBlock) {
+  for (int i = tid; i < PT; i += kCtBlock) {
     u32 v = red[0][i];
 #pragma unroll
     for (int w = 1; w < NW; w++) v = (red[w][i] > v) ? red[w][i] : v;
@@ -340,11 +221,11 @@ hipError_t launch_prefix_rows(const PrefixArgs& a, int method, hipStream_t strea
   if (a.nslots == 0) return hipSuccess;
   if (a.nslots < 0 || a.W2 < 1 || a.W32p < a.W2 || (method != 1 && method != 2)) return hipErrorInvalidValue;
   const i64 waves = a.nslots * ((a.W32p + 63) / 64);
-  const i64 blocks = (waves + kPfxBlock / 64 - 1) / (kPfxBlock / 64);
+  const i64 blocks = (waves + kPfxRowsBlock / 64 - 1) / (kPfxRowsBlock / 64);
   if (blocks > 0x7fffffff) return hipErrorInvalidValue;
   if (g_launch_trace) fprintf(stderr, "launch k_prefix_rows slots=%lld rows=%lld\n", (long long)a.nslots, (long long)a.nrows);
-  if (method == 1) hipLaunchKernelGGL(k_prefix_rows<1>, dim3((unsigned)blocks), dim3(kPfxBlock), 0, stream, a);
-  else hipLaunchKernelGGL(k_prefix_rows<2>, dim3((unsigned)blocks), dim3(kPfxBlock), 0, stream, a);
+  if (method == 1) hipLaunchKernelGGL(k_prefix_rows<1>, dim3((unsigned)blocks), dim3(kPfxRowsBlock), 0, stream, a);
+  else hipLaunchKernelGGL(k_prefix_rows<2>, dim3((unsigned)blocks), dim3(kPfxRowsBlock), 0, stream, a);
   return hipGetLastError();
 }
 
@@ -359,14 +240,14 @@ hipError_t launch_prefix_pick(const PrefixArgs& a, int method, hipStream_t strea
 
 hipError_t launch_prefix_null(const PrefixArgs& a, int method, hipStream_t stream) {
   if (a.nslots == 0 || a.K == 0) return hipSuccess;
-  if (a.nblocks < 1 || (int64_t)a.nkt * a.nblocks > 0x7fffffff || a.W32p % kPfxWC != 0 || a.nkt < 1 ||
-      (int64_t)a.nkt * kPfxPT > a.Kpad || (method != 1 && method != 2))
+  if (a.nblocks < 1 || (int64_t)a.nkt * a.nblocks > 0x7fffffff || a.W32p % kCtWC != 0 || a.nkt < 1 ||
+      (int64_t)a.nkt * kCtPT > a.Kpad || (method != 1 && method != 2))
     return hipErrorInvalidValue;
   const dim3 grid((unsigned)((int64_t)a.nkt * a.nblocks));
   if (g_launch_trace)
     fprintf(stderr, "launch k_prefix_null slots=%lld rows=%lld blocks=%d nkt=%d\n", (long long)a.nslots, (long long)a.nrows, a.nblocks, a.nkt);
-  if (method == 1) hipLaunchKernelGGL((k_prefix_null<1, 4, 4>), grid, dim3(kPfxBlock), 0, stream, a);
-  else hipLaunchKernelGGL((k_prefix_null<2, 2, 4>), grid, dim3(kPfxBlock), 0, stream, a);
+  if (method == 1) hipLaunchKernelGGL((k_prefix_null<1, 4, 4>), grid, dim3(kCtBlock), 0, stream, a);
+  else hipLaunchKernelGGL((k_prefix_null<2, 2, 4>), grid, dim3(kCtBlock), 0, stream, a);
   return hipGetLastError();
 }
 

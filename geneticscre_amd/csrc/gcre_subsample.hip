@@ -5,12 +5,14 @@
 //   * k_subsample_null   per (set, draw): the AND+popcount of the set's union row(s) with S_b, cases and controls apart; the
 //                        complement's counts as the set's totals minus them; both scores from the f64 tables of the half
 //                        cohorts; per cut the draws in which half A, half B and both reach it
-// k_subsample_null is k_set_null's mapping (gcre_sets.hip): lanes own draws (8 per lane), a set's words are wave-uniform
-// (scalar loads), the mask tile goes through LDS and is shared by the block's four waves.  It keeps two accumulators per
+// k_subsample_null has the mapping, the constants and the mask stream of gcre_count_tile.h: lanes own draws (8 per lane), a
+// set's words are wave-uniform (scalar loads), the mask tile goes through LDS and is shared by the block's four waves.  Its
+// chunk loop is its own, count_tile's with another accumulate step (a count_tile that takes the step as a functor cost
+// k_set_null 15 registers when it was tried, and this kernel stands at 243-248 of 256): it keeps two accumulators per
 // half-row; which one a mask dword feeds is wave-uniform by its word index, so the chunks left of the one that holds patient
 // n_cases feed the cases, the chunks right of it the controls, and only in that chunk is a set word split by constant masks.
 // Every global write is a vector store or a vector atomic.  The context-side entry is in gcre_host_subsample.hip.
-#include "gcre_kernels.h"
+#include "gcre_count_tile.h"
 #include "gcre_subsample.h"
 
 #include <type_traits>
@@ -18,31 +20,10 @@
 namespace gcre {
 namespace {
 
-typedef uint32_t u32;
-typedef uint64_t u64;
-typedef int64_t i64;
-typedef u32 __attribute__((ext_vector_type(4))) u32x4;
-
-// wave-uniform read-only inputs through the constant address space: scalar loads
-#define SUB_CONSTANT __attribute__((address_space(4)))
-template <typename T>
-__device__ __forceinline__ const T SUB_CONSTANT* sub_const(const T* p) {
-  return (const T SUB_CONSTANT*)p;
-}
-
-__device__ __forceinline__ u64 sub_diag(u64 t) { return (t * (t + 1)) >> 1; }
-
 // the low x bits set (x <= 0: none, x >= 32: all)
 __device__ __forceinline__ u32 sub_below(int x) { return x <= 0 ? 0u : (x >= 32 ? 0xffffffffu : ((1u << x) - 1u)); }
 
-constexpr int kSubBlock = 256;                // threads per block
-constexpr int kSubR = 8;                      // draws per lane
-constexpr int kSubPT = 64 * kSubR;            // draws per tile
-constexpr int kSubWC = 4;                     // mask dwords per staged chunk (one s_load_dwordx4 per set and half)
-static_assert(kSubPT == kSetPermTile && kSubPT == gcre_subsample::kSubsampleTile, "k_set_null's tile");
-
-// column of the draw tile that register j of a lane holds (k_set_null's layout)
-__device__ __forceinline__ int sub_col(int lane, int j) { return (j >> 2) * 256 + lane * 4 + (j & 3); }
+static_assert(kCtPT == gcre_subsample::kSubsampleTile, "tile");
 
 }  // namespace
 
@@ -74,15 +55,11 @@ __global__ __launch_bounds__(64) void k_subsample_masks(uint64_t seed1, int64_t 
 
 // M method, TPW sets per wave and set tile, OCC waves per SIMD the register allocation must admit
 template <int M, int TPW, int OCC>
-__global__ __launch_bounds__(kSubBlock, OCC) void k_subsample_null(const SubsampleArgs a) {
-  constexpr int R = kSubR, WC = kSubWC, PT = kSubPT;
-  constexpr int NW = kSubBlock / 64;
-  constexpr int TPB = NW * TPW;
-  constexpr int CHUNK = WC * PT;                // dwords per staged mask chunk
-  constexpr int VEC = CHUNK / 4 / kSubBlock;    // uint4 per thread per chunk
-  static_assert(VEC >= 1 && CHUNK % (4 * kSubBlock) == 0, "staging shape");
+__global__ __launch_bounds__(kCtBlock, OCC) void k_subsample_null(const SubsampleArgs a) {
+  constexpr int R = kCtR, WC = kCtWC, PT = kCtPT;
+  constexpr int TPB = kCtWaves * TPW;
 
-  __shared__ __attribute__((aligned(16))) u32 lds[2][CHUNK];
+  __shared__ __attribute__((aligned(16))) u32 lds[2][kCtChunk];
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -90,12 +67,11 @@ __global__ __launch_bounds__(kSubBlock, OCC) void k_subsample_null(const Subsamp
   const int kt = blockIdx.x % a.nkt;
   const int g = blockIdx.x / a.nkt;
 
-  const u32 SUB_CONSTANT* ROWS = sub_const(a.rows);
-  const u32 SUB_CONSTANT* TOT = sub_const(a.tot);
-  const double SUB_CONSTANT* CUT = sub_const(a.cut);
+  const u32 GCRE_CONSTANT* ROWS = as_const(a.rows);
+  const u32 GCRE_CONSTANT* TOT = as_const(a.tot);
+  const double GCRE_CONSTANT* CUT = as_const(a.cut);
 
   const int nchunks = a.W32p / WC;
-  const u32* mask_tile = a.masks + (size_t)kt * PT;   // column offset of this draw tile
 
   // the chunk that holds patient n_cases, and per dword of it the bits that are cases
   const int cbx = (a.n_cases >> 5) / WC;
@@ -104,34 +80,12 @@ __global__ __launch_bounds__(kSubBlock, OCC) void k_subsample_null(const Subsamp
 #pragma unroll
   for (int w = 0; w < WC; w++) cm[w] = sub_below(a.n_cases - 32 * (cb * WC + w));
 
-  // ---- mask staging: chunk c = rows [c*WC, c*WC+WC) x PT columns, row-major in LDS (as k_set_null) ----
-  u32x4 stage[VEC];
-  u32 voff[VEC];
-#pragma unroll
-  for (int i = 0; i < VEC; i++) {
-    const int e = tid + i * kSubBlock;
-    voff[i] = (u32)((e / (PT / 4)) * a.Kpad + (e % (PT / 4)) * 4) * 4u;
-  }
-  const size_t chunk_bytes = (size_t)WC * a.Kpad * 4;
-  auto stage_load = [&](int c) {
-    const char* cbp = (const char*)mask_tile + (size_t)c * chunk_bytes;
-#pragma unroll
-    for (int i = 0; i < VEC; i++) stage[i] = *(const u32x4*)(cbp + voff[i]);
-  };
-  auto stage_store = [&](int buf) {
-#pragma unroll
-    for (int i = 0; i < VEC; i++) *(u32x4*)(&lds[buf][(tid + i * kSubBlock) * 4]) = stage[i];
-  };
-
   // whether the draw of each register is one of the K (the padding up to Kpad never counts, and is never looked up)
   bool live[R];
 #pragma unroll
-  for (int j = 0; j < R; j++) live[j] = kt * PT + sub_col(lane, j) < a.K;
+  for (int j = 0; j < R; j++) live[j] = kt * PT + ct_col(lane, j) < a.K;
 
-  stage_load(0);
-  stage_store(0);
-  __syncthreads();
-  int buf = 0;
+  MaskStream ms(lds, a.masks + (size_t)kt * PT, a.Kpad);   // column offset of this draw tile
 
   const size_t rs = (size_t)M * a.W32p;   // dwords per set: (+) half, then (-) half (method 2)
 
@@ -155,12 +109,12 @@ __global__ __launch_bounds__(kSubBlock, OCC) void k_subsample_null(const Subsamp
       o[t] = (size_t)q * rs;
     }
 
-    // software pipeline over the flattened (chunk, set) sequence, as k_set_null
+    // software pipeline over the flattened (chunk, set) sequence, as count_tile
     u32x4 nx[M];
     auto fetch = [&](int c, int t) {
-      const u32 SUB_CONSTANT* b = ROWS + o[t] + (size_t)c * WC;
-      nx[0] = *(const u32x4 SUB_CONSTANT*)b;
-      if constexpr (M == 2) nx[1] = *(const u32x4 SUB_CONSTANT*)(b + a.W32p);
+      const u32 GCRE_CONSTANT* b = ROWS + o[t] + (size_t)c * WC;
+      nx[0] = *(const u32x4 GCRE_CONSTANT*)b;
+      if constexpr (M == 2) nx[1] = *(const u32x4 GCRE_CONSTANT*)(b + a.W32p);
     };
     fetch(0, 0);
 
@@ -168,17 +122,10 @@ __global__ __launch_bounds__(kSubBlock, OCC) void k_subsample_null(const Subsamp
     auto chunk = [&](int c, auto side) {
       constexpr int SIDE = decltype(side)::value;
       const int cn = (c + 1 == nchunks) ? 0 : c + 1;
-      stage_load(cn);   // the next chunk of this block's (periodic) mask stream
+      ms.load(cn);   // the next chunk of the stream
 
       u32 m[WC][R];
-#pragma unroll
-      for (int w = 0; w < WC; w++) {
-        const u32* row = &lds[buf][w * PT];
-        const u32x4 v0 = *(const u32x4*)(row + lane * 4);
-        const u32x4 v1 = *(const u32x4*)(row + 256 + lane * 4);
-        m[w][0] = v0.x; m[w][1] = v0.y; m[w][2] = v0.z; m[w][3] = v0.w;
-        m[w][4] = v1.x; m[w][5] = v1.y; m[w][6] = v1.z; m[w][7] = v1.w;
-      }
+      ms.read(m);
 
 #pragma unroll
       for (int t = 0; t < TPW; t++) {
@@ -208,9 +155,7 @@ __global__ __launch_bounds__(kSubBlock, OCC) void k_subsample_null(const Subsamp
         __builtin_amdgcn_sched_barrier(0);   // keep each set's scalar loads in its own region
       }
 
-      stage_store(buf ^ 1);
-      __syncthreads();
-      buf ^= 1;
+      ms.store_flip();
     };
     for (int c = 0; c < cb; c++) chunk(c, std::integral_constant<int, 0>{});
     chunk(cb, std::integral_constant<int, 1>{});
@@ -221,24 +166,24 @@ __global__ __launch_bounds__(kSubBlock, OCC) void k_subsample_null(const Subsamp
     for (int t = 0; t < TPW; t++) {
       const i64 q = qbase + t;
       if (q >= a.nsets) continue;   // wave-uniform
-      const u32 SUB_CONSTANT* T = TOT + (size_t)q * (2 * M);
+      const u32 GCRE_CONSTANT* T = TOT + (size_t)q * (2 * M);
       double sa[R], sb[R];
 #pragma unroll
       for (int j = 0; j < R; j++) {
         // half A: table_a[cases of P][controls of P] (+ table_a[controls of N][cases of N], in this order)
         const u64 pc = acc[0][0][t][j], pt_ = acc[0][1][t][j];
-        sa[j] = a.dvt_a[live[j] ? sub_diag(pc + pt_) + pc : 0];
+        sa[j] = a.dvt_a[live[j] ? tri_index(pc + pt_) + pc : 0];
         if constexpr (M == 2) {
           const u64 nc = acc[1][0][t][j], nt = acc[1][1][t][j];
-          sa[j] = sa[j] + a.dvt_a[live[j] ? sub_diag(nc + nt) + nt : 0];
+          sa[j] = sa[j] + a.dvt_a[live[j] ? tri_index(nc + nt) + nt : 0];
         }
         sb[j] = 0.0;
         if (a.dvt_b) {              // uniform over the grid
           const u64 qc = (u64)T[0] - pc, qt = (u64)T[1] - pt_;
-          sb[j] = a.dvt_b[live[j] ? sub_diag(qc + qt) + qc : 0];
+          sb[j] = a.dvt_b[live[j] ? tri_index(qc + qt) + qc : 0];
           if constexpr (M == 2) {
             const u64 nc = (u64)T[2] - acc[1][0][t][j], nt = (u64)T[3] - acc[1][1][t][j];
-            sb[j] = sb[j] + a.dvt_b[live[j] ? sub_diag(nc + nt) + nt : 0];
+            sb[j] = sb[j] + a.dvt_b[live[j] ? tri_index(nc + nt) + nt : 0];
           }
         }
       }
@@ -266,19 +211,17 @@ __global__ __launch_bounds__(kSubBlock, OCC) void k_subsample_null(const Subsamp
         double* out = a.scores_a + (size_t)q * (size_t)a.stride + (size_t)kt * PT;
 #pragma unroll
         for (int j = 0; j < R; j++)
-          if (live[j]) out[sub_col(lane, j)] = sa[j];
+          if (live[j]) out[ct_col(lane, j)] = sa[j];
       }
       if (a.scores_b) {
         double* out = a.scores_b + (size_t)q * (size_t)a.stride + (size_t)kt * PT;
 #pragma unroll
         for (int j = 0; j < R; j++)
-          if (live[j]) out[sub_col(lane, j)] = sb[j];
+          if (live[j]) out[ct_col(lane, j)] = sb[j];
       }
     }
   }
 }
-
-int subsample_tile_sets(int method) { return (kSubBlock / 64) * (method == 1 ? 4 : 2); }
 
 hipError_t launch_subsample_masks(uint64_t seed1, int64_t b0, int nb, int n_cases, int n_ctrls, int m_cases, int m_ctrls, int W32p,
                                   int Kpad, uint32_t* masks, hipStream_t stream) {
@@ -292,15 +235,15 @@ hipError_t launch_subsample_masks(uint64_t seed1, int64_t b0, int nb, int n_case
 
 hipError_t launch_subsample_null(const SubsampleArgs& a, int method, hipStream_t stream) {
   if (a.nsets == 0 || a.K == 0) return hipSuccess;
-  if ((int64_t)a.nkt * a.pgroups > 0x7fffffff || a.W32p % kSubWC != 0 || a.W32p < kSubWC || a.Kpad % kSubPT != 0 ||
-      (int64_t)a.nkt * kSubPT > a.Kpad || a.K > a.Kpad || a.stride < a.Kpad || a.n_cut < 0 ||
+  if ((int64_t)a.nkt * a.pgroups > 0x7fffffff || a.W32p % kCtWC != 0 || a.W32p < kCtWC || a.Kpad % kCtPT != 0 ||
+      (int64_t)a.nkt * kCtPT > a.Kpad || a.K > a.Kpad || a.stride < a.Kpad || a.n_cut < 0 ||
       a.n_cut > gcre_subsample::kSubsampleMaxCuts || (a.n_cut > 0 && (!a.cut || !a.n_a)) || (a.dvt_b && a.n_cut > 0 && (!a.n_b || !a.n_both)))
     return hipErrorInvalidValue;
   const dim3 grid((unsigned)(a.nkt * a.pgroups));
   if (g_launch_trace)
     fprintf(stderr, "launch k_subsample_null npt=%lld pgroups=%d draws=%d cuts=%d\n", (long long)a.npt, a.pgroups, a.K, a.n_cut);
-  if (method == 1) hipLaunchKernelGGL((k_subsample_null<1, 4, 2>), grid, dim3(kSubBlock), 0, stream, a);
-  else hipLaunchKernelGGL((k_subsample_null<2, 2, 2>), grid, dim3(kSubBlock), 0, stream, a);
+  if (method == 1) hipLaunchKernelGGL((k_subsample_null<1, 4, 2>), grid, dim3(kCtBlock), 0, stream, a);
+  else hipLaunchKernelGGL((k_subsample_null<2, 2, 2>), grid, dim3(kCtBlock), 0, stream, a);
   return hipGetLastError();
 }
 
