@@ -102,12 +102,22 @@ struct ChunkInsp {
   bool in_recipe = false;     // ... into the kept set's recipe (not into the buffers below)
   bool flags_valid = false;   // host copy of the inspector's flag block
   bool win_valid = false;     // top-k winners
+  // An inspection that ran ahead leaves its selection OPEN (GCRE_SELECT_DEFER): the digit passes are queued on the selection
+  // stream, their state lands in h_state, and whoever replays the chunk next -- the launch, behind its null kernels, or the
+  // join's own call -- closes it.  A launch leaves the winners' copies PENDING in `win`: the join's own call unpacks them
+  bool sel_open = false;
+  bool win_pending = false;
+  SelectState* h_state = nullptr;   // pinned: the state's copy must not hold the host, and must not move with the entry
   uint32_t flags[kFlagWords] = {};
   Winners win;
   ChunkBufs bufs;
+  // the entry describes nothing any more (the buffers stay).  Not while win_pending: drop_launch waits for the copies first
+  void forget() { inspected = with_lists = flags_valid = win_valid = sel_open = false; }
   void release() {
     bufs.release();
-    inspected = with_lists = flags_valid = win_valid = false;
+    if (h_state) (void)hipHostFree(h_state);
+    h_state = nullptr;
+    forget();
   }
 };
 
@@ -228,6 +238,13 @@ struct gcre_ctx {
   hipStream_t sel_stream = nullptr;
   hipEvent_t ev_sel = nullptr, ev_sel_done = nullptr;
   bool sel_async = true;
+  // GCRE_SELECT_DEFER=0: an ahead inspection closes its selection itself, before its join is launched (the order until the
+  // launch learned to close it behind its null kernels; A/B runs, tests)
+  bool sel_defer = true;
+  // keys the radix select's candidate buffer holds (GCRE_SELECT_CAND; 256 KB): after two digit passes the keys that still
+  // matter are copied there and the other six passes read them instead of every key.  0, or GCRE_SELECT_PASSES=8: eight
+  // passes over all keys (A/B runs, tests)
+  int sel_cand = 32768;
   // The recipe gather of a pruned method-1 launch (k_fill_rec_segs) is read by the pruned kernels only, not by the warm-up
   // slice in front of them: it runs beside the slice on a stream of its own (GCRE_REC_STREAM=0: on the join's stream, in
   // front of the slice).  ev_rec_in: on the join's stream where the gather is queued -- behind the recipe copies, the
@@ -318,7 +335,7 @@ struct gcre_ctx {
   // per-join scratch
   ChunkBufs scratch;                 // a chunk's buffers when the inspection cache is off
   DevBuf<uint32_t> d_sel, d_small, d_chunk, d_rec_segs;
-  DevBuf<uint64_t> d_wkey, d_doff, d_scan, d_excess, d_excess_b;
+  DevBuf<uint64_t> d_wkey, d_cand, d_doff, d_scan, d_excess, d_excess_b;
   DevBuf<uint64_t> d_ie_timing;      // GCRE_IE_TIMING: the section counters of a diagnostics build's pruned kernels
 
   // count-plane buffers of freed path sets, kept for the next set that needs one (hipMalloc of tens of GB costs
@@ -446,6 +463,8 @@ struct gcre_uids {
     std::vector<Candidate> cands;
     DevBuf<uint32_t> d_null;              // Kpad running maxima + one word: the launch's look-up counter
     hipEvent_t done = nullptr;            // behind the last kernel of the launch (main stream)
+    hipEvent_t sel_done = nullptr;        // behind the winners' copies of the selections the launch closed (selection stream)
+    bool sel_pending = false;             // some chunk entry holds such copies (ChunkInsp::win_pending)
     gcre_profile prof{};                  // what the ahead inspection and the launch accumulated for this join
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_null, ev_stats;
   };

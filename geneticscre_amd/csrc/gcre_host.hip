@@ -650,14 +650,21 @@ int ensure_quads(gcre_ctx* c, const gcre_uids& u, gcre_uids::SegCache& sc, int64
 // `key` = the keys of the scored paths (a chunk's key buffer + its first scored path): the indices are relative to it.
 // Two halves, so that a caller with a read-back of its own (the inspector's flags) can fold the state's into it:
 // select_begin queues the eight digit passes (one read-back of the state they leave, gcre_kernels.hip) and the copy
-// of that state into *hs; select_finish -- after a stream synchronisation -- queues the collection of the winners.
+// of that state into *hs; select_finish -- after a stream synchronisation -- queues the collection of the winners, over all
+// keys whatever the digit passes read (the index-ordered tie cut needs every key of the tie class in place).
 int select_begin(gcre_ctx* c, const uint64_t* key, int64_t count, int k, SelectState* hs, hipStream_t sst) {
   *hs = SelectState{};
   if (count == 0 || k <= 0) return GCRE_OK;
   HIP_TRY(c, c->d_small.reserve(512));
   HIP_TRY(c, c->d_sel.reserve((size_t)k + 64));
   SelectState* d_state = (SelectState*)(c->d_small.p + 264);
-  HIP_TRY(c, launch_radix_select(key, count, std::min<int64_t>(k, count), c->d_small.p, d_state, sst));
+  // the candidates of the third to eighth digit pass (gcre_kernels.hip); 0: every pass reads all keys.  One buffer per
+  // context like the rest of the selection's scratch: it is written and read inside the digit passes of one selection,
+  // which the selection stream runs one after the other
+  const uint32_t cand_cap = (uint32_t)c->sel_cand;
+  if (cand_cap) HIP_TRY(c, c->d_cand.reserve(cand_cap));
+  HIP_TRY(c, launch_radix_select(key, count, std::min<int64_t>(k, count), c->d_small.p, d_state, cand_cap ? c->d_cand.p : nullptr,
+                                 cand_cap, c->d_small.p + 257, sst));
   HIP_TRY(c, hipMemcpyAsync(hs, d_state, sizeof *hs, hipMemcpyDeviceToHost, sst));
   return GCRE_OK;
 }
@@ -735,6 +742,11 @@ void drop_ahead(gcre_ctx* c) {
 // a launch nobody came for (another window, other operands, the pass ended): wait for its kernels, forget it
 void drop_launch(const gcre_uids* u) {
   if (u->launch.active && u->launch.done) (void)hipEventSynchronize(u->launch.done);
+  if (u->launch.sel_pending) {   // the winners' copies of the selections it closed land in the chunk entries
+    if (u->ctx && u->ctx->sel_stream) (void)hipStreamSynchronize(u->ctx->sel_stream);
+    for (ChunkInsp& ci : u->insp) ci.win_pending = false;
+    u->launch.sel_pending = false;
+  }
   u->launch.active = false;
   u->launch.cands.clear();
   if (u->ctx) {
@@ -756,7 +768,9 @@ void gcre_host::free_uids(gcre_uids* u) {
   drop_launch(u);
   u->launch.d_null.release();
   if (u->launch.done) (void)hipEventDestroy(u->launch.done);
+  if (u->launch.sel_done) (void)hipEventDestroy(u->launch.sel_done);
   if (u->ctx && u->ctx->stream) (void)hipStreamSynchronize(u->ctx->stream);
+  if (u->ctx && u->ctx->sel_stream) (void)hipStreamSynchronize(u->ctx->sel_stream);   // (an open selection's state lands in its chunk entry)
   if (u->ctx && u->ctx->insp_stream) (void)hipStreamSynchronize(u->ctx->insp_stream);
   if (u->ctx && u->ctx->rec_stream) (void)hipStreamSynchronize(u->ctx->rec_stream);   // (the gather reads the segment tables)
   if (u->ctx) {
@@ -1117,6 +1131,26 @@ int collect_hits(gcre_ctx* c, gcre_hits* h, const ChunkBufs& b, int64_t cb, int6
   return GCRE_OK;
 }
 
+// the unpacked winners of a chunk whose first scored path is joined path `first`, as candidates of their join
+void push_candidates(std::vector<Candidate>& cands, const Winners& win, int64_t first) {
+  for (uint32_t i = 0; i < win.n; i++)
+    cands.push_back(Candidate{key_to_score(win.key[i]), first + (int64_t)win.sel[i], (int32_t)win.r0[i], (int32_t)win.r1[i],
+                              (int32_t)win.cases[i], (int32_t)win.ctrls[i]});
+}
+
+// once the copies queue_winners queued have arrived (the caller waited for their stream)
+void unpack_winners(Winners& w) {
+  if (w.pack.empty()) return;
+  const size_t n = w.n;
+  const uint32_t* h32 = (const uint32_t*)(w.pack.data() + n);
+  w.key.assign(w.pack.data(), w.pack.data() + n);
+  w.cases.assign(h32, h32 + n);
+  w.ctrls.assign(h32 + n, h32 + 2 * n);
+  w.r0.assign(h32 + 2 * n, h32 + 3 * n);
+  w.r1.assign(h32 + 3 * n, h32 + 4 * n);
+  w.pack.clear();
+}
+
 // The tail of a join whose kernels were launched ahead (run_join, kLaunch): wait for them, copy the maxima out of the join
 // index's own array, merge the winners its inspection cached.
 int finish_launched(gcre_ctx* c, const JoinPlan& jp, gcre_result* out) {
@@ -1132,6 +1166,19 @@ int finish_launched(gcre_ctx* c, const JoinPlan& jp, gcre_result* out) {
   if (K > 0) HIP_TRY(c, hipMemcpyAsync(&lookups, L.d_null.p + Kpad, 4, hipMemcpyDeviceToHost, c->insp_stream));
   std::vector<Candidate> cands = std::move(L.cands);
   L.cands.clear();
+  if (L.sel_pending) {
+    // the selections the launch closed behind its null kernels: their winners' copies have been queued since, here they are
+    // unpacked, become candidates and go to the inspection cache -- which then holds what an ahead inspection used to leave
+    HIP_TRY(c, hipEventSynchronize(L.sel_done));
+    for (ChunkInsp& ci : jp.u->insp) {
+      if (!ci.win_pending) continue;
+      ci.win_pending = false;
+      unpack_winners(ci.win);
+      push_candidates(cands, ci.win, ci.cb + ci.s0);
+      ci.win_valid = true;
+    }
+    L.sel_pending = false;
+  }
   c->prof = L.prof;
   L.prof = gcre_profile{};
   if (jp.tally) {
@@ -1211,6 +1258,7 @@ struct JoinRun {
   int exchanges_done = 0;
   std::vector<Candidate> cands;
   double select_ms = 0, select_wait_ms = 0;
+  bool sel_abandoned = false;          // begin_join: the join forgot a chunk entry whose selection was still open
   JoinRun(gcre_ctx* c_, const JoinPlan& jp_, gcre_result* out_, JoinMode m) : c(c_), jp(jp_), out(out_), mode(m) {}
 };
 
@@ -1230,7 +1278,9 @@ struct ChunkRun {
   uint32_t *rowz = nullptr, *linfo = nullptr, *lover = nullptr, *slot = nullptr, *over = nullptr;
   size_t over_cap = 0;
   bool sel_begun = false, sel_done = false;
+  bool sel_left_open = false;          // kInspect: the digit passes are queued, whoever replays the chunk closes the selection
   hipStream_t sel_on = nullptr;        // the stream the selection runs on
+  SelectState* hs = nullptr;           // where the digit passes' state lands: the chunk entry's pinned copy, or the context's
   Winners win;
   bool win_from_cache = false;
   uint32_t flags[kFlagWords] = {};     // score_chunk_ie: the inspector's flag block
@@ -1376,27 +1426,15 @@ int queue_winners(gcre_ctx* c, const ChunkBufs& b, int64_t s0, uint32_t nsel, Wi
   return GCRE_OK;
 }
 
-// once the copies queue_winners queued have arrived (the caller waited for their stream)
-void unpack_winners(Winners& w) {
-  if (w.pack.empty()) return;
-  const size_t n = w.n;
-  const uint32_t* h32 = (const uint32_t*)(w.pack.data() + n);
-  w.key.assign(w.pack.data(), w.pack.data() + n);
-  w.cases.assign(h32, h32 + n);
-  w.ctrls.assign(h32 + n, h32 + 2 * n);
-  w.r0.assign(h32 + 2 * n, h32 + 3 * n);
-  w.r1.assign(h32 + 3 * n, h32 + 4 * n);
-  w.pack.clear();
-}
-
 // the second half of a selection begun on C.sel_on, whose state has arrived (the caller waited for it): collect the
 // winners and queue their copies
 int finish_selection(JoinRun& R, ChunkRun& C) {
   uint32_t nsel = 0;
   const int64_t count = C.s1 - C.s0;
-  if (int rc = select_finish(R.c, C.b->key.p + C.s0, count, R.c->top_k, R.c->h_sel, &nsel, C.sel_on)) return rc;
+  if (int rc = select_finish(R.c, C.b->key.p + C.s0, count, R.c->top_k, *C.hs, &nsel, C.sel_on)) return rc;
   if (int rc = queue_winners(R.c, *C.b, C.s0, nsel, C.win, C.sel_on)) return rc;
   C.sel_done = true;
+  if (C.ci) C.ci->sel_open = false;
   return GCRE_OK;
 }
 
@@ -1485,7 +1523,8 @@ int begin_join(JoinRun& R, Begin* next) {
     if (mode == kInspect && R.replay) return GCRE_OK;   // already inspected (a later permutation window, kept inspections)
     if (!R.replay) {
       for (auto& ci : u.insp) {   // the buffers stay and serve the new chunks in turn
-        ci.inspected = ci.with_lists = ci.flags_valid = ci.win_valid = false;
+        R.sel_abandoned = R.sel_abandoned || ci.sel_open;
+        ci.forget();
         ci.cb = -1;
       }
       u.insp_key = ikey;
@@ -1527,6 +1566,10 @@ int begin_join(JoinRun& R, Begin* next) {
 
   hipStream_t st = R.st = mode == kInspect ? c->insp_stream : c->stream;
   R.exbuf = mode == kInspect ? &c->d_excess_b : &c->d_excess;
+  if (R.sel_abandoned) {   // digit passes nobody will come for may still read the keys this join's inspector rewrites
+    HIP_TRY(c, hipEventRecord(c->ev_sel_done, c->sel_stream));
+    HIP_TRY(c, hipStreamWaitEvent(st, c->ev_sel_done, 0));
+  }
   const bool own_sink = mode == kFull;
   R.prof = own_sink ? &c->prof : &u.launch.prof;
   R.ev_null = own_sink ? &c->ev_null : &u.launch.ev_null;
@@ -1541,6 +1584,8 @@ int begin_join(JoinRun& R, Begin* next) {
       HIP_TRY(c, u.launch.d_null.reserve((size_t)g.Kpad + 64));
       R.w_null = u.launch.d_null.p;
       if (!u.launch.done && hipEventCreateWithFlags(&u.launch.done, hipEventDisableTiming) != hipSuccess)
+        return fail(c, GCRE_ERR_DEVICE, "hipEventCreate failed");
+      if (!u.launch.sel_done && hipEventCreateWithFlags(&u.launch.sel_done, hipEventDisableTiming) != hipSuccess)
         return fail(c, GCRE_ERR_DEVICE, "hipEventCreate failed");
       HIP_TRY(c, hipMemsetAsync(R.w_null, 0, ((size_t)g.Kpad + 1) * 4, st));
     } else if (g.Kpad > 0 && mode != kCount) {   // (a counting pass writes no maxima)
@@ -1733,6 +1778,16 @@ int range_union_now(JoinRun& R) {
   return GCRE_OK;
 }
 
+// an open selection nobody will close (the entry is about to describe other paths): its digit passes may still be reading
+// the keys that the join's stream is about to rewrite
+int abandon_selection(JoinRun& R, ChunkInsp& ci) {
+  if (!ci.sel_open) return GCRE_OK;
+  ci.sel_open = false;
+  HIP_TRY(R.c, hipEventRecord(R.c->ev_sel_done, R.c->sel_stream));
+  HIP_TRY(R.c, hipStreamWaitEvent(R.st, R.c->ev_sel_done, 0));
+  return GCRE_OK;
+}
+
 // The chunk [cb, ce) of segment sg: what it scores, its inspection-cache entry, its buffers and their padding
 int open_chunk(JoinRun& R, ChunkRun& C, const Seg& sg, int64_t cb, int64_t ce) {
   gcre_ctx* c = R.c;
@@ -1756,11 +1811,14 @@ int open_chunk(JoinRun& R, ChunkRun& C, const Seg& sg, int64_t cb, int64_t ce) {
       for (auto& e : u.insp)   // an entry of an earlier join on this index: its buffers serve this chunk
         if (e.cb < 0) { ci = &e; break; }
       if (!ci) { u.insp.emplace_back(); ci = &u.insp.back(); }
-      ci->inspected = ci->with_lists = ci->flags_valid = ci->win_valid = false;
+      ci->forget();
       ci->cb = cb;
       ci->n = n;
     }
-    if (ci->s0 != C.s0 || ci->s1 != C.s1) ci->win_valid = false;
+    if (ci->s0 != C.s0 || ci->s1 != C.s1) {
+      ci->win_valid = false;
+      if (int rc = abandon_selection(R, *ci)) return rc;
+    }
     ci->s0 = C.s0;
     ci->s1 = C.s1;
   }
@@ -1771,7 +1829,10 @@ int open_chunk(JoinRun& R, ChunkRun& C, const Seg& sg, int64_t cb, int64_t ce) {
   // replayed: the inspector's output is in place (rows, statistics, keys, kept rows, lists when this chunk wants them)
   C.hit = ci && R.replay && ci->inspected &&
           (!C.use_ie || (ci->with_lists && ci->flags_valid && ci->in_recipe == (R.rcp != nullptr)));
-  if (ci && !C.hit) ci->inspected = ci->with_lists = ci->flags_valid = ci->win_valid = false;
+  if (ci && !C.hit) {
+    if (int rc = abandon_selection(R, *ci)) return rc;
+    ci->forget();
+  }
   if (C.hit) R.prof->inspect_replays++;
   const size_t cap = R.cap;
   hipStream_t st = R.st;
@@ -1919,13 +1980,24 @@ int inspect_chunk(JoinRun& R, ChunkRun& C, ChunkEnd* end) {
   }
   // the top-k selection only needs the keys the inspector just wrote: its digit passes run now, their state
   // comes back with the inspector's flags, its winners are collected before the null kernel starts
-  if (C.use_ie && g.K > 0 && C.scored && !C.sel_done && R.mode != kCount) {
+  C.hs = &c->h_sel;
+  if (C.hit && ci->sel_open && C.scored && !C.sel_done && R.mode != kCount) {
+    // the inspection that ran ahead queued the digit passes and left the rest to this call (score_chunk_ie, kInspect)
+    C.sel_on = c->sel_stream;
+    C.hs = ci->h_state;
+    C.sel_begun = true;
+  }
+  if (C.use_ie && g.K > 0 && C.scored && !C.sel_done && !C.sel_begun && R.mode != kCount) {
     if (c->sel_async) {   // beside the warm-up slice and the null kernel, behind the inspector
       HIP_TRY(c, hipEventRecord(c->ev_sel, st));
       HIP_TRY(c, hipStreamWaitEvent(c->sel_stream, c->ev_sel, 0));
       C.sel_on = c->sel_stream;
     }
-    if (int rc = select_begin(c, b.key.p + C.s0, C.s1 - C.s0, c->top_k, &c->h_sel, C.sel_on)) return rc;
+    if (ci && c->sel_defer && c->sel_async) {   // a state of the chunk's own: it may stay open behind other chunks' selections
+      if (!ci->h_state) HIP_TRY(c, hipHostMalloc((void**)&ci->h_state, sizeof(SelectState), hipHostMallocDefault));
+      C.hs = ci->h_state;
+    }
+    if (int rc = select_begin(c, b.key.p + C.s0, C.s1 - C.s0, c->top_k, C.hs, C.sel_on)) return rc;
     C.sel_begun = true;
   }
   *end = (!C.scored && !(C.use_ie && g.K > 0)) ? ChunkEnd::kNotNeeded : ChunkEnd::kOpen;
@@ -2000,8 +2072,10 @@ int fill_ie_args(JoinRun& R, const ChunkRun& C, IeArgs& ia, int64_t* nseg_scored
 
 // The launches of a chunk's inclusion-exclusion road: the warm-up slice, then the pruned kernel -- the quad form where
 // segments come in groups -- in one launch or in slices with a threshold exchange before each.  *quad: the quad form ran.
+// `behind_slice` runs once the slice and the gather are queued and nothing of the pruned launches is.
 int launch_ie_slices(JoinRun& R, const ChunkRun& C, IeArgs& ia, int planes, int64_t nseg_scored,
-                     gcre_uids::SegCache* seg_entry, int64_t ie_tile_factor, bool* quad_ran) {
+                     gcre_uids::SegCache* seg_entry, int64_t ie_tile_factor, bool* quad_ran,
+                     const std::function<int()>& behind_slice) {
   gcre_ctx* c = R.c;
   const JoinPlan& jp = R.jp;
   const Geometry& g = R.g;
@@ -2068,6 +2142,7 @@ int launch_ie_slices(JoinRun& R, const ChunkRun& C, IeArgs& ia, int planes, int6
     }
     ia.seg_begin = n_warm;
   }
+  if (int rc = behind_slice()) return rc;
   if (gathering.on) {   // from here on this stream carries the gather: whoever waits for it waits for both
     HIP_TRY(c, hipStreamWaitEvent(st, c->ev_rec_done, 0));
     gathering.on = nullptr;
@@ -2223,10 +2298,18 @@ int score_chunk_ie(JoinRun& R, ChunkRun& C, ChunkEnd* end) {
     std::memcpy(ci->flags, C.flags, sizeof C.flags);
     ci->flags_valid = true;
   }
-  if (R.mode == kInspect) {   // nothing of the permutation kernel's; the chunk's winners are collected next
+  if (R.mode == kInspect) {   // nothing of the permutation kernel's
     if (C.sel_begun && !C.sel_done) {
-      HIP_TRY(c, hipStreamSynchronize(C.sel_on));
-      if (int rc = finish_selection(R, C)) return rc;
+      if (c->sel_defer && ci && C.hs == ci->h_state && C.sel_on == c->sel_stream) {
+        // the selection stays open: nothing the launch needs depends on it, so the launch queues its slice and its gather
+        // first and closes it behind them (below, behind_slice); a join that is not launched closes it in its own call, the
+        // same way
+        ci->sel_open = true;
+        C.sel_left_open = true;
+      } else {   // the chunk's winners are collected next
+        HIP_TRY(c, hipStreamSynchronize(C.sel_on));
+        if (int rc = finish_selection(R, C)) return rc;
+      }
     }
     *end = ChunkEnd::kInspected;
     return GCRE_OK;
@@ -2275,15 +2358,32 @@ int score_chunk_ie(JoinRun& R, ChunkRun& C, ChunkEnd* end) {
     if (int rc = finish_selection(R, C)) return rc;
   hipEvent_t n0 = get_event(c), n1 = get_event(c);
   bool quad = false;
-  HIP_TRY(c, hipEventRecord(n0, st));
-  if (int rc = launch_ie_slices(R, C, ia, planes, nseg_scored, seg_entry, ie_tile_factor, &quad)) return rc;
-  HIP_TRY(c, hipEventRecord(n1, st));
-  if (C.sel_begun && !C.sel_done) {   // own stream: the digit passes ran beside the warm-up slice
+  // own stream: the digit passes ran beside whatever was queued since they were; the rest of the selection follows them
+  auto close_selection = [&]() -> int {
     const auto tw0 = std::chrono::steady_clock::now();
     HIP_TRY(c, hipStreamSynchronize(C.sel_on));
     R.select_wait_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tw0).count();
     if (int rc = finish_selection(R, C)) return rc;
-  }
+    if (R.mode == kLaunch)   // (no collect_winners behind it books this)
+      R.select_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tw0).count();
+    return GCRE_OK;
+  };
+  // A selection that an ahead inspection left open is closed between the slice and the pruned launch, and the pruned launch
+  // waits for it on the device: its digit passes have had the inspection's tail, this call's set-up and the slice to run
+  // beside, while a pruned kernel is persistent and fills the chip -- one-block kernels of another stream queued beside it
+  // (k_select_step, measured) wait until it ends, and the winners then cost the join its tail instead of nothing
+  auto behind_slice = [&]() -> int {
+    if (!(C.sel_begun && !C.sel_done && ci && ci->sel_open && C.sel_on != st)) return GCRE_OK;
+    if (int rc = close_selection()) return rc;
+    HIP_TRY(c, hipEventRecord(c->ev_sel_done, C.sel_on));
+    HIP_TRY(c, hipStreamWaitEvent(st, c->ev_sel_done, 0));
+    return GCRE_OK;
+  };
+  HIP_TRY(c, hipEventRecord(n0, st));
+  if (int rc = launch_ie_slices(R, C, ia, planes, nseg_scored, seg_entry, ie_tile_factor, &quad, behind_slice)) return rc;
+  HIP_TRY(c, hipEventRecord(n1, st));
+  if (C.sel_begun && !C.sel_done)
+    if (int rc = close_selection()) return rc;
   if (timing && R.mode != kLaunch)
     if (int rc = print_ie_timing(R, C, ia, quad)) return rc;
   R.ev_null->emplace_back(n0, n1);
@@ -2443,10 +2543,7 @@ int collect_winners(JoinRun& R, ChunkRun& C) {
       unpack_winners(C.win);
     }
     R.select_wait_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tw0).count();
-    const int64_t first = C.cb + C.s0;
-    for (uint32_t i = 0; i < win.n; i++)
-      R.cands.push_back(Candidate{key_to_score(win.key[i]), first + (int64_t)win.sel[i], (int32_t)win.r0[i], (int32_t)win.r1[i],
-                                  (int32_t)win.cases[i], (int32_t)win.ctrls[i]});
+    push_candidates(R.cands, win, C.cb + C.s0);
   }
   if (C.ci && !C.ci->win_valid) {   // (its copies have arrived: the stream was waited for above)
     C.ci->win = win;
@@ -2502,6 +2599,16 @@ int run_chunk(JoinRun& R, const Seg& sg, int64_t cb, int64_t ce, ChunkEnd* end) 
   if (R.jp.hits && (R.mode == kFull || R.mode == kCount))
     if (int rc = collect_hits(R.c, R.jp.hits, *C.b, C.cb, C.s0, C.s1, R.st)) return rc;
   if (R.mode == kCount) return GCRE_OK;
+  if (C.sel_left_open) return GCRE_OK;   // (kInspect: its winners come with the call that closes the selection)
+  if (R.mode == kLaunch && R.c->sel_defer && C.ci && C.sel_done && !C.win_from_cache && C.sel_on == R.c->sel_stream) {
+    // closed behind the null kernels: the winners' copies are queued and land in the chunk's entry, nothing is waited for;
+    // finish_launched unpacks them.  The next selection on that stream -- another chunk's, the next join's -- is behind them
+    C.ci->win = std::move(C.win);
+    C.ci->win_pending = true;
+    R.u->launch.sel_pending = true;
+    R.prof->paths += C.s1 - C.s0;
+    return GCRE_OK;
+  }
   if (int rc = collect_winners(R, C)) return rc;
   if (R.mode != kInspect) R.prof->paths += C.s1 - C.s0;   // (a launch books them on the profile of the join it is for)
   return GCRE_OK;
@@ -2558,6 +2665,8 @@ int finish_join(JoinRun& R) {
     // launched: the kernels are queued, nothing is waited for.  What the join's own call will need stays with the index
     gcre_uids::Launched& L = u.launch;
     HIP_TRY(c, hipEventRecord(L.done, st));
+    if (L.sel_pending) HIP_TRY(c, hipEventRecord(L.sel_done, c->sel_stream));
+    R.prof->select_ms += std::max(0.0, R.select_ms - R.select_wait_ms);
     L.cands = std::move(R.cands);
     L.key = R.ikey;
     L.res_ver = R.keep ? jp.res->version : 0;
@@ -2722,6 +2831,10 @@ gcre_ctx* gcre_create(int method, int n_cases, int n_ctrls, int iterations, int 
   ok = ok && hipEventCreateWithFlags(&c->ev_sel, hipEventDisableTiming) == hipSuccess;
   ok = ok && hipEventCreateWithFlags(&c->ev_sel_done, hipEventDisableTiming) == hipSuccess;
   if (const char* e = std::getenv("GCRE_SELECT_STREAM")) c->sel_async = std::atoi(e) != 0;
+  if (const char* e = std::getenv("GCRE_SELECT_DEFER")) c->sel_defer = std::atoi(e) != 0;
+  if (const char* e = std::getenv("GCRE_SELECT_CAND")) c->sel_cand = std::min(std::max(std::atoi(e), 0), 1 << 24);
+  if (const char* e = std::getenv("GCRE_SELECT_PASSES"))
+    if (std::atoi(e) == 8) c->sel_cand = 0;
   ok = ok && hipMalloc((void**)&c->d_case_mask, (size_t)g.Wp * 8) == hipSuccess;
   ok = ok && hipMalloc((void**)&c->d_max_tot, kFlagWords * 4) == hipSuccess;
   ok = ok && hipMalloc((void**)&c->d_max_tot_b, kFlagWords * 4) == hipSuccess;
@@ -2770,6 +2883,7 @@ void gcre_destroy(gcre_ctx* c) {
   for (auto* b : {&c->d_sel, &c->d_small, &c->d_chunk, &c->d_rec_segs}) b->release();
   c->d_hub_null.release();
   c->d_wkey.release();
+  c->d_cand.release();
   c->d_doff.release();
   c->d_scan.release();
   c->d_excess.release();

@@ -297,7 +297,9 @@ hipError_t launch_hist(const uint64_t* key, int64_t count, int shift, uint64_t p
                        hipStream_t stream);
 // all eight digit passes queued back to back, the state between them stays on the device: afterwards st->prefix is the
 // need-th largest key, st->greater the number of keys in higher buckets, st->need / st->eq_count the wanted / present
-// number of keys equal to it
+// number of keys equal to it.  With a candidate buffer (`cand`, `cand_cap` keys; `note`: two words of scratch) only the
+// first two passes and one compaction read all keys: the other six read the keys that share the 16 bits chosen by then,
+// unless more than cand_cap do -- then they read all keys as without a buffer.  The state is the same on every road.
 struct SelectState {
   uint64_t prefix;
   int64_t need;
@@ -306,7 +308,7 @@ struct SelectState {
   uint32_t pad;
 };
 hipError_t launch_radix_select(const uint64_t* key, int64_t count, int64_t need, uint32_t* hist256, SelectState* st,
-                               hipStream_t stream);
+                               uint64_t* cand, uint32_t cand_cap, uint32_t* note, hipStream_t stream);
 // appends every i with key[i] > thr (any order) to out[], counter in *n_out
 hipError_t launch_collect_gt(const uint64_t* key, int64_t count, uint64_t thr, uint32_t* out, uint32_t* n_out,
                              uint32_t cap, hipStream_t stream);

@@ -647,8 +647,10 @@ __global__ __launch_bounds__(256) void k_hist_st(const u64* key, i64 count, int 
   if (h[threadIdx.x]) atomicAdd(&hist256[threadIdx.x], h[threadIdx.x]);
 }
 
-// the bucket that holds the need-th largest key of this digit; leaves the histogram zeroed for the next pass
-__global__ __launch_bounds__(256) void k_select_step(SelectState* st, u32* hist256) {
+// the bucket that holds the need-th largest key of this digit; leaves the histogram zeroed for the next pass.  `note` (the
+// step behind the second digit pass): note[0] = the keys that share the 16 bits chosen so far -- the candidates of
+// k_select_compact --, note[1] = its cursor, zeroed
+__global__ __launch_bounds__(256) void k_select_step(SelectState* st, u32* hist256, u32* note) {
   __shared__ u32 h[256];
   h[threadIdx.x] = hist256[threadIdx.x];
   hist256[threadIdx.x] = 0;
@@ -666,16 +668,68 @@ __global__ __launch_bounds__(256) void k_select_step(SelectState* st, u32* hist2
   s.eq_count = h[b];
   s.prefix = (s.prefix << 8) | (u64)b;
   *st = s;
+  if (note) {
+    note[0] = h[b];
+    note[1] = 0;
+  }
+}
+
+// Behind the second digit pass: the keys whose top 16 bits (sign, exponent, four bits of mantissa) equal the prefix are all
+// that the six remaining passes can count.  Where at most `cap` of them exist they are copied to cand[] (any order: a
+// histogram does not care), one atomic per wave; where more exist (all scores equal, a constant table) nothing is copied
+// and the remaining passes read the keys themselves -- both decided from note[0], on the device.
+__global__ __launch_bounds__(256) void k_select_compact(const u64* key, i64 count, const SelectState* st, u64* cand, u32 cap,
+                                                        u32* note) {
+  if (note[0] > cap) return;
+  const u64 prefix = st->prefix;
+  const int lane = threadIdx.x & 63;
+  for (i64 base = (i64)blockIdx.x * blockDim.x + (threadIdx.x & ~63u); base < count; base += (i64)gridDim.x * blockDim.x) {
+    const i64 i = base + lane;
+    const u64 k = i < count ? key[i] : 0;
+    const bool match = i < count && (k >> 48) == prefix;
+    const u64 ball = __ballot(match);
+    if (ball == 0) continue;   // (wave-uniform)
+    u32 at = 0;
+    if (lane == 0) at = atomicAdd(&note[1], (u32)__popcll(ball));
+    at = (u32)__builtin_amdgcn_readfirstlane((int)at);
+    const u32 pos = at + (u32)__popcll(ball & (((u64)1 << lane) - 1));
+    if (match && pos < cap) cand[pos] = k;
+  }
+}
+
+// k_hist_st of the third to eighth digit: over the candidates where they were copied, over the keys where they were not.
+// Every key that matches a prefix of three or more digits is a candidate, so the histogram is the same either way.
+__global__ __launch_bounds__(256) void k_hist_cand(const u64* key, i64 count, int shift, const SelectState* st, u32* hist256,
+                                                   const u64* cand, u32 cap, const u32* note) {
+  __shared__ u32 h[256];
+  h[threadIdx.x] = 0;
+  __syncthreads();
+  const u32 nc = note[0];
+  const u64* src = nc <= cap ? cand : key;
+  const i64 n = nc <= cap ? (i64)nc : count;
+  const u64 prefix = st->prefix;
+  for (i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (i64)gridDim.x * blockDim.x) {
+    const u64 k = src[i];
+    if ((k >> (shift + 8)) == prefix) atomicAdd(&h[(u32)(k >> shift) & 255u], 1u);
+  }
+  __syncthreads();
+  if (h[threadIdx.x]) atomicAdd(&hist256[threadIdx.x], h[threadIdx.x]);
 }
 
 hipError_t launch_radix_select(const uint64_t* key, int64_t count, int64_t need, uint32_t* hist256, SelectState* st,
-                               hipStream_t stream) {
-  const int grid = (int)hmin((count + 2047) / 2048, 2048);
+                               uint64_t* cand, uint32_t cand_cap, uint32_t* note, hipStream_t stream) {
+  const int grid = count > 0 ? (int)hmin((count + 2047) / 2048, 2048) : 1;
   trace_launch("k_hist_st", (count + 2047) / 2048, grid);
   hipLaunchKernelGGL(k_select_init, dim3(1), dim3(256), 0, stream, st, need, hist256);
+  const bool compact = cand != nullptr && cand_cap > 0;
   for (int shift = 56; shift >= 0; shift -= 8) {
-    hipLaunchKernelGGL(k_hist_st, dim3(grid > 0 ? grid : 1), dim3(256), 0, stream, key, count, shift, st, hist256);
-    hipLaunchKernelGGL(k_select_step, dim3(1), dim3(256), 0, stream, st, hist256);
+    if (compact && shift < 48)
+      hipLaunchKernelGGL(k_hist_cand, dim3(grid), dim3(256), 0, stream, key, count, shift, st, hist256, cand, cand_cap, note);
+    else
+      hipLaunchKernelGGL(k_hist_st, dim3(grid), dim3(256), 0, stream, key, count, shift, st, hist256);
+    hipLaunchKernelGGL(k_select_step, dim3(1), dim3(256), 0, stream, st, hist256, (compact && shift == 48) ? note : nullptr);
+    if (compact && shift == 48)
+      hipLaunchKernelGGL(k_select_compact, dim3(grid), dim3(256), 0, stream, key, count, st, cand, cand_cap, note);
   }
   return hipGetLastError();
 }
