@@ -129,6 +129,9 @@ DOSE_SCORE = np.dtype([("score", "<f8"), ("n_ge", "<i8"), ("best_index", "<i4"),
 DOSE_MAX_LEVEL = 15   # GCRE_DOSE_MAX_LEVEL
 # gcre_seq_score
 SEQ_SCORE = np.dtype([("n_hit", "<i8"), ("n_perm", "<i8"), ("stopped", "<i4"), ("pad", "<i4")], align=True)
+# gcre_strata_score
+STRATA_SCORE = np.dtype([("score", "<f8"), ("n_ge", "<i8")], align=True)
+STRATA_MAX = 16   # GCRE_STRATA_MAX
 # gcre_burden
 BURDEN = np.dtype([("total", "<i8"), ("observed", "<i8"), ("n_ge", "<i8"), ("n_le", "<i8"), ("planes", "<i4"),
                    ("p_upper", "<f8"), ("p_lower", "<f8")], align=True)
@@ -155,6 +158,7 @@ EXPORTS = [
     "gcre_score_sets_subsample", "gcre_subsample_launches",
     "gcre_score_sets_dose", "gcre_dose_launches",
     "gcre_score_sets_sequential", "gcre_sequential_launches",
+    "gcre_score_sets_strata", "gcre_strata_launches",
     "gcre_set_overlap", "gcre_overlap_launches",
     "gcre_clump_sets", "gcre_clump_launches",
     "gcre_set_patient_counts", "gcre_patient_launches",
@@ -305,6 +309,10 @@ _FEATURES = {
         "gcre_score_sets_sequential": (_I, [_V, ctypes.POINTER(gcre_set_input), ctypes.c_uint64, _P, _I, _I64, _I64, _P, _I64,
                                             ctypes.POINTER(_I64), _P]),
         "gcre_sequential_launches": (_I64, [_V])}),
+    "strata": ("sets", ["gcre_score_sets_strata", "gcre_strata_launches"], "stratified set scores (gcre_score_sets_strata)", {
+        "gcre_score_sets_strata": (_I, [_V, ctypes.POINTER(gcre_set_input), _P, _I32, _P, _P, _P, _P, _P, _I64, ctypes.POINTER(_I64),
+                                        _P, _P, _P, _P, _P]),
+        "gcre_strata_launches": (_I64, [_V])}),
     "overlap": (None, ["gcre_set_overlap"], "carrier overlaps (gcre_set_overlap)", {
         "gcre_set_overlap": (_I, [_V, ctypes.POINTER(gcre_set_input), _P, _I64, _P, _I64, _P, _P]),
         "gcre_overlap_launches": (_I64, [_V])}),
@@ -374,6 +382,7 @@ _prefix_lib = functools.partial(_feature_lib, "prefix")
 _subsample_lib = functools.partial(_feature_lib, "subsample")
 _dose_lib = functools.partial(_feature_lib, "dose")
 _sequential_lib = functools.partial(_feature_lib, "sequential")
+_strata_lib = functools.partial(_feature_lib, "strata")
 _overlap_lib = functools.partial(_feature_lib, "overlap")
 _clump_lib = functools.partial(_feature_lib, "clump")
 _patients_lib = functools.partial(_feature_lib, "patients")
@@ -1315,6 +1324,61 @@ class JoinExec:
                                                         0 if st is None else int(st.max()) + 1, int(hits), int(max_perms), _ptr(out),
                                                         len(out), ctypes.byref(n_out), _ptr(seq)))
         return out[:n_out.value], seq[:n_out.value]
+
+    def strata_tests(self, sets, rows, signs=None, strata=None, tables=None, family: bool = False, null: bool = False,
+                     terms: bool = False):
+        """Stratified scores of the given sets (gcre_score_sets_strata): every stratum of the cohort scored on
+        its own counts against the value table of its own cases and controls, the terms summed in ascending order of the
+        stratum, and the same sum taken under every permutation of the context.  ``sets`` / ``rows`` / ``signs`` as
+        ``score_sets`` takes them.  ``strata``: one id per patient, any integers (mapped to 0 .. S-1 in ascending order of id;
+        at most 16 distinct); required.  The context's masks must keep these strata: ``generate_permutations(seed, strata)``
+        with the same ``strata`` -- anything else is refused.  ``tables``: one value table per stratum in ascending order of
+        id (cells a table lacks read as -1); None = ``values_table(cases_s, ctrls_s)`` of every stratum.  Returns ``(records,
+        strata_records)``: the SET_SCORE records of ``score_sets`` (the pooled score), and one STRATA_SCORE record per set --
+        ``score`` the summed observed score and ``n_ge`` the permutations whose sum reaches it (-1 for an NA member; 0
+        without permutations).  With ``family`` also float64 [iters], per permutation the maximum over the sets (NaN and
+        negatives as +0); with ``null`` also float64 [sets][iters], the summed null score (NaN rows for sets with an NA
+        member); with ``terms`` also float64 [sets][S], the observed terms, and int32 [sets][S][4], cases_pos, ctrls_pos,
+        cases_neg, ctrls_neg inside every stratum.  ``n_ge / iters`` is a nominal p-value of the sum; the terms and counts
+        are descriptive.  ``report.strata_reference`` restates the call in numpy.  Errors raise GcreError."""
+        n = self.num_cases + self.num_ctrls
+        inp, keep = _set_input(sets, rows, signs, n)
+        S = inp.n_sets
+        if strata is None:
+            raise ValueError("strata: one id per patient is required (score_sets gives the pooled score)")
+        ids, inv = np.unique(np.asarray(strata).reshape(-1), return_inverse=True)
+        if len(inv) != n:
+            raise ValueError(f"strata: one id per patient ({n}), not {len(inv)}")
+        st = np.ascontiguousarray(inv, dtype=np.int32)
+        NS = len(ids)
+        if tables is None:
+            tables = [values_table(int((st[:self.num_cases] == s).sum()), int((st[self.num_cases:] == s).sum())) for s in range(NS)]
+        tabs = [np.ascontiguousarray(t, dtype=np.float64) for t in tables]
+        if len(tabs) != NS or any(t.ndim != 2 for t in tabs):
+            raise ValueError(f"tables: one value table (rows and columns) per stratum ({NS}), in ascending order of id")
+        nrow = np.array([t.shape[0] for t in tabs], dtype=np.int32)
+        ncol = np.array([t.shape[1] for t in tabs], dtype=np.int32)
+        toff = np.concatenate([[0], np.cumsum([t.size for t in tabs])[:-1]]).astype(np.int64) if NS else np.zeros(0, np.int64)
+        flat = np.ascontiguousarray(np.concatenate([t.reshape(-1) for t in tabs] + [np.zeros(1)]))   # (never empty)
+        lib = _strata_lib()
+        out = np.zeros(max(S, 1), dtype=SET_SCORE)
+        sr = np.zeros(max(S, 1), dtype=STRATA_SCORE)
+        fam = np.zeros(self.iters, dtype=np.float64) if family else None
+        nul = np.full((S, self.iters), np.nan, dtype=np.float64) if null else None
+        trm = np.full((S, NS), np.nan, dtype=np.float64) if terms else None
+        cnt = np.zeros((S, NS, 4), dtype=np.int32) if terms else None
+        n_out = ctypes.c_int64(0)
+        given = lambda a: _ptr(a) if a is not None and a.size else None
+        self._check_gcre(lib.gcre_score_sets_strata(self._h, ctypes.byref(inp), _ptr(st), NS, _ptr(flat), _ptr(nrow), _ptr(ncol),
+                                                    _ptr(toff), _ptr(out), len(out), ctypes.byref(n_out), _ptr(sr), given(trm),
+                                                    given(cnt), given(nul), given(fam)))
+        res = (out[:n_out.value], sr[:n_out.value])
+        return res + ((fam,) if family else ()) + ((nul,) if null else ()) + ((trm, cnt) if terms else ())
+
+    def strata_launches(self) -> int:
+        """Kernels ``strata_tests`` launched for its own stage on this context so far: the indicator rows, the check of the
+        masks, one per table, then three per slab (two without permutations)."""
+        return int(_strata_lib().gcre_strata_launches(self._h))
 
     def sequential_launches(self) -> int:
         """Kernels ``sequential_tests`` launched for its own stage on this context so far: three per batch."""

@@ -803,6 +803,47 @@ struct DoseArgs {
 };
 hipError_t launch_dose_rows(const DoseArgs& a, int method, hipStream_t stream);
 
+// ---- stratified set scores: per-stratum counts and tables, summed (gcre_strata.hip) ----
+// k_strata_masks turns the stratum ids into S indicator rows; the check launch counts every resident mask against them.
+// Then one slab of whole sets: slot e of the slab has the S consecutive rows [e S, e S + S), row e S + s = "union & Z_s" in
+// SetNullArgs' row layout.  k_strata_rows builds them and their counts from the union rows the set stage left,
+// k_strata_observed makes the totals, the observed terms and their sum, k_strata_null the sum under every permutation.
+struct StrataArgs {
+  // k_strata_masks, the check
+  const int32_t* stratum;       // [n_patients] ids 0 .. S-1
+  uint32_t* zrows;              // [S][W32p] indicator rows; zero beyond the patients
+  const uint32_t* cases_in;     // [S] cases of every stratum: what every mask must count inside Z_s
+  unsigned int* violations;     // one dword, zero on entry: (stratum, permutation) pairs that do not
+  // k_strata_rows
+  const uint32_t* urows;        // [nslots][M][W32p] the slab's union rows as the set stage left them
+  uint32_t* rows;               // [nslots S][M][W32p] stratum rows: (+) half, then (-) half (method 2)
+  int32_t* cnt;                 // [nslots S][4] cases_pos, ctrls_pos, cases_neg, ctrls_neg; zero on entry (k_strata_rows adds)
+  // k_strata_observed
+  const double* dvt;            // the S diagonal-major tables, one behind the other
+  const int64_t* doff;          // [S] where table s starts, in doubles (read-only: scalar loads)
+  uint32_t* tot;                // [nslots S][M] carriers per half
+  double* obs;                  // [nslots] the sum of the observed terms
+  double* terms;                // optional [nslots][S]
+  // k_strata_null
+  const PrefixWaveDev* waves;   // [nblocks][4] the block table (gcre_prefix.h, every slot with S steps)
+  const uint32_t* masks;        // [W32p][Kpad]
+  unsigned long long* n_ge;     // [nslots], zero on entry
+  double* null_scores;          // optional [nslots][Kpad]
+  unsigned long long* fam_bits; // optional [Kpad] maxima over the slots as bit patterns of non-negative doubles (zero on
+                                // entry; accumulates over the slabs)
+  int64_t nslots;
+  int nblocks;                  // blocks of four slots
+  int S;                        // strata, 1 .. 16
+  int W32p, Kpad, K;
+  int nkt;                      // permutation tiles of kSetPermTile
+  int n_patients, n_cases;
+};
+hipError_t launch_strata_masks(const StrataArgs& a, hipStream_t stream);
+hipError_t launch_strata_check(const StrataArgs& a, hipStream_t stream);
+hipError_t launch_strata_rows(const StrataArgs& a, int method, hipStream_t stream);
+hipError_t launch_strata_observed(const StrataArgs& a, int method, hipStream_t stream);
+hipError_t launch_strata_null(const StrataArgs& a, int method, hipStream_t stream);
+
 // ---- carrier-overlap counts of caller-given sets (gcre_overlap.hip) ----
 constexpr int kOverlapTile = 64;    // pairs per edge of a block's tile
 constexpr int kOverlapChunk = 32;   // dwords of a row per staged chunk (128 bytes): rows are padded to a multiple of it

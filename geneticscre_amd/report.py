@@ -317,7 +317,7 @@ def score_paths(paths, genes: Sequence[str], data: np.ndarray, n_cases: int, n_c
                 device: int = 0, gwaspa_out: Optional[Dict[str, object]] = None, minp: bool = False,
                 competitive: int = 0, competitive_bins: int = 10, fixed: Optional[Sequence[str]] = None,
                 stability: int = 0, stability_cuts=None, sequential: int = 0, sequential_hits: int = 20,
-                family_inference: bool = False):
+                stratified: bool = False, family_inference: bool = False):
     """Permutation tests of paths and gene sets the caller names (gcre_score_sets on the device): what GWASPA cannot
     answer for a cascade outside its top K, or for a KEGG / Reactome list.  ``paths`` as ``parse_sets`` reads them;
     genes are looked up after ``preprocess_table(threshold)``, as GWASPA and ``decorated_table`` do (a symbol not found is
@@ -381,12 +381,24 @@ def score_paths(paths, genes: Sequence[str], data: np.ndarray, n_cases: int, n_c
     used, with a relative error of about 1 / sqrt(``sequential_hits``) wherever it is above ``sequential_hits`` /
     ``sequential``; ``SequentialPerms`` / ``SequentialHits`` are the two counts and ``SequentialStopped`` says whether the
     path reached its hits.  A nominal p-value, one path at a time: the paths stop at different permutations, so there is no
-    family-wise version of it.  ``sequential=0`` returns exactly the frame without it."""
+    family-wise version of it.  ``sequential=0`` returns exactly the frame without it.
+
+    ``stratified``: the columns of ``stratified_columns`` behind all of these (gcre_score_sets_strata; DESIGN.md §3.22);
+    needs ``strata``.  Stratified permutations keep every p-value above valid when case fraction and carrier frequency both
+    differ between the strata, but ``Scores`` is still the POOLED score: a gene that is merely commoner in the case-rich
+    stratum scores high under the observed labels and under every such permutation alike, and nothing is left to see.
+    ``StratifiedScores`` scores every stratum on its own counts against the value table of its own cases and controls and
+    sums the terms (the Cochran-Mantel-Haenszel idea); ``StratifiedPvalues`` is the nominal permutation p-value of that sum
+    under the same masks, ``StratifiedFamilyPvalues`` single-step max-T over the given paths.  ``Score.<id>`` / ``Cases.<id>``
+    / ``Controls.<id>`` show every stratum's term and carriers: descriptive, no test of heterogeneity is attached.
+    ``stratified=False`` returns exactly the frame without it."""
     import pandas as pd
     if int(stability) < 0:
         raise ValueError("stability: the number of draws must not be negative")
     if int(sequential) < 0:
         raise ValueError("sequential: the limit of permutations must not be negative")
+    if stratified and strata is None:
+        raise ValueError("stratified=True needs strata: one id per patient")
     if int(stability) > 0 and stability_cuts is None:
         raise ValueError("stability > 0 needs stability_cuts: there is no default cut (a cut is a choice the labels must not make)")
     method = 2 if signed else 1
@@ -440,6 +452,11 @@ def score_paths(paths, genes: Sequence[str], data: np.ndarray, n_cases: int, n_c
         seq = _sequential_counts(rows, signs, data, n_cases, n_ctrls, method, int(sequential_hits), int(sequential), strata, seed, device)
         cols.update(sequential_columns(seq, valid))
         names_out += SEQUENTIAL_COLUMNS
+    if stratified:
+        sr, sfam, terms, counts, ids = _stratified_scores(rows, signs, data, n_cases, n_ctrls, method, K, strata, seed, device)
+        more_cols = stratified_columns(sr, valid, sfam, terms, counts, ids, K)
+        cols.update(more_cols)
+        names_out += list(more_cols)
     df = pd.DataFrame(cols, columns=names_out)
     if per_half is not None:
         df.attrs["PerHalfSelected"] = per_half
@@ -1032,6 +1049,135 @@ def sequential_columns(seq, valid) -> Dict[str, np.ndarray]:
     p[sel] = n_hit[sel] / n_perm[sel]
     return {"SequentialPvalues": p, "SequentialPerms": np.where(ok, n_perm, nan), "SequentialHits": np.where(ok, n_hit, nan),
             "SequentialStopped": np.where(ok, stopped, nan)}
+
+
+# stratified set scores: every stratum scored against its own table, the terms summed
+
+STRATIFIED_COLUMNS = ["StratifiedScores", "StratifiedPvalues", "StratifiedFamilyPvalues"]
+STRATUM_COLUMNS = ["Score", "Cases", "Controls"]
+
+
+def strata_reference(sets, rows, signs, n_cases: int, strata, tables, masks, method: int) -> Dict[str, np.ndarray]:
+    """The numpy statement of gcre_score_sets_strata, no device call.  ``rows``: the 0/1 carrier matrix
+    [rows][patients], columns < n_cases the cases; ``sets`` / ``signs`` as ``JoinExec.score_sets`` takes them; ``strata``: one
+    id per patient, any integers, stratum s = the s-th id in ascending order; ``tables``: one value table per stratum in that
+    order, cells a table lacks reading as -1; ``masks`` bool [K][patients] from ``permutation_masks`` (None: no permutation).
+    With P, N a set's unions (method 1: one union alone), Z_s the patients of stratum s and m a label mask -- the observed
+    labels or a row of ``masks`` -- term_s(m) = T_s[|P & Z_s & m|][|P & Z_s \\ m|] (+ T_s[|N & Z_s \\ m|][|N & Z_s & m|],
+    added in this order) and score(m) = ((+0.0 + term_0) + term_1) + ..., in ascending s.  Returns ``score`` [sets] (NaN
+    for a set with an NA member), ``n_ge`` int64 [sets] = #{r : score(mask_r) >= score} as doubles (-1 for those), ``terms``
+    [sets][S], ``counts`` int32 [sets][S][4] (cases_pos, ctrls_pos, cases_neg, ctrls_neg), ``null_scores`` [sets][K] and
+    ``family_max`` [K], the maximum over the valid sets with NaN and negatives as +0."""
+    d = np.asarray(rows) != 0
+    n = d.shape[1]
+    NSETS = len(sets)
+    ids, st = np.unique(np.asarray(strata).reshape(-1), return_inverse=True)
+    if len(st) != n:
+        raise ValueError(f"strata: one id per patient ({n}), not {len(st)}")
+    NS = len(ids)
+    T = [np.asarray(t, np.float64) for t in tables]
+    if len(T) != NS:
+        raise ValueError(f"tables: one per stratum ({NS}), not {len(T)}")
+    obs = np.arange(n) < n_cases
+    mk = np.zeros((0, n), bool) if masks is None else np.asarray(masks, bool).reshape(-1, n)
+    K = len(mk)
+    Z = [st == s for s in range(NS)]
+    size = [int(z.sum()) for z in Z]
+
+    def summed(P, N, m):                       # P, N bool [n]; m bool [labels][n] -> (sum [labels], terms [S][labels], counts)
+        total = np.zeros(len(m))               # +0.0
+        terms, counts = [], []
+        for s in range(NS):                    # the stated order
+            a, b = (m & (P & Z[s])).sum(axis=1), (~m & (P & Z[s])).sum(axis=1)
+            term = _vt_cell(T[s], size[s], a, b)
+            k = [a, b, np.zeros_like(a), np.zeros_like(a)]
+            if method == 2:
+                c, e = (~m & (N & Z[s])).sum(axis=1), (m & (N & Z[s])).sum(axis=1)
+                with np.errstate(invalid="ignore"):      # inf - inf
+                    term = term + _vt_cell(T[s], size[s], c, e)
+                k[2], k[3] = c, e
+            with np.errstate(invalid="ignore"):
+                total = total + term
+            terms.append(term)
+            counts.append(k)
+        return total, terms, counts
+
+    res = {"score": np.full(NSETS, np.nan), "n_ge": np.zeros(NSETS, np.int64), "terms": np.full((NSETS, NS), np.nan),
+           "counts": np.zeros((NSETS, NS, 4), np.int32), "null_scores": np.full((NSETS, K), np.nan), "family_max": np.zeros(K)}
+    for i in range(NSETS):
+        mem = np.asarray(sets[i], dtype=np.int64).reshape(-1)
+        if (mem < 0).any():
+            res["n_ge"][i] = -1
+            continue
+        sg = np.ones(len(mem), np.int64) if signs is None else np.asarray(signs[i], dtype=np.int64).reshape(-1)
+        neg = (sg == -1) if method == 2 else np.zeros(len(mem), bool)
+        P = d[mem[~neg]].any(axis=0) if (~neg).any() else np.zeros(n, bool)
+        N = d[mem[neg]].any(axis=0) if neg.any() else np.zeros(n, bool)
+        total, terms, counts = summed(P, N, obs[None, :])
+        res["score"][i] = total[0]
+        res["terms"][i] = [t[0] for t in terms]
+        res["counts"][i] = [[int(x[0]) for x in k] for k in counts]
+        if K:
+            null = summed(P, N, mk)[0]
+            res["null_scores"][i] = null
+            with np.errstate(invalid="ignore"):
+                res["n_ge"][i] = int((null >= total[0]).sum())          # a NaN on either side never counts
+                res["family_max"] = np.maximum(res["family_max"], np.where(null > 0, null, 0.0))
+    return res
+
+
+def stratified_columns(strata_records, valid, family_max, terms, counts, ids, perms: int) -> Dict[str, np.ndarray]:
+    """The columns of the stratified scores from what ``JoinExec.strata_tests(family=True, terms=True)`` returns (or the dict
+    entries of ``strata_reference``): ``strata_records`` with ``score`` and ``n_ge``, ``family_max`` [perms], ``terms``
+    [sets][S], ``counts`` [sets][S][4]; ``ids``: the S stratum ids as the caller gave them, ascending.
+    ``StratifiedScores``: the sum over the strata of each stratum's score against its own value table.
+    ``StratifiedPvalues`` = n_ge / perms: a nominal permutation p-value of that sum, one set at a time (0 where no
+    permutation reached it).  ``StratifiedFamilyPvalues``: single-step max-T over the call's sets, the share of the
+    permutations whose maximum over all of them reaches the set's sum.  Per stratum ``Score.<id>`` (its term), ``Cases.<id>``
+    and ``Controls.<id>`` (the set's carriers among its cases and controls, as ``Cases`` / ``Controls`` count them): these
+    are descriptive, and no test of heterogeneity between the strata is attached.  NaN for a set with an NA member
+    (``valid`` 0 or n_ge < 0); the p-values are NaN without permutations."""
+    score = np.asarray(strata_records["score"], np.float64).reshape(-1)
+    n_ge = np.asarray(strata_records["n_ge"], np.int64).reshape(-1)
+    S = len(score)
+    ok = (np.asarray(valid).reshape(-1)[:S] != 0) & (n_ge >= 0)
+    K = int(perms)
+    nan = np.full(S, np.nan)
+    p, fp = nan.copy(), nan.copy()
+    if K > 0:
+        p[ok] = n_ge[ok] / K
+        fm = np.asarray(family_max, np.float64).reshape(-1)[:K]
+        with np.errstate(invalid="ignore"):
+            fp[ok] = (fm[None, :] >= score[ok][:, None]).sum(axis=1) / K
+    cols = {"StratifiedScores": np.where(ok, score, np.nan), "StratifiedPvalues": p, "StratifiedFamilyPvalues": fp}
+    ids = list(np.asarray(ids).reshape(-1).tolist())
+    tm = np.asarray(terms, np.float64).reshape(S, len(ids))
+    cn = np.asarray(counts, np.int64).reshape(S, len(ids), 4)
+    for j, name in enumerate(ids):
+        cols[f"Score.{name}"] = np.where(ok, tm[:, j], np.nan)
+        cols[f"Cases.{name}"] = np.where(ok, cn[:, j, 0] + cn[:, j, 2], np.nan)
+        cols[f"Controls.{name}"] = np.where(ok, cn[:, j, 1] + cn[:, j, 3], np.nan)
+    return cols
+
+
+def _stratified_scores(rows, signs, data, n_cases, n_ctrls, method, n_permutations, strata, seed, device):
+    """strata_tests for ``score_paths``: on the rows the sets use, on a context of its own whose masks keep ``strata``;
+    (strata records, family maxima, terms, counts, the ids ascending)."""
+    from . import api
+    used: Dict[int, int] = {}
+    sets = [[-1 if r < 0 else used.setdefault(r, len(used)) for r in rs] for rs in rows]
+    data = np.asarray(data)
+    sub = data[list(used.keys())] if used else np.zeros((0, n_cases + n_ctrls), np.int32)
+    ids, inv = np.unique(np.asarray(strata).reshape(-1), return_inverse=True)
+    ex = api.JoinExec(method, n_cases, n_ctrls, n_permutations, device=device)
+    try:
+        ex.set_value_table(api.values_table(n_cases, n_ctrls))
+        if n_permutations > 0:
+            ex.generate_permutations(seed, inv)
+        rec, sr, fam, terms, counts = ex.strata_tests(sets, sub, signs, strata=inv, family=True, terms=True)
+        return sr, fam, terms, counts, ids
+    finally:
+        ex.close()
 
 
 VARIABLE_THRESHOLD_COLUMNS = ["Sets", "Genes", "Scores", "NominalPvalues", "BestGenes", "BestThreshold", "AdaptiveScores",

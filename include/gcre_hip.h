@@ -748,6 +748,59 @@ int gcre_score_sets_sequential(gcre_ctx* ctx, const gcre_set_input* in, uint64_t
  * per batch (no other launch counter counts them, nor the reverse); -1 for a NULL context. */
 int64_t gcre_sequential_launches(const gcre_ctx* ctx);
 
+/* Stratified set scores (the Cochran-Mantel-Haenszel idea): every stratum of the cohort -- a sub-cohort, a
+ * sex, an ancestry cluster -- is scored on its own counts against the value table of ITS cases and controls, the terms are
+ * summed, and the same sum is taken under every permutation of the context.  gcre_generate_perm_masks(seed, stratum) keeps a
+ * pooled p-value valid when case fraction and carrier frequency both differ between the strata, but the pooled SCORE of a
+ * gene that is merely commoner in the case-rich stratum is large under the observed labels and under every such permutation
+ * alike; this sum is not.  `out`, *n_out: exactly what gcre_score_sets gives (the pooled score), so one call yields both.
+ * Inputs.  stratum [n]: ids 0 .. n_strata-1, n_strata 1 .. GCRE_STRATA_MAX; Z_s = the patients of stratum s, with cases_s of
+ * them among the columns < n_cases.  One raw row-major value table per stratum: T_s = tables + tab_off[s], nrow[s] x ncol[s],
+ * at least 1 x 1, the table of a cohort of cases_s cases and |Z_s| - cases_s controls; cells it does not have read as -1,
+ * as in gcre_set_value_table.  The context's own table is read only for `out`.
+ * Definition.  With P, N the unions gcre_score_sets defines (method 1: one union alone) and a label mask m -- the observed
+ * labels (the columns < n_cases), or the mask of permutation r:
+ *   term_s(m) = T_s[ |P & Z_s & m| ][ |P & Z_s \ m| ]   method 2:  + T_s[ |N & Z_s \ m| ][ |N & Z_s & m| ], added in this order
+ *   score(m)  = ((+0.0 + term_0) + term_1) + ...         ascending s, f64, additions only
+ *   score     = score(observed);   n_ge = #{r < iterations : score(mask_r) >= score}   as doubles, a NaN on either side
+ *               never counting; -1 for an invalid set (an NA member), whose score is NaN
+ * terms, optional [n_sets][n_strata]: term_s(observed), NaN rows for invalid sets.  counts, optional [n_sets][n_strata][4]:
+ * cases_pos, ctrls_pos, cases_neg, ctrls_neg of the set inside every stratum, as gcre_set_score counts them (zeros for
+ * invalid sets).  null_scores, optional [n_sets][iterations]: score(mask_r), NaN rows for invalid sets.  family_max, optional
+ * [iterations]: the maximum over the valid sets of score(mask_r), a NaN or negative score entering as +0 (all zeros without
+ * a valid set).  iterations == 0: score, terms and counts as above, n_ge = 0.
+ * The masks must keep the strata: a look-up outside "cases_s cases in stratum s" means nothing, so every resident mask is
+ * counted against every Z_s on the device first, and a context whose masks were not drawn by gcre_generate_perm_masks with
+ * these strata (or set by the caller to the same effect) is refused with GCRE_ERR_ARG.  This one refusal comes after
+ * launches: `out` holds gcre_score_sets' records, every output of this stage its defaults (NaN scores, n_ge 0 / -1).
+ * The valid sets are walked in slabs of whole sets whose stratum rows -- and null_scores rows, when asked -- stay under
+ * GCRE_STRATA_MAX_MB on the device (environment, read per call, default 1024; one set at the least; GCRE_STRATA_SLAB_SETS
+ * bounds a slab further); no result depends on the slabs.
+ * Errors, nothing launched and no output array written (*n_out as gcre_score_sets leaves it): everything gcre_score_sets
+ * refuses; GCRE_ERR_ARG -- NULL px_out, NULL stratum, n_strata outside 1 .. GCRE_STRATA_MAX, NULL tables / nrow / ncol /
+ * tab_off, a table without a row or a column, one 512-permutation tile of null_scores above GCRE_STRATA_MAX_MB;
+ * GCRE_ERR_RANGE -- a stratum id outside 0 .. n_strata-1.
+ * n_ge / iterations is a nominal permutation p-value of the summed score, one set at a time.  The terms and counts are
+ * descriptive; no test of heterogeneity between the strata is attached.  Not built: stratified joins, weights per stratum,
+ * stratified prefix / dose / sequential / min-P statistics, more than 16 strata. */
+#define GCRE_STRATA_MAX 16
+typedef struct {
+  double score;        /* the sum of the observed terms; NaN for an invalid set */
+  int64_t n_ge;        /* permutations whose sum reaches it; -1 for an invalid set */
+} gcre_strata_score;
+int gcre_score_sets_strata(gcre_ctx* ctx, const gcre_set_input* in, const int32_t* stratum, int32_t n_strata,
+                           const double* tables, const int32_t* nrow, const int32_t* ncol, const int64_t* tab_off,
+                           gcre_set_score* out, int64_t cap, int64_t* n_out,
+                           gcre_strata_score* px_out      /* [n_sets] */,
+                           double* terms                  /* optional [n_sets][n_strata] */,
+                           int32_t* counts                /* optional [n_sets][n_strata][4] */,
+                           double* null_scores            /* optional [n_sets][iterations] */,
+                           double* family_max             /* optional [iterations] */);
+/* Kernels gcre_score_sets_strata launched for its own stage on the context since gcre_create: k_strata_masks, the check of
+ * the masks (with permutations), one k_table_to_diag per stratum, then k_strata_rows, k_strata_observed and (with
+ * permutations) k_strata_null per slab (no other launch counter counts them, nor the reverse); -1 for a NULL context. */
+int64_t gcre_strata_launches(const gcre_ctx* ctx);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Carrier overlaps of caller-given sets: which sets are carried by the same patients.  No reference
  * counterpart.
