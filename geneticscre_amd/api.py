@@ -159,6 +159,7 @@ EXPORTS = [
     "gcre_score_sets_dose", "gcre_dose_launches",
     "gcre_score_sets_sequential", "gcre_sequential_launches",
     "gcre_score_sets_strata", "gcre_strata_launches",
+    "gcre_generate_weighted_masks", "gcre_weighted_thresholds", "gcre_weighted_launches",
     "gcre_set_overlap", "gcre_overlap_launches",
     "gcre_clump_sets", "gcre_clump_launches",
     "gcre_set_patient_counts", "gcre_patient_launches",
@@ -313,6 +314,11 @@ _FEATURES = {
         "gcre_score_sets_strata": (_I, [_V, ctypes.POINTER(gcre_set_input), _P, _I32, _P, _P, _P, _P, _P, _I64, ctypes.POINTER(_I64),
                                         _P, _P, _P, _P, _P]),
         "gcre_strata_launches": (_I64, [_V])}),
+    "weighted": (None, ["gcre_generate_weighted_masks", "gcre_weighted_thresholds", "gcre_weighted_launches"],
+                 "covariate-adjusted permutation masks (gcre_generate_weighted_masks)", {
+        "gcre_generate_weighted_masks": (_I, [_V, ctypes.c_uint64, _P, _P, _I32, _I64, _P]),
+        "gcre_weighted_thresholds": (_I, [_I32, _I32, _P, _P, _I32, _P, _P]),
+        "gcre_weighted_launches": (_I64, [_V])}),
     "overlap": (None, ["gcre_set_overlap"], "carrier overlaps (gcre_set_overlap)", {
         "gcre_set_overlap": (_I, [_V, ctypes.POINTER(gcre_set_input), _P, _I64, _P, _I64, _P, _P]),
         "gcre_overlap_launches": (_I64, [_V])}),
@@ -383,6 +389,7 @@ _subsample_lib = functools.partial(_feature_lib, "subsample")
 _dose_lib = functools.partial(_feature_lib, "dose")
 _sequential_lib = functools.partial(_feature_lib, "sequential")
 _strata_lib = functools.partial(_feature_lib, "strata")
+_weighted_lib = functools.partial(_feature_lib, "weighted")
 _overlap_lib = functools.partial(_feature_lib, "overlap")
 _clump_lib = functools.partial(_feature_lib, "clump")
 _patients_lib = functools.partial(_feature_lib, "patients")
@@ -990,6 +997,29 @@ class JoinExec:
         else:
             st = np.ascontiguousarray(strata, dtype=np.int32)
             self._check(self._lib.gcre_generate_perm_masks(self._h, int(seed) & (2**64 - 1), _ptr(st), int(st.max()) + 1))
+
+    def generate_weighted_permutations(self, seed: int, odds, strata=None, max_attempts: int = 1 << 20, attempts: bool = False):
+        """Covariate-adjusted permutations (gcre_generate_weighted_masks; Epstein et al. 2012): the case
+        labels of every permutation are redrawn with per-patient ``odds`` -- one finite value >= 0 per patient, e.g.
+        ``report.case_odds(covariates, ...)`` -- conditional on the number of cases, inside every stratum when ``strata`` is
+        given (one id per patient, any integers, mapped to 0 .. S-1 in ascending order; at most 16 distinct).  Equal odds
+        give the uniform law of ``generate_permutations`` (not its bits).  The masks replace the context's, so every join and
+        every set statistic that follows is tested against the adjusted null; the adjustment is on the null, not on the
+        statistic, and the p-values are only as good as the model behind ``odds``.  ``max_attempts``: the cap of the exact
+        rejection sampler per (permutation, stratum), not a tuning knob; a call that meets it is refused and the context
+        keeps the masks it had.  ``attempts=True`` returns the accepted attempts, uint32 [iters][S].
+        ``report.weighted_masks`` restates the draw in numpy on ``weighted_thresholds``.  Refusals raise GcreError."""
+        w, st, S, _ = _weighted_args(odds, strata, self.num_cases + self.num_ctrls)
+        lib = _weighted_lib()
+        att = np.zeros((self.iters, S), dtype=np.uint32) if attempts else None
+        self._check_gcre(lib.gcre_generate_weighted_masks(self._h, int(seed) & (2**64 - 1), _ptr(w), _ptr(st), S if st is not None else 0,
+                                                          int(max_attempts), _ptr(att) if attempts and att.size else None))
+        return att
+
+    def weighted_launches(self) -> int:
+        """k_weighted_search / k_weighted_write launches of ``generate_weighted_permutations`` on this context so far: two
+        per successful call, one for a call that met the cap, none for one refused up front."""
+        return int(_weighted_lib().gcre_weighted_launches(self._h))
 
     def set_perm_window(self, k0: int, k1: int) -> None:
         """Joins that follow score permutations [k0, k1) only (tile aligned); see gcre_set_perm_window."""
@@ -1697,6 +1727,38 @@ def values_table(n_cases: int, n_ctrls: int) -> np.ndarray:
     if rc != GCRE_OK:
         raise ValueError("bad table dimensions")
     return out
+
+
+def _weighted_args(odds, strata, n: int):
+    """odds as float64 [n] and ``strata`` mapped to ids 0 .. S-1 in ascending order (None: one stratum): (odds, ids or None,
+    S, the distinct strata)."""
+    w = np.ascontiguousarray(np.asarray(odds, dtype=np.float64).reshape(-1))
+    if len(w) != n:
+        raise ValueError(f"odds: one value per patient ({n}), not {len(w)}")
+    if strata is None:
+        return w, None, 1, np.zeros(1, np.int64)
+    ids, inv = np.unique(np.asarray(strata).reshape(-1), return_inverse=True)
+    if len(inv) != n:
+        raise ValueError(f"strata: one id per patient ({n}), not {len(inv)}")
+    return w, np.ascontiguousarray(inv, dtype=np.int32), len(ids), ids
+
+
+def weighted_thresholds(odds, n_cases: int, n_ctrls: int, strata=None):
+    """The 32-bit thresholds of ``JoinExec.generate_weighted_permutations`` (gcre_weighted_thresholds) and
+    the expected attempts per stratum, sqrt(2 pi V): ``(uint32 [n], float64 [S])``.  Host only, no GPU.  The thresholds are
+    the definition of the law that is sampled -- conditional Bernoulli with p = thr / 2^32 -- and what
+    ``report.weighted_masks`` takes.  ``strata`` as ``generate_weighted_permutations`` reads them.  Refusals raise GcreError
+    with the library's message."""
+    n = int(n_cases) + int(n_ctrls)
+    w, st, S, _ = _weighted_args(odds, strata, n)
+    lib = _weighted_lib()
+    thr = np.zeros(max(n, 1), dtype=np.uint32)
+    exp = np.zeros(max(S, 1), dtype=np.float64)
+    rc = lib.gcre_weighted_thresholds(n, int(n_cases), _ptr(w) if n else _ptr(np.zeros(1)), _ptr(st), S if st is not None else 0,
+                                      _ptr(thr), _ptr(exp))
+    if rc != GCRE_OK:
+        raise GcreError(lib.gcre_last_error(None).decode())
+    return thr[:n], exp[:S]
 
 
 def rccl_selftest(device: int = 0) -> None:

@@ -289,6 +289,7 @@ struct gcre_ctx {
   int64_t dose_launches = 0;         // kernels gcre_score_sets_dose launched for its own stage (gcre_dose_launches)
   int64_t sequential_launches = 0;   // kernels gcre_score_sets_sequential launched for its own stage (gcre_sequential_launches)
   int64_t strata_launches = 0;       // kernels gcre_score_sets_strata launched for its own stage (gcre_strata_launches)
+  int64_t weighted_launches = 0;     // k_weighted_search / k_weighted_write launches of this context (gcre_weighted_launches)
 
   // resident inputs
   uint64_t* d_case_mask = nullptr;   // [Wp]

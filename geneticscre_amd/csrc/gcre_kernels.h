@@ -844,6 +844,27 @@ hipError_t launch_strata_rows(const StrataArgs& a, int method, hipStream_t strea
 hipError_t launch_strata_observed(const StrataArgs& a, int method, hipStream_t stream);
 hipError_t launch_strata_null(const StrataArgs& a, int method, hipStream_t stream);
 
+// ---- covariate-adjusted permutation masks (gcre_weighted.hip; the law and the rule: gcre_weighted.h) ----
+// k_weighted_search finds the accepted attempt of every (permutation, stratum), one wave each, and writes no mask bit;
+// k_weighted_write, launched only when nothing was left over, rebuilds the accepted attempts' bits a lane per permutation.
+struct WeightedArgs {
+  uint64_t seed1;               // wt_seed(seed)
+  const int32_t* cols;          // per stratum, one behind the other: the columns of Z_s ...
+  const uint32_t* cthr;         // ... and their thresholds, in the same order
+  const uint32_t* soff;         // [S + 1] where stratum s starts in cols / cthr
+  const uint32_t* cases_in;     // [S]
+  uint32_t* att;                // [S][K] accepted attempts, kWeightedNone where the cap was met
+  unsigned int* left;           // one dword, zero on entry: (r, s) pairs without an accepted attempt
+  uint32_t cap;                 // max_attempts
+  // k_weighted_write
+  const int32_t* stratum;       // [n] or NULL (one stratum)
+  const uint32_t* thr;          // [n] thresholds by column
+  uint32_t* masks;              // [W32p][Kpad]
+  int S, K, n, W32p, Kpad;
+};
+hipError_t launch_weighted_search(const WeightedArgs& a, hipStream_t stream);
+hipError_t launch_weighted_write(const WeightedArgs& a, hipStream_t stream);
+
 // ---- carrier-overlap counts of caller-given sets (gcre_overlap.hip) ----
 constexpr int kOverlapTile = 64;    // pairs per edge of a block's tile
 constexpr int kOverlapChunk = 32;   // dwords of a row per staged chunk (128 bytes): rows are padded to a multiple of it

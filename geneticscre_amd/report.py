@@ -280,7 +280,7 @@ def parse_sets(paths, genes: Sequence[str]) -> Tuple[List[List[str]], List[List[
 
 
 def _score_sets(rows, signs, data, n_cases, n_ctrls, method, n_permutations, strata, seed, device, family_inference=False,
-                minp=False):
+                minp=False, case_odds=None):
     """score_sets on the rows the sets use, on a context of its own: (records, family maxima); with ``family_inference``
     family_tests instead: (records, family maxima, family records, kmax); with ``minp`` the MINP_SCORE records of
     minp_tests on the same context behind either."""
@@ -293,7 +293,7 @@ def _score_sets(rows, signs, data, n_cases, n_ctrls, method, n_permutations, str
     try:
         ex.set_value_table(api.values_table(n_cases, n_ctrls))
         if n_permutations > 0:
-            ex.generate_permutations(seed, strata)
+            _draw_permutations(ex, seed, strata, case_odds)
         more = (ex.minp_tests(sets, sub, signs)[1],) if minp else ()
         if family_inference:
             rec, fam, kmax = ex.family_tests(sets, sub, signs, kmax=True)
@@ -317,7 +317,7 @@ def score_paths(paths, genes: Sequence[str], data: np.ndarray, n_cases: int, n_c
                 device: int = 0, gwaspa_out: Optional[Dict[str, object]] = None, minp: bool = False,
                 competitive: int = 0, competitive_bins: int = 10, fixed: Optional[Sequence[str]] = None,
                 stability: int = 0, stability_cuts=None, sequential: int = 0, sequential_hits: int = 20,
-                stratified: bool = False, family_inference: bool = False):
+                stratified: bool = False, case_odds=None, family_inference: bool = False):
     """Permutation tests of paths and gene sets the caller names (gcre_score_sets on the device): what GWASPA cannot
     answer for a cascade outside its top K, or for a KEGG / Reactome list.  ``paths`` as ``parse_sets`` reads them;
     genes are looked up after ``preprocess_table(threshold)``, as GWASPA and ``decorated_table`` do (a symbol not found is
@@ -391,8 +391,20 @@ def score_paths(paths, genes: Sequence[str], data: np.ndarray, n_cases: int, n_c
     sums the terms (the Cochran-Mantel-Haenszel idea); ``StratifiedPvalues`` is the nominal permutation p-value of that sum
     under the same masks, ``StratifiedFamilyPvalues`` single-step max-T over the given paths.  ``Score.<id>`` / ``Cases.<id>``
     / ``Controls.<id>`` show every stratum's term and carriers: descriptive, no test of heterogeneity is attached.
-    ``stratified=False`` returns exactly the frame without it."""
+    ``stratified=False`` returns exactly the frame without it.
+
+    ``case_odds``: one fitted odds of being a case per patient (``case_odds(covariates, ...)``); the masks then come from
+    ``generate_weighted_permutations(seed, case_odds, strata)`` (gcre_generate_weighted_masks): every
+    permutation p-value above is taken against labels redrawn with these odds, so a continuous covariate that shifts both
+    the case fraction and the carrier frequency is in the null.  The adjustment is on the null, not on ``Scores``, and the
+    p-values are only as good as the fitted model.  ``gwaspa_out`` must come from ``gwaspa`` with the same ``case_odds``
+    (ValueError otherwise); ``sequential`` > 0 is refused with it (that stage makes its own, uniform masks).  None, the
+    default: exactly the frame without it."""
     import pandas as pd
+    if case_odds is not None and int(sequential) > 0:
+        raise ValueError("case_odds: sequential p-values draw their own uniform masks; weighted draws are not built there")
+    if gwaspa_out is not None and gwaspa_out.get("case_odds_digest") != _odds_digest(case_odds):
+        raise ValueError("gwaspa_out was drawn under different case_odds: its TestScores are not the null of these masks")
     if int(stability) < 0:
         raise ValueError("stability: the number of draws must not be negative")
     if int(sequential) < 0:
@@ -405,7 +417,7 @@ def score_paths(paths, genes: Sequence[str], data: np.ndarray, n_cases: int, n_c
     genes, data = preprocess_table(genes, data, threshold, n_cases, n_ctrls)
     names, rows, signs = parse_sets(paths, genes)
     K = int(n_permutations)
-    rec, fam, *more = _score_sets(rows, signs, data, n_cases, n_ctrls, method, K, strata, seed, device, family_inference, minp)
+    rec, fam, *more = _score_sets(rows, signs, data, n_cases, n_ctrls, method, K, strata, seed, device, family_inference, minp, case_odds)
     valid = rec["valid"] != 0
     score = rec["score"]
     lengths = np.array([len(n) for n in names], dtype=np.int64)
@@ -453,7 +465,7 @@ def score_paths(paths, genes: Sequence[str], data: np.ndarray, n_cases: int, n_c
         cols.update(sequential_columns(seq, valid))
         names_out += SEQUENTIAL_COLUMNS
     if stratified:
-        sr, sfam, terms, counts, ids = _stratified_scores(rows, signs, data, n_cases, n_ctrls, method, K, strata, seed, device)
+        sr, sfam, terms, counts, ids = _stratified_scores(rows, signs, data, n_cases, n_ctrls, method, K, strata, seed, device, case_odds)
         more_cols = stratified_columns(sr, valid, sfam, terms, counts, ids, K)
         cols.update(more_cols)
         names_out += list(more_cols)
@@ -1000,6 +1012,156 @@ def permutation_masks(n_cases: int, n_ctrls: int, perms, seed: int, strata=None)
     return out
 
 
+WEIGHTED_TAG = 0x7765696768746564   # kWeightedTag (csrc/gcre_weighted.h): "weighted"
+WEIGHTED_NONE = 0xFFFFFFFF          # kWeightedNone: no accepted attempt below the cap
+
+
+def _draw_permutations(ex, seed, strata, case_odds) -> None:
+    """The masks of a ``gwaspa`` / ``score_paths`` context: uniform, or with ``case_odds`` the covariate-adjusted ones."""
+    if case_odds is None:
+        ex.generate_permutations(seed, strata)
+    else:
+        ex.generate_weighted_permutations(seed, case_odds, strata)
+
+
+def _odds_digest(case_odds):
+    """What ``gwaspa`` records of the odds its masks were drawn with, and ``score_paths`` compares: None, or a digest."""
+    if case_odds is None:
+        return None
+    import hashlib
+    h = hashlib.sha256(np.ascontiguousarray(np.asarray(case_odds, dtype=np.float64).reshape(-1)).tobytes())
+    return h.hexdigest()
+
+
+def weighted_masks(thresholds, n_cases: int, n_ctrls: int, perms, seed: int, strata=None, max_attempts: int = 1 << 20):
+    """The draw rule of ``JoinExec.generate_weighted_permutations`` (csrc/gcre_weighted.h) in numpy, on the
+    library's own ``thresholds`` (``api.weighted_thresholds``: uint32 per patient): ``(masks, attempts)`` -- bool
+    [perms][n], row r the patients permutation r labels as cases, and uint32 [perms][S], the accepted attempts.  ``strata``:
+    one id per patient, any integers (mapped to 0 .. S-1 in ascending order), or None for one stratum.
+
+    Exact rejection in integers: with seed' = mix64(seed ^ WEIGHTED_TAG), key_r = mix64(seed' ^ C2 (r + 1)), base_rs =
+    mix64(key_r ^ C1 (s + 1)) and pair_rsj = mix64(base_rs + j), attempt a of (r, s) reads u = mix64(pair_rsj + c), j = a >> 1,
+    for the patient in column c of stratum s and labels it a case when the high half of u (a even) or the low half (a odd)
+    is below the patient's threshold.  The accepted attempt is the smallest a whose case count over the stratum equals its
+    cases among the columns < n_cases; a pair without one below ``max_attempts`` gets WEIGHTED_NONE and no case."""
+    n_cases, n_ctrls = int(n_cases), int(n_ctrls)
+    n = n_cases + n_ctrls
+    thr = np.asarray(thresholds, dtype=_U64).reshape(-1)
+    if len(thr) != n:
+        raise ValueError(f"thresholds: one per patient ({n}), not {len(thr)}")
+    if strata is None:
+        inv, S = np.zeros(n, np.int64), 1
+    else:
+        ids, inv = np.unique(np.asarray(strata).reshape(-1), return_inverse=True)
+        S = len(ids)
+        if len(inv) != n:
+            raise ValueError(f"strata: one id per patient ({n}), not {len(inv)}")
+    K = int(perms)
+    cap = int(max_attempts)
+    masks = np.zeros((K, n), bool)
+    att = np.full((K, S), WEIGHTED_NONE, dtype=np.uint32)
+    r = np.arange(K, dtype=_U64)
+    with np.errstate(over="ignore"):
+        seed1 = _mix64(_U64(int(seed) & (2**64 - 1)) ^ _U64(WEIGHTED_TAG))
+        key = _mix64(seed1 ^ (_U64(0x51ED270B7F3C9A1D) * (r + _U64(1))))
+    for s in range(S):
+        cols = np.flatnonzero(inv == s)
+        need = int((cols < n_cases).sum())
+        with np.errstate(over="ignore"):
+            base = _mix64(key ^ (_U64(0xD1B54A32D192ED03) * _U64(s + 1)))
+        todo = np.arange(K)
+        j = 0
+        while len(todo) and 2 * j < cap:
+            with np.errstate(over="ignore"):
+                pair = _mix64(base[todo] + _U64(j))
+                u = _mix64(pair[:, None] + cols.astype(_U64)[None, :])
+            even = (u >> _U64(32)) < thr[cols][None, :]
+            odd = (u & _U64(0xFFFFFFFF)) < thr[cols][None, :]
+            hit_e = even.sum(axis=1) == need
+            hit_o = (odd.sum(axis=1) == need) & ~hit_e & (2 * j + 1 < cap)
+            for hit, bits, a in ((hit_e, even, 2 * j), (hit_o, odd, 2 * j + 1)):
+                rows = todo[hit]
+                masks[np.ix_(rows, cols)] = bits[hit]
+                att[rows, s] = a
+            todo = todo[~(hit_e | hit_o)]
+            j += 1
+    return masks, att
+
+
+def conditional_bernoulli_reference(p, m: int, subsets: bool = False):
+    """The target law of the weighted masks, exactly: independent Bernoulli(p_c) conditioned on exactly ``m`` successes
+    (equivalently P(A) proportional to the product of the odds p_c / (1 - p_c) over A).  Returns the inclusion
+    probabilities P(c in A), float64 [n], by the standard recursion on R(k, C) = the sum over k-subsets of C of the product
+    of the odds: R(k, C) = R(k, C \\ c) + w_c R(k - 1, C \\ c), P(c in A) = w_c R(m - 1, C \\ c) / R(m, C).  With ``subsets``
+    (tiny n) also ``(subset tuples in lexicographic order, their probabilities)``.  p_c = 1 is not accepted (an odds of
+    +infinity)."""
+    p = np.asarray(p, dtype=np.float64).reshape(-1)
+    n, m = len(p), int(m)
+    if (p < 0).any() or (p >= 1).any() or not 0 <= m <= n:
+        raise ValueError("p in [0, 1) and 0 <= m <= n are required")
+    w = p / (1.0 - p)
+
+    def R(ws):
+        e = np.zeros(m + 1)
+        e[0] = 1.0
+        for x in ws:
+            e[1:] = e[1:] + x * e[:-1]
+        return e
+
+    total = R(w)[m]
+    if total <= 0:
+        raise ValueError("fewer patients with positive odds than successes")
+    incl = np.array([w[c] * R(np.delete(w, c))[m - 1] / total if m >= 1 else 0.0 for c in range(n)])
+    if not subsets:
+        return incl
+    import itertools
+    subs = list(itertools.combinations(range(n), m))
+    pr = np.array([np.prod(w[list(a)]) / total for a in subs])
+    return incl, subs, pr
+
+
+def case_odds(covariates, n_cases: int, n_ctrls: int, ridge: float = 0.0, max_iter: int = 50, tol: float = 1e-10) -> np.ndarray:
+    """Fitted odds of being a case, for ``generate_weighted_permutations`` / ``gwaspa(case_odds=)``: a logistic regression of
+    the labels (the columns < n_cases are the cases) on ``covariates`` ([n] or [n][k]) with an intercept, by iteratively
+    reweighted least squares in numpy; returns p / (1 - p), float64 [n].  ``ridge``: an L2 penalty on the slopes (not the
+    intercept), 0 by default.  Raises ValueError on separation (a fitted probability within 1e-8 of 0 or 1, or a
+    coefficient beyond 30 in absolute value on standardised covariates) and on non-convergence, instead of returning huge
+    odds silently.  The permutation p-values that follow are only as good as this model."""
+    n_cases, n_ctrls = int(n_cases), int(n_ctrls)
+    n = n_cases + n_ctrls
+    X = np.asarray(covariates, dtype=np.float64)
+    X = X.reshape(-1, 1) if X.ndim <= 1 else X
+    if X.shape[0] != n or not np.isfinite(X).all():
+        raise ValueError(f"covariates: finite values, one row per patient ({n})")
+    if n_cases == 0 or n_ctrls == 0:
+        raise ValueError("case_odds: needs at least one case and one control")
+    # standardise the columns that vary: the fitted probabilities do not depend on it, the conditioning does
+    sd = X.std(axis=0)
+    Z = (X[:, sd > 0] - X[:, sd > 0].mean(axis=0)) / sd[sd > 0]
+    A = np.hstack([np.ones((n, 1)), Z])
+    y = (np.arange(n) < n_cases).astype(np.float64)
+    pen = np.diag([0.0] + [float(ridge)] * Z.shape[1])
+    beta = np.zeros(A.shape[1])
+    beta[0] = np.log(n_cases / n_ctrls)
+    for _ in range(int(max_iter)):
+        eta = A @ beta
+        mu = 1.0 / (1.0 + np.exp(-eta))
+        wgt = mu * (1.0 - mu)
+        if (np.abs(beta) > 30).any() or (mu < 1e-8).any() or (mu > 1 - 1e-8).any():
+            raise ValueError("case_odds: the covariates separate cases from controls (perfectly or nearly): no finite fit; "
+                             "drop a covariate or set ridge > 0")
+        H = A.T @ (A * wgt[:, None]) + pen
+        step = np.linalg.solve(H, A.T @ (y - mu) - pen @ beta)
+        beta = beta + step
+        if np.abs(step).max() < tol:
+            mu = 1.0 / (1.0 + np.exp(-(A @ beta)))
+            if (np.abs(beta) > 30).any() or (mu < 1e-8).any() or (mu > 1 - 1e-8).any():
+                raise ValueError("case_odds: the covariates separate cases from controls (perfectly or nearly): no finite fit; "
+                                 "drop a covariate or set ridge > 0")
+            return mu / (1.0 - mu)
+    raise ValueError(f"case_odds: no convergence in {int(max_iter)} IRLS steps")
+
+
 def sequential_reference(null, obs, valid, hits: int, max_perms: int) -> Dict[str, np.ndarray]:
     """The definition of gcre_score_sets_sequential taken literally on a null matrix.  ``null``
     [sets][>= max_perms]: the null score of every set under permutations 0, 1, ... in order (the f32 values of
@@ -1160,7 +1322,7 @@ def stratified_columns(strata_records, valid, family_max, terms, counts, ids, pe
     return cols
 
 
-def _stratified_scores(rows, signs, data, n_cases, n_ctrls, method, n_permutations, strata, seed, device):
+def _stratified_scores(rows, signs, data, n_cases, n_ctrls, method, n_permutations, strata, seed, device, case_odds=None):
     """strata_tests for ``score_paths``: on the rows the sets use, on a context of its own whose masks keep ``strata``;
     (strata records, family maxima, terms, counts, the ids ascending)."""
     from . import api
@@ -1173,7 +1335,7 @@ def _stratified_scores(rows, signs, data, n_cases, n_ctrls, method, n_permutatio
     try:
         ex.set_value_table(api.values_table(n_cases, n_ctrls))
         if n_permutations > 0:
-            ex.generate_permutations(seed, inv)
+            _draw_permutations(ex, seed, inv, case_odds)
         rec, sr, fam, terms, counts = ex.strata_tests(sets, sub, signs, strata=inv, family=True, terms=True)
         return sr, fam, terms, counts, ids
     finally:
@@ -2719,7 +2881,7 @@ def frames_of(prep: Prepared, levels) -> Dict[str, Dict[str, np.ndarray]]:
 
 def gwaspa(genes: Sequence[str], data: np.ndarray, n_cases: int, n_ctrls: int, network, signed: bool = False,
            threshold: float = 0.05, top_k: int = 10, path_length: int = 5, n_permutations: int = 100,
-           strata: Optional[Sequence[int]] = None, seed: int = 0, device: int = 0,
+           strata: Optional[Sequence[int]] = None, seed: int = 0, device: int = 0, case_odds=None,
            decorated_pvalues: bool = False, gene_table: bool = False, fdr: bool = False,
            clump: Optional[float] = None, clump_conditional: bool = False, false_counts: bool = False,
            false_count_ks: Sequence[int] = (2, 5, 10), false_count_alpha: float = 0.05,
@@ -2802,6 +2964,13 @@ def gwaspa(genes: Sequence[str], data: np.ndarray, n_cases: int, n_ctrls: int, n
     group_sets, skipped).  The table is descriptive: exact counts, no test statistic -- the paths were selected on these
     very labels, so their carriers are enriched in cases by construction; look for a handful of patients on every hit (a
     batch artefact), not for significance.  False, the default: the output and every launch are what they were.
+
+    ``case_odds``: one fitted odds of being a case per patient (``case_odds(covariates, ...)``); the run's masks then come
+    from ``generate_weighted_permutations(seed, case_odds, strata)`` (Epstein et al. 2012) and every
+    ``Pvalues`` is taken against labels redrawn with these odds.  The adjustment is on the null, not on the scores, and the
+    p-values are only as good as the fitted model.  ``decorated_pvalues`` and ``clump_conditional`` draw nulls of their own
+    and are refused with it (ValueError before anything runs).  The output records "case_odds_digest", which
+    ``score_paths(gwaspa_out=)`` compares.  None, the default: the output and every launch are what they were.
     """
     from . import api
     from .synth import Problem
@@ -2809,6 +2978,9 @@ def gwaspa(genes: Sequence[str], data: np.ndarray, n_cases: int, n_ctrls: int, n
 
     method = "method2" if signed else "method1"
     check_input(n_cases, n_ctrls, method, threshold, top_k, path_length, n_permutations)
+    if case_odds is not None and (decorated_pvalues or clump_conditional):
+        raise ValueError("case_odds: decorated_pvalues and clump_conditional draw uniform nulls of their own; weighted draws are "
+                         "not built there")
     if clump_significant and (clump is None or significant is None):
         raise ValueError("clump_significant: needs both clump (the overlap r) and significant (the family-wise level)")
     if clump_significant and not 0 < clump <= 1:
@@ -2845,7 +3017,7 @@ def gwaspa(genes: Sequence[str], data: np.ndarray, n_cases: int, n_ctrls: int, n
     ex.top_k = top_k
     ex.set_value_table(table)
     if n_permutations > 0:
-        ex.generate_permutations(seed, strata)
+        _draw_permutations(ex, seed, strata, case_odds)
     tallies = {}
     if gene_table:
         tables = gene_tables(levels, g, n2)
@@ -2856,6 +3028,8 @@ def gwaspa(genes: Sequence[str], data: np.ndarray, n_cases: int, n_ctrls: int, n
     out = {"GWASPA.Results": results_table(lsts, path_length, frames,
                                            (prep.ents_uid, prep.ents_symbol), (prep.ents2_uid, prep.ents2_symbol)),
            "levels": lsts, "prepared": prep}
+    if case_odds is not None:
+        out["case_odds_digest"] = _odds_digest(case_odds)
     hit_lists, cutoffs = {}, {}
     if significant is not None:
         for L, name in enumerate(GENE_LEVELS[:path_length], start=1):

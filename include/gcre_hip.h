@@ -801,6 +801,48 @@ int gcre_score_sets_strata(gcre_ctx* ctx, const gcre_set_input* in, const int32_
  * permutations) k_strata_null per slab (no other launch counter counts them, nor the reverse); -1 for a NULL context. */
 int64_t gcre_strata_launches(const gcre_ctx* ctx);
 
+/* Covariate-adjusted permutation masks (Epstein et al. 2012): case labels redrawn with per-patient odds,
+ * conditional on the number of cases of every stratum -- Fisher's non-central hypergeometric law with one patient per class.
+ * Every statistic of this library is a count over the context's resident masks, so these masks put a continuous covariate
+ * (ancestry components, age, depth) into the null of the joins and of every set statistic at once.  The adjustment is on the
+ * null, not on the statistic, and the p-values are only as good as the model that gave the odds.
+ * Inputs.  odds [n]: one finite double >= 0 per patient column (the cases are the columns < n_cases, as everywhere); stratum
+ * [n] or NULL: ids 0 .. n_strata-1, n_strata 1 .. GCRE_STRATA_MAX; Z_s = the patients of stratum s, cases_s of them cases.
+ * Target law.  Inside stratum s mask r is a subset A of Z_s with |A| = cases_s and P(A) proportional to the product of odds_c
+ * over A; strata are independent.  Equal odds: the uniform law of gcre_generate_perm_masks (NOT its bits).
+ * Calibration (host).  Per stratum the tilt t_s is found by bisection so that p_c = t_s odds_c / (1 + t_s odds_c) sums to
+ * cases_s, and thr_c = min(floor(p_c 2^32), 2^32 - 1).  From there on the thresholds ARE the definition: what is sampled is
+ * conditional Bernoulli with p_c = thr_c / 2^32, exactly.  cases_s = 0: every thr 0; cases_s = the patients of Z_s with
+ * positive odds: 2^32 - 1 for those.  | sum thr_c / 2^32 - cases_s | < |Z_s| (2^-32 + 2^-44) + |Z_s|^2 2^-52.
+ * The draw is exact rejection in integers.  With
+ *   seed'    = gcre_mix64(seed ^ 0x7765696768746564)          key_r   = gcre_mix64(seed' ^ (0x51ed270b7f3c9a1d * (r + 1)))
+ *   base_rs  = gcre_mix64(key_r ^ (0xd1b54a32d192ed03 * (s + 1)))      pair_rsj = gcre_mix64(base_rs + j)
+ * attempt a = 0, 1, 2, ... of (r, s) reads u = gcre_mix64(pair_rsj + c) with j = a >> 1 for the patient in COLUMN c and labels
+ * it a case when the high half of u (a even) or the low half (a odd) is below thr_c.  The accepted attempt a*(r, s) is the
+ * SMALLEST a whose case count over Z_s is exactly cases_s; mask r is the union over s of the accepted attempts.  Nothing
+ * depends on grid, batch, launch order or memory layout.  About sqrt(2 pi V_s) attempts per (r, s), V_s = sum p (1 - p).
+ * max_attempts: a cap (above 2^31 it acts as 2^31), not a tuning knob; 2^20 is a sensible value.  attempts_out, optional
+ * [iterations][n_strata] (one column without `stratum`): a*(r, s).
+ * iterations == 0, the streams, the transposed copy and the reset of the permutation window: as gcre_generate_perm_masks.
+ * Errors, nothing launched: GCRE_ERR_ARG with a message naming the stratum -- NULL odds, an odds value that is negative, NaN
+ * or infinite, a stratum with fewer patients of positive odds than cases, n_strata outside 1 .. GCRE_STRATA_MAX, a stratum id
+ * out of range, max_attempts < 1; GCRE_ERR_RANGE -- a stratum whose estimate sqrt(2 pi V_s) alone exceeds max_attempts.
+ * After the search launch: GCRE_ERR_RANGE saying how many permutations were left over without an accepted attempt below
+ * max_attempts; no mask bit was written, and the context's masks, whether it has any, and its window are what they were.
+ * Not built: weighted draws in the sequential and subsample set scores (they make their own masks), weighted urns for
+ * decorated p-values, an exact sampler without rejection, odds of +infinity (forced cases). */
+int gcre_generate_weighted_masks(gcre_ctx* ctx, uint64_t seed, const double* odds, const int32_t* stratum, int32_t n_strata,
+                                 int64_t max_attempts, uint32_t* attempts_out /* optional [iterations][n_strata] */);
+/* The thresholds and sqrt(2 pi V_s) alone; host only, no device is touched.  thr_out [n]; expected_attempts_out optional
+ * [n_strata] (one entry without `stratum`).  Refuses what the call above refuses of odds and strata; the message is read with
+ * a NULL context. */
+int gcre_weighted_thresholds(int32_t n, int32_t n_cases, const double* odds, const int32_t* stratum, int32_t n_strata,
+                             uint32_t* thr_out, double* expected_attempts_out /* optional [n_strata] */);
+/* k_weighted_search / k_weighted_write launches on the context since gcre_create: two per successful call, one for a call
+ * that met the cap, none for one refused up front (no other launch counter counts them, nor the reverse); -1 for a NULL
+ * context. */
+int64_t gcre_weighted_launches(const gcre_ctx* ctx);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Carrier overlaps of caller-given sets: which sets are carried by the same patients.  No reference
  * counterpart.
