@@ -160,6 +160,7 @@ EXPORTS = [
     "gcre_score_sets_sequential", "gcre_sequential_launches",
     "gcre_score_sets_strata", "gcre_strata_launches",
     "gcre_generate_weighted_masks", "gcre_weighted_thresholds", "gcre_weighted_launches",
+    "gcre_score_sets_sequential_weighted",
     "gcre_set_overlap", "gcre_overlap_launches",
     "gcre_clump_sets", "gcre_clump_launches",
     "gcre_set_patient_counts", "gcre_patient_launches",
@@ -319,6 +320,10 @@ _FEATURES = {
         "gcre_generate_weighted_masks": (_I, [_V, ctypes.c_uint64, _P, _P, _I32, _I64, _P]),
         "gcre_weighted_thresholds": (_I, [_I32, _I32, _P, _P, _I32, _P, _P]),
         "gcre_weighted_launches": (_I64, [_V])}),
+    "sequential_weighted": ("sequential", ["gcre_score_sets_sequential_weighted"],
+                            "weighted sequential p-values (gcre_score_sets_sequential_weighted)", {
+        "gcre_score_sets_sequential_weighted": (_I, [_V, ctypes.POINTER(gcre_set_input), ctypes.c_uint64, _P, _P, _I, _I64, _I64, _I64,
+                                                     _P, _I64, ctypes.POINTER(_I64), _P])}),
     "overlap": (None, ["gcre_set_overlap"], "carrier overlaps (gcre_set_overlap)", {
         "gcre_set_overlap": (_I, [_V, ctypes.POINTER(gcre_set_input), _P, _I64, _P, _I64, _P, _P]),
         "gcre_overlap_launches": (_I64, [_V])}),
@@ -1355,6 +1360,35 @@ class JoinExec:
                                                         len(out), ctypes.byref(n_out), _ptr(seq)))
         return out[:n_out.value], seq[:n_out.value]
 
+    def weighted_sequential_tests(self, sets, rows, signs=None, odds=None, hits: int = 20, max_perms: int = 10**6, seed: int = 0,
+                                  strata=None, max_attempts: int = 1 << 20):
+        """Sequential permutation p-values under covariate-adjusted permutations (gcre_score_sets_sequential_weighted;
+        DESIGN.md §3.24): ``sequential_tests`` with the masks ``generate_weighted_permutations(seed, odds, strata,
+        max_attempts)`` draws -- permutation r is the same mask here and there -- made in batches as they are needed and never
+        kept.  ``odds`` (required) and ``strata`` as ``generate_weighted_permutations`` reads them (any integer ids, mapped to
+        0 .. S-1 in ascending order).  Returns ``(records, seq)`` as ``sequential_tests`` does.  Each weighted permutation
+        costs about sqrt(2 pi V) attempts over the whole stratum, where a uniform one costs one hash per patient.
+
+        Let R be the first permutation below ``max_perms`` with a stratum that has no accepted attempt below ``max_attempts``.
+        The sets are scored on the permutations in front of R; if every set has stopped there, the answer is complete and
+        returned, otherwise the call raises GcreError (GCRE_ERR_RANGE) naming R, the stratum, the cap and the sets still
+        active.  ``report.weighted_sequential_reference`` states the rule in numpy.  ``sequential_launches`` counts the
+        kernels: four per batch.  A missing or misshapen ``odds`` / ``strata`` is a ValueError; other errors raise
+        GcreError."""
+        if odds is None:
+            raise ValueError("odds: one value per patient is required (sequential_tests draws uniform permutations)")
+        w, st, S, _ = _weighted_args(odds, strata, self.num_cases + self.num_ctrls)
+        inp, keep = _set_input(sets, rows, signs, self.num_cases + self.num_ctrls)
+        n_sets = inp.n_sets
+        lib = _feature_lib("sequential_weighted")
+        out = np.zeros(max(n_sets, 1), dtype=SET_SCORE)
+        seq = np.zeros(max(n_sets, 1), dtype=SEQ_SCORE)
+        n_out = ctypes.c_int64(0)
+        self._check_gcre(lib.gcre_score_sets_sequential_weighted(self._h, ctypes.byref(inp), int(seed) & (2**64 - 1), _ptr(w), _ptr(st),
+                                                                 S if st is not None else 0, int(max_attempts), int(hits),
+                                                                 int(max_perms), _ptr(out), len(out), ctypes.byref(n_out), _ptr(seq)))
+        return out[:n_out.value], seq[:n_out.value]
+
     def strata_tests(self, sets, rows, signs=None, strata=None, tables=None, family: bool = False, null: bool = False,
                      terms: bool = False):
         """Stratified scores of the given sets (gcre_score_sets_strata): every stratum of the cohort scored on
@@ -1411,7 +1445,8 @@ class JoinExec:
         return int(_strata_lib().gcre_strata_launches(self._h))
 
     def sequential_launches(self) -> int:
-        """Kernels ``sequential_tests`` launched for its own stage on this context so far: three per batch."""
+        """Kernels ``sequential_tests`` launched for its own stage on this context so far: three per batch; and those of
+        ``weighted_sequential_tests``: four per batch, the search alone for a batch whose first permutation is left over."""
         return int(_feature_lib("sequential").gcre_sequential_launches(self._h))
 
     def dose_launches(self) -> int:

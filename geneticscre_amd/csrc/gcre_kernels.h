@@ -865,6 +865,33 @@ struct WeightedArgs {
 hipError_t launch_weighted_search(const WeightedArgs& a, hipStream_t stream);
 hipError_t launch_weighted_write(const WeightedArgs& a, hipStream_t stream);
 
+// ---- weighted sequential p-values: one batch of covariate-adjusted masks (gcre_seq_weighted.hip) ----
+// Permutations [r0, r0 + nb) of the weighted rule in k_seq_null's batch layout.  k_seq_weighted_search finds the accepted
+// attempts of the batch's columns and the first column without one; k_seq_weighted_write, launched on the columns in front of
+// it, writes their masks as k_seq_masks would: [W32p][stride] dwords, the columns nb .. stride-1 and the rows beyond the
+// patients zero.
+struct SeqWeightedArgs {
+  uint64_t seed1;               // wt_seed(seed)
+  uint64_t r0;                  // the first permutation of the batch
+  const int32_t* cols;          // per stratum, one behind the other: the columns of Z_s ...
+  const uint32_t* cthr;         // ... and their thresholds, in the same order
+  const uint32_t* soff;         // [S + 1] where stratum s starts in cols / cthr
+  const uint32_t* cases_in;     // [S]
+  uint32_t* att;                // [S][att_stride] accepted attempts of the batch's columns, kWeightedNone where the cap was met
+  uint32_t* first;              // one dword, 0xffffffff on entry: the smallest column with a stratum that met the cap
+  uint32_t cap;                 // max_attempts
+  // k_seq_weighted_write
+  const int32_t* stratum;       // [n] or NULL (one stratum)
+  const uint32_t* thr;          // [n] thresholds by column
+  uint32_t* masks;              // [W32p][stride]
+  int S, n, W32p;
+  int nb;                       // columns of the batch: searched (<= att_stride), written (<= stride)
+  int att_stride;               // columns of `att` per stratum
+  int stride;                   // columns of `masks` per row: a multiple of 64
+};
+hipError_t launch_seq_weighted_search(const SeqWeightedArgs& a, hipStream_t stream);
+hipError_t launch_seq_weighted_write(const SeqWeightedArgs& a, hipStream_t stream);
+
 // ---- carrier-overlap counts of caller-given sets (gcre_overlap.hip) ----
 constexpr int kOverlapTile = 64;    // pairs per edge of a block's tile
 constexpr int kOverlapChunk = 32;   // dwords of a row per staged chunk (128 bytes): rows are padded to a multiple of it

@@ -317,7 +317,7 @@ def score_paths(paths, genes: Sequence[str], data: np.ndarray, n_cases: int, n_c
                 device: int = 0, gwaspa_out: Optional[Dict[str, object]] = None, minp: bool = False,
                 competitive: int = 0, competitive_bins: int = 10, fixed: Optional[Sequence[str]] = None,
                 stability: int = 0, stability_cuts=None, sequential: int = 0, sequential_hits: int = 20,
-                stratified: bool = False, case_odds=None, family_inference: bool = False):
+                stratified: bool = False, case_odds=None, sequential_weighted: bool = False, family_inference: bool = False):
     """Permutation tests of paths and gene sets the caller names (gcre_score_sets on the device): what GWASPA cannot
     answer for a cascade outside its top K, or for a KEGG / Reactome list.  ``paths`` as ``parse_sets`` reads them;
     genes are looked up after ``preprocess_table(threshold)``, as GWASPA and ``decorated_table`` do (a symbol not found is
@@ -398,11 +398,23 @@ def score_paths(paths, genes: Sequence[str], data: np.ndarray, n_cases: int, n_c
     permutation p-value above is taken against labels redrawn with these odds, so a continuous covariate that shifts both
     the case fraction and the carrier frequency is in the null.  The adjustment is on the null, not on ``Scores``, and the
     p-values are only as good as the fitted model.  ``gwaspa_out`` must come from ``gwaspa`` with the same ``case_odds``
-    (ValueError otherwise); ``sequential`` > 0 is refused with it (that stage makes its own, uniform masks).  None, the
-    default: exactly the frame without it."""
+    (ValueError otherwise); ``sequential`` > 0 is refused with it (that stage makes its own, uniform masks) unless
+    ``sequential_weighted`` is set.  None, the default: exactly the frame without it.
+
+    ``sequential_weighted``: with ``case_odds`` and ``sequential`` > 0, the SEQUENTIAL_COLUMNS come from
+    ``weighted_sequential_tests(odds=case_odds, strata=strata, seed=seed)`` (gcre_score_sets_sequential_weighted; DESIGN.md
+    §3.24) on the call's own context: the permutations ``generate_weighted_permutations(seed, case_odds, strata)`` would
+    draw, made in batches and never kept.  The switch is explicit because of what it costs: each weighted permutation takes
+    about sqrt(2 pi V) attempts over the whole stratum (V the sum of p (1 - p) over its patients), where a uniform one
+    costs one hash per patient -- a limit of 10^6 permutations that is cheap without ``case_odds`` may not be with it.
+    Without ``case_odds``, or with ``sequential=0``, it is a ValueError.  False, the default: exactly the frame without it."""
     import pandas as pd
-    if case_odds is not None and int(sequential) > 0:
-        raise ValueError("case_odds: sequential p-values draw their own uniform masks; weighted draws are not built there")
+    if sequential_weighted and (case_odds is None or int(sequential) <= 0):
+        raise ValueError("sequential_weighted=True needs case_odds and sequential > 0: it draws the sequential permutations with "
+                         "these odds")
+    if case_odds is not None and int(sequential) > 0 and not sequential_weighted:
+        raise ValueError("case_odds: sequential p-values draw their own uniform masks; sequential_weighted=True draws them with "
+                         "these odds instead (each permutation then costs about sqrt(2 pi V) attempts over the whole stratum)")
     if gwaspa_out is not None and gwaspa_out.get("case_odds_digest") != _odds_digest(case_odds):
         raise ValueError("gwaspa_out was drawn under different case_odds: its TestScores are not the null of these masks")
     if int(stability) < 0:
@@ -461,7 +473,8 @@ def score_paths(paths, genes: Sequence[str], data: np.ndarray, n_cases: int, n_c
         cols.update(more_cols)
         names_out += list(more_cols)
     if int(sequential) > 0:
-        seq = _sequential_counts(rows, signs, data, n_cases, n_ctrls, method, int(sequential_hits), int(sequential), strata, seed, device)
+        seq = _sequential_counts(rows, signs, data, n_cases, n_ctrls, method, int(sequential_hits), int(sequential), strata, seed, device,
+                                 case_odds if sequential_weighted else None)
         cols.update(sequential_columns(seq, valid))
         names_out += SEQUENTIAL_COLUMNS
     if stratified:
@@ -491,9 +504,9 @@ def _stability_counts(rows, signs, data, n_cases, n_ctrls, method, draws, cuts, 
         ex.close()
 
 
-def _sequential_counts(rows, signs, data, n_cases, n_ctrls, method, hits, max_perms, strata, seed, device) -> np.ndarray:
-    """The SEQ_SCORE records of sequential_tests for ``score_paths``: on the rows the sets use, on a context of its own
-    without permutations."""
+def _sequential_counts(rows, signs, data, n_cases, n_ctrls, method, hits, max_perms, strata, seed, device, odds=None) -> np.ndarray:
+    """The SEQ_SCORE records of sequential_tests -- with ``odds`` of weighted_sequential_tests -- for ``score_paths``: on the
+    rows the sets use, on a context of its own without permutations."""
     from . import api
     used: Dict[int, int] = {}
     sets = [[-1 if r < 0 else used.setdefault(r, len(used)) for r in rs] for rs in rows]
@@ -502,6 +515,8 @@ def _sequential_counts(rows, signs, data, n_cases, n_ctrls, method, hits, max_pe
     ex = api.JoinExec(method, n_cases, n_ctrls, 0, device=device)
     try:
         ex.set_value_table(api.values_table(n_cases, n_ctrls))
+        if odds is not None:
+            return ex.weighted_sequential_tests(sets, sub, signs, odds=odds, hits=hits, max_perms=max_perms, seed=seed, strata=strata)[1]
         return ex.sequential_tests(sets, sub, signs, hits=hits, max_perms=max_perms, seed=seed, strata=strata)[1]
     finally:
         ex.close()
@@ -1192,6 +1207,31 @@ def sequential_reference(null, obs, valid, hits: int, max_perms: int) -> Dict[st
         else:
             n_hit[s], n_perm[s] = len(at), P
     return {"n_hit": n_hit, "n_perm": n_perm, "stopped": stopped}
+
+
+def weighted_sequential_reference(null, obs, valid, hits: int, max_perms: int, attempts) -> Dict[str, object]:
+    """The definition of gcre_score_sets_sequential_weighted (csrc/gcre_seq_weighted.h) taken literally.
+    ``null`` / ``obs`` / ``valid`` as ``sequential_reference`` takes them, the null scores under the masks of
+    ``weighted_masks``; ``attempts`` [>= max_perms][S]: its accepted attempts under the call's ``max_attempts``.  R
+    (``first_left_over``) is the first permutation below ``max_perms`` with a WEIGHTED_NONE entry, or None.
+    ``sequential_reference`` is applied to permutations 0 .. min(max_perms, R) - 1.  Without R: its dict as it is.  With R
+    and every valid set stopped (``n_perm`` <= R): the same, complete.  Otherwise ``refused`` is True -- a valid set had
+    not stopped in front of R; one with a NaN score never does -- and the counts are what the truncated range gave
+    (``n_active`` says how many sets were still active).  Returns the dict plus ``first_left_over``, ``refused`` and
+    ``n_active``."""
+    P = int(max_perms)
+    att = np.asarray(attempts)
+    att = att.reshape(len(att), -1)
+    if len(att) < P:
+        raise ValueError(f"weighted_sequential_reference: {len(att)} rows of attempts for max_perms = {P}")
+    bad = np.flatnonzero((att[:P] == WEIGHTED_NONE).any(axis=1))
+    R = int(bad[0]) if len(bad) else None
+    out: Dict[str, object] = dict(sequential_reference(null, obs, valid, hits, P if R is None else R))
+    active = (np.asarray(valid).reshape(-1)[:len(out["stopped"])] != 0) & (out["stopped"] == 0)
+    out["first_left_over"] = R
+    out["n_active"] = int(active.sum()) if R is not None else 0
+    out["refused"] = R is not None and bool(active.any())
+    return out
 
 
 def sequential_columns(seq, valid) -> Dict[str, np.ndarray]:

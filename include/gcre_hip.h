@@ -829,8 +829,9 @@ int64_t gcre_strata_launches(const gcre_ctx* ctx);
  * out of range, max_attempts < 1; GCRE_ERR_RANGE -- a stratum whose estimate sqrt(2 pi V_s) alone exceeds max_attempts.
  * After the search launch: GCRE_ERR_RANGE saying how many permutations were left over without an accepted attempt below
  * max_attempts; no mask bit was written, and the context's masks, whether it has any, and its window are what they were.
- * Not built: weighted draws in the sequential and subsample set scores (they make their own masks), weighted urns for
- * decorated p-values, an exact sampler without rejection, odds of +infinity (forced cases). */
+ * Weighted draws in the sequential set scores: gcre_score_sets_sequential_weighted, below.  Not built: weighted draws in the
+ * subsample set scores (they make their own masks), weighted urns for decorated p-values, an exact sampler without rejection,
+ * odds of +infinity (forced cases). */
 int gcre_generate_weighted_masks(gcre_ctx* ctx, uint64_t seed, const double* odds, const int32_t* stratum, int32_t n_strata,
                                  int64_t max_attempts, uint32_t* attempts_out /* optional [iterations][n_strata] */);
 /* The thresholds and sqrt(2 pi V_s) alone; host only, no device is touched.  thr_out [n]; expected_attempts_out optional
@@ -842,6 +843,33 @@ int gcre_weighted_thresholds(int32_t n, int32_t n_cases, const double* odds, con
  * that met the cap, none for one refused up front (no other launch counter counts them, nor the reverse); -1 for a NULL
  * context. */
 int64_t gcre_weighted_launches(const gcre_ctx* ctx);
+
+/* Weighted sequential p-values: gcre_score_sets_sequential with the covariate-adjusted masks of
+ * gcre_generate_weighted_masks, drawn in batches that are never resident as a whole.  A p-value below 1 / iterations under a
+ * null that holds a continuous covariate; `out`, *n_out, `seq_out`, h, max_perms, the batches and their environment variables
+ * as gcre_score_sets_sequential; odds, stratum, n_strata, max_attempts as gcre_generate_weighted_masks.  A context with
+ * iterations == 0 will do.
+ * Definition.  mask_r, 0 <= r < max_perms (r is 64-bit), is mask r of gcre_generate_weighted_masks(seed, odds, stratum,
+ * n_strata, max_attempts), bit for bit: the same thresholds, a*(r, s) the smallest accepted attempt below the cap.  Let R be the
+ * smallest r < max_perms for which some stratum has no accepted attempt below max_attempts (none: infinity).  The rule of
+ * gcre_score_sets_sequential is applied to permutations 0 .. min(max_perms, R) - 1.  R >= max_perms: the usual answer.  R <
+ * max_perms and every valid set has stopped with n_perm <= R: the answer is complete and returned.  Otherwise -- a set with a
+ * NaN score never stops, so it is always among these -- the call is refused with GCRE_ERR_RANGE and a message that names R, the
+ * stratum, the cap and how many sets were still active; `out` then holds gcre_score_sets' records and seq_out its defaults
+ * (zeros, -1 for an invalid set).  This depends on the inputs alone: not on batch size, schedule or the order of the active
+ * list.  No mask at or beyond R is drawn or scored.
+ * A batch takes its masks and one dword per stratum and permutation (the accepted attempts) under GCRE_SEQ_MAX_MB.  Each
+ * weighted permutation costs about sqrt(2 pi V_s) attempts over the whole stratum, where a uniform one costs one hash per
+ * patient.
+ * Errors, nothing launched and no output array written: everything gcre_score_sets, gcre_score_sets_sequential (h, max_perms,
+ * seq_out) and gcre_generate_weighted_masks (odds, strata, max_attempts, the estimate above the cap) refuse up front, the
+ * messages opening with score_sets_sequential_weighted.
+ * gcre_sequential_launches counts its kernels -- k_seq_weighted_search, k_seq_weighted_write, k_seq_null, k_seq_retire: four
+ * per batch; for a batch cut at R the search alone, or all four when permutations remain in front of R.
+ * gcre_weighted_launches does not move.  Not built: family-wise versions, weighted draws in the subsample scores. */
+int gcre_score_sets_sequential_weighted(gcre_ctx* ctx, const gcre_set_input* in, uint64_t seed, const double* odds,
+                                        const int32_t* stratum, int n_strata, int64_t max_attempts, int64_t h, int64_t max_perms,
+                                        gcre_set_score* out, int64_t cap, int64_t* n_out, gcre_seq_score* seq_out /* [n_sets] */);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Carrier overlaps of caller-given sets: which sets are carried by the same patients.  No reference
