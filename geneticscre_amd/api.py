@@ -161,6 +161,7 @@ EXPORTS = [
     "gcre_score_sets_strata", "gcre_strata_launches",
     "gcre_generate_weighted_masks", "gcre_weighted_thresholds", "gcre_weighted_launches",
     "gcre_score_sets_sequential_weighted",
+    "gcre_score_sets_prefix_sequential", "gcre_score_sets_dose_sequential", "gcre_seq_prefix_launches",
     "gcre_set_overlap", "gcre_overlap_launches",
     "gcre_clump_sets", "gcre_clump_launches",
     "gcre_set_patient_counts", "gcre_patient_launches",
@@ -324,6 +325,13 @@ _FEATURES = {
                             "weighted sequential p-values (gcre_score_sets_sequential_weighted)", {
         "gcre_score_sets_sequential_weighted": (_I, [_V, ctypes.POINTER(gcre_set_input), ctypes.c_uint64, _P, _P, _I, _I64, _I64, _I64,
                                                      _P, _I64, ctypes.POINTER(_I64), _P])}),
+    "seq_prefix": ("sequential", ["gcre_score_sets_prefix_sequential", "gcre_score_sets_dose_sequential", "gcre_seq_prefix_launches"],
+                   "sequential p-values of the adaptive set tests (gcre_score_sets_prefix_sequential)", {
+        "gcre_score_sets_prefix_sequential": (_I, [_V, ctypes.POINTER(gcre_set_input), _P, ctypes.c_uint64, _P, _P, _I, _I64, _I64, _I64,
+                                                   _P, _I64, ctypes.POINTER(_I64), _P, _P, _P]),
+        "gcre_score_sets_dose_sequential": (_I, [_V, ctypes.POINTER(gcre_set_input), _P, _I32, ctypes.c_uint64, _P, _P, _I, _I64, _I64,
+                                                 _I64, _P, _I64, ctypes.POINTER(_I64), _P, _P, _P]),
+        "gcre_seq_prefix_launches": (_I64, [_V])}),
     "overlap": (None, ["gcre_set_overlap"], "carrier overlaps (gcre_set_overlap)", {
         "gcre_set_overlap": (_I, [_V, ctypes.POINTER(gcre_set_input), _P, _I64, _P, _I64, _P, _P]),
         "gcre_overlap_launches": (_I64, [_V])}),
@@ -1388,6 +1396,92 @@ class JoinExec:
                                                                  S if st is not None else 0, int(max_attempts), int(hits),
                                                                  int(max_perms), _ptr(out), len(out), ctypes.byref(n_out), _ptr(seq)))
         return out[:n_out.value], seq[:n_out.value]
+
+    def _sequential_draw(self, strata, odds):
+        """(odds or None, strata ids or None, n_strata) of the two adaptive sequential entries: uniform permutations read
+        ``strata`` as ``sequential_tests`` does, weighted ones ``odds`` / ``strata`` as ``weighted_sequential_tests``."""
+        n = self.num_cases + self.num_ctrls
+        if odds is not None:
+            w, st, S, _ = _weighted_args(odds, strata, n)
+            return w, st, S if st is not None else 0
+        st = None if strata is None else np.ascontiguousarray(strata, dtype=np.int32).reshape(-1)
+        if st is not None and len(st) != n:
+            raise ValueError(f"strata: one id per patient ({n}), not {len(st)}")
+        return None, st, 0 if st is None else int(st.max()) + 1
+
+    def prefix_sequential_tests(self, sets, rows, signs=None, cuts=None, hits: int = 20, max_perms: int = 10**6, seed: int = 0,
+                                strata=None, odds=None, max_attempts: int = 1 << 20, steps: bool = False):
+        """Sequential p-values of the variable-threshold test (gcre_score_sets_prefix_sequential): the
+        statistic of ``prefix_tests`` -- the best score over nested prefixes of every set's member list -- with the
+        permutations of ``sequential_tests`` drawn in batches as they are needed: every set is permuted until the maximum
+        over its steps has reached its best observed score ``hits`` times, or ``max_perms`` permutations are used.  No
+        resident mask is read: a context with ``iters`` = 0 will do.  ``sets`` / ``rows`` / ``signs`` / ``cuts`` / ``steps``
+        as ``prefix_tests`` takes them; ``seed`` / ``strata`` as ``sequential_tests``; with ``odds`` the masks, ``strata``,
+        ``max_attempts`` and the refusal (GcreError, GCRE_ERR_RANGE) are ``weighted_sequential_tests``'.  Returns ``(records,
+        prefix, seq)``: the SET_SCORE records of ``score_sets``, the PREFIX_SCORE records of ``prefix_tests`` with ``n_ge`` 0
+        (-1 for an NA member), and one SEQ_SCORE record per set as ``sequential_tests`` gives them.  ``n_hit / n_perm`` is a
+        nominal p-value of the maximum, one set at a time.  With ``steps`` also float64 [members].
+        ``report.adaptive_sequential_reference`` states the rule in numpy.  A misshapen ``cuts`` / ``odds`` / ``strata`` is a
+        ValueError; other errors raise GcreError."""
+        S, off, members, sg = _set_lists(sets, signs)
+        ct = None
+        if cuts is not None:
+            if isinstance(sets, tuple) and len(sets) == 2 and isinstance(sets[0], np.ndarray):
+                ct = np.asarray(cuts).reshape(-1)
+                matching = len(ct) == len(members)
+            else:
+                matching = len(cuts) == S and all(len(x) == L for x, L in zip(cuts, np.diff(off)))
+                ct = np.concatenate([np.asarray(x).reshape(-1) for x in cuts]) if matching and S else np.zeros(0)
+            if not matching:
+                raise ValueError("cuts: one flag per member of every set")
+            ct = np.ascontiguousarray(ct != 0, dtype=np.uint8)
+        w, st, n_strata = self._sequential_draw(strata, odds)
+        lib = _feature_lib("seq_prefix")
+        inp, keep = _set_input((off, members), rows, sg, self.num_cases + self.num_ctrls)
+        out = np.zeros(max(S, 1), dtype=SET_SCORE)
+        px = np.zeros(max(S, 1), dtype=PREFIX_SCORE)
+        seq = np.zeros(max(S, 1), dtype=SEQ_SCORE)
+        stp = np.full(len(members), np.nan, dtype=np.float64) if steps else None
+        n_out = ctypes.c_int64(0)
+        self._check_gcre(lib.gcre_score_sets_prefix_sequential(
+            self._h, ctypes.byref(inp), _ptr(ct) if ct is not None and ct.size else None, int(seed) & (2**64 - 1), _ptr(w), _ptr(st),
+            n_strata, int(max_attempts), int(hits), int(max_perms), _ptr(out), len(out), ctypes.byref(n_out), _ptr(px), _ptr(seq),
+            _ptr(stp) if steps and stp.size else None))
+        n = n_out.value
+        return (out[:n], px[:n], seq[:n]) + ((stp,) if steps else ())
+
+    def dose_sequential_tests(self, sets, rows, signs=None, levels=(1, 2), hits: int = 20, max_perms: int = 10**6, seed: int = 0,
+                              strata=None, odds=None, max_attempts: int = 1 << 20, level_scores: bool = False):
+        """Sequential p-values of the multi-hit test (gcre_score_sets_dose_sequential): the statistic of
+        ``dose_tests`` -- the best score over the level rows "carries at least m of the set's members" -- with the
+        permutations of ``sequential_tests`` drawn in batches as they are needed, every set until the maximum over its
+        levels has reached its best observed score ``hits`` times.  ``sets`` / ``rows`` / ``signs`` / ``levels`` /
+        ``level_scores`` as ``dose_tests`` takes them; everything else as ``prefix_sequential_tests``.  Returns ``(records,
+        dose, seq)``: the DOSE_SCORE records with ``n_ge`` 0 (-1 for an NA member).  ``n_hit / n_perm`` is a nominal p-value
+        of the maximum, one set at a time.  With ``level_scores`` also float64 [sets][levels].  Bad ``levels`` / ``odds`` /
+        ``strata`` raise ValueError, errors of the library GcreError."""
+        S, off, members, sg = _set_lists(sets, signs)
+        lv = _dose_levels(levels)
+        w, st, n_strata = self._sequential_draw(strata, odds)
+        lib = _feature_lib("seq_prefix")
+        inp, keep = _set_input((off, members), rows, sg, self.num_cases + self.num_ctrls)
+        L = len(lv)
+        out = np.zeros(max(S, 1), dtype=SET_SCORE)
+        ds = np.zeros(max(S, 1), dtype=DOSE_SCORE)
+        seq = np.zeros(max(S, 1), dtype=SEQ_SCORE)
+        lsc = np.full((S, L), np.nan, dtype=np.float64) if level_scores else None
+        n_out = ctypes.c_int64(0)
+        self._check_gcre(lib.gcre_score_sets_dose_sequential(
+            self._h, ctypes.byref(inp), _ptr(lv), L, int(seed) & (2**64 - 1), _ptr(w), _ptr(st), n_strata, int(max_attempts), int(hits),
+            int(max_perms), _ptr(out), len(out), ctypes.byref(n_out), _ptr(ds), _ptr(seq),
+            _ptr(lsc) if level_scores and lsc.size else None))
+        n = n_out.value
+        return (out[:n], ds[:n], seq[:n]) + ((lsc,) if level_scores else ())
+
+    def seq_prefix_launches(self) -> int:
+        """Kernels ``prefix_sequential_tests`` and ``dose_sequential_tests`` launched for their own stage on this context so
+        far: three per slab, then three per batch (four weighted)."""
+        return int(_feature_lib("seq_prefix").gcre_seq_prefix_launches(self._h))
 
     def strata_tests(self, sets, rows, signs=None, strata=None, tables=None, family: bool = False, null: bool = False,
                      terms: bool = False):

@@ -1,6 +1,6 @@
 // gcre_count_tile.h -- device side, shared by the kernels that count one row against every mask of a permutation tile
-// (k_set_null, k_family_null, k_stepdown_null, k_prefix_null, k_seq_null, k_subsample_null, k_burden_null, k_strata_null,
-// k_strata_check):
+// (k_set_null, k_family_null, k_stepdown_null, k_prefix_null, k_seq_null, k_seq_prefix_null, k_subsample_null, k_burden_null,
+// k_strata_null, k_strata_check):
 //   * the tile's shape and the small device helpers every such kernel needs (also used by kernels without the loop);
 //   * MaskStream  the block's mask tile, double-buffered through LDS in chunks of kCtWC dwords;
 //   * count_tile  acc[h][t][j] = sum over the row's dwords of popcount(row & mask), for a wave's TPW rows;

@@ -288,6 +288,7 @@ struct gcre_ctx {
   int64_t subsample_launches = 0;    // kernels gcre_score_sets_subsample launched for its own stage (gcre_subsample_launches)
   int64_t dose_launches = 0;         // kernels gcre_score_sets_dose launched for its own stage (gcre_dose_launches)
   int64_t sequential_launches = 0;   // kernels gcre_score_sets_sequential launched for its own stage (gcre_sequential_launches)
+  int64_t seq_prefix_launches = 0;   // kernels gcre_score_sets_prefix_sequential / _dose_sequential launched for their own stage (gcre_seq_prefix_launches)
   int64_t strata_launches = 0;       // kernels gcre_score_sets_strata launched for its own stage (gcre_strata_launches)
   int64_t weighted_launches = 0;     // k_weighted_search / k_weighted_write launches of this context (gcre_weighted_launches)
 

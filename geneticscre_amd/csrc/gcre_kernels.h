@@ -803,6 +803,29 @@ struct DoseArgs {
 };
 hipError_t launch_dose_rows(const DoseArgs& a, int method, hipStream_t stream);
 
+// ---- sequential p-values of the two adaptive set tests (gcre_seq_prefix.hip) ----
+// One batch of permutations (SeqNullArgs' masks and bit rows) against the step rows of one PrefixArgs slab.  Slot i of the
+// active list is slot active[i] of the slab, its step rows [row0[e], row0[e + 1]).  Block (kt, g) stays on permutation tile
+// kt and walks the groups g, g + pgroups, ... of four consecutive slots of the active list, one slot per wave.
+struct SeqPrefixArgs {
+  const uint32_t* rows;         // [nrows][M][W32p] the slab's step rows
+  const uint32_t* masks;        // [W32p][stride] the batch's masks
+  const uint32_t* tot;          // [nrows][M] carriers per half
+  const uint32_t* thr;          // [nslots] f32 bit pattern of every slot's best observed score (k_prefix_pick)
+  const int64_t* row0;          // [nslots + 1] first step row of every slot (read-only: scalar loads)
+  const float* t32;             // M=1: sanitised f32 null table, diagonal-major
+  const double* d64;            // M=2: f64 vtmax, diagonal-major
+  const double* d64n;           // M=2: the table the (-) half reads
+  const uint32_t* active;       // [nactive] slots of the slab (read-only: scalar loads), in any order
+  unsigned long long* bits;     // [nactive][stride / 64]: bit i of slot a = the maximum of permutation r0 + i reached the score
+  int64_t nactive;
+  int64_t ngroups;              // ceil(nactive / 4)
+  int W32p, stride, K;          // K: permutations of the batch; the columns K .. nkt * kSetPermTile - 1 write 0
+  int nkt;                      // permutation tiles of kSetPermTile
+  int pgroups;                  // blocks per permutation tile
+};
+hipError_t launch_seq_prefix_null(const SeqPrefixArgs& a, int method, hipStream_t stream);
+
 // ---- stratified set scores: per-stratum counts and tables, summed (gcre_strata.hip) ----
 // k_strata_masks turns the stratum ids into S indicator rows; the check launch counts every resident mask against them.
 // Then one slab of whole sets: slot e of the slab has the S consecutive rows [e S, e S + S), row e S + s = "union & Z_s" in

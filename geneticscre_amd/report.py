@@ -1456,6 +1456,30 @@ def prefix_reference(step_obs, step_null, step_set, n_sets: int, valid) -> Dict[
     return out
 
 
+def adaptive_sequential_reference(step_obs, step_null, step_set, n_sets: int, valid, hits: int, max_perms: int,
+                                  attempts=None) -> Dict[str, object]:
+    """gcre_score_sets_prefix_sequential and gcre_score_sets_dose_sequential by their definition, in numpy, no device call
+    (DESIGN.md §3.25): ``prefix_reference``'s ``score`` and ``null_max`` fed to ``sequential_reference``.  ``step_obs`` /
+    ``step_null`` / ``step_set`` / ``valid`` as ``prefix_reference`` takes them -- the steps of ``prefix_sets`` or the level
+    sets of ``dose_sets`` -- with ``step_null`` [steps][>= max_perms] under permutations 0, 1, ... in order.  A NaN step is
+    skipped for the pick but still takes part in the null maximum (folded: 0); a set whose steps are all NaN has a NaN
+    score and never counts.  With ``attempts`` [>= max_perms][S] (the accepted attempts of ``weighted_masks``) the rule is
+    ``weighted_sequential_reference``'s, and the dict also holds ``first_left_over``, ``refused`` and ``n_active``.  Returns
+    ``n_hit`` / ``n_perm`` / ``stopped`` [n_sets] plus ``score`` and ``best_step`` of ``prefix_reference``.  It is a nominal
+    p-value of the maximum, one set at a time."""
+    ref = prefix_reference(step_obs, step_null, step_set, n_sets, valid)
+    null_max = ref["null_max"]
+    if null_max.shape[1] == 0:
+        null_max = np.zeros((int(n_sets), 0), np.float32)
+    if attempts is None:
+        out: Dict[str, object] = dict(sequential_reference(null_max, ref["score"], valid, hits, max_perms))
+    else:
+        out = weighted_sequential_reference(null_max, ref["score"], valid, hits, max_perms, attempts)
+    out["score"] = ref["score"]
+    out["best_step"] = ref["best_step"]
+    return out
+
+
 def threshold_order(set_genes, data):
     """The order and the cuts of the variable-threshold test (Price et al. 2010) for one set: ``(order, cuts)``.  ``set_genes``
     are rows of the 0/1 matrix ``data`` (-1 = NA); ``order`` int64 are positions of ``set_genes`` by ascending carrier total
@@ -1478,6 +1502,16 @@ def threshold_order(set_genes, data):
 def variable_threshold_test(sets, genes: Sequence[str], data: np.ndarray, n_cases: int, n_ctrls: int, signed: bool = False,
                             names=None, threshold: float = 0.05, n_permutations: int = 100,
                             strata: Optional[Sequence[int]] = None, seed: int = 0, device: int = 0):
+    """``variable_threshold_sequential_test`` without the sequential columns: the frame this function always returned (its
+    docstring describes the test and the VARIABLE_THRESHOLD_COLUMNS)."""
+    return variable_threshold_sequential_test(sets, genes, data, n_cases, n_ctrls, signed=signed, names=names, threshold=threshold,
+                                              n_permutations=n_permutations, strata=strata, seed=seed, device=device, sequential=0)
+
+
+def variable_threshold_sequential_test(sets, genes: Sequence[str], data: np.ndarray, n_cases: int, n_ctrls: int,
+                                       signed: bool = False, names=None, threshold: float = 0.05, n_permutations: int = 100,
+                                       strata: Optional[Sequence[int]] = None, seed: int = 0, device: int = 0, sequential: int = 0,
+                                       sequential_hits: int = 20):
     """Variable-threshold test of gene sets the caller names (``JoinExec.prefix_tests``).  Every other set
     statistic scores a set's full union, so which genes count is decided by one carrier-frequency threshold chosen before
     the analysis; here a set's genes are ordered by carrier total (``threshold_order``), every prefix "all genes with at
@@ -1489,7 +1523,14 @@ def variable_threshold_test(sets, genes: Sequence[str], data: np.ndarray, n_case
     as ``score_paths`` gives them; ``BestGenes`` the size of the best prefix and ``BestThreshold`` the carrier total of its
     last gene; ``AdaptiveScores`` its score; ``AdaptivePvalues`` = n_ge / permutations, a self-contained permutation p-value
     of the maximum over the set's nested prefixes, one set at a time; ``AdaptiveFamilyPvalues`` single-step max-T of that
-    statistic over the call's sets.  NaN for a set with a gene not found, a NaN score and 0 permutations."""
+    statistic over the call's sets.  NaN for a set with a gene not found, a NaN score and 0 permutations.
+
+    ``sequential`` = max_perms > 0 appends the SEQUENTIAL_COLUMNS of ``sequential_columns`` for the adaptive statistic
+    (``JoinExec.prefix_sequential_tests``): every set is permuted until the maximum over its prefixes has
+    reached ``AdaptiveScores`` ``sequential_hits`` times, with the seed and strata of the resident masks, in batches that are
+    never resident, so ``sequential`` may be far above ``n_permutations``.  It is a nominal p-value of the maximum, one set
+    at a time.  0, the default, returns the frame as it always was.  Not built: ``case_odds`` here (the API call takes
+    ``odds``), a family-wise value of the sequential p-value."""
     import pandas as pd
     from . import api
     genes, data = preprocess_table(genes, data, threshold, n_cases, n_ctrls)
@@ -1514,6 +1555,10 @@ def variable_threshold_test(sets, genes: Sequence[str], data: np.ndarray, n_case
         if K > 0:
             ex.generate_permutations(seed, strata)
         rec, px, fam = ex.prefix_tests(idx, sub, osigns, cuts=cuts, family=True)
+        seq = None
+        if int(sequential) > 0:
+            seq = ex.prefix_sequential_tests(idx, sub, osigns, cuts=cuts, hits=sequential_hits, max_perms=int(sequential), seed=seed,
+                                             strata=strata)[2]
     finally:
         ex.close()
     nan = np.full(S, np.nan)
@@ -1537,6 +1582,9 @@ def variable_threshold_test(sets, genes: Sequence[str], data: np.ndarray, n_case
         "AdaptivePvalues": adaptive_p,
         "AdaptiveFamilyPvalues": family_p,
     }
+    if seq is not None:
+        cols.update(sequential_columns(seq, rec["valid"]))
+        return pd.DataFrame(cols, columns=VARIABLE_THRESHOLD_COLUMNS + SEQUENTIAL_COLUMNS)
     return pd.DataFrame(cols, columns=VARIABLE_THRESHOLD_COLUMNS)
 
 
@@ -1592,6 +1640,16 @@ def pair_sets(rows):
 def multi_hit_test(sets, genes: Sequence[str], data: np.ndarray, n_cases: int, n_ctrls: int, signed: bool = False,
                    names=None, levels=(1, 2, 3), threshold: float = 0.05, n_permutations: int = 100,
                    strata: Optional[Sequence[int]] = None, seed: int = 0, device: int = 0):
+    """``multi_hit_sequential_test`` without the sequential columns: the frame this function always returned (its docstring
+    describes the test and the MULTI_HIT_COLUMNS)."""
+    return multi_hit_sequential_test(sets, genes, data, n_cases, n_ctrls, signed=signed, names=names, levels=levels, threshold=threshold,
+                                     n_permutations=n_permutations, strata=strata, seed=seed, device=device, sequential=0)
+
+
+def multi_hit_sequential_test(sets, genes: Sequence[str], data: np.ndarray, n_cases: int, n_ctrls: int, signed: bool = False,
+                              names=None, levels=(1, 2, 3), threshold: float = 0.05, n_permutations: int = 100,
+                              strata: Optional[Sequence[int]] = None, seed: int = 0, device: int = 0, sequential: int = 0,
+                              sequential_hits: int = 20):
     """Multi-hit test of gene sets the caller names (``JoinExec.dose_tests``).  Every other set statistic
     scores a set's union, where a patient with a variant in one gene of a pathway and a patient with variants in four count
     the same; here, per level m of ``levels``, the patients who carry at least m of the set's genes are scored, the best
@@ -1604,7 +1662,13 @@ def multi_hit_test(sets, genes: Sequence[str], data: np.ndarray, n_cases: int, n
     union, as ``score_paths`` gives them; ``BestLevel`` the best level and ``BestCases`` / ``BestControls`` the cases and
     controls of its (+) row; ``MultiHitScores`` its score; ``MultiHitPvalues`` = n_ge / permutations, a self-contained
     permutation p-value of the maximum over the levels, one set at a time; ``MultiHitFamilyPvalues`` single-step max-T of
-    that statistic over the call's sets.  NaN for a set with a gene not found, a NaN score and 0 permutations."""
+    that statistic over the call's sets.  NaN for a set with a gene not found, a NaN score and 0 permutations.
+
+    ``sequential`` = max_perms > 0 appends the SEQUENTIAL_COLUMNS of ``sequential_columns`` for the multi-hit statistic
+    (``JoinExec.dose_sequential_tests``): every set is permuted until the maximum over its levels has reached
+    ``MultiHitScores`` ``sequential_hits`` times, with the seed and strata of the resident masks, in batches that are never
+    resident.  It is a nominal p-value of the maximum, one set at a time.  0, the default, returns the frame as it always
+    was.  Not built: ``case_odds`` here (the API call takes ``odds``), a family-wise value of the sequential p-value."""
     import pandas as pd
     from . import api
     genes, data = preprocess_table(genes, data, threshold, n_cases, n_ctrls)
@@ -1629,6 +1693,10 @@ def multi_hit_test(sets, genes: Sequence[str], data: np.ndarray, n_cases: int, n
         if K > 0:
             ex.generate_permutations(seed, strata)
         rec, ds, fam = ex.dose_tests(idx, sub, osigns, levels=lv, family=True)
+        seq = None
+        if int(sequential) > 0:
+            seq = ex.dose_sequential_tests(idx, sub, osigns, levels=lv, hits=sequential_hits, max_perms=int(sequential), seed=seed,
+                                           strata=strata)[2]
     finally:
         ex.close()
     nan = np.full(S, np.nan)
@@ -1649,6 +1717,9 @@ def multi_hit_test(sets, genes: Sequence[str], data: np.ndarray, n_cases: int, n
         "MultiHitPvalues": own_p,
         "MultiHitFamilyPvalues": family_p,
     }
+    if seq is not None:
+        cols.update(sequential_columns(seq, rec["valid"]))
+        return pd.DataFrame(cols, columns=MULTI_HIT_COLUMNS + SEQUENTIAL_COLUMNS)
     return pd.DataFrame(cols, columns=MULTI_HIT_COLUMNS)
 
 

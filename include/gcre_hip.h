@@ -733,8 +733,8 @@ int64_t gcre_dose_launches(const gcre_ctx* ctx);
  * n_hit / n_perm is a nominal p-value, one set at a time, with a relative error of about 1 / sqrt(h) wherever it is above
  * h / max_perms; for the sets that did not stop, (n_hit + 1) / (n_perm + 1) is the usual conservative estimate.  The sets stop
  * at different permutations, so there is no common null matrix.  Not built: family-wise versions (max-T, step-down, min-P) of
- * it, sequential stopping of the prefix / dose / competitive statistics and of the joins, an early stop for sets that are
- * clearly significant. */
+ * it, sequential stopping of the competitive statistics and of the joins (the prefix and dose statistics:
+ * gcre_score_sets_prefix_sequential, below), an early stop for sets that are clearly significant. */
 typedef struct {
   int64_t n_hit;       /* exceedances counted: h when stopped; -1 for an invalid set */
   int64_t n_perm;      /* permutations used: the position of the h-th exceedance, or max_perms; -1 for an invalid set */
@@ -870,6 +870,42 @@ int64_t gcre_weighted_launches(const gcre_ctx* ctx);
 int gcre_score_sets_sequential_weighted(gcre_ctx* ctx, const gcre_set_input* in, uint64_t seed, const double* odds,
                                         const int32_t* stratum, int n_strata, int64_t max_attempts, int64_t h, int64_t max_perms,
                                         gcre_set_score* out, int64_t cap, int64_t* n_out, gcre_seq_score* seq_out /* [n_sets] */);
+
+/* Sequential p-values of the two adaptive set tests: the variable-threshold test (gcre_score_sets_prefix)
+ * and the multi-hit test (gcre_score_sets_dose) with permutations drawn in batches as they are needed, every set until the
+ * maximum over its steps (levels) has reached its best observed score h times.  No resident mask is read: a context with
+ * iterations == 0 will do, and max_perms may be far above what a context holds.
+ * `cut` / `levels`, `px_out` / `dose_out`, `step_scores` / `level_scores` as gcre_score_sets_prefix / gcre_score_sets_dose take
+ * and fill them, except n_ge: 0 for a valid set, -1 for an invalid one.  seed, stratum, n_strata, h, max_perms, seq_out and the
+ * batches as gcre_score_sets_sequential.  odds NULL: its uniform masks (max_attempts is not read).  odds given: the masks,
+ * the left-over permutation R and the refusal of gcre_score_sets_sequential_weighted.
+ * Definition.  With T_s(mask) = max over the steps k of set s of the f32 null score of step row k (a NaN step of the table still
+ * takes part, folded as 0), and score_s the best observed step score (NaN steps skipped), e_s[r] = ((double)T_s(mask_r) >=
+ * score_s); then the rule of gcre_score_sets_sequential.  A set whose steps are all NaN has a NaN score: uniform, it keeps
+ * zeros; weighted, it never stops and forces the refusal where there is an R.
+ * The sets are walked in the slabs of gcre_score_sets_prefix (GCRE_PREFIX_MAX_MB, GCRE_PREFIX_SLAB_SETS); every slab runs the
+ * whole sequential loop from permutation 0 and draws the masks again -- they are a function of (seed, r), so no value depends
+ * on the slabs, but a second slab pays for the draw a second time.  Weighted: every slab is run, the sets still active at R are
+ * summed over the slabs, and the call is refused with GCRE_ERR_RANGE if that sum is positive; seq_out then keeps its defaults.
+ * max_perms == 0: nothing of this stage is launched; px_out / dose_out keep a NaN score, seq_out zeros.
+ * Errors, nothing launched and no output array written: everything gcre_score_sets, gcre_score_sets_prefix / _dose (without a
+ * null_max matrix), gcre_score_sets_sequential and, with odds, gcre_generate_weighted_masks refuse up front.
+ * n_hit / n_perm is a nominal p-value of the maximum, one set at a time.  Not built: a family-wise value of it, a group order
+ * re-sorted after retirement, an early stop for sets that are clearly significant.
+ * gcre_seq_prefix_launches: the kernels of the two entries on the context since gcre_create -- per slab three (rows, observed
+ * scores, pick), then three per batch (four weighted; the search alone for a batch with nothing in front of R); no other
+ * launch counter counts them, nor the reverse; -1 for a NULL context. */
+int gcre_score_sets_prefix_sequential(gcre_ctx* ctx, const gcre_set_input* in, const uint8_t* cut /* [members], optional */,
+                                      uint64_t seed, const double* odds /* NULL: uniform */, const int32_t* stratum, int n_strata,
+                                      int64_t max_attempts, int64_t h, int64_t max_perms, gcre_set_score* out, int64_t cap,
+                                      int64_t* n_out, gcre_prefix_score* px_out /* [n_sets] */, gcre_seq_score* seq_out /* [n_sets] */,
+                                      double* step_scores /* [members], optional */);
+int gcre_score_sets_dose_sequential(gcre_ctx* ctx, const gcre_set_input* in, const int32_t* levels, int32_t n_levels, uint64_t seed,
+                                    const double* odds /* NULL: uniform */, const int32_t* stratum, int n_strata,
+                                    int64_t max_attempts, int64_t h, int64_t max_perms, gcre_set_score* out, int64_t cap,
+                                    int64_t* n_out, gcre_dose_score* dose_out /* [n_sets] */, gcre_seq_score* seq_out /* [n_sets] */,
+                                    double* level_scores /* [n_sets][n_levels], optional */);
+int64_t gcre_seq_prefix_launches(const gcre_ctx* ctx);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Carrier overlaps of caller-given sets: which sets are carried by the same patients.  No reference
