@@ -174,6 +174,7 @@ EXPORTS = [
     "gcre_exceed_stepdown", "gcre_stepdown_launches",
     "gcre_hits_create", "gcre_join_set_hits", "gcre_process_paths_set_hits", "gcre_hits_count", "gcre_hits_read",
     "gcre_hits_reset", "gcre_hits_free", "gcre_hits_launches",
+    "gcre_test_range_union", "gcre_test_expand",
 ]
 
 
@@ -261,6 +262,9 @@ def load_library():
     lib.gcre_mix64.restype = ctypes.c_uint64
     lib.gcre_mix64.argtypes = [ctypes.c_uint64]
     lib.gcre_get_perm_mask.argtypes = [V, I, P]
+    if hasattr(lib, "gcre_test_expand"):   # (a GCRE_LIB variant built from an older commit has neither)
+        lib.gcre_test_range_union.argtypes = [V, P, I64, P, I64, P, P, P, I64, I, I, I, P, P, P]
+        lib.gcre_test_expand.argtypes = [V, P, P, I64, P, I64, I, I, I64, I64, P, P]
     lib.gcre_uids_set_reduced.argtypes = [V, V, P, I64]
     lib.gcre_set_perm_window.argtypes = [V, I, I]
     lib.gcre_plan_perm_window.argtypes = [V, P, I]
@@ -1707,6 +1711,35 @@ class JoinExec:
         out = np.zeros(self.width_ul, dtype=np.uint64)
         self._check(self._lib.gcre_get_perm_mask(self._h, int(r), _ptr(out)))
         return out
+
+    def test_range_union(self, p1, pz, zindex, loc, cnt, wp: int, method: int):
+        """Tests: the range check of a hinted join (k_range_union) on given rows.  p1[n1][S], pz[nz][S] uint64 with
+        S = method * wp; zindex[n1] (bit 31 = halves swapped); ranges loc[r] .. loc[r] + cnt[r] - 1.
+        Returns (U[n_ranges][S], bad, rows per piece)."""
+        p1 = np.ascontiguousarray(p1, dtype=np.uint64)
+        pz = np.ascontiguousarray(pz, dtype=np.uint64)
+        zindex = np.ascontiguousarray(zindex, dtype=np.int32)
+        loc = np.ascontiguousarray(loc, dtype=np.int64)
+        cnt = np.ascontiguousarray(cnt, dtype=np.int32)
+        S = method * wp
+        assert p1.shape[1:] == (S,) and pz.shape[1:] == (S,) and len(zindex) == len(p1) and len(loc) == len(cnt)
+        u = np.zeros((len(loc), S), dtype=np.uint64)
+        bad = np.zeros(1, dtype=np.uint32)
+        piece = np.zeros(1, dtype=np.int32)
+        self._check(self._lib.gcre_test_range_union(self._h, _ptr(p1), len(p1), _ptr(pz), len(pz), _ptr(zindex), _ptr(loc), _ptr(cnt),
+                                                    len(loc), S, wp, method, _ptr(u), _ptr(bad), _ptr(piece)))
+        return u, int(bad[0]), int(piece[0])
+
+    def test_expand(self, path_idx, location, signs, path_length: int, method: int, first: int, count: int):
+        """Tests: the expansion of a join index (k_expand) for ordinals [first, first + count).  Returns (row0, row1)."""
+        path_idx = np.ascontiguousarray(path_idx, dtype=np.int64)
+        location = np.ascontiguousarray(location, dtype=np.int64)
+        signs = np.ascontiguousarray(signs, dtype=np.int32)
+        row0 = np.full(max(count, 1), 0xffffffff, dtype=np.uint32)
+        row1 = np.full(max(count, 1), 0xffffffff, dtype=np.uint32)
+        self._check(self._lib.gcre_test_expand(self._h, _ptr(path_idx), _ptr(location), len(location), _ptr(signs), len(signs),
+                                               int(path_length), int(method), int(first), int(count), _ptr(row0), _ptr(row1)))
+        return row0[:count], row1[:count]
 
     def create_path_set(self, size: int) -> PathSet:
         return PathSet(self, self._lib.gcre_pathset_zeros(self._h, int(size)))

@@ -36,6 +36,24 @@ struct ncclComm;   // RCCL's communicator, opaque here (ncclComm_t is a pointer 
 // What the host files see of each other stays out of the dynamic symbol table
 namespace gcre_host __attribute__((visibility("hidden"))) {
 
+// The piece table of the range check (RangePiece): range r = rows loc[r] .. loc[r] + cnt[r] - 1 of paths1, whole when it has at
+// most `piece_rows` rows, otherwise cut into pieces of that many and listed in `cut`.  Returns the rows in all.
+inline int64_t build_range_pieces(const std::vector<int64_t>& loc, const std::vector<int32_t>& cnt, std::vector<RangePiece>& pieces,
+                                  std::vector<int32_t>& cut, int32_t piece_rows = kRangePieceRows) {
+  int64_t rows = 0;
+  for (size_t r = 0; r < loc.size(); r++) {
+    rows += cnt[r];
+    if (cnt[r] <= piece_rows) {
+      pieces.push_back(RangePiece{loc[r], (int32_t)r, cnt[r]});
+      continue;
+    }
+    cut.push_back((int32_t)r);
+    for (int32_t t = 0; t < cnt[r]; t += piece_rows)
+      pieces.push_back(RangePiece{loc[r] + t, (int32_t)r, (int32_t)(std::min(piece_rows, cnt[r] - t) | 0x80000000)});
+  }
+  return rows;
+}
+
 template <typename T>
 struct DevBuf {   // grow-only device scratch
   T* p = nullptr;
@@ -47,6 +65,12 @@ struct DevBuf {   // grow-only device scratch
     cap = 0;
     hipError_t e = hipMalloc((void**)&p, n * sizeof(T));
     if (e == hipSuccess) cap = n;
+    return e;
+  }
+  // room for n elements (at least one), filled from the host
+  hipError_t upload(const T* src, size_t n, hipStream_t stream) {
+    hipError_t e = reserve(std::max<size_t>(n, 1));
+    if (e == hipSuccess && n) e = hipMemcpyAsync(p, src, n * sizeof(T), hipMemcpyHostToDevice, stream);
     return e;
   }
   // grow and keep the first `keep` elements
@@ -481,9 +505,10 @@ struct gcre_uids {
   // distinct (location, count) ranges of the uids (all uids with the same pivot gene share one): built on first use
   mutable int64_t n_ranges = -1;
   mutable int32_t* d_range_of = nullptr;    // uid -> range
-  mutable int64_t n_pairs = 0;              // (range, paths1 row) pairs = sum of the range lengths
-  mutable int32_t* d_pair_range = nullptr;
-  mutable int64_t* d_pair_loc = nullptr;
+  mutable int64_t n_pairs = 0;              // sum of the range lengths: the paths1 rows the range check reads
+  mutable int64_t n_pieces = 0, n_cut = 0;  // the ranges as the range check walks them (RangePiece), and those cut in pieces
+  mutable RangePiece* d_pieces = nullptr;
+  mutable int32_t* d_cut = nullptr;
 };
 
 // The per-gene best-path table of one join: which slots a joined path touches -- through its paths0 row

@@ -778,7 +778,7 @@ void gcre_host::free_uids(gcre_uids* u) {
     v.erase(std::remove(v.begin(), v.end(), u), v.end());
   }
   for (void* p : {(void*)u->d_path_idx, (void*)u->d_location, (void*)u->d_signs, (void*)u->d_red_index,
-                  (void*)u->d_range_of, (void*)u->d_pair_range, (void*)u->d_pair_loc})
+                  (void*)u->d_range_of, (void*)u->d_pieces, (void*)u->d_cut})
     if (p) (void)hipFree(p);
   for (auto& sc : u->seg_cache) {
     if (sc.d_segs) (void)hipFree(sc.d_segs);
@@ -876,24 +876,27 @@ int ensure_ranges(gcre_ctx* c, const gcre_uids& u) {
     range_of[(size_t)i] = r;
   }
   const size_t R = loc.size();
-  std::vector<int32_t> pair_range;
-  std::vector<int64_t> pair_loc;
-  for (size_t r = 0; r < R; r++)
-    for (int32_t t = 0; t < cnt[r]; t++) {
-      pair_range.push_back((int32_t)r);
-      pair_loc.push_back(loc[r] + t);
-    }
-  const size_t T = pair_range.size();
-  HIP_TRY(c, hipMalloc((void**)&u.d_range_of, range_of.size() * 4));
-  HIP_TRY(c, hipMalloc((void**)&u.d_pair_range, std::max<size_t>(T, 1) * 4));
-  HIP_TRY(c, hipMalloc((void**)&u.d_pair_loc, std::max<size_t>(T, 1) * 8));
-  HIP_TRY(c, hipMemcpyAsync(u.d_range_of, range_of.data(), range_of.size() * 4, hipMemcpyHostToDevice, c->stream));
-  if (T) {
-    HIP_TRY(c, hipMemcpyAsync(u.d_pair_range, pair_range.data(), T * 4, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(u.d_pair_loc, pair_loc.data(), T * 8, hipMemcpyHostToDevice, c->stream));
+  std::vector<RangePiece> pieces;
+  std::vector<int32_t> cut;
+  const int64_t T = build_range_pieces(loc, cnt, pieces, cut);
+  if (g_launch_trace) {
+    std::vector<int32_t> by_len(cnt);
+    std::sort(by_len.begin(), by_len.end());
+    auto q = [&](double f) { return R ? by_len[std::min(R - 1, (size_t)(f * (double)R))] : 0; };
+    fprintf(stderr, "ranges n_uids=%lld paths=%lld n_ranges=%zu n_pairs=%lld pieces=%zu cut=%zu rows/range median=%d p99=%d max=%d\n",
+            (long long)u.n_uids, (long long)u.total, R, (long long)T, pieces.size(), cut.size(), q(0.5), q(0.99), q(1.0));
   }
+  HIP_TRY(c, hipMalloc((void**)&u.d_range_of, range_of.size() * 4));
+  HIP_TRY(c, hipMalloc((void**)&u.d_pieces, std::max<size_t>(pieces.size(), 1) * sizeof(RangePiece)));
+  HIP_TRY(c, hipMalloc((void**)&u.d_cut, std::max<size_t>(cut.size(), 1) * 4));
+  HIP_TRY(c, hipMemcpyAsync(u.d_range_of, range_of.data(), range_of.size() * 4, hipMemcpyHostToDevice, c->stream));
+  if (!pieces.empty())
+    HIP_TRY(c, hipMemcpyAsync(u.d_pieces, pieces.data(), pieces.size() * sizeof(RangePiece), hipMemcpyHostToDevice, c->stream));
+  if (!cut.empty()) HIP_TRY(c, hipMemcpyAsync(u.d_cut, cut.data(), cut.size() * 4, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));   // the vectors are locals
-  u.n_pairs = (int64_t)T;
+  u.n_pairs = T;
+  u.n_pieces = (int64_t)pieces.size();
+  u.n_cut = (int64_t)cut.size();
   u.n_ranges = (int64_t)R;
   return GCRE_OK;
 }
@@ -1770,10 +1773,8 @@ int range_union_now(JoinRun& R) {
   const gcre_uids& u = *R.u;
   const Geometry& g = R.g;
   R.range_union_due = false;
-  const size_t ewords = (size_t)std::max<int64_t>(u.n_ranges, 1) * g.S;
-  HIP_TRY(c, hipMemsetAsync(R.exbuf->p, 0, ewords * 8, R.st));
   HIP_TRY(c, hipMemsetAsync(R.flagblk + kFlagRangeUnion, 0, (kFlagWords - kFlagRangeUnion) * 4, R.st));
-  HIP_TRY(c, launch_range_union(R.jp.p1->d_rows, R.red->d_rows, u.d_red_index, u.d_pair_range, u.d_pair_loc, u.n_pairs, g.S,
+  HIP_TRY(c, launch_range_union(R.jp.p1->d_rows, R.red->d_rows, u.d_red_index, u.d_pieces, u.n_pieces, u.d_cut, u.n_cut, g.S,
                                 g.Wp, g.method, R.exbuf->p, R.flagblk + kFlagRangeUnion, R.st));
   return GCRE_OK;
 }
@@ -3142,6 +3143,87 @@ int gcre_get_perm_mask(gcre_ctx* c, int r, uint64_t* out) {
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   HIP_TRY(c, hipMemcpy2D(col.data(), 4, c->d_masks + r, (size_t)g.Kpad * 4, 4, (size_t)2 * g.Wp, hipMemcpyDeviceToHost));
   for (int k = 0; k < g.W; k++) out[k] = (uint64_t)col[(size_t)2 * k] | ((uint64_t)col[(size_t)2 * k + 1] << 32);
+  return GCRE_OK;
+}
+
+// ---- tests: one helper kernel of a join on inputs given from the host ----
+int gcre_test_range_union(gcre_ctx* c, const uint64_t* p1, int64_t n1, const uint64_t* pz, int64_t nz, const int32_t* zindex,
+                          const int64_t* loc, const int32_t* cnt, int64_t n_ranges, int S, int Wp, int method, uint64_t* u_out,
+                          uint32_t* bad_out, int32_t* piece_rows_out) {
+  if (!c) return GCRE_ERR_ARG;
+  if (piece_rows_out) *piece_rows_out = kRangePieceRows;
+  if (n_ranges == 0) return GCRE_OK;
+  if (!p1 || !pz || !zindex || !loc || !cnt || !u_out || !bad_out || n_ranges < 0 || Wp <= 0 || Wp % 4 || (method != 1 && method != 2) ||
+      S != method * Wp)
+    return fail(c, GCRE_ERR_ARG, "gcre_test_range_union: bad arguments");
+  for (int64_t r = 0; r < n_ranges; r++) {
+    if (cnt[r] <= 0 || loc[r] < 0 || loc[r] + cnt[r] > n1) return fail(c, GCRE_ERR_RANGE, "gcre_test_range_union: range outside paths1");
+    for (int64_t l = loc[r]; l < loc[r] + cnt[r]; l++)
+      if ((int64_t)(zindex[l] & 0x7fffffff) >= nz) return fail(c, GCRE_ERR_RANGE, "gcre_test_range_union: reduced row out of range");
+  }
+  (void)hipSetDevice(c->device);
+  std::vector<RangePiece> pieces;
+  std::vector<int32_t> cut;
+  build_range_pieces(std::vector<int64_t>(loc, loc + n_ranges), std::vector<int32_t>(cnt, cnt + n_ranges), pieces, cut);
+  DevBuf<uint64_t> d1, dz, du;
+  DevBuf<int32_t> dzi, dcut;
+  DevBuf<RangePiece> dp;
+  DevBuf<uint32_t> dbad;
+  hipStream_t st = c->stream;
+  const size_t uw = (size_t)n_ranges * S;
+  hipError_t e = d1.upload(p1, (size_t)n1 * S, st);
+  if (e == hipSuccess) e = dz.upload(pz, (size_t)nz * S, st);
+  if (e == hipSuccess) e = dzi.upload(zindex, (size_t)n1, st);
+  if (e == hipSuccess) e = dp.upload(pieces.data(), pieces.size(), st);
+  if (e == hipSuccess) e = dcut.upload(cut.data(), cut.size(), st);
+  if (e == hipSuccess) e = du.reserve(uw);
+  if (e == hipSuccess) e = dbad.reserve(1);
+  if (e == hipSuccess) e = hipMemsetAsync(du.p, 0xa5, uw * 8, st);   // the kernel must not count on a zeroed table
+  if (e == hipSuccess) e = hipMemsetAsync(dbad.p, 0, 4, st);
+  if (e == hipSuccess)
+    e = launch_range_union(d1.p, dz.p, dzi.p, dp.p, (int64_t)pieces.size(), dcut.p, (int64_t)cut.size(), S, Wp, method, du.p, dbad.p, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(u_out, du.p, uw * 8, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(bad_out, dbad.p, 4, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  for (void* p : {(void*)d1.p, (void*)dz.p, (void*)du.p, (void*)dzi.p, (void*)dcut.p, (void*)dp.p, (void*)dbad.p})
+    if (p) (void)hipFree(p);
+  if (e != hipSuccess) return fail(c, GCRE_ERR_DEVICE, std::string("gcre_test_range_union: ") + hipGetErrorString(e));
+  return GCRE_OK;
+}
+
+int gcre_test_expand(gcre_ctx* c, const int64_t* path_idx, const int64_t* location, int64_t n_uids, const int32_t* signs,
+                     int64_t n_signs, int path_length, int method, int64_t first, int64_t count, uint32_t* row0, uint32_t* row1) {
+  if (!c) return GCRE_ERR_ARG;
+  if (count == 0) return GCRE_OK;
+  if (!path_idx || !location || !row0 || !row1 || n_uids <= 0 || first < 0 || count < 0 || n_signs < 0 || (n_signs && !signs) ||
+      (method != 1 && method != 2))
+    return fail(c, GCRE_ERR_ARG, "gcre_test_expand: bad arguments");
+  if (path_idx[0] != 0 || first + count > path_idx[n_uids]) return fail(c, GCRE_ERR_RANGE, "gcre_test_expand: ordinals outside the index");
+  for (int64_t i = 0; i < n_uids; i++) {
+    const int64_t n = path_idx[i + 1] - path_idx[i];
+    if (n < 0 || (n > 0 && location[i] < 0)) return fail(c, GCRE_ERR_RANGE, "gcre_test_expand: bad index");
+    // the signs a uid with paths is looked up by (begin_join makes the same demand of a join's index)
+    const int64_t need = n == 0 || method != 2 ? 0 : path_length > 3 ? i + 1 : path_length < 3 ? location[i] + n
+                                                                                                : std::max(i + 1, location[i] + n);
+    if (n_signs < need) return fail(c, GCRE_ERR_RANGE, "gcre_test_expand: signs vector shorter than the rows it is indexed by");
+  }
+  (void)hipSetDevice(c->device);
+  DevBuf<int64_t> dpi, dloc;
+  DevBuf<int32_t> dsg;
+  DevBuf<uint32_t> d0, d1;
+  hipStream_t st = c->stream;
+  hipError_t e = dpi.upload(path_idx, (size_t)n_uids + 1, st);
+  if (e == hipSuccess) e = dloc.upload(location, (size_t)n_uids, st);
+  if (e == hipSuccess) e = dsg.upload(signs, (size_t)n_signs, st);
+  if (e == hipSuccess) e = d0.reserve((size_t)count);
+  if (e == hipSuccess) e = d1.reserve((size_t)count);
+  if (e == hipSuccess) e = launch_expand(dpi.p, dloc.p, n_uids, dsg.p, path_length, method, first, count, d0.p, d1.p, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(row0, d0.p, (size_t)count * 4, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(row1, d1.p, (size_t)count * 4, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  for (void* p : {(void*)dpi.p, (void*)dloc.p, (void*)dsg.p, (void*)d0.p, (void*)d1.p})
+    if (p) (void)hipFree(p);
+  if (e != hipSuccess) return fail(c, GCRE_ERR_DEVICE, std::string("gcre_test_expand: ") + hipGetErrorString(e));
   return GCRE_OK;
 }
 

@@ -219,42 +219,94 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k
 
 // Excess of paths1 over the reduced operand, per distinct (location, count) range of the join index:
 //   U[r] = OR over loc in the range of  paths1[loc] & ~z'(loc),   z'(loc) = reduced[index[loc]] in paths1's orientation
-// and the check that z'(loc) lies inside paths1[loc].  One wave per (range, row) pair, OR-ed into U with atomics (the
-// excess is the pivot gene's carriers: a few dozen non-zero words); U is zero on entry.
-__global__ __launch_bounds__(256) void k_range_union(const u64* p1, const u64* pz, const int32_t* zindex, const int32_t* pair_range,
-                                                     const i64* pair_loc, i64 npairs, int S, int Wp, int M, u64* excess,
-                                                     u32* bad) {
-  const int lane = threadIdx.x & 63;
-  const i64 wave = (i64)blockIdx.x * 4 + (threadIdx.x >> 6);
+// and the check that z'(loc) lies inside paths1[loc].  A range is a block of consecutive paths1 rows (RangePiece; the host
+// cuts a range of more than kRangePieceRows rows into pieces of that many).  A wave owns one (piece, 32-word column): each of
+// its four 16-lane groups reads every fourth row of the piece, 16 bytes per lane and all its rows in flight at once, the
+// groups' excess words meet by two shuffles, and the column of U[range] is written once, zero words included -- a plain
+// store, U need not be zero on entry.  Only the pieces of a cut range meet in one row of U: they OR their non-zero words
+// into it with atomics, and k_range_zero clears those rows first.
+constexpr int kRangeGroupRows = kRangePieceRows / 4;
+constexpr int kRangeUnionMaxBlocks = 1024;   // x 4 waves x 64 lanes x kRangeGroupRows x 32 B in flight: 33 MB
+
+__global__ __launch_bounds__(256) void k_range_union(const u64* p1, const u64* pz, const int32_t* zindex, const RangePiece* pieces,
+                                                     i64 npieces, int S, int Wp, int M, u64* excess, u32* bad) {
+  const int sl = threadIdx.x & 15, grp = (threadIdx.x >> 4) & 3;
+  const int ncol = (S + 31) >> 5;                     // 32-word columns of a row
+  const i64 items = npieces * ncol;
   const i64 nwaves = (i64)gridDim.x * 4;
   bool my_bad = false;
-  for (i64 p = wave; p < npairs; p += nwaves) {
-    const i64 loc = pair_loc[p];
-    const u32 zraw = (u32)zindex[loc];
-    const u64* zrow = pz + (size_t)(zraw & 0x7fffffffu) * S;
-    const u64* yrow = p1 + (size_t)loc * S;
-    u64* urow = excess + (size_t)pair_range[p] * S;
-    for (int w = lane; w < S; w += 64) {
-      const int h = w / Wp, k = w - h * Wp;
-      const int hz = (M == 2 && (zraw >> 31)) ? 1 - h : h;
-      const u64 zw = zrow[(size_t)hz * Wp + k];
-      const u64 yw = yrow[w];
-      if (zw & ~yw) my_bad = true;
-      const u64 e = yw & ~zw;
-      if (e) atomicOr((unsigned long long*)(urow + w), (unsigned long long)e);
+  for (i64 it = (i64)blockIdx.x * 4 + (threadIdx.x >> 6); it < items; it += nwaves) {   // (wave-uniform)
+    const i64 pc = it / ncol;
+    const int w = ((int)(it - pc * ncol) << 5) + 2 * sl;   // this lane's two words (S and Wp are multiples of 4: never split)
+    const bool active = w < S;                             // (the same in the four lanes that meet below)
+    const RangePiece piece = pieces[pc];
+    const int n = piece.rows & 0x7fffffff;
+    const int h = active ? w / Wp : 0, k = active ? w - h * Wp : 0;
+    u32 zraw[kRangeGroupRows];
+    ulonglong2 y[kRangeGroupRows], z[kRangeGroupRows];
+#pragma unroll
+    for (int j = 0; j < kRangeGroupRows; j++) {
+      const bool v = active && grp + 4 * j < n;
+      zraw[j] = v ? (u32)zindex[piece.first + grp + 4 * j] : 0u;
+    }
+#pragma unroll
+    for (int j = 0; j < kRangeGroupRows; j++) {
+      const bool v = active && grp + 4 * j < n;
+      const int hz = (M == 2 && (zraw[j] >> 31)) ? 1 - h : h;
+      y[j] = z[j] = make_ulonglong2(0ull, 0ull);
+      if (v) {
+        y[j] = *reinterpret_cast<const ulonglong2*>(p1 + (size_t)(piece.first + grp + 4 * j) * S + w);
+        z[j] = *reinterpret_cast<const ulonglong2*>(pz + (size_t)(zraw[j] & 0x7fffffffu) * S + (size_t)hz * Wp + k);
+      }
+    }
+    ulonglong2 acc = make_ulonglong2(0ull, 0ull);
+#pragma unroll
+    for (int j = 0; j < kRangeGroupRows; j++) {
+      if ((z[j].x & ~y[j].x) | (z[j].y & ~y[j].y)) my_bad = true;
+      acc.x |= y[j].x & ~z[j].x;
+      acc.y |= y[j].y & ~z[j].y;
+    }
+#pragma unroll
+    for (int d = 16; d <= 32; d <<= 1) {
+      acc.x |= __shfl_xor(acc.x, d);
+      acc.y |= __shfl_xor(acc.y, d);
+    }
+    if (active && grp == 0) {
+      u64* u = excess + (size_t)piece.range * S + w;
+      if (piece.rows < 0) {   // a piece of a cut range
+        if (acc.x) atomicOr((unsigned long long*)u, acc.x);
+        if (acc.y) atomicOr((unsigned long long*)(u + 1), acc.y);
+      } else {
+        *reinterpret_cast<ulonglong2*>(u) = acc;
+      }
     }
   }
   if (my_bad) *bad = 1u;
 }
 
-hipError_t launch_range_union(const uint64_t* p1, const uint64_t* pz, const int32_t* zindex, const int32_t* pair_range,
-                              const int64_t* pair_loc, int64_t npairs, int S, int Wp, int method, uint64_t* excess,
+// the rows of U that the pieces of cut ranges OR into
+__global__ __launch_bounds__(256) void k_range_zero(const int32_t* cut, i64 ncut, int S, u64* excess) {
+  const i64 total = ncut * (S >> 1);
+  for (i64 i = (i64)blockIdx.x * 256 + threadIdx.x; i < total; i += (i64)gridDim.x * 256) {
+    const i64 c = i / (S >> 1);
+    const int w = (int)(i - c * (S >> 1)) * 2;
+    *reinterpret_cast<ulonglong2*>(excess + (size_t)cut[c] * S + w) = make_ulonglong2(0ull, 0ull);
+  }
+}
+
+hipError_t launch_range_union(const uint64_t* p1, const uint64_t* pz, const int32_t* zindex, const RangePiece* pieces,
+                              int64_t npieces, const int32_t* cut, int64_t ncut, int S, int Wp, int method, uint64_t* excess,
                               uint32_t* bad, hipStream_t stream) {
-  if (npairs == 0) return hipSuccess;
-  const i64 blocks = (npairs + 3) / 4;
-  trace_launch("k_range_union", blocks, blocks < 16384 ? blocks : 16384);
-  hipLaunchKernelGGL(k_range_union, dim3((unsigned)(blocks < 16384 ? blocks : 16384)), dim3(256), 0, stream, p1, pz, zindex,
-                     pair_range, pair_loc, npairs, S, Wp, method, excess, bad);
+  if (npieces == 0) return hipSuccess;
+  if (ncut) {
+    const i64 zb = (ncut * (S >> 1) + 255) / 256;
+    hipLaunchKernelGGL(k_range_zero, dim3((unsigned)(zb < 4096 ? zb : 4096)), dim3(256), 0, stream, cut, ncut, S, excess);
+  }
+  const i64 blocks = (npieces * ((S + 31) >> 5) + 3) / 4;
+  const i64 grid = blocks < kRangeUnionMaxBlocks ? blocks : kRangeUnionMaxBlocks;
+  trace_launch("k_range_union", blocks, grid);
+  hipLaunchKernelGGL(k_range_union, dim3((unsigned)grid), dim3(256), 0, stream, p1, pz, zindex, pieces, npieces, S, Wp, method,
+                     excess, bad);
   return hipGetLastError();
 }
 

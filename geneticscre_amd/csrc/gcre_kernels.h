@@ -288,8 +288,19 @@ constexpr int kInspectMaxBlocks = 256 * 16;
 constexpr int kStatsIeBlockPaths = 4 * kInspectBlockWaves;   // k_stats_ie: four paths per wave and pass, the most waves per path
 hipError_t launch_stats(const StatsArgs& a, int method, hipStream_t stream);
 hipError_t launch_stats_ie(const StatsArgs& a, int method, hipStream_t stream);   // gcre_inspect.hip
-hipError_t launch_range_union(const uint64_t* p1, const uint64_t* pz, const int32_t* zindex, const int32_t* pair_range,
-                              const int64_t* pair_loc, int64_t npairs, int S, int Wp, int method, uint64_t* excess,
+// The range check of a hinted join walks each distinct uid range -- `rows` consecutive paths1 rows from `first` -- once.  A
+// range of more than kRangePieceRows rows (a hub gene's) is cut into pieces of that many (the last one shorter), marked by
+// bit 31 of `rows`; `cut` lists the ranges that were cut.  16 rows: what one wave of k_range_union reads in a single round
+// (four 16-lane groups, four rows each in flight).  The benchmark's level 4: 16,881 ranges, median 7 rows, 99th percentile
+// 84, longest 3,467; 2,172 ranges are cut, 21,765 pieces in all (profiles/helpers_before.txt).
+constexpr int kRangePieceRows = 16;
+struct RangePiece {
+  int64_t first;     // paths1 row
+  int32_t range;     // row of U
+  int32_t rows;      // 1 .. kRangePieceRows; | 0x80000000: one piece of several
+};
+hipError_t launch_range_union(const uint64_t* p1, const uint64_t* pz, const int32_t* zindex, const RangePiece* pieces,
+                              int64_t npieces, const int32_t* cut, int64_t ncut, int S, int Wp, int method, uint64_t* excess,
                               uint32_t* bad, hipStream_t stream);
 
 // ---- top-k selection over key[0..count) ----

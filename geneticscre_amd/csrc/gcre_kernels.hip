@@ -385,43 +385,88 @@ hipError_t launch_masks_from_words(const uint64_t* packed, int nrows_in, const G
 // ------------------------------------------------------------------------------------------------
 // joined-path ordinal -> rows (the two nested loops of JoinExec::join, join_base.cpp:230-250)
 // ------------------------------------------------------------------------------------------------
-constexpr int kExpandRun = 8;   // consecutive joined paths per thread: one binary search, then a walk along the uids
+// A wave owns a tile of kExpandTile consecutive ordinals and walks the uids that cover it, 64 at a time: lane l holds uid
+// u0 + l (one coalesced load per array, the next 64 already on their way), every ordinal finds its uid among the wave's 64
+// by a six-step search through shuffles, and consecutive lanes write consecutive ordinals.  The tile's first uid is found
+// once, 64 probes a step, where every 8 paths used to pay a 21-step search of their own.
+// No LDS and few registers on purpose: the expansion of a level runs beside the pruned null kernel of the level before, whose
+// blocks leave wave slots free but no LDS -- a block that asks for any waits until that kernel has drained.
+constexpr int kExpandTile = 1024;
+constexpr int kExpandMaxBlocks = 1024;   // four tiles a block; a wave goes on to the tile 4,096 further on
 
-__global__ void k_expand(const i64* path_idx, const i64* location, i64 n_uids, const int32_t* signs, int path_length,
-                         int method, i64 first, i64 count, u32* row0, u32* row1) {
-  const i64 runs = (count + kExpandRun - 1) / kExpandRun;
-  for (i64 r = (i64)blockIdx.x * blockDim.x + threadIdx.x; r < runs; r += (i64)gridDim.x * blockDim.x) {
-    const i64 i0 = r * kExpandRun;
-    const i64 i1 = i0 + kExpandRun < count ? i0 + kExpandRun : count;
-    // last uid whose first path ordinal is <= p (uids with count 0 share an ordinal with their successor)
-    i64 lo = 0, hi = n_uids;   // invariant: path_idx[lo] <= p < path_idx[hi]
-    {
-      const i64 p = first + i0;
-      while (hi - lo > 1) {
-        const i64 mid = (lo + hi) >> 1;
-        if (path_idx[mid] <= p) lo = mid; else hi = mid;
-      }
+struct ExpandUids {   // the wave's 64 uids, one per lane; past the last uid: an empty one that starts where the index ends
+  i64 b0, b1;         // first ordinal of this uid and of the next
+  i64 loc;
+  int sign;
+};
+
+__device__ __forceinline__ ExpandUids expand_load(const i64* path_idx, const i64* location, const int32_t* signs, i64 n_uids, i64 u,
+                                                  bool want_sign) {
+  ExpandUids e;
+  const bool valid = u < n_uids;
+  e.b0 = path_idx[valid ? u : n_uids];
+  e.b1 = path_idx[valid ? u + 1 : n_uids];
+  e.loc = valid ? location[u] : 0;
+  // (signs reaches as far as the last uid that has paths: an empty uid's word is never used, and never read)
+  e.sign = (want_sign && e.b1 > e.b0) ? signs[u] : 0;
+  return e;
+}
+
+__global__ __launch_bounds__(256) void k_expand(const i64* path_idx, const i64* location, i64 n_uids, const int32_t* signs,
+                                                int path_length, int method, i64 first, i64 count, u32* row0, u32* row1) {
+  const int lane = threadIdx.x & 63;
+  const i64 nwaves = (i64)gridDim.x * 4;
+  const i64 tiles = (count + kExpandTile - 1) / kExpandTile;
+  const bool want_sign = method == 2 && path_length >= 3;
+  for (i64 tile = (i64)blockIdx.x * 4 + (threadIdx.x >> 6); tile < tiles; tile += nwaves) {   // (wave-uniform)
+    const i64 pb = first + tile * kExpandTile;                                   // ordinals [pb, pe)
+    const i64 pe = first + (tile * kExpandTile + kExpandTile < count ? tile * kExpandTile + kExpandTile : count);
+    // last uid whose first path ordinal is <= pb (uids with count 0 share an ordinal with their successor)
+    i64 lo = 0, hi = n_uids;   // invariant: path_idx[lo] <= pb < path_idx[hi]
+    while (hi - lo > 1) {
+      const i64 step = (hi - lo + 63) >> 6;
+      const i64 q = lo + (lane + 1) * step;
+      const bool le = q < hi && path_idx[q] <= pb;   // path_idx ascends: true in a prefix of the lanes
+      const i64 c = __popcll(__ballot(le));
+      hi = lo + (c + 1) * step < hi ? lo + (c + 1) * step : hi;
+      lo += c * step;
     }
-    i64 idx = lo;
-    i64 next = path_idx[idx + 1];   // first ordinal of the uid after idx
-    for (i64 i = i0; i < i1; i++) {
-      const i64 p = first + i;
-      while (next <= p) {           // the same "last uid with path_idx <= p" as the search: empty uids are stepped over
-        idx++;
-        next = path_idx[idx + 1];
+    ExpandUids cur = expand_load(path_idx, location, signs, n_uids, lo + lane, want_sign);
+    for (i64 u0 = lo;; u0 += 64) {
+      const ExpandUids nxt = expand_load(path_idx, location, signs, n_uids, u0 + 64 + lane, want_sign);
+      // a uid's start as the tile sees it: before the tile = 0, beyond 2^32 = beyond every ordinal of the tile
+      const i64 d = cur.b0 - pb;
+      const u32 rel = d < 0 ? 0u : d > 0xffffffffll ? 0xffffffffu : (u32)d;
+      const u32 base = (u32)(cur.loc - d);               // row of paths1 = base + (p - pb), modulo 2^32 (rows are below 2^31)
+      const i64 s_first = __shfl(cur.b0, 0), s_end = __shfl(cur.b1, 63);
+      const i64 qb = s_first > pb ? s_first : pb;
+      const i64 qe = s_end < pe ? s_end : pe;
+      for (i64 P = qb; P < qe; P += 64) {
+        const i64 p = P + lane;
+        const bool active = p < qe;
+        const u32 x = (u32)(p - pb);
+        int a = 0;   // the last lane whose uid starts at or before p: empty uids are stepped over (rel[0] <= x < "rel[64]")
+#pragma unroll
+        for (int w = 32; w > 0; w >>= 1)
+          if (__shfl(rel, a + w) <= x) a += w;
+        const u32 loc = __shfl(base, a) + x;
+        const int sign_a = __shfl(cur.sign, a);
+        if (active) {
+          u32 swap = 0;
+          if (method == 2) {
+            // UidRelSet::need_flip (gcre.h:71-81): sign == 1 keeps path1's halves, otherwise they swap
+            int sign;
+            if (path_length > 3) sign = sign_a;
+            else if (path_length < 3) sign = signs[loc];
+            else sign = (sign_a + signs[loc] == 0) ? -1 : 1;
+            swap = (sign == 1) ? 0u : 1u;
+          }
+          row0[p - first] = (u32)(u0 + a);
+          row1[p - first] = loc | (swap << 31);
+        }
       }
-      const i64 loc = location[idx] + (p - path_idx[idx]);
-      u32 swap = 0;
-      if (method == 2) {
-        // UidRelSet::need_flip (gcre.h:71-81): sign == 1 keeps path1's halves, otherwise they swap
-        int sign;
-        if (path_length > 3) sign = signs[idx];
-        else if (path_length < 3) sign = signs[loc];
-        else sign = (signs[idx] + signs[loc] == 0) ? -1 : 1;
-        swap = (sign == 1) ? 0u : 1u;
-      }
-      row0[i] = (u32)idx;
-      row1[i] = (u32)loc | (swap << 31);
+      if (s_end >= pe) break;   // (wave-uniform; path_idx[n_uids] >= first + count ends the walk at the latest)
+      cur = nxt;
     }
   }
 }
@@ -430,10 +475,11 @@ hipError_t launch_expand(const int64_t* path_idx, const int64_t* location, int64
                          int path_length, int method, int64_t first, int64_t count, uint32_t* row0, uint32_t* row1,
                          hipStream_t stream) {
   if (count == 0) return hipSuccess;
-  const int grid = (int)hmin((count + 255) / 256, 16384);
-  trace_launch("k_expand", (count + 255) / 256, grid);
-  hipLaunchKernelGGL(k_expand, dim3(grid), dim3(256), 0, stream, path_idx, location, n_uids, signs, path_length, method,
-                     first, count, row0, row1);
+  const i64 blocks = ((count + kExpandTile - 1) / kExpandTile + 3) / 4;
+  const int grid = (int)hmin(blocks, kExpandMaxBlocks);
+  trace_launch("k_expand", blocks, grid);
+  hipLaunchKernelGGL(k_expand, dim3(grid), dim3(256), 0, stream, path_idx, location, n_uids, signs, path_length, method, first,
+                     count, row0, row1);
   return hipGetLastError();
 }
 

@@ -327,6 +327,17 @@ int gcre_set_inspect_cache(gcre_ctx* ctx, int on);
 int gcre_drop_inspections(gcre_ctx* ctx, int release_memory);
 /* read permutation mask r back as width_ul words (bit c = patient c is a case under permutation r) */
 int gcre_get_perm_mask(gcre_ctx* ctx, int r, uint64_t* out);
+/* Tests only: one helper kernel of a join, run on inputs given from the host, its output copied back word for word.
+ * gcre_test_range_union: the range check of a hinted join over ranges r = rows loc[r] .. loc[r] + cnt[r] - 1 of p1 (n1 rows of
+ * S = method * Wp words; zindex[n1]: the row of pz that stands for each, bit 31 = halves swapped); u_out[n_ranges * S] is the
+ * excess per range, *bad_out whether some reduced row is not inside the row it stands for, *piece_rows_out the number of rows
+ * above which a range is walked in pieces.  gcre_test_expand: ordinals [first, first + count) of the join index
+ * (path_idx[n_uids + 1], location[n_uids], signs[n_signs]) to their rows of paths0 (row0) and paths1 (row1, bit 31 = swap). */
+int gcre_test_range_union(gcre_ctx* ctx, const uint64_t* p1, int64_t n1, const uint64_t* pz, int64_t nz, const int32_t* zindex,
+                          const int64_t* loc, const int32_t* cnt, int64_t n_ranges, int S, int Wp, int method, uint64_t* u_out,
+                          uint32_t* bad_out, int32_t* piece_rows_out);
+int gcre_test_expand(gcre_ctx* ctx, const int64_t* path_idx, const int64_t* location, int64_t n_uids, const int32_t* signs,
+                     int64_t n_signs, int path_length, int method, int64_t first, int64_t count, uint32_t* row0, uint32_t* row1);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Decorated p-values (getDecoratedPvalues / computeDecoratedPvalue, R/DecoratedPvalue.R:48-304; GWASPA's second table,
