@@ -174,7 +174,7 @@ EXPORTS = [
     "gcre_exceed_stepdown", "gcre_stepdown_launches",
     "gcre_hits_create", "gcre_join_set_hits", "gcre_process_paths_set_hits", "gcre_hits_count", "gcre_hits_read",
     "gcre_hits_reset", "gcre_hits_free", "gcre_hits_launches",
-    "gcre_test_range_union", "gcre_test_expand",
+    "gcre_test_range_union", "gcre_test_expand", "gcre_test_inspect",
 ]
 
 
@@ -265,6 +265,8 @@ def load_library():
     if hasattr(lib, "gcre_test_expand"):   # (a GCRE_LIB variant built from an older commit has neither)
         lib.gcre_test_range_union.argtypes = [V, P, I64, P, I64, P, P, P, I64, I, I, I, P, P, P]
         lib.gcre_test_expand.argtypes = [V, P, P, I64, P, I64, I, I, I64, I64, P, P]
+    if hasattr(lib, "gcre_test_inspect"):
+        lib.gcre_test_inspect.argtypes = [V, V, V, P, P, I64, P, I64, P, P, I64, I64, P, P, P, P, P, P, P, I64, P, P]
     lib.gcre_uids_set_reduced.argtypes = [V, V, P, I64]
     lib.gcre_set_perm_window.argtypes = [V, I, I]
     lib.gcre_plan_perm_window.argtypes = [V, P, I]
@@ -1740,6 +1742,46 @@ class JoinExec:
         self._check(self._lib.gcre_test_expand(self._h, _ptr(path_idx), _ptr(location), len(location), _ptr(signs), len(signs),
                                                int(path_length), int(method), int(first), int(count), _ptr(row0), _ptr(row1)))
         return row0[:count], row1[:count]
+
+    def test_inspect(self, p0: PathSet, red: PathSet, row0, row1, zindex=None, excess=None, range_of=None,
+                     over_entries: Optional[int] = None, ent_stride: Optional[int] = None, keep_rows: bool = False) -> dict:
+        """Tests: the method-1 inspector (k_stats_ie2) on given row numbers, on the road GCRE_STATS_IE_COUNTS selects.  Path i
+        joins row row0[i] of p0 to row row1[i] of red, or to row zindex[row1[i]] of it; excess[ranges][vlen] and
+        range_of[rows of p0] make it a hinted join.  Returns tot, cases, ctrls, rowz, linfo, key, lists (per path: the
+        entries without padding, as the inspector ordered them), padding (per path: the padding entries), flags and, with
+        keep_rows, rows."""
+        row0 = np.ascontiguousarray(row0, dtype=np.uint32)
+        row1 = np.ascontiguousarray(row1, dtype=np.uint32)
+        n = len(row0)
+        assert len(row1) == n
+        if zindex is not None:
+            zindex = np.ascontiguousarray(zindex, dtype=np.int32)
+        if excess is not None:
+            excess = np.ascontiguousarray(excess, dtype=np.uint64).reshape(-1, self.vlen)
+            range_of = np.ascontiguousarray(range_of, dtype=np.int32)
+            assert len(range_of) == p0.size
+        stride = int(ent_stride) if ent_stride is not None else 64 * self.vlen + 8
+        over = int(over_entries) if over_entries is not None else n * stride
+        out = {k: np.zeros(max(n, 1), dtype=np.uint32) for k in ("tot", "cases", "ctrls", "rowz", "linfo")}
+        out["key"] = np.zeros(max(n, 1), dtype=np.uint64)
+        entries = np.zeros((max(n, 1), stride), dtype=np.uint32)
+        rows = np.zeros((max(n, 1), self.vlen), dtype=np.uint64) if keep_rows else None
+        flags = np.zeros(8, dtype=np.uint32)
+        self._check(self._lib.gcre_test_inspect(
+            self._h, p0._h, red._h, _ptr(row0), _ptr(row1), n, _ptr(zindex) if zindex is not None else None,
+            len(zindex) if zindex is not None else 0, _ptr(excess) if excess is not None else None,
+            _ptr(range_of) if excess is not None else None, len(excess) if excess is not None else 0, over,
+            _ptr(out["tot"]), _ptr(out["cases"]), _ptr(out["ctrls"]), _ptr(out["rowz"]), _ptr(out["linfo"]), _ptr(out["key"]),
+            _ptr(entries), stride, _ptr(rows) if keep_rows else None, _ptr(flags)))
+        out = {k: v[:n] for k, v in out.items()}
+        len8 = (out["linfo"] & 0x0ffffff8).astype(np.int64)
+        pad = (out["linfo"] >> 28).astype(np.int64)
+        out["lists"] = [entries[i, :len8[i] - pad[i]] for i in range(n)]
+        out["padding"] = [entries[i, len8[i] - pad[i]:len8[i]] for i in range(n)]
+        out["flags"] = flags
+        if keep_rows:
+            out["rows"] = rows[:n]
+        return out
 
     def create_path_set(self, size: int) -> PathSet:
         return PathSet(self, self._lib.gcre_pathset_zeros(self._h, int(size)))

@@ -329,6 +329,7 @@ struct gcre_ctx {
   int ieq_batch = 0;                 // GCRE_IEQ_BATCH: quads per ticket of the quad kernel (0: twice ie_batch)
   int ie_quad = 1;                   // GCRE_IE_QUAD=0: the pruned method-1 launches stay on k_null_ie_m1 (cross-check)
   int ie_flagq = 1;                  // GCRE_IE_FLAGQ=0: the quad kernel's second look + exact pass instead of the flag queue (A/B runs, tests)
+  int stats_ie_counts = 1;           // GCRE_STATS_IE_COUNTS=0: the method-1 inspector counts every joined row's words (A/B runs, tests)
   int ie_zwide = 0;                  // GCRE_IE_ZWIDE=1: the quad kernel reaches every added row through a descriptor of its own (tests)
   int ie_warm_items = 4;             // (segment, tile) items per wave of the warm-up launch (GCRE_IE_WARM_ITEMS)
   int ie_warm_div = 4096;            // the slice grows with the join as scored segments / this (GCRE_IE_WARM_DIV; warm_segments)
@@ -424,6 +425,12 @@ struct gcre_pathset {
   mutable uint32_t max_bits = 0;          // longest list (entries incl. padding): bounds the carriers of any row
   mutable bool max_known = false;
   mutable int one_sided = -1;             // method 2: every row has an empty half (-1: not looked at; from h_loff)
+  // method 1: carriers | carriers among the cases << 16 of every row (k_row_counts), for the inspector of a join that has
+  // this set as its reduced operand; built on first use, dropped with the lists.  counts_on: the stream that built them,
+  // counts_ev: recorded behind the kernel -- an inspector on another stream waits for it
+  mutable uint32_t* d_counts = nullptr;
+  mutable hipStream_t counts_on = nullptr;
+  mutable hipEvent_t counts_ev = nullptr;
   // count planes for the inclusion-exclusion kernel: [tile][row*M+h][groups][64][4] dwords, valid for one mask epoch
   mutable uint32_t* d_planes = nullptr;
   mutable int plane_groups = 0;

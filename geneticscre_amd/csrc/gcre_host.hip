@@ -228,7 +228,10 @@ void drop_planes(const gcre_pathset* ps) {
   ps->planes_valid = false;
 }
 
+void drop_row_counts(const gcre_pathset* ps);
+
 void drop_lists(const gcre_pathset* ps) {
+  drop_row_counts(ps);
   if (ps->d_loff) (void)hipFree(ps->d_loff);
   if (ps->d_lidx) (void)hipFree(ps->d_lidx);
   ps->d_loff = nullptr;
@@ -291,6 +294,38 @@ bool one_sided(const gcre_pathset* ps) {
     ps->one_sided = yes;
   }
   return ps->one_sided == 1;
+}
+
+void drop_row_counts(const gcre_pathset* ps) {
+  if (ps->d_counts) (void)hipFree(ps->d_counts);
+  if (ps->counts_ev) (void)hipEventDestroy(ps->counts_ev);
+  ps->d_counts = nullptr;
+  ps->counts_ev = nullptr;
+  ps->counts_on = nullptr;
+}
+
+// method 1: the row totals of a reduced operand (gcre_pathset::d_counts) for an inspector of `paths` joined paths that is
+// about to be queued on `st`, or nullptr where the inspector is to count the joined rows' words itself: the knob is off, or
+// the set has more rows than the join has paths (counting them would cost more than it saves).  Built on `st` on first use.
+int row_counts_for(gcre_ctx* c, const gcre_pathset* ps, int64_t paths, hipStream_t st, const uint32_t** out) {
+  *out = nullptr;
+  const Geometry& g = c->g;
+  if (!c->stats_ie_counts || g.method != 1 || g.Wp > 160 || ps->nrows <= 0 || ps->nrows > paths) return GCRE_OK;
+  if (!ps->d_counts) {
+    HIP_TRY(c, hipMalloc((void**)&ps->d_counts, (size_t)ps->nrows * 4));
+    hipError_t e = launch_row_counts(ps->d_rows, ps->nrows, g.Wp, c->d_case_mask, ps->d_counts, st);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&ps->counts_ev, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventRecord(ps->counts_ev, st);
+    if (e != hipSuccess) {
+      drop_row_counts(ps);
+      return fail(c, GCRE_ERR_DEVICE, std::string("row counts: ") + hipGetErrorString(e));
+    }
+    ps->counts_on = st;
+  } else if (ps->counts_on != st) {
+    HIP_TRY(c, hipStreamWaitEvent(st, ps->counts_ev, 0));
+  }
+  *out = ps->d_counts;
+  return GCRE_OK;
 }
 
 // largest number of carriers a row of the set can have (from its lists, or from the join that produced it)
@@ -1957,6 +1992,8 @@ int inspect_chunk(JoinRun& R, ChunkRun& C, ChunkEnd* end) {
     sa.ov_count = R.flagblk + kFlagOverReserved;
     sa.zoff = (uint32_t)(64 * g.Wp) << 8;
     if (g.method == 2 && one_sided(R.red)) sa.lz_off = R.red->d_loff;   // one round per path instead of one per half
+    if (!C.hit)   // method 1: counts from the reduced operand's row totals, where the join has at least as many paths as it has rows
+      if (int rc = row_counts_for(c, R.red, R.P, st, &sa.z_counts)) return rc;
     if (!C.hit) HIP_TRY(c, launch_stats_ie(sa, g.method, st));
     // a kept row's carrier total bounds every count of it: the next level loads only the plane groups that can be non-zero
     if (rcp && !C.hit)
@@ -2815,6 +2852,7 @@ gcre_ctx* gcre_create(int method, int n_cases, int n_ctrls, int iterations, int 
   if (const char* e = std::getenv("GCRE_IE_QUAD")) c->ie_quad = std::min(std::max(std::atoi(e), 0), 2);   // 2: wherever it can run
   if (const char* e = std::getenv("GCRE_IE_FLAGQ")) c->ie_flagq = std::atoi(e) != 0;
   if (const char* e = std::getenv("GCRE_IE_ZWIDE")) c->ie_zwide = std::atoi(e) != 0;
+  if (const char* e = std::getenv("GCRE_STATS_IE_COUNTS")) c->stats_ie_counts = std::atoi(e) != 0;
   if (const char* e = std::getenv("GCRE_PLANES_OUT_MAX_MB")) c->planes_out_max = (size_t)std::max(0ll, std::atoll(e)) << 20;
   if (const char* e = std::getenv("GCRE_SPARSE_WAVES_PER_CU")) c->sparse_waves_per_cu = std::max(1, std::atoi(e));
 
@@ -3224,6 +3262,127 @@ int gcre_test_expand(gcre_ctx* c, const int64_t* path_idx, const int64_t* locati
   for (void* p : {(void*)dpi.p, (void*)dloc.p, (void*)dsg.p, (void*)d0.p, (void*)d1.p})
     if (p) (void)hipFree(p);
   if (e != hipSuccess) return fail(c, GCRE_ERR_DEVICE, std::string("gcre_test_expand: ") + hipGetErrorString(e));
+  return GCRE_OK;
+}
+
+// The method-1 inspector (launch_stats_ie) on given row numbers: path i joins row row0[i] of `p0` to row row1[i] of `red`, or,
+// with `zindex`, to row zindex[row1[i]] of it (a hinted join: then excess[n_ranges][W], rows as the host packs them, and range_of[rows of p0]
+// are its range table).  The counts come from the row totals of `red` where the context's knob and the join's size say so (row_counts_for).
+// Out, per path: tot, cases, ctrls, rowz, linfo, key, and the list's entries (padding included) in entries[i * ent_stride ..),
+// the slot's eight followed by the overflow part found through lover; res_out (optional): the kept rows; flags: the flag block.
+int gcre_test_inspect(gcre_ctx* c, const gcre_pathset* p0, const gcre_pathset* red, const uint32_t* row0, const uint32_t* row1,
+                      int64_t count, const int32_t* zindex, int64_t n_zindex, const uint64_t* excess, const int32_t* range_of,
+                      int64_t n_ranges, int64_t over_entries, uint32_t* tot, uint32_t* cases, uint32_t* ctrls, uint32_t* rowz,
+                      uint32_t* linfo, uint64_t* key, uint32_t* entries, int64_t ent_stride, uint64_t* res_out, uint32_t* flags) {
+  if (!c) return GCRE_ERR_ARG;
+  const Geometry& g = c->g;
+  if (!p0 || !red || p0->ctx != c || red->ctx != c || !row0 || !row1 || count <= 0 || count > (1 << 24) || over_entries < 0 ||
+      !tot || !cases || !ctrls || !rowz || !linfo || !key || !entries || ent_stride < 8 || !flags || (zindex && n_zindex <= 0) ||
+      ((excess != nullptr) != (range_of != nullptr)) || (excess && (!zindex || n_ranges <= 0)))
+    return fail(c, GCRE_ERR_ARG, "gcre_test_inspect: bad arguments");
+  if (g.method != 1 || g.Wp > 160) return fail(c, GCRE_ERR_ARG, "gcre_test_inspect: the block-staged method-1 inspector only");
+  if (!c->d_dvt) return fail(c, GCRE_ERR_ARG, "gcre_test_inspect: no value table");
+  for (int64_t i = 0; i < count; i++) {
+    if ((int64_t)row0[i] >= p0->nrows) return fail(c, GCRE_ERR_RANGE, "gcre_test_inspect: paths0 row out of range");
+    if ((row1[i] >> 31) || (int64_t)row1[i] >= (zindex ? n_zindex : red->nrows))
+      return fail(c, GCRE_ERR_RANGE, "gcre_test_inspect: paths1 row out of range");
+    if (zindex && (zindex[row1[i]] < 0 || (int64_t)zindex[row1[i]] >= red->nrows))
+      return fail(c, GCRE_ERR_RANGE, "gcre_test_inspect: reduced row out of range");
+    if (range_of && (range_of[row0[i]] < 0 || (int64_t)range_of[row0[i]] >= n_ranges))
+      return fail(c, GCRE_ERR_RANGE, "gcre_test_inspect: range out of range");
+  }
+  (void)hipSetDevice(c->device);
+  hipStream_t st = c->stream;
+  const size_t n = (size_t)count;
+  const size_t blocks = (n + kStatsIeBlockPaths - 1) / kStatsIeBlockPaths;
+  const size_t over_cap = (size_t)over_entries + (std::min<size_t>((size_t)kInspectMaxBlocks, blocks) * kInspectBlockWaves + 2) * kOverChunk + 16;
+  DevBuf<uint32_t> d0, d1, dtot, dcases, dctrls, drowz, dlinfo, dlover, dslot, dover, dflags;
+  DevBuf<int32_t> dzi, drng;
+  DevBuf<uint64_t> dkey, dex, dres;
+  std::vector<uint32_t> lover(n), slot(n * 8), over;
+  hipError_t e = d0.upload(row0, n, st);
+  if (e == hipSuccess) e = d1.upload(row1, n, st);
+  if (e == hipSuccess && zindex) e = dzi.upload(zindex, (size_t)n_zindex, st);
+  if (e == hipSuccess && excess) e = dex.reserve((size_t)n_ranges * g.S);   // rows of W words from the host, of S on the device
+  if (e == hipSuccess && excess) e = hipMemsetAsync(dex.p, 0, (size_t)n_ranges * g.S * 8, st);
+  if (e == hipSuccess && excess)
+    e = hipMemcpy2DAsync(dex.p, (size_t)g.S * 8, excess, (size_t)g.W * 8, (size_t)g.W * 8, (size_t)n_ranges, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess && excess) e = drng.upload(range_of, (size_t)p0->nrows, st);
+  for (DevBuf<uint32_t>* b : {&dtot, &dcases, &dctrls, &drowz, &dlinfo, &dlover})
+    if (e == hipSuccess) e = b->reserve(n);
+  if (e == hipSuccess) e = dkey.reserve(n);
+  if (e == hipSuccess) e = dslot.reserve(n * 8);
+  if (e == hipSuccess) e = dover.reserve(over_cap);
+  if (e == hipSuccess) e = dflags.reserve(kFlagWords);
+  if (e == hipSuccess && res_out) e = dres.reserve(n * g.S);
+  if (e == hipSuccess) e = hipMemsetAsync(dflags.p, 0, kFlagWords * 4, st);
+  StatsArgs sa{};
+  int rc = GCRE_OK;
+  if (e == hipSuccess) {
+    sa.p0 = p0->d_rows;
+    sa.p1 = red->d_rows;
+    sa.pz = red->d_rows;
+    sa.row0 = d0.p;
+    sa.row1 = d1.p;
+    sa.case_mask = c->d_case_mask;
+    sa.dvt = c->d_dvt;
+    sa.key = dkey.p;
+    sa.tot = dtot.p;
+    sa.cases = dcases.p;
+    sa.ctrls = dctrls.p;
+    sa.res = res_out ? dres.p : nullptr;
+    sa.max_tot = dflags.p;
+    sa.zindex = zindex ? dzi.p : nullptr;
+    sa.excess = excess ? dex.p : nullptr;
+    sa.range_of = excess ? drng.p : nullptr;
+    sa.rowz = drowz.p;
+    sa.bad = dflags.p + kFlagHintBroken;
+    sa.ie_bias = 8;
+    sa.ie_rule = 1;
+    sa.linfo = dlinfo.p;
+    sa.lover = dlover.p;
+    sa.slot = dslot.p;
+    sa.over = dover.p;
+    sa.over_cap = (uint32_t)std::min<size_t>(over_cap - 16, 0xfffffff0u);
+    sa.ov_count = dflags.p + kFlagOverReserved;
+    sa.zoff = (uint32_t)(64 * g.Wp) << 8;
+    sa.first = 0;
+    sa.count = count;
+    sa.S = g.S;
+    sa.Wp = g.Wp;
+    rc = row_counts_for(c, red, count, st, &sa.z_counts);
+  }
+  if (rc == GCRE_OK) {
+    if (e == hipSuccess) e = launch_stats_ie(sa, 1, st);
+    for (auto pr : {std::make_pair(tot, dtot.p), std::make_pair(cases, dcases.p), std::make_pair(ctrls, dctrls.p),
+                    std::make_pair(rowz, drowz.p), std::make_pair(linfo, dlinfo.p), std::make_pair(lover.data(), dlover.p)})
+      if (e == hipSuccess) e = hipMemcpyAsync(pr.first, pr.second, n * 4, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(key, dkey.p, n * 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(slot.data(), dslot.p, n * 32, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(flags, dflags.p, kFlagWords * 4, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && res_out)
+      e = hipMemcpy2DAsync(res_out, (size_t)g.W * 8, dres.p, (size_t)g.S * 8, (size_t)g.W * 8, n, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e == hipSuccess && flags[kFlagOverReserved] > sa.over_cap) rc = fail(c, GCRE_ERR_RANGE, "gcre_test_inspect: the lists need more overflow entries than given");
+    if (e == hipSuccess && rc == GCRE_OK && flags[kFlagOverReserved]) {
+      over.resize(flags[kFlagOverReserved]);
+      e = hipMemcpy(over.data(), dover.p, over.size() * 4, hipMemcpyDeviceToHost);
+    }
+  }
+  for (void* p : {(void*)d0.p, (void*)d1.p, (void*)dtot.p, (void*)dcases.p, (void*)dctrls.p, (void*)drowz.p, (void*)dlinfo.p,
+                  (void*)dlover.p, (void*)dslot.p, (void*)dover.p, (void*)dflags.p, (void*)dzi.p, (void*)drng.p, (void*)dkey.p,
+                  (void*)dex.p, (void*)dres.p})
+    if (p) (void)hipFree(p);
+  if (rc != GCRE_OK) return rc;
+  if (e != hipSuccess) return fail(c, GCRE_ERR_DEVICE, std::string("gcre_test_inspect: ") + hipGetErrorString(e));
+  for (size_t i = 0; i < n; i++) {
+    const uint32_t len8 = linfo_len(linfo[i]);
+    if ((int64_t)len8 > ent_stride) return fail(c, GCRE_ERR_RANGE, "gcre_test_inspect: a list is longer than the room per path");
+    if (len8 > 8 && (size_t)lover[i] + (len8 - 8) > over.size()) return fail(c, GCRE_ERR_DEVICE, "gcre_test_inspect: a list's overflow part lies outside the area");
+    uint32_t* dst = entries + i * (size_t)ent_stride;
+    std::copy(slot.begin() + (long)(i * 8), slot.begin() + (long)(i * 8 + 8), dst);
+    if (len8 > 8) std::copy(over.begin() + lover[i], over.begin() + lover[i] + (len8 - 8), dst + 8);
+  }
   return GCRE_OK;
 }
 

@@ -310,6 +310,50 @@ hipError_t launch_range_union(const uint64_t* p1, const uint64_t* pz, const int3
   return hipGetLastError();
 }
 
+// Row totals of a path set for the inspector's counts (k_stats_ie2<NL, true>): counts[r] = carriers | carriers among the
+// cases << 16 of row r.  A 16-lane group per row and round, 16 bytes per lane, up to five loads of a row in flight (rows
+// of at most 160 words: what the block-staged inspectors take); no LDS, so it runs beside a resident pruned kernel.
+constexpr int kRowCountsMaxBlocks = 1024;
+__global__ __launch_bounds__(256) void k_row_counts(const u64* rows, i64 nrows, int Wp, const u64* case_mask, u32* counts) {
+  typedef u64 __attribute__((ext_vector_type(2))) u64x2;
+  const int lane = threadIdx.x & 63, sl = lane & 15;
+  const i64 ngroups = (i64)gridDim.x * 16;
+  for (i64 r0 = (i64)blockIdx.x * 16 + (threadIdx.x >> 6) * 4; r0 < nrows; r0 += ngroups) {   // (wave-uniform)
+    const i64 r = r0 + (lane >> 4);
+    const bool valid = r < nrows;
+    u64x2 v[5];
+#pragma unroll
+    for (int it = 0; it < 5; it++) {
+      const int k = it * 32 + 2 * sl;
+      v[it] = u64x2{0ull, 0ull};
+      if (valid && k < Wp) v[it] = *(const u64x2*)(rows + (size_t)r * Wp + k);   // Wp is a multiple of 4: k + 1 is inside
+    }
+    u32 c = 0u;
+#pragma unroll
+    for (int it = 0; it < 5; it++) {
+      const int k = it * 32 + 2 * sl;
+      if (k < Wp) {
+        const u64x2 cm = *(const u64x2*)(case_mask + k);
+        c += (u32)__popcll(v[it].x) + (u32)__popcll(v[it].y) +
+             (((u32)__popcll(v[it].x & cm.x) + (u32)__popcll(v[it].y & cm.y)) << 16);
+      }
+    }
+    c = row_total(c, lane);
+    if (valid && sl == 0) counts[r] = c;
+  }
+}
+
+hipError_t launch_row_counts(const uint64_t* rows, int64_t nrows, int Wp, const uint64_t* case_mask, uint32_t* counts,
+                             hipStream_t stream) {
+  if (nrows == 0) return hipSuccess;
+  if (Wp > 160 || (Wp & 3)) return hipErrorInvalidValue;
+  const i64 blocks = (nrows + 15) / 16;
+  const i64 grid = blocks < kRowCountsMaxBlocks ? blocks : kRowCountsMaxBlocks;
+  trace_launch("k_row_counts", blocks, grid);
+  hipLaunchKernelGGL(k_row_counts, dim3((unsigned)grid), dim3(256), 0, stream, rows, nrows, Wp, case_mask, counts);
+  return hipGetLastError();
+}
+
 // ------------------------------------------------------------------------------------------------
 // The method-1 inspector, block-staged form.  Same outputs as k_stats_ie<1>, bit for bit, but organised around what
 // bounded that kernel: not its ~110 VALU instructions per path but its ~7.5 vector-memory instructions per path (the CU's
@@ -323,7 +367,16 @@ hipError_t launch_range_union(const uint64_t* p1, const uint64_t* pz, const int3
 // 122 VGPRs with one set of row registers (below): four waves per SIMD without a spill; 6.0 against 6.7 ms per pass at
 // three.  Five (96 VGPRs, 27 spilled, the pair buffer flushed in chunks to fit the LDS): 8.1 ms
 constexpr int kStatsWaves = 4;
-template <int NL>
+// CNT: the counts of the joined row from row totals instead of from its words (a.z_counts is set).  A join adds one short
+// row z to a row x whose counts are known, with ov = popc(x & z):
+//   carriers   popc(x | z)        = tot(x) + tot(z) - ov
+//   cases      popc((x | z) & cm) = cases(x) + cases(z) - popc(x & z & cm)
+//   delta      popc(z & ~x)       = tot(z) - ov
+// tot(z) | cases(z) << 16 is read per reduced row (k_row_counts wrote it once per path set), tot(x) | cases(x) << 16 is
+// counted when a group moves on to another paths0 row, and the words of x & z that are not zero -- a handful -- are what the
+// list pass collects anyway: each lane counts one collected word.  Four 64-bit popcounts per word and lane less; integers,
+// so the outputs are the same bit for bit.
+template <int NL, bool CNT>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NL <= 3 ? kStatsWaves : 2))) void k_stats_ie2(const StatsArgs a) {
   typedef u64 __attribute__((ext_vector_type(2))) u64x2;
   constexpr u32 kNoRange = 0xffffffffu;
@@ -384,6 +437,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NL <= 3 ? k
 #pragma unroll
     for (int it = 0; it < NL; it++) xw[it][0] = xw[it][1] = zw[it][0] = zw[it][1] = 0ull;
     u32 n_rz = 0u, n_rng = kNoRange, n_r0 = 0xffffffffu;
+    // CNT: the reduced row's totals, asked for a round ahead like its words; whether the round starts on another paths0 row;
+    // that row's totals, kept while the group stays on it
+    u32 n_zc = 0u, x_cnt = 0u;
+    bool n_newx = false;
     auto fetch_rows = [&](int it4n) {
       const int pln = it4n * 4 + grp;
       const u32 r0n = meta[0][pln];
@@ -391,6 +448,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NL <= 3 ? k
       n_rng = meta[2][pln];
       const bool new_x = r0n != n_r0;
       n_r0 = r0n;
+      if constexpr (CNT) {
+        n_newx = new_x;
+        n_zc = a.z_counts[n_rz];
+      }
       const u64* xn = a.p0 + (size_t)r0n * a.S;
       const u64* zn = a.pz + (size_t)n_rz * a.S;
 #pragma unroll
@@ -414,55 +475,150 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NL <= 3 ? k
       const u32 rz = n_rz, rng = n_rng;
       const u64* uu = (rng != kNoRange) ? a.excess + (size_t)rng * a.S : nullptr;
       u64* out = (a.res && active) ? a.res + (size_t)(a.first + base + pl) * a.S : nullptr;
-      u32 cc = 0u, dv = 0u;
-      u64 stray = 0;
+      u32 inc, tot, inm, mode, len, npair = 0u;
+      if constexpr (CNT) {
+        // ---- the hint check, in the rounds where some group starts a uid; the kept row ----
+        if (__builtin_amdgcn_ballot_w64(rng != kNoRange) != 0ull) {
+          u64 stray = 0;
 #pragma unroll
-      for (int it = 0; it < NL; it++) {
-        const int k = it * 32 + 2 * sl;
-        u64x2 uv = {0, 0};
-        if (k < Wp && uu) uv = *(const u64x2*)(uu + k);
-        const u64x2 cmv = *(const u64x2*)(cm_lds + k);
-        const u64 cme[2] = {cmv.x, cmv.y};
-#pragma unroll
-        for (int e = 0; e < 2; e++) {
-          const u64 xk = xw[it][e], zk = zw[it][e], uk = e ? uv.y : uv.x;
-          stray |= uk & ~xk;
-          const u64 j = xk | zk;
-          cc += (u32)__popcll(j & cme[e]) | ((u32)__popcll(j) << 16);
-          dv += (u32)__popcll(zk & ~xk) | ((u32)__popcll(zk) << 16);
-        }
-        if (out && k < Wp) *(u64x2*)(out + k) = u64x2{xw[it][0] | zw[it][0], xw[it][1] | zw[it][1]};
-      }
-      if (stray) my_bad = true;
-      const u32 c = row_total(cc, lane), d = row_total(dv, lane);
-      const u32 inc = c & 0xffffu, tot = c >> 16, inm = tot - inc;
-      const u32 dl = d & 0xffffu, ov = (d >> 16) - dl;
-      const u32 mode = a.ie_rule ? ((ov <= 8u || ov < dl) ? 1u : 0u) : ((a.ie_bias >= 0 && ov + (u32)a.ie_bias < dl) ? 1u : 0u);
-      const u32 len = mode ? ov : dl;
-      const u32 len8 = max(8u, (len + 7u) & ~7u);
-      // The list's bits are few and scattered -- three overlapping patients among a path's 96 lane-words -- so a loop per
-      // word runs its body for one lane at a time.  Instead the non-zero words are first collected per group (word, its
-      // index; positions from a ballot), then every lane takes one collected word and all of them give up a bit per round:
-      // two rounds instead of eight bodies.  Entries come out in collection order, not ascending (the list is a set).
-      u32 npair = 0u;
-#pragma unroll
-      for (int it = 0; it < NL; it++) {
-#pragma unroll
-        for (int e = 0; e < 2; e++) {
-          const u64 w = mode ? (zw[it][e] & xw[it][e]) : (zw[it][e] & ~xw[it][e]);
-          const bool nz = active && w != 0;
-          const u64 bal = __builtin_amdgcn_ballot_w64(nz);
-          if (bal == 0ull) continue;
-          const u32 m = (u32)(bal >> gsh) & 0xffffu;
-          const u32 at = npair + (u32)__builtin_popcount(m & ltm);
-          if (nz) {
-            pairs[0][at] = (u32)w;
-            pairs[1][at] = (u32)(w >> 32);
-            pairs[2][at] = (u32)(it * 32 + 2 * sl + e);
+          for (int it = 0; it < NL; it++) {
+            const int k = it * 32 + 2 * sl;
+            u64x2 uv = {0, 0};
+            if (k < Wp && uu) uv = *(const u64x2*)(uu + k);
+            stray |= (uv.x & ~xw[it][0]) | (uv.y & ~xw[it][1]);
           }
-          npair += (u32)__builtin_popcount(m);
+          if (stray) my_bad = true;
+        }
+        if (out) {
+#pragma unroll
+          for (int it = 0; it < NL; it++) {
+            const int k = it * 32 + 2 * sl;
+            if (k < Wp) *(u64x2*)(out + k) = u64x2{xw[it][0] | zw[it][0], xw[it][1] | zw[it][1]};
+          }
+        }
+        // ---- the paths0 row's totals, when the group has moved on to another row ----
+        if (n_newx) {
+          u32 xc = 0u;
+#pragma unroll
+          for (int it = 0; it < NL; it++) {
+            const u64x2 cmv = *(const u64x2*)(cm_lds + it * 32 + 2 * sl);
+            xc += (u32)__popcll(xw[it][0]) + (u32)__popcll(xw[it][1]) +
+                  (((u32)__popcll(xw[it][0] & cmv.x) + (u32)__popcll(xw[it][1] & cmv.y)) << 16);
+          }
+          x_cnt = row_total(xc, lane);
+        }
+        const u32 zc = n_zc;
+        // ---- the words of x & z that are not zero, collected per group as the list pass wants them (below) ----
+#pragma unroll
+        for (int it = 0; it < NL; it++) {
+#pragma unroll
+          for (int e = 0; e < 2; e++) {
+            const u64 w = zw[it][e] & xw[it][e];
+            const bool nz = active && w != 0;
+            const u64 bal = __builtin_amdgcn_ballot_w64(nz);
+            if (bal == 0ull) continue;
+            const u32 m = (u32)(bal >> gsh) & 0xffffu;
+            const u32 at = npair + (u32)__builtin_popcount(m & ltm);
+            if (nz) {
+              pairs[0][at] = (u32)w;
+              pairs[1][at] = (u32)(w >> 32);
+              pairs[2][at] = (u32)(it * 32 + 2 * sl + e);
+            }
+            npair += (u32)__builtin_popcount(m);
+          }
+        }
+        __builtin_amdgcn_wave_barrier();
+        // ---- overlap | overlap among the cases << 16: every lane counts one collected word ----
+        u32 ovc = 0u;
+        {
+          const u32 npmax = max(max(rdlane(npair, 0), rdlane(npair, 16)), max(rdlane(npair, 32), rdlane(npair, 48)));
+          for (u32 p0 = 0u; p0 < npmax; p0 += 16u) {
+            const u32 pi = p0 + (u32)sl;
+            const bool has = pi < npair;
+            const u64 w = has ? ((u64)pairs[1][pi] << 32) | (u64)pairs[0][pi] : 0ull;
+            const u32 k = has ? pairs[2][pi] : 0u;
+            ovc += (u32)__popcll(w) | ((u32)__popcll(w & cm_lds[k]) << 16);
+          }
+          if (npmax != 0u) ovc = row_total(ovc, lane);
+        }
+        const u32 c = x_cnt + zc - ovc;                     // (no borrow: each half of ovc is at most that half of zc)
+        tot = c & 0xffffu, inc = c >> 16, inm = tot - inc;
+        const u32 ov = ovc & 0xffffu, dl = (zc & 0xffffu) - ov;
+        mode = a.ie_rule ? ((ov <= 8u || ov < dl) ? 1u : 0u) : ((a.ie_bias >= 0 && ov + (u32)a.ie_bias < dl) ? 1u : 0u);
+        len = mode ? ov : dl;
+        // ---- a delta list (rare: an overlap above 8 and not below the delta): the group collects z & ~x instead ----
+        const bool delta = active && mode == 0u;
+        if (__builtin_amdgcn_ballot_w64(delta) != 0ull) {
+          if (delta) npair = 0u;
+#pragma unroll
+          for (int it = 0; it < NL; it++) {
+#pragma unroll
+            for (int e = 0; e < 2; e++) {
+              const u64 w = zw[it][e] & ~xw[it][e];
+              const bool nz = delta && w != 0;
+              const u64 bal = __builtin_amdgcn_ballot_w64(nz);
+              if (bal == 0ull) continue;
+              const u32 m = (u32)(bal >> gsh) & 0xffffu;
+              const u32 at = npair + (u32)__builtin_popcount(m & ltm);
+              if (nz) {
+                pairs[0][at] = (u32)w;
+                pairs[1][at] = (u32)(w >> 32);
+                pairs[2][at] = (u32)(it * 32 + 2 * sl + e);
+              }
+              npair += (u32)__builtin_popcount(m);
+            }
+          }
+        }
+      } else {
+        u32 cc = 0u, dv = 0u;
+        u64 stray = 0;
+#pragma unroll
+        for (int it = 0; it < NL; it++) {
+          const int k = it * 32 + 2 * sl;
+          u64x2 uv = {0, 0};
+          if (k < Wp && uu) uv = *(const u64x2*)(uu + k);
+          const u64x2 cmv = *(const u64x2*)(cm_lds + k);
+          const u64 cme[2] = {cmv.x, cmv.y};
+#pragma unroll
+          for (int e = 0; e < 2; e++) {
+            const u64 xk = xw[it][e], zk = zw[it][e], uk = e ? uv.y : uv.x;
+            stray |= uk & ~xk;
+            const u64 j = xk | zk;
+            cc += (u32)__popcll(j & cme[e]) | ((u32)__popcll(j) << 16);
+            dv += (u32)__popcll(zk & ~xk) | ((u32)__popcll(zk) << 16);
+          }
+          if (out && k < Wp) *(u64x2*)(out + k) = u64x2{xw[it][0] | zw[it][0], xw[it][1] | zw[it][1]};
+        }
+        if (stray) my_bad = true;
+        const u32 c = row_total(cc, lane), d = row_total(dv, lane);
+        inc = c & 0xffffu, tot = c >> 16, inm = tot - inc;
+        const u32 dl = d & 0xffffu, ov = (d >> 16) - dl;
+        mode = a.ie_rule ? ((ov <= 8u || ov < dl) ? 1u : 0u) : ((a.ie_bias >= 0 && ov + (u32)a.ie_bias < dl) ? 1u : 0u);
+        len = mode ? ov : dl;
+        // The list's bits are few and scattered -- three overlapping patients among a path's 96 lane-words -- so a loop per
+        // word runs its body for one lane at a time.  Instead the non-zero words are first collected per group (word, its
+        // index; positions from a ballot), then every lane takes one collected word and all of them give up a bit per round:
+        // two rounds instead of eight bodies.  Entries come out in collection order, not ascending (the list is a set).
+#pragma unroll
+        for (int it = 0; it < NL; it++) {
+#pragma unroll
+          for (int e = 0; e < 2; e++) {
+            const u64 w = mode ? (zw[it][e] & xw[it][e]) : (zw[it][e] & ~xw[it][e]);
+            const bool nz = active && w != 0;
+            const u64 bal = __builtin_amdgcn_ballot_w64(nz);
+            if (bal == 0ull) continue;
+            const u32 m = (u32)(bal >> gsh) & 0xffffu;
+            const u32 at = npair + (u32)__builtin_popcount(m & ltm);
+            if (nz) {
+              pairs[0][at] = (u32)w;
+              pairs[1][at] = (u32)(w >> 32);
+              pairs[2][at] = (u32)(it * 32 + 2 * sl + e);
+            }
+            npair += (u32)__builtin_popcount(m);
+          }
         }
       }
+      const u32 len8 = max(8u, (len + 7u) & ~7u);
       fetch_rows(it4 < 15 ? it4 + 1 : 15);   // (changes rz / rng of the NEXT iteration only: this one read them above)
       double score = 0.0;
       if (active && sl == 0) {
@@ -1040,10 +1196,14 @@ static hipError_t launch_staged(const StatsKernel (&kernel)[5], const char* name
 
 hipError_t launch_stats_ie(const StatsArgs& a, int method, hipStream_t stream) {
   if (a.count == 0) return hipSuccess;
-  static const StatsKernel ie2[5] = {k_stats_ie2<1>, k_stats_ie2<2>, k_stats_ie2<3>, k_stats_ie2<4>, k_stats_ie2<5>};
+  static const StatsKernel ie2[5] = {k_stats_ie2<1, false>, k_stats_ie2<2, false>, k_stats_ie2<3, false>, k_stats_ie2<4, false>,
+                                     k_stats_ie2<5, false>};
+  static const StatsKernel ie2c[5] = {k_stats_ie2<1, true>, k_stats_ie2<2, true>, k_stats_ie2<3, true>, k_stats_ie2<4, true>,
+                                      k_stats_ie2<5, true>};
   static const StatsKernel ie2h[5] = {k_stats_ie2h<1>, k_stats_ie2h<2>, k_stats_ie2h<3>, k_stats_ie2h<4>, k_stats_ie2h<5>};
   static const StatsKernel ie2s[5] = {k_stats_ie2s<1>, k_stats_ie2s<2>, k_stats_ie2s<3>, k_stats_ie2s<4>, k_stats_ie2s<5>};
   if (a.Wp <= 160) {
+    if (method == 1 && a.z_counts) return launch_staged(ie2c, "k_stats_ie2", 64, a, stream);   // counts from row totals
     if (method == 1) return launch_staged(ie2, "k_stats_ie2", 64, a, stream);
     // the signed method with one-sided reduced rows: one round per path (k_stats_ie2h); otherwise one per half
     if (a.lz_off) return launch_staged(ie2h, "k_stats_ie2h", 64, a, stream);

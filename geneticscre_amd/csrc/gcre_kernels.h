@@ -273,6 +273,9 @@ struct StatsArgs {
   // k_stats_ie2h (method 2): CSR offsets of the reduced operand's bit lists (two per row), set only when every row of it
   // has an empty half
   const uint64_t* lz_off;
+  // k_stats_ie2 (method 1): carriers | carriers among the cases << 16 of every row of the reduced operand (k_row_counts), or
+  // nullptr: the inspector counts the joined row's words itself
+  const uint32_t* z_counts;
   int64_t first;
   int64_t count;
   int S;
@@ -288,6 +291,9 @@ constexpr int kInspectMaxBlocks = 256 * 16;
 constexpr int kStatsIeBlockPaths = 4 * kInspectBlockWaves;   // k_stats_ie: four paths per wave and pass, the most waves per path
 hipError_t launch_stats(const StatsArgs& a, int method, hipStream_t stream);
 hipError_t launch_stats_ie(const StatsArgs& a, int method, hipStream_t stream);   // gcre_inspect.hip
+// counts[r] = carriers | carriers among the cases << 16 of row r (rows of Wp words, 64 * Wp < 65536: both fit 16 bits)
+hipError_t launch_row_counts(const uint64_t* rows, int64_t nrows, int Wp, const uint64_t* case_mask, uint32_t* counts,
+                             hipStream_t stream);
 // The range check of a hinted join walks each distinct uid range -- `rows` consecutive paths1 rows from `first` -- once.  A
 // range of more than kRangePieceRows rows (a hub gene's) is cut into pieces of that many (the last one shorter), marked by
 // bit 31 of `rows`; `cut` lists the ranges that were cut.  16 rows: what one wave of k_range_union reads in a single round

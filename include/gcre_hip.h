@@ -338,6 +338,17 @@ int gcre_test_range_union(gcre_ctx* ctx, const uint64_t* p1, int64_t n1, const u
                           uint32_t* bad_out, int32_t* piece_rows_out);
 int gcre_test_expand(gcre_ctx* ctx, const int64_t* path_idx, const int64_t* location, int64_t n_uids, const int32_t* signs,
                      int64_t n_signs, int path_length, int method, int64_t first, int64_t count, uint32_t* row0, uint32_t* row1);
+/* Tests only: the method-1 inspector of the inclusion-exclusion form on given row numbers.  Path i joins row row0[i] of p0 to
+ * row row1[i] of red, or, with zindex[n_zindex], to row zindex[row1[i]] of it (a hinted join; then excess[n_ranges * vlen] and
+ * range_of[rows of p0] are its range table, or both NULL).  The counts come from the row totals of red where
+ * GCRE_STATS_IE_COUNTS (default 1) and the sizes say so: red has no more rows than there are paths.  over_entries: room for
+ * the lists' parts beyond 8 entries.  Out, per path: tot, cases, ctrls, rowz, linfo, key, and entries[i * ent_stride ..): the
+ * list, padding included (its padded length: linfo & 0x0ffffff8); res_out (or NULL): the joined rows; flags[8]: the
+ * inspector's flag block (largest total, hint broken, overlap lists, -, overflow entries reserved, longest list). */
+int gcre_test_inspect(gcre_ctx* ctx, const gcre_pathset* p0, const gcre_pathset* red, const uint32_t* row0, const uint32_t* row1,
+                      int64_t count, const int32_t* zindex, int64_t n_zindex, const uint64_t* excess, const int32_t* range_of,
+                      int64_t n_ranges, int64_t over_entries, uint32_t* tot, uint32_t* cases, uint32_t* ctrls, uint32_t* rowz,
+                      uint32_t* linfo, uint64_t* key, uint32_t* entries, int64_t ent_stride, uint64_t* res_out, uint32_t* flags);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Decorated p-values (getDecoratedPvalues / computeDecoratedPvalue, R/DecoratedPvalue.R:48-304; GWASPA's second table,
