@@ -2013,6 +2013,8 @@ FDR_COLUMNS = ["ExpectedFalse", "FDR", "Qvalues"]
 def _vt_cell(VT, n, a, b):
     """VT[a][b] as the device reads its copy of the value table: -1 outside the caller's table and beyond n patients."""
     a, b = np.asarray(a, np.int64), np.asarray(b, np.int64)
+    if VT.size == 0:                                       # a table without a cell: everything is outside
+        return np.full(np.broadcast(a, b).shape, -1.0)
     ok = (a >= 0) & (b >= 0) & (a <= n) & (b <= n) & (a < VT.shape[0]) & (b < VT.shape[1])
     return np.where(ok, VT[np.clip(a, 0, VT.shape[0] - 1), np.clip(b, 0, VT.shape[1] - 1)], -1.0)
 

@@ -176,6 +176,80 @@ WIDE_TABLE_CASES = {
 }
 
 
+# ---- the table families through the sequential entries (tests/test_seq_tables_host.py, tests/test_gpu_seq_tables.py) ------
+# The inputs are those of tests/test_gpu_sequential.py (make_input, 70 + 61 patients, one stratum, permutation seed 11, 5
+# hits, at most 3,000 permutations); the table is special_table(family, ..., seed, variant), for the family "shapes"
+# shape_tables(..., seed)[SEQ_SHAPE_NAMES[variant]].  "huge+hi" / "huge+mid" are the huge table with one planted cell under
+# the observed counts of set 3: a finite score beyond FLT_OVERFLOW, and one between FLT_MAX and FLT_OVERFLOW.
+SEQ_SHAPE_NAMES = ("0x0", "1x1", "few_rows", "few_cols", "few_both", "larger", "square")
+SEQ_PLANTED = {"huge+hi": 3.5e38, "huge+mid": FLT_MAX + 2.0 ** 102}
+SEQ_ENTRIES = ("sequential", "weighted", "prefix", "dose")
+# (entry, family, method) -> [(table seed, variant, trial of make_input, max_perms)]: found on the CPU by
+# tools/seq_table_seeds.py so that the numpy definitions alone meet what tests/test_seq_tables_host.py asks of every case
+_SHAPE_SPECS = [(0, v, 0, 3000) for v in range(len(SEQ_SHAPE_NAMES))]
+SEQ_TABLE_CASES = {
+    ("sequential", "zeros", 1): [(0, 0, 0, 3000)],
+    ("sequential", "zeros", 2): [(1, 0, 0, 1562)],
+    ("sequential", "nonfinite", 1): [(0, 0, 0, 3000), (0, 1, 0, 3000), (0, 2, 0, 3000)],
+    ("sequential", "nonfinite", 2): [(1, 0, 0, 3000), (0, 1, 0, 3000), (0, 2, 0, 3000), (0, 3, 0, 3000), (0, 4, 0, 3000),
+                                     (0, 5, 0, 3000)],
+    ("sequential", "tiny", 1): [(0, 0, 0, 3000)],
+    ("sequential", "tiny", 2): [(2, 0, 1, 3000)],
+    ("sequential", "huge", 1): [(0, 0, 0, 3000), (3, 1, 0, 3000)],
+    ("sequential", "huge", 2): [(0, 0, 0, 3000), (5, 1, 7, 3000)],
+    ("sequential", "huge+hi", 1): [(0, 0, 0, 3000)],
+    ("sequential", "huge+hi", 2): [(0, 0, 0, 3000)],
+    ("sequential", "huge+mid", 1): [(0, 1, 0, 3000)],
+    ("sequential", "huge+mid", 2): [(0, 1, 0, 3000)],
+    ("sequential", "ladder", 1): [(1, 0, 0, 3000), (0, 1, 0, 3000)],
+    ("sequential", "ladder", 2): [(3, 0, 0, 3000), (5, 1, 1, 3000)],
+    ("sequential", "shapes", 1): _SHAPE_SPECS,
+    ("sequential", "shapes", 2): _SHAPE_SPECS,
+    ("weighted", "zeros", 1): [(0, 0, 0, 1137)],
+    ("weighted", "zeros", 2): [(1, 0, 0, 3000)],
+    ("weighted", "nonfinite", 1): [(0, 2, 0, 3000)],
+    ("weighted", "nonfinite", 2): [(0, 2, 0, 3000)],
+    ("weighted", "huge", 1): [(3, 1, 0, 3000)],
+    ("weighted", "huge", 2): [(1, 1, 65, 3000)],
+    ("weighted", "shapes", 1): [(0, 4, 0, 3000)],
+    ("weighted", "shapes", 2): [(0, 4, 0, 3000)],
+    ("prefix", "zeros", 1): [(1, 0, 1, 3000)],
+    ("prefix", "zeros", 2): [(2, 0, 0, 3000)],
+    ("prefix", "nonfinite", 1): [(0, 0, 0, 3000), (0, 1, 1, 3000), (4, 2, 0, 3000)],
+    ("prefix", "nonfinite", 2): [(1, 0, 0, 3000), (4, 1, 1, 736), (2, 2, 0, 3000), (0, 3, 0, 3000), (4, 4, 0, 3000),
+                                 (2, 5, 0, 3000)],
+    ("prefix", "tiny", 1): [(0, 0, 0, 3000)],
+    ("prefix", "tiny", 2): [(2, 0, 0, 3000)],
+    ("prefix", "huge", 1): [(0, 0, 0, 3000), (0, 1, 0, 3000)],
+    ("prefix", "huge", 2): [(0, 0, 0, 3000), (0, 1, 0, 3000)],
+    ("prefix", "huge+hi", 1): [(0, 0, 0, 3000)],
+    ("prefix", "huge+hi", 2): [(0, 0, 0, 3000)],
+    ("prefix", "huge+mid", 1): [(0, 1, 0, 3000)],
+    ("prefix", "huge+mid", 2): [(0, 1, 0, 3000)],
+    ("prefix", "ladder", 1): [(1, 0, 0, 3000), (0, 1, 0, 3000)],
+    ("prefix", "ladder", 2): [(3, 0, 0, 3000), (1, 1, 0, 3000)],
+    ("prefix", "shapes", 1): _SHAPE_SPECS,
+    ("prefix", "shapes", 2): _SHAPE_SPECS,
+    ("dose", "zeros", 1): [(1, 0, 0, 3000)],
+    ("dose", "zeros", 2): [(2, 0, 0, 3000)],
+    ("dose", "nonfinite", 1): [(0, 0, 0, 1662), (0, 1, 0, 3000), (0, 2, 0, 3000)],
+    ("dose", "nonfinite", 2): [(1, 0, 0, 3000), (0, 1, 0, 3000), (3, 2, 1, 3000), (1, 3, 0, 3000), (0, 4, 0, 3000),
+                               (0, 5, 0, 3000)],
+    ("dose", "tiny", 1): [(0, 0, 0, 3000)],
+    ("dose", "tiny", 2): [(2, 0, 1, 3000)],
+    ("dose", "huge", 1): [(0, 0, 0, 3000), (1, 1, 0, 3000)],
+    ("dose", "huge", 2): [(0, 0, 0, 3000), (1, 1, 0, 3000)],
+    ("dose", "huge+hi", 1): [(0, 0, 0, 3000)],
+    ("dose", "huge+hi", 2): [(0, 0, 0, 3000)],
+    ("dose", "huge+mid", 1): [(0, 1, 0, 3000)],
+    ("dose", "huge+mid", 2): [(0, 1, 0, 3000)],
+    ("dose", "ladder", 1): [(1, 0, 0, 3000), (4, 1, 0, 3000)],
+    ("dose", "ladder", 2): [(3, 0, 0, 3000), (1, 1, 0, 3000)],
+    ("dose", "shapes", 1): _SHAPE_SPECS[:3] + [(0, 3, 5, 3000)] + _SHAPE_SPECS[4:],
+    ("dose", "shapes", 2): _SHAPE_SPECS,
+}
+
+
 def table_problem(kind: str, size: str, method: str, top_k: int = 3000, table=None, case=None) -> Problem:
     """The problem of a table test.  ``case`` = (seed, variant): the table is special_table(kind, ..., seed, variant) unless
     ``table`` is given, and the network is drawn from the same seed; by default the case TABLE_CASES / WIDE_TABLE_CASES name."""

@@ -111,6 +111,61 @@ def random_case(seed, method):
     return nc, nt, data, paths, signs, small_table(nc, nt, seed)
 
 
+# ---- the special-value tables (tests/helpers.py) under the splits of random_case ----------------------------------------------
+TABLE_KINDS = ("zeros", "nonfinite", "tiny", "huge", "ladder", "few_both")
+TABLE_PERMS = 300
+# (kind, method) -> (seed of random_case, seed and variant of the table): found on the CPU so that the observed values of the
+# transcription alone hold what test_special_tables_hold_every_kind_of_observed_value asks
+TABLE_CASES = {
+    ("zeros", 1): (0, 0, 0), ("nonfinite", 1): (39, 3, 2), ("tiny", 1): (0, 0, 0), ("huge", 1): (0, 0, 0), ("ladder", 1): (0, 0, 0),
+    ("few_both", 1): (0, 0, 0),
+    ("zeros", 2): (0, 0, 0), ("nonfinite", 2): (0, 1, 2), ("tiny", 2): (0, 0, 0), ("huge", 2): (0, 0, 0), ("ladder", 2): (0, 0, 0),
+    ("few_both", 2): (0, 0, 0),
+}
+
+
+def table_case(kind, method):
+    """(nc, nt, data, paths, signs, VT): the splits of ``random_case`` on a table of the family ``kind``."""
+    from helpers import shape_tables, special_table
+    seed, tseed, variant = TABLE_CASES[(kind, method)]
+    nc, nt, data, paths, signs, _ = random_case(seed, method)
+    if kind == "few_both":
+        VT = dict((name, tb) for name, tb, _ in shape_tables(nc, nt, tseed))["few_both"]
+    else:
+        VT = special_table(kind, nc, nt, tseed, variant)
+    return nc, nt, data, paths, signs, VT
+
+
+def table_strata(nc, nt):
+    return (np.arange(nc + nt) * 7 % 3).astype(np.int32)
+
+
+def observed_kinds(scores):
+    """Which special values the observed scores of a list of splits hold."""
+    s = np.asarray(scores, np.float64)
+    tiny = float(np.finfo(np.float32).tiny)
+    return {"NaN": bool(np.isnan(s).any()), "+0": bool(((s == 0) & ~np.signbit(s)).any()), "-0": bool(((s == 0) & np.signbit(s)).any()),
+            "+inf": bool(np.isposinf(s).any()), "-inf": bool(np.isneginf(s).any()), "denormal": bool(((s > 0) & (s < tiny)).any()),
+            "negative": bool(((s < 0) & np.isfinite(s)).any())}
+
+
+def table_expectation(kind, method, stratified, seed=99):
+    """What the device must return for a table case, from the transcription, the host stage and the restated sampler:
+    (host records, their strata, urn counts [splits][K][2], n_ge [splits], exact ties [splits])."""
+    from test_gpu_decorated import perm_scores, restated_counts
+    nc, nt, data, paths, signs, VT = table_case(kind, method)
+    strata = table_strata(nc, nt) if stratified else None
+    host, st = api.decorated_splits(method, nc, nt, paths, data, signs, VT, strata)
+    counts = restated_counts(host, st, seed, TABLE_PERMS)
+    n_ge, ties = np.zeros(len(host), np.int64), np.zeros(len(host), np.int64)
+    with np.errstate(invalid="ignore"):
+        for s, r in enumerate(host):
+            if r["valid"]:
+                ps = perm_scores(r, counts[s, :, 0], counts[s, :, 1], method, VT)
+                n_ge[s], ties[s] = int((ps >= r["score"]).sum()), int((ps == r["score"]).sum())
+    return host, st, counts, n_ge, ties
+
+
 def assert_same(got, want, strata_got=None):
     assert len(got) == len(want)
     for i, (g, w) in enumerate(zip(got, want)):
@@ -296,3 +351,43 @@ def test_decorated_table_edge_cases():
         warnings.simplefilter("always")
         assert report.decorated_table(only1, genes, data, 4, 6, False, 100, path_length=1) is None
     assert [str(x.message) for x in w] == ["Can only compute the Decorated P-values for pathLength > 1!"]
+
+
+TABLE_ASKS = {"zeros": ("+0", "-0", "negative"), "nonfinite": ("NaN", "-inf", "+inf"), "tiny": ("denormal",), "huge": (),
+              "ladder": (), "few_both": ("negative",)}
+
+
+def table_case_holds(kind, method):
+    """(the kinds of observed value the case's splits hold, per stratification whether a drawing split has a permutation that
+    ties its observed value exactly while others do not); the host stage equals the transcription on the way."""
+    nc, nt, data, paths, signs, VT = table_case(kind, method)
+    kinds, tie = None, {}
+    for stratified in (False, True):
+        strata = table_strata(nc, nt) if stratified else None
+        want = r_decorated_splits(data, paths, signs, nc, nt, method, VT, strata)
+        host, st, counts, n_ge, ties = table_expectation(kind, method, stratified)
+        assert_same(host, want, st)
+        kinds = observed_kinds([w["score"] for w in want if w["valid"]])
+        draws = (host["k_pos"] + host["k_neg"] > 0) & (host["valid"] != 0)
+        tie[stratified] = bool((draws & (ties > 0) & (ties < TABLE_PERMS)).any())
+        nan = (host["valid"] != 0) & np.isnan(host["score"])
+        assert (n_ge[nan] == 0).all()               # R/DecoratedPvalue.R:290: which(scores >= NaN) is empty
+    return kinds, tie
+
+
+@pytest.mark.parametrize("method", [1, 2])
+def test_special_tables_hold_every_kind_of_observed_value(method):
+    """What tests/test_gpu_decorated.py::test_special_tables needs of its inputs, on the transcription and the restated
+    sampler alone: observed values of NaN, both zeros, both infinities and an f32 denormal, the -1 padding of a short
+    table, and with and without strata a split with a permutation that ties its observed value exactly."""
+    union, tie = {}, {False: False, True: False}
+    for kind in TABLE_KINDS:
+        kinds, t = table_case_holds(kind, method)
+        missing = [k for k in TABLE_ASKS[kind] if not kinds[k]]
+        assert not missing, (kind, method, missing)
+        for k, v in kinds.items():
+            union[k] = union.get(k, False) or v
+        for k in tie:
+            tie[k] |= t[k]
+    assert all(union.values()), union
+    assert all(tie.values()), tie

@@ -134,6 +134,52 @@ def test_device_draws_match_restatement(method, stratified):
     ex.close()
 
 
+@pytest.mark.parametrize("stratified", [False, True])
+@pytest.mark.parametrize("method", [1, 2])
+def test_special_tables(method, stratified):
+    """The table families of tests/helpers.py and a table shorter than the cohort both ways: k_decorated_observed and
+    k_decorated_null read the raw table in f64 and count ``ps >= o``.  On the transcription alone the splits hold observed
+    values of NaN, both zeros, both infinities and an f32 denormal, and a split with a permutation that ties its observed
+    value exactly (asserted again here; tests/test_decorated_host.py holds it without a GPU).  The observed scores equal
+    r_decorated_splits' bit for bit, the urn counts and n_ge the restatement's.  A NaN observed value is reached by no
+    permutation, as in R (DecoratedPvalue.R:290, ``which(scores >= score)`` is empty): n_ge = 0, and the p-value is n_ge / K
+    like every other."""
+    from test_decorated_host import TABLE_KINDS, TABLE_PERMS, observed_kinds, table_case, table_expectation, table_strata
+    union, tie = {}, False
+    for kind in TABLE_KINDS:
+        nc, nt, data, paths, signs, VT = table_case(kind, method)
+        strata = table_strata(nc, nt) if stratified else None
+        want = r_decorated_splits(data, paths, signs, nc, nt, method, VT, strata)
+        host, st, counts_want, n_ge, ties = table_expectation(kind, method, stratified)
+        valid = host["valid"] != 0
+        assert [w["valid"] for w in want] == valid.astype(int).tolist()
+        for k, v in observed_kinds([w["score"] for w in want if w["valid"]]).items():
+            union[k] = union.get(k, False) or v
+        tie |= bool((valid & (host["k_pos"] + host["k_neg"] > 0) & (ties > 0) & (ties < TABLE_PERMS)).any())
+        ex = api.JoinExec(method, nc, nt, TABLE_PERMS)
+        try:
+            ex.set_value_table(VT)
+            rec, counts = ex.decorated_pvalues(paths, data, signs, strata=strata, seed=99, return_counts=True)
+        finally:
+            ex.close()
+        assert len(rec) == len(want)
+        for s, w in enumerate(want):
+            if not w["valid"]:
+                assert np.isnan(rec[s]["score"]) and np.isnan(rec[s]["pvalue"])
+                continue
+            ws, gs = np.float64(w["score"]), np.float64(rec[s]["score"])
+            assert (np.isnan(ws) and np.isnan(gs)) or ws.view(np.uint64) == gs.view(np.uint64), (kind, s, gs, ws)
+            assert int(rec[s]["n_ge"]) == n_ge[s], (kind, s)
+            assert rec[s]["pvalue"] == n_ge[s] / TABLE_PERMS, (kind, s)
+            if np.isnan(ws):
+                assert int(rec[s]["n_ge"]) == 0
+        np.testing.assert_array_equal(counts, counts_want, err_msg=kind)
+        for f in ("path", "direction", "j", "cases1", "ctrls1", "cases2", "ctrls2", "k_pos", "k_neg"):
+            np.testing.assert_array_equal(rec[f], host[f], err_msg=f"{kind} {f}")
+    assert all(union.values()), union
+    assert tie
+
+
 def test_device_errors():
     nc, nt, data, paths, signs, VT = random_case(9, 1)
     ex = api.JoinExec(1, nc, nt, 10)

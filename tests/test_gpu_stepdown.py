@@ -216,6 +216,29 @@ def test_thresholds_in_any_order(method):
         np.testing.assert_array_equal(got[name], reference(cpu, name, top_rows(cpu, name))["n_ge"][perms[name]])
 
 
+# ---- 4b. the special-value tables ---------------------------------------------------------------------------------------
+
+
+@pytest.mark.parametrize("method", ["method1", "method2"])
+@pytest.mark.parametrize("kind", ["zeros", "nonfinite", "tiny", "huge", "ladder"])
+def test_stepdown_on_special_tables(kind, method):
+    """The table families of tests/helpers.py at 70 patients (what the problems must hold -- tied scores, both zeros among the
+    top rows, a row below its single-step count, non-finite top scores left out -- is asserted on the CPU in
+    tests/test_seq_tables_host.py).  gcre_exceed_stepdown refuses a set whose score is not its threshold bit for bit: under
+    signed zeros, denormals and sums that overflow f32 the join's score and the set's must still be one pattern, so no call
+    may be refused."""
+    from test_seq_tables_host import STEPDOWN_FAMILIES, stepdown_problem
+    assert kind in STEPDOWN_FAMILIES
+    cpu = stepdown_problem(kind, method)
+    tops = {name: top_rows(cpu, name) for name in LEVELS}
+    tops = {name: top for name, top in tops.items() if len(top[2])}
+    assert tops
+    try:
+        one_call(cpu.p, cpu, tops, what=f"{kind} {method}")
+    except api.GcreError as e:
+        pytest.fail(f"{kind} {method}: a call was refused: {e}")
+
+
 # ---- 5. refusals -----------------------------------------------------------------------------------------------------
 
 
