@@ -730,6 +730,22 @@ def _set_lists(sets, signs):
     return len(off) - 1, off, members, sg
 
 
+def _prefix_cuts(sets, cuts, S, off, members):
+    """``cuts`` of ``prefix_tests`` as uint8 flags [members], or None for None: it follows the signs of ``_set_lists`` -- one
+    sequence per set, or one flat array beside an ``(off, members)`` pair.  ValueError where it does not match the members."""
+    if cuts is None:
+        return None
+    if isinstance(sets, tuple) and len(sets) == 2 and isinstance(sets[0], np.ndarray):
+        ct = np.asarray(cuts).reshape(-1)
+        matching = len(ct) == len(members)
+    else:
+        matching = len(cuts) == S and all(len(x) == L for x, L in zip(cuts, np.diff(off)))
+        ct = np.concatenate([np.asarray(x).reshape(-1) for x in cuts]) if matching and S else np.zeros(0)
+    if not matching:
+        raise ValueError("cuts: one flag per member of every set")
+    return np.ascontiguousarray(ct != 0, dtype=np.uint8)
+
+
 def _dose_levels(levels) -> np.ndarray:
     """``levels`` of ``dose_tests`` as int32: 1 to 15 strictly ascending integers in 1 .. 15, or ValueError."""
     a = np.asarray(levels)
@@ -1232,17 +1248,7 @@ class JoinExec:
         [members], the observed score of the step ending at every member (NaN where none does).  The order and the cuts must
         not be chosen from the labels.  Errors raise GcreError."""
         S, off, members, sg = _set_lists(sets, signs)
-        ct = None
-        if cuts is not None:
-            if isinstance(sets, tuple) and len(sets) == 2 and isinstance(sets[0], np.ndarray):
-                ct = np.asarray(cuts).reshape(-1)
-                matching = len(ct) == len(members)
-            else:
-                matching = len(cuts) == S and all(len(x) == L for x, L in zip(cuts, np.diff(off)))
-                ct = np.concatenate([np.asarray(x).reshape(-1) for x in cuts]) if matching and S else np.zeros(0)
-            if not matching:
-                raise ValueError("cuts: one flag per member of every set")
-            ct = np.ascontiguousarray(ct != 0, dtype=np.uint8)
+        ct = _prefix_cuts(sets, cuts, S, off, members)
         lib = _prefix_lib()
         inp, keep = _set_input((off, members), rows, sg, self.num_cases + self.num_ctrls)
         out = np.zeros(max(S, 1), dtype=SET_SCORE)
@@ -1363,15 +1369,13 @@ class JoinExec:
         inp, keep = _set_input(sets, rows, signs, self.num_cases + self.num_ctrls)
         S = inp.n_sets
         lib = _feature_lib("sequential")
-        st = None if strata is None else np.ascontiguousarray(strata, dtype=np.int32).reshape(-1)
-        if st is not None and len(st) != self.num_cases + self.num_ctrls:
-            raise ValueError(f"strata: one id per patient ({self.num_cases + self.num_ctrls}), not {len(st)}")
+        _, st, n_strata = self._sequential_draw(strata, None)
         out = np.zeros(max(S, 1), dtype=SET_SCORE)
         seq = np.zeros(max(S, 1), dtype=SEQ_SCORE)
         n_out = ctypes.c_int64(0)
-        self._check_gcre(lib.gcre_score_sets_sequential(self._h, ctypes.byref(inp), int(seed) & (2**64 - 1), _ptr(st),
-                                                        0 if st is None else int(st.max()) + 1, int(hits), int(max_perms), _ptr(out),
-                                                        len(out), ctypes.byref(n_out), _ptr(seq)))
+        self._check_gcre(lib.gcre_score_sets_sequential(self._h, ctypes.byref(inp), int(seed) & (2**64 - 1), _ptr(st), n_strata,
+                                                        int(hits), int(max_perms), _ptr(out), len(out), ctypes.byref(n_out),
+                                                        _ptr(seq)))
         return out[:n_out.value], seq[:n_out.value]
 
     def weighted_sequential_tests(self, sets, rows, signs=None, odds=None, hits: int = 20, max_perms: int = 10**6, seed: int = 0,
@@ -1430,17 +1434,7 @@ class JoinExec:
         ``report.adaptive_sequential_reference`` states the rule in numpy.  A misshapen ``cuts`` / ``odds`` / ``strata`` is a
         ValueError; other errors raise GcreError."""
         S, off, members, sg = _set_lists(sets, signs)
-        ct = None
-        if cuts is not None:
-            if isinstance(sets, tuple) and len(sets) == 2 and isinstance(sets[0], np.ndarray):
-                ct = np.asarray(cuts).reshape(-1)
-                matching = len(ct) == len(members)
-            else:
-                matching = len(cuts) == S and all(len(x) == L for x, L in zip(cuts, np.diff(off)))
-                ct = np.concatenate([np.asarray(x).reshape(-1) for x in cuts]) if matching and S else np.zeros(0)
-            if not matching:
-                raise ValueError("cuts: one flag per member of every set")
-            ct = np.ascontiguousarray(ct != 0, dtype=np.uint8)
+        ct = _prefix_cuts(sets, cuts, S, off, members)
         w, st, n_strata = self._sequential_draw(strata, odds)
         lib = _feature_lib("seq_prefix")
         inp, keep = _set_input((off, members), rows, sg, self.num_cases + self.num_ctrls)

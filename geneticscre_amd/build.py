@@ -8,8 +8,8 @@ from concurrent.futures import ThreadPoolExecutor
 PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "libgcre_hip.so")
-SOURCES = ["gcre_kernels.hip", "gcre_sparse.hip", "gcre_ie.hip", "gcre_inspect.hip", "gcre_ie2.hip", "gcre_ieq.hip", "gcre_frontend.hip", "gcre_decorated.hip", "gcre_sets.hip", "gcre_given.hip", "gcre_family.hip", "gcre_minp.hip", "gcre_compete.hip", "gcre_prefix.hip", "gcre_dose.hip", "gcre_subsample.hip", "gcre_sequential.hip", "gcre_strata.hip", "gcre_weighted.hip", "gcre_seq_weighted.hip", "gcre_seq_prefix.hip", "gcre_overlap.hip", "gcre_clump.hip", "gcre_patients.hip", "gcre_burden.hip", "gcre_genes.hip", "gcre_exceed.hip", "gcre_stepdown.hip", "gcre_hits.hip", "gcre_host.hip", "gcre_host_stats.hip", "gcre_host_sets.hip", "gcre_host_family.hip", "gcre_host_minp.hip", "gcre_host_compete.hip", "gcre_host_prefix.hip", "gcre_host_subsample.hip", "gcre_host_dose.hip", "gcre_host_sequential.hip", "gcre_host_seq_prefix.hip", "gcre_host_strata.hip", "gcre_host_weighted.hip", "gcre_host_pipeline.hip"]
-HEADERS = ["gcre_kernels.h", "gcre_count_tile.h", "gcre_bitslice.h", "gcre_ie_common.h", "gcre_host.h", "gcre_set_stage.h", "gcre_threshold.h", "gcre_setlists.h", "gcre_family.h", "gcre_minp.h", "gcre_compete.h", "gcre_prefix.h", "gcre_dose.h", "gcre_subsample.h", "gcre_sequential.h", "gcre_strata.h", "gcre_weighted.h", "gcre_seq_weighted.h", "gcre_seq_loop.h", "gcre_seq_prefix.h", "gcre_clumporder.h", "gcre_pipeline.h", os.path.join("..", "..", "include", "gcre_hip.h")]
+SOURCES = ["gcre_kernels.hip", "gcre_sparse.hip", "gcre_ie.hip", "gcre_inspect.hip", "gcre_ie2.hip", "gcre_ieq.hip", "gcre_frontend.hip", "gcre_decorated.hip", "gcre_sets.hip", "gcre_given.hip", "gcre_family.hip", "gcre_minp.hip", "gcre_compete.hip", "gcre_prefix.hip", "gcre_dose.hip", "gcre_subsample.hip", "gcre_sequential.hip", "gcre_strata.hip", "gcre_weighted.hip", "gcre_seq_weighted.hip", "gcre_seq_prefix.hip", "gcre_overlap.hip", "gcre_clump.hip", "gcre_patients.hip", "gcre_burden.hip", "gcre_genes.hip", "gcre_exceed.hip", "gcre_stepdown.hip", "gcre_hits.hip", "gcre_host.hip", "gcre_host_stats.hip", "gcre_host_sets.hip", "gcre_host_family.hip", "gcre_host_minp.hip", "gcre_host_compete.hip", "gcre_host_steps.hip", "gcre_host_subsample.hip", "gcre_host_sequential.hip", "gcre_host_seq_prefix.hip", "gcre_host_strata.hip", "gcre_host_weighted.hip", "gcre_host_pipeline.hip"]
+HEADERS = ["gcre_kernels.h", "gcre_count_tile.h", "gcre_bitslice.h", "gcre_ie_common.h", "gcre_host.h", "gcre_set_stage.h", "gcre_threshold.h", "gcre_env.h", "gcre_setlists.h", "gcre_family.h", "gcre_minp.h", "gcre_compete.h", "gcre_prefix.h", "gcre_dose.h", "gcre_subsample.h", "gcre_sequential.h", "gcre_strata.h", "gcre_weighted.h", "gcre_seq_weighted.h", "gcre_seq_loop.h", "gcre_seq_prefix.h", "gcre_steps.h", "gcre_step_rows.h", "gcre_clumporder.h", "gcre_pipeline.h", os.path.join("..", "..", "include", "gcre_hip.h")]
 BASE_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-result"]
 # Defines that switch parts of a kernel off for timing experiments ("results are wrong") must never reach the shipped
 # library: build() refuses them unless GCRE_ALLOW_DIAG_BUILD=1, and the library reports what it was built with

@@ -52,11 +52,7 @@ inline int check_clump_order(const gcre_set_input* in, const int64_t* order, int
 }
 
 // GCRE_CLUMP_MAX_MB: the bound on the union rows the device holds, read per call (tests set fractions); default 32768
-inline double clump_max_mb() {
-  double mb = 32768;
-  if (const char* e = std::getenv("GCRE_CLUMP_MAX_MB")) mb = std::min(std::max(std::atof(e), 0.0), 65536.0);
-  return mb;
-}
+inline double clump_max_mb() { return gcre_env::env_mb("GCRE_CLUMP_MAX_MB", 32768, 65536.0); }
 
 // n_order union rows of row_bytes each against the bound
 inline int check_clump_bytes(int64_t n_order, int64_t row_bytes, double max_mb, std::string& msg) {

@@ -4,6 +4,7 @@
 // __host__ __device__, and tests/native/compete_main.cpp under plain g++.  report.competitive_picks restates it in Python.
 #pragma once
 #include "../../include/gcre_hip.h"
+#include "gcre_env.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -113,11 +114,7 @@ inline int compete_attempts() {
   if (const char* e = std::getenv("GCRE_COMPETE_ATTEMPTS")) a = std::min(std::max(std::atoi(e), 1), kCompeteAttempts);
   return a;
 }
-inline double compete_max_mb() {
-  double mb = 1024;
-  if (const char* e = std::getenv("GCRE_COMPETE_MAX_MB")) mb = std::min(std::max(std::atof(e), 0.0), 1048576.0);
-  return mb;
-}
+inline double compete_max_mb() { return gcre_env::env_mb("GCRE_COMPETE_MAX_MB", 1024, 1048576.0); }
 
 // What gcre_score_sets_compete refuses of its own arguments, after the checks of the set list (gcre_setlists.h) passed.
 // The bytes one draw adds to the optional outputs -- 8 per set of null_scores, 4 per listed member of picks -- must fit

@@ -1,7 +1,7 @@
 // gcre_dose.h -- the host plan of the multi-hit set tests (gcre_score_sets_dose): what the entry refuses of
 // its own arguments.  The slabs of whole sets and the block table are gcre_prefix.h's own (prefix_slabs, prefix_blocks), with
-// n_levels rows for every valid set.  Plain C++17 over include/gcre_hip.h, no HIP: the host stage (gcre_host_dose.hip)
-// includes it under hipcc and tests/native/dose_main.cpp under plain g++.
+// n_levels rows for every valid set.  Plain C++17 over include/gcre_hip.h, no HIP: the host stage (gcre_host_steps.hip, through
+// gcre_steps.h) includes it under hipcc and tests/native/dose_main.cpp under plain g++.
 #pragma once
 #include "gcre_prefix.h"
 

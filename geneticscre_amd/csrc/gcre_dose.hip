@@ -4,7 +4,7 @@
 //                  "count >= m", written in k_set_null's row layout, and the counts SetUnion::build (gcre_setlists.h) gives
 //                  such a row
 // The level rows are scored by k_set_observed (gcre_sets.hip) and walked by k_prefix_pick and k_prefix_null
-// (gcre_prefix.hip), which do not care how the rows of a slot were made.  The context-side entry is in gcre_host_dose.hip,
+// (gcre_prefix.hip), which do not care how the rows of a slot were made.  The context-side entry is in gcre_host_steps.hip,
 // the argument checks in gcre_dose.h.
 //
 // k_dose_rows is k_prefix_rows' mapping: one wave per (slot, 64-dword stretch of the row), one lane per dword, 32 patients

@@ -4,6 +4,7 @@
 // it under hipcc and tests/native/family_main.cpp under plain g++.
 #pragma once
 #include "../../include/gcre_hip.h"
+#include "gcre_env.h"
 #include "gcre_threshold.h"
 
 #include <algorithm>
@@ -17,15 +18,8 @@ using gcre_host::f32_threshold;
 
 // GCRE_FAMILY_MAX_MB: the bound on the null matrix a slab holds on the device, read per call (tests set fractions); default
 // 1024.  GCRE_FAMILY_SLAB_PERMS (tests) bounds the permutations of a slab further; 0 = no bound.
-inline double family_max_mb() {
-  double mb = 1024;
-  if (const char* e = std::getenv("GCRE_FAMILY_MAX_MB")) mb = std::min(std::max(std::atof(e), 0.0), 1048576.0);
-  return mb;
-}
-inline int64_t family_slab_perms() {
-  if (const char* e = std::getenv("GCRE_FAMILY_SLAB_PERMS")) return std::max<int64_t>(std::atoll(e), 1);
-  return 0;
-}
+inline double family_max_mb() { return gcre_env::env_mb("GCRE_FAMILY_MAX_MB", 1024, 1048576.0); }
+inline int64_t family_slab_perms() { return gcre_env::env_count("GCRE_FAMILY_SLAB_PERMS"); }
 
 // The slab: whole tiles of `tile` permutations whose null matrix, one row per valid set, stays under `max_mb`, and under
 // `slab_perms` permutations (0: no such bound; one tile at the least).  One row of one tile above the limit is refused.

@@ -1,7 +1,7 @@
 // gcre_host.h -- private to the host side of libgcre_hip.so: the state behind the handles of include/gcre_hip.h and the
 // few helpers that its translation units share.  gcre_host.hip holds the join driver and everything that feeds it,
 // gcre_host_sets.hip the set scores and their driver (gcre_set_stage.h), with one file per stage behind them
-// (gcre_host_family.hip, _minp, _compete, _prefix, _subsample, _dose, _sequential, _strata), gcre_host_stats.hip the other entry points that only use a
+// (gcre_host_family.hip, _minp, _compete, _steps, _subsample, _sequential, _strata), gcre_host_stats.hip the other entry points that only use a
 // context (decorated p-values, overlaps, clumps, tallies, burden tests, the gene tally, the exceedance counts and the hit lists
 // as objects), gcre_host_pipeline.hip the one-call pipeline on one device and on several (and with it everything of RCCL).
 // Nothing here is part of the ABI.

@@ -4,6 +4,7 @@
 // under plain g++.
 #pragma once
 #include "../../include/gcre_hip.h"
+#include "gcre_env.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -14,15 +15,8 @@ namespace gcre_minp __attribute__((visibility("hidden"))) {
 
 // GCRE_MINP_MAX_MB: the bound on the null scores and counts a slab holds on the device, read per call (tests set fractions);
 // default 1024.  GCRE_MINP_SLAB_SETS (tests) bounds the rows of a slab further; 0 = no bound.
-inline double minp_max_mb() {
-  double mb = 1024;
-  if (const char* e = std::getenv("GCRE_MINP_MAX_MB")) mb = std::min(std::max(std::atof(e), 0.0), 1048576.0);
-  return mb;
-}
-inline int64_t minp_slab_sets() {
-  if (const char* e = std::getenv("GCRE_MINP_SLAB_SETS")) return std::max<int64_t>(std::atoll(e), 1);
-  return 0;
-}
+inline double minp_max_mb() { return gcre_env::env_mb("GCRE_MINP_MAX_MB", 1024, 1048576.0); }
+inline int64_t minp_slab_sets() { return gcre_env::env_count("GCRE_MINP_SLAB_SETS"); }
 
 // The slab: whole rows -- every tile of `tile` permutations of a valid set, its null scores and its counts, 8 bytes per
 // column -- under `max_mb`, and at most `slab_sets` rows (0: no such bound).  One row above the limit is refused.  Without a

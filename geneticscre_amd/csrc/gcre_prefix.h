@@ -1,10 +1,11 @@
 // gcre_prefix.h -- the host plan of the variable-threshold set tests (gcre_score_sets_prefix), defined once:
 // the expansion of the cut flags into steps, what the entry refuses of its own arguments, the slabs of whole sets, the
 // size-sorted order of a slab's sets and the block table k_prefix_null reads.  Plain C++17 over include/gcre_hip.h, no HIP:
-// the host stage (gcre_host_prefix.hip) includes it under hipcc and tests/native/prefix_main.cpp under plain g++.
+// the host stage (gcre_host_steps.hip, through gcre_steps.h) includes it under hipcc and tests/native/prefix_main.cpp under plain g++.
 // tests/test_prefix_host.py restates it in Python.
 #pragma once
 #include "../../include/gcre_hip.h"
+#include "gcre_env.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -40,15 +41,8 @@ inline void prefix_steps(const gcre_set_input* in, const uint8_t* cut, PrefixSte
 
 // GCRE_PREFIX_MAX_MB: the bound on the step rows (and the null_max rows, when asked) a slab holds on the device, read per call
 // (tests set fractions); default 1024.  GCRE_PREFIX_SLAB_SETS (tests) bounds the sets of a slab further; 0 = no bound.
-inline double prefix_max_mb() {
-  double mb = 1024;
-  if (const char* e = std::getenv("GCRE_PREFIX_MAX_MB")) mb = std::min(std::max(std::atof(e), 0.0), 1048576.0);
-  return mb;
-}
-inline int64_t prefix_slab_sets() {
-  if (const char* e = std::getenv("GCRE_PREFIX_SLAB_SETS")) return std::max<int64_t>(std::atoll(e), 1);
-  return 0;
-}
+inline double prefix_max_mb() { return gcre_env::env_mb("GCRE_PREFIX_MAX_MB", 1024, 1048576.0); }
+inline int64_t prefix_slab_sets() { return gcre_env::env_count("GCRE_PREFIX_SLAB_SETS"); }
 
 // the working rows of one set on the device: its step rows [steps][M][W32p] dwords, and with null_max one row of Kpad floats
 inline double prefix_set_bytes(int64_t steps, int method, int32_t W32p, int32_t Kpad, bool want_null) {

@@ -8,7 +8,7 @@
 //                    the count of permutations whose maximum reaches the set's best observed score, and the
 //                    per-permutation maximum over the sets of the launch
 // The step rows are scored by k_set_observed (gcre_sets.hip) between the first two.  The context-side entry is in
-// gcre_host_prefix.hip, the host plan (steps, slabs, block table) in gcre_prefix.h.
+// gcre_host_steps.hip, the host plan (steps, slabs, block table) in gcre_prefix.h.
 //
 // k_prefix_rows is k_set_residual's mapping (gcre_given.hip), lanes over the dwords of a row, with one wave per set and
 // 64-dword stretch of the row: a wave's walk over the members is a chain of dependent loads, so the stretches of a row go to

@@ -3,7 +3,7 @@
 // of their own arguments, the first active list of a slab, what the slabs of a call add up to and how many kernels it
 // launches.  The steps and the slabs of whole sets are gcre_prefix.h's, the levels gcre_dose.h's, the stopping rule and the
 // batch schedule gcre_sequential.h's.  Plain C++17 over include/gcre_hip.h, no HIP: the host stage
-// (gcre_host_seq_prefix.hip) includes it under hipcc and tests/native/seq_prefix_main.cpp under plain g++.
+// (gcre_host_seq_prefix.hip, through gcre_steps.h) includes it under hipcc and tests/native/seq_prefix_main.cpp under plain g++.
 // tests/test_seq_prefix_host.py restates it in Python.
 //
 // Slabs.  The sequential loop runs once per slab of gcre_prefix.h, from permutation 0, and draws the masks again: they are a

@@ -6,6 +6,7 @@
 // report.permutation_masks and report.sequential_reference restate it in Python.
 #pragma once
 #include "../../include/gcre_hip.h"
+#include "gcre_env.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -131,11 +132,7 @@ inline int64_t sequential_find(const uint64_t* bits, int64_t n_bits, int64_t pri
 
 // GCRE_SEQ_MAX_MB (the masks and the bit rows of one batch on the device; tests set fractions) and GCRE_SEQ_BATCH_PERMS
 // (tests; 0 = unset): read per call
-inline double seq_max_mb() {
-  double mb = 1024;
-  if (const char* e = std::getenv("GCRE_SEQ_MAX_MB")) mb = std::min(std::max(std::atof(e), 0.0), 1048576.0);
-  return mb;
-}
+inline double seq_max_mb() { return gcre_env::env_mb("GCRE_SEQ_MAX_MB", 1024, 1048576.0); }
 inline int64_t seq_batch_perms_env() {
   const char* e = std::getenv("GCRE_SEQ_BATCH_PERMS");
   return e ? std::max<int64_t>(std::atoll(e), 0) : 0;

@@ -1,7 +1,7 @@
 // gcre_set_stage.h -- what the host files of the set scores share (hipcc only): gcre_host_sets.hip defines the checks, the
 // device stage of gcre_score_sets and its driver, score_sets_common; every entry that adds a statistic of its own to the
-// records (gcre_host_family.hip, _minp, _compete, _prefix, _subsample, _dose, _sequential, _strata) hands the driver one SetStage.  Nothing here is part
-// of the ABI.
+// records (gcre_host_family.hip, _minp, _compete, _steps, _subsample, _sequential, _seq_prefix, _strata) hands the driver one SetStage.
+// Nothing here is part of the ABI.
 #pragma once
 #include "gcre_host.h"
 #include "gcre_setlists.h"

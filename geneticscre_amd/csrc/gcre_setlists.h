@@ -5,6 +5,7 @@
 // burden_main.cpp: the argument checks of gcre_score_sets_given, gcre_set_patient_counts and gcre_patient_burden).
 #pragma once
 #include "../../include/gcre_hip.h"
+#include "gcre_env.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -89,11 +90,7 @@ inline int check_given_index(const gcre_set_input* in, const int64_t* which, con
 
 // GCRE_PATIENT_MAX_MB: the bound on the count cells (and on the member table) gcre_set_patient_counts holds on the device,
 // read per call (tests set fractions); default 1024
-inline double patient_max_mb() {
-  double mb = 1024;
-  if (const char* e = std::getenv("GCRE_PATIENT_MAX_MB")) mb = std::min(std::max(std::atof(e), 0.0), 65536.0);
-  return mb;
-}
+inline double patient_max_mb() { return gcre_env::env_mb("GCRE_PATIENT_MAX_MB", 1024, 65536.0); }
 
 // What gcre_set_patient_counts refuses of its own arguments, after the two checks above passed: `which` [n_which] names the
 // sets to count (NULL: 0 .. n_sets - 1, and then n_which must be n_sets), `group` [n_which] the group of every entry (-1:
@@ -137,11 +134,7 @@ inline int check_patient_index(const gcre_set_input* in, const int64_t* which, i
 
 // GCRE_BURDEN_MAX_MB: the bound on the bit planes and the sums gcre_patient_burden holds on the device at one time, read
 // per call (tests set fractions); default 1024
-inline double burden_max_mb() {
-  double mb = 1024;
-  if (const char* e = std::getenv("GCRE_BURDEN_MAX_MB")) mb = std::min(std::max(std::atof(e), 0.0), 65536.0);
-  return mb;
-}
+inline double burden_max_mb() { return gcre_env::env_mb("GCRE_BURDEN_MAX_MB", 1024, 65536.0); }
 
 // the bit length of a non-negative weight: the planes a row whose largest weight it is needs
 inline int32_t burden_bit_length(int32_t v) {

@@ -4,6 +4,7 @@
 // stage (gcre_host_strata.hip) includes it under hipcc and tests/native/strata_main.cpp under plain g++.
 #pragma once
 #include "../../include/gcre_hip.h"
+#include "gcre_env.h"
 #include "gcre_sequential.h"   // strata_counts: the strata as gcre_generate_perm_masks reads them
 
 #include <algorithm>
@@ -19,15 +20,8 @@ static_assert(kStrataMax == 16, "the limit the header promises, and the four wav
 
 // GCRE_STRATA_MAX_MB: the bound on the stratum rows (and the null_scores rows, when asked) a slab holds on the device, read
 // per call (tests set fractions); default 1024.  GCRE_STRATA_SLAB_SETS (tests) bounds the sets of a slab further; 0 = no bound.
-inline double strata_max_mb() {
-  double mb = 1024;
-  if (const char* e = std::getenv("GCRE_STRATA_MAX_MB")) mb = std::min(std::max(std::atof(e), 0.0), 1048576.0);
-  return mb;
-}
-inline int64_t strata_slab_sets_env() {
-  if (const char* e = std::getenv("GCRE_STRATA_SLAB_SETS")) return std::max<int64_t>(std::atoll(e), 1);
-  return 0;
-}
+inline double strata_max_mb() { return gcre_env::env_mb("GCRE_STRATA_MAX_MB", 1024, 1048576.0); }
+inline int64_t strata_slab_sets_env() { return gcre_env::env_count("GCRE_STRATA_SLAB_SETS"); }
 
 // What the entry is told beside the set list; pointers only as "given or not" where they are not read here
 struct StrataAsk {

@@ -5,6 +5,7 @@
 // restates it in Python.
 #pragma once
 #include "../../include/gcre_hip.h"
+#include "gcre_env.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -71,11 +72,7 @@ inline void subsample_draw(uint64_t seed, int64_t b, int32_t n_cases, int32_t n_
 
 // GCRE_SUBSAMPLE_MAX_MB (the masks and the optional outputs a slab of draws holds on the device; tests set fractions) and
 // GCRE_SUBSAMPLE_SLAB_DRAWS (tests): read per call
-inline double subsample_max_mb() {
-  double mb = 1024;
-  if (const char* e = std::getenv("GCRE_SUBSAMPLE_MAX_MB")) mb = std::min(std::max(std::atof(e), 0.0), 1048576.0);
-  return mb;
-}
+inline double subsample_max_mb() { return gcre_env::env_mb("GCRE_SUBSAMPLE_MAX_MB", 1024, 1048576.0); }
 
 // What the entry is told beside the set list; pointers only as "given or not"
 struct SubsampleAsk {

@@ -336,11 +336,21 @@ def test_interface_is_declared():
         "score", "n_ge", "best_index", "best_level", "levels", "cases_pos", "ctrls_pos", "cases_neg", "ctrls_neg", "pad")
     assert [api.DOSE_SCORE.fields[k][1] for k in api.DOSE_SCORE.names] == [0, 8, 16, 20, 24, 28, 32, 36, 40, 44]
     from geneticscre_amd import build
-    assert {"gcre_dose.hip", "gcre_host_dose.hip"} <= set(build.SOURCES) and "gcre_dose.h" in build.HEADERS
+    assert {"gcre_dose.hip", "gcre_host_steps.hip"} <= set(build.SOURCES) and "gcre_dose.h" in build.HEADERS
     kernels = open(os.path.join(ROOT, "geneticscre_amd", "csrc", "gcre_kernels.h")).read()
     assert "struct DoseArgs" in kernels and "launch_dose_rows(" in kernels
-    host = open(os.path.join(ROOT, "geneticscre_amd", "csrc", "gcre_host_dose.hip")).read()
-    assert "static_assert(sizeof(gcre_dose_score) == 48" in host and "c->dose_launches++" in host and "prefix_launches" not in host
+    # one host file for this entry and gcre_score_sets_prefix: each hands the stage its own counter and nobody else's, and the
+    # stage counts through what it was handed alone
+    host = open(os.path.join(ROOT, "geneticscre_amd", "csrc", "gcre_host_steps.hip")).read()
+    assert "static_assert(sizeof(gcre_dose_score) == 48" in host
+    entry = {m.group(1): m.group(2) for m in re.finditer(r"\nint (gcre_score_sets_\w+)\(.*?\) \{\n(.*?)\n\}\n", host, flags=re.S)}
+    assert set(entry) == {"gcre_score_sets_prefix", "gcre_score_sets_dose"}
+    assert "&gcre_ctx::dose_launches" in entry["gcre_score_sets_dose"] and "prefix_launches" not in entry["gcre_score_sets_dose"]
+    assert "&gcre_ctx::prefix_launches" in entry["gcre_score_sets_prefix"] and "dose_launches" not in entry["gcre_score_sets_prefix"]
+    stage = host[:host.index('extern "C"')]
+    assert "int64_t& launches = c->*counter;" in stage and "_launches" not in stage
+    rows = open(os.path.join(ROOT, "geneticscre_amd", "csrc", "gcre_step_rows.h")).read()
+    assert "if (d.ok()) counter++;" in rows and "_launches" not in rows
     lib = api._dose_lib()                                    # loads without a GPU
     assert lib.gcre_abi_version() == 4 and lib.gcre_dose_launches(None) == -1
     design = open(os.path.join(ROOT, "DESIGN.md")).read()

@@ -2,7 +2,9 @@
 on hand-worked matrices; the host plan of csrc/gcre_seq_prefix.h -- argument checks, the slab walk, the first active list of
 every slab, the sum of the sets still active at a left-over permutation, the launches -- driven by
 tests/native/seq_prefix_main.cpp under the address and undefined-behaviour sanitizers and compared with a restatement in
-Python; and what ``JoinExec.prefix_sequential_tests`` / ``dose_sequential_tests`` refuse before they reach the library.  No GPU."""
+Python; the row variants of csrc/gcre_steps.h and the budget readers of csrc/gcre_env.h, driven by tests/native/steps_main.cpp
+under the same sanitizers against values written down by hand; and what ``JoinExec.prefix_sequential_tests`` /
+``dose_sequential_tests`` refuse before they reach the library.  No GPU."""
 from __future__ import annotations
 
 import os
@@ -254,6 +256,73 @@ def test_native_refusals(prog, tmp_path):
     # the levels
     assert run_case(prog, tmp_path, base + [("levels", [2, 2])]) == [f"check {ERR_ARG} {WHO_D}the levels are not strictly ascending (2 after 2)"]
     assert run_case(prog, tmp_path, base + [("levels", [16])]) == [f"check {ERR_ARG} {WHO_D}level 16 (index 0) is outside 1 .. 15"]
+
+
+# ---- the two row variants the resident and the sequential stages share (csrc/gcre_steps.h), the budget readers (csrc/gcre_env.h) ----
+
+
+@pytest.fixture(scope="module")
+def steps_prog(tmp_path_factory):
+    out = str(tmp_path_factory.mktemp("steps") / "steps_main")
+    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-fsanitize=address,undefined",
+                    "-fno-sanitize-recover=undefined", "-static-libasan", "-static-libubsan",
+                    os.path.join(ROOT, "tests", "native", "steps_main.cpp"), "-o", out], check=True)
+    return out
+
+
+def run_steps(steps_prog, what, env=None):
+    keep = {k: v for k, v in os.environ.items() if k not in ("GCRE_TEST_MB", "GCRE_TEST_COUNT")}
+    r = subprocess.run([steps_prog, what], capture_output=True, text=True, timeout=300, env={**keep, **(env or {})})
+    assert r.returncode == 0, f"exit {r.returncode}\n{r.stdout}\n{r.stderr}"
+    return r.stdout.splitlines()
+
+
+def test_native_records_of_both_variants_by_hand(steps_prog):
+    """Sets [3, NA, 5], [1, 2, 9] and [4, 6, 7, 8] with cuts 1 1 1 | 0 0 0 | 0 1 0 1: three, one and two steps.  Set 1's pick is NaN,
+    set 2's is step 1 (members 4, level 3).  Every record starts as 0x5a bytes and every score as 7."""
+    nan10 = " ".join(["nan"] * 10)
+    assert run_steps(steps_prog, "records") == [
+        f"check {ERR_ARG} who: too many sets or members",                 # in front of the steps, resident and sequential
+        f"check_seq {ERR_ARG} who: too many sets or members",
+        "check 0 ",
+        # score n_ge best_step best_members steps, four counts
+        "px nan -1 -1 0 3 0 0 0 0",                                       # the defaults: -1 for the NA set, the steps of every set
+        "px nan 0 -1 0 1 0 0 0 0",
+        "px nan 0 -1 0 2 0 0 0 0",
+        f"step_scores {nan10}",
+        "px nan -1 -1 0 3 0 0 0 0",                                       # never written
+        "px nan 0 -1 0 1 0 0 0 0",                                        # a NaN pick: no step, no members, zeros; n_ge stands
+        "px 2.5 0 1 4 2 5 6 7 8",                                         # step 1 ends at the set's fourth member
+        "step_scores nan nan nan nan nan nan nan 1.5 nan 2.5",            # at the members that end a step
+        "vsteps 1 2",
+        "row0 0 1 3",                                                     # the running sum over the slab's sets
+        "row0 0 2",
+        "check_seq 0 ",
+        "bare 1 2 4",                                                     # without cuts every member ends a step
+        # score n_ge best_index best_level levels, four counts, pad
+        "ds nan -1 -1 0 2 0 0 0 0 0",
+        "ds nan 0 -1 0 2 0 0 0 0 0",
+        "ds nan 0 -1 0 2 0 0 0 0 0",
+        "level_scores nan nan nan nan nan nan",
+        "ds nan -1 -1 0 2 0 0 0 0 0",
+        "ds nan 0 -1 0 2 0 0 0 0 0",
+        "ds 4 0 1 3 2 1 2 3 4 0",                                         # index 1 of the levels 1, 3
+        "level_scores nan nan nan nan 3 4",                               # [set][level]
+        "vsteps 2 2",
+        "row0 0 2 4",
+        "row0 0 2",
+    ]
+
+
+ENV_CASES = [(None, None, "1024", "0"), ("-3", "-5", "0", "1"), ("1e9", "7", "65536", "7"), ("0.25", "7.9", "0.25", "7"),
+             ("65536.5", "0", "65536", "1"), ("abc", "", "0", "1"), ("12", str(2**40), "12", str(2**40))]
+
+
+@pytest.mark.parametrize("mb,count,want_mb,want_count", ENV_CASES, ids=[f"{c[0]}-{c[1]}" for c in ENV_CASES])
+def test_native_budget_readers_clamp(steps_prog, mb, count, want_mb, want_count):
+    """Unset: the default and 0 = no bound; else the MB clamped to [0, cap], fractions kept, and the count at least 1."""
+    env = {k: v for k, v in (("GCRE_TEST_MB", mb), ("GCRE_TEST_COUNT", count)) if v is not None}
+    assert run_steps(steps_prog, "env", env) == [f"mb {want_mb}", f"count {want_count}"]
 
 
 # ---- what the binding refuses before it reaches the library ------------------------------------------------------------------------
